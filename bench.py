@@ -462,6 +462,7 @@ class Step:
         self.pre, self.gather_work = None, None
         self.graph, self.static_feats, self.mode = None, None, 'eager'
         self.want_graph = use_graph
+        self.acc = None           # the model output of the last step taken (captured: the graph's static output buffer)
 
     # ---- eager pieces ----
     def features(self):
@@ -481,6 +482,7 @@ class Step:
             allreduce_gradients_p2p(self.params, self.p2p[1])
         elif self.sh is not None:
             allreduce_gradients(self.params, self.group)
+        self.acc = acc.detach()       # (detached: the autograd graph of an eager step is not kept alive)
         return acc
 
     def _deferred(self):
@@ -522,6 +524,7 @@ class Step:
                 self.bucket[:] = [flat, grads, torch.empty_like(flat), n]
         else:
             self.bucket[:] = [torch.cat([g.reshape(-1) for g in grads]), grads]
+        self.acc = acc.detach()       # (detached: the autograd graph of an eager step is not kept alive)
         return acc
 
     def exchange_forward(self):
@@ -785,6 +788,47 @@ def median(xs):
     return 0.0 if not xs else (xs[len(xs) // 2] if len(xs) % 2 else 0.5 * (xs[len(xs) // 2 - 1] + xs[len(xs) // 2]))
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(st, use_dist, world, n_real):
+    """What the last step `st` ran hands its caller, as host float32 arrays: the model output (acceleration, agents x 2), the
+    gradient of the scene state (position, velocity, acceleration: agents x 6) and every weight gradient.  Sharded: the agent
+    rows of all ranks in agent order (collective: every rank calls it), absent padding agents left out."""
+    acc = st.acc.detach().float()
+    # (sharded + captured: the exchange leaves this rank's rows in grad_own; an eager sharded step's autograd all-gather in .grad)
+    g_state = (st.grad_own if use_dist and st.graph is not None else st.state_own.grad).detach().float()
+    if use_dist and world > 1:
+        rows = []
+        for x in (acc, g_state):
+            full = torch.empty((world * x.shape[0],) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+            dist.all_gather_into_tensor(full, x.contiguous())
+            rows.append(full)
+        acc, g_state = rows
+    out = {'acceleration': acc[:n_real].cpu().numpy(), 'state_grad': g_state[:n_real].cpu().numpy()}
+    for name, p in st.model.named_parameters():
+        if p.grad is not None:
+            out['param_grad.' + name] = p.grad.detach().float().cpu().numpy()
+    return out
+
+
+def write_outputs(arrays, path, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """`arrays` as <path>/<name>.npy.  Over `max_bytes` in all, the per-agent arrays keep a fixed seeded sample of their rows
+    (the same rows for each; their indices in sampled_rows.npy)."""
+    os.makedirs(path, exist_ok=True)
+    per_agent = ('acceleration', 'state_grad')
+    total = sum(a.nbytes for a in arrays.values())
+    if total > max_bytes:
+        n = arrays['acceleration'].shape[0]
+        row_bytes = sum(arrays[k].nbytes // n for k in per_agent)
+        keep = max(1, (max_bytes - (total - sum(arrays[k].nbytes for k in per_agent))) // (row_bytes + 8))
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=min(n, keep), replace=False))
+        arrays = dict(arrays, sampled_rows=rows.astype(np.float64), **{k: arrays[k][rows] for k in per_agent})
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -842,6 +886,11 @@ def main():
                     help='1: load the pre-tuned GEMM selections for the MLP (tuned in-process if this stack rejects the file); '
                          '0: library defaults; 2: re-tune and write --tune-out; 3: force the in-process tuning')
     ap.add_argument('--tune-out', type=str, default='gpurun_out/tunableop_retuned.csv', help='result file of --tunableop 2')
+    ap.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                    help='after the timed steps write what the last one computed -- the model output, the state gradient and every '
+                         'weight gradient -- as DIR/<name>.npy (float32; at most 64 MB, a fixed seeded sample of the agent rows '
+                         'beyond that), for comparing two builds output for output.  With --train-mode 1 the dropout draws are '
+                         're-seeded in front of the timed steps, so that the last one\'s masks depend on --steps only')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -1039,6 +1088,11 @@ def main():
                 more = bool(t.item())
     for i in range(args.warmup):
         run_step(i, False)
+    if args.dump_outputs and args.train_mode:
+        # the spin-up's replay count depends on the clock: rewind the device's dropout draws (the state Step() set up) so that
+        # the masks of the last timed step are the same in every run with the same arguments
+        from piml_amd import ops
+        ops.dropout_seed(666, dev)
     st.barrier()
     _phase('warmup done')
     t0 = time.perf_counter()
@@ -1055,6 +1109,11 @@ def main():
         print('[bench] FATAL: the P2P exchange timed out during the run (sticky status word set on some rank): the timed replays '
               'skipped it.  Raise PIML_P2P_SPIN_LIMIT if the ranks start far apart, or use --exchange bucket.', file=sys.stderr, flush=True)
         sys.exit(5)
+    if args.dump_outputs:           # before anything else runs the step again (relfeat samples, the eager verification)
+        arrays = step_outputs(st, use_dist, world, N_real)
+        if rank == 0:
+            names = write_outputs(arrays, args.dump_outputs)
+            _phase(f'outputs of the last timed step written to {args.dump_outputs}: {len(names)} arrays')
     if graph is not None:           # the relfeat samples, behind the region (see above); two unsampled replays lead the burst
         for i in range(-2, n_samples):
             run_step(i, 'sample')

@@ -273,7 +273,7 @@ PIML_API int piml_p2p_exchange(const piml_p2p_msg* msg, int rank, int world, flo
     A.rank = rank; A.world = world; A.sum = msg->sum ? 1 : 0;
     // workgroups per receiver: ~2 float4 per thread (loads of the fine-grained receive buffers are uncached round trips: many
     // threads with few loads each), all of them resident at once (the waits spin): world * split <= 512
-    // PIML_P2P_MAX_SPLIT: a lower cap -- several ranks SHARING one GPU (tests/test_p2p_gpu.py: 8 processes on one device) need all
+    // PIML_P2P_MAX_SPLIT: a lower cap -- several ranks SHARING one GPU (tests/test_p2p_gpu.py: four processes on one device) need all
     // their launches resident together: world ranks x world x split workgroups <= 2048
     static const int max_split = getenv("PIML_P2P_MAX_SPLIT") && atoi(getenv("PIML_P2P_MAX_SPLIT")) > 0 ? atoi(getenv("PIML_P2P_MAX_SPLIT")) : 64;
     const int cap = max_split < 64 ? max_split : 64;

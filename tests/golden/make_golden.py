@@ -20,6 +20,8 @@ Fixture families:
                loss scalars, collision counts, gradients (rollout_more: UCY + pinnsf_res; rollout_flags: the
                non-default loss switches)
   metrics      functions.metrics (MAE, OT, MMD, collisions)
+  live_reference  get_relative_features on 120 random small scenes, the rollout losses and the pointwise data loader
+               (tests/test_oracle_live_reference.py)
 """
 import os
 import sys
@@ -871,7 +873,70 @@ def gen_mainflow_spread(case='ucy'):
         os.chdir(cwd)
 
 
-GENS = dict(mainflow_spread=gen_mainflow_spread, mainflow_pointwise=gen_mainflow_pointwise, mainflow=gen_mainflow, relfeat=gen_relfeat, collision=gen_collision, mlapm=gen_mlapm, calcacc=gen_calcacc, model=gen_model, rollout=gen_rollout, dataset=gen_dataset, metrics=gen_metrics, rollout_more=gen_rollout_more, rollout_flags=gen_rollout_flags, model_polar=gen_model_polar)
+def gen_live_reference():
+    """The cases of tests/test_oracle_live_reference.py: the reference's relfeat on 120 random small scenes (random k, sight
+    angles, thresholds), its rollout losses and its pointwise data loader, inputs and outputs both."""
+    import models.simulators as RSIM
+    import utils.data_loader as RLOAD
+    out = {}
+    ped = DATA.Pedestrians()
+    rng = np.random.default_rng(7)
+    n_cases = 120
+    for case in range(n_cases):
+        N = int(rng.integers(2, 60))
+        M = int(rng.choice([2, 5, 40, 150]))
+        Tn = int(rng.choice([1, 1, 1, 4]))
+        p = (rng.random((Tn, N, 2)) * 7).astype(np.float32)
+        v = rng.standard_normal((Tn, N, 2)).astype(np.float32)
+        v[rng.random((Tn, N)) < 0.2] = 0                      # exercises the temporal heading fill when T > 1
+        a = rng.standard_normal((Tn, N, 2)).astype(np.float32)
+        d = (rng.random((Tn, N, 2)) * 7).astype(np.float32)
+        absent = rng.random((Tn, N)) < 0.15
+        p[absent] = np.nan
+        d[absent] = np.nan
+        o = (rng.random((M, 2)) * 7).astype(np.float32)
+        kp, ko = int(rng.integers(1, 9)), int(rng.integers(1, 12))
+        ang_p, ang_o = float(rng.choice([30, 60, 90, 100, 150, 180])), float(rng.choice([45, 90, 135]))
+        dp, do = float(rng.choice([0.5, 1.5, 4, 50])), float(rng.choice([1.0, 4, 50]))
+        c = f'relfeat{case}/'
+        out.update({c + 'position': p, c + 'velocity': v, c + 'acceleration': a, c + 'destination': d, c + 'obstacles': o,
+                    c + 'params': np.array([kp, ang_p, dp, ko, ang_o, do], np.float64)})
+        t = [torch.tensor(x.copy()) for x in (p, v, a, d, o)]
+        pf, of, df = ped.get_relative_features(*t, kp, ang_p, dp, ko, ang_o, do)
+        out.update({c + 'ped_features': pf, c + 'obs_features': of, c + 'dest_features': df})
+    out['relfeat_cases'] = np.int64(n_cases)
+
+    ref = RSIM.BaseSimulator.__new__(RSIM.BaseSimulator)
+    g = torch.Generator().manual_seed(0)
+    pred, lab = torch.randn(3, 6, 11, 2, generator=g), torch.randn(3, 6, 11, 2, generator=g)
+    coll = (torch.rand(3, 6, 11, generator=g) > 0.8).float()
+    am = (torch.rand(11, generator=g) > 0.3).float()
+    emb = torch.randn(5, 7, generator=g)
+    out.update({'losses/pred': pred, 'losses/labels': lab, 'losses/collisions': coll, 'losses/abnormal_mask': am,
+                'losses/embedding': emb})
+    for decay in (1.0, 0.9):
+        for rev in (False, True):
+            out[f'losses/mse_d{decay}_r{int(rev)}'] = ref.multiple_rollout_mse_loss(pred, lab, decay, reduction='sum', reverse=rev)
+        out[f'losses/avoid_d{decay}'] = ref.multiple_rollout_collision_avoidance_loss(pred, lab, decay, reduction='none')
+        for tag, mask in (('none', None), ('mask', am)):
+            out[f'losses/coll_d{decay}_{tag}'] = ref.multiple_rollout_collision_loss(pred, lab, decay, 10, coll.clone(), reduction='sum',
+                                                                                     abnormal_mask=mask)
+    out['losses/l1'] = ref.l1_reg_loss(emb, 0.01, 'sum')
+
+    n = 23
+    feats = dict(ped_features=torch.arange(n * 2 * 6.).reshape(n, 2, 6), obs_features=torch.zeros(n, 3, 6),
+                 self_features=torch.arange(n * 7.).reshape(n, 7), labels=torch.arange(n * 12.).reshape(n, 12))
+    np.random.seed(5)
+    batches = RLOAD.data_loader(DATA.PointwisePedData(**feats), 4, seed=0)
+    out['loader/batches'] = np.int64(len(batches))
+    for i, batch in enumerate(batches):
+        out[f'loader/b{i}/fields'] = np.int64(len(batch))
+        for j, x in enumerate(batch):
+            out[f'loader/b{i}/{j}'] = x
+    save('live_reference', **out)
+
+
+GENS = dict(live_reference=gen_live_reference, mainflow_spread=gen_mainflow_spread, mainflow_pointwise=gen_mainflow_pointwise, mainflow=gen_mainflow, relfeat=gen_relfeat, collision=gen_collision, mlapm=gen_mlapm, calcacc=gen_calcacc, model=gen_model, rollout=gen_rollout, dataset=gen_dataset, metrics=gen_metrics, rollout_more=gen_rollout_more, rollout_flags=gen_rollout_flags, model_polar=gen_model_polar)
 
 if __name__ == '__main__':
     names = sys.argv[1:] or list(GENS)

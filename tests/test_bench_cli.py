@@ -1,6 +1,6 @@
 """CPU: the host logic of bench.py that does not need a GPU -- the self-launch of `--gpus G > 1` (a CHILD
-torch.distributed.run process, started before anything touches the GPU) and the committed profile digest that the
-JSON line's `roofline.kernels` is read from."""
+torch.distributed.run process, started before anything touches the GPU), the committed profile digest that the
+JSON line's `roofline.kernels` is read from and the writer behind `--dump-outputs`."""
 import json
 import os
 import sys
@@ -75,3 +75,44 @@ def test_packed_weights_is_a_noop_without_a_gpu():
             with net.packed_weights():          # re-entrant
                 b = net(*x)[0]
         assert torch.equal(a, b) and (net._packs is None or not net._packs.active)
+
+
+def test_dump_outputs_writes_what_the_step_computed(oracle, tmp_path):
+    """--dump-outputs: the model output, the state gradient and every weight gradient of the step as float32 .npy files (a CPU
+    step with the oracle behind the feature operators, as in tests/test_bench_step_dist.py); over the size cap a fixed seeded
+    sample of the agent rows."""
+    import numpy as np
+    import torch
+    from test_bench_step_dist import M, _ops_stub, _scene
+    bench = _bench()
+    scene = _scene()
+    N = scene['position'].shape[0]
+    st = bench.Step(scene, N, N, 0, M, torch.device('cpu'), None, False, False, False, ops_module=_ops_stub())
+    st.reset_grads()
+    acc = st.step_body()
+    arrays = bench.step_outputs(st, False, 1, N)
+    names = bench.write_outputs(arrays, str(tmp_path / 'all'))
+    params = dict(st.model.named_parameters())
+    assert names == sorted(['acceleration', 'state_grad'] + ['param_grad.' + k for k, p in params.items() if p.grad is not None])
+    assert len(names) > 2
+    got = {n: np.load(tmp_path / 'all' / (n + '.npy')) for n in names}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got['acceleration'].shape == (N, 2) and np.array_equal(got['acceleration'], acc.detach().numpy())
+    assert got['state_grad'].shape == (N, 6) and np.array_equal(got['state_grad'], st.state_own.grad.numpy())
+    for n in names:
+        if n.startswith('param_grad.'):
+            assert np.array_equal(got[n], params[n[len('param_grad.'):]].grad.numpy()), n
+    # a cap that holds the weight gradients and 10 agents' rows
+    total = sum(a.nbytes for a in arrays.values())
+    cap = total - (N - 10) * (2 + 6) * 4 - 1
+    names = bench.write_outputs(arrays, str(tmp_path / 'cap'), max_bytes=cap)
+    assert 'sampled_rows' in names
+    cut = {n: np.load(tmp_path / 'cap' / (n + '.npy')) for n in names}
+    rows = cut['sampled_rows']
+    assert rows.dtype == np.float64 and 0 < len(rows) <= 10 and np.all(np.diff(rows) > 0)
+    assert sum(a.nbytes for a in cut.values()) <= cap
+    rows = rows.astype(np.int64)
+    assert np.array_equal(cut['acceleration'], got['acceleration'][rows]) and np.array_equal(cut['state_grad'], got['state_grad'][rows])
+    assert all(np.array_equal(cut[n], got[n]) for n in got if n.startswith('param_grad.'))
+    bench.write_outputs(arrays, str(tmp_path / 'again'), max_bytes=cap)
+    assert np.array_equal(np.load(tmp_path / 'again' / 'sampled_rows.npy'), cut['sampled_rows'])

@@ -1,6 +1,8 @@
-"""CPU-only, world_size 2 / 4 / 8, gloo: agent-block sharding (piml_amd/sharded.py) -- the all-gather of
+"""CPU-only, world_size 2 / 3 / 4, gloo: agent-block sharding (piml_amd/sharded.py) -- the all-gather of
 state records, the reduce-scatter of their gradients and the bucketed all-reduce of the MLP
-gradients -- with the CPU oracle standing in for the HIP kernel (injected feature_fn)."""
+gradients -- with the CPU oracle standing in for the HIP kernel (injected feature_fn).  At most four rank processes:
+on a GPU machine every process that imports torch beside a pytest process holding the shared GPU counts against its
+limit of six."""
 import os
 import socket
 import types
@@ -160,9 +162,9 @@ def free_port():
         return s.getsockname()[1]
 
 
-@pytest.mark.parametrize('WORLD,n_real', [(2, 64), (4, 64), (8, 61)])
+@pytest.mark.parametrize('WORLD,n_real', [(2, 64), (4, 64), (3, 61)])
 def test_sharded_step_matches_single_process(oracle, WORLD, n_real):
-    """every rank's rows of the sharded step against the same scene in one process: world 2 / 4 / 8, and an agent count (61)
+    """every rank's rows of the sharded step against the same scene in one process: world 2 / 4 / 3, and an agent count (61)
     that no world size divides -- padded with absent agents, which nobody selects"""
     acc_ref, gstate_ref, gparams_ref = reference_single_process(n_real, WORLD)
     ctx = mp.get_context('spawn')
