@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PIML_HIP_ABI_VERSION 32
+#define PIML_HIP_ABI_VERSION 33
 #define PIML_MAX_TOPK 32 /* topk_ped / topk_obs upper bound (reference defaults 6 / 10) */
 
 /* ABI version of the loaded library (== PIML_HIP_ABI_VERSION). */
@@ -898,7 +898,9 @@ int piml_corrector_bwd(const piml_corrector* c, int accumulate, void* stream);
  * optimiser step that accumulate into the same buffers (PIML_ACCUMULATE: the frames of the rollout of
  * src/models/simulators.py:699-779): the unfold reads the folded layers' summed gradients and overwrites the unfolded ones, so
  * only the last pass's matters -- one launch per step instead of one per pass.  Another network's backward in between launches
- * what is waiting first.  Until the closing call dw1_out and the dW3 / db3 fields of the encoders' `grads` are NOT valid. */
+ * what is waiting first.  Until the closing call dw1_out and the dW3 / db3 fields of the encoders' `grads` are NOT valid.  Only
+ * backward passes that ask for it with PIML_DEFER_UNFOLD are deferred; every other one launches its unfold behind its sums as
+ * outside the deferral. */
 int piml_pinnsf_unfold_defer(int on, void* stream);
 #define PIML_PACKED_VALID 1
 #define PIML_FORK 2
@@ -952,6 +954,11 @@ int piml_pinnsf_unfold_defer(int on, void* stream);
                            src/models/model.py:82-119 (processor), :1279-1283 (the sum).  Served when
                            piml_pinnsf_pool_msgs_ok(enc, nbranches): k in {2, 6, 10}, whole agents, split products, relu_mask given,
                            more than piml_encoder_split_tiles_train() tiles; hipErrorInvalidValue otherwise */
+#define PIML_DEFER_UNFOLD 256 /* piml_pinnsf_bwd with PIML_POOL_TRAIN: this pass's unfold may wait for piml_pinnsf_unfold_defer(0, ...)
+                                 while a deferral is on.  The decision travels with the pass (its slot sums too, when PIML_DEFER_SLOT_SUMS
+                                 leaves them to a later launch): a pass without the flag launches its unfold behind its sums even while
+                                 the device defers -- for callers whose gradient buffers are read, or freed, before the deferral
+                                 ends (a pass whose buffers are not the ones the deferring step accumulates into) */
 int piml_pinnsf_pool_train_ok(const piml_encoder_branch* enc, int nbranches);
 int piml_pinnsf_pool_msgs_ok(const piml_encoder_branch* enc, int nbranches);
 int piml_pinnsf_pool_h2_ok(const piml_encoder_branch* enc, int nbranches);

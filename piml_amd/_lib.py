@@ -11,7 +11,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PIML_LIB=<path>: an experimental build of the same ABI beside the shipped library (piml_amd.build.variant; tools/ A/B timings)
 LIB_PATH = os.environ.get('PIML_LIB') or os.path.join(_HERE, 'libpiml_hip.so')
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 _lib = None
 
@@ -58,7 +58,7 @@ class Corrector(ctypes.Structure):
                 ('partials_a', _p), ('partials_b', _p), ('grads', _p)]
 
 
-PACKED_VALID, FORK, ACCUMULATE, DEFER_SLOT_SUMS, DEFER_PACK, POOL_H2, POOL_TRAIN, POOL_MSGS = 1, 2, 4, 8, 16, 32, 64, 128          # piml_pinnsf_* flags
+PACKED_VALID, FORK, ACCUMULATE, DEFER_SLOT_SUMS, DEFER_PACK, POOL_H2, POOL_TRAIN, POOL_MSGS, DEFER_UNFOLD = 1, 2, 4, 8, 16, 32, 64, 128, 256   # piml_pinnsf_* flags
 
 # name -> argtypes, in the order of include/piml_hip.h
 SIGNATURES = {

@@ -102,14 +102,17 @@ PIML_API int piml_adam_step(float* const* params, const float* const* grads, flo
                             float* const* steps, const long long* sizes, int n, double lr, double beta1, double beta2, double weight_decay,
                             double eps, unsigned* tickets, void* stream) {
     if (n < 0 || (n > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !steps || !sizes || !tickets))) return hipErrorInvalidValue;
+    // every tensor is checked before the first launch (a rejected table steps nothing).  An empty tensor's data pointers may be null
+    // (the caching allocator's empty tensors): the kernel never touches its elements, only its counter
+    for (int t = 0; t < n; ++t)
+        if (!steps[t] || sizes[t] < 0 || sizes[t] >= (1ll << 30) ||
+            (sizes[t] > 0 && (!params[t] || !grads[t] || !exp_avg[t] || !exp_avg_sq[t])))
+            return hipErrorInvalidValue;
     for (int t0 = 0; t0 < n; t0 += ADAM_MAX) {
         const int cnt = n - t0 < ADAM_MAX ? n - t0 : ADAM_MAX;
         AdamArgs A = {};
         int blocks = 0;
         for (int t = 0; t < cnt; ++t) {
-            if (!params[t0 + t] || !grads[t0 + t] || !exp_avg[t0 + t] || !exp_avg_sq[t0 + t] || !steps[t0 + t] || sizes[t0 + t] < 0 ||
-                sizes[t0 + t] >= (1ll << 30))
-                return hipErrorInvalidValue;
             A.param[t] = params[t0 + t]; A.grad[t] = grads[t0 + t]; A.exp_avg[t] = exp_avg[t0 + t]; A.exp_avg_sq[t] = exp_avg_sq[t0 + t];
             A.step[t] = steps[t0 + t]; A.n[t] = (int)sizes[t0 + t];
             A.first[t] = blocks;

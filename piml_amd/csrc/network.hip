@@ -155,7 +155,8 @@ static int launch_unfold_now(const ReduceAll& R, hipStream_t s) {
 // The unfold READS the folded layers' summed gradients and OVERWRITES the unfolded ones, so of the backward passes of one optimiser
 // step that accumulate into the same buffers (PIML_ACCUMULATE: the frames of a training rollout) only the LAST pass's unfold
 // matters -- the earlier ones compute from partial sums what the last one computes again.  While deferring, launch_unfold records
-// the sets instead of launching; another network's sets first launch what is waiting.
+// the sets of a pass that asked for it (PIML_DEFER_UNFOLD, carried in R through deferred slot sums) instead of launching; another
+// network's sets first launch what is waiting.  A pass without the flag launches at once: its buffers are the caller's to read.
 namespace {
 struct PendingUnfold {
     ReduceAll R;
@@ -187,7 +188,7 @@ int launch_unfold(const ReduceAll& R, hipStream_t s) {
     bool flush_old = false, deferred = false;
     if (P) {
         std::lock_guard<std::mutex> lock(g_mu);
-        if (P->deferring) {
+        if (P->deferring && R.defer_unfold) {
             if (P->valid && !same_unfold(P->R, R)) { old = P->R; olds = P->stream; flush_old = true; }
             P->R = R; P->stream = s; P->valid = true;
             deferred = true;
@@ -376,9 +377,10 @@ PIML_API int piml_pinnsf_pack_flush(void) { return pending_pack_flush(nullptr); 
 
 // every slot sum of the backward pass (encoder + decoder partials) in one launch on `s`
 static int reduce_all(const piml_encoder_branch* enc, const piml_decoder_branch* dec, int nbr, hipStream_t s, bool accumulate, bool defer = false,
-                      bool sums = false) {
+                      bool sums = false, bool defer_unfold = false) {
     ReduceAll R = {};
     R.accumulate = accumulate ? 1 : 0;
+    R.defer_unfold = defer_unfold ? 1 : 0;
     int w0 = 0, n = 0, maxl = 0;
     const int total = piml_encoder_workgroups(enc, nbr, &w0);
     const int dslots = piml_decoder_workgroups(dec[0].agents);
@@ -508,7 +510,8 @@ PIML_API int piml_pinnsf_bwd(const piml_encoder_branch* enc, const piml_decoder_
         trace_mark("dec_bwd", m);
         PIML_TRY(enc_stage_bwd_sum(enc, nbr, m));
         trace_mark("enc_bwd_dx", m);
-        return reduce_all(enc, dec, nbr, m, (flags & PIML_ACCUMULATE) != 0, (flags & PIML_DEFER_SLOT_SUMS) != 0, true);
+        return reduce_all(enc, dec, nbr, m, (flags & PIML_ACCUMULATE) != 0, (flags & PIML_DEFER_SLOT_SUMS) != 0, true,
+                          (flags & PIML_DEFER_UNFOLD) != 0);
     }
     if (!(flags & PIML_FORK)) {
         PIML_TRY(dec_stage_bwd_fused(dec, nbr, g_pred, self_features, tau, g_self, m));

@@ -37,6 +37,7 @@ struct ReduceAll {
     int gx;               // workgroups per set (the widest set's (lanes + 15) / 16)
     UnfoldSet unf[2];
     int nunf;             // > 0: launch_unfold behind the sums
+    int defer_unfold;     // PIML_DEFER_UNFOLD of the pass: its unfold may wait while the device defers (piml_pinnsf_unfold_defer)
 };
 constexpr int kUnfoldBlocks = 64 + 64 + 1;       // per set: rows of dW1 | row pairs of dW3 | db3
 int launch_unfold(const ReduceAll& R, hipStream_t s);

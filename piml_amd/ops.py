@@ -2475,7 +2475,8 @@ class ParamGradSink:
         self._seen, self._assign, self._mode = set(), {}, {}
         ParamGradSink._active = self
         # the step's backward passes accumulate the FOLDED layers' gradients (sums path); their unfold is linear and overwrites
-        # its outputs, so one launch at the end of the step stands for one per pass (piml_pinnsf_unfold_defer)
+        # its outputs, so one launch at the end of the step stands for one per pass (piml_pinnsf_unfold_defer) -- of the passes that
+        # accumulate into this sink's buffers (PIML_DEFER_UNFOLD, _backward_sums); any other pass unfolds at once
         dev = torch.cuda.current_device() if torch.cuda.is_available() else None
         if dev is not None:
             with torch.cuda.device(dev):
@@ -2902,6 +2903,7 @@ def _backward_sums(ctx, g_acc, g_coll, grads, x2s, masks, pooled, dh1, dd2, ewb,
                                         'of backward passes inside ParamGradSink.step()')
             if acc_e:
                 flags |= _lib.ACCUMULATE
+            flags |= _lib.DEFER_UNFOLD              # (the sink's buffers: read at the step's end, after its one unfold)
         else:
             flats = [torch.empty(L.piml_encoder_partial_floats(), **opt) for _ in range(nbr)]
         for b in range(nbr):

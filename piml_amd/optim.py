@@ -5,8 +5,11 @@ The optimiser of both training loops is `torch.optim.Adam(self.model.parameters(
 fused kernel: 5 + 13 us per step at PINNSF's 22 parameter tensors, launch-bound -- a tenth of a pointwise pre-training step.
 `Adam` below is the same optimiser (same constructor, same state: `step`, `exp_avg`, `exp_avg_sq` per parameter, so state_dict()s are
 interchangeable) whose step() is one kernel launch per parameter group, BITWISE equal to PyTorch's fused kernel
-(tests/test_losses_gpu.py); whatever that launch does not cover (amsgrad, maximize, a tensor learning rate, CPU parameters, other
-dtypes, differentiable steps, a gradient scaler) is left to torch.optim.Adam.step itself."""
+(tests/test_losses_gpu.py, tests/test_optim_gpu.py).  The launch serves groups constructed with fused=True only -- the arithmetic it
+restates is the fused kernel's; every other group gets torch's foreach / per-tensor arithmetic from torch.optim.Adam.step itself, as
+does whatever the launch does not cover (amsgrad, maximize, a tensor learning rate, CPU parameters, other dtypes, differentiable
+steps, a gradient scaler's grad_scale / found_inf).  One group left to torch leaves the whole step to torch.  A closure is evaluated
+first, once, under torch.enable_grad() (as torch.optim.Adam does), and the gradients it leaves are the ones stepped."""
 import ctypes
 
 import torch
@@ -20,8 +23,8 @@ class Adam(torch.optim.Adam):
         self._tickets = {}
 
     def _eligible(self, group, params, grads, exp_avgs, exp_avg_sqs, steps):
-        if group.get('amsgrad') or group.get('maximize') or group.get('differentiable') or group.get('decoupled_weight_decay') \
-                or not isinstance(group['lr'], float):
+        if not group.get('fused') or group.get('amsgrad') or group.get('maximize') or group.get('differentiable') \
+                or group.get('decoupled_weight_decay') or not isinstance(group['lr'], float):
             return False
         if getattr(self, 'grad_scale', None) is not None or getattr(self, 'found_inf', None) is not None:
             return False
@@ -36,6 +39,10 @@ class Adam(torch.optim.Adam):
 
     @torch.no_grad()
     def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
         work = []
         for group in self.param_groups:
             params, grads, exp_avgs, exp_avg_sqs, max_sqs, steps = [], [], [], [], [], []
@@ -43,12 +50,11 @@ class Adam(torch.optim.Adam):
             if not params:
                 continue
             if has_complex or not self._eligible(group, params, grads, exp_avgs, exp_avg_sqs, steps):
-                return super().step(closure)                  # (nothing has been stepped yet: the groups are only gathered above)
+                super().step()                                # (nothing has been stepped yet: the groups are only gathered above)
+                return loss
             work.append((group, params, grads, exp_avgs, exp_avg_sqs, steps))
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+        if not work:
+            return loss
         self._cuda_graph_capture_health_check()
         L = _lib.lib()
         for group, params, grads, exp_avgs, exp_avg_sqs, steps in work:
