@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PIML_HIP_ABI_VERSION 33
+#define PIML_HIP_ABI_VERSION 34
 #define PIML_MAX_TOPK 32 /* topk_ped / topk_obs upper bound (reference defaults 6 / 10) */
 
 /* ABI version of the loaded library (== PIML_HIP_ABI_VERSION). */
@@ -374,6 +374,39 @@ int piml_collision_counts_grid(const float* position, int S, int N, const float*
  * (dp, dv, ...), `row_stride` floats apart -> label[rows] in {0, 1}.
  */
 int piml_collision_label(const float* ped_features, size_t rows, int row_stride, float* label, void* stream);
+
+/*
+ * Evaluation metrics, every frame in ONE launch (one workgroup per frame, no host sync).  x: (F, n, 2), y: (F, m, 2)
+ * positions; mask_x (F, n) / mask_y (F, m): uint8 presence (non-zero = present), NULL = every point present.  Each frame's
+ * present points are compacted in slot order, as the reference's p[mask == 1] does; absent slots are never read (they may
+ * hold NaN).  A NaN in a present point makes that frame's result NaN.  Limits: 0 <= n, m <= 4096 (n != m allowed).
+ * Deterministic: no atomics, the same inputs give the same bits.
+ *
+ * Entropic OT.  Replaces SinkhornDistance.forward (src/functions/metrics.py:129-187) as ot_with_time_mask (:45-67) and
+ * wasserstein_distance_2d (:94-97) call it on one frame: log-domain Sinkhorn with uniform marginals, the cost
+ * C_ij = |x_i - y_j|^2 recomputed (never stored), at most max_iter iterations, the frame stopping after the iteration whose
+ * err = sum_i |u_i - u_i'| is < thresh (the reference's break, :161-172, 2-D input).  Float32 arithmetic as the reference's,
+ * the final sum(exp(M) * C) accumulated in float64.  cost (F) float32, iters (F) int32 = iterations run; u (F, n) and
+ * v (F, m) (each may be NULL) = the final potentials at the frame's slots, 0 at absent ones.
+ * hipErrorInvalidValue: F, n or m < 0, n or m > 4096, eps <= 0 (or NaN), max_iter < 0, a NULL x / y (with points) or
+ * cost / iters.  F == 0 is a no-op.
+ */
+int piml_sinkhorn_frames(const float* x, const float* y, const unsigned char* mask_x, const unsigned char* mask_y, int F,
+                         int n, int m, float eps, int max_iter, float thresh, float* cost, int* iters, float* u, float* v,
+                         void* stream);
+
+/*
+ * Multi-kernel Gaussian MMD.  Replaces MaximumMeanDiscrepancy.__call__ / guassian_kernel (src/functions/metrics.py:207-273)
+ * as mmd_with_time_mask (:70-91) and mmd_loss (:100-104) call it on one frame: bandwidth = sum L2 / ((n+m)^2 - (n+m)) over
+ * the frame's (n+m)^2 pairs unless fix_sigma != 0 (Python truthiness: 0 means "computed"), divided by
+ * kernel_mul^(kernel_num // 2); K = sum_i exp(-L2 / (bandwidth * kernel_mul^i)), i < kernel_num <= 8;
+ * out[f] = XX / n^2 + YY / m^2 - XY / (n m) - YX / (m n) (an empty block adds 0).  float64 from the float32 positions on,
+ * out (F) float32.  All points coinciding give bandwidth 0 and NaN, as in the reference.
+ * hipErrorInvalidValue: F, n or m < 0, n or m > 4096, kernel_num outside 1..8, a NULL x / y (with points) or out.
+ * F == 0 is a no-op.
+ */
+int piml_mmd_frames(const float* x, const float* y, const unsigned char* mask_x, const unsigned char* mask_y, int F, int n,
+                    int m, double kernel_mul, int kernel_num, double fix_sigma, float* out, void* stream);
 
 /*
  * utils.calc_acceleration (src/utils/utils.py:31-100): version 0/1/2 = 'v0'/'v1'/'v2' with the

@@ -11,12 +11,13 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PIML_LIB=<path>: an experimental build of the same ABI beside the shipped library (piml_amd.build.variant; tools/ A/B timings)
 LIB_PATH = os.environ.get('PIML_LIB') or os.path.join(_HERE, 'libpiml_hip.so')
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 _lib = None
 
 _i, _f, _p, _z = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 _ll = ctypes.c_longlong
+_d = ctypes.c_double
 
 
 class EncoderBranch(ctypes.Structure):
@@ -78,6 +79,8 @@ SIGNATURES = {
     'piml_collision_counts_scratch': [_p, _i, _i, _p, _i, _p, _p, _p],
     'piml_collision_counts_grid': [_p, _i, _i, _p, _i, _p, _p, _p],
     'piml_collision_label': [_p, _z, _i, _p, _p],
+    'piml_sinkhorn_frames': [_p, _p, _p, _p, _i, _i, _i, _f, _i, _f, _p, _p, _p, _p, _p],
+    'piml_mmd_frames': [_p, _p, _p, _p, _i, _i, _i, _d, _i, _d, _p, _p],
     'piml_calc_acceleration': [_p, _z, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p],
     'piml_rollout_step': [_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p,
                           _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p],

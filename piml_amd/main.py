@@ -63,6 +63,7 @@ def get_args(argv=None):
     A('--save_configs', action='store_true'); A('--reg_weight', type=float, default=0.)
     A('--collision_threshold', type=float, default=0.5); A('--collision_loss_weight', type=float, default=10)
     A('--val_coll_weight', type=float, default=30); A('--hard_collision_penalty', type=float, default=10)
+    A('--metrics_impl', type=str, default='torch', choices=('torch', 'hip'))   # evaluation OT / MMD: batched torch | HIP kernels
     A('--teacher_weight', type=float, default=0); A('--collision_pred_weight', type=float, default=10)
     A('--collision_focus_weight', type=float, default=10); A('--new_collision_loss_flag', type=int, default=0)
     A('--tags', type=str, default=''); A('--iter_flag', type=int, default=0)

@@ -1127,6 +1127,7 @@ class BaseSimulator(Pedestrians):
         reference has no FDE); OT / MMD are the batched restatements in functions/metrics.py."""
         from ..functions import metrics as METRIC
         args = self.args
+        impl = getattr(args, 'metrics_impl', 'torch')           # OT / MMD: batched torch or the per-frame HIP kernels
         self.model.eval()
         if not isinstance(data, list):
             # single-clip branch (simulators.py:471-490): predictions shifted by one frame against the labels,
@@ -1139,8 +1140,8 @@ class BaseSimulator(Pedestrians):
                 sel = mask == 1
                 loss = mse = F.mse_loss(p_pred[sel], labels[sel], reduction='mean').item()
                 mae = METRIC.mae_with_time_mask(p_pred, labels, mask, reduction='mean')
-                ot = METRIC.ot_with_time_mask(p_pred, labels, mask, reduction='mean')
-                mmd = METRIC.mmd_with_time_mask(p_pred, labels, mask, reduction='mean')
+                ot = METRIC.ot_with_time_mask(p_pred, labels, mask, reduction='mean', impl=impl)
+                mmd = METRIC.mmd_with_time_mask(p_pred, labels, mask, reduction='mean', impl=impl)
                 collision = METRIC.collision_count(p_pred, 0.6, reduction='sum')
             if test_flag:
                 print('---------------------------------------')
@@ -1169,8 +1170,8 @@ class BaseSimulator(Pedestrians):
                     fde_sum += METRIC.fde_with_time_mask(p_pred, labels, mask, reduction='sum')
                     fde_n += int(((mask == 1).sum(dim=0) > 0).sum().item())
                     mae_sum += METRIC.mae_with_time_mask(p_pred, labels, mask, reduction='sum')
-                    ot_sum += METRIC.ot_with_time_mask(p_pred, labels, mask, reduction='sum')
-                    mmd_sum += METRIC.mmd_with_time_mask(p_pred, labels, mask, reduction='sum')
+                    ot_sum += METRIC.ot_with_time_mask(p_pred, labels, mask, reduction='sum', impl=impl)
+                    mmd_sum += METRIC.mmd_with_time_mask(p_pred, labels, mask, reduction='sum', impl=impl)
                 n += int((mask == 1).sum().item())
                 frames += int((mask.sum(dim=1) > 0).sum().item())
                 loss_sum, mse_sum = loss_sum + loss, mse_sum + mse
