@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PIML_HIP_ABI_VERSION 34
+#define PIML_HIP_ABI_VERSION 35
 #define PIML_MAX_TOPK 32 /* topk_ped / topk_obs upper bound (reference defaults 6 / 10) */
 
 /* ABI version of the loaded library (== PIML_HIP_ABI_VERSION). */
@@ -454,6 +454,67 @@ int piml_rollout_step_ksum(const float* pred_ped, int kp, const float* pred_obs,
                            float* position_out, float* velocity_out, float* acceleration_out, float* mask_out,
                            float* self_features_next, const float* desired_speed, const int64_t* frame_counter, int C, int T,
                            int N, float dt, int remove_arrived, void* stream);
+
+/*
+ * Open-world scenario frame (ABI 35).  Replaces the simulation loop the reference stubs (BaseSimulator.run /
+ * run_single_step, src/models/simulators.py:834-838) around a scenario's update function -- GC's arrival rule and Poisson
+ * arrivals (src/data/scenarios.py:313-401), utils.route (src/utils/utils.py:141-165) -- and the frame protocol of
+ * RawData.add_frame / add_pedestrians (src/data/data.py:206-303), one launch per frame.  Storage is append-only: the agent
+ * of global ordinal n lives in slot n (as add_pedestrians appends); ordinals >= capacity are dropped, counted, never written.
+ *
+ * init == 0, frame t -> t+1 (t = *frame_counter, read on the device):
+ *   every slot i < min(spawned[t & 1], capacity) with mask[i] == 1: v' = v + a dt, p' = p + v dt, a' = a_next[i]; the
+ *   history shift and columns 2.. of its self_features row (history, a', v0) as piml_rollout_step; flag += 1 when
+ *   |p' - dest| or the distance from p' to entry exit_idx[flag] is < arrival_radius; then flag == D or a NaN
+ *   waypoint[flag] retires the agent for good (p, dest = NaN, v, a = 0, mask 0), otherwise dest = waypoint[flag];
+ *   k = Poisson(rate dt) draw of frame t+1 (k = #{j < spawn_cap : u24 >= poisson_thresholds[j]}) new agents of ordinals
+ *   spawned[t & 1] + j, one wave each: distinct uniform origin / destination entries, uniform point + U[0,1)^2 spawn_offset,
+ *   waypoints (route(o, d), d, NaN...), exit_idx of each, v0 = max(speed_min, speed_mean + speed_std z) (speed_mean if
+ *   uniform_speed), v = a = history = 0, flag 0, mask 1; spawned[(t+1) & 1] = spawned[t & 1] + k,
+ *   *dropped = max(0, spawned - capacity), spawn_out[t+1] = k;
+ *   frame t+1's p, v, a, dest, mask are written to the (T, capacity, .) outputs when t+1 < T.
+ * init == 1: the n_initial agents (ordinals 0 ..) spawn into frame t through the same path; a_next unused.
+ * The Philox word layout of the draws is documented in piml_amd/csrc/scenario.hip.  Columns 0..1 of self_features (the
+ * destination features) are piml_relfeat_fwd's.  Slots nobody has written (absent, not yet spawned) are the caller's to
+ * initialise (NaN positions / destinations, zero masks).  No atomics; the spawned count is ping-ponged by frame parity.
+ * hipErrorInvalidValue: capacity or T < 1, hist_width < 2, F != hist_width + 5, D outside 2..8, E < 2, P < 1, R < 2,
+ * n_initial outside 0..4096, route_max_iters outside 0..64, spawn_cap outside 0..8, dt <= 0, thresholds above 2^24 or
+ * decreasing, init not 0 / 1, a NULL buffer (spawn_out and spawn_iters may be NULL), a NULL a_next with init == 0.
+ */
+typedef struct piml_scenario {
+    float *position, *velocity, *acceleration, *destination; /* (capacity, 2) state, in place */
+    float* hist_velocity;                                   /* (capacity, hist_width) */
+    float* self_features;                                   /* (capacity, F) */
+    float* desired_speed;                                   /* (capacity) */
+    float* mask;                                            /* (capacity) 1 = present */
+    int* flag;                                              /* (capacity) index of the current waypoint */
+    float* waypoints;                                       /* (D, capacity, 2) */
+    int* exit_idx;                                          /* (D, capacity) entry nearest each waypoint */
+    int* spawn_iters;                                       /* (capacity) route iterations of each agent, or NULL */
+    float *position_out, *velocity_out, *acceleration_out, *destination_out; /* (T, capacity, 2) */
+    float* mask_out;                                        /* (T, capacity) */
+    int* spawn_out;                                         /* (T) agents spawned per frame, or NULL */
+    const int64_t* frame_counter;                           /* t */
+    int64_t* spawned;                                       /* [2], by frame parity: agents spawned through the frame */
+    int64_t* dropped;                                       /* [1] */
+    const float* entries;                                   /* (E, P, 2) */
+    const float* route_polyline;                            /* (R, 2) */
+    int hist_width, F, D, E, P, R, capacity, T, n_initial, route_max_iters, spawn_cap, uniform_speed;
+    float dt, spawn_offset, route_clearance, arrival_radius, speed_mean, speed_std, speed_min;
+    uint64_t seed;
+    uint32_t poisson_thresholds[8];                         /* ceil(2^24 P(K <= j)), j < spawn_cap */
+} piml_scenario;
+int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, void* stream);
+
+/*
+ * utils.route (src/utils/utils.py:141-165) for n (o, d) pairs, one wave each, the device function the spawn path uses:
+ * the segment o -> r is tested against the polyline's R-1 segments, the hit with the smallest alpha moves r to
+ * crossing + clearance * normal, until nothing is hit or max_iters moves were made.  float32 in the reference's order.
+ * origin / destination / waypoint (n, 2), polyline (R, 2), iters (n) int32 = moves made.
+ * hipErrorInvalidValue: n < 0, R < 2, max_iters outside 0..64, a NULL buffer with n > 0.  n == 0 is a no-op.
+ */
+int piml_scenario_route(const float* origin, const float* destination, int n, const float* polyline, int R, int max_iters,
+                        float clearance, float* waypoint, int* iters, void* stream);
 
 /*
  * The hand-written collision handling that closes PINNSF_polar_bottleneck_collision.forward

@@ -11,7 +11,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PIML_LIB=<path>: an experimental build of the same ABI beside the shipped library (piml_amd.build.variant; tools/ A/B timings)
 LIB_PATH = os.environ.get('PIML_LIB') or os.path.join(_HERE, 'libpiml_hip.so')
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 _lib = None
 
@@ -59,6 +59,19 @@ class Corrector(ctypes.Structure):
                 ('partials_a', _p), ('partials_b', _p), ('grads', _p)]
 
 
+class Scenario(ctypes.Structure):
+    """piml_scenario (include/piml_hip.h)."""
+    _fields_ = [('position', _p), ('velocity', _p), ('acceleration', _p), ('destination', _p), ('hist_velocity', _p),
+                ('self_features', _p), ('desired_speed', _p), ('mask', _p), ('flag', _p), ('waypoints', _p), ('exit_idx', _p),
+                ('spawn_iters', _p), ('position_out', _p), ('velocity_out', _p), ('acceleration_out', _p),
+                ('destination_out', _p), ('mask_out', _p), ('spawn_out', _p), ('frame_counter', _p), ('spawned', _p),
+                ('dropped', _p), ('entries', _p), ('route_polyline', _p),
+                ('hist_width', _i), ('F', _i), ('D', _i), ('E', _i), ('P', _i), ('R', _i), ('capacity', _i), ('T', _i),
+                ('n_initial', _i), ('route_max_iters', _i), ('spawn_cap', _i), ('uniform_speed', _i),
+                ('dt', _f), ('spawn_offset', _f), ('route_clearance', _f), ('arrival_radius', _f), ('speed_mean', _f),
+                ('speed_std', _f), ('speed_min', _f), ('seed', ctypes.c_uint64), ('poisson_thresholds', ctypes.c_uint32 * 8)]
+
+
 PACKED_VALID, FORK, ACCUMULATE, DEFER_SLOT_SUMS, DEFER_PACK, POOL_H2, POOL_TRAIN, POOL_MSGS, DEFER_UNFOLD = 1, 2, 4, 8, 16, 32, 64, 128, 256   # piml_pinnsf_* flags
 
 # name -> argtypes, in the order of include/piml_hip.h
@@ -86,6 +99,8 @@ SIGNATURES = {
                           _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p],
     'piml_rollout_step_ksum': [_p, _i, _p, _i, _f, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p,
                                _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p],
+    'piml_scenario_step': [_p, _p, _i, _p],
+    'piml_scenario_route': [_p, _p, _i, _p, _i, _i, _f, _p, _p, _p],
     'piml_collision_correction_fwd': [_p, _p, _p, _z, _i, _i, _f, _f, _p, _p],
     'piml_collision_correction_bwd': [_p, _p, _p, _p, _z, _i, _i, _f, _f, _p, _p, _p, _p],
     'piml_train_step_fwd': [_p] * 7 + [_i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p],

@@ -1,0 +1,356 @@
+// Open-world scenario frame: integrate, arrive, retire, spawn and record one simulated frame of a scene whose agents are not
+// recorded but generated -- the Grand Central hall of the reference (src/data/scenarios.py:313-401, GC()), driven by the
+// frame protocol of RawData.add_frame / add_pedestrians (src/data/data.py:206-303).  One launch per frame, no host sync:
+// a whole simulation replays as one captured frame (the frame counter and the spawn count live in device memory).
+//
+// Frame t -> t+1 (piml_scenario_step, init == 0):
+//   agents   (one thread per slot i < min(n_t, capacity), n_t = agents spawned through frame t)
+//     1. integrate  v' = v + a dt, p' = p + v dt (the lagged Euler of rollout_step_agent, pairwise.hip), a' = a_next; the
+//                   velocity history shifts and columns 2.. of the self_features row get (history, a', v0);
+//     2. arrive     GC's update (scenarios.py:376-384): dis2des = |p' - dest|, dis2exit = min over the points of entry
+//                   exit(dest) of |p' - e|, exit(w) = the entry whose points come nearest waypoint w (computed once at spawn);
+//                   flag += 1 if either is below arrival_radius (at most once per frame);
+//     3. retire     add_frame (data.py:236-247): flag == D or waypoint[flag] NaN -> p, dest = NaN, v, a = 0, mask 0, for
+//                   good; otherwise dest = waypoint[flag];
+//   spawn    (one wave per new agent j < k_{t+1} <= spawn_cap, ordinal n_t + j; ordinals >= capacity are dropped)
+//     4. k ~ Poisson(rate dt) by inversion, origin / destination entries distinct and uniform (random.sample(entry, 2)),
+//        a point index uniform in 0..P-1 and an offset U[0,1)^2 * spawn_offset for each, waypoints (r, d) = route(o, d)
+//        (lanes over the polyline's segments), v0 = max(speed_min, speed_mean + speed_std z) (or speed_mean), v = a = 0;
+//   5. record frame t+1's p, v, a, dest, mask into the (T, capacity, .) buffers (skipped from t+1 = T on).
+// init == 1 spawns the n_initial agents (ordinals 0 .. n_initial-1) into frame t through the same path (GC's generate(20)).
+//
+// Randomness: Philox4x32-10 (philox.hpp), key = (seed lo, seed hi).  Counter words (c0, c1, c2, c3):
+//   spawn count of frame f      (f lo, f hi, 0, 0x5CE00000): word 0 >> 8 = u24; k = #{j < spawn_cap : u24 >= thr[j]},
+//                               thr[j] = ceil(2^24 P(K <= j)) computed by the host (the documented cap: P(K > 8 | 0.4) ~ 1e-10)
+//   agent of ordinal n, call 1  (n lo, n hi, 0, 0x5CE00001): origin entry (w0 E) >> 32; destination entry (w1 (E-1)) >> 32,
+//                               shifted past the origin; origin point (w2 P) >> 32; destination point (w3 P) >> 32
+//                      call 2  (n lo, n hi, 0, 0x5CE00002): offsets (w0, w1) of the origin, (w2, w3) of the destination,
+//                               each (w >> 8) 2^-24
+//                      call 3  (n lo, n hi, 0, 0x5CE00003): z = sqrt(-2 ln u1) cos(2 pi u2) in double, u1 = ((w0 >> 8) + 1)
+//                               2^-24, u2 = (w1 >> 8) 2^-24
+// The dropout keep-mask stream uses c3 = (stream_id << 16) | sub with stream ids 0 and 1: stream 0x5CE0 is never one of
+// them.  The schedule depends on (seed, frame, ordinal) only, not on the dynamics; tests/scenario_ref.py restates it.
+//
+// Determinism: no atomics.  The spawned count is ping-ponged by frame parity (spawned[t & 1] read, spawned[(t+1) & 1]
+// written by one thread), so no workgroup reads a value another one writes in the same launch; spawned agents take slots
+// >= n_t, which no agent thread touches.
+#include "common.hpp"
+#include "philox.hpp"
+#include "../../include/piml_hip.h"
+
+#include <cmath>
+
+namespace piml {
+
+constexpr unsigned kScenarioStream = 0x5CE00000u;
+constexpr int kScenarioMaxSpawn = 8;       // spawn_cap bound (the Poisson inversion's cap)
+constexpr int kScenarioMaxD = 8;
+constexpr int kScenarioMaxIters = 64;
+constexpr int kScenarioMaxInitial = 4096;
+constexpr int kScenarioLdsPoints = 2048;   // entry points staged in LDS (16 KB) when E * P fits
+
+__device__ __forceinline__ unsigned pick(unsigned w, unsigned n) { return (unsigned)(((unsigned long long)w * n) >> 32); }
+__device__ __forceinline__ float unit24(unsigned w) { return (float)(w >> 8) * 5.9604644775390625e-8f; }
+__device__ __forceinline__ float qnan() { return __uint_as_float(0x7fc00000u); }
+
+// wave-wide lexicographic minimum of (alpha, j)
+__device__ __forceinline__ void wave_argmin(float& a, int& j) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float oa = __shfl_xor(a, o, 64);
+        const int oj = __shfl_xor(j, o, 64);
+        if (oa < a || (oa == a && oj < j)) { a = oa; j = oj; }
+    }
+}
+
+__device__ __forceinline__ float wave_min(float x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = fminf(x, __shfl_xor(x, o, 64));
+    return x;
+}
+
+// utils.route (src/utils/utils.py:141-165) for one (o, d) pair, one wave: every iteration tests the segment o -> r against
+// the polyline's R-1 segments (lanes strided over them), takes the hit with the smallest alpha (lowest segment on a tie, as
+// torch.argmin over the ascending hit indices), and moves r to the crossing + clearance * normal.  float32 in the
+// reference's operation order (cross_dot_z: product, product, one add).  Returns r; *iters = moves made (<= max_iters).
+// Wave-uniform result.
+__device__ float2 route_wave(float2 o, float2 d, const float2* __restrict__ poly, int R, int max_iters, float clearance, int* iters) {
+    const int lane = lane_id();
+    float2 r = d;
+    int it = 0;
+    for (; it < max_iters; ++it) {
+        const float Ax = __fsub_rn(r.x, o.x), Ay = __fsub_rn(r.y, o.y);
+        float best = INFINITY;
+        int bj = 0x7fffffff;
+        for (int j = lane; j < R - 1; j += 64) {
+            const float2 p0 = poly[j], p1 = poly[j + 1];
+            const float Bx = __fsub_rn(p1.x, p0.x), By = __fsub_rn(p1.y, p0.y);
+            const float Cx = __fsub_rn(p0.x, o.x), Cy = __fsub_rn(p0.y, o.y);
+            const float det = __fadd_rn(__fmul_rn(Ay, Bx), __fmul_rn(-Ax, By));
+            const float alpha = __fdiv_rn(__fadd_rn(__fmul_rn(Cy, Bx), __fmul_rn(-Cx, By)), det);
+            const float beta = __fdiv_rn(__fadd_rn(__fmul_rn(Cy, Ax), __fmul_rn(-Cx, Ay)), det);
+            if (0.f < alpha && alpha < 1.f && 0.f < beta && beta < 1.f && alpha < best) { best = alpha; bj = j; }
+        }
+        wave_argmin(best, bj);
+        if (bj == 0x7fffffff) break;
+        const float al = best;
+        const float2 p0 = poly[bj], p1 = poly[bj + 1];
+        const float Bx = __fsub_rn(p1.x, p0.x), By = __fsub_rn(p1.y, p0.y);
+        const float om = __fsub_rn(1.f, al);
+        const float cx = __fadd_rn(__fmul_rn(al, r.x), __fmul_rn(om, o.x));
+        const float cy = __fadd_rn(__fmul_rn(al, r.y), __fmul_rn(om, o.y));
+        const float s = -__fadd_rn(__fmul_rn(By, Ax), __fmul_rn(-Bx, Ay));
+        float nx = __fmul_rn(s, Ay), ny = __fmul_rn(s, -Ax);
+        const float nn = norm2(nx, ny);
+        nx = __fdiv_rn(nx, nn);
+        ny = __fdiv_rn(ny, nn);
+        r = make_float2(__fadd_rn(cx, __fmul_rn(clearance, nx)), __fadd_rn(cy, __fmul_rn(clearance, ny)));
+    }
+    *iters = it;
+    return r;
+}
+
+// the entry whose points come nearest q (argmin over entries of the min over their points of |q - e|, first entry on a
+// tie); one wave.  min_p sqrt_rn(s_p) = sqrt_rn(min_p s_p): the correctly rounded square root is monotonic, so the
+// per-entry minimum is taken on the squared distances and rooted once.
+__device__ int nearest_entry_wave(float2 q, const float2* entries, int E, int P) {
+    const int lane = lane_id();
+    float best = INFINITY;
+    int be = 0;
+    for (int e = 0; e < E; ++e) {
+        float m = INFINITY;
+        for (int p = lane; p < P; p += 64) {
+            const float2 x = entries[(size_t)e * P + p];
+            m = fminf(m, sq2(__fsub_rn(q.x, x.x), __fsub_rn(q.y, x.y)));
+        }
+        m = sqrtf(wave_min(m));
+        if (m < best) { best = m; be = e; }
+    }
+    return be;
+}
+
+struct ScenarioKernelArgs {
+    piml_scenario S;
+    const float2* a_next;
+    int init, agent_blocks;
+};
+
+__device__ __forceinline__ int poisson_count(const piml_scenario& S, long long frame) {
+    const PhiloxOut w = philox4x32_10((unsigned)frame, (unsigned)((unsigned long long)frame >> 32), 0u, kScenarioStream,
+                                      (unsigned)S.seed, (unsigned)(S.seed >> 32));
+    const unsigned u = w.x >> 8;
+    int k = 0;
+    for (int j = 0; j < S.spawn_cap; ++j) k += u >= S.poisson_thresholds[j];
+    return k;
+}
+
+__device__ __forceinline__ void agent_step(const ScenarioKernelArgs& K, const float2* entries, int i, long long t) {
+    const piml_scenario& S = K.S;
+    float2* P = (float2*)S.position;
+    float2* V = (float2*)S.velocity;
+    float2* Ac = (float2*)S.acceleration;
+    float2* Dst = (float2*)S.destination;
+    const long long tn = t + 1;
+    const bool rec = tn < S.T;
+    const size_t fr = (size_t)tn * S.capacity + i;
+    if (S.mask[i] == 0.f) {                                  // retired for good
+        if (rec) {
+            ((float2*)S.position_out)[fr] = make_float2(qnan(), qnan());
+            ((float2*)S.velocity_out)[fr] = make_float2(0.f, 0.f);
+            ((float2*)S.acceleration_out)[fr] = make_float2(0.f, 0.f);
+            ((float2*)S.destination_out)[fr] = make_float2(qnan(), qnan());
+            S.mask_out[fr] = 0.f;
+        }
+        return;
+    }
+    const float dt = S.dt;
+    const float2 p = P[i], v = V[i], a = Ac[i], d = Dst[i];
+    float2 an = K.a_next[i];
+    float2 vn = make_float2(__fadd_rn(v.x, __fmul_rn(a.x, dt)), __fadd_rn(v.y, __fmul_rn(a.y, dt)));
+    float2 pn = make_float2(__fadd_rn(p.x, __fmul_rn(v.x, dt)), __fadd_rn(p.y, __fmul_rn(v.y, dt)));
+    const int hw = S.hist_width;
+    float* h = S.hist_velocity + (size_t)i * hw;
+    float* so = S.self_features + (size_t)i * S.F;
+    for (int q = 0; q + 2 < hw; ++q) h[q] = h[q + 2];
+    h[hw - 2] = vn.x; h[hw - 1] = vn.y;
+    for (int q = 0; q < hw; ++q) so[2 + q] = h[q];
+    so[2 + hw] = an.x; so[3 + hw] = an.y; so[4 + hw] = S.desired_speed[i];
+
+    // 2. arrive (scenarios.py:376-384)
+    int f = S.flag[i];
+    const float2* ent = entries + (size_t)S.exit_idx[(size_t)f * S.capacity + i] * S.P;
+    float m2 = INFINITY;                                     // min over the exit's points of the squared distance
+#pragma unroll 10
+    for (int q = 0; q < S.P; ++q) m2 = fminf(m2, sq2(__fsub_rn(pn.x, ent[q].x), __fsub_rn(pn.y, ent[q].y)));
+    const bool near = norm2(__fsub_rn(pn.x, d.x), __fsub_rn(pn.y, d.y)) < S.arrival_radius || sqrtf(m2) < S.arrival_radius;
+    if (near) f += 1;
+    // 3. retire (data.py:236-247)
+    float2 dn = make_float2(qnan(), qnan());
+    bool gone = f >= S.D;
+    if (!gone) {
+        dn = ((const float2*)S.waypoints)[(size_t)f * S.capacity + i];
+        gone = dn.x != dn.x || dn.y != dn.y;
+    }
+    float m = 1.f;
+    if (gone) {
+        pn = make_float2(qnan(), qnan());
+        dn = make_float2(qnan(), qnan());
+        vn = make_float2(0.f, 0.f);
+        an = make_float2(0.f, 0.f);
+        m = 0.f;
+    }
+    P[i] = pn; V[i] = vn; Ac[i] = an; Dst[i] = dn;
+    S.flag[i] = f;
+    S.mask[i] = m;
+    if (rec) {
+        ((float2*)S.position_out)[fr] = pn;
+        ((float2*)S.velocity_out)[fr] = vn;
+        ((float2*)S.acceleration_out)[fr] = an;
+        ((float2*)S.destination_out)[fr] = dn;
+        S.mask_out[fr] = m;
+    }
+}
+
+// one wave: agent of ordinal `ord` (< capacity) appears in frame `f`
+__device__ void spawn_agent(const piml_scenario& S, const float2* ent, long long ord, long long f) {
+    const int lane = lane_id();
+    const unsigned k0 = (unsigned)S.seed, k1 = (unsigned)(S.seed >> 32);
+    const unsigned c0 = (unsigned)ord, c1 = (unsigned)((unsigned long long)ord >> 32);
+    const PhiloxOut w1 = philox4x32_10(c0, c1, 0u, kScenarioStream | 1u, k0, k1);
+    const PhiloxOut w2 = philox4x32_10(c0, c1, 0u, kScenarioStream | 2u, k0, k1);
+    const unsigned oe = pick(w1.x, (unsigned)S.E);
+    unsigned de = pick(w1.y, (unsigned)S.E - 1u);
+    de += de >= oe;
+    const unsigned oi = pick(w1.z, (unsigned)S.P), di = pick(w1.w, (unsigned)S.P);
+    const float2 eo = ent[(size_t)oe * S.P + oi], ed = ent[(size_t)de * S.P + di];
+    const float2 o = make_float2(__fadd_rn(eo.x, __fmul_rn(unit24(w2.x), S.spawn_offset)),
+                                 __fadd_rn(eo.y, __fmul_rn(unit24(w2.y), S.spawn_offset)));
+    const float2 d = make_float2(__fadd_rn(ed.x, __fmul_rn(unit24(w2.z), S.spawn_offset)),
+                                 __fadd_rn(ed.y, __fmul_rn(unit24(w2.w), S.spawn_offset)));
+    int iters;
+    const float2 r = route_wave(o, d, (const float2*)S.route_polyline, S.R, S.route_max_iters, S.route_clearance, &iters);
+    float v0 = S.speed_mean;
+    if (!S.uniform_speed) {
+        const PhiloxOut w3 = philox4x32_10(c0, c1, 0u, kScenarioStream | 3u, k0, k1);
+        const double u1 = (double)((w3.x >> 8) + 1u) * 5.9604644775390625e-8, u2 = (double)(w3.y >> 8) * 5.9604644775390625e-8;
+        const float z = (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
+        v0 = __fadd_rn(S.speed_mean, __fmul_rn(S.speed_std, z));
+        if (v0 < S.speed_min) v0 = S.speed_min;
+    }
+    // waypoints (r, d, NaN ...) and the exit entry of each, once
+    const size_t cap = (size_t)S.capacity, i = (size_t)ord;
+    for (int q = 0; q < S.D; ++q) {
+        const float2 wq = q == 0 ? r : (q == 1 ? d : make_float2(qnan(), qnan()));
+        const int ex = q < 2 ? nearest_entry_wave(wq, ent, S.E, S.P) : 0;
+        if (lane == 0) {
+            ((float2*)S.waypoints)[q * cap + i] = wq;
+            S.exit_idx[q * cap + i] = ex;
+        }
+    }
+    if (lane == 0) {
+        ((float2*)S.position)[i] = o;
+        ((float2*)S.velocity)[i] = make_float2(0.f, 0.f);
+        ((float2*)S.acceleration)[i] = make_float2(0.f, 0.f);
+        ((float2*)S.destination)[i] = r;
+        S.desired_speed[i] = v0;
+        S.flag[i] = 0;
+        S.mask[i] = 1.f;
+        if (S.spawn_iters) S.spawn_iters[i] = iters;
+        if (f < S.T) {
+            const size_t fr = (size_t)f * cap + i;
+            ((float2*)S.position_out)[fr] = o;
+            ((float2*)S.velocity_out)[fr] = make_float2(0.f, 0.f);
+            ((float2*)S.acceleration_out)[fr] = make_float2(0.f, 0.f);
+            ((float2*)S.destination_out)[fr] = r;
+            S.mask_out[fr] = 1.f;
+        }
+    }
+    for (int q = lane; q < S.hist_width; q += 64) S.hist_velocity[i * S.hist_width + q] = 0.f;
+    for (int q = 2 + lane; q < S.F; q += 64) S.self_features[i * S.F + q] = q == S.F - 1 ? v0 : 0.f;
+}
+
+__global__ __launch_bounds__(256) void scenario_step_kernel(const ScenarioKernelArgs K) {
+    __shared__ float2 lds_entries[kScenarioLdsPoints];
+    const piml_scenario& S = K.S;
+    const float2* ent = (const float2*)S.entries;
+    const bool lds = S.E * S.P <= kScenarioLdsPoints;        // kernel-uniform: every block stages the entry points
+    if (lds) {
+        for (int q = threadIdx.x; q < S.E * S.P; q += blockDim.x) lds_entries[q] = ent[q];
+        __syncthreads();
+        ent = lds_entries;
+    }
+    const long long t = *S.frame_counter;
+    const long long n = K.init ? 0 : S.spawned[t & 1];
+    const long long f = K.init ? t : t + 1;                  // the frame the new agents appear in
+    if ((int)blockIdx.x < K.agent_blocks) {
+        const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < n && i < S.capacity) {                       // (two inlined copies: LDS reads where the points fit)
+            if (lds) agent_step(K, lds_entries, (int)i, t);
+            else agent_step(K, (const float2*)S.entries, (int)i, t);
+        }
+        return;
+    }
+    const int k = K.init ? S.n_initial : poisson_count(S, f);
+    if (blockIdx.x == (unsigned)K.agent_blocks && threadIdx.x == 0) {
+        S.spawned[f & 1] = n + k;
+        *S.dropped = n + k > S.capacity ? n + k - S.capacity : 0;
+        if (S.spawn_out && f < S.T) S.spawn_out[f] = k;
+    }
+    const int j = (int)(blockIdx.x - K.agent_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
+    if (j >= k || n + j >= S.capacity) return;               // ordinals past the capacity are dropped, never written
+    spawn_agent(S, ent, n + j, f);
+}
+
+__global__ __launch_bounds__(256) void scenario_route_kernel(const float2* __restrict__ o, const float2* __restrict__ d, int n,
+                                                             const float2* __restrict__ poly, int R, int max_iters, float clearance,
+                                                             float2* __restrict__ out, int* __restrict__ iters) {
+    const int j = (int)blockIdx.x * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
+    if (j >= n) return;
+    int it;
+    const float2 r = route_wave(o[j], d[j], poly, R, max_iters, clearance, &it);
+    if (lane_id() == 0) {
+        out[j] = r;
+        iters[j] = it;
+    }
+}
+
+}  // namespace piml
+
+PIML_API int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, void* stream) {
+    if (!s) return hipErrorInvalidValue;
+    const piml_scenario& S = *s;
+    if (S.capacity < 1 || S.T < 1 || S.hist_width < 2 || S.F != S.hist_width + 5 || S.D < 2 || S.D > piml::kScenarioMaxD ||
+        S.E < 2 || S.P < 1 || S.R < 2 || S.n_initial < 0 || S.n_initial > piml::kScenarioMaxInitial ||
+        S.route_max_iters < 0 || S.route_max_iters > piml::kScenarioMaxIters || S.spawn_cap < 0 ||
+        S.spawn_cap > piml::kScenarioMaxSpawn || !(S.dt > 0.f) || (init != 0 && init != 1) || (!init && !a_next))
+        return hipErrorInvalidValue;
+    if (!S.position || !S.velocity || !S.acceleration || !S.destination || !S.hist_velocity || !S.self_features ||
+        !S.desired_speed || !S.flag || !S.mask || !S.waypoints || !S.exit_idx || !S.position_out || !S.velocity_out ||
+        !S.acceleration_out || !S.destination_out || !S.mask_out || !S.frame_counter || !S.spawned || !S.dropped ||
+        !S.entries || !S.route_polyline)
+        return hipErrorInvalidValue;
+    for (int j = 0; j < S.spawn_cap; ++j)
+        if (S.poisson_thresholds[j] > (1u << 24) || (j && S.poisson_thresholds[j] < S.poisson_thresholds[j - 1]))
+            return hipErrorInvalidValue;
+    piml::ScenarioKernelArgs K;
+    K.S = S;
+    K.a_next = (const float2*)a_next;
+    K.init = init;
+    K.agent_blocks = init ? 0 : (S.capacity + 255) / 256;
+    const int waves = init ? S.n_initial : S.spawn_cap;
+    const int spawn_blocks = waves > 0 ? (waves + 3) / 4 : 1;   // >= 1: block agent_blocks writes the spawned count
+    hipLaunchKernelGGL(piml::scenario_step_kernel, dim3((unsigned)(K.agent_blocks + spawn_blocks)), dim3(256), 0,
+                       piml::as_stream(stream), K);
+    return hipGetLastError();
+}
+
+PIML_API int piml_scenario_route(const float* origin, const float* destination, int n, const float* polyline, int R,
+                                 int max_iters, float clearance, float* waypoint, int* iters, void* stream) {
+    if (n < 0 || R < 2 || max_iters < 0 || max_iters > piml::kScenarioMaxIters) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    if (!origin || !destination || !polyline || !waypoint || !iters) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(piml::scenario_route_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, piml::as_stream(stream),
+                       (const float2*)origin, (const float2*)destination, n, (const float2*)polyline, R, max_iters, clearance,
+                       (float2*)waypoint, iters);
+    return hipGetLastError();
+}

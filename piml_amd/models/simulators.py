@@ -462,6 +462,80 @@ class BaseSimulator(Pedestrians):
                              mask_p=st.mask_new, meta_data=getattr(data, 'meta_data', None),
                              time_unit=data.time_unit)
 
+    # ---- open-world simulation: the loop the reference stubs (BaseSimulator.run / run_single_step, simulators.py:834-838) ----
+    def simulate_scenario(self, scenario, frames, seed=0, capacity=None, use_graph=None):
+        """Simulate `frames` frames of an entry / exit scene (piml_amd.scenarios.Scenario, e.g. gc_scenario()) with the
+        current model: frame 0 spawns the scenario's initial agents, every further frame is model -> piml_scenario_step
+        (integrate, arrive, retire, Poisson arrivals routed around the scenario's polyline, record) -> relative features.
+        The frame is captured into one graph and replayed (`use_graph=None`: when more than 8 frames); the Philox draws
+        make the spawn schedule a function of (seed, frame, ordinal).  `capacity` = agent slots (default: n_initial + a
+        1e-9 upper quantile of the arrivals); agents past it are dropped and counted.  Returns a ScenarioResult."""
+        only = hasattr(self.model, 'predictions_only')
+        before = getattr(self.model, 'predictions_only', False)
+        with torch.no_grad():
+            if only:
+                self.model.predictions_only = True
+            try:
+                with self._packed_weights():
+                    return self._simulate_scenario(scenario, frames, seed, capacity, use_graph)
+            finally:
+                if only:
+                    self.model.predictions_only = before
+
+    def _simulate_scenario(self, scenario, frames, seed, capacity, use_graph):
+        from .. import ops_scenario, scenarios, hip_graphs_safe
+        a = self.args
+        sc = scenario.to(torch.device(a.device))
+        T = int(frames)
+        if T < 1:
+            raise ValueError(f'frames must be >= 1, got {frames}')
+        cap = scenarios.default_capacity(sc, T) if capacity is None else int(capacity)
+        st = ops_scenario.scenario_state(sc, cap, T, 2 * int(a.num_history_velocity), seed, a.topk_ped, a.topk_obs)
+        feats = (st.pf, st.of, st.selff, st.ped_idx, st.obs_idx)
+        geo = (a.topk_ped, a.sight_angle_ped, a.dist_threshold_ped, a.topk_obs, a.sight_angle_obs, a.dist_threshold_obs)
+        ops_scenario.scenario_step(st, init=True)                                         # frame 0: generate(n_initial)
+        ops.relative_features_into(feats, st.p, st.v, st.a, st.dest, sc.obstacles, *geo)
+
+        def step():
+            a_next = self.model(st.pf, st.of, st.selff)[0]
+            ops_scenario.scenario_step(st, a_next.contiguous())
+            ops.relative_features_into(feats, st.p, st.v, st.a, st.dest, sc.obstacles, *geo, tick=st.t)   # + st.t += 1
+
+        steps = T - 1
+        if use_graph is None:
+            use_graph = steps > 8
+        use_graph = bool(use_graph) and hip_graphs_safe()
+        done = 0
+        if use_graph and steps > 3:
+            try:
+                if self._side_stream_ok(cap):
+                    self.model.obs_stream = torch.cuda.Stream()
+                for _ in range(2):                        # real frames, also warm every lazy init up
+                    step()
+                done = 2
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    step()
+                self.model.obs_stream = None
+                done += 1                                 # the capture does not execute: replay it once now
+                for _ in range(steps - done + 1):
+                    graph.replay()
+                done = steps
+            except RuntimeError as ex:                    # capture unsupported: finish eagerly
+                self.model.obs_stream = None
+                print(f'[piml_amd] scenario graph capture failed ({ex}); continuing eagerly')
+                torch.cuda.synchronize()
+                done = int(st.t.item())
+        for _ in range(steps - done):
+            step()
+        last = int(st.t.item())
+        return scenarios.ScenarioResult(
+            position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res, mask_p=st.mask_res,
+            waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles, time_unit=sc.time_unit,
+            spawned=int(st.spawned[last & 1].item()), dropped=int(st.dropped.item()), spawn_count=st.spawn_count,
+            capacity=cap, seed=int(seed), state=st)
+
     # ---- HOT LOOP C: differentiable rollout for fine-tuning (simulators.py:659-832) ----
     def test_multiple_rollouts_for_training(self, data, t_start=0):
         """(loss, mse_loss, collision_loss, hard_collision_loss, collision_pred_loss, collision_pred_acc,

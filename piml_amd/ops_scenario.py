@@ -1,0 +1,109 @@
+"""Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_route).
+
+`scenario_state` allocates the persistent (static-address) buffers of one simulation and the `piml_scenario` descriptor
+that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive, retire, spawn, record), with the
+frame index read from device memory so that one captured launch serves every frame of a replayed graph.  Like every
+operator of piml_amd they require GPU tensors and raise PimlHipError otherwise."""
+import ctypes
+import types
+
+import torch
+
+from . import _lib
+from .ops import _gpu_f32, _ptr, _stream
+
+
+def scenario_route(origin, destination, polyline, max_iters=16, clearance=2.0):
+    """utils.route (src/utils/utils.py:141-165) for every (origin, destination) pair, one wave each: (n, 2) x2, polyline
+    (R, 2) -> (waypoint r (n, 2), iterations (n) int32).  The route of pair j is (origin[j], r[j], destination[j])."""
+    o = _gpu_f32('origin', origin).reshape(-1, 2)
+    d = _gpu_f32('destination', destination).reshape(-1, 2)
+    poly = _gpu_f32('polyline', polyline).reshape(-1, 2)
+    if o.shape != d.shape:
+        raise ValueError(f'origin {tuple(o.shape)} and destination {tuple(d.shape)} differ')
+    if o.device != d.device or o.device != poly.device:
+        raise ValueError('origin, destination and polyline on different devices')
+    r = torch.empty_like(o)
+    iters = torch.empty(o.shape[0], device=o.device, dtype=torch.int32)
+    with torch.cuda.device(o.device):
+        _lib.check(_lib.lib().piml_scenario_route(_ptr(o), _ptr(d), o.shape[0], _ptr(poly), poly.shape[0], int(max_iters),
+                                                  float(clearance), _ptr(r), _ptr(iters), _stream()), 'piml_scenario_route')
+    return r, iters
+
+
+def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6, topk_obs=10):
+    """The buffers of one simulation of `scenario` (on its device) with `capacity` slots and `frames` recorded frames,
+    and their descriptor.  Absent slots start as NaN positions / destinations, zero velocity, acceleration and masks."""
+    dev = scenario.entries.device
+    if dev.type != 'cuda':
+        raise _lib.PimlHipError(f'scenario_state: the scenario must be on a GPU (piml_amd has no CPU path), got {dev}')
+    cap, T, D = int(capacity), int(frames), int(scenario.num_waypoints)
+    if cap < 1 or T < 1:
+        raise ValueError(f'capacity and frames must be >= 1, got {cap}, {T}')
+    st = types.SimpleNamespace(scenario=scenario, capacity=cap, T=T, seed=int(seed))
+    f32 = dict(device=dev, dtype=torch.float32)
+    nan = float('nan')
+    st.p = torch.full((cap, 2), nan, **f32)
+    st.v = torch.zeros(cap, 2, **f32)
+    st.a = torch.zeros(cap, 2, **f32)
+    st.dest = torch.full((cap, 2), nan, **f32)
+    st.hist = torch.zeros(cap, hist_width, **f32)
+    st.selff = torch.zeros(cap, hist_width + 5, **f32)
+    st.desired_speed = torch.zeros(cap, **f32)
+    st.mask = torch.zeros(cap, **f32)
+    st.flag = torch.zeros(cap, device=dev, dtype=torch.int32)
+    st.waypoints = torch.full((D, cap, 2), nan, **f32)
+    st.exit_idx = torch.zeros(D, cap, device=dev, dtype=torch.int32)
+    st.spawn_iters = torch.zeros(cap, device=dev, dtype=torch.int32)
+    st.p_res = torch.full((T, cap, 2), nan, **f32)
+    st.v_res = torch.zeros(T, cap, 2, **f32)
+    st.a_res = torch.zeros(T, cap, 2, **f32)
+    st.dest_res = torch.full((T, cap, 2), nan, **f32)
+    st.mask_res = torch.zeros(T, cap, **f32)
+    st.spawn_count = torch.zeros(T, device=dev, dtype=torch.int32)
+    st.t = torch.zeros(1, device=dev, dtype=torch.long)
+    st.spawned = torch.zeros(2, device=dev, dtype=torch.long)
+    st.dropped = torch.zeros(1, device=dev, dtype=torch.long)
+    # feature buffers the relative-feature kernel writes (ops.relative_features_into)
+    kp, ko = min(topk_ped, cap), min(topk_obs, scenario.obstacles.shape[0])
+    st.pf = torch.empty(cap, kp, 6, **f32)
+    st.of = torch.empty(cap, ko, 6, **f32)
+    st.ped_idx = torch.empty(cap, kp, device=dev, dtype=torch.int32)
+    st.obs_idx = torch.empty(cap, ko, device=dev, dtype=torch.int32)
+
+    s = _lib.Scenario()
+    for name, t in (('position', st.p), ('velocity', st.v), ('acceleration', st.a), ('destination', st.dest),
+                    ('hist_velocity', st.hist), ('self_features', st.selff), ('desired_speed', st.desired_speed),
+                    ('mask', st.mask), ('flag', st.flag), ('waypoints', st.waypoints), ('exit_idx', st.exit_idx),
+                    ('spawn_iters', st.spawn_iters), ('position_out', st.p_res), ('velocity_out', st.v_res),
+                    ('acceleration_out', st.a_res), ('destination_out', st.dest_res), ('mask_out', st.mask_res),
+                    ('spawn_out', st.spawn_count), ('frame_counter', st.t), ('spawned', st.spawned), ('dropped', st.dropped),
+                    ('entries', scenario.entries), ('route_polyline', scenario.route_polyline)):
+        setattr(s, name, t.data_ptr())
+    E, P = scenario.entries.shape[0], scenario.entries.shape[1]
+    s.hist_width, s.F, s.D, s.E, s.P, s.R = hist_width, hist_width + 5, D, E, P, scenario.route_polyline.shape[0]
+    s.capacity, s.T, s.n_initial = cap, T, int(scenario.n_initial)
+    s.route_max_iters, s.spawn_cap, s.uniform_speed = int(scenario.route_max_iters), int(scenario.spawn_cap), int(bool(scenario.uniform_desired_speed))
+    s.dt, s.spawn_offset, s.route_clearance = float(scenario.time_unit), float(scenario.spawn_offset), float(scenario.route_clearance)
+    s.arrival_radius, s.speed_mean, s.speed_min = float(scenario.arrival_radius), float(scenario.speed_mean), float(scenario.speed_min)
+    s.speed_std = float(scenario.speed_var ** 0.5)
+    s.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    thr = scenario.poisson_thresholds()
+    if len(thr) > 8:
+        raise ValueError(f'spawn_cap {len(thr)} > 8')
+    for j, x in enumerate(thr):
+        s.poisson_thresholds[j] = x
+    st.desc = s
+    return st
+
+
+def scenario_step(st, a_next=None, init=False):
+    """One launch: init=True spawns the scenario's n_initial agents into frame st.t; otherwise frame st.t -> st.t + 1 with
+    the network's accelerations a_next (capacity, 2).  The caller advances st.t (ops.relative_features_into(tick=st.t))."""
+    if not init:
+        a_next = _gpu_f32('a_next', a_next)
+        if tuple(a_next.shape) != (st.capacity, 2) or a_next.device != st.p.device:
+            raise ValueError(f'a_next: ({st.capacity}, 2) on {st.p.device} expected, got {tuple(a_next.shape)} on {a_next.device}')
+    with torch.cuda.device(st.p.device):
+        _lib.check(_lib.lib().piml_scenario_step(ctypes.byref(st.desc), _ptr(a_next) if not init else None, int(bool(init)),
+                                                 _stream()), 'piml_scenario_step')

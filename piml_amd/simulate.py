@@ -1,0 +1,61 @@
+"""Open-world crowd simulation with a trained PINNSF: generate a scene (default: the Grand Central hall), simulate it on
+the GPU and save the result as a v2.2 clip that `RawData.load_trajectory_data` (and so `--iter_flag` pre-training) reads.
+
+    python -m piml_amd.simulate --checkpoint model.pt --frames 750 --out clip.npy [model flags of piml_amd.main]
+
+Model flags (--model, --hidden sizes, --topk_*, --num_history_velocity, ...) are those of `piml_amd.main`, with its
+defaults.  Without --checkpoint the network keeps its initial weights (a smoke run)."""
+import argparse
+import os
+import sys
+
+os.environ.setdefault('DEBUG_CLR_GRAPH_PACKET_CAPTURE', '0')      # before torch brings the HIP runtime up (piml_amd.hip_graphs_safe)
+
+import torch  # noqa: E402
+
+from . import main as MAIN  # noqa: E402
+from . import scenarios as SCENARIOS  # noqa: E402
+from .functions import metrics as METRIC  # noqa: E402
+
+
+def get_args(argv=None):
+    p = argparse.ArgumentParser(description='open-world crowd simulation with a trained PINNSF')
+    p.add_argument('--checkpoint', type=str, default='', help='state_dict of the model (torch.save); "" = initial weights')
+    p.add_argument('--scenario', type=str, default='gc', choices=sorted(SCENARIOS.SCENARIOS))
+    p.add_argument('--frames', type=int, default=750)
+    p.add_argument('--seed', type=int, default=0, help='seed of the spawn schedule')
+    p.add_argument('--capacity', type=int, default=None, help='agent slots (default: from the arrival rate)')
+    p.add_argument('--out', type=str, default='clip.npy')
+    p.add_argument('--time_unit', type=float, default=0.08)
+    p.add_argument('--uniform_desired_speed', action='store_true')
+    own, rest = p.parse_known_args(argv)
+    model_args = MAIN.get_args(rest)
+    return own, model_args
+
+
+def main(argv=None):
+    own, args = get_args(argv)
+    from .models.simulators import BaseSimulator
+    MAIN.set_exp_configs(args)
+    # the feature widths piml_amd.data.dataset sets from a clip: 6-wide neighbour rows, self = (dest, history, a, v0)
+    args.ped_feature_dim = args.obs_feature_dim = 6
+    args.self_feature_dim = 5 + 2 * args.num_history_velocity
+    sim = BaseSimulator(args)
+    if own.checkpoint:
+        sim.model.load_state_dict(torch.load(own.checkpoint, map_location=args.device))
+    sim.model.eval()
+    scenario = SCENARIOS.SCENARIOS[own.scenario](time_unit=own.time_unit, uniform_desired_speed=own.uniform_desired_speed)
+    res = sim.simulate_scenario(scenario, own.frames, seed=own.seed, capacity=own.capacity)
+    n = res.num_agents
+    retired = n - int(res.mask_p[-1, :n].sum().item())
+    pos = res.position[:, :n]
+    soft = METRIC.collision_count(pos, args.collision_threshold, reduction='sum')       # as piml_amd.main reports them
+    hard = METRIC.collision_count(pos, args.collision_threshold / 2, reduction='sum')
+    res.save_data(own.out)
+    print(f'[simulate] {own.scenario}: {own.frames} frames, capacity {res.capacity}: spawned {res.spawned}, '
+          f'retired {retired}, dropped {res.dropped}; collisions soft {soft:g} hard {hard:g}; saved {own.out}')
+    return res
+
+
+if __name__ == '__main__':
+    main(sys.argv[1:])

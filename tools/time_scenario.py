@@ -1,0 +1,73 @@
+"""ms per simulated frame of the open-world scenario (BaseSimulator.simulate_scenario on gc_scenario(), one captured frame
+replayed) against the clip rollout's frame (get_multiple_rollouts on the synthetic GC clip of piml_amd.scenes with the
+same obstacle points) at the same N = capacity, pinnsf_m in eval mode.  Per-frame cost = the difference of two runs of
+different lengths (set-up, warm-up and capture cancel), median of --reps alternated pairs.
+Prints one JSON object.  Usage: python tools/time_scenario.py [--caps 256 1024 4096] [--reps 5]
+Kernel list of a frame: rocprofv3 --kernel-trace --stats -d <dir> -- python tools/time_scenario.py --caps 1024 --reps 1"""
+import argparse
+import json
+import os
+import sys
+
+os.environ.setdefault('DEBUG_CLR_GRAPH_PACKET_CAPTURE', '0')
+
+import torch  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--caps', type=int, nargs='+', default=[256, 1024, 4096])
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--short', type=int, default=40)
+    ap.add_argument('--long', type=int, default=240)
+    a = ap.parse_args()
+    from test_simulator_gpu import sim_args
+    from piml_amd.models.simulators import BaseSimulator
+    from piml_amd.scenarios import gc_scenario
+    from piml_amd.scenes import synthetic_rollout_data
+    torch.manual_seed(0)
+    sim = BaseSimulator(sim_args())
+    sim.model.eval()
+    sc = gc_scenario().to('cuda:0')
+    M = sc.obstacles.shape[0]
+    res = {'frames': [a.short, a.long], 'reps': a.reps, 'obstacles': M, 'scenario_ms_per_frame': {}, 'rollout_ms_per_frame': {},
+           'ratio': {}, 'agents_present_last_frame': {}}
+    for cap in a.caps:
+        clips = {T: synthetic_rollout_data(cap, M, T, 'cuda:0', seed=1) for T in (a.short, a.long)}
+
+        def scen(T):
+            return timed(lambda: sim.simulate_scenario(sc, T, seed=1, capacity=cap))
+
+        def roll(T):
+            return timed(lambda: sim.get_multiple_rollouts(clips[T], t_start=0, load_model=False))
+
+        with torch.no_grad():
+            scen(a.short), roll(a.short)                     # warm-up
+            s, r = [], []
+            for _ in range(a.reps):                          # alternated: the host is shared
+                s.append((scen(a.long) - scen(a.short)) / (a.long - a.short))
+                r.append((roll(a.long) - roll(a.short)) / (a.long - a.short))
+            last = sim.simulate_scenario(sc, a.long, seed=1, capacity=cap)
+        med = lambda x: sorted(x)[len(x) // 2]
+        res['scenario_ms_per_frame'][cap] = round(med(s), 4)
+        res['rollout_ms_per_frame'][cap] = round(med(r), 4)
+        res['ratio'][cap] = round(med(s) / med(r), 3)
+        res['agents_present_last_frame'][cap] = int(last.mask_p[-1].sum().item())
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
