@@ -507,6 +507,47 @@ typedef struct piml_scenario {
 int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, void* stream);
 
 /*
+ * Scene rules of piml_scenario_step_rules (ABI 35, additive): the reference's synthetic scenes (src/data/scenarios.py:9-311,
+ * crosswalk / four_directional_square / basic_unit1..3) in place of GC's entry pairs, route and exit distance.
+ * spawn_law (what a new agent of ordinal n looks like; word layout in piml_amd/csrc/scenario.hip):
+ *   PIML_SPAWN_GC          GC (scenarios.py:369-387): piml_scenario_step itself, arrival_rule must be PIML_ARRIVE_GC
+ *   PIML_SPAWN_CROSSWALK   scenarios.py:36-65: |x| = length/2 + 3u on a coin side, y = +-width/2 on a coin side,
+ *                          waypoints (-side_x length/2, +-width/2 by a coin) and (same x, 3 y), heading (0, -side_y)
+ *   PIML_SPAWN_SQUARE      scenarios.py:87-134: the init launch's n_initial = 4 grid^2 agents on the four blocks of
+ *                          square_grid (+-length, the block length), destinations at rank(cell) of grid^2 Philox keys
+ *                          (randperm), heading 0; no arrivals afterwards (spawn_cap 0)
+ *   PIML_SPAWN_UNIT1       scenarios.py:140-156: (0, width u) -> (length, y + 2u - 1), heading (1, 0)
+ *   PIML_SPAWN_UNIT2       scenarios.py:189-215: side / direction by u < side_ratio / u < direction_ratio, heading (+-1, 0)
+ *   PIML_SPAWN_UNIT3       scenarios.py:248-282: stream 1 as UNIT1; stream 2 (0..spawn_cap2 per frame, thresholds2) from
+ *                          (length u, 0) -> (x + 2u - 1, width), heading (0, 1)
+ * arrival_rule: PIML_ARRIVE_RADIUS |p' - dest| < arrival_radius -> flag += 1; PIML_ARRIVE_XBAND |p'.x - dest.x| <
+ * arrival_radius -> flag += 1; PIML_ARRIVE_XEXIT p'.x > length retires the agent (flag unchanged).  Retirement as
+ * piml_scenario_step (flag == D or waypoint[flag] NaN; or the x exit).
+ * initial_velocity: 0 = v0 vector 0, 1 = heading * v0 (the velocity of the spawn frame and the newest history slot; older
+ * slots 0).  speed_clamp: 1 = v0 = max(speed_min, speed_mean + speed_std z), 0 = no clamp (uniform_speed: v0 = speed_mean).
+ * entries, route_polyline and exit_idx are not read (may be NULL).  Same frame protocol, determinism and capture as
+ * piml_scenario_step.
+ * hipErrorInvalidValue: s or r NULL; the checks of piml_scenario_step except D (1..8 here, >= 2 for the crosswalk) and
+ * E, P, R, route_max_iters, entries, route_polyline, exit_idx; spawn_law / arrival_rule unknown or one GC and the other
+ * not; initial_velocity or speed_clamp not 0 / 1; spawn_cap2 outside 0..8 or non-zero for a law other than UNIT3;
+ * thresholds2 above 2^24 or decreasing; the square's grid outside 1..32 or n_initial != 4 grid^2.
+ */
+enum { PIML_SPAWN_GC = 0, PIML_SPAWN_CROSSWALK = 1, PIML_SPAWN_SQUARE = 2, PIML_SPAWN_UNIT1 = 3, PIML_SPAWN_UNIT2 = 4,
+       PIML_SPAWN_UNIT3 = 5 };
+enum { PIML_ARRIVE_GC = 0, PIML_ARRIVE_RADIUS = 1, PIML_ARRIVE_XBAND = 2, PIML_ARRIVE_XEXIT = 3 };
+typedef struct piml_scenario_rules {
+    int spawn_law, arrival_rule, initial_velocity, speed_clamp;
+    int spawn_cap2;                                         /* second Poisson stream's cap (UNIT3) */
+    int grid;                                               /* SQUARE: cells per side */
+    float length, width;                                    /* scene size (SQUARE: length = block length) */
+    float side_ratio, direction_ratio;                      /* UNIT2 */
+    uint32_t poisson_thresholds2[8];                        /* second stream's ceil(2^24 P(K <= j)), j < spawn_cap2 */
+    float square_grid[32];                                  /* SQUARE: the grid coordinates, grid of them */
+} piml_scenario_rules;
+int piml_scenario_step_rules(const piml_scenario* s, const piml_scenario_rules* r, const float* a_next, int init,
+                             void* stream);
+
+/*
  * utils.route (src/utils/utils.py:141-165) for n (o, d) pairs, one wave each, the device function the spawn path uses:
  * the segment o -> r is tested against the polyline's R-1 segments, the hit with the smallest alpha moves r to
  * crossing + clearance * normal, until nothing is hit or max_iters moves were made.  float32 in the reference's order.

@@ -72,6 +72,17 @@ class Scenario(ctypes.Structure):
                 ('speed_std', _f), ('speed_min', _f), ('seed', ctypes.c_uint64), ('poisson_thresholds', ctypes.c_uint32 * 8)]
 
 
+class ScenarioRules(ctypes.Structure):
+    """piml_scenario_rules (include/piml_hip.h)."""
+    _fields_ = [('spawn_law', _i), ('arrival_rule', _i), ('initial_velocity', _i), ('speed_clamp', _i), ('spawn_cap2', _i),
+                ('grid', _i), ('length', _f), ('width', _f), ('side_ratio', _f), ('direction_ratio', _f),
+                ('poisson_thresholds2', ctypes.c_uint32 * 8), ('square_grid', _f * 32)]
+
+
+SPAWN_LAWS = {'gc': 0, 'crosswalk': 1, 'square': 2, 'unit1': 3, 'unit2': 4, 'unit3': 5}      # PIML_SPAWN_*
+ARRIVAL_RULES = {'gc': 0, 'radius': 1, 'x_band': 2, 'x_exit': 3}                             # PIML_ARRIVE_*
+
+
 PACKED_VALID, FORK, ACCUMULATE, DEFER_SLOT_SUMS, DEFER_PACK, POOL_H2, POOL_TRAIN, POOL_MSGS, DEFER_UNFOLD = 1, 2, 4, 8, 16, 32, 64, 128, 256   # piml_pinnsf_* flags
 
 # name -> argtypes, in the order of include/piml_hip.h
@@ -100,6 +111,7 @@ SIGNATURES = {
     'piml_rollout_step_ksum': [_p, _i, _p, _i, _f, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p,
                                _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p],
     'piml_scenario_step': [_p, _p, _i, _p],
+    'piml_scenario_step_rules': [_p, _p, _p, _i, _p],
     'piml_scenario_route': [_p, _p, _i, _p, _i, _i, _f, _p, _p, _p],
     'piml_collision_correction_fwd': [_p, _p, _p, _z, _i, _i, _f, _f, _p, _p],
     'piml_collision_correction_bwd': [_p, _p, _p, _p, _z, _i, _i, _f, _f, _p, _p, _p, _p],

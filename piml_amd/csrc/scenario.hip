@@ -31,6 +31,26 @@
 // The dropout keep-mask stream uses c3 = (stream_id << 16) | sub with stream ids 0 and 1: stream 0x5CE0 is never one of
 // them.  The schedule depends on (seed, frame, ordinal) only, not on the dynamics; tests/scenario_ref.py restates it.
 //
+// Scene rules (piml_scenario_step_rules, piml_scenario_rules): the reference's synthetic scenes (scenarios.py:9-311) run
+// scenario_rules_kernel, which GC never reaches (GC's rules go to scenario_step_kernel above, unchanged).  Same frame order;
+// step 2 is the rule's (|p' - dest| < r, |p'.x - dest.x| < r, or retire when p'.x > length) and step 4 is the spawn law's.
+// Its Philox stream is c3 = 0x5CE10000 | sub (key = (seed lo, seed hi), the float of a word is (w >> 8) 2^-24 =: u(w),
+// a coin is w >> 31):
+//   spawn counts of frame f     (f lo, f hi, 0, 0x5CE10000): stream 1 k1 from word 0 >> 8 against thresholds,
+//                               stream 2 k2 (UNIT3) from word 1 >> 8 against thresholds2; the frame's first k1 new
+//                               ordinals are stream 1's, the next k2 stream 2's (torch.cat of generate(k1, k2))
+//   agent of ordinal n, call 1  (n lo, n hi, 0, 0x5CE10001):
+//       CROSSWALK       side_x = 2 coin(w0) - 1, side_y = 2 coin(w1) - 1, x = side_x (length/2 + 3 u(w2)),
+//                       waypoint y = -width/2 + width coin(w3)
+//       UNIT1, UNIT3/1  y = width u(w0), destination y = y + (2 u(w1) - 1)
+//       UNIT2           left side u(w0) < side_ratio, right-to-left u(w1) < direction_ratio, y = width/2 u(w2),
+//                       destination y = y + (2 u(w3) - 1)
+//       UNIT3/2         x = length u(w0), destination x = x + (2 u(w1) - 1)
+//       SQUARE          none
+//                      call 2  (n lo, n hi, 0, 0x5CE10002): z from (w0, w1) as GC's call 3 (double), when not uniform_speed
+//   square cell c's key         (c, 0, 0, 0x5CE10003) word 0: randperm(grid^2)[c] = rank of key c among the grid^2 keys,
+//                               ties by cell index (each init wave counts its own cell's rank)
+//
 // Determinism: no atomics.  The spawned count is ping-ponged by frame parity (spawned[t & 1] read, spawned[(t+1) & 1]
 // written by one thread), so no workgroup reads a value another one writes in the same launch; spawned agents take slots
 // >= n_t, which no agent thread touches.
@@ -314,6 +334,218 @@ __global__ __launch_bounds__(256) void scenario_route_kernel(const float2* __res
     }
 }
 
+
+// ---- scene rules (piml_scenario_step_rules): the synthetic scenes; GC never reaches these paths ----
+
+constexpr unsigned kRulesStream = 0x5CE10000u;
+constexpr int kRulesMaxGrid = 32;
+
+struct RulesKernelArgs {
+    piml_scenario S;
+    piml_scenario_rules R;
+    const float2* a_next;
+    int init, agent_blocks;
+};
+
+__device__ __forceinline__ int threshold_count(unsigned u, const uint32_t* thr, int cap) {
+    int k = 0;
+    for (int j = 0; j < cap; ++j) k += u >= thr[j];
+    return k;
+}
+
+__device__ __forceinline__ int wave_sum(int x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+__device__ __forceinline__ void rules_agent_step(const RulesKernelArgs& K, int i, long long t) {
+    const piml_scenario& S = K.S;
+    const piml_scenario_rules& R = K.R;
+    float2* P = (float2*)S.position;
+    float2* V = (float2*)S.velocity;
+    float2* Ac = (float2*)S.acceleration;
+    float2* Dst = (float2*)S.destination;
+    const long long tn = t + 1;
+    const bool rec = tn < S.T;
+    const size_t fr = (size_t)tn * S.capacity + i;
+    if (S.mask[i] == 0.f) {                                  // retired for good
+        if (rec) {
+            ((float2*)S.position_out)[fr] = make_float2(qnan(), qnan());
+            ((float2*)S.velocity_out)[fr] = make_float2(0.f, 0.f);
+            ((float2*)S.acceleration_out)[fr] = make_float2(0.f, 0.f);
+            ((float2*)S.destination_out)[fr] = make_float2(qnan(), qnan());
+            S.mask_out[fr] = 0.f;
+        }
+        return;
+    }
+    const float dt = S.dt;
+    const float2 p = P[i], v = V[i], a = Ac[i], d = Dst[i];
+    float2 an = K.a_next[i];
+    float2 vn = make_float2(__fadd_rn(v.x, __fmul_rn(a.x, dt)), __fadd_rn(v.y, __fmul_rn(a.y, dt)));
+    float2 pn = make_float2(__fadd_rn(p.x, __fmul_rn(v.x, dt)), __fadd_rn(p.y, __fmul_rn(v.y, dt)));
+    const int hw = S.hist_width;
+    float* h = S.hist_velocity + (size_t)i * hw;
+    float* so = S.self_features + (size_t)i * S.F;
+    for (int q = 0; q + 2 < hw; ++q) h[q] = h[q + 2];
+    h[hw - 2] = vn.x; h[hw - 1] = vn.y;
+    for (int q = 0; q < hw; ++q) so[2 + q] = h[q];
+    so[2 + hw] = an.x; so[3 + hw] = an.y; so[4 + hw] = S.desired_speed[i];
+
+    // 2. arrive: the scene's update (scenarios.py:67-69, 128-130, 159-160, 218-219, 286-287)
+    int f = S.flag[i];
+    bool gone = false;
+    if (R.arrival_rule == PIML_ARRIVE_RADIUS) f += norm2(__fsub_rn(pn.x, d.x), __fsub_rn(pn.y, d.y)) < S.arrival_radius;
+    else if (R.arrival_rule == PIML_ARRIVE_XBAND) f += fabsf(__fsub_rn(pn.x, d.x)) < S.arrival_radius;
+    else gone = pn.x > R.length;                             // PIML_ARRIVE_XEXIT: mask_p = 0
+    // 3. retire (data.py:236-247)
+    float2 dn = make_float2(qnan(), qnan());
+    gone = gone || f >= S.D;
+    if (!gone) {
+        dn = ((const float2*)S.waypoints)[(size_t)f * S.capacity + i];
+        gone = dn.x != dn.x || dn.y != dn.y;
+    }
+    float m = 1.f;
+    if (gone) {
+        pn = make_float2(qnan(), qnan());
+        dn = make_float2(qnan(), qnan());
+        vn = make_float2(0.f, 0.f);
+        an = make_float2(0.f, 0.f);
+        m = 0.f;
+    }
+    P[i] = pn; V[i] = vn; Ac[i] = an; Dst[i] = dn;
+    S.flag[i] = f;
+    S.mask[i] = m;
+    if (rec) {
+        ((float2*)S.position_out)[fr] = pn;
+        ((float2*)S.velocity_out)[fr] = vn;
+        ((float2*)S.acceleration_out)[fr] = an;
+        ((float2*)S.destination_out)[fr] = dn;
+        S.mask_out[fr] = m;
+    }
+}
+
+// 2 u - 1 of torch's (2 * torch.rand(n) - 1)
+__device__ __forceinline__ float jitter(unsigned w) { return __fsub_rn(__fmul_rn(2.f, unit24(w)), 1.f); }
+
+// one wave: agent of ordinal `ord` (< capacity) of spawn stream `group` (0 / 1) appears in frame `f`
+__device__ void rules_spawn_agent(const piml_scenario& S, const piml_scenario_rules& R, long long ord, int group, long long f) {
+    const int lane = lane_id();
+    const unsigned k0 = (unsigned)S.seed, k1 = (unsigned)(S.seed >> 32);
+    const unsigned c0 = (unsigned)ord, c1 = (unsigned)((unsigned long long)ord >> 32);
+    const float L = R.length, W = R.width;
+    float2 o, d0, d1 = make_float2(qnan(), qnan()), head = make_float2(0.f, 0.f);
+    if (R.spawn_law == PIML_SPAWN_SQUARE) {
+        const int cells = R.grid * R.grid, c = (int)(ord % cells), g = (int)(ord / cells);
+        const unsigned mine = philox4x32_10((unsigned)c, 0u, 0u, kRulesStream | 3u, k0, k1).x;
+        int below = 0;
+        for (int q = lane; q < cells; q += 64) {
+            const unsigned other = philox4x32_10((unsigned)q, 0u, 0u, kRulesStream | 3u, k0, k1).x;
+            below += other < mine || (other == mine && q < c);
+        }
+        const int s = wave_sum(below);                       // randperm(grid^2)[c]
+        const float gx = R.square_grid[c / R.grid], gy = R.square_grid[c % R.grid];
+        const float hx = R.square_grid[s / R.grid], hy = R.square_grid[s % R.grid];
+        if (g == 0)      { o = make_float2(__fsub_rn(gx, L), gy); d0 = make_float2(__fadd_rn(hx, L), hy); }
+        else if (g == 1) { o = make_float2(__fadd_rn(gx, L), gy); d0 = make_float2(__fsub_rn(hx, L), hy); }
+        else if (g == 2) { o = make_float2(gx, __fsub_rn(gy, L)); d0 = make_float2(hx, __fadd_rn(hy, L)); }
+        else             { o = make_float2(gx, __fadd_rn(gy, L)); d0 = make_float2(hx, __fsub_rn(hy, L)); }
+    } else {
+        const PhiloxOut w = philox4x32_10(c0, c1, 0u, kRulesStream | 1u, k0, k1);
+        if (R.spawn_law == PIML_SPAWN_CROSSWALK) {
+            const float sx = (w.x >> 31) ? 1.f : -1.f, sy = (w.y >> 31) ? 1.f : -1.f;
+            o = make_float2(sx * __fadd_rn(0.5f * L, __fmul_rn(3.f, unit24(w.z))), 0.5f * W * sy);
+            d0 = make_float2(-sx * (0.5f * L), __fadd_rn(-0.5f * W, (w.w >> 31) ? W : 0.f));
+            d1 = make_float2(d0.x, __fmul_rn(d0.y, 3.f));
+            head = make_float2(0.f, -sy);
+        } else if (R.spawn_law == PIML_SPAWN_UNIT2) {
+            const bool left = unit24(w.x) < R.side_ratio, rtl = unit24(w.y) < R.direction_ratio;
+            float y = __fmul_rn(0.5f * W, unit24(w.z));
+            if (left) y = __fadd_rn(y, 0.5f * W);
+            if (rtl) y = __fsub_rn(W, y);
+            o = make_float2(rtl ? L : 0.f, y);
+            d0 = make_float2(rtl ? 0.f : L, __fadd_rn(y, jitter(w.w)));
+            head = make_float2(rtl ? -1.f : 1.f, 0.f);
+        } else if (R.spawn_law == PIML_SPAWN_UNIT3 && group == 1) {
+            const float x = __fmul_rn(L, unit24(w.x));
+            o = make_float2(x, 0.f);
+            d0 = make_float2(__fadd_rn(x, jitter(w.y)), W);
+            head = make_float2(0.f, 1.f);
+        } else {                                             // UNIT1, UNIT3's first stream
+            const float y = __fmul_rn(W, unit24(w.x));
+            o = make_float2(0.f, y);
+            d0 = make_float2(L, __fadd_rn(y, jitter(w.y)));
+            head = make_float2(1.f, 0.f);
+        }
+    }
+    float v0 = S.speed_mean;
+    if (!S.uniform_speed) {
+        const PhiloxOut w2 = philox4x32_10(c0, c1, 0u, kRulesStream | 2u, k0, k1);
+        const double u1 = (double)((w2.x >> 8) + 1u) * 5.9604644775390625e-8, u2 = (double)(w2.y >> 8) * 5.9604644775390625e-8;
+        const float z = (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
+        v0 = __fadd_rn(S.speed_mean, __fmul_rn(S.speed_std, z));
+        if (R.speed_clamp && v0 < S.speed_min) v0 = S.speed_min;
+    }
+    // (a zero heading component stays +0, as torch.zeros_like, also for the crosswalk's v0 <= 0)
+    const float2 vel = R.initial_velocity ? make_float2(head.x != 0.f ? head.x * v0 : 0.f, head.y != 0.f ? head.y * v0 : 0.f)
+                                          : make_float2(0.f, 0.f);
+    const size_t cap = (size_t)S.capacity, i = (size_t)ord;
+    for (int q = lane; q < S.D; q += 64)
+        ((float2*)S.waypoints)[q * cap + i] = q == 0 ? d0 : (q == 1 ? d1 : make_float2(qnan(), qnan()));
+    if (lane == 0) {
+        ((float2*)S.position)[i] = o;
+        ((float2*)S.velocity)[i] = vel;
+        ((float2*)S.acceleration)[i] = make_float2(0.f, 0.f);
+        ((float2*)S.destination)[i] = d0;
+        S.desired_speed[i] = v0;
+        S.flag[i] = 0;
+        S.mask[i] = 1.f;
+        if (S.spawn_iters) S.spawn_iters[i] = 0;
+        if (f < S.T) {
+            const size_t fr = (size_t)f * cap + i;
+            ((float2*)S.position_out)[fr] = o;
+            ((float2*)S.velocity_out)[fr] = vel;
+            ((float2*)S.acceleration_out)[fr] = make_float2(0.f, 0.f);
+            ((float2*)S.destination_out)[fr] = d0;
+            S.mask_out[fr] = 1.f;
+        }
+    }
+    // history: the spawn frame's velocity in the newest slot, older slots 0 (make_dataset on add_pedestrians' zero fill)
+    const int hw = S.hist_width;
+    for (int q = lane; q < hw; q += 64) S.hist_velocity[i * hw + q] = q == hw - 2 ? vel.x : (q == hw - 1 ? vel.y : 0.f);
+    for (int q = 2 + lane; q < S.F; q += 64)
+        S.self_features[i * S.F + q] = q == S.F - 1 ? v0 : (q == hw ? vel.x : (q == hw + 1 ? vel.y : 0.f));
+}
+
+__global__ __launch_bounds__(256) void scenario_rules_kernel(const RulesKernelArgs K) {
+    const piml_scenario& S = K.S;
+    const piml_scenario_rules& R = K.R;
+    const long long t = *S.frame_counter;
+    const long long n = K.init ? 0 : S.spawned[t & 1];
+    const long long f = K.init ? t : t + 1;                  // the frame the new agents appear in
+    if ((int)blockIdx.x < K.agent_blocks) {
+        const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < n && i < S.capacity) rules_agent_step(K, (int)i, t);
+        return;
+    }
+    int k1 = S.n_initial, k2 = 0;
+    if (!K.init) {
+        const PhiloxOut w = philox4x32_10((unsigned)f, (unsigned)((unsigned long long)f >> 32), 0u, kRulesStream,
+                                          (unsigned)S.seed, (unsigned)(S.seed >> 32));
+        k1 = threshold_count(w.x >> 8, S.poisson_thresholds, S.spawn_cap);
+        k2 = threshold_count(w.y >> 8, R.poisson_thresholds2, R.spawn_cap2);
+    }
+    const int k = k1 + k2;
+    if (blockIdx.x == (unsigned)K.agent_blocks && threadIdx.x == 0) {
+        S.spawned[f & 1] = n + k;
+        *S.dropped = n + k > S.capacity ? n + k - S.capacity : 0;
+        if (S.spawn_out && f < S.T) S.spawn_out[f] = k;
+    }
+    const int j = (int)(blockIdx.x - K.agent_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
+    if (j >= k || n + j >= S.capacity) return;               // ordinals past the capacity are dropped, never written
+    rules_spawn_agent(S, R, n + j, j >= k1, f);
+}
+
 }  // namespace piml
 
 PIML_API int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, void* stream) {
@@ -352,5 +584,48 @@ PIML_API int piml_scenario_route(const float* origin, const float* destination, 
     hipLaunchKernelGGL(piml::scenario_route_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, piml::as_stream(stream),
                        (const float2*)origin, (const float2*)destination, n, (const float2*)polyline, R, max_iters, clearance,
                        (float2*)waypoint, iters);
+    return hipGetLastError();
+}
+
+
+PIML_API int piml_scenario_step_rules(const piml_scenario* s, const piml_scenario_rules* r, const float* a_next, int init,
+                                      void* stream) {
+    if (!s || !r) return hipErrorInvalidValue;
+    const piml_scenario& S = *s;
+    const piml_scenario_rules& R = *r;
+    const bool gc_law = R.spawn_law == PIML_SPAWN_GC, gc_rule = R.arrival_rule == PIML_ARRIVE_GC;
+    if (R.spawn_law < PIML_SPAWN_GC || R.spawn_law > PIML_SPAWN_UNIT3 || R.arrival_rule < PIML_ARRIVE_GC ||
+        R.arrival_rule > PIML_ARRIVE_XEXIT || gc_law != gc_rule)
+        return hipErrorInvalidValue;
+    if (gc_law) return piml_scenario_step(s, a_next, init, stream);   // GC: the unchanged kernel
+    if (S.capacity < 1 || S.T < 1 || S.hist_width < 2 || S.F != S.hist_width + 5 || S.D < 1 || S.D > piml::kScenarioMaxD ||
+        (R.spawn_law == PIML_SPAWN_CROSSWALK && S.D < 2) || S.n_initial < 0 || S.n_initial > piml::kScenarioMaxInitial ||
+        S.spawn_cap < 0 || S.spawn_cap > piml::kScenarioMaxSpawn || R.spawn_cap2 < 0 || R.spawn_cap2 > piml::kScenarioMaxSpawn ||
+        (R.spawn_cap2 && R.spawn_law != PIML_SPAWN_UNIT3) || (R.initial_velocity != 0 && R.initial_velocity != 1) ||
+        (R.speed_clamp != 0 && R.speed_clamp != 1) || !(S.dt > 0.f) || (init != 0 && init != 1) || (!init && !a_next))
+        return hipErrorInvalidValue;
+    if (R.spawn_law == PIML_SPAWN_SQUARE &&
+        (R.grid < 1 || R.grid > piml::kRulesMaxGrid || S.n_initial != 4 * R.grid * R.grid))
+        return hipErrorInvalidValue;
+    if (!S.position || !S.velocity || !S.acceleration || !S.destination || !S.hist_velocity || !S.self_features ||
+        !S.desired_speed || !S.flag || !S.mask || !S.waypoints || !S.position_out || !S.velocity_out ||
+        !S.acceleration_out || !S.destination_out || !S.mask_out || !S.frame_counter || !S.spawned || !S.dropped)
+        return hipErrorInvalidValue;
+    for (int j = 0; j < S.spawn_cap; ++j)
+        if (S.poisson_thresholds[j] > (1u << 24) || (j && S.poisson_thresholds[j] < S.poisson_thresholds[j - 1]))
+            return hipErrorInvalidValue;
+    for (int j = 0; j < R.spawn_cap2; ++j)
+        if (R.poisson_thresholds2[j] > (1u << 24) || (j && R.poisson_thresholds2[j] < R.poisson_thresholds2[j - 1]))
+            return hipErrorInvalidValue;
+    piml::RulesKernelArgs K;
+    K.S = S;
+    K.R = R;
+    K.a_next = (const float2*)a_next;
+    K.init = init;
+    K.agent_blocks = init ? 0 : (S.capacity + 255) / 256;
+    const int waves = init ? S.n_initial : S.spawn_cap + R.spawn_cap2;
+    const int spawn_blocks = waves > 0 ? (waves + 3) / 4 : 1;   // >= 1: block agent_blocks writes the spawned count
+    hipLaunchKernelGGL(piml::scenario_rules_kernel, dim3((unsigned)(K.agent_blocks + spawn_blocks)), dim3(256), 0,
+                       piml::as_stream(stream), K);
     return hipGetLastError();
 }

@@ -464,7 +464,8 @@ class BaseSimulator(Pedestrians):
 
     # ---- open-world simulation: the loop the reference stubs (BaseSimulator.run / run_single_step, simulators.py:834-838) ----
     def simulate_scenario(self, scenario, frames, seed=0, capacity=None, use_graph=None):
-        """Simulate `frames` frames of an entry / exit scene (piml_amd.scenarios.Scenario, e.g. gc_scenario()) with the
+        """Simulate `frames` frames of an entry / exit scene (piml_amd.scenarios.Scenario: gc_scenario() or a synthetic scene
+        of piml_amd.scenarios.SCENARIOS, which runs piml_scenario_step_rules) with the
         current model: frame 0 spawns the scenario's initial agents, every further frame is model -> piml_scenario_step
         (integrate, arrive, retire, Poisson arrivals routed around the scenario's polyline, record) -> relative features.
         The frame is captured into one graph and replayed (`use_graph=None`: when more than 8 frames); the Philox draws

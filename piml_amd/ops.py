@@ -1505,6 +1505,9 @@ class _ScaleKSum(torch.autograd.Function):
     def forward(ctx, e, scale, bias, keep_bits):
         e = _gpu_f32('e', e)
         k, cols = e.shape[-2], e.shape[-1]
+        if k == 0:                            # no neighbours (a scene without obstacles): the sum over an empty axis is 0
+            ctx.geom = None
+            return torch.empty_like(e), torch.zeros(*e.shape[:-2], cols, device=e.device, dtype=torch.float32)
         agents = e.numel() // (k * cols)
         msgs = torch.empty_like(e)
         pooled = torch.empty(*e.shape[:-2], cols, device=e.device, dtype=torch.float32)
@@ -1521,10 +1524,10 @@ class _ScaleKSum(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_msgs, g_pooled):
-        agents, k, cols, scale, shape = ctx.geom
         ref = g_pooled if g_pooled is not None else g_msgs
-        if ref is None:
+        if ref is None or ctx.geom is None:   # (an empty neighbour axis has no gradient to carry)
             return None, None, None, None
+        agents, k, cols, scale, shape = ctx.geom
         g_e = torch.empty(shape, device=ref.device, dtype=torch.float32)
         gm = g_msgs.contiguous() if g_msgs is not None else None
         gp = g_pooled.contiguous() if g_pooled is not None else None

@@ -1,4 +1,5 @@
-"""Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_route).
+"""Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_step_rules,
+piml_scenario_route).
 
 `scenario_state` allocates the persistent (static-address) buffers of one simulation and the `piml_scenario` descriptor
 that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive, retire, spawn, record), with the
@@ -94,7 +95,33 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
     for j, x in enumerate(thr):
         s.poisson_thresholds[j] = x
     st.desc = s
+    st.rules = scenario_rules(scenario) if scenario.spawn_law != 'gc' else None
     return st
+
+
+def scenario_rules(scenario):
+    """The piml_scenario_rules descriptor of a scene (its spawn law, arrival rule, velocity and speed laws, second stream)."""
+    r = _lib.ScenarioRules()
+    if scenario.spawn_law not in _lib.SPAWN_LAWS or scenario.arrival_rule not in _lib.ARRIVAL_RULES:
+        raise ValueError(f'unknown scene rule {scenario.spawn_law!r} / {scenario.arrival_rule!r}')
+    r.spawn_law, r.arrival_rule = _lib.SPAWN_LAWS[scenario.spawn_law], _lib.ARRIVAL_RULES[scenario.arrival_rule]
+    r.initial_velocity, r.speed_clamp = int(bool(scenario.initial_velocity)), int(bool(scenario.speed_clamp))
+    r.length, r.width = float(scenario.length), float(scenario.width)
+    r.side_ratio, r.direction_ratio = float(scenario.side_ratio), float(scenario.direction_ratio)
+    thr = scenario.poisson_thresholds2()
+    if len(thr) > 8:
+        raise ValueError(f'spawn_cap2 {len(thr)} > 8')
+    r.spawn_cap2 = len(thr)
+    for j, x in enumerate(thr):
+        r.poisson_thresholds2[j] = x
+    if scenario.square_grid is not None:
+        g = scenario.square_grid.detach().to('cpu', torch.float32).reshape(-1)
+        if g.numel() > 32:
+            raise ValueError(f'square grid of {g.numel()} > 32 cells per side')
+        r.grid = g.numel()
+        for j, x in enumerate(g.tolist()):
+            r.square_grid[j] = x
+    return r
 
 
 def scenario_step(st, a_next=None, init=False):
@@ -105,5 +132,10 @@ def scenario_step(st, a_next=None, init=False):
         if tuple(a_next.shape) != (st.capacity, 2) or a_next.device != st.p.device:
             raise ValueError(f'a_next: ({st.capacity}, 2) on {st.p.device} expected, got {tuple(a_next.shape)} on {a_next.device}')
     with torch.cuda.device(st.p.device):
-        _lib.check(_lib.lib().piml_scenario_step(ctypes.byref(st.desc), _ptr(a_next) if not init else None, int(bool(init)),
-                                                 _stream()), 'piml_scenario_step')
+        if st.rules is None:                                 # GC
+            _lib.check(_lib.lib().piml_scenario_step(ctypes.byref(st.desc), _ptr(a_next) if not init else None,
+                                                     int(bool(init)), _stream()), 'piml_scenario_step')
+        else:
+            _lib.check(_lib.lib().piml_scenario_step_rules(ctypes.byref(st.desc), ctypes.byref(st.rules),
+                                                           _ptr(a_next) if not init else None, int(bool(init)), _stream()),
+                       'piml_scenario_step_rules')

@@ -2,9 +2,11 @@
 
 A `Scenario` is data: entry segments sampled as points (agents appear at and leave through them), the polyline agents are
 routed around, the obstacle points the features see, the arrival process and the desired-speed law.  `gc_scenario()` is the
-reference's Grand Central hall (src/data/scenarios.py:313-401, GC()) tensor for tensor; other entry / exit scenes (the
-crosswalk, basic_unit*) are the same record with other tensors.  The per-frame work -- integration, arrival, retirement,
-Poisson arrivals with routing, recording -- is one HIP launch (piml_scenario_step, piml_amd/csrc/scenario.hip).
+reference's Grand Central hall (src/data/scenarios.py:313-401, GC()) tensor for tensor.  The reference's synthetic scenes
+(scenarios.py:9-311: crosswalk, four_directional_square, basic_unit1..3) are the same record with a scene rule instead of
+entries and a route: a spawn law, an arrival rule, an initial-velocity law, a speed law and an optional second Poisson
+stream (`spawn_law`, `arrival_rule`, ...; piml_scenario_rules).  The per-frame work -- integration, arrival, retirement,
+Poisson arrivals, recording -- is one HIP launch (piml_scenario_step / piml_scenario_step_rules, piml_amd/csrc/scenario.hip).
 
 `save_clip` writes a simulation as the reference's `RawData.save_data` does (src/data/data.py:305-341, version v2.2), so
 that `RawData.load_trajectory_data` -- here and in the reference -- reads it back as a training clip (`--iter_flag`).
@@ -39,6 +41,19 @@ class Scenario:
     route_max_iters: int = 16              # device bound on utils.route's loop
     spawn_cap: int = 8                     # bound of the per-frame Poisson draw (inversion cap)
     name: str = ''
+    # scene rule (piml_scenario_rules); the defaults are GC's
+    spawn_law: str = 'gc'                  # 'gc', 'crosswalk', 'square', 'unit1', 'unit2', 'unit3'
+    arrival_rule: str = 'gc'               # 'gc', 'radius' |p - dest| < r, 'x_band' |p.x - dest.x| < r, 'x_exit' x > length
+    initial_velocity: bool = False         # spawn with velocity heading * v0 (else 0)
+    speed_clamp: bool = True               # v0 = max(speed_min, ...) of a normal draw
+    fixed_spawn_rate: float = None         # arrivals per frame whatever time_unit (the crosswalk's 5 * 0.08)
+    rate2_per_s: float = 0.0               # second Poisson stream (basic_unit3's group 2)
+    spawn_cap2: int = 0
+    length: float = 0.0                    # scene size (the square: block length)
+    width: float = 0.0
+    side_ratio: float = 0.0                # basic_unit2
+    direction_ratio: float = 0.0
+    square_grid: torch.Tensor = None       # the square's (d,) grid coordinates
 
     def to(self, device):
         out = dataclasses.replace(self)
@@ -49,19 +64,33 @@ class Scenario:
     @property
     def spawn_rate(self):
         """Expected arrivals per frame (the reference's 5 * 0.08)."""
+        if self.fixed_spawn_rate is not None:
+            return self.fixed_spawn_rate
         return self.rate_per_s * self.time_unit
+
+    @property
+    def spawn_rate2(self):
+        """Expected arrivals per frame of the second stream."""
+        return self.rate2_per_s * self.time_unit if self.spawn_cap2 else 0.0
 
     def poisson_thresholds(self):
         """ceil(2^24 P(K <= j)), j < spawn_cap, K ~ Poisson(spawn_rate): the spawn count of a frame is the number of these
         its 24-bit uniform reaches (inversion, capped at spawn_cap)."""
-        lam = self.spawn_rate
-        p = math.exp(-lam)
-        cdf, out = p, []
-        for j in range(self.spawn_cap):
-            out.append(min(1 << 24, math.ceil(cdf * (1 << 24))))
-            p *= lam / (j + 1)
-            cdf += p
-        return out
+        return _poisson_thresholds(self.spawn_rate, self.spawn_cap)
+
+    def poisson_thresholds2(self):
+        """The second stream's thresholds (spawn_rate2, spawn_cap2)."""
+        return _poisson_thresholds(self.spawn_rate2, self.spawn_cap2)
+
+
+def _poisson_thresholds(lam, cap):
+    p = math.exp(-lam)
+    cdf, out = p, []
+    for j in range(cap):
+        out.append(min(1 << 24, math.ceil(cdf * (1 << 24))))
+        p *= lam / (j + 1)
+        cdf += p
+    return out
 
 
 def gc_scenario(time_unit=0.08, uniform_desired_speed=False):
@@ -93,14 +122,104 @@ def gc_scenario(time_unit=0.08, uniform_desired_speed=False):
                     time_unit=time_unit, uniform_desired_speed=uniform_desired_speed, name='gc')
 
 
-SCENARIOS = {'gc': gc_scenario}
+def _no_geometry():
+    return torch.zeros(0, 1, 2), torch.zeros(0, 2), torch.zeros(0, 2)
+
+
+def crosswalk_scenario(length=20.0, width=7.0, num_ped1=10, num_ped2=10, time_unit=0.08, uniform_desired_speed=False):
+    """The reference's crosswalk (scenarios.py:9-85): num_ped1 + num_ped2 agents at frame 0 and Poisson arrivals of
+    5 * 0.08 per frame (whatever time_unit: the reference hard-codes it), each on a coin side at |x| = length/2 + 3u,
+    y = +-width/2, walking (0, -+v0) across to (-+length/2, +-width/2 by a coin) and then (same x, 3 y).  v0 = 1.34 +
+    sqrt(0.26) z without a lower clamp; arrival |p - dest| < 1; no obstacles."""
+    entries, poly, obs = _no_geometry()
+    return Scenario(entries=entries, route_polyline=poly, obstacles=obs, time_unit=time_unit,
+                    n_initial=int(num_ped1) + int(num_ped2), uniform_desired_speed=uniform_desired_speed, num_waypoints=2,
+                    spawn_law='crosswalk', arrival_rule='radius', initial_velocity=True, speed_clamp=False,
+                    fixed_spawn_rate=5 * 0.08, length=float(length), width=float(width), name='crosswalk')
+
+
+def square_grid(block_length=20.0, peds_density=5):
+    """The (d,) grid coordinates of four_directional_square (scenarios.py:93-94), float32 as torch computes them."""
+    d = int(peds_density)
+    return torch.arange(1 - d, d + 1, 2) * block_length / 2 / d
+
+
+def square_layout(scenario, perm=None):
+    """(position, destination) (4 d^2, 2) of the square's agents in ordinal order (the four blocks: from the left, the
+    right, below, above), destinations of cell c at cell perm[c] (perm = None: unshuffled)."""
+    g = scenario.square_grid
+    d = g.shape[0]
+    gx, gy = torch.meshgrid(g, g, indexing='ij')
+    gx, gy = gx.reshape(-1), gy.reshape(-1)
+    hx, hy = (gx, gy) if perm is None else (gx[perm], gy[perm])
+    L = scenario.length
+    pos = [(gx - L, gy), (gx + L, gy), (gx, gy - L), (gx, gy + L)]
+    dst = [(hx + L, hy), (hx - L, hy), (hx, hy + L), (hx, hy - L)]
+    cat = lambda xs: torch.cat([torch.stack(x, dim=1) for x in xs], dim=0)
+    assert cat(pos).shape[0] == 4 * d * d
+    return cat(pos), cat(dst)
+
+
+def four_directional_square_scenario(block_length=20.0, peds_density=5, time_unit=0.08, uniform_desired_speed=True):
+    """The reference's four_directional_square (scenarios.py:87-134): 4 d^2 agents at frame 0 on a d x d grid in each of
+    four blocks around the origin, each walking to the opposite block, destinations shuffled by one randperm(d^2) shared
+    by the four blocks; no arrivals; v0 = 1.34 (+ sqrt(0.26) z, no clamp); arrival |p - dest| < 1; obstacles the
+    128-point circle of radius 5.  The reference fixes time_unit at 0.08."""
+    angle = torch.linspace(-torch.pi, +torch.pi, 128)
+    circle = torch.stack((5 * torch.cos(angle), 5 * torch.sin(angle)), dim=1)
+    entries, poly, _ = _no_geometry()
+    d = int(peds_density)
+    return Scenario(entries=entries, route_polyline=poly, obstacles=circle, time_unit=time_unit, n_initial=4 * d * d,
+                    uniform_desired_speed=uniform_desired_speed, num_waypoints=1, spawn_cap=0, spawn_law='square',
+                    arrival_rule='radius', initial_velocity=False, speed_clamp=False, length=float(block_length),
+                    square_grid=square_grid(block_length, d), name='four_directional_square')
+
+
+def _basic_unit(law, rule, radius, length, width, time_unit, poisson_lambda, uniform_desired_speed, name, **kw):
+    entries, poly, obs = _no_geometry()
+    return Scenario(entries=entries, route_polyline=poly, obstacles=obs, rate_per_s=float(poisson_lambda),
+                    time_unit=time_unit, n_initial=1, speed_mean=1.14, speed_var=0.1, speed_min=0.8,
+                    uniform_desired_speed=uniform_desired_speed, arrival_radius=radius, num_waypoints=1, spawn_law=law,
+                    arrival_rule=rule, initial_velocity=True, speed_clamp=True, length=float(length),
+                    width=float(width), name=name, **kw)
+
+
+def basic_unit1_scenario(length=20.0, width=10.0, time_unit=0.08, poisson_lambda=5, during=40, uniform_desired_speed=True):
+    """The reference's basic_unit1 (scenarios.py:137-181): one agent at frame 0 and Poisson(poisson_lambda time_unit)
+    arrivals at (0, width u) walking (v0, 0) to (length, y + 2u - 1); an agent retires when x > length (no arrival flag);
+    v0 = 1.14 (+ sqrt(0.1) z, at least 0.8).  `during` is unused, as in the reference."""
+    return _basic_unit('unit1', 'x_exit', 1.0, length, width, time_unit, poisson_lambda, uniform_desired_speed, 'basic_unit1')
+
+
+def basic_unit2_scenario(length=20.0, width=10.0, time_unit=0.08, poisson_lambda=5, side_ratio=0.3, direction_ratio=0.5,
+                         during=40, uniform_desired_speed=True):
+    """The reference's basic_unit2 (scenarios.py:183-242): basic_unit1's stream, with a fraction side_ratio of the agents
+    in the upper half (y += width/2) and a fraction direction_ratio walking right to left (x = length, y = width - y,
+    destination x = 0); arrival |p.x - dest.x| < 0.05.  `during` is unused."""
+    return _basic_unit('unit2', 'x_band', 0.05, length, width, time_unit, poisson_lambda, uniform_desired_speed, 'basic_unit2',
+                       side_ratio=float(side_ratio), direction_ratio=float(direction_ratio))
+
+
+def basic_unit3_scenario(length=20.0, width=10.0, time_unit=0.08, poisson_lambda=5, poisson_lambda2=1, during=40,
+                         uniform_desired_speed=True):
+    """The reference's basic_unit3 (scenarios.py:244-311): basic_unit1's stream (rate poisson_lambda) plus a second one
+    (rate poisson_lambda2) from (length u, 0) walking (0, v0) to (x + 2u - 1, width); arrival |p - dest| < 1.  A frame's
+    first-stream agents take the lower ordinals.  `during` is unused."""
+    return _basic_unit('unit3', 'radius', 1.0, length, width, time_unit, poisson_lambda, uniform_desired_speed, 'basic_unit3',
+                       rate2_per_s=float(poisson_lambda2), spawn_cap2=8)
+
+
+SCENARIOS = {'gc': gc_scenario, 'crosswalk': crosswalk_scenario, 'four_directional_square': four_directional_square_scenario,
+             'basic_unit1': basic_unit1_scenario, 'basic_unit2': basic_unit2_scenario, 'basic_unit3': basic_unit3_scenario}
 
 
 def default_capacity(scenario, frames, tail=1e-9):
-    """n_initial + the (1 - tail) quantile of Poisson(spawn_rate * (frames - 1)) (at most spawn_cap per frame)."""
+    """n_initial + the (1 - tail) quantile of Poisson((spawn_rate + spawn_rate2) * (frames - 1)) (at most spawn_cap +
+    spawn_cap2 per frame); n_initial for a scene without arrivals."""
     steps = max(int(frames) - 1, 0)
-    mu = scenario.spawn_rate * steps
-    if mu <= 0:
+    cap = scenario.spawn_cap + scenario.spawn_cap2
+    mu = (scenario.spawn_rate * (scenario.spawn_cap > 0) + scenario.spawn_rate2) * steps
+    if mu <= 0 or cap == 0:
         return max(1, scenario.n_initial)
     if mu < 600:
         logp = -mu
@@ -112,7 +231,7 @@ def default_capacity(scenario, frames, tail=1e-9):
         q = k
     else:                                     # normal approximation, 6 sigma
         q = int(math.ceil(mu + 6.0 * math.sqrt(mu)))
-    return max(1, scenario.n_initial + min(q, scenario.spawn_cap * steps))
+    return max(1, scenario.n_initial + min(q, cap * steps))
 
 
 class ScenarioResult(types.SimpleNamespace):
@@ -140,6 +259,7 @@ class ScenarioResult(types.SimpleNamespace):
                       acceleration=self.acceleration[:, :n].detach().cpu(), destination=d, waypoints=w, obstacles=o,
                       mask_p=m, meta_data={'time_unit': float(self.time_unit)})
         raw.num_destinations = w.shape[0]
+        raw.mask_v, raw.mask_a = m.clone(), m.clone()          # add_frame's masks (data.py:241-243)
         return raw
 
     def save_data(self, path):

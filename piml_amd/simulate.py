@@ -1,4 +1,5 @@
-"""Open-world crowd simulation with a trained PINNSF: generate a scene (default: the Grand Central hall), simulate it on
+"""Open-world crowd simulation with a trained PINNSF: generate a scene (default: the Grand Central hall; --scenario crosswalk,
+four_directional_square, basic_unit1..3 for the reference's synthetic scenes), simulate it on
 the GPU and save the result as a v2.2 clip that `RawData.load_trajectory_data` (and so `--iter_flag` pre-training) reads.
 
     python -m piml_amd.simulate --checkpoint model.pt --frames 750 --out clip.npy [model flags of piml_amd.main]
@@ -27,7 +28,8 @@ def get_args(argv=None):
     p.add_argument('--capacity', type=int, default=None, help='agent slots (default: from the arrival rate)')
     p.add_argument('--out', type=str, default='clip.npy')
     p.add_argument('--time_unit', type=float, default=0.08)
-    p.add_argument('--uniform_desired_speed', action='store_true')
+    p.add_argument('--uniform_desired_speed', action=argparse.BooleanOptionalAction, default=None,
+                   help="uniform desired speed (default: the scene's own; GC and the crosswalk no, the others yes)")
     own, rest = p.parse_known_args(argv)
     model_args = MAIN.get_args(rest)
     return own, model_args
@@ -44,7 +46,8 @@ def main(argv=None):
     if own.checkpoint:
         sim.model.load_state_dict(torch.load(own.checkpoint, map_location=args.device))
     sim.model.eval()
-    scenario = SCENARIOS.SCENARIOS[own.scenario](time_unit=own.time_unit, uniform_desired_speed=own.uniform_desired_speed)
+    kw = {} if own.uniform_desired_speed is None else {'uniform_desired_speed': own.uniform_desired_speed}
+    scenario = SCENARIOS.SCENARIOS[own.scenario](time_unit=own.time_unit, **kw)
     res = sim.simulate_scenario(scenario, own.frames, seed=own.seed, capacity=own.capacity)
     n = res.num_agents
     retired = n - int(res.mask_p[-1, :n].sum().item())

@@ -1,8 +1,8 @@
-"""ms per simulated frame of the open-world scenario (BaseSimulator.simulate_scenario on gc_scenario(), one captured frame
-replayed) against the clip rollout's frame (get_multiple_rollouts on the synthetic GC clip of piml_amd.scenes with the
-same obstacle points) at the same N = capacity, pinnsf_m in eval mode.  Per-frame cost = the difference of two runs of
+"""ms per simulated frame of the open-world scenario (BaseSimulator.simulate_scenario on a scene of
+piml_amd.scenarios.SCENARIOS, default gc, one captured frame replayed) at N = capacity, pinnsf_m in eval mode; for GC against
+the clip rollout's frame (get_multiple_rollouts on the synthetic GC clip of piml_amd.scenes with the same obstacle points).  Per-frame cost = the difference of two runs of
 different lengths (set-up, warm-up and capture cancel), median of --reps alternated pairs.
-Prints one JSON object.  Usage: python tools/time_scenario.py [--caps 256 1024 4096] [--reps 5]
+Prints one JSON object.  Usage: python tools/time_scenario.py [--scenario NAME] [--caps 256 1024 4096] [--reps 5]
 Kernel list of a frame: rocprofv3 --kernel-trace --stats -d <dir> -- python tools/time_scenario.py --caps 1024 --reps 1"""
 import argparse
 import json
@@ -29,6 +29,7 @@ def timed(fn):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--scenario', type=str, default='gc')
     ap.add_argument('--caps', type=int, nargs='+', default=[256, 1024, 4096])
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--short', type=int, default=40)
@@ -36,17 +37,18 @@ def main():
     a = ap.parse_args()
     from test_simulator_gpu import sim_args
     from piml_amd.models.simulators import BaseSimulator
-    from piml_amd.scenarios import gc_scenario
+    from piml_amd.scenarios import SCENARIOS
     from piml_amd.scenes import synthetic_rollout_data
     torch.manual_seed(0)
     sim = BaseSimulator(sim_args())
     sim.model.eval()
-    sc = gc_scenario().to('cuda:0')
+    sc = SCENARIOS[a.scenario]().to('cuda:0')
+    gc = a.scenario == 'gc'
     M = sc.obstacles.shape[0]
-    res = {'frames': [a.short, a.long], 'reps': a.reps, 'obstacles': M, 'scenario_ms_per_frame': {}, 'rollout_ms_per_frame': {},
+    res = {'scenario': a.scenario, 'frames': [a.short, a.long], 'reps': a.reps, 'obstacles': M, 'scenario_ms_per_frame': {}, 'rollout_ms_per_frame': {},
            'ratio': {}, 'agents_present_last_frame': {}}
     for cap in a.caps:
-        clips = {T: synthetic_rollout_data(cap, M, T, 'cuda:0', seed=1) for T in (a.short, a.long)}
+        clips = {T: synthetic_rollout_data(cap, M, T, 'cuda:0', seed=1) for T in (a.short, a.long)} if gc else None
 
         def scen(T):
             return timed(lambda: sim.simulate_scenario(sc, T, seed=1, capacity=cap))
@@ -55,16 +57,18 @@ def main():
             return timed(lambda: sim.get_multiple_rollouts(clips[T], t_start=0, load_model=False))
 
         with torch.no_grad():
-            scen(a.short), roll(a.short)                     # warm-up
+            scen(a.short), gc and roll(a.short)              # warm-up
             s, r = [], []
             for _ in range(a.reps):                          # alternated: the host is shared
                 s.append((scen(a.long) - scen(a.short)) / (a.long - a.short))
-                r.append((roll(a.long) - roll(a.short)) / (a.long - a.short))
+                if gc:
+                    r.append((roll(a.long) - roll(a.short)) / (a.long - a.short))
             last = sim.simulate_scenario(sc, a.long, seed=1, capacity=cap)
         med = lambda x: sorted(x)[len(x) // 2]
         res['scenario_ms_per_frame'][cap] = round(med(s), 4)
-        res['rollout_ms_per_frame'][cap] = round(med(r), 4)
-        res['ratio'][cap] = round(med(s) / med(r), 3)
+        if gc:
+            res['rollout_ms_per_frame'][cap] = round(med(r), 4)
+            res['ratio'][cap] = round(med(s) / med(r), 3)
         res['agents_present_last_frame'][cap] = int(last.mask_p[-1].sum().item())
     print(json.dumps(res))
 
