@@ -232,6 +232,27 @@ int piml_mlapm_step_bwd_ws(const float* g_action, const float* position, const f
                            float* g_destination, float* workspace, long long workspace_floats, void* stream);
 
 /*
+ * Calibration of MLAPM's constants to a clip: loss and parameter gradient in one pass (mlapm_fit.hip).
+ *   The clip is packed frame-major: entry e (E of them) is one agent present in one frame, state (E, 4) = (p, v),
+ *   destination (E, 2), desired_speed (E), target (E, 2) (normally v of the next frame; NaN = no target).
+ *   offsets (F + 1) int32: frame f holds entries [offsets[f], offsets[f + 1]), which are also its only sources;
+ *   frame_of (E) int32.  small_focal (n_small) / big_focal (n_big): the entries with a target, of frames with
+ *   <= 64 / > 64 entries (a lane / a wave per focal entry).  params (6) on the device = (tau, A, B, C, D, theta_deg).
+ *   For every focal entry, pred = MLAPM.step of its frame (piml_mlapm_step_fwd's variants and arithmetic), and
+ *   loss (1, float64) = sum |pred - target|^2 / focal count (0 without focal entries), grad (6, float32) = d loss / d params
+ *   (view, rotation sign and the UCY flag are constant; constants a variant does not use get exactly 0).
+ *   workspace: piml_mlapm_fit_workspace_doubles(n_small, n_big) float64 (-1 for negative counts).  Deterministic (no
+ *   atomics, fixed-order float64 sums).  hipErrorInvalidValue before any launch for negative sizes,
+ *   n_small + n_big > E, a variant outside 0..2, non-finite dt / radius, a NULL buffer that is needed, or a small workspace.
+ */
+long long piml_mlapm_fit_workspace_doubles(int n_small, int n_big);
+int piml_mlapm_fit_loss_grad(const float* state, const float* destination, const float* desired_speed,
+                             const float* target, const int* offsets, const int* frame_of, int E, int F,
+                             const int* small_focal, int n_small, const int* big_focal, int n_big,
+                             const float* params, int variant, float dt, float radius, double* workspace,
+                             long long workspace_doubles, double* loss, float* grad, void* stream);
+
+/*
  * Collision matrix, pair part of Pedestrians.collision_detection (src/data/data.py:549-564):
  * coll (S, N, N) = [|p_j - p_i| < threshold] (- I when minus_identity), NaN -> 0; S slices.
  * With minus_identity = 0 it is the `real_position` matrix of data.py:576-581.

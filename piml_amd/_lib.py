@@ -96,6 +96,8 @@ SIGNATURES = {
     'piml_mlapm_rollout_step': [_p, _p, _p, _p, _ll, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _p, _p, _p],
     'piml_mlapm_bwd_workspace_floats': [_i, _i],
     'piml_mlapm_step_bwd_ws': [_p, _p, _p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, _ll, _p],
+    'piml_mlapm_fit_workspace_doubles': [_i, _i],
+    'piml_mlapm_fit_loss_grad': [_p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _p, _i, _p, _i, _f, _f, _p, _ll, _p, _p, _p],
     'piml_collision_matrix': [_p, _i, _i, _f, _i, _p, _p],
     'piml_collision_friends': [_p, _p, _i, _i, _i, _i, _p],
     'piml_collision_counts': [_p, _i, _i, _p, _i, _p, _p],
@@ -266,6 +268,7 @@ def lib():
         L.piml_encoder_split_tiles.restype = _ll
         L.piml_encoder_split_tiles_train.restype = _ll
         L.piml_mlapm_bwd_workspace_floats.restype = _ll
+        L.piml_mlapm_fit_workspace_doubles.restype = _ll
         L.piml_error_string.argtypes = [_i]
         L.piml_error_string.restype = ctypes.c_char_p
         if L.piml_abi_version() != ABI_VERSION:

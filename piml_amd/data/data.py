@@ -20,6 +20,20 @@ def _tensor_attrs_to(obj, device):
             setattr(obj, k, v.to(device))
 
 
+def desired_speed_per_agent(velocity, skip_frames):
+    """Desired speed (N) of every agent of a (T, N, 2) velocity series: the mean |v| over the first `skip_frames` frames
+    after the agent starts moving (the first frame with |v| > 0), 0 for an agent that never moves.  The rule of
+    TimeIndexedPedData.make_dataset (absent agents hold velocity 0, as RawData.load_trajectory_data leaves them)."""
+    T = velocity.shape[0]
+    speed = torch.norm(velocity, p=2, dim=-1)                                # t, n
+    moving = speed > 0
+    ar = torch.arange(T, device=velocity.device).unsqueeze(1)
+    start = torch.where(moving, ar, T).min(0).values
+    start = torch.where(moving.any(0), start, torch.zeros_like(start))
+    win = (ar >= start.unsqueeze(0)) & (ar < (start + skip_frames).unsqueeze(0))
+    return (speed * win).sum(0) / win.sum(0).clamp(min=1)
+
+
 class RawData(object):
     """One scene clip (data.py:14-341).  position / velocity / acceleration / destination (T,N,2),
     waypoints (D,N,2), dest_idx (T,N), dest_num (N), obstacles (M,2), mask_p / mask_v / mask_a (T,N)."""
@@ -176,15 +190,7 @@ class TimeIndexedPedData(Pedestrians):
             hist[lag:, :, i, :] = vel[:T - lag]
         hist = hist.reshape(T, N, -1)
 
-        # desired speed = mean |v| over the first skip_frames frames after the agent starts moving
-        speed = torch.norm(vel, p=2, dim=-1)                                   # t, n
-        moving = speed > 0
-        ar = torch.arange(T, device=vel.device).unsqueeze(1)
-        start = torch.where(moving, ar, T).min(0).values
-        start = torch.where(moving.any(0), start, torch.zeros_like(start))
-        win = (ar >= start.unsqueeze(0)) & (ar < (start + args.skip_frames).unsqueeze(0))
-        desired = (speed * win).sum(0) / win.sum(0).clamp(min=1)
-        desired_speed = desired.reshape(1, N, 1).repeat(T, 1, 1)
+        desired_speed = desired_speed_per_agent(vel, args.skip_frames).reshape(1, N, 1).repeat(T, 1, 1)
 
         self.self_features = torch.cat((dest_features, hist, raw_data.acceleration, desired_speed), dim=-1)
         labels = torch.cat((raw_data.position, raw_data.velocity, raw_data.acceleration), dim=-1)

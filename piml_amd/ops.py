@@ -576,6 +576,41 @@ def mlapm_rollout_step(traj_position, traj_velocity, desired_speed, destination,
                                                       _ptr(done_counter), _stream()), 'piml_mlapm_rollout_step')
 
 
+def mlapm_fit_loss_grad(pack, params, version='GC', dt=0.08, radius=0.3, loss=None, grad=None):
+    """Loss and gradient of MLAPM's constants on a packed clip (piml_mlapm_fit_loss_grad; `pack` from
+    `piml_amd.calibrate.pack_clip`): loss = mean over the entries with a target of |MLAPM.step(frame)_i - target_i|^2,
+    grad = d loss / d params.  params: float32 (6,) on the device = (tau, A, B, C, D, theta_deg), read by the kernel from
+    device memory (a fit iteration can be captured).  Returns (loss float64 (1,), grad float32 (6,)) on the device, written
+    into `loss` / `grad` when given; never synchronises.  Deterministic: two calls give bitwise equal results."""
+    if version not in MLAPM_VARIANTS:
+        raise NotImplementedError(version)
+    prm = _gpu_f32('params', params)
+    if prm.numel() != 6:
+        raise ValueError(f'params must hold 6 values (tau, A, B, C, D, theta), got {tuple(params.shape)}')
+    if not pack.state.is_cuda or pack.state.device != prm.device:
+        raise _lib.PimlHipError('mlapm_fit_loss_grad: the pack and params must be on the same GPU (pack_clip(device=...))')
+    dev = prm.device
+    if loss is None:
+        loss = torch.empty(1, device=dev, dtype=torch.float64)
+    if grad is None:
+        grad = torch.empty(6, device=dev, dtype=torch.float32)
+    if loss.dtype != torch.float64 or grad.dtype != torch.float32 or loss.numel() != 1 or grad.numel() != 6:
+        raise ValueError('loss: float64 (1,), grad: float32 (6,)')
+    L = _lib.lib()
+    n_small, n_big = int(pack.small_focal.numel()), int(pack.big_focal.numel())
+    ws = getattr(pack, 'workspace', None)
+    need = int(L.piml_mlapm_fit_workspace_doubles(n_small, n_big))
+    if ws is None or ws.numel() < need or ws.device != dev:
+        ws = pack.workspace = torch.empty(max(need, 1), device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(L.piml_mlapm_fit_loss_grad(_ptr(pack.state), _ptr(pack.destination), _ptr(pack.desired_speed),
+                                              _ptr(pack.target), _ptr(pack.offsets), _ptr(pack.frame_of),
+                                              int(pack.state.shape[0]), int(pack.offsets.numel()) - 1,
+                                              _ptr(pack.small_focal), n_small, _ptr(pack.big_focal), n_big, _ptr(prm),
+                                              MLAPM_VARIANTS[version], float(dt), float(radius), _ptr(ws), ws.numel(),
+                                              _ptr(loss), _ptr(grad), _stream()), 'piml_mlapm_fit_loss_grad')
+    return loss, grad
+
 # ------------------------------------------------------------------------------------------
 # collisions (Pedestrians.collision_detection / calculate_collision_label)
 # ------------------------------------------------------------------------------------------
