@@ -569,6 +569,22 @@ int piml_scenario_step_rules(const piml_scenario* s, const piml_scenario_rules* 
                              void* stream);
 
 /*
+ * Ensembles (ABI 35, additive): `members` simulations of one scene, one frame of each in one launch (grid.y = member).
+ * s's per-member pointers are the bases of member-major buffers whose member-m slice has exactly the single-scene layout:
+ * state (members, capacity, .) -- position, velocity, acceleration, destination, hist_velocity, self_features,
+ * desired_speed, mask, flag, spawn_iters --, waypoints (members, D, capacity, 2), exit_idx (members, D, capacity),
+ * the recorded outputs (members, T, capacity, .), spawn_out (members, T), spawned (members, 2), dropped (members);
+ * a_next (members, capacity, 2).  frame_counter, entries, route_polyline, both threshold tables and every scalar are
+ * shared.  s->seed is ignored: member m's Philox key is seeds[m] (device memory, (members)).  r = NULL is GC's rule
+ * (piml_scenario_step); otherwise as piml_scenario_step_rules.  Member m is bitwise what piml_scenario_step[_rules]
+ * gives with seed = seeds[m]; no atomics, the parity ping-pong is per member; capturable as the single entries.
+ * hipErrorInvalidValue (before any launch): every check of piml_scenario_step / piml_scenario_step_rules, members
+ * outside 1..65535, NULL seeds.
+ */
+int piml_scenario_step_members(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                               const float* a_next, int init, void* stream);
+
+/*
  * utils.route (src/utils/utils.py:141-165) for n (o, d) pairs, one wave each, the device function the spawn path uses:
  * the segment o -> r is tested against the polyline's R-1 segments, the hit with the smallest alpha moves r to
  * crossing + clearance * normal, until nothing is hit or max_iters moves were made.  float32 in the reference's order.

@@ -114,6 +114,7 @@ SIGNATURES = {
                                _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p],
     'piml_scenario_step': [_p, _p, _i, _p],
     'piml_scenario_step_rules': [_p, _p, _p, _i, _p],
+    'piml_scenario_step_members': [_p, _p, _i, _p, _p, _i, _p],
     'piml_scenario_route': [_p, _p, _i, _p, _i, _i, _f, _p, _p, _p],
     'piml_collision_correction_fwd': [_p, _p, _p, _z, _i, _i, _f, _f, _p, _p],
     'piml_collision_correction_bwd': [_p, _p, _p, _p, _z, _i, _i, _f, _f, _p, _p, _p, _p],

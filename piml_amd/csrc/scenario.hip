@@ -546,6 +546,121 @@ __global__ __launch_bounds__(256) void scenario_rules_kernel(const RulesKernelAr
     rules_spawn_agent(S, R, n + j, j >= k1, f);
 }
 
+
+// ---- ensembles (piml_scenario_step_members): `members` simulations of one scene in one launch, grid.y = member ----
+//
+// Layout: the descriptor's per-member pointers are the bases of member-major buffers, member m's slice of each having
+// exactly the single-scene layout -- state (members, capacity, .), waypoints (members, D, capacity, 2), exit_idx
+// (members, D, capacity), recorded outputs (members, T, capacity, .), spawn_out (members, T), spawned (members, 2),
+// dropped (members), a_next (members, capacity, 2).  frame_counter, entries, route_polyline, both threshold tables and
+// every scalar are shared; S.seed is ignored and member m's Philox key is seeds[m].
+// A block builds member blockIdx.y's view (member_view) and runs the single-scene kernels' frame on it through the same
+// device functions (agent_step / spawn_agent, rules_agent_step / rules_spawn_agent, whose square rank count is per member
+// too), so member m is bitwise what piml_scenario_step[_rules] gives with seed = seeds[m].
+// Determinism: still no atomics; the parity ping-pong is per member (member m's spawned[m][t & 1] read, [(t+1) & 1]
+// written by its own block agent_blocks), and no block touches another member's slices.
+// Capture: the frame counter and the seeds are read on the device, so one captured launch serves every frame.
+
+__device__ __forceinline__ void member_view(piml_scenario& S, const float2*& a_next, int m, unsigned long long seed) {
+    const size_t mm = (size_t)m, cap = (size_t)S.capacity, T = (size_t)S.T, D = (size_t)S.D;
+    S.position += mm * cap * 2;
+    S.velocity += mm * cap * 2;
+    S.acceleration += mm * cap * 2;
+    S.destination += mm * cap * 2;
+    S.hist_velocity += mm * cap * (size_t)S.hist_width;
+    S.self_features += mm * cap * (size_t)S.F;
+    S.desired_speed += mm * cap;
+    S.mask += mm * cap;
+    S.flag += mm * cap;
+    S.waypoints += mm * D * cap * 2;
+    if (S.exit_idx) S.exit_idx += mm * D * cap;
+    if (S.spawn_iters) S.spawn_iters += mm * cap;
+    S.position_out += mm * T * cap * 2;
+    S.velocity_out += mm * T * cap * 2;
+    S.acceleration_out += mm * T * cap * 2;
+    S.destination_out += mm * T * cap * 2;
+    S.mask_out += mm * T * cap;
+    if (S.spawn_out) S.spawn_out += mm * T;
+    S.spawned += mm * 2;
+    S.dropped += mm;
+    S.seed = seed;
+    if (a_next) a_next += mm * cap;
+}
+
+__global__ __launch_bounds__(256) void scenario_step_members_kernel(const ScenarioKernelArgs K0,
+                                                                    const unsigned long long* __restrict__ seeds) {
+    __shared__ float2 lds_entries[kScenarioLdsPoints];
+    ScenarioKernelArgs K = K0;
+    member_view(K.S, K.a_next, (int)blockIdx.y, seeds[blockIdx.y]);
+    const piml_scenario& S = K.S;
+    const float2* ent = (const float2*)S.entries;
+    const bool lds = S.E * S.P <= kScenarioLdsPoints;
+    if (lds) {
+        for (int q = threadIdx.x; q < S.E * S.P; q += blockDim.x) lds_entries[q] = ent[q];
+        __syncthreads();
+        ent = lds_entries;
+    }
+    const long long t = *S.frame_counter;
+    const long long n = K.init ? 0 : S.spawned[t & 1];
+    const long long f = K.init ? t : t + 1;
+    if ((int)blockIdx.x < K.agent_blocks) {
+        const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < n && i < S.capacity) {
+            if (lds) agent_step(K, lds_entries, (int)i, t);
+            else agent_step(K, (const float2*)S.entries, (int)i, t);
+        }
+        return;
+    }
+    // poisson_count with the member's key and the thresholds of the kernel arguments (an indexed read of the local
+    // copy's table would put the whole descriptor in scratch)
+    int k = S.n_initial;
+    if (!K.init) {
+        const PhiloxOut w = philox4x32_10((unsigned)f, (unsigned)((unsigned long long)f >> 32), 0u, kScenarioStream,
+                                          (unsigned)S.seed, (unsigned)(S.seed >> 32));
+        k = threshold_count(w.x >> 8, K0.S.poisson_thresholds, S.spawn_cap);
+    }
+    if (blockIdx.x == (unsigned)K.agent_blocks && threadIdx.x == 0) {
+        S.spawned[f & 1] = n + k;
+        *S.dropped = n + k > S.capacity ? n + k - S.capacity : 0;
+        if (S.spawn_out && f < S.T) S.spawn_out[f] = k;
+    }
+    const int j = (int)(blockIdx.x - K.agent_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
+    if (j >= k || n + j >= S.capacity) return;
+    spawn_agent(S, ent, n + j, f);
+}
+
+__global__ __launch_bounds__(256) void scenario_rules_members_kernel(const RulesKernelArgs K0,
+                                                                     const unsigned long long* __restrict__ seeds) {
+    RulesKernelArgs K = K0;
+    member_view(K.S, K.a_next, (int)blockIdx.y, seeds[blockIdx.y]);
+    const piml_scenario& S = K.S;
+    const piml_scenario_rules& R = K0.R;
+    const long long t = *S.frame_counter;
+    const long long n = K.init ? 0 : S.spawned[t & 1];
+    const long long f = K.init ? t : t + 1;
+    if ((int)blockIdx.x < K.agent_blocks) {
+        const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < n && i < S.capacity) rules_agent_step(K, (int)i, t);
+        return;
+    }
+    int k1 = S.n_initial, k2 = 0;
+    if (!K.init) {
+        const PhiloxOut w = philox4x32_10((unsigned)f, (unsigned)((unsigned long long)f >> 32), 0u, kRulesStream,
+                                          (unsigned)S.seed, (unsigned)(S.seed >> 32));
+        k1 = threshold_count(w.x >> 8, K0.S.poisson_thresholds, S.spawn_cap);
+        k2 = threshold_count(w.y >> 8, R.poisson_thresholds2, R.spawn_cap2);
+    }
+    const int k = k1 + k2;
+    if (blockIdx.x == (unsigned)K.agent_blocks && threadIdx.x == 0) {
+        S.spawned[f & 1] = n + k;
+        *S.dropped = n + k > S.capacity ? n + k - S.capacity : 0;
+        if (S.spawn_out && f < S.T) S.spawn_out[f] = k;
+    }
+    const int j = (int)(blockIdx.x - K.agent_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
+    if (j >= k || n + j >= S.capacity) return;
+    rules_spawn_agent(S, R, n + j, j >= k1, f);
+}
+
 }  // namespace piml
 
 PIML_API int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, void* stream) {
@@ -627,5 +742,84 @@ PIML_API int piml_scenario_step_rules(const piml_scenario* s, const piml_scenari
     const int spawn_blocks = waves > 0 ? (waves + 3) / 4 : 1;   // >= 1: block agent_blocks writes the spawned count
     hipLaunchKernelGGL(piml::scenario_rules_kernel, dim3((unsigned)(K.agent_blocks + spawn_blocks)), dim3(256), 0,
                        piml::as_stream(stream), K);
+    return hipGetLastError();
+}
+
+
+namespace {
+
+// the argument checks of piml_scenario_step (GC) and piml_scenario_step_rules (the other laws), for the member entry
+bool gc_args_ok(const piml_scenario& S, const float* a_next, int init) {
+    if (S.capacity < 1 || S.T < 1 || S.hist_width < 2 || S.F != S.hist_width + 5 || S.D < 2 || S.D > piml::kScenarioMaxD ||
+        S.E < 2 || S.P < 1 || S.R < 2 || S.n_initial < 0 || S.n_initial > piml::kScenarioMaxInitial ||
+        S.route_max_iters < 0 || S.route_max_iters > piml::kScenarioMaxIters || S.spawn_cap < 0 ||
+        S.spawn_cap > piml::kScenarioMaxSpawn || !(S.dt > 0.f) || (init != 0 && init != 1) || (!init && !a_next))
+        return false;
+    if (!S.position || !S.velocity || !S.acceleration || !S.destination || !S.hist_velocity || !S.self_features ||
+        !S.desired_speed || !S.flag || !S.mask || !S.waypoints || !S.exit_idx || !S.position_out || !S.velocity_out ||
+        !S.acceleration_out || !S.destination_out || !S.mask_out || !S.frame_counter || !S.spawned || !S.dropped ||
+        !S.entries || !S.route_polyline)
+        return false;
+    for (int j = 0; j < S.spawn_cap; ++j)
+        if (S.poisson_thresholds[j] > (1u << 24) || (j && S.poisson_thresholds[j] < S.poisson_thresholds[j - 1])) return false;
+    return true;
+}
+
+bool rules_args_ok(const piml_scenario& S, const piml_scenario_rules& R, const float* a_next, int init) {
+    if (S.capacity < 1 || S.T < 1 || S.hist_width < 2 || S.F != S.hist_width + 5 || S.D < 1 || S.D > piml::kScenarioMaxD ||
+        (R.spawn_law == PIML_SPAWN_CROSSWALK && S.D < 2) || S.n_initial < 0 || S.n_initial > piml::kScenarioMaxInitial ||
+        S.spawn_cap < 0 || S.spawn_cap > piml::kScenarioMaxSpawn || R.spawn_cap2 < 0 || R.spawn_cap2 > piml::kScenarioMaxSpawn ||
+        (R.spawn_cap2 && R.spawn_law != PIML_SPAWN_UNIT3) || (R.initial_velocity != 0 && R.initial_velocity != 1) ||
+        (R.speed_clamp != 0 && R.speed_clamp != 1) || !(S.dt > 0.f) || (init != 0 && init != 1) || (!init && !a_next))
+        return false;
+    if (R.spawn_law == PIML_SPAWN_SQUARE && (R.grid < 1 || R.grid > piml::kRulesMaxGrid || S.n_initial != 4 * R.grid * R.grid))
+        return false;
+    if (!S.position || !S.velocity || !S.acceleration || !S.destination || !S.hist_velocity || !S.self_features ||
+        !S.desired_speed || !S.flag || !S.mask || !S.waypoints || !S.position_out || !S.velocity_out ||
+        !S.acceleration_out || !S.destination_out || !S.mask_out || !S.frame_counter || !S.spawned || !S.dropped)
+        return false;
+    for (int j = 0; j < S.spawn_cap; ++j)
+        if (S.poisson_thresholds[j] > (1u << 24) || (j && S.poisson_thresholds[j] < S.poisson_thresholds[j - 1])) return false;
+    for (int j = 0; j < R.spawn_cap2; ++j)
+        if (R.poisson_thresholds2[j] > (1u << 24) || (j && R.poisson_thresholds2[j] < R.poisson_thresholds2[j - 1]))
+            return false;
+    return true;
+}
+
+}  // namespace
+
+PIML_API int piml_scenario_step_members(const piml_scenario* s, const piml_scenario_rules* r, int members,
+                                        const uint64_t* seeds, const float* a_next, int init, void* stream) {
+    if (!s || !seeds || members < 1 || members > 65535) return hipErrorInvalidValue;
+    const piml_scenario& S = *s;
+    const bool gc = !r || r->spawn_law == PIML_SPAWN_GC;
+    if (r) {
+        const bool gc_rule = r->arrival_rule == PIML_ARRIVE_GC;
+        if (r->spawn_law < PIML_SPAWN_GC || r->spawn_law > PIML_SPAWN_UNIT3 || r->arrival_rule < PIML_ARRIVE_GC ||
+            r->arrival_rule > PIML_ARRIVE_XEXIT || gc != gc_rule)
+            return hipErrorInvalidValue;
+    }
+    if (gc ? !gc_args_ok(S, a_next, init) : !rules_args_ok(S, *r, a_next, init)) return hipErrorInvalidValue;
+    const int agent_blocks = init ? 0 : (S.capacity + 255) / 256;
+    const int waves = init ? S.n_initial : S.spawn_cap + (gc ? 0 : r->spawn_cap2);
+    const int spawn_blocks = waves > 0 ? (waves + 3) / 4 : 1;   // >= 1: block agent_blocks writes each member's count
+    const dim3 grid((unsigned)(agent_blocks + spawn_blocks), (unsigned)members);
+    const unsigned long long* sd = (const unsigned long long*)seeds;
+    if (gc) {
+        piml::ScenarioKernelArgs K;
+        K.S = S;
+        K.a_next = (const float2*)a_next;
+        K.init = init;
+        K.agent_blocks = agent_blocks;
+        hipLaunchKernelGGL(piml::scenario_step_members_kernel, grid, dim3(256), 0, piml::as_stream(stream), K, sd);
+    } else {
+        piml::RulesKernelArgs K;
+        K.S = S;
+        K.R = *r;
+        K.a_next = (const float2*)a_next;
+        K.init = init;
+        K.agent_blocks = agent_blocks;
+        hipLaunchKernelGGL(piml::scenario_rules_members_kernel, grid, dim3(256), 0, piml::as_stream(stream), K, sd);
+    }
     return hipGetLastError();
 }

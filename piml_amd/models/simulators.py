@@ -471,6 +471,20 @@ class BaseSimulator(Pedestrians):
         The frame is captured into one graph and replayed (`use_graph=None`: when more than 8 frames); the Philox draws
         make the spawn schedule a function of (seed, frame, ordinal).  `capacity` = agent slots (default: n_initial + a
         1e-9 upper quantile of the arrivals); agents past it are dropped and counted.  Returns a ScenarioResult."""
+        return self._in_scenario_mode(lambda: self._simulate_scenario(scenario, frames, seed, capacity, use_graph))
+
+    def simulate_ensemble(self, scenario, frames, seeds, capacity=None, use_graph=None):
+        """`simulate_scenario` for every seed of `seeds` at once: S = len(seeds) simulations of one scene with one capacity
+        (default: as simulate_scenario's, which does not depend on the seed), every frame of all of them one network
+        forward over the S * capacity rows, one piml_scenario_step_members launch and one relative-feature launch
+        (captured and replayed as simulate_scenario's frame).  Member m is the simulation of seed seeds[m]: the network
+        sees flat (S * capacity, .) rows, so members never see each other.  Returns a scenarios.ScenarioEnsemble."""
+        seeds = [int(x) for x in seeds]
+        if not seeds:
+            raise ValueError('simulate_ensemble: at least one seed expected')
+        return self._in_scenario_mode(lambda: self._simulate_ensemble(scenario, frames, seeds, capacity, use_graph))
+
+    def _in_scenario_mode(self, run):
         only = hasattr(self.model, 'predictions_only')
         before = getattr(self.model, 'predictions_only', False)
         with torch.no_grad():
@@ -478,28 +492,63 @@ class BaseSimulator(Pedestrians):
                 self.model.predictions_only = True
             try:
                 with self._packed_weights():
-                    return self._simulate_scenario(scenario, frames, seed, capacity, use_graph)
+                    return run()
             finally:
                 if only:
                     self.model.predictions_only = before
 
-    def _simulate_scenario(self, scenario, frames, seed, capacity, use_graph):
-        from .. import ops_scenario, scenarios, hip_graphs_safe
+    def _scenario_setup(self, scenario, frames, capacity, **state_kw):
+        from .. import ops_scenario, scenarios
         a = self.args
         sc = scenario.to(torch.device(a.device))
         T = int(frames)
         if T < 1:
             raise ValueError(f'frames must be >= 1, got {frames}')
         cap = scenarios.default_capacity(sc, T) if capacity is None else int(capacity)
-        st = ops_scenario.scenario_state(sc, cap, T, 2 * int(a.num_history_velocity), seed, a.topk_ped, a.topk_obs)
+        st = ops_scenario.scenario_state(sc, cap, T, 2 * int(a.num_history_velocity), topk_ped=a.topk_ped,
+                                         topk_obs=a.topk_obs, **state_kw)
+        return sc, T, cap, st
+
+    def _simulate_scenario(self, scenario, frames, seed, capacity, use_graph):
+        from .. import scenarios
+        sc, T, cap, st = self._scenario_setup(scenario, frames, capacity, seed=seed)
+        self._run_scenario(sc, T, st, (st.pf, st.of, st.selff), use_graph)
+        last = int(st.t.item())
+        return scenarios.ScenarioResult(
+            position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res, mask_p=st.mask_res,
+            waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles, time_unit=sc.time_unit,
+            spawned=int(st.spawned[last & 1].item()), dropped=int(st.dropped.item()), spawn_count=st.spawn_count,
+            capacity=cap, seed=int(seed), state=st)
+
+    def _simulate_ensemble(self, scenario, frames, seeds, capacity, use_graph):
+        from .. import scenarios
+        sc, T, cap, st = self._scenario_setup(scenario, frames, capacity, seeds=seeds)
+        rows = len(seeds) * cap
+        # flat 2-D rows: on a 3-D (S, cap, .) batch the model would normalise the desired force over the agent axis
+        #  and couple the members
+        inputs = (st.pf.view(rows, *st.pf.shape[2:]), st.of.view(rows, *st.of.shape[2:]), st.selff.view(rows, st.selff.shape[-1]))
+        self._run_scenario(sc, T, st, inputs, use_graph)
+        last = int(st.t.item())
+        spawned = st.spawned[:, last & 1].tolist()
+        return scenarios.ScenarioEnsemble(
+            seeds=seeds, position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res,
+            mask_p=st.mask_res, waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles,
+            time_unit=sc.time_unit, spawned=spawned, dropped=st.dropped.tolist(), spawn_count=st.spawn_count,
+            capacity=cap, state=st)
+
+    def _run_scenario(self, sc, T, st, inputs, use_graph):
+        """frame 0's spawn and features, then T - 1 frames of model(inputs) -> scenario_step -> relative features (the
+        model's rows `inputs` are views of st's feature buffers), captured and replayed when use_graph."""
+        from .. import ops_scenario, hip_graphs_safe
+        a = self.args
         feats = (st.pf, st.of, st.selff, st.ped_idx, st.obs_idx)
         geo = (a.topk_ped, a.sight_angle_ped, a.dist_threshold_ped, a.topk_obs, a.sight_angle_obs, a.dist_threshold_obs)
         ops_scenario.scenario_step(st, init=True)                                         # frame 0: generate(n_initial)
         ops.relative_features_into(feats, st.p, st.v, st.a, st.dest, sc.obstacles, *geo)
 
         def step():
-            a_next = self.model(st.pf, st.of, st.selff)[0]
-            ops_scenario.scenario_step(st, a_next.contiguous())
+            a_next = self.model(*inputs)[0]
+            ops_scenario.scenario_step(st, a_next.reshape(st.p.shape).contiguous())
             ops.relative_features_into(feats, st.p, st.v, st.a, st.dest, sc.obstacles, *geo, tick=st.t)   # + st.t += 1
 
         steps = T - 1
@@ -509,7 +558,7 @@ class BaseSimulator(Pedestrians):
         done = 0
         if use_graph and steps > 3:
             try:
-                if self._side_stream_ok(cap):
+                if self._side_stream_ok(inputs[0].shape[0]):
                     self.model.obs_stream = torch.cuda.Stream()
                 for _ in range(2):                        # real frames, also warm every lazy init up
                     step()
@@ -530,12 +579,6 @@ class BaseSimulator(Pedestrians):
                 done = int(st.t.item())
         for _ in range(steps - done):
             step()
-        last = int(st.t.item())
-        return scenarios.ScenarioResult(
-            position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res, mask_p=st.mask_res,
-            waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles, time_unit=sc.time_unit,
-            spawned=int(st.spawned[last & 1].item()), dropped=int(st.dropped.item()), spawn_count=st.spawn_count,
-            capacity=cap, seed=int(seed), state=st)
 
     # ---- HOT LOOP C: differentiable rollout for fine-tuning (simulators.py:659-832) ----
     def test_multiple_rollouts_for_training(self, data, t_start=0):

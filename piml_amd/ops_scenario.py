@@ -1,5 +1,5 @@
 """Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_step_rules,
-piml_scenario_route).
+piml_scenario_step_members, piml_scenario_route).
 
 `scenario_state` allocates the persistent (static-address) buffers of one simulation and the `piml_scenario` descriptor
 that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive, retire, spawn, record), with the
@@ -12,6 +12,8 @@ import torch
 
 from . import _lib
 from .ops import _gpu_f32, _ptr, _stream
+
+MAX_MEMBERS = 65535          # piml_scenario_step_members: one grid row per member
 
 
 def scenario_route(origin, destination, polyline, max_iters=16, clearance=2.0):
@@ -32,45 +34,57 @@ def scenario_route(origin, destination, polyline, max_iters=16, clearance=2.0):
     return r, iters
 
 
-def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6, topk_obs=10):
+def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6, topk_obs=10, seeds=None):
     """The buffers of one simulation of `scenario` (on its device) with `capacity` slots and `frames` recorded frames,
-    and their descriptor.  Absent slots start as NaN positions / destinations, zero velocity, acceleration and masks."""
+    and their descriptor.  Absent slots start as NaN positions / destinations, zero velocity, acceleration and masks.
+    seeds (a sequence of ints): an ensemble of S = len(seeds) simulations instead, every buffer but the frame counter with
+    a leading member axis (state (S, capacity, .), waypoints (S, D, capacity, 2), records (S, T, capacity, .), spawned
+    (S, 2), dropped (S), features (S, capacity, k, 6)); `seed` is then unused and st.seeds holds the seeds' 64-bit
+    patterns as a device int64 tensor (piml_scenario_step_members)."""
     dev = scenario.entries.device
     if dev.type != 'cuda':
         raise _lib.PimlHipError(f'scenario_state: the scenario must be on a GPU (piml_amd has no CPU path), got {dev}')
     cap, T, D = int(capacity), int(frames), int(scenario.num_waypoints)
     if cap < 1 or T < 1:
         raise ValueError(f'capacity and frames must be >= 1, got {cap}, {T}')
-    st = types.SimpleNamespace(scenario=scenario, capacity=cap, T=T, seed=int(seed))
+    st = types.SimpleNamespace(scenario=scenario, capacity=cap, T=T, seed=int(seed), members=None)
+    lead = ()
+    if seeds is not None:
+        seeds = [int(x) for x in seeds]
+        if not 1 <= len(seeds) <= MAX_MEMBERS:
+            raise ValueError(f'seeds: 1 .. {MAX_MEMBERS} of them expected, got {len(seeds)}')
+        bits = [(x & 0xFFFFFFFFFFFFFFFF) - ((x & 0x8000000000000000) << 1) for x in seeds]   # two's complement int64
+        st.members, st.seed_list, lead = len(seeds), seeds, (len(seeds),)
+        st.seeds = torch.tensor(bits, device=dev, dtype=torch.long)
     f32 = dict(device=dev, dtype=torch.float32)
     nan = float('nan')
-    st.p = torch.full((cap, 2), nan, **f32)
-    st.v = torch.zeros(cap, 2, **f32)
-    st.a = torch.zeros(cap, 2, **f32)
-    st.dest = torch.full((cap, 2), nan, **f32)
-    st.hist = torch.zeros(cap, hist_width, **f32)
-    st.selff = torch.zeros(cap, hist_width + 5, **f32)
-    st.desired_speed = torch.zeros(cap, **f32)
-    st.mask = torch.zeros(cap, **f32)
-    st.flag = torch.zeros(cap, device=dev, dtype=torch.int32)
-    st.waypoints = torch.full((D, cap, 2), nan, **f32)
-    st.exit_idx = torch.zeros(D, cap, device=dev, dtype=torch.int32)
-    st.spawn_iters = torch.zeros(cap, device=dev, dtype=torch.int32)
-    st.p_res = torch.full((T, cap, 2), nan, **f32)
-    st.v_res = torch.zeros(T, cap, 2, **f32)
-    st.a_res = torch.zeros(T, cap, 2, **f32)
-    st.dest_res = torch.full((T, cap, 2), nan, **f32)
-    st.mask_res = torch.zeros(T, cap, **f32)
-    st.spawn_count = torch.zeros(T, device=dev, dtype=torch.int32)
+    st.p = torch.full((*lead, cap, 2), nan, **f32)
+    st.v = torch.zeros(*lead, cap, 2, **f32)
+    st.a = torch.zeros(*lead, cap, 2, **f32)
+    st.dest = torch.full((*lead, cap, 2), nan, **f32)
+    st.hist = torch.zeros(*lead, cap, hist_width, **f32)
+    st.selff = torch.zeros(*lead, cap, hist_width + 5, **f32)
+    st.desired_speed = torch.zeros(*lead, cap, **f32)
+    st.mask = torch.zeros(*lead, cap, **f32)
+    st.flag = torch.zeros(*lead, cap, device=dev, dtype=torch.int32)
+    st.waypoints = torch.full((*lead, D, cap, 2), nan, **f32)
+    st.exit_idx = torch.zeros(*lead, D, cap, device=dev, dtype=torch.int32)
+    st.spawn_iters = torch.zeros(*lead, cap, device=dev, dtype=torch.int32)
+    st.p_res = torch.full((*lead, T, cap, 2), nan, **f32)
+    st.v_res = torch.zeros(*lead, T, cap, 2, **f32)
+    st.a_res = torch.zeros(*lead, T, cap, 2, **f32)
+    st.dest_res = torch.full((*lead, T, cap, 2), nan, **f32)
+    st.mask_res = torch.zeros(*lead, T, cap, **f32)
+    st.spawn_count = torch.zeros(*lead, T, device=dev, dtype=torch.int32)
     st.t = torch.zeros(1, device=dev, dtype=torch.long)
-    st.spawned = torch.zeros(2, device=dev, dtype=torch.long)
-    st.dropped = torch.zeros(1, device=dev, dtype=torch.long)
+    st.spawned = torch.zeros(*lead, 2, device=dev, dtype=torch.long)
+    st.dropped = torch.zeros(lead[0] if lead else 1, device=dev, dtype=torch.long)
     # feature buffers the relative-feature kernel writes (ops.relative_features_into)
     kp, ko = min(topk_ped, cap), min(topk_obs, scenario.obstacles.shape[0])
-    st.pf = torch.empty(cap, kp, 6, **f32)
-    st.of = torch.empty(cap, ko, 6, **f32)
-    st.ped_idx = torch.empty(cap, kp, device=dev, dtype=torch.int32)
-    st.obs_idx = torch.empty(cap, ko, device=dev, dtype=torch.int32)
+    st.pf = torch.empty(*lead, cap, kp, 6, **f32)
+    st.of = torch.empty(*lead, cap, ko, 6, **f32)
+    st.ped_idx = torch.empty(*lead, cap, kp, device=dev, dtype=torch.int32)
+    st.obs_idx = torch.empty(*lead, cap, ko, device=dev, dtype=torch.int32)
 
     s = _lib.Scenario()
     for name, t in (('position', st.p), ('velocity', st.v), ('acceleration', st.a), ('destination', st.dest),
@@ -126,13 +140,20 @@ def scenario_rules(scenario):
 
 def scenario_step(st, a_next=None, init=False):
     """One launch: init=True spawns the scenario's n_initial agents into frame st.t; otherwise frame st.t -> st.t + 1 with
-    the network's accelerations a_next (capacity, 2).  The caller advances st.t (ops.relative_features_into(tick=st.t))."""
+    the network's accelerations a_next (capacity, 2), or (S, capacity, 2) for an ensemble state (every member in the same
+    launch).  The caller advances st.t (ops.relative_features_into(tick=st.t))."""
     if not init:
         a_next = _gpu_f32('a_next', a_next)
-        if tuple(a_next.shape) != (st.capacity, 2) or a_next.device != st.p.device:
-            raise ValueError(f'a_next: ({st.capacity}, 2) on {st.p.device} expected, got {tuple(a_next.shape)} on {a_next.device}')
+        want = (st.capacity, 2) if st.members is None else (st.members, st.capacity, 2)
+        if tuple(a_next.shape) != want or a_next.device != st.p.device:
+            raise ValueError(f'a_next: {want} on {st.p.device} expected, got {tuple(a_next.shape)} on {a_next.device}')
     with torch.cuda.device(st.p.device):
-        if st.rules is None:                                 # GC
+        if st.members is not None:
+            _lib.check(_lib.lib().piml_scenario_step_members(ctypes.byref(st.desc),
+                                                             ctypes.byref(st.rules) if st.rules is not None else None,
+                                                             st.members, _ptr(st.seeds), _ptr(a_next) if not init else None,
+                                                             int(bool(init)), _stream()), 'piml_scenario_step_members')
+        elif st.rules is None:                               # GC
             _lib.check(_lib.lib().piml_scenario_step(ctypes.byref(st.desc), _ptr(a_next) if not init else None,
                                                      int(bool(init)), _stream()), 'piml_scenario_step')
         else:

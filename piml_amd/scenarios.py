@@ -8,6 +8,9 @@ entries and a route: a spawn law, an arrival rule, an initial-velocity law, a sp
 stream (`spawn_law`, `arrival_rule`, ...; piml_scenario_rules).  The per-frame work -- integration, arrival, retirement,
 Poisson arrivals, recording -- is one HIP launch (piml_scenario_step / piml_scenario_step_rules, piml_amd/csrc/scenario.hip).
 
+`ScenarioEnsemble` is what `BaseSimulator.simulate_ensemble` returns: S simulations of one scene (one per seed) with a
+leading member axis, each of them a `ScenarioResult` through `member(m)`.
+
 `save_clip` writes a simulation as the reference's `RawData.save_data` does (src/data/data.py:305-341, version v2.2), so
 that `RawData.load_trajectory_data` -- here and in the reference -- reads it back as a training clip (`--iter_flag`).
 """
@@ -265,6 +268,39 @@ class ScenarioResult(types.SimpleNamespace):
     def save_data(self, path):
         p, m, w, d, o = self._dense()
         return save_clip(path, p, m, w, d, o, {'time_unit': float(self.time_unit)})
+
+
+class ScenarioEnsemble(types.SimpleNamespace):
+    """What `BaseSimulator.simulate_ensemble` returns: the ScenarioResult fields with a leading member axis -- position /
+    velocity / acceleration / destination (S, T, cap, 2), mask_p (S, T, cap), waypoints (S, D, cap, 2), desired_speed
+    (S, cap), spawn_count (S, T) -- and seeds, spawned, dropped as lists of S ints; obstacles, time_unit and capacity
+    are shared.  Member m is the simulation of seed seeds[m]."""
+
+    def __len__(self):
+        return len(self.seeds)
+
+    def member(self, m):
+        """Member m as a ScenarioResult of views (save_data, to_raw_data, num_agents work on it)."""
+        return ScenarioResult(
+            position=self.position[m], velocity=self.velocity[m], acceleration=self.acceleration[m],
+            destination=self.destination[m], mask_p=self.mask_p[m], waypoints=self.waypoints[m],
+            desired_speed=self.desired_speed[m], obstacles=self.obstacles, time_unit=self.time_unit,
+            spawned=self.spawned[m], dropped=self.dropped[m], spawn_count=self.spawn_count[m], capacity=self.capacity,
+            seed=self.seeds[m])
+
+    def save_data(self, pattern):
+        """One v2.2 clip per member at pattern with '{seed}' replaced by the member's seed.  Returns the paths."""
+        if '{seed}' not in pattern:
+            raise ValueError(f"save_data: the path pattern must contain '{{seed}}', got {pattern!r}")
+        return [self.member(m).save_data(pattern.replace('{seed}', str(s))) for m, s in enumerate(self.seeds)]
+
+    def collision_counts(self, threshold):
+        """Per-member totals of collision_count(member.position, threshold, reduction='sum'): a list of S floats, one
+        read-back.  One ops.collision_counts call per member: on a stack of more than 25 frames the count applies the
+        friends rule, whose per-pair totals run over the whole stack, so one (S * T, cap, 2) stack would couple members."""
+        from . import ops
+        thr = (float(threshold),)
+        return torch.stack([ops.collision_counts(p, thr)[0].sum() for p in self.position]).tolist()
 
 
 def clip_tuple(position, mask_p, waypoints, destination, obstacles, meta_data):

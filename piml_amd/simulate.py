@@ -3,6 +3,7 @@ four_directional_square, basic_unit1..3 for the reference's synthetic scenes), s
 the GPU and save the result as a v2.2 clip that `RawData.load_trajectory_data` (and so `--iter_flag` pre-training) reads.
 
     python -m piml_amd.simulate --checkpoint model.pt --frames 750 --out clip.npy [model flags of piml_amd.main]
+    python -m piml_amd.simulate --seeds 0:32 --out 'gc_{seed}.npy'      (an ensemble: every seed in one launch per frame)
 
 Model flags (--model, --hidden sizes, --topk_*, --num_history_velocity, ...) are those of `piml_amd.main`, with its
 defaults.  Without --checkpoint the network keeps its initial weights (a smoke run)."""
@@ -24,15 +25,51 @@ def get_args(argv=None):
     p.add_argument('--checkpoint', type=str, default='', help='state_dict of the model (torch.save); "" = initial weights')
     p.add_argument('--scenario', type=str, default='gc', choices=sorted(SCENARIOS.SCENARIOS))
     p.add_argument('--frames', type=int, default=750)
-    p.add_argument('--seed', type=int, default=0, help='seed of the spawn schedule')
+    seed = p.add_mutually_exclusive_group()
+    seed.add_argument('--seed', type=int, default=0, help='seed of the spawn schedule')
+    seed.add_argument('--seeds', type=str, default=None,
+                      help="an ensemble, one simulation per seed: 'a:b' (a .. b-1) or 'a,b,c'; --out must contain {seed}")
     p.add_argument('--capacity', type=int, default=None, help='agent slots (default: from the arrival rate)')
     p.add_argument('--out', type=str, default='clip.npy')
     p.add_argument('--time_unit', type=float, default=0.08)
     p.add_argument('--uniform_desired_speed', action=argparse.BooleanOptionalAction, default=None,
                    help="uniform desired speed (default: the scene's own; GC and the crosswalk no, the others yes)")
     own, rest = p.parse_known_args(argv)
+    if own.seeds is not None:
+        try:
+            own.seeds = parse_seeds(own.seeds)
+        except ValueError as ex:
+            p.error(f'--seeds: {ex}')
+        if '{seed}' not in own.out:
+            p.error("--seeds: --out must contain '{seed}' (one clip per seed)")
     model_args = MAIN.get_args(rest)
     return own, model_args
+
+
+def parse_seeds(text):
+    """'a:b' -> [a, ..., b-1]; 'a,b,c' -> [a, b, c].  ValueError on anything else or on no seed at all."""
+    text = text.strip()
+    if ':' in text:
+        lo, hi = (int(x) for x in text.split(':'))
+        seeds = list(range(lo, hi))
+    else:
+        seeds = [int(x) for x in text.split(',')]
+    if not seeds:
+        raise ValueError(f'no seed in {text!r}')
+    return seeds
+
+
+def _report(tag, frames, res, threshold, out, soft=None, hard=None):
+    """(spawned, retired, dropped, soft, hard) of one simulation and its line, as piml_amd.main reports collisions."""
+    n = res.num_agents
+    retired = n - int(res.mask_p[-1, :n].sum().item())
+    if soft is None:
+        pos = res.position[:, :n]
+        soft = METRIC.collision_count(pos, threshold, reduction='sum')
+        hard = METRIC.collision_count(pos, threshold / 2, reduction='sum')
+    print(f'[simulate] {tag}: {frames} frames, capacity {res.capacity}: spawned {res.spawned}, '
+          f'retired {retired}, dropped {res.dropped}; collisions soft {soft:g} hard {hard:g}; saved {out}')
+    return res.spawned, retired, res.dropped, soft, hard
 
 
 def main(argv=None):
@@ -48,16 +85,26 @@ def main(argv=None):
     sim.model.eval()
     kw = {} if own.uniform_desired_speed is None else {'uniform_desired_speed': own.uniform_desired_speed}
     scenario = SCENARIOS.SCENARIOS[own.scenario](time_unit=own.time_unit, **kw)
+    if own.seeds is not None:
+        return _ensemble(sim, scenario, own, args)
     res = sim.simulate_scenario(scenario, own.frames, seed=own.seed, capacity=own.capacity)
-    n = res.num_agents
-    retired = n - int(res.mask_p[-1, :n].sum().item())
-    pos = res.position[:, :n]
-    soft = METRIC.collision_count(pos, args.collision_threshold, reduction='sum')       # as piml_amd.main reports them
-    hard = METRIC.collision_count(pos, args.collision_threshold / 2, reduction='sum')
     res.save_data(own.out)
-    print(f'[simulate] {own.scenario}: {own.frames} frames, capacity {res.capacity}: spawned {res.spawned}, '
-          f'retired {retired}, dropped {res.dropped}; collisions soft {soft:g} hard {hard:g}; saved {own.out}')
+    _report(own.scenario, own.frames, res, args.collision_threshold, own.out)
     return res
+
+
+def _ensemble(sim, scenario, own, args):
+    ens = sim.simulate_ensemble(scenario, own.frames, own.seeds, capacity=own.capacity)
+    paths = ens.save_data(own.out)
+    soft = ens.collision_counts(args.collision_threshold)
+    hard = ens.collision_counts(args.collision_threshold / 2)
+    rows = [_report(f'{own.scenario} (seed {s})', own.frames, ens.member(m), args.collision_threshold, paths[m], soft[m], hard[m])
+            for m, s in enumerate(ens.seeds)]
+    stats = torch.tensor(rows, dtype=torch.float64)
+    mean, std = stats.mean(0), stats.std(0, unbiased=False)
+    print(f'[simulate] {own.scenario}: {len(ens)} seeds, mean +- std: ' + ', '.join(
+        f'{k} {mean[j]:.4g} +- {std[j]:.3g}' for j, k in enumerate(('spawned', 'retired', 'dropped', 'soft', 'hard'))))
+    return ens
 
 
 if __name__ == '__main__':
