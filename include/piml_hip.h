@@ -585,6 +585,34 @@ int piml_scenario_step_members(const piml_scenario* s, const piml_scenario_rules
                                const float* a_next, int init, void* stream);
 
 /*
+ * MLAPM drives the scene (ABI 35, additive): one frame t -> t+1 of every member under the closed-form law instead of a
+ * network's a_next -- the simulation loop of src/main_mlapm.py:18-36 around the scene's arrivals, routing and exits.
+ * Buffers, members, seeds and r exactly as piml_scenario_step_members (members = 1 with one seed is the single run; r = NULL
+ * is GC); frame 0's spawn stays with that entry's init launch, which does not depend on the law.
+ * t = *frame_counter + frame_offset; the counter is read, not written (the caller adds the frames it ran: a captured graph
+ * of K frames takes offsets 0 .. K-1 and one add of K).  From t + 1 >= T on a call does nothing.
+ * Every slot i < min(spawned[t & 1], capacity) with mask[i] == 1:
+ *   F = MLAPM.step's force (src/models/mlapm.py:10-58, with the coll.unsqueeze(-1) fix for UCY) on (p, v, v0 =
+ *   desired_speed[i], dest = the current waypoint), the sources being the member's agents present in frame t as RECORDED
+ *   (position_out[t], velocity_out[t]; absent ones skipped, as main_mlapm.py:19-23 compacts them);
+ *   v' = v + F dt (mlapm.py:57), p' = p + v' dt (main_mlapm.py:25, explicit Euler), a' = F; then the history /
+ *   self_features update, arrival, retirement and record of piml_scenario_step (GC) or piml_scenario_step_rules.
+ * Spawns, waypoints, exit_idx, desired_speed, spawned, dropped and spawn_out are bitwise those of a piml_scenario_step_members
+ * run of the same seeds (they depend on (seed, frame, ordinal) only).  law->radius is MLAPM's UCY collision radius
+ * (mlapm.py:42-46), not the scene's arrival_radius.  MLAPM has no obstacle or wall term (the reference's neither).
+ * No atomics; capturable.
+ * hipErrorInvalidValue (before any launch): every check of piml_scenario_step_members except a_next / init; frame_offset < 0;
+ * NULL law; variant not 0 / 1 / 2; tau not finite and > 0; A, B, C, D or theta_deg not finite; radius not finite and > 0.
+ */
+typedef struct piml_mlapm_law {
+    int variant;                                            /* 0 raw, 1 GC, 2 UCY (piml_mlapm_step_fwd's) */
+    float tau, A, B, C, D, theta_deg;                       /* MLAPM(version, tau, A, B, C, D, theta) */
+    float radius;                                           /* UCY collision radius (MLAPM.step's radius) */
+} piml_mlapm_law;
+int piml_scenario_step_mlapm(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                             const piml_mlapm_law* law, int frame_offset, void* stream);
+
+/*
  * utils.route (src/utils/utils.py:141-165) for n (o, d) pairs, one wave each, the device function the spawn path uses:
  * the segment o -> r is tested against the polyline's R-1 segments, the hit with the smallest alpha moves r to
  * crossing + clearance * normal, until nothing is hit or max_iters moves were made.  float32 in the reference's order.

@@ -79,6 +79,11 @@ class ScenarioRules(ctypes.Structure):
                 ('poisson_thresholds2', ctypes.c_uint32 * 8), ('square_grid', _f * 32)]
 
 
+class MlapmLaw(ctypes.Structure):
+    """piml_mlapm_law (include/piml_hip.h)."""
+    _fields_ = [('variant', _i), ('tau', _f), ('A', _f), ('B', _f), ('C', _f), ('D', _f), ('theta_deg', _f), ('radius', _f)]
+
+
 SPAWN_LAWS = {'gc': 0, 'crosswalk': 1, 'square': 2, 'unit1': 3, 'unit2': 4, 'unit3': 5}      # PIML_SPAWN_*
 ARRIVAL_RULES = {'gc': 0, 'radius': 1, 'x_band': 2, 'x_exit': 3}                             # PIML_ARRIVE_*
 
@@ -115,6 +120,7 @@ SIGNATURES = {
     'piml_scenario_step': [_p, _p, _i, _p],
     'piml_scenario_step_rules': [_p, _p, _p, _i, _p],
     'piml_scenario_step_members': [_p, _p, _i, _p, _p, _i, _p],
+    'piml_scenario_step_mlapm': [_p, _p, _i, _p, _p, _i, _p],
     'piml_scenario_route': [_p, _p, _i, _p, _i, _i, _f, _p, _p, _p],
     'piml_collision_correction_fwd': [_p, _p, _p, _z, _i, _i, _f, _f, _p, _p],
     'piml_collision_correction_bwd': [_p, _p, _p, _p, _z, _i, _i, _f, _f, _p, _p, _p, _p],

@@ -14,148 +14,6 @@
 
 namespace piml {
 
-constexpr int kMlTile = 2048;   // agents per LDS tile (fwd 32 KiB, bwd 64 KiB)
-
-struct MlapmParams {
-    int variant;                 // 0 raw, 1 GC, 2 UCY (mlapm.py:28-53)
-    float tau, A, B, Cc, D, cth, sth, r2;   // cos/sin of theta, 2*radius
-    float B2, C2, D2;            // B, C, D pre-multiplied by log2(e): exp(x) = exp2(x * log2 e)
-    int skip_absent;             // 1: sources with a NaN position contribute nothing (absent agents)
-    int ucy_two_phase;           // backward, UCY: the two-phase form (PIML_MLAPM_UCY_TWO_PHASE=0 keeps the scalar loop)
-};
-
-// One ordered pair: focal (vix, viy, ex, ey) at the origin, source at (rx, ry) with
-// relative velocity (wx, wy).  Returns view * A * g * direction (mlapm.py:25-53).
-__device__ __forceinline__ float2 mlapm_pair(const MlapmParams& P, float rx, float ry, float wx, float wy,
-                                             float vix, float viy, float ex, float ey) {
-    const float d2 = rx * rx + ry * ry;
-    const bool pos = d2 > 0.f;                                      // NaN -> false, handled below
-    const float rinv = fast_rsq(d2);
-    const float r = pos ? d2 * rinv : d2;                           // :26 (0 stays 0, NaN stays NaN)
-    const float view = (vix * rx + viy * ry > 0.f) ? 1.f : 0.f;     // :27
-    const float ninv = pos ? rinv : 0.f;                            // F.normalize: 0 / eps = 0
-    const float nx = rx * ninv, ny = ry * ninv;
-    float g, dx, dy;
-    if (P.variant == 0) {
-        g = fast_exp2(P.B2 * r);                                    // :29
-        dx = nx; dy = ny;
-    } else {
-        const float cr = rx * ey - ry * ex;                         // :34 / :48
-        // theta = -sign(cr) * theta, 0 -> +theta; sign(NaN) = NaN propagates like the reference
-        const float st = cr > 0.f ? -P.sth : (cr <= 0.f ? P.sth : cr);
-        dx = P.cth * nx - st * ny; dy = st * nx + P.cth * ny;       // :36-39
-        if (P.variant == 1) {
-            const float w2 = wx * wx + wy * wy;
-            // cosine_similarity clamps both norms at 1e-8 (:32)
-            const float cs = (rx * wx + ry * wy) * fminf(rinv, 1e8f) * fminf(fast_rsq(w2), 1e8f);
-            g = fast_exp2(P.B2 * r + P.C2 * cs + P.D2 * r * cs);    // :40
-        } else {
-            const bool coll = ucy_collision(rx, ry, wx, wy, P.r2);      // :43-47, exact
-            g = coll ? fast_exp2(P.B2 * r + P.C2) : 1.f;            // :53 (with coll.unsqueeze(-1), Q8)
-            if (r != r) g = r;                                      // NaN poisons like the reference
-        }
-    }
-    const float s = view * P.A * g;
-    return make_float2(s * dx, s * dy);
-}
-
-// Two ordered pairs per lane with packed fp32 (v_pk_mul / v_pk_add / v_pk_fma_f32): the raw and GC force laws
-// (variants 0, 1).  Same expressions as mlapm_pair, element-wise on 2-vectors; products feeding sums are fused
-// (fma), which the 1e-5 relative bar of this smooth force law allows (the selections are unaffected).
-// (The variant stays a run-time value on purpose: a kernel specialised per variant at compile time measured
-// slower -- GC forward 38.7 us against 26.1 us at N = 4096; round 4, again, on the rollout frame: 47.5 against 34.1 us.)
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ v2f pk_sel(bool c0, bool c1, v2f a, v2f b) { return v2f{c0 ? a.x : b.x, c1 ? a.y : b.y}; }
-
-__device__ __forceinline__ void mlapm_pair2(const MlapmParams& P, v2f rx, v2f ry, v2f wx, v2f wy, float vix, float viy,
-                                            float ex, float ey, v2f& fx, v2f& fy) {
-    const v2f zero = {0.f, 0.f}, one = {1.f, 1.f};
-    const v2f d2 = pk_fma(ry, ry, rx * rx);
-    const bool p0 = d2.x > 0.f, p1 = d2.y > 0.f;                                  // NaN -> false
-    const v2f rinv = {fast_rsq(d2.x), fast_rsq(d2.y)};
-    const v2f r = pk_sel(p0, p1, d2 * rinv, d2);                                  // :26
-    const v2f dot = pk_fma(v2f{viy, viy}, ry, v2f{vix, vix} * rx);
-    const v2f view = pk_sel(dot.x > 0.f, dot.y > 0.f, one, zero);                 // :27
-    const v2f ninv = pk_sel(p0, p1, rinv, zero);
-    const v2f nx = rx * ninv, ny = ry * ninv;
-    v2f g, dx, dy;
-    if (P.variant == 0) {
-        const v2f a = v2f{P.B2, P.B2} * r;
-        g = v2f{fast_exp2(a.x), fast_exp2(a.y)};                                  // :29
-        dx = nx; dy = ny;
-    } else {
-        const v2f cr = pk_fma(rx, v2f{ey, ey}, -(ry * v2f{ex, ex}));              // :34
-        const v2f st = {cr.x > 0.f ? -P.sth : (cr.x <= 0.f ? P.sth : cr.x),
-                        cr.y > 0.f ? -P.sth : (cr.y <= 0.f ? P.sth : cr.y)};
-        const v2f cth = {P.cth, P.cth};
-        dx = pk_fma(cth, nx, -(st * ny));                                         // :36-39
-        dy = pk_fma(st, nx, cth * ny);
-        const v2f w2 = pk_fma(wy, wy, wx * wx);
-        const v2f ri8 = {fminf(rinv.x, 1e8f), fminf(rinv.y, 1e8f)};
-        const v2f qi8 = {fminf(fast_rsq(w2.x), 1e8f), fminf(fast_rsq(w2.y), 1e8f)};
-        const v2f cs = pk_fma(ry, wy, rx * wx) * ri8 * qi8;                       // :32
-        const v2f a = pk_fma(v2f{P.D2, P.D2} * r, cs, pk_fma(v2f{P.C2, P.C2}, cs, v2f{P.B2, P.B2} * r));
-        g = v2f{fast_exp2(a.x), fast_exp2(a.y)};                                  // :40
-    }
-    const v2f sc = view * v2f{P.A, P.A} * g;
-    fx = sc * dx;
-    fy = sc * dy;
-}
-
-// UCY (variant 2) in two phases (round 4).  g = exp(B r + C) only for pairs the collision predicate flags, 1 otherwise
-// (mlapm.py:43-53), and the predicate -- three square roots and two divisions in the reference's exact float32 operations --
-// cost more than the rest of the pair.  Phase 1 gives every pair its g = 1 term on packed arithmetic and a CONSERVATIVE
-// distance test: every clause of the predicate implies that the relative position comes within 2R of the origin for some
-// t in [0, 1] of r + t w, hence |r| - |w| < 2R; a pair with (|r| - |w|)^2 - (2R)^2 > 1e-6 (|r|^2 + 1) (the slack covers the
-// roundings of both sides, 1e-7 relative, with a factor of ten) cannot be flagged.  The others -- ~4 % of the pairs of a
-// 4096-agent hall -- are compacted into a per-wave ring and get the exact predicate 64 at a time; a flagged pair adds the
-// difference (g - 1) x its g = 1 term.  Same sums up to the order of the additions.
-__device__ __forceinline__ void mlapm_pair2_ucy(const MlapmParams& P, v2f rx, v2f ry, v2f wx, v2f wy, float vix, float viy,
-                                                float ex, float ey, v2f& fx, v2f& fy, bool& near0, bool& near1) {
-    const v2f zero = {0.f, 0.f}, one = {1.f, 1.f};
-    const v2f d2 = pk_fma(ry, ry, rx * rx);
-    const bool p0 = d2.x > 0.f, p1 = d2.y > 0.f;                                  // NaN -> false
-    const v2f rinv = {fast_rsq(d2.x), fast_rsq(d2.y)};
-    const v2f r = pk_sel(p0, p1, d2 * rinv, d2);
-    const v2f dot = pk_fma(v2f{viy, viy}, ry, v2f{vix, vix} * rx);
-    const v2f view = pk_sel(dot.x > 0.f, dot.y > 0.f, one, zero);                 // :27
-    const v2f ninv = pk_sel(p0, p1, rinv, zero);
-    const v2f nx = rx * ninv, ny = ry * ninv;
-    const v2f cr = pk_fma(rx, v2f{ey, ey}, -(ry * v2f{ex, ex}));                  // :48
-    const v2f st = {cr.x > 0.f ? -P.sth : (cr.x <= 0.f ? P.sth : cr.x),
-                    cr.y > 0.f ? -P.sth : (cr.y <= 0.f ? P.sth : cr.y)};
-    const v2f cth = {P.cth, P.cth};
-    const v2f sc = view * v2f{P.A, P.A};                                          // g = 1
-    fx = sc * pk_fma(cth, nx, -(st * ny));
-    fy = sc * pk_fma(st, nx, cth * ny);
-    // conservative test: far = certainly not flagged
-    const v2f w2 = pk_fma(wy, wy, wx * wx);
-    const v2f wn = w2 * v2f{fast_rsq(fmaxf(w2.x, 1e-30f)), fast_rsq(fmaxf(w2.y, 1e-30f))};
-    const v2f a = r - wn;
-    const v2f slack = pk_fma(v2f{1e-6f, 1e-6f}, d2, v2f{1e-6f + P.r2 * P.r2, 1e-6f + P.r2 * P.r2});
-    near0 = !(a.x > 0.f && a.x * a.x > slack.x);                                  // (NaN: near)
-    near1 = !(a.y > 0.f && a.y * a.y > slack.y);
-}
-
-// exact second phase of one candidate: the difference between its flagged term and the g = 1 term phase 1 added
-__device__ __forceinline__ float2 mlapm_ucy_correction(const MlapmParams& P, float rx, float ry, float wx, float wy,
-                                                       float vix, float viy, float ex, float ey) {
-    if (!ucy_collision(rx, ry, wx, wy, P.r2)) return make_float2(0.f, 0.f);       // :43-47, exact
-    const float d2 = rx * rx + ry * ry;
-    const bool pos = d2 > 0.f;
-    const float rinv = fast_rsq(d2);
-    const float r = pos ? d2 * rinv : d2;
-    const float view = (vix * rx + viy * ry > 0.f) ? 1.f : 0.f;
-    const float ninv = pos ? rinv : 0.f;
-    const float nx = rx * ninv, ny = ry * ninv;
-    const float cr = rx * ey - ry * ex;
-    const float st = cr > 0.f ? -P.sth : (cr <= 0.f ? P.sth : cr);
-    const float s = view * P.A * (fast_exp2(P.B2 * r + P.C2) - 1.f);              // :53 minus the g = 1 term
-    return make_float2(s * (P.cth * nx - st * ny), s * (st * nx + P.cth * ny));
-}
-
 // ROLL: one frame of the simulation loop of src/main_mlapm.py:18-36 in this launch.  The state of frame t - 1 is read from
 // the trajectory itself -- an agent that came within `radius` of its destination in frame t - 1 >= 1 is absent (NaN) from
 // frame t on (:34; frame 0 is the caller's initial state, not tested) -- the new velocity and p + v dt go to frame t, and the
@@ -219,74 +77,7 @@ __global__ __launch_bounds__(WAVES * 64) void mlapm_fwd_kernel(
         }
         __syncthreads();
         if (!has) continue;
-        int j = lane;
-        if (P.variant != 2) {
-            // two sources per lane and iteration (j, j + 64), packed arithmetic
-            const v2f pix = {pi.x, pi.x}, piy = {pi.y, pi.y}, vix2 = {vi.x, vi.x}, viy2 = {vi.y, vi.y};
-            for (; j + 64 < tn; j += 128) {
-                const float4 a = tile[j], b = tile[j + 64];
-                v2f fx, fy;
-                mlapm_pair2(P, v2f{a.x, b.x} - pix, v2f{a.y, b.y} - piy, v2f{a.z, b.z} - vix2, v2f{a.w, b.w} - viy2,
-                            vi.x, vi.y, ex, ey, fx, fy);
-                if (P.skip_absent) {                                        // absent sources contribute nothing
-                    if (a.x != a.x || a.y != a.y) { fx.x = 0.f; fy.x = 0.f; }
-                    if (b.x != b.x || b.y != b.y) { fx.y = 0.f; fy.y = 0.f; }
-                }
-                acc2x += fx; acc2y += fy;
-            }
-        }
-        if (P.variant == 2) {
-            // phase 1 on two sources per lane (j, j + 64; the second clamped and masked at the tile's end), candidates into
-            // the ring; phase 2 whenever 64 are waiting, and for what is left at the end of the tile
-            const v2f pix = {pi.x, pi.x}, piy = {pi.y, pi.y}, vix2 = {vi.x, vi.x}, viy2 = {vi.y, vi.y};
-            unsigned short* ring = ucy_ring[uniform(wave)];
-            unsigned head = 0, tail = 0;
-            for (int j0 = 0;; j0 += 128) {
-                const bool more = j0 < tn;
-                if (more) {
-                    const int ja = j0 + lane, jb = j0 + 64 + lane;
-                    const bool va = ja < tn, vb = jb < tn;
-                    const float4 a = tile[va ? ja : 0], b = tile[vb ? jb : 0];
-                    v2f fx, fy;
-                    bool na, nb;
-                    mlapm_pair2_ucy(P, v2f{a.x, b.x} - pix, v2f{a.y, b.y} - piy, v2f{a.z, b.z} - vix2, v2f{a.w, b.w} - viy2,
-                                    vi.x, vi.y, ex, ey, fx, fy, na, nb);
-                    const bool absent_a = P.skip_absent && (a.x != a.x || a.y != a.y);
-                    const bool absent_b = P.skip_absent && (b.x != b.x || b.y != b.y);
-                    if (!va || absent_a) { fx.x = 0.f; fy.x = 0.f; na = false; }
-                    if (!vb || absent_b) { fx.y = 0.f; fy.y = 0.f; nb = false; }
-                    acc2x += fx; acc2y += fy;
-                    const u64 ma = __builtin_amdgcn_ballot_w64(na);
-                    if (ma) {
-                        if (na) ring[(tail + mbcnt(ma)) & 255] = (unsigned short)ja;
-                        tail += (unsigned)__builtin_popcountll(ma);
-                    }
-                    const u64 mb = __builtin_amdgcn_ballot_w64(nb);
-                    if (mb) {
-                        if (nb) ring[(tail + mbcnt(mb)) & 255] = (unsigned short)jb;
-                        tail += (unsigned)__builtin_popcountll(mb);
-                    }
-                }
-                while (tail - head >= (more ? 64u : 1u)) {
-                    const unsigned n = min(64u, tail - head);
-                    __builtin_amdgcn_wave_barrier();
-                    if ((unsigned)lane < n) {
-                        const float4 c = tile[ring[(head + lane) & 255]];
-                        const float2 t = mlapm_ucy_correction(P, c.x - pi.x, c.y - pi.y, c.z - vi.x, c.w - vi.y, vi.x, vi.y, ex, ey);
-                        sx += t.x; sy += t.y;
-                    }
-                    head += n;
-                }
-                if (!more) break;
-            }
-            continue;
-        }
-        for (; j < tn; j += 64) {
-            const float4 s = tile[j];
-            if (P.skip_absent && (s.x != s.x || s.y != s.y)) continue;      // absent source
-            const float2 t = mlapm_pair(P, s.x - pi.x, s.y - pi.y, s.z - vi.x, s.w - vi.y, vi.x, vi.y, ex, ey);
-            sx += t.x; sy += t.y;
-        }
+        mlapm_tile_sum(P, tile, tn, lane, ucy_ring[uniform(wave)], pi, vi, ex, ey, sx, sy, acc2x, acc2y);
     }
     sx += acc2x.x + acc2x.y; sy += acc2y.x + acc2y.y;
     sx = wave_sum(sx); sy = wave_sum(sy);
@@ -1276,22 +1067,6 @@ __global__ void calc_acceleration_kernel(const float* __restrict__ rel, size_t R
 static int mlapm_wg16_min() {
     static const int v = getenv("PIML_MLAPM_WG16_MIN") ? atoi(getenv("PIML_MLAPM_WG16_MIN")) : 1024;
     return v;
-}
-
-static MlapmParams make_params(int variant, float tau, float A, float B, float Cc, float D, float theta_deg,
-                               float radius, int skip_absent = 0) {
-    MlapmParams P;
-    P.skip_absent = skip_absent;
-    static const bool two_phase_off = getenv("PIML_MLAPM_UCY_TWO_PHASE") && atoi(getenv("PIML_MLAPM_UCY_TWO_PHASE")) == 0;
-    P.ucy_two_phase = two_phase_off ? 0 : 1;
-    P.variant = variant; P.tau = tau; P.A = A; P.B = B; P.Cc = Cc; P.D = D;
-    // the reference forms theta = sign * theta / 180 * pi in float32 (mlapm.py:34)
-    const float th = theta_deg / 180.f * 3.14159265358979323846f;
-    P.cth = cosf(th); P.sth = sinf(th);
-    P.r2 = radius * 2.f;
-    const float log2e = 1.4426950408889634f;
-    P.B2 = B * log2e; P.C2 = Cc * log2e; P.D2 = D * log2e;
-    return P;
 }
 
 }  // namespace piml

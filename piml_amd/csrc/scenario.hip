@@ -55,10 +55,12 @@
 // written by one thread), so no workgroup reads a value another one writes in the same launch; spawned agents take slots
 // >= n_t, which no agent thread touches.
 #include "common.hpp"
+#include "mlapm.hpp"
 #include "philox.hpp"
 #include "../../include/piml_hip.h"
 
 #include <cmath>
+#include <cstring>
 
 namespace piml {
 
@@ -164,30 +166,20 @@ __device__ __forceinline__ int poisson_count(const piml_scenario& S, long long f
     return k;
 }
 
-__device__ __forceinline__ void agent_step(const ScenarioKernelArgs& K, const float2* entries, int i, long long t) {
-    const piml_scenario& S = K.S;
-    float2* P = (float2*)S.position;
-    float2* V = (float2*)S.velocity;
-    float2* Ac = (float2*)S.acceleration;
-    float2* Dst = (float2*)S.destination;
+// frame t+1's record of a slot retired for good
+__device__ __forceinline__ void record_retired(const piml_scenario& S, int i, long long t) {
     const long long tn = t + 1;
-    const bool rec = tn < S.T;
+    if (tn >= S.T) return;
     const size_t fr = (size_t)tn * S.capacity + i;
-    if (S.mask[i] == 0.f) {                                  // retired for good
-        if (rec) {
-            ((float2*)S.position_out)[fr] = make_float2(qnan(), qnan());
-            ((float2*)S.velocity_out)[fr] = make_float2(0.f, 0.f);
-            ((float2*)S.acceleration_out)[fr] = make_float2(0.f, 0.f);
-            ((float2*)S.destination_out)[fr] = make_float2(qnan(), qnan());
-            S.mask_out[fr] = 0.f;
-        }
-        return;
-    }
-    const float dt = S.dt;
-    const float2 p = P[i], v = V[i], a = Ac[i], d = Dst[i];
-    float2 an = K.a_next[i];
-    float2 vn = make_float2(__fadd_rn(v.x, __fmul_rn(a.x, dt)), __fadd_rn(v.y, __fmul_rn(a.y, dt)));
-    float2 pn = make_float2(__fadd_rn(p.x, __fmul_rn(v.x, dt)), __fadd_rn(p.y, __fmul_rn(v.y, dt)));
+    ((float2*)S.position_out)[fr] = make_float2(qnan(), qnan());
+    ((float2*)S.velocity_out)[fr] = make_float2(0.f, 0.f);
+    ((float2*)S.acceleration_out)[fr] = make_float2(0.f, 0.f);
+    ((float2*)S.destination_out)[fr] = make_float2(qnan(), qnan());
+    S.mask_out[fr] = 0.f;
+}
+
+// the velocity history shift and columns 2.. of slot i's self_features row (history, a', v0) after a step to (v', a')
+__device__ __forceinline__ void agent_history(const piml_scenario& S, int i, float2 vn, float2 an) {
     const int hw = S.hist_width;
     float* h = S.hist_velocity + (size_t)i * hw;
     float* so = S.self_features + (size_t)i * S.F;
@@ -195,18 +187,23 @@ __device__ __forceinline__ void agent_step(const ScenarioKernelArgs& K, const fl
     h[hw - 2] = vn.x; h[hw - 1] = vn.y;
     for (int q = 0; q < hw; ++q) so[2 + q] = h[q];
     so[2 + hw] = an.x; so[3 + hw] = an.y; so[4 + hw] = S.desired_speed[i];
+}
 
-    // 2. arrive (scenarios.py:376-384)
-    int f = S.flag[i];
-    const float2* ent = entries + (size_t)S.exit_idx[(size_t)f * S.capacity + i] * S.P;
-    float m2 = INFINITY;                                     // min over the exit's points of the squared distance
-#pragma unroll 10
-    for (int q = 0; q < S.P; ++q) m2 = fminf(m2, sq2(__fsub_rn(pn.x, ent[q].x), __fsub_rn(pn.y, ent[q].y)));
+// 2. arrive, GC's rule (scenarios.py:376-384): m2 = the minimum over the exit entry's points of |p' - e|^2
+__device__ __forceinline__ int gc_arrive(const piml_scenario& S, int f, float2 pn, float2 d, float m2) {
     const bool near = norm2(__fsub_rn(pn.x, d.x), __fsub_rn(pn.y, d.y)) < S.arrival_radius || sqrtf(m2) < S.arrival_radius;
-    if (near) f += 1;
-    // 3. retire (data.py:236-247)
+    return near ? f + 1 : f;
+}
+
+// 3. retire (data.py:236-247) with the flag f after step 2 (gone: the rule retired the agent itself), then slot i's state
+// and frame t+1's record
+__device__ __forceinline__ void agent_retire_record(const piml_scenario& S, int i, long long t, int f, bool gone, float2 pn,
+                                                    float2 vn, float2 an) {
+    const long long tn = t + 1;
+    const bool rec = tn < S.T;
+    const size_t fr = (size_t)tn * S.capacity + i;
     float2 dn = make_float2(qnan(), qnan());
-    bool gone = f >= S.D;
+    gone = gone || f >= S.D;
     if (!gone) {
         dn = ((const float2*)S.waypoints)[(size_t)f * S.capacity + i];
         gone = dn.x != dn.x || dn.y != dn.y;
@@ -219,7 +216,8 @@ __device__ __forceinline__ void agent_step(const ScenarioKernelArgs& K, const fl
         an = make_float2(0.f, 0.f);
         m = 0.f;
     }
-    P[i] = pn; V[i] = vn; Ac[i] = an; Dst[i] = dn;
+    ((float2*)S.position)[i] = pn; ((float2*)S.velocity)[i] = vn; ((float2*)S.acceleration)[i] = an;
+    ((float2*)S.destination)[i] = dn;
     S.flag[i] = f;
     S.mask[i] = m;
     if (rec) {
@@ -229,6 +227,30 @@ __device__ __forceinline__ void agent_step(const ScenarioKernelArgs& K, const fl
         ((float2*)S.destination_out)[fr] = dn;
         S.mask_out[fr] = m;
     }
+}
+
+__device__ __forceinline__ void agent_step(const ScenarioKernelArgs& K, const float2* entries, int i, long long t) {
+    const piml_scenario& S = K.S;
+    if (S.mask[i] == 0.f) {                                  // retired for good
+        record_retired(S, i, t);
+        return;
+    }
+    const float dt = S.dt;
+    const float2 p = ((const float2*)S.position)[i], v = ((const float2*)S.velocity)[i];
+    const float2 a = ((const float2*)S.acceleration)[i], d = ((const float2*)S.destination)[i];
+    const float2 an = K.a_next[i];
+    const float2 vn = make_float2(__fadd_rn(v.x, __fmul_rn(a.x, dt)), __fadd_rn(v.y, __fmul_rn(a.y, dt)));
+    const float2 pn = make_float2(__fadd_rn(p.x, __fmul_rn(v.x, dt)), __fadd_rn(p.y, __fmul_rn(v.y, dt)));
+    agent_history(S, i, vn, an);
+
+    // 2. arrive (scenarios.py:376-384)
+    const int f = S.flag[i];
+    const float2* ent = entries + (size_t)S.exit_idx[(size_t)f * S.capacity + i] * S.P;
+    float m2 = INFINITY;                                     // min over the exit's points of the squared distance
+#pragma unroll 10
+    for (int q = 0; q < S.P; ++q) m2 = fminf(m2, sq2(__fsub_rn(pn.x, ent[q].x), __fsub_rn(pn.y, ent[q].y)));
+    // 3. retire (data.py:236-247)
+    agent_retire_record(S, i, t, gc_arrive(S, f, pn, d, m2), false, pn, vn, an);
 }
 
 // one wave: agent of ordinal `ord` (< capacity) appears in frame `f`
@@ -359,70 +381,32 @@ __device__ __forceinline__ int wave_sum(int x) {
     return x;
 }
 
-__device__ __forceinline__ void rules_agent_step(const RulesKernelArgs& K, int i, long long t) {
-    const piml_scenario& S = K.S;
-    const piml_scenario_rules& R = K.R;
-    float2* P = (float2*)S.position;
-    float2* V = (float2*)S.velocity;
-    float2* Ac = (float2*)S.acceleration;
-    float2* Dst = (float2*)S.destination;
-    const long long tn = t + 1;
-    const bool rec = tn < S.T;
-    const size_t fr = (size_t)tn * S.capacity + i;
-    if (S.mask[i] == 0.f) {                                  // retired for good
-        if (rec) {
-            ((float2*)S.position_out)[fr] = make_float2(qnan(), qnan());
-            ((float2*)S.velocity_out)[fr] = make_float2(0.f, 0.f);
-            ((float2*)S.acceleration_out)[fr] = make_float2(0.f, 0.f);
-            ((float2*)S.destination_out)[fr] = make_float2(qnan(), qnan());
-            S.mask_out[fr] = 0.f;
-        }
-        return;
-    }
-    const float dt = S.dt;
-    const float2 p = P[i], v = V[i], a = Ac[i], d = Dst[i];
-    float2 an = K.a_next[i];
-    float2 vn = make_float2(__fadd_rn(v.x, __fmul_rn(a.x, dt)), __fadd_rn(v.y, __fmul_rn(a.y, dt)));
-    float2 pn = make_float2(__fadd_rn(p.x, __fmul_rn(v.x, dt)), __fadd_rn(p.y, __fmul_rn(v.y, dt)));
-    const int hw = S.hist_width;
-    float* h = S.hist_velocity + (size_t)i * hw;
-    float* so = S.self_features + (size_t)i * S.F;
-    for (int q = 0; q + 2 < hw; ++q) h[q] = h[q + 2];
-    h[hw - 2] = vn.x; h[hw - 1] = vn.y;
-    for (int q = 0; q < hw; ++q) so[2 + q] = h[q];
-    so[2 + hw] = an.x; so[3 + hw] = an.y; so[4 + hw] = S.desired_speed[i];
-
-    // 2. arrive: the scene's update (scenarios.py:67-69, 128-130, 159-160, 218-219, 286-287)
-    int f = S.flag[i];
-    bool gone = false;
+// 2. arrive: the scene's update (scenarios.py:67-69, 128-130, 159-160, 218-219, 286-287); gone: PIML_ARRIVE_XEXIT's exit
+__device__ __forceinline__ int rules_arrive(const piml_scenario& S, const piml_scenario_rules& R, int f, float2 pn, float2 d,
+                                            bool& gone) {
+    gone = false;
     if (R.arrival_rule == PIML_ARRIVE_RADIUS) f += norm2(__fsub_rn(pn.x, d.x), __fsub_rn(pn.y, d.y)) < S.arrival_radius;
     else if (R.arrival_rule == PIML_ARRIVE_XBAND) f += fabsf(__fsub_rn(pn.x, d.x)) < S.arrival_radius;
     else gone = pn.x > R.length;                             // PIML_ARRIVE_XEXIT: mask_p = 0
-    // 3. retire (data.py:236-247)
-    float2 dn = make_float2(qnan(), qnan());
-    gone = gone || f >= S.D;
-    if (!gone) {
-        dn = ((const float2*)S.waypoints)[(size_t)f * S.capacity + i];
-        gone = dn.x != dn.x || dn.y != dn.y;
+    return f;
+}
+
+__device__ __forceinline__ void rules_agent_step(const RulesKernelArgs& K, int i, long long t) {
+    const piml_scenario& S = K.S;
+    if (S.mask[i] == 0.f) {                                  // retired for good
+        record_retired(S, i, t);
+        return;
     }
-    float m = 1.f;
-    if (gone) {
-        pn = make_float2(qnan(), qnan());
-        dn = make_float2(qnan(), qnan());
-        vn = make_float2(0.f, 0.f);
-        an = make_float2(0.f, 0.f);
-        m = 0.f;
-    }
-    P[i] = pn; V[i] = vn; Ac[i] = an; Dst[i] = dn;
-    S.flag[i] = f;
-    S.mask[i] = m;
-    if (rec) {
-        ((float2*)S.position_out)[fr] = pn;
-        ((float2*)S.velocity_out)[fr] = vn;
-        ((float2*)S.acceleration_out)[fr] = an;
-        ((float2*)S.destination_out)[fr] = dn;
-        S.mask_out[fr] = m;
-    }
+    const float dt = S.dt;
+    const float2 p = ((const float2*)S.position)[i], v = ((const float2*)S.velocity)[i];
+    const float2 a = ((const float2*)S.acceleration)[i], d = ((const float2*)S.destination)[i];
+    const float2 an = K.a_next[i];
+    const float2 vn = make_float2(__fadd_rn(v.x, __fmul_rn(a.x, dt)), __fadd_rn(v.y, __fmul_rn(a.y, dt)));
+    const float2 pn = make_float2(__fadd_rn(p.x, __fmul_rn(v.x, dt)), __fadd_rn(p.y, __fmul_rn(v.y, dt)));
+    agent_history(S, i, vn, an);
+    bool gone;
+    const int f = rules_arrive(S, K.R, S.flag[i], pn, d, gone);
+    agent_retire_record(S, i, t, f, gone, pn, vn, an);           // 3. retire (data.py:236-247)
 }
 
 // 2 u - 1 of torch's (2 * torch.rand(n) - 1)
@@ -661,6 +645,137 @@ __global__ __launch_bounds__(256) void scenario_rules_members_kernel(const Rules
     rules_spawn_agent(S, R, n + j, j >= k1, f);
 }
 
+
+// ---- the MLAPM frame (piml_scenario_step_mlapm): the closed-form law of src/main_mlapm.py:18-36 drives the scene ----
+//
+// One launch per frame t -> t+1, every scene, grid.y = member (one member and its seed is the single run).  Blocks
+// 0 .. agent_blocks-1 hold one wave per slot i (4 per block); the rest are the spawn blocks of the members kernels, unchanged.
+// Per present slot i of member m: the member's sources are read from the RECORDS of frame t (position_out[t],
+// velocity_out[t]; the init launch or the previous frame wrote them), never from the state other waves overwrite in this
+// launch -- mlapm_fwd_kernel<ROLL> reads traj[t-1] and writes traj[t] the same way.  Sources: slots j < n_t = min(spawned,
+// capacity), retired ones NaN and skipped (skip_absent, main_mlapm's compaction); slots >= n_t are staged as NaN, the first
+// min(capacity, n_t + 64) of them, which puts every present source in the same packed / scalar lane of mlapm_tile_sum as a
+// piml_mlapm_step_fwd over all capacity rows, so the force is bitwise that call's.  Then
+//   F = (v0 e - v) / tau - sum (mlapm.py:21-58), v' = v + F dt (:57), p' = p + v' dt (main_mlapm.py:25, explicit Euler),
+//   a' = F; the history / self_features update, arrival, retirement and record of agent_step / rules_agent_step.
+// GC's exit distance is spread over the wave's lanes (the minimum is exact, so the order does not matter).
+// The frame index is *frame_counter + frame_offset, read and never written here: a captured graph of K frames carries
+// offsets 0 .. K-1 and one counter add of K, so a frame is one launch and nothing needs a grid-wide "last block" count.
+// Past the records (t + 1 >= T) a launch does nothing.  No atomics: the same parity ping-pong of the spawned count.
+
+constexpr int kMlScWaves = 4;
+
+struct MlapmScenarioArgs {
+    piml_scenario S;
+    piml_scenario_rules R;                                   // scenes other than GC
+    MlapmParams P;
+    int gc, agent_blocks, frame_offset;
+};
+
+__global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_kernel(const MlapmScenarioArgs K0,
+                                                                        const unsigned long long* __restrict__ seeds) {
+    __shared__ float4 tile[kMlTile];                         // agent blocks: the sources (px, py, vx, vy); spawn blocks: entries
+    __shared__ unsigned short ucy_ring[kMlScWaves][256];
+    static_assert(kScenarioLdsPoints * sizeof(float2) <= sizeof(tile), "the entry points fit the source tile");
+    piml_scenario S = K0.S;
+    const float2* no_a = nullptr;
+    member_view(S, no_a, (int)blockIdx.y, seeds[blockIdx.y]);
+    const MlapmParams& P = K0.P;
+    const long long t = *S.frame_counter + K0.frame_offset;
+    if (t + 1 >= S.T) return;                                // past the records: nothing to do
+    const long long n = S.spawned[t & 1];
+    const int cap = S.capacity;
+    if ((int)blockIdx.x < K0.agent_blocks) {
+        const int n_t = (int)min(n, (long long)cap);
+        if ((int)blockIdx.x * kMlScWaves >= n_t) return;     // (block-uniform) no slot of this block holds an agent yet
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int i = (int)blockIdx.x * kMlScWaves + wave;
+        const bool live = i < n_t && S.mask[i] != 0.f;       // wave-uniform
+        float2 pi = make_float2(0.f, 0.f), vi = pi, di = pi;
+        if (live) { pi = ((const float2*)S.position)[i]; vi = ((const float2*)S.velocity)[i]; di = ((const float2*)S.destination)[i]; }
+        float ex = di.x - pi.x, ey = di.y - pi.y;
+        const float en = fmaxf(norm2(ex, ey), 1e-12f);      // mlapm.py:21
+        ex /= en; ey /= en;
+        const float2* pt = (const float2*)S.position_out + (size_t)t * cap;
+        const float2* vt = (const float2*)S.velocity_out + (size_t)t * cap;
+        const int ns = min(cap, n_t + 64);
+        float sx = 0.f, sy = 0.f;
+        v2f acc2x = {0.f, 0.f}, acc2y = {0.f, 0.f};
+        for (int base = 0; base < ns; base += kMlTile) {
+            const int tn = min(kMlTile, ns - base);
+            __syncthreads();
+            for (int q = threadIdx.x; q < tn; q += kMlScWaves * 64) {
+                const int j = base + q;
+                float4 s = make_float4(qnan(), qnan(), qnan(), qnan());
+                if (j < n_t) {
+                    const float2 a = pt[j], b = vt[j];
+                    s = make_float4(a.x, a.y, b.x, b.y);
+                }
+                tile[q] = s;
+            }
+            __syncthreads();
+            if (!live) continue;
+            mlapm_tile_sum(P, tile, tn, lane, ucy_ring[uniform(wave)], pi, vi, ex, ey, sx, sy, acc2x, acc2y);
+        }
+        if (i >= n_t) return;
+        if (!live) {                                         // retired for good
+            if (lane == 0) record_retired(S, i, t);
+            return;
+        }
+        sx += acc2x.x + acc2x.y; sy += acc2y.x + acc2y.y;
+        sx = wave_sum(sx); sy = wave_sum(sy);
+        const float dt = S.dt;
+        const float v0i = S.desired_speed[i];
+        const float fx = (v0i * ex - vi.x) / P.tau - sx;     // :22, :29/:40/:53
+        const float fy = (v0i * ey - vi.y) / P.tau - sy;
+        const float2 vn = make_float2(vi.x + fx * dt, vi.y + fy * dt);          // :57
+        const float2 pn = make_float2(pi.x + vn.x * dt, pi.y + vn.y * dt);      // main_mlapm.py:25
+        const float2 an = make_float2(fx, fy);
+        const int f = S.flag[i];
+        float m2 = INFINITY;
+        if (K0.gc) {
+            const float2* ent = (const float2*)S.entries + (size_t)S.exit_idx[(size_t)f * cap + i] * S.P;
+            for (int q = lane; q < S.P; q += 64) m2 = fminf(m2, sq2(__fsub_rn(pn.x, ent[q].x), __fsub_rn(pn.y, ent[q].y)));
+            m2 = wave_min(m2);
+        }
+        if (lane == 0) {
+            agent_history(S, i, vn, an);
+            bool gone = false;
+            const int fn = K0.gc ? gc_arrive(S, f, pn, di, m2) : rules_arrive(S, K0.R, f, pn, di, gone);
+            agent_retire_record(S, i, t, fn, gone, pn, vn, an);
+        }
+        return;
+    }
+    // spawn blocks: scenario_step_members_kernel's / scenario_rules_members_kernel's (thresholds from the kernel arguments)
+    const long long f = t + 1;
+    int k1, k2 = 0;
+    const PhiloxOut w = philox4x32_10((unsigned)f, (unsigned)((unsigned long long)f >> 32), 0u,
+                                      K0.gc ? kScenarioStream : kRulesStream, (unsigned)S.seed, (unsigned)(S.seed >> 32));
+    k1 = threshold_count(w.x >> 8, K0.S.poisson_thresholds, S.spawn_cap);
+    if (!K0.gc) k2 = threshold_count(w.y >> 8, K0.R.poisson_thresholds2, K0.R.spawn_cap2);
+    const int k = k1 + k2;
+    if (blockIdx.x == (unsigned)K0.agent_blocks && threadIdx.x == 0) {
+        S.spawned[f & 1] = n + k;
+        *S.dropped = n + k > cap ? n + k - cap : 0;
+        if (S.spawn_out && f < S.T) S.spawn_out[f] = k;
+    }
+    const int j = (int)(blockIdx.x - K0.agent_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
+    if (K0.gc) {
+        const float2* ent = (const float2*)S.entries;
+        if (S.E * S.P <= kScenarioLdsPoints) {               // block-uniform, before any wave leaves
+            float2* lds_entries = (float2*)tile;
+            for (int q = threadIdx.x; q < S.E * S.P; q += blockDim.x) lds_entries[q] = ent[q];
+            __syncthreads();
+            ent = lds_entries;
+        }
+        if (j >= k || n + j >= cap) return;
+        spawn_agent(S, ent, n + j, f);
+    } else {
+        if (j >= k || n + j >= cap) return;
+        rules_spawn_agent(S, K0.R, n + j, j >= k1, f);
+    }
+}
+
 }  // namespace piml
 
 PIML_API int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, void* stream) {
@@ -821,5 +936,40 @@ PIML_API int piml_scenario_step_members(const piml_scenario* s, const piml_scena
         K.agent_blocks = agent_blocks;
         hipLaunchKernelGGL(piml::scenario_rules_members_kernel, grid, dim3(256), 0, piml::as_stream(stream), K, sd);
     }
+    return hipGetLastError();
+}
+
+
+PIML_API int piml_scenario_step_mlapm(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                                      const piml_mlapm_law* law, int frame_offset, void* stream) {
+    if (!s || !seeds || !law || members < 1 || members > 65535 || frame_offset < 0) return hipErrorInvalidValue;
+    const piml_scenario& S = *s;
+    const bool gc = !r || r->spawn_law == PIML_SPAWN_GC;
+    if (r) {
+        const bool gc_rule = r->arrival_rule == PIML_ARRIVE_GC;
+        if (r->spawn_law < PIML_SPAWN_GC || r->spawn_law > PIML_SPAWN_UNIT3 || r->arrival_rule < PIML_ARRIVE_GC ||
+            r->arrival_rule > PIML_ARRIVE_XEXIT || gc != gc_rule)
+            return hipErrorInvalidValue;
+    }
+    // the frame checks of the entries above (init = 1 there only waives a_next, which this frame does not take)
+    if (gc ? !gc_args_ok(S, nullptr, 1) : !rules_args_ok(S, *r, nullptr, 1)) return hipErrorInvalidValue;
+    const piml_mlapm_law& L = *law;
+    if (L.variant < 0 || L.variant > 2 || !std::isfinite(L.tau) || !(L.tau > 0.f) || !std::isfinite(L.A) ||
+        !std::isfinite(L.B) || !std::isfinite(L.C) || !std::isfinite(L.D) || !std::isfinite(L.theta_deg) ||
+        !std::isfinite(L.radius) || !(L.radius > 0.f))
+        return hipErrorInvalidValue;
+    piml::MlapmScenarioArgs K;
+    K.S = S;
+    if (r) K.R = *r;
+    else memset(&K.R, 0, sizeof(K.R));
+    K.P = piml::make_params(L.variant, L.tau, L.A, L.B, L.C, L.D, L.theta_deg, L.radius, 1);
+    K.gc = gc;
+    K.agent_blocks = (S.capacity + piml::kMlScWaves - 1) / piml::kMlScWaves;
+    K.frame_offset = frame_offset;
+    const int waves = S.spawn_cap + (gc ? 0 : r->spawn_cap2);
+    const int spawn_blocks = waves > 0 ? (waves + 3) / 4 : 1;   // >= 1: block agent_blocks writes each member's count
+    const dim3 grid((unsigned)(K.agent_blocks + spawn_blocks), (unsigned)members);
+    hipLaunchKernelGGL(piml::scenario_mlapm_kernel, grid, dim3(piml::kMlScWaves * 64), 0, piml::as_stream(stream), K,
+                       (const unsigned long long*)seeds);
     return hipGetLastError();
 }

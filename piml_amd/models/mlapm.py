@@ -1,5 +1,6 @@
 """`MLAPM`: the closed-form social-force law (reference src/models/mlapm.py), same constructor
-and `step` signature, evaluated by the HIP pair kernel with an analytic backward."""
+and `step` signature, evaluated by the HIP pair kernel with an analytic backward.  `simulate_scenario` /
+`simulate_ensemble` drive the open-world scenes of piml_amd.scenarios with it (one launch per frame)."""
 from .. import ops
 
 
@@ -118,3 +119,89 @@ class MLAPM:
             for _ in range(steps - done):
                 one()
         return traj_p, traj_v
+
+    # ---- open-world scenes (piml_scenario_step_mlapm): the law in place of a PINNSF, same arrivals ----
+    def _law(self, radius):
+        from .. import ops_scenario
+        a = self.args
+        return ops_scenario.mlapm_law(a['version'], a['tau'], a['A'], a['B'], a.get('C', 0.0), a.get('D', 0.0),
+                                      a.get('theta', 0.0), radius)
+
+    def simulate_scenario(self, scenario, frames, seed=0, capacity=None, use_graph=None, radius=0.3, device='cuda',
+                          hist_width=2, frames_per_graph=8):
+        """Simulate `frames` frames of an entry / exit scene (piml_amd.scenarios: gc_scenario() or a scene of SCENARIOS)
+        with this law, as BaseSimulator.simulate_scenario does with a PINNSF: frame 0 spawns the initial agents, every
+        further frame is ONE launch -- MLAPM.step's force from the agents present in the frame (main_mlapm.py:18-36),
+        v' = v + F dt, p' = p + v' dt, a' = F -- followed by the scene's arrivals, exits and Poisson spawns, which depend
+        on (seed, frame, ordinal) only: a PINNSF run of the same seed and capacity sees the same arrivals.
+        radius: MLAPM's UCY collision radius (mlapm.py:42-46), NOT the scene's arrival radius.  capacity: default
+        scenarios.default_capacity, as the PINNSF path.  use_graph (None: more than 8 frames): `frames_per_graph` frames
+        per captured graph, replayed.  hist_width: the velocity history kept for the self_features columns.
+        Limits of the reference's law, restated: no obstacle or wall term (the square's obstacle points are not felt;
+        GC agents pass the pillar by their waypoints), and an agent at rest sees nobody (view is v . r > 0).
+        Returns a scenarios.ScenarioResult."""
+        from .. import scenarios
+        sc, T, cap, st = self._scenario_setup(scenario, frames, capacity, device, hist_width, seed=seed)
+        self._run_scenario(st, T, self._law(radius), use_graph, frames_per_graph)
+        last = int(st.t.item())
+        return scenarios.ScenarioResult(
+            position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res, mask_p=st.mask_res,
+            waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles, time_unit=sc.time_unit,
+            spawned=int(st.spawned[last & 1].item()), dropped=int(st.dropped.item()), spawn_count=st.spawn_count,
+            capacity=cap, seed=int(seed), state=st)
+
+    def simulate_ensemble(self, scenario, frames, seeds, capacity=None, use_graph=None, radius=0.3, device='cuda',
+                          hist_width=2, frames_per_graph=8):
+        """simulate_scenario for every seed of `seeds` in the same launches (grid.y = member; members never see each
+        other).  Member m is bitwise simulate_scenario(seed=seeds[m]) with the same capacity.  Returns a
+        scenarios.ScenarioEnsemble."""
+        from .. import scenarios
+        seeds = [int(x) for x in seeds]
+        if not seeds:
+            raise ValueError('simulate_ensemble: at least one seed expected')
+        sc, T, cap, st = self._scenario_setup(scenario, frames, capacity, device, hist_width, seeds=seeds)
+        self._run_scenario(st, T, self._law(radius), use_graph, frames_per_graph)
+        last = int(st.t.item())
+        return scenarios.ScenarioEnsemble(
+            seeds=seeds, position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res,
+            mask_p=st.mask_res, waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles,
+            time_unit=sc.time_unit, spawned=st.spawned[:, last & 1].tolist(), dropped=st.dropped.tolist(),
+            spawn_count=st.spawn_count, capacity=cap, state=st)
+
+    def _scenario_setup(self, scenario, frames, capacity, device, hist_width, **state_kw):
+        import torch
+        from .. import ops_scenario, scenarios
+        sc = scenario.to(torch.device(device))
+        T = int(frames)
+        if T < 1:
+            raise ValueError(f'frames must be >= 1, got {frames}')
+        cap = scenarios.default_capacity(sc, T) if capacity is None else int(capacity)
+        st = ops_scenario.scenario_state(sc, cap, T, int(hist_width), **state_kw)
+        return sc, T, cap, st
+
+    def _run_scenario(self, st, T, law, use_graph, frames_per_graph):
+        """frame 0's spawn, then T - 1 MLAPM frames: K = frames_per_graph of them (offsets 0 .. K-1 and one counter add)
+        captured into one graph and replayed when use_graph, the rest eagerly."""
+        import torch
+        from .. import ops_scenario, hip_graphs_safe
+        with torch.no_grad():
+            ops_scenario.scenario_step(st, init=True)                 # frame 0: generate(n_initial)
+            steps = T - 1
+            if use_graph is None:
+                use_graph = steps > 8
+            per = max(1, int(frames_per_graph))
+            done = 0
+            if use_graph and steps >= per + 1 and hip_graphs_safe():
+                ops_scenario.scenario_step_mlapm(st, law)             # a real frame, also warms the library up
+                done = 1
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    for k in range(per):
+                        ops_scenario.scenario_step_mlapm(st, law, frame_offset=k, advance=False)
+                    st.t.add_(per)
+                for _ in range((steps - done) // per):
+                    graph.replay()
+                done += (steps - done) // per * per
+            for _ in range(steps - done):
+                ops_scenario.scenario_step_mlapm(st, law)

@@ -1,11 +1,12 @@
 """Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_step_rules,
-piml_scenario_step_members, piml_scenario_route).
+piml_scenario_step_members, piml_scenario_step_mlapm, piml_scenario_route).
 
 `scenario_state` allocates the persistent (static-address) buffers of one simulation and the `piml_scenario` descriptor
 that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive, retire, spawn, record), with the
 frame index read from device memory so that one captured launch serves every frame of a replayed graph.  Like every
 operator of piml_amd they require GPU tensors and raise PimlHipError otherwise."""
 import ctypes
+import math
 import types
 
 import torch
@@ -160,3 +161,50 @@ def scenario_step(st, a_next=None, init=False):
             _lib.check(_lib.lib().piml_scenario_step_rules(ctypes.byref(st.desc), ctypes.byref(st.rules),
                                                            _ptr(a_next) if not init else None, int(bool(init)), _stream()),
                        'piml_scenario_step_rules')
+
+
+def mlapm_law(version='GC', tau=0.5, A=7.55, B=-3.0, C=0.2, D=-0.3, theta=56.0, radius=0.3):
+    """The piml_mlapm_law of MLAPM(version, tau, A, B, C, D, theta) (defaults: src/main_mlapm.py:16's constants).
+    radius is MLAPM.step's (the UCY collision radius, mlapm.py:42-46), not the scene's arrival radius.  ValueError for an
+    unknown version, tau not finite and > 0, a non-finite constant or radius not finite and > 0."""
+    from .ops import MLAPM_VARIANTS
+    if version not in MLAPM_VARIANTS:
+        raise ValueError(f'MLAPM version {version!r} unknown (one of {sorted(MLAPM_VARIANTS)})')
+    vals = dict(tau=tau, A=A, B=B, C=C, D=D, theta=theta, radius=radius)
+    for k, x in vals.items():
+        if not math.isfinite(float(x)):
+            raise ValueError(f'MLAPM {k} = {x} is not finite')
+    if not float(tau) > 0 or not float(radius) > 0:
+        raise ValueError(f'MLAPM tau and radius must be > 0, got tau={tau}, radius={radius}')
+    law = _lib.MlapmLaw()
+    law.variant = MLAPM_VARIANTS[version]
+    law.tau, law.A, law.B, law.C, law.D = float(tau), float(A), float(B), float(C), float(D)
+    law.theta_deg, law.radius = float(theta), float(radius)
+    return law
+
+
+def scenario_step_mlapm(st, law, frame_offset=0, advance=True):
+    """One launch: frame t -> t + 1 of st (single or ensemble state) under the MLAPM law `law` (mlapm_law(...)), t =
+    st.t + frame_offset: the force of MLAPM.step from the agents present in frame t's records, v' = v + F dt, p' = p + v' dt
+    (src/main_mlapm.py:18-36), a' = F, then the scene's arrivals, exits and spawns as scenario_step.  advance: add 1 to
+    st.t afterwards (the kernel reads the counter, never writes it; a captured run of K frames passes offsets 0 .. K-1 and
+    advances once by K).  Frame 0's spawn is scenario_step(st, init=True), which does not depend on the law."""
+    if not isinstance(law, _lib.MlapmLaw):
+        raise TypeError(f'law: an ops_scenario.mlapm_law(...) expected, got {type(law).__name__}')
+    if int(frame_offset) < 0:
+        raise ValueError(f'frame_offset must be >= 0, got {frame_offset}')
+    if st.members is not None:
+        members, seeds = st.members, st.seeds
+    else:
+        seeds = getattr(st, 'seed_dev', None)
+        if seeds is None:                                    # the single run is member 0 of a one-member launch
+            bits = (st.seed & 0xFFFFFFFFFFFFFFFF) - ((st.seed & 0x8000000000000000) << 1)
+            seeds = st.seed_dev = torch.tensor([bits], device=st.p.device, dtype=torch.long)
+        members = 1
+    with torch.cuda.device(st.p.device):
+        _lib.check(_lib.lib().piml_scenario_step_mlapm(ctypes.byref(st.desc),
+                                                       ctypes.byref(st.rules) if st.rules is not None else None,
+                                                       members, _ptr(seeds), ctypes.byref(law), int(frame_offset),
+                                                       _stream()), 'piml_scenario_step_mlapm')
+        if advance:
+            st.t.add_(1)

@@ -1,9 +1,11 @@
-"""Open-world crowd simulation with a trained PINNSF: generate a scene (default: the Grand Central hall; --scenario crosswalk,
-four_directional_square, basic_unit1..3 for the reference's synthetic scenes), simulate it on
-the GPU and save the result as a v2.2 clip that `RawData.load_trajectory_data` (and so `--iter_flag` pre-training) reads.
+"""Open-world crowd simulation with a trained PINNSF or the closed-form MLAPM law: generate a scene (default: the Grand
+Central hall; --scenario crosswalk, four_directional_square, basic_unit1..3 for the reference's synthetic scenes), simulate
+it on the GPU and save the result as a v2.2 clip that `RawData.load_trajectory_data` (and so `--iter_flag` pre-training)
+reads.
 
     python -m piml_amd.simulate --checkpoint model.pt --frames 750 --out clip.npy [model flags of piml_amd.main]
     python -m piml_amd.simulate --seeds 0:32 --out 'gc_{seed}.npy'      (an ensemble: every seed in one launch per frame)
+    python -m piml_amd.simulate --law mlapm --params params.json --out clip.npy     (MLAPM; params: `calibrate --out`)
 
 Model flags (--model, --hidden sizes, --topk_*, --num_history_velocity, ...) are those of `piml_amd.main`, with its
 defaults.  Without --checkpoint the network keeps its initial weights (a smoke run)."""
@@ -21,8 +23,15 @@ from .functions import metrics as METRIC  # noqa: E402
 
 
 def get_args(argv=None):
-    p = argparse.ArgumentParser(description='open-world crowd simulation with a trained PINNSF')
+    p = argparse.ArgumentParser(description='open-world crowd simulation with a trained PINNSF or the MLAPM law')
+    p.add_argument('--law', type=str, default='pinnsf', choices=['pinnsf', 'mlapm'],
+                   help='force model: the network (default) or the closed-form MLAPM law')
     p.add_argument('--checkpoint', type=str, default='', help='state_dict of the model (torch.save); "" = initial weights')
+    p.add_argument('--params', type=str, default=None,
+                   help="--law mlapm: the JSON `calibrate --out` writes (version and the six constants); default "
+                        "main_mlapm.py's constants, version GC")
+    p.add_argument('--mlapm_radius', type=float, default=0.3,
+                   help="--law mlapm: MLAPM's UCY collision radius (not the scene's arrival radius)")
     p.add_argument('--scenario', type=str, default='gc', choices=sorted(SCENARIOS.SCENARIOS))
     p.add_argument('--frames', type=int, default=750)
     seed = p.add_mutually_exclusive_group()
@@ -42,8 +51,42 @@ def get_args(argv=None):
             p.error(f'--seeds: {ex}')
         if '{seed}' not in own.out:
             p.error("--seeds: --out must contain '{seed}' (one clip per seed)")
+    if own.law == 'mlapm':
+        if own.checkpoint:
+            p.error('--checkpoint is a PINNSF state_dict: not with --law mlapm (use --params)')
+        try:
+            own.mlapm = load_mlapm_params(own.params)
+        except (OSError, ValueError) as ex:
+            p.error(f'--params: {ex}')
+    elif own.params is not None:
+        p.error('--params needs --law mlapm')
     model_args = MAIN.get_args(rest)
     return own, model_args
+
+
+def load_mlapm_params(path):
+    """MLAPM's constructor arguments from the JSON `python -m piml_amd.calibrate --out` writes ({'version', 'tau', 'A',
+    'B', 'C', 'D', 'theta'}); constants the file leaves out keep calibrate.DEFAULT_INIT's values (main_mlapm.py:16), and
+    path None is those constants with version GC.  ValueError on an unknown version, an unknown key or a non-number."""
+    import json
+    from . import calibrate, ops
+    params = {'version': 'GC', **calibrate.DEFAULT_INIT}
+    if path is None:
+        return params
+    with open(path) as fh:
+        got = json.load(fh)
+    if not isinstance(got, dict):
+        raise ValueError(f'{path}: a JSON object expected')
+    unknown = sorted(set(got) - {'version', *calibrate.PARAM_NAMES})
+    if unknown:
+        raise ValueError(f'{path}: unknown keys {unknown} (expected version and {list(calibrate.PARAM_NAMES)})')
+    if got.get('version', 'GC') not in ops.MLAPM_VARIANTS:
+        raise ValueError(f"{path}: unknown version {got.get('version')!r} (one of {sorted(ops.MLAPM_VARIANTS)})")
+    for k in calibrate.PARAM_NAMES:
+        if k in got and (isinstance(got[k], bool) or not isinstance(got[k], (int, float))):
+            raise ValueError(f'{path}: {k} = {got[k]!r} is not a number')
+    params.update(got)
+    return params
 
 
 def parse_seeds(text):
@@ -74,27 +117,33 @@ def _report(tag, frames, res, threshold, out, soft=None, hard=None):
 
 def main(argv=None):
     own, args = get_args(argv)
-    from .models.simulators import BaseSimulator
     MAIN.set_exp_configs(args)
-    # the feature widths piml_amd.data.dataset sets from a clip: 6-wide neighbour rows, self = (dest, history, a, v0)
-    args.ped_feature_dim = args.obs_feature_dim = 6
-    args.self_feature_dim = 5 + 2 * args.num_history_velocity
-    sim = BaseSimulator(args)
-    if own.checkpoint:
-        sim.model.load_state_dict(torch.load(own.checkpoint, map_location=args.device))
-    sim.model.eval()
+    if own.law == 'mlapm':
+        from .models.mlapm import MLAPM
+        sim = MLAPM(**own.mlapm)
+        run_kw = dict(radius=own.mlapm_radius, device=args.device, hist_width=2 * args.num_history_velocity)
+    else:
+        from .models.simulators import BaseSimulator
+        # the feature widths piml_amd.data.dataset sets from a clip: 6-wide neighbour rows, self = (dest, history, a, v0)
+        args.ped_feature_dim = args.obs_feature_dim = 6
+        args.self_feature_dim = 5 + 2 * args.num_history_velocity
+        sim = BaseSimulator(args)
+        if own.checkpoint:
+            sim.model.load_state_dict(torch.load(own.checkpoint, map_location=args.device))
+        sim.model.eval()
+        run_kw = {}
     kw = {} if own.uniform_desired_speed is None else {'uniform_desired_speed': own.uniform_desired_speed}
     scenario = SCENARIOS.SCENARIOS[own.scenario](time_unit=own.time_unit, **kw)
     if own.seeds is not None:
-        return _ensemble(sim, scenario, own, args)
-    res = sim.simulate_scenario(scenario, own.frames, seed=own.seed, capacity=own.capacity)
+        return _ensemble(sim, scenario, own, args, run_kw)
+    res = sim.simulate_scenario(scenario, own.frames, seed=own.seed, capacity=own.capacity, **run_kw)
     res.save_data(own.out)
     _report(own.scenario, own.frames, res, args.collision_threshold, own.out)
     return res
 
 
-def _ensemble(sim, scenario, own, args):
-    ens = sim.simulate_ensemble(scenario, own.frames, own.seeds, capacity=own.capacity)
+def _ensemble(sim, scenario, own, args, run_kw):
+    ens = sim.simulate_ensemble(scenario, own.frames, own.seeds, capacity=own.capacity, **run_kw)
     paths = ens.save_data(own.out)
     soft = ens.collision_counts(args.collision_threshold)
     hard = ens.collision_counts(args.collision_threshold / 2)
