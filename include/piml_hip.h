@@ -482,6 +482,8 @@ int piml_rollout_step_ksum(const float* pred_ped, int kp, const float* pred_obs,
  * arrivals (src/data/scenarios.py:313-401), utils.route (src/utils/utils.py:141-165) -- and the frame protocol of
  * RawData.add_frame / add_pedestrians (src/data/data.py:206-303), one launch per frame.  Storage is append-only: the agent
  * of global ordinal n lives in slot n (as add_pedestrians appends); ordinals >= capacity are dropped, counted, never written.
+ * This block is the frame that piml_scenario_step, piml_scenario_step_rules and piml_scenario_step_members share (one
+ * kernel); piml_scenario_step runs it under GC's rule, the other two state what they change.
  *
  * init == 0, frame t -> t+1 (t = *frame_counter, read on the device):
  *   every slot i < min(spawned[t & 1], capacity) with mask[i] == 1: v' = v + a dt, p' = p + v dt, a' = a_next[i]; the
@@ -528,10 +530,11 @@ typedef struct piml_scenario {
 int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, void* stream);
 
 /*
- * Scene rules of piml_scenario_step_rules (ABI 35, additive): the reference's synthetic scenes (src/data/scenarios.py:9-311,
- * crosswalk / four_directional_square / basic_unit1..3) in place of GC's entry pairs, route and exit distance.
+ * Scene rules of piml_scenario_step_rules (ABI 35, additive): piml_scenario_step's frame with the reference's synthetic
+ * scenes (src/data/scenarios.py:9-311, crosswalk / four_directional_square / basic_unit1..3) in place of GC's entry pairs,
+ * route and exit distance.
  * spawn_law (what a new agent of ordinal n looks like; word layout in piml_amd/csrc/scenario.hip):
- *   PIML_SPAWN_GC          GC (scenarios.py:369-387): piml_scenario_step itself, arrival_rule must be PIML_ARRIVE_GC
+ *   PIML_SPAWN_GC          GC (scenarios.py:369-387): piml_scenario_step, arrival_rule must be PIML_ARRIVE_GC
  *   PIML_SPAWN_CROSSWALK   scenarios.py:36-65: |x| = length/2 + 3u on a coin side, y = +-width/2 on a coin side,
  *                          waypoints (-side_x length/2, +-width/2 by a coin) and (same x, 3 y), heading (0, -side_y)
  *   PIML_SPAWN_SQUARE      scenarios.py:87-134: the init launch's n_initial = 4 grid^2 agents on the four blocks of
@@ -546,8 +549,7 @@ int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, vo
  * piml_scenario_step (flag == D or waypoint[flag] NaN; or the x exit).
  * initial_velocity: 0 = v0 vector 0, 1 = heading * v0 (the velocity of the spawn frame and the newest history slot; older
  * slots 0).  speed_clamp: 1 = v0 = max(speed_min, speed_mean + speed_std z), 0 = no clamp (uniform_speed: v0 = speed_mean).
- * entries, route_polyline and exit_idx are not read (may be NULL).  Same frame protocol, determinism and capture as
- * piml_scenario_step.
+ * entries, route_polyline and exit_idx are not read (may be NULL).
  * hipErrorInvalidValue: s or r NULL; the checks of piml_scenario_step except D (1..8 here, >= 2 for the crosswalk) and
  * E, P, R, route_max_iters, entries, route_polyline, exit_idx; spawn_law / arrival_rule unknown or one GC and the other
  * not; initial_velocity or speed_clamp not 0 / 1; spawn_cap2 outside 0..8 or non-zero for a law other than UNIT3;
@@ -569,7 +571,8 @@ int piml_scenario_step_rules(const piml_scenario* s, const piml_scenario_rules* 
                              void* stream);
 
 /*
- * Ensembles (ABI 35, additive): `members` simulations of one scene, one frame of each in one launch (grid.y = member).
+ * Ensembles (ABI 35, additive): piml_scenario_step's frame for `members` simulations of one scene in one launch
+ * (grid.y = member; the single-run entries are one member).
  * s's per-member pointers are the bases of member-major buffers whose member-m slice has exactly the single-scene layout:
  * state (members, capacity, .) -- position, velocity, acceleration, destination, hist_velocity, self_features,
  * desired_speed, mask, flag, spawn_iters --, waypoints (members, D, capacity, 2), exit_idx (members, D, capacity),
@@ -577,7 +580,7 @@ int piml_scenario_step_rules(const piml_scenario* s, const piml_scenario_rules* 
  * a_next (members, capacity, 2).  frame_counter, entries, route_polyline, both threshold tables and every scalar are
  * shared.  s->seed is ignored: member m's Philox key is seeds[m] (device memory, (members)).  r = NULL is GC's rule
  * (piml_scenario_step); otherwise as piml_scenario_step_rules.  Member m is bitwise what piml_scenario_step[_rules]
- * gives with seed = seeds[m]; no atomics, the parity ping-pong is per member; capturable as the single entries.
+ * gives with seed = seeds[m]; the parity ping-pong is per member.
  * hipErrorInvalidValue (before any launch): every check of piml_scenario_step / piml_scenario_step_rules, members
  * outside 1..65535, NULL seeds.
  */

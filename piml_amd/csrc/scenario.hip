@@ -1,25 +1,32 @@
 // Open-world scenario frame: integrate, arrive, retire, spawn and record one simulated frame of a scene whose agents are not
-// recorded but generated -- the Grand Central hall of the reference (src/data/scenarios.py:313-401, GC()), driven by the
-// frame protocol of RawData.add_frame / add_pedestrians (src/data/data.py:206-303).  One launch per frame, no host sync:
-// a whole simulation replays as one captured frame (the frame counter and the spawn count live in device memory).
+// recorded but generated -- the Grand Central hall of the reference (src/data/scenarios.py:313-401, GC()) and its synthetic
+// scenes (scenarios.py:9-311), driven by the frame protocol of RawData.add_frame / add_pedestrians (src/data/data.py:206-303).
+// One launch per frame, no host sync: a whole simulation replays as one captured frame (the frame counter and the spawn
+// count live in device memory).
 //
-// Frame t -> t+1 (piml_scenario_step, init == 0):
+// Every network-driven entry (piml_scenario_step, piml_scenario_step_rules, piml_scenario_step_members) launches the one
+// frame kernel, scenario_frame_kernel<kGC>: kGC is GC's rule (entry points, route, exit distance), otherwise a scene rule of
+// piml_scenario_rules.  Grid (agent blocks + spawn blocks, members): a single run is one member whose Philox key is S.seed,
+// member m of an ensemble has key seeds[m] (member_view below).
+// Frame t -> t+1 (init == 0):
 //   agents   (one thread per slot i < min(n_t, capacity), n_t = agents spawned through frame t)
 //     1. integrate  v' = v + a dt, p' = p + v dt (the lagged Euler of rollout_step_agent, pairwise.hip), a' = a_next; the
 //                   velocity history shifts and columns 2.. of the self_features row get (history, a', v0);
-//     2. arrive     GC's update (scenarios.py:376-384): dis2des = |p' - dest|, dis2exit = min over the points of entry
-//                   exit(dest) of |p' - e|, exit(w) = the entry whose points come nearest waypoint w (computed once at spawn);
-//                   flag += 1 if either is below arrival_radius (at most once per frame);
+//     2. arrive     GC (scenarios.py:376-384): dis2des = |p' - dest|, dis2exit = min over the points of entry exit(dest) of
+//                   |p' - e|, exit(w) = the entry whose points come nearest waypoint w (computed once at spawn); flag += 1
+//                   if either is below arrival_radius (at most once per frame).  A scene rule: |p' - dest| < r or
+//                   |p'.x - dest.x| < r -> flag += 1, or retire when p'.x > length;
 //     3. retire     add_frame (data.py:236-247): flag == D or waypoint[flag] NaN -> p, dest = NaN, v, a = 0, mask 0, for
 //                   good; otherwise dest = waypoint[flag];
-//   spawn    (one wave per new agent j < k_{t+1} <= spawn_cap, ordinal n_t + j; ordinals >= capacity are dropped)
-//     4. k ~ Poisson(rate dt) by inversion, origin / destination entries distinct and uniform (random.sample(entry, 2)),
+//   spawn    (one wave per new agent j < k_{t+1}, ordinal n_t + j; ordinals >= capacity are dropped)
+//     4. GC: k ~ Poisson(rate dt) by inversion, origin / destination entries distinct and uniform (random.sample(entry, 2)),
 //        a point index uniform in 0..P-1 and an offset U[0,1)^2 * spawn_offset for each, waypoints (r, d) = route(o, d)
-//        (lanes over the polyline's segments), v0 = max(speed_min, speed_mean + speed_std z) (or speed_mean), v = a = 0;
+//        (lanes over the polyline's segments), v0 = max(speed_min, speed_mean + speed_std z) (or speed_mean), v = a = 0.
+//        A scene rule: k1 + k2 agents of its spawn law (below);
 //   5. record frame t+1's p, v, a, dest, mask into the (T, capacity, .) buffers (skipped from t+1 = T on).
 // init == 1 spawns the n_initial agents (ordinals 0 .. n_initial-1) into frame t through the same path (GC's generate(20)).
 //
-// Randomness: Philox4x32-10 (philox.hpp), key = (seed lo, seed hi).  Counter words (c0, c1, c2, c3):
+// GC's randomness: Philox4x32-10 (philox.hpp), key = (seed lo, seed hi).  Counter words (c0, c1, c2, c3):
 //   spawn count of frame f      (f lo, f hi, 0, 0x5CE00000): word 0 >> 8 = u24; k = #{j < spawn_cap : u24 >= thr[j]},
 //                               thr[j] = ceil(2^24 P(K <= j)) computed by the host (the documented cap: P(K > 8 | 0.4) ~ 1e-10)
 //   agent of ordinal n, call 1  (n lo, n hi, 0, 0x5CE00001): origin entry (w0 E) >> 32; destination entry (w1 (E-1)) >> 32,
@@ -31,10 +38,7 @@
 // The dropout keep-mask stream uses c3 = (stream_id << 16) | sub with stream ids 0 and 1: stream 0x5CE0 is never one of
 // them.  The schedule depends on (seed, frame, ordinal) only, not on the dynamics; tests/scenario_ref.py restates it.
 //
-// Scene rules (piml_scenario_step_rules, piml_scenario_rules): the reference's synthetic scenes (scenarios.py:9-311) run
-// scenario_rules_kernel, which GC never reaches (GC's rules go to scenario_step_kernel above, unchanged).  Same frame order;
-// step 2 is the rule's (|p' - dest| < r, |p'.x - dest.x| < r, or retire when p'.x > length) and step 4 is the spawn law's.
-// Its Philox stream is c3 = 0x5CE10000 | sub (key = (seed lo, seed hi), the float of a word is (w >> 8) 2^-24 =: u(w),
+// A scene rule's randomness: c3 = 0x5CE10000 | sub (key = (seed lo, seed hi), the float of a word is (w >> 8) 2^-24 =: u(w),
 // a coin is w >> 31):
 //   spawn counts of frame f     (f lo, f hi, 0, 0x5CE10000): stream 1 k1 from word 0 >> 8 against thresholds,
 //                               stream 2 k2 (UNIT3) from word 1 >> 8 against thresholds2; the frame's first k1 new
@@ -51,20 +55,28 @@
 //   square cell c's key         (c, 0, 0, 0x5CE10003) word 0: randperm(grid^2)[c] = rank of key c among the grid^2 keys,
 //                               ties by cell index (each init wave counts its own cell's rank)
 //
-// Determinism: no atomics.  The spawned count is ping-ponged by frame parity (spawned[t & 1] read, spawned[(t+1) & 1]
-// written by one thread), so no workgroup reads a value another one writes in the same launch; spawned agents take slots
-// >= n_t, which no agent thread touches.
+// Members: the descriptor's per-member pointers are the bases of member-major buffers, member m's slice of each having
+// exactly the single-run layout -- state (members, capacity, .), waypoints (members, D, capacity, 2), exit_idx
+// (members, D, capacity), recorded outputs (members, T, capacity, .), spawn_out (members, T), spawned (members, 2),
+// dropped (members), a_next (members, capacity, 2).  frame_counter, entries, route_polyline, both threshold tables and
+// every scalar are shared.  A block builds member blockIdx.y's view of the descriptor (member_view; a no-op for member 0)
+// and runs the frame on it, so member m is bitwise the single run with seed = seeds[m].
+//
+// Determinism: no atomics.  The spawned count is ping-ponged by frame parity per member (spawned[t & 1] read,
+// spawned[(t+1) & 1] written by one thread of block agent_blocks), so no workgroup reads a value another one writes in the
+// same launch; spawned agents take slots >= n_t, which no agent thread touches, and no block touches another member's slices.
 #include "common.hpp"
 #include "mlapm.hpp"
 #include "philox.hpp"
 #include "../../include/piml_hip.h"
 
 #include <cmath>
-#include <cstring>
 
 namespace piml {
 
 constexpr unsigned kScenarioStream = 0x5CE00000u;
+constexpr unsigned kRulesStream = 0x5CE10000u;
+constexpr int kRulesMaxGrid = 32;
 constexpr int kScenarioMaxSpawn = 8;       // spawn_cap bound (the Poisson inversion's cap)
 constexpr int kScenarioMaxD = 8;
 constexpr int kScenarioMaxIters = 64;
@@ -89,6 +101,19 @@ __device__ __forceinline__ float wave_min(float x) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) x = fminf(x, __shfl_xor(x, o, 64));
     return x;
+}
+
+__device__ __forceinline__ int wave_sum(int x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// the spawn count of a Poisson draw u24 by inversion: #{j < cap : u >= thr[j]}
+__device__ __forceinline__ int threshold_count(unsigned u, const uint32_t* thr, int cap) {
+    int k = 0;
+    for (int j = 0; j < cap; ++j) k += u >= thr[j];
+    return k;
 }
 
 // utils.route (src/utils/utils.py:141-165) for one (o, d) pair, one wave: every iteration tests the segment o -> r against
@@ -151,21 +176,6 @@ __device__ int nearest_entry_wave(float2 q, const float2* entries, int E, int P)
     return be;
 }
 
-struct ScenarioKernelArgs {
-    piml_scenario S;
-    const float2* a_next;
-    int init, agent_blocks;
-};
-
-__device__ __forceinline__ int poisson_count(const piml_scenario& S, long long frame) {
-    const PhiloxOut w = philox4x32_10((unsigned)frame, (unsigned)((unsigned long long)frame >> 32), 0u, kScenarioStream,
-                                      (unsigned)S.seed, (unsigned)(S.seed >> 32));
-    const unsigned u = w.x >> 8;
-    int k = 0;
-    for (int j = 0; j < S.spawn_cap; ++j) k += u >= S.poisson_thresholds[j];
-    return k;
-}
-
 // frame t+1's record of a slot retired for good
 __device__ __forceinline__ void record_retired(const piml_scenario& S, int i, long long t) {
     const long long tn = t + 1;
@@ -193,6 +203,16 @@ __device__ __forceinline__ void agent_history(const piml_scenario& S, int i, flo
 __device__ __forceinline__ int gc_arrive(const piml_scenario& S, int f, float2 pn, float2 d, float m2) {
     const bool near = norm2(__fsub_rn(pn.x, d.x), __fsub_rn(pn.y, d.y)) < S.arrival_radius || sqrtf(m2) < S.arrival_radius;
     return near ? f + 1 : f;
+}
+
+// 2. arrive, a scene rule (scenarios.py:67-69, 128-130, 159-160, 218-219, 286-287); gone: PIML_ARRIVE_XEXIT's exit
+__device__ __forceinline__ int rules_arrive(const piml_scenario& S, const piml_scenario_rules& R, int f, float2 pn, float2 d,
+                                            bool& gone) {
+    gone = false;
+    if (R.arrival_rule == PIML_ARRIVE_RADIUS) f += norm2(__fsub_rn(pn.x, d.x), __fsub_rn(pn.y, d.y)) < S.arrival_radius;
+    else if (R.arrival_rule == PIML_ARRIVE_XBAND) f += fabsf(__fsub_rn(pn.x, d.x)) < S.arrival_radius;
+    else gone = pn.x > R.length;                             // PIML_ARRIVE_XEXIT: mask_p = 0
+    return f;
 }
 
 // 3. retire (data.py:236-247) with the flag f after step 2 (gone: the rule retired the agent itself), then slot i's state
@@ -229,8 +249,10 @@ __device__ __forceinline__ void agent_retire_record(const piml_scenario& S, int 
     }
 }
 
-__device__ __forceinline__ void agent_step(const ScenarioKernelArgs& K, const float2* entries, int i, long long t) {
-    const piml_scenario& S = K.S;
+// steps 1-3 and the record of slot i (member view S, the network's a_next); entries: GC's entry points (LDS or global)
+template <bool kGC>
+__device__ __forceinline__ void agent_step(const piml_scenario& S, const piml_scenario_rules& R, const float2* a_next,
+                                           const float2* entries, int i, long long t) {
     if (S.mask[i] == 0.f) {                                  // retired for good
         record_retired(S, i, t);
         return;
@@ -238,19 +260,23 @@ __device__ __forceinline__ void agent_step(const ScenarioKernelArgs& K, const fl
     const float dt = S.dt;
     const float2 p = ((const float2*)S.position)[i], v = ((const float2*)S.velocity)[i];
     const float2 a = ((const float2*)S.acceleration)[i], d = ((const float2*)S.destination)[i];
-    const float2 an = K.a_next[i];
+    const float2 an = a_next[i];
     const float2 vn = make_float2(__fadd_rn(v.x, __fmul_rn(a.x, dt)), __fadd_rn(v.y, __fmul_rn(a.y, dt)));
     const float2 pn = make_float2(__fadd_rn(p.x, __fmul_rn(v.x, dt)), __fadd_rn(p.y, __fmul_rn(v.y, dt)));
     agent_history(S, i, vn, an);
-
-    // 2. arrive (scenarios.py:376-384)
     const int f = S.flag[i];
-    const float2* ent = entries + (size_t)S.exit_idx[(size_t)f * S.capacity + i] * S.P;
-    float m2 = INFINITY;                                     // min over the exit's points of the squared distance
+    bool gone = false;
+    int fn;
+    if (kGC) {
+        const float2* ent = entries + (size_t)S.exit_idx[(size_t)f * S.capacity + i] * S.P;
+        float m2 = INFINITY;                                 // min over the exit's points of the squared distance
 #pragma unroll 10
-    for (int q = 0; q < S.P; ++q) m2 = fminf(m2, sq2(__fsub_rn(pn.x, ent[q].x), __fsub_rn(pn.y, ent[q].y)));
-    // 3. retire (data.py:236-247)
-    agent_retire_record(S, i, t, gc_arrive(S, f, pn, d, m2), false, pn, vn, an);
+        for (int q = 0; q < S.P; ++q) m2 = fminf(m2, sq2(__fsub_rn(pn.x, ent[q].x), __fsub_rn(pn.y, ent[q].y)));
+        fn = gc_arrive(S, f, pn, d, m2);
+    } else {
+        fn = rules_arrive(S, R, f, pn, d, gone);
+    }
+    agent_retire_record(S, i, t, fn, gone, pn, vn, an);      // 3. retire (data.py:236-247)
 }
 
 // one wave: agent of ordinal `ord` (< capacity) appears in frame `f`
@@ -311,38 +337,6 @@ __device__ void spawn_agent(const piml_scenario& S, const float2* ent, long long
     for (int q = 2 + lane; q < S.F; q += 64) S.self_features[i * S.F + q] = q == S.F - 1 ? v0 : 0.f;
 }
 
-__global__ __launch_bounds__(256) void scenario_step_kernel(const ScenarioKernelArgs K) {
-    __shared__ float2 lds_entries[kScenarioLdsPoints];
-    const piml_scenario& S = K.S;
-    const float2* ent = (const float2*)S.entries;
-    const bool lds = S.E * S.P <= kScenarioLdsPoints;        // kernel-uniform: every block stages the entry points
-    if (lds) {
-        for (int q = threadIdx.x; q < S.E * S.P; q += blockDim.x) lds_entries[q] = ent[q];
-        __syncthreads();
-        ent = lds_entries;
-    }
-    const long long t = *S.frame_counter;
-    const long long n = K.init ? 0 : S.spawned[t & 1];
-    const long long f = K.init ? t : t + 1;                  // the frame the new agents appear in
-    if ((int)blockIdx.x < K.agent_blocks) {
-        const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-        if (i < n && i < S.capacity) {                       // (two inlined copies: LDS reads where the points fit)
-            if (lds) agent_step(K, lds_entries, (int)i, t);
-            else agent_step(K, (const float2*)S.entries, (int)i, t);
-        }
-        return;
-    }
-    const int k = K.init ? S.n_initial : poisson_count(S, f);
-    if (blockIdx.x == (unsigned)K.agent_blocks && threadIdx.x == 0) {
-        S.spawned[f & 1] = n + k;
-        *S.dropped = n + k > S.capacity ? n + k - S.capacity : 0;
-        if (S.spawn_out && f < S.T) S.spawn_out[f] = k;
-    }
-    const int j = (int)(blockIdx.x - K.agent_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
-    if (j >= k || n + j >= S.capacity) return;               // ordinals past the capacity are dropped, never written
-    spawn_agent(S, ent, n + j, f);
-}
-
 __global__ __launch_bounds__(256) void scenario_route_kernel(const float2* __restrict__ o, const float2* __restrict__ d, int n,
                                                              const float2* __restrict__ poly, int R, int max_iters, float clearance,
                                                              float2* __restrict__ out, int* __restrict__ iters) {
@@ -357,57 +351,7 @@ __global__ __launch_bounds__(256) void scenario_route_kernel(const float2* __res
 }
 
 
-// ---- scene rules (piml_scenario_step_rules): the synthetic scenes; GC never reaches these paths ----
-
-constexpr unsigned kRulesStream = 0x5CE10000u;
-constexpr int kRulesMaxGrid = 32;
-
-struct RulesKernelArgs {
-    piml_scenario S;
-    piml_scenario_rules R;
-    const float2* a_next;
-    int init, agent_blocks;
-};
-
-__device__ __forceinline__ int threshold_count(unsigned u, const uint32_t* thr, int cap) {
-    int k = 0;
-    for (int j = 0; j < cap; ++j) k += u >= thr[j];
-    return k;
-}
-
-__device__ __forceinline__ int wave_sum(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-// 2. arrive: the scene's update (scenarios.py:67-69, 128-130, 159-160, 218-219, 286-287); gone: PIML_ARRIVE_XEXIT's exit
-__device__ __forceinline__ int rules_arrive(const piml_scenario& S, const piml_scenario_rules& R, int f, float2 pn, float2 d,
-                                            bool& gone) {
-    gone = false;
-    if (R.arrival_rule == PIML_ARRIVE_RADIUS) f += norm2(__fsub_rn(pn.x, d.x), __fsub_rn(pn.y, d.y)) < S.arrival_radius;
-    else if (R.arrival_rule == PIML_ARRIVE_XBAND) f += fabsf(__fsub_rn(pn.x, d.x)) < S.arrival_radius;
-    else gone = pn.x > R.length;                             // PIML_ARRIVE_XEXIT: mask_p = 0
-    return f;
-}
-
-__device__ __forceinline__ void rules_agent_step(const RulesKernelArgs& K, int i, long long t) {
-    const piml_scenario& S = K.S;
-    if (S.mask[i] == 0.f) {                                  // retired for good
-        record_retired(S, i, t);
-        return;
-    }
-    const float dt = S.dt;
-    const float2 p = ((const float2*)S.position)[i], v = ((const float2*)S.velocity)[i];
-    const float2 a = ((const float2*)S.acceleration)[i], d = ((const float2*)S.destination)[i];
-    const float2 an = K.a_next[i];
-    const float2 vn = make_float2(__fadd_rn(v.x, __fmul_rn(a.x, dt)), __fadd_rn(v.y, __fmul_rn(a.y, dt)));
-    const float2 pn = make_float2(__fadd_rn(p.x, __fmul_rn(v.x, dt)), __fadd_rn(p.y, __fmul_rn(v.y, dt)));
-    agent_history(S, i, vn, an);
-    bool gone;
-    const int f = rules_arrive(S, K.R, S.flag[i], pn, d, gone);
-    agent_retire_record(S, i, t, f, gone, pn, vn, an);           // 3. retire (data.py:236-247)
-}
+// ---- scene rules (piml_scenario_rules): the synthetic scenes' spawn laws ----
 
 // 2 u - 1 of torch's (2 * torch.rand(n) - 1)
 __device__ __forceinline__ float jitter(unsigned w) { return __fsub_rn(__fmul_rn(2.f, unit24(w)), 1.f); }
@@ -501,51 +445,35 @@ __device__ void rules_spawn_agent(const piml_scenario& S, const piml_scenario_ru
         S.self_features[i * S.F + q] = q == S.F - 1 ? v0 : (q == hw ? vel.x : (q == hw + 1 ? vel.y : 0.f));
 }
 
-__global__ __launch_bounds__(256) void scenario_rules_kernel(const RulesKernelArgs K) {
-    const piml_scenario& S = K.S;
-    const piml_scenario_rules& R = K.R;
-    const long long t = *S.frame_counter;
-    const long long n = K.init ? 0 : S.spawned[t & 1];
-    const long long f = K.init ? t : t + 1;                  // the frame the new agents appear in
-    if ((int)blockIdx.x < K.agent_blocks) {
-        const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-        if (i < n && i < S.capacity) rules_agent_step(K, (int)i, t);
-        return;
-    }
+// ---- the frame ----
+
+// a spawn block (b = blockIdx.x - agent_blocks) of member view S: the spawn count of frame f -- init: n_initial; GC: k of
+// stream 0x5CE0; a scene rule: k1 + k2 of stream 0x5CE1 --, its bookkeeping by one thread of block 0, then one wave per new
+// agent of ordinal n + j.  thr / R are the kernel arguments' (an indexed read of a local copy's table would put the whole
+// descriptor in scratch); ent: GC's entry points (LDS or global).
+__device__ __forceinline__ void spawn_block(bool gc, const piml_scenario& S, const piml_scenario_rules& R, const uint32_t* thr,
+                                            const float2* ent, int init, long long n, long long f, int b) {
     int k1 = S.n_initial, k2 = 0;
-    if (!K.init) {
-        const PhiloxOut w = philox4x32_10((unsigned)f, (unsigned)((unsigned long long)f >> 32), 0u, kRulesStream,
-                                          (unsigned)S.seed, (unsigned)(S.seed >> 32));
-        k1 = threshold_count(w.x >> 8, S.poisson_thresholds, S.spawn_cap);
-        k2 = threshold_count(w.y >> 8, R.poisson_thresholds2, R.spawn_cap2);
+    if (!init) {
+        const PhiloxOut w = philox4x32_10((unsigned)f, (unsigned)((unsigned long long)f >> 32), 0u,
+                                          gc ? kScenarioStream : kRulesStream, (unsigned)S.seed, (unsigned)(S.seed >> 32));
+        k1 = threshold_count(w.x >> 8, thr, S.spawn_cap);
+        if (!gc) k2 = threshold_count(w.y >> 8, R.poisson_thresholds2, R.spawn_cap2);
     }
     const int k = k1 + k2;
-    if (blockIdx.x == (unsigned)K.agent_blocks && threadIdx.x == 0) {
+    if (b == 0 && threadIdx.x == 0) {
         S.spawned[f & 1] = n + k;
         *S.dropped = n + k > S.capacity ? n + k - S.capacity : 0;
         if (S.spawn_out && f < S.T) S.spawn_out[f] = k;
     }
-    const int j = (int)(blockIdx.x - K.agent_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
+    const int j = b * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
     if (j >= k || n + j >= S.capacity) return;               // ordinals past the capacity are dropped, never written
-    rules_spawn_agent(S, R, n + j, j >= k1, f);
+    if (gc) spawn_agent(S, ent, n + j, f);
+    else rules_spawn_agent(S, R, n + j, j >= k1, f);
 }
 
-
-// ---- ensembles (piml_scenario_step_members): `members` simulations of one scene in one launch, grid.y = member ----
-//
-// Layout: the descriptor's per-member pointers are the bases of member-major buffers, member m's slice of each having
-// exactly the single-scene layout -- state (members, capacity, .), waypoints (members, D, capacity, 2), exit_idx
-// (members, D, capacity), recorded outputs (members, T, capacity, .), spawn_out (members, T), spawned (members, 2),
-// dropped (members), a_next (members, capacity, 2).  frame_counter, entries, route_polyline, both threshold tables and
-// every scalar are shared; S.seed is ignored and member m's Philox key is seeds[m].
-// A block builds member blockIdx.y's view (member_view) and runs the single-scene kernels' frame on it through the same
-// device functions (agent_step / spawn_agent, rules_agent_step / rules_spawn_agent, whose square rank count is per member
-// too), so member m is bitwise what piml_scenario_step[_rules] gives with seed = seeds[m].
-// Determinism: still no atomics; the parity ping-pong is per member (member m's spawned[m][t & 1] read, [(t+1) & 1]
-// written by its own block agent_blocks), and no block touches another member's slices.
-// Capture: the frame counter and the seeds are read on the device, so one captured launch serves every frame.
-
-__device__ __forceinline__ void member_view(piml_scenario& S, const float2*& a_next, int m, unsigned long long seed) {
+// member m's view of the descriptor (the file header's layout); member 0's pointers are the bases
+__device__ __forceinline__ void member_view(piml_scenario& S, const float2*& a_next, int m) {
     const size_t mm = (size_t)m, cap = (size_t)S.capacity, T = (size_t)S.T, D = (size_t)S.D;
     S.position += mm * cap * 2;
     S.velocity += mm * cap * 2;
@@ -567,89 +495,50 @@ __device__ __forceinline__ void member_view(piml_scenario& S, const float2*& a_n
     if (S.spawn_out) S.spawn_out += mm * T;
     S.spawned += mm * 2;
     S.dropped += mm;
-    S.seed = seed;
     if (a_next) a_next += mm * cap;
 }
 
-__global__ __launch_bounds__(256) void scenario_step_members_kernel(const ScenarioKernelArgs K0,
-                                                                    const unsigned long long* __restrict__ seeds) {
+struct FrameArgs {
+    piml_scenario S;
+    piml_scenario_rules R;                                   // a scene rule's; not read by GC's frame
+    const float2* a_next;
+    int init, agent_blocks;
+};
+
+// Blocks 0 .. agent_blocks-1: one thread per slot; the rest spawn (spawn_block).  seeds NULL: the single run, key S.seed.
+template <bool kGC>
+__global__ __launch_bounds__(256) void scenario_frame_kernel(const FrameArgs K0, const unsigned long long* __restrict__ seeds) {
     __shared__ float2 lds_entries[kScenarioLdsPoints];
-    ScenarioKernelArgs K = K0;
-    member_view(K.S, K.a_next, (int)blockIdx.y, seeds[blockIdx.y]);
-    const piml_scenario& S = K.S;
+    piml_scenario S = K0.S;
+    const float2* a_next = K0.a_next;
+    member_view(S, a_next, (int)blockIdx.y);
+    if (seeds) S.seed = seeds[blockIdx.y];                   // (a select of the key in one expression cost 19 VGPRs)
     const float2* ent = (const float2*)S.entries;
-    const bool lds = S.E * S.P <= kScenarioLdsPoints;
+    const bool lds = kGC && S.E * S.P <= kScenarioLdsPoints; // kernel-uniform: every GC block stages the entry points
     if (lds) {
         for (int q = threadIdx.x; q < S.E * S.P; q += blockDim.x) lds_entries[q] = ent[q];
         __syncthreads();
         ent = lds_entries;
     }
     const long long t = *S.frame_counter;
-    const long long n = K.init ? 0 : S.spawned[t & 1];
-    const long long f = K.init ? t : t + 1;
-    if ((int)blockIdx.x < K.agent_blocks) {
+    const long long n = K0.init ? 0 : S.spawned[t & 1];
+    const long long f = K0.init ? t : t + 1;                 // the frame the new agents appear in
+    if ((int)blockIdx.x < K0.agent_blocks) {
         const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-        if (i < n && i < S.capacity) {
-            if (lds) agent_step(K, lds_entries, (int)i, t);
-            else agent_step(K, (const float2*)S.entries, (int)i, t);
+        if (i < n && i < S.capacity) {                       // (two inlined copies: LDS reads where the points fit)
+            if (lds) agent_step<kGC>(S, K0.R, a_next, lds_entries, (int)i, t);
+            else agent_step<kGC>(S, K0.R, a_next, (const float2*)S.entries, (int)i, t);
         }
         return;
     }
-    // poisson_count with the member's key and the thresholds of the kernel arguments (an indexed read of the local
-    // copy's table would put the whole descriptor in scratch)
-    int k = S.n_initial;
-    if (!K.init) {
-        const PhiloxOut w = philox4x32_10((unsigned)f, (unsigned)((unsigned long long)f >> 32), 0u, kScenarioStream,
-                                          (unsigned)S.seed, (unsigned)(S.seed >> 32));
-        k = threshold_count(w.x >> 8, K0.S.poisson_thresholds, S.spawn_cap);
-    }
-    if (blockIdx.x == (unsigned)K.agent_blocks && threadIdx.x == 0) {
-        S.spawned[f & 1] = n + k;
-        *S.dropped = n + k > S.capacity ? n + k - S.capacity : 0;
-        if (S.spawn_out && f < S.T) S.spawn_out[f] = k;
-    }
-    const int j = (int)(blockIdx.x - K.agent_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
-    if (j >= k || n + j >= S.capacity) return;
-    spawn_agent(S, ent, n + j, f);
-}
-
-__global__ __launch_bounds__(256) void scenario_rules_members_kernel(const RulesKernelArgs K0,
-                                                                     const unsigned long long* __restrict__ seeds) {
-    RulesKernelArgs K = K0;
-    member_view(K.S, K.a_next, (int)blockIdx.y, seeds[blockIdx.y]);
-    const piml_scenario& S = K.S;
-    const piml_scenario_rules& R = K0.R;
-    const long long t = *S.frame_counter;
-    const long long n = K.init ? 0 : S.spawned[t & 1];
-    const long long f = K.init ? t : t + 1;
-    if ((int)blockIdx.x < K.agent_blocks) {
-        const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-        if (i < n && i < S.capacity) rules_agent_step(K, (int)i, t);
-        return;
-    }
-    int k1 = S.n_initial, k2 = 0;
-    if (!K.init) {
-        const PhiloxOut w = philox4x32_10((unsigned)f, (unsigned)((unsigned long long)f >> 32), 0u, kRulesStream,
-                                          (unsigned)S.seed, (unsigned)(S.seed >> 32));
-        k1 = threshold_count(w.x >> 8, K0.S.poisson_thresholds, S.spawn_cap);
-        k2 = threshold_count(w.y >> 8, R.poisson_thresholds2, R.spawn_cap2);
-    }
-    const int k = k1 + k2;
-    if (blockIdx.x == (unsigned)K.agent_blocks && threadIdx.x == 0) {
-        S.spawned[f & 1] = n + k;
-        *S.dropped = n + k > S.capacity ? n + k - S.capacity : 0;
-        if (S.spawn_out && f < S.T) S.spawn_out[f] = k;
-    }
-    const int j = (int)(blockIdx.x - K.agent_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
-    if (j >= k || n + j >= S.capacity) return;
-    rules_spawn_agent(S, R, n + j, j >= k1, f);
+    spawn_block(kGC, S, K0.R, K0.S.poisson_thresholds, ent, K0.init, n, f, (int)blockIdx.x - K0.agent_blocks);
 }
 
 
 // ---- the MLAPM frame (piml_scenario_step_mlapm): the closed-form law of src/main_mlapm.py:18-36 drives the scene ----
 //
 // One launch per frame t -> t+1, every scene, grid.y = member (one member and its seed is the single run).  Blocks
-// 0 .. agent_blocks-1 hold one wave per slot i (4 per block); the rest are the spawn blocks of the members kernels, unchanged.
+// 0 .. agent_blocks-1 hold one wave per slot i (4 per block); the rest are scenario_frame_kernel's spawn blocks (spawn_block).
 // Per present slot i of member m: the member's sources are read from the RECORDS of frame t (position_out[t],
 // velocity_out[t]; the init launch or the previous frame wrote them), never from the state other waves overwrite in this
 // launch -- mlapm_fwd_kernel<ROLL> reads traj[t-1] and writes traj[t] the same way.  Sources: slots j < n_t = min(spawned,
@@ -657,7 +546,7 @@ __global__ __launch_bounds__(256) void scenario_rules_members_kernel(const Rules
 // min(capacity, n_t + 64) of them, which puts every present source in the same packed / scalar lane of mlapm_tile_sum as a
 // piml_mlapm_step_fwd over all capacity rows, so the force is bitwise that call's.  Then
 //   F = (v0 e - v) / tau - sum (mlapm.py:21-58), v' = v + F dt (:57), p' = p + v' dt (main_mlapm.py:25, explicit Euler),
-//   a' = F; the history / self_features update, arrival, retirement and record of agent_step / rules_agent_step.
+//   a' = F; the history / self_features update, arrival, retirement and record of agent_step.
 // GC's exit distance is spread over the wave's lanes (the minimum is exact, so the order does not matter).
 // The frame index is *frame_counter + frame_offset, read and never written here: a captured graph of K frames carries
 // offsets 0 .. K-1 and one counter add of K, so a frame is one launch and nothing needs a grid-wide "last block" count.
@@ -679,7 +568,8 @@ __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_kernel(const M
     static_assert(kScenarioLdsPoints * sizeof(float2) <= sizeof(tile), "the entry points fit the source tile");
     piml_scenario S = K0.S;
     const float2* no_a = nullptr;
-    member_view(S, no_a, (int)blockIdx.y, seeds[blockIdx.y]);
+    member_view(S, no_a, (int)blockIdx.y);
+    S.seed = seeds[blockIdx.y];
     const MlapmParams& P = K0.P;
     const long long t = *S.frame_counter + K0.frame_offset;
     if (t + 1 >= S.T) return;                                // past the records: nothing to do
@@ -746,65 +636,122 @@ __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_kernel(const M
         }
         return;
     }
-    // spawn blocks: scenario_step_members_kernel's / scenario_rules_members_kernel's (thresholds from the kernel arguments)
-    const long long f = t + 1;
-    int k1, k2 = 0;
-    const PhiloxOut w = philox4x32_10((unsigned)f, (unsigned)((unsigned long long)f >> 32), 0u,
-                                      K0.gc ? kScenarioStream : kRulesStream, (unsigned)S.seed, (unsigned)(S.seed >> 32));
-    k1 = threshold_count(w.x >> 8, K0.S.poisson_thresholds, S.spawn_cap);
-    if (!K0.gc) k2 = threshold_count(w.y >> 8, K0.R.poisson_thresholds2, K0.R.spawn_cap2);
-    const int k = k1 + k2;
-    if (blockIdx.x == (unsigned)K0.agent_blocks && threadIdx.x == 0) {
-        S.spawned[f & 1] = n + k;
-        *S.dropped = n + k > cap ? n + k - cap : 0;
-        if (S.spawn_out && f < S.T) S.spawn_out[f] = k;
+    // spawn blocks: the frame kernel's, from the same thresholds of the kernel arguments
+    const float2* ent = (const float2*)S.entries;
+    if (K0.gc && S.E * S.P <= kScenarioLdsPoints) {          // block-uniform, before any wave leaves
+        float2* lds_entries = (float2*)tile;
+        for (int q = threadIdx.x; q < S.E * S.P; q += blockDim.x) lds_entries[q] = ent[q];
+        __syncthreads();
+        ent = lds_entries;
     }
-    const int j = (int)(blockIdx.x - K0.agent_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
-    if (K0.gc) {
-        const float2* ent = (const float2*)S.entries;
-        if (S.E * S.P <= kScenarioLdsPoints) {               // block-uniform, before any wave leaves
-            float2* lds_entries = (float2*)tile;
-            for (int q = threadIdx.x; q < S.E * S.P; q += blockDim.x) lds_entries[q] = ent[q];
-            __syncthreads();
-            ent = lds_entries;
-        }
-        if (j >= k || n + j >= cap) return;
-        spawn_agent(S, ent, n + j, f);
-    } else {
-        if (j >= k || n + j >= cap) return;
-        rules_spawn_agent(S, K0.R, n + j, j >= k1, f);
-    }
+    spawn_block(K0.gc, S, K0.R, K0.S.poisson_thresholds, ent, 0, n, t + 1, (int)blockIdx.x - K0.agent_blocks);
 }
 
 }  // namespace piml
 
-PIML_API int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, void* stream) {
-    if (!s) return hipErrorInvalidValue;
-    const piml_scenario& S = *s;
-    if (S.capacity < 1 || S.T < 1 || S.hist_width < 2 || S.F != S.hist_width + 5 || S.D < 2 || S.D > piml::kScenarioMaxD ||
-        S.E < 2 || S.P < 1 || S.R < 2 || S.n_initial < 0 || S.n_initial > piml::kScenarioMaxInitial ||
-        S.route_max_iters < 0 || S.route_max_iters > piml::kScenarioMaxIters || S.spawn_cap < 0 ||
-        S.spawn_cap > piml::kScenarioMaxSpawn || !(S.dt > 0.f) || (init != 0 && init != 1) || (!init && !a_next))
-        return hipErrorInvalidValue;
+namespace {
+
+bool thresholds_ok(const uint32_t* thr, int cap) {
+    for (int j = 0; j < cap; ++j)
+        if (thr[j] > (1u << 24) || (j && thr[j] < thr[j - 1])) return false;
+    return true;
+}
+
+// the checks of every frame entry (include/piml_hip.h); r == NULL is GC
+bool frame_args_ok(const piml_scenario& S, const piml_scenario_rules* r, const float* a_next, int init) {
+    const bool gc = !r || r->spawn_law == PIML_SPAWN_GC;
+    if (r && (r->spawn_law < PIML_SPAWN_GC || r->spawn_law > PIML_SPAWN_UNIT3 || r->arrival_rule < PIML_ARRIVE_GC ||
+              r->arrival_rule > PIML_ARRIVE_XEXIT || gc != (r->arrival_rule == PIML_ARRIVE_GC)))
+        return false;
+    if (S.capacity < 1 || S.T < 1 || S.hist_width < 2 || S.F != S.hist_width + 5 || S.D > piml::kScenarioMaxD ||
+        S.n_initial < 0 || S.n_initial > piml::kScenarioMaxInitial || S.spawn_cap < 0 || S.spawn_cap > piml::kScenarioMaxSpawn ||
+        !(S.dt > 0.f) || (init != 0 && init != 1) || (!init && !a_next))
+        return false;
     if (!S.position || !S.velocity || !S.acceleration || !S.destination || !S.hist_velocity || !S.self_features ||
-        !S.desired_speed || !S.flag || !S.mask || !S.waypoints || !S.exit_idx || !S.position_out || !S.velocity_out ||
+        !S.desired_speed || !S.flag || !S.mask || !S.waypoints || !S.position_out || !S.velocity_out ||
         !S.acceleration_out || !S.destination_out || !S.mask_out || !S.frame_counter || !S.spawned || !S.dropped ||
-        !S.entries || !S.route_polyline)
-        return hipErrorInvalidValue;
-    for (int j = 0; j < S.spawn_cap; ++j)
-        if (S.poisson_thresholds[j] > (1u << 24) || (j && S.poisson_thresholds[j] < S.poisson_thresholds[j - 1]))
-            return hipErrorInvalidValue;
-    piml::ScenarioKernelArgs K;
+        !thresholds_ok(S.poisson_thresholds, S.spawn_cap))
+        return false;
+    if (gc)
+        return S.D >= 2 && S.E >= 2 && S.P >= 1 && S.R >= 2 && S.route_max_iters >= 0 &&
+               S.route_max_iters <= piml::kScenarioMaxIters && S.exit_idx && S.entries && S.route_polyline;
+    const piml_scenario_rules& R = *r;
+    if (S.D < 1 || (R.spawn_law == PIML_SPAWN_CROSSWALK && S.D < 2) || R.spawn_cap2 < 0 ||
+        R.spawn_cap2 > piml::kScenarioMaxSpawn || (R.spawn_cap2 && R.spawn_law != PIML_SPAWN_UNIT3) ||
+        (R.initial_velocity != 0 && R.initial_velocity != 1) || (R.speed_clamp != 0 && R.speed_clamp != 1))
+        return false;
+    if (R.spawn_law == PIML_SPAWN_SQUARE && (R.grid < 1 || R.grid > piml::kRulesMaxGrid || S.n_initial != 4 * R.grid * R.grid))
+        return false;
+    return thresholds_ok(R.poisson_thresholds2, R.spawn_cap2);
+}
+
+// >= 1: block agent_blocks writes each member's spawned count
+int spawn_blocks(const piml_scenario& S, const piml_scenario_rules* r, int init) {
+    const int waves = init ? S.n_initial : S.spawn_cap + (r && r->spawn_law != PIML_SPAWN_GC ? r->spawn_cap2 : 0);
+    return waves > 0 ? (waves + 3) / 4 : 1;
+}
+
+// one scenario_frame_kernel launch over frame_args_ok's arguments; seeds NULL: one member, key S.seed
+int launch_frame(const piml_scenario& S, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                 const float* a_next, int init, void* stream) {
+    piml::FrameArgs K;
     K.S = S;
+    K.R = r ? *r : piml_scenario_rules{};
     K.a_next = (const float2*)a_next;
     K.init = init;
     K.agent_blocks = init ? 0 : (S.capacity + 255) / 256;
-    const int waves = init ? S.n_initial : S.spawn_cap;
-    const int spawn_blocks = waves > 0 ? (waves + 3) / 4 : 1;   // >= 1: block agent_blocks writes the spawned count
-    hipLaunchKernelGGL(piml::scenario_step_kernel, dim3((unsigned)(K.agent_blocks + spawn_blocks)), dim3(256), 0,
-                       piml::as_stream(stream), K);
+    const dim3 grid((unsigned)(K.agent_blocks + spawn_blocks(S, r, init)), (unsigned)members);
+    const unsigned long long* sd = (const unsigned long long*)seeds;
+    if (K.R.spawn_law == PIML_SPAWN_GC)
+        hipLaunchKernelGGL(piml::scenario_frame_kernel<true>, grid, dim3(256), 0, piml::as_stream(stream), K, sd);
+    else
+        hipLaunchKernelGGL(piml::scenario_frame_kernel<false>, grid, dim3(256), 0, piml::as_stream(stream), K, sd);
     return hipGetLastError();
 }
+
+}  // namespace
+
+PIML_API int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, void* stream) {
+    if (!s || !frame_args_ok(*s, nullptr, a_next, init)) return hipErrorInvalidValue;
+    return launch_frame(*s, nullptr, 1, nullptr, a_next, init, stream);
+}
+
+PIML_API int piml_scenario_step_rules(const piml_scenario* s, const piml_scenario_rules* r, const float* a_next, int init,
+                                      void* stream) {
+    if (!s || !r || !frame_args_ok(*s, r, a_next, init)) return hipErrorInvalidValue;
+    return launch_frame(*s, r, 1, nullptr, a_next, init, stream);
+}
+
+PIML_API int piml_scenario_step_members(const piml_scenario* s, const piml_scenario_rules* r, int members,
+                                        const uint64_t* seeds, const float* a_next, int init, void* stream) {
+    if (!s || !seeds || members < 1 || members > 65535 || !frame_args_ok(*s, r, a_next, init)) return hipErrorInvalidValue;
+    return launch_frame(*s, r, members, seeds, a_next, init, stream);
+}
+
+PIML_API int piml_scenario_step_mlapm(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                                      const piml_mlapm_law* law, int frame_offset, void* stream) {
+    // the frame checks (init = 1 only waives a_next, which this frame does not take)
+    if (!s || !seeds || !law || members < 1 || members > 65535 || frame_offset < 0 || !frame_args_ok(*s, r, nullptr, 1))
+        return hipErrorInvalidValue;
+    const piml_scenario& S = *s;
+    const piml_mlapm_law& L = *law;
+    if (L.variant < 0 || L.variant > 2 || !std::isfinite(L.tau) || !(L.tau > 0.f) || !std::isfinite(L.A) ||
+        !std::isfinite(L.B) || !std::isfinite(L.C) || !std::isfinite(L.D) || !std::isfinite(L.theta_deg) ||
+        !std::isfinite(L.radius) || !(L.radius > 0.f))
+        return hipErrorInvalidValue;
+    piml::MlapmScenarioArgs K;
+    K.S = S;
+    K.R = r ? *r : piml_scenario_rules{};
+    K.P = piml::make_params(L.variant, L.tau, L.A, L.B, L.C, L.D, L.theta_deg, L.radius, 1);
+    K.gc = K.R.spawn_law == PIML_SPAWN_GC;
+    K.agent_blocks = (S.capacity + piml::kMlScWaves - 1) / piml::kMlScWaves;
+    K.frame_offset = frame_offset;
+    const dim3 grid((unsigned)(K.agent_blocks + spawn_blocks(S, r, 0)), (unsigned)members);
+    hipLaunchKernelGGL(piml::scenario_mlapm_kernel, grid, dim3(piml::kMlScWaves * 64), 0, piml::as_stream(stream), K,
+                       (const unsigned long long*)seeds);
+    return hipGetLastError();
+}
+
 
 PIML_API int piml_scenario_route(const float* origin, const float* destination, int n, const float* polyline, int R,
                                  int max_iters, float clearance, float* waypoint, int* iters, void* stream) {
@@ -814,162 +761,5 @@ PIML_API int piml_scenario_route(const float* origin, const float* destination, 
     hipLaunchKernelGGL(piml::scenario_route_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, piml::as_stream(stream),
                        (const float2*)origin, (const float2*)destination, n, (const float2*)polyline, R, max_iters, clearance,
                        (float2*)waypoint, iters);
-    return hipGetLastError();
-}
-
-
-PIML_API int piml_scenario_step_rules(const piml_scenario* s, const piml_scenario_rules* r, const float* a_next, int init,
-                                      void* stream) {
-    if (!s || !r) return hipErrorInvalidValue;
-    const piml_scenario& S = *s;
-    const piml_scenario_rules& R = *r;
-    const bool gc_law = R.spawn_law == PIML_SPAWN_GC, gc_rule = R.arrival_rule == PIML_ARRIVE_GC;
-    if (R.spawn_law < PIML_SPAWN_GC || R.spawn_law > PIML_SPAWN_UNIT3 || R.arrival_rule < PIML_ARRIVE_GC ||
-        R.arrival_rule > PIML_ARRIVE_XEXIT || gc_law != gc_rule)
-        return hipErrorInvalidValue;
-    if (gc_law) return piml_scenario_step(s, a_next, init, stream);   // GC: the unchanged kernel
-    if (S.capacity < 1 || S.T < 1 || S.hist_width < 2 || S.F != S.hist_width + 5 || S.D < 1 || S.D > piml::kScenarioMaxD ||
-        (R.spawn_law == PIML_SPAWN_CROSSWALK && S.D < 2) || S.n_initial < 0 || S.n_initial > piml::kScenarioMaxInitial ||
-        S.spawn_cap < 0 || S.spawn_cap > piml::kScenarioMaxSpawn || R.spawn_cap2 < 0 || R.spawn_cap2 > piml::kScenarioMaxSpawn ||
-        (R.spawn_cap2 && R.spawn_law != PIML_SPAWN_UNIT3) || (R.initial_velocity != 0 && R.initial_velocity != 1) ||
-        (R.speed_clamp != 0 && R.speed_clamp != 1) || !(S.dt > 0.f) || (init != 0 && init != 1) || (!init && !a_next))
-        return hipErrorInvalidValue;
-    if (R.spawn_law == PIML_SPAWN_SQUARE &&
-        (R.grid < 1 || R.grid > piml::kRulesMaxGrid || S.n_initial != 4 * R.grid * R.grid))
-        return hipErrorInvalidValue;
-    if (!S.position || !S.velocity || !S.acceleration || !S.destination || !S.hist_velocity || !S.self_features ||
-        !S.desired_speed || !S.flag || !S.mask || !S.waypoints || !S.position_out || !S.velocity_out ||
-        !S.acceleration_out || !S.destination_out || !S.mask_out || !S.frame_counter || !S.spawned || !S.dropped)
-        return hipErrorInvalidValue;
-    for (int j = 0; j < S.spawn_cap; ++j)
-        if (S.poisson_thresholds[j] > (1u << 24) || (j && S.poisson_thresholds[j] < S.poisson_thresholds[j - 1]))
-            return hipErrorInvalidValue;
-    for (int j = 0; j < R.spawn_cap2; ++j)
-        if (R.poisson_thresholds2[j] > (1u << 24) || (j && R.poisson_thresholds2[j] < R.poisson_thresholds2[j - 1]))
-            return hipErrorInvalidValue;
-    piml::RulesKernelArgs K;
-    K.S = S;
-    K.R = R;
-    K.a_next = (const float2*)a_next;
-    K.init = init;
-    K.agent_blocks = init ? 0 : (S.capacity + 255) / 256;
-    const int waves = init ? S.n_initial : S.spawn_cap + R.spawn_cap2;
-    const int spawn_blocks = waves > 0 ? (waves + 3) / 4 : 1;   // >= 1: block agent_blocks writes the spawned count
-    hipLaunchKernelGGL(piml::scenario_rules_kernel, dim3((unsigned)(K.agent_blocks + spawn_blocks)), dim3(256), 0,
-                       piml::as_stream(stream), K);
-    return hipGetLastError();
-}
-
-
-namespace {
-
-// the argument checks of piml_scenario_step (GC) and piml_scenario_step_rules (the other laws), for the member entry
-bool gc_args_ok(const piml_scenario& S, const float* a_next, int init) {
-    if (S.capacity < 1 || S.T < 1 || S.hist_width < 2 || S.F != S.hist_width + 5 || S.D < 2 || S.D > piml::kScenarioMaxD ||
-        S.E < 2 || S.P < 1 || S.R < 2 || S.n_initial < 0 || S.n_initial > piml::kScenarioMaxInitial ||
-        S.route_max_iters < 0 || S.route_max_iters > piml::kScenarioMaxIters || S.spawn_cap < 0 ||
-        S.spawn_cap > piml::kScenarioMaxSpawn || !(S.dt > 0.f) || (init != 0 && init != 1) || (!init && !a_next))
-        return false;
-    if (!S.position || !S.velocity || !S.acceleration || !S.destination || !S.hist_velocity || !S.self_features ||
-        !S.desired_speed || !S.flag || !S.mask || !S.waypoints || !S.exit_idx || !S.position_out || !S.velocity_out ||
-        !S.acceleration_out || !S.destination_out || !S.mask_out || !S.frame_counter || !S.spawned || !S.dropped ||
-        !S.entries || !S.route_polyline)
-        return false;
-    for (int j = 0; j < S.spawn_cap; ++j)
-        if (S.poisson_thresholds[j] > (1u << 24) || (j && S.poisson_thresholds[j] < S.poisson_thresholds[j - 1])) return false;
-    return true;
-}
-
-bool rules_args_ok(const piml_scenario& S, const piml_scenario_rules& R, const float* a_next, int init) {
-    if (S.capacity < 1 || S.T < 1 || S.hist_width < 2 || S.F != S.hist_width + 5 || S.D < 1 || S.D > piml::kScenarioMaxD ||
-        (R.spawn_law == PIML_SPAWN_CROSSWALK && S.D < 2) || S.n_initial < 0 || S.n_initial > piml::kScenarioMaxInitial ||
-        S.spawn_cap < 0 || S.spawn_cap > piml::kScenarioMaxSpawn || R.spawn_cap2 < 0 || R.spawn_cap2 > piml::kScenarioMaxSpawn ||
-        (R.spawn_cap2 && R.spawn_law != PIML_SPAWN_UNIT3) || (R.initial_velocity != 0 && R.initial_velocity != 1) ||
-        (R.speed_clamp != 0 && R.speed_clamp != 1) || !(S.dt > 0.f) || (init != 0 && init != 1) || (!init && !a_next))
-        return false;
-    if (R.spawn_law == PIML_SPAWN_SQUARE && (R.grid < 1 || R.grid > piml::kRulesMaxGrid || S.n_initial != 4 * R.grid * R.grid))
-        return false;
-    if (!S.position || !S.velocity || !S.acceleration || !S.destination || !S.hist_velocity || !S.self_features ||
-        !S.desired_speed || !S.flag || !S.mask || !S.waypoints || !S.position_out || !S.velocity_out ||
-        !S.acceleration_out || !S.destination_out || !S.mask_out || !S.frame_counter || !S.spawned || !S.dropped)
-        return false;
-    for (int j = 0; j < S.spawn_cap; ++j)
-        if (S.poisson_thresholds[j] > (1u << 24) || (j && S.poisson_thresholds[j] < S.poisson_thresholds[j - 1])) return false;
-    for (int j = 0; j < R.spawn_cap2; ++j)
-        if (R.poisson_thresholds2[j] > (1u << 24) || (j && R.poisson_thresholds2[j] < R.poisson_thresholds2[j - 1]))
-            return false;
-    return true;
-}
-
-}  // namespace
-
-PIML_API int piml_scenario_step_members(const piml_scenario* s, const piml_scenario_rules* r, int members,
-                                        const uint64_t* seeds, const float* a_next, int init, void* stream) {
-    if (!s || !seeds || members < 1 || members > 65535) return hipErrorInvalidValue;
-    const piml_scenario& S = *s;
-    const bool gc = !r || r->spawn_law == PIML_SPAWN_GC;
-    if (r) {
-        const bool gc_rule = r->arrival_rule == PIML_ARRIVE_GC;
-        if (r->spawn_law < PIML_SPAWN_GC || r->spawn_law > PIML_SPAWN_UNIT3 || r->arrival_rule < PIML_ARRIVE_GC ||
-            r->arrival_rule > PIML_ARRIVE_XEXIT || gc != gc_rule)
-            return hipErrorInvalidValue;
-    }
-    if (gc ? !gc_args_ok(S, a_next, init) : !rules_args_ok(S, *r, a_next, init)) return hipErrorInvalidValue;
-    const int agent_blocks = init ? 0 : (S.capacity + 255) / 256;
-    const int waves = init ? S.n_initial : S.spawn_cap + (gc ? 0 : r->spawn_cap2);
-    const int spawn_blocks = waves > 0 ? (waves + 3) / 4 : 1;   // >= 1: block agent_blocks writes each member's count
-    const dim3 grid((unsigned)(agent_blocks + spawn_blocks), (unsigned)members);
-    const unsigned long long* sd = (const unsigned long long*)seeds;
-    if (gc) {
-        piml::ScenarioKernelArgs K;
-        K.S = S;
-        K.a_next = (const float2*)a_next;
-        K.init = init;
-        K.agent_blocks = agent_blocks;
-        hipLaunchKernelGGL(piml::scenario_step_members_kernel, grid, dim3(256), 0, piml::as_stream(stream), K, sd);
-    } else {
-        piml::RulesKernelArgs K;
-        K.S = S;
-        K.R = *r;
-        K.a_next = (const float2*)a_next;
-        K.init = init;
-        K.agent_blocks = agent_blocks;
-        hipLaunchKernelGGL(piml::scenario_rules_members_kernel, grid, dim3(256), 0, piml::as_stream(stream), K, sd);
-    }
-    return hipGetLastError();
-}
-
-
-PIML_API int piml_scenario_step_mlapm(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
-                                      const piml_mlapm_law* law, int frame_offset, void* stream) {
-    if (!s || !seeds || !law || members < 1 || members > 65535 || frame_offset < 0) return hipErrorInvalidValue;
-    const piml_scenario& S = *s;
-    const bool gc = !r || r->spawn_law == PIML_SPAWN_GC;
-    if (r) {
-        const bool gc_rule = r->arrival_rule == PIML_ARRIVE_GC;
-        if (r->spawn_law < PIML_SPAWN_GC || r->spawn_law > PIML_SPAWN_UNIT3 || r->arrival_rule < PIML_ARRIVE_GC ||
-            r->arrival_rule > PIML_ARRIVE_XEXIT || gc != gc_rule)
-            return hipErrorInvalidValue;
-    }
-    // the frame checks of the entries above (init = 1 there only waives a_next, which this frame does not take)
-    if (gc ? !gc_args_ok(S, nullptr, 1) : !rules_args_ok(S, *r, nullptr, 1)) return hipErrorInvalidValue;
-    const piml_mlapm_law& L = *law;
-    if (L.variant < 0 || L.variant > 2 || !std::isfinite(L.tau) || !(L.tau > 0.f) || !std::isfinite(L.A) ||
-        !std::isfinite(L.B) || !std::isfinite(L.C) || !std::isfinite(L.D) || !std::isfinite(L.theta_deg) ||
-        !std::isfinite(L.radius) || !(L.radius > 0.f))
-        return hipErrorInvalidValue;
-    piml::MlapmScenarioArgs K;
-    K.S = S;
-    if (r) K.R = *r;
-    else memset(&K.R, 0, sizeof(K.R));
-    K.P = piml::make_params(L.variant, L.tau, L.A, L.B, L.C, L.D, L.theta_deg, L.radius, 1);
-    K.gc = gc;
-    K.agent_blocks = (S.capacity + piml::kMlScWaves - 1) / piml::kMlScWaves;
-    K.frame_offset = frame_offset;
-    const int waves = S.spawn_cap + (gc ? 0 : r->spawn_cap2);
-    const int spawn_blocks = waves > 0 ? (waves + 3) / 4 : 1;   // >= 1: block agent_blocks writes each member's count
-    const dim3 grid((unsigned)(K.agent_blocks + spawn_blocks), (unsigned)members);
-    hipLaunchKernelGGL(piml::scenario_mlapm_kernel, grid, dim3(piml::kMlScWaves * 64), 0, piml::as_stream(stream), K,
-                       (const unsigned long long*)seeds);
     return hipGetLastError();
 }

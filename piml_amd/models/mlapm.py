@@ -140,53 +140,34 @@ class MLAPM:
         Limits of the reference's law, restated: no obstacle or wall term (the square's obstacle points are not felt;
         GC agents pass the pillar by their waypoints), and an agent at rest sees nobody (view is v . r > 0).
         Returns a scenarios.ScenarioResult."""
-        from .. import scenarios
-        sc, T, cap, st = self._scenario_setup(scenario, frames, capacity, device, hist_width, seed=seed)
-        self._run_scenario(st, T, self._law(radius), use_graph, frames_per_graph)
-        last = int(st.t.item())
-        return scenarios.ScenarioResult(
-            position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res, mask_p=st.mask_res,
-            waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles, time_unit=sc.time_unit,
-            spawned=int(st.spawned[last & 1].item()), dropped=int(st.dropped.item()), spawn_count=st.spawn_count,
-            capacity=cap, seed=int(seed), state=st)
+        return self._simulate(scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, seed=seed)
 
     def simulate_ensemble(self, scenario, frames, seeds, capacity=None, use_graph=None, radius=0.3, device='cuda',
                           hist_width=2, frames_per_graph=8):
         """simulate_scenario for every seed of `seeds` in the same launches (grid.y = member; members never see each
         other).  Member m is bitwise simulate_scenario(seed=seeds[m]) with the same capacity.  Returns a
         scenarios.ScenarioEnsemble."""
-        from .. import scenarios
         seeds = [int(x) for x in seeds]
         if not seeds:
             raise ValueError('simulate_ensemble: at least one seed expected')
-        sc, T, cap, st = self._scenario_setup(scenario, frames, capacity, device, hist_width, seeds=seeds)
-        self._run_scenario(st, T, self._law(radius), use_graph, frames_per_graph)
-        last = int(st.t.item())
-        return scenarios.ScenarioEnsemble(
-            seeds=seeds, position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res,
-            mask_p=st.mask_res, waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles,
-            time_unit=sc.time_unit, spawned=st.spawned[:, last & 1].tolist(), dropped=st.dropped.tolist(),
-            spawn_count=st.spawn_count, capacity=cap, state=st)
+        return self._simulate(scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph,
+                              seeds=seeds)
 
-    def _scenario_setup(self, scenario, frames, capacity, device, hist_width, **state_kw):
-        import torch
-        from .. import ops_scenario, scenarios
-        sc = scenario.to(torch.device(device))
-        T = int(frames)
-        if T < 1:
-            raise ValueError(f'frames must be >= 1, got {frames}')
-        cap = scenarios.default_capacity(sc, T) if capacity is None else int(capacity)
-        st = ops_scenario.scenario_state(sc, cap, T, int(hist_width), **state_kw)
-        return sc, T, cap, st
+    def _simulate(self, scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, **state_kw):
+        from .. import scenarios
+        law = self._law(radius)
+        st = scenarios.scenario_state_for(scenario, frames, capacity, device, hist_width, **state_kw)
+        self._run_scenario(st, law, use_graph, frames_per_graph)
+        return scenarios.scenario_result(st)
 
-    def _run_scenario(self, st, T, law, use_graph, frames_per_graph):
+    def _run_scenario(self, st, law, use_graph, frames_per_graph):
         """frame 0's spawn, then T - 1 MLAPM frames: K = frames_per_graph of them (offsets 0 .. K-1 and one counter add)
         captured into one graph and replayed when use_graph, the rest eagerly."""
         import torch
         from .. import ops_scenario, hip_graphs_safe
         with torch.no_grad():
             ops_scenario.scenario_step(st, init=True)                 # frame 0: generate(n_initial)
-            steps = T - 1
+            steps = st.T - 1
             if use_graph is None:
                 use_graph = steps > 8
             per = max(1, int(frames_per_graph))

@@ -465,24 +465,24 @@ class BaseSimulator(Pedestrians):
     # ---- open-world simulation: the loop the reference stubs (BaseSimulator.run / run_single_step, simulators.py:834-838) ----
     def simulate_scenario(self, scenario, frames, seed=0, capacity=None, use_graph=None):
         """Simulate `frames` frames of an entry / exit scene (piml_amd.scenarios.Scenario: gc_scenario() or a synthetic scene
-        of piml_amd.scenarios.SCENARIOS, which runs piml_scenario_step_rules) with the
-        current model: frame 0 spawns the scenario's initial agents, every further frame is model -> piml_scenario_step
-        (integrate, arrive, retire, Poisson arrivals routed around the scenario's polyline, record) -> relative features.
+        of piml_amd.scenarios.SCENARIOS) with the current model: frame 0 spawns the scenario's initial agents, every further
+        frame is model -> one scenario_frame_kernel launch (integrate, arrive, retire, Poisson arrivals routed around the
+        scenario's polyline or by the scene's spawn law, record) -> relative features.
         The frame is captured into one graph and replayed (`use_graph=None`: when more than 8 frames); the Philox draws
         make the spawn schedule a function of (seed, frame, ordinal).  `capacity` = agent slots (default: n_initial + a
         1e-9 upper quantile of the arrivals); agents past it are dropped and counted.  Returns a ScenarioResult."""
-        return self._in_scenario_mode(lambda: self._simulate_scenario(scenario, frames, seed, capacity, use_graph))
+        return self._in_scenario_mode(lambda: self._simulate(scenario, frames, capacity, use_graph, seed=seed))
 
     def simulate_ensemble(self, scenario, frames, seeds, capacity=None, use_graph=None):
         """`simulate_scenario` for every seed of `seeds` at once: S = len(seeds) simulations of one scene with one capacity
         (default: as simulate_scenario's, which does not depend on the seed), every frame of all of them one network
-        forward over the S * capacity rows, one piml_scenario_step_members launch and one relative-feature launch
+        forward over the S * capacity rows, one scenario_frame_kernel launch and one relative-feature launch
         (captured and replayed as simulate_scenario's frame).  Member m is the simulation of seed seeds[m]: the network
         sees flat (S * capacity, .) rows, so members never see each other.  Returns a scenarios.ScenarioEnsemble."""
         seeds = [int(x) for x in seeds]
         if not seeds:
             raise ValueError('simulate_ensemble: at least one seed expected')
-        return self._in_scenario_mode(lambda: self._simulate_ensemble(scenario, frames, seeds, capacity, use_graph))
+        return self._in_scenario_mode(lambda: self._simulate(scenario, frames, capacity, use_graph, seeds=seeds))
 
     def _in_scenario_mode(self, run):
         only = hasattr(self.model, 'predictions_only')
@@ -497,50 +497,23 @@ class BaseSimulator(Pedestrians):
                 if only:
                     self.model.predictions_only = before
 
-    def _scenario_setup(self, scenario, frames, capacity, **state_kw):
-        from .. import ops_scenario, scenarios
+    def _simulate(self, scenario, frames, capacity, use_graph, **state_kw):
+        from .. import scenarios
         a = self.args
-        sc = scenario.to(torch.device(a.device))
-        T = int(frames)
-        if T < 1:
-            raise ValueError(f'frames must be >= 1, got {frames}')
-        cap = scenarios.default_capacity(sc, T) if capacity is None else int(capacity)
-        st = ops_scenario.scenario_state(sc, cap, T, 2 * int(a.num_history_velocity), topk_ped=a.topk_ped,
-                                         topk_obs=a.topk_obs, **state_kw)
-        return sc, T, cap, st
-
-    def _simulate_scenario(self, scenario, frames, seed, capacity, use_graph):
-        from .. import scenarios
-        sc, T, cap, st = self._scenario_setup(scenario, frames, capacity, seed=seed)
-        self._run_scenario(sc, T, st, (st.pf, st.of, st.selff), use_graph)
-        last = int(st.t.item())
-        return scenarios.ScenarioResult(
-            position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res, mask_p=st.mask_res,
-            waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles, time_unit=sc.time_unit,
-            spawned=int(st.spawned[last & 1].item()), dropped=int(st.dropped.item()), spawn_count=st.spawn_count,
-            capacity=cap, seed=int(seed), state=st)
-
-    def _simulate_ensemble(self, scenario, frames, seeds, capacity, use_graph):
-        from .. import scenarios
-        sc, T, cap, st = self._scenario_setup(scenario, frames, capacity, seeds=seeds)
-        rows = len(seeds) * cap
+        st = scenarios.scenario_state_for(scenario, frames, capacity, a.device, 2 * int(a.num_history_velocity),
+                                          topk_ped=a.topk_ped, topk_obs=a.topk_obs, **state_kw)
+        rows = st.mask.numel()
         # flat 2-D rows: on a 3-D (S, cap, .) batch the model would normalise the desired force over the agent axis
         #  and couple the members
-        inputs = (st.pf.view(rows, *st.pf.shape[2:]), st.of.view(rows, *st.of.shape[2:]), st.selff.view(rows, st.selff.shape[-1]))
-        self._run_scenario(sc, T, st, inputs, use_graph)
-        last = int(st.t.item())
-        spawned = st.spawned[:, last & 1].tolist()
-        return scenarios.ScenarioEnsemble(
-            seeds=seeds, position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res,
-            mask_p=st.mask_res, waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles,
-            time_unit=sc.time_unit, spawned=spawned, dropped=st.dropped.tolist(), spawn_count=st.spawn_count,
-            capacity=cap, state=st)
+        inputs = (st.pf.view(rows, *st.pf.shape[-2:]), st.of.view(rows, *st.of.shape[-2:]), st.selff.view(rows, st.selff.shape[-1]))
+        self._run_scenario(st, inputs, use_graph)
+        return scenarios.scenario_result(st)
 
-    def _run_scenario(self, sc, T, st, inputs, use_graph):
+    def _run_scenario(self, st, inputs, use_graph):
         """frame 0's spawn and features, then T - 1 frames of model(inputs) -> scenario_step -> relative features (the
         model's rows `inputs` are views of st's feature buffers), captured and replayed when use_graph."""
         from .. import ops_scenario, hip_graphs_safe
-        a = self.args
+        a, sc, T = self.args, st.scenario, st.T
         feats = (st.pf, st.of, st.selff, st.ped_idx, st.obs_idx)
         geo = (a.topk_ped, a.sight_angle_ped, a.dist_threshold_ped, a.topk_obs, a.sight_angle_obs, a.dist_threshold_obs)
         ops_scenario.scenario_step(st, init=True)                                         # frame 0: generate(n_initial)

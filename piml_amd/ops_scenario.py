@@ -1,10 +1,10 @@
 """Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_step_rules,
 piml_scenario_step_members, piml_scenario_step_mlapm, piml_scenario_route).
 
-`scenario_state` allocates the persistent (static-address) buffers of one simulation and the `piml_scenario` descriptor
-that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive, retire, spawn, record), with the
-frame index read from device memory so that one captured launch serves every frame of a replayed graph.  Like every
-operator of piml_amd they require GPU tensors and raise PimlHipError otherwise."""
+`scenario_state` allocates the persistent (static-address) buffers of one simulation or an ensemble and the
+`piml_scenario` descriptor that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive,
+retire, spawn, record), with the frame index read from device memory so that one captured launch serves every frame of a
+replayed graph.  Like every operator of piml_amd they require GPU tensors and raise PimlHipError otherwise."""
 import ctypes
 import math
 import types
@@ -38,10 +38,11 @@ def scenario_route(origin, destination, polyline, max_iters=16, clearance=2.0):
 def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6, topk_obs=10, seeds=None):
     """The buffers of one simulation of `scenario` (on its device) with `capacity` slots and `frames` recorded frames,
     and their descriptor.  Absent slots start as NaN positions / destinations, zero velocity, acceleration and masks.
-    seeds (a sequence of ints): an ensemble of S = len(seeds) simulations instead, every buffer but the frame counter with
-    a leading member axis (state (S, capacity, .), waypoints (S, D, capacity, 2), records (S, T, capacity, .), spawned
-    (S, 2), dropped (S), features (S, capacity, k, 6)); `seed` is then unused and st.seeds holds the seeds' 64-bit
-    patterns as a device int64 tensor (piml_scenario_step_members)."""
+    seeds (a sequence of ints): an ensemble of S = st.members = len(seeds) simulations instead, every buffer but the frame
+    counter with a leading member axis (state (S, capacity, .), waypoints (S, D, capacity, 2), records (S, T, capacity, .),
+    spawned (S, 2), dropped (S), features (S, capacity, k, 6)); `seed` is then unused.  A single run has st.members None
+    and is the one member of its launch: st.seeds holds the 64-bit patterns of the seed or seeds as a device int64 tensor,
+    and st.rules the scene's piml_scenario_rules (GC's all-zero one for GC)."""
     dev = scenario.entries.device
     if dev.type != 'cuda':
         raise _lib.PimlHipError(f'scenario_state: the scenario must be on a GPU (piml_amd has no CPU path), got {dev}')
@@ -54,9 +55,9 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
         seeds = [int(x) for x in seeds]
         if not 1 <= len(seeds) <= MAX_MEMBERS:
             raise ValueError(f'seeds: 1 .. {MAX_MEMBERS} of them expected, got {len(seeds)}')
-        bits = [(x & 0xFFFFFFFFFFFFFFFF) - ((x & 0x8000000000000000) << 1) for x in seeds]   # two's complement int64
         st.members, st.seed_list, lead = len(seeds), seeds, (len(seeds),)
-        st.seeds = torch.tensor(bits, device=dev, dtype=torch.long)
+    bits = [(x & 0xFFFFFFFFFFFFFFFF) - ((x & 0x8000000000000000) << 1) for x in (seeds or [int(seed)])]   # int64 patterns
+    st.seeds = torch.tensor(bits, device=dev, dtype=torch.long)
     f32 = dict(device=dev, dtype=torch.float32)
     nan = float('nan')
     st.p = torch.full((*lead, cap, 2), nan, **f32)
@@ -110,7 +111,7 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
     for j, x in enumerate(thr):
         s.poisson_thresholds[j] = x
     st.desc = s
-    st.rules = scenario_rules(scenario) if scenario.spawn_law != 'gc' else None
+    st.rules = scenario_rules(scenario) if scenario.spawn_law != 'gc' else _lib.ScenarioRules()
     return st
 
 
@@ -149,18 +150,9 @@ def scenario_step(st, a_next=None, init=False):
         if tuple(a_next.shape) != want or a_next.device != st.p.device:
             raise ValueError(f'a_next: {want} on {st.p.device} expected, got {tuple(a_next.shape)} on {a_next.device}')
     with torch.cuda.device(st.p.device):
-        if st.members is not None:
-            _lib.check(_lib.lib().piml_scenario_step_members(ctypes.byref(st.desc),
-                                                             ctypes.byref(st.rules) if st.rules is not None else None,
-                                                             st.members, _ptr(st.seeds), _ptr(a_next) if not init else None,
-                                                             int(bool(init)), _stream()), 'piml_scenario_step_members')
-        elif st.rules is None:                               # GC
-            _lib.check(_lib.lib().piml_scenario_step(ctypes.byref(st.desc), _ptr(a_next) if not init else None,
-                                                     int(bool(init)), _stream()), 'piml_scenario_step')
-        else:
-            _lib.check(_lib.lib().piml_scenario_step_rules(ctypes.byref(st.desc), ctypes.byref(st.rules),
-                                                           _ptr(a_next) if not init else None, int(bool(init)), _stream()),
-                       'piml_scenario_step_rules')
+        _lib.check(_lib.lib().piml_scenario_step_members(ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(),
+                                                         _ptr(st.seeds), _ptr(a_next) if not init else None,
+                                                         int(bool(init)), _stream()), 'piml_scenario_step_members')
 
 
 def mlapm_law(version='GC', tau=0.5, A=7.55, B=-3.0, C=0.2, D=-0.3, theta=56.0, radius=0.3):
@@ -193,18 +185,9 @@ def scenario_step_mlapm(st, law, frame_offset=0, advance=True):
         raise TypeError(f'law: an ops_scenario.mlapm_law(...) expected, got {type(law).__name__}')
     if int(frame_offset) < 0:
         raise ValueError(f'frame_offset must be >= 0, got {frame_offset}')
-    if st.members is not None:
-        members, seeds = st.members, st.seeds
-    else:
-        seeds = getattr(st, 'seed_dev', None)
-        if seeds is None:                                    # the single run is member 0 of a one-member launch
-            bits = (st.seed & 0xFFFFFFFFFFFFFFFF) - ((st.seed & 0x8000000000000000) << 1)
-            seeds = st.seed_dev = torch.tensor([bits], device=st.p.device, dtype=torch.long)
-        members = 1
     with torch.cuda.device(st.p.device):
-        _lib.check(_lib.lib().piml_scenario_step_mlapm(ctypes.byref(st.desc),
-                                                       ctypes.byref(st.rules) if st.rules is not None else None,
-                                                       members, _ptr(seeds), ctypes.byref(law), int(frame_offset),
-                                                       _stream()), 'piml_scenario_step_mlapm')
+        _lib.check(_lib.lib().piml_scenario_step_mlapm(ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(),
+                                                       _ptr(st.seeds), ctypes.byref(law), int(frame_offset), _stream()),
+                   'piml_scenario_step_mlapm')
         if advance:
             st.t.add_(1)

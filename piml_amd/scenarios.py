@@ -6,7 +6,8 @@ reference's Grand Central hall (src/data/scenarios.py:313-401, GC()) tensor for 
 (scenarios.py:9-311: crosswalk, four_directional_square, basic_unit1..3) are the same record with a scene rule instead of
 entries and a route: a spawn law, an arrival rule, an initial-velocity law, a speed law and an optional second Poisson
 stream (`spawn_law`, `arrival_rule`, ...; piml_scenario_rules).  The per-frame work -- integration, arrival, retirement,
-Poisson arrivals, recording -- is one HIP launch (piml_scenario_step / piml_scenario_step_rules, piml_amd/csrc/scenario.hip).
+Poisson arrivals, recording -- is one HIP launch of scenario_frame_kernel (piml_amd/csrc/scenario.hip), for a single run
+and an ensemble alike; `scenario_state_for` / `scenario_result` are every simulator's set-up and result.
 
 `ScenarioEnsemble` is what `BaseSimulator.simulate_ensemble` returns: S simulations of one scene (one per seed) with a
 leading member axis, each of them a `ScenarioResult` through `member(m)`.
@@ -301,6 +302,32 @@ class ScenarioEnsemble(types.SimpleNamespace):
         from . import ops
         thr = (float(threshold),)
         return torch.stack([ops.collision_counts(p, thr)[0].sum() for p in self.position]).tolist()
+
+
+def scenario_state_for(scenario, frames, capacity=None, device='cuda', hist_width=2, **kw):
+    """ops_scenario.scenario_state of `scenario` moved to `device`, for `frames` (>= 1) recorded frames and `capacity` slots
+    (default: default_capacity); kw: scenario_state's seed / seeds / topk_ped / topk_obs.  The set-up of every simulator's
+    simulate_scenario / simulate_ensemble."""
+    from . import ops_scenario
+    sc = scenario.to(torch.device(device))
+    T = int(frames)
+    if T < 1:
+        raise ValueError(f'frames must be >= 1, got {frames}')
+    cap = default_capacity(sc, T) if capacity is None else int(capacity)
+    return ops_scenario.scenario_state(sc, cap, T, int(hist_width), **kw)
+
+
+def scenario_result(st):
+    """The ScenarioResult of a finished single-run state of scenario_state_for, or the ScenarioEnsemble of an ensemble's."""
+    sc, last = st.scenario, int(st.t.item())
+    common = dict(position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res, mask_p=st.mask_res,
+                  waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles, time_unit=sc.time_unit,
+                  spawn_count=st.spawn_count, capacity=st.capacity, state=st)
+    if st.members is None:
+        return ScenarioResult(spawned=int(st.spawned[last & 1].item()), dropped=int(st.dropped.item()), seed=st.seed,
+                              **common)
+    return ScenarioEnsemble(seeds=st.seed_list, spawned=st.spawned[:, last & 1].tolist(), dropped=st.dropped.tolist(),
+                            **common)
 
 
 def clip_tuple(position, mask_p, waypoints, destination, obstacles, meta_data):

@@ -103,4 +103,5 @@ def test_frame_kernel_builds_for_gfx950_without_scratch(tmp_path):
     names = [n for n, _ in report if n]
     scratch = [int(s) for _, s in report if s]
     assert len(names) == len(scratch) and any('scenario_mlapm_kernel' in n for n in names), names
+    assert sum('scenario_frame_kernel' in n for n in names) == 2, names         # one instantiation per scene law
     assert all(s == 0 for s in scratch), dict(zip(names, scratch))
