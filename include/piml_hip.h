@@ -253,6 +253,35 @@ int piml_mlapm_fit_loss_grad(const float* state, const float* destination, const
                              long long workspace_doubles, double* loss, float* grad, void* stream);
 
 /*
+ * Calibration of MLAPM's constants on multi-frame rollouts: loss and parameter gradient of H closed-loop steps per window,
+ * forward and adjoint in one launch (mlapm_rollout_fit.hip).  Extends the one-step loss above to the reference's
+ * multi-frame rollout training (multiple_rollout_mse_loss with time_decay, src/models/simulators.py:172-193, 659-832) on
+ * the MLAPM law (src/models/mlapm.py:10-58, explicit Euler of src/main_mlapm.py:25).
+ *   The windows are packed (piml_amd/calibrate.py pack_windows): window w (W of them) owns the slots
+ *   [slot_offsets[w], slot_offsets[w + 1]) (S in all); entry (w, k, s) = (H + 1) slot_offsets[w] + k n_w + s, k = 0 .. H,
+ *   holds rec_state (4) = the recorded (p, v) of frame t0 + k, destination (2) and flags (1 byte: bit 0 present, bit 1
+ *   injected, bit 2 carried from k - 1); desired_speed (S) per slot.  small_windows (n_small): windows of <= 64 slots,
+ *   H <= 48 (a lane per slot, states in LDS); big_windows (n_big) with big_base (n_big) = the prefix sum of their slot
+ *   counts (big_slots in all): a wave per focal slot, states in the workspace.  params (6) on the device.
+ *   Carried slots step v' = MLAPM.step over the slots present in k (piml_mlapm_step_fwd's variants and arithmetic),
+ *   p' = p + v' dt; entering slots take their recorded state.  loss (1, float64) = sum_k,s w_k |p^ - P|^2 / sum w_k over
+ *   the carried (k >= 1, slot), w_k = time_decay^(H - k) (0 without terms); grad (6, float32) = d loss / d params through
+ *   the whole chain (view, rotation sign and the UCY flag are constant; unused constants exactly 0).  per_step (2 H
+ *   float64, optional): the squared-error sums, then the term counts, of k = 1 .. H.
+ *   workspace: piml_mlapm_rollout_fit_workspace_doubles(n_small + n_big, H, big_slots) float64 (-1 for negative sizes or
+ *   H < 1).  Deterministic (no atomics, fixed-order float64 sums).  hipErrorInvalidValue before any launch for negative
+ *   sizes, H < 1, small windows with H > 48, n_small + n_big > W, a variant outside 0..2, dt not finite and > 0, radius
+ *   not finite and >= 0, time_decay not finite and >= 0, a NULL buffer that is needed, or a short workspace.
+ */
+long long piml_mlapm_rollout_fit_workspace_doubles(int n_windows, int horizon, long long big_slots);
+int piml_mlapm_rollout_fit_loss_grad(const float* rec_state, const float* destination, const unsigned char* flags,
+                                     const float* desired_speed, const int* slot_offsets, int W, long long S, int horizon,
+                                     const int* small_windows, int n_small, const int* big_windows, const int* big_base,
+                                     int n_big, long long big_slots, const float* params, int variant, float dt,
+                                     float radius, double time_decay, double* workspace, long long workspace_doubles,
+                                     double* loss, float* grad, double* per_step, void* stream);
+
+/*
  * Collision matrix, pair part of Pedestrians.collision_detection (src/data/data.py:549-564):
  * coll (S, N, N) = [|p_j - p_i| < threshold] (- I when minus_identity), NaN -> 0; S slices.
  * With minus_identity = 0 it is the `real_position` matrix of data.py:576-581.

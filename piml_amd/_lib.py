@@ -103,6 +103,9 @@ SIGNATURES = {
     'piml_mlapm_step_bwd_ws': [_p, _p, _p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, _ll, _p],
     'piml_mlapm_fit_workspace_doubles': [_i, _i],
     'piml_mlapm_fit_loss_grad': [_p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _p, _i, _p, _i, _f, _f, _p, _ll, _p, _p, _p],
+    'piml_mlapm_rollout_fit_workspace_doubles': [_i, _i, _ll],
+    'piml_mlapm_rollout_fit_loss_grad': [_p, _p, _p, _p, _p, _i, _ll, _i, _p, _i, _p, _p, _i, _ll, _p, _i, _f, _f, _d,
+                                         _p, _ll, _p, _p, _p, _p],
     'piml_collision_matrix': [_p, _i, _i, _f, _i, _p, _p],
     'piml_collision_friends': [_p, _p, _i, _i, _i, _i, _p],
     'piml_collision_counts': [_p, _i, _i, _p, _i, _p, _p],
@@ -276,6 +279,7 @@ def lib():
         L.piml_encoder_split_tiles_train.restype = _ll
         L.piml_mlapm_bwd_workspace_floats.restype = _ll
         L.piml_mlapm_fit_workspace_doubles.restype = _ll
+        L.piml_mlapm_rollout_fit_workspace_doubles.restype = _ll
         L.piml_error_string.argtypes = [_i]
         L.piml_error_string.restype = ctypes.c_char_p
         if L.piml_abi_version() != ABI_VERSION:

@@ -1,13 +1,16 @@
 """Calibrate MLAPM's constants (tau, A, B, C, D, theta) to a clip on the GPU.
 
-    python -m piml_amd.calibrate --data clip.npy --version GC [--init A=7.55,B=-3] [--fit A,B,theta] [--frames a:b]
-                                 [--valid_frames c:d] [--steps N] --out params.json
+    python -m piml_amd.calibrate --data clip.npy [clip2.npy ...] --version GC [--init A=7.55,B=-3] [--fit A,B,theta]
+                                 [--frames a:b] [--valid_frames c:d] [--horizon H [--stride S] [--time_decay g]]
+                                 [--steps N] --out params.json
 
 The clip is a recorded GC / UCY clip, or one that `python -m piml_amd.simulate` wrote with a trained PINNSF: fitting the
 closed-form law to the network's own trajectories distils it into MLAPM's six constants.  The loss is the mean squared
 residual of one MLAPM.step per (frame, agent) against the agent's velocity in the next frame, and its gradient with
-respect to the constants is analytic (piml_mlapm_fit_loss_grad, one pass over the pairs).  `MLAPM(**result.params)`
-simulates with the result."""
+respect to the constants is analytic (piml_mlapm_fit_loss_grad, one pass over the pairs).  With --horizon H the loss is
+instead the mean squared position error of H closed-loop MLAPM steps per window, the law's own errors fed back through
+the neighbours as `simulate --law mlapm` runs it (piml_mlapm_rollout_fit_loss_grad, forward and adjoint in one launch).
+`MLAPM(**result.params)` simulates with the result."""
 import argparse
 import json
 import math
@@ -39,7 +42,10 @@ def _frame_list(frames, T):
 def pack_clip(raw_data, frames=None, desired_speed=None, skip_frames=25, target=None, device=None):
     """A clip as the fit kernel reads it, built once per fit.
 
-    raw_data: a `RawData` (loaded clip, or `ScenarioResult.to_raw_data()`).  An agent is present in frame t when its
+    raw_data: a `RawData` (loaded clip, or `ScenarioResult.to_raw_data()`), or a list of them: the frames of a fit are
+    independent, so several clips pack as the concatenation of their single packs (frames, entries and focal lists in
+    clip order; `desired_speed` / `target` then a list with one value per clip, or one scalar speed for all; every clip's
+    time unit must agree).  An agent is present in frame t when its
     position, velocity and destination are finite there and (where the clip has `mask_v`) its velocity is not the
     loader's placeholder of its last frame.  Present agents are compacted frame-major (CSR): `offsets` (F + 1) int32,
     then per entry `state` (p, v), `destination`, `desired_speed`, `target`; the entries of a frame are its only sources.
@@ -51,6 +57,8 @@ def pack_clip(raw_data, frames=None, desired_speed=None, skip_frames=25, target=
     from .data.data import desired_speed_per_agent
     if device is None:
         device = 'cuda' if torch.cuda.is_available() else 'cpu'
+    if isinstance(raw_data, (list, tuple)):
+        return _pack_clips(raw_data, frames, desired_speed, skip_frames, target, device)
     P = torch.as_tensor(raw_data.position).detach().float().cpu()
     V = torch.as_tensor(raw_data.velocity).detach().float().cpu()
     D = torch.as_tensor(raw_data.destination).detach().float().cpu()
@@ -99,6 +107,151 @@ def pack_clip(raw_data, frames=None, desired_speed=None, skip_frames=25, target=
         time_unit=float(getattr(raw_data, 'time_unit', 0.0) or 0.0))
 
 
+def _clip_time_unit(clips):
+    units = [float(getattr(c, 'time_unit', 0.0) or 0.0) for c in clips]
+    if any(not math.isclose(u, units[0], rel_tol=1e-9, abs_tol=0.0) for u in units):
+        raise ValueError(f'the clips have different time units: {units}')
+    return units[0]
+
+
+def _per_clip(value, clips, name):
+    if isinstance(value, (list, tuple)):
+        if len(value) != len(clips):
+            raise ValueError(f'{name}: one value per clip ({len(clips)}), got {len(value)}')
+        return list(value)
+    if value is not None and name == 'target':
+        raise ValueError('target: one (T, N, 2) tensor per clip')
+    return [value] * len(clips)
+
+
+def _pack_clips(clips, frames, desired_speed, skip_frames, target, device):
+    """pack_clip of several clips: the concatenation of their single packs."""
+    if not clips:
+        raise ValueError('no clip to pack')
+    unit = _clip_time_unit(clips)
+    packs = [pack_clip(c, frames=frames, desired_speed=ds, skip_frames=skip_frames, target=tg, device=device)
+             for c, ds, tg in zip(clips, _per_clip(desired_speed, clips, 'desired_speed'), _per_clip(target, clips, 'target'))]
+    e0 = [0]
+    f0 = [0]
+    for p in packs:
+        e0.append(e0[-1] + p.num_entries)
+        f0.append(f0[-1] + len(p.frames))
+    if e0[-1] >= 2 ** 31:
+        raise ValueError(f'{e0[-1]} entries: more than the kernel indexes (int32)')
+    cat = lambda name: torch.cat([getattr(p, name) for p in packs])            # noqa: E731
+    shifted = lambda name, base: torch.cat([getattr(p, name) + b for p, b in zip(packs, base)])  # noqa: E731
+    offsets = torch.cat([packs[0].offsets[:1]] + [p.offsets[1:] + e for p, e in zip(packs, e0)])
+    return types.SimpleNamespace(
+        state=cat('state'), destination=cat('destination'), desired_speed=cat('desired_speed'), target=cat('target'),
+        offsets=offsets, frame_of=shifted('frame_of', f0), small_focal=shifted('small_focal', e0),
+        big_focal=shifted('big_focal', e0), frames=[f for p in packs for f in p.frames], frame=cat('frame'),
+        agent=cat('agent'), clip=torch.cat([torch.full((p.num_entries,), c, dtype=torch.int64) for c, p in enumerate(packs)]),
+        num_entries=e0[-1], num_focal=sum(p.num_focal for p in packs), time_unit=unit)
+
+
+def _present_and_speed(raw_data, desired_speed, skip_frames):
+    """pack_clip's presence rule and per-agent desired speed of one clip, on the CPU."""
+    from .data.data import desired_speed_per_agent
+    P = torch.as_tensor(raw_data.position).detach().float().cpu()
+    V = torch.as_tensor(raw_data.velocity).detach().float().cpu()
+    D = torch.as_tensor(raw_data.destination).detach().float().cpu()
+    N = P.shape[1]
+    present = torch.isfinite(P).all(-1) & torch.isfinite(V).all(-1) & torch.isfinite(D).all(-1)
+    mask_v = getattr(raw_data, 'mask_v', None)
+    if mask_v is not None:
+        present &= torch.as_tensor(mask_v).cpu() != 0
+    if desired_speed is None:
+        v0 = desired_speed_per_agent(torch.where(present.unsqueeze(-1), V, torch.zeros_like(V)), skip_frames)
+    else:
+        v0 = torch.as_tensor(desired_speed, dtype=torch.float32).detach().cpu().reshape(-1)
+        v0 = v0.expand(N).clone() if v0.numel() == 1 else v0
+        if v0.numel() != N:
+            raise ValueError(f'desired_speed must hold N={N} values, got {v0.numel()}')
+    return P, V, D, present, v0
+
+
+ROLL_SMALL = 64           # windows up to this many slots: a lane per slot, states in LDS (with horizon <= ROLL_SMALL_MAX_H)
+ROLL_SMALL_MAX_H = 48
+PRESENT, INJECTED, CARRIED = 1, 2, 4
+
+
+def pack_windows(data, horizon, frames=None, stride=1, desired_speed=None, skip_frames=25, device=None):
+    """Rollout windows of one or more clips as the rollout-fit kernel reads them, built once per fit.
+
+    data: a `RawData` (a loaded clip or `ScenarioResult.to_raw_data()`) or a list of them; windows never cross clips and
+    every clip's time unit must agree.  Presence is pack_clip's rule.  frames: the frame range of every clip (None = all;
+    a slice, 'a:b' or a list of consecutive frames).  A window starts at every `stride`-th frame t0 of the range whose
+    t0 + horizon is in the range too, and its slots are the agents present in any of its frames t0 .. t0 + horizon,
+    ascending.  Entry (w, k, s) = (H + 1) slot_offsets[w] + k n_w + s: `rec` (p, v) recorded in frame t0 + k (0 where
+    absent), `destination`, `flags` (PRESENT; INJECTED: present and not in k - 1, or k = 0; CARRIED: present in k and
+    k - 1, one loss term).  desired_speed: per clip as pack_clip (a list for several clips, or one scalar for all).
+    small_windows / big_windows: windows of <= 64 slots (when horizon <= 48) / the others, with big_base the prefix sum
+    of the big windows' slot counts."""
+    clips = list(data) if isinstance(data, (list, tuple)) else [data]
+    if not clips:
+        raise ValueError('no clip to pack')
+    H = int(horizon)
+    if H < 1:
+        raise ValueError(f'horizon must be >= 1, got {horizon}')
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError(f'stride must be >= 1, got {stride}')
+    if device is None:
+        device = 'cuda' if torch.cuda.is_available() else 'cpu'
+    unit = _clip_time_unit(clips)
+    recs, dests, flags, speeds, counts, agents, clip_of, starts = [], [], [], [], [], [], [], []
+    for c, (raw, ds) in enumerate(zip(clips, _per_clip(desired_speed, clips, 'desired_speed'))):
+        P, V, D, present, v0 = _present_and_speed(raw, ds, skip_frames)
+        fl = _frame_list(frames, P.shape[0])
+        if fl and fl != list(range(fl[0], fl[0] + len(fl))):
+            raise ValueError('the frame range of a rollout fit must be consecutive frames')
+        state = torch.where(present.unsqueeze(-1), torch.cat((P, V), -1), torch.zeros(()))
+        dest = torch.where(present.unsqueeze(-1), D, torch.zeros(()))
+        for s in range(0, len(fl) - H, stride):
+            t0 = fl[s]
+            pres = present[t0:t0 + H + 1]                                     # (H + 1, N)
+            ag = pres.any(0).nonzero(as_tuple=True)[0]
+            pw = pres[:, ag]
+            prev = torch.cat((torch.zeros(1, len(ag), dtype=torch.bool), pw[:-1]), 0)
+            fw = pw.to(torch.uint8) * PRESENT + (pw & ~prev).to(torch.uint8) * INJECTED + (pw & prev).to(torch.uint8) * CARRIED
+            recs.append(state[t0:t0 + H + 1, ag].reshape(-1, 4))
+            dests.append(dest[t0:t0 + H + 1, ag].reshape(-1, 2))
+            flags.append(fw.reshape(-1))
+            speeds.append(v0[ag])
+            counts.append(len(ag))
+            agents.append(ag)
+            clip_of.append(c)
+            starts.append(t0)
+    W = len(counts)
+    cnt = torch.tensor(counts, dtype=torch.int64)
+    offsets = torch.zeros(W + 1, dtype=torch.int64)
+    offsets[1:] = torch.cumsum(cnt, 0)
+    S = int(offsets[-1])
+    if (H + 1) * S >= 2 ** 31:
+        raise ValueError(f'{(H + 1) * S} window entries: more than the packing indexes (int32)')
+    small = (cnt <= ROLL_SMALL) if H <= ROLL_SMALL_MAX_H else torch.zeros(W, dtype=torch.bool)
+    w_idx = torch.arange(W, dtype=torch.int64)
+    big_cnt = cnt[~small]
+    big_base = torch.zeros(len(big_cnt), dtype=torch.int64)
+    if len(big_cnt):
+        big_base[1:] = torch.cumsum(big_cnt, 0)[:-1]
+    fl_all = torch.cat(flags) if flags else torch.zeros(0, dtype=torch.uint8)
+    carried = ((fl_all & CARRIED) != 0).reshape(-1)
+    # terms per k: the entries of window w are k-major blocks of n_w
+    k_of = torch.cat([torch.arange(H + 1).repeat_interleave(n) for n in counts]) if counts else torch.zeros(0, dtype=torch.int64)
+    per_k = torch.bincount(k_of[carried], minlength=H + 1)[1:] if counts else torch.zeros(H, dtype=torch.int64)
+    i32 = lambda x: x.to(torch.int32).contiguous().to(device)                 # noqa: E731
+    f32 = lambda x: x.to(torch.float32).contiguous().to(device)               # noqa: E731
+    return types.SimpleNamespace(
+        rec=f32(torch.cat(recs) if recs else torch.zeros(0, 4)), destination=f32(torch.cat(dests) if dests else torch.zeros(0, 2)),
+        flags=fl_all.contiguous().to(device), desired_speed=f32(torch.cat(speeds) if speeds else torch.zeros(0)),
+        slot_offsets=i32(offsets), small_windows=i32(w_idx[small]), big_windows=i32(w_idx[~small]), big_base=i32(big_base),
+        big_slots=int(big_cnt.sum()), horizon=H, stride=stride, num_windows=W, num_slots=S,
+        num_terms=int(carried.sum()), terms_per_step=per_k.tolist(), slot_count=counts,
+        agent=torch.cat(agents) if agents else torch.zeros(0, dtype=torch.int64), clip=clip_of, start=starts,
+        time_unit=unit)
+
+
 def _params_vector(d, device):
     return torch.tensor([float(d[k]) for k in PARAM_NAMES], dtype=torch.float32, device=device)
 
@@ -112,17 +265,39 @@ def mlapm_fit_loss(pack, params, version='GC', dt=None, radius=0.3):
     return float(loss.item()), grad.cpu().tolist()
 
 
+def mlapm_rollout_fit_loss(pack, params, version='GC', dt=None, radius=0.3, time_decay=1.0, per_step=False):
+    """(loss, grad) of the rollout loss on a pack_windows result at `params` (a dict of the six constants, or a (6,)
+    device tensor) as Python numbers; with per_step=True also (sse, count), the squared-error sums and term counts of
+    k = 1 .. H as lists."""
+    from . import ops
+    dev = pack.rec.device
+    p = params if isinstance(params, torch.Tensor) else _params_vector({**DEFAULT_INIT, **params}, dev)
+    ps = torch.empty(2 * pack.horizon, dtype=torch.float64, device=dev) if per_step else None
+    loss, grad = ops.mlapm_rollout_fit_loss_grad(pack, p, version, pack.time_unit if dt is None else dt, radius,
+                                                 time_decay, per_step=ps)
+    if not per_step:
+        return float(loss.item()), grad.cpu().tolist()
+    ps = ps.cpu().tolist()
+    return float(loss.item()), grad.cpu().tolist(), (ps[:pack.horizon], ps[pack.horizon:])
+
+
 class CalibrationResult(types.SimpleNamespace):
     """params: {'version', 'tau', 'A', 'B', 'C', 'D', 'theta'} -- `MLAPM(**params)` as is; initial_loss / final_loss;
-    history: the loss before each optimiser step; steps; fit: the names that were fitted."""
+    history: the loss before each optimiser step; steps; fit: the names that were fitted; horizon: None (one-step
+    velocity loss) or the rollout length of the position loss."""
 
 
 def calibrate_mlapm(data, version='GC', init=None, fit=PARAM_NAMES, steps=500, lr=0.02, lr_final=0.01, use_graph=True,
                     graph_steps=50, radius=0.3, dt=None, frames=None, desired_speed=None, skip_frames=25, target=None,
-                    betas=(0.9, 0.999), eps=1e-12, device=None):
+                    betas=(0.9, 0.999), eps=1e-12, device=None, horizon=None, stride=1, time_decay=1.0):
     """Fit MLAPM's constants to a clip with Adam on the device.
 
-    data: a RawData (packed here with pack_clip(frames, desired_speed, skip_frames, target)) or a pack_clip result.
+    data: a RawData or a list of them (packed here with pack_clip(frames, desired_speed, skip_frames, target)) or a
+    pack_clip result.
+    horizon: None fits the one-step velocity loss above (piml_mlapm_fit_loss_grad).  horizon=H fits the H-step rollout
+    loss instead (piml_mlapm_rollout_fit_loss_grad: windows of pack_windows(data, H, frames, stride, desired_speed,
+    skip_frames), or a pack_windows result as `data`; positions weighted by time_decay^(H - k)), with the same Adam,
+    schedule, masking and capture.
     init: starting constants (default: main_mlapm.py's, DEFAULT_INIT); fit: the names that move, the others stay fixed
     (their gradient is masked).  dt: the clip's time unit by default.
     One iteration = piml_mlapm_fit_loss_grad + an Adam step of the 6-vector, both on the device.  Adam runs on
@@ -138,10 +313,21 @@ def calibrate_mlapm(data, version='GC', init=None, fit=PARAM_NAMES, steps=500, l
     unknown = [k for k in fit if k not in PARAM_NAMES]
     if unknown:
         raise ValueError(f'unknown constants to fit: {unknown} (of {PARAM_NAMES})')
-    pack = data if hasattr(data, 'offsets') else pack_clip(data, frames=frames, desired_speed=desired_speed,
-                                                            skip_frames=skip_frames, target=target, device=device)
-    dev = pack.state.device
-    if not pack.state.is_cuda:
+    if horizon is None:
+        pack = data if hasattr(data, 'offsets') else pack_clip(data, frames=frames, desired_speed=desired_speed,
+                                                                skip_frames=skip_frames, target=target, device=device)
+        ref = pack.state
+    else:
+        if target is not None:
+            raise ValueError('target: the rollout loss fits recorded positions')
+        pack = data if hasattr(data, 'slot_offsets') else pack_windows(data, horizon, frames=frames, stride=stride,
+                                                                       desired_speed=desired_speed,
+                                                                       skip_frames=skip_frames, device=device)
+        if int(pack.horizon) != int(horizon):
+            raise ValueError(f'the pack holds windows of {pack.horizon} steps, not {horizon}')
+        ref = pack.rec
+    dev = ref.device
+    if not ref.is_cuda:
         raise ValueError('calibrate_mlapm needs the clip packed on a GPU')
     dt = pack.time_unit if dt is None else float(dt)
     if not dt > 0:
@@ -162,9 +348,14 @@ def calibrate_mlapm(data, version='GC', init=None, fit=PARAM_NAMES, steps=500, l
         hist = torch.zeros(max(steps, 1), dtype=torch.float64, device=dev)
         b1, b2 = betas
         one = torch.ones(1, dtype=torch.float64, device=dev)
+        if horizon is None:
+            loss_grad = lambda **kw: ops.mlapm_fit_loss_grad(pack, params, version, dt, radius, **kw)   # noqa: E731
+        else:
+            loss_grad = lambda **kw: ops.mlapm_rollout_fit_loss_grad(pack, params, version, dt, radius,  # noqa: E731
+                                                                     time_decay, **kw)
 
         def iteration():
-            ops.mlapm_fit_loss_grad(pack, params, version, dt, radius, loss=loss, grad=grad)
+            loss_grad(loss=loss, grad=grad)
             hist.index_copy_(0, t_idx, loss)
             t_idx.add_(1)
             t.add_(1.0)
@@ -178,7 +369,7 @@ def calibrate_mlapm(data, version='GC', init=None, fit=PARAM_NAMES, steps=500, l
             x.sub_(lr_t * mhat / (vhat.sqrt() + eps))
             params.copy_(x * scale)
 
-        ops.mlapm_fit_loss_grad(pack, params, version, dt, radius, loss=loss, grad=grad)    # also sizes the workspace
+        loss_grad(loss=loss, grad=grad)                        # also sizes the workspace
         initial = loss.clone()
         done = 0
         per = max(1, int(graph_steps))
@@ -195,12 +386,12 @@ def calibrate_mlapm(data, version='GC', init=None, fit=PARAM_NAMES, steps=500, l
             done += (steps - done) // per * per
         for _ in range(steps - done):
             iteration()
-        final, _ = ops.mlapm_fit_loss_grad(pack, params, version, dt, radius)
+        final, _ = loss_grad()
         out = params.double().cpu().tolist()
     res = {'version': version}
     res.update({k: float(val) for k, val in zip(PARAM_NAMES, out)})
     return CalibrationResult(params=res, initial_loss=float(initial.item()), final_loss=float(final.item()),
-                             history=hist[:steps].cpu().tolist(), steps=steps, fit=tuple(fit))
+                             history=hist[:steps].cpu().tolist(), steps=steps, fit=tuple(fit), horizon=horizon)
 
 
 def _parse_init(text):
@@ -223,12 +414,17 @@ def _parse_fit(text):
 
 def get_args(argv=None):
     p = argparse.ArgumentParser(description="fit MLAPM's constants (tau, A, B, C, D, theta) to a clip on the GPU")
-    p.add_argument('--data', type=str, required=True, help='a v2.2 clip (.npy), recorded or written by piml_amd.simulate')
+    p.add_argument('--data', type=str, nargs='+', required=True,
+                   help='one or more v2.2 clips (.npy), recorded or written by piml_amd.simulate')
     p.add_argument('--version', type=str, default='GC', choices=['raw', 'GC', 'UCY'])
     p.add_argument('--init', type=_parse_init, default={}, help='starting constants, e.g. A=7.55,B=-3 (default: main_mlapm.py\'s)')
     p.add_argument('--fit', type=_parse_fit, default=PARAM_NAMES, help='constants to fit, e.g. A,B,theta (default: all six)')
     p.add_argument('--frames', type=str, default=None, help='training frames a:b (default: all)')
     p.add_argument('--valid_frames', type=str, default=None, help='held-out frames c:d: their loss is reported before and after')
+    p.add_argument('--horizon', type=int, default=None,
+                   help='fit H-step closed-loop rollouts (position error) instead of one step (velocity error)')
+    p.add_argument('--stride', type=int, default=1, help='rollout windows start every this many frames')
+    p.add_argument('--time_decay', type=float, default=1.0, help='rollout step k weighs time_decay^(H - k)')
     p.add_argument('--steps', type=int, default=500)
     p.add_argument('--lr', type=float, default=0.02, help='Adam step size relative to each constant\'s magnitude')
     p.add_argument('--radius', type=float, default=0.3)
@@ -241,10 +437,16 @@ def get_args(argv=None):
 def main(argv=None):
     a = get_args(argv)
     from .data.data import RawData
-    raw = RawData()
-    raw.load_trajectory_data(a.data)
-    pack = pack_clip(raw, frames=a.frames, skip_frames=a.skip_frames)
+    raws = []
+    for path in a.data:
+        raw = RawData()
+        raw.load_trajectory_data(path)
+        raws.append(raw)
+    raw = raws[0] if len(raws) == 1 else raws
     init = {**DEFAULT_INIT, **a.init}
+    if a.horizon is not None:
+        return _main_rollout(a, raw, init)
+    pack = pack_clip(raw, frames=a.frames, skip_frames=a.skip_frames)
     res = calibrate_mlapm(pack, version=a.version, init=init, fit=a.fit, steps=a.steps, lr=a.lr, radius=a.radius,
                           use_graph=not a.no_graph)
     print(f'[calibrate] {a.version} on {len(pack.frames)} frames, {pack.num_focal} agent steps: loss {res.initial_loss:.6g} -> '
@@ -255,6 +457,28 @@ def main(argv=None):
         before, _ = mlapm_fit_loss(vp, init, a.version, radius=a.radius)
         after, _ = mlapm_fit_loss(vp, res.params, a.version, radius=a.radius)
         print(f'[calibrate] held-out loss ({len(vp.frames)} frames, {vp.num_focal} agent steps): {before:.6g} -> {after:.6g}')
+    with open(a.out, 'w') as fh:
+        json.dump(res.params, fh, indent=1)
+    print(f'[calibrate] wrote {a.out}')
+    return res
+
+
+def _main_rollout(a, raw, init):
+    pack = pack_windows(raw, a.horizon, frames=a.frames, stride=a.stride, skip_frames=a.skip_frames)
+    res = calibrate_mlapm(pack, version=a.version, init=init, fit=a.fit, steps=a.steps, lr=a.lr, radius=a.radius,
+                          use_graph=not a.no_graph, horizon=a.horizon, time_decay=a.time_decay)
+    print(f'[calibrate] {a.version} on {pack.num_windows} windows of {a.horizon} steps, {pack.num_terms} agent steps: '
+          f'rollout loss {res.initial_loss:.6g} -> {res.final_loss:.6g} m^2 after {res.steps} steps')
+    print('[calibrate] ' + ', '.join(f'{k}={res.params[k]:.6g}' for k in PARAM_NAMES))
+    if a.valid_frames:
+        vp = pack_windows(raw, a.horizon, frames=a.valid_frames, stride=a.stride, skip_frames=a.skip_frames)
+        out = []
+        for prm in (init, res.params):
+            loss, _, (sse, cnt) = mlapm_rollout_fit_loss(vp, prm, a.version, radius=a.radius, time_decay=a.time_decay,
+                                                         per_step=True)
+            out.append((loss, math.sqrt(sse[-1] / cnt[-1]) if cnt[-1] else float('nan')))
+        print(f'[calibrate] held-out rollout loss ({vp.num_windows} windows, {vp.num_terms} agent steps): '
+              f'{out[0][0]:.6g} -> {out[1][0]:.6g} m^2; RMSE at k = {a.horizon}: {out[0][1]:.4g} -> {out[1][1]:.4g} m')
     with open(a.out, 'w') as fh:
         json.dump(res.params, fh, indent=1)
     print(f'[calibrate] wrote {a.out}')

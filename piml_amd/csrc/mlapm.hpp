@@ -1,5 +1,6 @@
 // Pair arithmetic shared by the MLAPM kernels (pairwise.hip: step / rollout / state gradient; mlapm_fit.hip: loss and
-// parameter gradient for calibration; scenario.hip: the MLAPM scenario frame).
+// parameter gradient for calibration; mlapm_rollout_fit.hip: the same over multi-frame rollouts; scenario.hip: the MLAPM
+// scenario frame).
 #pragma once
 #include "common.hpp"
 
@@ -250,6 +251,131 @@ __device__ __forceinline__ void mlapm_tile_sum(const MlapmParams& P, const float
         const float2 t = mlapm_pair(P, s.x - pi.x, s.y - pi.y, s.z - vi.x, s.w - vi.y, vi.x, vi.y, ex, ey);
         sx += t.x; sy += t.y;
     }
+}
+
+// d(-G . T)/d(vr), d(-G . T)/d(vv) of one ordered pair, T the pair term of mlapm_pair and
+// (Gx, Gy) the upstream gradient on the focal agent's force.  view, the rotation sign and the
+// UCY collision flag are piecewise constant and carry no gradient (as in autograd).
+__device__ __forceinline__ void mlapm_pair_grad(const MlapmParams& P, float rx, float ry, float wx, float wy,
+                                                float vix, float viy, float ex, float ey, float Gx, float Gy,
+                                                float& ax, float& ay, float& bx, float& by, int ucy_flag = -1) {
+    ax = ay = bx = by = 0.f;
+    const float d2 = rx * rx + ry * ry;
+    if (!(d2 > 0.f) || !(vix * rx + viy * ry > 0.f)) return;
+    const float rinv = fast_rsq(d2), r = d2 * rinv;
+    const float nx = rx * rinv, ny = ry * rinv;
+    float st = 0.f, ct = 1.f;
+    if (P.variant != 0) {
+        const float cr = rx * ey - ry * ex;
+        st = cr > 0.f ? -P.sth : P.sth; ct = P.cth;
+    }
+    const float ux = ct * Gx + st * Gy, uy = -st * Gx + ct * Gy;   // R^T G
+    const float un = ux * nx + uy * ny;
+    float phi2, fx, fy, hx = 0.f, hy = 0.f;                        // phi*log2e, d(phi)/d(vr), d(phi)/d(vv)
+    if (P.variant == 0) {
+        phi2 = P.B2 * r; fx = P.B * nx; fy = P.B * ny;
+    } else if (P.variant == 1) {
+        const float w2 = wx * wx + wy * wy;
+        const float ri8 = fminf(rinv, 1e8f), qi8 = fminf(fast_rsq(w2), 1e8f);
+        const float n8x = rx * ri8, n8y = ry * ri8, mx = wx * qi8, my = wy * qi8;
+        const float cs = n8x * mx + n8y * my;
+        phi2 = P.B2 * r + P.C2 * cs + P.D2 * r * cs;
+        const float k1 = P.Cc + P.D * r;
+        const bool r_ok = r > 1e-8f, q_ok = w2 > 1e-16f;
+        const float csx = (r_ok ? mx - cs * n8x : mx) * ri8;       // d(cs)/d(vr)
+        const float csy = (r_ok ? my - cs * n8y : my) * ri8;
+        fx = P.B * nx + k1 * csx + P.D * cs * nx;
+        fy = P.B * ny + k1 * csy + P.D * cs * ny;
+        hx = k1 * (q_ok ? n8x - cs * mx : n8x) * qi8;              // d(cs)/d(vv)
+        hy = k1 * (q_ok ? n8y - cs * my : n8y) * qi8;
+    } else {
+        const float cf = (ucy_flag >= 0 ? ucy_flag != 0 : ucy_collision(rx, ry, wx, wy, P.r2)) ? 1.f : 0.f;      // the forward's exact flag
+        phi2 = (P.B2 * r + P.C2) * cf; fx = P.B * cf * nx; fy = P.B * cf * ny;
+    }
+    const float AE = -P.A * fast_exp2(phi2);
+    ax = AE * (un * fx + (ux - un * nx) * rinv);
+    ay = AE * (un * fy + (uy - un * ny) * rinv);
+    bx = AE * un * hx;
+    by = AE * un * hy;
+}
+
+// The constants of a calibration launch, read from device memory (mlapm_fit.hip, mlapm_rollout_fit.hip), and the
+// per-focal parameter sums of the calibration kernels.
+struct FitConst {
+    float tau, A, B2, C2, D2, cth, sth, r2;
+    int variant;
+};
+
+__device__ __forceinline__ FitConst fit_const(const float* __restrict__ params, int variant, float radius) {
+    FitConst K;
+    K.variant = variant;
+    K.tau = params[0]; K.A = params[1];
+    const float log2e = 1.4426950408889634f;
+    K.B2 = params[2] * log2e; K.C2 = params[3] * log2e; K.D2 = params[4] * log2e;
+    // cos / sin of theta pi / 180 by sincospif (make_params forms theta / 180 * pi and calls cosf / sinf on the host; the two
+    // agree to an ulp, and sincospif needs no large-argument reduction, which would put an array in scratch memory)
+    sincospif(params[5] / 180.f, &K.sth, &K.cth);
+    K.r2 = radius * 2.f;
+    return K;
+}
+
+// The focal agent's sums over its sources, with u = view * g (mlapm.py:25-53) and dir the (rotated) unit direction:
+//   U = sum u dir            (force = A U;            d force / dA = U)
+//   UB = sum u kB dir        (d force / dB = A UB;    kB = r, UCY r [coll])
+//   UC = sum u kC dir        (d force / dC = A UC;    kC = cos (GC), [coll] (UCY))
+//   UD = sum u r cos dir     (d force / dD = A UD;    GC)
+//   UT = sum u d dir / d theta_deg   (rotation R(s theta pi / 180), GC and UCY)
+struct FitAcc {
+    float ux, uy, bx, by, cx, cy, dx, dy, tx, ty;
+};
+
+__device__ __forceinline__ void fit_pair(const FitConst& K, float rx, float ry, float wx, float wy, float vix, float viy,
+                                         float ex, float ey, FitAcc& a) {
+    // (every sum is updated unconditionally, with zero factors where a term does not apply: selects rather than branches
+    // keep the accumulators in registers)
+    const float d2 = rx * rx + ry * ry;
+    const bool pos = d2 > 0.f;
+    const float rinv = fast_rsq(d2);
+    const float r = pos ? d2 * rinv : d2;                           // :26
+    const float view = (vix * rx + viy * ry > 0.f) ? 1.f : 0.f;     // :27
+    const float ninv = pos ? rinv : 0.f;
+    const float nx = rx * ninv, ny = ry * ninv;
+    float u, kB = r, kC = 0.f, kD = 0.f, dirx = nx, diry = ny, ddx = 0.f, ddy = 0.f;
+    if (K.variant == 0) {
+        u = fast_exp2(K.B2 * r);                                    // :29
+    } else {
+        const float cr = rx * ey - ry * ex;                         // :34 / :48
+        const float sg = cr > 0.f ? -1.f : 1.f;                     // theta_ij = -sign(cr) theta, 0 -> +theta
+        const float st = sg * K.sth;
+        dirx = K.cth * nx - st * ny; diry = st * nx + K.cth * ny;   // :36-39
+        // d dir / d theta_deg = (pi / 180) sg (-sin nx - cos ny, cos nx - sin ny) at theta_ij
+        const float k = sg * 0.017453292519943295f;
+        ddx = k * (-st * nx - K.cth * ny); ddy = k * (K.cth * nx - st * ny);
+        if (K.variant == 1) {
+            const float w2 = wx * wx + wy * wy;
+            const float cs = (rx * wx + ry * wy) * fminf(rinv, 1e8f) * fminf(fast_rsq(w2), 1e8f);   // :32
+            u = fast_exp2(K.B2 * r + K.C2 * cs + K.D2 * r * cs);     // :40
+            kC = cs; kD = r * cs;
+        } else {
+            const bool coll = ucy_collision(rx, ry, wx, wy, K.r2);  // :43-47, exact; no gradient
+            u = coll ? fast_exp2(K.B2 * r + K.C2) : 1.f;            // :53 (coll.unsqueeze(-1))
+            kB = coll ? r : 0.f; kC = coll ? 1.f : 0.f;
+        }
+    }
+    u *= view;
+    const float ux = u * dirx, uy = u * diry;
+    a.ux += ux; a.uy += uy;
+    a.bx += kB * ux; a.by += kB * uy;
+    a.cx += kC * ux; a.cy += kC * uy;
+    a.dx += kD * ux; a.dy += kD * uy;
+    a.tx += u * ddx; a.ty += u * ddy;
+}
+
+// float64 sum over the 64 lanes of a wave (fixed butterfly order)
+__device__ __forceinline__ double wave_sum_d(double x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
 }
 
 // the constants of a launch (host)

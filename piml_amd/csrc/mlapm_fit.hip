@@ -34,76 +34,6 @@ struct FitPack {
     int E, F;
 };
 
-struct FitConst {
-    float tau, A, B2, C2, D2, cth, sth, r2;
-    int variant;
-};
-
-__device__ __forceinline__ FitConst fit_const(const float* __restrict__ params, int variant, float radius) {
-    FitConst K;
-    K.variant = variant;
-    K.tau = params[0]; K.A = params[1];
-    const float log2e = 1.4426950408889634f;
-    K.B2 = params[2] * log2e; K.C2 = params[3] * log2e; K.D2 = params[4] * log2e;
-    // cos / sin of theta pi / 180 by sincospif (make_params forms theta / 180 * pi and calls cosf / sinf on the host; the two
-    // agree to an ulp, and sincospif needs no large-argument reduction, which would put an array in scratch memory)
-    sincospif(params[5] / 180.f, &K.sth, &K.cth);
-    K.r2 = radius * 2.f;
-    return K;
-}
-
-// The focal agent's sums over its sources, with u = view * g (mlapm.py:25-53) and dir the (rotated) unit direction:
-//   U = sum u dir            (force = A U;            d force / dA = U)
-//   UB = sum u kB dir        (d force / dB = A UB;    kB = r, UCY r [coll])
-//   UC = sum u kC dir        (d force / dC = A UC;    kC = cos (GC), [coll] (UCY))
-//   UD = sum u r cos dir     (d force / dD = A UD;    GC)
-//   UT = sum u d dir / d theta_deg   (rotation R(s theta pi / 180), GC and UCY)
-struct FitAcc {
-    float ux, uy, bx, by, cx, cy, dx, dy, tx, ty;
-};
-
-__device__ __forceinline__ void fit_pair(const FitConst& K, float rx, float ry, float wx, float wy, float vix, float viy,
-                                         float ex, float ey, FitAcc& a) {
-    // (every sum is updated unconditionally, with zero factors where a term does not apply: selects rather than branches
-    // keep the accumulators in registers)
-    const float d2 = rx * rx + ry * ry;
-    const bool pos = d2 > 0.f;
-    const float rinv = fast_rsq(d2);
-    const float r = pos ? d2 * rinv : d2;                           // :26
-    const float view = (vix * rx + viy * ry > 0.f) ? 1.f : 0.f;     // :27
-    const float ninv = pos ? rinv : 0.f;
-    const float nx = rx * ninv, ny = ry * ninv;
-    float u, kB = r, kC = 0.f, kD = 0.f, dirx = nx, diry = ny, ddx = 0.f, ddy = 0.f;
-    if (K.variant == 0) {
-        u = fast_exp2(K.B2 * r);                                    // :29
-    } else {
-        const float cr = rx * ey - ry * ex;                         // :34 / :48
-        const float sg = cr > 0.f ? -1.f : 1.f;                     // theta_ij = -sign(cr) theta, 0 -> +theta
-        const float st = sg * K.sth;
-        dirx = K.cth * nx - st * ny; diry = st * nx + K.cth * ny;   // :36-39
-        // d dir / d theta_deg = (pi / 180) sg (-sin nx - cos ny, cos nx - sin ny) at theta_ij
-        const float k = sg * 0.017453292519943295f;
-        ddx = k * (-st * nx - K.cth * ny); ddy = k * (K.cth * nx - st * ny);
-        if (K.variant == 1) {
-            const float w2 = wx * wx + wy * wy;
-            const float cs = (rx * wx + ry * wy) * fminf(rinv, 1e8f) * fminf(fast_rsq(w2), 1e8f);   // :32
-            u = fast_exp2(K.B2 * r + K.C2 * cs + K.D2 * r * cs);     // :40
-            kC = cs; kD = r * cs;
-        } else {
-            const bool coll = ucy_collision(rx, ry, wx, wy, K.r2);  // :43-47, exact; no gradient
-            u = coll ? fast_exp2(K.B2 * r + K.C2) : 1.f;            // :53 (coll.unsqueeze(-1))
-            kB = coll ? r : 0.f; kC = coll ? 1.f : 0.f;
-        }
-    }
-    u *= view;
-    const float ux = u * dirx, uy = u * diry;
-    a.ux += ux; a.uy += uy;
-    a.bx += kB * ux; a.by += kB * uy;
-    a.cx += kC * ux; a.cy += kC * uy;
-    a.dx += kD * ux; a.dy += kD * uy;
-    a.tx += u * ddx; a.ty += u * ddy;
-}
-
 // One focal entry's row: prediction v + dt ((v0 e - v) / tau - A U) (mlapm.py:21-22, :57), residual against the target,
 // and 2 r . d pred / d param, in float64 from the float32 sums.  Unused constants get exactly 0.
 __device__ __forceinline__ void fit_focal_row(const FitConst& K, float dt, float4 s, float2 d, float v0, float2 tg,
@@ -134,12 +64,6 @@ __device__ __forceinline__ bool frame_range(const FitPack& Q, int e, int& lo, in
     if (f < 0 || f >= Q.F) return false;
     lo = max(Q.offsets[f], 0); hi = min(Q.offsets[f + 1], Q.E);
     return true;
-}
-
-__device__ __forceinline__ double wave_sum_d(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
 }
 
 // lanes = focal entries of frames with <= 64 agents

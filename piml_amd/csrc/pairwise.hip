@@ -102,52 +102,6 @@ __global__ __launch_bounds__(WAVES * 64) void mlapm_fwd_kernel(
     }
 }
 
-// d(-G . T)/d(vr), d(-G . T)/d(vv) of one ordered pair, T the pair term of mlapm_pair and
-// (Gx, Gy) the upstream gradient on the focal agent's force.  view, the rotation sign and the
-// UCY collision flag are piecewise constant and carry no gradient (as in autograd).
-__device__ __forceinline__ void mlapm_pair_grad(const MlapmParams& P, float rx, float ry, float wx, float wy,
-                                                float vix, float viy, float ex, float ey, float Gx, float Gy,
-                                                float& ax, float& ay, float& bx, float& by, int ucy_flag = -1) {
-    ax = ay = bx = by = 0.f;
-    const float d2 = rx * rx + ry * ry;
-    if (!(d2 > 0.f) || !(vix * rx + viy * ry > 0.f)) return;
-    const float rinv = fast_rsq(d2), r = d2 * rinv;
-    const float nx = rx * rinv, ny = ry * rinv;
-    float st = 0.f, ct = 1.f;
-    if (P.variant != 0) {
-        const float cr = rx * ey - ry * ex;
-        st = cr > 0.f ? -P.sth : P.sth; ct = P.cth;
-    }
-    const float ux = ct * Gx + st * Gy, uy = -st * Gx + ct * Gy;   // R^T G
-    const float un = ux * nx + uy * ny;
-    float phi2, fx, fy, hx = 0.f, hy = 0.f;                        // phi*log2e, d(phi)/d(vr), d(phi)/d(vv)
-    if (P.variant == 0) {
-        phi2 = P.B2 * r; fx = P.B * nx; fy = P.B * ny;
-    } else if (P.variant == 1) {
-        const float w2 = wx * wx + wy * wy;
-        const float ri8 = fminf(rinv, 1e8f), qi8 = fminf(fast_rsq(w2), 1e8f);
-        const float n8x = rx * ri8, n8y = ry * ri8, mx = wx * qi8, my = wy * qi8;
-        const float cs = n8x * mx + n8y * my;
-        phi2 = P.B2 * r + P.C2 * cs + P.D2 * r * cs;
-        const float k1 = P.Cc + P.D * r;
-        const bool r_ok = r > 1e-8f, q_ok = w2 > 1e-16f;
-        const float csx = (r_ok ? mx - cs * n8x : mx) * ri8;       // d(cs)/d(vr)
-        const float csy = (r_ok ? my - cs * n8y : my) * ri8;
-        fx = P.B * nx + k1 * csx + P.D * cs * nx;
-        fy = P.B * ny + k1 * csy + P.D * cs * ny;
-        hx = k1 * (q_ok ? n8x - cs * mx : n8x) * qi8;              // d(cs)/d(vv)
-        hy = k1 * (q_ok ? n8y - cs * my : n8y) * qi8;
-    } else {
-        const float cf = (ucy_flag >= 0 ? ucy_flag != 0 : ucy_collision(rx, ry, wx, wy, P.r2)) ? 1.f : 0.f;      // the forward's exact flag
-        phi2 = (P.B2 * r + P.C2) * cf; fx = P.B * cf * nx; fy = P.B * cf * ny;
-    }
-    const float AE = -P.A * fast_exp2(phi2);
-    ax = AE * (un * fx + (ux - un * nx) * rinv);
-    ay = AE * (un * fy + (uy - un * ny) * rinv);
-    bx = AE * un * hx;
-    by = AE * un * hy;
-}
-
 // mlapm_pair_grad for the raw / GC laws on 2-vectors: element 0 and element 1 are two ordered pairs that may
 // differ in everything (the backward kernel feeds it the two roles of one unordered pair).  Same expressions,
 // packed fp32 arithmetic; a pair outside the view half plane (or at zero distance) yields exact zeros.

@@ -611,6 +611,47 @@ def mlapm_fit_loss_grad(pack, params, version='GC', dt=0.08, radius=0.3, loss=No
                                               _ptr(loss), _ptr(grad), _stream()), 'piml_mlapm_fit_loss_grad')
     return loss, grad
 
+def mlapm_rollout_fit_loss_grad(pack, params, version='GC', dt=0.08, radius=0.3, time_decay=1.0, loss=None, grad=None,
+                                per_step=None):
+    """Loss and gradient of MLAPM's constants on H-step closed-loop rollouts (piml_mlapm_rollout_fit_loss_grad; `pack`
+    from `piml_amd.calibrate.pack_windows`): loss = sum over the carried (window, k >= 1, agent) of
+    w_k |p^_k - P_k|^2 / sum w_k, w_k = time_decay^(H - k), grad = d loss / d params through the whole rollout.
+    params: float32 (6,) on the device, read by the kernel from device memory (a fit iteration can be captured).
+    per_step: a float64 (2 H,) device tensor to receive the squared-error sums and then the term counts of k = 1 .. H.
+    Returns (loss float64 (1,), grad float32 (6,)) on the device, written into `loss` / `grad` when given; never
+    synchronises.  Deterministic: two calls give bitwise equal results."""
+    if version not in MLAPM_VARIANTS:
+        raise NotImplementedError(version)
+    prm = _gpu_f32('params', params)
+    if prm.numel() != 6:
+        raise ValueError(f'params must hold 6 values (tau, A, B, C, D, theta), got {tuple(params.shape)}')
+    if not pack.rec.is_cuda or pack.rec.device != prm.device:
+        raise _lib.PimlHipError('mlapm_rollout_fit_loss_grad: the pack and params must be on the same GPU (pack_windows(device=...))')
+    dev = prm.device
+    H = int(pack.horizon)
+    if loss is None:
+        loss = torch.empty(1, device=dev, dtype=torch.float64)
+    if grad is None:
+        grad = torch.empty(6, device=dev, dtype=torch.float32)
+    if loss.dtype != torch.float64 or grad.dtype != torch.float32 or loss.numel() != 1 or grad.numel() != 6:
+        raise ValueError('loss: float64 (1,), grad: float32 (6,)')
+    if per_step is not None and (per_step.dtype != torch.float64 or per_step.numel() != 2 * H or per_step.device != dev):
+        raise ValueError(f'per_step: float64 ({2 * H},) on the device')
+    L = _lib.lib()
+    n_small, n_big = int(pack.small_windows.numel()), int(pack.big_windows.numel())
+    ws = getattr(pack, 'workspace', None)
+    need = int(L.piml_mlapm_rollout_fit_workspace_doubles(n_small + n_big, H, int(pack.big_slots)))
+    if ws is None or ws.numel() < need or ws.device != dev:
+        ws = pack.workspace = torch.empty(max(need, 2), device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(L.piml_mlapm_rollout_fit_loss_grad(
+            _ptr(pack.rec), _ptr(pack.destination), _ptr(pack.flags), _ptr(pack.desired_speed), _ptr(pack.slot_offsets),
+            int(pack.slot_offsets.numel()) - 1, int(pack.desired_speed.numel()), H, _ptr(pack.small_windows), n_small,
+            _ptr(pack.big_windows), _ptr(pack.big_base), n_big, int(pack.big_slots), _ptr(prm), MLAPM_VARIANTS[version],
+            float(dt), float(radius), float(time_decay), _ptr(ws), ws.numel(), _ptr(loss), _ptr(grad),
+            _ptr(per_step) if per_step is not None else None, _stream()), 'piml_mlapm_rollout_fit_loss_grad')
+    return loss, grad
+
 # ------------------------------------------------------------------------------------------
 # collisions (Pedestrians.collision_detection / calculate_collision_label)
 # ------------------------------------------------------------------------------------------
