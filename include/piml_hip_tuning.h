@@ -88,6 +88,11 @@ int piml_encoder_fused_bwd(int on);
  * two forms agree bitwise.  Environment at load time: PIML_ENC_SUMS_BWD=1 / 2.  Returns the previous value; other arguments
  * only query. */
 int piml_encoder_sums_bwd(int form);
+/* Where the decoder's weight-gradient slots of that backward are summed (two-crew form only; same summation order, bitwise the same
+ * gradients): 1 (default) = by the encoder backward's workgroups, so that the unfold of the folded first layers (reduce.hpp) runs
+ * as workgroups of the slot-sum launch instead of a launch of its own; 0 = by the slot-sum launch, the unfold behind it.
+ * Environment at load time: PIML_ENC_DEC_SLOTS=0 / 1.  Returns the previous value; < 0 only queries. */
+int piml_encoder_sums_dec_slots(int on);
 /* The library-owned side streams of PIML_FORK (piml_pinnsf_fwd / bwd with the independent stages forked: measured slower inside
  * captured graphs, kept for A/B): created per device on first use, outside any capture; idempotent. */
 int piml_pinnsf_streams_init(void);

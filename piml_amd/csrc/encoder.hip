@@ -1310,7 +1310,8 @@ int piml::enc_stage_fwd_sum(const piml_encoder_branch* br, int nbr, hipStream_t 
 }
 
 // backward of enc_stage_fwd_sum: the one-pass kernel without its W3^T layer and without dW3 (encoder_bwd3.hip, SUMS = true)
-int piml::enc_stage_bwd_sum(const piml_encoder_branch* br, int nbr, hipStream_t s) {
+int piml::enc_stage_bwd_sum(const piml_encoder_branch* br, int nbr, hipStream_t s, const DecSlotSums* dec, bool* dec_summed) {
+    if (dec_summed) *dec_summed = false;
     if (int e = enc_check(br, nbr)) return e;
     if (!enc_pool_train_ok(br, nbr)) return hipErrorInvalidValue;
     for (int i = 0; i < nbr; ++i) {
@@ -1325,7 +1326,8 @@ int piml::enc_stage_bwd_sum(const piml_encoder_branch* br, int nbr, hipStream_t 
     if (ready) return ready;
     const int nA[2] = {nbr > 1 ? A.wg_split : total, nbr > 1 ? total - A.wg_split : 0};
     const int zero[2] = {0, 0};
-    if (g_sums_bwd == 1 || !enc_f5_launch(A, nA, s)) enc_f3_launch(A, nA, zero, false, s, true);
+    if (g_sums_bwd == 1 || !enc_f5_launch(A, nA, s, dec)) enc_f3_launch(A, nA, zero, false, s, true);
+    else if (dec_summed) *dec_summed = dec && dec->nsets > 0;
     return hipGetLastError();
 }
 

@@ -84,8 +84,9 @@ int enc_f3_set_attributes();
 // sums: the PIML_POOL_TRAIN form (G2 = g_pooled[agent] * [h2 > 0]: no W3^T layer, no dW3; sign words of h2 in the exchanged layout)
 void enc_f3_launch(const EncArgs& A, const int* nA, const int* slot0, bool with_dw3, hipStream_t s, bool sums = false);
 // encoder_bwd5.hip: the PIML_POOL_TRAIN backward as two crews of four waves (chain | weight gradients), two waves per SIMD;
-// bitwise the results of enc_f3_launch(..., sums = true).  false: a shape it does not take (the caller falls back)
+// bitwise the results of enc_f3_launch(..., sums = true).  false: a shape it does not take (the caller falls back).  dec (optional,
+// dec->nsets > 0): the launch's workgroups also sum the decoder's slot sets, in the order of the slot-sum launch (pack.hpp)
 int enc_f5_set_attributes();
-bool enc_f5_launch(const EncArgs& A, const int* nA, hipStream_t s);
+bool enc_f5_launch(const EncArgs& A, const int* nA, hipStream_t s, const DecSlotSums* dec = nullptr);
 
 }  // namespace piml

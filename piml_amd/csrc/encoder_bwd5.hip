@@ -82,7 +82,53 @@ constexpr int F5_PART1 = EH * EH + 1024 + 2 * EH;            // = F3_PART1 (enco
 struct F5Args {
     EncArgs A;
     int nA[2];          // workgroups of branch 0 / branch 1 (grid = their sum)
+    DecSlotSums D;      // the decoder's slot sets, summed by this launch's workgroups (D.nsets = 0: left to the slot-sum launch)
 };
+
+// Where the decoder slot sums run: 1 = crew A alone, between its last tile and its trailing barriers, i.e. while crew B works on the
+// last tile and stores its slot (crew A only waits there); 0 = behind both crews' epilogues, every thread of the workgroup
+#ifndef PIML_F5_DEC_AT
+#define PIML_F5_DEC_AT 1
+#endif
+
+// row_shl:C of a DPP row (16 lanes): lane i reads lane i + C
+template <int C>
+__device__ __forceinline__ float f5_row_shl(float v) {
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x100 + C, 0xf, 0xf, false));
+}
+// lane 0 of the row: s (its own chain 0) += the chains of lanes 1 .. 15, in that order
+template <int C>
+__device__ __forceinline__ void f5_chains_add(float4& s, const float4 v) {
+    if constexpr (C < 16) {
+        slot_chains_add(s, make_float4(f5_row_shl<C>(v.x), f5_row_shl<C>(v.y), f5_row_shl<C>(v.z), f5_row_shl<C>(v.w)));
+        f5_chains_add<C + 1>(s, v);
+    }
+}
+// The decoder sets' slot sums (pack.hpp: slot_chains, the summation order of the slot-sum launch): workgroup wg of nwg owns float4
+// columns [wg per, (wg + 1) per) of the sets' concatenation; thread t of nthr takes chain t & 15 of columns t >> 4 and t >> 4 +
+// nthr / 16 of every round of nthr / 8 columns (all 16 loads in flight: at cfg3 one round for crew A), so the 16 chains of a
+// column are one DPP row and meet in its lane 0 without LDS.
+__device__ __forceinline__ void f5_dec_sums(const DecSlotSums& D, int wg, int nwg, int t, int nthr) {
+    const int total = D.nsets * D.lanes, per = (total + nwg - 1) / nwg;
+    const int e1 = min(wg * per + per, total), half = nthr >> 4;
+    for (int e = wg * per + (t >> 4); e < e1; e += 2 * half) {          // (the 16 lanes of a row share e: a row is active or not)
+        const bool two = e + half < e1;
+        const int ea = e, eb = two ? e + half : e;
+        const int sa = ea >= D.lanes ? 1 : 0, sb = eb >= D.lanes ? 1 : 0;
+        const float4* const p[2] = {reinterpret_cast<const float4*>(sa ? D.parts[1] : D.parts[0]),
+                                    reinterpret_cast<const float4*>(sb ? D.parts[1] : D.parts[0])};
+        const int j[2] = {ea - sa * D.lanes, eb - sb * D.lanes};
+        float4 s[2];
+        slot_chains<2>(p, D.slots, D.lanes, j, t & 15, s);
+        const float4 va = s[0], vb = s[1];
+        f5_chains_add<1>(s[0], va);
+        f5_chains_add<1>(s[1], vb);
+        if ((t & 15) == 0) {
+            slot_sum_store(reinterpret_cast<float4*>(sa ? D.grads[1] : D.grads[0]) + j[0], s[0], D.accumulate != 0);
+            if (two) slot_sum_store(reinterpret_cast<float4*>(sb ? D.grads[1] : D.grads[0]) + j[1], s[1], D.accumulate != 0);
+        }
+    }
+}
 
 #ifdef PIML_F5_STAMPS
 // diagnostic build only (tools/f5_stamps.py): cycles between the stamps of every wave, summed over the workgroup's tiles
@@ -487,6 +533,10 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
             F5_BARRIER();
         }
         F5_STAMP(3);
+        if (PIML_F5_DEC_AT == 1 && F.D.nsets > 0) {
+            f5_dec_sums(F.D, (int)blockIdx.x, (int)gridDim.x, ctid, 256);
+            F5_STAMP(12);
+        }
         F5_BARRIER();                                          // (crew B's two trailing barriers)
         F5_BARRIER();
         db1 += __shfl_xor(db1, 32, 64);
@@ -809,6 +859,10 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
         }
         F5_STAMP(11);
     }
+    if (PIML_F5_DEC_AT == 0 && F.D.nsets > 0) {
+        f5_dec_sums(F.D, (int)blockIdx.x, (int)gridDim.x, tid, F5_THREADS);
+        F5_STAMP(12);
+    }
 #ifdef PIML_F5_STAMPS
     if (lane == 0)
         for (int i = 0; i < 16; ++i) g_f5_stamps[(blockIdx.x * 8 + wv) * 16 + i] = st[i];
@@ -831,10 +885,11 @@ int enc_f5_set_attributes() {
 
 // the PIML_POOL_TRAIN backward (g_pooled = the gradient of the agents' sums; checked by the caller); false: a shape this kernel
 // does not take (k > 16) -- the caller launches enc_f3_launch(..., sums = true)
-bool enc_f5_launch(const EncArgs& A, const int* nA, hipStream_t s) {
+bool enc_f5_launch(const EncArgs& A, const int* nA, hipStream_t s, const DecSlotSums* D) {
     F5Args F;
     F.A = A;
     F.nA[0] = nA[0]; F.nA[1] = A.nbr > 1 ? nA[1] : 0;
+    F.D = D ? *D : DecSlotSums{};
     bool in6 = true;
     for (int i = 0; i < A.nbr; ++i) {
         if (A.br[i].k > F5_KMAX) return false;

@@ -22,6 +22,7 @@
 //
 // The side streams belong to the library (one pair per device, created on first use outside any capture).
 #include <cstdio>
+#include <cstdlib>
 #include <mutex>
 
 #include "common.hpp"
@@ -93,51 +94,18 @@ int launch_pack(const PackAll& A, hipStream_t s) {
 
 // ---- one launch for every slot sum of the backward pass (reduce.hpp): a set of slots per gx workgroups (encoder branches --
 // one set each, or two with the layer-split slots of encoder_dw2.hip -- then the decoder branches) ----
-__global__ __launch_bounds__(256) void pinnsf_reduce_kernel(ReduceAll A) { reduce_block(A, (int)blockIdx.x); }
+// (with A.unf_blocks > 0 the unfold's workgroups lead: reduce_launch_block)
+__global__ __launch_bounds__(256) void pinnsf_reduce_kernel(ReduceAll A) { reduce_launch_block(A, (int)blockIdx.x); }
 
 int launch_slot_sums(const ReduceAll& R, hipStream_t s) {
-    hipLaunchKernelGGL(pinnsf_reduce_kernel, dim3((unsigned)(R.gx * R.nsets)), dim3(256), 0, s, R);
+    hipLaunchKernelGGL(pinnsf_reduce_kernel, dim3((unsigned)reduce_launch_blocks(R)), dim3(256), 0, s, R);
     return hipGetLastError();
 }
 
-// ---- PIML_POOL_TRAIN: the folded first layers' gradients -> the gradients of their factors (reduce.hpp: UnfoldSet) ----
-// float64 accumulation (the kernel is 4 M multiply-adds: its time is the launch); one thread per output element.
-__global__ __launch_bounds__(256) void pinnsf_unfold_kernel(ReduceAll R) {
-    const UnfoldSet U = R.unf[blockIdx.y];
-    const int x = blockIdx.x, tid = threadIdx.x;
-    const float* __restrict__ G = U.dgrads;
-    const float* __restrict__ gb = U.dgrads + DD * DH + DD * DD + 2 * DD;
-    const double sc = (double)U.scale;
-    if (x < 64) {                     // row x of dW1: s (G[x][:] W3^T + k g_b[x] b3)
-        __shared__ float g[DH];
-        __shared__ double part[256];
-        if (tid < DH) g[tid] = G[(size_t)x * DH + tid];
-        __syncthreads();
-        const int m = tid & 127, half = tid >> 7;
-        const float4* wr = reinterpret_cast<const float4*>(U.w3 + (size_t)m * EH + 64 * half);
-        double a = 0.0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const float4 wv = wr[q];
-            const float* gq = g + 64 * half + 4 * q;
-            a += (double)gq[0] * wv.x + (double)gq[1] * wv.y + (double)gq[2] * wv.z + (double)gq[3] * wv.w;
-        }
-        part[tid] = a;
-        __syncthreads();
-        if (tid < DH)
-            U.dw1_out[(size_t)x * DH + tid] = (float)(sc * ((part[tid] + part[tid + 128]) + (double)U.k * (double)gb[x] * (double)U.b3[tid]));
-    } else if (x < 128) {             // rows 2 (x - 64), + 1 of dW3 = s W1^T G
-        const int m = 2 * (x - 64) + (tid >> 7), j = tid & 127;
-        double a = 0.0;
-#pragma unroll 8
-        for (int i = 0; i < DD; ++i) a += (double)U.w1[(size_t)i * DH + m] * (double)G[(size_t)i * DH + j];
-        U.egrads[(size_t)m * EH + j] = (float)(sc * a);
-    } else if (tid < EH) {            // db3 = s k W1^T g_b
-        double a = 0.0;
-        for (int i = 0; i < DD; ++i) a += (double)U.w1[(size_t)i * DH + tid] * (double)gb[i];
-        U.egrads[2 * EH * EH + 8 * EH + tid] = (float)(sc * (double)U.k * a);
-    }
-}
+// ---- PIML_POOL_TRAIN: the folded first layers' gradients -> the gradients of their factors (reduce.hpp: UnfoldSet, unfold_block) ----
+// A launch of its own where the decoder sets are summed by the same slot-sum launch (it has to see their sums) and for a deferred
+// unfold; otherwise the unfold's workgroups ride in the slot-sum launch.
+__global__ __launch_bounds__(256) void pinnsf_unfold_kernel(ReduceAll R) { unfold_block(R, (int)(blockIdx.y * kUnfoldBlocks + blockIdx.x)); }
 
 // (Round 5, built, parity green, measured and removed: the unfold as workgroups of the launch that sums the slots, gated by a
 // device-side ticket the decoder sets' sum workgroups raise -- sums written with device-scope stores, unfold reads through LDS in
@@ -154,7 +122,7 @@ static int launch_unfold_now(const ReduceAll& R, hipStream_t s) {
 // ---- deferred unfold (piml_pinnsf_unfold_defer): one waiting entry per device ----
 // The unfold READS the folded layers' summed gradients and OVERWRITES the unfolded ones, so of the backward passes of one optimiser
 // step that accumulate into the same buffers (PIML_ACCUMULATE: the frames of a training rollout) only the LAST pass's unfold
-// matters -- the earlier ones compute from partial sums what the last one computes again.  While deferring, launch_unfold records
+// matters -- the earlier ones compute from partial sums what the last one computes again.  While deferring, unfold_begin records
 // the sets of a pass that asked for it (PIML_DEFER_UNFOLD, carried in R through deferred slot sums) instead of launching; another
 // network's sets first launch what is waiting.  A pass without the flag launches at once: its buffers are the caller's to read.
 namespace {
@@ -180,23 +148,28 @@ bool same_unfold(const ReduceAll& a, const ReduceAll& b) {
 }
 }  // namespace
 
-int launch_unfold(const ReduceAll& R, hipStream_t s) {
-    if (R.nunf <= 0) return hipSuccess;
+ReduceAll unfold_begin(const ReduceAll& R, hipStream_t s, UnfoldTail* t) {
+    ReduceAll out = R;
+    out.unf_blocks = 0;
+    t->go = false;
+    if (R.nunf <= 0) return out;
     PendingUnfold* P = pending_unfold_entry();
-    ReduceAll old;
-    hipStream_t olds = nullptr;
-    bool flush_old = false, deferred = false;
+    bool deferred = false;
     if (P) {
         std::lock_guard<std::mutex> lock(g_mu);
         if (P->deferring && R.defer_unfold) {
-            if (P->valid && !same_unfold(P->R, R)) { old = P->R; olds = P->stream; flush_old = true; }
+            if (P->valid && !same_unfold(P->R, R)) { t->R = P->R; t->stream = P->stream; t->go = true; }
             P->R = R; P->stream = s; P->valid = true;
             deferred = true;
         }
     }
-    if (!deferred) return launch_unfold_now(R, s);
-    return flush_old ? launch_unfold_now(old, olds) : (int)hipSuccess;
+    if (deferred) return out;
+    if (R.dec_upstream) out.unf_blocks = R.nunf * kUnfoldBlocks;
+    else { t->R = R; t->stream = s; t->go = true; }
+    return out;
 }
+
+int unfold_end(const UnfoldTail& t) { return t.go ? launch_unfold_now(t.R, t.stream) : (int)hipSuccess; }
 
 PIML_API int piml_pinnsf_unfold_defer(int on, void* stream) {
     PendingUnfold* P = pending_unfold_entry();
@@ -287,9 +260,19 @@ int pending_slot_sums_flush() {
         if (!P->valid) return hipSuccess;
         R = P->R; s = P->stream; P->valid = false;
     }
-    if (int e = launch_slot_sums(R, s)) return e;
+    UnfoldTail t;
+    if (int e = launch_slot_sums(unfold_begin(R, s, &t), s)) return e;
     trace_mark("pinnsf_reduce", s);
-    return launch_unfold(R, s);
+    return unfold_end(t);
+}
+
+bool pending_slot_sums_write(const float* grads) {
+    PendingSums* P = pending_entry();
+    if (!P) return false;
+    std::lock_guard<std::mutex> lock(g_mu);
+    for (int i = 0; P->valid && i < P->R.nsets; ++i)
+        if (P->R.set[i].grads == grads) return true;
+    return false;
 }
 
 int pending_slot_sums_leave(const ReduceAll& R, hipStream_t s) {
@@ -375,12 +358,14 @@ PIML_API int piml_pinnsf_pack(const piml_encoder_branch* enc, const piml_decoder
 
 PIML_API int piml_pinnsf_pack_flush(void) { return pending_pack_flush(nullptr); }
 
-// every slot sum of the backward pass (encoder + decoder partials) in one launch on `s`
+// every slot sum of the backward pass (encoder + decoder partials) in one launch on `s`; dec_summed: the decoder sets were summed
+// by the encoder backward (PIML_POOL_TRAIN, encoder_bwd5.hip) -- left out here, and the unfold's workgroups ride in this launch
 static int reduce_all(const piml_encoder_branch* enc, const piml_decoder_branch* dec, int nbr, hipStream_t s, bool accumulate, bool defer = false,
-                      bool sums = false, bool defer_unfold = false) {
+                      bool sums = false, bool defer_unfold = false, bool dec_summed = false) {
     ReduceAll R = {};
     R.accumulate = accumulate ? 1 : 0;
     R.defer_unfold = defer_unfold ? 1 : 0;
+    R.dec_upstream = dec_summed ? 1 : 0;
     int w0 = 0, n = 0, maxl = 0;
     const int total = piml_encoder_workgroups(enc, nbr, &w0);
     const int dslots = piml_decoder_workgroups(dec[0].agents);
@@ -413,13 +398,26 @@ static int reduce_all(const piml_encoder_branch* enc, const piml_decoder_branch*
         }
     }
     div = PIML_REDUCE_DEC_DIV;
-    for (int i = 0; i < nbr; ++i) add(dec[i].partials, dec[i].grads, dslots, DEC_PART / 4, 0x7fffffff, 0, 0);
+    if (!dec_summed)
+        for (int i = 0; i < nbr; ++i) add(dec[i].partials, dec[i].grads, dslots, DEC_PART / 4, 0x7fffffff, 0, 0);
     R.nsets = n;
     R.gx = (maxl + 15) / 16;
     if (defer) return pending_slot_sums_leave(R, s);          // the next piml_relfeat_self_bwd on `s` (or a flush) runs them
-    if (int e = launch_slot_sums(R, s)) return e;
+    UnfoldTail t;
+    if (int e = launch_slot_sums(unfold_begin(R, s, &t), s)) return e;
     trace_mark("pinnsf_reduce", s);
-    return launch_unfold(R, s);
+    return unfold_end(t);
+}
+
+// Decoder slot sets of the PIML_POOL_TRAIN backward: 1 (default) = summed by the two-crew encoder backward's workgroups (the next
+// launch boundary publishes them, and the unfold rides in the slot-sum launch); 0 = by the slot-sum launch, the unfold a launch of
+// its own behind it.  PIML_ENC_DEC_SLOTS=0 / 1 at load time
+static int g_dec_slots_enc = !(getenv("PIML_ENC_DEC_SLOTS") && atoi(getenv("PIML_ENC_DEC_SLOTS")) == 0);
+
+PIML_API int piml_encoder_sums_dec_slots(int on) {
+    const int old = g_dec_slots_enc;
+    if (on >= 0) g_dec_slots_enc = on ? 1 : 0;
+    return old;
 }
 
 PIML_API int piml_pinnsf_slot_sums_flush(void) { return pending_slot_sums_flush(); }
@@ -508,10 +506,24 @@ PIML_API int piml_pinnsf_bwd(const piml_encoder_branch* enc, const piml_decoder_
             if (!dec[i].dw1_out || !dec[i].fold_w3 || dec[i].g_pooled != enc[i].g_pooled) return hipErrorInvalidValue;
         PIML_TRY(dec_stage_bwd_fused(dec, nbr, g_pred, self_features, tau, g_self, m, true));
         trace_mark("dec_bwd", m);
-        PIML_TRY(enc_stage_bwd_sum(enc, nbr, m));
+        // the decoder sets to the encoder backward -- unless deferred sums that write the same gradients still wait: theirs go first
+        DecSlotSums D = {};
+        if (g_dec_slots_enc) {
+            D.nsets = nbr;
+            D.slots = piml_decoder_workgroups(dec[0].agents);
+            D.lanes = DEC_PART / 4;
+            D.accumulate = (flags & PIML_ACCUMULATE) != 0;
+            for (int i = 0; i < nbr; ++i) {
+                D.parts[i] = dec[i].partials;
+                D.grads[i] = dec[i].grads;
+                if (pending_slot_sums_write(dec[i].grads)) D.nsets = 0;
+            }
+        }
+        bool dec_summed = false;
+        PIML_TRY(enc_stage_bwd_sum(enc, nbr, m, D.nsets > 0 ? &D : nullptr, &dec_summed));
         trace_mark("enc_bwd_dx", m);
         return reduce_all(enc, dec, nbr, m, (flags & PIML_ACCUMULATE) != 0, (flags & PIML_DEFER_SLOT_SUMS) != 0, true,
-                          (flags & PIML_DEFER_UNFOLD) != 0);
+                          (flags & PIML_DEFER_UNFOLD) != 0, dec_summed);
     }
     if (!(flags & PIML_FORK)) {
         PIML_TRY(dec_stage_bwd_fused(dec, nbr, g_pred, self_features, tau, g_self, m));

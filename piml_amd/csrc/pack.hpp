@@ -240,43 +240,68 @@ __device__ __forceinline__ void head_fold_store(const piml_collision_head& H, in
 // the gradient buffer: the layer-split slots of encoder_dw2.hip); the plain form is split = lanes, off0 = 0.
 // accumulate: grads += the sum (a second backward pass through the same weights inside one optimiser step).
 // (bx: the column block, blockIdx.x of a launch of its own)
+//
+// THE summation order of a slot sum, wherever it runs (here; the decoder slots inside enc_bwd_sums2_kernel, encoder_bwd5.hip):
+// chain c (0 .. 15) adds slots c, c + 16, c + 32, ... < B in increasing order, starting from 0.f (slot_chains); the chains are added
+// in order 0 .. 15 (slot_chains_add, c = 1 .. 15 onto chain 0); then the accumulate add (slot_sum_store).  slot_chains runs chain
+// c of N float4 columns j[n] of the slot sets at parts[n] (`lanes` columns per slot) with all their loads of a round in flight.
+template <int N>
+__device__ __forceinline__ void slot_chains(const float4* const (&parts)[N], int B, int lanes, const int (&j)[N], int c, float4 (&s)[N]) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) s[n] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int q0 = c; q0 < B; q0 += 16 * 8) {
+        float4 v[N][8];
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int q = q0 + 16 * u;
+                v[n][u] = parts[n][(size_t)(q < B ? q : c) * lanes + j[n]];
+            }
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const bool ok = q0 + 16 * u < B;
+                s[n].x += ok ? v[n][u].x : 0.f; s[n].y += ok ? v[n][u].y : 0.f; s[n].z += ok ? v[n][u].z : 0.f; s[n].w += ok ? v[n][u].w : 0.f;
+            }
+    }
+}
+__device__ __forceinline__ void slot_chains_add(float4& s, const float4 v) { s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+__device__ __forceinline__ void slot_sum_store(float4* dst, float4 s, bool accumulate) {
+    if (accumulate) slot_chains_add(s, *dst);
+    *dst = s;
+}
+
 __device__ __forceinline__ void sum_slots_16x16_at(int bx, const float* __restrict__ partials, float* __restrict__ grads, int B, int lanes,
                                                    int split = 0x7fffffff, int off0 = 0, int off1 = 0, bool accumulate = false) {
     __shared__ float4 sh[256];
     const int col = threadIdx.x & 15, grp = threadIdx.x >> 4;
     const int j = bx * 16 + col;
-    const float4* parts = reinterpret_cast<const float4*>(partials);
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (j < lanes)
-        for (int q0 = grp; q0 < B; q0 += 16 * 8) {
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int q = q0 + 16 * u;
-                v[u] = parts[(size_t)(q < B ? q : grp) * lanes + j];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const bool ok = q0 + 16 * u < B;
-                s.x += ok ? v[u].x : 0.f; s.y += ok ? v[u].y : 0.f; s.z += ok ? v[u].z : 0.f; s.w += ok ? v[u].w : 0.f;
-            }
-        }
+    if (j < lanes) {
+        const float4* const p[1] = {reinterpret_cast<const float4*>(partials)};
+        const int jj[1] = {j};
+        float4 r[1];
+        slot_chains<1>(p, B, lanes, jj, grp, r);
+        s = r[0];
+    }
     sh[threadIdx.x] = s;
     __syncthreads();
     if (grp == 0 && j < lanes) {
 #pragma unroll
-        for (int q = 1; q < 16; ++q) {
-            const float4 v = sh[q * 16 + col];
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-        float4* dst = reinterpret_cast<float4*>(grads) + (j < split ? off0 + j : off1 + (j - split));
-        if (accumulate) {
-            const float4 o = *dst;
-            s.x += o.x; s.y += o.y; s.z += o.z; s.w += o.w;
-        }
-        *dst = s;
+        for (int q = 1; q < 16; ++q) slot_chains_add(s, sh[q * 16 + col]);
+        slot_sum_store(reinterpret_cast<float4*>(grads) + (j < split ? off0 + j : off1 + (j - split)), s, accumulate);
     }
 }
+
+// the decoder sets of a PIML_POOL_TRAIN backward, summed by the encoder backward's workgroups (encoder_bwd5.hip) instead of the
+// slot-sum launch: set i = `slots` slots of `lanes` float4 columns at parts[i] -> grads[i]; nsets = 0: none
+struct DecSlotSums {
+    const float* parts[2];
+    float* grads[2];
+    int nsets, slots, lanes, accumulate;
+};
 
 __device__ __forceinline__ void sum_slots_16x16(const float* __restrict__ partials, float* __restrict__ grads, int B, int lanes,
                                                 int split = 0x7fffffff, int off0 = 0, int off1 = 0, bool accumulate = false) {

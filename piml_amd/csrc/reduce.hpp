@@ -36,11 +36,80 @@ struct ReduceAll {
     int accumulate;       // PIML_ACCUMULATE: grads += the sums
     int gx;               // workgroups per set (the widest set's (lanes + 15) / 16)
     UnfoldSet unf[2];
-    int nunf;             // > 0: launch_unfold behind the sums
+    int nunf;             // > 0: the unfold behind the sums
     int defer_unfold;     // PIML_DEFER_UNFOLD of the pass: its unfold may wait while the device defers (piml_pinnsf_unfold_defer)
+    int dec_upstream;     // the decoder sets were summed by the encoder backward's launch (DecSlotSums, encoder_bwd5.hip): nothing in
+                          // this launch writes what the unfold reads, so its workgroups may ride in it (unfold_begin)
+    int unf_blocks;       // set by unfold_begin: the launch's leading workgroups that run the unfold (nunf * kUnfoldBlocks, or 0)
 };
 constexpr int kUnfoldBlocks = 64 + 64 + 1;       // per set: rows of dW1 | row pairs of dW3 | db3
-int launch_unfold(const ReduceAll& R, hipStream_t s);
+
+// The unfold of R at the launch that sums R's slots, decided once (network.hip).  While the device defers (piml_pinnsf_unfold_defer)
+// a pass that asked for it, R's unfold is recorded and waits; otherwise with R.dec_upstream it rides in the sums launch (the
+// returned description carries unf_blocks), else it is a launch of its own behind it.  unfold_end, behind the sums launch,
+// launches what is left: R's own unfold, or the entry of another network that R's recording replaced.
+struct UnfoldTail {
+    ReduceAll R;
+    hipStream_t stream = nullptr;
+    bool go = false;
+};
+ReduceAll unfold_begin(const ReduceAll& R, hipStream_t s, UnfoldTail* t);
+int unfold_end(const UnfoldTail& t);
+
+// unfold workgroup `bid` of nunf * kUnfoldBlocks: set bid / kUnfoldBlocks, block bid % kUnfoldBlocks.  float64 accumulation (4 M
+// multiply-adds in all: its time was the launch); one thread per output element.  Reads the decoder's summed `grads` (G = the FOLDED
+// dW1' field, g_b = its db1' field), W1, W3, b3; writes dw1_out and the dW3 / db3 fields of the encoder's `grads` -- [0, EH EH) and
+// [2 EH EH + 8 EH, + EH), disjoint from the layer-1 set (DW2_L1_OFF0 / OFF1) the same launch sums into that buffer.  (Unrolled
+// to stay within 64 registers: as leading workgroups of the relfeat backward the body sets that launch's occupancy.)
+__device__ __forceinline__ void unfold_block(const ReduceAll& R, int bid) {
+    const int y = bid / kUnfoldBlocks, x = bid - y * kUnfoldBlocks, tid = (int)threadIdx.x;
+    const UnfoldSet U = R.unf[y];
+    const float* __restrict__ G = U.dgrads;
+    const float* __restrict__ gb = U.dgrads + DD * DH + DD * DD + 2 * DD;
+    const double sc = (double)U.scale;
+    if (x < 64) {                     // row x of dW1: s (G[x][:] W3^T + k g_b[x] b3)
+        __shared__ float g[DH];
+        __shared__ double part[256];
+        if (tid < DH) g[tid] = G[(size_t)x * DH + tid];
+        __syncthreads();
+        const int m = tid & 127, half = tid >> 7;
+        const float4* wr = reinterpret_cast<const float4*>(U.w3 + (size_t)m * EH + 64 * half);
+        double a = 0.0;
+#pragma unroll 8
+        for (int q = 0; q < 16; ++q) {
+            const float4 wv = wr[q];
+            const float* gq = g + 64 * half + 4 * q;
+            a += (double)gq[0] * wv.x + (double)gq[1] * wv.y + (double)gq[2] * wv.z + (double)gq[3] * wv.w;
+        }
+        part[tid] = a;
+        __syncthreads();
+        if (tid < DH)
+            U.dw1_out[(size_t)x * DH + tid] = (float)(sc * ((part[tid] + part[tid + 128]) + (double)U.k * (double)gb[x] * (double)U.b3[tid]));
+    } else if (x < 128) {             // rows 2 (x - 64), + 1 of dW3 = s W1^T G (the terms in order of i, 8 loads of each factor in flight)
+        const int m = __builtin_amdgcn_readfirstlane(2 * (x - 64) + (tid >> 7)), j = tid & 127;
+        double a = 0.0;
+        for (int i0 = 0; i0 < DD; i0 += 8) {
+            float wv[8], gv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { wv[u] = U.w1[(size_t)(i0 + u) * DH + m]; gv[u] = G[(size_t)(i0 + u) * DH + j]; }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) a += (double)wv[u] * (double)gv[u];
+        }
+        U.egrads[(size_t)m * EH + j] = (float)(sc * a);
+    } else if (tid < EH) {            // db3 = s k W1^T g_b (the same way)
+        double a = 0.0;
+        for (int i0 = 0; i0 < DD; i0 += 8) {
+            float wv[8], gv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { wv[u] = U.w1[(size_t)(i0 + u) * DH + tid]; gv[u] = gb[i0 + u]; }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) a += (double)wv[u] * (double)gv[u];
+        }
+        U.egrads[2 * EH * EH + 8 * EH + tid] = (float)(sc * (double)U.k * a);
+    }
+}
+static_assert(2 * EH * EH + 8 * EH >= (DW2_L1_OFF0 + DW2_L1_SPLIT) * 4 && 2 * EH * EH + 9 * EH <= DW2_L1_OFF1 * 4 && EH * EH <= DW2_L1_OFF0 * 4,
+              "the unfold's dW3 / db3 fields lie outside the encoder layer-1 set's targets");
 
 // workgroup `bid` of gx * nsets: set bid / gx, column block bid % gx
 __device__ __forceinline__ void reduce_block(const ReduceAll& A, int bid) {
@@ -48,6 +117,12 @@ __device__ __forceinline__ void reduce_block(const ReduceAll& A, int bid) {
     const ReduceSet S = A.set[y];
     if (x * 16 < S.lanes) sum_slots_16x16_at(x, S.parts, S.grads, S.slots, S.lanes, S.split, S.off0, S.off1, A.accumulate != 0);
 }
+// workgroup `bid` of a slot-sum launch of A.unf_blocks + gx * nsets: the unfold's workgroups lead (their f64 chains are the longest)
+__device__ __forceinline__ void reduce_launch_block(const ReduceAll& A, int bid) {
+    if (bid < A.unf_blocks) unfold_block(A, bid);
+    else reduce_block(A, bid - A.unf_blocks);
+}
+__host__ __device__ inline int reduce_launch_blocks(const ReduceAll& A) { return A.unf_blocks + A.gx * A.nsets; }
 
 // ---- the weight pack of the network (every operand image in one launch, network.hip) and its deferred form: a
 // piml_pinnsf_pack called with PIML_DEFER_PACK leaves its description here, and the next relfeat FORWARD launch on the same
@@ -166,5 +241,6 @@ int launch_slot_sums(const ReduceAll& R, hipStream_t s);          // the stand-a
 int pending_slot_sums_leave(const ReduceAll& R, hipStream_t s);
 bool pending_slot_sums_take(hipStream_t s, ReduceAll* out);
 int pending_slot_sums_flush();
+bool pending_slot_sums_write(const float* grads);                  // deferred sums waiting that write into `grads`
 
 }  // namespace piml

@@ -525,14 +525,15 @@ __global__ __launch_bounds__(256) void relfeat_bwd_kernel(
 }
 
 // The same rows behind the DEFERRED slot sums of the network's backward pass (reduce.hpp): workgroups [0, nred) sum weight-
-// gradient slots (bandwidth: they go first), the rest are the relfeat backward's -- two independent small kernels in one launch.
+// gradient slots (bandwidth: they go first; the unfold's workgroups in front of them when R.unf_blocks > 0), the rest are the
+// relfeat backward's -- independent small kernels in one launch.
 __global__ __launch_bounds__(256) void relfeat_bwd_reduce_kernel(
         const ReduceAll R, int nred, const float* __restrict__ g_ped, const float* __restrict__ g_obs,
         const float2* __restrict__ g_destf, const int* __restrict__ ped_idx, const int* __restrict__ obs_idx,
         const float* __restrict__ p, int ld, const float2* __restrict__ dest, int C, int N, int f0, int fcnt, int kpe, int koe,
         float* g_state, float2* g_dest, float* __restrict__ g_speed) {
     if ((int)blockIdx.x < nred) {
-        reduce_block(R, (int)blockIdx.x);
+        reduce_launch_block(R, (int)blockIdx.x);
         return;
     }
     relfeat_bwd_rows((int)blockIdx.x - nred, g_ped, g_obs, g_destf, ped_idx, obs_idx, p, ld, dest, C, N, f0, fcnt, kpe, koe, g_state,
@@ -540,7 +541,8 @@ __global__ __launch_bounds__(256) void relfeat_bwd_reduce_kernel(
 }
 
 // the relfeat backward over d/d(self_features) rows (gld = 7), carrying the slot sums a piml_pinnsf_bwd(PIML_DEFER_SLOT_SUMS) left on
-// this stream as its leading workgroups (and the unfold of PIML_POOL_TRAIN behind them)
+// this stream as its leading workgroups (and the unfold of PIML_POOL_TRAIN: in front of them, or behind as a launch of its own --
+// reduce.hpp: unfold_begin)
 static int relfeat_bwd_self_launch(const float* g_ped_feat, const float* g_obs_feat, const float* g_self, const int* ped_idx,
                                    const int* obs_idx, const float* position, int state_ld, const float* destination, int C, int N,
                                    int focal_begin, int focal_count, int kp_eff, int ko_eff, float* g_state, float* g_destination,
@@ -548,13 +550,16 @@ static int relfeat_bwd_self_launch(const float* g_ped_feat, const float* g_obs_f
     const long rows = (long)C * focal_count;
     ReduceAll R;
     if (pending_slot_sums_take(as_stream(stream), &R)) {
-        const int nred = R.gx * R.nsets;
+        UnfoldTail t;
+        const ReduceAll Rl = unfold_begin(R, as_stream(stream), &t);
+        const int nred = reduce_launch_blocks(Rl);
         hipLaunchKernelGGL(relfeat_bwd_reduce_kernel, dim3((unsigned)(nred + (rows + 3) / 4)), dim3(256), 0, as_stream(stream),
-                           R, nred, g_ped_feat, g_obs_feat, (const float2*)g_self, ped_idx, obs_idx, position, state_ld,
+                           Rl, nred, g_ped_feat, g_obs_feat, (const float2*)g_self, ped_idx, obs_idx, position, state_ld,
                            (const float2*)destination, C, N, focal_begin, focal_count, kp_eff, ko_eff, g_state,
                            (float2*)g_destination, g_speed);
         trace_mark("relfeat_bwd", as_stream(stream));
-        if (R.nunf > 0) return launch_unfold(R, as_stream(stream));
+        if (int e = hipGetLastError()) return e;
+        return unfold_end(t);
     } else {
         hipLaunchKernelGGL(relfeat_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, as_stream(stream), g_ped_feat,
                            g_obs_feat, (const float2*)g_self, ped_idx, obs_idx, position, state_ld, (const float2*)destination, C, N,

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/piml_hip.h"
+#include "pack.hpp"
 
 namespace piml {
 
@@ -24,7 +25,9 @@ int enc_stage_fwd_pool(const piml_encoder_branch* br, int nbr, hipStream_t s, fl
 // enc_pool_train_ok: the configuration they serve
 bool enc_pool_train_ok(const piml_encoder_branch* br, int nbr);
 int enc_stage_fwd_sum(const piml_encoder_branch* br, int nbr, hipStream_t s, float* zero = nullptr, long long zero_n = 0);
-int enc_stage_bwd_sum(const piml_encoder_branch* br, int nbr, hipStream_t s);        // slots: one DW2_PART1 slot per workgroup
+// slots: one DW2_PART1 slot per workgroup.  dec (optional): decoder slot sets the launch may sum on the way (the two-crew form
+// only); *dec_summed (optional) says whether it did
+int enc_stage_bwd_sum(const piml_encoder_branch* br, int nbr, hipStream_t s, const DecSlotSums* dec = nullptr, bool* dec_summed = nullptr);
 int enc_stage_bwd_dx(const piml_encoder_branch* br, int nbr, hipStream_t s);
 int enc_stage_bwd_dw(const piml_encoder_branch* br, int nbr, hipStream_t s);          // dW partials (after bwd_dx)
 int enc_stage_reduce(const piml_encoder_branch* br, int nbr, hipStream_t s, bool accumulate = false, bool defer = false);      // defer: PIML_DEFER_SLOT_SUMS
