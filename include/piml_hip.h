@@ -459,6 +459,33 @@ int piml_mmd_frames(const float* x, const float* y, const unsigned char* mask_x,
                     int m, double kernel_mul, int kernel_num, double fix_sigma, float* out, void* stream);
 
 /*
+ * Crowd-dynamics statistics without agent pairing (crowdstats.hip), S members x T frames in one call.
+ * P, V (S, T, N, 2) positions / velocities, M (S, T, N) presence, float32.  Agent i is present in slice (s, t) when
+ * M == 1 and both coordinates of P are finite; it has a speed when both components of V are finite too.  n_active (S)
+ * int32 or NULL: member s's slots at or past n_active[s] are not swept (they never held an agent).  Frames [t0, t1)
+ * (T' = t1 - t0).  A present agent is focal when has_box == 0 or x0 <= x < x1 and y0 <= y < y1.  For every focal agent:
+ *   rho = sum_j exp(-|p_j - p_i|^2 / R^2) / (pi R^2) over the slice's present j (j = i included), no cut-off;
+ *   u = sqrt(vx^2 + vy^2); bin = min(floor(rho / rho_bin), rho_bins - 1); cell (floor((x - x0) / cell),
+ *   floor((y - y0) / cell)), dropped outside [0, gx) x [0, gy); all of these in float32, the divisions true divisions.
+ * Outputs: n, n_speed (S, T') int64 focal agents / those with a speed; sum_speed, sum_density (S, T') float64;
+ * fd_count (S, rho_bins) int64, fd_sum, fd_sum2 (S, rho_bins) float64 = count, sum u, sum u^2 over the focal agents with a
+ * speed of every frame; map (S, gy, gx) int64 focal agent-frames per cell (has_box only; zeroed by the call);
+ * density (S, T', N) float32 or NULL: rho at focal agents, NaN elsewhere.  workspace: at least
+ * piml_crowd_stats_workspace_bytes(S, T', rho_bins) bytes (-1 for negative arguments).  One memset (map) and two launches,
+ * no host synchronisation (capturable).  Deterministic: no float atomics (the map counts are 64-bit integer atomics);
+ * member s's results are bitwise those of an S = 1 call on member s alone.
+ * hipErrorInvalidValue: S, T or N <= 0, frames outside [0, T] or empty, R <= 0 or not finite, rho_bin <= 0, rho_bins
+ * outside 1..256, with a box: a non-finite or empty box, cell <= 0, gx or gy < 1 or a NULL map; a NULL input, output or
+ * workspace, or a workspace too small.
+ */
+long long piml_crowd_stats_workspace_bytes(int S, int frames, int rho_bins);
+int piml_crowd_stats(const float* P, const float* V, const float* M, const int* n_active, int S, int T, int N, int t0, int t1,
+                     float radius, int has_box, float x0, float x1, float y0, float y1, float cell, int gx, int gy,
+                     float rho_bin, int rho_bins, long long* n, long long* n_speed, double* sum_speed, double* sum_density,
+                     long long* fd_count, double* fd_sum, double* fd_sum2, long long* map, float* density, void* workspace,
+                     long long workspace_bytes, void* stream);
+
+/*
  * utils.calc_acceleration (src/utils/utils.py:31-100): version 0/1/2 = 'v0'/'v1'/'v2' with the
  * caller-supplied constants (A, B, C, D, theta [rad]); rows of >= 2 floats -> acc (rows, 2).
  */

@@ -1,0 +1,383 @@
+"""Crowd-dynamics statistics that need no agent pairing: the speed-density relation (fundamental diagram)
+on a Gaussian local density per agent, time-averaged density maps and per-frame occupancy / speed / density series, for
+simulated scenes, ensembles and recorded clips.  The pair sums run in one HIP call for all members
+(ops_metrics.crowd_stats_frames, piml_crowd_stats).
+
+    python -m piml_amd.crowdstats --data sim_0.npy [sim_1.npy ...] [--ref recorded.npy] [--box x0,x1,y0,y1 | --box auto]
+                                  [--radius 0.7] [--cell 0.5] [--frames a:b] [--out stats.json]
+
+Definitions, for every focal agent i of slice (member s, frame t): present = mask 1 and a finite position; focal = present
+and inside the box [x0, x1) x [y0, y1) (every present agent without a box); rho_i = sum_j exp(-|p_j - p_i|^2 / R^2) /
+(pi R^2) over the slice's present j, j = i included; u_i = |v_i| where the velocity is finite; bin = min(floor(rho_i /
+rho_bin), rho_bins - 1); map cell (floor((x - x0) / h), floor((y - y0) / h))."""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+JSON_VERSION = 1
+ARRAYS = ('n', 'n_speed', 'sum_speed', 'sum_density', 'fd_count', 'fd_sum', 'fd_sum2', 'map', 'slices')
+
+
+def _f32(x):
+    return float(np.float32(x))
+
+
+def grid_shape(box, cell):
+    """(gx, gy) = (ceil((x1 - x0) / h), ceil((y1 - y0) / h)) of the float32 box and cell, in float64 on the host."""
+    x0, x1, y0, y1 = (_f32(v) for v in box)
+    h = _f32(cell)
+    return int(math.ceil((x1 - x0) / h)), int(math.ceil((y1 - y0) / h))
+
+
+def check_options(radius=0.7, box=None, cell=0.5, rho_bin=0.25, rho_bins=24, frames=None, T=None):
+    """ValueError on a bad option; returns (box as 4 floats or None, (gx, gy) or None, frames (a, b) or None)."""
+    from .ops_metrics import CROWD_MAX_BINS
+    if not (math.isfinite(float(radius)) and float(radius) > 0):
+        raise ValueError(f'radius must be a positive number, got {radius}')
+    if not (math.isfinite(float(rho_bin)) and float(rho_bin) > 0):
+        raise ValueError(f'rho_bin must be a positive number, got {rho_bin}')
+    if isinstance(rho_bins, bool) or int(rho_bins) != rho_bins or not 1 <= int(rho_bins) <= CROWD_MAX_BINS:
+        raise ValueError(f'rho_bins must be an integer in 1..{CROWD_MAX_BINS}, got {rho_bins}')
+    grid = None
+    if box is not None:
+        box = tuple(float(v) for v in box)
+        if len(box) != 4 or not all(math.isfinite(v) for v in box):
+            raise ValueError(f'box must be four finite numbers (x0, x1, y0, y1), got {box}')
+        if not (_f32(box[0]) < _f32(box[1]) and _f32(box[2]) < _f32(box[3])):
+            raise ValueError(f'box {box} is empty (need x0 < x1 and y0 < y1)')
+        if not (math.isfinite(float(cell)) and float(cell) > 0):
+            raise ValueError(f'cell must be a positive number, got {cell}')
+        grid = grid_shape(box, cell)
+    if frames is not None:
+        a, b = (int(v) for v in frames)
+        if a < 0 or b <= a or (T is not None and b > T):
+            raise ValueError(f'frames must satisfy 0 <= a < b <= {T}, got {tuple(frames)}')
+        frames = (a, b)
+    return box, grid, frames
+
+
+def _promote(P, V, M):
+    """(T, N, .) -> (1, T, N, .); torch or numpy in, float32 contiguous on a GPU out."""
+    dev = next((x.device for x in (P, V, M) if isinstance(x, torch.Tensor) and x.is_cuda), torch.device('cuda'))
+    P, V, M = (torch.as_tensor(x) for x in (P, V, M))
+    if P.dim() == 3:
+        P, V, M = P[None], V[None], M[None]
+    if P.dim() != 4 or P.shape[-1] != 2 or tuple(V.shape) != tuple(P.shape) or tuple(M.shape) != tuple(P.shape[:3]):
+        raise ValueError(f'expected P, V (S, T, N, 2) or (T, N, 2) and M (S, T, N) or (T, N), got {tuple(P.shape)}, '
+                         f'{tuple(V.shape)}, {tuple(M.shape)}')
+    if min(P.shape[:3]) < 1:
+        raise ValueError(f'empty input {tuple(P.shape)}')
+    return tuple(x.to(device=dev, dtype=torch.float32).contiguous() for x in (P, V, M))
+
+
+def _nan_div(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(b > 0, a / np.where(b > 0, b, 1), np.nan)
+
+
+class CrowdStats:
+    """The statistics of S members over T' frames.  Raw arrays (numpy): n, n_speed (S, T') int64 focal agents / those with
+    a speed; sum_speed, sum_density (S, T') float64; fd_count (S, B) int64, fd_sum, fd_sum2 (S, B) float64 (count, sum u,
+    sum u^2 per density bin); map (S, gy, gx) int64 focal agent-frames per cell (None without a box); density (S, T', N)
+    float32 per-agent density (NaN where not focal; None unless asked for); slices (S) the number of (member, frame)
+    slices each row holds (T' per member, more once pooled).  options: radius, box, cell, rho_bin, rho_bins, frames."""
+
+    def __init__(self, arrays, options, density=None):
+        for k in ARRAYS:
+            v = arrays.get(k)
+            setattr(self, k, None if v is None else np.asarray(v, np.float64 if k in ('sum_speed', 'sum_density', 'fd_sum',
+                                                                                    'fd_sum2') else np.int64))
+        self.density = density
+        self.options = dict(options)
+
+    @property
+    def members(self):
+        return self.n.shape[0]
+
+    @property
+    def bin_edges(self):
+        """lower edges of the density bins (m^-2); the last bin is open-ended"""
+        return np.arange(self.options['rho_bins'], dtype=np.float64) * np.float32(self.options['rho_bin'])
+
+    @property
+    def mean_speed(self):
+        """(S, T') mean speed of the focal agents with a speed (NaN in a frame without any)"""
+        return _nan_div(self.sum_speed, self.n_speed)
+
+    @property
+    def mean_density(self):
+        """(S, T') mean local density of the focal agents (NaN in a frame without any)"""
+        return _nan_div(self.sum_density, self.n)
+
+    @property
+    def fd_mean(self):
+        """(S, B) mean speed per density bin (NaN in an empty bin)"""
+        return _nan_div(self.fd_sum, self.fd_count)
+
+    @property
+    def fd_std(self):
+        """(S, B) population standard deviation of the speed per density bin (NaN in an empty bin)"""
+        mean = self.fd_mean
+        return np.sqrt(np.maximum(_nan_div(self.fd_sum2, self.fd_count) - mean * mean, 0.0))
+
+    @property
+    def map_density(self):
+        """(S, gy, gx) time-averaged agents per m^2: map / (slices * cell^2); None without a box"""
+        if self.map is None:
+            return None
+        h = float(np.float32(self.options['cell']))
+        return self.map / (self.slices[:, None, None].astype(np.float64) * h * h)
+
+    def member(self, m):
+        """Member m as a one-member CrowdStats (views)."""
+        pick = lambda x: None if x is None else x[m:m + 1]
+        return CrowdStats({k: pick(getattr(self, k)) for k in ARRAYS}, self.options, density=pick(self.density))
+
+    def pooled(self):
+        """The sum over members, added in member order: a one-member CrowdStats (no per-agent density)."""
+        def total(x):
+            if x is None:
+                return None
+            acc = x[0].copy()
+            for m in range(1, x.shape[0]):
+                acc += x[m]
+            return acc[None]
+        return CrowdStats({k: total(getattr(self, k)) for k in ARRAYS}, self.options)
+
+    def to_json(self, path=None):
+        """A JSON-ready dict of the options, the raw arrays and the derived pooled summary; written to path if given."""
+        pool = self.pooled()
+        d = {'version': JSON_VERSION, 'options': {**self.options,
+                                                 'box': None if self.options.get('box') is None else list(self.options['box']),
+                                                 'frames': list(self.options['frames'])},
+             'arrays': {k: None if getattr(self, k) is None else getattr(self, k).tolist() for k in ARRAYS},
+             'pooled': {'bin_edges': self.bin_edges.tolist(), 'fd_count': pool.fd_count[0].tolist(),
+                        'fd_mean': _json_floats(pool.fd_mean[0]), 'fd_std': _json_floats(pool.fd_std[0]),
+                        'mean_speed': _json_float(_nan_div(pool.sum_speed.sum(), pool.n_speed.sum())),
+                        'mean_density': _json_float(_nan_div(pool.sum_density.sum(), pool.n.sum()))}}
+        if path is not None:
+            with open(path, 'w') as fh:
+                json.dump(d, fh)
+        return d
+
+    @classmethod
+    def from_json(cls, src):
+        """A CrowdStats from what to_json wrote (a path or the dict)."""
+        if not isinstance(src, dict):
+            with open(src) as fh:
+                src = json.load(fh)
+        if src.get('version') != JSON_VERSION:
+            raise ValueError(f'crowd stats JSON version {src.get("version")!r} (expected {JSON_VERSION})')
+        opts = dict(src['options'])
+        opts['box'] = None if opts.get('box') is None else tuple(opts['box'])
+        opts['frames'] = tuple(opts['frames'])
+        return cls(src['arrays'], opts)
+
+
+def _json_float(x):
+    x = float(x)
+    return x if math.isfinite(x) else None
+
+
+def _json_floats(a):
+    return [_json_float(x) for x in np.asarray(a).ravel()]
+
+
+def crowd_stats(P, V, M, radius=0.7, box=None, cell=0.5, rho_bin=0.25, rho_bins=24, frames=None, return_density=False,
+                n_active=None):
+    """The statistics of positions P (S, T, N, 2), velocities V (S, T, N, 2) and presence M (S, T, N) -- (T, N, .) is one
+    member -- in one device call for all members: CrowdStats.  box (x0, x1, y0, y1) restricts the focal agents and enables
+    the map with cells of `cell` m; frames (a, b) a frame range; n_active (S) ints: member s's slots at or past
+    n_active[s] never held an agent and are not swept."""
+    from . import ops_metrics
+    P, V, M = _promote(P, V, M)
+    S, T, N = P.shape[:3]
+    box, grid, frames = check_options(radius, box, cell, rho_bin, rho_bins, frames, T)
+    frames = frames or (0, T)
+    if n_active is not None:
+        n_active = torch.as_tensor(n_active).reshape(-1)
+        if n_active.numel() != S:
+            raise ValueError(f'n_active: {n_active.numel()} bounds for {S} members')
+        n_active = n_active.clamp(0, N).to(device=P.device, dtype=torch.int32)
+    out = ops_metrics.crowd_stats_frames(P, V, M, radius, box, grid, cell, rho_bin, int(rho_bins), frames, return_density,
+                                         n_active)
+    host = {k: (None if v is None else v.cpu().numpy()) for k, v in out.items()}
+    host['slices'] = np.full(S, frames[1] - frames[0], np.int64)
+    opts = dict(radius=float(radius), box=box, cell=float(cell), rho_bin=float(rho_bin), rho_bins=int(rho_bins),
+                frames=frames)
+    return CrowdStats(host, opts, density=host.pop('density'))
+
+
+def crowd_stats_of_raw(raw_data, **kw):
+    """crowd_stats of a loaded clip (piml_amd.data.data.RawData: position, velocity, mask_p), one member."""
+    return crowd_stats(raw_data.position, raw_data.velocity, raw_data.mask_p, **kw)
+
+
+def merge(stats):
+    """Several CrowdStats with the same options (frames aside) as one member: each pooled, their frames laid end to end
+    in the series, diagrams and maps added in list order."""
+    if not stats:
+        raise ValueError('merge: no statistics')
+    pools = [s.pooled() for s in stats]
+    keys = ('radius', 'box', 'cell', 'rho_bin', 'rho_bins')
+    for p in pools[1:]:
+        if any(p.options[k] != pools[0].options[k] for k in keys):
+            raise ValueError('merge: the statistics were taken with different options')
+    arrays = {}
+    for k in ARRAYS:
+        if k in ('n', 'n_speed', 'sum_speed', 'sum_density'):
+            arrays[k] = np.concatenate([getattr(p, k) for p in pools], 1)
+        elif getattr(pools[0], k) is None:
+            arrays[k] = None
+        else:
+            acc = getattr(pools[0], k).copy()
+            for p in pools[1:]:
+                acc += getattr(p, k)
+            arrays[k] = acc
+    opts = dict(pools[0].options)
+    opts['frames'] = (0, int(arrays['n'].shape[1]))
+    return CrowdStats(arrays, opts)
+
+
+def compare_crowd_stats(a, b, min_count=50):
+    """Distances between two CrowdStats, each pooled over its members first:
+      fd_distance = sqrt(sum_b w_b (mean_a,b - mean_b,b)^2 / sum_b w_b), w_b = min(count_a,b, count_b,b), over the bins
+                    where both counts are >= min_count (NaN when there is none; fd_bins says how many were used);
+      map_distance = sum |m_a - m_b| of the two maps normalised to sum 1 (0 .. 2; None when either side has no map or
+                    the boxes / cells differ; NaN when a map is empty);
+      mean_speed_diff, mean_density_diff = pooled mean of a - pooled mean of b (means over all focal agent-frames)."""
+    if a.options['rho_bins'] != b.options['rho_bins'] or a.options['rho_bin'] != b.options['rho_bin']:
+        raise ValueError('compare_crowd_stats: the density bins differ')
+    pa, pb = a.pooled(), b.pooled()
+    ca, cb = pa.fd_count[0], pb.fd_count[0]
+    use = (ca >= min_count) & (cb >= min_count)
+    w = np.minimum(ca, cb)[use].astype(np.float64)
+    d = (pa.fd_mean[0] - pb.fd_mean[0])[use]
+    fd = float(np.sqrt((w * d * d).sum() / w.sum())) if use.any() else float('nan')
+    mp = None
+    if pa.map is not None and pb.map is not None and pa.options['box'] == pb.options['box'] \
+            and pa.options['cell'] == pb.options['cell']:
+        ma, mb = pa.map[0].astype(np.float64), pb.map[0].astype(np.float64)
+        sa, sb = ma.sum(), mb.sum()
+        mp = float(np.abs(ma / sa - mb / sb).sum()) if sa > 0 and sb > 0 else float('nan')
+    mean = lambda p, s, c: float(_nan_div(getattr(p, s).sum(), getattr(p, c).sum()))
+    return {'fd_distance': fd, 'fd_bins': int(use.sum()), 'map_distance': mp,
+            'mean_speed_diff': mean(pa, 'sum_speed', 'n_speed') - mean(pb, 'sum_speed', 'n_speed'),
+            'mean_density_diff': mean(pa, 'sum_density', 'n') - mean(pb, 'sum_density', 'n')}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# command line
+
+def parse_box(text):
+    """'x0,x1,y0,y1' -> 4 floats; 'auto' -> 'auto'."""
+    if text == 'auto':
+        return 'auto'
+    vals = [float(v) for v in text.split(',')]
+    if len(vals) != 4:
+        raise ValueError(f'expected x0,x1,y0,y1, got {text!r}')
+    return tuple(vals)
+
+
+def parse_frames(text):
+    """'a:b' -> (a, b)"""
+    a, b = text.split(':')
+    return int(a), int(b)
+
+
+def auto_box(position, mask, cell):
+    """The bounding box of the present agents of (T, N, 2) positions, widened outward to whole cells: x0 = floor(min / h) h,
+    x1 = (floor(max / h) + 1) h (the extreme agents are focal), likewise in y."""
+    p = np.asarray(position, np.float64).reshape(-1, 2)
+    m = (np.asarray(mask).reshape(-1) == 1) & np.isfinite(p).all(1)
+    if not m.any():
+        raise ValueError('--box auto: no present agent')
+    lo, hi = p[m].min(0), p[m].max(0)
+    h = float(cell)
+    x0, y0 = math.floor(lo[0] / h) * h, math.floor(lo[1] / h) * h
+    x1, y1 = (math.floor(hi[0] / h) + 1) * h, (math.floor(hi[1] / h) + 1) * h
+    return (x0, x1, y0, y1)
+
+
+def get_args(argv=None):
+    p = argparse.ArgumentParser(description='crowd-dynamics statistics (fundamental diagram, density map, series) of clips')
+    p.add_argument('--data', nargs='+', required=True, help='v2.2 clips (simulated or recorded), pooled together')
+    p.add_argument('--ref', type=str, default=None, help='a clip to compare against')
+    p.add_argument('--box', type=str, default=None, help="x0,x1,y0,y1 or 'auto' (bounding box of --ref, else of the first --data)")
+    p.add_argument('--radius', type=float, default=0.7)
+    p.add_argument('--cell', type=float, default=0.5)
+    p.add_argument('--rho_bin', type=float, default=0.25)
+    p.add_argument('--rho_bins', type=int, default=24)
+    p.add_argument('--frames', type=str, default=None, help="'a:b' (frames a .. b-1 of every clip)")
+    p.add_argument('--min_count', type=int, default=50)
+    p.add_argument('--out', type=str, default=None, help='JSON of the pooled statistics (and the comparison)')
+    args = p.parse_args(argv)
+    try:
+        args.box = None if args.box is None else parse_box(args.box)
+        args.frames = None if args.frames is None else parse_frames(args.frames)
+        check_options(args.radius, None if args.box in (None, 'auto') else args.box, args.cell, args.rho_bin,
+                      args.rho_bins, args.frames)
+    except ValueError as ex:
+        p.error(str(ex))
+    return args
+
+
+def _load(path):
+    from .data.data import RawData
+    raw = RawData()
+    raw.load_trajectory_data(path)
+    return raw
+
+
+def print_diagram(stats, tag, file=sys.stdout):
+    pool = stats.pooled()
+    edges = stats.bin_edges
+    print(f'[crowdstats] {tag}: fundamental diagram (density bin [m^-2]: count, mean speed +- std [m/s])', file=file)
+    for k in range(len(edges)):
+        c = int(pool.fd_count[0, k])
+        if c:
+            hi = f'{edges[k + 1]:.2f}' if k + 1 < len(edges) else 'inf'
+            print(f'  [{edges[k]:.2f}, {hi}): {c:8d}  {pool.fd_mean[0, k]:.3f} +- {pool.fd_std[0, k]:.3f}', file=file)
+    ms = _nan_div(pool.sum_speed.sum(), pool.n_speed.sum())
+    md = _nan_div(pool.sum_density.sum(), pool.n.sum())
+    print(f'[crowdstats] {tag}: {int(pool.n.sum())} focal agent-frames, mean speed {float(ms):.4f} m/s, '
+          f'mean density {float(md):.4f} m^-2', file=file)
+
+
+def main(argv=None):
+    args = get_args(argv)
+    raws = [_load(p) for p in args.data]
+    ref = _load(args.ref) if args.ref else None
+    box = args.box
+    if box == 'auto':
+        src = ref if ref is not None else raws[0]
+        box = auto_box(src.position.numpy(), src.mask_p.numpy(), args.cell)
+        print(f'[crowdstats] --box auto: {",".join(f"{v:g}" for v in box)}')
+    kw = dict(radius=args.radius, box=box, cell=args.cell, rho_bin=args.rho_bin, rho_bins=args.rho_bins,
+              frames=args.frames)
+    data = merge([crowd_stats_of_raw(r, **kw) for r in raws])
+    print_diagram(data, 'data')
+    out = {'data': data.to_json()}
+    if ref is not None:
+        rs = crowd_stats_of_raw(ref, **kw)
+        print_diagram(rs, 'ref')
+        cmp = compare_crowd_stats(data, rs, args.min_count)
+        print('[crowdstats] data vs ref: ' + ', '.join(f'{k} {v:.4g}' if isinstance(v, float) else f'{k} {v}'
+                                                      for k, v in cmp.items()))
+        out['ref'] = rs.to_json()
+        out['compare'] = {k: (_json_float(v) if isinstance(v, float) else v) for k, v in cmp.items()}
+    if args.out:
+        with open(args.out, 'w') as fh:
+            json.dump(out, fh)
+        print(f'[crowdstats] wrote {os.path.abspath(args.out)}')
+    return out
+
+
+if __name__ == '__main__':
+    main(sys.argv[1:])

@@ -270,6 +270,11 @@ class ScenarioResult(types.SimpleNamespace):
         p, m, w, d, o = self._dense()
         return save_clip(path, p, m, w, d, o, {'time_unit': float(self.time_unit)})
 
+    def crowd_stats(self, **kw):
+        """piml_amd.crowdstats.crowd_stats of the run (simulated velocities; slots past num_agents not swept)."""
+        from .crowdstats import crowd_stats
+        return crowd_stats(self.position, self.velocity, self.mask_p, n_active=[self.num_agents], **kw)
+
 
 class ScenarioEnsemble(types.SimpleNamespace):
     """What `BaseSimulator.simulate_ensemble` returns: the ScenarioResult fields with a leading member axis -- position /
@@ -294,6 +299,13 @@ class ScenarioEnsemble(types.SimpleNamespace):
         if '{seed}' not in pattern:
             raise ValueError(f"save_data: the path pattern must contain '{{seed}}', got {pattern!r}")
         return [self.member(m).save_data(pattern.replace('{seed}', str(s))) for m, s in enumerate(self.seeds)]
+
+    def crowd_stats(self, **kw):
+        """piml_amd.crowdstats.crowd_stats of every member in one call (member m's slots past its num_agents not swept):
+        member m's statistics are bitwise those of member(m).crowd_stats(**kw)."""
+        from .crowdstats import crowd_stats
+        cap = self.position.shape[2]
+        return crowd_stats(self.position, self.velocity, self.mask_p, n_active=[min(int(n), cap) for n in self.spawned], **kw)
 
     def collision_counts(self, threshold):
         """Per-member totals of collision_count(member.position, threshold, reduction='sum'): a list of S floats, one

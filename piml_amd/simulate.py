@@ -6,6 +6,7 @@ reads.
     python -m piml_amd.simulate --checkpoint model.pt --frames 750 --out clip.npy [model flags of piml_amd.main]
     python -m piml_amd.simulate --seeds 0:32 --out 'gc_{seed}.npy'      (an ensemble: every seed in one launch per frame)
     python -m piml_amd.simulate --law mlapm --params params.json --out clip.npy     (MLAPM; params: `calibrate --out`)
+    python -m piml_amd.simulate --seeds 0:32 --stats stats.json      (crowd statistics of the run, no clips written)
 
 Model flags (--model, --hidden sizes, --topk_*, --num_history_velocity, ...) are those of `piml_amd.main`, with its
 defaults.  Without --checkpoint the network keeps its initial weights (a smoke run)."""
@@ -40,6 +41,9 @@ def get_args(argv=None):
                       help="an ensemble, one simulation per seed: 'a:b' (a .. b-1) or 'a,b,c'; --out must contain {seed}")
     p.add_argument('--capacity', type=int, default=None, help='agent slots (default: from the arrival rate)')
     p.add_argument('--out', type=str, default='clip.npy')
+    p.add_argument('--stats', type=str, default=None,
+                   help='write the crowd statistics (piml_amd.crowdstats, defaults, no box) of the run or ensemble as JSON '
+                        'to this path instead of writing clips')
     p.add_argument('--time_unit', type=float, default=0.08)
     p.add_argument('--uniform_desired_speed', action=argparse.BooleanOptionalAction, default=None,
                    help="uniform desired speed (default: the scene's own; GC and the crosswalk no, the others yes)")
@@ -49,7 +53,7 @@ def get_args(argv=None):
             own.seeds = parse_seeds(own.seeds)
         except ValueError as ex:
             p.error(f'--seeds: {ex}')
-        if '{seed}' not in own.out:
+        if '{seed}' not in own.out and own.stats is None:
             p.error("--seeds: --out must contain '{seed}' (one clip per seed)")
     if own.law == 'mlapm':
         if own.checkpoint:
@@ -137,14 +141,30 @@ def main(argv=None):
     if own.seeds is not None:
         return _ensemble(sim, scenario, own, args, run_kw)
     res = sim.simulate_scenario(scenario, own.frames, seed=own.seed, capacity=own.capacity, **run_kw)
-    res.save_data(own.out)
-    _report(own.scenario, own.frames, res, args.collision_threshold, own.out)
+    if own.stats is not None:
+        _stats(res, own.stats)
+    else:
+        res.save_data(own.out)
+    _report(own.scenario, own.frames, res, args.collision_threshold, own.out if own.stats is None else own.stats)
     return res
+
+
+def _stats(res, path):
+    """--stats: the CrowdStats JSON of a run or an ensemble (one call for every member)."""
+    from . import crowdstats
+    st = res.crowd_stats()
+    st.to_json(path)
+    crowdstats.print_diagram(st, 'simulate --stats')
+    return st
 
 
 def _ensemble(sim, scenario, own, args, run_kw):
     ens = sim.simulate_ensemble(scenario, own.frames, own.seeds, capacity=own.capacity, **run_kw)
-    paths = ens.save_data(own.out)
+    if own.stats is not None:
+        _stats(ens, own.stats)
+        paths = [own.stats] * len(ens)
+    else:
+        paths = ens.save_data(own.out)
     soft = ens.collision_counts(args.collision_threshold)
     hard = ens.collision_counts(args.collision_threshold / 2)
     rows = [_report(f'{own.scenario} (seed {s})', own.frames, ens.member(m), args.collision_threshold, paths[m], soft[m], hard[m])
