@@ -486,6 +486,38 @@ int piml_crowd_stats(const float* P, const float* V, const float* M, const int* 
                      long long workspace_bytes, void* stream);
 
 /*
+ * Time-to-collision and pair-distance statistics without agent pairing (pairstats.hip), S members in one
+ * call.  P, V (S, T, N, 2), M (S, T, N) float32; n_active (S) int32 or NULL as for piml_crowd_stats.  Agent i takes part
+ * in slice (s, t) when M == 1 and both coordinates of P and both components of V are finite (slots at or past
+ * n_active[s] are not swept); it is focal when it takes part and has_box == 0 or x0 <= x < x1 and y0 <= y < y1.  lags:
+ * a host array of K (0..8) positive, ascending frame counts, copied into the kernel arguments; lag index 0 is L = 0.
+ * Pair slice (s, t, k) for t0 <= t and t + L_k < t1 pairs every focal i of frame t with every participant j != i (as a
+ * slot) of frame t + L_k, ordered pairs.  Per pair in float32 (true divisions and square roots, no contraction):
+ * d = p_j - p_i, w = v_j - v_i, c = |d|^2 - R^2, b = d.w, a = |w|^2; distance sqrt(|d|^2); pairs with distance >= r_max
+ * are skipped entirely (r_max <= 0: no cut-off); overlap when c < 0; otherwise a collision course when b < 0 and
+ * disc = b^2 - a c >= 0, tau = c / (-b + sqrt(disc)).  Outputs, int64, zeroed by the call:
+ *   focal, pairs, overlap (S, K + 1): focal agent-frames, ordered pairs evaluated, overlapping pairs;
+ *   ttc (S, K + 1, tau_bins): collision-course pairs by floor(tau / tau_bin), where that is < tau_bins;
+ *   dist (S, K + 1, r_bins): pairs by floor(distance / r_bin), where that is < r_bins;
+ *   nn (S, r_bins + 1): lag 0, each focal agent's smallest distance bin, r_bins when none is below r_bins * r_bin;
+ *   min_ttc (S, tau_bins + 1): lag 0, each focal agent's smallest tau bin, tau_bins when none is below tau_bins * tau_bin.
+ * A lag that reaches past the frames has no slices and zero counts.  workspace: at least
+ * piml_pair_stats_workspace_bytes(S, K, tau_bins, r_bins) bytes (-1 for negative arguments).  One memset and two
+ * launches, no host synchronisation (capturable).  Deterministic: integer counts only, added with integer atomics;
+ * member s's results are bitwise those of an S = 1 call on member s alone.
+ * hipErrorInvalidValue: S, T or N <= 0, N > 65536 (the per-slice u32 counters), frames outside [0, T] or empty, K outside
+ * 0..8, lags NULL (K > 0), not positive or not ascending, R <= 0 or not finite, r_max NaN, tau_bin or r_bin <= 0 or not
+ * finite, tau_bins or r_bins outside 1..256, a non-finite or empty box, a NULL input, output or workspace, or a
+ * workspace too small.
+ */
+long long piml_pair_stats_workspace_bytes(int S, int K, int tau_bins, int r_bins);
+int piml_pair_stats(const float* P, const float* V, const float* M, const int* n_active, int S, int T, int N, int t0, int t1,
+                    const int* lags, int K, float radius, float r_max, int has_box, float x0, float x1, float y0, float y1,
+                    float tau_bin, int tau_bins, float r_bin, int r_bins, long long* focal, long long* pairs,
+                    long long* overlap, long long* ttc, long long* dist, long long* nn, long long* min_ttc, void* workspace,
+                    long long workspace_bytes, void* stream);
+
+/*
  * utils.calc_acceleration (src/utils/utils.py:31-100): version 0/1/2 = 'v0'/'v1'/'v2' with the
  * caller-supplied constants (A, B, C, D, theta [rad]); rows of >= 2 floats -> acc (rows, 2).
  */

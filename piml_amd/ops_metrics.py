@@ -117,3 +117,51 @@ def crowd_stats_frames(P, V, M, radius=0.7, box=None, grid=None, cell=0.5, rho_b
                                       ws.numel(), _stream()),
                    'piml_crowd_stats')
     return out
+
+
+PAIR_MAX_BINS = 256           # piml_pair_stats' limits on tau_bins / r_bins, the number of lags and the slots per frame
+PAIR_MAX_LAGS = 8
+PAIR_MAX_N = 65536
+
+
+def pair_stats_frames(P, V, M, radius=0.5, lags=(64, 128, 192), tau_bin=0.1, tau_bins=100, r_bin=0.05, r_bins=100,
+                      r_max=None, box=None, frames=None, n_active=None):
+    """The device half of piml_amd.pairstats.pair_stats (piml_pair_stats): P, V (S, T, N, 2) and M (S, T, N)
+    float32 GPU tensors, lags a sequence of K positive ascending ints, r_max a distance or None, box (x0, x1, y0, y1) or
+    None, frames (a, b) or None, n_active (S) int32 GPU tensor or None.  Returns a dict of int64 GPU tensors -- focal,
+    pairs, overlap (S, K+1), ttc (S, K+1, tau_bins), dist (S, K+1, r_bins), nn (S, r_bins+1), min_ttc (S, tau_bins+1) --
+    with no host synchronisation (capturable in a graph)."""
+    import ctypes
+    P, V, M = _gpu_f32('P', P), _gpu_f32('V', V), _gpu_f32('M', M)
+    if P.dim() != 4 or P.shape[-1] != 2 or V.shape != P.shape or M.shape != P.shape[:3]:
+        raise ValueError(f'expected P, V (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(V.shape)}, '
+                         f'{tuple(M.shape)}')
+    S, T, N = P.shape[:3]
+    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    lags = [int(x) for x in lags]
+    K, TB, RB = len(lags), int(tau_bins), int(r_bins)
+    dev = P.device
+    if n_active is not None:
+        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
+                or tuple(n_active.shape) != (S,):
+            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
+        n_active = n_active.contiguous()
+    x0, x1, y0, y1 = (0.0, 0.0, 0.0, 0.0) if box is None else (float(v) for v in box)
+    i64 = dict(device=dev, dtype=torch.int64)
+    K1, TBc, RBc = K + 1, max(TB, 0), max(RB, 0)
+    out = dict(focal=torch.empty(S, K1, **i64), pairs=torch.empty(S, K1, **i64), overlap=torch.empty(S, K1, **i64),
+               ttc=torch.empty(S, K1, TBc, **i64), dist=torch.empty(S, K1, RBc, **i64), nn=torch.empty(S, RBc + 1, **i64),
+               min_ttc=torch.empty(S, TBc + 1, **i64))
+    L = _lib.lib()
+    ws_bytes = L.piml_pair_stats_workspace_bytes(S, K, TBc, RBc)
+    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    lag_arr = (ctypes.c_int * max(K, 1))(*lags)
+    with torch.cuda.device(dev):
+        _lib.check(L.piml_pair_stats(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), S, T, N, a, b,
+                                     ctypes.addressof(lag_arr) if K else None, K, float(radius),
+                                     float(r_max) if r_max is not None else 0.0, int(box is not None), x0, x1, y0, y1,
+                                     float(tau_bin), TB, float(r_bin), RB, _ptr(out['focal']), _ptr(out['pairs']),
+                                     _ptr(out['overlap']), _ptr(out['ttc']), _ptr(out['dist']), _ptr(out['nn']),
+                                     _ptr(out['min_ttc']), _ptr(ws), ws.numel(), _stream()),
+                   'piml_pair_stats')
+    return out

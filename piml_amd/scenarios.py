@@ -275,6 +275,11 @@ class ScenarioResult(types.SimpleNamespace):
         from .crowdstats import crowd_stats
         return crowd_stats(self.position, self.velocity, self.mask_p, n_active=[self.num_agents], **kw)
 
+    def pair_stats(self, **kw):
+        """piml_amd.pairstats.pair_stats of the run (simulated velocities; slots past num_agents not swept)."""
+        from .pairstats import pair_stats
+        return pair_stats(self.position, self.velocity, self.mask_p, n_active=[self.num_agents], **kw)
+
 
 class ScenarioEnsemble(types.SimpleNamespace):
     """What `BaseSimulator.simulate_ensemble` returns: the ScenarioResult fields with a leading member axis -- position /
@@ -306,6 +311,13 @@ class ScenarioEnsemble(types.SimpleNamespace):
         from .crowdstats import crowd_stats
         cap = self.position.shape[2]
         return crowd_stats(self.position, self.velocity, self.mask_p, n_active=[min(int(n), cap) for n in self.spawned], **kw)
+
+    def pair_stats(self, **kw):
+        """piml_amd.pairstats.pair_stats of every member in one call (member m's slots past its num_agents not swept):
+        member m's statistics are bitwise those of member(m).pair_stats(**kw)."""
+        from .pairstats import pair_stats
+        cap = self.position.shape[2]
+        return pair_stats(self.position, self.velocity, self.mask_p, n_active=[min(int(n), cap) for n in self.spawned], **kw)
 
     def collision_counts(self, threshold):
         """Per-member totals of collision_count(member.position, threshold, reduction='sum'): a list of S floats, one

@@ -7,6 +7,7 @@ reads.
     python -m piml_amd.simulate --seeds 0:32 --out 'gc_{seed}.npy'      (an ensemble: every seed in one launch per frame)
     python -m piml_amd.simulate --law mlapm --params params.json --out clip.npy     (MLAPM; params: `calibrate --out`)
     python -m piml_amd.simulate --seeds 0:32 --stats stats.json      (crowd statistics of the run, no clips written)
+    python -m piml_amd.simulate --seeds 0:32 --pair-stats pairs.json      (time-to-collision statistics, no clips written)
 
 Model flags (--model, --hidden sizes, --topk_*, --num_history_velocity, ...) are those of `piml_amd.main`, with its
 defaults.  Without --checkpoint the network keeps its initial weights (a smoke run)."""
@@ -44,6 +45,9 @@ def get_args(argv=None):
     p.add_argument('--stats', type=str, default=None,
                    help='write the crowd statistics (piml_amd.crowdstats, defaults, no box) of the run or ensemble as JSON '
                         'to this path instead of writing clips')
+    p.add_argument('--pair-stats', dest='pair_stats', type=str, default=None,
+                   help='write the time-to-collision and pair-distance statistics (piml_amd.pairstats, defaults, no box) '
+                        'of the run or ensemble as JSON to this path instead of writing clips')
     p.add_argument('--time_unit', type=float, default=0.08)
     p.add_argument('--uniform_desired_speed', action=argparse.BooleanOptionalAction, default=None,
                    help="uniform desired speed (default: the scene's own; GC and the crosswalk no, the others yes)")
@@ -53,7 +57,7 @@ def get_args(argv=None):
             own.seeds = parse_seeds(own.seeds)
         except ValueError as ex:
             p.error(f'--seeds: {ex}')
-        if '{seed}' not in own.out and own.stats is None:
+        if '{seed}' not in own.out and own.stats is None and own.pair_stats is None:
             p.error("--seeds: --out must contain '{seed}' (one clip per seed)")
     if own.law == 'mlapm':
         if own.checkpoint:
@@ -141,28 +145,37 @@ def main(argv=None):
     if own.seeds is not None:
         return _ensemble(sim, scenario, own, args, run_kw)
     res = sim.simulate_scenario(scenario, own.frames, seed=own.seed, capacity=own.capacity, **run_kw)
-    if own.stats is not None:
-        _stats(res, own.stats)
+    if own.stats is not None or own.pair_stats is not None:
+        _stats(res, own)
     else:
         res.save_data(own.out)
-    _report(own.scenario, own.frames, res, args.collision_threshold, own.out if own.stats is None else own.stats)
+    _report(own.scenario, own.frames, res, args.collision_threshold, _stats_path(own) or own.out)
     return res
 
 
-def _stats(res, path):
-    """--stats: the CrowdStats JSON of a run or an ensemble (one call for every member)."""
-    from . import crowdstats
-    st = res.crowd_stats()
-    st.to_json(path)
-    crowdstats.print_diagram(st, 'simulate --stats')
-    return st
+def _stats_path(own):
+    return ', '.join(p for p in (own.stats, own.pair_stats) if p is not None)
+
+
+def _stats(res, own):
+    """--stats / --pair-stats: the CrowdStats / PairStats JSON of a run or an ensemble (one call for every member)."""
+    if own.stats is not None:
+        from . import crowdstats
+        st = res.crowd_stats()
+        st.to_json(own.stats)
+        crowdstats.print_diagram(st, 'simulate --stats')
+    if own.pair_stats is not None:
+        from . import pairstats
+        ps = res.pair_stats()
+        ps.to_json(own.pair_stats)
+        pairstats.print_pair_stats(ps, 'simulate --pair-stats')
 
 
 def _ensemble(sim, scenario, own, args, run_kw):
     ens = sim.simulate_ensemble(scenario, own.frames, own.seeds, capacity=own.capacity, **run_kw)
-    if own.stats is not None:
-        _stats(ens, own.stats)
-        paths = [own.stats] * len(ens)
+    if own.stats is not None or own.pair_stats is not None:
+        _stats(ens, own)
+        paths = [_stats_path(own)] * len(ens)
     else:
         paths = ens.save_data(own.out)
     soft = ens.collision_counts(args.collision_threshold)
