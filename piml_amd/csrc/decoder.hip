@@ -271,6 +271,9 @@ __device__ __forceinline__ void dec_fwd_body(const DecArgs& A, long long tile, i
         float x[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) x[r] = fmaxf(part1[bi][kh][0][r][lane] + part1[bi][kh][1][r][lane], 0.f);
+        // fmaxf answers 0 to a NaN, torch.relu answers NaN: an agent whose input carries a NaN has it in every feature of this
+        // layer, so one feature carries it on (fma(pre, 0, relu) = relu + (+-0 | NaN): the bits of relu for a finite pre)
+        x[0] = __builtin_fmaf(part1[bi][kh][0][0][lane] + part1[bi][kh][1][0][lane], 0.f, x[0]);
         if (ob == 0 && J.h1 && valid) {
             float* o = J.h1 + agent * DD;
 #pragma unroll

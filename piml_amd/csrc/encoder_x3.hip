@@ -566,8 +566,13 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_fwd_pool_x3_kernel(EncArgs A)
             }
 #pragma unroll
             for (int s = 0; s < 4; ++s) a[blk] = mfma32(W1f[(blk * 4 + s) * 64 + lane_t], xb[s], a[blk]);
+            // relu1 (v_med3) answers 0 to a NaN, torch.relu answers NaN: a row with a NaN / Inf input has it in every
+            // pre-activation, so ONE feature per row carries it on -- fma(pre, 0, relu) is relu + (+-0 | NaN), the bits of relu
+            // for every finite pre (1 + 16 instructions per tile; the decoder's first ReLU does the same, dec_fwd_body)
+            const float pre0 = a[blk][0];
 #pragma unroll
             for (int r = 0; r < 16; ++r) a[blk][r] = relu1(a[blk][r]);
+            if (blk == 0) a[0][0] = __builtin_fmaf(pre0, 0.f, a[0][0]);
         }
         split_tile(a, P);
         load_x(xb, J.x, tile + stride, ntiles, R, IN, lane);       // the next tile's input row
@@ -584,7 +589,10 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_fwd_pool_x3_kernel(EncArgs A)
                 kblock_x3_t(acc, sm, W2hm[(fb * 2) * 64], W2hm[(fb * 2 + 1) * 64], W2lo[fb * 64], P.hi[kb], P.mid[kb], P.lo[kb]);
             }
 #pragma unroll
-            for (int r = 0; r < 16; ++r) a[blk][r] = relu1(acc[r] + sm[r]);
+            for (int r = 0; r < 16; ++r) {
+                const float pre = acc[r] + sm[r];
+                a[blk][r] = blk == 0 ? __builtin_fmaf(pre, 0.f, relu1(pre)) : relu1(pre);     // (a NaN row: NaN in the first feature block)
+            }
         }
         // ---- the agents' sums (wave-uniform choice of the register -> agent map) ----
         pool_rows_k(a, k, tile, agents, lane_t, J.msgs, J.h2);
