@@ -3,8 +3,8 @@ repository snapshot).  `python -m piml_amd.build` or `__graft_entry__.build()`.
 
 Every csrc/*.hip is compiled to an object of its own under piml_amd/_obj/ (git-ignored; re-made only when the source, a
 header or the flags changed) and the objects are linked into the library: an edit of one kernel file costs seconds, not
-a minute.  `variant(name, {file: [-D flags]})` links an EXPERIMENTAL library beside the shipped one from the same
-objects with some files re-compiled under extra flags (tools/: A/B timings, "results wrong on purpose" builds); it is
+a minute.  `variant(name, {file: [-D flags]})` links a DIAGNOSTIC library beside the shipped one from the same
+objects with some files re-compiled under extra flags (tools/: the in-kernel stamp and counter builds); it is
 selected at run time with PIML_LIB=<path> (piml_amd/_lib.py) and never overwrites libpiml_hip.so."""
 import glob
 import hashlib
@@ -94,7 +94,7 @@ def build(force=False, verbose=False, extra=()):
 
 
 def variant(name, defines, verbose=False):
-    """libpiml_hip_<name>.so: the shipped objects, with the files named in `defines` ({'encoder_bwd3.hip': ['-DX=1']})
+    """libpiml_hip_<name>.so: the shipped objects, with the files named in `defines` ({'encoder_bwd3.hip': ['-DPIML_F3_STAMPS']})
     re-compiled under the extra flags.  Returns the path (pass it as PIML_LIB)."""
     flags = CFLAGS + os.environ.get('PIML_HIPCC_EXTRA', '').split()
     objs = []

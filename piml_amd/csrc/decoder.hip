@@ -1006,11 +1006,6 @@ __global__ __launch_bounds__(512) void rowdec_bwd_dx_big_kernel(DecArgs A, int w
 // weights while it stages them (three items per thread, once per launch).  The 64 -> 2 predictor is 64 FMAs per lane and one
 // cross-half add instead of 32 padded matrix instructions; W3^T (k = 2) stays on the f32 instruction (two per tile).
 // LDS (u32x4): [fb][piece 3][lane 64]. ----
-// dX kernel: 1 = the first tile's row loads between the staging's loads and its split, 0 (default, measured 0.5 us ahead) = behind
-// the staging's LDS stores
-#ifndef PIML_ROWDEC_HOIST
-#define PIML_ROWDEC_HOIST 0
-#endif
 struct RowPieces { u32x4 hi[8], mid[8], lo[8]; };
 template <int NB>          // NB accumulator blocks -> 2 NB k-blocks
 __device__ __forceinline__ void rowdec_split(const f32x16 (&in)[NB], RowPieces& P) {
@@ -1224,12 +1219,11 @@ __global__ __launch_bounds__(512) void rowdec_bwd_dx_x3_kernel(DecArgs A, int wg
         S2.load(J.packed + DP_T2, tid);
         S1.load(J.packed + DP_T1, tid);
         const float fv = tid < 128 ? J.packed[DP_T3 + tid] : 0.f;
-        if (PIML_ROWDEC_HOIST && first < ntiles) load_rows(first);
         S2.land(img + RDXX_T2, tid);
         S1.land(img + RDXX_T1, tid);
         if (tid < 128) T3[tid] = fv;
     }
-    if (!PIML_ROWDEC_HOIST && first < ntiles) load_rows(first);
+    if (first < ntiles) load_rows(first);      // (behind the staging's LDS stores: measured 0.5 us ahead of between its loads and its split)
     __syncthreads();
     for (long long tile = first; tile < ntiles; tile += stride) {
         int lane_t = lane;
@@ -1576,22 +1570,18 @@ __global__ __launch_bounds__(512) void rowdec_bwd_dw_x3_kernel(DecArgs A, int sl
         // looked at behind the products of chunk t + 1 (requested in front of the products of chunk t they had the products' time
         // only: 25.8 us for the launch at the reference's row counts)
         // (the barrier: this wave's LDS operations done, nothing said about its loads in flight -- __syncthreads() waits for them)
-#ifndef PIML_RWX_EARLY
-#define PIML_RWX_EARLY 1
-#endif
         Stage S = stage_load(s0);
         stage_write(S, rx_smem, s0);
-        if (PIML_RWX_EARLY) S = stage_load(s0 + RD_CHUNK);          // past the slab: clamped + zeroed, written but never read
+        S = stage_load(s0 + RD_CHUNK);          // past the slab: clamped + zeroed, written but never read
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         for (int t = 0; t < nb; ++t) {
             unsigned char* cur = rx_smem + (t & 1) * RWX_BUF;
             unsigned char* nxt = rx_smem + ((t + 1) & 1) * RWX_BUF;
-            if (!PIML_RWX_EARLY) S = stage_load(s0 + (long long)(t + 1) * RD_CHUNK);
             __builtin_amdgcn_sched_barrier(0);
             compute(cur);
             __builtin_amdgcn_sched_barrier(0);
             stage_write(S, nxt, s0 + (long long)(t + 1) * RD_CHUNK);
-            if (PIML_RWX_EARLY) S = stage_load(s0 + (long long)(t + 2) * RD_CHUNK);
+            S = stage_load(s0 + (long long)(t + 2) * RD_CHUNK);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

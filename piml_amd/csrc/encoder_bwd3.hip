@@ -58,13 +58,6 @@ constexpr int F3_TDUMMY = F3_T + 4 * 16 * F3_TROW * 4;        // [wave 4][lane 3
 constexpr int F3_LDS_BYTES = F3_TDUMMY + 4 * 32 * 16;
 static_assert(F3_LDS_BYTES <= 160 * 1024, "fits the CU");
 
-// diagnostic builds (tools/r4_ab.sh; RESULTS WRONG ON PURPOSE): PIML_F3_SKIP = bits of work left out, to see what it costs
-//   1: the steps between layer A's products   2: those of layer B   4: those of dW2   8: G2's mask / split / hand-over
-//   16: the products of dW2   32: the products of both chain layers
-#ifndef PIML_F3_SKIP
-#define PIML_F3_SKIP 0
-#endif
-
 #ifdef PIML_F3_STAMPS
 // diagnostic build only (tools/f3_stamps.py): cycles of wave 0 between the stamps, summed over the workgroup's tiles
 __device__ unsigned long long g_f3_stamps[256 * 64];          // [workgroup][wave 4][stamp 16]
@@ -84,24 +77,7 @@ __device__ unsigned long long g_f3_stamps[256 * 64];          // [workgroup][wav
 
 // The workgroup barrier of the tile loops: this wave's LDS operations done, nothing said about its loads in flight (the requests of
 // the next tile travel across it; __syncthreads() also waits for vmcnt(0) -- the stamps read 400 - 1040 cycles at B1 for that).
-// PIML_F3_SYNCTHREADS=1: the plain barrier (A/B)
-#ifndef PIML_F3_SYNCTHREADS
-#define PIML_F3_SYNCTHREADS 0
-#endif
-#if PIML_F3_SYNCTHREADS
-#define F3_BARRIER() __syncthreads()
-#else
 #define F3_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#endif
-
-// 1: g_x = G1 W1 on v_mfma_f32_16x16x4_f32 (exact f32 products): per pass of 16 features two chains (rows 0 .. 15 / 16 .. 31) of four
-// products; the G1 operand is one ds_read_b32 of the wave's half tile per product, the W1 operand EIGHT registers for the whole
-// slab -- instead of 32 ds_read_b32 + 32 broadcast ds_read_b128 of W1 rows + 128 FMAs per wave and tile (the LDS pipe, not the
-// FMAs, was the price there: encoder_bwd5.hip).  Built, green (246 tests) and LEVEL here (58.3 against 58.4 us in the dropout step): the
-// lone wave's vector form already sits in the shadow of the dW2 products.  0 (default): the vector form
-#ifndef PIML_F3_GX_MFMA
-#define PIML_F3_GX_MFMA 0
-#endif
 
 struct F3Args {
     EncArgs A;
@@ -140,23 +116,20 @@ __device__ __forceinline__ void split_half(const f32x16& a, Pieces2& P, int s) {
 // (cdna_hip_programming.md 5.7): results in VGPRs, `=&v` where the chain starts from zero (the destination must not land on
 // an operand), two wait states in front of a product whose A operand may come from a move (s_nop 1), and f3_settle() --
 // sixteen states -- between a chain's last product and the first vector instruction that reads it.
-#ifndef PIML_F3_PAD
-#define PIML_F3_PAD ""
-#endif
 __device__ __forceinline__ void f3_mfma0(f32x16& d, const u32x4& a, const u32x4& b_acc) {          // d = a x B(agpr)
-    asm volatile(PIML_F3_PAD "v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b_acc));
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b_acc));
 }
 __device__ __forceinline__ void f3_mfma0v(f32x16& d, const u32x4& a, const u32x4& b) {             // d = a x b(vgpr)
-    asm volatile(PIML_F3_PAD "v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b));
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b));
 }
 __device__ __forceinline__ void f3_mfma(f32x16& d, const u32x4& a, const u32x4& b_acc) {           // d += a x B(agpr)
-    asm volatile(PIML_F3_PAD "v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b_acc));
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b_acc));
 }
 __device__ __forceinline__ void f3_mfmav(f32x16& d, const u32x4& a, const u32x4& b) {              // d += a x b(vgpr)
-    asm volatile(PIML_F3_PAD "v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
 }
 __device__ __forceinline__ void f3_mfma32(f32x16& d, float a, float b) {                            // f32 instruction, all VGPRs
-    asm volatile(PIML_F3_PAD "v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
+    asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
 }
 __device__ __forceinline__ void f3_settle(f32x16& d) { asm volatile("s_nop 7\n\ts_nop 7" : "+v"(d)); }
 // inputs of a tile that come from memory, requested one tile ahead
@@ -236,9 +209,6 @@ __global__ __launch_bounds__(F3_THREADS) void enc_bwd_fused_x3_kernel(F3Args F) 
 #pragma unroll
     for (int s = 0; s < 4; ++s) w1v[s] = W1rows[(32 * w + n) * 8 + 2 * s + h];
     const float b1v = J.b1[32 * w + n];
-    float w1g[8];                                             // B operand of the g_x products: W1[32 w + 16 p + 4 j + (lane >> 4)][lane & 15]
-#pragma unroll
-    for (int q = 0; q < 8; ++q) w1g[q] = (GX && PIML_F3_GX_MFMA && (lane & 15) < 8) ? W1rows[(32 * w + 4 * q + (lane >> 4)) * 8 + (lane & 15)] : 0.f;
 
     // ---- per-lane LDS addresses ----
     u32x4* const bufA = reinterpret_cast<u32x4*>(smem + F3_BUFA) + lane;
@@ -410,14 +380,7 @@ __global__ __launch_bounds__(F3_THREADS) void enc_bwd_fused_x3_kernel(F3Args F) 
 
 #define F3_SLOT(MF, FILL)                        \
     do {                                         \
-        if (!(PIML_F3_SKIP & 32)) { MF; }        \
-        __builtin_amdgcn_sched_barrier(0);       \
-        FILL;                                    \
-        __builtin_amdgcn_sched_barrier(0);       \
-    } while (0)
-#define F3_SLOTW(MF, FILL)                       \
-    do {                                         \
-        if (!(PIML_F3_SKIP & 16)) { MF; }        \
+        MF;                                      \
         __builtin_amdgcn_sched_barrier(0);       \
         FILL;                                    \
         __builtin_amdgcn_sched_barrier(0);       \
@@ -509,7 +472,6 @@ __global__ __launch_bounds__(F3_THREADS) void enc_bwd_fused_x3_kernel(F3Args F) 
                 return;
             }
             const int f = sl < 40 ? sl - sl / 5 - 1 : sl - 8;  // 40 free steps
-            if ((PIML_F3_SKIP & 1) && f >= 7) return;
             if (f < 7) pf_step(f, ntile);
             else if (f == 7) { if (GX) gx_store(prev_tile); }
             else if (f == 9) f3_settle(hacc);
@@ -532,25 +494,23 @@ __global__ __launch_bounds__(F3_THREADS) void enc_bwd_fused_x3_kernel(F3Args F) 
         }
         F3_STAMP(1);
         if (!SUMS) f3_settle(acc);
-        if (!(PIML_F3_SKIP & 8)) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int t = SUMS ? __builtin_amdgcn_sbfe(m2w, r, 1) : __builtin_amdgcn_sbfe(mkw[r], bp, 1);
-                acc[r] = __uint_as_float(__float_as_uint(acc[r]) & (unsigned)t);
-                db2 += acc[r];
-            }
-            Pieces2 G2;
+        for (int r = 0; r < 16; ++r) {
+            const int t = SUMS ? __builtin_amdgcn_sbfe(m2w, r, 1) : __builtin_amdgcn_sbfe(mkw[r], bp, 1);
+            acc[r] = __uint_as_float(__float_as_uint(acc[r]) & (unsigned)t);
+            db2 += acc[r];
+        }
+        Pieces2 G2;
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                split_half(acc, G2, s);
+        for (int s = 0; s < 2; ++s) {
+            split_half(acc, G2, s);
 #pragma unroll
-                for (int g = 2 * s; g < 2 * s + 2; ++g) {
-                    const int slot = ((2 * g + h) ^ swz_w) * 8;
-                    const int d = 2 * (g & 1);
-                    *reinterpret_cast<uint2*>(Mw + slot) = make_uint2(G2.hi[s][d], G2.hi[s][d + 1]);
-                    *reinterpret_cast<uint2*>(Mw + 8192 + slot) = make_uint2(G2.mid[s][d], G2.mid[s][d + 1]);
-                    *reinterpret_cast<uint2*>(Mw + 16384 + slot) = make_uint2(G2.lo[s][d], G2.lo[s][d + 1]);
-                }
+            for (int g = 2 * s; g < 2 * s + 2; ++g) {
+                const int slot = ((2 * g + h) ^ swz_w) * 8;
+                const int d = 2 * (g & 1);
+                *reinterpret_cast<uint2*>(Mw + slot) = make_uint2(G2.hi[s][d], G2.hi[s][d + 1]);
+                *reinterpret_cast<uint2*>(Mw + 8192 + slot) = make_uint2(G2.mid[s][d], G2.mid[s][d + 1]);
+                *reinterpret_cast<uint2*>(Mw + 16384 + slot) = make_uint2(G2.lo[s][d], G2.lo[s][d + 1]);
             }
         }
         F3_STAMP(2);
@@ -584,7 +544,6 @@ __global__ __launch_bounds__(F3_THREADS) void enc_bwd_fused_x3_kernel(F3Args F) 
                 return;
             }
             const int f = sl < 40 ? sl - sl / 5 - 1 : sl - 8;
-            if ((PIML_F3_SKIP & 2) && f >= 1) return;
             if (f == 0) stage(par ^ 1);
             else if (f >= 1 && f < 23) {
                 if (!SUMS) g3_step(f - 1);
@@ -670,29 +629,6 @@ __global__ __launch_bounds__(F3_THREADS) void enc_bwd_fused_x3_kernel(F3Args F) 
                 w1acc[6] = __fmaf_rn(g, xb4.z, w1acc[6]); w1acc[7] = __fmaf_rn(g, xb4.w, w1acc[7]);
             }
         };
-        // g_x on the matrix instruction: operand A = lane (m = row & 15, k = lane >> 4) reads G1[feature 4 j + k of the pass][row 16 r + m]
-        f32x4 gd[2];
-        float ga[4][2];
-        const float* const Tm = Tbase + (lane >> 4) * F3_TROW + (lane & 15);        // + 4 j features, + 16 r rows
-        auto gm_load = [&]() {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int r = 0; r < 2; ++r) ga[j][r] = Tm[4 * j * F3_TROW + 16 * r];
-        };
-        auto gm_mma = [&](int p_, int j) {
-#pragma unroll
-            for (int r = 0; r < 2; ++r) gd[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[j][r], w1g[4 * p_ + j], gd[r], 0, 0, 0);
-        };
-        auto gm_store = [&]() {                              // rows 16 r + 4 (lane >> 4) + i, column lane & 15 (columns >= 8: a slot of the lane's own)
-            float* dst = (lane & 15) < 8 ? reinterpret_cast<float*>(smem + F3_GX) + (w * 32 + 4 * (lane >> 4)) * 8 + (lane & 15)
-                                          : reinterpret_cast<float*>(smem + F3_TDUMMY) + (w * 32 + (lane & 31)) * 4 - 0;
-            const int stride = (lane & 15) < 8 ? 8 : 0;
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) dst[(16 * r + i) * stride] = gd[r][i];
-        };
         auto fill_w = [&](int sl) {
             if (sl % 6 == 0) {
                 const int u_ = sl / 6 + 1;
@@ -701,7 +637,6 @@ __global__ __launch_bounds__(F3_THREADS) void enc_bwd_fused_x3_kernel(F3Args F) 
             }
             if (sl == 23) { load_g2(1); return; }             // (behind the last product of k-step 0)
             const int f = sl - sl / 6 - 1 - (sl > 23);        // 39 free steps
-            if (PIML_F3_SKIP & 4) return;
             if (f < 8) {                                       // G1 = (G2 W2) * [h1 > 0], two rows a step
 #pragma unroll
                 for (int r = 2 * f; r < 2 * f + 2; ++r) {
@@ -709,20 +644,12 @@ __global__ __launch_bounds__(F3_THREADS) void enc_bwd_fused_x3_kernel(F3Args F) 
                     acc[r] = __uint_as_float(__float_as_uint(acc[r]) & (unsigned)t);
                     db1 += acc[r];
                 }
-            } else if (GX && PIML_F3_GX_MFMA && f >= 8 && f < 26) {
-                if (f == 8) { gd[0] = gd[1] = (f32x4){0.f, 0.f, 0.f, 0.f}; t_write(0); }
-                else if (f == 9) gm_load();
-                else if (f >= 11 && f < 15) gm_mma(0, f - 11);
-                else if (f == 15) t_write(1);                 // (behind the pass-0 reads: a wave's LDS operations complete in order)
-                else if (f == 16) gm_load();
-                else if (f >= 18 && f < 22) gm_mma(1, f - 18);
-                else if (f == 25) gm_store();
             } else if (GX && f == 8) { t_write(0); gx_load(0, 0); }
             else if (GX && f >= 9 && f < 17) { if (f < 16) gx_load(0, f - 8); gx_fma(f - 9); }
             else if (GX && f == 17) { t_write(1); gx_load(1, 0); }
             else if (GX && f >= 18 && f < 26) { if (f < 25) gx_load(1, f - 17); gx_fma(f - 18); }
             else if (f == 26) {
-                if (GX && !PIML_F3_GX_MFMA) reinterpret_cast<float4*>(smem + F3_GX)[(w * 32 + n) * 2 + h] = make_float4(gx[0], gx[1], gx[2], gx[3]);
+                if (GX) reinterpret_cast<float4*>(smem + F3_GX)[(w * 32 + n) * 2 + h] = make_float4(gx[0], gx[1], gx[2], gx[3]);
                 x_load(0);
             } else if (f >= 27 && f < 35) { if (f < 34) x_load(f - 26); x_fma(f - 27); }
         };
@@ -732,12 +659,12 @@ __global__ __launch_bounds__(F3_THREADS) void enc_bwd_fused_x3_kernel(F3Args F) 
         for (int u = 0; u < 8; ++u) {                          // u = 4 s + jb
             const int jb = u & 3;
             const u32x4 (&o)[3] = opb[u & 1];
-            F3_SLOTW(sm[jb] = mfma_bf(g2f[2], o[0], sm[jb]), fill_w(u * 6 + 0));
-            F3_SLOTW(sm[jb] = mfma_bf(g2f[1], o[1], sm[jb]), fill_w(u * 6 + 1));
-            F3_SLOTW(sm[jb] = mfma_bf(g2f[0], o[2], sm[jb]), fill_w(u * 6 + 2));
-            F3_SLOTW(sm[jb] = mfma_bf(g2f[1], o[0], sm[jb]), fill_w(u * 6 + 3));
-            F3_SLOTW(sm[jb] = mfma_bf(g2f[0], o[1], sm[jb]), fill_w(u * 6 + 4));
-            F3_SLOTW(c[jb] = mfma_bf(g2f[0], o[0], c[jb]), fill_w(u * 6 + 5));
+            F3_SLOT(sm[jb] = mfma_bf(g2f[2], o[0], sm[jb]), fill_w(u * 6 + 0));
+            F3_SLOT(sm[jb] = mfma_bf(g2f[1], o[1], sm[jb]), fill_w(u * 6 + 1));
+            F3_SLOT(sm[jb] = mfma_bf(g2f[0], o[2], sm[jb]), fill_w(u * 6 + 2));
+            F3_SLOT(sm[jb] = mfma_bf(g2f[1], o[0], sm[jb]), fill_w(u * 6 + 3));
+            F3_SLOT(sm[jb] = mfma_bf(g2f[0], o[1], sm[jb]), fill_w(u * 6 + 4));
+            F3_SLOT(c[jb] = mfma_bf(g2f[0], o[0], c[jb]), fill_w(u * 6 + 5));
         }
         F3_STAMP(6);
         prev_tile = tile;

@@ -69,20 +69,17 @@ typedef float f32x4_ __attribute__((ext_vector_type(4)));
 // ---- matrix instructions as asm statements (see encoder_bwd3.hip): the weight operand in an AGPR ("a"), results in VGPRs for
 // the chain (read by vector instructions right away) and in AGPRs for the slab accumulators.  hipcc pads nothing inside an asm
 // statement.  The chain's operands come straight from LDS loads and an accumulator's first product starts from the literal 0,
-// so no vector instruction writes a register a chain product reads: no wait states in front (PIML_F4_PAD for A/B); the dW
+// so no vector instruction writes a register a chain product reads: no wait states in front; the dW
 // products read pieces a vector instruction made (two wait states in front) and f4_settle() stands between a chain's last
 // product and the first vector instruction that reads the result. ----
-#ifndef PIML_F4_PAD
-#define PIML_F4_PAD ""
-#endif
 __device__ __forceinline__ void f4_mfma(f32x4_& d, const u32x4& a, const u32x4& b_acc) {
-    asm volatile(PIML_F4_PAD "v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b_acc));
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b_acc));
 }
 __device__ __forceinline__ void f4_mfma0(f32x4_& d, const u32x4& a, const u32x4& b_acc) {        // d = a x B: a chain's first product
-    asm volatile(PIML_F4_PAD "v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b_acc));
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b_acc));
 }
 __device__ __forceinline__ void f4_mfmav(f32x4_& d, const u32x4& a, const u32x4& b) {
-    asm volatile(PIML_F4_PAD "v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
 }
 __device__ __forceinline__ void f4_mfma_acc(f32x4_& d, const u32x4& a, const u32x4& b) {        // slab accumulator in an AGPR
     asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(d) : "v"(a), "v"(b));

@@ -43,35 +43,9 @@ constexpr int F5_TBYTES = 128 * F5_TROW * 4;
 constexpr int F5_T = F5_H + 2 * F5_IMG;                      // G1 tiles [parity 2][feature 128][36] floats
 constexpr int F5_XS = F5_T + 2 * F5_TBYTES;                  // x rows [ring 3][32][8] floats
 constexpr int F5_MK = F5_XS + 3 * 1024;                      // sign words of h1 [parity 2][128 dwords]
-constexpr int F5_W1 = F5_MK + 2 * 512;                       // W1 rows [128][8] floats
-constexpr int F5_GXP = F5_W1 + 4096;                         // g_x partials [parity 2][wave 4][row 32][8] floats
-// 1: complementary halves -- crew A's products beside crew B's vector work, then crew A's vector work beside crew B's products;
-// 0: every wave interleaves its vector work with its own products (both waves of a SIMD want both pipes all the time)
-#ifndef PIML_F5_PHASED
-#define PIML_F5_PHASED 1
-#endif
-// 1: crew A's requests of the tile after the next between its products (second register set, 21 moves); 0: behind its vector
-// half.  Measured level-to-worse (30.2 - 30.5 against 29.5 - 29.7 us): what crew A saves, crew B's products lose -- the SIMD issues
-// about one instruction per six cycles whichever wave it comes from
-#ifndef PIML_F5_REQ_EARLY
-#define PIML_F5_REQ_EARLY 0
-#endif
-// 1: g_x = G1 W1 on v_mfma_f32_16x16x4_f32 -- the W1 operand is EIGHT registers per lane for the whole slab and the G1 operand one
-// conflict-light ds_read_b32 per product (16 per tile); 0: vector FMAs on W1 rows broadcast from LDS (32 ds_read_b128 per wave and
-// tile, which the stamps price at ~1000 cycles of the tile: the LDS pipe, not the FMAs, was crew B's vector half)
-#ifndef PIML_F5_GX_MFMA
-#define PIML_F5_GX_MFMA 1
-#endif
-// 1: dW1 = G1^T X on the same instruction (two chains of eight products per tile into eight persistent registers; operands: one
-// ds_read_b32 of the G1 tile and one of the x rows per product) instead of 96 FMAs on 36 LDS reads per wave and tile.  Built,
-// green, and SLOWER (31.5 against 29.5 us): with it crew B has no vector half left, its 80 products start beside crew A's chain
-// and the tile becomes the matrix pipe's 134 x 32 cycles.  Off; the vector form is the default.
-#ifndef PIML_F5_DW1_MFMA
-#define PIML_F5_DW1_MFMA 0
-#endif
-static_assert(!PIML_F5_GX_MFMA || PIML_F5_PHASED, "the g_x products ride in the phased schedule");
-static_assert(!PIML_F5_DW1_MFMA || PIML_F5_GX_MFMA, "the dW1 products need the zero region the g_x products freed");
-constexpr int F5_GXP_BYTES = PIML_F5_GX_MFMA ? 4 * 32 * 16 * 4 : 4096;      // one parity: [wave 4][row 32][16 | 8] floats
+constexpr int F5_W1 = F5_MK + 2 * 512;                       // 4096 zero bytes (the W1 rows of a dropped vector form of g_x)
+constexpr int F5_GXP = F5_W1 + 4096;                         // g_x partials [parity 2][wave 4][row 32][16] floats
+constexpr int F5_GXP_BYTES = 4 * 32 * 16 * 4;                // one parity
 constexpr int F5_TAB = F5_GXP + 2 * F5_GXP_BYTES;            // gather table [rem < 16][half 2][register 16] byte offsets
 constexpr int F5_KMAX = 16;
 constexpr int F5_LDS_BYTES = F5_TAB + F5_KMAX * 2 * 16 * 4;
@@ -84,12 +58,6 @@ struct F5Args {
     int nA[2];          // workgroups of branch 0 / branch 1 (grid = their sum)
     DecSlotSums D;      // the decoder's slot sets, summed by this launch's workgroups (D.nsets = 0: left to the slot-sum launch)
 };
-
-// Where the decoder slot sums run: 1 = crew A alone, between its last tile and its trailing barriers, i.e. while crew B works on the
-// last tile and stores its slot (crew A only waits there); 0 = behind both crews' epilogues, every thread of the workgroup
-#ifndef PIML_F5_DEC_AT
-#define PIML_F5_DEC_AT 1
-#endif
 
 // row_shl:C of a DPP row (16 lanes): lane i reads lane i + C
 template <int C>
@@ -153,13 +121,6 @@ __device__ unsigned long long g_f5_stamps[256 * 8 * 16];      // [workgroup][wav
 __device__ __forceinline__ float f5_relu(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
 __device__ __forceinline__ constexpr int f5_rho(int r) { return (r & 3) + 8 * (r >> 2); }      // row of accumulator register r in lane half 0 (half 1: + 4)
 
-// diagnostic builds (tools/r6_f5skip.sh; RESULTS WRONG ON PURPOSE): PIML_F5_SKIP = bits of work left out, to see what it costs
-//   1: crew B's lagging vector work (g_x, dW1)   2: g_x only   4: crew A's G2 image of the next tile   8: crew A's H1
-//   16: crew A's G1 mask + tile   32: crew B's products   64: crew A's products   128: crew A's requests
-#ifndef PIML_F5_SKIP
-#define PIML_F5_SKIP 0
-#endif
-
 #define F5_SLOT(MF, FILL)                        \
     do {                                         \
         MF;                                      \
@@ -209,7 +170,7 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
     for (int i = 0; i < 16; ++i) st[i] = 0;
 #endif
 
-    // ---- LDS: the buffers the lagging work of the first iterations reads must hold zeros; the gather table; W1 rows ----
+    // ---- LDS: the buffers the lagging work of the first iterations reads must hold zeros; the gather table ----
     {
         float4* z = reinterpret_cast<float4*>(smem + F5_T);
         constexpr int NZ = (F5_W1 - F5_T) / 16;               // G1 tiles | x ring | sign words
@@ -224,17 +185,7 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
             const unsigned rem = (unsigned)tid >> 5, hh = ((unsigned)tid >> 4) & 1u, r = (unsigned)tid & 15u;
             reinterpret_cast<unsigned*>(smem + F5_TAB)[tid] = ((rem + 4u * hh + (unsigned)f5_rho((int)r)) / K) * (EH * 4);
         }
-        if (tid < 256 && PIML_F5_GX_MFMA) {                  // no W1 rows in LDS: the region is the zero operand of the dW1 products' idle columns
-            reinterpret_cast<float4*>(smem + F5_W1)[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-        } else if (tid < 256) {
-            const float* W1r = J.packed + PACK_FWD + 32768;     // W1 rows padded to 8 columns
-            if (INC == 6) {                                   // g_x: lane half h takes columns 3 h .. 3 h + 2 -> [feature][half][c, c, c, 0]
-                const float* src = W1r + (tid >> 1) * 8 + 3 * (tid & 1);
-                reinterpret_cast<float4*>(smem + F5_W1)[tid] = make_float4(src[0], src[1], src[2], 0.f);
-            } else {
-                reinterpret_cast<float4*>(smem + F5_W1)[tid] = reinterpret_cast<const float4*>(W1r)[tid];
-            }
-        }
+        if (tid < 256) reinterpret_cast<float4*>(smem + F5_W1)[tid] = make_float4(0.f, 0.f, 0.f, 0.f);      // (nothing reads it)
     }
 
     if (crew == 0) {
@@ -308,46 +259,6 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
                 xa[s] = __uint_as_float(ld1(rs_x, (valid & (cx < IN)) ? (row * IN + cx) * 4u : kOut, 0u));
             }
             mkv = ld1(rs_mk, tile < ntiles ? (unsigned)tile * 1024u + (unsigned)(ctid & 127) * 4u : kOut, 0u);
-        };
-        // The same requests cut into six steps that ride between the products (PIML_F5_REQ_EARLY): a vector-memory instruction costs
-        // the lone issuer 15 - 30 cycles, the 22 of a tile were ~950 cycles of crew A's vector half; between products they are
-        // covered.  They land in a second register set (the first still holds the tile the vector half is about to consume).
-        float g2n[16];
-        unsigned m2n = 0, mkvn = 0;
-        float xan[NS];
-        uint4 tabv;
-        auto req_step = [&](int i, int tile) {
-            const unsigned t32 = __builtin_amdgcn_readfirstlane((unsigned)tile * 32u);
-            const unsigned a0 = __builtin_amdgcn_readfirstlane(__umulhi(t32, kmagic)), rem = t32 - a0 * K;
-            const bool live = tile < ntiles;
-            const uint4* tab = reinterpret_cast<const uint4*>(smem + F5_TAB + (rem * 32u + 16u * (unsigned)h) * 4u);
-            if (i == 0) { tabv = tab[0]; return; }
-            if (i <= 4) {
-                const unsigned gb = live ? gbase + a0 * (EH * 4) : kOut;
-                const uint4 o = tabv;
-                if (i < 4) tabv = tab[i];
-                g2n[4 * i - 4] = __uint_as_float(ld1(rs_gp, gb + o.x, 0u));
-                g2n[4 * i - 3] = __uint_as_float(ld1(rs_gp, gb + o.y, 0u));
-                g2n[4 * i - 2] = __uint_as_float(ld1(rs_gp, gb + o.z, 0u));
-                g2n[4 * i - 1] = __uint_as_float(ld1(rs_gp, gb + o.w, 0u));
-                return;
-            }
-            m2n = ld1(rs_mk, live ? (unsigned)tile * 1024u + (128u + 2u * (unsigned)lane + (unsigned)(w >> 1)) * 4u : kOut, 0u);
-            const unsigned row = (unsigned)tile * 32u + (unsigned)n;
-            const bool valid = live & (row < R);
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const unsigned cx = 2u * s + h;
-                xan[s] = __uint_as_float(ld1(rs_x, (valid & (cx < IN)) ? (row * IN + cx) * 4u : kOut, 0u));
-            }
-            mkvn = ld1(rs_mk, live ? (unsigned)tile * 1024u + (unsigned)(ctid & 127) * 4u : kOut, 0u);
-        };
-        auto req_take = [&]() {                                // the incoming set becomes the current one
-#pragma unroll
-            for (int r = 0; r < 16; ++r) g2[r] = g2n[r];
-#pragma unroll
-            for (int s = 0; s < NS; ++s) xa[s] = xan[s];
-            m2 = m2n; mkv = mkvn;
         };
         // G2 of the requested tile = g2 * [h2 > 0] -> db2 -> bf16 pieces -> image `pm`; 16 steps (k-step s = j >> 3)
         float db1 = 0.f, db2 = 0.f;
@@ -438,8 +349,7 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
             const int par = it & 1, tile = bx + it * nwg;
             F5_STAMP(0);
             // layer B: G1 = (G2 W2) * [h1 > 0], 48 products into one accumulator (the five small products of every k-block first,
-            // the eight hi x hi on top: encoder_bwd3.hip); between them the NEXT tile's G2 and H1 images and the requests of the
-            // tile after it
+            // the eight hi x hi on top: encoder_bwd3.hip); between them the operand loads and this tile's sign words of h1
             f32x16 acc;
             u32x4 opa[2][3], ahi[8];                          // (ahi: the activations' hi pieces, kept for the eight hi x hi products)
             unsigned mkw[16];
@@ -452,24 +362,11 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
                 }
                 if (sl == 38 || sl == 39) return;
                 const int f = sl < 40 ? sl - sl / 5 - 1 : sl - 10;     // free steps: 0 .. 29 under the small products, 30 .. 37 under the hi x hi ones
-                if (PIML_F5_PHASED) {                          // the requests of the tile after the next; this tile's sign words (late: used right behind)
-                    if (PIML_F5_REQ_EARLY && f >= 2 && f < 14 && !(f & 1) && !(PIML_F5_SKIP & 128)) req_step(f / 2 - 1, tile + 2 * nwg);
-                    if (f >= 30 && f < 34) {
+                (void)it;      // (keeps the capture of a dropped branch: without it the same instructions come out in another order)
+                if (f >= 30 && f < 34) {                       // this tile's sign words (late: used right behind)
 #pragma unroll
-                        for (int i = 4 * (f - 30); i < 4 * (f - 30) + 4; ++i) mkw[i] = mk1[2 * f5_rho(i)];
-                    }
-                    return;
+                    for (int i = 4 * (f - 30); i < 4 * (f - 30) + 4; ++i) mkw[i] = mk1[2 * f5_rho(i)];
                 }
-                if (f < 16) { if (!(PIML_F5_SKIP & 4)) g2_step(f, par ^ 1); }
-                else if (f < 20) {
-#pragma unroll
-                    for (int i = 4 * (f - 16); i < 4 * (f - 16) + 4; ++i) mkw[i] = mk1[2 * f5_rho(i)];
-                }
-                else if (f == 20) { if (!(PIML_F5_SKIP & 8)) h1_mma(); }
-                else if (f >= 23 && f < 33) { if (!(PIML_F5_SKIP & 8)) h1_step(f - 23, par ^ 1); }
-                else if (f == 33) stage((it + 1) % 3, par ^ 1);
-                else if (f == 34) { if (!(PIML_F5_SKIP & 128)) req_g(tile + 2 * nwg); }
-                else if (f == 35) { if (!(PIML_F5_SKIP & 128)) req_x(tile + 2 * nwg); }
             };
             load_b(opa[0], 0, par);
             const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -477,63 +374,46 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
             for (int kb = 0; kb < 8; ++kb) {
                 const u32x4 (&o)[3] = opa[kb & 1];
                 ahi[kb] = o[0];
-#define F5_MA(X) do { if (!(PIML_F5_SKIP & 64)) { X; } else if (kb == 0) acc = zero16; } while (0)
-                F5_SLOT(F5_MA(acc = mfma_bf(o[2], wh[kb], kb == 0 ? zero16 : acc)), fill_a(kb * 5 + 0));
-                F5_SLOT(F5_MA(acc = mfma_bf(o[1], wm[kb], acc)), fill_a(kb * 5 + 1));
-                F5_SLOT(F5_MA(acc = mfma_bf(o[0], wl[kb], acc)), fill_a(kb * 5 + 2));
-                F5_SLOT(F5_MA(acc = mfma_bf(o[1], wh[kb], acc)), fill_a(kb * 5 + 3));
-                F5_SLOT(F5_MA(acc = mfma_bf(o[0], wm[kb], acc)), fill_a(kb * 5 + 4));
+                F5_SLOT(acc = mfma_bf(o[2], wh[kb], kb == 0 ? zero16 : acc), fill_a(kb * 5 + 0));
+                F5_SLOT(acc = mfma_bf(o[1], wm[kb], acc), fill_a(kb * 5 + 1));
+                F5_SLOT(acc = mfma_bf(o[0], wl[kb], acc), fill_a(kb * 5 + 2));
+                F5_SLOT(acc = mfma_bf(o[1], wh[kb], acc), fill_a(kb * 5 + 3));
+                F5_SLOT(acc = mfma_bf(o[0], wm[kb], acc), fill_a(kb * 5 + 4));
             }
-#ifdef PIML_F5_ACC2
-            f32x16 acc2 = zero16;
 #pragma unroll
-            for (int kb = 0; kb < 8; ++kb) F5_SLOT(if (kb & 1) acc2 = mfma_bf(ahi[kb], wh[kb], acc2); else acc = mfma_bf(ahi[kb], wh[kb], acc), fill_a(40 + kb));
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] += acc2[r];
-#else
-#pragma unroll
-            for (int kb = 0; kb < 8; ++kb) F5_SLOT(F5_MA(acc = mfma_bf(ahi[kb], wh[kb], acc)), fill_a(40 + kb));
-#endif
+            for (int kb = 0; kb < 8; ++kb) F5_SLOT(acc = mfma_bf(ahi[kb], wh[kb], acc), fill_a(40 + kb));
             F5_STAMP(1);
             // G1: mask, db1, the lane's 16 rows of its feature -> the G1 tile
-            if (!(PIML_F5_SKIP & 16))
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int t = __builtin_amdgcn_sbfe(mkw[r], bp, 1);
                 acc[r] = __uint_as_float(__float_as_uint(acc[r]) & (unsigned)t);
                 db1 += acc[r];
             }
-            if (!(PIML_F5_SKIP & 16)) {
+            {
                 float4* dst = reinterpret_cast<float4*>(smem + t_off + par * F5_TBYTES);
 #pragma unroll
                 for (int g = 0; g < 4; ++g) dst[2 * g] = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
             }
             F5_STAMP(2);
-            if (PIML_F5_PHASED) {
-                // the vector half of the tile, while crew B's products hold the matrix pipe: the NEXT tile's H1 (its three f32
-                // products first: they queue behind crew B's) and G2 images, the requests of the tile after it
-                if (!(PIML_F5_SKIP & 8)) h1_mma();
-                if (!(PIML_F5_SKIP & 4)) {
+            // the vector half of the tile, while crew B's products hold the matrix pipe: the NEXT tile's H1 (its three f32
+            // products first: they queue behind crew B's) and G2 images, the requests of the tile after it
+            h1_mma();
 #pragma unroll
-                    for (int j = 0; j < 16; ++j) g2_step(j, par ^ 1);
-                }
-                F5_STAMP(6);
-                if (!(PIML_F5_SKIP & 8)) {
+            for (int j = 0; j < 16; ++j) g2_step(j, par ^ 1);
+            F5_STAMP(6);
 #pragma unroll
-                    for (int j = 0; j < 10; ++j) h1_step(j, par ^ 1);
-                }
-                F5_STAMP(7);
-                stage((it + 1) % 3, par ^ 1);
-                if (!(PIML_F5_SKIP & 128)) {
-                    if (PIML_F5_REQ_EARLY) req_take();
-                    else { req_g(tile + 2 * nwg); req_x(tile + 2 * nwg); }
-                }
-                F5_STAMP(5);
-            }
+            for (int j = 0; j < 10; ++j) h1_step(j, par ^ 1);
+            F5_STAMP(7);
+            stage((it + 1) % 3, par ^ 1);
+            req_g(tile + 2 * nwg);
+            req_x(tile + 2 * nwg);
+            F5_STAMP(5);
             F5_BARRIER();
         }
         F5_STAMP(3);
-        if (PIML_F5_DEC_AT == 1 && F.D.nsets > 0) {
+        // the decoder slot sums: crew A alone, while crew B works on the last tile and stores its slot (crew A only waits there)
+        if (F.D.nsets > 0) {
             f5_dec_sums(F.D, (int)blockIdx.x, (int)gridDim.x, ctid, 256);
             F5_STAMP(12);
         }
@@ -567,8 +447,6 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
         const int swz_w = (fw >> 1) & 7;
         const int mw_off = F5_M + fw * 64;                     // this lane's own feature of the G2 image (A fragments of dW2)
         const int t_row = F5_T + fw * (F5_TROW * 4) + (4 * h) * 4;        // this lane's feature of the G1 tile, rows 4 h ..
-        const int t_col = F5_T + (32 * w) * (F5_TROW * 4) + n * 4;        // g_x: feature 32 w + f, row n: + f * 144
-        const int w1_off = F5_W1 + (32 * w) * 32 + h * 16;                // g_x: W1[32 w + f][4 h .. 4 h + 3]: + f * 32
         const int xs_off = F5_XS + (4 * h) * 32;                          // dW1: x rows 4 h ..
 
         auto load_g2 = [&](u32x4 (&g)[3], int s_, int pm) {
@@ -588,47 +466,13 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
         // g_x of a finished tile: the four waves' partials, fixed order; crew thread (row ctid >> 3, column ctid & 7)
         auto gx_store = [&](int tile, int pm) {
             const unsigned grow = (unsigned)tile * 32u + (unsigned)(ctid >> 3), cs = (unsigned)ctid & 7u;
-            float v;
-            if (PIML_F5_GX_MFMA) {                           // [wave][row][16]: column = slot
-                const float* gp = reinterpret_cast<const float*>(smem + F5_GXP + pm * F5_GXP_BYTES) + (ctid >> 3) * 16 + (ctid & 7);
-                v = ((gp[0] + gp[512]) + gp[1024]) + gp[1536];
-            } else {
-                const float* gp = reinterpret_cast<const float*>(smem + F5_GXP + pm * F5_GXP_BYTES) + ctid;
-                v = ((gp[0] + gp[256]) + gp[512]) + gp[768];
-            }
-            // (vector form, INC == 6: slot 4 h + j of a row's eight holds column 3 h + j, slots 3 and 7 nothing)
-            const unsigned cx = (INC == 6 && !PIML_F5_GX_MFMA) ? 3u * (cs >> 2) + (cs & 3u) : cs;
-            const bool cok = (INC == 6 && !PIML_F5_GX_MFMA) ? (cs & 3u) != 3u : cx < IN;
-            const unsigned off = (grow * IN + cx) * 4u;
+            const float* gp = reinterpret_cast<const float*>(smem + F5_GXP + pm * F5_GXP_BYTES) + (ctid >> 3) * 16 + (ctid & 7);      // [wave][row][16]: column = slot
+            const float v = ((gp[0] + gp[512]) + gp[1024]) + gp[1536];
+            const bool cok = cs < IN;
+            const unsigned off = (grow * IN + cs) * 4u;
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs_gx, (int)(((tile >= 0) & (tile < ntiles) & (grow < R) & cok) ? off : kOut), 0, 0);
         };
         // the lagging vector work on the G1 tile `pm` and x ring slot `xslot`
-#ifndef PIML_F5_GXD
-#define PIML_F5_GXD 1
-#endif
-        constexpr int GXR = PIML_F5_GXD + 1;                   // ring: loads PIML_F5_GXD steps ahead of their use
-        float gx[4];
-        float tv[GXR][2];
-        float4 tw[GXR][2];
-        auto gx_load = [&](int k, int pm) {                    // features 2 k, 2 k + 1 of the wave's block
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                if (PIML_F5_SKIP & 512) tv[k % GXR][e] = (float)k; else
-                tv[k % GXR][e] = *reinterpret_cast<const float*>(smem + t_col + pm * F5_TBYTES + (2 * k + e) * (F5_TROW * 4));
-                if (PIML_F5_SKIP & 256) tw[k % GXR][e] = make_float4(1.f, 2.f, 3.f, (float)k); else
-                tw[k % GXR][e] = *reinterpret_cast<const float4*>(smem + w1_off + (2 * k + e) * 32);
-            }
-        };
-        auto gx_fma = [&](int k) {
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const float v = tv[k % GXR][e];
-                const float4 wv = tw[k % GXR][e];
-                gx[0] = __fmaf_rn(wv.x, v, gx[0]); gx[1] = __fmaf_rn(wv.y, v, gx[1]);
-                gx[2] = __fmaf_rn(wv.z, v, gx[2]);
-                if (INC == 8) gx[3] = __fmaf_rn(wv.w, v, gx[3]);
-            }
-        };
         float g1[16];
         float4 xv[2][4];
         auto g1_load = [&](int half_, int pm) {
@@ -662,7 +506,6 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
                 if (INC == 8) { w1acc[INC - 2] = __fmaf_rn(g, xb4.z, w1acc[INC - 2]); w1acc[INC - 1] = __fmaf_rn(g, xb4.w, w1acc[INC - 1]); }
             }
         };
-        // 27 steps: g_x (features two by two, loads a step ahead), its partial, dW1 (rows two by two, loads a step ahead)
         // g_x on the f32 matrix instruction: D[row][c] = sum over the wave's 32 features of G1[row][f] W1[f][c], two chains (rows
         // 0 .. 15 / 16 .. 31) of eight products (four features each); operand A: lane (m = row & 15, k = lane >> 4) reads
         // G1[feature 4 j + k][row] from the tile, operand B: lane (k, n = column) holds W1[4 j + k][n] (0 beyond column 7)
@@ -672,27 +515,6 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
         auto gm_load = [&](int j, int pm) {
 #pragma unroll
             for (int r = 0; r < 2; ++r) ga[j][r] = *reinterpret_cast<const float*>(smem + ga_off + pm * F5_TBYTES + j * (4 * F5_TROW * 4) + r * 64);
-        };
-        // dW1 the same way: D[feature][c] += sum over the tile's rows of G1[row][feature] x[row][c]; chain c2 = features 16 c2 .. + 15
-        // of the wave's block; operand A: lane (m = feature & 15, k = lane >> 4) reads G1[feature][row 4 j + k], operand B: lane
-        // (k, n = column) reads x[row 4 j + k][n] -- columns 8 .. 15 read zeros (the former W1 region)
-        f32x4 dw1m[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-        float da[8][2], dbv[8];
-        const int da_off = F5_T + (32 * w + (lane & 15)) * (F5_TROW * 4) + (lane >> 4) * 4;      // + 16 c2 features, + 4 j rows
-        const int db_off = (lane & 15) < 8 ? F5_XS + (lane >> 4) * 32 + (lane & 15) * 4 : F5_W1 + (lane >> 4) * 32;
-        auto dwm_step = [&](int f, int pm, int xslot) {       // 0 .. 9
-            if (f < 2) {
-#pragma unroll
-                for (int j = 4 * f; j < 4 * f + 4; ++j) {
-#pragma unroll
-                    for (int c2 = 0; c2 < 2; ++c2) da[j][c2] = *reinterpret_cast<const float*>(smem + da_off + pm * F5_TBYTES + c2 * (16 * F5_TROW * 4) + j * 16);
-                    dbv[j] = *reinterpret_cast<const float*>(smem + db_off + xslot * 1024 + j * 128);
-                }
-            } else {
-                const int j = f - 2;
-#pragma unroll
-                for (int c2 = 0; c2 < 2; ++c2) dw1m[c2] = __builtin_amdgcn_mfma_f32_16x16x4f32(da[j][c2], dbv[j], dw1m[c2], 0, 0, 0);
-            }
         };
         // (these products ride between crew B's OWN products, not in its vector half: there crew A's chain of 51 dependent products
         // owns the matrix pipe -- the older wave wins the arbitration every time -- and crew B's in-order stream stood behind its
@@ -715,47 +537,20 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
                     for (int i = 0; i < 4; ++i) dst[(16 * r + i) * 16] = gd[r][i];
             }
         };
-        auto lag_step_m = [&](int f, int pm, int xslot) {     // dW1 alone: 10 steps
-            if (PIML_F5_DW1_MFMA) return;
+        auto lag_step = [&](int f, int pm, int xslot) {       // dW1: 0 .. 9 (rows two by two, loads a step ahead; step 9 is empty)
             if (f == 0) { g1_load(0, pm); g1_load(1, pm); x_load(0, xslot); }
             else if (f == 1) { x_load(1, xslot); x_fma(0); }
             else if (f < 9) { if (f < 8) x_load(f, xslot); x_fma(f - 1); }
         };
-        auto lag_step_v = [&](int f, int pm, int xslot) {
-            if (f == 0) {
-                gx[0] = gx[1] = gx[2] = gx[3] = 0.f;
-                if (GX && !(PIML_F5_SKIP & 2)) {
-#pragma unroll
-                    for (int k = 0; k < PIML_F5_GXD; ++k) gx_load(k, pm);
-                }
-            } else if (f <= 16) {
-                if (GX && !(PIML_F5_SKIP & 2)) { if (f - 1 + PIML_F5_GXD < 16) gx_load(f - 1 + PIML_F5_GXD, pm); gx_fma(f - 1); }
-                if (f == 15) g1_load(0, pm);
-                if (f == 16) { g1_load(1, pm); x_load(0, xslot); }
-            } else if (f == 17) {
-                if (GX) reinterpret_cast<float4*>(smem + F5_GXP + (pm ^ 1) * F5_GXP_BYTES)[(w * 32 + n) * 2 + h] = make_float4(gx[0], gx[1], gx[2], gx[3]);
-                x_load(1, xslot); x_fma(0);
-            } else if (f < 25) {
-                if (f < 24) x_load(f - 16, xslot);
-                x_fma(f - 17);
-            }
-        };
-        auto lag_step = [&](int f, int pm, int xslot) {
-            if (PIML_F5_GX_MFMA) lag_step_m(f, pm, xslot); else lag_step_v(f, pm, xslot);
-        };
 
-#ifdef PIML_F5_PRIO_B
-        __builtin_amdgcn_s_setprio(PIML_F5_PRIO_B);
-#endif
         F5_BARRIER();                                          // the table (crew A's prologue barrier)
         F5_STAMP(15);
         F5_BARRIER();
         for (int it = 0; it < nit; ++it) {
             const int par = it & 1, tile = bx + it * nwg;
             F5_STAMP(0);
-            // dW2 += G2^T H1: 48 products (8 groups u = 4 s + jb of six) into the slab's accumulators; between them the vector work
-            // on the tile BEFORE (its G1 tile is in the other buffer, its x rows two ring slots back) and the g_x store of the one
-            // before that
+            // dW2 += G2^T H1: 48 products (8 groups u = 4 s + jb of six) into the slab's accumulators; between them the g_x products
+            // of the tile BEFORE (its G1 tile is in the other buffer)
             u32x4 g2f[3], opb[2][3];
             const int lpm = par ^ 1, xslot = (it + 2) % 3;
             auto fill_b = [&](int sl) {
@@ -766,52 +561,30 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
                 }
                 if (sl == 23) { load_g2(g2f, 1, par); return; }   // (behind the last product of k-step 0)
                 const int f = sl - sl / 6 - 1 - (sl > 23);         // 39 free steps
-                if (PIML_F5_PHASED) {
-                    if (PIML_F5_GX_MFMA && !(PIML_F5_SKIP & 2)) {
-                        if (f == 1) gxm_step(0, lpm);
-                        else if (f >= 6 && f < 14) gxm_step(f - 5, lpm);
-                        else if (f == 22) gxm_step(9, lpm);
-                    }
-                    if (PIML_F5_DW1_MFMA && !(PIML_F5_SKIP & 1)) {
-                        if (f == 2 || f == 3) dwm_step(f - 2, lpm, xslot);
-                        else if (f >= 14 && f < 22) dwm_step(f - 12, lpm, xslot);
-                    }
-                    return;
-                }
-                if (PIML_F5_SKIP & 1) return;
-                if (f == 0) { if (GX) gx_store(tile - 2 * nwg, par ^ 1); }
-                else if (f < 28) lag_step(f - 1, lpm, xslot);
+                if (f == 1) gxm_step(0, lpm);
+                else if (f >= 6 && f < 14) gxm_step(f - 5, lpm);
+                else if (f == 22) gxm_step(9, lpm);
             };
-            if (PIML_F5_PHASED && !(PIML_F5_SKIP & 1)) {
-                // the vector half first, while crew A's products hold the matrix pipe
-                if (GX) gx_store(tile - 2 * nwg, par ^ 1);
+            // the vector half first, while crew A's products hold the matrix pipe: the g_x store of the tile two back, dW1 of
+            // the tile before (its x rows two ring slots back)
+            if (GX) gx_store(tile - 2 * nwg, par ^ 1);
 #pragma unroll
-                for (int f = 0; f < 17; ++f) lag_step(f, lpm, xslot);
-                F5_STAMP(6);
-#pragma unroll
-                for (int f = 17; f < 27; ++f) lag_step(f, lpm, xslot);
-                F5_STAMP(5);
-            }
-#ifdef PIML_F5_PRIO_PROD
-            __builtin_amdgcn_s_setprio(PIML_F5_PRIO_PROD);      // the products' issue slots in front of crew A's vector stream (the older wave)
-#endif
+            for (int f = 0; f < 10; ++f) lag_step(f, lpm, xslot);
+            F5_STAMP(6);
+            F5_STAMP(5);
             load_g2(g2f, 0, par);
             load_h(opb[0], 0, par);
 #pragma unroll
             for (int u = 0; u < 8; ++u) {                          // u = 4 s + jb
                 const int jb = u & 3;
                 const u32x4 (&o)[3] = opb[u & 1];
-#define F5_MB(X) do { if (!(PIML_F5_SKIP & 32)) { X; } } while (0)
-                F5_SLOT(F5_MB(sm[jb] = mfma_bf(g2f[2], o[0], sm[jb])), fill_b(u * 6 + 0));
-                F5_SLOT(F5_MB(sm[jb] = mfma_bf(g2f[1], o[1], sm[jb])), fill_b(u * 6 + 1));
-                F5_SLOT(F5_MB(sm[jb] = mfma_bf(g2f[0], o[2], sm[jb])), fill_b(u * 6 + 2));
-                F5_SLOT(F5_MB(sm[jb] = mfma_bf(g2f[1], o[0], sm[jb])), fill_b(u * 6 + 3));
-                F5_SLOT(F5_MB(sm[jb] = mfma_bf(g2f[0], o[1], sm[jb])), fill_b(u * 6 + 4));
-                F5_SLOT(F5_MB(c[jb] = mfma_bf(g2f[0], o[0], c[jb])), fill_b(u * 6 + 5));
+                F5_SLOT(sm[jb] = mfma_bf(g2f[2], o[0], sm[jb]), fill_b(u * 6 + 0));
+                F5_SLOT(sm[jb] = mfma_bf(g2f[1], o[1], sm[jb]), fill_b(u * 6 + 1));
+                F5_SLOT(sm[jb] = mfma_bf(g2f[0], o[2], sm[jb]), fill_b(u * 6 + 2));
+                F5_SLOT(sm[jb] = mfma_bf(g2f[1], o[0], sm[jb]), fill_b(u * 6 + 3));
+                F5_SLOT(sm[jb] = mfma_bf(g2f[0], o[1], sm[jb]), fill_b(u * 6 + 4));
+                F5_SLOT(c[jb] = mfma_bf(g2f[0], o[0], c[jb]), fill_b(u * 6 + 5));
             }
-#ifdef PIML_F5_PRIO_PROD
-            __builtin_amdgcn_s_setprio(0);
-#endif
             F5_STAMP(1);
             F5_BARRIER();
         }
@@ -821,15 +594,9 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
             const int it = nit, par = it & 1, tile = bx + it * nwg;
             if (GX) gx_store(tile - 2 * nwg, par ^ 1);
 #pragma unroll
-            for (int f = 0; f < 27; ++f) lag_step(f, par ^ 1, (it + 2) % 3);
-            if (PIML_F5_GX_MFMA) {
+            for (int f = 0; f < 10; ++f) lag_step(f, par ^ 1, (it + 2) % 3);
 #pragma unroll
-                for (int f = 0; f < 10; ++f) gxm_step(f, par ^ 1);
-            }
-            if (PIML_F5_DW1_MFMA) {
-#pragma unroll
-                for (int f = 0; f < 10; ++f) dwm_step(f, par ^ 1, (it + 2) % 3);
-            }
+            for (int f = 0; f < 10; ++f) gxm_step(f, par ^ 1);
             F5_BARRIER();
             if (GX) gx_store(tile - nwg, par);
             F5_BARRIER();
@@ -840,28 +607,15 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
         for (int jb = 0; jb < 4; ++jb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) P[(size_t)(32 * w + f5_rho(r) + 4 * h) * EH + 32 * jb + n] = c[jb][r] + sm[jb][r];
-        if (PIML_F5_DW1_MFMA) {                                // register i of chain c2: feature 32 w + 16 c2 + 4 (lane >> 4) + i, column lane & 15
-            if ((unsigned)(lane & 15) < IN) {
 #pragma unroll
-                for (int c2 = 0; c2 < 2; ++c2)
+        for (int cc = 0; cc < INC; ++cc) w1acc[cc] += __shfl_xor(w1acc[cc], 32, 64);
+        if (h == 0) {
+            float* o = P + EH * EH + (size_t)(32 * w + n) * IN;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) P[EH * EH + (size_t)(32 * w + 16 * c2 + 4 * (lane >> 4) + i) * IN + (lane & 15)] = dw1m[c2][i];
-            }
-        } else {
-#pragma unroll
-            for (int cc = 0; cc < INC; ++cc) w1acc[cc] += __shfl_xor(w1acc[cc], 32, 64);
-            if (h == 0) {
-                float* o = P + EH * EH + (size_t)(32 * w + n) * IN;
-#pragma unroll
-                for (int cc = 0; cc < INC; ++cc)
-                    if ((unsigned)cc < IN) o[cc] = w1acc[cc];
-            }
+            for (int cc = 0; cc < INC; ++cc)
+                if ((unsigned)cc < IN) o[cc] = w1acc[cc];
         }
         F5_STAMP(11);
-    }
-    if (PIML_F5_DEC_AT == 0 && F.D.nsets > 0) {
-        f5_dec_sums(F.D, (int)blockIdx.x, (int)gridDim.x, tid, F5_THREADS);
-        F5_STAMP(12);
     }
 #ifdef PIML_F5_STAMPS
     if (lane == 0)

@@ -41,9 +41,7 @@ constexpr int DW2_RED = 8 * 128 * 9;                 // floats of the final dW1 
 static_assert(DW2_PART0 + DW2_PART1 == ENC_PART, "the two slot kinds partition a full slot");
 static_assert((DW2_RED + 4 * 128) * 4 <= DW2_LDS_BYTES, "final exchange fits");
 
-#ifndef PIML_DW2_DEPTH
-#define PIML_DW2_DEPTH 2
-#endif
+constexpr int DW2_DEPTH = 2;                         // batches in flight
 
 struct Dw2Args {
     EncArgs A;
@@ -306,7 +304,7 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_bwd_dw2_x3_kernel(Dw2Args D) 
         };
         // DEPTH batches ahead.  Measured at the 4096-agent scene (us, same box): depth 2: 39.6, 3: 41.2, 4: 41.5, 5: 44.8 -- the
         // bytes in flight are not what holds this kernel back (a deeper ring costs registers and moves instead).
-        constexpr int DEPTH = (POOL && MSGS) ? (DROP && H1R ? 1 : 2) : (DROP ? (PIML_DW2_DEPTH > 3 ? 3 : PIML_DW2_DEPTH) : PIML_DW2_DEPTH);      // (the g_msgs variant holds two arrays per batch; with keep bits and the recomputation on top, two batches in flight spilled 25 registers)
+        constexpr int DEPTH = (POOL && MSGS) ? (DROP && H1R ? 1 : 2) : (DROP ? (DW2_DEPTH > 3 ? 3 : DW2_DEPTH) : DW2_DEPTH);      // (the g_msgs variant holds two arrays per batch; with keep bits and the recomputation on top, two batches in flight spilled 25 registers)
         constexpr int UNROLL = (DEPTH % 2) ? 2 * DEPTH : DEPTH;
         Stage S[DEPTH];
         S[0] = stage_load(r0);

@@ -27,11 +27,9 @@ struct UnfoldSet {
     float* dw1_out;
     float* egrads;         // encoder `grads` (ENC_PART layout)
 };
+constexpr int REDUCE_SETS = 8;   // (the bottleneck variants leave 4 encoder + 2 row decoder + 1 head sets in one backward pass)
 struct ReduceAll {
-#ifndef PIML_REDUCE_SETS
-#define PIML_REDUCE_SETS 8       // (the bottleneck variants leave 4 encoder + 2 row decoder + 1 head sets in one backward pass)
-#endif
-    ReduceSet set[PIML_REDUCE_SETS];
+    ReduceSet set[REDUCE_SETS];
     int nsets;
     int accumulate;       // PIML_ACCUMULATE: grads += the sums
     int gx;               // workgroups per set (the widest set's (lanes + 15) / 16)

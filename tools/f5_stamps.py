@@ -7,7 +7,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np, torch
 from piml_amd import ops, _lib
 from test_sums_gpu import make_net, run
-NAMES = {15: 'prologue (once)', 0: 'barrier wait', 1: 'products + fills', 2: 'A: G1 mask + tile', 6: 'A: H1 mma + G2 | B: g_x', 7: 'A: H1 pieces', 5: 'A: stage + requests | B: dW1', 3: 'loop exit (once)', 4: 'B: last tile (once)', 11: 'epilogue (once)'}
+NAMES = {15: 'prologue (once)', 0: 'barrier wait', 1: 'products + fills', 2: 'A: G1 mask + tile', 6: 'A: H1 mma + G2 | B: dW1', 7: 'A: H1 pieces', 5: 'A: stage + requests', 3: 'loop exit (once)', 4: 'B: last tile (once)', 11: 'epilogue (once)'}
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 brs, sf, head, wa, g = make_net(n, (6, 10), True, seed=1)
 for _ in range(3):

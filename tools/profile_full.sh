@@ -35,8 +35,8 @@ cp $(ls $O/res/*/*kernel_stats.csv | head -1) $O/pinnsf_res_kernel_stats.csv; rm
 # the row decoder's many-rows kernels in both arithmetic forms
 cd $R
 for MODEL in pinnsf_m pinnsf_bm; do
-  FT_MODEL=$MODEL bash tools/r5_ft_trace.sh > /dev/null 2>&1; cp gpurun_out/r5ft/step.txt $O/finetune_step_${MODEL}.txt
-  MODEL=$MODEL P=0 bash tools/r6_pw_trace.sh > /dev/null 2>&1; cp gpurun_out/r6pw/step.txt $O/pointwise_step_${MODEL}.txt
+  OUT=$O/ftstep FT_MODEL=$MODEL bash tools/trace_finetune_step.sh > /dev/null 2>&1; cp $O/ftstep/step.txt $O/finetune_step_${MODEL}.txt; rm -rf $O/ftstep
+  OUT=$O/pwstep MODEL=$MODEL P=0 bash tools/trace_pointwise_step.sh > /dev/null 2>&1; cp $O/pwstep/step.txt $O/pointwise_step_${MODEL}.txt; rm -rf $O/pwstep
   python3 tools/time_finetune.py 100 $MODEL 2>&1 | grep fine-tune >> $O/time_finetune.log
 done
 bash tools/prof_script.sh tools/time_rowdec.py 2>&1 | grep rowdec > $O/time_rowdec.log
