@@ -75,12 +75,10 @@ int piml_encoder_dw2(int layer_split);
 /* One-pass backward above piml_encoder_split_tiles() tiles (piml_amd/csrc/encoder_bwd3.hip; reference: the autograd of
  * src/models/model.py:40-65 under :82-119): 1 (default) = where the layer-split weight gradients run, the forward left
  * `relu_mask` and the branches carry the same kinds of upstream gradients, the dX chain and dW2 / dW1 / db2 / db1 are ONE launch
- * that keeps the pre-activation gradients on the CU -- `g2` / `g1` are neither written nor read and may be NULL -- and dW3 /
- * db3 are the layer-0 workgroups of piml_encoder_dw2's kernel; 0 = the dX kernel writes g2 / g1 and the weight-gradient kernel
- * reads them back; 2 = the one-pass kernel as eight waves of 16-feature blocks (encoder_bwd4.hip, two waves per SIMD; measured
- * level with the four-wave form, kept for A/B).  In the one-pass forms dW3 / db3 are a second phase of the same launch
- * (PIML_ENC_FUSED_DW3=0: the layer-0 workgroups of piml_encoder_dw2's kernel in a launch of their own).  Environment at load
- * time: PIML_ENC_FUSED_BWD=0 / 1 / 2.  Returns the previous value; < 0 only queries. */
+ * that keeps the pre-activation gradients on the CU -- `g2` / `g1` are neither written nor read and may be NULL -- with dW3 /
+ * db3 as a second phase of the same launch; 0 = the dX kernel writes g2 / g1 and the weight-gradient kernel reads them back.
+ * Any other positive value means 1.  Environment at load time: PIML_ENC_FUSED_BWD=0 / 1.  Returns the previous value (0 / 1);
+ * < 0 only queries. */
 int piml_encoder_fused_bwd(int on);
 /* Backward of the sums path (PIML_POOL_TRAIN of piml_pinnsf_bwd; reference: the autograd of src/models/model.py:40-65 below
  * the neighbour-axis sum :1279-1283): 2 (default) = two crews of four waves per workgroup -- the dX chain and the weight-gradient

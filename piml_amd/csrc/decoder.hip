@@ -736,16 +736,6 @@ __global__ __launch_bounds__(512) void dec_bwd_dw_kernel(DecArgs A) {
     dec_bwd_dw_body<false>(A, b, (int)blockIdx.x - (b ? A.wg_split : 0), w, lane);
 }
 
-// dX chain and weight-gradient partials of a 32-agent tile in ONE launch: the dW slab of a workgroup is exactly the tile
-// whose g_pre2 / g_pre1 it has just written (visible to the whole workgroup after the barrier: one CU, one L1).
-__global__ __launch_bounds__(512) void dec_bwd_kernel(DecArgs A) {
-    dec_bwd_dx_body<false>(A, blockIdx.x);
-    __threadfence_block();
-    __syncthreads();
-    const int lane = threadIdx.x & 63, w = uniform((int)(threadIdx.x >> 6));
-    for (int b = 0; b < A.nbr; ++b) dec_bwd_dw_body<false>(A, b, (int)blockIdx.x, w, lane);
-}
-
 // ---- the same network per neighbour ROW (bottleneck variants): (tile, branch) workgroups, branches of different sizes ----
 __global__ __launch_bounds__(256) void rowdec_fwd_kernel(DecArgs A, int tiles0) {
     const int bx = blockIdx.x;
@@ -2048,9 +2038,7 @@ int piml::dec_stage_bwd_fused(const piml_decoder_branch* br, int nbr, const floa
     }
     static_assert(DEC_SLAB == 32, "the dW slab of a workgroup is its dX tile");
     const unsigned tiles = (unsigned)((br[0].agents + 31) / 32);
-    static const bool whole = getenv("PIML_DEC_BWD_SPLIT") && atoi(getenv("PIML_DEC_BWD_SPLIT")) == 0;     // A/B: the 8-wave form
-    if (whole && !sums) hipLaunchKernelGGL(dec_bwd_kernel, dim3(tiles), dim3(512), 0, s, A);
-    else hipLaunchKernelGGL(dec_bwd_split_kernel, dim3(tiles * (unsigned)nbr), dim3(256), 0, s, A);
+    hipLaunchKernelGGL(dec_bwd_split_kernel, dim3(tiles * (unsigned)nbr), dim3(256), 0, s, A);
     return hipGetLastError();
 }
 

@@ -905,14 +905,14 @@ PIML_API int piml_encoder_products(int x3) {
 }
 
 // One-pass backward (encoder_bwd3.hip): where the layer-split weight gradients run AND the forward left the sign bits AND the
-// branches carry the same kinds of upstream gradients, the dX chain and dW2 / dW1 / db2 / db1 are one launch that keeps g2 / g1
-// on the CU; dW3 / db3 stay with the layer-0 workgroups of encoder_dw2.hip, now all of them.  PIML_ENC_FUSED_BWD=0 keeps the
+// branches carry the same kinds of upstream gradients, the dX chain and every weight gradient (dW3 / db3 in the layer-0 slots,
+// dW2 / dW1 / db2 / db1 in the layer-1 slots) are one launch that keeps g2 / g1 on the CU.  PIML_ENC_FUSED_BWD=0 keeps the
 // two-kernel form (A/B).
-static int g_f3 = getenv("PIML_ENC_FUSED_BWD") ? (atoi(getenv("PIML_ENC_FUSED_BWD")) == 2 ? 2 : atoi(getenv("PIML_ENC_FUSED_BWD")) != 0) : 1;
+static int g_f3 = getenv("PIML_ENC_FUSED_BWD") ? atoi(getenv("PIML_ENC_FUSED_BWD")) != 0 : 1;
 
 PIML_API int piml_encoder_fused_bwd(int on) {
     const int old = g_f3;
-    if (on >= 0) g_f3 = on == 2 ? 2 : (on ? 1 : 0);
+    if (on >= 0) g_f3 = on != 0;
     return old;
 }
 
@@ -926,13 +926,7 @@ PIML_API int piml_encoder_sums_bwd(int form) {
     return old;
 }
 
-// PIML_ENC_FUSED_DW3=0: dW3 / db3 stay a launch of their own (the layer-0 workgroups of encoder_dw2.hip) behind the one-pass kernel
-static int g_f3_dw3 = !(getenv("PIML_ENC_FUSED_DW3") && atoi(getenv("PIML_ENC_FUSED_DW3")) == 0);
-
-// PIML_ENC_DX_SPLIT=f32: the few-rows dX chain on the f32 matrix instruction even with split products elsewhere (A/B)
-static const bool g_dx_split_f32 = getenv("PIML_ENC_DX_SPLIT") && getenv("PIML_ENC_DX_SPLIT")[0] == 'f';
-
-bool piml::enc_f32_images_needed() { return !g_x3 || g_dx_split_f32; }
+bool piml::enc_f32_images_needed() { return !g_x3; }
 
 // h1 may be absent (all branches) exactly when the backward runs without it: the dX chain on sign bits (relu_mask, more than
 // piml_encoder_split_tiles() tiles, split products) and the weight gradients on the layer-split kernel, which recomputes it
@@ -955,6 +949,15 @@ static int enc_bwd_check(const piml_encoder_branch* br, int nbr) {
     return hipSuccess;
 }
 
+// forward only, optional: a buffer the launch clears on the way.  A clear that cannot be honoured is an error, not a skip
+static int set_zero(EncArgs& A, float* zero, long long zero_n) {
+    if (!zero || zero_n <= 0) return hipSuccess;
+    if (zero_n >= (1ll << 31)) return hipErrorInvalidValue;
+    A.zero = zero;
+    A.zero_n = (int)zero_n;
+    return hipSuccess;
+}
+
 static int x3_ready() {
     static int state = -1;
     if (state < 0) state = enc_x3_set_attributes();
@@ -972,11 +975,7 @@ int piml::enc_stage_fwd(const piml_encoder_branch* br, int nbr, hipStream_t s, f
         if (int e = enc_set_lds(reinterpret_cast<const void*>(enc_fwd_kernel), FWD_LDS_FLOATS * 4)) return e;
         attr_set = true;
     }
-    if (zero && zero_n > 0) {
-        if (zero_n >= (1ll << 31)) return hipErrorInvalidValue;       // a clear that cannot be honoured is an error, not a skip
-        A.zero = zero;
-        A.zero_n = (int)zero_n;
-    }
+    if (int e = set_zero(A, zero, zero_n)) return e;
     // Train-mode dropout drawn by this call (piml_encoder_branch.drop_state): p = 0.5 on the split-product kernels inside the
     // forward kernel, everything else by one generator launch for all branches in front of it
     if (br[0].drop_state) {
@@ -1023,6 +1022,23 @@ int piml::enc_stage_fwd(const piml_encoder_branch* br, int nbr, hipStream_t s, f
     return hipGetLastError();
 }
 
+// What the three pooled forms below ask of their branches, once: split products, whole agents of k = 6 or 10 neighbours, an input
+// that fits the packed image, and what the caller adds (`extra`, per branch).  train: the forms a one-pass backward follows, which
+// also take k = 2 and whose 32-bit byte offsets into (rows, 128) arrays bound the rows.  Returns the branches' row tiles, or -1.
+template <class Extra>
+static long long pool_tiles(const piml_encoder_branch* br, int nbr, bool train, Extra extra) {
+    if (!g_x3 || !br || nbr < 1 || nbr > 2) return -1;
+    long long tiles = 0;
+    for (int i = 0; i < nbr; ++i) {
+        const piml_encoder_branch& b = br[i];
+        if ((b.k != 6 && b.k != 10 && !(train && b.k == 2)) || b.rows <= 0 || b.rows % b.k || b.in_dim < 1 || b.in_dim > 8 ||
+            (train && b.rows >= (1ll << 22)) || !extra(b))
+            return -1;
+        tiles += (b.rows + 31) / 32;
+    }
+    return tiles;
+}
+
 // The inference forward on pooled h2 serves: split products, no dropout, k = 6 or 10 neighbours per agent, whole agents, and
 // more than 32 tiles (PIML_POOL_H2_MIN_TILES).  It also replaces the few-rows forward (four waves per tile): half the matrix
 // work and no message rows weigh more than the shorter chains -- rollout frame 44 -> 40 us at 512 agents, 48 -> 42 at 1024,
@@ -1030,14 +1046,9 @@ int piml::enc_stage_fwd(const piml_encoder_branch* br, int nbr, hipStream_t s, f
 bool piml::enc_pool_h2_ok(const piml_encoder_branch* br, int nbr) {
     static const bool off = getenv("PIML_POOL_H2") && atoi(getenv("PIML_POOL_H2")) == 0;
     static const long long min_tiles = getenv("PIML_POOL_H2_MIN_TILES") ? atoll(getenv("PIML_POOL_H2_MIN_TILES")) : -1;
-    if (off || !g_x3 || !br || nbr < 1 || nbr > 2) return false;
-    long long tiles = 0;
-    for (int i = 0; i < nbr; ++i) {
-        const piml_encoder_branch& b = br[i];
-        if ((b.k != 6 && b.k != 10) || b.rows <= 0 || b.rows % b.k || b.keep_bits || b.drop_state || b.in_dim > 8) return false;
-        tiles += (b.rows + 31) / 32;
-    }
-    return tiles > (min_tiles >= 0 ? min_tiles : 32);
+    if (off) return false;
+    const long long tiles = pool_tiles(br, nbr, false, [](const piml_encoder_branch& b) { return !b.keep_bits && !b.drop_state; });
+    return tiles >= 0 && tiles > (min_tiles >= 0 ? min_tiles : 32);
 }
 
 int piml::enc_stage_fwd_pool(const piml_encoder_branch* br, int nbr, hipStream_t s, float* zero, long long zero_n) {
@@ -1047,11 +1058,7 @@ int piml::enc_stage_fwd_pool(const piml_encoder_branch* br, int nbr, hipStream_t
         if (!br[i].msgs || !br[i].h2) return hipErrorInvalidValue;
     EncArgs A;
     const int total = fill_args(A, br, nbr);
-    if (zero && zero_n > 0) {
-        if (zero_n >= (1ll << 31)) return hipErrorInvalidValue;
-        A.zero = zero;
-        A.zero_n = (int)zero_n;
-    }
+    if (int e = set_zero(A, zero, zero_n)) return e;
     if (int e = x3_ready()) return e;
     enc_x3_launch_fwd_pool(A, total, s);
     return hipGetLastError();
@@ -1061,17 +1068,13 @@ int piml::enc_stage_bwd_dx(const piml_encoder_branch* br, int nbr, hipStream_t s
     if (int e = enc_bwd_check(br, nbr)) return e;
     EncArgs A;
     const int total = fill_args(A, br, nbr);
-    if (enc_bwd_is_fused(br, nbr)) {          // dX chain + dW2 / dW1 / db2 / db1, one workgroup (four waves, one per SIMD) per CU
+    if (enc_bwd_is_fused(br, nbr)) {          // dX chain + every weight gradient, one workgroup (four waves, one per SIMD) per CU
         if (int e = x3_ready()) return e;
         static int ready = -1;
-        if (ready < 0) {
-            ready = enc_f3_set_attributes();
-            if (!ready) ready = enc_f4_set_attributes();
-        }
+        if (ready < 0) ready = enc_f3_set_attributes();
         if (ready) return ready;
         const int nA[2] = {nbr > 1 ? A.wg_split : total, nbr > 1 ? total - A.wg_split : 0};
-        if (g_f3 == 2) enc_f4_launch(A, nA, nA, g_f3_dw3 != 0, s);      // eight waves of 16-feature blocks (encoder_bwd4.hip)
-        else enc_f3_launch(A, nA, nA, g_f3_dw3 != 0, s);                // four waves of 32-feature blocks (encoder_bwd3.hip): the default
+        enc_f3_launch(A, nA, nA, true, s);          // with dW3 / db3: enc_stage_bwd_dw has nothing left to launch
         return hipGetLastError();
     }
     static bool attr_set = false;
@@ -1084,7 +1087,7 @@ int piml::enc_stage_bwd_dx(const piml_encoder_branch* br, int nbr, hipStream_t s
     // the backward form breaks even earlier than the forward, every wave rebuilding the whole g3.)
     if ((tiles[0] + tiles[1]) * 4 <= split_bound(br, nbr) * 3) {
         const int pairs0 = (int)((tiles[0] + 1) / 2), pairs1 = (int)((tiles[1] + 1) / 2);
-        if (g_x3 && !g_dx_split_f32) {
+        if (g_x3) {
             if (int e = x3_ready()) return e;
             enc_x3_launch_bwd_dx_split(A, pairs0, pairs1, br[0].keep_bits != nullptr, s);
             return hipGetLastError();
@@ -1116,12 +1119,16 @@ PIML_API int piml_encoder_dw2(int on) {
     return old;
 }
 
+// the kernel variant (which upstream gradients exist) is per launch: true where one launch can serve both branches
+static bool same_upstream(const piml_encoder_branch* br, int nbr) {
+    return nbr == 1 || ((br[0].g_pooled != nullptr) == (br[1].g_pooled != nullptr) && (br[0].g_msgs != nullptr) == (br[1].g_msgs != nullptr));
+}
+
 static bool enc_f3_used(const piml_encoder_branch* br, int nbr) {
-    if (!g_f3) return false;
+    if (!g_f3 || !same_upstream(br, nbr)) return false;
     for (int i = 0; i < nbr; ++i)
-        if (!br[i].relu_mask || (br[i].g_pooled != nullptr) != (br[0].g_pooled != nullptr) ||
-            (br[i].g_msgs != nullptr) != (br[0].g_msgs != nullptr) || (!br[i].g_pooled && !br[i].g_msgs) ||
-            (br[i].g_x != nullptr) != (br[0].g_x != nullptr) || br[i].rows >= (1ll << 22))      // (32-bit byte offsets into (rows, 128) arrays)
+        if (!br[i].relu_mask || (!br[i].g_pooled && !br[i].g_msgs) || (br[i].g_x != nullptr) != (br[0].g_x != nullptr) ||
+            br[i].rows >= (1ll << 22))      // (32-bit byte offsets into (rows, 128) arrays)
             return false;
     return true;
 }
@@ -1141,14 +1148,14 @@ bool piml::enc_dw2_used(const piml_encoder_branch* br, int nbr, int* n0, int* n1
         if (w[i] < 2) return false;
         int a, c;
         enc_dw2_split(w[i], &a, &c);
-        if (f3) a = c = w[i];        // every workgroup of the branch writes a layer-0 slot in one launch and a layer-1 slot in the other
+        if (f3) a = c = w[i];        // every workgroup of the one-pass launch writes a layer-0 slot and a layer-1 slot
         if (n0) n0[i] = a;
         if (n1) n1[i] = c;
     }
     return true;
 }
 
-// true: the backward of these branches is enc_f3_launch + the layer-0 half of enc_dw2_launch
+// true: the backward of these branches is enc_f3_launch alone
 static bool enc_bwd_is_fused(const piml_encoder_branch* br, int nbr) {
     return enc_dw2_used(br, nbr, nullptr, nullptr) && enc_f3_used(br, nbr);
 }
@@ -1157,54 +1164,39 @@ int piml::enc_stage_bwd_dw(const piml_encoder_branch* br, int nbr, hipStream_t s
     if (int e = enc_bwd_check(br, nbr)) return e;
     EncArgs A;
     const int total = fill_args(A, br, nbr);
-    if (enc_dw2_used(br, nbr, nullptr, nullptr)) {
+    const bool dw2 = enc_dw2_used(br, nbr, nullptr, nullptr);
+    if (dw2) {
         static int ready = -1;
         if (ready < 0) ready = enc_dw2_set_attributes();
         if (ready) return ready;
-        // the kernel variant (which upstream gradients exist) is per launch: branches that disagree are launched separately,
-        // each on its own workgroups and slots
-        if (enc_f3_used(br, nbr)) {                 // the lower layers' gradients came with the dX chain (enc_stage_bwd_dx)
-            if (!g_f3_dw3) enc_dw2_launch(A, total, s, true);        // (and dW3 / db3 too, unless PIML_ENC_FUSED_DW3=0)
-        } else if (nbr == 1 || ((br[0].g_pooled != nullptr) == (br[1].g_pooled != nullptr) && (br[0].g_msgs != nullptr) == (br[1].g_msgs != nullptr))) {
-            enc_dw2_launch(A, total, s);
-        } else {
-            for (int i = 0; i < 2; ++i) {
-                EncArgs B = A;
-                B.nbr = 1;
-                B.br[0] = B.br[1] = A.br[i];
-                enc_dw2_launch(B, i == 0 ? A.wg_split : total - A.wg_split, s);
-            }
+        if (enc_f3_used(br, nbr)) return hipGetLastError();          // every weight gradient came with the dX chain (enc_stage_bwd_dx)
+    } else {
+        static bool attr_set = false;
+        if (!attr_set) {
+            const void* dw[3] = {reinterpret_cast<const void*>(enc_bwd_dw_kernel<true, true>),
+                                 reinterpret_cast<const void*>(enc_bwd_dw_kernel<true, false>),
+                                 reinterpret_cast<const void*>(enc_bwd_dw_kernel<false, true>)};
+            for (const void* f : dw)
+                if (int e = enc_set_lds(f, DW_LDS_FLOATS * 4)) return e;
+            attr_set = true;
         }
-        return hipGetLastError();
-    }
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void* dw[3] = {reinterpret_cast<const void*>(enc_bwd_dw_kernel<true, true>),
-                             reinterpret_cast<const void*>(enc_bwd_dw_kernel<true, false>),
-                             reinterpret_cast<const void*>(enc_bwd_dw_kernel<false, true>)};
-        for (const void* f : dw)
-            if (int e = enc_set_lds(f, DW_LDS_FLOATS * 4)) return e;
-        attr_set = true;
-    }
-    if (g_x3)
-        if (int e = x3_ready()) return e;
-    if (g_x3) {
-        static int wide_ready = -1;
-        if (wide_ready < 0) wide_ready = enc_dww_set_attributes();
-        if (wide_ready) return wide_ready;
+        if (g_x3) {
+            if (int e = x3_ready()) return e;
+            static int wide_ready = -1;
+            if (wide_ready < 0) wide_ready = enc_dww_set_attributes();
+            if (wide_ready) return wide_ready;
+        }
     }
     auto launch_dw = [&](const EncArgs& B, int grid) {
+        if (dw2) return enc_dw2_launch(B, grid, s);
         if (g_x3) return enc_dww_launch(B, grid, B.br[0].keep_bits != nullptr, s);
         const bool pool = B.br[0].g_pooled != nullptr, msgs = B.br[0].g_msgs != nullptr;
         if (pool && msgs) hipLaunchKernelGGL((enc_bwd_dw_kernel<true, true>), dim3(grid), dim3(ENC_THREADS), DW_LDS_FLOATS * 4, s, B);
         else if (pool) hipLaunchKernelGGL((enc_bwd_dw_kernel<true, false>), dim3(grid), dim3(ENC_THREADS), DW_LDS_FLOATS * 4, s, B);
         else hipLaunchKernelGGL((enc_bwd_dw_kernel<false, true>), dim3(grid), dim3(ENC_THREADS), DW_LDS_FLOATS * 4, s, B);
     };
-    // the kernel variant (which upstream gradients exist) is per launch: branches that disagree are launched
-    // separately, each on its own share of the partial slots
-    const bool same = nbr == 1 || ((br[0].g_pooled != nullptr) == (br[1].g_pooled != nullptr) &&
-                                   (br[0].g_msgs != nullptr) == (br[1].g_msgs != nullptr));
-    if (same) {
+    // branches that disagree are launched separately, each on its own share of the workgroups and partial slots
+    if (same_upstream(br, nbr)) {
         launch_dw(A, total);
     } else {
         for (int i = 0; i < 2; ++i) {
@@ -1260,16 +1252,9 @@ int piml::enc_stage_reduce(const piml_encoder_branch* br, int nbr, hipStream_t s
 // neighbours per agent, whole agents, no dropout mask.  PIML_POOL_TRAIN=0 in the environment turns it off (A/B).
 bool piml::enc_pool_train_ok(const piml_encoder_branch* br, int nbr) {
     static const bool off = getenv("PIML_POOL_TRAIN") && atoi(getenv("PIML_POOL_TRAIN")) == 0;
-    if (off || !g_x3 || !g_dw2 || g_f3 != 1 || !br || nbr < 1 || nbr > 2) return false;
-    long long tiles = 0;
-    for (int i = 0; i < nbr; ++i) {
-        const piml_encoder_branch& b = br[i];
-        if ((b.k != 2 && b.k != 6 && b.k != 10) || b.rows <= 0 || b.rows % b.k || b.keep_bits || b.drop_state || b.in_dim < 1 || b.in_dim > 8 ||
-            b.rows >= (1ll << 22))
-            return false;
-        tiles += (b.rows + 31) / 32;
-    }
-    if (tiles <= g_split_tiles_train) return false;
+    if (off || !g_dw2 || g_f3 != 1) return false;
+    const long long tiles = pool_tiles(br, nbr, true, [](const piml_encoder_branch& b) { return !b.keep_bits && !b.drop_state; });
+    if (tiles < 0 || tiles <= g_split_tiles_train) return false;
     const int total = 256, w0 = split_workgroups(br, nbr, total, 1);
     return nbr == 1 || (w0 >= 2 && total - w0 >= 2);
 }
@@ -1280,16 +1265,9 @@ bool piml::enc_pool_train_ok(const piml_encoder_branch* br, int nbr) {
 // PIML_POOL_MSGS=0 in the environment turns it off (A/B).
 bool piml::enc_pool_msgs_ok(const piml_encoder_branch* br, int nbr) {
     static const bool off = getenv("PIML_POOL_MSGS") && atoi(getenv("PIML_POOL_MSGS")) == 0;
-    if (off || !g_x3 || !br || nbr < 1 || nbr > 2) return false;
-    long long tiles = 0;
-    for (int i = 0; i < nbr; ++i) {
-        const piml_encoder_branch& b = br[i];
-        if ((b.k != 2 && b.k != 6 && b.k != 10) || b.rows <= 0 || b.rows % b.k || !b.relu_mask || b.in_dim < 1 || b.in_dim > 8 ||
-            b.rows >= (1ll << 22))
-            return false;
-        tiles += (b.rows + 31) / 32;
-    }
-    return tiles > g_split_tiles_train;
+    if (off) return false;
+    const long long tiles = pool_tiles(br, nbr, true, [](const piml_encoder_branch& b) { return b.relu_mask != nullptr; });
+    return tiles >= 0 && tiles > g_split_tiles_train;
 }
 
 int piml::enc_stage_fwd_sum(const piml_encoder_branch* br, int nbr, hipStream_t s, float* zero, long long zero_n) {
@@ -1299,11 +1277,7 @@ int piml::enc_stage_fwd_sum(const piml_encoder_branch* br, int nbr, hipStream_t 
         if (!br[i].sum_a || !br[i].sum_b || !br[i].relu_mask) return hipErrorInvalidValue;
     EncArgs A;
     const int total = fill_args(A, br, nbr);
-    if (zero && zero_n > 0) {
-        if (zero_n >= (1ll << 31)) return hipErrorInvalidValue;
-        A.zero = zero;
-        A.zero_n = (int)zero_n;
-    }
+    if (int e = set_zero(A, zero, zero_n)) return e;
     if (int e = x3_ready()) return e;
     enc_x3_launch_fwd_sum(A, total, s);
     return hipGetLastError();

@@ -126,9 +126,9 @@ def test_tuning_file_is_consistent():
 
 
 def test_no_kernel_of_the_default_dispatch_spills():
-    """Register / scratch figures straight from the code objects inside libpiml_hip.so (`_lib.kernel_resource_usage`): the only
-    kernels with a non-zero spill count are the two A/B forms the default dispatch never launches (profiles/r05_kernel_usage.md:
-    `PIML_DEC_BWD_SPLIT=0`, `PIML_ENC_FUSED_BWD=2`)."""
+    """Register / scratch figures straight from the code objects inside libpiml_hip.so (`_lib.kernel_resource_usage`): no kernel
+    of the library has a non-zero spill count.  (The two that had one were A/B forms no dispatch reached; they are retired:
+    DESIGN.md 9.)"""
     pytest.importorskip('msgpack')          # (the code objects' metadata notes are msgpack; not a dependency of the package itself)
     from piml_amd import _lib
     usage = _lib.kernel_resource_usage()
@@ -140,7 +140,7 @@ def test_no_kernel_of_the_default_dispatch_spills():
                  'pinnsf_unfold_kernel',
                  'dec_fwd_head_kernel<true>', 'dec_bwd_split_kernel', 'relfeat_bwd_reduce_kernel', 'mlapm_bwd_sys_kernel<1>'):
         assert name in usage, name
-    not_reached = {'dec_bwd_kernel', 'enc_bwd_fused8_x3_kernel<true, true, true, false>'}
+    not_reached = set()
     # (scalar registers parked in lanes of a vector register -- `sgpr_spill`, no memory traffic -- are not counted)
     spilling = {k: v['vgpr_spill'] for k, v in usage.items() if v['vgpr_spill']}
     assert set(spilling) <= not_reached, spilling
