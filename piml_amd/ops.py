@@ -4,6 +4,8 @@ PyTorch is plumbing here: it owns device memory and the stream, and autograd.Fun
 the forward/backward kernels into the reference's training loops.  Every operator requires
 float32 tensors on the GPU and raises otherwise (no CPU fallback).
 """
+import collections
+import ctypes
 import math
 
 import torch
@@ -56,49 +58,99 @@ def heading_direction(velocity):
     return out
 
 
-def _launch_relfeat_fwd(p_ptr, v_ptr, a_ptr, ld, hd, dest_rows, o, lead, C, N, f0, fcnt, kp, ko,
-                        cos_p, cos_o, dthr_p, dthr_o, device, outs=None, dest_ld=2, tick=None):
+RelGeom = collections.namedtuple('RelGeom', 'kp ko cos_p cos_o dthr_p dthr_o')    # top-k, view-cone cosine, distance bound: pedestrians / obstacles
+
+
+def _rel_geom(topk_ped, sight_angle_ped, dist_threshold_ped, topk_obs, sight_angle_obs, dist_threshold_obs):
+    """The RelGeom of the public wrappers' six geometry keywords."""
+    if topk_ped > MAX_TOPK or topk_obs > MAX_TOPK:
+        raise ValueError(f'topk must be <= {MAX_TOPK}')
+    return RelGeom(int(topk_ped), int(topk_obs), cos_threshold(sight_angle_ped), cos_threshold(sight_angle_obs),
+                   float(dist_threshold_ped), float(dist_threshold_obs))
+
+
+_FEAT_DTYPES = (torch.float32,) * 3 + (torch.int32,) * 2
+
+
+def _feat_shapes(lead, n, kpe, koe, width):
+    """Shapes of (ped_feat, obs_feat, third, ped_idx, obs_idx) for n focal rows; third = dest_features (width 2) or self_features (7)."""
+    return (*lead, n, kpe, 6), (*lead, n, koe, 6), (*lead, n, width), (*lead, n, kpe), (*lead, n, koe)
+
+
+def _alloc_feats(lead, n, kpe, koe, width, device):
+    return tuple(torch.empty(s, device=device, dtype=dt) for s, dt in zip(_feat_shapes(lead, n, kpe, koe, width), _FEAT_DTYPES))
+
+
+def _fresh_zeros(shape, device):
+    return torch.zeros(shape, device=device, dtype=torch.float32)
+
+
+def _dense(grads, shapes, device, zeros):
+    """Upstream gradients with the ones that did not arrive as zeros(shape, device): _fresh_zeros (a fill launch each), or
+    _zeros_ro inside captured training graphs, whose persistent read-only zeros save that launch per frame."""
+    return [zeros(s, device) if g is None else _gpu_f32('grad', g) for g, s in zip(grads, shapes)]
+
+
+def _separate_state(position, velocity, acceleration, destination):
+    """The separate layout, four (..., N, 2) tensors -> (p, v, a, d coerced, N, lead, C)."""
+    p, v, a, d = [_gpu_f32(n, x) for n, x in (('position', position), ('velocity', velocity),
+                                              ('acceleration', acceleration), ('destination', destination))]
+    if not (p.shape == v.shape == a.shape == d.shape) or p.shape[-1] != 2 or p.dim() < 2:
+        raise ValueError(f'position/velocity/acceleration/destination must share a (..., N, 2) shape, got '
+                         f'{tuple(p.shape)} {tuple(v.shape)} {tuple(a.shape)} {tuple(d.shape)}')
+    N = p.shape[-2]
+    return p, v, a, d, N, tuple(p.shape[:-2]), p.numel() // max(N * 2, 1)
+
+
+def _packed_state(state, destination_rows, focal_count, flat=False):
+    """The packed layout, (..., N, 6) = (p, v, a) records ((N, 6) alone with `flat`) + the focal rows' destinations
+    -> (state, destination_rows coerced, N, lead, C)."""
+    s = _gpu_f32('state', state)
+    d_rows = _gpu_f32('destination_rows', destination_rows)
+    if s.shape[-1] != 6 or (s.dim() != 2 if flat else s.dim() < 2):
+        raise ValueError(f'state must be {"(N, 6)" if flat else "(..., N, 6)"}, got {tuple(s.shape)}')
+    N = s.shape[-2]
+    lead = tuple(s.shape[:-2])
+    if tuple(d_rows.shape) != (*lead, focal_count, 2):
+        raise ValueError(f'destination_rows must be {(*lead, focal_count, 2)}, got {tuple(d_rows.shape)}')
+    return s, d_rows, N, lead, s.numel() // max(N * 6, 1)
+
+
+def _focal_speed(desired_speed, focal_count):
+    w = _gpu_f32('desired_speed', desired_speed)
+    if w.numel() != focal_count:
+        raise ValueError('destination_rows (n, 2) and desired_speed (n, 1) expected for the focal rows')
+    return w
+
+
+def _launch_relfeat_fwd(p_ptr, v_ptr, a_ptr, ld, hd, dest_rows, o, lead, C, N, f0, fcnt, geo, device,
+                        outs=None, dest_ld=2, tick=None):
     M = o.shape[0]
-    kpe, koe = min(kp, N), min(ko, M)
+    kpe, koe = min(geo.kp, N), min(geo.ko, M)
     if outs is None:
-        opt = dict(device=device, dtype=torch.float32)
-        ped_feat = torch.empty(*lead, fcnt, kpe, 6, **opt)
-        obs_feat = torch.empty(*lead, fcnt, koe, 6, **opt)
-        dest_feat = torch.empty(*lead, fcnt, 2, **opt)
-        ped_idx = torch.empty(*lead, fcnt, kpe, device=device, dtype=torch.int32)
-        obs_idx = torch.empty(*lead, fcnt, koe, device=device, dtype=torch.int32)
+        outs = _alloc_feats(lead, fcnt, kpe, koe, 2, device)
     else:
-        ped_feat, obs_feat, dest_feat, ped_idx, obs_idx = outs
-        want = ((*lead, fcnt, kpe, 6), (*lead, fcnt, koe, 6), (*lead, fcnt, dest_ld), (*lead, fcnt, kpe), (*lead, fcnt, koe))
-        for t, shp, dt in zip(outs, want, (torch.float32,) * 3 + (torch.int32,) * 2):
+        for t, shp, dt in zip(outs, _feat_shapes(lead, fcnt, kpe, koe, dest_ld), _FEAT_DTYPES):
             if tuple(t.shape) != shp or t.dtype != dt or not t.is_contiguous() or t.device != device:
                 raise ValueError(f'output buffer mismatch: expected {shp} {dt}, got {tuple(t.shape)} {t.dtype}')
+    ped_feat, obs_feat, dest_feat, ped_idx, obs_idx = outs
+    args = (p_ptr, _ptr(hd), v_ptr, a_ptr, ld, _ptr(dest_rows), _ptr(o), C, N, M, f0, fcnt, *geo,
+            _ptr(ped_feat), _ptr(obs_feat), _ptr(dest_feat), dest_ld, _ptr(ped_idx), _ptr(obs_idx))
     with torch.cuda.device(device):
         if tick is not None:
             if tick.dtype != torch.int64 or tick.numel() != 1 or tick.device != device:
                 raise ValueError('tick: a one-element int64 tensor on the same device expected')
-            _lib.check(_lib.lib().piml_relfeat_fwd_tick(
-                p_ptr, _ptr(hd), v_ptr, a_ptr, ld, _ptr(dest_rows), _ptr(o), C, N, M, f0, fcnt,
-                kp, ko, cos_p, cos_o, dthr_p, dthr_o, _ptr(ped_feat), _ptr(obs_feat), _ptr(dest_feat), dest_ld,
-                _ptr(ped_idx), _ptr(obs_idx), _ptr(tick), _stream()), 'piml_relfeat_fwd_tick')
-            return ped_feat, obs_feat, dest_feat, ped_idx, obs_idx
-        _lib.check(_lib.lib().piml_relfeat_fwd(
-            p_ptr, _ptr(hd), v_ptr, a_ptr, ld, _ptr(dest_rows), _ptr(o), C, N, M, f0, fcnt,
-            kp, ko, cos_p, cos_o, dthr_p, dthr_o, _ptr(ped_feat), _ptr(obs_feat), _ptr(dest_feat), dest_ld,
-            _ptr(ped_idx), _ptr(obs_idx), _stream()), 'piml_relfeat_fwd')
-    return ped_feat, obs_feat, dest_feat, ped_idx, obs_idx
+            _lib.check(_lib.lib().piml_relfeat_fwd_tick(*args, _ptr(tick), _stream()), 'piml_relfeat_fwd_tick')
+        else:
+            _lib.check(_lib.lib().piml_relfeat_fwd(*args, _stream()), 'piml_relfeat_fwd')
+    return outs
 
 
 def _launch_relfeat_bwd(ctx_geom, g_ped, g_obs, g_dest, ped_idx, obs_idx, p_ptr, ld, dest_rows, device,
                         g_state=None):
     """`g_state` given: the kernel accumulates into it (all its writes are atomic adds)."""
     C, N, f0, fcnt, kpe, koe, lead = ctx_geom
-
-    def dense(g, shape):
-        return torch.zeros(shape, device=device, dtype=torch.float32) if g is None else _gpu_f32('grad', g)
-    g_ped = dense(g_ped, (*lead, fcnt, kpe, 6))
-    g_obs = dense(g_obs, (*lead, fcnt, koe, 6))
-    g_dest = dense(g_dest, (*lead, fcnt, 2))
+    g_ped, g_obs, g_dest = _dense((g_ped, g_obs, g_dest), _feat_shapes(lead, fcnt, kpe, koe, 2), device, _fresh_zeros)
     if g_state is None and not DETERMINISTIC_BWD:
         g_state = torch.zeros(*lead, N, 6, device=device, dtype=torch.float32)
     g_dest_rows = torch.empty(*lead, fcnt, 2, device=device, dtype=torch.float32)
@@ -124,29 +176,46 @@ def _launch_relfeat_bwd(ctx_geom, g_ped, g_obs, g_dest, ped_idx, obs_idx, p_ptr,
     return g_state, g_dest_rows
 
 
+def _relfeat_self_fwd(p, v, a, d, o, v0, lead, C, N, geo, g_state):
+    """piml_relfeat_fwd_self over all N rows of separate (*lead, N, 2) tensors -> (ped_feat, obs_feat, self_features (*lead, N, 7),
+    ped_idx, obs_idx); the same launch clears `g_state` (*lead, N, 6) when one is given."""
+    M = o.shape[0]
+    outs = _alloc_feats(lead, N, min(geo.kp, N), min(geo.ko, M), 7, p.device)
+    with torch.cuda.device(p.device):
+        _lib.check(_lib.lib().piml_relfeat_fwd_self(
+            _ptr(p), None, _ptr(v), _ptr(a), 2, _ptr(d), _ptr(o), _ptr(v0), C, N, M, 0, N, *geo,
+            *[_ptr(x) for x in outs], _ptr(g_state), _stream()), 'piml_relfeat_fwd_self')
+    return outs
+
+
+def _relfeat_self_bwd(grads, pi, oi, p, d, lead, C, N, g_state, g_speed, zeros):
+    """piml_relfeat_bwd_self: `grads` = (g_ped, g_obs, g_self), missing ones from `zeros` (_dense); accumulates into the cleared
+    `g_state` (None: a fresh one is cleared here) -> (g_state (*lead, N, 6), g_destination)."""
+    kpe, koe = pi.shape[-1], oi.shape[-1]
+    g_ped, g_obs, g_self = _dense(grads, _feat_shapes(lead, N, kpe, koe, 7), p.device, zeros)
+    if g_state is None:
+        g_state = _fresh_zeros((*lead, N, 6), p.device)
+    g_dest = torch.empty(*lead, N, 2, device=p.device, dtype=torch.float32)
+    with torch.cuda.device(p.device):
+        _lib.check(_lib.lib().piml_relfeat_bwd_self(
+            _ptr(g_ped), _ptr(g_obs), _ptr(g_self), _ptr(pi), _ptr(oi), _ptr(p), 2, _ptr(d), C, N, 0, N, kpe, koe,
+            _ptr(g_state), _ptr(g_dest), _ptr(g_speed), _stream()), 'piml_relfeat_bwd_self')
+    return g_state, g_dest
+
+
 class _RelativeFeatures(torch.autograd.Function):
     """Separate (..., N, 2) position / velocity / acceleration / destination tensors."""
 
     @staticmethod
-    def forward(ctx, position, velocity, acceleration, destination, obstacles, heading,
-                focal_begin, focal_count, kp, ko, cos_p, cos_o, dthr_p, dthr_o):
-        p = _gpu_f32('position', position)
-        v = _gpu_f32('velocity', velocity)
-        a = _gpu_f32('acceleration', acceleration)
-        d = _gpu_f32('destination', destination)
+    def forward(ctx, position, velocity, acceleration, destination, obstacles, heading, focal_begin, focal_count, geo):
+        p, v, a, d, N, lead, C = _separate_state(position, velocity, acceleration, destination)
         o = _gpu_f32('obstacles', obstacles).reshape(-1, 2)
-        if not (p.shape == v.shape == a.shape == d.shape) or p.shape[-1] != 2 or p.dim() < 2:
-            raise ValueError(f'position/velocity/acceleration/destination must share a (..., N, 2) shape, got '
-                             f'{tuple(p.shape)} {tuple(v.shape)} {tuple(a.shape)} {tuple(d.shape)}')
-        N = p.shape[-2]
-        lead = tuple(p.shape[:-2])
-        C = p.numel() // max(N * 2, 1)
         if focal_count is None:
             focal_begin, focal_count = 0, N
         hd = None if heading is None else _gpu_f32('heading', heading)
         d_rows = d if focal_count == N else d[..., focal_begin:focal_begin + focal_count, :].contiguous()
         out = _launch_relfeat_fwd(_ptr(p), _ptr(v), _ptr(a), 2, hd, d_rows, o, lead, C, N, focal_begin,
-                                  focal_count, kp, ko, cos_p, cos_o, dthr_p, dthr_o, p.device)
+                                  focal_count, geo, p.device)
         ctx.save_for_backward(out[3], out[4], p, d_rows)
         ctx.geom = (C, N, focal_begin, focal_count, out[3].shape[-1], out[4].shape[-1], lead)
         ctx.mark_non_differentiable(out[3], out[4])
@@ -156,7 +225,7 @@ class _RelativeFeatures(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_ped, g_obs, g_dest, _gi, _go):
         if g_ped is None and g_obs is None and g_dest is None:
-            return (None,) * 14
+            return (None,) * 9
         ped_idx, obs_idx, p, d_rows = ctx.saved_tensors
         C, N, f0, fcnt, kpe, koe, lead = ctx.geom
         g_state, g_d_rows = _launch_relfeat_bwd(ctx.geom, g_ped, g_obs, g_dest, ped_idx, obs_idx,
@@ -166,7 +235,7 @@ class _RelativeFeatures(torch.autograd.Function):
         else:
             g_destination = torch.zeros(*lead, N, 2, device=p.device, dtype=torch.float32)
             g_destination[..., f0:f0 + fcnt, :] = g_d_rows
-        return (g_state[..., 0:2], g_state[..., 2:4], g_state[..., 4:6], g_destination) + (None,) * 10
+        return (g_state[..., 0:2], g_state[..., 2:4], g_state[..., 4:6], g_destination) + (None,) * 5
 
 
 class _RelativeFeaturesSelf(torch.autograd.Function):
@@ -174,56 +243,28 @@ class _RelativeFeaturesSelf(torch.autograd.Function):
     (piml_relfeat_fwd_self / piml_relfeat_bwd_self): the training rollout's per-frame torch.cat inside the launch."""
 
     @staticmethod
-    def forward(ctx, position, velocity, acceleration, destination, obstacles, desired_speed, kp, ko, cos_p, cos_o, dthr_p, dthr_o):
-        p = _gpu_f32('position', position)
-        v = _gpu_f32('velocity', velocity)
-        a = _gpu_f32('acceleration', acceleration)
-        d = _gpu_f32('destination', destination)
+    def forward(ctx, position, velocity, acceleration, destination, obstacles, desired_speed, geo):
+        p, v, a, d, N, lead, C = _separate_state(position, velocity, acceleration, destination)
         o = _gpu_f32('obstacles', obstacles).reshape(-1, 2)
-        if not (p.shape == v.shape == a.shape == d.shape) or p.shape[-1] != 2 or p.dim() < 2:
-            raise ValueError('position/velocity/acceleration/destination must share a (..., N, 2) shape')
-        N = p.shape[-2]
-        lead = tuple(p.shape[:-2])
-        C = p.numel() // max(N * 2, 1)
         v0 = _gpu_f32('desired_speed', desired_speed)
         if v0.numel() != C * N:
             raise ValueError(f'desired_speed must hold one value per agent, got {tuple(v0.shape)}')
-        M = o.shape[0]
-        kpe, koe = min(kp, N), min(ko, M)
-        opt = dict(device=p.device, dtype=torch.float32)
-        pf, of = torch.empty(*lead, N, kpe, 6, **opt), torch.empty(*lead, N, koe, 6, **opt)
-        sf = torch.empty(*lead, N, 7, **opt)
-        pi = torch.empty(*lead, N, kpe, device=p.device, dtype=torch.int32)
-        oi = torch.empty(*lead, N, koe, device=p.device, dtype=torch.int32)
-        with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().piml_relfeat_fwd_self(
-                _ptr(p), None, _ptr(v), _ptr(a), 2, _ptr(d), _ptr(o), _ptr(v0), C, N, M, 0, N, kp, ko, cos_p, cos_o, dthr_p, dthr_o,
-                _ptr(pf), _ptr(of), _ptr(sf), _ptr(pi), _ptr(oi), None, _stream()), 'piml_relfeat_fwd_self')
-        ctx.save_for_backward(pi, oi, p, d)
-        ctx.geom = (C, N, kpe, koe, lead, tuple(desired_speed.shape))
-        ctx.mark_non_differentiable(pi, oi)
+        outs = _relfeat_self_fwd(p, v, a, d, o, v0, lead, C, N, geo, None)
+        ctx.save_for_backward(outs[3], outs[4], p, d)
+        ctx.geom = (C, N, lead, tuple(desired_speed.shape))
+        ctx.mark_non_differentiable(outs[3], outs[4])
         ctx.set_materialize_grads(False)
-        return pf, of, sf, pi, oi
+        return outs
 
     @staticmethod
     def backward(ctx, g_ped, g_obs, g_self, _gi, _go):
         if g_ped is None and g_obs is None and g_self is None:
-            return (None,) * 12
+            return (None,) * 7
         pi, oi, p, d = ctx.saved_tensors
-        C, N, kpe, koe, lead, speed_shape = ctx.geom
-        opt = dict(device=p.device, dtype=torch.float32)
-
-        def dense(g, shape):
-            return torch.zeros(shape, **opt) if g is None else _gpu_f32('grad', g)
-        g_ped, g_obs, g_self = dense(g_ped, (*lead, N, kpe, 6)), dense(g_obs, (*lead, N, koe, 6)), dense(g_self, (*lead, N, 7))
-        g_state = torch.zeros(*lead, N, 6, **opt)
-        g_dest = torch.empty(*lead, N, 2, **opt)
-        g_speed = torch.empty(speed_shape, **opt) if ctx.needs_input_grad[5] else None
-        with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().piml_relfeat_bwd_self(
-                _ptr(g_ped), _ptr(g_obs), _ptr(g_self), _ptr(pi), _ptr(oi), _ptr(p), 2, _ptr(d), C, N, 0, N, kpe, koe,
-                _ptr(g_state), _ptr(g_dest), _ptr(g_speed), _stream()), 'piml_relfeat_bwd_self')
-        return (g_state[..., 0:2], g_state[..., 2:4], g_state[..., 4:6], g_dest, None, g_speed) + (None,) * 6
+        C, N, lead, speed_shape = ctx.geom
+        g_speed = torch.empty(speed_shape, device=p.device, dtype=torch.float32) if ctx.needs_input_grad[5] else None
+        g_state, g_dest = _relfeat_self_bwd((g_ped, g_obs, g_self), pi, oi, p, d, lead, C, N, None, g_speed, _fresh_zeros)
+        return (g_state[..., 0:2], g_state[..., 2:4], g_state[..., 4:6], g_dest, None, g_speed, None)
 
 
 class _RelativeFeaturesPacked(torch.autograd.Function):
@@ -231,21 +272,12 @@ class _RelativeFeaturesPacked(torch.autograd.Function):
     agent-block sharding) + destinations of the focal rows only."""
 
     @staticmethod
-    def forward(ctx, state, destination_rows, obstacles, focal_begin, focal_count, kp, ko,
-                cos_p, cos_o, dthr_p, dthr_o):
-        s = _gpu_f32('state', state)
-        d_rows = _gpu_f32('destination_rows', destination_rows)
+    def forward(ctx, state, destination_rows, obstacles, focal_begin, focal_count, geo):
+        s, d_rows, N, lead, C = _packed_state(state, destination_rows, focal_count)
         o = _gpu_f32('obstacles', obstacles).reshape(-1, 2)
-        if s.shape[-1] != 6 or s.dim() < 2:
-            raise ValueError(f'state must be (..., N, 6), got {tuple(s.shape)}')
-        N = s.shape[-2]
-        lead = tuple(s.shape[:-2])
-        if tuple(d_rows.shape) != (*lead, focal_count, 2):
-            raise ValueError(f'destination_rows must be {(*lead, focal_count, 2)}, got {tuple(d_rows.shape)}')
-        C = s.numel() // max(N * 6, 1)
         base = s.data_ptr()
         out = _launch_relfeat_fwd(base, base + 8, base + 16, 6, None, d_rows, o, lead, C, N, focal_begin,
-                                  focal_count, kp, ko, cos_p, cos_o, dthr_p, dthr_o, s.device)
+                                  focal_count, geo, s.device)
         ctx.save_for_backward(out[3], out[4], s, d_rows)
         ctx.geom = (C, N, focal_begin, focal_count, out[3].shape[-1], out[4].shape[-1], lead)
         ctx.mark_non_differentiable(out[3], out[4])
@@ -255,11 +287,11 @@ class _RelativeFeaturesPacked(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_ped, g_obs, g_dest, _gi, _go):
         if g_ped is None and g_obs is None and g_dest is None:
-            return (None,) * 11
+            return (None,) * 6
         ped_idx, obs_idx, s, d_rows = ctx.saved_tensors
         g_state, g_d_rows = _launch_relfeat_bwd(ctx.geom, g_ped, g_obs, g_dest, ped_idx, obs_idx,
                                                 s.data_ptr(), 6, d_rows, s.device)
-        return (g_state, g_d_rows) + (None,) * 9
+        return (g_state, g_d_rows) + (None,) * 4
 
 
 class _RelativeFeaturesPackedSelf(torch.autograd.Function):
@@ -269,44 +301,30 @@ class _RelativeFeaturesPackedSelf(torch.autograd.Function):
     (piml_relfeat_self_bwd: scatter + the rows' own terms + the self-feature columns) accumulates into."""
 
     @staticmethod
-    def forward(ctx, state, destination_rows, obstacles, desired_speed, focal_begin, focal_count, kp, ko,
-                cos_p, cos_o, dthr_p, dthr_o, local=None):
-        s = _gpu_f32('state', state)
-        d_rows = _gpu_f32('destination_rows', destination_rows)
+    def forward(ctx, state, destination_rows, obstacles, desired_speed, focal_begin, focal_count, geo, local=None):
+        s, d_rows, N, _, _ = _packed_state(state, destination_rows, focal_count, flat=True)
         o = _gpu_f32('obstacles', obstacles).reshape(-1, 2)
-        w = _gpu_f32('desired_speed', desired_speed)
-        if s.dim() != 2 or s.shape[-1] != 6:
-            raise ValueError(f'state must be (N, 6), got {tuple(s.shape)}')
-        N = s.shape[0]
-        if tuple(d_rows.shape) != (focal_count, 2) or w.numel() != focal_count:
-            raise ValueError('destination_rows (n, 2) and desired_speed (n, 1) expected for the focal rows')
+        w = _focal_speed(desired_speed, focal_count)
         M = o.shape[0]
-        kpe, koe = min(kp, N), min(ko, M)
-        opt = dict(device=s.device, dtype=torch.float32)
+        kpe, koe = min(geo.kp, N), min(geo.ko, M)
         need_grad = any(ctx.needs_input_grad[:4]) and not DETERMINISTIC_BWD
         if local is None:
-            sf = torch.empty(focal_count, 7, **opt)
-            outs = (torch.empty(focal_count, kpe, 6, **opt), torch.empty(focal_count, koe, 6, **opt), sf,
-                    torch.empty(focal_count, kpe, device=s.device, dtype=torch.int32),
-                    torch.empty(focal_count, koe, device=s.device, dtype=torch.int32))
-            ctx.g_state = torch.empty(N, 6, **opt) if need_grad else None       # cleared by the launch below
+            outs = _alloc_feats((), focal_count, kpe, koe, 7, s.device)
+            ctx.g_state = torch.empty(N, 6, device=s.device, dtype=torch.float32) if need_grad else None   # cleared by the launch below
             with torch.cuda.device(s.device):
                 _lib.check(_lib.lib().piml_relfeat_self_fwd(
-                    _ptr(s), _ptr(d_rows), _ptr(o), _ptr(w), N, M, focal_begin, focal_count, kp, ko, cos_p, cos_o,
-                    dthr_p, dthr_o, _ptr(outs[0]), _ptr(outs[1]), _ptr(sf), _ptr(outs[3]), _ptr(outs[4]),
-                    _ptr(ctx.g_state), _stream()), 'piml_relfeat_self_fwd')
+                    _ptr(s), _ptr(d_rows), _ptr(o), _ptr(w), N, M, focal_begin, focal_count, *geo,
+                    *[_ptr(x) for x in outs], _ptr(ctx.g_state), _stream()), 'piml_relfeat_self_fwd')
         else:                 # the LOCAL part ran earlier (relative_features_local_part): finish with the remote sources
-            geom = (s.data_ptr(), N, M, focal_begin, focal_count, kp, ko, cos_p, cos_o, dthr_p, dthr_o)
-            if local.geom != geom:
+            if local.geom != (s.data_ptr(), N, M, focal_begin, focal_count, geo):
                 raise ValueError('relative_features_packed_self: `local` was made for another state buffer / geometry')
-            outs = (torch.empty(focal_count, kpe, 6, **opt), local.obs_feat, local.self_features, local.ped_idx,
-                    local.obs_idx)
+            outs = (local.ped_feat, local.obs_feat, local.self_features, local.ped_idx, local.obs_idx)
             ctx.g_state = local.g_state if need_grad else None
             local.g_state = None
             with torch.cuda.device(s.device):
                 _lib.check(_lib.lib().piml_relfeat_self_fwd_part(
-                    2, _ptr(s), None, None, None, N, M, focal_begin, focal_count, kp, ko, cos_p, cos_o,
-                    dthr_p, dthr_o, _ptr(outs[0]), None, None, _ptr(outs[3]), None, None, _stream()),
+                    2, _ptr(s), None, None, None, N, M, focal_begin, focal_count, *geo,
+                    _ptr(outs[0]), None, None, _ptr(outs[3]), None, None, _stream()),
                     'piml_relfeat_self_fwd_part(REMOTE)')
         ctx.save_for_backward(outs[3], outs[4], s, d_rows)
         ctx.geom = (1, N, focal_begin, focal_count, kpe, koe, ())
@@ -318,7 +336,7 @@ class _RelativeFeaturesPackedSelf(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_ped, g_obs, g_self, _gi, _go):
         if g_ped is None and g_obs is None and g_self is None:
-            return (None,) * 13
+            return (None,) * 8
         ped_idx, obs_idx, s, d_rows = ctx.saved_tensors
         _, N, f0, fcnt, kpe, koe, _ = ctx.geom
         opt = dict(device=s.device, dtype=torch.float32)
@@ -337,11 +355,8 @@ class _RelativeFeaturesPackedSelf(torch.autograd.Function):
                                                                  _stream()), 'piml_self_features_bwd')
             g_state, g_d_rows = _launch_relfeat_bwd(ctx.geom, g_ped, g_obs, g_dest, ped_idx, obs_idx, s.data_ptr(), 6,
                                                     d_rows, s.device, g_state=g_state)
-            return (g_state, g_d_rows, None, g_speed) + (None,) * 9
-
-        def dense(g, shape):
-            return torch.zeros(shape, **opt) if g is None else _gpu_f32('grad', g)
-        g_ped, g_obs, g_self = dense(g_ped, (fcnt, kpe, 6)), dense(g_obs, (fcnt, koe, 6)), dense(g_self, (fcnt, 7))
+            return (g_state, g_d_rows, None, g_speed) + (None,) * 4
+        g_ped, g_obs, g_self = _dense((g_ped, g_obs, g_self), _feat_shapes((), fcnt, kpe, koe, 7), s.device, _fresh_zeros)
         g_state, ctx.g_state = ctx.g_state, None        # the forward's cleared buffer, once; a second backward pass
         if g_state is None:                             # (retain_graph) clears a fresh one
             g_state = torch.zeros(N, 6, **opt)
@@ -351,14 +366,15 @@ class _RelativeFeaturesPackedSelf(torch.autograd.Function):
             _lib.check(_lib.lib().piml_relfeat_self_bwd(
                 _ptr(g_ped), _ptr(g_obs), _ptr(g_self), _ptr(ped_idx), _ptr(obs_idx), _ptr(s), _ptr(d_rows), N, f0, fcnt,
                 kpe, koe, _ptr(g_state), _ptr(g_d_rows), _ptr(g_speed), _stream()), 'piml_relfeat_self_bwd')
-        return (g_state, g_d_rows, None, g_speed) + (None,) * 9
+        return (g_state, g_d_rows, None, g_speed) + (None,) * 4
 
 
 class LocalFeatures:
-    """What relative_features_local_part leaves behind for relative_features_packed_self(local=...)."""
+    """What relative_features_local_part leaves behind for relative_features_packed_self(local=...): the five output
+    buffers (ped_feat still to be written by the remote half), the cleared state-gradient buffer and the geometry."""
 
     def __init__(self):
-        self.obs_feat = self.self_features = self.ped_idx = self.obs_idx = self.g_state = None
+        self.ped_feat = self.obs_feat = self.self_features = self.ped_idx = self.obs_idx = self.g_state = None
         self.geom = None
 
 
@@ -370,34 +386,22 @@ def relative_features_local_part(state, destination_rows, obstacles, desired_spe
     self_features rows -- so that it can be enqueued while the all-gather of the other blocks is still in flight (the
     rows outside [focal_begin, focal_begin + focal_count) are not read).  No autograd here: pass the result as
     `local=` to relative_features_packed_self, which finishes with the remote agents and owns the whole gradient."""
-    if topk_ped > MAX_TOPK or topk_obs > MAX_TOPK:
-        raise ValueError(f'topk must be <= {MAX_TOPK}')
-    s = _gpu_f32('state', state.detach())
-    d_rows = _gpu_f32('destination_rows', destination_rows.detach())
+    geo = _rel_geom(topk_ped, sight_angle_ped, dist_threshold_ped, topk_obs, sight_angle_obs, dist_threshold_obs)
+    focal_begin, focal_count = int(focal_begin), int(focal_count)
+    s, d_rows, N, _, _ = _packed_state(state.detach(), destination_rows.detach(), focal_count, flat=True)
     o = _gpu_f32('obstacles', obstacles.detach()).reshape(-1, 2)
-    w = _gpu_f32('desired_speed', desired_speed.detach())
-    if s.dim() != 2 or s.shape[-1] != 6:
-        raise ValueError(f'state must be (N, 6), got {tuple(s.shape)}')
-    N, M = s.shape[0], o.shape[0]
-    focal_begin, focal_count, kp, ko = int(focal_begin), int(focal_count), int(topk_ped), int(topk_obs)
-    if tuple(d_rows.shape) != (focal_count, 2) or w.numel() != focal_count:
-        raise ValueError('destination_rows (n, 2) and desired_speed (n, 1) expected for the focal rows')
-    kpe, koe = min(kp, N), min(ko, M)
-    opt = dict(device=s.device, dtype=torch.float32)
+    w = _focal_speed(desired_speed.detach(), focal_count)
+    M = o.shape[0]
     L = LocalFeatures()
-    L.obs_feat = torch.empty(focal_count, koe, 6, **opt)
-    L.self_features = torch.empty(focal_count, 7, **opt)
-    L.ped_idx = torch.empty(focal_count, kpe, device=s.device, dtype=torch.int32)
-    L.obs_idx = torch.empty(focal_count, koe, device=s.device, dtype=torch.int32)
-    L.g_state = torch.empty(N, 6, **opt) if (want_grad and not DETERMINISTIC_BWD) else None
-    cos_p, cos_o = cos_threshold(sight_angle_ped), cos_threshold(sight_angle_obs)
-    L.geom = (s.data_ptr(), N, M, focal_begin, focal_count, kp, ko, cos_p, cos_o, float(dist_threshold_ped),
-              float(dist_threshold_obs))
+    L.ped_feat, L.obs_feat, L.self_features, L.ped_idx, L.obs_idx = _alloc_feats((), focal_count, min(geo.kp, N), min(geo.ko, M),
+                                                                                 7, s.device)
+    L.g_state = torch.empty(N, 6, device=s.device, dtype=torch.float32) if (want_grad and not DETERMINISTIC_BWD) else None
+    L.geom = (s.data_ptr(), N, M, focal_begin, focal_count, geo)
     with torch.cuda.device(s.device):
         _lib.check(_lib.lib().piml_relfeat_self_fwd_part(
-            1, _ptr(s), _ptr(d_rows), _ptr(o), _ptr(w), N, M, focal_begin, focal_count, kp, ko, cos_p, cos_o,
-            float(dist_threshold_ped), float(dist_threshold_obs), None, _ptr(L.obs_feat), _ptr(L.self_features),
-            _ptr(L.ped_idx), _ptr(L.obs_idx), _ptr(L.g_state), _stream()), 'piml_relfeat_self_fwd_part(LOCAL)')
+            1, _ptr(s), _ptr(d_rows), _ptr(o), _ptr(w), N, M, focal_begin, focal_count, *geo,
+            None, _ptr(L.obs_feat), _ptr(L.self_features), _ptr(L.ped_idx), _ptr(L.obs_idx), _ptr(L.g_state), _stream()),
+            'piml_relfeat_self_fwd_part(LOCAL)')
     return L
 
 
@@ -408,12 +412,9 @@ def relative_features_packed_self(state, destination_rows, obstacles, desired_sp
     relative_features_packed + the model's self-feature rows [dest - p, v, a, v0] in one autograd node.
     local: the LocalFeatures of relative_features_local_part on the same buffer and geometry; only the remote half of
     the neighbour search is then left to do (results bit-identical to the one-launch form)."""
-    if topk_ped > MAX_TOPK or topk_obs > MAX_TOPK:
-        raise ValueError(f'topk must be <= {MAX_TOPK}')
+    geo = _rel_geom(topk_ped, sight_angle_ped, dist_threshold_ped, topk_obs, sight_angle_obs, dist_threshold_obs)
     out = _RelativeFeaturesPackedSelf.apply(state, destination_rows, obstacles, desired_speed, int(focal_begin),
-                                            int(focal_count), int(topk_ped), int(topk_obs),
-                                            cos_threshold(sight_angle_ped), cos_threshold(sight_angle_obs),
-                                            float(dist_threshold_ped), float(dist_threshold_obs), local)
+                                            int(focal_count), geo, local)
     return out if return_index else out[:3]
 
 
@@ -424,17 +425,12 @@ def relative_features_packed_into(outs, state, destination_rows, obstacles, foca
     obs_features, dest_features (n, 2) or self_features (n, 7; columns 0-1 are rewritten), ped_idx,
     obs_idx) of an earlier relative_features_packed / relative_features_packed_self call
     (static buffers of a captured step; bench.py relaunches the kernel between HIP events)."""
-    s = _gpu_f32('state', state.detach())
-    d_rows = _gpu_f32('destination_rows', destination_rows)
+    geo = _rel_geom(topk_ped, sight_angle_ped, dist_threshold_ped, topk_obs, sight_angle_obs, dist_threshold_obs)
+    s, d_rows, N, lead, C = _packed_state(state.detach(), destination_rows, int(focal_count))
     o = _gpu_f32('obstacles', obstacles).reshape(-1, 2)
-    N = s.shape[-2]
-    lead = tuple(s.shape[:-2])
-    C = s.numel() // max(N * 6, 1)
     base = s.data_ptr()
     _launch_relfeat_fwd(base, base + 8, base + 16, 6, None, d_rows, o, lead, C, N, int(focal_begin),
-                        int(focal_count), int(topk_ped), int(topk_obs), cos_threshold(sight_angle_ped),
-                        cos_threshold(sight_angle_obs), float(dist_threshold_ped), float(dist_threshold_obs),
-                        s.device, outs=tuple(outs), dest_ld=outs[2].shape[-1])
+                        int(focal_count), geo, s.device, outs=tuple(outs), dest_ld=outs[2].shape[-1])
     return outs
 
 
@@ -443,12 +439,8 @@ def relative_features_packed(state, destination_rows, obstacles, focal_begin, fo
                              topk_obs=10, sight_angle_obs=90, dist_threshold_obs=4, return_index=False):
     """relative_features for an interleaved (..., N, 6) state buffer; the gradient w.r.t.
     `state` covers all N sources (a rank's partial sum under agent-block sharding)."""
-    if topk_ped > MAX_TOPK or topk_obs > MAX_TOPK:
-        raise ValueError(f'topk must be <= {MAX_TOPK}')
-    out = _RelativeFeaturesPacked.apply(state, destination_rows, obstacles, int(focal_begin), int(focal_count),
-                                        int(topk_ped), int(topk_obs), cos_threshold(sight_angle_ped),
-                                        cos_threshold(sight_angle_obs), float(dist_threshold_ped),
-                                        float(dist_threshold_obs))
+    geo = _rel_geom(topk_ped, sight_angle_ped, dist_threshold_ped, topk_obs, sight_angle_obs, dist_threshold_obs)
+    out = _RelativeFeaturesPacked.apply(state, destination_rows, obstacles, int(focal_begin), int(focal_count), geo)
     return out if return_index else out[:3]
 
 
@@ -464,13 +456,25 @@ def relative_features(position, velocity, acceleration, destination, obstacles,
     acceleration and destination.  Returns (ped_features (..., n, kp, 6), obs_features
     (..., n, ko, 6), dest_features (..., n, 2)) [+ int32 index tensors], n = focal_count.
     """
-    if topk_ped > MAX_TOPK or topk_obs > MAX_TOPK:
-        raise ValueError(f'topk must be <= {MAX_TOPK}')
+    geo = _rel_geom(topk_ped, sight_angle_ped, dist_threshold_ped, topk_obs, sight_angle_obs, dist_threshold_obs)
     out = _RelativeFeatures.apply(position, velocity, acceleration, destination, obstacles, heading,
-                                  focal_begin, focal_count, int(topk_ped), int(topk_obs),
-                                  cos_threshold(sight_angle_ped), cos_threshold(sight_angle_obs),
-                                  float(dist_threshold_ped), float(dist_threshold_obs))
+                                  focal_begin, focal_count, geo)
     return out if return_index else out[:3]
+
+
+def relative_features_into(outs, position, velocity, acceleration, destination, obstacles,
+                           topk_ped=6, sight_angle_ped=90, dist_threshold_ped=4,
+                           topk_obs=10, sight_angle_obs=90, dist_threshold_obs=4, tick=None):
+    """Forward only, no autograd, no allocation: per-step features of (..., N, 2) state into the
+    preallocated `outs` = (ped_features, obs_features, self_features, ped_idx, obs_idx), where
+    dest_features land in columns 0..1 of the (..., N, F) self_features buffer (row stride F).
+    Used by the captured inference-rollout step; `tick` (one-element int64 tensor) is advanced by one by the same launch."""
+    geo = _rel_geom(topk_ped, sight_angle_ped, dist_threshold_ped, topk_obs, sight_angle_obs, dist_threshold_obs)
+    p, v, a, d, N, lead, C = _separate_state(position, velocity, acceleration, destination)
+    o = _gpu_f32('obstacles', obstacles).reshape(-1, 2)
+    _launch_relfeat_fwd(_ptr(p), _ptr(v), _ptr(a), 2, None, d, o, lead, C, N, 0, N, geo, p.device,
+                        outs=tuple(outs), dest_ld=outs[2].shape[-1], tick=tick)
+    return outs
 
 
 def relative_features_self(position, velocity, acceleration, destination, obstacles, desired_speed,
@@ -479,17 +483,13 @@ def relative_features_self(position, velocity, acceleration, destination, obstac
     """relative_features whose third result is the model's self_features (..., N, 7) = [dest - p, v, a, v0] -- what the
     training rollout concatenates per frame (src/models/simulators.py:778-779) -- written by the same launch.
     desired_speed (..., N, 1) or (..., N).  Differentiable w.r.t. position, velocity, acceleration, destination, speed."""
-    if topk_ped > MAX_TOPK or topk_obs > MAX_TOPK:
-        raise ValueError(f'topk must be <= {MAX_TOPK}')
+    geo = _rel_geom(topk_ped, sight_angle_ped, dist_threshold_ped, topk_obs, sight_angle_obs, dist_threshold_obs)
     if DETERMINISTIC_BWD:       # the atomics-free backward exists for the plain operator: features + cat, as before
-        out = relative_features(position, velocity, acceleration, destination, obstacles, topk_ped, sight_angle_ped,
-                                dist_threshold_ped, topk_obs, sight_angle_obs, dist_threshold_obs, return_index=True)
+        out = _RelativeFeatures.apply(position, velocity, acceleration, destination, obstacles, None, 0, None, geo)
         v0 = desired_speed if desired_speed.dim() == position.dim() else desired_speed.unsqueeze(-1)
         out = (out[0], out[1], torch.cat((out[2], velocity, acceleration, v0), dim=-1), out[3], out[4])
         return out if return_index else out[:3]
-    out = _RelativeFeaturesSelf.apply(position, velocity, acceleration, destination, obstacles, desired_speed,
-                                      int(topk_ped), int(topk_obs), cos_threshold(sight_angle_ped), cos_threshold(sight_angle_obs),
-                                      float(dist_threshold_ped), float(dist_threshold_obs))
+    out = _RelativeFeaturesSelf.apply(position, velocity, acceleration, destination, obstacles, desired_speed, geo)
     return out if return_index else out[:3]
 
 
@@ -697,6 +697,15 @@ def collision_detection(position, threshold, real_position=None):
 _THRESHOLDS = {}
 
 
+def _thresholds(device, thresholds):
+    """The thresholds as a float32 tensor on `device`, cached: a host-to-device copy is not capturable into a graph."""
+    key = (device, tuple(float(t) for t in thresholds))
+    thr = _THRESHOLDS.get(key)
+    if thr is None:
+        thr = _THRESHOLDS[key] = torch.tensor(key[1], device=device, dtype=torch.float32)
+    return thr
+
+
 COLLISION_GRID = _os.environ.get('PIML_COLLISION_GRID', '1') != '0'
 
 
@@ -707,10 +716,7 @@ def collision_counts(position, thresholds):
     if p.dim() != 3:
         raise ValueError('position must be (S, N, 2)')
     S, N = p.shape[0], p.shape[1]
-    key = (p.device, tuple(float(t) for t in thresholds))
-    thr = _THRESHOLDS.get(key)
-    if thr is None:                 # cached: a host-to-device copy is not capturable into a graph
-        thr = _THRESHOLDS[key] = torch.tensor(key[1], device=p.device, dtype=torch.float32)
+    thr = _thresholds(p.device, thresholds)
     counts = torch.empty(len(thresholds), S, N, device=p.device, dtype=torch.float32)
     with torch.cuda.device(p.device):
         if S > 25 and len(thresholds) <= 4 and len(thresholds) * N * N <= (1 << 28):
@@ -732,7 +738,6 @@ def collision_counts_frames(frames, thresholds):
     """[collision_counts(f, thresholds) for f in frames] in ONE launch (piml_collision_counts_frames): `frames` = up to 32
     (S, N, 2) tensors of one shape with S <= 25 (the frames of a training rollout, each counted on its own by
     src/models/simulators.py:708-715).  Returns a list of (len(thresholds), S, N) views of one buffer."""
-    import ctypes
     ps = [_gpu_f32('position', f.detach()) for f in frames]
     if not ps:
         return []
@@ -742,10 +747,7 @@ def collision_counts_frames(frames, thresholds):
     if len(ps) > 32 or S > 25 or not 1 <= len(thresholds) <= 4:
         return [collision_counts(p, thresholds) for p in ps]
     dev = ps[0].device
-    key = (dev, tuple(float(t) for t in thresholds))
-    thr = _THRESHOLDS.get(key)
-    if thr is None:
-        thr = _THRESHOLDS[key] = torch.tensor(key[1], device=dev, dtype=torch.float32)
+    thr = _thresholds(dev, thresholds)
     counts = torch.empty(len(ps), len(thresholds), S, N, device=dev, dtype=torch.float32)
     arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
     with torch.cuda.device(dev):
@@ -776,7 +778,6 @@ def _zeros_ro(shape, dev):
 def multi_copy(dsts, srcs):
     """dst[i].copy_(src[i]) for lists of GPU tensors in ONE launch (piml_multi_copy) when every pair is contiguous, of one
     dtype and shape and on the current stream's device; anything else goes through torch._foreach_copy_."""
-    import ctypes
     dsts, srcs = list(dsts), list(srcs)
     ok = len(dsts) == len(srcs) and len(dsts) > 0 and all(
         d.is_cuda and s.is_cuda and d.device == s.device == dsts[0].device and d.dtype == s.dtype and d.shape == s.shape
@@ -884,7 +885,6 @@ class _RolloutLossesFrames(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p, labels, mask_pred, gates, focus, abnormal_mask, time_decay, w_coll, w_hard, *frames):
-        import ctypes
         L = _lib.lib()
         pc = _gpu_f32('p', p.detach())
         C, T, N = pc.shape[0], pc.shape[1], pc.shape[2]
@@ -959,7 +959,6 @@ class _CollisionPredLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gates_f, t_start, T, weight, nframes, *tensors):
-        import ctypes
         L = _lib.lib()
         preds = [_gpu_f32('prediction', t.detach()) for t in tensors[:nframes]]
         feats = [_gpu_f32('ped_features', t.detach()) for t in tensors[nframes:]]
@@ -1146,25 +1145,6 @@ def calc_acceleration(relative_data, equation_version='v0', dataset='gc1560', ep
                                                      D, th, float(eps), _ptr(out), _stream()),
                    'piml_calc_acceleration')
     return out
-
-
-def relative_features_into(outs, position, velocity, acceleration, destination, obstacles,
-                           topk_ped=6, sight_angle_ped=90, dist_threshold_ped=4,
-                           topk_obs=10, sight_angle_obs=90, dist_threshold_obs=4, tick=None):
-    """Forward only, no autograd, no allocation: per-step features of (..., N, 2) state into the
-    preallocated `outs` = (ped_features, obs_features, self_features, ped_idx, obs_idx), where
-    dest_features land in columns 0..1 of the (..., N, F) self_features buffer (row stride F).
-    Used by the captured inference-rollout step; `tick` (one-element int64 tensor) is advanced by one by the same launch."""
-    p, v, a, d = [_gpu_f32(n, x) for n, x in (('position', position), ('velocity', velocity),
-                                              ('acceleration', acceleration), ('destination', destination))]
-    o = _gpu_f32('obstacles', obstacles).reshape(-1, 2)
-    N = p.shape[-2]
-    lead = tuple(p.shape[:-2])
-    C = p.numel() // max(N * 2, 1)
-    _launch_relfeat_fwd(_ptr(p), _ptr(v), _ptr(a), 2, None, d, o, lead, C, N, 0, N, int(topk_ped), int(topk_obs),
-                        cos_threshold(sight_angle_ped), cos_threshold(sight_angle_obs), float(dist_threshold_ped),
-                        float(dist_threshold_obs), p.device, outs=tuple(outs), dest_ld=outs[2].shape[-1], tick=tick)
-    return outs
 
 
 def rollout_step(st, data, a_next, remove_arrived=True, ksum=None):
@@ -1817,6 +1797,47 @@ def _check_keep_bits(keep_bits, rows, cols, device):
     return keep_bits
 
 
+def _check_rollout_inputs(who, C, N, dest_idx, dest_num, waypoints, new_flag, series, copy_flag):
+    """The checks train_rollout_step and rollout_frame share -> (new_flag as uint8 or None, series or None).  waypoints None:
+    the caller takes them unchecked (rollout_frame).  A non-contiguous new_flag is copied with `copy_flag` (train_rollout_step)
+    and refused without it (rollout_frame, whose captured loops must not pay a copy per frame)."""
+    if dest_idx.dtype != torch.int64 or dest_num.dtype != torch.int64:
+        raise TypeError(f'{who}: dest_idx / dest_num must be int64')
+    if tuple(dest_idx.shape) != (C, N) or dest_num.numel() != N:
+        raise ValueError(f'{who}: dest_idx (C, N) and dest_num (N) expected')
+    if waypoints is not None and (waypoints.dtype != torch.float32 or waypoints.shape[-2:] != (N, 2) or
+                                  (waypoints.dim() == 4 and waypoints.shape[0] != C) or waypoints.dim() not in (3, 4)):
+        raise ValueError(f'{who}: waypoints (D, N, 2) or (C, D, N, 2) float32 expected')
+    if new_flag is None:
+        return None, None
+    if series is None or len(series) != 5:
+        raise ValueError(f'{who}: new_flag needs the five ground-truth series')
+    T = series[0].shape[1]
+    if new_flag.dtype == torch.bool:
+        new_flag = new_flag.view(torch.uint8)
+    if new_flag.dtype != torch.uint8 or tuple(new_flag.shape) != (C, T, N) or not (copy_flag or new_flag.is_contiguous()):
+        raise ValueError(f'{who}: new_flag must be {"" if copy_flag else "contiguous "}(C, T, N) bool / uint8')
+    for x, w, dt_ in zip(series, (2, 2, 2, 2, None), (torch.float32,) * 4 + (torch.int64,)):
+        want = (C, T, N) + ((w,) if w else ())
+        if tuple(x.shape) != want or x.dtype != dt_ or not x.is_contiguous():
+            raise ValueError(f'{who}: series tensor must be contiguous {want} {dt_}')
+    return new_flag.contiguous(), series
+
+
+def _step_fwd_args(p, v, a, dest, dest_idx, waypoints, dest_num, new_flag, series, t_next, dt, nan_flag, zero_nan):
+    """The outputs of a rollout step's forward and the arguments its three entry points share
+    -> (outs, idx_out, zero_mask, T, head, rest): a call is (*head, <a_pred | the tail's arguments>, *rest, [<copy target>,] stream)."""
+    C, N = p.shape[0], p.shape[1]
+    T = series[0].shape[1] if series is not None else max(int(t_next), 1)
+    outs = [torch.empty(C, N, 2, device=p.device, dtype=torch.float32) for _ in range(4)]
+    idx_out = torch.empty(C, N, device=p.device, dtype=torch.int64)
+    zero_mask = torch.empty(C, N, device=p.device, dtype=torch.uint8) if zero_nan else None
+    rest = (_ptr(dest), _ptr(dest_idx), _ptr(waypoints), waypoints.shape[-3], int(waypoints.dim() == 4), _ptr(dest_num),
+            _ptr(new_flag), *([None] * 5 if series is None else [_ptr(x) for x in series]), C, T, N, int(t_next), float(dt),
+            *[_ptr(o) for o in outs], _ptr(idx_out), _ptr(nan_flag), _ptr(zero_mask))
+    return outs, idx_out, zero_mask, T, (_ptr(p), _ptr(v), _ptr(a)), rest
+
+
 class _TrainRolloutStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p, v, a, a_pred, dest, dest_idx, waypoints, dest_num, new_flag, series, t_next, dt, nan_flag,
@@ -1825,20 +1846,10 @@ class _TrainRolloutStep(torch.autograd.Function):
                                  (('position', p), ('velocity', v), ('acceleration', a), ('a_pred', a_pred),
                                   ('destination', dest))]
         C, N = p.shape[0], p.shape[1]
-        D = waypoints.shape[-3]
-        per_slice = int(waypoints.dim() == 4)
-        T = series[0].shape[1] if series is not None else max(int(t_next), 1)
-        opt = dict(device=p.device, dtype=torch.float32)
-        outs = [torch.empty(C, N, 2, **opt) for _ in range(4)]
-        idx_out = torch.empty(C, N, device=p.device, dtype=torch.int64)
-        sp = [None] * 5 if series is None else [_ptr(x) for x in series]
-        zero_mask = torch.empty(C, N, device=p.device, dtype=torch.uint8) if zero_nan else None
+        outs, idx_out, zero_mask, T, head, rest = _step_fwd_args(p, v, a, dest, dest_idx, waypoints, dest_num, new_flag, series,
+                                                                 t_next, dt, nan_flag, zero_nan)
         with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().piml_train_step_fwd(
-                _ptr(p), _ptr(v), _ptr(a), _ptr(a_pred), _ptr(dest), _ptr(dest_idx), _ptr(waypoints), D, per_slice,
-                _ptr(dest_num), _ptr(new_flag) if new_flag is not None else None, *sp, C, T, N, int(t_next),
-                float(dt), *[_ptr(o) for o in outs], _ptr(idx_out), _ptr(nan_flag) if nan_flag is not None else None,
-                _ptr(zero_mask) if zero_mask is not None else None, _stream()), 'piml_train_step_fwd')
+            _lib.check(_lib.lib().piml_train_step_fwd(*head, _ptr(a_pred), *rest, _stream()), 'piml_train_step_fwd')
         ctx.new_flag, ctx.zero_mask, ctx.geom = new_flag, zero_mask, (C, T, N, int(t_next), float(dt))
         ctx.mark_non_differentiable(outs[3], idx_out)
         ctx.set_materialize_grads(False)
@@ -1860,8 +1871,7 @@ class _TrainRolloutStep(torch.autograd.Function):
         cont = [None if g is None else g.contiguous() for g in (gp_o, gv_o, ga_o)]
         with torch.cuda.device(ref.device):
             _lib.check(_lib.lib().piml_train_step_bwd(
-                *[_ptr(g) for g in cont], _ptr(ctx.new_flag) if ctx.new_flag is not None else None,
-                _ptr(ctx.zero_mask) if ctx.zero_mask is not None else None, C, T, N, t_next,
+                *[_ptr(g) for g in cont], _ptr(ctx.new_flag), _ptr(ctx.zero_mask), C, T, N, t_next,
                 dt, *[_ptr(g) for g in gs], _stream()), 'piml_train_step_bwd')
         return (*gs,) + (None,) * 10
 
@@ -1881,29 +1891,8 @@ def train_rollout_step(position, velocity, acceleration, a_pred, destination, de
         raise ValueError('train_rollout_step: (C, N, 2) state expected')
     if not position.is_cuda:
         raise _lib.PimlHipError('train_rollout_step: expected GPU tensors (piml_amd has no CPU path)')
-    C, N = position.shape[0], position.shape[1]
-    if dest_idx.dtype != torch.int64 or dest_num.dtype != torch.int64:
-        raise TypeError('train_rollout_step: dest_idx / dest_num must be int64')
-    if tuple(dest_idx.shape) != (C, N) or dest_num.numel() != N:
-        raise ValueError('train_rollout_step: dest_idx (C, N) and dest_num (N) expected')
-    if waypoints.dtype != torch.float32 or waypoints.shape[-2:] != (N, 2) or \
-            (waypoints.dim() == 4 and waypoints.shape[0] != C) or waypoints.dim() not in (3, 4):
-        raise ValueError('train_rollout_step: waypoints (D, N, 2) or (C, D, N, 2) float32 expected')
-    if new_flag is not None:
-        if series is None or len(series) != 5:
-            raise ValueError('train_rollout_step: new_flag needs the five ground-truth series')
-        T = series[0].shape[1]
-        if new_flag.dtype == torch.bool:
-            new_flag = new_flag.view(torch.uint8)
-        if new_flag.dtype != torch.uint8 or tuple(new_flag.shape) != (C, T, N):
-            raise ValueError('train_rollout_step: new_flag must be (C, T, N) bool / uint8')
-        new_flag = new_flag.contiguous()
-        for x, w, dt_ in zip(series, (2, 2, 2, 2, None), (torch.float32,) * 4 + (torch.int64,)):
-            want = (C, T, N) + ((w,) if w else ())
-            if tuple(x.shape) != want or x.dtype != dt_ or not x.is_contiguous():
-                raise ValueError(f'train_rollout_step: series tensor must be contiguous {want} {dt_}')
-    else:
-        series = None
+    new_flag, series = _check_rollout_inputs('train_rollout_step', position.shape[0], position.shape[1], dest_idx, dest_num,
+                                             waypoints, new_flag, series, copy_flag=True)
     return _TrainRolloutStep.apply(position, velocity, acceleration, a_pred, destination, dest_idx.contiguous(),
                                    waypoints.contiguous(), dest_num.contiguous(), new_flag, series, int(t_next),
                                    float(dt), nan_flag, bool(zero_nan))
@@ -1919,71 +1908,47 @@ class _RolloutFrame(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p, v, a, a_pred, dest, dest_idx, waypoints, dest_num, new_flag, series, t_next, dt, nan_flag,
-                obstacles, speed, kp, ko, cos_p, cos_o, dthr_p, dthr_o, alias_p=False, stack=None, tail_ped=None, tail_obs=None,
-                tail_sf=None, tail_tau=None):
+                obstacles, speed, geo, alias_p=False, stack=None, tail_ped=None, tail_obs=None, tail_sf=None, tail_tau=None):
         L = _lib.lib()
         p_arg = p
-        p, v, a, dest = [_gpu_f32(n, x) for n, x in (('position', p), ('velocity', v), ('acceleration', a), ('destination', dest))]
+        p, v, a, dest, N, (C,), _ = _separate_state(p, v, a, dest)
         # tail_*: the model's tail rides in the step's launch (piml_train_step_tail_fwd): a_pred is None, the prediction is made there
         tail = tail_ped is not None
         if tail:
             t_ped = _gpu_f32('tail acc_ped', tail_ped)
             t_obs = _gpu_f32('tail acc_obs', tail_obs) if tail_obs is not None else None
             t_sf = _gpu_f32('tail self_features', tail_sf)
-            Cn = p.shape[0] * p.shape[1]
+            Cn = C * N
             tkp, tko = t_ped.numel() // (Cn * 2), (t_obs.numel() // (Cn * 2) if t_obs is not None else 1)
-            if tuple(t_sf.shape) != (p.shape[0], p.shape[1], 7) or t_ped.numel() != Cn * tkp * 2 or \
+            if tuple(t_sf.shape) != (C, N, 7) or t_ped.numel() != Cn * tkp * 2 or \
                     (t_obs is not None and t_obs.numel() != Cn * tko * 2):
                 raise ValueError('rollout_frame: tail = (acc_ped (C, N[, k], 2), acc_obs | None, self_features (C, N, 7), tau)')
+            special = (_ptr(t_ped), tkp, _ptr(t_obs), tko, _ptr(t_sf), float(tail_tau))
         else:
             a_pred = _gpu_f32('a_pred', a_pred)
+            special = (_ptr(a_pred),)
         o = _gpu_f32('obstacles', obstacles).reshape(-1, 2)
         v0 = _gpu_f32('desired_speed', speed)
-        C, N = p.shape[0], p.shape[1]
-        D = waypoints.shape[-3]
-        per_slice = int(waypoints.dim() == 4)
-        T = series[0].shape[1] if series is not None else max(int(t_next), 1)
-        dev = p.device
-        opt = dict(device=dev, dtype=torch.float32)
-        outs = [torch.empty(C, N, 2, **opt) for _ in range(4)]
-        idx_out = torch.empty(C, N, device=dev, dtype=torch.int64)
-        sp = [None] * 5 if series is None else [_ptr(x) for x in series]
-        zero_mask = torch.empty(C, N, device=dev, dtype=torch.uint8)
-        M = o.shape[0]
-        kpe, koe = min(kp, N), min(ko, M)
-        pf, of, sf = torch.empty(C, N, kpe, 6, **opt), torch.empty(C, N, koe, 6, **opt), torch.empty(C, N, 7, **opt)
-        pi = torch.empty(C, N, kpe, device=dev, dtype=torch.int32)
-        oi = torch.empty(C, N, koe, device=dev, dtype=torch.int32)
-        need = any(ctx.needs_input_grad[:4]) or (tail and any(ctx.needs_input_grad[23:26]))
-        g6 = torch.empty(C, N, 6, **opt) if need else None
-        with torch.cuda.device(dev):
-            copy_ptr, copy_stride = None, 0
-            if stack is not None:         # (buffer (C, T', N, 2) float32 contiguous, frame index): the input position into its frame
-                sbuf, st_ = stack
-                copy_ptr, copy_stride = sbuf.data_ptr() + int(st_) * N * 2 * 4, sbuf.shape[1] * N * 2
-            if tail:
-                _lib.check(L.piml_train_step_tail_fwd(
-                    _ptr(p), _ptr(v), _ptr(a), _ptr(t_ped), tkp, _ptr(t_obs), tko, _ptr(t_sf), float(tail_tau), _ptr(dest), _ptr(dest_idx),
-                    _ptr(waypoints), D, per_slice, _ptr(dest_num), _ptr(new_flag) if new_flag is not None else None, *sp, C, T, N,
-                    int(t_next), float(dt), *[_ptr(x) for x in outs], _ptr(idx_out), _ptr(nan_flag) if nan_flag is not None else None,
-                    _ptr(zero_mask), copy_ptr, int(copy_stride), _stream()), 'piml_train_step_tail_fwd')
-            else:
-                _lib.check(L.piml_train_step_fwd_copy(
-                    _ptr(p), _ptr(v), _ptr(a), _ptr(a_pred), _ptr(dest), _ptr(dest_idx), _ptr(waypoints), D, per_slice,
-                    _ptr(dest_num), _ptr(new_flag) if new_flag is not None else None, *sp, C, T, N, int(t_next),
-                    float(dt), *[_ptr(x) for x in outs], _ptr(idx_out), _ptr(nan_flag) if nan_flag is not None else None,
-                    _ptr(zero_mask), copy_ptr, int(copy_stride), _stream()), 'piml_train_step_fwd_copy')
-            _lib.check(L.piml_relfeat_fwd_self(
-                _ptr(outs[0]), None, _ptr(outs[1]), _ptr(outs[2]), 2, _ptr(outs[3]), _ptr(o), _ptr(v0), C, N, M, 0, N, kp, ko,
-                cos_p, cos_o, dthr_p, dthr_o, _ptr(pf), _ptr(of), _ptr(sf), _ptr(pi), _ptr(oi), _ptr(g6), _stream()),
-                'piml_relfeat_fwd_self')
+        outs, idx_out, zero_mask, T, head, rest = _step_fwd_args(p, v, a, dest, dest_idx, waypoints, dest_num, new_flag, series,
+                                                                 t_next, dt, nan_flag, True)
+        need = any(ctx.needs_input_grad[:4]) or (tail and any(ctx.needs_input_grad[18:21]))
+        g6 = torch.empty(C, N, 6, device=p.device, dtype=torch.float32) if need else None
+        copy_ptr, copy_stride = None, 0
+        if stack is not None:         # (buffer (C, T', N, 2) float32 contiguous, frame index): the input position into its frame
+            sbuf, st_ = stack
+            copy_ptr, copy_stride = sbuf.data_ptr() + int(st_) * N * 2 * 4, sbuf.shape[1] * N * 2
+        with torch.cuda.device(p.device):
+            step, what = (L.piml_train_step_tail_fwd, 'piml_train_step_tail_fwd') if tail else \
+                (L.piml_train_step_fwd_copy, 'piml_train_step_fwd_copy')
+            _lib.check(step(*head, *special, *rest, copy_ptr, int(copy_stride), _stream()), what)
+        pf, of, sf, pi, oi = _relfeat_self_fwd(*outs, o, v0, (C,), C, N, geo, g6)
         if tail:
             ctx.save_for_backward(pi, oi, outs[0], outs[3], t_sf)
             ctx.tail = (tkp, tko, float(tail_tau), tuple(tail_ped.shape), None if tail_obs is None else tuple(tail_obs.shape))
         else:
             ctx.save_for_backward(pi, oi, outs[0], outs[3])
             ctx.tail = None
-        ctx.new_flag, ctx.zero_mask, ctx.geom, ctx.g6 = new_flag, zero_mask, (C, T, N, int(t_next), float(dt), kpe, koe), g6
+        ctx.new_flag, ctx.zero_mask, ctx.geom, ctx.g6 = new_flag, zero_mask, (C, T, N, int(t_next), float(dt)), g6
         ctx.mark_non_differentiable(outs[3], idx_out)
         ctx.set_materialize_grads(False)
         if alias_p:
@@ -1996,40 +1961,31 @@ class _RolloutFrame(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gp_o, gv_o, ga_o, _gd, _gi, g_pf, g_of, g_sf, g_alias=None):
-        C, T, N, t_next, dt, kpe, koe = ctx.geom
+        C, T, N, t_next, dt = ctx.geom
         feats = any(g is not None for g in (g_pf, g_of, g_sf))
         if not feats and all(g is None for g in (gp_o, gv_o, ga_o)):
-            return (g_alias if ctx.needs_input_grad[0] else None,) + (None,) * 26
+            return (g_alias if ctx.needs_input_grad[0] else None,) + (None,) * 21
         pi, oi, p_out, dest_out = ctx.saved_tensors[:4]
         dev = p_out.device
         opt = dict(device=dev, dtype=torch.float32)
         L = _lib.lib()
         g6 = None
+        if feats:           # (the step's destination output carries no gradient: the features' g_destination is dropped)
+            g6, ctx.g6 = ctx.g6, None                      # the forward's cleared buffer, once; a second pass clears a fresh one
+            g6, _ = _relfeat_self_bwd((g_pf, g_of, g_sf), pi, oi, p_out, dest_out, (C,), C, N, g6, None, _zeros_ro)
         with torch.cuda.device(dev):
-            if feats:
-                g6, ctx.g6 = ctx.g6, None                      # the forward's cleared buffer, once; a second pass clears a fresh one
-                if g6 is None:
-                    g6 = torch.zeros(C, N, 6, **opt)
-
-                def dense(g, shape):
-                    return _zeros_ro(shape, dev) if g is None else _gpu_f32('grad', g)
-                g_pf, g_of, g_sf = dense(g_pf, (C, N, kpe, 6)), dense(g_of, (C, N, koe, 6)), dense(g_sf, (C, N, 7))
-                g_dest = torch.empty(C, N, 2, **opt)           # (the step's destination output carries no gradient)
-                _lib.check(L.piml_relfeat_bwd_self(
-                    _ptr(g_pf), _ptr(g_of), _ptr(g_sf), _ptr(pi), _ptr(oi), _ptr(p_out), 2, _ptr(dest_out), C, N, 0, N, kpe, koe,
-                    _ptr(g6), _ptr(g_dest), None, _stream()), 'piml_relfeat_bwd_self')
             need = ctx.needs_input_grad
             # an input whose gradient is identically zero gets None (not zeros): autograd then does not walk into the model
             # call that produced a_pred just to propagate nothing (g_p = g_p', g_v = g_v' + dt g_p', g_a = dt g_v', g_a_pred = g_a')
             hp, hv, ha = (gp_o is not None or feats), (gv_o is not None or feats), (ga_o is not None or feats)
-            # the alias gradient as it stands when its (N, 2) slices are contiguous (a time slice of the loss's (C, T, N, 2) gradient)
+
             def sliced(g):          # a (C, N, 2) gradient as it stands when its (N, 2) slices are contiguous -> (tensor, slice stride)
                 g_ = g if (g.is_cuda and g.dtype == torch.float32 and g.dim() == 3) else _gpu_f32('grad', g)
                 if not (g_.stride(2) == 1 and g_.stride(1) == 2 and g_.stride(0) % 2 == 0 and g_.data_ptr() % 8 == 0):
                     g_ = g_.contiguous()
                 return g_, (0 if g_.is_contiguous() else g_.stride(0))
             gin, gin_stride = None, 0
-            if g_alias is not None and need[0]:
+            if g_alias is not None and need[0]:       # (a time slice of the loss's (C, T, N, 2) gradient)
                 gin, gin_stride = sliced(g_alias)
                 if gin_stride == 0:
                     gin_stride = N * 2
@@ -2037,28 +1993,25 @@ class _RolloutFrame(torch.autograd.Function):
             gs = [torch.empty(C, N, 2, **opt) if (need[k] and live[k]) else None for k in range(4)]
             gpo, gpo_stride = (None, 0) if gp_o is None else sliced(gp_o)
             cont = [None if g is None else _gpu_f32('grad', g) for g in (gv_o, ga_o)]
+            common = (_ptr(gpo), int(gpo_stride), *[_ptr(g) for g in cont], _ptr(g6), _ptr(gin), int(gin_stride),
+                      _ptr(ctx.new_flag), _ptr(ctx.zero_mask), C, T, N, t_next, dt)
             g_tail = (None, None, None)
-            if ctx.tail is not None and ha and any(need[23:26]):
+            if ctx.tail is not None and ha and any(need[18:21]):
                 # the step's backward and the tail's in one launch: d/d(prediction) -> the tail's summands (broadcast over k) and g_self
                 tkp, tko, tau, shp_p, shp_o = ctx.tail
                 t_sf = ctx.saved_tensors[4]
                 g_pred = torch.empty(C, N, 2, **opt)
-                g_tp = (torch.empty(shp_p, **opt) if tkp > 1 else g_pred.view(shp_p)) if need[23] else None
-                g_to = (torch.empty(shp_o, **opt) if tko > 1 else g_pred.view(shp_o)) if (shp_o is not None and need[24]) else None
-                g_tsf = torch.empty(C, N, 7, **opt) if need[25] else None
+                g_tp = (torch.empty(shp_p, **opt) if tkp > 1 else g_pred.view(shp_p)) if need[18] else None
+                g_to = (torch.empty(shp_o, **opt) if tko > 1 else g_pred.view(shp_o)) if (shp_o is not None and need[19]) else None
+                g_tsf = torch.empty(C, N, 7, **opt) if need[20] else None
                 _lib.check(L.piml_train_step_tail_bwd(
-                    _ptr(gpo), int(gpo_stride), *[_ptr(g) for g in cont], _ptr(g6), _ptr(gin), int(gin_stride),
-                    _ptr(ctx.new_flag) if ctx.new_flag is not None else None, _ptr(ctx.zero_mask), C, T, N, t_next, dt,
-                    *[_ptr(g) for g in gs[:3]], _ptr(g_pred), _ptr(t_sf), tau, tkp, tko,
-                    _ptr(g_tp) if (g_tp is not None and tkp > 1) else None, _ptr(g_to) if (g_to is not None and tko > 1) else None,
-                    _ptr(g_tsf), _stream()), 'piml_train_step_tail_bwd')
+                    *common, *[_ptr(g) for g in gs[:3]], _ptr(g_pred), _ptr(t_sf), tau, tkp, tko,
+                    _ptr(g_tp) if tkp > 1 else None, _ptr(g_to) if tko > 1 else None, _ptr(g_tsf), _stream()),
+                    'piml_train_step_tail_bwd')
                 g_tail = (g_tp, g_to, g_tsf)
             else:
-                _lib.check(L.piml_train_step_bwd7(
-                    _ptr(gpo), int(gpo_stride), *[_ptr(g) for g in cont], _ptr(g6), _ptr(gin), int(gin_stride),
-                    _ptr(ctx.new_flag) if ctx.new_flag is not None else None,
-                    _ptr(ctx.zero_mask), C, T, N, t_next, dt, *[_ptr(g) for g in gs], _stream()), 'piml_train_step_bwd7')
-        return (*gs,) + (None,) * 19 + g_tail + (None,)
+                _lib.check(L.piml_train_step_bwd7(*common, *[_ptr(g) for g in gs], _stream()), 'piml_train_step_bwd7')
+        return (*gs,) + (None,) * 14 + g_tail + (None,)
 
 
 def rollout_frame(position, velocity, acceleration, a_pred, destination, dest_idx, waypoints, dest_num, dt, new_flag, series,
@@ -2075,8 +2028,7 @@ def rollout_frame(position, velocity, acceleration, a_pred, destination, dest_id
     (ops.stack_of makes the filled buffer a differentiable function of the aliases: no concatenation behind the loop)."""
     if position.dim() != 3 or position.shape[-1] != 2 or not position.is_cuda:
         raise ValueError('rollout_frame: (C, N, 2) GPU state expected')
-    if topk_ped > MAX_TOPK or topk_obs > MAX_TOPK:
-        raise ValueError(f'topk must be <= {MAX_TOPK}')
+    geo = _rel_geom(topk_ped, sight_angle_ped, dist_threshold_ped, topk_obs, sight_angle_obs, dist_threshold_obs)
     if tail is not None and (DETERMINISTIC_BWD or a_pred is not None):
         if a_pred is not None:
             raise ValueError('rollout_frame: a_pred or tail, not both')
@@ -2089,25 +2041,11 @@ def rollout_frame(position, velocity, acceleration, a_pred, destination, dest_id
         out = (*st, *relative_features_self(st[0], st[1], st[2], st[3], obstacles, desired_speed, topk_ped, sight_angle_ped,
                                             dist_threshold_ped, topk_obs, sight_angle_obs, dist_threshold_obs))
         return out + (position,) if alias_position else out
-    C, N = position.shape[0], position.shape[1]
-    if dest_idx.dtype != torch.int64 or dest_num.dtype != torch.int64 or tuple(dest_idx.shape) != (C, N) or dest_num.numel() != N:
-        raise ValueError('rollout_frame: dest_idx (C, N) int64 and dest_num (N) int64 expected')
-    if new_flag is not None:
-        if new_flag.dtype == torch.bool:
-            new_flag = new_flag.view(torch.uint8)
-        T = series[0].shape[1]
-        if new_flag.dtype != torch.uint8 or tuple(new_flag.shape) != (C, T, N) or not new_flag.is_contiguous():
-            raise ValueError('rollout_frame: new_flag must be contiguous (C, T, N) bool / uint8')
-        for x, w, dt_ in zip(series, (2, 2, 2, 2, None), (torch.float32,) * 4 + (torch.int64,)):
-            if tuple(x.shape) != (C, T, N) + ((w,) if w else ()) or x.dtype != dt_ or not x.is_contiguous():
-                raise ValueError('rollout_frame: series tensors must be contiguous (C, T, N[, 2]) float32 / int64')
-    else:
-        series = None
+    new_flag, series = _check_rollout_inputs('rollout_frame', position.shape[0], position.shape[1], dest_idx, dest_num, None,
+                                             new_flag, series, copy_flag=False)
     return _RolloutFrame.apply(position, velocity, acceleration, a_pred, destination, dest_idx.contiguous(), waypoints.contiguous(),
                                dest_num.contiguous(), new_flag, series, int(t_next), float(dt), nan_flag, obstacles, desired_speed,
-                               int(topk_ped), int(topk_obs), cos_threshold(sight_angle_ped), cos_threshold(sight_angle_obs),
-                               float(dist_threshold_ped), float(dist_threshold_obs), bool(alias_position),
-                               None if (stack is None or DETERMINISTIC_BWD) else stack,
+                               geo, bool(alias_position), stack,
                                *((None, None, None, None) if tail is None else (tail[0], tail[1], tail[2], float(tail[3]))))
 
 
@@ -2223,7 +2161,6 @@ def _h1_needed(rows_per_branch, alone=True):
     one-wave kernels on its own (`alone` is kept for the callers' sake and no longer changes the answer)."""
     if not (H1_RECOMPUTE and RELU_MASK):
         return True
-    import ctypes
     L = _lib.lib()
     # EVERY branch on its own above the training bound (round 5: also for the network, whose backward normally has a gradient for all
     # branches -- but a loss on the collision head or the messages alone arrives through ONE branch, and that launch must not fall back
@@ -2338,7 +2275,6 @@ class _FusedEncoders(torch.autograd.Function):
             structs.append(_enc_branch_struct(x2s[b], ks[b], scales[b], wbs[b], None, h1s[b], h2s[b], gp, gm, g2, g1, gx,
                                               packed=packed[b], keep_bits=ctx.keeps[b]))
         arr = (_lib.EncoderBranch * len(live))(*structs)
-        import ctypes
         w0 = ctypes.c_int(0)
         total = L.piml_encoder_workgroups(arr, len(live), ctypes.byref(w0))
         slots = [w0.value, total - w0.value] if len(live) == 2 else [total]
@@ -2503,7 +2439,6 @@ def pinnsf_prepack(packs, enc_w, dec_w, head_w=None, defer=None, fold=None):
     every consumer of the packs launches it itself if no relfeat forward came in between.
     fold: per branch the processor scale -- the same launch ALSO packs the decoders' first layers and the head's with the
     encoders' last layer folded in (fused_pinnsf(..., sums=True) / PIML_POOL_TRAIN); None: plain images only."""
-    import ctypes
     enc_w = [[_gpu_f32('encoder weight', t.detach()) for t in wb] for wb in enc_w]
     dec_w = [[_gpu_f32('decoder weight', t.detach()) for t in wb] for wb in dec_w]
     head_w = None if head_w is None else [_gpu_f32('head weight', t.detach()) for t in head_w]
@@ -2691,7 +2626,6 @@ class _FusedPinnsf(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, need_grad, nbr, scales, tau, fold_epilogue, packs, nhead, keeps, sums, self_features, *tensors):
-        import ctypes
         L = _lib.lib()
         PER = _FusedPinnsf.PER
         xs = [tensors[PER * b] for b in range(nbr)]
@@ -2857,7 +2791,6 @@ class _FusedPinnsf(torch.autograd.Function):
                 estructs.append(_enc_branch_struct(x2s[b], ks[b], scales[b], ewb[b], None, h1s[b], h2s[b], g_pooled[b], gm,
                                                    g2, g1, gx, packed=epack[b], keep_bits=ctx.keeps[b]))
             earr = (_lib.EncoderBranch * len(live))(*estructs)
-            import ctypes
             w0 = ctypes.c_int(0)
             total = L.piml_encoder_workgroups(earr, len(live), ctypes.byref(w0))
             slots = [w0.value, total - w0.value] if len(live) == 2 else [total]
@@ -2941,7 +2874,6 @@ class _FusedPinnsf(torch.autograd.Function):
 def _backward_sums(ctx, g_acc, g_coll, grads, x2s, masks, pooled, dh1, dd2, ewb, dwb, epack, dpack, sf):
     """Backward of a PIML_POOL_TRAIN forward (fused_pinnsf(..., sums=True)): decoder tails with the folded first layer ->
     one-pass encoder backward on G2 = d/d(sum)[agent] * [h2 > 0] -> slot sums -> the folded layers' gradients unfolded."""
-    import ctypes
     nbr, scales, tau, fold, ks, xshapes, sf_shape, agents, need_grad, nhead = ctx.meta
     PER, FIRST = _FusedPinnsf.PER, _FusedPinnsf.FIRST
     if g_coll is not None:
@@ -3108,7 +3040,6 @@ def fused_pinnsf_pooled(branches, self_features, tau, fold_epilogue=True, packs=
     (w1', b1', w2, b2, wp, bp) and `scale` is not applied again.  packs: a PinnsfPacks prepacked from these very tensors.
     Returns acc (..., N, 2), or None when the library does not serve the configuration (k other than 6 / 10, few rows, f32
     matrix instruction): the caller then takes fused_pinnsf."""
-    import ctypes
     if torch.is_grad_enabled() and any(t.requires_grad for b in branches for t in (b['x'], *b['encoder'], *b['decoder'])):
         raise ValueError('fused_pinnsf_pooled is an inference path: call it under torch.no_grad()')
     L = _lib.lib()
@@ -3330,7 +3261,6 @@ class _CollisionHead64(torch.autograd.Function):
         H.x, H.rows = x2.data_ptr(), rows
         H.w1, H.b1, H.w2, H.b2 = [t.data_ptr() for t in wb]
         H.hidden, H.out = _ptr(hidden), out.data_ptr()
-        import ctypes
         with torch.cuda.device(x2.device):
             _lib.check(L.piml_head64_fwd(ctypes.byref(H), _stream()), 'piml_head64_fwd')
         if need_grad:
@@ -3346,7 +3276,6 @@ class _CollisionHead64(torch.autograd.Function):
     def backward(ctx, g):
         if g is None:
             return (None,) * 5
-        import ctypes
         L = _lib.lib()
         x2, hidden, out, w1, b1, w2, b2 = ctx.saved_tensors
         rows = x2.shape[0]
@@ -3391,7 +3320,6 @@ class _Corrector(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, enc, scale, keep_bits, *weights):
-        import ctypes
         L = _lib.lib()
         e2 = _gpu_f32('enc', enc)
         k = e2.shape[-2]
@@ -3427,7 +3355,6 @@ class _Corrector(torch.autograd.Function):
     def backward(ctx, g):
         if g is None:
             return (None,) * 11
-        import ctypes
         L = _lib.lib()
         e2, hid, score, attn, pooled, chid, *wb = ctx.saved_tensors
         enc_shape, agents, k, scale = ctx.meta
