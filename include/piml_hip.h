@@ -632,19 +632,32 @@ int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, vo
  *   PIML_SPAWN_UNIT2       scenarios.py:189-215: side / direction by u < side_ratio / u < direction_ratio, heading (+-1, 0)
  *   PIML_SPAWN_UNIT3       scenarios.py:248-282: stream 1 as UNIT1; stream 2 (0..spawn_cap2 per frame, thresholds2) from
  *                          (length u, 0) -> (x + 2u - 1, width), heading (0, 1)
+ *   PIML_SPAWN_CLIP        a recorded clip's arrivals resampled (a bootstrap of its tracks; no reference counterpart).
+ *                          s->entries is the track table, (E, P, 2) float32 with P = 3 + D, one row per recorded track:
+ *                          point 0 the position at the track's first frame inside the window, point 1 the velocity at that
+ *                          frame, point 2 (desired_speed, 0), points 3 .. 3+D-1 the waypoints from that frame on (NaN =
+ *                          none; the last non-NaN one is the destination).  Rows [0, n_initial) are the tracks present at
+ *                          the window's first frame: the init launch places row i in slot i, nothing drawn.  Rows
+ *                          [n_initial, E) are the Ka = E - n_initial arrival rows: a new agent of ordinal n takes row
+ *                          n_initial + ((u24 Ka) >> 24) of its own Philox draw (integer arithmetic), origin = the row's +
+ *                          spawn_offset (2u - 1, 2u - 1) (the row's bitwise when spawn_offset == 0), velocity the row's
+ *                          (0 unless initial_velocity), desired speed the row's: uniform_speed, speed_mean, speed_std,
+ *                          speed_min and speed_clamp are not read.  The per-frame count is stream 1's, as every law's.
+ *                          Any arrival rule but PIML_ARRIVE_GC.
  * arrival_rule: PIML_ARRIVE_RADIUS |p' - dest| < arrival_radius -> flag += 1; PIML_ARRIVE_XBAND |p'.x - dest.x| <
  * arrival_radius -> flag += 1; PIML_ARRIVE_XEXIT p'.x > length retires the agent (flag unchanged).  Retirement as
  * piml_scenario_step (flag == D or waypoint[flag] NaN; or the x exit).
  * initial_velocity: 0 = v0 vector 0, 1 = heading * v0 (the velocity of the spawn frame and the newest history slot; older
  * slots 0).  speed_clamp: 1 = v0 = max(speed_min, speed_mean + speed_std z), 0 = no clamp (uniform_speed: v0 = speed_mean).
- * entries, route_polyline and exit_idx are not read (may be NULL).
+ * entries (but for PIML_SPAWN_CLIP's table), route_polyline and exit_idx are not read (may be NULL).
  * hipErrorInvalidValue: s or r NULL; the checks of piml_scenario_step except D (1..8 here, >= 2 for the crosswalk) and
  * E, P, R, route_max_iters, entries, route_polyline, exit_idx; spawn_law / arrival_rule unknown or one GC and the other
  * not; initial_velocity or speed_clamp not 0 / 1; spawn_cap2 outside 0..8 or non-zero for a law other than UNIT3;
- * thresholds2 above 2^24 or decreasing; the square's grid outside 1..32 or n_initial != 4 grid^2.
+ * thresholds2 above 2^24 or decreasing; the square's grid outside 1..32 or n_initial != 4 grid^2; for PIML_SPAWN_CLIP a
+ * NULL entries, P != 3 + D, n_initial > E, no arrival row (E == n_initial) with spawn_cap > 0, more than 2^24 arrival rows.
  */
 enum { PIML_SPAWN_GC = 0, PIML_SPAWN_CROSSWALK = 1, PIML_SPAWN_SQUARE = 2, PIML_SPAWN_UNIT1 = 3, PIML_SPAWN_UNIT2 = 4,
-       PIML_SPAWN_UNIT3 = 5 };
+       PIML_SPAWN_UNIT3 = 5, PIML_SPAWN_CLIP = 6 };
 enum { PIML_ARRIVE_GC = 0, PIML_ARRIVE_RADIUS = 1, PIML_ARRIVE_XBAND = 2, PIML_ARRIVE_XEXIT = 3 };
 typedef struct piml_scenario_rules {
     int spawn_law, arrival_rule, initial_velocity, speed_clamp;

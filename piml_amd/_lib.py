@@ -84,7 +84,7 @@ class MlapmLaw(ctypes.Structure):
     _fields_ = [('variant', _i), ('tau', _f), ('A', _f), ('B', _f), ('C', _f), ('D', _f), ('theta_deg', _f), ('radius', _f)]
 
 
-SPAWN_LAWS = {'gc': 0, 'crosswalk': 1, 'square': 2, 'unit1': 3, 'unit2': 4, 'unit3': 5}      # PIML_SPAWN_*
+SPAWN_LAWS = {'gc': 0, 'crosswalk': 1, 'square': 2, 'unit1': 3, 'unit2': 4, 'unit3': 5, 'clip': 6}     # PIML_SPAWN_*
 ARRIVAL_RULES = {'gc': 0, 'radius': 1, 'x_band': 2, 'x_exit': 3}                             # PIML_ARRIVE_*
 
 

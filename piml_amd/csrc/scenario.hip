@@ -55,6 +55,14 @@
 //   square cell c's key         (c, 0, 0, 0x5CE10003) word 0: randperm(grid^2)[c] = rank of key c among the grid^2 keys,
 //                               ties by cell index (each init wave counts its own cell's rank)
 //
+// The clip law's randomness (PIML_SPAWN_CLIP, a bootstrap of a recorded clip's arrivals; the table layout is in
+// include/piml_hip.h): c3 = 0x5CE20000 | sub, key = (seed lo, seed hi).  The spawn count of a frame is the scene rules'
+// stream-1 draw above (0x5CE10000 word 0); there is no second stream.
+//   agent of ordinal n, call 1  (n lo, n hi, 0, 0x5CE20001): arrival row n_initial + (((w0 >> 8) Ka) >> 24) (64-bit integer
+//                               product, Ka = E - n_initial <= 2^24 arrival rows: exact, every row reachable), origin =
+//                               the row's + spawn_offset (2 u(w1) - 1, 2 u(w2) - 1) (not added when spawn_offset == 0)
+// The init launch draws nothing: slot i < n_initial is row i.
+//
 // Members: the descriptor's per-member pointers are the bases of member-major buffers, member m's slice of each having
 // exactly the single-run layout -- state (members, capacity, .), waypoints (members, D, capacity, 2), exit_idx
 // (members, D, capacity), recorded outputs (members, T, capacity, .), spawn_out (members, T), spawned (members, 2),
@@ -76,6 +84,8 @@ namespace piml {
 
 constexpr unsigned kScenarioStream = 0x5CE00000u;
 constexpr unsigned kRulesStream = 0x5CE10000u;
+constexpr unsigned kClipStream = 0x5CE20000u;
+constexpr unsigned kClipMaxArrivals = 1u << 24; // arrival rows the 24-bit row draw reaches
 constexpr int kRulesMaxGrid = 32;
 constexpr int kScenarioMaxSpawn = 8;       // spawn_cap bound (the Poisson inversion's cap)
 constexpr int kScenarioMaxD = 8;
@@ -356,6 +366,40 @@ __global__ __launch_bounds__(256) void scenario_route_kernel(const float2* __res
 // 2 u - 1 of torch's (2 * torch.rand(n) - 1)
 __device__ __forceinline__ float jitter(unsigned w) { return __fsub_rn(__fmul_rn(2.f, unit24(w)), 1.f); }
 
+// what a scene rule's spawn writes, one wave: slot `ord`'s state (flag 0, mask 1, a = 0, destination = waypoint 0), its
+// waypoints way(q), q < D, the record of frame f, and the history / self_features row -- the spawn frame's velocity in the
+// newest slot, older slots 0 (make_dataset on add_pedestrians' zero fill)
+template <class Way>
+__device__ __forceinline__ void rules_spawn_write(const piml_scenario& S, long long ord, long long f, float2 o, float2 vel,
+                                                  float v0, Way way) {
+    const int lane = lane_id();
+    const size_t cap = (size_t)S.capacity, i = (size_t)ord;
+    for (int q = lane; q < S.D; q += 64) ((float2*)S.waypoints)[q * cap + i] = way(q);
+    if (lane == 0) {
+        const float2 d0 = way(0);
+        ((float2*)S.position)[i] = o;
+        ((float2*)S.velocity)[i] = vel;
+        ((float2*)S.acceleration)[i] = make_float2(0.f, 0.f);
+        ((float2*)S.destination)[i] = d0;
+        S.desired_speed[i] = v0;
+        S.flag[i] = 0;
+        S.mask[i] = 1.f;
+        if (S.spawn_iters) S.spawn_iters[i] = 0;
+        if (f < S.T) {
+            const size_t fr = (size_t)f * cap + i;
+            ((float2*)S.position_out)[fr] = o;
+            ((float2*)S.velocity_out)[fr] = vel;
+            ((float2*)S.acceleration_out)[fr] = make_float2(0.f, 0.f);
+            ((float2*)S.destination_out)[fr] = d0;
+            S.mask_out[fr] = 1.f;
+        }
+    }
+    const int hw = S.hist_width;
+    for (int q = lane; q < hw; q += 64) S.hist_velocity[i * hw + q] = q == hw - 2 ? vel.x : (q == hw - 1 ? vel.y : 0.f);
+    for (int q = 2 + lane; q < S.F; q += 64)
+        S.self_features[i * S.F + q] = q == S.F - 1 ? v0 : (q == hw ? vel.x : (q == hw + 1 ? vel.y : 0.f));
+}
+
 // one wave: agent of ordinal `ord` (< capacity) of spawn stream `group` (0 / 1) appears in frame `f`
 __device__ void rules_spawn_agent(const piml_scenario& S, const piml_scenario_rules& R, long long ord, int group, long long f) {
     const int lane = lane_id();
@@ -417,40 +461,36 @@ __device__ void rules_spawn_agent(const piml_scenario& S, const piml_scenario_ru
     // (a zero heading component stays +0, as torch.zeros_like, also for the crosswalk's v0 <= 0)
     const float2 vel = R.initial_velocity ? make_float2(head.x != 0.f ? head.x * v0 : 0.f, head.y != 0.f ? head.y * v0 : 0.f)
                                           : make_float2(0.f, 0.f);
-    const size_t cap = (size_t)S.capacity, i = (size_t)ord;
-    for (int q = lane; q < S.D; q += 64)
-        ((float2*)S.waypoints)[q * cap + i] = q == 0 ? d0 : (q == 1 ? d1 : make_float2(qnan(), qnan()));
-    if (lane == 0) {
-        ((float2*)S.position)[i] = o;
-        ((float2*)S.velocity)[i] = vel;
-        ((float2*)S.acceleration)[i] = make_float2(0.f, 0.f);
-        ((float2*)S.destination)[i] = d0;
-        S.desired_speed[i] = v0;
-        S.flag[i] = 0;
-        S.mask[i] = 1.f;
-        if (S.spawn_iters) S.spawn_iters[i] = 0;
-        if (f < S.T) {
-            const size_t fr = (size_t)f * cap + i;
-            ((float2*)S.position_out)[fr] = o;
-            ((float2*)S.velocity_out)[fr] = vel;
-            ((float2*)S.acceleration_out)[fr] = make_float2(0.f, 0.f);
-            ((float2*)S.destination_out)[fr] = d0;
-            S.mask_out[fr] = 1.f;
-        }
+    rules_spawn_write(S, ord, f, o, vel, v0,
+                      [&](int q) { return q == 0 ? d0 : (q == 1 ? d1 : make_float2(qnan(), qnan())); });
+}
+
+// one wave: agent of ordinal `ord` (< capacity) of the clip law appears in frame `f`: row `ord` of the track table in the
+// init launch, otherwise an arrival row drawn from stream kClipStream (the file header's word layout)
+__device__ void clip_spawn_agent(const piml_scenario& S, const piml_scenario_rules& R, int init, long long ord, long long f) {
+    size_t row = (size_t)ord;
+    float2 off = make_float2(0.f, 0.f);
+    const bool moved = !init && S.spawn_offset != 0.f;       // (x + 0 would turn a -0 coordinate into +0)
+    if (!init) {
+        const PhiloxOut w = philox4x32_10((unsigned)ord, (unsigned)((unsigned long long)ord >> 32), 0u, kClipStream | 1u,
+                                          (unsigned)S.seed, (unsigned)(S.seed >> 32));
+        const unsigned long long Ka = (unsigned long long)(S.E - S.n_initial);
+        row = (size_t)S.n_initial + (size_t)(((unsigned long long)(w.x >> 8) * Ka) >> 24);
+        off = make_float2(__fmul_rn(S.spawn_offset, jitter(w.y)), __fmul_rn(S.spawn_offset, jitter(w.z)));
     }
-    // history: the spawn frame's velocity in the newest slot, older slots 0 (make_dataset on add_pedestrians' zero fill)
-    const int hw = S.hist_width;
-    for (int q = lane; q < hw; q += 64) S.hist_velocity[i * hw + q] = q == hw - 2 ? vel.x : (q == hw - 1 ? vel.y : 0.f);
-    for (int q = 2 + lane; q < S.F; q += 64)
-        S.self_features[i * S.F + q] = q == S.F - 1 ? v0 : (q == hw ? vel.x : (q == hw + 1 ? vel.y : 0.f));
+    const float2* r = (const float2*)S.entries + row * (size_t)S.P;
+    float2 o = r[0];
+    if (moved) o = make_float2(__fadd_rn(o.x, off.x), __fadd_rn(o.y, off.y));
+    const float2 vel = R.initial_velocity ? r[1] : make_float2(0.f, 0.f);
+    rules_spawn_write(S, ord, f, o, vel, r[2].x, [&](int q) { return r[3 + q]; });
 }
 
 // ---- the frame ----
 
 // a spawn block (b = blockIdx.x - agent_blocks) of member view S: the spawn count of frame f -- init: n_initial; GC: k of
-// stream 0x5CE0; a scene rule: k1 + k2 of stream 0x5CE1 --, its bookkeeping by one thread of block 0, then one wave per new
-// agent of ordinal n + j.  thr / R are the kernel arguments' (an indexed read of a local copy's table would put the whole
-// descriptor in scratch); ent: GC's entry points (LDS or global).
+// stream 0x5CE0; a scene rule (the clip law too): k1 + k2 of stream 0x5CE1 --, its bookkeeping by one thread of block 0,
+// then one wave per new agent of ordinal n + j.  thr / R are the kernel arguments' (an indexed read of a local copy's table
+// would put the whole descriptor in scratch); ent: GC's entry points (LDS or global).
 __device__ __forceinline__ void spawn_block(bool gc, const piml_scenario& S, const piml_scenario_rules& R, const uint32_t* thr,
                                             const float2* ent, int init, long long n, long long f, int b) {
     int k1 = S.n_initial, k2 = 0;
@@ -469,6 +509,7 @@ __device__ __forceinline__ void spawn_block(bool gc, const piml_scenario& S, con
     const int j = b * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
     if (j >= k || n + j >= S.capacity) return;               // ordinals past the capacity are dropped, never written
     if (gc) spawn_agent(S, ent, n + j, f);
+    else if (R.spawn_law == PIML_SPAWN_CLIP) clip_spawn_agent(S, R, init, n + j, f);
     else rules_spawn_agent(S, R, n + j, j >= k1, f);
 }
 
@@ -660,7 +701,7 @@ bool thresholds_ok(const uint32_t* thr, int cap) {
 // the checks of every frame entry (include/piml_hip.h); r == NULL is GC
 bool frame_args_ok(const piml_scenario& S, const piml_scenario_rules* r, const float* a_next, int init) {
     const bool gc = !r || r->spawn_law == PIML_SPAWN_GC;
-    if (r && (r->spawn_law < PIML_SPAWN_GC || r->spawn_law > PIML_SPAWN_UNIT3 || r->arrival_rule < PIML_ARRIVE_GC ||
+    if (r && (r->spawn_law < PIML_SPAWN_GC || r->spawn_law > PIML_SPAWN_CLIP || r->arrival_rule < PIML_ARRIVE_GC ||
               r->arrival_rule > PIML_ARRIVE_XEXIT || gc != (r->arrival_rule == PIML_ARRIVE_GC)))
         return false;
     if (S.capacity < 1 || S.T < 1 || S.hist_width < 2 || S.F != S.hist_width + 5 || S.D > piml::kScenarioMaxD ||
@@ -681,6 +722,10 @@ bool frame_args_ok(const piml_scenario& S, const piml_scenario_rules* r, const f
         (R.initial_velocity != 0 && R.initial_velocity != 1) || (R.speed_clamp != 0 && R.speed_clamp != 1))
         return false;
     if (R.spawn_law == PIML_SPAWN_SQUARE && (R.grid < 1 || R.grid > piml::kRulesMaxGrid || S.n_initial != 4 * R.grid * R.grid))
+        return false;
+    if (R.spawn_law == PIML_SPAWN_CLIP &&                    // the track table: (E, 3 + D, 2), rows n_initial.. the arrivals
+        (!S.entries || S.P != 3 + S.D || S.n_initial > S.E || (S.spawn_cap > 0 && S.E == S.n_initial) ||
+         (unsigned)(S.E - S.n_initial) > piml::kClipMaxArrivals))
         return false;
     return thresholds_ok(R.poisson_thresholds2, R.spawn_cap2);
 }

@@ -116,7 +116,8 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
 
 
 def scenario_rules(scenario):
-    """The piml_scenario_rules descriptor of a scene (its spawn law, arrival rule, velocity and speed laws, second stream)."""
+    """The piml_scenario_rules descriptor of a scene (its spawn law, arrival rule, velocity and speed laws, second stream).
+    The 'clip' law's track table is the scene's `entries`, which scenario_state puts into the piml_scenario descriptor."""
     r = _lib.ScenarioRules()
     if scenario.spawn_law not in _lib.SPAWN_LAWS or scenario.arrival_rule not in _lib.ARRIVAL_RULES:
         raise ValueError(f'unknown scene rule {scenario.spawn_law!r} / {scenario.arrival_rule!r}')

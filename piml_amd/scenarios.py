@@ -12,6 +12,9 @@ and an ensemble alike; `scenario_state_for` / `scenario_result` are every simula
 `ScenarioEnsemble` is what `BaseSimulator.simulate_ensemble` returns: S simulations of one scene (one per seed) with a
 leading member axis, each of them a `ScenarioResult` through `member(m)`.
 
+`clip_scenario(raw_data)` makes a scene of any recorded clip: its geometry, the agents of its first frame, and arrivals
+resampled from its own tracks (PIML_SPAWN_CLIP: the table of tracks travels in `entries`).
+
 `save_clip` writes a simulation as the reference's `RawData.save_data` does (src/data/data.py:305-341, version v2.2), so
 that `RawData.load_trajectory_data` -- here and in the reference -- reads it back as a training clip (`--iter_flag`).
 """
@@ -28,7 +31,7 @@ from . import scenes
 @dataclasses.dataclass
 class Scenario:
     """An entry / exit scene.  Tensors are float32; `to(device)` moves them."""
-    entries: torch.Tensor                  # (E, P, 2) sampled entry segments: origins and destinations
+    entries: torch.Tensor                  # (E, P, 2) sampled entry segments: origins and destinations ('clip': the track table)
     route_polyline: torch.Tensor           # (R, 2) what utils.route routes around
     obstacles: torch.Tensor                # (M, 2) every obstacle point the features see
     rate_per_s: float = 5.0                # Poisson arrivals per second
@@ -46,7 +49,7 @@ class Scenario:
     spawn_cap: int = 8                     # bound of the per-frame Poisson draw (inversion cap)
     name: str = ''
     # scene rule (piml_scenario_rules); the defaults are GC's
-    spawn_law: str = 'gc'                  # 'gc', 'crosswalk', 'square', 'unit1', 'unit2', 'unit3'
+    spawn_law: str = 'gc'                  # 'gc', 'crosswalk', 'square', 'unit1', 'unit2', 'unit3', 'clip'
     arrival_rule: str = 'gc'               # 'gc', 'radius' |p - dest| < r, 'x_band' |p.x - dest.x| < r, 'x_exit' x > length
     initial_velocity: bool = False         # spawn with velocity heading * v0 (else 0)
     speed_clamp: bool = True               # v0 = max(speed_min, ...) of a normal draw
@@ -211,6 +214,92 @@ def basic_unit3_scenario(length=20.0, width=10.0, time_unit=0.08, poisson_lambda
     first-stream agents take the lower ordinals.  `during` is unused."""
     return _basic_unit('unit3', 'radius', 1.0, length, width, time_unit, poisson_lambda, uniform_desired_speed, 'basic_unit3',
                        rate2_per_s=float(poisson_lambda2), spawn_cap2=8)
+
+
+CLIP_MAX_INITIAL = 4096                    # the frame's bound on n_initial
+CLIP_MAX_WAYPOINTS = 8                     # ... on D
+CLIP_MAX_SPAWN_CAP = 8                     # ... on spawn_cap
+CLIP_SPAWN_TAIL = 1e-6                     # the Poisson mass allowed beyond spawn_cap
+
+
+def _poisson_tail(lam, cap):
+    """P(K > cap), K ~ Poisson(lam)."""
+    p = math.exp(-lam)
+    cdf = p
+    for j in range(cap):
+        p *= lam / (j + 1)
+        cdf += p
+    return max(0.0, 1.0 - cdf)
+
+
+def clip_scenario(raw_data, frames=None, arrival_radius=1.0, jitter=0.0, initial_velocity=True, spawn_cap=8, skip_frames=25):
+    """A recorded clip as an open-world scene (spawn law 'clip', PIML_SPAWN_CLIP): its obstacles, time unit and D
+    waypoints; frame 0 holds the agents present at the window's first frame with the state they had there; afterwards
+    agents arrive as a Poisson process at the clip's own rate, each a draw (with replacement) from the tracks that first
+    appear later in the window -- origin (+ jitter * U(-1, 1)^2), velocity (0 unless initial_velocity), desired speed and
+    the waypoints still ahead of it.  Arrival is |p - dest| < arrival_radius.
+
+    raw_data: a `piml_amd.data.data.RawData` (position, velocity, mask_p, waypoints, dest_idx, obstacles, time_unit).
+    frames = (a, b): the window [a, b) of the clip (default: all of it).  The desired speed per agent is
+    `data.desired_speed_per_agent(velocity, skip_frames)` over the whole clip, the value the data pipeline feeds the network.
+    The table is `entries` (E, 3 + D, 2): per track (position, velocity, (desired_speed, 0), waypoints...), the
+    n_initial tracks of the first frame in clip order, then the Ka arrival tracks in clip order; the rate is
+    Ka / (b - a - 1) per frame (`fixed_spawn_rate`); no arrival track: spawn_cap 0, a closed scene.
+    ValueError: a window shorter than 2 frames or outside the clip, no track in the window, more than 4096 agents in its
+    first frame, D > 8, spawn_cap outside 0..8, or P(K > spawn_cap) > 1e-6 at the clip's rate (the frame caps a draw at
+    spawn_cap)."""
+    from .data.data import desired_speed_per_agent
+    pos = torch.as_tensor(raw_data.position).detach().float().cpu()
+    vel = torch.as_tensor(raw_data.velocity).detach().float().cpu()
+    msk = torch.as_tensor(raw_data.mask_p).detach().cpu() == 1
+    way = torch.as_tensor(raw_data.waypoints).detach().float().cpu()
+    T, N, D = pos.shape[0], pos.shape[1], way.shape[0]
+    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    if not 0 <= a < b <= T:
+        raise ValueError(f'clip_scenario: frames {(a, b)} outside the clip\'s 0..{T}')
+    if b - a < 2:
+        raise ValueError(f'clip_scenario: a window of at least 2 frames expected, got {(a, b)}')
+    if not 1 <= D <= CLIP_MAX_WAYPOINTS:
+        raise ValueError(f'clip_scenario: {D} waypoints per agent, 1..{CLIP_MAX_WAYPOINTS} supported')
+    if not 0 <= int(spawn_cap) <= CLIP_MAX_SPAWN_CAP:
+        raise ValueError(f'clip_scenario: spawn_cap {spawn_cap} outside 0..{CLIP_MAX_SPAWN_CAP} (the device limit)')
+    win = msk[a:b]
+    seen = win.any(0)
+    if not bool(seen.any()):
+        raise ValueError(f'clip_scenario: no track in frames {(a, b)}')
+    first = a + win.to(torch.uint8).argmax(0)                             # (N) first in-window frame
+    order = torch.cat(((seen & (first == a)).nonzero().flatten(), (seen & (first > a)).nonzero().flatten()))
+    n_initial = int((seen & (first == a)).sum())
+    Ka = order.numel() - n_initial
+    if n_initial > CLIP_MAX_INITIAL:
+        raise ValueError(f'clip_scenario: {n_initial} agents in frame {a}, more than {CLIP_MAX_INITIAL}')
+    rate = Ka / (b - a - 1)
+    cap = int(spawn_cap) if Ka else 0
+    if Ka and _poisson_tail(rate, cap) > CLIP_SPAWN_TAIL:
+        raise ValueError(f'clip_scenario: {rate:.4g} arrivals per frame: P(K > spawn_cap = {cap}) = '
+                         f'{_poisson_tail(rate, cap):.3g} > {CLIP_SPAWN_TAIL:g}; raise spawn_cap (at most '
+                         f'{CLIP_MAX_SPAWN_CAP}) or widen the window')
+    v0 = desired_speed_per_agent(vel, int(skip_frames))
+    f0 = first[order]
+    dest_idx = getattr(raw_data, 'dest_idx', None)
+    if dest_idx is not None:
+        k0 = torch.as_tensor(dest_idx).cpu().long()[f0, order]
+    else:                                     # (ScenarioResult.to_raw_data) the waypoint that is the destination there
+        d = torch.as_tensor(raw_data.destination).detach().float().cpu()[f0, order]
+        k0 = (torch.norm(way[:, order] - d.unsqueeze(0), dim=-1) < 0.01).to(torch.uint8).argmax(0)
+    table = torch.full((order.numel(), 3 + D, 2), float('nan'))
+    table[:, 0], table[:, 1] = pos[f0, order], vel[f0, order]
+    table[:, 2, 0], table[:, 2, 1] = v0[order], 0.0
+    q = k0.unsqueeze(1) + torch.arange(D).unsqueeze(0)                    # (E, D) waypoint index of table point 3 + j
+    rows = way[:, order].permute(1, 0, 2)                                 # (E, D, 2)
+    ahead = torch.gather(rows, 1, q.clamp(max=D - 1).unsqueeze(-1).expand(-1, -1, 2))
+    table[:, 3:] = torch.where((q < D).unsqueeze(-1), ahead, torch.full_like(ahead, float('nan')))
+    obs = torch.as_tensor(raw_data.obstacles).detach().float().cpu().reshape(-1, 2)
+    return Scenario(entries=table.contiguous(), route_polyline=torch.zeros(0, 2), obstacles=obs.contiguous(),
+                    time_unit=float(raw_data.time_unit), n_initial=n_initial, spawn_offset=float(jitter),
+                    arrival_radius=float(arrival_radius), num_waypoints=D, spawn_cap=cap, spawn_law='clip',
+                    arrival_rule='radius', initial_velocity=bool(initial_velocity), speed_clamp=False,
+                    fixed_spawn_rate=rate, name='clip')
 
 
 SCENARIOS = {'gc': gc_scenario, 'crosswalk': crosswalk_scenario, 'four_directional_square': four_directional_square_scenario,

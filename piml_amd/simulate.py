@@ -1,6 +1,6 @@
 """Open-world crowd simulation with a trained PINNSF or the closed-form MLAPM law: generate a scene (default: the Grand
-Central hall; --scenario crosswalk, four_directional_square, basic_unit1..3 for the reference's synthetic scenes), simulate
-it on the GPU and save the result as a v2.2 clip that `RawData.load_trajectory_data` (and so `--iter_flag` pre-training)
+Central hall; --scenario crosswalk, four_directional_square, basic_unit1..3 for the reference's synthetic scenes;
+--scene-from CLIP.npy for a recorded clip's geometry, first frame and resampled arrivals), simulate it on the GPU and save the result as a v2.2 clip that `RawData.load_trajectory_data` (and so `--iter_flag` pre-training)
 reads.
 
     python -m piml_amd.simulate --checkpoint model.pt --frames 750 --out clip.npy [model flags of piml_amd.main]
@@ -8,6 +8,7 @@ reads.
     python -m piml_amd.simulate --law mlapm --params params.json --out clip.npy     (MLAPM; params: `calibrate --out`)
     python -m piml_amd.simulate --seeds 0:32 --stats stats.json      (crowd statistics of the run, no clips written)
     python -m piml_amd.simulate --seeds 0:32 --pair-stats pairs.json      (time-to-collision statistics, no clips written)
+    python -m piml_amd.simulate --law mlapm --scene-from ucy.npy --seeds 0:32 --pair-stats sim.json   (a clip as the scene)
 
 Model flags (--model, --hidden sizes, --topk_*, --num_history_velocity, ...) are those of `piml_amd.main`, with its
 defaults.  Without --checkpoint the network keeps its initial weights (a smoke run)."""
@@ -35,6 +36,13 @@ def get_args(argv=None):
     p.add_argument('--mlapm_radius', type=float, default=0.3,
                    help="--law mlapm: MLAPM's UCY collision radius (not the scene's arrival radius)")
     p.add_argument('--scenario', type=str, default='gc', choices=sorted(SCENARIOS.SCENARIOS))
+    p.add_argument('--scene-from', dest='scene_from', type=str, default=None,
+                   help='build the scene from this recorded v2.2 clip instead of --scenario (scenarios.clip_scenario): its '
+                        'obstacles, the agents of its first frame, arrivals resampled from its own tracks at its own rate')
+    p.add_argument('--scene-frames', dest='scene_frames', type=str, default=None,
+                   help="--scene-from: the window 'a:b' of the clip's frames (default: all)")
+    p.add_argument('--scene-jitter', dest='scene_jitter', type=float, default=0.0,
+                   help='--scene-from: arrivals start within +- this many metres of the recorded origin (default 0)')
     p.add_argument('--frames', type=int, default=750)
     seed = p.add_mutually_exclusive_group()
     seed.add_argument('--seed', type=int, default=0, help='seed of the spawn schedule')
@@ -59,6 +67,17 @@ def get_args(argv=None):
             p.error(f'--seeds: {ex}')
         if '{seed}' not in own.out and own.stats is None and own.pair_stats is None:
             p.error("--seeds: --out must contain '{seed}' (one clip per seed)")
+    if own.scene_from is not None:
+        if own.scenario != p.get_default('scenario'):
+            p.error('--scene-from builds the scene from a clip: not with --scenario')
+        if own.scene_frames is not None:
+            try:
+                a, b = (int(x) for x in own.scene_frames.split(':'))
+            except ValueError:
+                p.error(f"--scene-frames: 'a:b' expected, got {own.scene_frames!r}")
+            own.scene_frames = (a, b)
+    elif own.scene_frames is not None or own.scene_jitter != 0.0:
+        p.error('--scene-frames / --scene-jitter need --scene-from')
     if own.law == 'mlapm':
         if own.checkpoint:
             p.error('--checkpoint is a PINNSF state_dict: not with --law mlapm (use --params)')
@@ -140,8 +159,12 @@ def main(argv=None):
             sim.model.load_state_dict(torch.load(own.checkpoint, map_location=args.device))
         sim.model.eval()
         run_kw = {}
-    kw = {} if own.uniform_desired_speed is None else {'uniform_desired_speed': own.uniform_desired_speed}
-    scenario = SCENARIOS.SCENARIOS[own.scenario](time_unit=own.time_unit, **kw)
+    if own.scene_from is not None:
+        scenario = _clip_scene(own)
+        own.scenario = scenario.name
+    else:
+        kw = {} if own.uniform_desired_speed is None else {'uniform_desired_speed': own.uniform_desired_speed}
+        scenario = SCENARIOS.SCENARIOS[own.scenario](time_unit=own.time_unit, **kw)
     if own.seeds is not None:
         return _ensemble(sim, scenario, own, args, run_kw)
     res = sim.simulate_scenario(scenario, own.frames, seed=own.seed, capacity=own.capacity, **run_kw)
@@ -151,6 +174,18 @@ def main(argv=None):
         res.save_data(own.out)
     _report(own.scenario, own.frames, res, args.collision_threshold, _stats_path(own) or own.out)
     return res
+
+
+def _clip_scene(own):
+    """--scene-from: scenarios.clip_scenario of the clip (its own time unit and desired speeds; --time_unit and
+    --uniform_desired_speed do not apply)."""
+    from .data.data import RawData
+    raw = RawData()
+    raw.load_trajectory_data(own.scene_from)
+    try:
+        return SCENARIOS.clip_scenario(raw, frames=own.scene_frames, jitter=own.scene_jitter)
+    except ValueError as ex:
+        sys.exit(f'--scene-from {own.scene_from}: {ex}')
 
 
 def _stats_path(own):
