@@ -717,6 +717,32 @@ int piml_scenario_step_mlapm(const piml_scenario* s, const piml_scenario_rules* 
                              const piml_mlapm_law* law, int frame_offset, void* stream);
 
 /*
+ * One law per ensemble member (ABI 35, additive): piml_scenario_step_mlapm with member m stepping under row m of a table
+ * of laws, so a parameter sweep, a sensitivity study or a population of candidates is ONE ensemble run -- in place of one
+ * run of the loop of src/main_mlapm.py:18-36 per parameter set, which is what the reference's src/utils/grid_search.py
+ * does (one process per grid point).
+ * The table holds each law's DERIVED constants (cos / sin of theta, B, C, D times log2 e, twice the radius, the absent-source
+ * switch), formed on the host by the same code as piml_scenario_step_mlapm's launch, so member m of a table run is bitwise
+ * the member of a piml_scenario_step_mlapm run under laws[m].  The row layout is private: size it with
+ * piml_mlapm_law_table_bytes(n) (n rows; -1 for n < 0) and fill it with piml_mlapm_law_table_fill.
+ * piml_mlapm_law_table_fill(laws, n, table_host): HOST to HOST, no stream and no GPU call (it runs on a machine without a
+ * GPU).  hipErrorInvalidValue with table_host untouched: n < 0, a NULL pointer with n > 0, or any law that
+ * piml_scenario_step_mlapm rejects (variant not 0 / 1 / 2; tau not finite and > 0; A, B, C, D or theta_deg not finite;
+ * radius not finite and > 0); every law is checked before the first row is written.
+ * piml_scenario_step_mlapm_laws: table_device = the filled bytes in device memory (the caller's upload), `members` rows.
+ * The kernel reads member m's row on every launch (scalar loads; members may differ in variant): overwriting the buffer
+ * in place between two replays of a captured graph changes the law of the later frames, with no re-capture.
+ * hipErrorInvalidValue (before any launch): every frame check of piml_scenario_step_mlapm, NULL table_device.  The entry
+ * CANNOT validate the table's contents, which live in device memory: that is piml_mlapm_law_table_fill's job, and bytes
+ * from anywhere else are undefined behaviour of the force law (not of memory: a row indexes nothing).
+ * No atomics; capturable; no scratch.
+ */
+long long piml_mlapm_law_table_bytes(int n);
+int piml_mlapm_law_table_fill(const piml_mlapm_law* laws, int n, void* table_host);
+int piml_scenario_step_mlapm_laws(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                                  const void* table_device, int frame_offset, void* stream);
+
+/*
  * utils.route (src/utils/utils.py:141-165) for n (o, d) pairs, one wave each, the device function the spawn path uses:
  * the segment o -> r is tested against the polyline's R-1 segments, the hit with the smallest alpha moves r to
  * crossing + clearance * normal, until nothing is hit or max_iters moves were made.  float32 in the reference's order.

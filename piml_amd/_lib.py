@@ -130,6 +130,9 @@ SIGNATURES = {
     'piml_scenario_step_rules': [_p, _p, _p, _i, _p],
     'piml_scenario_step_members': [_p, _p, _i, _p, _p, _i, _p],
     'piml_scenario_step_mlapm': [_p, _p, _i, _p, _p, _i, _p],
+    'piml_mlapm_law_table_bytes': [_i],
+    'piml_mlapm_law_table_fill': [_p, _i, _p],
+    'piml_scenario_step_mlapm_laws': [_p, _p, _i, _p, _p, _i, _p],
     'piml_scenario_route': [_p, _p, _i, _p, _i, _i, _f, _p, _p, _p],
     'piml_collision_correction_fwd': [_p, _p, _p, _z, _i, _i, _f, _f, _p, _p],
     'piml_collision_correction_bwd': [_p, _p, _p, _p, _z, _i, _i, _f, _f, _p, _p, _p, _p],
@@ -289,6 +292,7 @@ def lib():
         L.piml_mlapm_rollout_fit_workspace_doubles.restype = _ll
         L.piml_crowd_stats_workspace_bytes.restype = _ll
         L.piml_pair_stats_workspace_bytes.restype = _ll
+        L.piml_mlapm_law_table_bytes.restype = _ll
         L.piml_error_string.argtypes = [_i]
         L.piml_error_string.restype = ctypes.c_char_p
         if L.piml_abi_version() != ABI_VERSION:

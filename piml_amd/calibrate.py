@@ -10,7 +10,16 @@ residual of one MLAPM.step per (frame, agent) against the agent's velocity in th
 respect to the constants is analytic (piml_mlapm_fit_loss_grad, one pass over the pairs).  With --horizon H the loss is
 instead the mean squared position error of H closed-loop MLAPM steps per window, the law's own errors fed back through
 the neighbours as `simulate --law mlapm` runs it (piml_mlapm_rollout_fit_loss_grad, forward and adjoint in one launch).
-`MLAPM(**result.params)` simulates with the result."""
+`MLAPM(**result.params)` simulates with the result.
+
+    python -m piml_amd.calibrate --data clip.npy --version UCY --match-stats [--match crowd,pairs] [--scene-frames a:b]
+                                 [--scene-jitter x] [--seeds 0:8] [--population 16] [--generations 30] [--search-seed 0]
+                                 [--init ...] [--fit A,B] --out params.json
+
+--match-stats fits the law to crowd statistics instead of trajectories (calibrate_mlapm_to_stats): the clip becomes an
+open-world scene (scenarios.clip_scenario), every generation of a derivative-free search runs population x seeds members
+in one ensemble (MLAPM.simulate_sweep's law table), and the objective is the distance between each candidate's pooled
+crowd / pair statistics and the clip's own (stats_objective)."""
 import argparse
 import json
 import math
@@ -284,7 +293,8 @@ def mlapm_rollout_fit_loss(pack, params, version='GC', dt=None, radius=0.3, time
 class CalibrationResult(types.SimpleNamespace):
     """params: {'version', 'tau', 'A', 'B', 'C', 'D', 'theta'} -- `MLAPM(**params)` as is; initial_loss / final_loss;
     history: the loss before each optimiser step; steps; fit: the names that were fitted; horizon: None (one-step
-    velocity loss) or the rollout length of the position loss."""
+    velocity loss) or the rollout length of the position loss.  calibrate_mlapm_to_stats: history is the best objective
+    so far per generation, and terms, generations, population, seeds and status are added."""
 
 
 def calibrate_mlapm(data, version='GC', init=None, fit=PARAM_NAMES, steps=500, lr=0.02, lr_final=0.01, use_graph=True,
@@ -394,6 +404,220 @@ def calibrate_mlapm(data, version='GC', init=None, fit=PARAM_NAMES, steps=500, l
                              history=hist[:steps].cpu().tolist(), steps=steps, fit=tuple(fit), horizon=horizon)
 
 
+OBJECTIVE_KEYS = {'crowd': ('fd_distance', 'map_distance', 'mean_speed_diff'),
+                  'pairs': ('ttc_l1', 'nn_l1', 'overlap_rate_diff')}
+DEFAULT_BOUNDS = {'tau': (1e-3, None)}
+
+
+def stats_objective(crowd=None, pairs=None, ref_crowd=None, ref_pairs=None, weights=None, min_count=50):
+    """(J, terms): how far simulated statistics are from a reference's.  crowd / ref_crowd: CrowdStats, pairs / ref_pairs:
+    PairStats; a side takes part when both of its statistics are given.  terms is the union of compare_crowd_stats(crowd,
+    ref_crowd, min_count) and compare_pair_stats(pairs, ref_pairs, min_count) for the sides given, and
+    J = sum_k w_k |terms[k]| over fd_distance, map_distance, mean_speed_diff (crowd) and ttc_l1, nn_l1, overlap_rate_diff
+    (pairs), every weight 1.0 unless `weights` names it.  map_distance is left out when it is None (no common map); a NaN
+    term of non-zero weight makes J = inf.  ValueError: no side given, or a weight for an unknown key."""
+    from .crowdstats import compare_crowd_stats
+    from .pairstats import compare_pair_stats
+    known = OBJECTIVE_KEYS['crowd'] + OBJECTIVE_KEYS['pairs']
+    unknown = sorted(set(weights or {}) - set(known))
+    if unknown:
+        raise ValueError(f'stats_objective: weights for unknown terms {unknown} (of {known})')
+    terms, keys = {}, []
+    if crowd is not None and ref_crowd is not None:
+        terms.update(compare_crowd_stats(crowd, ref_crowd, min_count))
+        keys += OBJECTIVE_KEYS['crowd']
+    if pairs is not None and ref_pairs is not None:
+        terms.update(compare_pair_stats(pairs, ref_pairs, min_count))
+        keys += OBJECTIVE_KEYS['pairs']
+    if not keys:
+        raise ValueError('stats_objective: neither crowd nor pair statistics with a reference')
+    J = 0.0
+    for k in keys:
+        w = float((weights or {}).get(k, 1.0))
+        if terms[k] is None or w == 0.0:
+            continue
+        if math.isnan(terms[k]):
+            return float('inf'), terms
+        J += w * abs(float(terms[k]))
+    return J, terms
+
+
+def _options_of(stats, keys):
+    return {k: stats.options[k] for k in keys}
+
+
+class _StatsEvaluator:
+    """calibrate_mlapm_to_stats' objective on the GPU: list of candidate dicts -> list of J, one SweepRun generation each."""
+
+    def __init__(self, scenario, reference, frames, seeds, population, radius, capacity, crowd_kw, pair_kw, weights,
+                 min_count, device):
+        from . import crowdstats, pairstats
+        from .models.mlapm import SweepRun
+        if isinstance(reference, (tuple, list)):
+            self.ref_crowd, self.ref_pairs = reference
+            if crowd_kw is None and self.ref_crowd is not None:
+                crowd_kw = _options_of(self.ref_crowd, ('radius', 'box', 'cell', 'rho_bin', 'rho_bins'))
+            if pair_kw is None and self.ref_pairs is not None:
+                pair_kw = _options_of(self.ref_pairs, ('radius', 'lags', 'tau_bin', 'tau_bins', 'r_bin', 'r_bins', 'r_max',
+                                                       'box'))
+        else:                                     # a RawData: its own statistics, the crowd box its bounding box
+            crowd_kw = dict(crowd_kw or {})
+            if crowd_kw.get('box') is None:
+                crowd_kw['box'] = crowdstats.auto_box(torch.as_tensor(reference.position).cpu().numpy(),
+                                                      torch.as_tensor(reference.mask_p).cpu().numpy(),
+                                                      crowd_kw.get('cell', 0.5))
+            self.ref_crowd = crowdstats.crowd_stats_of_raw(reference, **crowd_kw)
+            self.ref_pairs = pairstats.pair_stats_of_raw(reference, **dict(pair_kw or {}))
+            if frames is None:
+                frames = int(torch.as_tensor(reference.position).shape[0])
+        if self.ref_crowd is None and self.ref_pairs is None:
+            raise ValueError('calibrate_mlapm_to_stats: the reference holds no statistics')
+        self.crowd_kw, self.pair_kw = dict(crowd_kw or {}), dict(pair_kw or {})
+        self.weights, self.min_count, self.radius = weights, min_count, radius
+        self.frames = 200 if frames is None else int(frames)
+        self.run = SweepRun(scenario, self.frames, population, seeds, capacity=capacity, device=device)
+        self.seconds = {'run': 0.0, 'crowd': 0.0, 'pairs': 0.0, 'host': 0.0}
+        self.last_terms = []
+
+    def __call__(self, cands):
+        import time
+        t0 = time.perf_counter()
+        sw = self.run.run(cands, self.radius)
+        # one reduction: a member with a non-finite position or velocity in a present slot is an exploded run
+        bad = ((~(torch.isfinite(sw.position).all(-1) & torch.isfinite(sw.velocity).all(-1))) & (sw.mask_p != 0)) \
+            .flatten(1).any(1)
+        bad_host = bad.cpu().tolist()                                         # (synchronises: the run is done)
+        t1 = time.perf_counter()
+        mask = sw.mask_p
+        if any(bad_host):                          # never hand an exploded member to the statistics kernels as it is
+            mask = mask.clone()
+            mask[bad] = 0.0
+        n_active = [min(int(n), sw.capacity) for n in sw.spawned]
+        crowd = pairs = None
+        if self.ref_crowd is not None:
+            from .crowdstats import crowd_stats
+            crowd = crowd_stats(sw.position, sw.velocity, mask, n_active=n_active, **self.crowd_kw)
+        t2 = time.perf_counter()
+        if self.ref_pairs is not None:
+            from .pairstats import pair_stats
+            pairs = pair_stats(sw.position, sw.velocity, mask, n_active=n_active, **self.pair_kw)
+        t3 = time.perf_counter()
+        out, self.last_terms = [], []
+        for c in range(sw.n_candidates):
+            group = sw.members_of(c)
+            if any(bad_host[m] for m in group):
+                out.append(float('inf'))
+                self.last_terms.append({'exploded': True})
+                continue
+            J, terms = stats_objective(None if crowd is None else crowd.select(group).pooled(),
+                                       None if pairs is None else pairs.select(group).pooled(),
+                                       self.ref_crowd, self.ref_pairs, self.weights, self.min_count)
+            out.append(J)
+            self.last_terms.append(terms)
+        t4 = time.perf_counter()
+        for k, dt in zip(('run', 'crowd', 'pairs', 'host'), (t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
+            self.seconds[k] += dt
+        return out
+
+
+def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=PARAM_NAMES, frames=None, seeds=range(8),
+                             population=16, generations=30, elite=0.25, sigma=0.2, sigma_floor=1e-3, bounds=None,
+                             weights=None, crowd_kw=None, pair_kw=None, search_seed=0, radius=0.3, capacity=None,
+                             evaluate=None, min_count=50, device='cuda'):
+    """Fit MLAPM's constants so that the law, run open-world in `scenario`, reproduces the reference's crowd statistics.
+
+    reference: a RawData (its crowd_stats / pair_stats are taken with crowd_kw / pair_kw, the crowd box defaulting to
+    crowdstats.auto_box of the recording, and the simulated side uses the same options, so the maps are comparable) or a
+    pair (CrowdStats | None, PairStats | None) (a None side takes no part; the simulated side then uses the reference's
+    own options unless crowd_kw / pair_kw are given).  frames: the simulated frames (default: the recording's length, 200
+    for a statistics pair).  The objective of a candidate is stats_objective of its members' statistics pooled over
+    `seeds` (weights, min_count).
+    The search is a cross-entropy method, deterministic under numpy.random.default_rng(search_seed), in calibrate_mlapm's
+    scaled space x = p / scale, scale = |init| (1 where init is 0): only the `fit` names move, the other constants are
+    carried through bit for bit.  Every generation evaluates `population` candidates -- candidate 0 is the best seen so
+    far (generation 0: init), the others mean + sigma z per coordinate, clipped to bounds ({name: (lo, hi)}, None = open;
+    tau >= 1e-3 unless overridden) -- and then the mean becomes that of the best ceil(elite * population) candidates with a
+    finite objective and the per-coordinate sigma their RMS distance from the previous mean (never below sigma_floor).  A generation is ONE ensemble run of population
+    x len(seeds) members: the candidates' law table is overwritten in place, the captured frames are replayed from an
+    emptied state (models.mlapm.SweepRun), one crowd_stats and one pair_stats call cover every member, and a candidate
+    with a non-finite position or velocity in a present slot of any of its members gets J = inf (its members reach the
+    statistics kernels with their masks zeroed).
+    evaluate: a callable list[dict] -> list[float] that replaces the simulation (the search then makes no GPU call;
+    scenario and reference may be None).
+    Not a gradient method (arrivals and retirements are not differentiable); the result is tuned to the chosen seeds
+    (common random numbers), and is identified no better than the statistics allow.
+    Returns a CalibrationResult: params, initial_loss (init's objective), final_loss, history (the best objective so far
+    after each generation, non-increasing), fit, terms (the best candidate's term dict; None with `evaluate`),
+    generations, population, seeds, status ('ok', or that no candidate had a finite objective and init was kept)."""
+    import numpy as np
+    from . import ops
+    if version not in ops.MLAPM_VARIANTS:
+        raise NotImplementedError(version)
+    fit = tuple(fit)
+    unknown = [k for k in fit if k not in PARAM_NAMES]
+    if unknown or not fit:
+        raise ValueError(f'constants to fit: names of {PARAM_NAMES} expected, got {fit}')
+    population, generations = int(population), int(generations)
+    if population < 2 or generations < 1:
+        raise ValueError(f'population >= 2 and generations >= 1 expected, got {population}, {generations}')
+    if not 0 < float(elite) <= 1 or not float(sigma) > 0 or not float(sigma_floor) >= 0:
+        raise ValueError(f'elite in (0, 1], sigma > 0, sigma_floor >= 0 expected, got {elite}, {sigma}, {sigma_floor}')
+    bad = sorted(set(bounds or {}) - set(PARAM_NAMES))
+    if bad:
+        raise ValueError(f'bounds for unknown constants {bad}')
+    limits = {**DEFAULT_BOUNDS, **(bounds or {})}
+    start = {**DEFAULT_INIT, **(init or {})}
+    start = {k: float(start[k]) for k in PARAM_NAMES}
+    seeds = [int(x) for x in seeds]
+    terms_of = None
+    if evaluate is None:
+        evaluate = terms_of = _StatsEvaluator(scenario, reference, frames, seeds, population, radius, capacity, crowd_kw,
+                                              pair_kw, weights, min_count, device)
+    scale = np.array([abs(start[k]) if start[k] != 0 else 1.0 for k in fit])
+    lo = np.array([-np.inf if limits.get(k, (None, None))[0] is None else limits[k][0] for k in fit], np.float64)
+    hi = np.array([np.inf if limits.get(k, (None, None))[1] is None else limits[k][1] for k in fit], np.float64)
+    rng = np.random.default_rng(search_seed)
+    x_of = lambda p: np.array([p[k] for k in fit]) / scale                    # noqa: E731
+    mean, sig = x_of(start), np.full(len(fit), float(sigma))
+    n_elite = int(math.ceil(float(elite) * population))
+    best, best_J, best_terms, initial, history = dict(start), float('inf'), None, None, []
+    for g in range(generations):
+        cands = [dict(best)]
+        for _ in range(population - 1):
+            p = np.clip((mean + sig * rng.standard_normal(len(fit))) * scale, lo, hi)
+            cands.append({**start, **{k: float(v) for k, v in zip(fit, p)}})
+        J = [float(v) for v in evaluate([{'version': version, **c} for c in cands])]
+        if len(J) != population:
+            raise ValueError(f'evaluate returned {len(J)} values for {population} candidates')
+        J = [v if math.isfinite(v) else float('inf') for v in J]              # NaN and inf are never selected
+        if g == 0:
+            initial = J[0]
+        order = sorted((i for i in range(population) if math.isfinite(J[i])), key=lambda i: (J[i], i))
+        if order and J[order[0]] < best_J:
+            best, best_J = dict(cands[order[0]]), J[order[0]]
+            if terms_of is not None:
+                best_terms = terms_of.last_terms[order[0]]
+        if order:
+            xs = np.stack([x_of(cands[i]) for i in order[:n_elite]])
+            # sigma about the OLD mean (the rank-mu form): while the elite sits to one side of the mean the spread keeps the
+            # length of the move instead of collapsing onto the elite's own scatter, which stalls a plain cross-entropy
+            # update well short of an optimum several sigma away
+            sig = np.maximum(np.sqrt(((xs - mean) ** 2).mean(0)), float(sigma_floor))
+            mean = xs.mean(0)
+        history.append(best_J)
+    status = 'ok' if math.isfinite(best_J) else 'no candidate had a finite objective: init kept'
+    if status != 'ok':
+        import warnings
+        warnings.warn(f'calibrate_mlapm_to_stats: {status}')
+    res = {'version': version, **best}
+    out = CalibrationResult(params=res, initial_loss=initial, final_loss=best_J, history=history, fit=fit,
+                            terms=best_terms, generations=generations, population=population, seeds=seeds, status=status,
+                            steps=generations, horizon=None)
+    if terms_of is not None:
+        out.seconds = dict(terms_of.seconds)
+    return out
+
+
 def _parse_init(text):
     out = {}
     for item in filter(None, (s.strip() for s in (text or '').split(','))):
@@ -431,7 +655,34 @@ def get_args(argv=None):
     p.add_argument('--skip_frames', type=int, default=25, help='desired speed = mean |v| over this many frames after the start')
     p.add_argument('--no_graph', action='store_true', help='eager iterations instead of a replayed graph')
     p.add_argument('--out', type=str, default='params.json')
-    return p.parse_args(argv)
+    p.add_argument('--match-stats', dest='match_stats', action='store_true',
+                   help="fit the law to the clip's crowd statistics, run open-world in the clip's own scene "
+                        '(calibrate_mlapm_to_stats), instead of to its trajectories')
+    p.add_argument('--match', type=str, default='crowd,pairs', help='--match-stats: the statistics to match (crowd, pairs)')
+    p.add_argument('--scene-frames', dest='scene_frames', type=str, default=None,
+                   help="--match-stats: the window 'a:b' of the clip that is the scene and the reference (default: all)")
+    p.add_argument('--scene-jitter', dest='scene_jitter', type=float, default=0.0,
+                   help='--match-stats: arrivals start within +- this many metres of the recorded origin')
+    p.add_argument('--seeds', type=str, default='0:8', help="--match-stats: the seeds every candidate runs, 'a:b' or 'a,b,c'")
+    p.add_argument('--population', type=int, default=16)
+    p.add_argument('--generations', type=int, default=30)
+    p.add_argument('--search-seed', dest='search_seed', type=int, default=0)
+    a = p.parse_args(argv)
+    if a.match_stats:
+        if len(a.data) != 1:
+            p.error('--match-stats takes one clip')
+        a.match = tuple(filter(None, (x.strip() for x in a.match.split(','))))
+        if not a.match or any(x not in ('crowd', 'pairs') for x in a.match):
+            p.error(f"--match: 'crowd', 'pairs' or both expected, got {a.match}")
+        try:
+            from .simulate import parse_seeds
+            a.seeds = parse_seeds(a.seeds)
+            if a.scene_frames is not None:
+                lo, hi = (int(x) for x in a.scene_frames.split(':'))
+                a.scene_frames = (lo, hi)
+        except ValueError as ex:
+            p.error(f'--seeds / --scene-frames: {ex}')
+    return a
 
 
 def main(argv=None):
@@ -444,6 +695,8 @@ def main(argv=None):
         raws.append(raw)
     raw = raws[0] if len(raws) == 1 else raws
     init = {**DEFAULT_INIT, **a.init}
+    if a.match_stats:
+        return _main_stats(a, raw, init)
     if a.horizon is not None:
         return _main_rollout(a, raw, init)
     pack = pack_clip(raw, frames=a.frames, skip_frames=a.skip_frames)
@@ -479,6 +732,31 @@ def _main_rollout(a, raw, init):
             out.append((loss, math.sqrt(sse[-1] / cnt[-1]) if cnt[-1] else float('nan')))
         print(f'[calibrate] held-out rollout loss ({vp.num_windows} windows, {vp.num_terms} agent steps): '
               f'{out[0][0]:.6g} -> {out[1][0]:.6g} m^2; RMSE at k = {a.horizon}: {out[0][1]:.4g} -> {out[1][1]:.4g} m')
+    with open(a.out, 'w') as fh:
+        json.dump(res.params, fh, indent=1)
+    print(f'[calibrate] wrote {a.out}')
+    return res
+
+
+def _main_stats(a, raw, init):
+    from . import crowdstats, pairstats, scenarios
+    try:
+        scene = scenarios.clip_scenario(raw, frames=a.scene_frames, jitter=a.scene_jitter)
+    except ValueError as ex:
+        sys.exit(f'--match-stats: {ex}')
+    lo, hi = a.scene_frames or (0, int(raw.position.shape[0]))
+    box = crowdstats.auto_box(raw.position[lo:hi].numpy(), raw.mask_p[lo:hi].numpy(), 0.5)
+    ref_crowd = crowdstats.crowd_stats_of_raw(raw, box=box, frames=(lo, hi)) if 'crowd' in a.match else None
+    ref_pairs = pairstats.pair_stats_of_raw(raw, frames=(lo, hi)) if 'pairs' in a.match else None
+    res = calibrate_mlapm_to_stats(scene, (ref_crowd, ref_pairs), version=a.version, init=init, fit=a.fit, frames=hi - lo,
+                                   seeds=a.seeds, population=a.population, generations=a.generations,
+                                   search_seed=a.search_seed, radius=a.radius)
+    print(f'[calibrate] {a.version} against the statistics ({", ".join(a.match)}) of frames {lo}:{hi}, {a.population} '
+          f'candidates x {len(a.seeds)} seeds x {a.generations} generations: objective {res.initial_loss:.6g} -> '
+          f'{res.final_loss:.6g} ({res.status})')
+    print('[calibrate] ' + ', '.join(f'{k}={res.params[k]:.6g}' for k in PARAM_NAMES))
+    print('[calibrate] terms: ' + ', '.join(f'{k} {v:.4g}' if isinstance(v, float) else f'{k} {v}'
+                                           for k, v in (res.terms or {}).items()))
     with open(a.out, 'w') as fh:
         json.dump(res.params, fh, indent=1)
     print(f'[calibrate] wrote {a.out}')

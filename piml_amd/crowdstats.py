@@ -81,6 +81,15 @@ def _nan_div(a, b):
         return np.where(b > 0, a / np.where(b > 0, b, 1), np.nan)
 
 
+def member_indices(members, count):
+    """`members` as an int64 index array into `count` members; IndexError on anything but integers in 0 .. count - 1."""
+    idx = list(members)
+    for m in idx:
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= int(m) < count:
+            raise IndexError(f'member {m!r} of {count}')
+    return np.asarray(idx, np.int64).reshape(-1)
+
+
 class CrowdStats:
     """The statistics of S members over T' frames.  Raw arrays (numpy): n, n_speed (S, T') int64 focal agents / those with
     a speed; sum_speed, sum_density (S, T') float64; fd_count (S, B) int64, fd_sum, fd_sum2 (S, B) float64 (count, sum u,
@@ -137,6 +146,13 @@ class CrowdStats:
     def member(self, m):
         """Member m as a one-member CrowdStats (views)."""
         pick = lambda x: None if x is None else x[m:m + 1]
+        return CrowdStats({k: pick(getattr(self, k)) for k in ARRAYS}, self.options, density=pick(self.density))
+
+    def select(self, members):
+        """The same statistics restricted to the members of a list of indices (0 .. members - 1, in the list's order, repeats
+        allowed), with the same options: `.select(group).pooled()` pools one group.  IndexError on an index out of range."""
+        idx = member_indices(members, self.members)
+        pick = lambda x: None if x is None else x[idx]
         return CrowdStats({k: pick(getattr(self, k)) for k in ARRAYS}, self.options, density=pick(self.density))
 
     def pooled(self):

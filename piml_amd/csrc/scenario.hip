@@ -602,8 +602,17 @@ struct MlapmScenarioArgs {
     int gc, agent_blocks, frame_offset;
 };
 
+// One body, two forms.  kTable == false (piml_scenario_step_mlapm): every member steps under the launch's by-value law K0.P;
+// `table` is not read.  kTable == true (piml_scenario_step_mlapm_laws): member m steps under table[m], a row of derived
+// constants that piml_mlapm_law_table_fill formed on the host with make_params (K0.P is not read).  The row is read on every
+// launch -- a captured graph follows what the table's buffer holds at replay time -- and its index is the block's member,
+// so the 56 bytes arrive by scalar loads.  The tile loop, the NaN staging of absent sources, GC's exit distance and the
+// spawn blocks are the same code in both; the kTable == false code is instruction for instruction what it was before the
+// table existed (the extra pointer moved one hidden-argument offset).
+template <bool kTable>
 __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_kernel(const MlapmScenarioArgs K0,
-                                                                        const unsigned long long* __restrict__ seeds) {
+                                                                        const unsigned long long* __restrict__ seeds,
+                                                                        const MlapmParams* __restrict__ table) {
     __shared__ float4 tile[kMlTile];                         // agent blocks: the sources (px, py, vx, vy); spawn blocks: entries
     __shared__ unsigned short ucy_ring[kMlScWaves][256];
     static_assert(kScenarioLdsPoints * sizeof(float2) <= sizeof(tile), "the entry points fit the source tile");
@@ -611,7 +620,9 @@ __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_kernel(const M
     const float2* no_a = nullptr;
     member_view(S, no_a, (int)blockIdx.y);
     S.seed = seeds[blockIdx.y];
-    const MlapmParams& P = K0.P;
+    MlapmParams row;
+    if (kTable) row = table[blockIdx.y];                     // block-uniform index: scalar loads
+    const MlapmParams& P = kTable ? row : K0.P;
     const long long t = *S.frame_counter + K0.frame_offset;
     if (t + 1 >= S.T) return;                                // past the records: nothing to do
     const long long n = S.spawned[t & 1];
@@ -773,27 +784,63 @@ PIML_API int piml_scenario_step_members(const piml_scenario* s, const piml_scena
     return launch_frame(*s, r, members, seeds, a_next, init, stream);
 }
 
+// the law checks of the MLAPM frame entries (include/piml_hip.h)
+static bool mlapm_law_ok(const piml_mlapm_law& L) {
+    return L.variant >= 0 && L.variant <= 2 && std::isfinite(L.tau) && L.tau > 0.f && std::isfinite(L.A) &&
+           std::isfinite(L.B) && std::isfinite(L.C) && std::isfinite(L.D) && std::isfinite(L.theta_deg) &&
+           std::isfinite(L.radius) && L.radius > 0.f;
+}
+
+// the arguments of an MLAPM frame launch (K.P left to the caller) and its grid
+static dim3 mlapm_frame_launch(piml::MlapmScenarioArgs& K, const piml_scenario& S, const piml_scenario_rules* r, int members,
+                               int frame_offset) {
+    K.S = S;
+    K.R = r ? *r : piml_scenario_rules{};
+    K.gc = K.R.spawn_law == PIML_SPAWN_GC;
+    K.agent_blocks = (S.capacity + piml::kMlScWaves - 1) / piml::kMlScWaves;
+    K.frame_offset = frame_offset;
+    return dim3((unsigned)(K.agent_blocks + spawn_blocks(S, r, 0)), (unsigned)members);
+}
+
 PIML_API int piml_scenario_step_mlapm(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
                                       const piml_mlapm_law* law, int frame_offset, void* stream) {
     // the frame checks (init = 1 only waives a_next, which this frame does not take)
     if (!s || !seeds || !law || members < 1 || members > 65535 || frame_offset < 0 || !frame_args_ok(*s, r, nullptr, 1))
         return hipErrorInvalidValue;
-    const piml_scenario& S = *s;
     const piml_mlapm_law& L = *law;
-    if (L.variant < 0 || L.variant > 2 || !std::isfinite(L.tau) || !(L.tau > 0.f) || !std::isfinite(L.A) ||
-        !std::isfinite(L.B) || !std::isfinite(L.C) || !std::isfinite(L.D) || !std::isfinite(L.theta_deg) ||
-        !std::isfinite(L.radius) || !(L.radius > 0.f))
+    if (!mlapm_law_ok(L)) return hipErrorInvalidValue;
+    piml::MlapmScenarioArgs K;
+    const dim3 grid = mlapm_frame_launch(K, *s, r, members, frame_offset);
+    K.P = piml::make_params(L.variant, L.tau, L.A, L.B, L.C, L.D, L.theta_deg, L.radius, 1);
+    hipLaunchKernelGGL(piml::scenario_mlapm_kernel<false>, grid, dim3(piml::kMlScWaves * 64), 0, piml::as_stream(stream), K,
+                       (const unsigned long long*)seeds, (const piml::MlapmParams*)nullptr);
+    return hipGetLastError();
+}
+
+PIML_API long long piml_mlapm_law_table_bytes(int n) { return n < 0 ? -1 : (long long)n * (long long)sizeof(piml::MlapmParams); }
+
+PIML_API int piml_mlapm_law_table_fill(const piml_mlapm_law* laws, int n, void* table_host) {
+    if (n < 0 || (n > 0 && (!laws || !table_host))) return hipErrorInvalidValue;
+    for (int m = 0; m < n; ++m)                              // every law before the first byte is written
+        if (!mlapm_law_ok(laws[m])) return hipErrorInvalidValue;
+    piml::MlapmParams* rows = (piml::MlapmParams*)table_host;
+    for (int m = 0; m < n; ++m) {
+        const piml_mlapm_law& L = laws[m];
+        rows[m] = piml::make_params(L.variant, L.tau, L.A, L.B, L.C, L.D, L.theta_deg, L.radius, 1);
+    }
+    return hipSuccess;
+}
+
+PIML_API int piml_scenario_step_mlapm_laws(const piml_scenario* s, const piml_scenario_rules* r, int members,
+                                           const uint64_t* seeds, const void* table_device, int frame_offset, void* stream) {
+    if (!s || !seeds || !table_device || members < 1 || members > 65535 || frame_offset < 0 ||
+        !frame_args_ok(*s, r, nullptr, 1))
         return hipErrorInvalidValue;
     piml::MlapmScenarioArgs K;
-    K.S = S;
-    K.R = r ? *r : piml_scenario_rules{};
-    K.P = piml::make_params(L.variant, L.tau, L.A, L.B, L.C, L.D, L.theta_deg, L.radius, 1);
-    K.gc = K.R.spawn_law == PIML_SPAWN_GC;
-    K.agent_blocks = (S.capacity + piml::kMlScWaves - 1) / piml::kMlScWaves;
-    K.frame_offset = frame_offset;
-    const dim3 grid((unsigned)(K.agent_blocks + spawn_blocks(S, r, 0)), (unsigned)members);
-    hipLaunchKernelGGL(piml::scenario_mlapm_kernel, grid, dim3(piml::kMlScWaves * 64), 0, piml::as_stream(stream), K,
-                       (const unsigned long long*)seeds);
+    const dim3 grid = mlapm_frame_launch(K, *s, r, members, frame_offset);
+    K.P = piml::MlapmParams{};                               // not read: the rows are the table's
+    hipLaunchKernelGGL(piml::scenario_mlapm_kernel<true>, grid, dim3(piml::kMlScWaves * 64), 0, piml::as_stream(stream), K,
+                       (const unsigned long long*)seeds, (const piml::MlapmParams*)table_device);
     return hipGetLastError();
 }
 

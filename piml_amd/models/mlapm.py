@@ -1,6 +1,7 @@
 """`MLAPM`: the closed-form social-force law (reference src/models/mlapm.py), same constructor
 and `step` signature, evaluated by the HIP pair kernel with an analytic backward.  `simulate_scenario` /
-`simulate_ensemble` drive the open-world scenes of piml_amd.scenarios with it (one launch per frame)."""
+`simulate_ensemble` drive the open-world scenes of piml_amd.scenarios with it (one launch per frame); `simulate_sweep` does
+so for a list of laws at once, one law per ensemble member."""
 from .. import ops
 
 
@@ -160,9 +161,12 @@ class MLAPM:
         self._run_scenario(st, law, use_graph, frames_per_graph)
         return scenarios.scenario_result(st)
 
-    def _run_scenario(self, st, law, use_graph, frames_per_graph):
+    @staticmethod
+    def _run_scenario(st, law, use_graph, frames_per_graph, graph=None):
         """frame 0's spawn, then T - 1 MLAPM frames: K = frames_per_graph of them (offsets 0 .. K-1 and one counter add)
-        captured into one graph and replayed when use_graph, the rest eagerly."""
+        captured into one graph and replayed when use_graph, the rest eagerly.  law: a mlapm_law or a law table.  Returns
+        the captured graph (None for an eager run); passed back as `graph` with the same state, the run replays it
+        instead of capturing again."""
         import torch
         from .. import ops_scenario, hip_graphs_safe
         with torch.no_grad():
@@ -175,14 +179,94 @@ class MLAPM:
             if use_graph and steps >= per + 1 and hip_graphs_safe():
                 ops_scenario.scenario_step_mlapm(st, law)             # a real frame, also warms the library up
                 done = 1
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    for k in range(per):
-                        ops_scenario.scenario_step_mlapm(st, law, frame_offset=k, advance=False)
-                    st.t.add_(per)
+                if graph is None:
+                    torch.cuda.synchronize()
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph):
+                        for k in range(per):
+                            ops_scenario.scenario_step_mlapm(st, law, frame_offset=k, advance=False)
+                        st.t.add_(per)
                 for _ in range((steps - done) // per):
                     graph.replay()
                 done += (steps - done) // per * per
             for _ in range(steps - done):
                 ops_scenario.scenario_step_mlapm(st, law)
+        return graph
+
+    # ---- one law per member (piml_scenario_step_mlapm_laws): a sweep of candidates x seeds in one ensemble run ----
+    @staticmethod
+    def simulate_sweep(scenario, frames, params, seeds, capacity=None, use_graph=None, radius=0.3, device='cuda',
+                       hist_width=2, frames_per_graph=8):
+        """simulate_ensemble for every candidate of `params` in the same launches: params is a list of C dicts in
+        MLAPM(**params) form (version, tau, A, B and optionally C, D, theta; an optional 'radius' overrides `radius` for
+        that candidate), and member c * len(seeds) + k runs law c under seeds[k] -- candidate-major, every candidate on
+        the same seeds and so the same arrivals (common random numbers).  Candidates may differ in version.  Member
+        (c, k) is bitwise MLAPM(**params[c]).simulate_ensemble(scenario, frames, seeds, capacity=same)'s member k.
+        What the reference does with one process per parameter set (src/utils/grid_search.py) is one run here.
+        ValueError: an empty list, an unknown or missing key, C * len(seeds) > 65535.  Returns a scenarios.ScenarioSweep."""
+        return SweepRun(scenario, frames, len(params) if hasattr(params, '__len__') else 0, seeds, capacity, use_graph,
+                        device, hist_width, frames_per_graph).run(params, radius)
+
+
+SWEEP_KEYS = ('version', 'tau', 'A', 'B', 'C', 'D', 'theta', 'radius')
+
+
+def sweep_laws(params, radius=0.3):
+    """The mlapm_law of every candidate dict (simulate_sweep's form).  ValueError on an empty list, an unknown or
+    missing key, or a value mlapm_law refuses."""
+    from .. import ops_scenario
+    params = list(params)
+    if not params:
+        raise ValueError('simulate_sweep: at least one candidate expected')
+    laws = []
+    for c, a in enumerate(params):
+        if not isinstance(a, dict):
+            raise ValueError(f'candidate {c}: a dict in MLAPM(**params) form expected, got {type(a).__name__}')
+        unknown = sorted(set(a) - set(SWEEP_KEYS))
+        missing = [k for k in ('version', 'tau', 'A', 'B') if k not in a]
+        if unknown or missing:
+            raise ValueError(f'candidate {c}: unknown keys {unknown}, missing keys {missing} (of {SWEEP_KEYS})')
+        laws.append(ops_scenario.mlapm_law(a['version'], a['tau'], a['A'], a['B'], a.get('C', 0.0), a.get('D', 0.0),
+                                           a.get('theta', 0.0), a.get('radius', radius)))
+    return laws
+
+
+class SweepRun:
+    """The state, law table and captured frames of a sweep of n_candidates laws x seeds, kept for running again:
+    run(params) writes the candidates' table into the same device buffer, puts the state back to empty and replays the
+    graph captured by the first run, so a further population costs one small copy, the fills and the replays -- what a
+    generation of calibrate.calibrate_mlapm_to_stats is.  Every run is bitwise a fresh MLAPM.simulate_sweep."""
+
+    def __init__(self, scenario, frames, n_candidates, seeds, capacity=None, use_graph=None, device='cuda', hist_width=2,
+                 frames_per_graph=8):
+        from .. import ops_scenario, scenarios
+        self.seeds = [int(x) for x in seeds]
+        self.n_candidates = int(n_candidates)
+        if not self.seeds or self.n_candidates < 1:
+            raise ValueError('simulate_sweep: at least one candidate and one seed expected')
+        if self.n_candidates * len(self.seeds) > ops_scenario.MAX_MEMBERS:
+            raise ValueError(f'simulate_sweep: {self.n_candidates} candidates x {len(self.seeds)} seeds = '
+                             f'{self.n_candidates * len(self.seeds)} members, more than {ops_scenario.MAX_MEMBERS}')
+        self.scenario, self.frames, self.capacity, self.device = scenario, frames, capacity, device
+        self.hist_width, self.use_graph, self.frames_per_graph = hist_width, use_graph, frames_per_graph
+        self.st = self.table = self.graph = None
+
+    def run(self, params, radius=0.3):
+        from .. import ops_scenario, scenarios
+        params = [dict(a) for a in params]
+        laws = sweep_laws(params, radius)
+        if len(laws) != self.n_candidates:
+            raise ValueError(f'{len(laws)} candidates for a sweep of {self.n_candidates}')
+        S = len(self.seeds)
+        rows = [law for law in laws for _ in range(S)]
+        if self.st is None:
+            self.st = scenarios.scenario_state_for(self.scenario, self.frames, self.capacity, self.device, self.hist_width,
+                                                   seeds=self.seeds * self.n_candidates)
+            self.table = ops_scenario.mlapm_law_table(rows, self.st.p.device)
+        else:
+            ops_scenario.mlapm_law_table(rows, out=self.table)
+            ops_scenario.scenario_state_reset(self.st)
+        self.graph = MLAPM._run_scenario(self.st, self.table, self.use_graph, self.frames_per_graph, graph=self.graph)
+        ens = scenarios.scenario_result(self.st)
+        fields = dict(vars(ens))
+        return scenarios.ScenarioSweep(params=params, n_candidates=self.n_candidates, seeds_per_candidate=S, **fields)

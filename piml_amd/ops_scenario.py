@@ -1,5 +1,5 @@
 """Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_step_rules,
-piml_scenario_step_members, piml_scenario_step_mlapm, piml_scenario_route).
+piml_scenario_step_members, piml_scenario_step_mlapm, piml_scenario_step_mlapm_laws, piml_scenario_route).
 
 `scenario_state` allocates the persistent (static-address) buffers of one simulation or an ensemble and the
 `piml_scenario` descriptor that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive,
@@ -115,6 +115,18 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
     return st
 
 
+def scenario_state_reset(st):
+    """Put the buffers of scenario_state back to what it allocated them as, in place (the addresses a captured graph
+    holds stay valid): absent slots, empty records, frame counter and spawn counts 0.  Then scenario_step(st, init=True)
+    starts the same simulation again."""
+    nan = float('nan')
+    for x in (st.p, st.dest, st.waypoints, st.p_res, st.dest_res):
+        x.fill_(nan)
+    for x in (st.v, st.a, st.hist, st.selff, st.desired_speed, st.mask, st.flag, st.exit_idx, st.spawn_iters, st.v_res,
+              st.a_res, st.mask_res, st.spawn_count, st.t, st.spawned, st.dropped):
+        x.zero_()
+
+
 def scenario_rules(scenario):
     """The piml_scenario_rules descriptor of a scene (its spawn law, arrival rule, velocity and speed laws, second stream).
     The 'clip' law's track table is the scene's `entries`, which scenario_state puts into the piml_scenario descriptor."""
@@ -176,19 +188,71 @@ def mlapm_law(version='GC', tau=0.5, A=7.55, B=-3.0, C=0.2, D=-0.3, theta=56.0, 
     return law
 
 
+def mlapm_law_table_host(laws):
+    """The law table of a list of mlapm_law(...) as a CPU uint8 tensor (piml_mlapm_law_table_fill: host to host, no GPU call):
+    row m holds law m's derived constants, formed by the code that forms the single-law launch's.  ValueError on an empty
+    list or a law the library rejects (the bytes are then not produced)."""
+    laws = list(laws)
+    if not laws:
+        raise ValueError('mlapm_law_table: at least one law expected')
+    for law in laws:
+        if not isinstance(law, _lib.MlapmLaw):
+            raise TypeError(f'laws: ops_scenario.mlapm_law(...) values expected, got {type(law).__name__}')
+    L = _lib.lib()
+    arr = (_lib.MlapmLaw * len(laws))(*laws)
+    host = torch.zeros(int(L.piml_mlapm_law_table_bytes(len(laws))), dtype=torch.uint8)
+    if L.piml_mlapm_law_table_fill(arr, len(laws), host.data_ptr()) != 0:
+        raise ValueError('mlapm_law_table: a law is out of range (variant 0..2, finite constants, tau > 0, radius > 0)')
+    return host
+
+
+def mlapm_law_table(laws, device='cuda', out=None):
+    """The law table of piml_scenario_step_mlapm_laws for a list of mlapm_law(...): a (len(laws), row bytes) device uint8
+    tensor, one host fill and one copy.  out: a table of the same shape to overwrite in place instead (a captured run
+    reads the buffer at every replay, so this changes the laws of the frames replayed afterwards)."""
+    host = mlapm_law_table_host(laws)
+    host = host.view(len(laws), -1)
+    if out is not None:
+        if out.dtype != torch.uint8 or tuple(out.shape) != tuple(host.shape) or not out.is_contiguous():
+            raise ValueError(f'out: a contiguous uint8 table {tuple(host.shape)} expected, got {out.dtype} {tuple(out.shape)}')
+        out.copy_(host)
+        return out
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.PimlHipError(f'mlapm_law_table: a GPU device expected (piml_amd has no CPU path), got {dev}')
+    return host.to(dev)
+
+
 def scenario_step_mlapm(st, law, frame_offset=0, advance=True):
     """One launch: frame t -> t + 1 of st (single or ensemble state) under the MLAPM law `law` (mlapm_law(...)), t =
     st.t + frame_offset: the force of MLAPM.step from the agents present in frame t's records, v' = v + F dt, p' = p + v' dt
     (src/main_mlapm.py:18-36), a' = F, then the scene's arrivals, exits and spawns as scenario_step.  advance: add 1 to
     st.t afterwards (the kernel reads the counter, never writes it; a captured run of K frames passes offsets 0 .. K-1 and
-    advances once by K).  Frame 0's spawn is scenario_step(st, init=True), which does not depend on the law."""
-    if not isinstance(law, _lib.MlapmLaw):
-        raise TypeError(f'law: an ops_scenario.mlapm_law(...) expected, got {type(law).__name__}')
+    advances once by K).  Frame 0's spawn is scenario_step(st, init=True), which does not depend on the law.
+    law may instead be a table of mlapm_law_table(...) with one row per member of st (member m steps under row m,
+    piml_scenario_step_mlapm_laws); ValueError when it does not hold exactly st.seeds.numel() rows or is on another device."""
+    table = isinstance(law, torch.Tensor)
+    if table:
+        row = int(_lib.lib().piml_mlapm_law_table_bytes(1))
+        if law.dtype != torch.uint8 or law.dim() != 2 or law.shape[1] != row or not law.is_contiguous():
+            raise ValueError(f'law table: a contiguous uint8 (members, {row}) tensor of mlapm_law_table expected, got '
+                             f'{law.dtype} {tuple(law.shape)}')
+        if law.shape[0] != st.seeds.numel():
+            raise ValueError(f'law table: {law.shape[0]} rows for {st.seeds.numel()} members')
+        if law.device != st.p.device:
+            raise ValueError(f'law table on {law.device}, the state on {st.p.device}')
+    elif not isinstance(law, _lib.MlapmLaw):
+        raise TypeError(f'law: an ops_scenario.mlapm_law(...) or a mlapm_law_table(...) expected, got {type(law).__name__}')
     if int(frame_offset) < 0:
         raise ValueError(f'frame_offset must be >= 0, got {frame_offset}')
     with torch.cuda.device(st.p.device):
-        _lib.check(_lib.lib().piml_scenario_step_mlapm(ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(),
-                                                       _ptr(st.seeds), ctypes.byref(law), int(frame_offset), _stream()),
-                   'piml_scenario_step_mlapm')
+        if table:
+            _lib.check(_lib.lib().piml_scenario_step_mlapm_laws(ctypes.byref(st.desc), ctypes.byref(st.rules),
+                                                                st.seeds.numel(), _ptr(st.seeds), _ptr(law),
+                                                                int(frame_offset), _stream()), 'piml_scenario_step_mlapm_laws')
+        else:
+            _lib.check(_lib.lib().piml_scenario_step_mlapm(ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(),
+                                                           _ptr(st.seeds), ctypes.byref(law), int(frame_offset), _stream()),
+                       'piml_scenario_step_mlapm')
         if advance:
             st.t.add_(1)

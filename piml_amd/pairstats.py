@@ -35,7 +35,8 @@ import sys
 import numpy as np
 import torch
 
-from .crowdstats import _f32, _json_float, _json_floats, _load, _nan_div, _promote, auto_box, parse_box, parse_frames
+from .crowdstats import (_f32, _json_float, _json_floats, _load, _nan_div, _promote, auto_box, member_indices, parse_box,
+                         parse_frames)
 
 JSON_VERSION = 1
 ARRAYS = ('focal', 'pairs', 'overlap', 'ttc', 'dist', 'nn', 'min_ttc')
@@ -129,6 +130,12 @@ class PairStats:
     def member(self, m):
         """Member m as a one-member PairStats (views)."""
         return PairStats({k: getattr(self, k)[m:m + 1] for k in ARRAYS}, self.options)
+
+    def select(self, members):
+        """The same statistics restricted to the members of a list of indices (0 .. members - 1, in the list's order, repeats
+        allowed), with the same options: `.select(group).pooled()` pools one group.  IndexError on an index out of range."""
+        idx = member_indices(members, self.members)
+        return PairStats({k: getattr(self, k)[idx] for k in ARRAYS}, self.options)
 
     def pooled(self):
         """The sum over members: a one-member PairStats."""

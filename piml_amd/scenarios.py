@@ -10,7 +10,8 @@ Poisson arrivals, recording -- is one HIP launch of scenario_frame_kernel (piml_
 and an ensemble alike; `scenario_state_for` / `scenario_result` are every simulator's set-up and result.
 
 `ScenarioEnsemble` is what `BaseSimulator.simulate_ensemble` returns: S simulations of one scene (one per seed) with a
-leading member axis, each of them a `ScenarioResult` through `member(m)`.
+leading member axis, each of them a `ScenarioResult` through `member(m)`.  `ScenarioSweep` is the ensemble of
+`MLAPM.simulate_sweep`: candidates x seeds members, every candidate under its own law.
 
 `clip_scenario(raw_data)` makes a scene of any recorded clip: its geometry, the agents of its first frame, and arrivals
 resampled from its own tracks (PIML_SPAWN_CLIP: the table of tracks travels in `entries`).
@@ -415,6 +416,40 @@ class ScenarioEnsemble(types.SimpleNamespace):
         from . import ops
         thr = (float(threshold),)
         return torch.stack([ops.collision_counts(p, thr)[0].sum() for p in self.position]).tolist()
+
+
+class ScenarioSweep(ScenarioEnsemble):
+    """What `MLAPM.simulate_sweep` returns: a ScenarioEnsemble of n_candidates * seeds_per_candidate members laid out
+    candidate-major -- member c * seeds_per_candidate + k ran law params[c] under the k-th seed -- plus params (the
+    candidates' dicts), n_candidates and seeds_per_candidate.  `seeds` lists every member's seed (the seed list once per
+    candidate); crowd_stats / pair_stats compute all members in one call, and `.select(sweep.members_of(c)).pooled()` of
+    the result pools one candidate."""
+
+    def members_of(self, c):
+        """The member indices of candidate c."""
+        c = int(c)
+        if not 0 <= c < self.n_candidates:
+            raise IndexError(f'candidate {c} of {self.n_candidates}')
+        return list(range(c * self.seeds_per_candidate, (c + 1) * self.seeds_per_candidate))
+
+    def candidate(self, c):
+        """Candidate c's members as a ScenarioEnsemble of views."""
+        m = self.members_of(c)
+        sl = slice(m[0], m[-1] + 1)
+        return ScenarioEnsemble(
+            position=self.position[sl], velocity=self.velocity[sl], acceleration=self.acceleration[sl],
+            destination=self.destination[sl], mask_p=self.mask_p[sl], waypoints=self.waypoints[sl],
+            desired_speed=self.desired_speed[sl], spawn_count=self.spawn_count[sl], obstacles=self.obstacles,
+            time_unit=self.time_unit, capacity=self.capacity, seeds=self.seeds[sl], spawned=self.spawned[sl],
+            dropped=self.dropped[sl])
+
+    def save_data(self, pattern):
+        """One v2.2 clip per member at pattern with '{candidate}' and '{seed}' replaced.  Returns the paths."""
+        if '{seed}' not in pattern or '{candidate}' not in pattern:
+            raise ValueError(f"save_data: the path pattern must contain '{{candidate}}' and '{{seed}}', got {pattern!r}")
+        S = self.seeds_per_candidate
+        return [self.member(m).save_data(pattern.replace('{candidate}', str(m // S)).replace('{seed}', str(s)))
+                for m, s in enumerate(self.seeds)]
 
 
 def scenario_state_for(scenario, frames, capacity=None, device='cuda', hist_width=2, **kw):

@@ -9,6 +9,8 @@ reads.
     python -m piml_amd.simulate --seeds 0:32 --stats stats.json      (crowd statistics of the run, no clips written)
     python -m piml_amd.simulate --seeds 0:32 --pair-stats pairs.json      (time-to-collision statistics, no clips written)
     python -m piml_amd.simulate --law mlapm --scene-from ucy.npy --seeds 0:32 --pair-stats sim.json   (a clip as the scene)
+    python -m piml_amd.simulate --law mlapm --params-sweep a.json b.json --seeds 0:8 --stats sweep.json
+                                (one law per file, every law on every seed in ONE ensemble run; statistics per candidate)
 
 Model flags (--model, --hidden sizes, --topk_*, --num_history_velocity, ...) are those of `piml_amd.main`, with its
 defaults.  Without --checkpoint the network keeps its initial weights (a smoke run)."""
@@ -33,6 +35,10 @@ def get_args(argv=None):
     p.add_argument('--params', type=str, default=None,
                    help="--law mlapm: the JSON `calibrate --out` writes (version and the six constants); default "
                         "main_mlapm.py's constants, version GC")
+    p.add_argument('--params-sweep', dest='params_sweep', type=str, nargs='+', default=None,
+                   help='--law mlapm with --seeds: several --params files, every law on every seed in one ensemble run '
+                        "(MLAPM.simulate_sweep); --stats / --pair-stats then hold one entry per candidate, pooled over its "
+                        "seeds, and --out must contain '{candidate}' and '{seed}'")
     p.add_argument('--mlapm_radius', type=float, default=0.3,
                    help="--law mlapm: MLAPM's UCY collision radius (not the scene's arrival radius)")
     p.add_argument('--scenario', type=str, default='gc', choices=sorted(SCENARIOS.SCENARIOS))
@@ -78,13 +84,21 @@ def get_args(argv=None):
             own.scene_frames = (a, b)
     elif own.scene_frames is not None or own.scene_jitter != 0.0:
         p.error('--scene-frames / --scene-jitter need --scene-from')
+    if own.params_sweep is not None:
+        if own.params is not None:
+            p.error('--params-sweep takes the place of --params: not both')
+        if own.law != 'mlapm' or own.seeds is None:
+            p.error('--params-sweep needs --law mlapm and --seeds')
+        if own.stats is None and own.pair_stats is None and '{candidate}' not in own.out:
+            p.error("--params-sweep: --out must contain '{candidate}' and '{seed}' (one clip per candidate and seed)")
     if own.law == 'mlapm':
         if own.checkpoint:
             p.error('--checkpoint is a PINNSF state_dict: not with --law mlapm (use --params)')
         try:
             own.mlapm = load_mlapm_params(own.params)
+            own.mlapm_sweep = None if own.params_sweep is None else [load_mlapm_params(f) for f in own.params_sweep]
         except (OSError, ValueError) as ex:
-            p.error(f'--params: {ex}')
+            p.error(f'--params / --params-sweep: {ex}')
     elif own.params is not None:
         p.error('--params needs --law mlapm')
     model_args = MAIN.get_args(rest)
@@ -165,6 +179,8 @@ def main(argv=None):
     else:
         kw = {} if own.uniform_desired_speed is None else {'uniform_desired_speed': own.uniform_desired_speed}
         scenario = SCENARIOS.SCENARIOS[own.scenario](time_unit=own.time_unit, **kw)
+    if own.law == 'mlapm' and own.mlapm_sweep is not None:
+        return _sweep(sim, scenario, own, run_kw)
     if own.seeds is not None:
         return _ensemble(sim, scenario, own, args, run_kw)
     res = sim.simulate_scenario(scenario, own.frames, seed=own.seed, capacity=own.capacity, **run_kw)
@@ -204,6 +220,35 @@ def _stats(res, own):
         ps = res.pair_stats()
         ps.to_json(own.pair_stats)
         pairstats.print_pair_stats(ps, 'simulate --pair-stats')
+
+
+def _sweep(sim, scenario, own, run_kw):
+    """--params-sweep: every law on every seed in one ensemble run; statistics per candidate, pooled over its seeds."""
+    import json
+    sw = sim.simulate_sweep(scenario, own.frames, own.mlapm_sweep, own.seeds, capacity=own.capacity, **run_kw)
+    groups = [sw.members_of(c) for c in range(sw.n_candidates)]
+    if own.stats is not None:
+        st = sw.crowd_stats()
+        entries = [{'params': sw.params[c], 'file': own.params_sweep[c], 'stats': st.select(g).pooled().to_json()}
+                   for c, g in enumerate(groups)]
+        with open(own.stats, 'w') as fh:
+            json.dump({'seeds': own.seeds, 'candidates': entries}, fh)
+    if own.pair_stats is not None:
+        ps = sw.pair_stats()
+        entries = [{'params': sw.params[c], 'file': own.params_sweep[c], 'stats': ps.select(g).pooled().to_json()}
+                   for c, g in enumerate(groups)]
+        with open(own.pair_stats, 'w') as fh:
+            json.dump({'seeds': own.seeds, 'candidates': entries}, fh)
+    where = _stats_path(own)
+    if not where:
+        sw.save_data(own.out)
+        where = own.out
+    for c, g in enumerate(groups):
+        spawned = [sw.spawned[m] for m in g]
+        dropped = [sw.dropped[m] for m in g]
+        print(f'[simulate] {own.scenario} candidate {c} ({own.params_sweep[c]}): {len(g)} seeds x {own.frames} frames, '
+              f'capacity {sw.capacity}: spawned {sum(spawned)}, dropped {sum(dropped)}; saved {where}')
+    return sw
 
 
 def _ensemble(sim, scenario, own, args, run_kw):
