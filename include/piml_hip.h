@@ -762,6 +762,9 @@ int piml_scenario_route(const float* origin, const float* destination, int n, co
  * acceleration that cancels the normal closing speed within one time unit is added (step 2, then step 3 on
  * the result).  bwd is the analytic gradient w.r.t. predictions, velocity and the (p_ji, v_ji) columns of the
  * two selected neighbour rows (flags / selections are piecewise constant); any gradient output may be NULL.
+ * NaN: a NaN offset component reads as 0 (the reference's nan_to_num) and receives no gradient; a flagged chasing row's
+ * NaN velocity makes the agent NaN as in the reference; an unflagged row's never does (the reference lets slot 0's through
+ * when nobody is chasing).  k == 0 (ped_features may be NULL): out = predictions, the gradient passes through.
  */
 int piml_collision_correction_fwd(const float* predictions, const float* ped_features, const float* velocity,
                                   size_t rows, int k, int row_stride, float collision_threshold, float time_unit,

@@ -1679,6 +1679,13 @@ __device__ __forceinline__ float2 corr_normal(const float* f, float& r_out, floa
     return make_float2(px / d, py / d);
 }
 
+// v_ji of the row step 3 gathers.  With nobody chasing (mc == 0) that row is slot 0, whatever it holds, and the reference
+// multiplies what it computes from it by 0 afterwards -- which lets a NaN velocity there (an absent neighbour's row) turn
+// the whole agent NaN.  Deviation: an unflagged row's NaN velocity reads as 0, so the agent comes out as with that row zeroed.
+__device__ __forceinline__ float2 corr_chased_velocity(const float* fc, float mc) {
+    return mc != 0.f ? make_float2(fc[2], fc[3]) : make_float2(nan_to_zero(fc[2]), nan_to_zero(fc[3]));
+}
+
 __global__ void collision_correction_fwd_kernel(const float2* __restrict__ pred, const float* __restrict__ ped,
                                                 const float2* __restrict__ vel, size_t rows, int k, int stride,
                                                 float radius, float dt, float2* __restrict__ out) {
@@ -1705,7 +1712,8 @@ __global__ void collision_correction_fwd_kernel(const float2* __restrict__ pred,
     {
         const float* fc = f + (size_t)s.c * stride;
         const float2 n = corr_normal(fc, r, p);
-        const float q = fc[2] * n.x + fc[3] * n.y;
+        const float2 w = corr_chased_velocity(fc, s.mc);
+        const float q = w.x * n.x + w.y * n.y;
         const float h = q < 0.f ? 1.f : 0.f;
         const float2 a = make_float2(q * h * n.x / dt * s.mc, q * h * n.y / dt * s.mc);
         float2 Pm = make_float2(P.x * s.mc, P.y * s.mc);
@@ -1755,7 +1763,7 @@ __global__ void collision_correction_bwd_kernel(const float2* __restrict__ g_out
     const float g1 = s1raw > 0.f ? 1.f : 0.f;
     const float2 P1 = make_float2((1.f + s.me) * P.x - g1 * s1raw * n1.x - s.me * u * n1.x / dt,
                                   (1.f + s.me) * P.y - g1 * s1raw * n1.y - s.me * u * n1.y / dt);
-    const float2 w = make_float2(fc[2], fc[3]);
+    const float2 w = corr_chased_velocity(fc, s.mc);
     const float q = w.x * n2.x + w.y * n2.y;
     const float h = q < 0.f ? 1.f : 0.f;
     const float s2raw = s.mc * (P1.x * n2.x + P1.y * n2.y);
@@ -1779,16 +1787,17 @@ __global__ void collision_correction_bwd_kernel(const float2* __restrict__ g_out
     if (g_ped) {
         float* o = g_ped + g * (size_t)k * stride;
         for (int j = 0; j < k * stride; ++j) o[j] = 0.f;
-        const bool nan1 = f[(size_t)s.e * stride] != f[(size_t)s.e * stride] || f[(size_t)s.e * stride + 1] != f[(size_t)s.e * stride + 1];
-        if (s.me != 0.f && !nan1) {
+        // a NaN offset component was read as 0 (nan_to_num): it receives no gradient, the finite one of the same row does
+        if (s.me != 0.f) {
+            const float* fe = f + (size_t)s.e * stride;
             const float2 gp = corr_normal_bwd(gn1, p1, r1);
-            o[(size_t)s.e * stride] += gp.x;
-            o[(size_t)s.e * stride + 1] += gp.y;
+            if (fe[0] == fe[0]) o[(size_t)s.e * stride] += gp.x;
+            if (fe[1] == fe[1]) o[(size_t)s.e * stride + 1] += gp.y;
         }
         if (s.mc != 0.f) {
             const float2 gp = corr_normal_bwd(gn2, p2, r2);
-            o[(size_t)s.c * stride] += gp.x;
-            o[(size_t)s.c * stride + 1] += gp.y;
+            if (fc[0] == fc[0]) o[(size_t)s.c * stride] += gp.x;
+            if (fc[1] == fc[1]) o[(size_t)s.c * stride + 1] += gp.y;
             o[(size_t)s.c * stride + 2] += gw.x;
             o[(size_t)s.c * stride + 3] += gw.y;
         }
