@@ -433,3 +433,146 @@ def test_one_launch_adam_is_bitwise_pytorchs_fused_adam(wd):
         for name in ('step', 'exp_avg', 'exp_avg_sq'):
             assert torch.equal(sa[k][name], sb[k][name]), (k, name)
     ob.load_state_dict(oa.state_dict())        # interchangeable
+
+
+def _ticket_is_zero():
+    from piml_amd import ops
+    t = ops._LOSS_TICKETS.get(torch.device(DEV))
+    return t is not None and int(t.item()) == 0
+
+
+def _collision_pred_case(C, T, N, k, t_start, seed):
+    g = torch.Generator().manual_seed(seed)
+    gates_f = torch.ones(T)
+    gates_f[t_start] = 0.0 if T - t_start > 2 else 1.0
+    preds = [torch.rand(C, N, k, generator=g).clamp(1e-4, 1 - 1e-4).to(DEV) for _ in range(T - t_start)]
+    feats = [(torch.randn(C, N, k, 6, generator=g) * torch.tensor([0.6, 0.6, 1.0, 1.0, 1.0, 1.0])).to(DEV) for _ in range(T - t_start)]
+    return preds, feats, gates_f.to(DEV)
+
+
+def _collision_pred_want(preds, feats, gates_f, t_start, T, weight):
+    """the reference's statements in float64 -> (loss, accuracy, gradients of 1.7 * loss)"""
+    import torch.nn.functional as F
+    from piml_amd import ops
+    ref_p = [p.detach().double().requires_grad_(True) for p in preds]
+    gk = gates_f.double().view(1, -1, 1, 1)
+    pad = [torch.zeros_like(ref_p[0])] * t_start
+    pc = torch.stack(pad + ref_p, dim=1) * gk
+    tc = torch.stack(pad + [ops.collision_label(x).double() for x in feats], dim=1) * gk
+    loss = F.binary_cross_entropy(pc, tc, reduction='sum') * weight
+    acc = torch.sum(torch.round(pc) == tc) / tc.numel()
+    return loss, acc, torch.autograd.grad(loss * 1.7, ref_p)
+
+
+def _pointwise_case(rows, k, seed):
+    g = torch.Generator().manual_seed(seed)
+    pred = torch.randn(rows, 2, generator=g).to(DEV)
+    msgs = torch.randn(rows, k, 2, generator=g).to(DEV)
+    coll = torch.rand(rows, k, generator=g).clamp(1e-4, 1 - 1e-4).to(DEV)
+    labels = torch.cat((torch.randn(rows, 6, generator=g), (torch.rand(rows, k, generator=g) < 0.2).float()), 1).to(DEV)
+    return pred, msgs, coll, labels
+
+
+def _pointwise_want(pred, msgs, coll, labels, w):
+    """float64 torch expression -> (loss, mse, reg, cp, gradients of 0.7 * loss)"""
+    import torch.nn.functional as F
+    x = [t.detach().double().requires_grad_(True) for t in (pred, msgs, coll)]
+    lab = labels.double()
+    mse = F.mse_loss(x[0], lab[:, 4:6], reduction='sum')
+    reg = torch.sum(w * torch.abs(x[1]))
+    cp = F.binary_cross_entropy(x[2], lab[:, 6:], reduction='sum')
+    loss = mse + reg + cp
+    return loss, mse, reg, cp, torch.autograd.grad(loss * 0.7, x)
+
+
+_rel = lambda a, b: abs(float(a) - float(b)) / max(abs(float(b)), 1e-30)
+
+
+def test_collision_pred_loss_beyond_one_pass_of_its_capped_grid():
+    """ops.collision_pred_loss with n = C N k = 65544, just above 64 * 4 * 256: the grid is capped at 64 workgroups per frame, so
+    its threads take a SECOND turn of the grid-stride loop (no other test reaches it) -- against the float64 torch expression, at
+    the bounds of test_collision_pred_loss_equals_the_torch_expression; the shared ticket reads zero afterwards."""
+    from piml_amd import ops
+    C, T, N, k, t_start = 2, 3, 5462, 6, 1
+    assert C * N * k > 64 * 4 * 256 and ops._lib.lib().piml_collision_pred_loss_blocks(C * N * k, T - t_start) == 64 * (T - t_start)
+    preds, feats, gates_f = _collision_pred_case(C, T, N, k, t_start, seed=31)
+    leaves = [p.clone().requires_grad_(True) for p in preds]
+    got_loss, got_acc = ops.collision_pred_loss(leaves, feats, gates_f, t_start, T, 5e-2)
+    got_g = torch.autograd.grad(got_loss * 1.7, leaves)
+    assert _ticket_is_zero()
+    want_loss, want_acc, want_g = _collision_pred_want(preds, feats, gates_f, t_start, T, 5e-2)
+    print(f'collision_pred_loss n={C * N * k}: loss {_rel(got_loss, want_loss):.1e}')
+    assert _rel(got_loss, want_loss) <= 2e-6
+    assert float(got_acc) == pytest.approx(float(want_acc), abs=1e-6)
+    for a, b in zip(got_g, want_g):
+        assert torch.allclose(a.double(), b, rtol=2e-6, atol=1e-7)
+
+
+def test_pointwise_losses_beyond_one_pass_of_their_capped_grid():
+    """ops.pointwise_losses with 2 rows + |msgs| + rows k = 262160 elements, just above 256 * 4 * 256 (the grid's cap): a second turn
+    of the grid-stride loop -- against the float64 torch expression, at the bounds of test_pointwise_losses_equal_the_torch_expressions;
+    the shared ticket reads zero afterwards."""
+    from piml_amd import ops
+    rows, k, w = 13108, 6, 1e-2
+    assert rows * (2 + 2 * k + k) > 256 * 4 * 256 and ops._lib.lib().piml_pointwise_losses_blocks(rows, rows * k * 2, k) == 256
+    pred, msgs, coll, labels = _pointwise_case(rows, k, seed=32)
+    leaves = [t.clone().requires_grad_(True) for t in (pred, msgs, coll)]
+    got = ops.pointwise_losses(leaves[0], labels, w, leaves[1], leaves[2])
+    got_g = torch.autograd.grad(got[0] * 0.7, leaves)
+    assert _ticket_is_zero()
+    want = _pointwise_want(pred, msgs, coll, labels, w)
+    print('pointwise_losses 262160 elements: ' + ' '.join(f'{_rel(a, b):.1e}' for a, b in zip(got, want[:4])))
+    for a, b in zip(got, want[:4]):
+        assert _rel(a, b) <= 2e-6
+    for a, b in zip(got_g, want[4]):
+        assert torch.allclose(a.double(), b, rtol=2e-6, atol=1e-7)
+
+
+def test_the_three_loss_operators_back_to_back_share_one_ticket():
+    """rollout_losses_frames, collision_pred_loss and pointwise_losses, each on a multi-workgroup size, back to back on ONE stream
+    with nothing in between: they share the one ticket per device, so every launch must leave it zero for the next.  Each result
+    equals the operator's value when it runs alone (bitwise: the reductions are deterministic), in both orders."""
+    from piml_amd import ops
+    g = torch.Generator().manual_seed(33)
+    C, T, N = 3, 5, 700                                           # 2100 (window, agent) pairs: 9 workgroups
+    p = torch.randn(C, T, N, 2, generator=g).to(DEV)
+    labels = torch.randn(C, T, N, 7, generator=g).to(DEV)
+    mask = (torch.rand(C, T, N, generator=g) > 0.3).long().to(DEV)
+    gates = mask.sum(dim=(0, 2)) > 0
+    recs = [(torch.rand(2, C, N, generator=g) > 0.9).float().to(DEV) for _ in range(T)]
+    preds, feats, gates_f = _collision_pred_case(2, 3, 1500, 6, 0, seed=34)       # 18000 per frame: 18 workgroups x 3 frames
+    pred, msgs, coll, plab = _pointwise_case(4096, 6, seed=35)                    # 81920 elements: 80 workgroups
+    assert ops._lib.lib().piml_rollout_losses_blocks(C, N) > 1 and ops._lib.lib().piml_collision_pred_loss_blocks(18000, 3) > 3 and \
+        ops._lib.lib().piml_pointwise_losses_blocks(4096, 4096 * 12, 6) > 1
+
+    def three(order):
+        out = {}
+        for name in order:
+            if name == 'rollout':
+                out[name] = torch.stack(ops.rollout_losses_frames(p, labels, mask, gates, recs, True, None, 0.9, 0.7, 2.1)[:4])
+            elif name == 'collision':
+                out[name] = torch.stack(ops.collision_pred_loss(preds, feats, gates_f, 0, 3, 5e-2))
+            else:
+                out[name] = torch.stack(ops.pointwise_losses(pred, plab, 1e-2, msgs, coll))
+        return out
+    alone = {}
+    for name in ('rollout', 'collision', 'pointwise'):
+        alone.update(three([name]))
+        torch.cuda.synchronize()
+        assert _ticket_is_zero()
+    for order in (('rollout', 'collision', 'pointwise'), ('pointwise', 'collision', 'rollout', 'collision', 'rollout', 'pointwise')):
+        got = three(order)                                         # (no synchronisation between the launches)
+        torch.cuda.synchronize()
+        assert _ticket_is_zero()
+        for name in got:
+            assert torch.equal(got[name], alone[name]), f'{name} after {order}'
+    # and each alone equals its float64 expression at the neighbouring tests' bounds
+    want_cp = _collision_pred_want(preds, feats, gates_f, 0, 3, 5e-2)
+    assert _rel(alone['collision'][0], want_cp[0]) <= 2e-6
+    want_pw = _pointwise_want(pred, msgs, coll, plab, 1e-2)
+    for a, b in zip(alone['pointwise'], want_pw[:4]):
+        assert _rel(a, b) <= 2e-6
+    import rollout_window_ref as R
+    want_rl = R.window_losses(p.double(), labels.double(), mask, gates, recs, torch.ones(N, device=DEV), 0.9, 0.7, 2.1)
+    for a, b in zip(alone['rollout'], want_rl[:4]):
+        assert _rel(a, b) <= 1e-5
