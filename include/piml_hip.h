@@ -486,6 +486,37 @@ int piml_crowd_stats(const float* P, const float* V, const float* M, const int* 
                      long long workspace_bytes, void* stream);
 
 /*
+ * The same statistics on the Voronoi local density of Steffen and Seyfried (2010) (voronoi.hip).  Inputs,
+ * presence, frames, the focal box, speed, bin, map cell, every sum and every output are those of piml_crowd_stats; with
+ * has_bounds a focal agent must also lie inside the walkable rectangle (bx0 <= x < bx1, by0 <= y < by1).  rho = 1 / area
+ * of the agent's cell.  dirs: a host array of `sides` (3..32) unit vectors (x, y pairs, counter-clockwise), copied into the
+ * kernel arguments.  In coordinates relative to p_i, in float32 without contraction:
+ *   the cell starts as the polygon with vertices cutoff * dirs[k];
+ *   with has_bounds it is clipped by x >= bx0 - x_i, x <= bx1 - x_i, y >= by0 - y_i, y <= by1 - y_i, in this order;
+ *   then, in slot order, by q . d <= |d|^2 / 2, d = p_j - p_i, for every present agent j of the slice below the member's
+ *   bound; pairs with |d|^2 >= 4 cutoff^2 (they cannot cut) or |d|^2 == 0 (i itself; coincident agents share one cell) are
+ *   skipped.  Obstacles do not bound cells.
+ * A clip keeps the vertices with signed distance s <= 0 and adds, on every edge whose ends differ in that, the point
+ * v_in + t (v_out - v_in), t = s_in / (s_in - s_out); on a side of the rectangle that point's coordinate along the normal
+ * is the side's own.  The area is the shoelace sum over the final vertices with float64 products and a float64 sum,
+ * rounded to float32; rho = 1 / area is a float32 true division.  The polygon holds 64 vertices: an agent whose polygon
+ * would pass that in the course of the clips, or whose area is not > 0, is left out of every statistic, has density NaN
+ * and adds 1 to dropped[s].  dropped (S) int64, zeroed by the call.  workspace: at least
+ * piml_crowd_stats_voronoi_workspace_bytes(S, T', N, rho_bins) bytes (-1 for negative arguments).  Two memsets and three
+ * launches, no host synchronisation (capturable).  Deterministic: no float atomics (map and dropped are 64-bit integer
+ * atomics); member s's results are bitwise those of an S = 1 call on member s alone.
+ * hipErrorInvalidValue: everything piml_crowd_stats refuses (its radius aside); cutoff <= 0 or not finite; sides outside
+ * 3..32; a NULL dirs or dropped; with has_bounds, a non-finite or empty rectangle.
+ */
+long long piml_crowd_stats_voronoi_workspace_bytes(int S, int frames, int N, int rho_bins);
+int piml_crowd_stats_voronoi(const float* P, const float* V, const float* M, const int* n_active, int S, int T, int N, int t0,
+                             int t1, float cutoff, const float* dirs, int sides, int has_bounds, float bx0, float bx1,
+                             float by0, float by1, int has_box, float x0, float x1, float y0, float y1, float cell, int gx,
+                             int gy, float rho_bin, int rho_bins, long long* n, long long* n_speed, double* sum_speed,
+                             double* sum_density, long long* fd_count, double* fd_sum, double* fd_sum2, long long* map,
+                             float* density, long long* dropped, void* workspace, long long workspace_bytes, void* stream);
+
+/*
  * Time-to-collision and pair-distance statistics without agent pairing (pairstats.hip), S members in one
  * call.  P, V (S, T, N, 2), M (S, T, N) float32; n_active (S) int32 or NULL as for piml_crowd_stats.  Agent i takes part
  * in slice (s, t) when M == 1 and both coordinates of P and both components of V are finite (slots at or past

@@ -118,6 +118,9 @@ SIGNATURES = {
     'piml_crowd_stats_workspace_bytes': [_i, _i, _i],
     'piml_crowd_stats': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _f, _i, _i, _f, _i,
                          _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _ll, _p],
+    'piml_crowd_stats_voronoi_workspace_bytes': [_i, _i, _i, _i],
+    'piml_crowd_stats_voronoi': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _i, _i, _f, _f, _f, _f, _i, _f, _f, _f, _f, _f,
+                                 _i, _i, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _ll, _p],
     'piml_pair_stats_workspace_bytes': [_i, _i, _i, _i],
     'piml_pair_stats': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _f, _f, _i, _f, _f, _f, _f, _f, _i, _f, _i,
                         _p, _p, _p, _p, _p, _p, _p, _p, _ll, _p],
@@ -291,6 +294,7 @@ def lib():
         L.piml_mlapm_fit_workspace_doubles.restype = _ll
         L.piml_mlapm_rollout_fit_workspace_doubles.restype = _ll
         L.piml_crowd_stats_workspace_bytes.restype = _ll
+        L.piml_crowd_stats_voronoi_workspace_bytes.restype = _ll
         L.piml_pair_stats_workspace_bytes.restype = _ll
         L.piml_mlapm_law_table_bytes.restype = _ll
         L.piml_error_string.argtypes = [_i]

@@ -456,7 +456,7 @@ class _StatsEvaluator:
         if isinstance(reference, (tuple, list)):
             self.ref_crowd, self.ref_pairs = reference
             if crowd_kw is None and self.ref_crowd is not None:
-                crowd_kw = _options_of(self.ref_crowd, ('radius', 'box', 'cell', 'rho_bin', 'rho_bins'))
+                crowd_kw = crowdstats.call_options(self.ref_crowd)
             if pair_kw is None and self.ref_pairs is not None:
                 pair_kw = _options_of(self.ref_pairs, ('radius', 'lags', 'tau_bin', 'tau_bins', 'r_bin', 'r_bins', 'r_max',
                                                        'box'))
@@ -659,6 +659,10 @@ def get_args(argv=None):
                    help="fit the law to the clip's crowd statistics, run open-world in the clip's own scene "
                         '(calibrate_mlapm_to_stats), instead of to its trajectories')
     p.add_argument('--match', type=str, default='crowd,pairs', help='--match-stats: the statistics to match (crowd, pairs)')
+    p.add_argument('--stats-density', dest='stats_density', choices=('gaussian', 'voronoi'), default='gaussian',
+                   help='--match-stats: the local density of the crowd statistics (DESIGN 4.16 / 4.20)')
+    p.add_argument('--stats-cutoff', dest='stats_cutoff', type=float, default=None,
+                   help='--stats-density voronoi: the cut-off radius of a cell (default 1.0)')
     p.add_argument('--scene-frames', dest='scene_frames', type=str, default=None,
                    help="--match-stats: the window 'a:b' of the clip that is the scene and the reference (default: all)")
     p.add_argument('--scene-jitter', dest='scene_jitter', type=float, default=0.0,
@@ -674,6 +678,11 @@ def get_args(argv=None):
         a.match = tuple(filter(None, (x.strip() for x in a.match.split(','))))
         if not a.match or any(x not in ('crowd', 'pairs') for x in a.match):
             p.error(f"--match: 'crowd', 'pairs' or both expected, got {a.match}")
+        try:
+            from .crowdstats import check_density
+            check_density(a.stats_density, a.stats_cutoff)
+        except ValueError as ex:
+            p.error(f'--stats-density / --stats-cutoff: {ex}')
         try:
             from .simulate import parse_seeds
             a.seeds = parse_seeds(a.seeds)
@@ -746,7 +755,10 @@ def _main_stats(a, raw, init):
         sys.exit(f'--match-stats: {ex}')
     lo, hi = a.scene_frames or (0, int(raw.position.shape[0]))
     box = crowdstats.auto_box(raw.position[lo:hi].numpy(), raw.mask_p[lo:hi].numpy(), 0.5)
-    ref_crowd = crowdstats.crowd_stats_of_raw(raw, box=box, frames=(lo, hi)) if 'crowd' in a.match else None
+    density_kw = {} if a.stats_density == 'gaussian' else dict(density=a.stats_density, cutoff=a.stats_cutoff)
+    ref_crowd = crowdstats.crowd_stats_of_raw(raw, box=box, frames=(lo, hi), **density_kw) if 'crowd' in a.match else None
+    if ref_crowd is not None:
+        crowdstats.print_dropped(ref_crowd, 'calibrate --match-stats')
     ref_pairs = pairstats.pair_stats_of_raw(raw, frames=(lo, hi)) if 'pairs' in a.match else None
     res = calibrate_mlapm_to_stats(scene, (ref_crowd, ref_pairs), version=a.version, init=init, fit=a.fit, frames=hi - lo,
                                    seeds=a.seeds, population=a.population, generations=a.generations,

@@ -1,15 +1,20 @@
-"""Crowd-dynamics statistics that need no agent pairing: the speed-density relation (fundamental diagram)
-on a Gaussian local density per agent, time-averaged density maps and per-frame occupancy / speed / density series, for
-simulated scenes, ensembles and recorded clips.  The pair sums run in one HIP call for all members
-(ops_metrics.crowd_stats_frames, piml_crowd_stats).
+"""Crowd-dynamics statistics that need no agent pairing: the speed-density relation (fundamental
+diagram) on a local density per agent -- a Gaussian kernel sum or the Voronoi density of Steffen and Seyfried (2010) --
+time-averaged density maps and per-frame occupancy / speed / density series, for simulated scenes, ensembles and recorded
+clips.  Everything runs in one HIP call for all members (ops_metrics.crowd_stats_frames, piml_crowd_stats;
+ops_metrics.crowd_stats_voronoi_frames, piml_crowd_stats_voronoi).
 
     python -m piml_amd.crowdstats --data sim_0.npy [sim_1.npy ...] [--ref recorded.npy] [--box x0,x1,y0,y1 | --box auto]
                                   [--radius 0.7] [--cell 0.5] [--frames a:b] [--out stats.json]
+                                  [--density voronoi [--cutoff 1.0] [--bounds x0,x1,y0,y1 | --bounds auto]]
 
 Definitions, for every focal agent i of slice (member s, frame t): present = mask 1 and a finite position; focal = present
 and inside the box [x0, x1) x [y0, y1) (every present agent without a box); rho_i = sum_j exp(-|p_j - p_i|^2 / R^2) /
 (pi R^2) over the slice's present j, j = i included; u_i = |v_i| where the velocity is finite; bin = min(floor(rho_i /
-rho_bin), rho_bins - 1); map cell (floor((x - x0) / h), floor((y - y0) / h))."""
+rho_bin), rho_bins - 1); map cell (floor((x - x0) / h), floor((y - y0) / h)).  With density='voronoi', rho_i = 1 / area of
+the agent's Voronoi cell among the slice's present agents, cut off at a regular polygon of `sides` vertices and radius
+`cutoff` around it and at the walkable rectangle `bounds` (outside which no agent is focal); agents whose cell cannot be
+formed are left out and counted in `dropped` (include/piml_hip.h has the clip rules)."""
 import argparse
 import json
 import math
@@ -20,7 +25,11 @@ import numpy as np
 import torch
 
 JSON_VERSION = 1
-ARRAYS = ('n', 'n_speed', 'sum_speed', 'sum_density', 'fd_count', 'fd_sum', 'fd_sum2', 'map', 'slices')
+ARRAYS = ('n', 'n_speed', 'sum_speed', 'sum_density', 'fd_count', 'fd_sum', 'fd_sum2', 'map', 'slices', 'dropped')
+DENSITIES = ('gaussian', 'voronoi')
+DENSITY_KEYS = ('density', 'cutoff', 'bounds', 'sides')       # the options that say which density the abscissa is
+VORONOI_SIDES = 16
+VORONOI_MAX_SIDES = 32
 
 
 def _f32(x):
@@ -34,9 +43,42 @@ def grid_shape(box, cell):
     return int(math.ceil((x1 - x0) / h)), int(math.ceil((y1 - y0) / h))
 
 
-def check_options(radius=0.7, box=None, cell=0.5, rho_bin=0.25, rho_bins=24, frames=None, T=None):
+def voronoi_dirs(sides=VORONOI_SIDES):
+    """(sides, 2) float32: (cos, sin) of 2 pi k / sides, evaluated in float64 and rounded; the cut-off polygon's vertices
+    are cutoff * dirs[k] on the host and on the device alike."""
+    ang = 2.0 * np.pi * np.arange(int(sides), dtype=np.float64) / int(sides)
+    return np.stack([np.cos(ang), np.sin(ang)], 1).astype(np.float32)
+
+
+def check_density(density='gaussian', cutoff=None, bounds=None, sides=None):
+    """ValueError on a bad density option; returns the four as the options record them: ('gaussian', None, None, None) or
+    ('voronoi', cutoff (default 1.0), bounds as 4 floats or None, sides (default 16))."""
+    if density not in DENSITIES:
+        raise ValueError(f'density must be one of {DENSITIES}, got {density!r}')
+    if density == 'gaussian':
+        if cutoff is not None or bounds is not None or sides is not None:
+            raise ValueError("cutoff, bounds and sides belong to density='voronoi'")
+        return density, None, None, None
+    cutoff = 1.0 if cutoff is None else float(cutoff)
+    if not (math.isfinite(cutoff) and _f32(cutoff) > 0 and math.isfinite(_f32(cutoff))):
+        raise ValueError(f'cutoff must be a positive number, got {cutoff}')
+    sides = VORONOI_SIDES if sides is None else sides
+    if isinstance(sides, bool) or int(sides) != sides or not 3 <= int(sides) <= VORONOI_MAX_SIDES:
+        raise ValueError(f'sides must be an integer in 3..{VORONOI_MAX_SIDES}, got {sides}')
+    if bounds is not None:
+        bounds = tuple(float(v) for v in bounds)
+        if len(bounds) != 4 or not all(math.isfinite(v) for v in bounds):
+            raise ValueError(f'bounds must be four finite numbers (x0, x1, y0, y1), got {bounds}')
+        if not (_f32(bounds[0]) < _f32(bounds[1]) and _f32(bounds[2]) < _f32(bounds[3])):
+            raise ValueError(f'bounds {bounds} are empty (need x0 < x1 and y0 < y1)')
+    return density, cutoff, bounds, int(sides)
+
+
+def check_options(radius=0.7, box=None, cell=0.5, rho_bin=0.25, rho_bins=24, frames=None, T=None, density='gaussian',
+                  cutoff=None, bounds=None, sides=None):
     """ValueError on a bad option; returns (box as 4 floats or None, (gx, gy) or None, frames (a, b) or None)."""
     from .ops_metrics import CROWD_MAX_BINS
+    check_density(density, cutoff, bounds, sides)
     if not (math.isfinite(float(radius)) and float(radius) > 0):
         raise ValueError(f'radius must be a positive number, got {radius}')
     if not (math.isfinite(float(rho_bin)) and float(rho_bin) > 0):
@@ -95,15 +137,19 @@ class CrowdStats:
     a speed; sum_speed, sum_density (S, T') float64; fd_count (S, B) int64, fd_sum, fd_sum2 (S, B) float64 (count, sum u,
     sum u^2 per density bin); map (S, gy, gx) int64 focal agent-frames per cell (None without a box); density (S, T', N)
     float32 per-agent density (NaN where not focal; None unless asked for); slices (S) the number of (member, frame)
-    slices each row holds (T' per member, more once pooled).  options: radius, box, cell, rho_bin, rho_bins, frames."""
+    slices each row holds (T' per member, more once pooled); dropped (S) focal agents left out because their Voronoi cell
+    could not be formed (0 for the Gaussian density).  options: radius, box, cell, rho_bin, rho_bins, frames and
+    density, cutoff, bounds, sides ('gaussian', None, None, None where they are not given)."""
 
     def __init__(self, arrays, options, density=None):
         for k in ARRAYS:
             v = arrays.get(k)
             setattr(self, k, None if v is None else np.asarray(v, np.float64 if k in ('sum_speed', 'sum_density', 'fd_sum',
                                                                                     'fd_sum2') else np.int64))
+        if self.dropped is None:
+            self.dropped = np.zeros(self.n.shape[0], np.int64)
         self.density = density
-        self.options = dict(options)
+        self.options = {'density': 'gaussian', 'cutoff': None, 'bounds': None, 'sides': None, **options}
 
     @property
     def members(self):
@@ -171,6 +217,8 @@ class CrowdStats:
         pool = self.pooled()
         d = {'version': JSON_VERSION, 'options': {**self.options,
                                                  'box': None if self.options.get('box') is None else list(self.options['box']),
+                                                 'bounds': None if self.options.get('bounds') is None
+                                                 else list(self.options['bounds']),
                                                  'frames': list(self.options['frames'])},
              'arrays': {k: None if getattr(self, k) is None else getattr(self, k).tolist() for k in ARRAYS},
              'pooled': {'bin_edges': self.bin_edges.tolist(), 'fd_count': pool.fd_count[0].tolist(),
@@ -192,6 +240,7 @@ class CrowdStats:
             raise ValueError(f'crowd stats JSON version {src.get("version")!r} (expected {JSON_VERSION})')
         opts = dict(src['options'])
         opts['box'] = None if opts.get('box') is None else tuple(opts['box'])
+        opts['bounds'] = None if opts.get('bounds') is None else tuple(opts['bounds'])
         opts['frames'] = tuple(opts['frames'])
         return cls(src['arrays'], opts)
 
@@ -206,27 +255,34 @@ def _json_floats(a):
 
 
 def crowd_stats(P, V, M, radius=0.7, box=None, cell=0.5, rho_bin=0.25, rho_bins=24, frames=None, return_density=False,
-                n_active=None):
+                n_active=None, density='gaussian', cutoff=None, bounds=None, sides=None):
     """The statistics of positions P (S, T, N, 2), velocities V (S, T, N, 2) and presence M (S, T, N) -- (T, N, .) is one
     member -- in one device call for all members: CrowdStats.  box (x0, x1, y0, y1) restricts the focal agents and enables
     the map with cells of `cell` m; frames (a, b) a frame range; n_active (S) ints: member s's slots at or past
-    n_active[s] never held an agent and are not swept."""
+    n_active[s] never held an agent and are not swept.  density 'gaussian' (radius) or 'voronoi' (radius is ignored;
+    cutoff, default 1.0 m; bounds (x0, x1, y0, y1), the walkable rectangle, or None; sides of the cut-off polygon, default
+    16): cutoff, bounds and sides are an error with 'gaussian'."""
     from . import ops_metrics
     P, V, M = _promote(P, V, M)
     S, T, N = P.shape[:3]
     box, grid, frames = check_options(radius, box, cell, rho_bin, rho_bins, frames, T)
+    density, cutoff, bounds, sides = check_density(density, cutoff, bounds, sides)
     frames = frames or (0, T)
     if n_active is not None:
         n_active = torch.as_tensor(n_active).reshape(-1)
         if n_active.numel() != S:
             raise ValueError(f'n_active: {n_active.numel()} bounds for {S} members')
         n_active = n_active.clamp(0, N).to(device=P.device, dtype=torch.int32)
-    out = ops_metrics.crowd_stats_frames(P, V, M, radius, box, grid, cell, rho_bin, int(rho_bins), frames, return_density,
-                                         n_active)
+    if density == 'voronoi':
+        out = ops_metrics.crowd_stats_voronoi_frames(P, V, M, cutoff, voronoi_dirs(sides), bounds, box, grid, cell, rho_bin,
+                                                     int(rho_bins), frames, return_density, n_active)
+    else:
+        out = ops_metrics.crowd_stats_frames(P, V, M, radius, box, grid, cell, rho_bin, int(rho_bins), frames,
+                                             return_density, n_active)
     host = {k: (None if v is None else v.cpu().numpy()) for k, v in out.items()}
     host['slices'] = np.full(S, frames[1] - frames[0], np.int64)
     opts = dict(radius=float(radius), box=box, cell=float(cell), rho_bin=float(rho_bin), rho_bins=int(rho_bins),
-                frames=frames)
+                frames=frames, density=density, cutoff=cutoff, bounds=bounds, sides=sides)
     return CrowdStats(host, opts, density=host.pop('density'))
 
 
@@ -235,13 +291,27 @@ def crowd_stats_of_raw(raw_data, **kw):
     return crowd_stats(raw_data.position, raw_data.velocity, raw_data.mask_p, **kw)
 
 
+def call_options(stats):
+    """The keywords that make crowd_stats take statistics comparable with `stats` (its options, frames aside)."""
+    keys = ('radius', 'box', 'cell', 'rho_bin', 'rho_bins')
+    if stats.options['density'] != 'gaussian':
+        keys += DENSITY_KEYS
+    return {k: stats.options[k] for k in keys}
+
+
+def same_density(a, b):
+    """Whether two CrowdStats measure density the same way: kind, cut-off, bounds and sides (and, for the Gaussian kind,
+    nothing else: different radii were comparable before there was a second kind and stay so)."""
+    return all(a.options[k] == b.options[k] for k in DENSITY_KEYS)
+
+
 def merge(stats):
     """Several CrowdStats with the same options (frames aside) as one member: each pooled, their frames laid end to end
     in the series, diagrams and maps added in list order."""
     if not stats:
         raise ValueError('merge: no statistics')
     pools = [s.pooled() for s in stats]
-    keys = ('radius', 'box', 'cell', 'rho_bin', 'rho_bins')
+    keys = ('radius', 'box', 'cell', 'rho_bin', 'rho_bins') + DENSITY_KEYS
     for p in pools[1:]:
         if any(p.options[k] != pools[0].options[k] for k in keys):
             raise ValueError('merge: the statistics were taken with different options')
@@ -270,6 +340,9 @@ def compare_crowd_stats(a, b, min_count=50):
       mean_speed_diff, mean_density_diff = pooled mean of a - pooled mean of b (means over all focal agent-frames)."""
     if a.options['rho_bins'] != b.options['rho_bins'] or a.options['rho_bin'] != b.options['rho_bin']:
         raise ValueError('compare_crowd_stats: the density bins differ')
+    if not same_density(a, b):
+        raise ValueError('compare_crowd_stats: the two sides measure density differently ('
+                         + ' vs '.join(', '.join(f'{k} {s.options[k]}' for k in DENSITY_KEYS) for s in (a, b)) + ')')
     pa, pb = a.pooled(), b.pooled()
     ca, cb = pa.fd_count[0], pb.fd_count[0]
     use = (ca >= min_count) & (cb >= min_count)
@@ -330,6 +403,10 @@ def get_args(argv=None):
     p.add_argument('--cell', type=float, default=0.5)
     p.add_argument('--rho_bin', type=float, default=0.25)
     p.add_argument('--rho_bins', type=int, default=24)
+    p.add_argument('--density', choices=DENSITIES, default='gaussian', help='the local density (voronoi: --radius is ignored)')
+    p.add_argument('--cutoff', type=float, default=None, help='--density voronoi: the cut-off radius of a cell (default 1.0)')
+    p.add_argument('--bounds', type=str, default=None,
+                   help="--density voronoi: the walkable rectangle x0,x1,y0,y1 that bounds the cells, or 'auto' (the --box in use)")
     p.add_argument('--frames', type=str, default=None, help="'a:b' (frames a .. b-1 of every clip)")
     p.add_argument('--min_count', type=int, default=50)
     p.add_argument('--out', type=str, default=None, help='JSON of the pooled statistics (and the comparison)')
@@ -337,8 +414,12 @@ def get_args(argv=None):
     try:
         args.box = None if args.box is None else parse_box(args.box)
         args.frames = None if args.frames is None else parse_frames(args.frames)
+        args.bounds = None if args.bounds is None else parse_box(args.bounds)
+        if args.bounds == 'auto' and args.box is None:
+            raise ValueError('--bounds auto is the --box in use: give --box')
         check_options(args.radius, None if args.box in (None, 'auto') else args.box, args.cell, args.rho_bin,
-                      args.rho_bins, args.frames)
+                      args.rho_bins, args.frames, density=args.density, cutoff=args.cutoff,
+                      bounds=None if args.bounds in (None, 'auto') else args.bounds)
     except ValueError as ex:
         p.error(str(ex))
     return args
@@ -364,6 +445,14 @@ def print_diagram(stats, tag, file=sys.stdout):
     md = _nan_div(pool.sum_density.sum(), pool.n.sum())
     print(f'[crowdstats] {tag}: {int(pool.n.sum())} focal agent-frames, mean speed {float(ms):.4f} m/s, '
           f'mean density {float(md):.4f} m^-2', file=file)
+    print_dropped(stats, tag, file)
+
+
+def print_dropped(stats, tag, file=sys.stdout):
+    """Says so when Voronoi cells could not be formed (never silently)."""
+    if int(stats.dropped.sum()):
+        print(f'[crowdstats] {tag}: {int(stats.dropped.sum())} agent-frames left out (Voronoi cell not formed; per member '
+              f'{stats.dropped.tolist()})', file=file)
 
 
 def main(argv=None):
@@ -377,6 +466,8 @@ def main(argv=None):
         print(f'[crowdstats] --box auto: {",".join(f"{v:g}" for v in box)}')
     kw = dict(radius=args.radius, box=box, cell=args.cell, rho_bin=args.rho_bin, rho_bins=args.rho_bins,
               frames=args.frames)
+    if args.density != 'gaussian':
+        kw.update(density=args.density, cutoff=args.cutoff, bounds=box if args.bounds == 'auto' else args.bounds)
     data = merge([crowd_stats_of_raw(r, **kw) for r in raws])
     print_diagram(data, 'data')
     out = {'data': data.to_json()}

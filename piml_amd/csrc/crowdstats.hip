@@ -15,77 +15,15 @@
 // Reduce pass (crowd_fd_reduce_kernel): one workgroup per (member, bin) sums its T' slots in a fixed tree (lane strides over
 // the frames, butterfly, waves in order).  No float atomics anywhere: two calls give the same bits, and member m of an
 // S-member call gives the bits of an S = 1 call on that member alone.
-#include "common.hpp"
+// The statistics pass exists twice from one body (crowd_density_body): crowd_density_kernel as above, and
+// crowd_given_density_kernel, which takes every agent's density from a.rho_in (voronoi.hip fills it) and neither stages
+// nor sweeps.  The shared declarations and the host half both entries use are in crowdstats.hpp.
+#include "crowdstats.hpp"
 #include "../../include/piml_hip.h"
 
 #include <cmath>
 
 namespace piml {
-
-constexpr int CD_THREADS = 256;
-constexpr int CD_WAVES = CD_THREADS / 64;
-constexpr int CD_TILE = 1024;                 // source slots per LDS tile (8 KiB of positions)
-constexpr int CD_MAX_BINS = 256;
-constexpr long long CD_MAX_GRID = 1 << 20;
-
-struct CrowdArgs {
-    const float *P, *V, *M;                   // (S, T, N, 2), (S, T, N, 2), (S, T, N)
-    const int* n_active;                      // (S) or NULL
-    int S, T, N, t0, Tp, B;
-    float inv_r2, rho_bin;
-    double area;                              // pi R^2
-    int has_box, gx, gy;
-    float x0, x1, y0, y1, cell;
-    long long *n, *n_speed;                   // (S, T')
-    double *sum_speed, *sum_density;          // (S, T')
-    long long* map;                           // (S, gy, gx) or NULL
-    float* density;                           // (S, T', N) or NULL
-    double *ws_sum, *ws_sum2;                 // (S T', B)
-    int* ws_count;                            // (S T', B)
-    long long *fd_count;                      // (S, B)
-    double *fd_sum, *fd_sum2;                 // (S, B)
-};
-
-__device__ __forceinline__ double cd_wave_sum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ __forceinline__ long long cd_wave_sum(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-__device__ __forceinline__ bool cd_present(float m, float2 p) { return m == 1.f && isfinite(p.x) && isfinite(p.y); }
-
-// Compacts the present agents of slots [lo, hi) (hi - lo <= CD_TILE) into src in slot order; returns their number.  Every
-// thread of the workgroup calls it; src may still be read by other waves on entry (no write before the first barrier).
-__device__ int cd_stage(const float2* P, const float* M, int lo, int hi, float2* src, int* wave_cnt) {
-    const int tid = threadIdx.x, w = tid >> 6;
-    int base = 0;
-    for (int s0 = lo; s0 < hi; s0 += CD_THREADS) {
-        const int j = s0 + tid;
-        float2 p = make_float2(0.f, 0.f);
-        bool pres = false;
-        if (j < hi) {
-            p = P[j];
-            pres = cd_present(M[j], p);
-        }
-        const u64 b = __ballot(pres);
-        if ((tid & 63) == 0) wave_cnt[w] = __popcll(b);
-        __syncthreads();
-        int before = base, total = base;
-        for (int k = 0; k < CD_WAVES; ++k) {
-            before += k < w ? wave_cnt[k] : 0;
-            total += wave_cnt[k];
-        }
-        if (pres) src[before + (int)mbcnt(b)] = p;
-        __syncthreads();                      // src complete; wave_cnt is rewritten by the next round
-        base = total;
-    }
-    return base;
-}
 
 __device__ __forceinline__ double cd_sweep(const float2* src, int cnt, float2 pi, float inv_r2) {
     double acc = 0.0;
@@ -98,8 +36,11 @@ __device__ __forceinline__ double cd_sweep(const float2* src, int cnt, float2 pi
     return acc;
 }
 
-__global__ void __launch_bounds__(CD_THREADS) crowd_density_kernel(CrowdArgs a) {
-    __shared__ float2 src[CD_TILE];
+// The statistics pass.  GIVEN: every agent's density was computed beforehand (a.rho_in, NaN where the agent is to be left
+// out); nothing is staged or swept, everything else is the same code.
+template <bool GIVEN>
+__device__ __forceinline__ void crowd_density_body(const CrowdArgs& a) {
+    __shared__ float2 src[GIVEN ? 1 : CD_TILE];
     __shared__ int wave_cnt[CD_WAVES];
     __shared__ double w_sum[CD_WAVES][CD_MAX_BINS], w_sum2[CD_WAVES][CD_MAX_BINS];
     __shared__ int w_cnt[CD_WAVES][CD_MAX_BINS];
@@ -120,8 +61,12 @@ __global__ void __launch_bounds__(CD_THREADS) crowd_density_kernel(CrowdArgs a) 
             (&w_sum2[0][0])[(k / B) * CD_MAX_BINS + k % B] = 0.0;
             (&w_cnt[0][0])[(k / B) * CD_MAX_BINS + k % B] = 0;
         }
-        const bool one_tile = bound <= CD_TILE;
-        int cnt = one_tile ? cd_stage(P, M, 0, bound, src, wave_cnt) : 0;     // (its barriers also cover the zeroing)
+        const bool one_tile = GIVEN || bound <= CD_TILE;
+        int cnt = 0;
+        if constexpr (GIVEN)
+            __syncthreads();                  // the zeroing
+        else
+            cnt = one_tile ? cd_stage(P, M, 0, bound, src, wave_cnt) : 0;     // (its barriers also cover the zeroing)
         long long n_focal = 0, n_spd = 0;
         double s_speed = 0.0, s_dens = 0.0;
         for (int c0 = 0; c0 < bound; c0 += CD_THREADS) {
@@ -133,14 +78,19 @@ __global__ void __launch_bounds__(CD_THREADS) crowd_density_kernel(CrowdArgs a) 
                 focal = cd_present(M[i], pi) &&
                         (!a.has_box || (a.x0 <= pi.x && pi.x < a.x1 && a.y0 <= pi.y && pi.y < a.y1));
             }
+            float rho_given = 0.f;
+            if constexpr (GIVEN) {
+                if (focal) rho_given = a.rho_in[sl * a.N + i];
+                focal = focal && !isnan(rho_given);
+            }
             if (!__syncthreads_or(focal)) {
                 if (a.density && i < a.N) a.density[sl * a.N + i] = NAN;
                 continue;
             }
             double acc = 0.0;
-            if (one_tile) {
+            if (!GIVEN && one_tile) {
                 acc = cd_sweep(src, cnt, pi, a.inv_r2);
-            } else {
+            } else if (!GIVEN) {
                 for (int lo = 0; lo < bound; lo += CD_TILE) {
                     cnt = cd_stage(P, M, lo, min(lo + CD_TILE, bound), src, wave_cnt);
                     acc += cd_sweep(src, cnt, pi, a.inv_r2);
@@ -148,7 +98,7 @@ __global__ void __launch_bounds__(CD_THREADS) crowd_density_kernel(CrowdArgs a) 
                 }
             }
             // epilogue: density, speed, bin, cell
-            const float rho = (float)(acc / a.area);
+            const float rho = GIVEN ? rho_given : (float)(acc / a.area);
             int bin = -1;
             float u = 0.f;
             if (focal) {
@@ -230,6 +180,9 @@ __global__ void __launch_bounds__(CD_THREADS) crowd_density_kernel(CrowdArgs a) 
     }
 }
 
+__global__ void __launch_bounds__(CD_THREADS) crowd_density_kernel(CrowdArgs a) { crowd_density_body<false>(a); }
+__global__ void __launch_bounds__(CD_THREADS) crowd_given_density_kernel(CrowdArgs a) { crowd_density_body<true>(a); }
+
 __global__ void __launch_bounds__(CD_THREADS) crowd_fd_reduce_kernel(CrowdArgs a) {
     __shared__ double red[2][CD_WAVES];
     __shared__ long long red_c[CD_WAVES];
@@ -266,7 +219,57 @@ __global__ void __launch_bounds__(CD_THREADS) crowd_fd_reduce_kernel(CrowdArgs a
     }
 }
 
-static long long cd_workspace_bytes(long long slices, int B) { return slices * B * (long long)(2 * sizeof(double) + sizeof(int)); }
+long long cd_workspace_bytes(long long slices, int B) { return slices * B * (long long)(2 * sizeof(double) + sizeof(int)); }
+
+hipError_t cd_prepare(CrowdArgs& a, const float* P, const float* V, const float* M, const int* n_active, int S, int T, int N,
+                      int t0, int t1, int has_box, float x0, float x1, float y0, float y1, float cell, int gx, int gy,
+                      float rho_bin, int rho_bins, long long* n, long long* n_speed, double* sum_speed, double* sum_density,
+                      long long* fd_count, double* fd_sum, double* fd_sum2, long long* map, float* density, void* workspace,
+                      long long workspace_bytes, long long extra_bytes, void** extra) {
+    if (S <= 0 || T <= 0 || N <= 0 || t0 < 0 || t1 > T || t1 <= t0 || !(rho_bin > 0.f) || !std::isfinite(rho_bin) ||
+        rho_bins < 1 || rho_bins > CD_MAX_BINS)
+        return hipErrorInvalidValue;
+    if (has_box && (!std::isfinite(x0) || !std::isfinite(x1) || !std::isfinite(y0) || !std::isfinite(y1) || !(x0 < x1) ||
+                    !(y0 < y1) || !(cell > 0.f) || !std::isfinite(cell) || gx < 1 || gy < 1 || !map))
+        return hipErrorInvalidValue;
+    if (!P || !V || !M || !n || !n_speed || !sum_speed || !sum_density || !fd_count || !fd_sum || !fd_sum2 || !workspace)
+        return hipErrorInvalidValue;
+    const int Tp = t1 - t0;
+    const long long slices = (long long)S * Tp;
+    if (workspace_bytes < cd_workspace_bytes(slices, rho_bins) + extra_bytes) return hipErrorInvalidValue;
+    a = CrowdArgs{};
+    a.P = P, a.V = V, a.M = M, a.n_active = n_active;
+    a.S = S, a.T = T, a.N = N, a.t0 = t0, a.Tp = Tp, a.B = rho_bins;
+    a.rho_bin = rho_bin;
+    a.has_box = has_box ? 1 : 0, a.gx = gx, a.gy = gy;
+    a.x0 = x0, a.x1 = x1, a.y0 = y0, a.y1 = y1, a.cell = cell;
+    a.n = n, a.n_speed = n_speed, a.sum_speed = sum_speed, a.sum_density = sum_density;
+    a.map = has_box ? map : nullptr;
+    a.density = density;
+    a.ws_sum = static_cast<double*>(workspace);
+    a.ws_sum2 = a.ws_sum + slices * rho_bins;
+    a.ws_count = reinterpret_cast<int*>(a.ws_sum2 + slices * rho_bins);
+    a.fd_count = fd_count, a.fd_sum = fd_sum, a.fd_sum2 = fd_sum2;
+    if (extra) *extra = a.ws_count + slices * rho_bins;
+    return hipSuccess;
+}
+
+hipError_t cd_run(const CrowdArgs& a, bool given_density, hipStream_t st) {
+    const long long slices = (long long)a.S * a.Tp;
+    if (a.map) {
+        const hipError_t e = hipMemsetAsync(a.map, 0, (size_t)a.S * a.gy * a.gx * sizeof(long long), st);
+        if (e != hipSuccess) return e;
+    }
+    const dim3 grid((unsigned)(slices < CD_MAX_GRID ? slices : CD_MAX_GRID));
+    if (given_density)
+        hipLaunchKernelGGL(crowd_given_density_kernel, grid, dim3(CD_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL(crowd_density_kernel, grid, dim3(CD_THREADS), 0, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(crowd_fd_reduce_kernel, dim3((unsigned)(a.S * a.B)), dim3(CD_THREADS), 0, st, a);
+    return hipGetLastError();
+}
 
 }  // namespace piml
 
@@ -282,41 +285,13 @@ PIML_API int piml_crowd_stats(const float* P, const float* V, const float* M, co
                               int gx, int gy, float rho_bin, int rho_bins, long long* n, long long* n_speed,
                               double* sum_speed, double* sum_density, long long* fd_count, double* fd_sum, double* fd_sum2,
                               long long* map, float* density, void* workspace, long long workspace_bytes, void* stream) {
-    if (S <= 0 || T <= 0 || N <= 0 || t0 < 0 || t1 > T || t1 <= t0 || !(radius > 0.f) || !std::isfinite(radius) ||
-        !(rho_bin > 0.f) || !std::isfinite(rho_bin) || rho_bins < 1 || rho_bins > CD_MAX_BINS)
-        return hipErrorInvalidValue;
-    if (has_box && (!std::isfinite(x0) || !std::isfinite(x1) || !std::isfinite(y0) || !std::isfinite(y1) || !(x0 < x1) ||
-                    !(y0 < y1) || !(cell > 0.f) || !std::isfinite(cell) || gx < 1 || gy < 1 || !map))
-        return hipErrorInvalidValue;
-    if (!P || !V || !M || !n || !n_speed || !sum_speed || !sum_density || !fd_count || !fd_sum || !fd_sum2 || !workspace)
-        return hipErrorInvalidValue;
-    const int Tp = t1 - t0;
-    const long long slices = (long long)S * Tp;
-    if (workspace_bytes < cd_workspace_bytes(slices, rho_bins)) return hipErrorInvalidValue;
-    CrowdArgs a{};
-    a.P = P, a.V = V, a.M = M, a.n_active = n_active;
-    a.S = S, a.T = T, a.N = N, a.t0 = t0, a.Tp = Tp, a.B = rho_bins;
-    a.inv_r2 = 1.f / (radius * radius);
-    a.rho_bin = rho_bin;
-    a.area = M_PI * (double)radius * (double)radius;
-    a.has_box = has_box ? 1 : 0, a.gx = gx, a.gy = gy;
-    a.x0 = x0, a.x1 = x1, a.y0 = y0, a.y1 = y1, a.cell = cell;
-    a.n = n, a.n_speed = n_speed, a.sum_speed = sum_speed, a.sum_density = sum_density;
-    a.map = has_box ? map : nullptr;
-    a.density = density;
-    a.ws_sum = static_cast<double*>(workspace);
-    a.ws_sum2 = a.ws_sum + slices * rho_bins;
-    a.ws_count = reinterpret_cast<int*>(a.ws_sum2 + slices * rho_bins);
-    a.fd_count = fd_count, a.fd_sum = fd_sum, a.fd_sum2 = fd_sum2;
-    hipStream_t st = as_stream(stream);
-    if (a.map) {
-        const hipError_t e = hipMemsetAsync(map, 0, (size_t)S * gy * gx * sizeof(long long), st);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(crowd_density_kernel, dim3((unsigned)(slices < CD_MAX_GRID ? slices : CD_MAX_GRID)), dim3(CD_THREADS),
-                       0, st, a);
-    hipError_t e = hipGetLastError();
+    if (!(radius > 0.f) || !std::isfinite(radius)) return hipErrorInvalidValue;
+    CrowdArgs a;
+    const hipError_t e = cd_prepare(a, P, V, M, n_active, S, T, N, t0, t1, has_box, x0, x1, y0, y1, cell, gx, gy, rho_bin,
+                                    rho_bins, n, n_speed, sum_speed, sum_density, fd_count, fd_sum, fd_sum2, map, density,
+                                    workspace, workspace_bytes, 0, nullptr);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(crowd_fd_reduce_kernel, dim3((unsigned)(S * rho_bins)), dim3(CD_THREADS), 0, st, a);
-    return hipGetLastError();
+    a.inv_r2 = 1.f / (radius * radius);
+    a.area = M_PI * (double)radius * (double)radius;
+    return cd_run(a, false, as_stream(stream));
 }

@@ -76,13 +76,8 @@ def mmd_frames(x, y, mask_x=None, mask_y=None, kernel_mul=2.0, kernel_num=5, fix
 CROWD_MAX_BINS = 256          # piml_crowd_stats' limit on rho_bins
 
 
-def crowd_stats_frames(P, V, M, radius=0.7, box=None, grid=None, cell=0.5, rho_bin=0.25, rho_bins=24, frames=None,
-                       return_density=False, n_active=None):
-    """The device half of piml_amd.crowdstats.crowd_stats (piml_crowd_stats; DESIGN 4.16): P, V (S, T, N, 2) and M
-    (S, T, N) float32 GPU tensors, box (x0, x1, y0, y1) with its grid (gx, gy) or None, frames (a, b) or None,
-    n_active (S) int32 GPU tensor or None.  Returns a dict of GPU tensors -- n, n_speed (S, T') int64, sum_speed,
-    sum_density (S, T') float64, fd_count (S, B) int64, fd_sum, fd_sum2 (S, B) float64, map (S, gy, gx) int64 or None,
-    density (S, T', N) float32 or None -- with no host synchronisation (capturable in a graph)."""
+def _crowd_setup(P, V, M, box, grid, rho_bins, frames, return_density, n_active):
+    """What the two crowd-statistics calls share: checked inputs, the frame range, the box as numbers and the outputs."""
     P, V, M = _gpu_f32('P', P), _gpu_f32('V', V), _gpu_f32('M', M)
     if P.dim() != 4 or P.shape[-1] != 2 or V.shape != P.shape or M.shape != P.shape[:3]:
         raise ValueError(f'expected P, V (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(V.shape)}, '
@@ -97,7 +92,7 @@ def crowd_stats_frames(P, V, M, radius=0.7, box=None, grid=None, cell=0.5, rho_b
             raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
         n_active = n_active.contiguous()
     gx, gy = (1, 1) if box is None else (int(grid[0]), int(grid[1]))
-    x0, x1, y0, y1 = (0.0, 0.0, 0.0, 0.0) if box is None else (float(v) for v in box)
+    rect = (0.0, 0.0, 0.0, 0.0) if box is None else tuple(float(v) for v in box)
     i64, f64 = dict(device=dev, dtype=torch.int64), dict(device=dev, dtype=torch.float64)
     shape_s, shape_b = (S, max(Tp, 0)), (S, max(B, 0))
     out = dict(n=torch.empty(shape_s, **i64), n_speed=torch.empty(shape_s, **i64), sum_speed=torch.empty(shape_s, **f64),
@@ -105,17 +100,59 @@ def crowd_stats_frames(P, V, M, radius=0.7, box=None, grid=None, cell=0.5, rho_b
                fd_sum=torch.empty(shape_b, **f64), fd_sum2=torch.empty(shape_b, **f64),
                map=torch.empty(S, gy, gx, **i64) if box is not None else None,
                density=torch.empty(S, max(Tp, 0), N, device=dev, dtype=torch.float32) if return_density else None)
+    return P, V, M, n_active, (S, T, N, a, b), (Tp, B), rect, (gx, gy), out
+
+
+def _crowd_out_ptrs(out):
+    return tuple(_ptr(out[k]) for k in ('n', 'n_speed', 'sum_speed', 'sum_density', 'fd_count', 'fd_sum', 'fd_sum2', 'map',
+                                        'density'))
+
+
+def crowd_stats_frames(P, V, M, radius=0.7, box=None, grid=None, cell=0.5, rho_bin=0.25, rho_bins=24, frames=None,
+                       return_density=False, n_active=None):
+    """The device half of piml_amd.crowdstats.crowd_stats (piml_crowd_stats; DESIGN 4.16): P, V (S, T, N, 2) and M
+    (S, T, N) float32 GPU tensors, box (x0, x1, y0, y1) with its grid (gx, gy) or None, frames (a, b) or None,
+    n_active (S) int32 GPU tensor or None.  Returns a dict of GPU tensors -- n, n_speed (S, T') int64, sum_speed,
+    sum_density (S, T') float64, fd_count (S, B) int64, fd_sum, fd_sum2 (S, B) float64, map (S, gy, gx) int64 or None,
+    density (S, T', N) float32 or None -- with no host synchronisation (capturable in a graph)."""
+    P, V, M, n_active, dims, (Tp, B), rect, (gx, gy), out = _crowd_setup(P, V, M, box, grid, rho_bins, frames,
+                                                                         return_density, n_active)
     L = _lib.lib()
-    ws_bytes = L.piml_crowd_stats_workspace_bytes(S, max(Tp, 0), max(B, 0))
-    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
-    with torch.cuda.device(dev):
-        _lib.check(L.piml_crowd_stats(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), S, T, N, a, b, float(radius),
-                                      int(box is not None), x0, x1, y0, y1, float(cell), gx, gy, float(rho_bin), B,
-                                      _ptr(out['n']), _ptr(out['n_speed']), _ptr(out['sum_speed']),
-                                      _ptr(out['sum_density']), _ptr(out['fd_count']), _ptr(out['fd_sum']),
-                                      _ptr(out['fd_sum2']), _ptr(out['map']), _ptr(out['density']), _ptr(ws),
-                                      ws.numel(), _stream()),
+    ws_bytes = L.piml_crowd_stats_workspace_bytes(dims[0], max(Tp, 0), max(B, 0))
+    ws = torch.empty(max(ws_bytes, 8), device=P.device, dtype=torch.uint8)
+    with torch.cuda.device(P.device):
+        _lib.check(L.piml_crowd_stats(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), *dims, float(radius),
+                                      int(box is not None), *rect, float(cell), gx, gy, float(rho_bin), B,
+                                      *_crowd_out_ptrs(out), _ptr(ws), ws.numel(), _stream()),
                    'piml_crowd_stats')
+    return out
+
+
+def crowd_stats_voronoi_frames(P, V, M, cutoff=1.0, dirs=None, bounds=None, box=None, grid=None, cell=0.5, rho_bin=0.25,
+                               rho_bins=24, frames=None, return_density=False, n_active=None):
+    """crowd_stats_frames on the Voronoi density (piml_crowd_stats_voronoi): cutoff the cells' cut-off radius,
+    dirs (sides, 2) float32 unit vectors on the host (crowdstats.voronoi_dirs), bounds (x0, x1, y0, y1) the walkable
+    rectangle or None.  The same dict, and dropped (S) int64: the focal agents whose cell could not be formed."""
+    import ctypes
+    import numpy as np
+    P, V, M, n_active, dims, (Tp, B), rect, (gx, gy), out = _crowd_setup(P, V, M, box, grid, rho_bins, frames,
+                                                                         return_density, n_active)
+    S, N = dims[0], dims[2]
+    dirs = np.ascontiguousarray(dirs, np.float32)
+    if dirs.ndim != 2 or dirs.shape[1] != 2:
+        raise ValueError(f'dirs: expected (sides, 2), got {dirs.shape}')
+    out['dropped'] = torch.empty(S, device=P.device, dtype=torch.int64)
+    brect = (0.0, 0.0, 0.0, 0.0) if bounds is None else tuple(float(v) for v in bounds)
+    L = _lib.lib()
+    ws_bytes = L.piml_crowd_stats_voronoi_workspace_bytes(S, max(Tp, 0), N, max(B, 0))
+    ws = torch.empty(max(ws_bytes, 8), device=P.device, dtype=torch.uint8)
+    with torch.cuda.device(P.device):
+        _lib.check(L.piml_crowd_stats_voronoi(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), *dims, float(cutoff),
+                                              dirs.ctypes.data_as(ctypes.c_void_p), int(dirs.shape[0]),
+                                              int(bounds is not None), *brect, int(box is not None), *rect, float(cell),
+                                              gx, gy, float(rho_bin), B, *_crowd_out_ptrs(out), _ptr(out['dropped']),
+                                              _ptr(ws), ws.numel(), _stream()),
+                   'piml_crowd_stats_voronoi')
     return out
 
 

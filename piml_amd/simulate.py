@@ -59,6 +59,10 @@ def get_args(argv=None):
     p.add_argument('--stats', type=str, default=None,
                    help='write the crowd statistics (piml_amd.crowdstats, defaults, no box) of the run or ensemble as JSON '
                         'to this path instead of writing clips')
+    p.add_argument('--stats-density', dest='stats_density', choices=('gaussian', 'voronoi'), default='gaussian',
+                   help='--stats: the local density of the fundamental diagram (DESIGN 4.16 / 4.20)')
+    p.add_argument('--stats-cutoff', dest='stats_cutoff', type=float, default=None,
+                   help='--stats-density voronoi: the cut-off radius of a cell (default 1.0)')
     p.add_argument('--pair-stats', dest='pair_stats', type=str, default=None,
                    help='write the time-to-collision and pair-distance statistics (piml_amd.pairstats, defaults, no box) '
                         'of the run or ensemble as JSON to this path instead of writing clips')
@@ -66,6 +70,11 @@ def get_args(argv=None):
     p.add_argument('--uniform_desired_speed', action=argparse.BooleanOptionalAction, default=None,
                    help="uniform desired speed (default: the scene's own; GC and the crosswalk no, the others yes)")
     own, rest = p.parse_known_args(argv)
+    try:
+        from .crowdstats import check_density
+        check_density(own.stats_density, own.stats_cutoff)
+    except ValueError as ex:
+        p.error(f'--stats-density / --stats-cutoff: {ex}')
     if own.seeds is not None:
         try:
             own.seeds = parse_seeds(own.seeds)
@@ -208,11 +217,15 @@ def _stats_path(own):
     return ', '.join(p for p in (own.stats, own.pair_stats) if p is not None)
 
 
+def _crowd_kw(own):
+    return {} if own.stats_density == 'gaussian' else dict(density=own.stats_density, cutoff=own.stats_cutoff)
+
+
 def _stats(res, own):
     """--stats / --pair-stats: the CrowdStats / PairStats JSON of a run or an ensemble (one call for every member)."""
     if own.stats is not None:
         from . import crowdstats
-        st = res.crowd_stats()
+        st = res.crowd_stats(**_crowd_kw(own))
         st.to_json(own.stats)
         crowdstats.print_diagram(st, 'simulate --stats')
     if own.pair_stats is not None:
@@ -228,7 +241,9 @@ def _sweep(sim, scenario, own, run_kw):
     sw = sim.simulate_sweep(scenario, own.frames, own.mlapm_sweep, own.seeds, capacity=own.capacity, **run_kw)
     groups = [sw.members_of(c) for c in range(sw.n_candidates)]
     if own.stats is not None:
-        st = sw.crowd_stats()
+        from . import crowdstats
+        st = sw.crowd_stats(**_crowd_kw(own))
+        crowdstats.print_dropped(st, 'simulate --stats')
         entries = [{'params': sw.params[c], 'file': own.params_sweep[c], 'stats': st.select(g).pooled().to_json()}
                    for c, g in enumerate(groups)]
         with open(own.stats, 'w') as fh:

@@ -3,8 +3,12 @@
 recorded GC clip.  Device time per call from events around `reps` back-to-back calls of ops_metrics.crowd_stats_frames
 (two launches and a memset); the end-to-end time of crowdstats.crowd_stats (with its read-back) from a host clock.  Pair
 terms = sum over slices of (focal agents x present agents), what the density pass must evaluate.
+--density voronoi times piml_crowd_stats_voronoi (cutoff 1.0, the box as the walkable area where there is a
+box) and the Gaussian call in the same run, the two alternating `--repeats` times: every figure is the median of the
+repeats, with their smallest and largest value as the run-to-run spread.
 
-    python tools/time_crowdstats.py [--reps 20] [--out profiles/crowdstats_time.json]"""
+    python tools/time_crowdstats.py [--reps 20] [--out profiles/crowdstats_time.json]
+    python tools/time_crowdstats.py --density voronoi [--repeats 5] [--out profiles/voronoi_time.json]"""
 import argparse
 import json
 import os
@@ -32,24 +36,30 @@ def pair_terms(P, M, n_active, box):
     return int((focal.sum(-1).double() * pres.sum(-1).double()).sum().item())
 
 
-def time_one(P, V, M, n_active, box, reps):
+def time_one(P, V, M, n_active, box, reps, density='gaussian'):
     from piml_amd import crowdstats, ops_metrics
     grid = None if box is None else crowdstats.grid_shape(box, 0.5)
     na = None if n_active is None else torch.tensor(n_active, device=P.device, dtype=torch.int32)
-    args = (P, V, M, 0.7, box, grid, 0.5, 0.25, 24, None, False, na)
+    if density == 'voronoi':
+        dirs = crowdstats.voronoi_dirs()
+        call = lambda: ops_metrics.crowd_stats_voronoi_frames(P, V, M, 1.0, dirs, box, box, grid, 0.5, 0.25, 24, None, False, na)
+        kw = dict(density='voronoi', bounds=box)
+    else:
+        call = lambda: ops_metrics.crowd_stats_frames(P, V, M, 0.7, box, grid, 0.5, 0.25, 24, None, False, na)
+        kw = {}
     for _ in range(3):
-        ops_metrics.crowd_stats_frames(*args)
+        call()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(reps):
-        ops_metrics.crowd_stats_frames(*args)
+        call()
     e1.record()
     torch.cuda.synchronize()
     dev_ms = e0.elapsed_time(e1) / reps
     t = time.perf_counter()
     for _ in range(reps):
-        crowdstats.crowd_stats(P, V, M, box=box, n_active=n_active)
+        crowdstats.crowd_stats(P, V, M, box=box, n_active=n_active, **kw)
     torch.cuda.synchronize()
     e2e_ms = (time.perf_counter() - t) * 1e3 / reps
     pairs = pair_terms(P, M, n_active, box)
@@ -57,12 +67,30 @@ def time_one(P, V, M, n_active, box, reps):
                 pair_terms_per_s=float(f'{pairs / (dev_ms * 1e-3):.4g}'))
 
 
+def time_both(P, V, M, n_active, box, reps, repeats):
+    """Gaussian and Voronoi alternating `repeats` times: {density: time_one's dict with medians, and the spread}."""
+    runs = {'gaussian': [], 'voronoi': []}
+    for _ in range(repeats):
+        for density in runs:
+            runs[density].append(time_one(P, V, M, n_active, box, reps, density))
+    out = {}
+    for density, rs in runs.items():
+        med = lambda k: sorted(r[k] for r in rs)[len(rs) // 2]
+        out[density] = dict(device_ms=med('device_ms'), end_to_end_ms=med('end_to_end_ms'),
+                            device_ms_spread=[min(r['device_ms'] for r in rs), max(r['device_ms'] for r in rs)],
+                            pair_terms=rs[0]['pair_terms'])
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--members', type=str, default='1,8,32')
     ap.add_argument('--out', type=str, default=None)
+    ap.add_argument('--density', choices=('gaussian', 'voronoi'), default='gaussian')
+    ap.add_argument('--repeats', type=int, default=5, help='--density voronoi: alternating repeats of the two calls')
     a = ap.parse_args(argv)
+    one = (lambda *x: time_both(*x, a.repeats)) if a.density == 'voronoi' else time_one
     from piml_amd.models.mlapm import MLAPM
     from piml_amd.scenarios import SCENARIOS
     from piml_amd.data.data import RawData
@@ -75,15 +103,21 @@ def main(argv=None):
         n_active = [min(int(n), cap) for n in ens.spawned]
         res['capacity'] = cap
         for tag, box in (('no_box', None), ('box', BOX)):
-            r = time_one(ens.position, ens.velocity, ens.mask_p, n_active, box, a.reps)
+            r = one(ens.position, ens.velocity, ens.mask_p, n_active, box, a.reps)
             res['gc'].setdefault(str(S), {})[tag] = r
             print(f'[crowdstats] GC S={S} x 750 frames, cap {cap}, {tag}: {r}', flush=True)
         del ens
     raw = RawData()
     raw.load_trajectory_data(os.path.join(ROOT, GC_CLIP))
     dev = lambda x: x.to('cuda').contiguous()
-    r = time_one(dev(raw.position)[None], dev(raw.velocity)[None], dev(raw.mask_p)[None], None, BOX, a.reps)
+    r = one(dev(raw.position)[None], dev(raw.velocity)[None], dev(raw.mask_p)[None], None, BOX, a.reps)
     res['recorded_gc_clip'] = dict(frames=raw.num_steps, agents=raw.num_pedestrians, **r)
+    if a.density == 'voronoi':
+        from piml_amd import _lib
+        usage = _lib.kernel_resource_usage()
+        res.update(density='voronoi', cutoff=1.0, sides=16, repeats=a.repeats,
+                   kernels={k: usage[k] for k in ('voronoi_cell_kernel', 'crowd_given_density_kernel', 'crowd_density_kernel')
+                            if k in usage})
     print(f'[crowdstats] recorded GC clip ({raw.num_steps} frames, {raw.num_pedestrians} agents), box: {r}', flush=True)
     if a.out:
         with open(a.out, 'w') as fh:
