@@ -549,6 +549,39 @@ int piml_pair_stats(const float* P, const float* V, const float* M, const int* n
                     long long workspace_bytes, void* stream);
 
 /*
+ * Collective-motion statistics (flowstats.hip), S members in one call: the velocity-velocity correlation over
+ * distance, the lane order parameter of Rex and Loewen (2007) and the velocity field.  P, V, M, n_active, the frames
+ * [t0, t1) and the box as for piml_pair_stats.  Agent i takes part in slice (s, t) when M == 1, both coordinates of P are
+ * finite and both components of V are finite and below 1024 in magnitude; it is focal when it takes part and has_box == 0
+ * or x0 <= x < x1 and y0 <= y < y1.  A mover has s = sqrt(vx^2 + vy^2) >= v_min and the heading h = v / s; a lane mover has
+ * |v.e| >= v_min along e = (ex, ey) and the direction sign(v.e).  Same-frame ordered pairs only, in float32 (true divisions
+ * and square roots, no contraction), d = p_j - p_i, Q = 2^20.  Outputs, int64:
+ *   corr_pairs, corr_sum (S, r_bins): focal mover i, mover j != i (as a slot), r = sqrt(|d|^2) < r_max, by floor(r / r_bin)
+ *     where that is < r_bins: the pairs and the sum of llrintf((h_i.h_j) Q);
+ *   lane_n, lane_sum, lane_same, lane_opp, dir_plus, dir_minus (S, T'): focal lane mover i counts the lane movers j != i
+ *     with |d.(-ey, ex)| < lane_width and |d.e| < lane_length as n_same (equal direction) or n_opp; dir_plus / dir_minus
+ *     count the focal lane movers by direction; those with n_same + n_opp > 0 add 1 to lane_n, llrintf(phi Q) with
+ *     phi = ((n_same - n_opp) / (n_same + n_opp))^2 to lane_sum, n_same to lane_same and n_opp to lane_opp;
+ *   map_n, map_vx, map_vy (S, gy, gx), has_box only: every focal participant adds 1, llrintf(vx Q), llrintf(vy Q) to the cell
+ *     (floor((x - x0) / cell), floor((y - y0) / cell)) of piml_crowd_stats when it lies in the grid.
+ * workspace: at least piml_flow_stats_workspace_bytes(S, r_bins, gx, gy) bytes (gx = gy = 0 without a box; -1 for negative
+ * arguments).  One memset and two launches, no host synchronisation (capturable).  Deterministic: integer outputs only,
+ * added with integer atomics; member s's results are bitwise those of an S = 1 call on member s alone.  S, T' or N == 0:
+ * success, nothing is done.
+ * hipErrorInvalidValue, before any HIP call: S, T or N < 0, N > 65536 (the per-slice u32 counters), frames outside [0, T]
+ * or t1 < t0, v_min, r_bin, r_max, lane_width or lane_length <= 0 or not finite, r_bins outside 1..256,
+ * | |e|^2 - 1 | > 1e-4, a non-finite or empty box, cell <= 0, gx or gy < 1; then, unless there is nothing to do, a NULL
+ * input, output (the maps with a box only) or workspace, or a workspace too small.
+ */
+long long piml_flow_stats_workspace_bytes(int S, int r_bins, int gx, int gy);
+int piml_flow_stats(const float* P, const float* V, const float* M, const int* n_active, int S, int T, int N, int t0, int t1,
+                    float v_min, float r_bin, int r_bins, float r_max, float ex, float ey, float lane_width,
+                    float lane_length, int has_box, float x0, float x1, float y0, float y1, float cell, int gx, int gy,
+                    long long* corr_pairs, long long* corr_sum, long long* lane_n, long long* lane_sum, long long* lane_same,
+                    long long* lane_opp, long long* dir_plus, long long* dir_minus, long long* map_n, long long* map_vx,
+                    long long* map_vy, void* workspace, long long workspace_bytes, void* stream);
+
+/*
  * utils.calc_acceleration (src/utils/utils.py:31-100): version 0/1/2 = 'v0'/'v1'/'v2' with the
  * caller-supplied constants (A, B, C, D, theta [rad]); rows of >= 2 floats -> acc (rows, 2).
  */

@@ -202,3 +202,50 @@ def pair_stats_frames(P, V, M, radius=0.5, lags=(64, 128, 192), tau_bin=0.1, tau
                                      _ptr(out['min_ttc']), _ptr(ws), ws.numel(), _stream()),
                    'piml_pair_stats')
     return out
+
+
+FLOW_MAX_BINS = 256           # piml_flow_stats' limits on r_bins and the slots per frame
+FLOW_MAX_N = 65536
+FLOW_Q = 1 << 20              # the fixed-point scale of corr_sum, lane_sum, map_vx and map_vy
+FLOW_SERIES = ('lane_n', 'lane_sum', 'lane_same', 'lane_opp', 'dir_plus', 'dir_minus')
+
+
+def flow_stats_frames(P, V, M, v_min=0.1, r_bin=0.1, r_bins=60, r_max=6.0, axis=(1.0, 0.0), lane_width=0.5,
+                      lane_length=5.0, box=None, grid=None, cell=0.5, frames=None, n_active=None):
+    """The device half of piml_amd.flowstats.flow_stats (piml_flow_stats): P, V (S, T, N, 2) and M (S, T, N)
+    float32 GPU tensors, axis a unit 2-vector, box (x0, x1, y0, y1) with its grid (gx, gy) or None, frames (a, b) or None,
+    n_active (S) int32 GPU tensor or None.  Returns a dict of int64 GPU tensors -- corr_pairs, corr_sum (S, r_bins);
+    lane_n, lane_sum, lane_same, lane_opp, dir_plus, dir_minus (S, T'); map_n, map_vx, map_vy (S, gy, gx) or None -- with
+    no host synchronisation (capturable in a graph)."""
+    P, V, M = _gpu_f32('P', P), _gpu_f32('V', V), _gpu_f32('M', M)
+    if P.dim() != 4 or P.shape[-1] != 2 or V.shape != P.shape or M.shape != P.shape[:3]:
+        raise ValueError(f'expected P, V (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(V.shape)}, '
+                         f'{tuple(M.shape)}')
+    S, T, N = P.shape[:3]
+    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    RB, Tp = int(r_bins), max(b - a, 0)
+    dev = P.device
+    if n_active is not None:
+        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
+                or tuple(n_active.shape) != (S,):
+            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
+        n_active = n_active.contiguous()
+    gx, gy = (0, 0) if box is None else (int(grid[0]), int(grid[1]))
+    rect = (0.0, 0.0, 0.0, 0.0) if box is None else tuple(float(v) for v in box)
+    # a call with nothing to do leaves its outputs alone: hand it zeros
+    new = torch.zeros if S * Tp * N == 0 else torch.empty
+    i64 = dict(device=dev, dtype=torch.int64)
+    out = {k: new(S, max(RB, 0), **i64) for k in ('corr_pairs', 'corr_sum')}
+    out.update({k: new(S, Tp, **i64) for k in FLOW_SERIES})
+    out.update({k: new(S, gy, gx, **i64) if box is not None else None for k in ('map_n', 'map_vx', 'map_vy')})
+    L = _lib.lib()
+    ws_bytes = L.piml_flow_stats_workspace_bytes(S, max(RB, 0), max(gx, 0), max(gy, 0))
+    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        _lib.check(L.piml_flow_stats(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), S, T, N, a, b, float(v_min), float(r_bin),
+                                     RB, float(r_max), float(axis[0]), float(axis[1]), float(lane_width),
+                                     float(lane_length), int(box is not None), *rect, float(cell), gx, gy,
+                                     *(_ptr(out[k]) for k in ('corr_pairs', 'corr_sum') + FLOW_SERIES
+                                       + ('map_n', 'map_vx', 'map_vy')), _ptr(ws), ws.numel(), _stream()),
+                   'piml_flow_stats')
+    return out

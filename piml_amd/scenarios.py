@@ -370,6 +370,11 @@ class ScenarioResult(types.SimpleNamespace):
         from .pairstats import pair_stats
         return pair_stats(self.position, self.velocity, self.mask_p, n_active=[self.num_agents], **kw)
 
+    def flow_stats(self, **kw):
+        """piml_amd.flowstats.flow_stats of the run (simulated velocities; slots past num_agents not swept)."""
+        from .flowstats import flow_stats
+        return flow_stats(self.position, self.velocity, self.mask_p, n_active=[self.num_agents], **kw)
+
 
 class ScenarioEnsemble(types.SimpleNamespace):
     """What `BaseSimulator.simulate_ensemble` returns: the ScenarioResult fields with a leading member axis -- position /
@@ -408,6 +413,14 @@ class ScenarioEnsemble(types.SimpleNamespace):
         from .pairstats import pair_stats
         cap = self.position.shape[2]
         return pair_stats(self.position, self.velocity, self.mask_p, n_active=[min(int(n), cap) for n in self.spawned], **kw)
+
+    def flow_stats(self, **kw):
+        """piml_amd.flowstats.flow_stats of every member in one call (member m's slots past its num_agents not swept):
+        member m's statistics are bitwise those of member(m).flow_stats(**kw) (axis='auto' is taken over all members: hand
+        a member the ensemble's `options['axis']`)."""
+        from .flowstats import flow_stats
+        cap = self.position.shape[2]
+        return flow_stats(self.position, self.velocity, self.mask_p, n_active=[min(int(n), cap) for n in self.spawned], **kw)
 
     def collision_counts(self, threshold):
         """Per-member totals of collision_count(member.position, threshold, reduction='sum'): a list of S floats, one

@@ -9,6 +9,8 @@ reads.
     python -m piml_amd.simulate --seeds 0:32 --stats stats.json      (crowd statistics of the run, no clips written)
     python -m piml_amd.simulate --seeds 0:32 --pair-stats pairs.json      (time-to-collision statistics, no clips written)
     python -m piml_amd.simulate --law mlapm --scene-from ucy.npy --seeds 0:32 --pair-stats sim.json   (a clip as the scene)
+    python -m piml_amd.simulate --scenario crosswalk --seeds 0:32 --flow-stats flow.json [--flow-axis x|y|auto|deg]
+                                (velocity correlation and lane order, no clips written)
     python -m piml_amd.simulate --law mlapm --params-sweep a.json b.json --seeds 0:8 --stats sweep.json
                                 (one law per file, every law on every seed in ONE ensemble run; statistics per candidate)
 
@@ -66,6 +68,11 @@ def get_args(argv=None):
     p.add_argument('--pair-stats', dest='pair_stats', type=str, default=None,
                    help='write the time-to-collision and pair-distance statistics (piml_amd.pairstats, defaults, no box) '
                         'of the run or ensemble as JSON to this path instead of writing clips')
+    p.add_argument('--flow-stats', dest='flow_stats', type=str, default=None,
+                   help='write the collective-motion statistics (piml_amd.flowstats: velocity correlation, lane order; '
+                        'defaults, no box) of the run or ensemble as JSON to this path instead of writing clips')
+    p.add_argument('--flow-axis', dest='flow_axis', type=str, default='x',
+                   help="--flow-stats: the lane axis, x, y, auto (principal axis of the velocities) or an angle in degrees")
     p.add_argument('--time_unit', type=float, default=0.08)
     p.add_argument('--uniform_desired_speed', action=argparse.BooleanOptionalAction, default=None,
                    help="uniform desired speed (default: the scene's own; GC and the crosswalk no, the others yes)")
@@ -75,12 +82,17 @@ def get_args(argv=None):
         check_density(own.stats_density, own.stats_cutoff)
     except ValueError as ex:
         p.error(f'--stats-density / --stats-cutoff: {ex}')
+    try:
+        from .flowstats import parse_axis
+        own.flow_axis = parse_axis(own.flow_axis)
+    except ValueError as ex:
+        p.error(f'--flow-axis: {ex}')
     if own.seeds is not None:
         try:
             own.seeds = parse_seeds(own.seeds)
         except ValueError as ex:
             p.error(f'--seeds: {ex}')
-        if '{seed}' not in own.out and own.stats is None and own.pair_stats is None:
+        if '{seed}' not in own.out and not _stats_path(own):
             p.error("--seeds: --out must contain '{seed}' (one clip per seed)")
     if own.scene_from is not None:
         if own.scenario != p.get_default('scenario'):
@@ -98,7 +110,7 @@ def get_args(argv=None):
             p.error('--params-sweep takes the place of --params: not both')
         if own.law != 'mlapm' or own.seeds is None:
             p.error('--params-sweep needs --law mlapm and --seeds')
-        if own.stats is None and own.pair_stats is None and '{candidate}' not in own.out:
+        if not _stats_path(own) and '{candidate}' not in own.out:
             p.error("--params-sweep: --out must contain '{candidate}' and '{seed}' (one clip per candidate and seed)")
     if own.law == 'mlapm':
         if own.checkpoint:
@@ -193,7 +205,7 @@ def main(argv=None):
     if own.seeds is not None:
         return _ensemble(sim, scenario, own, args, run_kw)
     res = sim.simulate_scenario(scenario, own.frames, seed=own.seed, capacity=own.capacity, **run_kw)
-    if own.stats is not None or own.pair_stats is not None:
+    if _stats_path(own):
         _stats(res, own)
     else:
         res.save_data(own.out)
@@ -214,7 +226,7 @@ def _clip_scene(own):
 
 
 def _stats_path(own):
-    return ', '.join(p for p in (own.stats, own.pair_stats) if p is not None)
+    return ', '.join(p for p in (own.stats, own.pair_stats, own.flow_stats) if p is not None)
 
 
 def _crowd_kw(own):
@@ -222,7 +234,8 @@ def _crowd_kw(own):
 
 
 def _stats(res, own):
-    """--stats / --pair-stats: the CrowdStats / PairStats JSON of a run or an ensemble (one call for every member)."""
+    """--stats / --pair-stats / --flow-stats: the CrowdStats / PairStats / FlowStats JSON of a run or an ensemble (one call
+    for every member)."""
     if own.stats is not None:
         from . import crowdstats
         st = res.crowd_stats(**_crowd_kw(own))
@@ -233,6 +246,11 @@ def _stats(res, own):
         ps = res.pair_stats()
         ps.to_json(own.pair_stats)
         pairstats.print_pair_stats(ps, 'simulate --pair-stats')
+    if own.flow_stats is not None:
+        from . import flowstats
+        fs = res.flow_stats(axis=own.flow_axis)
+        fs.to_json(own.flow_stats)
+        flowstats.print_flow_stats(fs, 'simulate --flow-stats')
 
 
 def _sweep(sim, scenario, own, run_kw):
@@ -254,6 +272,12 @@ def _sweep(sim, scenario, own, run_kw):
                    for c, g in enumerate(groups)]
         with open(own.pair_stats, 'w') as fh:
             json.dump({'seeds': own.seeds, 'candidates': entries}, fh)
+    if own.flow_stats is not None:
+        fs = sw.flow_stats(axis=own.flow_axis)
+        entries = [{'params': sw.params[c], 'file': own.params_sweep[c], 'stats': fs.select(g).pooled().to_json()}
+                   for c, g in enumerate(groups)]
+        with open(own.flow_stats, 'w') as fh:
+            json.dump({'seeds': own.seeds, 'candidates': entries}, fh)
     where = _stats_path(own)
     if not where:
         sw.save_data(own.out)
@@ -268,7 +292,7 @@ def _sweep(sim, scenario, own, run_kw):
 
 def _ensemble(sim, scenario, own, args, run_kw):
     ens = sim.simulate_ensemble(scenario, own.frames, own.seeds, capacity=own.capacity, **run_kw)
-    if own.stats is not None or own.pair_stats is not None:
+    if _stats_path(own):
         _stats(ens, own)
         paths = [_stats_path(own)] * len(ens)
     else:
