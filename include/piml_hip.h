@@ -582,6 +582,44 @@ int piml_flow_stats(const float* P, const float* V, const float* M, const int* n
                     long long* map_vy, void* workspace, long long workspace_bytes, void* stream);
 
 /*
+ * Track statistics (trackstats.hip), S members in one call: what an agent does along its own track.  Slot n of
+ * member s is one agent for the whole run; P (S, T, N, 2) and M (S, T, N) float32, n_active (S) int32 or NULL and the frames
+ * [t0, t1) as for piml_pair_stats; velocities are not an input.  Agent i takes part at (s, t) when M == 1 and both
+ * coordinates of P are finite and below 65536 in magnitude; slots at or past n_active[s] are not swept.  float32 (true
+ * divisions and square roots, no contraction), Q = 2^20, t an index into the window (T' = t1 - t0 frames):
+ *   step (i, t): i takes part at t and t + 1; u = p(t+1) - p(t), l = sqrt(ux^2 + uy^2); a mover when l / dt >= v_min, with the
+ *     heading h = u / l.  Nothing requires presence between two frames that are compared.
+ * Outputs, int64:
+ *   ac_n, ac_sum (S, n_lags): lag L = 1 .. n_lags, every t where steps t and t + L are movers: 1 and llrintf((h_t.h_{t+L}) Q);
+ *   msd_n, msd_sum, msd_far (S, n_lags): every t where i takes part at t and t + L, d = p(t+L) - p(t), d2 = dx^2 + dy^2:
+ *     sqrt(d2) < d_max adds 1 to msd_n and llrintf(d2 Q) to msd_sum, otherwise 1 to msd_far;
+ *   acc (S, acc_bins + 1), acc_sum (S): every t where steps t and t + 1 exist, a = sqrt(|u_{t+1} - u_t|^2) / dt / dt: bin
+ *     min(floor(a / acc_bin), acc_bins) (the last bin is open), and llrintf(a Q) where a < acc_bin * acc_bins;
+ *   trk_frames, trk_steps, trk_first, trk_last, trk_path, trk_net (S, N): per track the frames taking part, the steps, the
+ *     first and last participating frame (-1 without one), sum llrintf(l Q) over its steps, and llrintf(|p(last) - p(first)| Q)
+ *     (0 with fewer than two frames).
+ * One workgroup per track; the span [first, last] is staged in LDS tiles of PIML_TRACK_TILE frames with a halo of n_lags,
+ * PIML_TRACK_LAG_LANES lags per pass, one lag per lane.
+ * workspace: at least piml_track_stats_workspace_bytes(S, n_lags, acc_bins) = S (5 n_lags + acc_bins + 2) 8 bytes (-1 for
+ * negative arguments).  One memset and two launches, no host synchronisation (capturable).  Deterministic: integer outputs
+ * only, added with integer atomics; member s's results are bitwise those of an S = 1 call on member s alone.  S, T' or
+ * N == 0: success, nothing is done.
+ * hipErrorInvalidValue, before any HIP call: S, T or N < 0, N > 65536, frames outside [0, T] or t1 < t0, T' > 2^25, dt, v_min, d_max or
+ * acc_bin <= 0 or not finite, d_max > 1024, n_lags outside 1..PIML_TRACK_MAX_LAGS, acc_bins outside 1..256,
+ * d_max^2 Q N T' >= 2^63 or acc_bin acc_bins Q N T' >= 2^63 (the 64-bit sums); then, unless there is nothing to do, a NULL
+ * input, output or workspace, or a workspace too small.
+ */
+#define PIML_TRACK_TILE 1024
+#define PIML_TRACK_LAG_LANES 128
+#define PIML_TRACK_MAX_LAGS 512
+long long piml_track_stats_workspace_bytes(int S, int n_lags, int acc_bins);
+int piml_track_stats(const float* P, const float* M, const int* n_active, int S, int T, int N, int t0, int t1, float dt,
+                     float v_min, int n_lags, float d_max, float acc_bin, int acc_bins, long long* ac_n, long long* ac_sum,
+                     long long* msd_n, long long* msd_sum, long long* msd_far, long long* acc, long long* acc_sum,
+                     long long* trk_frames, long long* trk_steps, long long* trk_first, long long* trk_last,
+                     long long* trk_path, long long* trk_net, void* workspace, long long workspace_bytes, void* stream);
+
+/*
  * utils.calc_acceleration (src/utils/utils.py:31-100): version 0/1/2 = 'v0'/'v1'/'v2' with the
  * caller-supplied constants (A, B, C, D, theta [rad]); rows of >= 2 floats -> acc (rows, 2).
  */

@@ -249,3 +249,58 @@ def flow_stats_frames(P, V, M, v_min=0.1, r_bin=0.1, r_bins=60, r_max=6.0, axis=
                                        + ('map_n', 'map_vx', 'map_vy')), _ptr(ws), ws.numel(), _stream()),
                    'piml_flow_stats')
     return out
+
+
+TRACK_TILE = 1024             # piml_track_stats: frames per staged LDS tile (PIML_TRACK_TILE), lags per pass
+TRACK_LAG_LANES = 128         # (PIML_TRACK_LAG_LANES), and its limits on n_lags, the slots per frame, acc_bins and d_max
+TRACK_MAX_LAGS = 512
+TRACK_MAX_N = 65536
+TRACK_MAX_BINS = 256
+TRACK_MAX_D = 1024.0
+TRACK_MAX_FRAMES = 1 << 25   # frames per window: a track's path sum stays below 2^63
+TRACK_Q = 1 << 20             # the fixed-point scale of ac_sum, msd_sum, acc_sum, trk_path and trk_net
+TRACK_LAG_ROWS = ('ac_n', 'ac_sum', 'msd_n', 'msd_sum', 'msd_far')
+TRACK_ROWS = ('trk_frames', 'trk_steps', 'trk_first', 'trk_last', 'trk_path', 'trk_net')
+
+
+def track_stats_frames(P, M, dt=0.08, v_min=0.1, n_lags=128, d_max=64.0, acc_bin=0.25, acc_bins=40, frames=None,
+                       n_active=None):
+    """The device half of piml_amd.trackstats.track_stats (piml_track_stats): P (S, T, N, 2) and M (S, T, N)
+    float32 GPU tensors, frames (a, b) or None, n_active (S) int32 GPU tensor or None.  Returns a dict of int64 GPU tensors --
+    ac_n, ac_sum, msd_n, msd_sum, msd_far (S, n_lags); acc (S, acc_bins + 1); acc_sum (S); trk_frames, trk_steps, trk_first,
+    trk_last, trk_path, trk_net (S, N) -- with no host synchronisation (capturable in a graph)."""
+    P, M = _gpu_f32('P', P), _gpu_f32('M', M)
+    if P.dim() != 4 or P.shape[-1] != 2 or M.shape != P.shape[:3]:
+        raise ValueError(f'expected P (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(M.shape)}')
+    if M.device != P.device:
+        raise ValueError('P and M on different devices')
+    S, T, N = P.shape[:3]
+    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    NL, AB, Tp = int(n_lags), int(acc_bins), max(b - a, 0)
+    dev = P.device
+    if n_active is not None:
+        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
+                or tuple(n_active.shape) != (S,):
+            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
+        n_active = n_active.contiguous()
+    # a call with nothing to do leaves its outputs alone: hand it the values of empty tracks
+    idle = S * Tp * N == 0
+    new = torch.zeros if idle else torch.empty
+    i64 = dict(device=dev, dtype=torch.int64)
+    out = {k: new(S, max(NL, 0), **i64) for k in TRACK_LAG_ROWS}
+    out['acc'] = new(S, max(AB, 0) + 1, **i64)
+    out['acc_sum'] = new(S, **i64)
+    out.update({k: new(S, N, **i64) for k in TRACK_ROWS})
+    if idle:
+        out['trk_first'] -= 1
+        out['trk_last'] -= 1
+    L = _lib.lib()
+    ws_bytes = L.piml_track_stats_workspace_bytes(S, max(NL, 0), max(AB, 0))
+    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        _lib.check(L.piml_track_stats(_ptr(P), _ptr(M), _ptr(n_active), S, T, N, a, b, float(dt), float(v_min), NL,
+                                      float(d_max), float(acc_bin), AB,
+                                      *(_ptr(out[k]) for k in TRACK_LAG_ROWS + ('acc', 'acc_sum') + TRACK_ROWS), _ptr(ws),
+                                      ws.numel(), _stream()),
+                   'piml_track_stats')
+    return out
