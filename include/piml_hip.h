@@ -620,6 +620,52 @@ int piml_track_stats(const float* P, const float* M, const int* n_active, int S,
                      long long* trk_path, long long* trk_net, void* workspace, long long workspace_bytes, void* stream);
 
 /*
+ * Obstacle statistics (obstaclestats.hip), S members in one call against one shared list of obstacle points:
+ * clearance, contacts, crossings and time to wall.  P, V, M, n_active, the frames [t0, t1) and the box as for
+ * piml_pair_stats; obs (O, 2) float32.  Agent i takes part at (s, t) when M == 1, both coordinates of P are finite and below
+ * 65536 in magnitude and both components of V are finite and below 1024 in magnitude (slots at or past n_active[s] are not
+ * swept); it is focal when it takes part and has_box == 0 or x0 <= x < x1 and y0 <= y < y1.  An obstacle point is valid when
+ * both coordinates are finite; the others are skipped, and with no valid point only focal and steps count.  float32 (true
+ * divisions and square roots, no contraction), Q = 2^20, t an index into the window (T' = t1 - t0 frames).  For a focal
+ * (i, t) and every valid point q, e = q - p(t):
+ *   clearance r = sqrt(min_q |e|^2); a contact when r < radius;
+ *   time to wall: c = |e|^2 - radius^2, b = -(e.v), a = |v|^2; on a collision course when c >= 0, b < 0 and
+ *     disc = b^2 - a c >= 0, then tau = c / (-b + sqrt(disc)); tau_min = min_q tau;
+ *   a step (i, t) exists when i is focal at t, takes part at t + 1 and t + 1 < T': u = p(t+1) - p(t), len2 = |u|^2,
+ *     s = min(max((e.u) / len2, 0), 1) (0 when len2 == 0), m = sqrt(min_q |e - s u|^2); a hit when m < hit_radius (the
+ *     step's segment touches the obstacle, even when neither end is in contact).
+ * The minima are exact in float32 whatever the order of the points.  Outputs, int64:
+ *   focal, steps, contact, hit (S): the focal agent-frames, the steps, the contacts and the hits;
+ *   clear (S, r_bins + 1): every focal agent-frame by min(floor(r / r_bin), r_bins) (the last bin is open); clear_speed (S,
+ *     r_bins + 1): the sum of llrintf(sqrt(|v|^2) Q) over the same items per bin; clear_sum (S): the sum of llrintf(r Q) over
+ *     the items with r < r_bin * r_bins;
+ *   swept (S, r_bins + 1): every step by min(floor(m / r_bin), r_bins);
+ *   min_ttc (S, tau_bins + 1): every focal agent-frame by floor(tau_min / tau_bin) where that is < tau_bins, else (no
+ *     collision course, or beyond the range) bin tau_bins;
+ *   trk_frames, trk_contacts, trk_hits, trk_min (S, N): per track its focal frames, contacts and hits, and
+ *     llrintf(Q min(r, 2^24)) of its smallest r (-1 without a focal frame).
+ * One lane per focal agent-frame; the points are staged in LDS tiles of PIML_OBS_TILE, the skipped ones filtered out while
+ * staging.  dt (seconds per frame) is checked and recorded by the callers; no device quantity depends on it.
+ * workspace: at least piml_obstacle_stats_workspace_bytes(S, N, r_bins, tau_bins) = S (3 r_bins + tau_bins + 9 + 4 N) 8
+ * bytes (-1 for negative arguments).  One memset and two launches, no host synchronisation (capturable).  Deterministic:
+ * integer outputs only, added with integer atomics; member s's results are bitwise those of an S = 1 call on member s
+ * alone.  S, T', N or O == 0: success, nothing is done (the outputs are left alone).
+ * hipErrorInvalidValue, before any HIP call: S, T, N or O < 0, N > 65536, O > 2^24, frames outside [0, T] or t1 < t0, dt,
+ * radius, hit_radius, r_bin or tau_bin <= 0 or not finite, r_bins or tau_bins outside 1..256, a non-finite or empty box,
+ * 1449 Q N T' >= 2^63 (clear_speed: a speed is below sqrt(2) 1024 < 1449) or r_bin r_bins Q N T' >= 2^63 (clear_sum); then,
+ * unless there is nothing to do, a NULL input, output or workspace, or a workspace too small.
+ */
+#define PIML_OBS_TILE 4096
+long long piml_obstacle_stats_workspace_bytes(int S, int N, int r_bins, int tau_bins);
+int piml_obstacle_stats(const float* P, const float* V, const float* M, const int* n_active, int S, int T, int N, int t0,
+                        int t1, const float* obs, int O, float dt, float radius, float hit_radius, int has_box, float x0,
+                        float x1, float y0, float y1, float r_bin, int r_bins, float tau_bin, int tau_bins, long long* focal,
+                        long long* steps, long long* contact, long long* hit, long long* clear_sum, long long* clear,
+                        long long* clear_speed, long long* swept, long long* min_ttc, long long* trk_frames,
+                        long long* trk_contacts, long long* trk_hits, long long* trk_min, void* workspace,
+                        long long workspace_bytes, void* stream);
+
+/*
  * utils.calc_acceleration (src/utils/utils.py:31-100): version 0/1/2 = 'v0'/'v1'/'v2' with the
  * caller-supplied constants (A, B, C, D, theta [rad]); rows of >= 2 floats -> acc (rows, 2).
  */

@@ -304,3 +304,63 @@ def track_stats_frames(P, M, dt=0.08, v_min=0.1, n_lags=128, d_max=64.0, acc_bin
                                       ws.numel(), _stream()),
                    'piml_track_stats')
     return out
+
+
+OBS_TILE = 4096               # piml_obstacle_stats: obstacle points per staged LDS tile (PIML_OBS_TILE), and its limits on the
+OBS_MAX_N = 65536             # slots per frame, the obstacle points and r_bins / tau_bins
+OBS_MAX_O = 1 << 24
+OBS_MAX_BINS = 256
+OBS_Q = 1 << 20               # the fixed-point scale of clear_speed, clear_sum and trk_min
+OBS_COUNTS = ('focal', 'steps', 'contact', 'hit', 'clear_sum')
+OBS_R_ROWS = ('clear', 'clear_speed', 'swept')
+OBS_TRACK_ROWS = ('trk_frames', 'trk_contacts', 'trk_hits', 'trk_min')
+
+
+def obstacle_stats_frames(P, V, M, obstacles, dt=0.08, radius=0.25, hit_radius=0.1, r_bin=0.05, r_bins=100, tau_bin=0.1,
+                          tau_bins=100, box=None, frames=None, n_active=None):
+    """The device half of piml_amd.obstaclestats.obstacle_stats (piml_obstacle_stats): P, V (S, T, N, 2), M
+    (S, T, N) and obstacles (O, 2) float32 GPU tensors, box (x0, x1, y0, y1) or None, frames (a, b) or None, n_active (S)
+    int32 GPU tensor or None.  Returns a dict of int64 GPU tensors -- focal, steps, contact, hit, clear_sum (S); clear,
+    clear_speed, swept (S, r_bins + 1); min_ttc (S, tau_bins + 1); trk_frames, trk_contacts, trk_hits, trk_min (S, N) -- with
+    no host synchronisation (capturable in a graph)."""
+    P, V, M, obstacles = _gpu_f32('P', P), _gpu_f32('V', V), _gpu_f32('M', M), _gpu_f32('obstacles', obstacles)
+    if P.dim() != 4 or P.shape[-1] != 2 or V.shape != P.shape or M.shape != P.shape[:3]:
+        raise ValueError(f'expected P, V (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(V.shape)}, '
+                         f'{tuple(M.shape)}')
+    if obstacles.dim() != 2 or obstacles.shape[-1] != 2:
+        raise ValueError(f'obstacles: expected (O, 2), got {tuple(obstacles.shape)}')
+    dev = P.device
+    if any(x.device != dev for x in (V, M, obstacles)):
+        raise ValueError('P, V, M and obstacles on different devices')
+    S, T, N = P.shape[:3]
+    O = obstacles.shape[0]
+    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    RB, TB, Tp = int(r_bins), int(tau_bins), max(b - a, 0)
+    if n_active is not None:
+        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
+                or tuple(n_active.shape) != (S,):
+            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
+        n_active = n_active.contiguous()
+    x0, x1, y0, y1 = (0.0, 0.0, 0.0, 0.0) if box is None else (float(v) for v in box)
+    # a call with nothing to do leaves its outputs alone: hand it the values of an empty problem
+    idle = S * Tp * N * O == 0
+    new = torch.zeros if idle else torch.empty
+    i64 = dict(device=dev, dtype=torch.int64)
+    out = {k: new(S, **i64) for k in OBS_COUNTS}
+    out.update({k: new(S, max(RB, 0) + 1, **i64) for k in OBS_R_ROWS})
+    out['min_ttc'] = new(S, max(TB, 0) + 1, **i64)
+    out.update({k: new(S, N, **i64) for k in OBS_TRACK_ROWS})
+    if idle:
+        out['trk_min'] -= 1
+    L = _lib.lib()
+    ws_bytes = L.piml_obstacle_stats_workspace_bytes(S, N, max(RB, 0), max(TB, 0))
+    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        _lib.check(L.piml_obstacle_stats(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), S, T, N, a, b, _ptr(obstacles), O,
+                                         float(dt), float(radius), float(hit_radius), int(box is not None), x0, x1, y0, y1,
+                                         float(r_bin), RB, float(tau_bin), TB,
+                                         *(_ptr(out[k]) for k in OBS_COUNTS[:4]), _ptr(out['clear_sum']),
+                                         *(_ptr(out[k]) for k in OBS_R_ROWS), _ptr(out['min_ttc']),
+                                         *(_ptr(out[k]) for k in OBS_TRACK_ROWS), _ptr(ws), ws.numel(), _stream()),
+                   'piml_obstacle_stats')
+    return out

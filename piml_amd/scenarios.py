@@ -328,6 +328,14 @@ def default_capacity(scenario, frames, tail=1e-9):
     return max(1, scenario.n_initial + min(q, cap * steps))
 
 
+def _scene_obstacles(res):
+    """the obstacles of a result or ensemble; ValueError when its scene has none"""
+    obs = res.obstacles
+    if obs is None or obs.numel() == 0:
+        raise ValueError('obstacle_stats: the scene has no obstacles')
+    return obs
+
+
 class ScenarioResult(types.SimpleNamespace):
     """What `BaseSimulator.simulate_scenario` returns.  position / velocity / acceleration / destination (T, cap, 2),
     mask_p (T, cap), waypoints (D, cap, 2), desired_speed (cap), obstacles (M, 2), time_unit, spawned (agents generated,
@@ -380,6 +388,14 @@ class ScenarioResult(types.SimpleNamespace):
         from .trackstats import track_stats
         kw.setdefault('dt', float(self.time_unit))
         return track_stats(self.position, self.mask_p, n_active=[self.num_agents], **kw)
+
+    def obstacle_stats(self, **kw):
+        """piml_amd.obstaclestats.obstacle_stats of the run against the scene's obstacles (simulated velocities, dt =
+        time_unit; slots past num_agents not swept).  ValueError for a scene without obstacles."""
+        from .obstaclestats import obstacle_stats
+        kw.setdefault('dt', float(self.time_unit))
+        return obstacle_stats(self.position, self.velocity, self.mask_p, _scene_obstacles(self), n_active=[self.num_agents],
+                              **kw)
 
 
 class ScenarioEnsemble(types.SimpleNamespace):
@@ -436,6 +452,16 @@ class ScenarioEnsemble(types.SimpleNamespace):
         kw.setdefault('dt', float(self.time_unit))
         return track_stats(self.position, self.mask_p, n_active=[min(int(n), cap) for n in self.spawned], **kw)
 
+    def obstacle_stats(self, **kw):
+        """piml_amd.obstaclestats.obstacle_stats of every member in one call against the scene's obstacles (dt = time_unit;
+        member m's slots past its num_agents not swept): member m's statistics are bitwise those of
+        member(m).obstacle_stats(**kw).  ValueError for a scene without obstacles."""
+        from .obstaclestats import obstacle_stats
+        cap = self.position.shape[2]
+        kw.setdefault('dt', float(self.time_unit))
+        return obstacle_stats(self.position, self.velocity, self.mask_p, _scene_obstacles(self),
+                              n_active=[min(int(n), cap) for n in self.spawned], **kw)
+
     def collision_counts(self, threshold):
         """Per-member totals of collision_count(member.position, threshold, reduction='sum'): a list of S floats, one
         read-back.  One ops.collision_counts call per member: on a stack of more than 25 frames the count applies the
@@ -449,7 +475,7 @@ class ScenarioSweep(ScenarioEnsemble):
     """What `MLAPM.simulate_sweep` returns: a ScenarioEnsemble of n_candidates * seeds_per_candidate members laid out
     candidate-major -- member c * seeds_per_candidate + k ran law params[c] under the k-th seed -- plus params (the
     candidates' dicts), n_candidates and seeds_per_candidate.  `seeds` lists every member's seed (the seed list once per
-    candidate); crowd_stats / pair_stats / flow_stats / track_stats compute all members in one call, and `.select(sweep.members_of(c)).pooled()` of
+    candidate); crowd_stats / pair_stats / flow_stats / track_stats / obstacle_stats compute all members in one call, and `.select(sweep.members_of(c)).pooled()` of
     the result pools one candidate."""
 
     def members_of(self, c):

@@ -12,6 +12,7 @@ reads.
     python -m piml_amd.simulate --scenario crosswalk --seeds 0:32 --flow-stats flow.json [--flow-axis x|y|auto|deg]
     python -m piml_amd.simulate --law mlapm --scenario crosswalk --seeds 0:32 --track-stats tracks.json   (track statistics)
                                 (velocity correlation and lane order, no clips written)
+    python -m piml_amd.simulate --law mlapm --scenario gc --seeds 0:32 --obstacle-stats walls.json   (obstacle statistics)
     python -m piml_amd.simulate --law mlapm --params-sweep a.json b.json --seeds 0:8 --stats sweep.json
                                 (one law per file, every law on every seed in ONE ensemble run; statistics per candidate)
 
@@ -40,7 +41,7 @@ def get_args(argv=None):
                         "main_mlapm.py's constants, version GC")
     p.add_argument('--params-sweep', dest='params_sweep', type=str, nargs='+', default=None,
                    help='--law mlapm with --seeds: several --params files, every law on every seed in one ensemble run '
-                        "(MLAPM.simulate_sweep); --stats / --pair-stats / --flow-stats / --track-stats then hold one entry per candidate, pooled over its "
+                        "(MLAPM.simulate_sweep); --stats / --pair-stats / --flow-stats / --track-stats / --obstacle-stats then hold one entry per candidate, pooled over its "
                         "seeds, and --out must contain '{candidate}' and '{seed}'")
     p.add_argument('--mlapm_radius', type=float, default=0.3,
                    help="--law mlapm: MLAPM's UCY collision radius (not the scene's arrival radius)")
@@ -78,6 +79,10 @@ def get_args(argv=None):
                    help='write the track statistics (piml_amd.trackstats: heading persistence, MSD, acceleration, path '
                         'shape; defaults, dt = the time unit) of the run or ensemble as JSON to this path instead of writing '
                         'clips')
+    p.add_argument('--obstacle-stats', dest='obstacle_stats', type=str, default=None,
+                   help='write the obstacle statistics (piml_amd.obstaclestats: wall clearance, contacts, crossings, time '
+                        "to wall; defaults, no box, the scene's obstacles) of the run or ensemble as JSON to this path "
+                        'instead of writing clips')
     p.add_argument('--time_unit', type=float, default=0.08)
     p.add_argument('--uniform_desired_speed', action=argparse.BooleanOptionalAction, default=None,
                    help="uniform desired speed (default: the scene's own; GC and the crosswalk no, the others yes)")
@@ -231,7 +236,8 @@ def _clip_scene(own):
 
 
 def _stats_path(own):
-    return ', '.join(p for p in (own.stats, own.pair_stats, own.flow_stats, own.track_stats) if p is not None)
+    return ', '.join(p for p in (own.stats, own.pair_stats, own.flow_stats, own.track_stats, own.obstacle_stats)
+                     if p is not None)
 
 
 def _crowd_kw(own):
@@ -239,8 +245,8 @@ def _crowd_kw(own):
 
 
 def _stats(res, own):
-    """--stats / --pair-stats / --flow-stats / --track-stats: the CrowdStats / PairStats / FlowStats / TrackStats JSON of a
-    run or an ensemble (one call for every member)."""
+    """--stats / --pair-stats / --flow-stats / --track-stats / --obstacle-stats: the CrowdStats / PairStats / FlowStats /
+    TrackStats / ObstacleStats JSON of a run or an ensemble (one call for every member)."""
     if own.stats is not None:
         from . import crowdstats
         st = res.crowd_stats(**_crowd_kw(own))
@@ -261,6 +267,14 @@ def _stats(res, own):
         ts = res.track_stats()
         ts.to_json(own.track_stats)
         trackstats.print_track_stats(ts, 'simulate --track-stats')
+    if own.obstacle_stats is not None:
+        from . import obstaclestats
+        try:
+            os_ = res.obstacle_stats()
+        except ValueError as ex:
+            sys.exit(f'--obstacle-stats: {ex}')
+        os_.to_json(own.obstacle_stats)
+        obstaclestats.print_obstacle_stats(os_, 'simulate --obstacle-stats')
 
 
 def _sweep(sim, scenario, own, run_kw):
@@ -293,6 +307,15 @@ def _sweep(sim, scenario, own, run_kw):
         entries = [{'params': sw.params[c], 'file': own.params_sweep[c], 'stats': ts.select(g).pooled().to_json()}
                    for c, g in enumerate(groups)]
         with open(own.track_stats, 'w') as fh:
+            json.dump({'seeds': own.seeds, 'candidates': entries}, fh)
+    if own.obstacle_stats is not None:
+        try:
+            os_ = sw.obstacle_stats()
+        except ValueError as ex:
+            sys.exit(f'--obstacle-stats: {ex}')
+        entries = [{'params': sw.params[c], 'file': own.params_sweep[c], 'stats': os_.select(g).pooled().to_json()}
+                   for c, g in enumerate(groups)]
+        with open(own.obstacle_stats, 'w') as fh:
             json.dump({'seeds': own.seeds, 'candidates': entries}, fh)
     where = _stats_path(own)
     if not where:
