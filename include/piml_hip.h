@@ -851,7 +851,8 @@ int piml_scenario_step_members(const piml_scenario* s, const piml_scenario_rules
  *   self_features update, arrival, retirement and record of piml_scenario_step (GC) or piml_scenario_step_rules.
  * Spawns, waypoints, exit_idx, desired_speed, spawned, dropped and spawn_out are bitwise those of a piml_scenario_step_members
  * run of the same seeds (they depend on (seed, frame, ordinal) only).  law->radius is MLAPM's UCY collision radius
- * (mlapm.py:42-46), not the scene's arrival_radius.  MLAPM has no obstacle or wall term (the reference's neither).
+ * (mlapm.py:42-46), not the scene's arrival_radius.  This entry has no obstacle or wall term (the reference's law has
+ * none); piml_scenario_step_mlapm_walls below adds one.
  * No atomics; capturable.
  * hipErrorInvalidValue (before any launch): every check of piml_scenario_step_members except a_next / init; frame_offset < 0;
  * NULL law; variant not 0 / 1 / 2; tau not finite and > 0; A, B, C, D or theta_deg not finite; radius not finite and > 0.
@@ -889,6 +890,61 @@ long long piml_mlapm_law_table_bytes(int n);
 int piml_mlapm_law_table_fill(const piml_mlapm_law* laws, int n, void* table_host);
 int piml_scenario_step_mlapm_laws(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
                                   const void* table_device, int frame_offset, void* stream);
+
+/*
+ * A wall term for the MLAPM scenario frame (ABI 35, additive): the repulsion of the scene's nearest obstacle point.
+ * p is the agent position; the VALID obstacle points are those with both coordinates finite; q* is the valid point nearest
+ * p under d2 = fadd(fmul(e.x, e.x), fmul(e.y, e.y)), e = q - p, in exact float32, ties to the point that comes first in the
+ * grid's sorted order.  The agent feels the wall when d2 < c2, c2 = fl(cutoff cutoff) formed once on the host:
+ *   W = A exp(B d) (p - q*) / d,  d = sqrt(d2);  W = 0 when d2 == 0 (F.normalize's convention, as the pair law's).
+ * Otherwise (no valid point within the cutoff, a NaN position) W = 0, index -1 and dist2 +inf.  The term is isotropic: it has
+ * no view factor, so a resting agent still feels the wall.  Its value jumps by A exp(B cutoff) at the cutoff; this is
+ * documented, not smoothed.  A = 50, B = -5 is Helbing and Molnar's 1995 boundary potential (U0 = 10 m^2/s^2, R = 0.2 m), the
+ * literature's starting point for a fit -- not a default: the entries below are the only ones with a wall term.
+ * The value uses the fast reciprocal-sqrt / exp2 units (1e-5 relative, as the pair law); the selection (index, dist2, the
+ * cutoff predicate) is exact float32.
+ *
+ * piml_wall_grid: a static uniform cell grid over the valid points, built once per scene by the host
+ * (piml_amd.ops_scenario.wall_grid).  cell >= cutoff (1 + 2^-5) is the cell side, (x0, y0) the points' minimum, a point's
+ * cell (floor((q.x - x0) / cell), floor((q.y - y0) / cell)) in float32, `points` the valid points sorted stably by
+ * cy gx + cx, cell_start the CSR offsets of the gx gy cells into them.  The kernel finds the agent's cell by the same
+ * formula, clamps it to [-1, gx] x [-1, gy] and searches its 3 x 3 neighbourhood, one wave per agent; with gx, gy <= 1024
+ * the float32 cell quotients are off by less than 2^-7 cells and the margin 2^-5 makes that search exact.  Every range
+ * read from cell_start is clamped to [0, n_points]: a corrupt table gives a wrong force, never a read outside `points`.
+ *
+ * piml_wall_force: position (rows, 2) -> force (rows, 2) and optionally the selection dist2 (rows), index (rows; into
+ * `points`, -1 for none), one wave per row.  rows == 0 or n_points == 0: success without a launch (with n_points == 0 the
+ * outputs are the caller's to fill: force 0, dist2 +inf, index -1).
+ * hipErrorInvalidValue (before any HIP call): rows < 0; NULL g or force; NULL position with rows > 0 and n_points > 0;
+ * n_points < 0; NULL points / cell_start with n_points > 0; gx or gy outside 1..1024; cell or cutoff not finite and > 0;
+ * cell < cutoff (1 + 2^-5); x0 or y0 not finite; A or B not finite; A < 0; B > 0.
+ *
+ * piml_scenario_step_mlapm_walls: piml_scenario_step_mlapm (law != NULL, table_device == NULL) or
+ * piml_scenario_step_mlapm_laws (law == NULL, table_device != NULL) with the frame's force
+ *   F = ((v0 e - v) / tau - sum over pairs) + W,  componentwise, the wall added last,
+ * W evaluated at the agent's position of frame t by the code of piml_wall_force.  Integration, history, arrival, retirement,
+ * spawns and records are exactly piml_scenario_step_mlapm's.  The wall law is `wall` by value, or member m's row of
+ * wall_table_device ((members) piml_wall_law in device memory, read on every launch: overwriting it between two replays of
+ * a captured graph changes the later frames, with no re-capture).
+ * hipErrorInvalidValue (before any launch): every check of piml_scenario_step_mlapm / piml_scenario_step_mlapm_laws for the
+ * form used; law and table_device both NULL or both given; wall and wall_table_device both NULL or both given; the grid
+ * checks of piml_wall_force; the A / B checks on a by-value wall.  The entry CANNOT validate a wall table's contents, which
+ * live in device memory (A >= 0, B <= 0, finite, are the caller's to keep; other values are undefined behaviour of the
+ * force, not of memory: a row indexes nothing).  No atomics, no scratch, no host synchronisation; capturable.
+ */
+typedef struct piml_wall_grid {
+    const float* points;                                    /* (n_points, 2) device; the valid points in sorted order */
+    const int* cell_start;                                  /* (gx*gy + 1) device */
+    int n_points, gx, gy;
+    float x0, y0, cell, cutoff;
+} piml_wall_grid;
+typedef struct piml_wall_law { float A, B; } piml_wall_law;
+int piml_wall_force(const float* position, long long rows, const piml_wall_grid* g, float A, float B,
+                    float* force, float* dist2, int* index, void* stream);
+int piml_scenario_step_mlapm_walls(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                                   const piml_mlapm_law* law, const void* table_device, const piml_wall_grid* g,
+                                   const piml_wall_law* wall, const piml_wall_law* wall_table_device, int frame_offset,
+                                   void* stream);
 
 /*
  * utils.route (src/utils/utils.py:141-165) for n (o, d) pairs, one wave each, the device function the spawn path uses:

@@ -84,6 +84,17 @@ class MlapmLaw(ctypes.Structure):
     _fields_ = [('variant', _i), ('tau', _f), ('A', _f), ('B', _f), ('C', _f), ('D', _f), ('theta_deg', _f), ('radius', _f)]
 
 
+class WallGrid(ctypes.Structure):
+    """piml_wall_grid (include/piml_hip.h)."""
+    _fields_ = [('points', _p), ('cell_start', _p), ('n_points', _i), ('gx', _i), ('gy', _i),
+                ('x0', _f), ('y0', _f), ('cell', _f), ('cutoff', _f)]
+
+
+class WallLaw(ctypes.Structure):
+    """piml_wall_law (include/piml_hip.h)."""
+    _fields_ = [('A', _f), ('B', _f)]
+
+
 SPAWN_LAWS = {'gc': 0, 'crosswalk': 1, 'square': 2, 'unit1': 3, 'unit2': 4, 'unit3': 5, 'clip': 6}     # PIML_SPAWN_*
 ARRIVAL_RULES = {'gc': 0, 'radius': 1, 'x_band': 2, 'x_exit': 3}                             # PIML_ARRIVE_*
 
@@ -145,6 +156,8 @@ SIGNATURES = {
     'piml_mlapm_law_table_bytes': [_i],
     'piml_mlapm_law_table_fill': [_p, _i, _p],
     'piml_scenario_step_mlapm_laws': [_p, _p, _i, _p, _p, _i, _p],
+    'piml_wall_force': [_p, _ll, _p, _f, _f, _p, _p, _p, _p],
+    'piml_scenario_step_mlapm_walls': [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _p],
     'piml_scenario_route': [_p, _p, _i, _p, _i, _i, _f, _p, _p, _p],
     'piml_collision_correction_fwd': [_p, _p, _p, _z, _i, _i, _f, _f, _p, _p],
     'piml_collision_correction_bwd': [_p, _p, _p, _p, _z, _i, _i, _f, _f, _p, _p, _p, _p],

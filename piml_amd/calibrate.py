@@ -32,6 +32,8 @@ os.environ.setdefault('DEBUG_CLR_GRAPH_PACKET_CAPTURE', '0')      # before torch
 import torch  # noqa: E402
 
 PARAM_NAMES = ('tau', 'A', 'B', 'C', 'D', 'theta')
+# the wall term of the scene runs (MLAPM(..., Aw=, Bw=)): fitted by calibrate_mlapm_to_stats only, and never by default
+WALL_PARAM_NAMES = ('Aw', 'Bw')
 # the constants src/main_mlapm.py:16 types in
 DEFAULT_INIT = {'tau': 0.5, 'A': 7.55, 'B': -3.0, 'C': 0.2, 'D': -0.3, 'theta': 56.0}
 SMALL_FRAME = 64          # frames up to this many agents: a lane per focal agent; above: a wave per focal agent
@@ -405,20 +407,24 @@ def calibrate_mlapm(data, version='GC', init=None, fit=PARAM_NAMES, steps=500, l
 
 
 OBJECTIVE_KEYS = {'crowd': ('fd_distance', 'map_distance', 'mean_speed_diff'),
-                  'pairs': ('ttc_l1', 'nn_l1', 'overlap_rate_diff')}
-DEFAULT_BOUNDS = {'tau': (1e-3, None)}
+                  'pairs': ('ttc_l1', 'nn_l1', 'overlap_rate_diff'),
+                  'obstacles': ('hit_track_fraction_diff', 'contact_rate_diff', 'clearance_l1')}
+DEFAULT_BOUNDS = {'tau': (1e-3, None), 'Aw': (0.0, None), 'Bw': (None, 0.0)}
 
 
-def stats_objective(crowd=None, pairs=None, ref_crowd=None, ref_pairs=None, weights=None, min_count=50):
+def stats_objective(crowd=None, pairs=None, ref_crowd=None, ref_pairs=None, weights=None, min_count=50, obstacles=None,
+                    ref_obstacles=None):
     """(J, terms): how far simulated statistics are from a reference's.  crowd / ref_crowd: CrowdStats, pairs / ref_pairs:
-    PairStats; a side takes part when both of its statistics are given.  terms is the union of compare_crowd_stats(crowd,
-    ref_crowd, min_count) and compare_pair_stats(pairs, ref_pairs, min_count) for the sides given, and
-    J = sum_k w_k |terms[k]| over fd_distance, map_distance, mean_speed_diff (crowd) and ttc_l1, nn_l1, overlap_rate_diff
-    (pairs), every weight 1.0 unless `weights` names it.  map_distance is left out when it is None (no common map); a NaN
+    PairStats, obstacles / ref_obstacles: ObstacleStats; a side takes part when both of its statistics are given.  terms is
+    the union of compare_crowd_stats(crowd, ref_crowd, min_count), compare_pair_stats(pairs, ref_pairs, min_count) and
+    compare_obstacle_stats(obstacles, ref_obstacles, min_count) for the sides given, and
+    J = sum_k w_k |terms[k]| over fd_distance, map_distance, mean_speed_diff (crowd), ttc_l1, nn_l1, overlap_rate_diff
+    (pairs) and hit_track_fraction_diff, contact_rate_diff, clearance_l1 (obstacles), every weight 1.0 unless `weights`
+    names it.  map_distance is left out when it is None (no common map); a NaN
     term of non-zero weight makes J = inf.  ValueError: no side given, or a weight for an unknown key."""
     from .crowdstats import compare_crowd_stats
     from .pairstats import compare_pair_stats
-    known = OBJECTIVE_KEYS['crowd'] + OBJECTIVE_KEYS['pairs']
+    known = OBJECTIVE_KEYS['crowd'] + OBJECTIVE_KEYS['pairs'] + OBJECTIVE_KEYS['obstacles']
     unknown = sorted(set(weights or {}) - set(known))
     if unknown:
         raise ValueError(f'stats_objective: weights for unknown terms {unknown} (of {known})')
@@ -429,8 +435,12 @@ def stats_objective(crowd=None, pairs=None, ref_crowd=None, ref_pairs=None, weig
     if pairs is not None and ref_pairs is not None:
         terms.update(compare_pair_stats(pairs, ref_pairs, min_count))
         keys += OBJECTIVE_KEYS['pairs']
+    if obstacles is not None and ref_obstacles is not None:
+        from .obstaclestats import compare_obstacle_stats
+        terms.update(compare_obstacle_stats(obstacles, ref_obstacles, min_count))
+        keys += OBJECTIVE_KEYS['obstacles']
     if not keys:
-        raise ValueError('stats_objective: neither crowd nor pair statistics with a reference')
+        raise ValueError('stats_objective: neither crowd, pair nor obstacle statistics with a reference')
     J = 0.0
     for k in keys:
         w = float((weights or {}).get(k, 1.0))
@@ -450,11 +460,18 @@ class _StatsEvaluator:
     """calibrate_mlapm_to_stats' objective on the GPU: list of candidate dicts -> list of J, one SweepRun generation each."""
 
     def __init__(self, scenario, reference, frames, seeds, population, radius, capacity, crowd_kw, pair_kw, weights,
-                 min_count, device):
+                 min_count, device, obstacle_kw=None, wall_cutoff=None):
         from . import crowdstats, pairstats
-        from .models.mlapm import SweepRun
+        from .models.mlapm import DEFAULT_WALL_CUTOFF, SweepRun
+        self.ref_obstacles = None
         if isinstance(reference, (tuple, list)):
-            self.ref_crowd, self.ref_pairs = reference
+            if len(reference) == 3:                  # (crowd, pairs, obstacles): the obstacle side takes part
+                self.ref_crowd, self.ref_pairs, self.ref_obstacles = reference
+            else:
+                self.ref_crowd, self.ref_pairs = reference
+            if obstacle_kw is None and self.ref_obstacles is not None:
+                obstacle_kw = _options_of(self.ref_obstacles, ('dt', 'radius', 'hit_radius', 'r_bin', 'r_bins', 'tau_bin',
+                                                               'tau_bins', 'box'))
             if crowd_kw is None and self.ref_crowd is not None:
                 crowd_kw = crowdstats.call_options(self.ref_crowd)
             if pair_kw is None and self.ref_pairs is not None:
@@ -470,13 +487,14 @@ class _StatsEvaluator:
             self.ref_pairs = pairstats.pair_stats_of_raw(reference, **dict(pair_kw or {}))
             if frames is None:
                 frames = int(torch.as_tensor(reference.position).shape[0])
-        if self.ref_crowd is None and self.ref_pairs is None:
+        if self.ref_crowd is None and self.ref_pairs is None and self.ref_obstacles is None:
             raise ValueError('calibrate_mlapm_to_stats: the reference holds no statistics')
-        self.crowd_kw, self.pair_kw = dict(crowd_kw or {}), dict(pair_kw or {})
+        self.crowd_kw, self.pair_kw, self.obstacle_kw = dict(crowd_kw or {}), dict(pair_kw or {}), dict(obstacle_kw or {})
         self.weights, self.min_count, self.radius = weights, min_count, radius
         self.frames = 200 if frames is None else int(frames)
-        self.run = SweepRun(scenario, self.frames, population, seeds, capacity=capacity, device=device)
-        self.seconds = {'run': 0.0, 'crowd': 0.0, 'pairs': 0.0, 'host': 0.0}
+        self.run = SweepRun(scenario, self.frames, population, seeds, capacity=capacity, device=device,
+                            wall_cutoff=DEFAULT_WALL_CUTOFF if wall_cutoff is None else wall_cutoff)
+        self.seconds = {'run': 0.0, 'crowd': 0.0, 'pairs': 0.0, 'obstacles': 0.0, 'host': 0.0}
         self.last_terms = []
 
     def __call__(self, cands):
@@ -502,6 +520,12 @@ class _StatsEvaluator:
             from .pairstats import pair_stats
             pairs = pair_stats(sw.position, sw.velocity, mask, n_active=n_active, **self.pair_kw)
         t3 = time.perf_counter()
+        obstacles = None
+        if self.ref_obstacles is not None:           # the scene's own obstacle statistics, one call for all members
+            from .obstaclestats import obstacle_stats
+            kw = {'dt': float(sw.time_unit), **self.obstacle_kw}
+            obstacles = obstacle_stats(sw.position, sw.velocity, mask, sw.obstacles, n_active=n_active, **kw)
+        t3b = time.perf_counter()
         out, self.last_terms = [], []
         for c in range(sw.n_candidates):
             group = sw.members_of(c)
@@ -511,11 +535,12 @@ class _StatsEvaluator:
                 continue
             J, terms = stats_objective(None if crowd is None else crowd.select(group).pooled(),
                                        None if pairs is None else pairs.select(group).pooled(),
-                                       self.ref_crowd, self.ref_pairs, self.weights, self.min_count)
+                                       self.ref_crowd, self.ref_pairs, self.weights, self.min_count,
+                                       None if obstacles is None else obstacles.select(group).pooled(), self.ref_obstacles)
             out.append(J)
             self.last_terms.append(terms)
         t4 = time.perf_counter()
-        for k, dt in zip(('run', 'crowd', 'pairs', 'host'), (t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
+        for k, dt in zip(('run', 'crowd', 'pairs', 'obstacles', 'host'), (t1 - t0, t2 - t1, t3 - t2, t3b - t3, t4 - t3b)):
             self.seconds[k] += dt
         return out
 
@@ -523,8 +548,16 @@ class _StatsEvaluator:
 def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=PARAM_NAMES, frames=None, seeds=range(8),
                              population=16, generations=30, elite=0.25, sigma=0.2, sigma_floor=1e-3, bounds=None,
                              weights=None, crowd_kw=None, pair_kw=None, search_seed=0, radius=0.3, capacity=None,
-                             evaluate=None, min_count=50, device='cuda'):
+                             evaluate=None, min_count=50, device='cuda', obstacle_kw=None, wall_cutoff=None):
     """Fit MLAPM's constants so that the law, run open-world in `scenario`, reproduces the reference's crowd statistics.
+
+    The wall term: fit may also name Aw, Bw (WALL_PARAM_NAMES), and init may carry Aw, Bw: the candidates then run the
+    frames with the wall term (MLAPM(..., Aw=, Bw=, wall_cutoff=wall_cutoff), default cutoff 2.0 m; the cutoff is the
+    grid's and is not fitted).  init must hold both when either is fitted -- the term has no default; Aw = 50, Bw = -5
+    (Helbing and Molnar 1995) is the literature's starting point -- and Aw >= 0, Bw <= 0 are bounded so by default.  A
+    reference triple (CrowdStats | None, PairStats | None, ObstacleStats | None) adds the obstacle side: the candidates'
+    obstacle_stats against the scene's own obstacles (obstacle_kw, default the reference's options; one call for every
+    member) enter stats_objective with the reference's.  The result's params then carry Aw, Bw and wall_cutoff.
 
     reference: a RawData (its crowd_stats / pair_stats are taken with crowd_kw / pair_kw, the crowd box defaulting to
     crowdstats.auto_box of the recording, and the simulated side uses the same options, so the maps are comparable) or a
@@ -554,25 +587,34 @@ def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=P
     if version not in ops.MLAPM_VARIANTS:
         raise NotImplementedError(version)
     fit = tuple(fit)
-    unknown = [k for k in fit if k not in PARAM_NAMES]
+    unknown = [k for k in fit if k not in PARAM_NAMES + WALL_PARAM_NAMES]
     if unknown or not fit:
-        raise ValueError(f'constants to fit: names of {PARAM_NAMES} expected, got {fit}')
+        raise ValueError(f'constants to fit: names of {PARAM_NAMES + WALL_PARAM_NAMES} expected, got {fit}')
+    walls = any(k in (init or {}) for k in WALL_PARAM_NAMES)
+    if (walls or any(k in WALL_PARAM_NAMES for k in fit)) and not all(k in (init or {}) for k in WALL_PARAM_NAMES):
+        raise ValueError(f'the wall term has no default: init must hold both of {WALL_PARAM_NAMES} (fit {fit}, init '
+                         f'{sorted(init or {})})')
+    names = PARAM_NAMES + (WALL_PARAM_NAMES if walls else ())
     population, generations = int(population), int(generations)
     if population < 2 or generations < 1:
         raise ValueError(f'population >= 2 and generations >= 1 expected, got {population}, {generations}')
     if not 0 < float(elite) <= 1 or not float(sigma) > 0 or not float(sigma_floor) >= 0:
         raise ValueError(f'elite in (0, 1], sigma > 0, sigma_floor >= 0 expected, got {elite}, {sigma}, {sigma_floor}')
-    bad = sorted(set(bounds or {}) - set(PARAM_NAMES))
+    bad = sorted(set(bounds or {}) - set(PARAM_NAMES + WALL_PARAM_NAMES))
     if bad:
         raise ValueError(f'bounds for unknown constants {bad}')
     limits = {**DEFAULT_BOUNDS, **(bounds or {})}
     start = {**DEFAULT_INIT, **(init or {})}
-    start = {k: float(start[k]) for k in PARAM_NAMES}
+    start = {k: float(start[k]) for k in names}
+    if walls:
+        from .models.mlapm import DEFAULT_WALL_CUTOFF, wall_args
+        wall_cutoff = DEFAULT_WALL_CUTOFF if wall_cutoff is None else float(wall_cutoff)
+        wall_args({'Aw': start['Aw'], 'Bw': start['Bw'], 'wall_cutoff': wall_cutoff})
     seeds = [int(x) for x in seeds]
     terms_of = None
     if evaluate is None:
         evaluate = terms_of = _StatsEvaluator(scenario, reference, frames, seeds, population, radius, capacity, crowd_kw,
-                                              pair_kw, weights, min_count, device)
+                                              pair_kw, weights, min_count, device, obstacle_kw, wall_cutoff)
     scale = np.array([abs(start[k]) if start[k] != 0 else 1.0 for k in fit])
     lo = np.array([-np.inf if limits.get(k, (None, None))[0] is None else limits[k][0] for k in fit], np.float64)
     hi = np.array([np.inf if limits.get(k, (None, None))[1] is None else limits[k][1] for k in fit], np.float64)
@@ -610,6 +652,8 @@ def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=P
         import warnings
         warnings.warn(f'calibrate_mlapm_to_stats: {status}')
     res = {'version': version, **best}
+    if walls:
+        res['wall_cutoff'] = wall_cutoff
     out = CalibrationResult(params=res, initial_loss=initial, final_loss=best_J, history=history, fit=fit,
                             terms=best_terms, generations=generations, population=population, seeds=seeds, status=status,
                             steps=generations, horizon=None)
@@ -622,17 +666,18 @@ def _parse_init(text):
     out = {}
     for item in filter(None, (s.strip() for s in (text or '').split(','))):
         k, _, val = item.partition('=')
-        if k not in PARAM_NAMES or not _:
-            raise argparse.ArgumentTypeError(f'--init expects name=value with names in {PARAM_NAMES}, got {item!r}')
+        if k not in PARAM_NAMES + WALL_PARAM_NAMES or not _:
+            raise argparse.ArgumentTypeError(f'--init expects name=value with names in {PARAM_NAMES + WALL_PARAM_NAMES}, '
+                                             f'got {item!r}')
         out[k] = float(val)
     return out
 
 
 def _parse_fit(text):
     names = tuple(filter(None, (s.strip() for s in text.split(','))))
-    bad = [k for k in names if k not in PARAM_NAMES]
+    bad = [k for k in names if k not in PARAM_NAMES + WALL_PARAM_NAMES]
     if bad or not names:
-        raise argparse.ArgumentTypeError(f'--fit expects names from {PARAM_NAMES}, got {text!r}')
+        raise argparse.ArgumentTypeError(f'--fit expects names from {PARAM_NAMES + WALL_PARAM_NAMES}, got {text!r}')
     return names
 
 
@@ -658,7 +703,11 @@ def get_args(argv=None):
     p.add_argument('--match-stats', dest='match_stats', action='store_true',
                    help="fit the law to the clip's crowd statistics, run open-world in the clip's own scene "
                         '(calibrate_mlapm_to_stats), instead of to its trajectories')
-    p.add_argument('--match', type=str, default='crowd,pairs', help='--match-stats: the statistics to match (crowd, pairs)')
+    p.add_argument('--match', type=str, default=None,
+                   help='--match-stats: the statistics to match (crowd, pairs, obstacles); default crowd,pairs, and obstacles '
+                        'too when the law has a wall term (--init Aw=..,Bw=..)')
+    p.add_argument('--wall-cutoff', dest='wall_cutoff', type=float, default=None,
+                   help='--match-stats with a wall term: its cutoff in metres (default 2.0); not fitted')
     p.add_argument('--stats-density', dest='stats_density', choices=('gaussian', 'voronoi'), default='gaussian',
                    help='--match-stats: the local density of the crowd statistics (DESIGN 4.16 / 4.20)')
     p.add_argument('--stats-cutoff', dest='stats_cutoff', type=float, default=None,
@@ -672,12 +721,23 @@ def get_args(argv=None):
     p.add_argument('--generations', type=int, default=30)
     p.add_argument('--search-seed', dest='search_seed', type=int, default=0)
     a = p.parse_args(argv)
+    wall_names = [k for k in WALL_PARAM_NAMES if k in a.init or k in a.fit]
+    if wall_names:
+        if not a.match_stats:
+            p.error(f'{wall_names}: the wall term is fitted by --match-stats only (it exists in the scene runs, not in the '
+                    'one-step or rollout fit)')
+        if not all(k in a.init for k in WALL_PARAM_NAMES):
+            p.error('the wall term has no default: --init must give Aw and Bw (the literature starts at Aw=50,Bw=-5)')
+    elif a.wall_cutoff is not None:
+        p.error('--wall-cutoff needs a wall term (--init Aw=..,Bw=..)')
     if a.match_stats:
         if len(a.data) != 1:
             p.error('--match-stats takes one clip')
+        if a.match is None:
+            a.match = 'crowd,pairs,obstacles' if wall_names else 'crowd,pairs'
         a.match = tuple(filter(None, (x.strip() for x in a.match.split(','))))
-        if not a.match or any(x not in ('crowd', 'pairs') for x in a.match):
-            p.error(f"--match: 'crowd', 'pairs' or both expected, got {a.match}")
+        if not a.match or any(x not in ('crowd', 'pairs', 'obstacles') for x in a.match):
+            p.error(f"--match: 'crowd', 'pairs', 'obstacles' or several expected, got {a.match}")
         try:
             from .crowdstats import check_density
             check_density(a.stats_density, a.stats_cutoff)
@@ -760,13 +820,21 @@ def _main_stats(a, raw, init):
     if ref_crowd is not None:
         crowdstats.print_dropped(ref_crowd, 'calibrate --match-stats')
     ref_pairs = pairstats.pair_stats_of_raw(raw, frames=(lo, hi)) if 'pairs' in a.match else None
-    res = calibrate_mlapm_to_stats(scene, (ref_crowd, ref_pairs), version=a.version, init=init, fit=a.fit, frames=hi - lo,
-                                   seeds=a.seeds, population=a.population, generations=a.generations,
-                                   search_seed=a.search_seed, radius=a.radius)
+    ref_obstacles = None
+    if 'obstacles' in a.match:
+        from . import obstaclestats
+        try:
+            ref_obstacles = obstaclestats.obstacle_stats_of_raw(raw, scene.obstacles, frames=(lo, hi))
+        except ValueError as ex:
+            sys.exit(f'--match obstacles: {ex}')
+    res = calibrate_mlapm_to_stats(scene, (ref_crowd, ref_pairs, ref_obstacles), version=a.version, init=init, fit=a.fit,
+                                   frames=hi - lo, seeds=a.seeds, population=a.population, generations=a.generations,
+                                   search_seed=a.search_seed, radius=a.radius, wall_cutoff=a.wall_cutoff)
     print(f'[calibrate] {a.version} against the statistics ({", ".join(a.match)}) of frames {lo}:{hi}, {a.population} '
           f'candidates x {len(a.seeds)} seeds x {a.generations} generations: objective {res.initial_loss:.6g} -> '
           f'{res.final_loss:.6g} ({res.status})')
-    print('[calibrate] ' + ', '.join(f'{k}={res.params[k]:.6g}' for k in PARAM_NAMES))
+    print('[calibrate] ' + ', '.join(f'{k}={res.params[k]:.6g}' for k in PARAM_NAMES + WALL_PARAM_NAMES + ('wall_cutoff',)
+                                     if k in res.params))
     print('[calibrate] terms: ' + ', '.join(f'{k} {v:.4g}' if isinstance(v, float) else f'{k} {v}'
                                            for k, v in (res.terms or {}).items()))
     with open(a.out, 'w') as fh:

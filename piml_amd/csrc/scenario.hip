@@ -76,6 +76,7 @@
 #include "common.hpp"
 #include "mlapm.hpp"
 #include "philox.hpp"
+#include "walls.hpp"
 #include "../../include/piml_hip.h"
 
 #include <cmath>
@@ -609,10 +610,15 @@ struct MlapmScenarioArgs {
 // so the 56 bytes arrive by scalar loads.  The tile loop, the NaN staging of absent sources, GC's exit distance and the
 // spawn blocks are the same code in both; the kTable == false code is instruction for instruction what it was before the
 // table existed (the extra pointer moved one hidden-argument offset).
-template <bool kTable>
-__global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_kernel(const MlapmScenarioArgs K0,
-                                                                        const unsigned long long* __restrict__ seeds,
-                                                                        const MlapmParams* __restrict__ table) {
+//
+// kWalls (piml_scenario_step_mlapm_walls): the frame with the wall term of walls.hpp, F = ((v0 e - v) / tau - sum) + W, W
+// from the agent's position in the state (frame t's) and added last, one float32 add per component; everything else is the
+// same code.  The wall law is the by-value `wall`, or row blockIdx.y of `wall_table` when that is not NULL (read on every
+// launch, as the law table).  kWalls == false is the two plain kernels below, whose names and arguments did not change.
+template <bool kTable, bool kWalls>
+__device__ __forceinline__ void scenario_mlapm_body(const MlapmScenarioArgs& K0, const unsigned long long* __restrict__ seeds,
+                                                    const MlapmParams* __restrict__ table, const WallArgs& WG,
+                                                    const piml_wall_law& wall, const piml_wall_law* __restrict__ wall_table) {
     __shared__ float4 tile[kMlTile];                         // agent blocks: the sources (px, py, vx, vy); spawn blocks: entries
     __shared__ unsigned short ucy_ring[kMlScWaves][256];
     static_assert(kScenarioLdsPoints * sizeof(float2) <= sizeof(tile), "the entry points fit the source tile");
@@ -668,8 +674,13 @@ __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_kernel(const M
         sx = wave_sum(sx); sy = wave_sum(sy);
         const float dt = S.dt;
         const float v0i = S.desired_speed[i];
-        const float fx = (v0i * ex - vi.x) / P.tau - sx;     // :22, :29/:40/:53
-        const float fy = (v0i * ey - vi.y) / P.tau - sy;
+        float fx = (v0i * ex - vi.x) / P.tau - sx;           // :22, :29/:40/:53
+        float fy = (v0i * ey - vi.y) / P.tau - sy;
+        if constexpr (kWalls) {
+            const piml_wall_law w = wall_table ? wall_table[blockIdx.y] : wall;   // block-uniform index: scalar loads
+            const WallHit h = wall_force_wave(WG, w.A, w.B, make_float2(uniform(pi.x), uniform(pi.y)), lane);
+            fx += h.force.x; fy += h.force.y;
+        }
         const float2 vn = make_float2(vi.x + fx * dt, vi.y + fy * dt);          // :57
         const float2 pn = make_float2(pi.x + vn.x * dt, pi.y + vn.y * dt);      // main_mlapm.py:25
         const float2 an = make_float2(fx, fy);
@@ -697,6 +708,22 @@ __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_kernel(const M
         ent = lds_entries;
     }
     spawn_block(K0.gc, S, K0.R, K0.S.poisson_thresholds, ent, 0, n, t + 1, (int)blockIdx.x - K0.agent_blocks);
+}
+
+template <bool kTable>
+__global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_kernel(const MlapmScenarioArgs K0,
+                                                                        const unsigned long long* __restrict__ seeds,
+                                                                        const MlapmParams* __restrict__ table) {
+    scenario_mlapm_body<kTable, false>(K0, seeds, table, WallArgs{}, piml_wall_law{}, nullptr);
+}
+
+template <bool kTable>
+__global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_walls_kernel(const MlapmScenarioArgs K0,
+                                                                              const unsigned long long* __restrict__ seeds,
+                                                                              const MlapmParams* __restrict__ table,
+                                                                              const WallArgs WG, const piml_wall_law wall,
+                                                                              const piml_wall_law* __restrict__ wall_table) {
+    scenario_mlapm_body<kTable, true>(K0, seeds, table, WG, wall, wall_table);
 }
 
 }  // namespace piml
@@ -841,6 +868,34 @@ PIML_API int piml_scenario_step_mlapm_laws(const piml_scenario* s, const piml_sc
     K.P = piml::MlapmParams{};                               // not read: the rows are the table's
     hipLaunchKernelGGL(piml::scenario_mlapm_kernel<true>, grid, dim3(piml::kMlScWaves * 64), 0, piml::as_stream(stream), K,
                        (const unsigned long long*)seeds, (const piml::MlapmParams*)table_device);
+    return hipGetLastError();
+}
+
+PIML_API int piml_scenario_step_mlapm_walls(const piml_scenario* s, const piml_scenario_rules* r, int members,
+                                            const uint64_t* seeds, const piml_mlapm_law* law, const void* table_device,
+                                            const piml_wall_grid* g, const piml_wall_law* wall,
+                                            const piml_wall_law* wall_table_device, int frame_offset, void* stream) {
+    if (!s || !seeds || members < 1 || members > 65535 || frame_offset < 0 || !frame_args_ok(*s, r, nullptr, 1))
+        return hipErrorInvalidValue;
+    if (!law == !table_device || !wall == !wall_table_device) return hipErrorInvalidValue;   // exactly one of each pair
+    if (law && !mlapm_law_ok(*law)) return hipErrorInvalidValue;
+    if (!piml::wall_grid_ok(g) || (wall && !piml::wall_law_ok(wall->A, wall->B))) return hipErrorInvalidValue;
+    piml::MlapmScenarioArgs K;
+    const dim3 grid = mlapm_frame_launch(K, *s, r, members, frame_offset);
+    const piml::WallArgs WG = piml::wall_args(*g);
+    const piml_wall_law w = wall ? *wall : piml_wall_law{};
+    if (law) {
+        const piml_mlapm_law& L = *law;
+        K.P = piml::make_params(L.variant, L.tau, L.A, L.B, L.C, L.D, L.theta_deg, L.radius, 1);
+        hipLaunchKernelGGL(piml::scenario_mlapm_walls_kernel<false>, grid, dim3(piml::kMlScWaves * 64), 0,
+                           piml::as_stream(stream), K, (const unsigned long long*)seeds, (const piml::MlapmParams*)nullptr, WG,
+                           w, wall_table_device);
+    } else {
+        K.P = piml::MlapmParams{};                           // not read: the rows are the table's
+        hipLaunchKernelGGL(piml::scenario_mlapm_walls_kernel<true>, grid, dim3(piml::kMlScWaves * 64), 0,
+                           piml::as_stream(stream), K, (const unsigned long long*)seeds,
+                           (const piml::MlapmParams*)table_device, WG, w, wall_table_device);
+    }
     return hipGetLastError();
 }
 

@@ -1,8 +1,12 @@
 """`MLAPM`: the closed-form social-force law (reference src/models/mlapm.py), same constructor
 and `step` signature, evaluated by the HIP pair kernel with an analytic backward.  `simulate_scenario` /
 `simulate_ensemble` drive the open-world scenes of piml_amd.scenarios with it (one launch per frame); `simulate_sweep` does
-so for a list of laws at once, one law per ensemble member."""
+so for a list of laws at once, one law per ensemble member.  With the optional constants Aw, Bw (and wall_cutoff) the scene
+runs add a wall term, the repulsion Aw exp(Bw d) of the nearest obstacle point within wall_cutoff (include/piml_hip.h,
+piml_scenario_step_mlapm_walls); `step` and `rollout` never have one."""
 from .. import ops
+
+DEFAULT_WALL_CUTOFF = 2.0     # metres
 
 
 class MLAPM:
@@ -10,6 +14,7 @@ class MLAPM:
         self.args = args
         if args.get('version') not in ops.MLAPM_VARIANTS:
             raise NotImplementedError(args.get('version'))
+        wall_args(args)                                       # (ValueError on a half-given or out-of-range wall term)
 
     def step(self, position, velocity, desired_speed, destination, dt, radius=0.3):
         """position, velocity, destination: (N, 2); desired_speed: (N, 1), (N,) or (N, 2).  Returns the new
@@ -138,8 +143,11 @@ class MLAPM:
         radius: MLAPM's UCY collision radius (mlapm.py:42-46), NOT the scene's arrival radius.  capacity: default
         scenarios.default_capacity, as the PINNSF path.  use_graph (None: more than 8 frames): `frames_per_graph` frames
         per captured graph, replayed.  hist_width: the velocity history kept for the self_features columns.
-        Limits of the reference's law, restated: no obstacle or wall term (the square's obstacle points are not felt;
-        GC agents pass the pillar by their waypoints), and an agent at rest sees nobody (view is v . r > 0).
+        The reference's law has no obstacle or wall term (the square's obstacle points are not felt; GC agents pass the
+        pillar by their waypoints), and an agent at rest sees nobody (view is v . r > 0).  MLAPM(..., Aw=, Bw=[,
+        wall_cutoff=2.0]) adds one: W = Aw exp(Bw d) (p - q*) / d for the nearest valid obstacle point q* within wall_cutoff,
+        isotropic (a resting agent feels it), added to the force last; Aw = 50, Bw = -5 (Helbing and Molnar 1995) is the
+        literature's starting point for a fit, not a default.  ValueError when Aw is given and the scene has no obstacles.
         Returns a scenarios.ScenarioResult."""
         return self._simulate(scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, seed=seed)
 
@@ -155,16 +163,23 @@ class MLAPM:
                               seeds=seeds)
 
     def _simulate(self, scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, **state_kw):
-        from .. import scenarios
+        from .. import ops_scenario, scenarios
         law = self._law(radius)
+        wall = wall_args(self.args)
+        if wall is not None:
+            check_scene_walls(scenario)
         st = scenarios.scenario_state_for(scenario, frames, capacity, device, hist_width, **state_kw)
-        self._run_scenario(st, law, use_graph, frames_per_graph)
+        walls = None
+        if wall is not None:
+            walls = (ops_scenario.wall_grid(st.scenario.obstacles, wall[2], st.p.device), ops_scenario.wall_law(*wall[:2]))
+        self._run_scenario(st, law, use_graph, frames_per_graph, walls=walls)
         return scenarios.scenario_result(st)
 
     @staticmethod
-    def _run_scenario(st, law, use_graph, frames_per_graph, graph=None):
+    def _run_scenario(st, law, use_graph, frames_per_graph, graph=None, walls=None):
         """frame 0's spawn, then T - 1 MLAPM frames: K = frames_per_graph of them (offsets 0 .. K-1 and one counter add)
-        captured into one graph and replayed when use_graph, the rest eagerly.  law: a mlapm_law or a law table.  Returns
+        captured into one graph and replayed when use_graph, the rest eagerly.  law: a mlapm_law or a law table; walls:
+        None or ops_scenario.scenario_step_mlapm's (grid, wall law or wall table) for the frames with the wall term.  Returns
         the captured graph (None for an eager run); passed back as `graph` with the same state, the run replays it
         instead of capturing again."""
         import torch
@@ -177,43 +192,85 @@ class MLAPM:
             per = max(1, int(frames_per_graph))
             done = 0
             if use_graph and steps >= per + 1 and hip_graphs_safe():
-                ops_scenario.scenario_step_mlapm(st, law)             # a real frame, also warms the library up
+                ops_scenario.scenario_step_mlapm(st, law, walls=walls)     # a real frame, also warms the library up
                 done = 1
                 if graph is None:
                     torch.cuda.synchronize()
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
                         for k in range(per):
-                            ops_scenario.scenario_step_mlapm(st, law, frame_offset=k, advance=False)
+                            ops_scenario.scenario_step_mlapm(st, law, frame_offset=k, advance=False, walls=walls)
                         st.t.add_(per)
                 for _ in range((steps - done) // per):
                     graph.replay()
                 done += (steps - done) // per * per
             for _ in range(steps - done):
-                ops_scenario.scenario_step_mlapm(st, law)
+                ops_scenario.scenario_step_mlapm(st, law, walls=walls)
         return graph
 
     # ---- one law per member (piml_scenario_step_mlapm_laws): a sweep of candidates x seeds in one ensemble run ----
     @staticmethod
     def simulate_sweep(scenario, frames, params, seeds, capacity=None, use_graph=None, radius=0.3, device='cuda',
-                       hist_width=2, frames_per_graph=8):
+                       hist_width=2, frames_per_graph=8, wall_cutoff=DEFAULT_WALL_CUTOFF):
         """simulate_ensemble for every candidate of `params` in the same launches: params is a list of C dicts in
         MLAPM(**params) form (version, tau, A, B and optionally C, D, theta; an optional 'radius' overrides `radius` for
-        that candidate), and member c * len(seeds) + k runs law c under seeds[k] -- candidate-major, every candidate on
+        that candidate; optionally the wall term's Aw, Bw, in every candidate or in none -- wall_cutoff is common to the
+        sweep, a property of the scene's grid), and member c * len(seeds) + k runs law c under seeds[k] -- candidate-major, every candidate on
         the same seeds and so the same arrivals (common random numbers).  Candidates may differ in version.  Member
         (c, k) is bitwise MLAPM(**params[c]).simulate_ensemble(scenario, frames, seeds, capacity=same)'s member k.
         What the reference does with one process per parameter set (src/utils/grid_search.py) is one run here.
-        ValueError: an empty list, an unknown or missing key, C * len(seeds) > 65535.  Returns a scenarios.ScenarioSweep."""
+        ValueError: an empty list, an unknown or missing key, candidates with and without a wall term, a wall term in a
+        scene without obstacles, C * len(seeds) > 65535.  Returns a scenarios.ScenarioSweep."""
         return SweepRun(scenario, frames, len(params) if hasattr(params, '__len__') else 0, seeds, capacity, use_graph,
-                        device, hist_width, frames_per_graph).run(params, radius)
+                        device, hist_width, frames_per_graph, wall_cutoff).run(params, radius)
 
 
-SWEEP_KEYS = ('version', 'tau', 'A', 'B', 'C', 'D', 'theta', 'radius')
+SWEEP_KEYS = ('version', 'tau', 'A', 'B', 'C', 'D', 'theta', 'radius', 'Aw', 'Bw')
+
+
+def wall_args(args):
+    """(Aw, Bw, wall_cutoff) of MLAPM(**args)'s wall term, None without one.  ValueError: Bw or wall_cutoff without Aw, Aw
+    without Bw, a value that is not finite, Aw < 0, Bw > 0, wall_cutoff <= 0."""
+    import math
+    if 'Aw' not in args:
+        if 'Bw' in args or 'wall_cutoff' in args:
+            raise ValueError('MLAPM: Bw / wall_cutoff belong to the wall term and need Aw')
+        return None
+    if 'Bw' not in args:
+        raise ValueError('MLAPM: the wall term needs both Aw and Bw')
+    Aw, Bw, cutoff = float(args['Aw']), float(args['Bw']), float(args.get('wall_cutoff', DEFAULT_WALL_CUTOFF))
+    if not all(math.isfinite(x) for x in (Aw, Bw, cutoff)) or Aw < 0 or Bw > 0 or not cutoff > 0:
+        raise ValueError(f'MLAPM: finite Aw >= 0, Bw <= 0 and wall_cutoff > 0 expected, got {Aw}, {Bw}, {cutoff}')
+    return Aw, Bw, cutoff
+
+
+def check_scene_walls(scenario):
+    """ValueError when the scene has no valid (finite) obstacle point for a wall term to act from."""
+    import torch
+    obs = scenario.obstacles
+    if obs is None or obs.numel() == 0 or not bool(torch.isfinite(obs.reshape(-1, 2)).all(1).any()):
+        raise ValueError('MLAPM: a wall term (Aw) was given, but the scene has no obstacles')
+
+
+def sweep_walls(params):
+    """The (Aw, Bw) pair of every candidate dict, or None when no candidate has a wall term.  ValueError when only some
+    have one, or on a value wall_args refuses."""
+    params = list(params)
+    have = [isinstance(a, dict) and 'Aw' in a for a in params]
+    if any(have) and not all(have):
+        raise ValueError(f'simulate_sweep: candidates {[c for c, h in enumerate(have) if not h]} have no wall term (Aw, Bw) '
+                         'and the others do: every candidate or none')
+    for c, a in enumerate(params):
+        if isinstance(a, dict) and not have[c] and 'Bw' in a:
+            raise ValueError(f'candidate {c}: Bw without Aw')
+    if not any(have):
+        return None
+    return [wall_args({k: a[k] for k in ('Aw', 'Bw') if k in a})[:2] for a in params]
 
 
 def sweep_laws(params, radius=0.3):
     """The mlapm_law of every candidate dict (simulate_sweep's form).  ValueError on an empty list, an unknown or
-    missing key, or a value mlapm_law refuses."""
+    missing key, a value mlapm_law refuses, or candidates with and without a wall term (sweep_walls gives its rows)."""
     from .. import ops_scenario
     params = list(params)
     if not params:
@@ -228,17 +285,19 @@ def sweep_laws(params, radius=0.3):
             raise ValueError(f'candidate {c}: unknown keys {unknown}, missing keys {missing} (of {SWEEP_KEYS})')
         laws.append(ops_scenario.mlapm_law(a['version'], a['tau'], a['A'], a['B'], a.get('C', 0.0), a.get('D', 0.0),
                                            a.get('theta', 0.0), a.get('radius', radius)))
+    sweep_walls(params)
     return laws
 
 
 class SweepRun:
-    """The state, law table and captured frames of a sweep of n_candidates laws x seeds, kept for running again:
-    run(params) writes the candidates' table into the same device buffer, puts the state back to empty and replays the
+    """The state, law table (and wall table, when the candidates carry Aw, Bw) and captured frames of a sweep of
+    n_candidates laws x seeds, kept for running again:
+    run(params) writes the candidates' tables into the same device buffers, puts the state back to empty and replays the
     graph captured by the first run, so a further population costs one small copy, the fills and the replays -- what a
     generation of calibrate.calibrate_mlapm_to_stats is.  Every run is bitwise a fresh MLAPM.simulate_sweep."""
 
     def __init__(self, scenario, frames, n_candidates, seeds, capacity=None, use_graph=None, device='cuda', hist_width=2,
-                 frames_per_graph=8):
+                 frames_per_graph=8, wall_cutoff=DEFAULT_WALL_CUTOFF):
         from .. import ops_scenario, scenarios
         self.seeds = [int(x) for x in seeds]
         self.n_candidates = int(n_candidates)
@@ -249,7 +308,8 @@ class SweepRun:
                              f'{self.n_candidates * len(self.seeds)} members, more than {ops_scenario.MAX_MEMBERS}')
         self.scenario, self.frames, self.capacity, self.device = scenario, frames, capacity, device
         self.hist_width, self.use_graph, self.frames_per_graph = hist_width, use_graph, frames_per_graph
-        self.st = self.table = self.graph = None
+        self.wall_cutoff = float(wall_cutoff)
+        self.st = self.table = self.graph = self.wall_grid = self.wall_table = None
 
     def run(self, params, radius=0.3):
         from .. import ops_scenario, scenarios
@@ -259,14 +319,27 @@ class SweepRun:
             raise ValueError(f'{len(laws)} candidates for a sweep of {self.n_candidates}')
         S = len(self.seeds)
         rows = [law for law in laws for _ in range(S)]
+        walls = sweep_walls(params)
+        wall_rows = None if walls is None else [ops_scenario.wall_law(*w) for w in walls for _ in range(S)]
         if self.st is None:
+            if walls is not None:
+                wall_args({'Aw': 0.0, 'Bw': 0.0, 'wall_cutoff': self.wall_cutoff})
+                check_scene_walls(self.scenario)
             self.st = scenarios.scenario_state_for(self.scenario, self.frames, self.capacity, self.device, self.hist_width,
                                                    seeds=self.seeds * self.n_candidates)
             self.table = ops_scenario.mlapm_law_table(rows, self.st.p.device)
+            if walls is not None:
+                self.wall_grid = ops_scenario.wall_grid(self.st.scenario.obstacles, self.wall_cutoff, self.st.p.device)
+                self.wall_table = ops_scenario.wall_law_table(wall_rows, self.st.p.device)
         else:
+            if (walls is None) != (self.wall_table is None):  # the captured frames are those of the first run's kernel
+                raise ValueError('SweepRun: every run of a sweep has a wall term (Aw, Bw) or none has')
             ops_scenario.mlapm_law_table(rows, out=self.table)
+            if walls is not None:
+                ops_scenario.wall_law_table(wall_rows, out=self.wall_table)
             ops_scenario.scenario_state_reset(self.st)
-        self.graph = MLAPM._run_scenario(self.st, self.table, self.use_graph, self.frames_per_graph, graph=self.graph)
+        self.graph = MLAPM._run_scenario(self.st, self.table, self.use_graph, self.frames_per_graph, graph=self.graph,
+                                         walls=None if walls is None else (self.wall_grid, self.wall_table))
         ens = scenarios.scenario_result(self.st)
         fields = dict(vars(ens))
         return scenarios.ScenarioSweep(params=params, n_candidates=self.n_candidates, seeds_per_candidate=S, **fields)

@@ -1,5 +1,6 @@
 """Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_step_rules,
-piml_scenario_step_members, piml_scenario_step_mlapm, piml_scenario_step_mlapm_laws, piml_scenario_route).
+piml_scenario_step_members, piml_scenario_step_mlapm, piml_scenario_step_mlapm_laws, piml_scenario_step_mlapm_walls,
+piml_wall_force, piml_scenario_route).
 
 `scenario_state` allocates the persistent (static-address) buffers of one simulation or an ensemble and the
 `piml_scenario` descriptor that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive,
@@ -223,14 +224,145 @@ def mlapm_law_table(laws, device='cuda', out=None):
     return host.to(dev)
 
 
-def scenario_step_mlapm(st, law, frame_offset=0, advance=True):
+WALL_CELL_MARGIN = 1.0 + 2.0 ** -5     # cell >= cutoff (1 + 2^-5): the 3 x 3 neighbourhood's exactness margin (walls.hpp)
+WALL_MAX_CELLS = 1024                  # per axis
+
+
+def wall_law(Aw, Bw):
+    """The piml_wall_law of W = Aw exp(Bw d) n (include/piml_hip.h).  ValueError unless both are finite, Aw >= 0, Bw <= 0."""
+    Aw, Bw = float(Aw), float(Bw)
+    if not (math.isfinite(Aw) and math.isfinite(Bw)) or Aw < 0 or Bw > 0:
+        raise ValueError(f'wall law: finite Aw >= 0 and Bw <= 0 expected, got Aw={Aw}, Bw={Bw}')
+    law = _lib.WallLaw()
+    law.A, law.B = Aw, Bw
+    return law
+
+
+def wall_grid_host(obstacles, cutoff=2.0):
+    """The static cell grid of a scene's obstacle points, on the host in numpy (no GPU call): a namespace of
+    points (n, 2) float32 -- the valid points (both coordinates finite) sorted stably by cell index cy gx + cx --, order (n)
+    the sorted points' indices into `obstacles`, cell_start (gx gy + 1) int32 CSR offsets, n_points, gx, gy and the float32
+    scalars x0, y0 (the points' minimum), cell, cutoff.  A point's cell is floor((q - origin) / cell) in float32;
+    cell = cutoff (1 + 2^-5), coarsened (with a warning) when that would need more than 1024 cells per axis.
+    ValueError unless cutoff is finite and > 0."""
+    import numpy as np
+    f32 = np.float32
+    if not math.isfinite(float(cutoff)) or not float(cutoff) > 0:
+        raise ValueError(f'wall_grid: a finite cutoff > 0 expected, got {cutoff}')
+    if isinstance(obstacles, torch.Tensor):
+        obstacles = obstacles.detach().cpu().numpy()
+    obs = np.ascontiguousarray(np.asarray(obstacles, dtype=f32).reshape(-1, 2))
+    keep = np.flatnonzero(np.isfinite(obs).all(1))
+    pts = obs[keep]
+    cutoff = f32(cutoff)
+    cell = f32(cutoff * f32(WALL_CELL_MARGIN))
+    g = types.SimpleNamespace(cutoff=float(cutoff), n_points=int(pts.shape[0]))
+    if pts.shape[0] == 0:
+        g.points, g.order = pts, keep
+        g.cell_start = np.zeros(2, np.int32)
+        g.gx = g.gy = 1
+        g.x0 = g.y0 = 0.0
+        g.cell = float(cell)
+        return g
+    origin = pts.min(0)
+    span = float((pts.max(0).astype(np.float64) - origin).max())
+    if span / float(cell) >= WALL_MAX_CELLS - 1:
+        import warnings
+        coarse = f32(span / (WALL_MAX_CELLS - 2))
+        warnings.warn(f'wall_grid: the obstacles span {span:g} m, more than {WALL_MAX_CELLS} cells of {float(cell):g} m per '
+                      f'axis: cells coarsened to {float(coarse):g} m')
+        cell = max(cell, coarse)
+    c = np.floor((pts - origin) / cell).astype(np.int64)
+    gx, gy = int(c[:, 0].max()) + 1, int(c[:, 1].max()) + 1
+    if gx > WALL_MAX_CELLS or gy > WALL_MAX_CELLS:
+        raise ValueError(f'wall_grid: {gx} x {gy} cells (more than {WALL_MAX_CELLS} per axis)')
+    key = c[:, 1] * gx + c[:, 0]
+    order = np.argsort(key, kind='stable')
+    g.points = np.ascontiguousarray(pts[order])
+    g.order = keep[order]
+    g.cell_start = np.concatenate(([0], np.cumsum(np.bincount(key, minlength=gx * gy)))).astype(np.int32)
+    g.gx, g.gy, g.x0, g.y0, g.cell = gx, gy, float(origin[0]), float(origin[1]), float(cell)
+    return g
+
+
+def wall_grid(obstacles, cutoff=2.0, device='cuda'):
+    """wall_grid_host's grid with its points and cell_start on `device` and the piml_wall_grid descriptor that points at
+    them: a namespace of points, cell_start (device tensors), desc, cutoff, cell, gx, gy, x0, y0, n_points and host (the
+    wall_grid_host namespace: the numpy copies and `order`).  Built once per scene; the obstacles are static."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.PimlHipError(f'wall_grid: a GPU device expected (piml_amd has no CPU path), got {dev}')
+    h = wall_grid_host(obstacles, cutoff)
+    g = types.SimpleNamespace(host=h, cutoff=h.cutoff, cell=h.cell, gx=h.gx, gy=h.gy, x0=h.x0, y0=h.y0, n_points=h.n_points)
+    g.points = torch.from_numpy(h.points).to(dev)
+    g.cell_start = torch.from_numpy(h.cell_start).to(dev)
+    g.desc = wall_grid_desc(h, g.points.data_ptr() if h.n_points else None, g.cell_start.data_ptr())
+    return g
+
+
+def wall_grid_desc(h, points_ptr, cell_start_ptr):
+    """The piml_wall_grid of a wall_grid_host namespace over the given buffers."""
+    d = _lib.WallGrid()
+    d.points, d.cell_start = points_ptr, cell_start_ptr
+    d.n_points, d.gx, d.gy = h.n_points, h.gx, h.gy
+    d.x0, d.y0, d.cell, d.cutoff = h.x0, h.y0, h.cell, h.cutoff
+    return d
+
+
+def wall_force(position, grid, Aw, Bw, return_selection=False):
+    """The wall term W = Aw exp(Bw d) (p - q*) / d of every row of position (..., 2) against the nearest valid obstacle point
+    q* within grid.cutoff (wall_grid(...); piml_wall_force, one wave per row): force (..., 2), zero where no point is felt
+    (none within the cutoff, a NaN position, d == 0).  return_selection: also dist2 (...) float32 (the exact squared
+    distance, +inf for none) and index (...) int32 into grid.points (grid.host.order maps it to the obstacle list; -1 for
+    none)."""
+    law = wall_law(Aw, Bw)
+    p = _gpu_f32('position', position)
+    if p.dim() < 1 or p.shape[-1] != 2:
+        raise ValueError(f'position: (..., 2) expected, got {tuple(p.shape)}')
+    if grid.cell_start.device != p.device:
+        raise ValueError(f'position on {p.device}, the wall grid on {grid.cell_start.device}')
+    lead = p.shape[:-1]
+    rows = p.numel() // 2
+    force = torch.zeros_like(p)
+    dist2 = torch.full(lead, float('inf'), device=p.device, dtype=torch.float32) if return_selection else None
+    index = torch.full(lead, -1, device=p.device, dtype=torch.int32) if return_selection else None
+    if rows and grid.n_points:                   # (an empty problem keeps the fills above: the entry launches nothing)
+        with torch.cuda.device(p.device):
+            _lib.check(_lib.lib().piml_wall_force(_ptr(p), rows, ctypes.byref(grid.desc), law.A, law.B, _ptr(force),
+                                                  _ptr(dist2), _ptr(index), _stream()), 'piml_wall_force')
+    return (force, dist2, index) if return_selection else force
+
+
+def wall_law_table(rows, device='cuda', out=None):
+    """The wall table of piml_scenario_step_mlapm_walls: rows, a list of (Aw, Bw) pairs or wall_law(...) values, one per
+    member, as a (len(rows), 2) float32 device tensor (every row checked as wall_law does).  out: a table of the same
+    shape to overwrite in place instead (a captured run reads the buffer at every replay)."""
+    laws = [r if isinstance(r, _lib.WallLaw) else wall_law(*r) for r in rows]
+    if not laws:
+        raise ValueError('wall_law_table: at least one row expected')
+    host = torch.tensor([[w.A, w.B] for w in laws], dtype=torch.float32)
+    if out is not None:
+        if out.dtype != torch.float32 or tuple(out.shape) != tuple(host.shape) or not out.is_contiguous():
+            raise ValueError(f'out: a contiguous float32 table {tuple(host.shape)} expected, got {out.dtype} {tuple(out.shape)}')
+        out.copy_(host)
+        return out
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.PimlHipError(f'wall_law_table: a GPU device expected (piml_amd has no CPU path), got {dev}')
+    return host.to(dev)
+
+
+def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None):
     """One launch: frame t -> t + 1 of st (single or ensemble state) under the MLAPM law `law` (mlapm_law(...)), t =
     st.t + frame_offset: the force of MLAPM.step from the agents present in frame t's records, v' = v + F dt, p' = p + v' dt
     (src/main_mlapm.py:18-36), a' = F, then the scene's arrivals, exits and spawns as scenario_step.  advance: add 1 to
     st.t afterwards (the kernel reads the counter, never writes it; a captured run of K frames passes offsets 0 .. K-1 and
     advances once by K).  Frame 0's spawn is scenario_step(st, init=True), which does not depend on the law.
     law may instead be a table of mlapm_law_table(...) with one row per member of st (member m steps under row m,
-    piml_scenario_step_mlapm_laws); ValueError when it does not hold exactly st.seeds.numel() rows or is on another device."""
+    piml_scenario_step_mlapm_laws); ValueError when it does not hold exactly st.seeds.numel() rows or is on another device.
+    walls = (grid, wall): the frame with the wall term (piml_scenario_step_mlapm_walls), F = (MLAPM's force) + W of
+    wall_force at the agent's position; grid a wall_grid(...) of the scene's obstacles, wall a wall_law(Aw, Bw) for every
+    member or a wall_law_table(...) with one row per member."""
     table = isinstance(law, torch.Tensor)
     if table:
         row = int(_lib.lib().piml_mlapm_law_table_bytes(1))
@@ -245,6 +377,28 @@ def scenario_step_mlapm(st, law, frame_offset=0, advance=True):
         raise TypeError(f'law: an ops_scenario.mlapm_law(...) or a mlapm_law_table(...) expected, got {type(law).__name__}')
     if int(frame_offset) < 0:
         raise ValueError(f'frame_offset must be >= 0, got {frame_offset}')
+    if walls is not None:
+        grid, wall = walls
+        wall_table = isinstance(wall, torch.Tensor)
+        if wall_table:
+            if wall.dtype != torch.float32 or tuple(wall.shape) != (st.seeds.numel(), 2) or not wall.is_contiguous():
+                raise ValueError(f'wall table: a contiguous float32 ({st.seeds.numel()}, 2) tensor of wall_law_table '
+                                 f'expected, got {wall.dtype} {tuple(wall.shape)}')
+            if wall.device != st.p.device:
+                raise ValueError(f'wall table on {wall.device}, the state on {st.p.device}')
+        elif not isinstance(wall, _lib.WallLaw):
+            raise TypeError(f'walls: (wall_grid, wall_law or wall_law_table) expected, got {type(wall).__name__}')
+        if grid.cell_start.device != st.p.device:
+            raise ValueError(f'wall grid on {grid.cell_start.device}, the state on {st.p.device}')
+        with torch.cuda.device(st.p.device):
+            _lib.check(_lib.lib().piml_scenario_step_mlapm_walls(
+                ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(), _ptr(st.seeds),
+                None if table else ctypes.byref(law), _ptr(law) if table else None, ctypes.byref(grid.desc),
+                None if wall_table else ctypes.byref(wall), _ptr(wall) if wall_table else None, int(frame_offset),
+                _stream()), 'piml_scenario_step_mlapm_walls')
+            if advance:
+                st.t.add_(1)
+        return
     with torch.cuda.device(st.p.device):
         if table:
             _lib.check(_lib.lib().piml_scenario_step_mlapm_laws(ctypes.byref(st.desc), ctypes.byref(st.rules),

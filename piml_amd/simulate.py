@@ -13,6 +13,8 @@ reads.
     python -m piml_amd.simulate --law mlapm --scenario crosswalk --seeds 0:32 --track-stats tracks.json   (track statistics)
                                 (velocity correlation and lane order, no clips written)
     python -m piml_amd.simulate --law mlapm --scenario gc --seeds 0:32 --obstacle-stats walls.json   (obstacle statistics)
+    python -m piml_amd.simulate --law mlapm --params p.json --seeds 0:32 --obstacle-stats walls.json
+                                (p.json with Aw, Bw [, wall_cutoff]: the law with a wall term, e.g. Aw = 50, Bw = -5)
     python -m piml_amd.simulate --law mlapm --params-sweep a.json b.json --seeds 0:8 --stats sweep.json
                                 (one law per file, every law on every seed in ONE ensemble run; statistics per candidate)
 
@@ -37,8 +39,8 @@ def get_args(argv=None):
                    help='force model: the network (default) or the closed-form MLAPM law')
     p.add_argument('--checkpoint', type=str, default='', help='state_dict of the model (torch.save); "" = initial weights')
     p.add_argument('--params', type=str, default=None,
-                   help="--law mlapm: the JSON `calibrate --out` writes (version and the six constants); default "
-                        "main_mlapm.py's constants, version GC")
+                   help="--law mlapm: the JSON `calibrate --out` writes (version and the six constants, optionally the wall "
+                        "term's Aw, Bw, wall_cutoff); default main_mlapm.py's constants, version GC, no wall term")
     p.add_argument('--params-sweep', dest='params_sweep', type=str, nargs='+', default=None,
                    help='--law mlapm with --seeds: several --params files, every law on every seed in one ensemble run '
                         "(MLAPM.simulate_sweep); --stats / --pair-stats / --flow-stats / --track-stats / --obstacle-stats then hold one entry per candidate, pooled over its "
@@ -128,6 +130,8 @@ def get_args(argv=None):
         try:
             own.mlapm = load_mlapm_params(own.params)
             own.mlapm_sweep = None if own.params_sweep is None else [load_mlapm_params(f) for f in own.params_sweep]
+            if own.mlapm_sweep is not None:
+                own.mlapm_sweep, own.wall_cutoff = _sweep_candidates(own.mlapm_sweep)
         except (OSError, ValueError) as ex:
             p.error(f'--params / --params-sweep: {ex}')
     elif own.params is not None:
@@ -138,8 +142,10 @@ def get_args(argv=None):
 
 def load_mlapm_params(path):
     """MLAPM's constructor arguments from the JSON `python -m piml_amd.calibrate --out` writes ({'version', 'tau', 'A',
-    'B', 'C', 'D', 'theta'}); constants the file leaves out keep calibrate.DEFAULT_INIT's values (main_mlapm.py:16), and
-    path None is those constants with version GC.  ValueError on an unknown version, an unknown key or a non-number."""
+    'B', 'C', 'D', 'theta'} and, for a law with a wall term, 'Aw', 'Bw', 'wall_cutoff'); constants the file leaves out keep
+    calibrate.DEFAULT_INIT's values (main_mlapm.py:16) -- the wall term has no default: without Aw there is none --, and
+    path None is those constants with version GC.  ValueError on an unknown version, an unknown key, a non-number or a
+    wall term MLAPM refuses (Bw or wall_cutoff without Aw, Aw < 0, Bw > 0, wall_cutoff <= 0)."""
     import json
     from . import calibrate, ops
     params = {'version': 'GC', **calibrate.DEFAULT_INIT}
@@ -149,16 +155,33 @@ def load_mlapm_params(path):
         got = json.load(fh)
     if not isinstance(got, dict):
         raise ValueError(f'{path}: a JSON object expected')
-    unknown = sorted(set(got) - {'version', *calibrate.PARAM_NAMES})
+    numbers = calibrate.PARAM_NAMES + calibrate.WALL_PARAM_NAMES + ('wall_cutoff',)
+    unknown = sorted(set(got) - {'version', *numbers})
     if unknown:
-        raise ValueError(f'{path}: unknown keys {unknown} (expected version and {list(calibrate.PARAM_NAMES)})')
+        raise ValueError(f'{path}: unknown keys {unknown} (expected version and {list(numbers)})')
     if got.get('version', 'GC') not in ops.MLAPM_VARIANTS:
         raise ValueError(f"{path}: unknown version {got.get('version')!r} (one of {sorted(ops.MLAPM_VARIANTS)})")
-    for k in calibrate.PARAM_NAMES:
+    for k in numbers:
         if k in got and (isinstance(got[k], bool) or not isinstance(got[k], (int, float))):
             raise ValueError(f'{path}: {k} = {got[k]!r} is not a number')
     params.update(got)
+    from .models.mlapm import wall_args
+    try:
+        wall_args(params)
+    except ValueError as ex:
+        raise ValueError(f'{path}: {ex}') from None
     return params
+
+
+def _sweep_candidates(params):
+    """--params-sweep: the candidates without their wall_cutoff, and the one cutoff they share (a sweep runs on one wall
+    grid).  ValueError when the files disagree on it or only some carry a wall term."""
+    from .models.mlapm import DEFAULT_WALL_CUTOFF, sweep_walls
+    sweep_walls(params)
+    cut = sorted({float(a.get('wall_cutoff', DEFAULT_WALL_CUTOFF)) for a in params if 'Aw' in a})
+    if len(cut) > 1:
+        raise ValueError(f'the files disagree on wall_cutoff ({cut}): a sweep runs on one wall grid')
+    return [{k: v for k, v in a.items() if k != 'wall_cutoff'} for a in params], (cut[0] if cut else DEFAULT_WALL_CUTOFF)
 
 
 def parse_seeds(text):
@@ -210,6 +233,12 @@ def main(argv=None):
     else:
         kw = {} if own.uniform_desired_speed is None else {'uniform_desired_speed': own.uniform_desired_speed}
         scenario = SCENARIOS.SCENARIOS[own.scenario](time_unit=own.time_unit, **kw)
+    if own.law == 'mlapm' and any('Aw' in a for a in (own.mlapm_sweep or [own.mlapm])):
+        from .models.mlapm import check_scene_walls
+        try:
+            check_scene_walls(scenario)
+        except ValueError as ex:
+            sys.exit(f'--params / --params-sweep: {ex}')
     if own.law == 'mlapm' and own.mlapm_sweep is not None:
         return _sweep(sim, scenario, own, run_kw)
     if own.seeds is not None:
@@ -280,7 +309,8 @@ def _stats(res, own):
 def _sweep(sim, scenario, own, run_kw):
     """--params-sweep: every law on every seed in one ensemble run; statistics per candidate, pooled over its seeds."""
     import json
-    sw = sim.simulate_sweep(scenario, own.frames, own.mlapm_sweep, own.seeds, capacity=own.capacity, **run_kw)
+    sw = sim.simulate_sweep(scenario, own.frames, own.mlapm_sweep, own.seeds, capacity=own.capacity,
+                            wall_cutoff=own.wall_cutoff, **run_kw)
     groups = [sw.members_of(c) for c in range(sw.n_candidates)]
     if own.stats is not None:
         from . import crowdstats
