@@ -39,6 +39,9 @@
 extern "C" {
 #endif
 
+/* Bumped when a declared function changes its signature or a struct changes a field that exists.  Fields APPENDED to a struct and
+ * added functions leave it alone (35 since the scenario structs): a caller built against an older header of the same version
+ * must zero-fill the structs it passes to a newer library to their CURRENT size -- piml_amd/_lib.py and the library travel together. */
 #define PIML_HIP_ABI_VERSION 35
 #define PIML_MAX_TOPK 32 /* topk_ped / topk_obs upper bound (reference defaults 6 / 10) */
 
@@ -1240,7 +1243,27 @@ typedef struct piml_encoder_branch {
      * non-NULL (the collision head reads the rows), `msgs` is not written.  bwd in: g_pooled = d/d(sums) (agents, 128);
      * dW3 / db3 are not produced here (they follow from the decoder's folded first layer: piml_pinnsf_bwd). */
     float *sum_a, *sum_b;
+    /* PIML_POOL_TRAIN, optional, branch 1 of a two-branch call only (a branch whose rows nothing reads one by one): COMPACT ROWS.
+     * An agent whose first neighbour slot is empty (nbr_idx[agent * k] < 0: the relative-feature kernels fill the slots of a row
+     * front to back, and an empty slot is an all-zero feature row) has k identical zero rows, whose layers give one constant.  With
+     * nbr_idx (rows ints: the branch's neighbour indices) and plan (PIML_COMPACT_PLAN_INTS(rows / k) ints of scratch) the forward
+     * runs only the agents that have a neighbour, 32 / k of them per tile, writes the constant for the others and leaves the
+     * lists of both kinds and the backward's workgroup split in `plan`; the backward (same `plan`, nbr_idx not read) follows it and
+     * adds the other agents' share of the weight gradients in closed form.  relu_mask must then hold
+     * PIML_COMPACT_TILES(rows / k, k) tiles when that is more than ceil(rows / 32), `partials` PIML_COMPACT_SLOTS slots in BOTH
+     * branches (the split between them follows the data), and g_x rows of agents without a neighbour are NOT written (they keep
+     * whatever the caller's buffer held; the relative-feature backward reads no row whose index is negative).  `packed` must come
+     * from piml_pinnsf_pack or piml_encoder_pack of this library version (both write the zero row's constants behind the images).
+     * Serves k = 2, 6 or 10 in branch 1, k <= 16 in branch 0, in_dim = 6 in both, rows / k <= PIML_COMPACT_MAX_AGENTS, the two-crew
+     * backward (piml_encoder_sums_bwd(2), the default); anything else with these pointers set is hipErrorInvalidValue, in the
+     * forward already.  Both NULL: every row goes through the layers. */
+    const int* nbr_idx;
+    int* plan;
 } piml_encoder_branch;
+#define PIML_COMPACT_MAX_AGENTS 16384
+#define PIML_COMPACT_PLAN_INTS(agents) (16 + 2 * (((agents) + 3) / 4 * 4))
+#define PIML_COMPACT_TILES(agents, k) (((agents) + 32 / (k) - 1) / (32 / (k)))
+#define PIML_COMPACT_SLOTS 256
 
 /* floats of one partial slot / of one `packed` buffer */
 int piml_encoder_partial_floats(void);

@@ -91,6 +91,11 @@ int piml_encoder_sums_bwd(int form);
  * as workgroups of the slot-sum launch instead of a launch of its own; 0 = by the slot-sum launch, the unfold behind it.
  * Environment at load time: PIML_ENC_DEC_SLOTS=0 / 1.  Returns the previous value; < 0 only queries. */
 int piml_encoder_sums_dec_slots(int on);
+/* Compact rows of that path (piml_encoder_branch.nbr_idx / plan): 1 (default) = callers that know a branch's neighbour indices
+ * hand them over, and agents without a neighbour skip the encoder layers; 0 = every row goes through them.  The library itself
+ * follows the pointers it is given; this switch is what piml_amd.ops asks before it sets them.  Environment at load time:
+ * PIML_ENC_COMPACT=0 / 1.  Returns the previous value; < 0 only queries. */
+int piml_encoder_compact_rows(int on);
 /* The library-owned side streams of PIML_FORK (piml_pinnsf_fwd / bwd with the independent stages forked: measured slower inside
  * captured graphs, kept for A/B): created per device on first use, outside any capture; idempotent. */
 int piml_pinnsf_streams_init(void);

@@ -12,6 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PIML_LIB=<path>: an experimental build of the same ABI beside the shipped library (piml_amd.build.variant; tools/ A/B timings)
 LIB_PATH = os.environ.get('PIML_LIB') or os.path.join(_HERE, 'libpiml_hip.so')
 ABI_VERSION = 35
+COMPACT_MAX_AGENTS = 16384      # PIML_COMPACT_MAX_AGENTS / PIML_COMPACT_SLOTS (include/piml_hip.h: compact rows)
+COMPACT_SLOTS = 256
 
 _lib = None
 
@@ -26,7 +28,8 @@ class EncoderBranch(ctypes.Structure):
                 ('w1', _p), ('b1', _p), ('w2', _p), ('b2', _p), ('w3', _p), ('b3', _p),
                 ('scale', _f), ('h1', _p), ('h2', _p), ('msgs', _p), ('g_pooled', _p), ('g_msgs', _p),
                 ('g2', _p), ('g1', _p), ('g_x', _p), ('partials', _p), ('grads', _p), ('packed', _p), ('relu_mask', _p),
-                ('keep_bits', _p), ('drop_state', _p), ('drop_p', _f), ('sum_a', _p), ('sum_b', _p)]
+                ('keep_bits', _p), ('drop_state', _p), ('drop_p', _f), ('sum_a', _p), ('sum_b', _p),
+                ('nbr_idx', _p), ('plan', _p)]
 
 
 class DecoderBranch(ctypes.Structure):
@@ -227,6 +230,7 @@ SIGNATURES = {
     'piml_encoder_fused_bwd': [_i],
     'piml_encoder_sums_bwd': [_i],
     'piml_encoder_sums_dec_slots': [_i],
+    'piml_encoder_compact_rows': [_i],
     'piml_encoder_pack': [ctypes.POINTER(EncoderBranch), _i, _p],
     'piml_encoder_workgroups': [ctypes.POINTER(EncoderBranch), _i, ctypes.POINTER(_i)],
     'piml_encoder_fwd': [ctypes.POINTER(EncoderBranch), _i, _p],

@@ -46,6 +46,13 @@ __global__ __launch_bounds__(256) void enc_pack_kernel(EncArgs A) {
     const piml_encoder_branch J = b ? A.br[1] : A.br[0];
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e < PACK_FLOATS) J.packed[e] = pack_value(J, e);
+    else if (e < PACK_FLOATS + EH) J.packed[e] = fmaxf(J.b1[e - PACK_FLOATS], 0.f);      // the zero row's constants (pack.hpp: PACK_ZROW)
+    else if (e < PACK_TOTAL) {                                                           // (float64 sum in index order, rounded once)
+        const int j = e - PACK_FLOATS - EH;
+        double sum = 0.0;
+        for (int q = 0; q < EH; ++q) sum += (double)J.w2[(size_t)j * EH + q] * (double)fmaxf(J.b1[q], 0.f);
+        J.packed[e] = fmaxf((float)((double)J.b2[j] + sum), 0.f);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -816,7 +823,7 @@ PIML_API int piml_encoder_workgroups(const piml_encoder_branch* br, int nbr, int
     return total;
 }
 
-PIML_API int piml_encoder_pack_floats(void) { return PACK_FLOATS; }
+PIML_API int piml_encoder_pack_floats(void) { return PACK_TOTAL; }
 
 static int enc_check(const piml_encoder_branch* br, int nbr) {
     if (!br || nbr < 1 || nbr > 2) return hipErrorInvalidValue;
@@ -850,7 +857,7 @@ int piml::enc_stage_pack(const piml_encoder_branch* br, int nbr, hipStream_t s) 
     A.zero = nullptr;
     A.zero_n = 0;
     A.gen_state = nullptr;
-    hipLaunchKernelGGL(enc_pack_kernel, dim3((PACK_FLOATS + 255) / 256, nbr), dim3(256), 0, s, A);
+    hipLaunchKernelGGL(enc_pack_kernel, dim3((PACK_TOTAL + 255) / 256, nbr), dim3(256), 0, s, A);
     return hipGetLastError();
 }
 
@@ -1270,9 +1277,27 @@ bool piml::enc_pool_msgs_ok(const piml_encoder_branch* br, int nbr) {
     return tiles >= 0 && tiles > g_split_tiles_train;
 }
 
+// compact rows (piml_encoder_branch.nbr_idx / plan): 0 = not asked for, 1 = branch 1 runs compact, -1 = asked for a shape or a
+// configuration that is not served: k of branch 1 other than 2 / 6 / 10 (the forward's compiled register -> agent maps), k of
+// branch 0 above 16 (the two-crew backward would refuse and the one-wave kernel knows no plan), the one-wave backward selected
+// (piml_encoder_sums_bwd(1)) -- checked in the forward already, so that no compact forward is left without its backward.
+// fwd: the forward also needs nbr_idx
+static int enc_compact_asked(const piml_encoder_branch* br, int nbr, bool fwd) {
+    bool any = false;
+    for (int i = 0; i < nbr; ++i) any = any || br[i].plan || br[i].nbr_idx;
+    if (!any) return 0;
+    if (nbr != 2 || br[0].plan || br[0].nbr_idx || !br[1].plan || (fwd && !br[1].nbr_idx)) return -1;
+    const piml_encoder_branch& b = br[1];
+    if ((b.k != 2 && b.k != 6 && b.k != 10) || br[0].k < 1 || br[0].k > 16 || b.rows % b.k || b.rows / b.k > PIML_COMPACT_MAX_AGENTS ||
+        b.in_dim != 6 || br[0].in_dim != 6 || b.h2 || g_sums_bwd == 1)
+        return -1;
+    return 1;
+}
+
 int piml::enc_stage_fwd_sum(const piml_encoder_branch* br, int nbr, hipStream_t s, float* zero, long long zero_n) {
     if (int e = enc_check(br, nbr)) return e;
     if (!enc_pool_train_ok(br, nbr)) return hipErrorInvalidValue;
+    if (enc_compact_asked(br, nbr, true) < 0) return hipErrorInvalidValue;
     for (int i = 0; i < nbr; ++i)
         if (!br[i].sum_a || !br[i].sum_b || !br[i].relu_mask) return hipErrorInvalidValue;
     EncArgs A;
@@ -1292,14 +1317,22 @@ int piml::enc_stage_bwd_sum(const piml_encoder_branch* br, int nbr, hipStream_t 
         const piml_encoder_branch& b = br[i];
         if (!b.g_pooled || b.g_msgs || !b.relu_mask || !b.partials || !b.grads || (b.g_x != nullptr) != (br[0].g_x != nullptr)) return hipErrorInvalidValue;
     }
+    const int compact = enc_compact_asked(br, nbr, false);
+    if (compact < 0) return hipErrorInvalidValue;
     EncArgs A;
     const int total = fill_args(A, br, nbr);
+    if (compact && total != PIML_COMPACT_SLOTS) return hipErrorInvalidValue;
     if (int e = x3_ready()) return e;
     static int ready = -1;
     if (ready < 0) { ready = enc_f3_set_attributes(); if (!ready) ready = enc_f5_set_attributes(); }
     if (ready) return ready;
     const int nA[2] = {nbr > 1 ? A.wg_split : total, nbr > 1 ? total - A.wg_split : 0};
     const int zero[2] = {0, 0};
+    if (compact) {            // (a compact forward's sign words and sums: the two-crew kernel or nothing)
+        if (!enc_f5_launch(A, nA, s, dec)) return hipErrorInvalidValue;
+        if (dec_summed) *dec_summed = dec && dec->nsets > 0;
+        return hipGetLastError();
+    }
     if (g_sums_bwd == 1 || !enc_f5_launch(A, nA, s, dec)) enc_f3_launch(A, nA, zero, false, s, true);
     else if (dec_summed) *dec_summed = dec && dec->nsets > 0;
     return hipGetLastError();

@@ -12,6 +12,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int ENC_THREADS = 512;        // 8 waves per workgroup: 2 per SIMD
 constexpr int ENC_WAVES = ENC_THREADS / 64;
+constexpr int CP_LISTS = 16;            // compact rows: the plan's lists behind its header (encoder_x3.hip)
 
 struct EncArgs {
     piml_encoder_branch br[2];

@@ -43,7 +43,7 @@ constexpr int F5_TBYTES = 128 * F5_TROW * 4;
 constexpr int F5_T = F5_H + 2 * F5_IMG;                      // G1 tiles [parity 2][feature 128][36] floats
 constexpr int F5_XS = F5_T + 2 * F5_TBYTES;                  // x rows [ring 3][32][8] floats
 constexpr int F5_MK = F5_XS + 3 * 1024;                      // sign words of h1 [parity 2][128 dwords]
-constexpr int F5_W1 = F5_MK + 2 * 512;                       // 4096 zero bytes (the W1 rows of a dropped vector form of g_x)
+constexpr int F5_W1 = F5_MK + 2 * 512;                       // 4096 bytes: zeros, or (compact rows) the 128 floats of S, written by crew B, read by both crews
 constexpr int F5_GXP = F5_W1 + 4096;                         // g_x partials [parity 2][wave 4][row 32][16] floats
 constexpr int F5_GXP_BYTES = 4 * 32 * 16 * 4;                // one parity
 constexpr int F5_TAB = F5_GXP + 2 * F5_GXP_BYTES;            // gather table [rem < 16][half 2][register 16] byte offsets
@@ -131,8 +131,19 @@ __device__ __forceinline__ constexpr int f5_rho(int r) { return (r & 3) + 8 * (r
 
 // INC: the columns of x the vector loops run over -- 6 when in_dim == 6 (every PINNSF encoder of the reference:
 // ped_feature_dim = obs_feature_dim = 6, src/main.py:60-62), else 8 (in_dim <= 8, padded with zeros)
-template <bool GX, int INC>
-__global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
+// CP: compact rows (piml_encoder_branch.plan of branch 1; the plan, its tiles and the constants of the zero row: encoder_x3.hip /
+// pack.hpp).  The split of the grid between the branches, the tiles of branch 1 and the agents behind their rows come from the plan
+// the forward left; the agents WITHOUT a neighbour -- k identical zero rows each, G2 = g_sum[agent] * [h2c > 0] on every one -- enter
+// in closed form behind the tile loop: with S = k * (sum of g_sum over the workgroup's share of them) * [h2c > 0],
+//     dW2 += S (x) h1c      db2 += S      db1 += (W2^T S) * [h1c > 0]      dW1 += 0 (their x is zero)
+// in a fixed order (share = agents e = bx, bx + nwg, ... of empty_of, lane half h the even / odd ones of them; dW2's accumulators
+// START from S (x) h1c), and their rows of g_x
+// are not written (the relative-feature backward reads no row whose index is negative).
+// CPM: 0 = no plan; 1 / 2 = a workgroup of branch 0 / 1 of a launch with one (two copies of the body in that kernel: the compact
+// requests beside the dense ones in ONE copy cost more registers than a wave has)
+template <bool GX, int INC, int CPM>
+__device__ __forceinline__ void enc_bwd_sums2_body(const F5Args& F) {
+    constexpr bool CP = CPM != 0;
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -140,13 +151,22 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
     const int ctid = tid & 255;                               // thread index within the crew
     const int n = lane & 31, h = lane >> 5;
     int bx = (int)blockIdx.x, b = 0;
-    if (bx >= F.nA[0]) { b = 1; bx -= F.nA[0]; }
+    const int* __restrict__ plan = CP ? F.A.br[1].plan : nullptr;
+    int nA0 = F.nA[0], nA1 = F.nA[1], nne = 0, nemp = 0, ctiles = 0;
+    if (CP) {
+        nne = __builtin_amdgcn_readfirstlane(plan[0]); nemp = __builtin_amdgcn_readfirstlane(plan[1]);
+        ctiles = __builtin_amdgcn_readfirstlane(plan[2]);
+        nA0 = __builtin_amdgcn_readfirstlane(plan[3]); nA1 = __builtin_amdgcn_readfirstlane(plan[4]);
+    }
+    if (CPM == 2 || (CPM == 0 && bx >= nA0)) { b = 1; bx -= nA0; }
     const piml_encoder_branch J = b ? F.A.br[1] : F.A.br[0];
-    const int nwg = F.nA[b];
+    const int nwg = b ? nA1 : nA0;
+    constexpr bool cp = CPM == 2;                              // this workgroup's tiles are compact
+    const bool cpe = cp && nemp > 0;                           // ... and it has a share of the agents without a neighbour
     const unsigned R = (unsigned)J.rows;                      // rows < 2^22 (checked on the host): byte offsets fit 32 bits
     const unsigned IN = __builtin_amdgcn_readfirstlane((unsigned)J.in_dim), K = __builtin_amdgcn_readfirstlane((unsigned)J.k);
     const unsigned kmagic = __builtin_amdgcn_readfirstlane((unsigned)((0x100000000ull + K - 1) / K));      // row / K == umulhi(row, kmagic)
-    const int ntiles = (int)((R + 31) >> 5);
+    const int ntiles = cp ? ctiles : (int)((R + 31) >> 5);
     const int nit = bx < ntiles ? (ntiles - bx + nwg - 1) / nwg : 0;      // tiles of this workgroup: bx, bx + nwg, ...
     float* P = J.partials + (size_t)bx * F5_PART1;
     constexpr int NS = INC == 6 ? 3 : 4;                      // column pairs of x
@@ -160,6 +180,8 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
     const __amdgpu_buffer_rsrc_t rs_x = rsrc(J.x, R * IN * 4);
     const __amdgpu_buffer_rsrc_t rs_mk = rsrc(J.relu_mask, (unsigned)ntiles * 1024);
     const __amdgpu_buffer_rsrc_t rs_gx = rsrc(J.g_x, GX ? R * IN * 4 : 0u);
+    const unsigned cS = CP ? 32u / K : 1u;                     // agents of a compact tile
+    const __amdgpu_buffer_rsrc_t rs_pl = rsrc(CP ? plan + CP_LISTS : nullptr, CP ? (unsigned)nne * 4u : 0u);      // agent_of
     auto ld1 = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned voff, unsigned soff) {
         return (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)voff, (int)soff, 0);
     };
@@ -185,7 +207,7 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
             const unsigned rem = (unsigned)tid >> 5, hh = ((unsigned)tid >> 4) & 1u, r = (unsigned)tid & 15u;
             reinterpret_cast<unsigned*>(smem + F5_TAB)[tid] = ((rem + 4u * hh + (unsigned)f5_rho((int)r)) / K) * (EH * 4);
         }
-        if (tid < 256) reinterpret_cast<float4*>(smem + F5_W1)[tid] = make_float4(0.f, 0.f, 0.f, 0.f);      // (nothing reads it)
+        if (tid < 256) reinterpret_cast<float4*>(smem + F5_W1)[tid] = make_float4(0.f, 0.f, 0.f, 0.f);      // (read only in the compact copy, behind crew B's S)
     }
 
     if (crew == 0) {
@@ -234,7 +256,26 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
         float xa[NS];
         // (every offset that must be range-checked travels in the VECTOR offset: the scalar offset of a buffer access is not part
         // of the check)
+        // compact tiles: the agent behind row n of the tile requested NEXT (-1: a dead row), fetched one request ahead
+        const unsigned slot_n = CP ? (unsigned)n / K : 0u, kn = (unsigned)n - slot_n * K;
+        int av = -1;
+        auto plan_req = [&](int tile) {
+            const unsigned idx = cS * (unsigned)tile + slot_n;
+            const bool ok = (tile < ntiles) & (slot_n < cS) & (idx < (unsigned)nne);
+            const unsigned v = ld1(rs_pl, ok ? idx * 4u : kOut, 0u);
+            av = ok ? (int)v : -1;
+        };
         auto req_g = [&](int tile) {
+            if (CP && cp) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int sa = __builtin_amdgcn_readlane(av, f5_rho(r)), sb = __builtin_amdgcn_readlane(av, f5_rho(r) + 4);
+                    const int a_ = h ? sb : sa;
+                    g2[r] = __uint_as_float(ld1(rs_gp, a_ >= 0 ? gbase + (unsigned)a_ * (EH * 4) : kOut, 0u));
+                }
+                m2 = ld1(rs_mk, tile < ntiles ? (unsigned)tile * 1024u + (128u + 2u * (unsigned)lane + (unsigned)(w >> 1)) * 4u : kOut, 0u);
+                return;
+            }
             const unsigned t32 = __builtin_amdgcn_readfirstlane((unsigned)tile * 32u);
             const unsigned a0 = __builtin_amdgcn_readfirstlane(__umulhi(t32, kmagic)), rem = t32 - a0 * K;
             const bool live = tile < ntiles;
@@ -251,14 +292,15 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
             m2 = ld1(rs_mk, live ? (unsigned)tile * 1024u + (128u + 2u * (unsigned)lane + (unsigned)(w >> 1)) * 4u : kOut, 0u);
         };
         auto req_x = [&](int tile) {
-            const unsigned row = (unsigned)tile * 32u + (unsigned)n;
-            const bool valid = (tile < ntiles) & (row < R);
+            const unsigned row = (CP && cp) ? (unsigned)av * K + kn : (unsigned)tile * 32u + (unsigned)n;
+            const bool valid = (CP && cp) ? av >= 0 : (tile < ntiles) & (row < R);
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const unsigned cx = 2u * s + h;
                 xa[s] = __uint_as_float(ld1(rs_x, (valid & (cx < IN)) ? (row * IN + cx) * 4u : kOut, 0u));
             }
             mkv = ld1(rs_mk, tile < ntiles ? (unsigned)tile * 1024u + (unsigned)(ctid & 127) * 4u : kOut, 0u);
+            if (CP && cp) plan_req(tile + nwg);               // (the requests come in tile order: bx, bx + nwg, ...)
         };
         // G2 of the requested tile = g2 * [h2 > 0] -> db2 -> bf16 pieces -> image `pm`; 16 steps (k-step s = j >> 3)
         float db1 = 0.f, db2 = 0.f;
@@ -332,6 +374,7 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
 
         F5_BARRIER();                                          // the table
         // ---- prologue: the first tile's images, the second tile's requests ----
+        if (CP && cp) plan_req(bx);
         req_g(bx);
         req_x(bx);
 #pragma unroll
@@ -417,6 +460,26 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
             f5_dec_sums(F.D, (int)blockIdx.x, (int)gridDim.x, ctid, 256);
             F5_STAMP(12);
         }
+        // compact rows: db2 += S, db1 += (W2^T S) * [h1c > 0] -- the lane half's 64 terms in order, the halves added (S: crew B's
+        // prologue left it in LDS)
+        if (CP && cpe) {
+            const float* sv = reinterpret_cast<const float*>(smem + F5_W1);
+            const float* __restrict__ wc = J.w2 + (size_t)(64 * h) * EH + 32 * w + n;      // the W2 column of the lane's feature
+            float pacc = 0.f;
+#pragma unroll 1
+            for (int q0 = 0; q0 < 64; q0 += 16) {
+                float w2c[16];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) w2c[q] = wc[(size_t)(q0 + q) * EH];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) pacc = __fmaf_rn(w2c[q], sv[64 * h + q0 + q], pacc);
+            }
+            pacc += __shfl_xor(pacc, 32, 64);
+            if (h == 0) {
+                db1 += J.packed[PACK_ZROW + 32 * w + n] > 0.f ? pacc : 0.f;
+                db2 += sv[32 * w + n];
+            }
+        }
         F5_BARRIER();                                          // (crew B's two trailing barriers)
         F5_BARRIER();
         db1 += __shfl_xor(db1, 32, 64);
@@ -464,13 +527,24 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
             for (int p = 0; p < 3; ++p) o[p] = hr[((jb_ * 2 + s_) * 3 + p) * 64];
         };
         // g_x of a finished tile: the four waves' partials, fixed order; crew thread (row ctid >> 3, column ctid & 7)
+        // compact tiles: the agent behind this thread's row (ctid >> 3) of the tile stored NEXT, fetched one store ahead
+        const unsigned slot_m = CP ? (unsigned)(ctid >> 3) / K : 0u, km = (unsigned)(ctid >> 3) - slot_m * K;
+        int bav = -1;
         auto gx_store = [&](int tile, int pm) {
-            const unsigned grow = (unsigned)tile * 32u + (unsigned)(ctid >> 3), cs = (unsigned)ctid & 7u;
+            const unsigned grow = (CP && cp) ? (unsigned)bav * K + km : (unsigned)tile * 32u + (unsigned)(ctid >> 3), cs = (unsigned)ctid & 7u;
             const float* gp = reinterpret_cast<const float*>(smem + F5_GXP + pm * F5_GXP_BYTES) + (ctid >> 3) * 16 + (ctid & 7);      // [wave][row][16]: column = slot
             const float v = ((gp[0] + gp[512]) + gp[1024]) + gp[1536];
             const bool cok = cs < IN;
             const unsigned off = (grow * IN + cs) * 4u;
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs_gx, (int)(((tile >= 0) & (tile < ntiles) & (grow < R) & cok) ? off : kOut), 0, 0);
+            const bool rok = (CP && cp) ? bav >= 0 : (tile >= 0) & (tile < ntiles) & (grow < R);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs_gx, (int)((rok & cok) ? off : kOut), 0, 0);
+            if (CP && cp) {                                    // (the stores come in tile order: bx - 2 nwg, bx - nwg, bx, ...)
+                const int nt = tile + nwg;
+                const unsigned idx = cS * (unsigned)nt + slot_m;
+                const bool ok = (nt >= 0) & (nt < ntiles) & (slot_m < cS) & (idx < (unsigned)nne);
+                const unsigned pv = ld1(rs_pl, ok ? idx * 4u : kOut, 0u);
+                bav = ok ? (int)pv : -1;
+            }
         };
         // the lagging vector work on the G1 tile `pm` and x ring slot `xslot`
         float g1[16];
@@ -544,8 +618,36 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
         };
 
         F5_BARRIER();                                          // the table (crew A's prologue barrier)
+        // compact rows, while crew A prepares the first tile: S of this workgroup's share (lane half h: every second agent of it)
+        // -> LDS (the 4096 bytes at F5_W1 nothing else uses; crew A reads it behind its loop)
+        if (CP && cpe) {
+            const int* __restrict__ eo = plan + CP_LISTS + (((int)(R / K) + 3) & ~3);
+            const float* __restrict__ gp = J.g_pooled + 32 * w + n;
+            float sacc = 0.f;
+            for (int e0 = bx + h * nwg; e0 < nemp; e0 += 16 * nwg) {
+                int ai[8];
+                float gv[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) ai[u] = eo[min(e0 + 2 * u * nwg, nemp - 1)];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) gv[u] = gp[(size_t)ai[u] * EH];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) sacc += e0 + 2 * u * nwg < nemp ? gv[u] : 0.f;
+            }
+            sacc += __shfl_xor(sacc, 32, 64);
+            if (h == 0) reinterpret_cast<float*>(smem + F5_W1)[32 * w + n] = J.packed[PACK_ZROW + EH + 32 * w + n] > 0.f ? (float)K * sacc : 0.f;
+        }
         F5_STAMP(15);
         F5_BARRIER();
+        if (CP && cpe) {                                       // dW2 starts from S (x) h1c
+            const float* sv = reinterpret_cast<const float*>(smem + F5_W1) + 32 * w + 4 * h;
+#pragma unroll
+            for (int jb = 0; jb < 4; ++jb) {
+                const float h1v = J.packed[PACK_ZROW + 32 * jb + n];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) c[jb][r] = sv[f5_rho(r)] * h1v;
+            }
+        }
         for (int it = 0; it < nit; ++it) {
             const int par = it & 1, tile = bx + it * nwg;
             F5_STAMP(0);
@@ -622,6 +724,13 @@ __global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) {
         for (int i = 0; i < 16; ++i) g_f5_stamps[(blockIdx.x * 8 + wv) * 16 + i] = st[i];
 #endif
 }
+template <bool GX, int INC>
+__global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_kernel(F5Args F) { enc_bwd_sums2_body<GX, INC, 0>(F); }
+template <bool GX>
+__global__ __launch_bounds__(F5_THREADS) void enc_bwd_sums2_cp_kernel(F5Args F) {
+    if ((int)blockIdx.x < __builtin_amdgcn_readfirstlane(F.A.br[1].plan[3])) enc_bwd_sums2_body<GX, 6, 1>(F);
+    else enc_bwd_sums2_body<GX, 6, 2>(F);
+}
 
 #ifdef PIML_F5_STAMPS
 extern "C" __attribute__((visibility("default"))) int piml_f5_stamps(unsigned long long* out) {
@@ -634,6 +743,8 @@ int enc_f5_set_attributes() {
     if (int e = set(reinterpret_cast<const void*>(enc_bwd_sums2_kernel<false, 6>))) return e;
     if (int e = set(reinterpret_cast<const void*>(enc_bwd_sums2_kernel<true, 6>))) return e;
     if (int e = set(reinterpret_cast<const void*>(enc_bwd_sums2_kernel<false, 8>))) return e;
+    if (int e = set(reinterpret_cast<const void*>(enc_bwd_sums2_cp_kernel<false>))) return e;
+    if (int e = set(reinterpret_cast<const void*>(enc_bwd_sums2_cp_kernel<true>))) return e;
     return set(reinterpret_cast<const void*>(enc_bwd_sums2_kernel<true, 8>));
 }
 
@@ -651,7 +762,10 @@ bool enc_f5_launch(const EncArgs& A, const int* nA, hipStream_t s, const DecSlot
     }
     const bool gx = A.br[0].g_x != nullptr;
     const dim3 g((unsigned)(F.nA[0] + F.nA[1])), blk(F5_THREADS);
-    if (in6) {
+    if (A.nbr > 1 && A.br[1].plan) {          // compact rows (in_dim = 6 in both branches and the grid = PIML_COMPACT_SLOTS: checked by the caller)
+        if (gx) hipLaunchKernelGGL((enc_bwd_sums2_cp_kernel<true>), g, blk, F5_LDS_LAUNCH, s, F);
+        else hipLaunchKernelGGL((enc_bwd_sums2_cp_kernel<false>), g, blk, F5_LDS_LAUNCH, s, F);
+    } else if (in6) {
         if (gx) hipLaunchKernelGGL((enc_bwd_sums2_kernel<true, 6>), g, blk, F5_LDS_LAUNCH, s, F);
         else hipLaunchKernelGGL((enc_bwd_sums2_kernel<false, 6>), g, blk, F5_LDS_LAUNCH, s, F);
     } else {

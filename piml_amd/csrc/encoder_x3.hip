@@ -631,7 +631,80 @@ __device__ __forceinline__ void store_h2_rows(const f32x16 (&a)[4], float* __res
     }
 }
 
-__global__ __launch_bounds__(ENC_THREADS) void enc_fwd_sum_x3_kernel(EncArgs A) {
+// ---- compact rows (piml_encoder_branch.nbr_idx / plan, include/piml_hip.h): branch 1 without its agents that have no neighbour ----
+// Plan (ints, global): [0] agents with a neighbour (nne) [1] agents without (nemp) [2] compact tiles [3] / [4] the backward's
+// workgroups of branch 0 / 1; agent_of[nne] at CP_LISTS, ascending; empty_of[nemp] at CP_LISTS + agents rounded up to 4, ascending.
+// A compact tile holds S = 32 / k agents: agent slot j = rows k j .. k j + k - 1, the rows behind S k are dead (zero in, summed
+// nowhere, no gradient out).  Every workgroup of the branch rebuilds the lists in LDS (the region W3 has in enc_fwd_x3_kernel:
+// this kernel stages no W3) from one index word per agent, requested in front of the weight staging; the branch's first
+// workgroup also writes them to `plan` for the launches behind this one (the launch boundary publishes them).
+constexpr int CP_LDS_CNT = X3_IMG;               // float offsets: 256 wave counts -> their exclusive scan, [256] = nne, [257] = the split key
+constexpr int CP_LDS_LIST = X3_IMG + 1024;       // u16 [agents]: agent_of from the front, empty_of from the back (reversed)
+constexpr int CP_ROUNDS0 = 8;                    // index words per thread requested before the weight staging (4096 agents)
+static_assert((CP_LDS_LIST - X3_IMG) * 4 + PIML_COMPACT_MAX_AGENTS * 2 <= (X3_FWD_F32 - X3_IMG) * 4, "the lists fit W3's region");
+static_assert(PIML_COMPACT_MAX_AGENTS <= 65536 && PIML_COMPACT_MAX_AGENTS <= 32 * ENC_THREADS, "u16 entries, a 32-bit flag word per thread");
+
+// an agent whose k rows straddle two tiles of the DENSE layout: the decoder adds its sum_b row to sum_a (the compact forward
+// stores zeros there)
+__device__ __forceinline__ bool cp_straddles(int agent, int k) { return ((agent * k) >> 5) != ((agent * k + k - 1) >> 5); }
+
+// cost model of the backward's split (cycles; DESIGN.md 4.5: a tile of the two-crew backward ~6000, the closed-form share of the
+// agents without a neighbour ~2500 + 40 per agent of the workgroup's share).  Clamped below 2^23: the caller's key is
+// cost * 256 + w0 in 32 bits (beyond ~1400 tiles per workgroup every split costs the same to it and the smallest w0 wins)
+__device__ __forceinline__ unsigned cp_split_cost(int w0, int tiles0, int tiles1, int nemp) {
+    const int w1 = PIML_COMPACT_SLOTS - w0;
+    const unsigned c0 = (unsigned)((tiles0 + w0 - 1) / w0) * 6000u;
+    const unsigned c1 = (unsigned)((tiles1 + w1 - 1) / w1) * 6000u + (nemp > 0 ? 2500u + 40u * (unsigned)((nemp + w1 - 1) / w1) : 0u);
+    return min(c0 > c1 ? c0 : c1, (1u << 23) - 1u);
+}
+
+template <int K>
+__device__ __forceinline__ void pool_rows_c(const f32x16 (&a)[4], int tile, int nne, const unsigned short* list, int lane,
+                                            float* __restrict__ sum_a, float* __restrict__ sum_b) {
+    constexpr int S = 32 / K;
+    const int i = lane & 31;
+    const bool h = lane >= 32;
+    float tot[4][S];
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk) {
+        float sum[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) sum[s] = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m0 = (r & 3) + 8 * (r >> 2), s0 = m0 / K, s1 = (m0 + 4) / K;      // the register's row in half 0 / half 1
+            if (s0 == s1) {
+                if (s0 < S) sum[s0] += a[blk][r];
+            } else {
+                if (s0 < S) sum[s0] += h ? 0.f : a[blk][r];
+                if (s1 < S) sum[s1] += h ? a[blk][r] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < S; ++s) tot[blk][s] = add_halves(sum[s]);
+    }
+    const int left = nne - S * tile;          // agents of the tile that exist (wave-uniform)
+    if (!h) {
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            if (s < left) {
+                const int ag = list[S * tile + s];
+                float* __restrict__ dst = sum_a + (size_t)ag * EH + i;
+#pragma unroll
+                for (int blk = 0; blk < 4; ++blk) dst[32 * blk] = tot[blk][s];
+                if (cp_straddles(ag, K)) {
+                    float* __restrict__ zb = sum_b + (size_t)ag * EH + i;
+#pragma unroll
+                    for (int blk = 0; blk < 4; ++blk) zb[32 * blk] = 0.f;
+                }
+            }
+        }
+    }
+}
+
+// CP: branch 1 carries nbr_idx / plan (checked by the caller: two branches, k = 2, 6 or 10, agents <= PIML_COMPACT_MAX_AGENTS)
+template <bool CP>
+__device__ __forceinline__ void enc_fwd_sum_body(const EncArgs& A) {
     extern __shared__ __align__(16) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = uniform((int)(threadIdx.x >> 6));      // in an SGPR: `tile` and every address built on it stay scalar
     const int b = (A.nbr > 1 && (int)blockIdx.x >= A.wg_split) ? 1 : 0;
@@ -640,7 +713,8 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_fwd_sum_x3_kernel(EncArgs A) 
     const int nwg = b ? (int)gridDim.x - A.wg_split : (A.nbr > 1 ? A.wg_split : (int)gridDim.x);
     const long long R = J.rows;
     const int IN = J.in_dim;
-    const long long ntiles = (R + 31) >> 5;
+    const bool cp = CP && b == 1;
+    long long ntiles = (R + 31) >> 5;
     // wave-major: tile t of the first nwg tiles goes to wave 0 of workgroup t, the next nwg tiles to the workgroups' waves 1, ... --
     // below nwg x 8 tiles the work spreads over the CUs (and over their SIMDs) before any SIMD gets a second wave (round 5: at the
     // fine-tuning loop's 488 agents the block-major order kept 31 workgroups of eight waves busy and 225 CUs idle)
@@ -648,18 +722,109 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_fwd_sum_x3_kernel(EncArgs A) 
     const long long stride = (long long)nwg * ENC_WAVES;
     if (A.zero)
         for (int e = blockIdx.x * ENC_THREADS + tid; e < A.zero_n; e += gridDim.x * ENC_THREADS) A.zero[e] = 0.f;
-    if ((long long)((int)blockIdx.x - wg0) >= ntiles) return;        // whole workgroup idle (not even wave 0 has a tile)
+    if (!cp && (long long)((int)blockIdx.x - wg0) >= ntiles) return;        // whole workgroup idle (not even wave 0 has a tile)
     const float* x3 = J.packed + PACK_F32;
     float xb[4];
     ENC_STAMP(0, false);
-    load_x(xb, J.x, first, ntiles, R, IN, lane);
+    // compact rows: the first index word of CP_ROUNDS0 agents per thread, in flight with the weights
+    const int k = J.k;
+    const int agents = CP ? (int)(R / k) : 0;
+    int iv[CP_ROUNDS0];
+    if (cp) {
+#pragma unroll
+        for (int i = 0; i < CP_ROUNDS0; ++i) {
+            const int a = i * ENC_THREADS + tid;
+            iv[i] = a < agents ? J.nbr_idx[(size_t)a * k] : -1;
+        }
+    } else {
+        load_x(xb, J.x, first, ntiles, R, IN, lane);
+    }
     stage_linear<X3_IMG>(lds, x3, tid);                                         // W2's image; W3 is not needed
     stage_linear<1024 + 384>(lds + X3_FWD_F32, J.packed + 32768, tid);
     ENC_STAMP(1, true);
-    __syncthreads();
+    int nne = 0, nemp = 0, S = 1, slot_n = 0, kn = 0;
+    bool rowlive = false;
+    const unsigned short* list = reinterpret_cast<const unsigned short*>(lds + CP_LDS_LIST);
+    if (cp) {
+        int* cnt = reinterpret_cast<int*>(lds + CP_LDS_CNT);
+        unsigned short* lw = reinterpret_cast<unsigned short*>(lds + CP_LDS_LIST);
+        const int rounds = (agents + ENC_THREADS - 1) / ENC_THREADS;       // <= 32
+        unsigned flags = 0;
+#pragma unroll
+        for (int i = 0; i < CP_ROUNDS0; ++i) flags |= (iv[i] >= 0 ? 1u : 0u) << i;
+        for (int i = CP_ROUNDS0; i < rounds; ++i) {
+            const int a = i * ENC_THREADS + tid;
+            const int v = a < agents ? J.nbr_idx[(size_t)a * k] : -1;
+            flags |= (v >= 0 ? 1u : 0u) << i;
+        }
+        for (int i = 0; i < rounds; ++i) {
+            const unsigned long long bal = __ballot((flags >> i) & 1u);
+            if (lane == 0) cnt[i * ENC_WAVES + wave] = __popcll(bal);
+        }
+        __syncthreads();                                                   // (also: the staged weights)
+        if (wave == 0) {                  // exclusive scan of the rounds x 8 counts, in (round, wave) = agent order
+            int v[4], tot = 0;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { v[u] = 4 * lane + u < rounds * ENC_WAVES ? cnt[4 * lane + u] : 0; tot += v[u]; }
+            int inc = tot;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int o = __shfl_up(inc, d, 64);
+                if (lane >= d) inc += o;
+            }
+            int ex = inc - tot;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { cnt[4 * lane + u] = ex; ex += v[u]; }
+            if (lane == 63) cnt[256] = inc;
+        }
+        __syncthreads();
+        nne = uniform(cnt[256]);
+        nemp = agents - nne;
+        for (int i = 0; i < rounds; ++i) {
+            const int a = i * ENC_THREADS + tid;
+            const unsigned bit = (flags >> i) & 1u;
+            const unsigned long long bal = __ballot(bit);
+            const int pos = cnt[i * ENC_WAVES + wave] + __popcll(bal & ((1ull << lane) - 1ull));      // agents with a neighbour in front of a
+            if (a < agents) lw[bit ? pos : agents - 1 - (a - pos)] = (unsigned short)a;
+        }
+        S = 32 / k;
+        ntiles = (nne + S - 1) / S;
+        const int n = lane & 31;
+        slot_n = n / k; kn = n - slot_n * k; rowlive = slot_n < S;
+        if ((int)blockIdx.x == wg0) {          // the backward's split: the cheapest of the 253 candidates (the smallest w0 among equals)
+            if (tid == 0) cnt[257] = 0x7fffffff;                 // (above every key: costs are clamped below 2^23)
+        }
+        __syncthreads();
+        if ((int)blockIdx.x == wg0) {
+            const int tiles0 = (int)((A.br[0].rows + 31) >> 5);
+            if (tid >= 2 && tid <= PIML_COMPACT_SLOTS - 2)
+                atomicMin(reinterpret_cast<unsigned*>(cnt + 257), cp_split_cost(tid, tiles0, (int)ntiles, nemp) * 256u + (unsigned)tid);
+            const int apad = (agents + 3) & ~3;
+            for (int c = tid; c < nne; c += ENC_THREADS) J.plan[CP_LISTS + c] = list[c];
+            for (int e = tid; e < nemp; e += ENC_THREADS) J.plan[CP_LISTS + apad + e] = list[agents - 1 - e];
+            __syncthreads();
+            if (tid == 0) {
+                const int w0 = cnt[257] & 255;
+                J.plan[0] = nne; J.plan[1] = nemp; J.plan[2] = (int)ntiles; J.plan[3] = w0; J.plan[4] = PIML_COMPACT_SLOTS - w0;
+            }
+        }
+    } else {
+        __syncthreads();
+    }
     ENC_STAMP(2, false);
-    const int k = J.k;
-    const long long agents = R / k;
+    // the input rows of compact tile t: row n of the tile = row kn of agent agent_of[S t + slot_n]
+    auto load_xc = [&](long long tile) {
+        const int idx = S * (int)tile + slot_n;
+        const bool ok = tile < ntiles && rowlive && idx < nne;
+        const long long row = ok ? (long long)list[idx] * k + kn : 0;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int c = 2 * s + (lane >> 5);
+            xb[s] = (ok && c < IN) ? J.x[row * IN + c] : 0.f;
+        }
+    };
+    if (cp) load_xc(first);
+    const long long agents_d = R / k;
     for (long long tile = first; tile < ntiles; tile += stride) {
         int lane_t = lane;
         asm volatile("" : "+v"(lane_t));
@@ -687,7 +852,8 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_fwd_sum_x3_kernel(EncArgs A) 
         ENC_STAMP(3, false);
         split_tile(a, P);
         ENC_STAMP(4, false);
-        load_x(xb, J.x, tile + stride, ntiles, R, IN, lane);       // the next tile's input row
+        if (cp) load_xc(tile + stride);
+        else load_x(xb, J.x, tile + stride, ntiles, R, IN, lane);       // the next tile's input row
         // ---- layer 2, exchanged operands: a[blk] = relu(h2)[row rho(r) + 4 h][feature 32 blk + (lane & 31)] ----
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk) {
@@ -707,11 +873,34 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_fwd_sum_x3_kernel(EncArgs A) 
         mrow[64] = make_uint2(sign_bits(a[0], a[1]), sign_bits(a[2], a[3]));      // h2: lane = feature, bits = the tile's rows
         if (J.h2) store_h2_rows<true>(a, J.h2, tile, R, lane_t);
         ENC_STAMP(6, false);
-        pool_rows_k(a, k, tile, agents, lane_t, J.sum_a, J.sum_b);
+        if (cp) {
+            if (k == 10) pool_rows_c<10>(a, (int)tile, nne, list, lane_t, J.sum_a, J.sum_b);
+            else if (k == 6) pool_rows_c<6>(a, (int)tile, nne, list, lane_t, J.sum_a, J.sum_b);
+            else pool_rows_c<2>(a, (int)tile, nne, list, lane_t, J.sum_a, J.sum_b);
+        } else {
+            pool_rows_k(a, k, tile, agents_d, lane_t, J.sum_a, J.sum_b);
+        }
         ENC_STAMP(7, false);
+    }
+    if (cp && nemp > 0) {
+        // the agents without a neighbour: sum = k h2c (pack.hpp: PACK_ZROW), written by the waves that have no tile (by all when every
+        // wave has one); lane = two features
+        const int nwav = nwg * ENC_WAVES, idle = nwav - (int)ntiles;
+        const int q = idle > 0 ? (int)first - (int)ntiles : (int)first, share = idle > 0 ? idle : nwav;
+        if (q >= 0) {
+            const float2 hc = reinterpret_cast<const float2*>(J.packed + PACK_ZROW + EH)[lane];
+            const float2 v = make_float2((float)k * hc.x, (float)k * hc.y);
+            for (int e = q; e < nemp; e += share) {
+                const int ag = list[agents - 1 - e];
+                reinterpret_cast<float2*>(J.sum_a + (size_t)ag * EH)[lane] = v;
+                if (cp_straddles(ag, k)) reinterpret_cast<float2*>(J.sum_b + (size_t)ag * EH)[lane] = make_float2(0.f, 0.f);
+            }
+        }
     }
     ENC_STAMP(8, true);
 }
+__global__ __launch_bounds__(ENC_THREADS) void enc_fwd_sum_x3_kernel(EncArgs A) { enc_fwd_sum_body<false>(A); }
+__global__ __launch_bounds__(ENC_THREADS) void enc_fwd_sum_x3_cp_kernel(EncArgs A) { enc_fwd_sum_body<true>(A); }
 
 // ---------------------------------------------------------------------------------------------------------
 // forward for FEW rows (rollouts of real clips: 100 .. 1000 agents): four waves per tile like enc_fwd_split_kernel
@@ -1290,6 +1479,7 @@ int enc_x3_set_attributes() {
         if (int e = set(f, X3_DX_LDS_BYTES)) return e;
     if (int e = set(reinterpret_cast<const void*>(enc_fwd_pool_x3_kernel), X3_FWD_LDS_BYTES)) return e;
     if (int e = set(reinterpret_cast<const void*>(enc_fwd_sum_x3_kernel), X3_FWD_LDS_BYTES)) return e;
+    if (int e = set(reinterpret_cast<const void*>(enc_fwd_sum_x3_cp_kernel), X3_FWD_LDS_BYTES)) return e;
     if (int e = set(reinterpret_cast<const void*>(enc_fwd_x3_kernel<2, true>), X3_FWD_LDS_BYTES)) return e;
     if (int e = set(reinterpret_cast<const void*>(enc_fwd_x3_kernel<1, true>), X3_FWD_LDS_BYTES)) return e;
     if (int e = set(reinterpret_cast<const void*>(enc_fwd_x3_kernel<0, true>), X3_FWD_LDS_BYTES)) return e;
@@ -1325,7 +1515,8 @@ void enc_x3_launch_fwd_pool(const EncArgs& A, int total, hipStream_t s) {
 }
 
 void enc_x3_launch_fwd_sum(const EncArgs& A, int total, hipStream_t s) {
-    hipLaunchKernelGGL(enc_fwd_sum_x3_kernel, dim3(total), dim3(ENC_THREADS), X3_FWD_LDS_BYTES, s, A);
+    if (A.nbr > 1 && A.br[1].plan) hipLaunchKernelGGL(enc_fwd_sum_x3_cp_kernel, dim3(total), dim3(ENC_THREADS), X3_FWD_LDS_BYTES, s, A);
+    else hipLaunchKernelGGL(enc_fwd_sum_x3_kernel, dim3(total), dim3(ENC_THREADS), X3_FWD_LDS_BYTES, s, A);
 }
 
 void enc_x3_launch_fwd(const EncArgs& A, int total, bool drop, hipStream_t s, bool exch) {

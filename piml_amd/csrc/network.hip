@@ -378,6 +378,8 @@ static int reduce_all(const piml_encoder_branch* enc, const piml_decoder_branch*
     for (int i = 0; i < nbr; ++i) {
         if (sums) {          // PIML_POOL_TRAIN: one layer-1 slot (dW2 | dW1 | db2 | db1) per workgroup; dW3 / db3 come from the unfold
             add(enc[i].partials, enc[i].grads, nbr == 1 ? total : (i == 0 ? w0 : total - w0), DW2_L1_LANES, DW2_L1_SPLIT, DW2_L1_OFF0, DW2_L1_OFF1);
+            // compact rows: the backward's split follows the plan (ints 3 / 4: the workgroups = slots of branch 0 / 1), so the sums read it
+            if (nbr == 2 && enc[1].plan) R.set[n - 1].dev_slots = enc[1].plan + 3 + i;
             R.unf[i] = UnfoldSet{dec[i].grads, dec[i].w1, enc[i].w3, enc[i].b3, dec[i].fold_scale, enc[i].k, dec[i].dw1_out, enc[i].grads};
             R.nunf = nbr;
         } else if (dw2) {
@@ -406,6 +408,16 @@ static int g_dec_slots_enc = !(getenv("PIML_ENC_DEC_SLOTS") && atoi(getenv("PIML
 PIML_API int piml_encoder_sums_dec_slots(int on) {
     const int old = g_dec_slots_enc;
     if (on >= 0) g_dec_slots_enc = on ? 1 : 0;
+    return old;
+}
+
+// Compact rows on the PIML_POOL_TRAIN path (piml_encoder_branch.nbr_idx / plan): what piml_amd.ops asks before it sets the pointers.
+// PIML_ENC_COMPACT=0 / 1 at load time
+static int g_compact_rows = !(getenv("PIML_ENC_COMPACT") && atoi(getenv("PIML_ENC_COMPACT")) == 0);
+
+PIML_API int piml_encoder_compact_rows(int on) {
+    const int old = g_compact_rows;
+    if (on >= 0) g_compact_rows = on ? 1 : 0;
     return old;
 }
 

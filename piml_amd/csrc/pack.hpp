@@ -37,6 +37,11 @@ constexpr int X3_LO = 32 * 64 * 4;              //  8192 dwords
 constexpr int X3_IMG = X3_HM + X3_LO;           // 24576 dwords = 96 KB
 constexpr int PACK_X3 = 4 * X3_IMG;             // W2 | W3 | W3^T | W2^T
 constexpr int PACK_FLOATS = PACK_F32 + PACK_X3;
+// behind the images: what the two layers make of an ALL-ZERO input row (compact rows, piml_encoder_branch.plan) -- h1c = relu(b1)
+// (128) | h2c = relu(W2 h1c + b2) (128; float64 sum in index order, rounded once).  Written by the network's pack (reduce.hpp:
+// zrow_block), so once per optimiser step like the images.
+constexpr int PACK_ZROW = PACK_FLOATS;
+constexpr int PACK_TOTAL = PACK_FLOATS + 2 * EH;
 
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));

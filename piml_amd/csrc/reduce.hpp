@@ -14,6 +14,8 @@ struct ReduceSet {
     const float* parts;
     float* grads;
     int slots, lanes, split, off0, off1;       // float4 geometry: sum_slots_16x16 (pack.hpp)
+    const int* dev_slots;                      // non-NULL: the slot count is read here (compact rows: the split of the encoder
+                                               // backward's workgroups between the branches follows the plan, encoder_bwd5.hip)
 };
 // PIML_POOL_TRAIN: behind the slot sums, the gradient of a decoder's FOLDED first layer W1' = s W1 W3, b1' = b1 + k s W1 b3
 // (G = d/d(W1'), g_b = d/d(b1'), both in the decoder's summed `grads`) is unfolded into the gradients of its factors:
@@ -113,7 +115,7 @@ static_assert(2 * EH * EH + 8 * EH >= (DW2_L1_OFF0 + DW2_L1_SPLIT) * 4 && 2 * EH
 __device__ __forceinline__ void reduce_block(const ReduceAll& A, int bid) {
     const int y = bid / A.gx, x = bid - y * A.gx;
     const ReduceSet S = A.set[y];
-    if (x * 16 < S.lanes) sum_slots_16x16_at(x, S.parts, S.grads, S.slots, S.lanes, S.split, S.off0, S.off1, A.accumulate != 0);
+    if (x * 16 < S.lanes) sum_slots_16x16_at(x, S.parts, S.grads, S.dev_slots ? *S.dev_slots : S.slots, S.lanes, S.split, S.off0, S.off1, A.accumulate != 0);
 }
 // workgroup `bid` of a slot-sum launch of A.unf_blocks + gx * nsets: the unfold's workgroups lead (their f64 chains are the longest)
 __device__ __forceinline__ void reduce_launch_block(const ReduceAll& A, int bid) {
@@ -211,7 +213,35 @@ struct PackWork {
 __host__ __device__ inline int pack_plain_blocks(const PackAll& A, int threads) {
     return (pack_elems_total(A) + threads * kPackPerThread - 1) / (threads * kPackPerThread);
 }
-__host__ __device__ inline int pack_blocks_total(const PackAll& A, int threads) { return pack_plain_blocks(A, threads) + fold_blocks(A, threads); }
+// the zero-row constants of encoder branch y (pack.hpp: PACK_ZROW), one workgroup each: thread (feature j, part p of threads / 128)
+// sums 128 / parts terms of W2[j] . relu(b1) in float64, sixteen loads in flight; the parts meet in LDS in order.  The whole
+// workgroup calls it (barrier); red: `threads` doubles
+__device__ __forceinline__ void zrow_block(const PackAll& A, int y, int threads, double* red) {
+    const piml_encoder_branch& J = A.enc[y];
+    const int t = (int)threadIdx.x, parts = threads >= 512 ? 4 : 2, per = EH / parts;
+    double part = 0.0;
+    if (t < parts * EH) {
+        const int j = t & (EH - 1), p = t >> 7;
+        const float* __restrict__ wr = J.w2 + (size_t)j * EH + p * per;
+        const float* __restrict__ br = J.b1 + p * per;
+        for (int q0 = 0; q0 < per; q0 += 16) {
+            float wv[16], bv[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) { wv[u] = wr[q0 + u]; bv[u] = br[q0 + u]; }
+#pragma unroll
+            for (int u = 0; u < 16; ++u) part += (double)wv[u] * (double)fmaxf(bv[u], 0.f);
+        }
+    }
+    red[t] = part;
+    __syncthreads();
+    if (t < EH) {
+        double sum = 0.0;
+        for (int p = 0; p < parts; ++p) sum += red[t + p * EH];
+        J.packed[PACK_ZROW + t] = fmaxf(J.b1[t], 0.f);
+        J.packed[PACK_ZROW + EH + t] = fmaxf((float)((double)J.b2[t] + sum), 0.f);
+    }
+}
+__host__ __device__ inline int pack_blocks_total(const PackAll& A, int threads) { return pack_plain_blocks(A, threads) + fold_blocks(A, threads) + A.nbr; }
 // red: `threads` doubles of LDS (the folded images' partial sums); the whole workgroup calls this
 __device__ __forceinline__ void pack_block(const PackAll& A, int bid, int threads, double* red) {
     const int plain = pack_plain_blocks(A, threads);
@@ -222,6 +252,8 @@ __device__ __forceinline__ void pack_block(const PackAll& A, int bid, int thread
             const int t = (bid * kPackPerThread + j) * threads + (int)threadIdx.x;
             if (t < total) pack_flat(A, t);
         }
+    } else if (bid >= plain + fold_blocks(A, threads)) {
+        zrow_block(A, bid - plain - fold_blocks(A, threads), threads, red);
     } else if (threads >= 512) {
         fold_block<8>(A, bid - plain, threads, red);
     } else {

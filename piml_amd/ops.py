@@ -5,6 +5,7 @@ the forward/backward kernels into the reference's training loops.  Every operato
 float32 tensors on the GPU and raises otherwise (no CPU fallback).
 """
 import collections
+import weakref
 import ctypes
 import math
 
@@ -79,6 +80,44 @@ def _feat_shapes(lead, n, kpe, koe, width):
 
 def _alloc_feats(lead, n, kpe, koe, width, device):
     return tuple(torch.empty(s, device=device, dtype=dt) for s, dt in zip(_feat_shapes(lead, n, kpe, koe, width), _FEAT_DTYPES))
+
+
+# ---- the neighbour indices of a feature tensor (compact rows of the fused network, include/piml_hip.h: piml_encoder_branch.nbr_idx) ----
+# The relative-feature operators return features and indices side by side, but a model is called with the features alone
+# (model(pf, of, self_features)).  Each operator notes here which index tensor belongs to the obstacle features it returned, keyed by
+# the features' address, with a weak reference to the tensor and its version counter; fused_pinnsf looks its input up and uses the
+# indices only while that tensor is alive (the address still means the same memory), is the whole input, and neither it nor the
+# index tensor has been written to by any torch operation since (views share the counter).  Anything else -- a caller that builds x itself -- finds nothing.
+_NBR_IDX = collections.OrderedDict()      # at most _NBR_IDX_MAX notes, the oldest evicted (a note keeps its index tensor alive)
+_NBR_IDX_MAX = 8
+
+
+def _note_nbr_idx(feat, idx):
+    if feat is None or idx is None or feat.numel() == 0:
+        return
+    key = feat.data_ptr()
+    _NBR_IDX.pop(key, None)
+    for dead in [k for k, (ref, _, _) in _NBR_IDX.items() if ref() is None]:
+        del _NBR_IDX[dead]
+    while len(_NBR_IDX) >= _NBR_IDX_MAX:
+        _NBR_IDX.popitem(last=False)
+    _NBR_IDX[key] = (weakref.ref(feat), idx, (feat._version, idx._version))
+
+
+def _nbr_idx_of(x):
+    """The int32 (..., N, k) index tensor noted for the features `x` (..., N, k, 6), or None."""
+    hit = _NBR_IDX.get(x.data_ptr())
+    if hit is None:
+        return None
+    feat, idx, version = hit[0](), hit[1], hit[2]
+    if feat is None:
+        del _NBR_IDX[x.data_ptr()]
+        return None
+    if feat._version != version[0] or x._version != version[0] or idx._version != version[1] or feat.data_ptr() != x.data_ptr() or tuple(feat.shape) != tuple(x.shape) or \
+            not x.is_contiguous() or tuple(idx.shape) != tuple(x.shape[:-1]) or idx.dtype != torch.int32 or not idx.is_contiguous() or \
+            idx.device != x.device:
+        return None
+    return idx
 
 
 def _fresh_zeros(shape, device):
@@ -220,6 +259,7 @@ class _RelativeFeatures(torch.autograd.Function):
         ctx.geom = (C, N, focal_begin, focal_count, out[3].shape[-1], out[4].shape[-1], lead)
         ctx.mark_non_differentiable(out[3], out[4])
         ctx.set_materialize_grads(False)     # no zero tensors for the index outputs / unused features
+        _note_nbr_idx(out[1], out[4])
         return out
 
     @staticmethod
@@ -254,6 +294,7 @@ class _RelativeFeaturesSelf(torch.autograd.Function):
         ctx.geom = (C, N, lead, tuple(desired_speed.shape))
         ctx.mark_non_differentiable(outs[3], outs[4])
         ctx.set_materialize_grads(False)
+        _note_nbr_idx(outs[1], outs[4])
         return outs
 
     @staticmethod
@@ -282,6 +323,7 @@ class _RelativeFeaturesPacked(torch.autograd.Function):
         ctx.geom = (C, N, focal_begin, focal_count, out[3].shape[-1], out[4].shape[-1], lead)
         ctx.mark_non_differentiable(out[3], out[4])
         ctx.set_materialize_grads(False)     # no zero tensors for the index outputs / unused features
+        _note_nbr_idx(out[1], out[4])
         return out
 
     @staticmethod
@@ -331,6 +373,7 @@ class _RelativeFeaturesPackedSelf(torch.autograd.Function):
         ctx.speed_shape = tuple(desired_speed.shape)
         ctx.mark_non_differentiable(outs[3], outs[4])
         ctx.set_materialize_grads(False)
+        _note_nbr_idx(outs[1], outs[4])
         return outs
 
     @staticmethod
@@ -2130,9 +2173,10 @@ ENCODER_MAX_IN = 8
 
 def _enc_branch_struct(x2, k, scale, wb, msgs, h1=None, h2=None, g_pooled=None, g_msgs=None, g2=None, g1=None,
                        g_x=None, partials=None, packed=None, grads=None, keep_bits=None, draw_p=None, relu_mask=None,
-                       sum_a=None, sum_b=None):
+                       sum_a=None, sum_b=None, nbr_idx=None, plan=None):
     B = _lib.EncoderBranch()
     B.sum_a, B.sum_b = _ptr(sum_a), _ptr(sum_b)
+    B.nbr_idx, B.plan = _ptr(nbr_idx), _ptr(plan)          # compact rows (PIML_POOL_TRAIN, branch 1)
     B.keep_bits = _ptr(keep_bits)
     if draw_p is not None:            # the forward draws the mask itself (into keep_bits) from the device's dropout state
         B.drop_state, B.drop_p = dropout_state(x2.device).data_ptr(), float(draw_p)
@@ -2663,6 +2707,15 @@ class _FusedPinnsf(torch.autograd.Function):
                     probe[b].relu_mask = 1          # (any non-NULL value: the probe looks at the configuration only)
                 msum = bool(L.piml_pinnsf_pool_msgs_ok(probe, nbr))
         ctx.sums = sums
+        # compact rows: the obstacle branch (no consumer reads its rows one by one) without its agents that have no neighbour, when the
+        # features still are what a relative-feature operator returned (_nbr_idx_of) and the library serves the shape
+        nidx, plan = None, None
+        if sums and nbr == 2 and ks[1] in (2, 6, 10) and x2s[0].shape[1] == 6 and x2s[1].shape[1] == 6 and \
+                agents <= _lib.COMPACT_MAX_AGENTS and L.piml_encoder_compact_rows(-1) and L.piml_encoder_sums_bwd(-1) == 2:      # (the plan is the two-crew backward's)
+            nidx = _nbr_idx_of(xs[1]) if xs[1].data_ptr() == x2s[1].data_ptr() else None
+            if nidx is not None:
+                plan = torch.empty(16 + 2 * ((agents + 3) // 4 * 4), device=dev, dtype=torch.int32)
+        ctx.plan = plan
         sum_a, sum_b, masks = [None] * nbr, [None] * nbr, [None] * nbr
         for b in range(nbr):
             R = x2s[b].shape[0]
@@ -2676,7 +2729,10 @@ class _FusedPinnsf(torch.autograd.Function):
                 # collision head reads them (branch 0)
                 msgs.append(None)
                 sum_a[b], sum_b[b] = torch.empty(agents, H, **opt), torch.empty(agents, H, **opt)
-                masks[b] = torch.empty(2 * ((R + 31) // 32), H, **opt)
+                tiles = (R + 31) // 32
+                if plan is not None and b == 1:              # (a compact tile holds 32 // k agents: more tiles when nearly all have a neighbour)
+                    tiles = max(tiles, -(-agents // (32 // ks[b])))
+                masks[b] = torch.empty(2 * tiles, H, **opt)
                 h2s.append(torch.empty(R, H, **opt) if (nhead and b == 0) else None)
             else:
                 msgs.append(torch.empty(R, H, **opt))
@@ -2697,7 +2753,8 @@ class _FusedPinnsf(torch.autograd.Function):
         keeps, draws = zip(*[_resolve_keep(keeps[b], x2s[b].shape[0], H, dev) for b in range(nbr)])
         earr = (_lib.EncoderBranch * nbr)(*[_enc_branch_struct(x2s[b], ks[b], scales[b], ewb[b], msgs[b], h1s[b], h2s[b],
                                                                packed=epack[b], keep_bits=keeps[b], draw_p=draws[b],
-                                                               relu_mask=masks[b], sum_a=sum_a[b], sum_b=sum_b[b])
+                                                               relu_mask=masks[b], sum_a=sum_a[b], sum_b=sum_b[b],
+                                                               nbr_idx=nidx if b == 1 else None, plan=plan if b == 1 else None)
                                             for b in range(nbr)])
         # (sums: the decoder reads the first parts from `pooled` and leaves the completed sums there)
         pooled = sum_a if (sums or msum) else [torch.empty(agents, H, **opt) for _ in range(nbr)]      # always: the decoder kernel reads it
@@ -2892,11 +2949,17 @@ def _backward_sums(ctx, g_acc, g_coll, grads, x2s, masks, pooled, dh1, dd2, ewb,
         if len({g is None for g in gxs}) > 1:              # one kernel variant per launch: both inputs' gradients or neither
             gxs = [g if g is not None else torch.empty(x2s[b].shape, **opt) for b, g in enumerate(gxs)]
         earr = (_lib.EncoderBranch * nbr)(*[_enc_branch_struct(x2s[b], ks[b], scales[b], ewb[b], None, None, None, g_pooled[b], None,
-                                                               None, None, gxs[b], packed=epack[b], relu_mask=masks[b])
+                                                               None, None, gxs[b], packed=epack[b], relu_mask=masks[b],
+                                                               plan=ctx.plan if b == 1 else None)
                                             for b in range(nbr)])
         w0 = ctypes.c_int(0)
         total = L.piml_encoder_workgroups(earr, nbr, ctypes.byref(w0))
         slots = [w0.value, total - w0.value] if nbr == 2 else [total]
+        if ctx.plan is not None:                           # compact rows: the split follows the data (the plan), either branch may get most
+            slots = [_lib.COMPACT_SLOTS] * nbr
+            # (and the backward writes no g_x row of an agent without a neighbour: those rows of gxs[1] stay uninitialised.  Their
+            # indices are negative, so the relative-feature backward -- the consumer of that gradient wherever compact rows are chosen,
+            # _nbr_idx_of -- does not use them; a hook or retain_grad on the obstacle features sees them as they are)
         parts = [torch.empty(n, part1, **opt) for n in slots]
         # weight gradients: fresh buffers handed to autograd, or -- inside ParamGradSink.step() -- the sink's persistent ones, summed
         # across the backward passes of the step by the slot-sum launch itself (the folded layers' gradients accumulate FOLDED and
@@ -2936,7 +2999,7 @@ def _backward_sums(ctx, g_acc, g_coll, grads, x2s, masks, pooled, dh1, dd2, ewb,
         darr = (_lib.DecoderBranch * nbr)(*dstructs)
         if _defer_slot_sums([ctx.params[PER * b + jx] for b in range(nbr) for jx in range(1, 13)], sink, dev):
             flags |= _lib.DEFER_SLOT_SUMS
-            _defer_keep(parts, dparts, dflats, flats, dw1)
+            _defer_keep(parts, dparts, dflats, flats, dw1, ctx.plan)
         _lib.check(L.piml_pinnsf_bwd(earr, darr, nbr, _ptr(ga), _ptr(sf), float(tau), _ptr(g_self), flags, _stream()), 'piml_pinnsf_bwd')
         if want_self:
             grads[_FusedPinnsf.SELF] = g_self.view(sf_shape)
