@@ -669,6 +669,49 @@ int piml_obstacle_stats(const float* P, const float* V, const float* M, const in
                         long long workspace_bytes, void* stream);
 
 /*
+ * Measurement-line statistics (linestats.hip), S members in one call against L shared lines: crossings, the
+ * N-t curve, crossing speed, lateral profile and per track the first crossing.  P (S, T, N, 2), M (S, T, N), n_active and
+ * the frames [t0, t1) as for piml_track_stats (velocities are not an input; slot n of a member is one agent for the whole
+ * run); lines (L, 4) float32, each row (ax, ay, bx, by).  Agent i takes part at (s, t) when M == 1 and both coordinates of
+ * P are finite and below 65536 in magnitude (slots at or past n_active[s] are not swept).  A step (i, t) exists when i takes
+ * part at t and t + 1 and t + 1 < T' (T' = t1 - t0; no step spans a gap).  float32 (true divisions and square roots, no
+ * contraction), Q = 2^20.  Per line, d = b - a, len2 = dx dx + dy dy, side(p) = dx (py - ay) - dy (px - ax); for a step
+ * s0 = side(p(t)), s1 = side(p(t+1)):
+ *   direction 0 when s0 < 0 and s1 >= 0, direction 1 when s0 >= 0 and s1 < 0 (a point on the line is on the left side);
+ *   f = s0 / (s0 - s1), u = p(t+1) - p(t), c = p(t) + f u, w = ((cx - ax) dx + (cy - ay) dy) / len2;
+ *   a crossing when 0 <= w < 1 (half-open: collinear lines sharing an end point count a crossing once between them);
+ *   vn = |s1 - s0| / sqrt(len2) / dt; tc = t Q + llrintf(f Q).
+ * Outputs, int64:
+ *   cross (S, L, 2): crossings per direction; nt (S, L, 2, T'): crossings whose step starts at frame t (entry T' - 1 is 0);
+ *   speed (S, L, 2, v_bins + 1): by min(floor(vn / v_bin), v_bins) (the last bin is open); speed_sum (S, L, 2): the sum of
+ *     llrintf(vn Q) over the crossings with vn < v_bin * v_bins;
+ *   profile (S, L, 2, w_bins): by min(floor(w w_bins), w_bins - 1);
+ *   steps (S): the steps swept; trk_steps (S, N): the steps of each track;
+ *   trk_count (S, L, N): the track's crossings of the line, both directions; trk_first (S, L, N): its smallest tc (-1
+ *     without a crossing); trk_dir (S, L, N): the direction of that crossing (-1 without one): the minimum is taken over
+ *     2 tc + dir, so time and direction come from the same step and direction 0 is the first of two at the same tc.
+ * A line the host has not checked (a == b, non-finite) counts no crossing.  One lane per track over PIML_LINE_CHUNK steps,
+ * the lanes of a workgroup on neighbouring slots; the lines are held in LDS; every row takes integer atomics directly.
+ * workspace: at least piml_line_stats_workspace_bytes(S, N, L, T', v_bins, w_bins) =
+ * S (2 L (T' + v_bins + w_bins + 3) + 1 + N + 2 L N) 8 bytes (-1 for negative arguments).  One memset and two launches (one
+ * when T' == 1), no host synchronisation (capturable).  Deterministic: integer outputs only, added with integer atomics;
+ * member s's results are bitwise those of an S = 1 call on member s alone.  S, T', N or L == 0: success, nothing is done
+ * (the outputs are left alone).
+ * hipErrorInvalidValue, before any HIP call: S, T or N < 0, N > 65536, L outside 0..PIML_LINE_MAX_L, frames outside [0, T]
+ * or t1 < t0, T' > 2^25 (tc and the packed word stay far below 2^63), dt or v_bin <= 0 or not finite, v_bins or w_bins outside
+ * 1..256, v_bin v_bins Q N T' >= 2^63 (speed_sum); then, unless there is nothing to do, a NULL input, output or workspace,
+ * or a workspace too small.
+ */
+#define PIML_LINE_MAX_L 16
+#define PIML_LINE_CHUNK 32
+long long piml_line_stats_workspace_bytes(int S, int N, int L, int frames, int v_bins, int w_bins);
+int piml_line_stats(const float* P, const float* M, const int* n_active, int S, int T, int N, int t0, int t1,
+                    const float* lines, int L, float dt, float v_bin, int v_bins, int w_bins, long long* cross, long long* nt,
+                    long long* speed, long long* speed_sum, long long* profile, long long* steps, long long* trk_steps,
+                    long long* trk_count, long long* trk_first, long long* trk_dir, void* workspace,
+                    long long workspace_bytes, void* stream);
+
+/*
  * utils.calc_acceleration (src/utils/utils.py:31-100): version 0/1/2 = 'v0'/'v1'/'v2' with the
  * caller-supplied constants (A, B, C, D, theta [rad]); rows of >= 2 floats -> acc (rows, 2).
  */

@@ -147,6 +147,9 @@ SIGNATURES = {
     'piml_obstacle_stats_workspace_bytes': [_i, _i, _i, _i],
     'piml_obstacle_stats': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _f, _f, _f, _i, _f, _f, _f, _f, _f, _i, _f, _i,
                             _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _ll, _p],
+    'piml_line_stats_workspace_bytes': [_i, _i, _i, _i, _i, _i],
+    'piml_line_stats': [_p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _f, _f, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _ll,
+                        _p],
     'piml_calc_acceleration': [_p, _z, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p],
     'piml_rollout_step': [_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p,
                           _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p],
@@ -325,6 +328,7 @@ def lib():
         L.piml_flow_stats_workspace_bytes.restype = _ll
         L.piml_track_stats_workspace_bytes.restype = _ll
         L.piml_obstacle_stats_workspace_bytes.restype = _ll
+        L.piml_line_stats_workspace_bytes.restype = _ll
         L.piml_mlapm_law_table_bytes.restype = _ll
         L.piml_error_string.argtypes = [_i]
         L.piml_error_string.restype = ctypes.c_char_p

@@ -364,3 +364,62 @@ def obstacle_stats_frames(P, V, M, obstacles, dt=0.08, radius=0.25, hit_radius=0
                                          *(_ptr(out[k]) for k in OBS_TRACK_ROWS), _ptr(ws), ws.numel(), _stream()),
                    'piml_obstacle_stats')
     return out
+
+
+LINE_MAX_L = 16               # piml_line_stats: its limits on the lines (PIML_LINE_MAX_L), the slots per frame, v_bins /
+LINE_MAX_N = 65536            # w_bins and the frames per window, and the steps a lane sweeps per work item
+LINE_MAX_BINS = 256
+LINE_MAX_FRAMES = 1 << 25
+LINE_CHUNK = 32
+LINE_Q = 1 << 20              # the fixed-point scale of speed_sum and of the crossing times trk_first
+LINE_DIR_ROWS = ('cross', 'speed_sum')
+LINE_TRACK_ROWS = ('trk_count', 'trk_first', 'trk_dir')
+LINE_ROWS = ('cross', 'nt', 'speed', 'speed_sum', 'profile', 'steps', 'trk_steps') + LINE_TRACK_ROWS
+
+
+def line_stats_frames(P, M, lines, dt=0.08, v_bin=0.1, v_bins=40, w_bins=16, frames=None, n_active=None):
+    """The device half of piml_amd.linestats.line_stats (piml_line_stats): P (S, T, N, 2), M (S, T, N) and
+    lines (L, 4) float32 GPU tensors (rows ax, ay, bx, by; their values are the caller's to check: a bad row counts no
+    crossing), frames (a, b) or None, n_active (S) int32 GPU tensor or None.  Returns a dict of int64 GPU tensors -- cross,
+    speed_sum (S, L, 2); nt (S, L, 2, T'); speed (S, L, 2, v_bins + 1); profile (S, L, 2, w_bins); steps (S); trk_steps (S, N);
+    trk_count, trk_first, trk_dir (S, L, N) -- with no host synchronisation (capturable in a graph)."""
+    P, M, lines = _gpu_f32('P', P), _gpu_f32('M', M), _gpu_f32('lines', lines)
+    if P.dim() != 4 or P.shape[-1] != 2 or M.shape != P.shape[:3]:
+        raise ValueError(f'expected P (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(M.shape)}')
+    if lines.dim() != 2 or lines.shape[-1] != 4:
+        raise ValueError(f'lines: expected (L, 4), got {tuple(lines.shape)}')
+    dev = P.device
+    if M.device != dev or lines.device != dev:
+        raise ValueError('P, M and lines on different devices')
+    S, T, N = P.shape[:3]
+    NL = lines.shape[0]
+    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    VB, WB, Tp = int(v_bins), int(w_bins), max(b - a, 0)
+    if n_active is not None:
+        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
+                or tuple(n_active.shape) != (S,):
+            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
+        n_active = n_active.contiguous()
+    # a call with nothing to do leaves its outputs alone: hand it the values of an empty problem
+    idle = S * Tp * N * NL == 0
+    new = torch.zeros if idle else torch.empty
+    i64 = dict(device=dev, dtype=torch.int64)
+    out = {k: new(S, NL, 2, **i64) for k in LINE_DIR_ROWS}
+    out['nt'] = new(S, NL, 2, Tp, **i64)
+    out['speed'] = new(S, NL, 2, max(VB, 0) + 1, **i64)
+    out['profile'] = new(S, NL, 2, max(WB, 0), **i64)
+    out['steps'] = new(S, **i64)
+    out['trk_steps'] = new(S, N, **i64)
+    out.update({k: new(S, NL, N, **i64) for k in LINE_TRACK_ROWS})
+    if idle:
+        out['trk_first'] -= 1
+        out['trk_dir'] -= 1
+    L = _lib.lib()
+    ws_bytes = L.piml_line_stats_workspace_bytes(S, N, NL, Tp, max(VB, 0), max(WB, 0))
+    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        _lib.check(L.piml_line_stats(_ptr(P), _ptr(M), _ptr(n_active), S, T, N, a, b, _ptr(lines), NL, float(dt),
+                                     float(v_bin), VB, WB, *(_ptr(out[k]) for k in LINE_ROWS), _ptr(ws), ws.numel(),
+                                     _stream()),
+                   'piml_line_stats')
+    return out

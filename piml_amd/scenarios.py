@@ -397,6 +397,13 @@ class ScenarioResult(types.SimpleNamespace):
         return obstacle_stats(self.position, self.velocity, self.mask_p, _scene_obstacles(self), n_active=[self.num_agents],
                               **kw)
 
+    def line_stats(self, lines, **kw):
+        """piml_amd.linestats.line_stats of the run against the measurement lines `lines` (L, 4), rows (ax, ay, bx, by)
+        (positions only, dt = time_unit; slots past num_agents not swept)."""
+        from .linestats import line_stats
+        kw.setdefault('dt', float(self.time_unit))
+        return line_stats(self.position, self.mask_p, lines, n_active=[self.num_agents], **kw)
+
 
 class ScenarioEnsemble(types.SimpleNamespace):
     """What `BaseSimulator.simulate_ensemble` returns: the ScenarioResult fields with a leading member axis -- position /
@@ -462,6 +469,15 @@ class ScenarioEnsemble(types.SimpleNamespace):
         return obstacle_stats(self.position, self.velocity, self.mask_p, _scene_obstacles(self),
                               n_active=[min(int(n), cap) for n in self.spawned], **kw)
 
+    def line_stats(self, lines, **kw):
+        """piml_amd.linestats.line_stats of every member in one call against the measurement lines `lines` (dt = time_unit;
+        member m's slots past its num_agents not swept): member m's statistics are bitwise those of
+        member(m).line_stats(lines, **kw)."""
+        from .linestats import line_stats
+        cap = self.position.shape[2]
+        kw.setdefault('dt', float(self.time_unit))
+        return line_stats(self.position, self.mask_p, lines, n_active=[min(int(n), cap) for n in self.spawned], **kw)
+
     def collision_counts(self, threshold):
         """Per-member totals of collision_count(member.position, threshold, reduction='sum'): a list of S floats, one
         read-back.  One ops.collision_counts call per member: on a stack of more than 25 frames the count applies the
@@ -475,7 +491,7 @@ class ScenarioSweep(ScenarioEnsemble):
     """What `MLAPM.simulate_sweep` returns: a ScenarioEnsemble of n_candidates * seeds_per_candidate members laid out
     candidate-major -- member c * seeds_per_candidate + k ran law params[c] under the k-th seed -- plus params (the
     candidates' dicts), n_candidates and seeds_per_candidate.  `seeds` lists every member's seed (the seed list once per
-    candidate); crowd_stats / pair_stats / flow_stats / track_stats / obstacle_stats compute all members in one call, and `.select(sweep.members_of(c)).pooled()` of
+    candidate); crowd_stats / pair_stats / flow_stats / track_stats / obstacle_stats / line_stats compute all members in one call, and `.select(sweep.members_of(c)).pooled()` of
     the result pools one candidate."""
 
     def members_of(self, c):

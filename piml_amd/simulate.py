@@ -15,6 +15,7 @@ reads.
     python -m piml_amd.simulate --law mlapm --scenario gc --seeds 0:32 --obstacle-stats walls.json   (obstacle statistics)
     python -m piml_amd.simulate --law mlapm --params p.json --seeds 0:32 --obstacle-stats walls.json
                                 (p.json with Aw, Bw [, wall_cutoff]: the law with a wall term, e.g. Aw = 50, Bw = -5)
+    python -m piml_amd.simulate --law mlapm --scenario gc --seeds 0:32 --line-stats gates.json --lines '0,2,30,2;2,5,2,17'
     python -m piml_amd.simulate --law mlapm --params-sweep a.json b.json --seeds 0:8 --stats sweep.json
                                 (one law per file, every law on every seed in ONE ensemble run; statistics per candidate)
 
@@ -43,7 +44,7 @@ def get_args(argv=None):
                         "term's Aw, Bw, wall_cutoff); default main_mlapm.py's constants, version GC, no wall term")
     p.add_argument('--params-sweep', dest='params_sweep', type=str, nargs='+', default=None,
                    help='--law mlapm with --seeds: several --params files, every law on every seed in one ensemble run '
-                        "(MLAPM.simulate_sweep); --stats / --pair-stats / --flow-stats / --track-stats / --obstacle-stats then hold one entry per candidate, pooled over its "
+                        "(MLAPM.simulate_sweep); --stats / --pair-stats / --flow-stats / --track-stats / --obstacle-stats / --line-stats then hold one entry per candidate, pooled over its "
                         "seeds, and --out must contain '{candidate}' and '{seed}'")
     p.add_argument('--mlapm_radius', type=float, default=0.3,
                    help="--law mlapm: MLAPM's UCY collision radius (not the scene's arrival radius)")
@@ -85,6 +86,11 @@ def get_args(argv=None):
                    help='write the obstacle statistics (piml_amd.obstaclestats: wall clearance, contacts, crossings, time '
                         "to wall; defaults, no box, the scene's obstacles) of the run or ensemble as JSON to this path "
                         'instead of writing clips')
+    p.add_argument('--line-stats', dest='line_stats', type=str, default=None,
+                   help='write the measurement-line statistics (piml_amd.linestats: flow, headway, crossing speed, travel '
+                        'time; defaults, dt = the time unit) of the run or ensemble across --lines as JSON to this path '
+                        'instead of writing clips')
+    p.add_argument('--lines', type=str, default=None, help="--line-stats: the measurement lines, 'ax,ay,bx,by;ax,ay,bx,by;...'")
     p.add_argument('--time_unit', type=float, default=0.08)
     p.add_argument('--uniform_desired_speed', action=argparse.BooleanOptionalAction, default=None,
                    help="uniform desired speed (default: the scene's own; GC and the crosswalk no, the others yes)")
@@ -99,6 +105,16 @@ def get_args(argv=None):
         own.flow_axis = parse_axis(own.flow_axis)
     except ValueError as ex:
         p.error(f'--flow-axis: {ex}')
+    if (own.line_stats is None) != (own.lines is None):
+        p.error('--line-stats needs --lines, and --lines feeds --line-stats only')
+    if own.lines is not None:
+        try:
+            from .linestats import parse_lines
+            own.lines = parse_lines(own.lines)
+            if isinstance(own.lines, str):
+                raise ValueError("'auto' needs a box: give the lines")
+        except ValueError as ex:
+            p.error(f'--lines: {ex}')
     if own.seeds is not None:
         try:
             own.seeds = parse_seeds(own.seeds)
@@ -265,7 +281,7 @@ def _clip_scene(own):
 
 
 def _stats_path(own):
-    return ', '.join(p for p in (own.stats, own.pair_stats, own.flow_stats, own.track_stats, own.obstacle_stats)
+    return ', '.join(p for p in (own.stats, own.pair_stats, own.flow_stats, own.track_stats, own.obstacle_stats, own.line_stats)
                      if p is not None)
 
 
@@ -274,8 +290,8 @@ def _crowd_kw(own):
 
 
 def _stats(res, own):
-    """--stats / --pair-stats / --flow-stats / --track-stats / --obstacle-stats: the CrowdStats / PairStats / FlowStats /
-    TrackStats / ObstacleStats JSON of a run or an ensemble (one call for every member)."""
+    """--stats / --pair-stats / --flow-stats / --track-stats / --obstacle-stats / --line-stats: the CrowdStats / PairStats /
+    FlowStats / TrackStats / ObstacleStats / LineStats JSON of a run or an ensemble (one call for every member)."""
     if own.stats is not None:
         from . import crowdstats
         st = res.crowd_stats(**_crowd_kw(own))
@@ -304,6 +320,11 @@ def _stats(res, own):
             sys.exit(f'--obstacle-stats: {ex}')
         os_.to_json(own.obstacle_stats)
         obstaclestats.print_obstacle_stats(os_, 'simulate --obstacle-stats')
+    if own.line_stats is not None:
+        from . import linestats
+        ls = res.line_stats(own.lines)
+        ls.to_json(own.line_stats)
+        linestats.print_line_stats(ls, 'simulate --line-stats')
 
 
 def _sweep(sim, scenario, own, run_kw):
@@ -346,6 +367,12 @@ def _sweep(sim, scenario, own, run_kw):
         entries = [{'params': sw.params[c], 'file': own.params_sweep[c], 'stats': os_.select(g).pooled().to_json()}
                    for c, g in enumerate(groups)]
         with open(own.obstacle_stats, 'w') as fh:
+            json.dump({'seeds': own.seeds, 'candidates': entries}, fh)
+    if own.line_stats is not None:
+        ls = sw.line_stats(own.lines)
+        entries = [{'params': sw.params[c], 'file': own.params_sweep[c], 'stats': ls.select(g).pooled().to_json()}
+                   for c, g in enumerate(groups)]
+        with open(own.line_stats, 'w') as fh:
             json.dump({'seeds': own.seeds, 'candidates': entries}, fh)
     where = _stats_path(own)
     if not where:
