@@ -712,6 +712,51 @@ int piml_line_stats(const float* P, const float* M, const int* n_active, int S, 
                     long long workspace_bytes, void* stream);
 
 /*
+ * Group statistics (groupstats.hip), S members in one call: who walks with whom.  P (S, T, N, 2), M (S, T, N),
+ * n_active and the frames [t0, t1) as for piml_line_stats (velocities are not an input; slot n of a member is one agent for
+ * the whole run).  Agent i takes part at (s, t) when M == 1, both coordinates of P are finite and below 65536 in magnitude
+ * and i < n_active[s].  A step (i, t) exists when i takes part at t and t + 1 and t + 1 < T' (T' = t1 - t0); its
+ * displacement is u_i(t) = p_i(t+1) - p_i(t), metres per frame.  float32 with separately rounded products, true square
+ * roots and divisions and no contraction, Q = 2^20.  The caller makes each threshold once in float64 and rounds it once:
+ * r2 = radius^2, dv2 = (dv_max dt)^2, vm2 = (v_min dt)^2.  A pair-frame (i, j, t), i < j, exists when both steps exist at
+ * t; with e = p_j(t) - p_i(t) and g = u_j(t) - u_i(t) it is together when ex ex + ey ey < r2, gx gx + gy gy < dv2,
+ * |u_i|^2 >= vm2 and |u_j|^2 >= vm2 (each sum the x term plus the y term).  co[i, j] counts the pair-frames, near[i, j] the
+ * together ones; a pair is a candidate when near >= min_frames.
+ *
+ * piml_group_pairs (pass 1): edges (S, max_edges, 4) int32 rows (i, j, co, near), one per candidate, in any order; n_edges
+ * (S) int32 the true number of candidates, also when it exceeds max_edges (rows past max_edges are not written; rows past
+ * n_edges are left alone); trk_steps, trk_path (S, N) int64 the steps of each track and the sum of llrintf(sqrtf(|u|^2) Q)
+ * over them; pairs, together (S) int64 the pair-frames swept and the together ones.  One workgroup per (member, focal
+ * track), the focal staged in LDS in tiles of PIML_GROUP_TILE frames, one lane per partner, one integer atomic per wave to
+ * append.  Three memsets and one launch, no host synchronisation (capturable).  The cost grows as S N^2 times the frames
+ * present.
+ *
+ * piml_group_members (pass 2): links (K, 3) int32 rows (member, i, j); over every together pair-frame of a link, with
+ * d2 = ex ex + ey ey, d = sqrtf(d2), w = u_i + u_j, w2 = wx wx + wy wy:
+ *   dist (S, r_bins + 1): by min(floor(d / r_bin), r_bins); dist_sum (S): the sum of llrintf(d Q);
+ *   abreast (S, a_bins): by min(floor(c a_bins), a_bins - 1), c = fabsf(ex wx + ey wy) / (sqrtf(d2) sqrtf(w2)) (bin 0: side
+ *     by side; the last bin: in file); abreast_skipped (S): the pair-frames with d2 == 0 or w2 == 0 instead;
+ *   link_frames (S): the together pair-frames of the member's links.
+ * All int64; a member without links gives zeros; a link with an index out of range is skipped.  Five memsets and one
+ * launch (none for K == 0 or T' == 1).
+ *
+ * Deterministic: integer outputs, integer atomics; member s's results are bitwise those of an S = 1 call on member s alone
+ * (its edge rows up to their order).  S, T' or N == 0: success, nothing is done (the outputs are left alone).
+ * hipErrorInvalidValue, before any HIP call: S, T or N < 0, N > 65536, frames outside [0, T] or t1 < t0, T' > 2^25, r2 or
+ * dv2 <= 0 or not finite, vm2 < 0 or not finite, sqrt(r2) Q N^2 / 2 T' >= 2^63 (dist_sum), min_frames < 1, max_edges < 0,
+ * n_links < 0, r_bin <= 0 or not finite, r_bins or a_bins outside 1..256; then, unless there is nothing to do, a NULL
+ * input or output (edges may be NULL when max_edges == 0, links when K == 0).
+ */
+#define PIML_GROUP_TILE 256
+int piml_group_pairs(const float* P, const float* M, const int* n_active, int S, int T, int N, int t0, int t1, float r2,
+                     float dv2, float vm2, int min_frames, int max_edges, int* edges, int* n_edges, long long* trk_steps,
+                     long long* trk_path, long long* pairs, long long* together, void* stream);
+int piml_group_members(const float* P, const float* M, int S, int T, int N, int t0, int t1, const int* links, int n_links,
+                       float r2, float dv2, float vm2, float r_bin, int r_bins, int a_bins, long long* dist,
+                       long long* dist_sum, long long* abreast, long long* abreast_skipped, long long* link_frames,
+                       void* stream);
+
+/*
  * utils.calc_acceleration (src/utils/utils.py:31-100): version 0/1/2 = 'v0'/'v1'/'v2' with the
  * caller-supplied constants (A, B, C, D, theta [rad]); rows of >= 2 floats -> acc (rows, 2).
  */

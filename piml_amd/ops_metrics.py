@@ -3,6 +3,9 @@
 Entropic OT and multi-kernel MMD of point clouds, every frame in one launch.  Like every operator of piml_amd they
 require float32 GPU tensors and raise PimlHipError on CPU ones; functions/metrics.py builds the reference's interface on
 them."""
+import math
+
+import numpy as np
 import torch
 
 from . import _lib
@@ -422,4 +425,117 @@ def line_stats_frames(P, M, lines, dt=0.08, v_bin=0.1, v_bins=40, w_bins=16, fra
                                      float(v_bin), VB, WB, *(_ptr(out[k]) for k in LINE_ROWS), _ptr(ws), ws.numel(),
                                      _stream()),
                    'piml_line_stats')
+    return out
+
+
+GROUP_MAX_N = 65536           # piml_group_pairs / piml_group_members: their limits on the slots per frame, the frames per
+GROUP_MAX_FRAMES = 1 << 25    # window, r_bins / a_bins and the default cap on the edge rows per member, the focal frames
+GROUP_MAX_BINS = 256          # staged per LDS tile, the fixed-point scale of trk_path and dist_sum, the unit of `share`
+GROUP_MAX_EDGES = 1 << 20
+GROUP_TILE = 256
+GROUP_Q = 1 << 20
+GROUP_SHARE_UNIT = 1024
+GROUP_PAIR_ROWS = ('trk_steps', 'trk_path', 'pairs', 'together')
+GROUP_MEMBER_ROWS = ('dist', 'dist_sum', 'abreast', 'abreast_skipped', 'link_frames')
+
+
+def group_thresholds(dt, radius, dv_max, v_min, min_time, share):
+    """What the kernels and a restatement receive: (r2, dv2, vm2) = float32 of radius^2, (dv_max dt)^2, (v_min dt)^2, each made
+    once in float64 and rounded once; min_frames = max(1, ceil(min_time / dt)); share_q = round(share * 1024)."""
+    dt, radius, dv_max, v_min = float(dt), float(radius), float(dv_max), float(v_min)
+    r2, dv2, vm2 = (float(np.float32(x)) for x in (radius * radius, (dv_max * dt) ** 2, (v_min * dt) ** 2))
+    return r2, dv2, vm2, max(1, math.ceil(float(min_time) / dt)), int(round(float(share) * GROUP_SHARE_UNIT))
+
+
+def _group_setup(P, M, frames, n_active):
+    P, M = _gpu_f32('P', P), _gpu_f32('M', M)
+    if P.dim() != 4 or P.shape[-1] != 2 or M.shape != P.shape[:3]:
+        raise ValueError(f'expected P (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(M.shape)}')
+    dev = P.device
+    if M.device != dev:
+        raise ValueError('P and M on different devices')
+    S, T, N = P.shape[:3]
+    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    if n_active is not None:
+        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
+                or tuple(n_active.shape) != (S,):
+            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
+        n_active = n_active.contiguous()
+    return P, M, n_active, a, b
+
+
+def group_pairs_frames(P, M, r2, dv2, vm2, min_frames, frames=None, n_active=None, max_edges=None):
+    """Pass 1 of the group statistics alone (piml_group_pairs): P (S, T, N, 2), M (S, T, N) float32 GPU tensors,
+    the thresholds of group_thresholds, frames (a, b) or None, n_active (S) int32 GPU tensor or None; max_edges None:
+    min(N (N - 1) / 2, 2^20).  Returns a dict of GPU tensors -- edges (S, max_edges, 4) int32, rows (i, j, co, near) of the
+    candidates in any order (rows at or past n_edges[s] hold nothing), n_edges (S) int32 the true count, trk_steps, trk_path
+    (S, N) and pairs, together (S) int64 -- with no host synchronisation (capturable in a graph)."""
+    P, M, n_active, a, b = _group_setup(P, M, frames, n_active)
+    S, T, N = P.shape[:3]
+    dev = P.device
+    cap = min(N * (N - 1) // 2, GROUP_MAX_EDGES) if max_edges is None else int(max_edges)
+    idle = S * max(b - a, 0) * N == 0
+    new = torch.zeros if idle else torch.empty
+    out = {'edges': new(S, max(cap, 0), 4, device=dev, dtype=torch.int32), 'n_edges': new(S, device=dev, dtype=torch.int32),
+           'trk_steps': new(S, N, device=dev, dtype=torch.int64), 'trk_path': new(S, N, device=dev, dtype=torch.int64),
+           'pairs': new(S, device=dev, dtype=torch.int64), 'together': new(S, device=dev, dtype=torch.int64)}
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().piml_group_pairs(_ptr(P), _ptr(M), _ptr(n_active), S, T, N, a, b, float(r2), float(dv2), float(vm2),
+                                               int(min_frames), cap, _ptr(out['edges']) if cap > 0 else None,
+                                               _ptr(out['n_edges']), *(_ptr(out[k]) for k in GROUP_PAIR_ROWS), _stream()),
+                   'piml_group_pairs')
+    return out
+
+
+def group_members_frames(P, M, links, r2, dv2, vm2, r_bin=0.1, r_bins=20, a_bins=10, frames=None):
+    """Pass 2 of the group statistics alone (piml_group_members): links (K, 3) int32 GPU tensor, rows (member, i, j).  Returns
+    a dict of int64 GPU tensors -- dist (S, r_bins + 1), abreast (S, a_bins), dist_sum, abreast_skipped, link_frames (S)."""
+    P, M, _, a, b = _group_setup(P, M, frames, None)
+    S, T, N = P.shape[:3]
+    dev = P.device
+    if not isinstance(links, torch.Tensor) or links.device != dev or links.dtype != torch.int32 or links.dim() != 2 \
+            or links.shape[1] != 3:
+        raise ValueError(f'links: expected an int32 (K, 3) tensor on {dev}')
+    links = links.contiguous()
+    RB, AB = int(r_bins), int(a_bins)
+    i64 = dict(device=dev, dtype=torch.int64)
+    out = {'dist': torch.zeros(S, max(RB, 0) + 1, **i64), 'dist_sum': torch.zeros(S, **i64),
+           'abreast': torch.zeros(S, max(AB, 0), **i64), 'abreast_skipped': torch.zeros(S, **i64),
+           'link_frames': torch.zeros(S, **i64)}
+    K = links.shape[0]
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().piml_group_members(_ptr(P), _ptr(M), S, T, N, a, b, _ptr(links) if K else None, K, float(r2),
+                                                 float(dv2), float(vm2), float(r_bin), RB, AB,
+                                                 *(_ptr(out[k]) for k in GROUP_MEMBER_ROWS), _stream()),
+                   'piml_group_members')
+    return out
+
+
+def group_stats_frames(P, M, dt=0.08, radius=2.0, dv_max=0.5, v_min=0.1, min_time=2.0, share=0.8, r_bin=0.1, r_bins=20,
+                       a_bins=10, frames=None, n_active=None, max_edges=None):
+    """The device half of piml_amd.groupstats.group_stats: the pair sweep, the link rule, the member
+    statistics.  P (S, T, N, 2), M (S, T, N) float32 GPU tensors, frames (a, b) or None, n_active (S) int32 GPU tensor or
+    None.  Returns a dict of GPU tensors: edges (E, 5) int64, rows (member, i, j, co, near) of every candidate sorted by
+    (member, i, j); n_edges (S) int64; trk_steps, trk_path (S, N), pairs, together (S) int64; and the rows of
+    group_members_frames over the links (near * 1024 >= round(share * 1024) * co).  The candidate counts are read back
+    between the passes (not capturable; group_pairs_frames alone is).  ValueError when a member has more than max_edges
+    candidates (None: min(N (N - 1) / 2, 2^20)), naming the count that was needed."""
+    r2, dv2, vm2, min_frames, share_q = group_thresholds(dt, radius, dv_max, v_min, min_time, share)
+    raw = group_pairs_frames(P, M, r2, dv2, vm2, min_frames, frames, n_active, max_edges)
+    n = raw['n_edges'].to(torch.int64)
+    cap = raw['edges'].shape[1]
+    need = int(n.max().item()) if n.numel() else 0
+    if need > cap:
+        raise ValueError(f'group_stats: a member has {need} candidate pairs, max_edges is {cap}: pass max_edges={need}')
+    S = n.shape[0]
+    rows = raw['edges'][:, :need].to(torch.int64)                                 # (S, need, 4)
+    valid = torch.arange(need, device=n.device)[None, :] < n[:, None]
+    member = torch.arange(S, device=n.device)[:, None].expand(S, need)
+    flat = torch.cat([member[valid][:, None], rows[valid]], 1)                    # (E, 5)
+    order = torch.argsort((flat[:, 0] << 32) | (flat[:, 1] << 16) | flat[:, 2]) if flat.shape[0] else flat[:, 0]
+    edges = flat[order]
+    link = edges[:, 4] * GROUP_SHARE_UNIT >= share_q * edges[:, 3]
+    out = {'edges': edges, 'n_edges': n}
+    out.update({k: raw[k] for k in GROUP_PAIR_ROWS})
+    out.update(group_members_frames(P, M, edges[link][:, :3].to(torch.int32), r2, dv2, vm2, r_bin, r_bins, a_bins, frames))
     return out

@@ -404,6 +404,13 @@ class ScenarioResult(types.SimpleNamespace):
         kw.setdefault('dt', float(self.time_unit))
         return line_stats(self.position, self.mask_p, lines, n_active=[self.num_agents], **kw)
 
+    def group_stats(self, **kw):
+        """piml_amd.groupstats.group_stats of the run: who walks with whom, group size, spacing and formation (positions
+        only, dt = time_unit; slots past num_agents not swept)."""
+        from .groupstats import group_stats
+        kw.setdefault('dt', float(self.time_unit))
+        return group_stats(self.position, self.mask_p, n_active=[self.num_agents], **kw)
+
 
 class ScenarioEnsemble(types.SimpleNamespace):
     """What `BaseSimulator.simulate_ensemble` returns: the ScenarioResult fields with a leading member axis -- position /
@@ -478,6 +485,14 @@ class ScenarioEnsemble(types.SimpleNamespace):
         kw.setdefault('dt', float(self.time_unit))
         return line_stats(self.position, self.mask_p, lines, n_active=[min(int(n), cap) for n in self.spawned], **kw)
 
+    def group_stats(self, **kw):
+        """piml_amd.groupstats.group_stats of every member in one call (dt = time_unit; member m's slots past its num_agents
+        not swept): member m's statistics are bitwise those of member(m).group_stats(**kw)."""
+        from .groupstats import group_stats
+        cap = self.position.shape[2]
+        kw.setdefault('dt', float(self.time_unit))
+        return group_stats(self.position, self.mask_p, n_active=[min(int(n), cap) for n in self.spawned], **kw)
+
     def collision_counts(self, threshold):
         """Per-member totals of collision_count(member.position, threshold, reduction='sum'): a list of S floats, one
         read-back.  One ops.collision_counts call per member: on a stack of more than 25 frames the count applies the
@@ -491,7 +506,7 @@ class ScenarioSweep(ScenarioEnsemble):
     """What `MLAPM.simulate_sweep` returns: a ScenarioEnsemble of n_candidates * seeds_per_candidate members laid out
     candidate-major -- member c * seeds_per_candidate + k ran law params[c] under the k-th seed -- plus params (the
     candidates' dicts), n_candidates and seeds_per_candidate.  `seeds` lists every member's seed (the seed list once per
-    candidate); crowd_stats / pair_stats / flow_stats / track_stats / obstacle_stats / line_stats compute all members in one call, and `.select(sweep.members_of(c)).pooled()` of
+    candidate); crowd_stats / pair_stats / flow_stats / track_stats / obstacle_stats / line_stats / group_stats compute all members in one call, and `.select(sweep.members_of(c)).pooled()` of
     the result pools one candidate."""
 
     def members_of(self, c):

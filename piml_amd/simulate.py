@@ -16,6 +16,7 @@ reads.
     python -m piml_amd.simulate --law mlapm --params p.json --seeds 0:32 --obstacle-stats walls.json
                                 (p.json with Aw, Bw [, wall_cutoff]: the law with a wall term, e.g. Aw = 50, Bw = -5)
     python -m piml_amd.simulate --law mlapm --scenario gc --seeds 0:32 --line-stats gates.json --lines '0,2,30,2;2,5,2,17'
+    python -m piml_amd.simulate --law mlapm --scenario gc --seeds 0:32 --group-stats groups.json        (group statistics)
     python -m piml_amd.simulate --law mlapm --params-sweep a.json b.json --seeds 0:8 --stats sweep.json
                                 (one law per file, every law on every seed in ONE ensemble run; statistics per candidate)
 
@@ -44,7 +45,7 @@ def get_args(argv=None):
                         "term's Aw, Bw, wall_cutoff); default main_mlapm.py's constants, version GC, no wall term")
     p.add_argument('--params-sweep', dest='params_sweep', type=str, nargs='+', default=None,
                    help='--law mlapm with --seeds: several --params files, every law on every seed in one ensemble run '
-                        "(MLAPM.simulate_sweep); --stats / --pair-stats / --flow-stats / --track-stats / --obstacle-stats / --line-stats then hold one entry per candidate, pooled over its "
+                        "(MLAPM.simulate_sweep); --stats / --pair-stats / --flow-stats / --track-stats / --obstacle-stats / --line-stats / --group-stats then hold one entry per candidate, pooled over its "
                         "seeds, and --out must contain '{candidate}' and '{seed}'")
     p.add_argument('--mlapm_radius', type=float, default=0.3,
                    help="--law mlapm: MLAPM's UCY collision radius (not the scene's arrival radius)")
@@ -90,6 +91,10 @@ def get_args(argv=None):
                    help='write the measurement-line statistics (piml_amd.linestats: flow, headway, crossing speed, travel '
                         'time; defaults, dt = the time unit) of the run or ensemble across --lines as JSON to this path '
                         'instead of writing clips')
+    p.add_argument('--group-stats', dest='group_stats', type=str, default=None,
+                   help='write the group statistics (piml_amd.groupstats: who walks with whom, group size, spacing, '
+                        'formation; defaults, dt = the time unit) of the run or ensemble as JSON to this path instead of '
+                        'writing clips')
     p.add_argument('--lines', type=str, default=None, help="--line-stats: the measurement lines, 'ax,ay,bx,by;ax,ay,bx,by;...'")
     p.add_argument('--time_unit', type=float, default=0.08)
     p.add_argument('--uniform_desired_speed', action=argparse.BooleanOptionalAction, default=None,
@@ -281,7 +286,8 @@ def _clip_scene(own):
 
 
 def _stats_path(own):
-    return ', '.join(p for p in (own.stats, own.pair_stats, own.flow_stats, own.track_stats, own.obstacle_stats, own.line_stats)
+    return ', '.join(p for p in (own.stats, own.pair_stats, own.flow_stats, own.track_stats, own.obstacle_stats, own.line_stats,
+                                 own.group_stats)
                      if p is not None)
 
 
@@ -290,8 +296,8 @@ def _crowd_kw(own):
 
 
 def _stats(res, own):
-    """--stats / --pair-stats / --flow-stats / --track-stats / --obstacle-stats / --line-stats: the CrowdStats / PairStats /
-    FlowStats / TrackStats / ObstacleStats / LineStats JSON of a run or an ensemble (one call for every member)."""
+    """--stats / --pair-stats / --flow-stats / --track-stats / --obstacle-stats / --line-stats / --group-stats: the CrowdStats /
+    PairStats / FlowStats / TrackStats / ObstacleStats / LineStats / GroupStats JSON of a run or an ensemble (one call for every member)."""
     if own.stats is not None:
         from . import crowdstats
         st = res.crowd_stats(**_crowd_kw(own))
@@ -325,6 +331,11 @@ def _stats(res, own):
         ls = res.line_stats(own.lines)
         ls.to_json(own.line_stats)
         linestats.print_line_stats(ls, 'simulate --line-stats')
+    if own.group_stats is not None:
+        from . import groupstats
+        gs = res.group_stats()
+        gs.to_json(own.group_stats)
+        groupstats.print_group_stats(gs, 'simulate --group-stats')
 
 
 def _sweep(sim, scenario, own, run_kw):
@@ -373,6 +384,12 @@ def _sweep(sim, scenario, own, run_kw):
         entries = [{'params': sw.params[c], 'file': own.params_sweep[c], 'stats': ls.select(g).pooled().to_json()}
                    for c, g in enumerate(groups)]
         with open(own.line_stats, 'w') as fh:
+            json.dump({'seeds': own.seeds, 'candidates': entries}, fh)
+    if own.group_stats is not None:
+        gs = sw.group_stats()
+        entries = [{'params': sw.params[c], 'file': own.params_sweep[c], 'stats': gs.select(g).pooled().to_json()}
+                   for c, g in enumerate(groups)]
+        with open(own.group_stats, 'w') as fh:
             json.dump({'seeds': own.seeds, 'candidates': entries}, fh)
     where = _stats_path(own)
     if not where:
