@@ -883,6 +883,8 @@ int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, vo
  *                          (0 unless initial_velocity), desired speed the row's: uniform_speed, speed_mean, speed_std,
  *                          speed_min and speed_clamp are not read.  The per-frame count is stream 1's, as every law's.
  *                          Any arrival rule but PIML_ARRIVE_GC.
+ *   PIML_SPAWN_CLIP_GROUPS the clip law with arrival units (groups that appear together): piml_scenario_step_mlapm_groups
+ *                          below, the only entry that takes it.
  * arrival_rule: PIML_ARRIVE_RADIUS |p' - dest| < arrival_radius -> flag += 1; PIML_ARRIVE_XBAND |p'.x - dest.x| <
  * arrival_radius -> flag += 1; PIML_ARRIVE_XEXIT p'.x > length retires the agent (flag unchanged).  Retirement as
  * piml_scenario_step (flag == D or waypoint[flag] NaN; or the x exit).
@@ -896,7 +898,8 @@ int piml_scenario_step(const piml_scenario* s, const float* a_next, int init, vo
  * NULL entries, P != 3 + D, n_initial > E, no arrival row (E == n_initial) with spawn_cap > 0, more than 2^24 arrival rows.
  */
 enum { PIML_SPAWN_GC = 0, PIML_SPAWN_CROSSWALK = 1, PIML_SPAWN_SQUARE = 2, PIML_SPAWN_UNIT1 = 3, PIML_SPAWN_UNIT2 = 4,
-       PIML_SPAWN_UNIT3 = 5, PIML_SPAWN_CLIP = 6 };
+       PIML_SPAWN_UNIT3 = 5, PIML_SPAWN_CLIP = 6,
+       PIML_SPAWN_CLIP_GROUPS = 7 /* piml_scenario_step_mlapm_groups only: every other entry rejects it */ };
 enum { PIML_ARRIVE_GC = 0, PIML_ARRIVE_RADIUS = 1, PIML_ARRIVE_XBAND = 2, PIML_ARRIVE_XEXIT = 3 };
 typedef struct piml_scenario_rules {
     int spawn_law, arrival_rule, initial_velocity, speed_clamp;
@@ -1036,6 +1039,65 @@ int piml_scenario_step_mlapm_walls(const piml_scenario* s, const piml_scenario_r
                                    const piml_mlapm_law* law, const void* table_device, const piml_wall_grid* g,
                                    const piml_wall_law* wall, const piml_wall_law* wall_table_device, int frame_offset,
                                    void* stream);
+
+/*
+ * Group arrivals and a group cohesion term for the MLAPM scenario frame (ABI 35, additive).
+ *
+ * PIML_SPAWN_CLIP_GROUPS is PIML_SPAWN_CLIP's track table (s->entries, (E, 3 + D, 2), rows [0, n_initial) the first frame)
+ * whose rows are bundled into UNITS of 1 .. 4 consecutive rows that appear together -- the recorded clip's groups
+ * (piml_amd.scenarios.clip_scenario(groups=)).  piml_scene_groups describes the bundling and holds the per-slot bookkeeping:
+ *   row_unit   (E, 2) int32, device: per table row (its index inside its unit, the unit's size)
+ *   unit_rows  (n_units) int32, device: the first row of each ARRIVAL unit (rows >= n_initial)
+ *   group_first, group_size  (members, capacity) int32, device, member-major like the state: for a slot that holds an agent,
+ *              the slot of its unit's first member and the unit's size; the caller zeroes them (size 0 = never spawned).
+ * init == 1: the init launch.  Slot i < n_initial is row i, nothing is drawn; group_first[i] = i - row_unit[i][0],
+ * group_size[i] = row_unit[i][1].  The laws, the wall arguments and frame_offset are not read.
+ * init == 0: frame t -> t + 1 as piml_scenario_step_mlapm (law != NULL, law_table_device == NULL),
+ * piml_scenario_step_mlapm_laws (the other way round) or, with wall_grid != NULL, piml_scenario_step_mlapm_walls.  The spawn
+ * count of the frame -- the scene rules' stream-1 draw against poisson_thresholds, as for every law -- is a number of UNITS
+ * k.  Unit j < k draws u = ((u24 n_units) >> 24) from its own Philox call (word layout in piml_amd/csrc/scenario.hip),
+ * first = unit_rows[u], size = row_unit[first][1], and one offset spawn_offset (2u - 1, 2u - 1) shared by its members (none
+ * when spawn_offset == 0).  With n the agents spawned through frame t, member q of unit j takes row first + q into slot
+ * n + (the sizes of units 0 .. j-1) + q; slots >= capacity are dropped and never written; group_first / group_size are
+ * written for every member that is.  spawned grows by the sum of the sizes, spawn_out[t + 1] is that sum, dropped the agents
+ * past the capacity.  The arrivals depend on (seed, frame, index in frame) only, never on a law.
+ *
+ * The group term (glaw or glaw_table_device given; both NULL: none, the units still arrive together).  For slot i the
+ * mates are the slots j in [group_first[i], group_first[i] + group_size[i]) clamped to [0, n_t), n_t = min(spawned, capacity);
+ * a mate is present when its RECORDED position of frame t is not NaN.  In float32, every operation rounded on its own:
+ *   n = the present mates (i among them); n < 2: G = 0;  c = (sum of p_j, ascending j) / (float)n;  e = c - p_i;
+ *   d = sqrt(ex ex + ey ey);  thr = dist (float)(n - 1);  G = d > thr ? ((A ex) / d, (A ey) / d) : 0,
+ * the attraction term of Moussaid et al. 2010 (their threshold is (n - 1) / 2 m: dist = 0.5); their gaze term is not built.
+ * The frame adds it last: F = ((v0 e - v) / tau - sum [+ W]) + G.  glaw_table_device: (members) piml_group_law in device
+ * memory, read on every launch, as the wall table.  A has no default (about 3 m/s^2 in the paper: a starting point for a fit).
+ *
+ * piml_group_force: G for every row of position (rows, 2) with its own group_first / group_size (rows) (the clamp is to
+ * [0, rows)), one thread per row; bitwise what the frame adds.  A NaN position[i] gives 0.
+ * hipErrorInvalidValue (before any launch) -- piml_group_force: rows < 0; A or dist not finite or negative; a NULL pointer
+ * with rows > 0.  piml_scenario_step_mlapm_groups: s, r, seeds or g NULL; members outside 1..65535; frame_offset < 0; init not
+ * 0 / 1; r->spawn_law != PIML_SPAWN_CLIP_GROUPS; any frame check of PIML_SPAWN_CLIP on the same descriptor; a NULL pointer
+ * inside g; n_units < 0, n_units == 0 with spawn_cap > 0, n_units > 2^24; glaw and glaw_table_device both given; glaw's A or
+ * dist not finite or negative; and with init == 0: law and law_table_device both NULL or both given, a law
+ * piml_scenario_step_mlapm rejects, wall / wall_table_device not exactly one with a wall_grid or any of them without one, a
+ * grid or by-value wall law piml_scenario_step_mlapm_walls rejects.  The tables' contents (row_unit, unit_rows, a law table)
+ * live in device memory and cannot be checked: rows and sizes read from them are clamped to the track table, so a corrupt
+ * table spawns the wrong rows and reads or writes nothing outside the buffers.  No atomics, no scratch, capturable.
+ */
+typedef struct piml_group_law { float A, dist; } piml_group_law;
+typedef struct piml_scene_groups {
+    const int* row_unit;                                    /* (E, 2) */
+    const int* unit_rows;                                   /* (n_units) */
+    int n_units;
+    int *group_first, *group_size;                          /* (members, capacity) */
+} piml_scene_groups;
+int piml_group_force(const float* position, const int* group_first, const int* group_size, long long rows, float A,
+                     float dist, float* force, void* stream);
+int piml_scenario_step_mlapm_groups(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                                    const piml_mlapm_law* law, const void* law_table_device,
+                                    const piml_wall_grid* wall_grid /* NULL: no wall term */, const piml_wall_law* wall,
+                                    const piml_wall_law* wall_table_device, const piml_scene_groups* g,
+                                    const piml_group_law* glaw /* both NULL: no group term */,
+                                    const piml_group_law* glaw_table_device, int init, int frame_offset, void* stream);
 
 /*
  * utils.route (src/utils/utils.py:141-165) for n (o, d) pairs, one wave each, the device function the spawn path uses:

@@ -63,6 +63,20 @@
 //                               the row's + spawn_offset (2 u(w1) - 1, 2 u(w2) - 1) (not added when spawn_offset == 0)
 // The init launch draws nothing: slot i < n_initial is row i.
 //
+// The grouped clip law's randomness (PIML_SPAWN_CLIP_GROUPS, piml_scenario_step_mlapm_groups only: the clip law whose
+// arrivals are UNITS of 1 .. 4 table rows that appear together; row_unit / unit_rows in include/piml_hip.h): c3 =
+// 0x5CE30000 | sub, key = (seed lo, seed hi).  The UNIT count k of a frame is again the scene rules' stream-1 draw
+// (0x5CE10000 word 0 against poisson_thresholds).
+//   unit j < k of frame f       (f lo, f hi, j, 0x5CE30001): unit u = ((w0 >> 8) Ua) >> 24 (64-bit integer product, Ua <= 2^24
+//                               units: exact, every unit reachable), first row unit_rows[u], size row_unit[first][1]; one
+//                               offset spawn_offset (2 u(w1) - 1, 2 u(w2) - 1) for the whole unit, so that its members keep
+//                               their relative geometry (not added when spawn_offset == 0)
+// Slots: base_j = n + the sizes of units 0 .. j-1 of the frame; member q takes row first + q into slot base_j + q (dropped,
+// never written, from the capacity on) and group_first = base_j, group_size = size.  Block j of the spawn blocks serves unit
+// j, its wave q member q; every wave redraws units 0 .. j to find its base (at most 8 Philox calls) and the bookkeeping
+// thread all k for the total, so nothing is exchanged between waves.  The init launch draws nothing: slot i is row i,
+// group_first = i - row_unit[i][0], group_size = row_unit[i][1].  The draws depend on (seed, frame, unit) only.
+//
 // Members: the descriptor's per-member pointers are the bases of member-major buffers, member m's slice of each having
 // exactly the single-run layout -- state (members, capacity, .), waypoints (members, D, capacity, 2), exit_idx
 // (members, D, capacity), recorded outputs (members, T, capacity, .), spawn_out (members, T), spawned (members, 2),
@@ -74,6 +88,7 @@
 // spawned[(t+1) & 1] written by one thread of block agent_blocks), so no workgroup reads a value another one writes in the
 // same launch; spawned agents take slots >= n_t, which no agent thread touches, and no block touches another member's slices.
 #include "common.hpp"
+#include "groups.hpp"
 #include "mlapm.hpp"
 #include "philox.hpp"
 #include "walls.hpp"
@@ -86,6 +101,7 @@ namespace piml {
 constexpr unsigned kScenarioStream = 0x5CE00000u;
 constexpr unsigned kRulesStream = 0x5CE10000u;
 constexpr unsigned kClipStream = 0x5CE20000u;
+constexpr unsigned kGroupStream = 0x5CE30000u;
 constexpr unsigned kClipMaxArrivals = 1u << 24; // arrival rows the 24-bit row draw reaches
 constexpr int kRulesMaxGrid = 32;
 constexpr int kScenarioMaxSpawn = 8;       // spawn_cap bound (the Poisson inversion's cap)
@@ -486,6 +502,83 @@ __device__ void clip_spawn_agent(const piml_scenario& S, const piml_scenario_rul
     rules_spawn_write(S, ord, f, o, vel, r[2].x, [&](int q) { return r[3 + q]; });
 }
 
+// ---- the grouped clip law (PIML_SPAWN_CLIP_GROUPS): arrival units of the track table (the file header's word layout) ----
+
+struct GroupArgs {
+    const int* row_unit;                                     // (E, 2) per table row: index inside its unit, the unit's size
+    const int* unit_rows;                                    // (n_units) first row of each arrival unit
+    int n_units;
+    int *group_first, *group_size;                           // (members, capacity); member_view's layout
+    piml_group_law law;                                      // the group term, by value ...
+    const piml_group_law* law_table;                         // ... or row blockIdx.y of this table when not NULL
+    int term;                                                // 0: no group term (the units still arrive together)
+};
+
+__device__ __forceinline__ void group_view(GroupArgs& G, int capacity, int m) {
+    G.group_first += (size_t)m * (size_t)capacity;
+    G.group_size += (size_t)m * (size_t)capacity;
+}
+
+// one wave: table row `row` appears in slot `slot` (< capacity) in frame f, moved by `off` when `moved`
+__device__ void group_spawn_member(const piml_scenario& S, const piml_scenario_rules& R, size_t row, long long slot, long long f,
+                                   bool moved, float2 off) {
+    const float2* r = (const float2*)S.entries + row * (size_t)S.P;
+    float2 o = r[0];
+    if (moved) o = make_float2(__fadd_rn(o.x, off.x), __fadd_rn(o.y, off.y));   // (x + 0 would turn a -0 coordinate into +0)
+    const float2 vel = R.initial_velocity ? r[1] : make_float2(0.f, 0.f);
+    rules_spawn_write(S, slot, f, o, vel, r[2].x, [&](int q) { return r[3 + q]; });
+}
+
+struct GroupUnit {
+    int first, size;                                         // table rows first .. first + size - 1
+    unsigned w1, w2;                                         // the unit's offset words
+};
+
+// unit j of frame f.  first and size come from device tables: they are clamped to the table (a corrupt table spawns the
+// wrong rows, it never reads outside `entries` or writes more than kGroupMaxSize slots)
+__device__ __forceinline__ GroupUnit group_unit_draw(const piml_scenario& S, const GroupArgs& G, long long f, int j) {
+    const PhiloxOut w = philox4x32_10((unsigned)f, (unsigned)((unsigned long long)f >> 32), (unsigned)j, kGroupStream | 1u,
+                                      (unsigned)S.seed, (unsigned)(S.seed >> 32));
+    const int u = (int)(((unsigned long long)(w.x >> 8) * (unsigned long long)G.n_units) >> 24);
+    GroupUnit un;
+    un.first = min(max(G.unit_rows[u], 0), S.E - 1);
+    un.size = min(max(G.row_unit[2 * (size_t)un.first + 1], 1), min(kGroupMaxSize, S.E - un.first));
+    un.w1 = w.y;
+    un.w2 = w.z;
+    return un;
+}
+
+// spawn block b of the grouped law: unit b of frame f, one wave per member; block 0's first thread does the bookkeeping
+__device__ __forceinline__ void group_spawn_block(const piml_scenario& S, const piml_scenario_rules& R, const GroupArgs& G,
+                                                  const uint32_t* thr, long long n, long long f, int b) {
+    const PhiloxOut w = philox4x32_10((unsigned)f, (unsigned)((unsigned long long)f >> 32), 0u, kRulesStream, (unsigned)S.seed,
+                                      (unsigned)(S.seed >> 32));
+    const int k = threshold_count(w.x >> 8, thr, S.spawn_cap);
+    if (b == 0 && threadIdx.x == 0) {
+        long long total = 0;
+        for (int j = 0; j < k; ++j) total += group_unit_draw(S, G, f, j).size;
+        S.spawned[f & 1] = n + total;
+        *S.dropped = n + total > S.capacity ? n + total - S.capacity : 0;
+        if (S.spawn_out && f < S.T) S.spawn_out[f] = (int)total;
+    }
+    const int q = (int)(threadIdx.x >> 6);
+    if (b >= k) return;
+    long long base = n;
+    GroupUnit un = group_unit_draw(S, G, f, 0);
+    for (int j = 0; j < b; ++j) {
+        base += un.size;
+        un = group_unit_draw(S, G, f, j + 1);
+    }
+    const long long slot = base + q;
+    if (q >= un.size || slot >= S.capacity) return;          // members past the capacity are dropped, never written
+    const float2 off = make_float2(__fmul_rn(S.spawn_offset, jitter(un.w1)), __fmul_rn(S.spawn_offset, jitter(un.w2)));
+    group_spawn_member(S, R, (size_t)(un.first + q), slot, f, S.spawn_offset != 0.f, off);
+    if (lane_id() == 0) {
+        G.group_first[slot] = (int)base;
+        G.group_size[slot] = un.size;
+    }
+}
+
 // ---- the frame ----
 
 // a spawn block (b = blockIdx.x - agent_blocks) of member view S: the spawn count of frame f -- init: n_initial; GC: k of
@@ -538,6 +631,29 @@ __device__ __forceinline__ void member_view(piml_scenario& S, const float2*& a_n
     S.spawned += mm * 2;
     S.dropped += mm;
     if (a_next) a_next += mm * cap;
+}
+
+// the init launch of a grouped scene: slot i < n_initial is table row i, nothing is drawn (grid: waves over n_initial, members)
+__global__ __launch_bounds__(256) void scenario_groups_init_kernel(const piml_scenario S0, const piml_scenario_rules R,
+                                                                   const GroupArgs G0) {
+    piml_scenario S = S0;
+    GroupArgs G = G0;
+    const float2* no_a = nullptr;
+    member_view(S, no_a, (int)blockIdx.y);
+    group_view(G, S.capacity, (int)blockIdx.y);
+    const long long f = *S.frame_counter;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        S.spawned[f & 1] = S.n_initial;
+        *S.dropped = S.n_initial > S.capacity ? S.n_initial - S.capacity : 0;
+        if (S.spawn_out && f < S.T) S.spawn_out[f] = S.n_initial;
+    }
+    const int i = (int)blockIdx.x * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
+    if (i >= S.n_initial || i >= S.capacity) return;
+    group_spawn_member(S, R, (size_t)i, i, f, false, make_float2(0.f, 0.f));
+    if (lane_id() == 0) {
+        G.group_first[i] = i - G.row_unit[2 * (size_t)i];
+        G.group_size[i] = G.row_unit[2 * (size_t)i + 1];
+    }
 }
 
 struct FrameArgs {
@@ -615,10 +731,17 @@ struct MlapmScenarioArgs {
 // from the agent's position in the state (frame t's) and added last, one float32 add per component; everything else is the
 // same code.  The wall law is the by-value `wall`, or row blockIdx.y of `wall_table` when that is not NULL (read on every
 // launch, as the law table).  kWalls == false is the two plain kernels below, whose names and arguments did not change.
-template <bool kTable, bool kWalls>
+//
+// kGroups (piml_scenario_step_mlapm_groups): the frame of a grouped clip scene.  Its spawn blocks are group_spawn_block's
+// (one block per arrival unit), and with GA.term the force gains the group term of groups.hpp, F = (the above) + G, added
+// last, one float32 add per component.  G reads the mates' positions from the RECORDS of frame t, as the pair sum does its
+// sources -- never from S.position or S.mask, which other waves overwrite in this launch.  The group law is GA.law, or row
+// blockIdx.y of GA.law_table when that is not NULL.  kGroups == false does not read GA: those kernels are what they were.
+template <bool kTable, bool kWalls, bool kGroups>
 __device__ __forceinline__ void scenario_mlapm_body(const MlapmScenarioArgs& K0, const unsigned long long* __restrict__ seeds,
                                                     const MlapmParams* __restrict__ table, const WallArgs& WG,
-                                                    const piml_wall_law& wall, const piml_wall_law* __restrict__ wall_table) {
+                                                    const piml_wall_law& wall, const piml_wall_law* __restrict__ wall_table,
+                                                    const GroupArgs& GA) {
     __shared__ float4 tile[kMlTile];                         // agent blocks: the sources (px, py, vx, vy); spawn blocks: entries
     __shared__ unsigned short ucy_ring[kMlScWaves][256];
     static_assert(kScenarioLdsPoints * sizeof(float2) <= sizeof(tile), "the entry points fit the source tile");
@@ -681,6 +804,14 @@ __device__ __forceinline__ void scenario_mlapm_body(const MlapmScenarioArgs& K0,
             const WallHit h = wall_force_wave(WG, w.A, w.B, make_float2(uniform(pi.x), uniform(pi.y)), lane);
             fx += h.force.x; fy += h.force.y;
         }
+        if constexpr (kGroups) {
+            if (GA.term) {
+                const piml_group_law gl = GA.law_table ? GA.law_table[blockIdx.y] : GA.law;   // block-uniform index
+                const size_t mo = (size_t)blockIdx.y * (size_t)cap + (size_t)i;               // member_view's layout
+                const float2 g = group_force_row(pt, n_t, i, GA.group_first[mo], GA.group_size[mo], gl.A, gl.dist);
+                fx = __fadd_rn(fx, g.x); fy = __fadd_rn(fy, g.y);
+            }
+        }
         const float2 vn = make_float2(vi.x + fx * dt, vi.y + fy * dt);          // :57
         const float2 pn = make_float2(pi.x + vn.x * dt, pi.y + vn.y * dt);      // main_mlapm.py:25
         const float2 an = make_float2(fx, fy);
@@ -699,6 +830,12 @@ __device__ __forceinline__ void scenario_mlapm_body(const MlapmScenarioArgs& K0,
         }
         return;
     }
+    if constexpr (kGroups) {                                 // the grouped law's spawn blocks: one per arrival unit
+        GroupArgs G = GA;
+        group_view(G, cap, (int)blockIdx.y);
+        group_spawn_block(S, K0.R, G, K0.S.poisson_thresholds, n, t + 1, (int)blockIdx.x - K0.agent_blocks);
+        return;
+    }
     // spawn blocks: the frame kernel's, from the same thresholds of the kernel arguments
     const float2* ent = (const float2*)S.entries;
     if (K0.gc && S.E * S.P <= kScenarioLdsPoints) {          // block-uniform, before any wave leaves
@@ -714,7 +851,7 @@ template <bool kTable>
 __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_kernel(const MlapmScenarioArgs K0,
                                                                         const unsigned long long* __restrict__ seeds,
                                                                         const MlapmParams* __restrict__ table) {
-    scenario_mlapm_body<kTable, false>(K0, seeds, table, WallArgs{}, piml_wall_law{}, nullptr);
+    scenario_mlapm_body<kTable, false, false>(K0, seeds, table, WallArgs{}, piml_wall_law{}, nullptr, GroupArgs{});
 }
 
 template <bool kTable>
@@ -723,7 +860,19 @@ __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_walls_kernel(c
                                                                               const MlapmParams* __restrict__ table,
                                                                               const WallArgs WG, const piml_wall_law wall,
                                                                               const piml_wall_law* __restrict__ wall_table) {
-    scenario_mlapm_body<kTable, true>(K0, seeds, table, WG, wall, wall_table);
+    scenario_mlapm_body<kTable, true, false>(K0, seeds, table, WG, wall, wall_table, GroupArgs{});
+}
+
+static_assert(kMlScWaves == kGroupMaxSize, "a spawn block of the grouped law holds one wave per member of a unit");
+
+template <bool kTable, bool kWalls>
+__global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_groups_kernel(const MlapmScenarioArgs K0,
+                                                                               const unsigned long long* __restrict__ seeds,
+                                                                               const MlapmParams* __restrict__ table,
+                                                                               const WallArgs WG, const piml_wall_law wall,
+                                                                               const piml_wall_law* __restrict__ wall_table,
+                                                                               const GroupArgs GA) {
+    scenario_mlapm_body<kTable, kWalls, true>(K0, seeds, table, WG, wall, wall_table, GA);
 }
 
 }  // namespace piml
@@ -899,6 +1048,66 @@ PIML_API int piml_scenario_step_mlapm_walls(const piml_scenario* s, const piml_s
     return hipGetLastError();
 }
 
+PIML_API int piml_scenario_step_mlapm_groups(const piml_scenario* s, const piml_scenario_rules* r, int members,
+                                             const uint64_t* seeds, const piml_mlapm_law* law, const void* law_table_device,
+                                             const piml_wall_grid* wall_grid, const piml_wall_law* wall,
+                                             const piml_wall_law* wall_table_device, const piml_scene_groups* g,
+                                             const piml_group_law* glaw, const piml_group_law* glaw_table_device, int init,
+                                             int frame_offset, void* stream) {
+    if (!s || !r || !seeds || !g || members < 1 || members > 65535 || frame_offset < 0 || (init != 0 && init != 1) ||
+        r->spawn_law != PIML_SPAWN_CLIP_GROUPS)
+        return hipErrorInvalidValue;
+    piml_scenario_rules clip = *r;                           // the frame checks of the clip law: the table is the same
+    clip.spawn_law = PIML_SPAWN_CLIP;
+    if (!frame_args_ok(*s, &clip, nullptr, 1)) return hipErrorInvalidValue;
+    if (!g->row_unit || !g->unit_rows || !g->group_first || !g->group_size || g->n_units < 0 ||
+        (g->n_units == 0 && s->spawn_cap > 0) || (unsigned)g->n_units > piml::kGroupMaxUnits)
+        return hipErrorInvalidValue;
+    if (glaw && glaw_table_device) return hipErrorInvalidValue;
+    if (glaw && !piml::group_law_ok(glaw->A, glaw->dist)) return hipErrorInvalidValue;
+    piml::GroupArgs GA;
+    GA.row_unit = g->row_unit;
+    GA.unit_rows = g->unit_rows;
+    GA.n_units = g->n_units;
+    GA.group_first = g->group_first;
+    GA.group_size = g->group_size;
+    GA.law = glaw ? *glaw : piml_group_law{};
+    GA.law_table = glaw_table_device;
+    GA.term = glaw || glaw_table_device;
+    if (init) {                                              // the laws are not read
+        const dim3 grid((unsigned)(s->n_initial > 0 ? (s->n_initial + 3) / 4 : 1), (unsigned)members);
+        hipLaunchKernelGGL(piml::scenario_groups_init_kernel, grid, dim3(256), 0, piml::as_stream(stream), *s, *r, GA);
+        return hipGetLastError();
+    }
+    if (!law == !law_table_device) return hipErrorInvalidValue;                               // exactly one
+    if (law && !mlapm_law_ok(*law)) return hipErrorInvalidValue;
+    if (wall_grid ? (!wall == !wall_table_device) : (wall || wall_table_device)) return hipErrorInvalidValue;
+    if (wall_grid && (!piml::wall_grid_ok(wall_grid) || (wall && !piml::wall_law_ok(wall->A, wall->B))))
+        return hipErrorInvalidValue;
+    piml::MlapmScenarioArgs K;
+    mlapm_frame_launch(K, *s, r, members, frame_offset);
+    const dim3 grid((unsigned)(K.agent_blocks + (s->spawn_cap > 0 ? s->spawn_cap : 1)), (unsigned)members);   // a block per unit
+    K.P = piml::MlapmParams{};                               // (not read with a table)
+    if (law) K.P = piml::make_params(law->variant, law->tau, law->A, law->B, law->C, law->D, law->theta_deg, law->radius, 1);
+    const piml::WallArgs WG = wall_grid ? piml::wall_args(*wall_grid) : piml::WallArgs{};
+    const piml_wall_law w = wall ? *wall : piml_wall_law{};
+    const unsigned long long* sd = (const unsigned long long*)seeds;
+    const piml::MlapmParams* tb = (const piml::MlapmParams*)law_table_device;
+    const dim3 block(piml::kMlScWaves * 64);
+    hipStream_t st = piml::as_stream(stream);
+    if (wall_grid) {
+        if (law) hipLaunchKernelGGL((piml::scenario_mlapm_groups_kernel<false, true>), grid, block, 0, st, K, sd, tb, WG, w,
+                                    wall_table_device, GA);
+        else hipLaunchKernelGGL((piml::scenario_mlapm_groups_kernel<true, true>), grid, block, 0, st, K, sd, tb, WG, w,
+                                wall_table_device, GA);
+    } else {
+        if (law) hipLaunchKernelGGL((piml::scenario_mlapm_groups_kernel<false, false>), grid, block, 0, st, K, sd, tb, WG, w,
+                                    wall_table_device, GA);
+        else hipLaunchKernelGGL((piml::scenario_mlapm_groups_kernel<true, false>), grid, block, 0, st, K, sd, tb, WG, w,
+                                wall_table_device, GA);
+    }
+    return hipGetLastError();
+}
 
 PIML_API int piml_scenario_route(const float* origin, const float* destination, int n, const float* polyline, int R,
                                  int max_iters, float clearance, float* waypoint, int* iters, void* stream) {

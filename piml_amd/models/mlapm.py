@@ -3,10 +3,13 @@ and `step` signature, evaluated by the HIP pair kernel with an analytic backward
 `simulate_ensemble` drive the open-world scenes of piml_amd.scenarios with it (one launch per frame); `simulate_sweep` does
 so for a list of laws at once, one law per ensemble member.  With the optional constants Aw, Bw (and wall_cutoff) the scene
 runs add a wall term, the repulsion Aw exp(Bw d) of the nearest obstacle point within wall_cutoff (include/piml_hip.h,
-piml_scenario_step_mlapm_walls); `step` and `rollout` never have one."""
+piml_scenario_step_mlapm_walls); `step` and `rollout` never have one.  With Ag (and group_dist) the runs of a grouped clip
+scene (scenarios.clip_scenario(groups=)) add a group cohesion term, a pull of Ag towards the centroid of the agent's group
+(piml_scenario_step_mlapm_groups); `step`, `rollout` and the fits never have one either."""
 from .. import ops
 
 DEFAULT_WALL_CUTOFF = 2.0     # metres
+DEFAULT_GROUP_DIST = 0.5      # metres per further member: Moussaid et al. 2010's (n - 1) / 2
 
 
 class MLAPM:
@@ -15,6 +18,7 @@ class MLAPM:
         if args.get('version') not in ops.MLAPM_VARIANTS:
             raise NotImplementedError(args.get('version'))
         wall_args(args)                                       # (ValueError on a half-given or out-of-range wall term)
+        group_args(args)                                      # (... or group term)
 
     def step(self, position, velocity, desired_speed, destination, dt, radius=0.3):
         """position, velocity, destination: (N, 2); desired_speed: (N, 1), (N,) or (N, 2).  Returns the new
@@ -148,6 +152,12 @@ class MLAPM:
         wall_cutoff=2.0]) adds one: W = Aw exp(Bw d) (p - q*) / d for the nearest valid obstacle point q* within wall_cutoff,
         isotropic (a resting agent feels it), added to the force last; Aw = 50, Bw = -5 (Helbing and Molnar 1995) is the
         literature's starting point for a fit, not a default.  ValueError when Aw is given and the scene has no obstacles.
+        A grouped clip scene (scenarios.clip_scenario(groups=), MLAPM only) spawns its units together whatever the law, and
+        the result's group_first / group_size / planted_groups() tell which slots were planted as one.  MLAPM(..., Ag=[,
+        group_dist=0.5]) adds the group term last: G = Ag e / |e| towards the centroid c of the agent's present mates, e =
+        c - p, once |e| > group_dist (n - 1) -- the attraction term of Moussaid et al. 2010 without their gaze term.  Ag has
+        no default; about 3 m/s^2 is the paper's order of magnitude, a starting point for a fit that nobody has verified
+        here.  ValueError when Ag is given and the scene has no groups.
         Returns a scenarios.ScenarioResult."""
         return self._simulate(scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, seed=seed)
 
@@ -168,44 +178,49 @@ class MLAPM:
         wall = wall_args(self.args)
         if wall is not None:
             check_scene_walls(scenario)
+        group = group_args(self.args)
+        if group is not None:
+            check_scene_groups(scenario)
         st = scenarios.scenario_state_for(scenario, frames, capacity, device, hist_width, **state_kw)
         walls = None
         if wall is not None:
             walls = (ops_scenario.wall_grid(st.scenario.obstacles, wall[2], st.p.device), ops_scenario.wall_law(*wall[:2]))
-        self._run_scenario(st, law, use_graph, frames_per_graph, walls=walls)
+        self._run_scenario(st, law, use_graph, frames_per_graph, walls=walls,
+                           groups=None if group is None else ops_scenario.group_law(*group))
         return scenarios.scenario_result(st)
 
     @staticmethod
-    def _run_scenario(st, law, use_graph, frames_per_graph, graph=None, walls=None):
+    def _run_scenario(st, law, use_graph, frames_per_graph, graph=None, walls=None, groups=None):
         """frame 0's spawn, then T - 1 MLAPM frames: K = frames_per_graph of them (offsets 0 .. K-1 and one counter add)
         captured into one graph and replayed when use_graph, the rest eagerly.  law: a mlapm_law or a law table; walls:
-        None or ops_scenario.scenario_step_mlapm's (grid, wall law or wall table) for the frames with the wall term.  Returns
+        None or ops_scenario.scenario_step_mlapm's (grid, wall law or wall table) for the frames with the wall term; groups: None
+        or its group law or group table (a grouped clip scene's frames with the group term).  Returns
         the captured graph (None for an eager run); passed back as `graph` with the same state, the run replays it
         instead of capturing again."""
         import torch
         from .. import ops_scenario, hip_graphs_safe
         with torch.no_grad():
-            ops_scenario.scenario_step(st, init=True)                 # frame 0: generate(n_initial)
+            ops_scenario.scenario_step_mlapm(st, None, init=True)     # frame 0: generate(n_initial)
             steps = st.T - 1
             if use_graph is None:
                 use_graph = steps > 8
             per = max(1, int(frames_per_graph))
             done = 0
             if use_graph and steps >= per + 1 and hip_graphs_safe():
-                ops_scenario.scenario_step_mlapm(st, law, walls=walls)     # a real frame, also warms the library up
+                ops_scenario.scenario_step_mlapm(st, law, walls=walls, groups=groups)     # a real frame, also warms the library up
                 done = 1
                 if graph is None:
                     torch.cuda.synchronize()
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
                         for k in range(per):
-                            ops_scenario.scenario_step_mlapm(st, law, frame_offset=k, advance=False, walls=walls)
+                            ops_scenario.scenario_step_mlapm(st, law, frame_offset=k, advance=False, walls=walls, groups=groups)
                         st.t.add_(per)
                 for _ in range((steps - done) // per):
                     graph.replay()
                 done += (steps - done) // per * per
             for _ in range(steps - done):
-                ops_scenario.scenario_step_mlapm(st, law, walls=walls)
+                ops_scenario.scenario_step_mlapm(st, law, walls=walls, groups=groups)
         return graph
 
     # ---- one law per member (piml_scenario_step_mlapm_laws): a sweep of candidates x seeds in one ensemble run ----
@@ -215,17 +230,52 @@ class MLAPM:
         """simulate_ensemble for every candidate of `params` in the same launches: params is a list of C dicts in
         MLAPM(**params) form (version, tau, A, B and optionally C, D, theta; an optional 'radius' overrides `radius` for
         that candidate; optionally the wall term's Aw, Bw, in every candidate or in none -- wall_cutoff is common to the
-        sweep, a property of the scene's grid), and member c * len(seeds) + k runs law c under seeds[k] -- candidate-major, every candidate on
+        sweep, a property of the scene's grid; optionally the group term's Ag and group_dist, again in every candidate or
+        in none, on a grouped clip scene), and member c * len(seeds) + k runs law c under seeds[k] -- candidate-major, every candidate on
         the same seeds and so the same arrivals (common random numbers).  Candidates may differ in version.  Member
         (c, k) is bitwise MLAPM(**params[c]).simulate_ensemble(scenario, frames, seeds, capacity=same)'s member k.
         What the reference does with one process per parameter set (src/utils/grid_search.py) is one run here.
         ValueError: an empty list, an unknown or missing key, candidates with and without a wall term, a wall term in a
-        scene without obstacles, C * len(seeds) > 65535.  Returns a scenarios.ScenarioSweep."""
+        scene without obstacles, candidates with and without a group term, a group term in a scene without groups,
+        C * len(seeds) > 65535.  Returns a scenarios.ScenarioSweep."""
         return SweepRun(scenario, frames, len(params) if hasattr(params, '__len__') else 0, seeds, capacity, use_graph,
                         device, hist_width, frames_per_graph, wall_cutoff).run(params, radius)
 
 
 SWEEP_KEYS = ('version', 'tau', 'A', 'B', 'C', 'D', 'theta', 'radius', 'Aw', 'Bw')
+GROUP_KEYS = ('Ag', 'group_dist')       # a candidate's optional group term (a grouped clip scene)
+
+
+def group_args(args):
+    """(Ag, group_dist) of MLAPM(**args)'s group term, None without one.  ValueError: group_dist without Ag, a value that is
+    not finite or is negative."""
+    import math
+    if 'Ag' not in args:
+        if 'group_dist' in args:
+            raise ValueError('MLAPM: group_dist belongs to the group term and needs Ag')
+        return None
+    Ag, dist = float(args['Ag']), float(args.get('group_dist', DEFAULT_GROUP_DIST))
+    if not (math.isfinite(Ag) and math.isfinite(dist)) or Ag < 0 or dist < 0:
+        raise ValueError(f'MLAPM: finite Ag >= 0 and group_dist >= 0 expected, got {Ag}, {dist}')
+    return Ag, dist
+
+
+def check_scene_groups(scenario):
+    """ValueError when the scene is not a grouped clip scene for a group term to act in."""
+    if scenario.spawn_law != 'clip_groups':
+        raise ValueError("MLAPM: a group term (Ag) was given, but the scene has no groups (scenarios.clip_scenario(groups=))")
+
+
+def sweep_groups(params):
+    """The (Ag, group_dist) pair of every candidate dict, or None when no candidate has a group term.  ValueError when only
+    some have one, or on a value group_args refuses."""
+    params = list(params)
+    have = [isinstance(a, dict) and 'Ag' in a for a in params]
+    if any(have) and not all(have):
+        raise ValueError(f'simulate_sweep: candidates {[c for c, h in enumerate(have) if not h]} have no group term (Ag) '
+                         'and the others do: every candidate or none')
+    rows = [group_args({k: a[k] for k in ('Ag', 'group_dist') if k in a}) for a in params if isinstance(a, dict)]
+    return rows if any(have) else None
 
 
 def wall_args(args):
@@ -279,18 +329,20 @@ def sweep_laws(params, radius=0.3):
     for c, a in enumerate(params):
         if not isinstance(a, dict):
             raise ValueError(f'candidate {c}: a dict in MLAPM(**params) form expected, got {type(a).__name__}')
-        unknown = sorted(set(a) - set(SWEEP_KEYS))
+        unknown = sorted(set(a) - set(SWEEP_KEYS) - set(GROUP_KEYS))
         missing = [k for k in ('version', 'tau', 'A', 'B') if k not in a]
         if unknown or missing:
-            raise ValueError(f'candidate {c}: unknown keys {unknown}, missing keys {missing} (of {SWEEP_KEYS})')
+            raise ValueError(f'candidate {c}: unknown keys {unknown}, missing keys {missing} (of {SWEEP_KEYS + GROUP_KEYS})')
         laws.append(ops_scenario.mlapm_law(a['version'], a['tau'], a['A'], a['B'], a.get('C', 0.0), a.get('D', 0.0),
                                            a.get('theta', 0.0), a.get('radius', radius)))
     sweep_walls(params)
+    sweep_groups(params)
     return laws
 
 
 class SweepRun:
-    """The state, law table (and wall table, when the candidates carry Aw, Bw) and captured frames of a sweep of
+    """The state, law table (and wall table, when the candidates carry Aw, Bw; and group table, when they carry Ag) and
+    captured frames of a sweep of
     n_candidates laws x seeds, kept for running again:
     run(params) writes the candidates' tables into the same device buffers, puts the state back to empty and replays the
     graph captured by the first run, so a further population costs one small copy, the fills and the replays -- what a
@@ -309,7 +361,7 @@ class SweepRun:
         self.scenario, self.frames, self.capacity, self.device = scenario, frames, capacity, device
         self.hist_width, self.use_graph, self.frames_per_graph = hist_width, use_graph, frames_per_graph
         self.wall_cutoff = float(wall_cutoff)
-        self.st = self.table = self.graph = self.wall_grid = self.wall_table = None
+        self.st = self.table = self.graph = self.wall_grid = self.wall_table = self.group_table = None
 
     def run(self, params, radius=0.3):
         from .. import ops_scenario, scenarios
@@ -321,7 +373,11 @@ class SweepRun:
         rows = [law for law in laws for _ in range(S)]
         walls = sweep_walls(params)
         wall_rows = None if walls is None else [ops_scenario.wall_law(*w) for w in walls for _ in range(S)]
+        groups = sweep_groups(params)
+        group_rows = None if groups is None else [ops_scenario.group_law(*g) for g in groups for _ in range(S)]
         if self.st is None:
+            if groups is not None:
+                check_scene_groups(self.scenario)
             if walls is not None:
                 wall_args({'Aw': 0.0, 'Bw': 0.0, 'wall_cutoff': self.wall_cutoff})
                 check_scene_walls(self.scenario)
@@ -331,15 +387,22 @@ class SweepRun:
             if walls is not None:
                 self.wall_grid = ops_scenario.wall_grid(self.st.scenario.obstacles, self.wall_cutoff, self.st.p.device)
                 self.wall_table = ops_scenario.wall_law_table(wall_rows, self.st.p.device)
+            if groups is not None:
+                self.group_table = ops_scenario.group_law_table(group_rows, self.st.p.device)
         else:
             if (walls is None) != (self.wall_table is None):  # the captured frames are those of the first run's kernel
                 raise ValueError('SweepRun: every run of a sweep has a wall term (Aw, Bw) or none has')
+            if (groups is None) != (self.group_table is None):
+                raise ValueError('SweepRun: every run of a sweep has a group term (Ag) or none has')
             ops_scenario.mlapm_law_table(rows, out=self.table)
+            if groups is not None:
+                ops_scenario.group_law_table(group_rows, out=self.group_table)
             if walls is not None:
                 ops_scenario.wall_law_table(wall_rows, out=self.wall_table)
             ops_scenario.scenario_state_reset(self.st)
         self.graph = MLAPM._run_scenario(self.st, self.table, self.use_graph, self.frames_per_graph, graph=self.graph,
-                                         walls=None if walls is None else (self.wall_grid, self.wall_table))
+                                         walls=None if walls is None else (self.wall_grid, self.wall_table),
+                                         groups=self.group_table)
         ens = scenarios.scenario_result(self.st)
         fields = dict(vars(ens))
         return scenarios.ScenarioSweep(params=params, n_candidates=self.n_candidates, seeds_per_candidate=S, **fields)

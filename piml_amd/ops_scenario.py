@@ -1,6 +1,6 @@
 """Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_step_rules,
 piml_scenario_step_members, piml_scenario_step_mlapm, piml_scenario_step_mlapm_laws, piml_scenario_step_mlapm_walls,
-piml_wall_force, piml_scenario_route).
+piml_wall_force, piml_scenario_step_mlapm_groups, piml_group_force, piml_scenario_route).
 
 `scenario_state` allocates the persistent (static-address) buffers of one simulation or an ensemble and the
 `piml_scenario` descriptor that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive,
@@ -43,7 +43,9 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
     counter with a leading member axis (state (S, capacity, .), waypoints (S, D, capacity, 2), records (S, T, capacity, .),
     spawned (S, 2), dropped (S), features (S, capacity, k, 6)); `seed` is then unused.  A single run has st.members None
     and is the one member of its launch: st.seeds holds the 64-bit patterns of the seed or seeds as a device int64 tensor,
-    and st.rules the scene's piml_scenario_rules (GC's all-zero one for GC)."""
+    and st.rules the scene's piml_scenario_rules (GC's all-zero one for GC).  A grouped clip scene ('clip_groups') also
+    gets st.group_first / st.group_size ((S,) capacity int32, zero: per slot the first slot and the size of its unit) and
+    st.groups, the piml_scene_groups over them and the scene's row_unit / unit_rows."""
     dev = scenario.entries.device
     if dev.type != 'cuda':
         raise _lib.PimlHipError(f'scenario_state: the scenario must be on a GPU (piml_amd has no CPU path), got {dev}')
@@ -113,6 +115,19 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
         s.poisson_thresholds[j] = x
     st.desc = s
     st.rules = scenario_rules(scenario) if scenario.spawn_law != 'gc' else _lib.ScenarioRules()
+    st.groups = None
+    if scenario.spawn_law == 'clip_groups':
+        ru, ur = scenario.row_unit, scenario.unit_rows
+        if ru is None or ur is None or ru.dtype != torch.int32 or ur.dtype != torch.int32 or ru.device != dev or \
+                ur.device != dev or tuple(ru.shape) != (E, 2) or ur.dim() != 1 or not (ru.is_contiguous() and ur.is_contiguous()):
+            raise ValueError(f"a 'clip_groups' scene needs row_unit ({E}, 2) and unit_rows (Ua,) int32 on {dev} (Scenario.to)")
+        st.group_first = torch.zeros(*lead, cap, device=dev, dtype=torch.int32)
+        st.group_size = torch.zeros(*lead, cap, device=dev, dtype=torch.int32)
+        st.unit_rows = ur if ur.numel() else torch.zeros(1, device=dev, dtype=torch.int32)   # (the entry takes no NULL)
+        g = _lib.SceneGroups()
+        g.row_unit, g.unit_rows, g.n_units = ru.data_ptr(), st.unit_rows.data_ptr(), int(ur.numel())
+        g.group_first, g.group_size = st.group_first.data_ptr(), st.group_size.data_ptr()
+        st.groups = g
     return st
 
 
@@ -126,15 +141,19 @@ def scenario_state_reset(st):
     for x in (st.v, st.a, st.hist, st.selff, st.desired_speed, st.mask, st.flag, st.exit_idx, st.spawn_iters, st.v_res,
               st.a_res, st.mask_res, st.spawn_count, st.t, st.spawned, st.dropped):
         x.zero_()
+    if getattr(st, 'groups', None) is not None:
+        st.group_first.zero_()
+        st.group_size.zero_()
 
 
 def scenario_rules(scenario):
     """The piml_scenario_rules descriptor of a scene (its spawn law, arrival rule, velocity and speed laws, second stream).
     The 'clip' law's track table is the scene's `entries`, which scenario_state puts into the piml_scenario descriptor."""
     r = _lib.ScenarioRules()
-    if scenario.spawn_law not in _lib.SPAWN_LAWS or scenario.arrival_rule not in _lib.ARRIVAL_RULES:
+    laws = dict(_lib.SPAWN_LAWS, clip_groups=_lib.SPAWN_CLIP_GROUPS)
+    if scenario.spawn_law not in laws or scenario.arrival_rule not in _lib.ARRIVAL_RULES:
         raise ValueError(f'unknown scene rule {scenario.spawn_law!r} / {scenario.arrival_rule!r}')
-    r.spawn_law, r.arrival_rule = _lib.SPAWN_LAWS[scenario.spawn_law], _lib.ARRIVAL_RULES[scenario.arrival_rule]
+    r.spawn_law, r.arrival_rule = laws[scenario.spawn_law], _lib.ARRIVAL_RULES[scenario.arrival_rule]
     r.initial_velocity, r.speed_clamp = int(bool(scenario.initial_velocity)), int(bool(scenario.speed_clamp))
     r.length, r.width = float(scenario.length), float(scenario.width)
     r.side_ratio, r.direction_ratio = float(scenario.side_ratio), float(scenario.direction_ratio)
@@ -157,7 +176,10 @@ def scenario_rules(scenario):
 def scenario_step(st, a_next=None, init=False):
     """One launch: init=True spawns the scenario's n_initial agents into frame st.t; otherwise frame st.t -> st.t + 1 with
     the network's accelerations a_next (capacity, 2), or (S, capacity, 2) for an ensemble state (every member in the same
-    launch).  The caller advances st.t (ops.relative_features_into(tick=st.t))."""
+    launch).  The caller advances st.t (ops.relative_features_into(tick=st.t)).  ValueError for a grouped clip scene
+    ('clip_groups'): its frames, the init launch included, are scenario_step_mlapm's."""
+    if getattr(st, 'groups', None) is not None:
+        raise ValueError("scenario_step: a 'clip_groups' scene runs under the MLAPM frame only (scenario_step_mlapm)")
     if not init:
         a_next = _gpu_f32('a_next', a_next)
         want = (st.capacity, 2) if st.members is None else (st.members, st.capacity, 2)
@@ -352,7 +374,70 @@ def wall_law_table(rows, device='cuda', out=None):
     return host.to(dev)
 
 
-def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None):
+def group_law(Ag, dist=0.5):
+    """The piml_group_law of the group term (include/piml_hip.h): a pull of Ag m/s^2 towards the centroid of the agent's
+    group once it is further from it than dist (n - 1) m.  ValueError unless both are finite and >= 0."""
+    Ag, dist = float(Ag), float(dist)
+    if not (math.isfinite(Ag) and math.isfinite(dist)) or Ag < 0 or dist < 0:
+        raise ValueError(f'group law: finite Ag >= 0 and dist >= 0 expected, got Ag={Ag}, dist={dist}')
+    law = _lib.GroupLaw()
+    law.A, law.dist = Ag, dist
+    return law
+
+
+def group_law_table(rows, device='cuda', out=None):
+    """The group table of piml_scenario_step_mlapm_groups: rows, a list of (Ag, dist) pairs or group_law(...) values, one per
+    member, as a (len(rows), 2) float32 device tensor (every row checked as group_law does).  out: a table of the same
+    shape to overwrite in place instead (a captured run reads the buffer at every replay)."""
+    laws = [r if isinstance(r, _lib.GroupLaw) else group_law(*r) for r in rows]
+    if not laws:
+        raise ValueError('group_law_table: at least one row expected')
+    host = torch.tensor([[g.A, g.dist] for g in laws], dtype=torch.float32)
+    if out is not None:
+        if out.dtype != torch.float32 or tuple(out.shape) != tuple(host.shape) or not out.is_contiguous():
+            raise ValueError(f'out: a contiguous float32 table {tuple(host.shape)} expected, got {out.dtype} {tuple(out.shape)}')
+        out.copy_(host)
+        return out
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.PimlHipError(f'group_law_table: a GPU device expected (piml_amd has no CPU path), got {dev}')
+    return host.to(dev)
+
+
+def group_force(position, group_first, group_size, Ag, dist=0.5):
+    """The group term G of every slot of position (..., N, 2) (piml_group_force, one thread per row; include/piml_hip.h):
+    slot i's mates are the slots [group_first[i], group_first[i] + group_size[i]) of its own (N, 2) block, clamped to
+    [0, N), present when their position is not NaN; G = Ag e / |e| towards the present mates' centroid when |e| > dist
+    (n - 1), else 0 (also for a NaN position and for fewer than two present mates).  group_first, group_size: int32 (N) or
+    (..., N) (broadcast over the leading axes), as a result's or ensemble's .group_first / .group_size.  Bitwise what the
+    frame adds for a frame whose recorded positions are `position`."""
+    law = group_law(Ag, dist)
+    p = _gpu_f32('position', position)
+    if p.dim() < 2 or p.shape[-1] != 2:
+        raise ValueError(f'position: (..., N, 2) expected, got {tuple(p.shape)}')
+    N = p.shape[-2]
+    gf = torch.as_tensor(group_first, device=p.device).to(torch.int32)
+    gs = torch.as_tensor(group_size, device=p.device).to(torch.int32)
+    if gf.shape[-1:] != (N,) or gs.shape[-1:] != (N,):
+        raise ValueError(f'group_first / group_size: (..., {N}) expected, got {tuple(gf.shape)}, {tuple(gs.shape)}')
+    if p.dim() > 2:                                  # blocks of N rows: clamp to the block here, then shift to flat rows
+        gf, gs = gf.expand(p.shape[:-1]), gs.expand(p.shape[:-1])
+        lo, hi = gf.long().clamp(min=0), (gf.long() + gs.long()).clamp(max=N)
+        block = torch.arange(p.numel() // (2 * N), device=p.device).reshape(*p.shape[:-2], 1) * N
+        gf, gs = (lo + block).to(torch.int32), (hi - lo).clamp(min=0).to(torch.int32)
+        if p.numel() // 2 > 0x7fffffff:
+            raise ValueError(f'position: {p.numel() // 2} rows, more than 2^31 - 1')
+    gf, gs = gf.contiguous(), gs.contiguous()
+    force = torch.zeros_like(p)
+    rows = p.numel() // 2
+    if rows:
+        with torch.cuda.device(p.device):
+            _lib.check(_lib.lib().piml_group_force(_ptr(p), _ptr(gf), _ptr(gs), rows, law.A, law.dist, _ptr(force),
+                                                   _stream()), 'piml_group_force')
+    return force
+
+
+def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, groups=None, init=False):
     """One launch: frame t -> t + 1 of st (single or ensemble state) under the MLAPM law `law` (mlapm_law(...)), t =
     st.t + frame_offset: the force of MLAPM.step from the agents present in frame t's records, v' = v + F dt, p' = p + v' dt
     (src/main_mlapm.py:18-36), a' = F, then the scene's arrivals, exits and spawns as scenario_step.  advance: add 1 to
@@ -362,7 +447,25 @@ def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None):
     piml_scenario_step_mlapm_laws); ValueError when it does not hold exactly st.seeds.numel() rows or is on another device.
     walls = (grid, wall): the frame with the wall term (piml_scenario_step_mlapm_walls), F = (MLAPM's force) + W of
     wall_force at the agent's position; grid a wall_grid(...) of the scene's obstacles, wall a wall_law(Aw, Bw) for every
-    member or a wall_law_table(...) with one row per member."""
+    member or a wall_law_table(...) with one row per member.
+    A grouped clip scene (st.groups, scenarios.clip_scenario(groups=)) goes to piml_scenario_step_mlapm_groups in every form
+    above; groups = a group_law(Ag, dist) for every member or a group_law_table(...) with one row per member adds the group
+    term last, F = (the above) + G of group_force on frame t's records; groups = None: no group term, the units still arrive
+    together.  ValueError for groups on a scene without them.
+    init = True: the init launch instead (frame st.t gets the scene's n_initial agents; law, walls, groups and frame_offset
+    are not read, st.t is not advanced) -- scenario_step(st, init=True) for every scene but a grouped one, whose init launch
+    is the new entry's."""
+    grouped = getattr(st, 'groups', None) is not None
+    if init:
+        if not grouped:
+            return scenario_step(st, init=True)
+        with torch.cuda.device(st.p.device):
+            _lib.check(_lib.lib().piml_scenario_step_mlapm_groups(
+                ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(), _ptr(st.seeds), None, None, None, None, None,
+                ctypes.byref(st.groups), None, None, 1, 0, _stream()), 'piml_scenario_step_mlapm_groups')
+        return
+    if groups is not None and not grouped:
+        raise ValueError("groups: the scene has no groups (scenarios.clip_scenario(groups=) makes a 'clip_groups' scene)")
     table = isinstance(law, torch.Tensor)
     if table:
         row = int(_lib.lib().piml_mlapm_law_table_bytes(1))
@@ -390,6 +493,31 @@ def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None):
             raise TypeError(f'walls: (wall_grid, wall_law or wall_law_table) expected, got {type(wall).__name__}')
         if grid.cell_start.device != st.p.device:
             raise ValueError(f'wall grid on {grid.cell_start.device}, the state on {st.p.device}')
+    if grouped:
+        group_table = isinstance(groups, torch.Tensor)
+        if group_table:
+            if groups.dtype != torch.float32 or tuple(groups.shape) != (st.seeds.numel(), 2) or not groups.is_contiguous():
+                raise ValueError(f'group table: a contiguous float32 ({st.seeds.numel()}, 2) tensor of group_law_table '
+                                 f'expected, got {groups.dtype} {tuple(groups.shape)}')
+            if groups.device != st.p.device:
+                raise ValueError(f'group table on {groups.device}, the state on {st.p.device}')
+        elif groups is not None and not isinstance(groups, _lib.GroupLaw):
+            raise TypeError(f'groups: a group_law or a group_law_table expected, got {type(groups).__name__}')
+        grid, wall = walls if walls is not None else (None, None)
+        wall_table = isinstance(wall, torch.Tensor)
+        with torch.cuda.device(st.p.device):
+            _lib.check(_lib.lib().piml_scenario_step_mlapm_groups(
+                ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(), _ptr(st.seeds),
+                None if table else ctypes.byref(law), _ptr(law) if table else None,
+                None if grid is None else ctypes.byref(grid.desc),
+                None if wall is None or wall_table else ctypes.byref(wall), _ptr(wall) if wall_table else None,
+                ctypes.byref(st.groups), None if groups is None or group_table else ctypes.byref(groups),
+                _ptr(groups) if group_table else None, 0, int(frame_offset), _stream()), 'piml_scenario_step_mlapm_groups')
+            if advance:
+                st.t.add_(1)
+        return
+    if walls is not None:
+        grid, wall = walls
         with torch.cuda.device(st.p.device):
             _lib.check(_lib.lib().piml_scenario_step_mlapm_walls(
                 ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(), _ptr(st.seeds),

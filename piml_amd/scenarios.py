@@ -50,7 +50,7 @@ class Scenario:
     spawn_cap: int = 8                     # bound of the per-frame Poisson draw (inversion cap)
     name: str = ''
     # scene rule (piml_scenario_rules); the defaults are GC's
-    spawn_law: str = 'gc'                  # 'gc', 'crosswalk', 'square', 'unit1', 'unit2', 'unit3', 'clip'
+    spawn_law: str = 'gc'                  # 'gc', 'crosswalk', 'square', 'unit1', 'unit2', 'unit3', 'clip', 'clip_groups'
     arrival_rule: str = 'gc'               # 'gc', 'radius' |p - dest| < r, 'x_band' |p.x - dest.x| < r, 'x_exit' x > length
     initial_velocity: bool = False         # spawn with velocity heading * v0 (else 0)
     speed_clamp: bool = True               # v0 = max(speed_min, ...) of a normal draw
@@ -62,11 +62,17 @@ class Scenario:
     side_ratio: float = 0.0                # basic_unit2
     direction_ratio: float = 0.0
     square_grid: torch.Tensor = None       # the square's (d,) grid coordinates
+    # 'clip_groups' (clip_scenario(groups=)): the table's rows bundled into units whose members appear together
+    row_unit: torch.Tensor = None          # (E, 2) int32 per table row: its index inside its unit, the unit's size
+    unit_rows: torch.Tensor = None         # (Ua,) int32 the first row of each arrival unit
 
     def to(self, device):
         out = dataclasses.replace(self)
         for f in ('entries', 'route_polyline', 'obstacles'):
             setattr(out, f, getattr(self, f).to(device).contiguous())
+        for f in ('row_unit', 'unit_rows'):
+            if getattr(self, f) is not None:
+                setattr(out, f, getattr(self, f).to(device=device, dtype=torch.int32).contiguous())
         return out
 
     @property
@@ -221,6 +227,7 @@ CLIP_MAX_INITIAL = 4096                    # the frame's bound on n_initial
 CLIP_MAX_WAYPOINTS = 8                     # ... on D
 CLIP_MAX_SPAWN_CAP = 8                     # ... on spawn_cap
 CLIP_SPAWN_TAIL = 1e-6                     # the Poisson mass allowed beyond spawn_cap
+CLIP_MAX_GROUP = 4                         # members of an arrival unit (a spawn block's waves); larger groups are cut
 
 
 def _poisson_tail(lam, cap):
@@ -233,7 +240,51 @@ def _poisson_tail(lam, cap):
     return max(0.0, 1.0 - cdf)
 
 
-def clip_scenario(raw_data, frames=None, arrival_radius=1.0, jitter=0.0, initial_velocity=True, spawn_cap=8, skip_frames=25):
+def _clip_units(groups, win, first, a):
+    """The units of clip_scenario(groups=): [(tracks ascending, f_u)] for the initial units (f_u == a) and for the arrival
+    units, each list ordered by its units' smallest track.  groups: lists of track indices; win (b - a, N) bool presence in
+    the window; first (N) each track's first in-window frame."""
+    import warnings
+    N = win.shape[1]
+    seen = win.any(0)
+    taken = set()
+    checked = []
+    for g in groups:
+        g = [int(i) for i in g]
+        if len(g) < 2:
+            raise ValueError(f'clip_scenario: a group of at least 2 tracks expected, got {g}')
+        for i in g:
+            if not 0 <= i < N:
+                raise ValueError(f'clip_scenario: track {i} of group {g} outside the clip\'s 0..{N - 1}')
+            if i in taken:
+                raise ValueError(f'clip_scenario: track {i} is in two groups (or twice in one)')
+            taken.add(i)
+        checked.append(sorted(g))
+    units, grouped, apart, cut = [], set(), 0, 0
+    for g in checked:
+        g = [i for i in g if bool(seen[i])]                   # tracks not seen in the window leave their group
+        if len(g) < 2:
+            continue
+        all_on = win[:, g].all(1)
+        if not bool(all_on.any()):                            # never all present at once: singles
+            apart += 1
+            continue
+        f_u = a + int(all_on.to(torch.uint8).argmax())
+        cut += len(g) > CLIP_MAX_GROUP
+        for k in range(0, len(g), CLIP_MAX_GROUP):
+            units.append((g[k:k + CLIP_MAX_GROUP], f_u))
+        grouped.update(g)
+    if apart:
+        warnings.warn(f'clip_scenario: {apart} group(s) whose members never share a frame of the window become singles')
+    if cut:
+        warnings.warn(f'clip_scenario: {cut} group(s) of more than {CLIP_MAX_GROUP} cut into units of at most {CLIP_MAX_GROUP}')
+    units += [([i], int(first[i])) for i in seen.nonzero().flatten().tolist() if i not in grouped]
+    units.sort(key=lambda u: u[0][0])
+    return [u for u in units if u[1] == a], [u for u in units if u[1] != a]
+
+
+def clip_scenario(raw_data, frames=None, arrival_radius=1.0, jitter=0.0, initial_velocity=True, spawn_cap=8, skip_frames=25,
+                  groups=None):
     """A recorded clip as an open-world scene (spawn law 'clip', PIML_SPAWN_CLIP): its obstacles, time unit and D
     waypoints; frame 0 holds the agents present at the window's first frame with the state they had there; afterwards
     agents arrive as a Poisson process at the clip's own rate, each a draw (with replacement) from the tracks that first
@@ -248,7 +299,23 @@ def clip_scenario(raw_data, frames=None, arrival_radius=1.0, jitter=0.0, initial
     Ka / (b - a - 1) per frame (`fixed_spawn_rate`); no arrival track: spawn_cap 0, a closed scene.
     ValueError: a window shorter than 2 frames or outside the clip, no track in the window, more than 4096 agents in its
     first frame, D > 8, spawn_cap outside 0..8, or P(K > spawn_cap) > 1e-6 at the clip's rate (the frame caps a draw at
-    spawn_cap)."""
+    spawn_cap).
+
+    groups (default None: the scene above, law 'clip'): keep the clip's groups as arrival UNITS whose members appear
+    together (spawn law 'clip_groups', PIML_SPAWN_CLIP_GROUPS; MLAPM-driven runs only).  A list of lists of track indices
+    (columns of raw_data.position; [] is valid: every unit a single), or 'auto' = groupstats.group_stats_of_raw(raw_data,
+    frames=frames).groups(0), which needs a GPU.  Tracks not seen in the window leave their group, and a group left with
+    one member is a single.  A unit's frame f_u: a single's first in-window frame; a group's first frame of the window at
+    which ALL its members are present (none: its members become singles, one warning with the count).  Groups of more than
+    CLIP_MAX_GROUP = 4 are cut in ascending track order into consecutive units of at most 4, each at the group's f_u (one
+    warning).  A unit with f_u == a is an initial unit, any other an arrival unit, and a track appears in exactly one row:
+    a member of an arrival group that was already walking at frame a is therefore NOT in the scene's first frame -- it
+    arrives with its group.  Rows: the initial units ordered by their smallest track, members in ascending track order,
+    then the arrival units likewise (with groups=[] today's order); a row is (position, velocity, (desired_speed, 0),
+    waypoints ahead...) at the unit's f_u.  n_initial is the number of initial rows; `row_unit` (E, 2) int32 holds per row
+    (its index inside its unit, the unit's size), `unit_rows` (Ua,) int32 the first row of each arrival unit.  The rate is
+    Ua / (b - a - 1) UNITS per frame and the P(K > spawn_cap) check applies to units.
+    ValueError besides the above: an index out of range, a track in two groups, a list shorter than 2."""
     from .data.data import desired_speed_per_agent
     pos = torch.as_tensor(raw_data.position).detach().float().cpu()
     vel = torch.as_tensor(raw_data.velocity).detach().float().cpu()
@@ -269,9 +336,25 @@ def clip_scenario(raw_data, frames=None, arrival_radius=1.0, jitter=0.0, initial
     if not bool(seen.any()):
         raise ValueError(f'clip_scenario: no track in frames {(a, b)}')
     first = a + win.to(torch.uint8).argmax(0)                             # (N) first in-window frame
-    order = torch.cat(((seen & (first == a)).nonzero().flatten(), (seen & (first > a)).nonzero().flatten()))
-    n_initial = int((seen & (first == a)).sum())
-    Ka = order.numel() - n_initial
+    if groups is not None:
+        if isinstance(groups, str):
+            if groups != 'auto':
+                raise ValueError(f"clip_scenario: groups: lists of track indices or 'auto' expected, got {groups!r}")
+            from .groupstats import group_stats_of_raw
+            groups = group_stats_of_raw(raw_data, frames=None if frames is None else (a, b)).groups(0)
+        initial, arrivals = _clip_units(list(groups), win, first, a)
+        units = initial + arrivals
+        order = torch.tensor([i for u, _ in units for i in u], dtype=torch.long)
+        f0 = torch.tensor([f for u, f in units for _ in u], dtype=torch.long)
+        row_unit = torch.tensor([(q, len(u)) for u, _ in units for q in range(len(u))], dtype=torch.int32).reshape(-1, 2)
+        n_initial = sum(len(u) for u, _ in initial)
+        Ka = len(arrivals)                                                # arrival UNITS: the rate and the cap count units
+        unit_rows = (n_initial + torch.tensor([0] + [len(u) for u, _ in arrivals], dtype=torch.long).cumsum(0)[:-1]).int()
+    else:
+        order = torch.cat(((seen & (first == a)).nonzero().flatten(), (seen & (first > a)).nonzero().flatten()))
+        n_initial = int((seen & (first == a)).sum())
+        Ka = order.numel() - n_initial
+        f0 = None
     if n_initial > CLIP_MAX_INITIAL:
         raise ValueError(f'clip_scenario: {n_initial} agents in frame {a}, more than {CLIP_MAX_INITIAL}')
     rate = Ka / (b - a - 1)
@@ -281,7 +364,8 @@ def clip_scenario(raw_data, frames=None, arrival_radius=1.0, jitter=0.0, initial
                          f'{_poisson_tail(rate, cap):.3g} > {CLIP_SPAWN_TAIL:g}; raise spawn_cap (at most '
                          f'{CLIP_MAX_SPAWN_CAP}) or widen the window')
     v0 = desired_speed_per_agent(vel, int(skip_frames))
-    f0 = first[order]
+    if f0 is None:
+        f0 = first[order]
     dest_idx = getattr(raw_data, 'dest_idx', None)
     if dest_idx is not None:
         k0 = torch.as_tensor(dest_idx).cpu().long()[f0, order]
@@ -296,6 +380,12 @@ def clip_scenario(raw_data, frames=None, arrival_radius=1.0, jitter=0.0, initial
     ahead = torch.gather(rows, 1, q.clamp(max=D - 1).unsqueeze(-1).expand(-1, -1, 2))
     table[:, 3:] = torch.where((q < D).unsqueeze(-1), ahead, torch.full_like(ahead, float('nan')))
     obs = torch.as_tensor(raw_data.obstacles).detach().float().cpu().reshape(-1, 2)
+    if groups is not None:
+        return Scenario(entries=table.contiguous(), route_polyline=torch.zeros(0, 2), obstacles=obs.contiguous(),
+                        time_unit=float(raw_data.time_unit), n_initial=n_initial, spawn_offset=float(jitter),
+                        arrival_radius=float(arrival_radius), num_waypoints=D, spawn_cap=cap, spawn_law='clip_groups',
+                        arrival_rule='radius', initial_velocity=bool(initial_velocity), speed_clamp=False,
+                        fixed_spawn_rate=rate, name='clip', row_unit=row_unit.contiguous(), unit_rows=unit_rows.contiguous())
     return Scenario(entries=table.contiguous(), route_polyline=torch.zeros(0, 2), obstacles=obs.contiguous(),
                     time_unit=float(raw_data.time_unit), n_initial=n_initial, spawn_offset=float(jitter),
                     arrival_radius=float(arrival_radius), num_waypoints=D, spawn_cap=cap, spawn_law='clip',
@@ -309,7 +399,8 @@ SCENARIOS = {'gc': gc_scenario, 'crosswalk': crosswalk_scenario, 'four_direction
 
 def default_capacity(scenario, frames, tail=1e-9):
     """n_initial + the (1 - tail) quantile of Poisson((spawn_rate + spawn_rate2) * (frames - 1)) (at most spawn_cap +
-    spawn_cap2 per frame); n_initial for a scene without arrivals."""
+    spawn_cap2 per frame); n_initial for a scene without arrivals.  A grouped clip scene ('clip_groups') draws UNITS: its
+    agents are bounded by the unit quantile times the largest arrival-unit size, an upper bound (most units are smaller)."""
     steps = max(int(frames) - 1, 0)
     cap = scenario.spawn_cap + scenario.spawn_cap2
     mu = (scenario.spawn_rate * (scenario.spawn_cap > 0) + scenario.spawn_rate2) * steps
@@ -325,7 +416,10 @@ def default_capacity(scenario, frames, tail=1e-9):
         q = k
     else:                                     # normal approximation, 6 sigma
         q = int(math.ceil(mu + 6.0 * math.sqrt(mu)))
-    return max(1, scenario.n_initial + min(q, cap * steps))
+    largest = 1
+    if scenario.unit_rows is not None and scenario.unit_rows.numel():
+        largest = int(scenario.row_unit[scenario.unit_rows.long(), 1].max())
+    return max(1, scenario.n_initial + min(q, cap * steps) * largest)
 
 
 def _scene_obstacles(res):
@@ -340,11 +434,23 @@ class ScenarioResult(types.SimpleNamespace):
     """What `BaseSimulator.simulate_scenario` returns.  position / velocity / acceleration / destination (T, cap, 2),
     mask_p (T, cap), waypoints (D, cap, 2), desired_speed (cap), obstacles (M, 2), time_unit, spawned (agents generated,
     dropped ones included), dropped (agents past the capacity, never simulated), spawn_count (T) per frame.  Slot n holds
-    the agent of ordinal n; slots past min(spawned, cap) never held an agent."""
+    the agent of ordinal n; slots past min(spawned, cap) never held an agent.  A grouped clip scene's run ('clip_groups')
+    also has group_first, group_size (cap) int32 -- per slot the first slot and the size of the unit it was spawned with, 0
+    for a slot that never held an agent -- (None for every other scene) and `planted_groups()`."""
 
     @property
     def num_agents(self):
         return min(int(self.spawned), self.position.shape[1])
+
+    def planted_groups(self):
+        """The slot lists of the units of two or more that a grouped clip scene ('clip_groups') spawned together, ordered by
+        their first slot (a unit cut by the capacity lists the slots it got); [] for any other scene."""
+        gf, gs = getattr(self, 'group_first', None), getattr(self, 'group_size', None)
+        if gf is None or gs is None:
+            return []
+        n = self.num_agents
+        gf, gs = gf[:n].detach().cpu().tolist(), gs[:n].detach().cpu().tolist()
+        return [list(range(i, min(i + gs[i], n))) for i in range(n) if gf[i] == i and gs[i] >= 2]
 
     def _dense(self):
         n = self.num_agents
@@ -412,11 +518,16 @@ class ScenarioResult(types.SimpleNamespace):
         return group_stats(self.position, self.mask_p, n_active=[self.num_agents], **kw)
 
 
+def _index(x, key):
+    return None if x is None else x[key]
+
+
 class ScenarioEnsemble(types.SimpleNamespace):
     """What `BaseSimulator.simulate_ensemble` returns: the ScenarioResult fields with a leading member axis -- position /
     velocity / acceleration / destination (S, T, cap, 2), mask_p (S, T, cap), waypoints (S, D, cap, 2), desired_speed
     (S, cap), spawn_count (S, T) -- and seeds, spawned, dropped as lists of S ints; obstacles, time_unit and capacity
-    are shared.  Member m is the simulation of seed seeds[m]."""
+    are shared; group_first, group_size (S, cap) for a grouped clip scene, else None.  Member m is the simulation of seed
+    seeds[m]."""
 
     def __len__(self):
         return len(self.seeds)
@@ -428,7 +539,12 @@ class ScenarioEnsemble(types.SimpleNamespace):
             destination=self.destination[m], mask_p=self.mask_p[m], waypoints=self.waypoints[m],
             desired_speed=self.desired_speed[m], obstacles=self.obstacles, time_unit=self.time_unit,
             spawned=self.spawned[m], dropped=self.dropped[m], spawn_count=self.spawn_count[m], capacity=self.capacity,
-            seed=self.seeds[m])
+            seed=self.seeds[m], group_first=_index(getattr(self, 'group_first', None), m),
+            group_size=_index(getattr(self, 'group_size', None), m))
+
+    def planted_groups(self, member=0):
+        """member(member).planted_groups(): the slot lists of the units of two or more spawned together."""
+        return self.member(member).planted_groups()
 
     def save_data(self, pattern):
         """One v2.2 clip per member at pattern with '{seed}' replaced by the member's seed.  Returns the paths."""
@@ -525,7 +641,8 @@ class ScenarioSweep(ScenarioEnsemble):
             destination=self.destination[sl], mask_p=self.mask_p[sl], waypoints=self.waypoints[sl],
             desired_speed=self.desired_speed[sl], spawn_count=self.spawn_count[sl], obstacles=self.obstacles,
             time_unit=self.time_unit, capacity=self.capacity, seeds=self.seeds[sl], spawned=self.spawned[sl],
-            dropped=self.dropped[sl])
+            dropped=self.dropped[sl], group_first=_index(getattr(self, 'group_first', None), sl),
+            group_size=_index(getattr(self, 'group_size', None), sl))
 
     def save_data(self, pattern):
         """One v2.2 clip per member at pattern with '{candidate}' and '{seed}' replaced.  Returns the paths."""
@@ -554,7 +671,8 @@ def scenario_result(st):
     sc, last = st.scenario, int(st.t.item())
     common = dict(position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res, mask_p=st.mask_res,
                   waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles, time_unit=sc.time_unit,
-                  spawn_count=st.spawn_count, capacity=st.capacity, state=st)
+                  spawn_count=st.spawn_count, capacity=st.capacity, state=st,
+                  group_first=getattr(st, 'group_first', None), group_size=getattr(st, 'group_size', None))
     if st.members is None:
         return ScenarioResult(spawned=int(st.spawned[last & 1].item()), dropped=int(st.dropped.item()), seed=st.seed,
                               **common)

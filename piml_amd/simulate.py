@@ -9,6 +9,8 @@ reads.
     python -m piml_amd.simulate --seeds 0:32 --stats stats.json      (crowd statistics of the run, no clips written)
     python -m piml_amd.simulate --seeds 0:32 --pair-stats pairs.json      (time-to-collision statistics, no clips written)
     python -m piml_amd.simulate --law mlapm --scene-from ucy.npy --seeds 0:32 --pair-stats sim.json   (a clip as the scene)
+    python -m piml_amd.simulate --law mlapm --scene-from gc.npy --scene-groups auto --params p.json --seeds 0:32 --group-stats g.json
+                                (the clip's groups arrive together; p.json with Ag [, group_dist] adds the group term)
     python -m piml_amd.simulate --scenario crosswalk --seeds 0:32 --flow-stats flow.json [--flow-axis x|y|auto|deg]
     python -m piml_amd.simulate --law mlapm --scenario crosswalk --seeds 0:32 --track-stats tracks.json   (track statistics)
                                 (velocity correlation and lane order, no clips written)
@@ -57,6 +59,10 @@ def get_args(argv=None):
                    help="--scene-from: the window 'a:b' of the clip's frames (default: all)")
     p.add_argument('--scene-jitter', dest='scene_jitter', type=float, default=0.0,
                    help='--scene-from: arrivals start within +- this many metres of the recorded origin (default 0)')
+    p.add_argument('--scene-groups', dest='scene_groups', type=str, default=None,
+                   help="--scene-from with --law mlapm: keep the clip's groups as arrival units whose members appear "
+                        "together (scenarios.clip_scenario(groups=)): 'auto' (the clip's own group statistics) or a JSON "
+                        'file holding a list of lists of track indices')
     p.add_argument('--frames', type=int, default=750)
     seed = p.add_mutually_exclusive_group()
     seed.add_argument('--seed', type=int, default=0, help='seed of the spawn schedule')
@@ -136,8 +142,16 @@ def get_args(argv=None):
             except ValueError:
                 p.error(f"--scene-frames: 'a:b' expected, got {own.scene_frames!r}")
             own.scene_frames = (a, b)
-    elif own.scene_frames is not None or own.scene_jitter != 0.0:
-        p.error('--scene-frames / --scene-jitter need --scene-from')
+        if own.scene_groups is not None and own.law != 'mlapm':
+            p.error('--scene-groups: a grouped scene runs under --law mlapm only (the network-driven frame has no group '
+                    'arrivals), not with --law pinnsf')
+        if own.scene_groups is not None and own.scene_groups != 'auto':
+            try:
+                own.scene_groups = load_scene_groups(own.scene_groups)
+            except (OSError, ValueError) as ex:
+                p.error(f'--scene-groups: {ex}')
+    elif own.scene_frames is not None or own.scene_jitter != 0.0 or own.scene_groups is not None:
+        p.error('--scene-frames / --scene-jitter / --scene-groups need --scene-from')
     if own.params_sweep is not None:
         if own.params is not None:
             p.error('--params-sweep takes the place of --params: not both')
@@ -161,12 +175,25 @@ def get_args(argv=None):
     return own, model_args
 
 
+def load_scene_groups(path):
+    """--scene-groups FILE.json: a list of lists of track indices.  ValueError on anything else."""
+    import json
+    with open(path) as fh:
+        got = json.load(fh)
+    if not isinstance(got, list) or not all(isinstance(g, list) and all(isinstance(i, int) and not isinstance(i, bool)
+                                                                         for i in g) for g in got):
+        raise ValueError(f'{path}: a JSON list of lists of track indices expected')
+    return got
+
+
 def load_mlapm_params(path):
     """MLAPM's constructor arguments from the JSON `python -m piml_amd.calibrate --out` writes ({'version', 'tau', 'A',
-    'B', 'C', 'D', 'theta'} and, for a law with a wall term, 'Aw', 'Bw', 'wall_cutoff'); constants the file leaves out keep
+    'B', 'C', 'D', 'theta'} and, for a law with a wall term, 'Aw', 'Bw', 'wall_cutoff'; for one with a group term, 'Ag' and
+    optionally 'group_dist'); constants the file leaves out keep
     calibrate.DEFAULT_INIT's values (main_mlapm.py:16) -- the wall term has no default: without Aw there is none --, and
     path None is those constants with version GC.  ValueError on an unknown version, an unknown key, a non-number or a
-    wall term MLAPM refuses (Bw or wall_cutoff without Aw, Aw < 0, Bw > 0, wall_cutoff <= 0)."""
+    wall term MLAPM refuses (Bw or wall_cutoff without Aw, Aw < 0, Bw > 0, wall_cutoff <= 0) or a group term it refuses
+    (group_dist without Ag, a negative value)."""
     import json
     from . import calibrate, ops
     params = {'version': 'GC', **calibrate.DEFAULT_INIT}
@@ -176,7 +203,7 @@ def load_mlapm_params(path):
         got = json.load(fh)
     if not isinstance(got, dict):
         raise ValueError(f'{path}: a JSON object expected')
-    numbers = calibrate.PARAM_NAMES + calibrate.WALL_PARAM_NAMES + ('wall_cutoff',)
+    numbers = calibrate.PARAM_NAMES + calibrate.WALL_PARAM_NAMES + ('wall_cutoff', 'Ag', 'group_dist')
     unknown = sorted(set(got) - {'version', *numbers})
     if unknown:
         raise ValueError(f'{path}: unknown keys {unknown} (expected version and {list(numbers)})')
@@ -186,9 +213,10 @@ def load_mlapm_params(path):
         if k in got and (isinstance(got[k], bool) or not isinstance(got[k], (int, float))):
             raise ValueError(f'{path}: {k} = {got[k]!r} is not a number')
     params.update(got)
-    from .models.mlapm import wall_args
+    from .models.mlapm import group_args, wall_args
     try:
         wall_args(params)
+        group_args(params)
     except ValueError as ex:
         raise ValueError(f'{path}: {ex}') from None
     return params
@@ -260,6 +288,12 @@ def main(argv=None):
             check_scene_walls(scenario)
         except ValueError as ex:
             sys.exit(f'--params / --params-sweep: {ex}')
+    if own.law == 'mlapm' and any('Ag' in a for a in (own.mlapm_sweep or [own.mlapm])):
+        from .models.mlapm import check_scene_groups
+        try:
+            check_scene_groups(scenario)
+        except ValueError as ex:
+            sys.exit(f'--params / --params-sweep: {ex} (--scene-from CLIP --scene-groups auto|FILE.json)')
     if own.law == 'mlapm' and own.mlapm_sweep is not None:
         return _sweep(sim, scenario, own, run_kw)
     if own.seeds is not None:
@@ -280,7 +314,7 @@ def _clip_scene(own):
     raw = RawData()
     raw.load_trajectory_data(own.scene_from)
     try:
-        return SCENARIOS.clip_scenario(raw, frames=own.scene_frames, jitter=own.scene_jitter)
+        return SCENARIOS.clip_scenario(raw, frames=own.scene_frames, jitter=own.scene_jitter, groups=getattr(own, 'scene_groups', None))
     except ValueError as ex:
         sys.exit(f'--scene-from {own.scene_from}: {ex}')
 
