@@ -112,6 +112,47 @@ def test_library_argument_checks_of_glue_entries():
     assert L.piml_train_step_bwd(None, None, None, None, None, 0, 1, 5, 0, 0.08, None, None, None, None, None) == 0
 
 
+def test_corrector_and_head64_argument_checks_without_gpu():
+    """piml_corrector_fwd / bwd and piml_head64_fwd / bwd_acc refuse out-of-range sizes and null buffers before any launch; an
+    empty problem is a no-op; the slot counts at the boundaries of their weight-gradient workgroups (128 rows / 128 agents for
+    the corrector; one tile per slot up to 2048 tiles, four above, for the head)."""
+    import ctypes
+    from piml_amd import _lib
+    L = _lib.lib()
+
+    def corrector(agents, k):
+        c = _lib.Corrector()                            # every pointer null
+        c.agents, c.k, c.scale = agents, k, 2.0
+        return (L.piml_corrector_fwd(ctypes.byref(c), None), L.piml_corrector_bwd(ctypes.byref(c), 0, None))
+
+    assert corrector(8, 0) == (1, 1)
+    assert corrector(8, 65) == (1, 1)
+    assert corrector(-1, 6) == (1, 1)
+    assert corrector(1 << 25, 64) == (1, 1)             # agents * k = 2^31
+    assert corrector(1, 6) == (1, 1)                    # NULL buffers
+    assert corrector(0, 6) == (0, 0)                    # empty: no-op
+    assert L.piml_corrector_fwd(None, None) == 1 and L.piml_corrector_bwd(None, 0, None) == 1
+
+    def head64(rows):
+        h = _lib.Head64()
+        h.rows = rows
+        return (L.piml_head64_fwd(ctypes.byref(h), None), L.piml_head64_bwd_acc(ctypes.byref(h), 0, None))
+
+    assert head64(-1) == (1, 1)
+    assert head64(1 << 25) == (1, 1)
+    assert head64(1) == (1, 1)                          # NULL buffers
+    assert head64(0) == (0, 0)                          # empty: no-op
+    assert L.piml_head64_fwd(None, None) == 1 and L.piml_head64_bwd_acc(None, 1, None) == 1
+
+    assert L.piml_corrector_slots(0, 129, 1) == 2
+    assert L.piml_corrector_slots(1, 129, 1) == 2
+    assert L.piml_corrector_slots(1, 128, 64) == 1
+    assert L.piml_corrector_slots(0, 128, 1) == 1 and L.piml_corrector_slots(0, 128, 64) == 64
+    assert L.piml_head64_slots(65536) == 2048
+    assert L.piml_head64_slots(65537) == 513
+    assert L.piml_head64_slots(0) == 0
+
+
 def test_tuning_file_is_consistent():
     """The committed TunableOp result file: validators first, then one line per GEMM shape, no duplicates."""
     from piml_amd import tuning
