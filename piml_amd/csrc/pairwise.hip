@@ -598,6 +598,14 @@ __device__ __forceinline__ bool collide(const float2* __restrict__ p, int N, int
     return norm2(pj.x - pi.x, pj.y - pi.y) < th;           // NaN compares false -> 0
 }
 
+// The pair (i, i) of a count: data.py:562 subtracts the identity whatever the threshold, so a present agent's own entry is
+// [0 < thr] - 1, i.e. 0 for a positive threshold and -1 for a non-positive (or NaN) one; an absent agent's is NaN -> 0.  It
+// never counts as a friend (its total over the slices is at most 0).
+__device__ __forceinline__ float self_count(float2 pi, float th) {
+    const float d = norm2(pi.x - pi.x, pi.y - pi.y);
+    return d != d ? 0.f : (d < th ? 0.f : -1.f);
+}
+
 // General path (more than 25 slices, e.g. the (t, N, 2) rollouts of the evaluation): one wavefront per agent i.
 // Pass 1, per block of 64 partners j: the pair's collisions summed over all slices (the friends total).  Pass 2,
 // only for the (few) partners that collide at all and are not friends: lanes take slices and bump a wave-private
@@ -626,7 +634,7 @@ __global__ __launch_bounds__(WAVES * 64) void collision_counts_kernel(const floa
                     if (collide(p, N, s, i, jj, th)) cnt[s] += 1.f;
             }
         }
-        for (int s = lane; s < S; s += 64) counts[((size_t)h * S + s) * N + i] = cnt[s];
+        for (int s = lane; s < S; s += 64) counts[((size_t)h * S + s) * N + i] = cnt[s] + self_count(p[(size_t)s * N + i], th);
     }
 }
 
@@ -765,7 +773,7 @@ __global__ __launch_bounds__(256) void collision_counts_from_totals_kernel(const
             int c = cnt[u][h];
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-            if (lane == 0 && i0 + u < N) counts[((size_t)h * S + s) * N + i0 + u] = (float)c;
+            if (lane == 0 && i0 + u < N) counts[((size_t)h * S + s) * N + i0 + u] = (float)c + self_count(pi[u], thr[h]);
         }
 }
 
@@ -881,7 +889,7 @@ __global__ __launch_bounds__(256) void collision_grid_kernel(const float2* __res
         }
         if (PASS == 1) {
 #pragma unroll
-            for (int h = 0; h < T; ++h) counts[((size_t)h * S + s) * N + i] = (float)acc[h];
+            for (int h = 0; h < T; ++h) counts[((size_t)h * S + s) * N + i] = (float)acc[h] + self_count(pi, thr[h]);
         }
     }
 }
@@ -944,7 +952,7 @@ __device__ __forceinline__ void cc_fast_slice(const float2* __restrict__ ps, int
         int c = cnt[h];
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-        if (lane == 0) out[(size_t)h * hstride] = (float)c;
+        if (lane == 0) out[(size_t)h * hstride] = (float)c + self_count(pi, thr[h]);
     }
 }
 

@@ -210,8 +210,10 @@ def test_calc_acceleration_matches_reference(ver, ds):
 
 
 def test_collision_counts_fast_path_equals_general_and_oracle(oracle):
-    """S <= 25 takes the streaming kernel, S > 25 the general one (friends rule active): both against
-    the oracle's collision_detection(...).sum(-1), incl. a multi-tile N and thresholds on exact distances."""
+    """S <= 25 takes the streaming kernel (collision_counts_fast_kernel<., 3>), S > 25 with these 3 thresholds the cell-grid
+    form (collision_grid_kernel<3, .>, friends rule active; the scratch-free collision_counts_kernel is reached from
+    ops.collision_counts with 5 or more thresholds only, see test_collision_gpu.py): both against the oracle's
+    collision_detection(...).sum(-1), incl. a multi-tile N and thresholds on exact distances."""
     from piml_amd import ops
     rng = np.random.default_rng(5)
     for S, N in ((4, 700), (1, 5000), (25, 130), (26, 130), (40, 90)):
