@@ -757,6 +757,34 @@ int piml_group_members(const float* P, const float* M, int S, int T, int N, int 
                        void* stream);
 
 /*
+ * The host half of the group statistics on the device (groupstats.hip): the link rule, the connected
+ * components of the links and the sizes of the groups, for S members in ONE launch with no host read -- what stands between
+ * piml_group_pairs and piml_group_members.  edges (S, cap, 4) int32 rows (i, j, co, near) in any order, as piml_group_pairs
+ * writes them, and n_edges (S) int32 its true counts: min(max(n_edges[s], 0), cap) rows of member s are read, the others
+ * never.  trk_steps, trk_path (S, N) int64 as piml_group_pairs writes them.  A row is a link when
+ * near 1024 >= share_q co in 64-bit integers (and both indices lie in [0, N): any other row is no link); a track is eligible
+ * when trk_steps >= min_frames; the groups are the connected components of the links.
+ *   candidates (S) int64 = n_edges; links (S) int64 the rows that are links;
+ *   group_id (S, N) int32: the smallest slot of the track's component, -1 for a track that is not eligible;
+ *   size_tracks, size_path, size_steps (S, g_max + 1) int64: at index k = min(size, g_max) the eligible tracks in groups of
+ *     that many eligible tracks and the sums of their trk_path and trk_steps (index 0 stays 0);
+ *   workspace (S, N) int32 scratch; status (S) int32: 0, or 1 when member s's labels had not settled after N rounds (they
+ *     always do: a non-zero word is a defect of the kernel and its rows are not to be used).
+ * Every output element is written by the launch itself: nothing is zeroed before and nothing accumulates across calls.
+ * One workgroup of 256 lanes per member: labels start at their own slot in the group_id row; a round lowers both ends of
+ * every link to the smaller label (integer atomic minimum) and then jumps label[x] to label[label[x]], until a round
+ * changes nothing; the sizes by integer atomics, the tables in LDS.  Integers only, so the result is the same bit for bit
+ * whatever the order of the rows and of the lanes, and equal to piml_amd.groupstats.host_rows on the same rows.  One launch,
+ * capturable.  S or N == 0: success, nothing is done.
+ * hipErrorInvalidValue, before any HIP call: S, N or cap < 0, N > 65536, g_max outside 1..64, min_frames < 1, share_q
+ * outside 1..1024; then, unless there is nothing to do, a NULL pointer (edges may be NULL when cap == 0).
+ */
+int piml_group_components(const int* edges, const int* n_edges, const long long* trk_steps, const long long* trk_path, int S,
+                          int N, int cap, int min_frames, int share_q, int g_max, long long* candidates, long long* links,
+                          int* group_id, long long* size_tracks, long long* size_path, long long* size_steps, int* workspace,
+                          int* status, void* stream);
+
+/*
  * utils.calc_acceleration (src/utils/utils.py:31-100): version 0/1/2 = 'v0'/'v1'/'v2' with the
  * caller-supplied constants (A, B, C, D, theta [rad]); rows of >= 2 floats -> acc (rows, 2).
  */

@@ -163,6 +163,7 @@ SIGNATURES = {
                         _p],
     'piml_group_pairs': [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p, _p, _p],
     'piml_group_members': [_p, _p, _i, _i, _i, _i, _i, _p, _i, _f, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p, _p],
+    'piml_group_components': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     'piml_calc_acceleration': [_p, _z, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p],
     'piml_rollout_step': [_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p,
                           _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p],

@@ -19,7 +19,14 @@ the neighbours as `simulate --law mlapm` runs it (piml_mlapm_rollout_fit_loss_gr
 --match-stats fits the law to crowd statistics instead of trajectories (calibrate_mlapm_to_stats): the clip becomes an
 open-world scene (scenarios.clip_scenario), every generation of a derivative-free search runs population x seeds members
 in one ensemble (MLAPM.simulate_sweep's law table), and the objective is the distance between each candidate's pooled
-crowd / pair statistics and the clip's own (stats_objective)."""
+crowd / pair statistics and the clip's own (stats_objective).
+
+    python -m piml_amd.calibrate --data clip.npy --match-stats --scene-groups auto|FILE.json --fit Ag,group_dist --init Ag=3
+                                 [--match crowd,pairs,groups] --out grouped.json
+
+--scene-groups keeps the clip's groups as arrival units (scenarios.clip_scenario(groups=)), the candidates run the group
+cohesion term (Ag, group_dist) and the group statistics join the objective; grouped.json is what
+`simulate --params` reads."""
 import argparse
 import json
 import math
@@ -34,6 +41,8 @@ import torch  # noqa: E402
 PARAM_NAMES = ('tau', 'A', 'B', 'C', 'D', 'theta')
 # the wall term of the scene runs (MLAPM(..., Aw=, Bw=)): fitted by calibrate_mlapm_to_stats only, and never by default
 WALL_PARAM_NAMES = ('Aw', 'Bw')
+# the group term of a grouped clip scene's runs (MLAPM(..., Ag=[, group_dist=])): fitted by calibrate_mlapm_to_stats only
+GROUP_PARAM_NAMES = ('Ag', 'group_dist')
 # the constants src/main_mlapm.py:16 types in
 DEFAULT_INIT = {'tau': 0.5, 'A': 7.55, 'B': -3.0, 'C': 0.2, 'D': -0.3, 'theta': 56.0}
 SMALL_FRAME = 64          # frames up to this many agents: a lane per focal agent; above: a wave per focal agent
@@ -408,23 +417,33 @@ def calibrate_mlapm(data, version='GC', init=None, fit=PARAM_NAMES, steps=500, l
 
 OBJECTIVE_KEYS = {'crowd': ('fd_distance', 'map_distance', 'mean_speed_diff'),
                   'pairs': ('ttc_l1', 'nn_l1', 'overlap_rate_diff'),
-                  'obstacles': ('hit_track_fraction_diff', 'contact_rate_diff', 'clearance_l1')}
-DEFAULT_BOUNDS = {'tau': (1e-3, None), 'Aw': (0.0, None), 'Bw': (None, 0.0)}
+                  'obstacles': ('hit_track_fraction_diff', 'contact_rate_diff', 'clearance_l1'),
+                  'groups': ('group_fraction_diff', 'size_l1', 'member_distance_l1', 'abreast_l1', 'speed_ratio_diff')}
+# speed_ratio_diff needs min_count GROUPED tracks on both sides, which a recorded clip does not have (GC 11, UCY 26): NaN at
+# any honest min_count, and a NaN term of non-zero weight makes J infinite -- so it is off unless `weights` switches it on
+DEFAULT_WEIGHTS = {'speed_ratio_diff': 0.0}
+DEFAULT_BOUNDS = {'tau': (1e-3, None), 'Aw': (0.0, None), 'Bw': (None, 0.0), 'Ag': (0.0, None), 'group_dist': (0.0, None)}
+GROUP_OPTION_KEYS = ('radius', 'dv_max', 'v_min', 'min_time', 'share', 'r_bin', 'r_bins', 'a_bins')
 
 
 def stats_objective(crowd=None, pairs=None, ref_crowd=None, ref_pairs=None, weights=None, min_count=50, obstacles=None,
-                    ref_obstacles=None):
+                    ref_obstacles=None, groups=None, ref_groups=None):
     """(J, terms): how far simulated statistics are from a reference's.  crowd / ref_crowd: CrowdStats, pairs / ref_pairs:
-    PairStats, obstacles / ref_obstacles: ObstacleStats; a side takes part when both of its statistics are given.  terms is
-    the union of compare_crowd_stats(crowd, ref_crowd, min_count), compare_pair_stats(pairs, ref_pairs, min_count) and
-    compare_obstacle_stats(obstacles, ref_obstacles, min_count) for the sides given, and
+    PairStats, obstacles / ref_obstacles: ObstacleStats, groups / ref_groups: GroupStats; a side takes part when both of its
+    statistics are given.  terms is
+    the union of compare_crowd_stats(crowd, ref_crowd, min_count), compare_pair_stats(pairs, ref_pairs, min_count),
+    compare_obstacle_stats(obstacles, ref_obstacles, min_count) and compare_group_stats(groups, ref_groups, min_count) for
+    the sides given, and
     J = sum_k w_k |terms[k]| over fd_distance, map_distance, mean_speed_diff (crowd), ttc_l1, nn_l1, overlap_rate_diff
-    (pairs) and hit_track_fraction_diff, contact_rate_diff, clearance_l1 (obstacles), every weight 1.0 unless `weights`
-    names it.  map_distance is left out when it is None (no common map); a NaN
-    term of non-zero weight makes J = inf.  ValueError: no side given, or a weight for an unknown key."""
+    (pairs), hit_track_fraction_diff, contact_rate_diff, clearance_l1 (obstacles) and group_fraction_diff, size_l1,
+    member_distance_l1, abreast_l1, speed_ratio_diff (groups), every weight 1.0 unless `weights` names it -- but
+    speed_ratio_diff, whose default weight is 0.0 (DEFAULT_WEIGHTS: it needs min_count grouped tracks on both sides, more
+    than a recorded clip holds).  map_distance is left out when it is None (no common map); a term of weight zero is skipped
+    before it is looked at, and a NaN term of non-zero weight makes J = inf.  ValueError: no side given, or a weight for an
+    unknown key."""
     from .crowdstats import compare_crowd_stats
     from .pairstats import compare_pair_stats
-    known = OBJECTIVE_KEYS['crowd'] + OBJECTIVE_KEYS['pairs'] + OBJECTIVE_KEYS['obstacles']
+    known = OBJECTIVE_KEYS['crowd'] + OBJECTIVE_KEYS['pairs'] + OBJECTIVE_KEYS['obstacles'] + OBJECTIVE_KEYS['groups']
     unknown = sorted(set(weights or {}) - set(known))
     if unknown:
         raise ValueError(f'stats_objective: weights for unknown terms {unknown} (of {known})')
@@ -439,11 +458,15 @@ def stats_objective(crowd=None, pairs=None, ref_crowd=None, ref_pairs=None, weig
         from .obstaclestats import compare_obstacle_stats
         terms.update(compare_obstacle_stats(obstacles, ref_obstacles, min_count))
         keys += OBJECTIVE_KEYS['obstacles']
+    if groups is not None and ref_groups is not None:
+        from .groupstats import compare_group_stats
+        terms.update(compare_group_stats(groups, ref_groups, min_count))
+        keys += OBJECTIVE_KEYS['groups']
     if not keys:
-        raise ValueError('stats_objective: neither crowd, pair nor obstacle statistics with a reference')
+        raise ValueError('stats_objective: neither crowd, pair, obstacle nor group statistics with a reference')
     J = 0.0
     for k in keys:
-        w = float((weights or {}).get(k, 1.0))
+        w = float((weights or {}).get(k, DEFAULT_WEIGHTS.get(k, 1.0)))
         if terms[k] is None or w == 0.0:
             continue
         if math.isnan(terms[k]):
@@ -460,18 +483,22 @@ class _StatsEvaluator:
     """calibrate_mlapm_to_stats' objective on the GPU: list of candidate dicts -> list of J, one SweepRun generation each."""
 
     def __init__(self, scenario, reference, frames, seeds, population, radius, capacity, crowd_kw, pair_kw, weights,
-                 min_count, device, obstacle_kw=None, wall_cutoff=None):
+                 min_count, device, obstacle_kw=None, wall_cutoff=None, group_kw=None, components='device'):
         from . import crowdstats, pairstats
         from .models.mlapm import DEFAULT_WALL_CUTOFF, SweepRun
-        self.ref_obstacles = None
+        self.ref_obstacles = self.ref_groups = None
         if isinstance(reference, (tuple, list)):
-            if len(reference) == 3:                  # (crowd, pairs, obstacles): the obstacle side takes part
+            if len(reference) == 4:                  # (crowd, pairs, obstacles, groups): the group side takes part too
+                self.ref_crowd, self.ref_pairs, self.ref_obstacles, self.ref_groups = reference
+            elif len(reference) == 3:                # (crowd, pairs, obstacles): the obstacle side takes part
                 self.ref_crowd, self.ref_pairs, self.ref_obstacles = reference
             else:
                 self.ref_crowd, self.ref_pairs = reference
             if obstacle_kw is None and self.ref_obstacles is not None:
                 obstacle_kw = _options_of(self.ref_obstacles, ('dt', 'radius', 'hit_radius', 'r_bin', 'r_bins', 'tau_bin',
                                                                'tau_bins', 'box'))
+            if group_kw is None and self.ref_groups is not None:
+                group_kw = _options_of(self.ref_groups, GROUP_OPTION_KEYS)
             if crowd_kw is None and self.ref_crowd is not None:
                 crowd_kw = crowdstats.call_options(self.ref_crowd)
             if pair_kw is None and self.ref_pairs is not None:
@@ -487,14 +514,15 @@ class _StatsEvaluator:
             self.ref_pairs = pairstats.pair_stats_of_raw(reference, **dict(pair_kw or {}))
             if frames is None:
                 frames = int(torch.as_tensor(reference.position).shape[0])
-        if self.ref_crowd is None and self.ref_pairs is None and self.ref_obstacles is None:
+        if self.ref_crowd is None and self.ref_pairs is None and self.ref_obstacles is None and self.ref_groups is None:
             raise ValueError('calibrate_mlapm_to_stats: the reference holds no statistics')
         self.crowd_kw, self.pair_kw, self.obstacle_kw = dict(crowd_kw or {}), dict(pair_kw or {}), dict(obstacle_kw or {})
+        self.group_kw, self.components = dict(group_kw or {}), components
         self.weights, self.min_count, self.radius = weights, min_count, radius
         self.frames = 200 if frames is None else int(frames)
         self.run = SweepRun(scenario, self.frames, population, seeds, capacity=capacity, device=device,
                             wall_cutoff=DEFAULT_WALL_CUTOFF if wall_cutoff is None else wall_cutoff)
-        self.seconds = {'run': 0.0, 'crowd': 0.0, 'pairs': 0.0, 'obstacles': 0.0, 'host': 0.0}
+        self.seconds = {'run': 0.0, 'crowd': 0.0, 'pairs': 0.0, 'obstacles': 0.0, 'groups': 0.0, 'host': 0.0}
         self.last_terms = []
 
     def __call__(self, cands):
@@ -526,6 +554,12 @@ class _StatsEvaluator:
             kw = {'dt': float(sw.time_unit), **self.obstacle_kw}
             obstacles = obstacle_stats(sw.position, sw.velocity, mask, sw.obstacles, n_active=n_active, **kw)
         t3b = time.perf_counter()
+        groups = None
+        if self.ref_groups is not None:              # one call for every member: both passes and the components between them
+            from .groupstats import group_stats
+            kw = {'dt': float(sw.time_unit), **self.group_kw}
+            groups = group_stats(sw.position, mask, n_active=n_active, components=self.components, **kw)
+        t3c = time.perf_counter()
         out, self.last_terms = [], []
         for c in range(sw.n_candidates):
             group = sw.members_of(c)
@@ -536,11 +570,13 @@ class _StatsEvaluator:
             J, terms = stats_objective(None if crowd is None else crowd.select(group).pooled(),
                                        None if pairs is None else pairs.select(group).pooled(),
                                        self.ref_crowd, self.ref_pairs, self.weights, self.min_count,
-                                       None if obstacles is None else obstacles.select(group).pooled(), self.ref_obstacles)
+                                       None if obstacles is None else obstacles.select(group).pooled(), self.ref_obstacles,
+                                       None if groups is None else groups.select(group).pooled(), self.ref_groups)
             out.append(J)
             self.last_terms.append(terms)
         t4 = time.perf_counter()
-        for k, dt in zip(('run', 'crowd', 'pairs', 'obstacles', 'host'), (t1 - t0, t2 - t1, t3 - t2, t3b - t3, t4 - t3b)):
+        for k, dt in zip(('run', 'crowd', 'pairs', 'obstacles', 'groups', 'host'),
+                         (t1 - t0, t2 - t1, t3 - t2, t3b - t3, t3c - t3b, t4 - t3c)):
             self.seconds[k] += dt
         return out
 
@@ -548,8 +584,17 @@ class _StatsEvaluator:
 def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=PARAM_NAMES, frames=None, seeds=range(8),
                              population=16, generations=30, elite=0.25, sigma=0.2, sigma_floor=1e-3, bounds=None,
                              weights=None, crowd_kw=None, pair_kw=None, search_seed=0, radius=0.3, capacity=None,
-                             evaluate=None, min_count=50, device='cuda', obstacle_kw=None, wall_cutoff=None):
+                             evaluate=None, min_count=50, device='cuda', obstacle_kw=None, wall_cutoff=None, group_kw=None):
     """Fit MLAPM's constants so that the law, run open-world in `scenario`, reproduces the reference's crowd statistics.
+
+    The group term: fit may also name Ag, group_dist (GROUP_PARAM_NAMES), and init may carry them: the candidates then run a
+    grouped clip scene (scenarios.clip_scenario(groups=); ValueError before anything is launched for any other scene) with
+    the group term (MLAPM(..., Ag=, group_dist=)).  init must hold Ag when either is fitted or present -- the term has no
+    default; about 3 m/s^2 (Moussaid et al. 2010) is a starting point -- and group_dist defaults to 0.5; Ag >= 0 and
+    group_dist >= 0 are bounded so by default.  A reference 4-tuple (CrowdStats | None, PairStats | None, ObstacleStats |
+    None, GroupStats | None) adds the group side: one group_stats call (group_kw, default the reference's radius, dv_max,
+    v_min, min_time, share and bins; dt the scene's; the components on the device) covers every member of a
+    generation and enters stats_objective with the reference's.  The result's params then carry Ag and group_dist.
 
     The wall term: fit may also name Aw, Bw (WALL_PARAM_NAMES), and init may carry Aw, Bw: the candidates then run the
     frames with the wall term (MLAPM(..., Aw=, Bw=, wall_cutoff=wall_cutoff), default cutoff 2.0 m; the cutoff is the
@@ -587,24 +632,34 @@ def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=P
     if version not in ops.MLAPM_VARIANTS:
         raise NotImplementedError(version)
     fit = tuple(fit)
-    unknown = [k for k in fit if k not in PARAM_NAMES + WALL_PARAM_NAMES]
+    every = PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES
+    unknown = [k for k in fit if k not in every]
     if unknown or not fit:
-        raise ValueError(f'constants to fit: names of {PARAM_NAMES + WALL_PARAM_NAMES} expected, got {fit}')
+        raise ValueError(f'constants to fit: names of {every} expected, got {fit}')
     walls = any(k in (init or {}) for k in WALL_PARAM_NAMES)
     if (walls or any(k in WALL_PARAM_NAMES for k in fit)) and not all(k in (init or {}) for k in WALL_PARAM_NAMES):
         raise ValueError(f'the wall term has no default: init must hold both of {WALL_PARAM_NAMES} (fit {fit}, init '
                          f'{sorted(init or {})})')
-    names = PARAM_NAMES + (WALL_PARAM_NAMES if walls else ())
+    grouped = any(k in (init or {}) for k in GROUP_PARAM_NAMES)
+    if (grouped or any(k in GROUP_PARAM_NAMES for k in fit)) and 'Ag' not in (init or {}):
+        raise ValueError(f'the group term has no default: init must hold Ag (fit {fit}, init {sorted(init or {})})')
+    names = PARAM_NAMES + (WALL_PARAM_NAMES if walls else ()) + (GROUP_PARAM_NAMES if grouped else ())
     population, generations = int(population), int(generations)
     if population < 2 or generations < 1:
         raise ValueError(f'population >= 2 and generations >= 1 expected, got {population}, {generations}')
     if not 0 < float(elite) <= 1 or not float(sigma) > 0 or not float(sigma_floor) >= 0:
         raise ValueError(f'elite in (0, 1], sigma > 0, sigma_floor >= 0 expected, got {elite}, {sigma}, {sigma_floor}')
-    bad = sorted(set(bounds or {}) - set(PARAM_NAMES + WALL_PARAM_NAMES))
+    bad = sorted(set(bounds or {}) - set(every))
     if bad:
         raise ValueError(f'bounds for unknown constants {bad}')
     limits = {**DEFAULT_BOUNDS, **(bounds or {})}
     start = {**DEFAULT_INIT, **(init or {})}
+    if grouped:
+        from .models.mlapm import DEFAULT_GROUP_DIST, check_scene_groups, group_args
+        start.setdefault('group_dist', DEFAULT_GROUP_DIST)
+        group_args({k: start[k] for k in GROUP_PARAM_NAMES})
+        if scenario is not None:
+            check_scene_groups(scenario)
     start = {k: float(start[k]) for k in names}
     if walls:
         from .models.mlapm import DEFAULT_WALL_CUTOFF, wall_args
@@ -614,7 +669,7 @@ def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=P
     terms_of = None
     if evaluate is None:
         evaluate = terms_of = _StatsEvaluator(scenario, reference, frames, seeds, population, radius, capacity, crowd_kw,
-                                              pair_kw, weights, min_count, device, obstacle_kw, wall_cutoff)
+                                              pair_kw, weights, min_count, device, obstacle_kw, wall_cutoff, group_kw)
     scale = np.array([abs(start[k]) if start[k] != 0 else 1.0 for k in fit])
     lo = np.array([-np.inf if limits.get(k, (None, None))[0] is None else limits[k][0] for k in fit], np.float64)
     hi = np.array([np.inf if limits.get(k, (None, None))[1] is None else limits[k][1] for k in fit], np.float64)
@@ -666,18 +721,19 @@ def _parse_init(text):
     out = {}
     for item in filter(None, (s.strip() for s in (text or '').split(','))):
         k, _, val = item.partition('=')
-        if k not in PARAM_NAMES + WALL_PARAM_NAMES or not _:
-            raise argparse.ArgumentTypeError(f'--init expects name=value with names in {PARAM_NAMES + WALL_PARAM_NAMES}, '
-                                             f'got {item!r}')
+        if k not in PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES or not _:
+            raise argparse.ArgumentTypeError('--init expects name=value with names in '
+                                             f'{PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES}, got {item!r}')
         out[k] = float(val)
     return out
 
 
 def _parse_fit(text):
     names = tuple(filter(None, (s.strip() for s in text.split(','))))
-    bad = [k for k in names if k not in PARAM_NAMES + WALL_PARAM_NAMES]
+    bad = [k for k in names if k not in PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES]
     if bad or not names:
-        raise argparse.ArgumentTypeError(f'--fit expects names from {PARAM_NAMES + WALL_PARAM_NAMES}, got {text!r}')
+        raise argparse.ArgumentTypeError(f'--fit expects names from {PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES}, '
+                                         f'got {text!r}')
     return names
 
 
@@ -704,8 +760,12 @@ def get_args(argv=None):
                    help="fit the law to the clip's crowd statistics, run open-world in the clip's own scene "
                         '(calibrate_mlapm_to_stats), instead of to its trajectories')
     p.add_argument('--match', type=str, default=None,
-                   help='--match-stats: the statistics to match (crowd, pairs, obstacles); default crowd,pairs, and obstacles '
-                        'too when the law has a wall term (--init Aw=..,Bw=..)')
+                   help='--match-stats: the statistics to match (crowd, pairs, obstacles, groups); default crowd,pairs, '
+                        'obstacles too when the law has a wall term (--init Aw=..,Bw=..) and groups too when it has a group '
+                        'term (--init Ag=..)')
+    p.add_argument('--scene-groups', dest='scene_groups', type=str, default=None,
+                   help="--match-stats: the clip's groups as arrival units, 'auto' (found by groupstats) or a JSON file of "
+                        'lists of track indices (simulate --scene-groups); needed by a group term')
     p.add_argument('--wall-cutoff', dest='wall_cutoff', type=float, default=None,
                    help='--match-stats with a wall term: its cutoff in metres (default 2.0); not fitted')
     p.add_argument('--stats-density', dest='stats_density', choices=('gaussian', 'voronoi'), default='gaussian',
@@ -730,14 +790,31 @@ def get_args(argv=None):
             p.error('the wall term has no default: --init must give Aw and Bw (the literature starts at Aw=50,Bw=-5)')
     elif a.wall_cutoff is not None:
         p.error('--wall-cutoff needs a wall term (--init Aw=..,Bw=..)')
+    group_names = [k for k in GROUP_PARAM_NAMES if k in a.init or k in a.fit]
+    if group_names:
+        if not a.match_stats:
+            p.error(f'{group_names}: the group term is fitted by --match-stats only (it exists in the scene runs, not in the '
+                    'one-step or rollout fit)')
+        if 'Ag' not in a.init:
+            p.error('the group term has no default: --init must give Ag (the literature starts at Ag=3)')
+        if a.scene_groups is None:
+            p.error("the group term needs the clip's groups: --scene-groups auto or FILE.json")
+    if a.scene_groups is not None and not a.match_stats:
+        p.error('--scene-groups belongs to --match-stats')
     if a.match_stats:
         if len(a.data) != 1:
             p.error('--match-stats takes one clip')
         if a.match is None:
-            a.match = 'crowd,pairs,obstacles' if wall_names else 'crowd,pairs'
+            a.match = ('crowd,pairs,obstacles' if wall_names else 'crowd,pairs') + (',groups' if group_names else '')
         a.match = tuple(filter(None, (x.strip() for x in a.match.split(','))))
-        if not a.match or any(x not in ('crowd', 'pairs', 'obstacles') for x in a.match):
-            p.error(f"--match: 'crowd', 'pairs', 'obstacles' or several expected, got {a.match}")
+        if not a.match or any(x not in ('crowd', 'pairs', 'obstacles', 'groups') for x in a.match):
+            p.error(f"--match: 'crowd', 'pairs', 'obstacles', 'groups' or several expected, got {a.match}")
+        if a.scene_groups is not None and a.scene_groups != 'auto':
+            try:
+                from .simulate import load_scene_groups
+                a.scene_groups = load_scene_groups(a.scene_groups)
+            except (OSError, ValueError) as ex:
+                p.error(f'--scene-groups: {ex}')
         try:
             from .crowdstats import check_density
             check_density(a.stats_density, a.stats_cutoff)
@@ -810,7 +887,8 @@ def _main_rollout(a, raw, init):
 def _main_stats(a, raw, init):
     from . import crowdstats, pairstats, scenarios
     try:
-        scene = scenarios.clip_scenario(raw, frames=a.scene_frames, jitter=a.scene_jitter)
+        group_kw = {} if a.scene_groups is None else {'groups': a.scene_groups}
+        scene = scenarios.clip_scenario(raw, frames=a.scene_frames, jitter=a.scene_jitter, **group_kw)
     except ValueError as ex:
         sys.exit(f'--match-stats: {ex}')
     lo, hi = a.scene_frames or (0, int(raw.position.shape[0]))
@@ -827,13 +905,17 @@ def _main_stats(a, raw, init):
             ref_obstacles = obstaclestats.obstacle_stats_of_raw(raw, scene.obstacles, frames=(lo, hi))
         except ValueError as ex:
             sys.exit(f'--match obstacles: {ex}')
-    res = calibrate_mlapm_to_stats(scene, (ref_crowd, ref_pairs, ref_obstacles), version=a.version, init=init, fit=a.fit,
+    ref_groups = None
+    if 'groups' in a.match:
+        from .groupstats import group_stats_of_raw
+        ref_groups = group_stats_of_raw(raw, frames=(lo, hi))
+    res = calibrate_mlapm_to_stats(scene, (ref_crowd, ref_pairs, ref_obstacles, ref_groups), version=a.version, init=init, fit=a.fit,
                                    frames=hi - lo, seeds=a.seeds, population=a.population, generations=a.generations,
                                    search_seed=a.search_seed, radius=a.radius, wall_cutoff=a.wall_cutoff)
     print(f'[calibrate] {a.version} against the statistics ({", ".join(a.match)}) of frames {lo}:{hi}, {a.population} '
           f'candidates x {len(a.seeds)} seeds x {a.generations} generations: objective {res.initial_loss:.6g} -> '
           f'{res.final_loss:.6g} ({res.status})')
-    print('[calibrate] ' + ', '.join(f'{k}={res.params[k]:.6g}' for k in PARAM_NAMES + WALL_PARAM_NAMES + ('wall_cutoff',)
+    print('[calibrate] ' + ', '.join(f'{k}={res.params[k]:.6g}' for k in PARAM_NAMES + WALL_PARAM_NAMES + ('wall_cutoff',) + GROUP_PARAM_NAMES
                                      if k in res.params))
     print('[calibrate] terms: ' + ', '.join(f'{k} {v:.4g}' if isinstance(v, float) else f'{k} {v}'
                                            for k, v in (res.terms or {}).items()))

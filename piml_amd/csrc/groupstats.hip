@@ -259,6 +259,112 @@ __global__ void __launch_bounds__(GS_THREADS) group_members_kernel(GroupMemberAr
     }
 }
 
+// group_components_kernel: the link rule, the connected components and the sizes between the passes, one
+// workgroup per member.  label (the group_id row) starts at label[x] = x; a round is an edge sweep -- every link lowers the
+// larger of its two ends' labels to the smaller with an integer atomic minimum -- and a pointer-jumping sweep
+// label[x] = min(label[x], label[label[x]]).  Labels only decrease, label[x] <= x, and a label never leaves its component,
+// so when a round changes nothing every track of a component carries the component's smallest slot, whatever the order of
+// the rows and of the lanes.  After k edge sweeps the tracks within k links of that slot carry it, so N rounds always
+// suffice; `status` is 1 if they did not (a logic error, never a spin).  Every access to a label another lane may be
+// lowering is an atomic of agent scope, and a fence and a barrier stand between the sweeps.  The sizes: count[root] over the
+// eligible tracks in the int32 workspace row, then the three tables by 64-bit integer atomics in LDS, stored once.
+struct GroupCompArgs {
+    const int* edges;                              // (S, cap, 4)
+    const int* n_edges;                            // (S)
+    const long long *trk_steps, *trk_path;         // (S, N)
+    int S, N, cap, min_frames, share_q, G;
+    long long *candidates, *links;                 // (S)
+    int* group_id;                                 // (S, N): the labels
+    long long *size_tracks, *size_path, *size_steps;                              // (S, G + 1)
+    int *work, *status;                            // (S, N), (S)
+};
+
+constexpr int GS_MAX_G = 64;
+
+__device__ __forceinline__ int gs_label(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ void gs_sweep_end() {   // what this sweep lowered is seen by every lane of the next
+    __threadfence();
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(GS_THREADS) group_components_kernel(GroupCompArgs a) {
+    __shared__ unsigned long long table[3][GS_MAX_G + 1];
+    __shared__ int n_links, changed;
+    const int tid = threadIdx.x, s = blockIdx.x, N = a.N, G = a.G;
+    const int4* rows = reinterpret_cast<const int4*>(a.edges) + (long long)s * a.cap;
+    const int listed = a.n_edges[s];
+    const int ne = min(max(listed, 0), a.cap);
+    int* label = a.group_id + (long long)s * N;
+    int* count = a.work + (long long)s * N;
+    const long long* steps = a.trk_steps + (long long)s * N;
+    const long long* path = a.trk_path + (long long)s * N;
+    const auto is_link = [&](int4 r) {             // (i, j, co, near): the share rule in 64-bit integers, both ends in range
+        return (long long)r.w * 1024 >= (long long)a.share_q * r.z && r.x >= 0 && r.x < N && r.y >= 0 && r.y < N;
+    };
+    if (tid == 0) n_links = 0, changed = 0;
+    for (int k = tid; k < 3 * (GS_MAX_G + 1); k += GS_THREADS) (&table[0][0])[k] = 0ull;
+    for (int x = tid; x < N; x += GS_THREADS) {
+        __hip_atomic_store(label + x, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(count + x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    int mine = 0;
+    for (int e = tid; e < ne; e += GS_THREADS) mine += is_link(rows[e]) ? 1 : 0;
+    if (mine) atomicAdd(&n_links, mine);
+    gs_sweep_end();
+    const int links = n_links;
+    bool settled = links == 0;
+    for (int round = 0; round < N && !settled; ++round) {
+        int ch = 0;
+        for (int e = tid; e < ne; e += GS_THREADS) {
+            const int4 r = rows[e];
+            if (!is_link(r)) continue;
+            const int li = gs_label(label + r.x), lj = gs_label(label + r.y);
+            if (li < lj) atomicMin(label + r.y, li), ch = 1;
+            else if (lj < li) atomicMin(label + r.x, lj), ch = 1;
+        }
+        gs_sweep_end();
+        for (int x = tid; x < N; x += GS_THREADS) {
+            const int l = gs_label(label + x);     // 0 <= label[x] <= x < N always
+            const int ll = gs_label(label + l);
+            if (ll < l) atomicMin(label + x, ll), ch = 1;
+        }
+        if (ch) atomicOr(&changed, 1);
+        gs_sweep_end();
+        settled = changed == 0;
+        __syncthreads();                           // every lane has read the word
+        if (tid == 0) changed = 0;
+        __syncthreads();
+    }
+    // the sizes of the components over the eligible tracks
+    for (int x = tid; x < N; x += GS_THREADS)
+        if (steps[x] >= a.min_frames) atomicAdd(count + gs_label(label + x), 1);
+    gs_sweep_end();
+    for (int x = tid; x < N; x += GS_THREADS) {
+        const long long st = steps[x];
+        if (st >= a.min_frames) {
+            const int k = min(gs_label(count + gs_label(label + x)), G);
+            atomicAdd(&table[0][k], 1ull);
+            atomicAdd(&table[1][k], (unsigned long long)path[x]);
+            atomicAdd(&table[2][k], (unsigned long long)st);
+        } else {
+            label[x] = -1;                         // nobody else reads label[x] any more: the others read their own and a count
+        }
+    }
+    __syncthreads();
+    for (int k = tid; k <= G; k += GS_THREADS) {
+        a.size_tracks[(long long)s * (G + 1) + k] = (long long)table[0][k];
+        a.size_path[(long long)s * (G + 1) + k] = (long long)table[1][k];
+        a.size_steps[(long long)s * (G + 1) + k] = (long long)table[2][k];
+    }
+    if (tid == 0) {
+        a.candidates[s] = listed;
+        a.links[s] = links;
+        a.status[s] = settled ? 0 : 1;
+    }
+}
+
 // the arguments both entries share; no 64-bit sum overflows: dist_sum adds at most N (N - 1) / 2 T' terms below sqrt(r2) Q
 // (trk_path: T' <= 2^25 steps below 2^37.5 each)
 static bool gs_bad_common(int S, int T, int N, int t0, int t1, float r2, float dv2, float vm2) {
@@ -323,5 +429,26 @@ PIML_API int piml_group_members(const float* P, const float* M, int S, int T, in
     if (err == hipSuccess) err = hipMemsetAsync(link_frames, 0, (size_t)S * sizeof(long long), st);
     if (err != hipSuccess || n_links == 0 || t1 - t0 < 2) return err;
     hipLaunchKernelGGL(group_members_kernel, dim3((unsigned)(n_links < 65536 ? n_links : 65536)), dim3(GS_THREADS), 0, st, a);
+    return hipGetLastError();
+}
+
+PIML_API int piml_group_components(const int* edges, const int* n_edges, const long long* trk_steps, const long long* trk_path,
+                                   int S, int N, int cap, int min_frames, int share_q, int g_max, long long* candidates,
+                                   long long* links, int* group_id, long long* size_tracks, long long* size_path,
+                                   long long* size_steps, int* workspace, int* status, void* stream) {
+    if (S < 0 || N < 0 || cap < 0 || N > GS_MAX_N || g_max < 1 || g_max > GS_MAX_G || min_frames < 1 || share_q < 1 ||
+        share_q > 1024)
+        return hipErrorInvalidValue;
+    if (S == 0 || N == 0) return hipSuccess;
+    if ((cap > 0 && !edges) || !n_edges || !trk_steps || !trk_path || !candidates || !links || !group_id || !size_tracks ||
+        !size_path || !size_steps || !workspace || !status)
+        return hipErrorInvalidValue;
+    GroupCompArgs a{};
+    a.edges = edges, a.n_edges = n_edges, a.trk_steps = trk_steps, a.trk_path = trk_path;
+    a.S = S, a.N = N, a.cap = cap, a.min_frames = min_frames, a.share_q = share_q, a.G = g_max;
+    a.candidates = candidates, a.links = links, a.group_id = group_id;
+    a.size_tracks = size_tracks, a.size_path = size_path, a.size_steps = size_steps;
+    a.work = workspace, a.status = status;
+    hipLaunchKernelGGL(group_components_kernel, dim3((unsigned)S), dim3(GS_THREADS), 0, as_stream(stream), a);
     return hipGetLastError();
 }

@@ -2,8 +2,9 @@
 street walk with someone (Moussaid et al. 2010); groups walk side by side and more slowly than singles.  The siblings
 (crowdstats, pairstats, flowstats, trackstats, obstaclestats, linestats) cannot see it: pair statistics forget identities
 after one frame and track statistics follow one agent at a time.  This family keeps the identities of a pair through time:
-a pair sweep on the device (piml_group_pairs), the link rule and a union-find on the host, and the member statistics of
-the linked pairs on the device again (piml_group_members); ops_metrics.group_stats_frames runs the three for all members.
+a pair sweep on the device (piml_group_pairs), the link rule and a union-find on the host (or, with components='device',
+in piml_group_components: DESIGN 4.28), and the member statistics of the linked pairs on the device again
+(piml_group_members); ops_metrics.group_stats_frames runs the three for all members.
 
     python -m piml_amd.groupstats --data sim_0.npy [sim_1.npy ...] [--ref recorded.npy] [--frames a:b] [--radius 2.0]
                                   [--dv-max 0.5] [--min-time 2.0] [--share 0.8] [--out groups.json]
@@ -321,14 +322,18 @@ def make_options(dt, radius, dv_max, v_min, min_time, share, r_bin, r_bins, a_bi
 
 
 def group_stats(P, M, dt=0.08, radius=2.0, dv_max=0.5, v_min=0.1, min_time=2.0, share=0.8, r_bin=0.1, r_bins=20, a_bins=10,
-                frames=None, n_active=None, max_edges=None):
+                frames=None, n_active=None, max_edges=None, components='host'):
     """The group statistics of positions P (S, T, N, 2) and presence M (S, T, N) -- (T, N, .) is one member -- for all
     members at once: GroupStats.  dt the seconds per frame; two agents are together in a frame when they are closer than
     `radius` m, their velocities differ by less than `dv_max` m/s and both move at `v_min` m/s or more; a pair is linked when
     it is together for at least `min_time` s and for at least `share` of the frames both are present.  frames (a, b) the
     window; n_active (S) ints: member s's slots at or past n_active[s] never held an agent and are not swept; max_edges the
     cap on the candidate pairs per member (None: min(N (N - 1) / 2, 2^20); ValueError naming the count needed when it is too
-    small).  Every option is checked on the host before anything is launched."""
+    small).  components: 'host' (the default) runs the link rule, the components and the sizes in host_rows; 'device' runs
+    them in piml_group_components between the two passes -- the same GroupStats array for array, without the
+    interpreter loop per member.  Every option is checked on the host before anything is launched."""
+    if components not in ('host', 'device'):
+        raise ValueError(f"components: 'host' or 'device' expected, got {components!r}")
     from . import ops_metrics
     shape = tuple(getattr(P, 'shape', ()))
     T, N = (shape[-3], shape[-2]) if len(shape) in (3, 4) else (None, None)
@@ -342,10 +347,14 @@ def group_stats(P, M, dt=0.08, radius=2.0, dv_max=0.5, v_min=0.1, min_time=2.0, 
             raise ValueError(f'n_active: {n_active.numel()} bounds for {S} members')
         n_active = n_active.clamp(0, N).to(device=P.device, dtype=torch.int32)
     out = ops_metrics.group_stats_frames(P, M, dt, radius, dv_max, v_min, min_time, share, r_bin, int(r_bins), int(a_bins),
-                                         frames, n_active, max_edges)
+                                         frames, n_active, max_edges, components, G_MAX)
     host = {k: v.cpu().numpy() for k, v in out.items()}
     opts = make_options(dt, radius, dv_max, v_min, min_time, share, r_bin, r_bins, a_bins, frames)
-    host.update(host_rows(host, opts['min_frames'], opts['share_q']))
+    if components == 'device':
+        if host.pop('status').any():
+            raise RuntimeError('group_stats: piml_group_components did not settle (status != 0)')
+    else:
+        host.update(host_rows(host, opts['min_frames'], opts['share_q']))
     host['slices'] = np.full(S, frames[1] - frames[0], np.int64)
     return GroupStats(host, opts)
 

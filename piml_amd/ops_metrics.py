@@ -511,15 +511,59 @@ def group_members_frames(P, M, links, r2, dv2, vm2, r_bin=0.1, r_bins=20, a_bins
     return out
 
 
+GROUP_MAX_G = 64               # piml_group_components: the largest g_max
+GROUP_COMPONENT_ROWS = ('candidates', 'links', 'group_id', 'size_tracks', 'size_path', 'size_steps')
+
+
+def group_components_frames(edges, n_edges, trk_steps, trk_path, min_frames, share_q, g_max=8):
+    """The host half of the group statistics on the device (piml_group_components): edges (S, cap, 4) int32,
+    rows (i, j, co, near) in any order, n_edges (S) int32, trk_steps, trk_path (S, N) int64 GPU tensors -- what
+    group_pairs_frames returns, unsorted.  Returns a dict of GPU tensors, piml_amd.groupstats.host_rows' bit for bit:
+    candidates, links (S) int64, group_id (S, N) int32, size_tracks, size_path, size_steps (S, g_max + 1) int64, and status
+    (S) int32 (0; non-zero only if the kernel's rounds did not settle, a defect).  One launch that writes every element, no
+    host synchronisation (capturable in a graph)."""
+    for name, x, dt, nd in (('edges', edges, torch.int32, 3), ('n_edges', n_edges, torch.int32, 1),
+                            ('trk_steps', trk_steps, torch.int64, 2), ('trk_path', trk_path, torch.int64, 2)):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise _lib.PimlHipError(f'{name}: a GPU tensor expected')
+        if x.dtype != dt or x.dim() != nd:
+            raise ValueError(f'{name}: expected a {nd}-dimensional {dt} tensor, got {tuple(x.shape)} {x.dtype}')
+    dev = trk_steps.device
+    S, N = trk_steps.shape
+    if edges.shape[0] != S or edges.shape[2] != 4 or tuple(n_edges.shape) != (S,) or tuple(trk_path.shape) != (S, N) \
+            or any(x.device != dev for x in (edges, n_edges, trk_path)):
+        raise ValueError(f'expected edges ({S}, cap, 4), n_edges ({S},) and trk_path ({S}, {N}) on {dev}, got '
+                         f'{tuple(edges.shape)}, {tuple(n_edges.shape)}, {tuple(trk_path.shape)}')
+    edges, n_edges, trk_steps, trk_path = (x.contiguous() for x in (edges, n_edges, trk_steps, trk_path))
+    cap, G = edges.shape[1], int(g_max)
+    new = torch.zeros if S * N == 0 else torch.empty
+    i64, i32 = dict(device=dev, dtype=torch.int64), dict(device=dev, dtype=torch.int32)
+    out = {'candidates': new(S, **i64), 'links': new(S, **i64), 'group_id': new(S, N, **i32),
+           'size_tracks': new(S, max(G, 0) + 1, **i64), 'size_path': new(S, max(G, 0) + 1, **i64),
+           'size_steps': new(S, max(G, 0) + 1, **i64), 'status': new(S, **i32)}
+    work = torch.empty(S, N, **i32)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().piml_group_components(_ptr(edges) if cap > 0 else None, _ptr(n_edges), _ptr(trk_steps),
+                                                    _ptr(trk_path), S, N, cap, int(min_frames), int(share_q), G,
+                                                    *(_ptr(out[k]) for k in GROUP_COMPONENT_ROWS), _ptr(work),
+                                                    _ptr(out['status']), _stream()), 'piml_group_components')
+    return out
+
+
 def group_stats_frames(P, M, dt=0.08, radius=2.0, dv_max=0.5, v_min=0.1, min_time=2.0, share=0.8, r_bin=0.1, r_bins=20,
-                       a_bins=10, frames=None, n_active=None, max_edges=None):
+                       a_bins=10, frames=None, n_active=None, max_edges=None, components='host', g_max=8):
     """The device half of piml_amd.groupstats.group_stats: the pair sweep, the link rule, the member
     statistics.  P (S, T, N, 2), M (S, T, N) float32 GPU tensors, frames (a, b) or None, n_active (S) int32 GPU tensor or
     None.  Returns a dict of GPU tensors: edges (E, 5) int64, rows (member, i, j, co, near) of every candidate sorted by
     (member, i, j); n_edges (S) int64; trk_steps, trk_path (S, N), pairs, together (S) int64; and the rows of
     group_members_frames over the links (near * 1024 >= round(share * 1024) * co).  The candidate counts are read back
     between the passes (not capturable; group_pairs_frames alone is).  ValueError when a member has more than max_edges
-    candidates (None: min(N (N - 1) / 2, 2^20)), naming the count that was needed."""
+    candidates (None: min(N (N - 1) / 2, 2^20)), naming the count that was needed.  components='device' also returns the six
+    rows of the host half (candidates, links, group_id, size_tracks, size_path, size_steps) and `status` as GPU
+    tensors: group_components_frames on pass 1's unsorted rows, after the capacity check; 'host' (the default) leaves them to
+    piml_amd.groupstats.host_rows."""
+    if components not in ('host', 'device'):
+        raise ValueError(f"components: 'host' or 'device' expected, got {components!r}")
     r2, dv2, vm2, min_frames, share_q = group_thresholds(dt, radius, dv_max, v_min, min_time, share)
     raw = group_pairs_frames(P, M, r2, dv2, vm2, min_frames, frames, n_active, max_edges)
     n = raw['n_edges'].to(torch.int64)
@@ -528,6 +572,9 @@ def group_stats_frames(P, M, dt=0.08, radius=2.0, dv_max=0.5, v_min=0.1, min_tim
     if need > cap:
         raise ValueError(f'group_stats: a member has {need} candidate pairs, max_edges is {cap}: pass max_edges={need}')
     S = n.shape[0]
+    comp = None
+    if components == 'device':
+        comp = group_components_frames(raw['edges'], raw['n_edges'], raw['trk_steps'], raw['trk_path'], min_frames, share_q, g_max)
     rows = raw['edges'][:, :need].to(torch.int64)                                 # (S, need, 4)
     valid = torch.arange(need, device=n.device)[None, :] < n[:, None]
     member = torch.arange(S, device=n.device)[:, None].expand(S, need)
@@ -538,4 +585,6 @@ def group_stats_frames(P, M, dt=0.08, radius=2.0, dv_max=0.5, v_min=0.1, min_tim
     out = {'edges': edges, 'n_edges': n}
     out.update({k: raw[k] for k in GROUP_PAIR_ROWS})
     out.update(group_members_frames(P, M, edges[link][:, :3].to(torch.int32), r2, dv2, vm2, r_bin, r_bins, a_bins, frames))
+    if comp is not None:
+        out.update(comp)
     return out

@@ -512,7 +512,7 @@ class ScenarioResult(types.SimpleNamespace):
 
     def group_stats(self, **kw):
         """piml_amd.groupstats.group_stats of the run: who walks with whom, group size, spacing and formation (positions
-        only, dt = time_unit; slots past num_agents not swept)."""
+        only, dt = time_unit; slots past num_agents not swept; components='host' | 'device' as group_stats takes it)."""
         from .groupstats import group_stats
         kw.setdefault('dt', float(self.time_unit))
         return group_stats(self.position, self.mask_p, n_active=[self.num_agents], **kw)
@@ -603,7 +603,9 @@ class ScenarioEnsemble(types.SimpleNamespace):
 
     def group_stats(self, **kw):
         """piml_amd.groupstats.group_stats of every member in one call (dt = time_unit; member m's slots past its num_agents
-        not swept): member m's statistics are bitwise those of member(m).group_stats(**kw)."""
+        not swept): member m's statistics are bitwise those of member(m).group_stats(**kw).  components='device' runs the
+        link rule and the components of every member in one launch instead of a host loop per member; a
+        ScenarioSweep passes it on the same way."""
         from .groupstats import group_stats
         cap = self.position.shape[2]
         kw.setdefault('dt', float(self.time_unit))
