@@ -1128,6 +1128,59 @@ int piml_scenario_step_mlapm_groups(const piml_scenario* s, const piml_scenario_
                                     const piml_group_law* glaw_table_device, int init, int frame_offset, void* stream);
 
 /*
+ * A fluctuation term for the MLAPM scenario frame (ABI 35, additive): the fluctuation of Helbing and Molnar 1995 as an
+ * Ornstein-Uhlenbeck acceleration eta per agent, added to the force last, after the wall and group terms:
+ *   F = (((v0 e - v) / tau - sum) [+ W]) [+ G]) + eta',    eta' = rho eta + amp z   (float32, every operation rounded alone),
+ *   rho = exp(-dt / noise_tau) (0 for noise_tau == 0: white noise),  amp = An sqrt(1 - rho^2),
+ * An (m/s^2) the stationary standard deviation of each component.  The caller forms (rho, amp) in float64 and rounds them
+ * to float32 (piml_amd.ops_scenario.noise_law): piml_noise_law holds the two floats.
+ *
+ * z: two standard normals from Philox4x32-10, key = the member's seed, counter = (t lo, t hi, slot, 0x5CE40001), t =
+ * *frame_counter + frame_offset the frame stepped from; z_x from the words (w0, w1), z_y from (w2, w3), each
+ * (float)(sqrt(-2 ln u1) cos(2 pi u2)) in double with u1 = ((wa >> 8) + 1) 2^-24, u2 = (wb >> 8) 2^-24.  The draws depend
+ * on (seed, frame, slot) only, never on the dynamics, and the arrivals never on the noise.
+ *
+ * piml_noise_args.state: (members, capacity, 2) float32 in device memory, member-major like the state, eta of every slot;
+ * the caller zeroes it before frame 0 (a slot is one agent for the whole run: eta = 0 at birth, nothing is written at
+ * spawn).  Only the wave that steps live slot i of member m reads and writes state[m capacity + i]; absent and retired
+ * slots are not touched and draw nothing.  law: the term by value; law_table: (members) piml_noise_law in device memory,
+ * row m for member m, read on every launch (law is then not read).  A row with amp == 0 skips the draw, the state update and
+ * the add: that member's frame is piml_scenario_step_mlapm_groups' / _walls' / _laws' / piml_scenario_step_mlapm's bit for bit.
+ *
+ * piml_scenario_step_mlapm_noise takes what piml_scenario_step_mlapm_groups takes and steps the same frame: with g != NULL
+ * a grouped clip scene (r->spawn_law == PIML_SPAWN_CLIP_GROUPS), with g == NULL (then glaw and glaw_table_device NULL too)
+ * every other scene as piml_scenario_step_mlapm / _laws / _walls.  init == 1 is the grouped scene's init launch (g != NULL;
+ * the state is not read); every other scene's init launch is piml_scenario_step_members'.
+ *
+ * piml_noise_force: one OU step for every row of eta_in (members, N, 2): row (m, i) draws z with key seeds[m], frame
+ * `frame`, slot i, and eta_out = rho eta_in + amp z; z_out (may be NULL) gets z.  present (may be NULL: all) (members, N)
+ * bytes: a row with present == 0 is copied unchanged and its z is 0.  One thread per row; eta_out may be eta_in.  Bitwise the
+ * state the frame leaves and the value it adds.
+ * hipErrorInvalidValue (before any launch) -- both: rho not finite or outside [0, 1), amp not finite or negative (a by-value
+ * law; a table's rows live in device memory and cannot be checked).  piml_noise_force: members, N or frame < 0; eta_out,
+ * eta_in or seeds NULL with members N > 0.  piml_scenario_step_mlapm_noise: noise or noise->state NULL; with g != NULL every
+ * check of piml_scenario_step_mlapm_groups; with g == NULL: glaw or glaw_table_device given, init != 0, and the checks of
+ * piml_scenario_step_mlapm (law), piml_scenario_step_mlapm_laws (law_table_device) -- exactly one of the two -- and, with
+ * wall_grid != NULL, piml_scenario_step_mlapm_walls; wall or wall_table_device without a grid.  No atomics, capturable.
+ */
+typedef struct piml_noise_law { float rho, amp; } piml_noise_law;
+typedef struct piml_noise_args {
+    float* state;                                           /* (members, capacity, 2) */
+    piml_noise_law law;
+    const piml_noise_law* law_table;                        /* (members), device; NULL: `law` for every member */
+} piml_noise_args;
+int piml_noise_force(float* eta_out, float* z_out /* may be NULL */, const float* eta_in,
+                     const unsigned char* present /* may be NULL */, const uint64_t* seeds, int members, int N, long long frame,
+                     float rho, float amp, void* stream);
+int piml_scenario_step_mlapm_noise(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                                   const piml_mlapm_law* law, const void* law_table_device,
+                                   const piml_wall_grid* wall_grid /* NULL: no wall term */, const piml_wall_law* wall,
+                                   const piml_wall_law* wall_table_device, const piml_scene_groups* g /* NULL: no groups */,
+                                   const piml_group_law* glaw /* both NULL: no group term */,
+                                   const piml_group_law* glaw_table_device, const piml_noise_args* noise, int init,
+                                   int frame_offset, void* stream);
+
+/*
  * utils.route (src/utils/utils.py:141-165) for n (o, d) pairs, one wave each, the device function the spawn path uses:
  * the segment o -> r is tested against the polyline's R-1 segments, the hit with the smallest alpha moves r to
  * crossing + clearance * normal, until nothing is hit or max_iters moves were made.  float32 in the reference's order.

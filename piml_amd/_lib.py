@@ -108,6 +108,16 @@ class SceneGroups(ctypes.Structure):
     _fields_ = [('row_unit', _p), ('unit_rows', _p), ('n_units', _i), ('group_first', _p), ('group_size', _p)]
 
 
+class NoiseLaw(ctypes.Structure):
+    """piml_noise_law (include/piml_hip.h)."""
+    _fields_ = [('rho', _f), ('amp', _f)]
+
+
+class NoiseArgs(ctypes.Structure):
+    """piml_noise_args (include/piml_hip.h)."""
+    _fields_ = [('state', _p), ('law', NoiseLaw), ('law_table', _p)]
+
+
 SPAWN_LAWS = {'gc': 0, 'crosswalk': 1, 'square': 2, 'unit1': 3, 'unit2': 4, 'unit3': 5, 'clip': 6}     # PIML_SPAWN_*
 SPAWN_CLIP_GROUPS = 7          # PIML_SPAWN_CLIP_GROUPS ('clip_groups'): piml_scenario_step_mlapm_groups only, so not in SPAWN_LAWS
 ARRIVAL_RULES = {'gc': 0, 'radius': 1, 'x_band': 2, 'x_exit': 3}                             # PIML_ARRIVE_*
@@ -180,6 +190,8 @@ SIGNATURES = {
     'piml_scenario_step_mlapm_walls': [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _p],
     'piml_group_force': [_p, _p, _p, _ll, _f, _f, _p, _p],
     'piml_scenario_step_mlapm_groups': [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p],
+    'piml_noise_force': [_p, _p, _p, _p, _p, _i, _i, _ll, _f, _f, _p],
+    'piml_scenario_step_mlapm_noise': [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p],
     'piml_scenario_route': [_p, _p, _i, _p, _i, _i, _f, _p, _p, _p],
     'piml_collision_correction_fwd': [_p, _p, _p, _z, _i, _i, _f, _f, _p, _p],
     'piml_collision_correction_bwd': [_p, _p, _p, _p, _z, _i, _i, _f, _f, _p, _p, _p, _p],

@@ -43,6 +43,7 @@ PARAM_NAMES = ('tau', 'A', 'B', 'C', 'D', 'theta')
 WALL_PARAM_NAMES = ('Aw', 'Bw')
 # the group term of a grouped clip scene's runs (MLAPM(..., Ag=[, group_dist=])): fitted by calibrate_mlapm_to_stats only
 GROUP_PARAM_NAMES = ('Ag', 'group_dist')
+NOISE_PARAM_NAMES = ('An', 'noise_tau')       # the fluctuation term of the scene runs: fitted by calibrate_mlapm_to_stats only
 # the constants src/main_mlapm.py:16 types in
 DEFAULT_INIT = {'tau': 0.5, 'A': 7.55, 'B': -3.0, 'C': 0.2, 'D': -0.3, 'theta': 56.0}
 SMALL_FRAME = 64          # frames up to this many agents: a lane per focal agent; above: a wave per focal agent
@@ -418,18 +419,27 @@ def calibrate_mlapm(data, version='GC', init=None, fit=PARAM_NAMES, steps=500, l
 OBJECTIVE_KEYS = {'crowd': ('fd_distance', 'map_distance', 'mean_speed_diff'),
                   'pairs': ('ttc_l1', 'nn_l1', 'overlap_rate_diff'),
                   'obstacles': ('hit_track_fraction_diff', 'contact_rate_diff', 'clearance_l1'),
-                  'groups': ('group_fraction_diff', 'size_l1', 'member_distance_l1', 'abreast_l1', 'speed_ratio_diff')}
+                  'groups': ('group_fraction_diff', 'size_l1', 'member_distance_l1', 'abreast_l1', 'speed_ratio_diff'),
+                  'tracks': ('heading_ac_max_diff', 'persistence_time_diff', 'msd_exponent_diff', 'acc_l1',
+                             'mean_acceleration_diff', 'straightness_l1', 'speed_l1', 'duration_l1')}
 # speed_ratio_diff needs min_count GROUPED tracks on both sides, which a recorded clip does not have (GC 11, UCY 26): NaN at
 # any honest min_count, and a NaN term of non-zero weight makes J infinite -- so it is off unless `weights` switches it on
 DEFAULT_WEIGHTS = {'speed_ratio_diff': 0.0}
-DEFAULT_BOUNDS = {'tau': (1e-3, None), 'Aw': (0.0, None), 'Bw': (None, 0.0), 'Ag': (0.0, None), 'group_dist': (0.0, None)}
+# the track side: persistence_time_diff is NaN for both recorded clips (their heading autocorrelation never falls to 1 / e
+# inside the lags); speed_l1 and duration_l1 belong to the scene (the desired speeds and the routes), not the law
+TRACK_DEFAULT_WEIGHTS = {'persistence_time_diff': 0.0, 'speed_l1': 0.0, 'duration_l1': 0.0}
+DEFAULT_BOUNDS = {'tau': (1e-3, None), 'Aw': (0.0, None), 'Bw': (None, 0.0), 'Ag': (0.0, None), 'group_dist': (0.0, None),
+                  'An': (0.0, None), 'noise_tau': (0.0, None)}
 GROUP_OPTION_KEYS = ('radius', 'dv_max', 'v_min', 'min_time', 'share', 'r_bin', 'r_bins', 'a_bins')
 
 
 def stats_objective(crowd=None, pairs=None, ref_crowd=None, ref_pairs=None, weights=None, min_count=50, obstacles=None,
-                    ref_obstacles=None, groups=None, ref_groups=None):
+                    ref_obstacles=None, groups=None, ref_groups=None, tracks=None, ref_tracks=None):
     """(J, terms): how far simulated statistics are from a reference's.  crowd / ref_crowd: CrowdStats, pairs / ref_pairs:
-    PairStats, obstacles / ref_obstacles: ObstacleStats, groups / ref_groups: GroupStats; a side takes part when both of its
+    PairStats, obstacles / ref_obstacles: ObstacleStats, groups / ref_groups: GroupStats, tracks / ref_tracks: TrackStats
+    (compare_track_stats' terms, OBJECTIVE_KEYS['tracks']: weight 1.0 for heading_ac_max_diff, msd_exponent_diff, acc_l1,
+    mean_acceleration_diff and straightness_l1, 0.0 by default (TRACK_DEFAULT_WEIGHTS) for persistence_time_diff -- NaN for
+    both recorded clips -- and for speed_l1 and duration_l1, which belong to the scene, not the law); a side takes part when both of its
     statistics are given.  terms is
     the union of compare_crowd_stats(crowd, ref_crowd, min_count), compare_pair_stats(pairs, ref_pairs, min_count),
     compare_obstacle_stats(obstacles, ref_obstacles, min_count) and compare_group_stats(groups, ref_groups, min_count) for
@@ -443,7 +453,8 @@ def stats_objective(crowd=None, pairs=None, ref_crowd=None, ref_pairs=None, weig
     unknown key."""
     from .crowdstats import compare_crowd_stats
     from .pairstats import compare_pair_stats
-    known = OBJECTIVE_KEYS['crowd'] + OBJECTIVE_KEYS['pairs'] + OBJECTIVE_KEYS['obstacles'] + OBJECTIVE_KEYS['groups']
+    known = OBJECTIVE_KEYS['crowd'] + OBJECTIVE_KEYS['pairs'] + OBJECTIVE_KEYS['obstacles'] + OBJECTIVE_KEYS['groups'] + \
+        OBJECTIVE_KEYS['tracks']
     unknown = sorted(set(weights or {}) - set(known))
     if unknown:
         raise ValueError(f'stats_objective: weights for unknown terms {unknown} (of {known})')
@@ -462,11 +473,15 @@ def stats_objective(crowd=None, pairs=None, ref_crowd=None, ref_pairs=None, weig
         from .groupstats import compare_group_stats
         terms.update(compare_group_stats(groups, ref_groups, min_count))
         keys += OBJECTIVE_KEYS['groups']
+    if tracks is not None and ref_tracks is not None:
+        from .trackstats import compare_track_stats
+        terms.update(compare_track_stats(tracks, ref_tracks, min_count))
+        keys += OBJECTIVE_KEYS['tracks']
     if not keys:
-        raise ValueError('stats_objective: neither crowd, pair, obstacle nor group statistics with a reference')
+        raise ValueError('stats_objective: neither crowd, pair, obstacle, group nor track statistics with a reference')
     J = 0.0
     for k in keys:
-        w = float((weights or {}).get(k, DEFAULT_WEIGHTS.get(k, 1.0)))
+        w = float((weights or {}).get(k, DEFAULT_WEIGHTS.get(k, TRACK_DEFAULT_WEIGHTS.get(k, 1.0))))
         if terms[k] is None or w == 0.0:
             continue
         if math.isnan(terms[k]):
@@ -483,12 +498,14 @@ class _StatsEvaluator:
     """calibrate_mlapm_to_stats' objective on the GPU: list of candidate dicts -> list of J, one SweepRun generation each."""
 
     def __init__(self, scenario, reference, frames, seeds, population, radius, capacity, crowd_kw, pair_kw, weights,
-                 min_count, device, obstacle_kw=None, wall_cutoff=None, group_kw=None, components='device'):
+                 min_count, device, obstacle_kw=None, wall_cutoff=None, group_kw=None, components='device', track_kw=None):
         from . import crowdstats, pairstats
         from .models.mlapm import DEFAULT_WALL_CUTOFF, SweepRun
-        self.ref_obstacles = self.ref_groups = None
+        self.ref_obstacles = self.ref_groups = self.ref_tracks = None
         if isinstance(reference, (tuple, list)):
-            if len(reference) == 4:                  # (crowd, pairs, obstacles, groups): the group side takes part too
+            if len(reference) == 5:                  # (crowd, pairs, obstacles, groups, tracks): the track side too
+                self.ref_crowd, self.ref_pairs, self.ref_obstacles, self.ref_groups, self.ref_tracks = reference
+            elif len(reference) == 4:                  # (crowd, pairs, obstacles, groups): the group side takes part too
                 self.ref_crowd, self.ref_pairs, self.ref_obstacles, self.ref_groups = reference
             elif len(reference) == 3:                # (crowd, pairs, obstacles): the obstacle side takes part
                 self.ref_crowd, self.ref_pairs, self.ref_obstacles = reference
@@ -499,6 +516,9 @@ class _StatsEvaluator:
                                                                'tau_bins', 'box'))
             if group_kw is None and self.ref_groups is not None:
                 group_kw = _options_of(self.ref_groups, GROUP_OPTION_KEYS)
+            if track_kw is None and self.ref_tracks is not None:
+                from .trackstats import OPTION_KEYS as TRACK_OPTION_KEYS
+                track_kw = _options_of(self.ref_tracks, [k for k in TRACK_OPTION_KEYS if k != 'dt'])
             if crowd_kw is None and self.ref_crowd is not None:
                 crowd_kw = crowdstats.call_options(self.ref_crowd)
             if pair_kw is None and self.ref_pairs is not None:
@@ -514,15 +534,16 @@ class _StatsEvaluator:
             self.ref_pairs = pairstats.pair_stats_of_raw(reference, **dict(pair_kw or {}))
             if frames is None:
                 frames = int(torch.as_tensor(reference.position).shape[0])
-        if self.ref_crowd is None and self.ref_pairs is None and self.ref_obstacles is None and self.ref_groups is None:
+        if self.ref_crowd is None and self.ref_pairs is None and self.ref_obstacles is None and self.ref_groups is None and \
+                self.ref_tracks is None:
             raise ValueError('calibrate_mlapm_to_stats: the reference holds no statistics')
         self.crowd_kw, self.pair_kw, self.obstacle_kw = dict(crowd_kw or {}), dict(pair_kw or {}), dict(obstacle_kw or {})
-        self.group_kw, self.components = dict(group_kw or {}), components
+        self.group_kw, self.components, self.track_kw = dict(group_kw or {}), components, dict(track_kw or {})
         self.weights, self.min_count, self.radius = weights, min_count, radius
         self.frames = 200 if frames is None else int(frames)
         self.run = SweepRun(scenario, self.frames, population, seeds, capacity=capacity, device=device,
                             wall_cutoff=DEFAULT_WALL_CUTOFF if wall_cutoff is None else wall_cutoff)
-        self.seconds = {'run': 0.0, 'crowd': 0.0, 'pairs': 0.0, 'obstacles': 0.0, 'groups': 0.0, 'host': 0.0}
+        self.seconds = {'run': 0.0, 'crowd': 0.0, 'pairs': 0.0, 'obstacles': 0.0, 'groups': 0.0, 'tracks': 0.0, 'host': 0.0}
         self.last_terms = []
 
     def __call__(self, cands):
@@ -560,6 +581,12 @@ class _StatsEvaluator:
             kw = {'dt': float(sw.time_unit), **self.group_kw}
             groups = group_stats(sw.position, mask, n_active=n_active, components=self.components, **kw)
         t3c = time.perf_counter()
+        tracks = None
+        if self.ref_tracks is not None:              # one call for every member, the reference's options, the scene's dt
+            from .trackstats import track_stats
+            kw = {'dt': float(sw.time_unit), **self.track_kw}
+            tracks = track_stats(sw.position, mask, n_active=n_active, **kw)
+        t3d = time.perf_counter()
         out, self.last_terms = [], []
         for c in range(sw.n_candidates):
             group = sw.members_of(c)
@@ -571,12 +598,13 @@ class _StatsEvaluator:
                                        None if pairs is None else pairs.select(group).pooled(),
                                        self.ref_crowd, self.ref_pairs, self.weights, self.min_count,
                                        None if obstacles is None else obstacles.select(group).pooled(), self.ref_obstacles,
-                                       None if groups is None else groups.select(group).pooled(), self.ref_groups)
+                                       None if groups is None else groups.select(group).pooled(), self.ref_groups,
+                                       None if tracks is None else tracks.select(group).pooled(), self.ref_tracks)
             out.append(J)
             self.last_terms.append(terms)
         t4 = time.perf_counter()
-        for k, dt in zip(('run', 'crowd', 'pairs', 'obstacles', 'groups', 'host'),
-                         (t1 - t0, t2 - t1, t3 - t2, t3b - t3, t3c - t3b, t4 - t3c)):
+        for k, dt in zip(('run', 'crowd', 'pairs', 'obstacles', 'groups', 'tracks', 'host'),
+                         (t1 - t0, t2 - t1, t3 - t2, t3b - t3, t3c - t3b, t3d - t3c, t4 - t3d)):
             self.seconds[k] += dt
         return out
 
@@ -584,8 +612,17 @@ class _StatsEvaluator:
 def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=PARAM_NAMES, frames=None, seeds=range(8),
                              population=16, generations=30, elite=0.25, sigma=0.2, sigma_floor=1e-3, bounds=None,
                              weights=None, crowd_kw=None, pair_kw=None, search_seed=0, radius=0.3, capacity=None,
-                             evaluate=None, min_count=50, device='cuda', obstacle_kw=None, wall_cutoff=None, group_kw=None):
+                             evaluate=None, min_count=50, device='cuda', obstacle_kw=None, wall_cutoff=None, group_kw=None,
+                             track_kw=None):
     """Fit MLAPM's constants so that the law, run open-world in `scenario`, reproduces the reference's crowd statistics.
+
+    The fluctuation term: fit may also name An, noise_tau (NOISE_PARAM_NAMES), and init may carry them: the candidates then
+    run the frames with the fluctuation term (MLAPM(..., An=, noise_tau=)), in any scene.  init must hold An when either is
+    fitted or present -- the term has no default -- and noise_tau defaults to 0 (white noise); An >= 0 and noise_tau >= 0
+    are bounded so by default.  A reference 5-tuple (CrowdStats | None, PairStats | None, ObstacleStats | None, GroupStats |
+    None, TrackStats | None) adds the track side, the one that sees the term: one track_stats call (track_kw, default the
+    reference's OPTION_KEYS options; dt the scene's) covers every member of a generation and enters stats_objective with the
+    reference's.  The result's params then carry An and noise_tau.
 
     The group term: fit may also name Ag, group_dist (GROUP_PARAM_NAMES), and init may carry them: the candidates then run a
     grouped clip scene (scenarios.clip_scenario(groups=); ValueError before anything is launched for any other scene) with
@@ -632,7 +669,7 @@ def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=P
     if version not in ops.MLAPM_VARIANTS:
         raise NotImplementedError(version)
     fit = tuple(fit)
-    every = PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES
+    every = PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES + NOISE_PARAM_NAMES
     unknown = [k for k in fit if k not in every]
     if unknown or not fit:
         raise ValueError(f'constants to fit: names of {every} expected, got {fit}')
@@ -643,7 +680,11 @@ def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=P
     grouped = any(k in (init or {}) for k in GROUP_PARAM_NAMES)
     if (grouped or any(k in GROUP_PARAM_NAMES for k in fit)) and 'Ag' not in (init or {}):
         raise ValueError(f'the group term has no default: init must hold Ag (fit {fit}, init {sorted(init or {})})')
-    names = PARAM_NAMES + (WALL_PARAM_NAMES if walls else ()) + (GROUP_PARAM_NAMES if grouped else ())
+    noisy = any(k in (init or {}) for k in NOISE_PARAM_NAMES)
+    if (noisy or any(k in NOISE_PARAM_NAMES for k in fit)) and 'An' not in (init or {}):
+        raise ValueError(f'the fluctuation term has no default: init must hold An (fit {fit}, init {sorted(init or {})})')
+    names = PARAM_NAMES + (WALL_PARAM_NAMES if walls else ()) + (GROUP_PARAM_NAMES if grouped else ()) + \
+        (NOISE_PARAM_NAMES if noisy else ())
     population, generations = int(population), int(generations)
     if population < 2 or generations < 1:
         raise ValueError(f'population >= 2 and generations >= 1 expected, got {population}, {generations}')
@@ -660,6 +701,10 @@ def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=P
         group_args({k: start[k] for k in GROUP_PARAM_NAMES})
         if scenario is not None:
             check_scene_groups(scenario)
+    if noisy:
+        from .models.mlapm import DEFAULT_NOISE_TAU, noise_args
+        start.setdefault('noise_tau', DEFAULT_NOISE_TAU)
+        noise_args({k: start[k] for k in NOISE_PARAM_NAMES})
     start = {k: float(start[k]) for k in names}
     if walls:
         from .models.mlapm import DEFAULT_WALL_CUTOFF, wall_args
@@ -669,7 +714,8 @@ def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=P
     terms_of = None
     if evaluate is None:
         evaluate = terms_of = _StatsEvaluator(scenario, reference, frames, seeds, population, radius, capacity, crowd_kw,
-                                              pair_kw, weights, min_count, device, obstacle_kw, wall_cutoff, group_kw)
+                                              pair_kw, weights, min_count, device, obstacle_kw, wall_cutoff, group_kw,
+                                              track_kw=track_kw)
     scale = np.array([abs(start[k]) if start[k] != 0 else 1.0 for k in fit])
     lo = np.array([-np.inf if limits.get(k, (None, None))[0] is None else limits[k][0] for k in fit], np.float64)
     hi = np.array([np.inf if limits.get(k, (None, None))[1] is None else limits[k][1] for k in fit], np.float64)
@@ -721,18 +767,18 @@ def _parse_init(text):
     out = {}
     for item in filter(None, (s.strip() for s in (text or '').split(','))):
         k, _, val = item.partition('=')
-        if k not in PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES or not _:
+        if k not in PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES + NOISE_PARAM_NAMES or not _:
             raise argparse.ArgumentTypeError('--init expects name=value with names in '
-                                             f'{PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES}, got {item!r}')
+                                             f'{PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES + NOISE_PARAM_NAMES}, got {item!r}')
         out[k] = float(val)
     return out
 
 
 def _parse_fit(text):
     names = tuple(filter(None, (s.strip() for s in text.split(','))))
-    bad = [k for k in names if k not in PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES]
+    bad = [k for k in names if k not in PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES + NOISE_PARAM_NAMES]
     if bad or not names:
-        raise argparse.ArgumentTypeError(f'--fit expects names from {PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES}, '
+        raise argparse.ArgumentTypeError(f'--fit expects names from {PARAM_NAMES + WALL_PARAM_NAMES + GROUP_PARAM_NAMES + NOISE_PARAM_NAMES}, '
                                          f'got {text!r}')
     return names
 
@@ -760,9 +806,9 @@ def get_args(argv=None):
                    help="fit the law to the clip's crowd statistics, run open-world in the clip's own scene "
                         '(calibrate_mlapm_to_stats), instead of to its trajectories')
     p.add_argument('--match', type=str, default=None,
-                   help='--match-stats: the statistics to match (crowd, pairs, obstacles, groups); default crowd,pairs, '
+                   help='--match-stats: the statistics to match (crowd, pairs, obstacles, groups, tracks); default crowd,pairs, '
                         'obstacles too when the law has a wall term (--init Aw=..,Bw=..) and groups too when it has a group '
-                        'term (--init Ag=..)')
+                        'term (--init Ag=..) and tracks too when it has a fluctuation term (--init An=..)')
     p.add_argument('--scene-groups', dest='scene_groups', type=str, default=None,
                    help="--match-stats: the clip's groups as arrival units, 'auto' (found by groupstats) or a JSON file of "
                         'lists of track indices (simulate --scene-groups); needed by a group term')
@@ -799,16 +845,24 @@ def get_args(argv=None):
             p.error('the group term has no default: --init must give Ag (the literature starts at Ag=3)')
         if a.scene_groups is None:
             p.error("the group term needs the clip's groups: --scene-groups auto or FILE.json")
+    noise_names = [k for k in NOISE_PARAM_NAMES if k in a.init or k in a.fit]
+    if noise_names:
+        if not a.match_stats:
+            p.error(f'{noise_names}: the fluctuation term is fitted by --match-stats only (it exists in the scene runs, not '
+                    'in the one-step or rollout fit)')
+        if 'An' not in a.init:
+            p.error('the fluctuation term has no default: --init must give An (m/s^2, e.g. An=0.5)')
     if a.scene_groups is not None and not a.match_stats:
         p.error('--scene-groups belongs to --match-stats')
     if a.match_stats:
         if len(a.data) != 1:
             p.error('--match-stats takes one clip')
         if a.match is None:
-            a.match = ('crowd,pairs,obstacles' if wall_names else 'crowd,pairs') + (',groups' if group_names else '')
+            a.match = ('crowd,pairs,obstacles' if wall_names else 'crowd,pairs') + (',groups' if group_names else '') + \
+                (',tracks' if noise_names else '')
         a.match = tuple(filter(None, (x.strip() for x in a.match.split(','))))
-        if not a.match or any(x not in ('crowd', 'pairs', 'obstacles', 'groups') for x in a.match):
-            p.error(f"--match: 'crowd', 'pairs', 'obstacles', 'groups' or several expected, got {a.match}")
+        if not a.match or any(x not in ('crowd', 'pairs', 'obstacles', 'groups', 'tracks') for x in a.match):
+            p.error(f"--match: 'crowd', 'pairs', 'obstacles', 'groups', 'tracks' or several expected, got {a.match}")
         if a.scene_groups is not None and a.scene_groups != 'auto':
             try:
                 from .simulate import load_scene_groups
@@ -909,13 +963,17 @@ def _main_stats(a, raw, init):
     if 'groups' in a.match:
         from .groupstats import group_stats_of_raw
         ref_groups = group_stats_of_raw(raw, frames=(lo, hi))
-    res = calibrate_mlapm_to_stats(scene, (ref_crowd, ref_pairs, ref_obstacles, ref_groups), version=a.version, init=init, fit=a.fit,
+    ref_tracks = None
+    if 'tracks' in a.match:
+        from .trackstats import track_stats_of_raw
+        ref_tracks = track_stats_of_raw(raw, frames=(lo, hi))
+    res = calibrate_mlapm_to_stats(scene, (ref_crowd, ref_pairs, ref_obstacles, ref_groups, ref_tracks), version=a.version, init=init, fit=a.fit,
                                    frames=hi - lo, seeds=a.seeds, population=a.population, generations=a.generations,
                                    search_seed=a.search_seed, radius=a.radius, wall_cutoff=a.wall_cutoff)
     print(f'[calibrate] {a.version} against the statistics ({", ".join(a.match)}) of frames {lo}:{hi}, {a.population} '
           f'candidates x {len(a.seeds)} seeds x {a.generations} generations: objective {res.initial_loss:.6g} -> '
           f'{res.final_loss:.6g} ({res.status})')
-    print('[calibrate] ' + ', '.join(f'{k}={res.params[k]:.6g}' for k in PARAM_NAMES + WALL_PARAM_NAMES + ('wall_cutoff',) + GROUP_PARAM_NAMES
+    print('[calibrate] ' + ', '.join(f'{k}={res.params[k]:.6g}' for k in PARAM_NAMES + WALL_PARAM_NAMES + ('wall_cutoff',) + GROUP_PARAM_NAMES + NOISE_PARAM_NAMES
                                      if k in res.params))
     print('[calibrate] terms: ' + ', '.join(f'{k} {v:.4g}' if isinstance(v, float) else f'{k} {v}'
                                            for k, v in (res.terms or {}).items()))

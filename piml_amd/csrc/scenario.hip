@@ -77,6 +77,12 @@
 // thread all k for the total, so nothing is exchanged between waves.  The init launch draws nothing: slot i is row i,
 // group_first = i - row_unit[i][0], group_size = row_unit[i][1].  The draws depend on (seed, frame, unit) only.
 //
+// The fluctuation term's randomness (piml_scenario_step_mlapm_noise; noise.hpp): c3 = 0x5CE40000 | sub, key = (seed lo,
+// seed hi).
+//   slot i, step from frame t   (t lo, t hi, i, 0x5CE40001): z_x from (w0, w1), z_y from (w2, w3), each as GC's call 3 (double)
+// One call per live slot and frame, by one lane of the slot's wave; absent and retired slots draw nothing.  The draws depend
+// on (seed, frame, slot) only, never on the dynamics.
+//
 // Members: the descriptor's per-member pointers are the bases of member-major buffers, member m's slice of each having
 // exactly the single-run layout -- state (members, capacity, .), waypoints (members, D, capacity, 2), exit_idx
 // (members, D, capacity), recorded outputs (members, T, capacity, .), spawn_out (members, T), spawned (members, 2),
@@ -87,9 +93,13 @@
 // Determinism: no atomics.  The spawned count is ping-ponged by frame parity per member (spawned[t & 1] read,
 // spawned[(t+1) & 1] written by one thread of block agent_blocks), so no workgroup reads a value another one writes in the
 // same launch; spawned agents take slots >= n_t, which no agent thread touches, and no block touches another member's slices.
+// The fluctuation term's state eta (members, capacity, 2) keeps the rule: element (m, i) is read and written by lane 0 of the
+// one wave that steps live slot i of member m, and by nobody else in the launch -- spawn blocks never touch it (eta = 0 at
+// birth is the caller's zero fill), other waves never read it (the pair sum, the wall and the group term read positions).
 #include "common.hpp"
 #include "groups.hpp"
 #include "mlapm.hpp"
+#include "noise.hpp"
 #include "philox.hpp"
 #include "walls.hpp"
 #include "../../include/piml_hip.h"
@@ -737,11 +747,19 @@ struct MlapmScenarioArgs {
 // last, one float32 add per component.  G reads the mates' positions from the RECORDS of frame t, as the pair sum does its
 // sources -- never from S.position or S.mask, which other waves overwrite in this launch.  The group law is GA.law, or row
 // blockIdx.y of GA.law_table when that is not NULL.  kGroups == false does not read GA: those kernels are what they were.
-template <bool kTable, bool kWalls, bool kGroups>
+//
+// kNoise (piml_scenario_step_mlapm_noise): any of the forms above with the fluctuation term of noise.hpp, F = (the above) +
+// eta', added last, one float32 add per component.  Lane 0 of the slot's wave draws z for (seed, t, i), steps eta = NA.state[m
+// capacity + i] and writes it back -- before the pair sum, where few values are live; it depends on nothing the sum makes --
+// and the wave takes eta' from lane 0 when it adds.  The law is NA.law, or row blockIdx.y of NA.law_table when that is not
+// NULL (amp is read again at the add: a flag kept across the tile loop cost the one scalar register that gave a kernel a
+// stack frame); amp == 0 skips the draw, the state and the add.  kNoise == false does not read NA: the kernels above compile
+// to the instructions they had.
+template <bool kTable, bool kWalls, bool kGroups, bool kNoise = false>
 __device__ __forceinline__ void scenario_mlapm_body(const MlapmScenarioArgs& K0, const unsigned long long* __restrict__ seeds,
                                                     const MlapmParams* __restrict__ table, const WallArgs& WG,
                                                     const piml_wall_law& wall, const piml_wall_law* __restrict__ wall_table,
-                                                    const GroupArgs& GA) {
+                                                    const GroupArgs& GA, const piml_noise_args& NA = piml_noise_args{}) {
     __shared__ float4 tile[kMlTile];                         // agent blocks: the sources (px, py, vx, vy); spawn blocks: entries
     __shared__ unsigned short ucy_ring[kMlScWaves][256];
     static_assert(kScenarioLdsPoints * sizeof(float2) <= sizeof(tile), "the entry points fit the source tile");
@@ -764,6 +782,18 @@ __device__ __forceinline__ void scenario_mlapm_body(const MlapmScenarioArgs& K0,
         const bool live = i < n_t && S.mask[i] != 0.f;       // wave-uniform
         float2 pi = make_float2(0.f, 0.f), vi = pi, di = pi;
         if (live) { pi = ((const float2*)S.position)[i]; vi = ((const float2*)S.velocity)[i]; di = ((const float2*)S.destination)[i]; }
+        // the fluctuation of this step, drawn before the pair sum while few values are live (it depends on (seed, t, i) and
+        // the slot's own state only); added to the force last, below
+        float2 eta = make_float2(0.f, 0.f);
+        if constexpr (kNoise) {
+            const float rho = NA.law_table ? NA.law_table[blockIdx.y].rho : NA.law.rho;       // block-uniform index
+            const float amp = NA.law_table ? NA.law_table[blockIdx.y].amp : NA.law.amp;
+            if (amp != 0.f && live && lane == 0) {
+                float2* st = (float2*)NA.state + ((size_t)blockIdx.y * (size_t)cap + (size_t)i);   // member_view's layout
+                eta = noise_step(*st, rho, amp, noise_draw(S.seed, t, (unsigned)i));
+                *st = eta;
+            }
+        }
         float ex = di.x - pi.x, ey = di.y - pi.y;
         const float en = fmaxf(norm2(ex, ey), 1e-12f);      // mlapm.py:21
         ex /= en; ey /= en;
@@ -811,6 +841,10 @@ __device__ __forceinline__ void scenario_mlapm_body(const MlapmScenarioArgs& K0,
                 const float2 g = group_force_row(pt, n_t, i, GA.group_first[mo], GA.group_size[mo], gl.A, gl.dist);
                 fx = __fadd_rn(fx, g.x); fy = __fadd_rn(fy, g.y);
             }
+        }
+        if constexpr (kNoise) {
+            const float amp = NA.law_table ? NA.law_table[blockIdx.y].amp : NA.law.amp;       // (read again: nothing is kept)
+            if (amp != 0.f) { fx = __fadd_rn(fx, __shfl(eta.x, 0, 64)); fy = __fadd_rn(fy, __shfl(eta.y, 0, 64)); }
         }
         const float2 vn = make_float2(vi.x + fx * dt, vi.y + fy * dt);          // :57
         const float2 pn = make_float2(pi.x + vn.x * dt, pi.y + vn.y * dt);      // main_mlapm.py:25
@@ -873,6 +907,17 @@ __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_groups_kernel(
                                                                                const piml_wall_law* __restrict__ wall_table,
                                                                                const GroupArgs GA) {
     scenario_mlapm_body<kTable, kWalls, true>(K0, seeds, table, WG, wall, wall_table, GA);
+}
+
+// every form of the frame with the fluctuation term; kGroups == false does not read GA, kWalls == false neither WG nor the laws
+template <bool kTable, bool kWalls, bool kGroups>
+__global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_noise_kernel(const MlapmScenarioArgs K0,
+                                                                              const unsigned long long* __restrict__ seeds,
+                                                                              const MlapmParams* __restrict__ table,
+                                                                              const WallArgs WG, const piml_wall_law wall,
+                                                                              const piml_wall_law* __restrict__ wall_table,
+                                                                              const GroupArgs GA, const piml_noise_args NA) {
+    scenario_mlapm_body<kTable, kWalls, kGroups, true>(K0, seeds, table, WG, wall, wall_table, GA, NA);
 }
 
 }  // namespace piml
@@ -1105,6 +1150,78 @@ PIML_API int piml_scenario_step_mlapm_groups(const piml_scenario* s, const piml_
                                     wall_table_device, GA);
         else hipLaunchKernelGGL((piml::scenario_mlapm_groups_kernel<true, false>), grid, block, 0, st, K, sd, tb, WG, w,
                                 wall_table_device, GA);
+    }
+    return hipGetLastError();
+}
+
+template <bool kTable, bool kWalls, bool kGroups>
+static void launch_mlapm_noise(dim3 grid, hipStream_t st, const piml::MlapmScenarioArgs& K, const unsigned long long* sd,
+                               const piml::MlapmParams* tb, const piml::WallArgs& WG, const piml_wall_law& w,
+                               const piml_wall_law* wt, const piml::GroupArgs& GA, const piml_noise_args& NA) {
+    hipLaunchKernelGGL((piml::scenario_mlapm_noise_kernel<kTable, kWalls, kGroups>), grid, dim3(piml::kMlScWaves * 64), 0, st, K,
+                       sd, tb, WG, w, wt, GA, NA);
+}
+
+PIML_API int piml_scenario_step_mlapm_noise(const piml_scenario* s, const piml_scenario_rules* r, int members,
+                                            const uint64_t* seeds, const piml_mlapm_law* law, const void* law_table_device,
+                                            const piml_wall_grid* wall_grid, const piml_wall_law* wall,
+                                            const piml_wall_law* wall_table_device, const piml_scene_groups* g,
+                                            const piml_group_law* glaw, const piml_group_law* glaw_table_device,
+                                            const piml_noise_args* noise, int init, int frame_offset, void* stream) {
+    if (!noise || !noise->state || (!noise->law_table && !piml::noise_law_ok(noise->law.rho, noise->law.amp)))
+        return hipErrorInvalidValue;
+    if (init)                                                // the grouped scene's init launch: no law, no state is read
+        return g ? piml_scenario_step_mlapm_groups(s, r, members, seeds, law, law_table_device, wall_grid, wall,
+                                                   wall_table_device, g, glaw, glaw_table_device, init, frame_offset, stream)
+                 : (int)hipErrorInvalidValue;
+    if (!s || !seeds || members < 1 || members > 65535 || frame_offset < 0) return hipErrorInvalidValue;
+    piml::GroupArgs GA{};
+    if (g) {                                                 // piml_scenario_step_mlapm_groups' checks
+        if (!r || r->spawn_law != PIML_SPAWN_CLIP_GROUPS) return hipErrorInvalidValue;
+        piml_scenario_rules clip = *r;
+        clip.spawn_law = PIML_SPAWN_CLIP;
+        if (!frame_args_ok(*s, &clip, nullptr, 1)) return hipErrorInvalidValue;
+        if (!g->row_unit || !g->unit_rows || !g->group_first || !g->group_size || g->n_units < 0 ||
+            (g->n_units == 0 && s->spawn_cap > 0) || (unsigned)g->n_units > piml::kGroupMaxUnits)
+            return hipErrorInvalidValue;
+        if (glaw && glaw_table_device) return hipErrorInvalidValue;
+        if (glaw && !piml::group_law_ok(glaw->A, glaw->dist)) return hipErrorInvalidValue;
+        GA.row_unit = g->row_unit;
+        GA.unit_rows = g->unit_rows;
+        GA.n_units = g->n_units;
+        GA.group_first = g->group_first;
+        GA.group_size = g->group_size;
+        GA.law = glaw ? *glaw : piml_group_law{};
+        GA.law_table = glaw_table_device;
+        GA.term = glaw || glaw_table_device;
+    } else if (glaw || glaw_table_device || !frame_args_ok(*s, r, nullptr, 1)) {
+        return hipErrorInvalidValue;
+    }
+    if (!law == !law_table_device) return hipErrorInvalidValue;                               // exactly one
+    if (law && !mlapm_law_ok(*law)) return hipErrorInvalidValue;
+    if (wall_grid ? (!wall == !wall_table_device) : (wall || wall_table_device)) return hipErrorInvalidValue;
+    if (wall_grid && (!piml::wall_grid_ok(wall_grid) || (wall && !piml::wall_law_ok(wall->A, wall->B))))
+        return hipErrorInvalidValue;
+    piml::MlapmScenarioArgs K;
+    dim3 grid = mlapm_frame_launch(K, *s, r, members, frame_offset);
+    if (g) grid = dim3((unsigned)(K.agent_blocks + (s->spawn_cap > 0 ? s->spawn_cap : 1)), (unsigned)members);   // a block per unit
+    K.P = piml::MlapmParams{};                               // (not read with a table)
+    if (law) K.P = piml::make_params(law->variant, law->tau, law->A, law->B, law->C, law->D, law->theta_deg, law->radius, 1);
+    const piml::WallArgs WG = wall_grid ? piml::wall_args(*wall_grid) : piml::WallArgs{};
+    const piml_wall_law w = wall ? *wall : piml_wall_law{};
+    const unsigned long long* sd = (const unsigned long long*)seeds;
+    const piml::MlapmParams* tb = (const piml::MlapmParams*)law_table_device;
+    hipStream_t st = piml::as_stream(stream);
+    const int form = (law ? 0 : 4) | (wall_grid ? 2 : 0) | (g ? 1 : 0);
+    switch (form) {
+    case 0: launch_mlapm_noise<false, false, false>(grid, st, K, sd, tb, WG, w, wall_table_device, GA, *noise); break;
+    case 1: launch_mlapm_noise<false, false, true>(grid, st, K, sd, tb, WG, w, wall_table_device, GA, *noise); break;
+    case 2: launch_mlapm_noise<false, true, false>(grid, st, K, sd, tb, WG, w, wall_table_device, GA, *noise); break;
+    case 3: launch_mlapm_noise<false, true, true>(grid, st, K, sd, tb, WG, w, wall_table_device, GA, *noise); break;
+    case 4: launch_mlapm_noise<true, false, false>(grid, st, K, sd, tb, WG, w, wall_table_device, GA, *noise); break;
+    case 5: launch_mlapm_noise<true, false, true>(grid, st, K, sd, tb, WG, w, wall_table_device, GA, *noise); break;
+    case 6: launch_mlapm_noise<true, true, false>(grid, st, K, sd, tb, WG, w, wall_table_device, GA, *noise); break;
+    default: launch_mlapm_noise<true, true, true>(grid, st, K, sd, tb, WG, w, wall_table_device, GA, *noise); break;
     }
     return hipGetLastError();
 }

@@ -5,11 +5,14 @@ so for a list of laws at once, one law per ensemble member.  With the optional c
 runs add a wall term, the repulsion Aw exp(Bw d) of the nearest obstacle point within wall_cutoff (include/piml_hip.h,
 piml_scenario_step_mlapm_walls); `step` and `rollout` never have one.  With Ag (and group_dist) the runs of a grouped clip
 scene (scenarios.clip_scenario(groups=)) add a group cohesion term, a pull of Ag towards the centroid of the agent's group
-(piml_scenario_step_mlapm_groups); `step`, `rollout` and the fits never have one either."""
+(piml_scenario_step_mlapm_groups); `step`, `rollout` and the fits never have one either.  With An (and noise_tau) the scene
+runs add a fluctuation term, an Ornstein-Uhlenbeck acceleration per agent of stationary standard deviation An and correlation
+time noise_tau (piml_scenario_step_mlapm_noise); again `step`, `rollout` and the gradient fits never have one."""
 from .. import ops
 
 DEFAULT_WALL_CUTOFF = 2.0     # metres
 DEFAULT_GROUP_DIST = 0.5      # metres per further member: Moussaid et al. 2010's (n - 1) / 2
+DEFAULT_NOISE_TAU = 0.0       # seconds: white noise
 
 
 class MLAPM:
@@ -19,6 +22,7 @@ class MLAPM:
             raise NotImplementedError(args.get('version'))
         wall_args(args)                                       # (ValueError on a half-given or out-of-range wall term)
         group_args(args)                                      # (... or group term)
+        noise_args(args)                                      # (... or fluctuation term)
 
     def step(self, position, velocity, desired_speed, destination, dt, radius=0.3):
         """position, velocity, destination: (N, 2); desired_speed: (N, 1), (N,) or (N, 2).  Returns the new
@@ -158,6 +162,12 @@ class MLAPM:
         c - p, once |e| > group_dist (n - 1) -- the attraction term of Moussaid et al. 2010 without their gaze term.  Ag has
         no default; about 3 m/s^2 is the paper's order of magnitude, a starting point for a fit that nobody has verified
         here.  ValueError when Ag is given and the scene has no groups.
+        MLAPM(..., An=[, noise_tau=0.0]) adds the fluctuation term of Helbing and Molnar 1995 last, after the wall and group
+        terms: an Ornstein-Uhlenbeck acceleration eta per agent, eta' = rho eta + amp z with rho = exp(-dt / noise_tau) and
+        amp = An sqrt(1 - rho^2), z two standard normals drawn from (seed, frame, slot) only -- the arrivals do not change and
+        a run is still a function of its seed.  An (m/s^2) is the stationary standard deviation of each component and has
+        no default; eta is 0 at birth.  With noise_tau = 0 the noise is white, eta = An z: the per-frame acceleration then
+        has standard deviation An whatever dt is (a shorter time step does not shrink it).
         Returns a scenarios.ScenarioResult."""
         return self._simulate(scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, seed=seed)
 
@@ -185,42 +195,48 @@ class MLAPM:
         walls = None
         if wall is not None:
             walls = (ops_scenario.wall_grid(st.scenario.obstacles, wall[2], st.p.device), ops_scenario.wall_law(*wall[:2]))
+        noise = noise_args(self.args)
         self._run_scenario(st, law, use_graph, frames_per_graph, walls=walls,
-                           groups=None if group is None else ops_scenario.group_law(*group))
+                           groups=None if group is None else ops_scenario.group_law(*group),
+                           noise=None if noise is None else ops_scenario.noise_law(*noise, float(st.scenario.time_unit)))
         return scenarios.scenario_result(st)
 
     @staticmethod
-    def _run_scenario(st, law, use_graph, frames_per_graph, graph=None, walls=None, groups=None):
+    def _run_scenario(st, law, use_graph, frames_per_graph, graph=None, walls=None, groups=None, noise=None):
         """frame 0's spawn, then T - 1 MLAPM frames: K = frames_per_graph of them (offsets 0 .. K-1 and one counter add)
         captured into one graph and replayed when use_graph, the rest eagerly.  law: a mlapm_law or a law table; walls:
         None or ops_scenario.scenario_step_mlapm's (grid, wall law or wall table) for the frames with the wall term; groups: None
-        or its group law or group table (a grouped clip scene's frames with the group term).  Returns
+        or its group law or group table (a grouped clip scene's frames with the group term); noise: None or its noise law or
+        noise table (the frames with the fluctuation term; its state is allocated here, before any capture).  Returns
         the captured graph (None for an eager run); passed back as `graph` with the same state, the run replays it
         instead of capturing again."""
         import torch
         from .. import ops_scenario, hip_graphs_safe
         with torch.no_grad():
             ops_scenario.scenario_step_mlapm(st, None, init=True)     # frame 0: generate(n_initial)
+            if noise is not None:
+                ops_scenario.scenario_noise_state(st)
             steps = st.T - 1
             if use_graph is None:
                 use_graph = steps > 8
             per = max(1, int(frames_per_graph))
             done = 0
             if use_graph and steps >= per + 1 and hip_graphs_safe():
-                ops_scenario.scenario_step_mlapm(st, law, walls=walls, groups=groups)     # a real frame, also warms the library up
+                ops_scenario.scenario_step_mlapm(st, law, walls=walls, groups=groups, noise=noise)     # a real frame, also warms the library up
                 done = 1
                 if graph is None:
                     torch.cuda.synchronize()
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
                         for k in range(per):
-                            ops_scenario.scenario_step_mlapm(st, law, frame_offset=k, advance=False, walls=walls, groups=groups)
+                            ops_scenario.scenario_step_mlapm(st, law, frame_offset=k, advance=False, walls=walls, groups=groups,
+                                                             noise=noise)
                         st.t.add_(per)
                 for _ in range((steps - done) // per):
                     graph.replay()
                 done += (steps - done) // per * per
             for _ in range(steps - done):
-                ops_scenario.scenario_step_mlapm(st, law, walls=walls, groups=groups)
+                ops_scenario.scenario_step_mlapm(st, law, walls=walls, groups=groups, noise=noise)
         return graph
 
     # ---- one law per member (piml_scenario_step_mlapm_laws): a sweep of candidates x seeds in one ensemble run ----
@@ -231,7 +247,8 @@ class MLAPM:
         MLAPM(**params) form (version, tau, A, B and optionally C, D, theta; an optional 'radius' overrides `radius` for
         that candidate; optionally the wall term's Aw, Bw, in every candidate or in none -- wall_cutoff is common to the
         sweep, a property of the scene's grid; optionally the group term's Ag and group_dist, again in every candidate or
-        in none, on a grouped clip scene), and member c * len(seeds) + k runs law c under seeds[k] -- candidate-major, every candidate on
+        in none, on a grouped clip scene; optionally the fluctuation term's An and noise_tau, in any subset of the
+        candidates: one without An runs without the term, bitwise as if no candidate had one), and member c * len(seeds) + k runs law c under seeds[k] -- candidate-major, every candidate on
         the same seeds and so the same arrivals (common random numbers).  Candidates may differ in version.  Member
         (c, k) is bitwise MLAPM(**params[c]).simulate_ensemble(scenario, frames, seeds, capacity=same)'s member k.
         What the reference does with one process per parameter set (src/utils/grid_search.py) is one run here.
@@ -244,6 +261,32 @@ class MLAPM:
 
 SWEEP_KEYS = ('version', 'tau', 'A', 'B', 'C', 'D', 'theta', 'radius', 'Aw', 'Bw')
 GROUP_KEYS = ('Ag', 'group_dist')       # a candidate's optional group term (a grouped clip scene)
+NOISE_KEYS = ('An', 'noise_tau')        # a candidate's optional fluctuation term
+
+
+def noise_args(args):
+    """(An, noise_tau) of MLAPM(**args)'s fluctuation term, None without one.  ValueError: noise_tau without An, a value that
+    is not finite or is negative."""
+    import math
+    if 'An' not in args:
+        if 'noise_tau' in args:
+            raise ValueError('MLAPM: noise_tau belongs to the fluctuation term and needs An')
+        return None
+    An, tau = float(args['An']), float(args.get('noise_tau', DEFAULT_NOISE_TAU))
+    if not (math.isfinite(An) and math.isfinite(tau)) or An < 0 or tau < 0:
+        raise ValueError(f'MLAPM: finite An >= 0 and noise_tau >= 0 expected, got {An}, {tau}')
+    return An, tau
+
+
+def sweep_noise(params):
+    """The (An, noise_tau) pair of every candidate dict -- (0, 0), no term, for a candidate without An --, or None when no
+    candidate has a fluctuation term.  Unlike the wall and group terms a sweep may mix candidates with and without one: a
+    row of amp 0 is skipped by the frame.  ValueError on a value noise_args refuses."""
+    params = list(params)
+    rows = [noise_args({k: a[k] for k in NOISE_KEYS if k in a}) for a in params if isinstance(a, dict)]
+    if all(r is None for r in rows):
+        return None
+    return [(0.0, 0.0) if r is None else r for r in rows]
 
 
 def group_args(args):
@@ -329,14 +372,15 @@ def sweep_laws(params, radius=0.3):
     for c, a in enumerate(params):
         if not isinstance(a, dict):
             raise ValueError(f'candidate {c}: a dict in MLAPM(**params) form expected, got {type(a).__name__}')
-        unknown = sorted(set(a) - set(SWEEP_KEYS) - set(GROUP_KEYS))
+        unknown = sorted(set(a) - set(SWEEP_KEYS) - set(GROUP_KEYS) - set(NOISE_KEYS))
         missing = [k for k in ('version', 'tau', 'A', 'B') if k not in a]
         if unknown or missing:
-            raise ValueError(f'candidate {c}: unknown keys {unknown}, missing keys {missing} (of {SWEEP_KEYS + GROUP_KEYS})')
+            raise ValueError(f'candidate {c}: unknown keys {unknown}, missing keys {missing} (of {SWEEP_KEYS + GROUP_KEYS + NOISE_KEYS})')
         laws.append(ops_scenario.mlapm_law(a['version'], a['tau'], a['A'], a['B'], a.get('C', 0.0), a.get('D', 0.0),
                                            a.get('theta', 0.0), a.get('radius', radius)))
     sweep_walls(params)
     sweep_groups(params)
+    sweep_noise(params)
     return laws
 
 
@@ -361,7 +405,7 @@ class SweepRun:
         self.scenario, self.frames, self.capacity, self.device = scenario, frames, capacity, device
         self.hist_width, self.use_graph, self.frames_per_graph = hist_width, use_graph, frames_per_graph
         self.wall_cutoff = float(wall_cutoff)
-        self.st = self.table = self.graph = self.wall_grid = self.wall_table = self.group_table = None
+        self.st = self.table = self.graph = self.wall_grid = self.wall_table = self.group_table = self.noise_table = None
 
     def run(self, params, radius=0.3):
         from .. import ops_scenario, scenarios
@@ -375,6 +419,9 @@ class SweepRun:
         wall_rows = None if walls is None else [ops_scenario.wall_law(*w) for w in walls for _ in range(S)]
         groups = sweep_groups(params)
         group_rows = None if groups is None else [ops_scenario.group_law(*g) for g in groups for _ in range(S)]
+        noise = sweep_noise(params)
+        dt = float(self.scenario.time_unit)
+        noise_rows = None if noise is None else [ops_scenario.noise_law(*z, dt) for z in noise for _ in range(S)]
         if self.st is None:
             if groups is not None:
                 check_scene_groups(self.scenario)
@@ -389,11 +436,17 @@ class SweepRun:
                 self.wall_table = ops_scenario.wall_law_table(wall_rows, self.st.p.device)
             if groups is not None:
                 self.group_table = ops_scenario.group_law_table(group_rows, self.st.p.device)
+            if noise is not None:
+                self.noise_table = ops_scenario.noise_law_table(noise_rows, dt, self.st.p.device)
         else:
             if (walls is None) != (self.wall_table is None):  # the captured frames are those of the first run's kernel
                 raise ValueError('SweepRun: every run of a sweep has a wall term (Aw, Bw) or none has')
             if (groups is None) != (self.group_table is None):
                 raise ValueError('SweepRun: every run of a sweep has a group term (Ag) or none has')
+            if noise is not None and self.noise_table is None:
+                raise ValueError('SweepRun: the first run of this sweep had no fluctuation term (An); its captured frames have none')
+            if self.noise_table is not None:                  # (no An in this run: rows of amp 0, which the frame skips)
+                ops_scenario.noise_law_table(noise_rows or [(0.0, 0.0)] * len(rows), dt, out=self.noise_table)
             ops_scenario.mlapm_law_table(rows, out=self.table)
             if groups is not None:
                 ops_scenario.group_law_table(group_rows, out=self.group_table)
@@ -402,7 +455,7 @@ class SweepRun:
             ops_scenario.scenario_state_reset(self.st)
         self.graph = MLAPM._run_scenario(self.st, self.table, self.use_graph, self.frames_per_graph, graph=self.graph,
                                          walls=None if walls is None else (self.wall_grid, self.wall_table),
-                                         groups=self.group_table)
+                                         groups=self.group_table, noise=self.noise_table)
         ens = scenarios.scenario_result(self.st)
         fields = dict(vars(ens))
         return scenarios.ScenarioSweep(params=params, n_candidates=self.n_candidates, seeds_per_candidate=S, **fields)

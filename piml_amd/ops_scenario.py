@@ -1,6 +1,7 @@
 """Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_step_rules,
 piml_scenario_step_members, piml_scenario_step_mlapm, piml_scenario_step_mlapm_laws, piml_scenario_step_mlapm_walls,
-piml_wall_force, piml_scenario_step_mlapm_groups, piml_group_force, piml_scenario_route).
+piml_wall_force, piml_scenario_step_mlapm_groups, piml_group_force, piml_scenario_step_mlapm_noise, piml_noise_force,
+piml_scenario_route).
 
 `scenario_state` allocates the persistent (static-address) buffers of one simulation or an ensemble and the
 `piml_scenario` descriptor that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive,
@@ -45,7 +46,8 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
     and is the one member of its launch: st.seeds holds the 64-bit patterns of the seed or seeds as a device int64 tensor,
     and st.rules the scene's piml_scenario_rules (GC's all-zero one for GC).  A grouped clip scene ('clip_groups') also
     gets st.group_first / st.group_size ((S,) capacity int32, zero: per slot the first slot and the size of its unit) and
-    st.groups, the piml_scene_groups over them and the scene's row_unit / unit_rows."""
+    st.groups, the piml_scene_groups over them and the scene's row_unit / unit_rows.  st.noise_state is None until a frame
+    with the fluctuation term needs it (scenario_noise_state: (S,) capacity, 2 float32 zeros, eta of every slot)."""
     dev = scenario.entries.device
     if dev.type != 'cuda':
         raise _lib.PimlHipError(f'scenario_state: the scenario must be on a GPU (piml_amd has no CPU path), got {dev}')
@@ -116,6 +118,7 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
     st.desc = s
     st.rules = scenario_rules(scenario) if scenario.spawn_law != 'gc' else _lib.ScenarioRules()
     st.groups = None
+    st.noise_state = None
     if scenario.spawn_law == 'clip_groups':
         ru, ur = scenario.row_unit, scenario.unit_rows
         if ru is None or ur is None or ru.dtype != torch.int32 or ur.dtype != torch.int32 or ru.device != dev or \
@@ -144,6 +147,16 @@ def scenario_state_reset(st):
     if getattr(st, 'groups', None) is not None:
         st.group_first.zero_()
         st.group_size.zero_()
+    if getattr(st, 'noise_state', None) is not None:
+        st.noise_state.zero_()
+
+
+def scenario_noise_state(st):
+    """The fluctuation term's state of st, eta per slot ((S,) capacity, 2 float32), allocated as zeros when first needed and
+    kept (scenario_state_reset zeroes it in place: eta = 0 at birth)."""
+    if getattr(st, 'noise_state', None) is None:
+        st.noise_state = torch.zeros_like(st.v)
+    return st.noise_state
 
 
 def scenario_rules(scenario):
@@ -437,7 +450,92 @@ def group_force(position, group_first, group_size, Ag, dist=0.5):
     return force
 
 
-def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, groups=None, init=False):
+def noise_law(An, noise_tau, dt):
+    """The piml_noise_law (rho, amp) of the fluctuation term eta' = rho eta + amp z (include/piml_hip.h): rho = exp(-dt /
+    noise_tau), 0 for noise_tau == 0 (white noise, eta = An z), amp = An sqrt(1 - rho^2), both formed in float64 and rounded
+    to float32 once.  An (m/s^2) is the stationary standard deviation of each component of eta; with noise_tau == 0 the
+    per-frame acceleration has standard deviation An whatever dt is (the velocity kick An dt is NOT a Wiener increment).
+    ValueError unless all three are finite, An >= 0, noise_tau >= 0 and dt > 0, or when noise_tau is so long that rho rounds
+    to 1 in float32."""
+    An, noise_tau, dt = float(An), float(noise_tau), float(dt)
+    if not (math.isfinite(An) and math.isfinite(noise_tau) and math.isfinite(dt)) or An < 0 or noise_tau < 0 or not dt > 0:
+        raise ValueError(f'noise law: finite An >= 0, noise_tau >= 0 and dt > 0 expected, got An={An}, noise_tau={noise_tau}, '
+                         f'dt={dt}')
+    rho = math.exp(-dt / noise_tau) if noise_tau > 0 else 0.0
+    law = _lib.NoiseLaw()
+    law.rho, law.amp = rho, An * math.sqrt(1.0 - rho * rho)
+    if not law.rho < 1.0:
+        raise ValueError(f'noise law: noise_tau={noise_tau} is too long for dt={dt} (rho rounds to 1 in float32)')
+    return law
+
+
+def noise_law_table(rows, dt, device='cuda', out=None):
+    """The noise table of piml_scenario_step_mlapm_noise: rows, a list of (An, noise_tau) pairs or noise_law(...) values, one
+    per member, as a (len(rows), 2) float32 device tensor of (rho, amp) (every pair formed as noise_law does with `dt`).
+    out: a table of the same shape to overwrite in place instead (a captured run reads the buffer at every replay)."""
+    laws = [r if isinstance(r, _lib.NoiseLaw) else noise_law(r[0], r[1], dt) for r in rows]
+    if not laws:
+        raise ValueError('noise_law_table: at least one row expected')
+    host = torch.tensor([[w.rho, w.amp] for w in laws], dtype=torch.float32)
+    if out is not None:
+        if out.dtype != torch.float32 or tuple(out.shape) != tuple(host.shape) or not out.is_contiguous():
+            raise ValueError(f'out: a contiguous float32 table {tuple(host.shape)} expected, got {out.dtype} {tuple(out.shape)}')
+        out.copy_(host)
+        return out
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.PimlHipError(f'noise_law_table: a GPU device expected (piml_amd has no CPU path), got {dev}')
+    return host.to(dev)
+
+
+def noise_force(eta, seeds, frame, An, noise_tau, dt, present=None, return_draws=False):
+    """One step of the fluctuation term for every row of eta ((members,) N, 2) (piml_noise_force, one thread per row): row
+    (m, i) draws two standard normals z for (seeds[m], frame, slot i) and gets rho eta + amp z with noise_law(An, noise_tau,
+    dt)'s constants.  seeds: one int, or `members` of them (64-bit patterns, as scenario_state takes them).  present
+    ((members,) N, anything whose != 0 marks a live slot; None: all): a row that is not present keeps its eta and draws
+    nothing (z = 0).  Returns the new eta, and z with return_draws.  Bitwise what the frame leaves in its state and adds to
+    the force for the step from frame `frame`."""
+    law = noise_law(An, noise_tau, dt)
+    e = _gpu_f32('eta', eta)
+    if e.dim() not in (2, 3) or e.shape[-1] != 2:
+        raise ValueError(f'eta: ((members,) N, 2) expected, got {tuple(e.shape)}')
+    members, N = (1 if e.dim() == 2 else e.shape[0]), e.shape[-2]
+    seeds = [int(seeds)] if isinstance(seeds, int) else [int(x) for x in (seeds.tolist() if isinstance(seeds, torch.Tensor) else seeds)]
+    if len(seeds) != members:
+        raise ValueError(f'seeds: {members} expected, got {len(seeds)}')
+    if int(frame) < 0:
+        raise ValueError(f'frame must be >= 0, got {frame}')
+    bits = [(x & 0xFFFFFFFFFFFFFFFF) - ((x & 0x8000000000000000) << 1) for x in seeds]
+    sd = torch.tensor(bits, device=e.device, dtype=torch.long)
+    pr = None
+    if present is not None:
+        pr = (torch.as_tensor(present, device=e.device) != 0).to(torch.uint8).contiguous()
+        if tuple(pr.shape) != tuple(e.shape[:-1]):
+            raise ValueError(f'present: {tuple(e.shape[:-1])} expected, got {tuple(pr.shape)}')
+    out = torch.empty_like(e)
+    z = torch.empty_like(e) if return_draws else None
+    if e.numel():
+        with torch.cuda.device(e.device):
+            _lib.check(_lib.lib().piml_noise_force(_ptr(out), _ptr(z), _ptr(e), _ptr(pr), _ptr(sd), members, N, int(frame),
+                                                   law.rho, law.amp, _stream()), 'piml_noise_force')
+    return (out, z) if return_draws else out
+
+
+def _group_arg_is_table(st, groups):
+    """scenario_step_mlapm's check of `groups`; True for a table"""
+    group_table = isinstance(groups, torch.Tensor)
+    if group_table:
+        if groups.dtype != torch.float32 or tuple(groups.shape) != (st.seeds.numel(), 2) or not groups.is_contiguous():
+            raise ValueError(f'group table: a contiguous float32 ({st.seeds.numel()}, 2) tensor of group_law_table '
+                             f'expected, got {groups.dtype} {tuple(groups.shape)}')
+        if groups.device != st.p.device:
+            raise ValueError(f'group table on {groups.device}, the state on {st.p.device}')
+    elif groups is not None and not isinstance(groups, _lib.GroupLaw):
+        raise TypeError(f'groups: a group_law or a group_law_table expected, got {type(groups).__name__}')
+    return group_table
+
+
+def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, groups=None, init=False, noise=None):
     """One launch: frame t -> t + 1 of st (single or ensemble state) under the MLAPM law `law` (mlapm_law(...)), t =
     st.t + frame_offset: the force of MLAPM.step from the agents present in frame t's records, v' = v + F dt, p' = p + v' dt
     (src/main_mlapm.py:18-36), a' = F, then the scene's arrivals, exits and spawns as scenario_step.  advance: add 1 to
@@ -454,7 +552,11 @@ def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, group
     together.  ValueError for groups on a scene without them.
     init = True: the init launch instead (frame st.t gets the scene's n_initial agents; law, walls, groups and frame_offset
     are not read, st.t is not advanced) -- scenario_step(st, init=True) for every scene but a grouped one, whose init launch
-    is the new entry's."""
+    is the new entry's.
+    noise = a noise_law(An, noise_tau, dt) for every member or a noise_law_table(...) with one row per member: any of the
+    forms above with the fluctuation term (piml_scenario_step_mlapm_noise), F = (the above) + eta', added last; eta lives in
+    scenario_noise_state(st), allocated at the first such frame (before any capture: a run's first frame is eager) and
+    zeroed by scenario_state_reset.  noise = None takes the entries above, untouched."""
     grouped = getattr(st, 'groups', None) is not None
     if init:
         if not grouped:
@@ -493,16 +595,39 @@ def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, group
             raise TypeError(f'walls: (wall_grid, wall_law or wall_law_table) expected, got {type(wall).__name__}')
         if grid.cell_start.device != st.p.device:
             raise ValueError(f'wall grid on {grid.cell_start.device}, the state on {st.p.device}')
+    if noise is not None:
+        noise_table = isinstance(noise, torch.Tensor)
+        if noise_table:
+            if noise.dtype != torch.float32 or tuple(noise.shape) != (st.seeds.numel(), 2) or not noise.is_contiguous():
+                raise ValueError(f'noise table: a contiguous float32 ({st.seeds.numel()}, 2) tensor of noise_law_table '
+                                 f'expected, got {noise.dtype} {tuple(noise.shape)}')
+            if noise.device != st.p.device:
+                raise ValueError(f'noise table on {noise.device}, the state on {st.p.device}')
+        elif not isinstance(noise, _lib.NoiseLaw):
+            raise TypeError(f'noise: a noise_law or a noise_law_table expected, got {type(noise).__name__}')
+        group_table = _group_arg_is_table(st, groups) if grouped else False
+        grid, wall = walls if walls is not None else (None, None)
+        wall_table = isinstance(wall, torch.Tensor)
+        na = _lib.NoiseArgs()
+        na.state = scenario_noise_state(st).data_ptr()
+        if noise_table:
+            na.law_table = noise.data_ptr()
+        else:
+            na.law = noise
+        with torch.cuda.device(st.p.device):
+            _lib.check(_lib.lib().piml_scenario_step_mlapm_noise(
+                ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(), _ptr(st.seeds),
+                None if table else ctypes.byref(law), _ptr(law) if table else None,
+                None if grid is None else ctypes.byref(grid.desc),
+                None if wall is None or wall_table else ctypes.byref(wall), _ptr(wall) if wall_table else None,
+                ctypes.byref(st.groups) if grouped else None, None if groups is None or group_table else ctypes.byref(groups),
+                _ptr(groups) if group_table else None, ctypes.byref(na), 0, int(frame_offset), _stream()),
+                'piml_scenario_step_mlapm_noise')
+            if advance:
+                st.t.add_(1)
+        return
     if grouped:
-        group_table = isinstance(groups, torch.Tensor)
-        if group_table:
-            if groups.dtype != torch.float32 or tuple(groups.shape) != (st.seeds.numel(), 2) or not groups.is_contiguous():
-                raise ValueError(f'group table: a contiguous float32 ({st.seeds.numel()}, 2) tensor of group_law_table '
-                                 f'expected, got {groups.dtype} {tuple(groups.shape)}')
-            if groups.device != st.p.device:
-                raise ValueError(f'group table on {groups.device}, the state on {st.p.device}')
-        elif groups is not None and not isinstance(groups, _lib.GroupLaw):
-            raise TypeError(f'groups: a group_law or a group_law_table expected, got {type(groups).__name__}')
+        group_table = _group_arg_is_table(st, groups)
         grid, wall = walls if walls is not None else (None, None)
         wall_table = isinstance(wall, torch.Tensor)
         with torch.cuda.device(st.p.device):

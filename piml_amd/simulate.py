@@ -11,6 +11,8 @@ reads.
     python -m piml_amd.simulate --law mlapm --scene-from ucy.npy --seeds 0:32 --pair-stats sim.json   (a clip as the scene)
     python -m piml_amd.simulate --law mlapm --scene-from gc.npy --scene-groups auto --params p.json --seeds 0:32 --group-stats g.json
                                 (the clip's groups arrive together; p.json with Ag [, group_dist] adds the group term)
+    python -m piml_amd.simulate --law mlapm --scenario gc --params noisy.json --seeds 0:32 --track-stats tracks.json
+                                (noisy.json with An [, noise_tau] adds the fluctuation term, in any scene)
     python -m piml_amd.simulate --scenario crosswalk --seeds 0:32 --flow-stats flow.json [--flow-axis x|y|auto|deg]
     python -m piml_amd.simulate --law mlapm --scenario crosswalk --seeds 0:32 --track-stats tracks.json   (track statistics)
                                 (velocity correlation and lane order, no clips written)
@@ -189,11 +191,11 @@ def load_scene_groups(path):
 def load_mlapm_params(path):
     """MLAPM's constructor arguments from the JSON `python -m piml_amd.calibrate --out` writes ({'version', 'tau', 'A',
     'B', 'C', 'D', 'theta'} and, for a law with a wall term, 'Aw', 'Bw', 'wall_cutoff'; for one with a group term, 'Ag' and
-    optionally 'group_dist'); constants the file leaves out keep
+    optionally 'group_dist'; for one with a fluctuation term, 'An' and optionally 'noise_tau'); constants the file leaves out keep
     calibrate.DEFAULT_INIT's values (main_mlapm.py:16) -- the wall term has no default: without Aw there is none --, and
     path None is those constants with version GC.  ValueError on an unknown version, an unknown key, a non-number or a
     wall term MLAPM refuses (Bw or wall_cutoff without Aw, Aw < 0, Bw > 0, wall_cutoff <= 0) or a group term it refuses
-    (group_dist without Ag, a negative value)."""
+    (group_dist without Ag, a negative value) or a fluctuation term it refuses (noise_tau without An, a negative value)."""
     import json
     from . import calibrate, ops
     params = {'version': 'GC', **calibrate.DEFAULT_INIT}
@@ -203,7 +205,7 @@ def load_mlapm_params(path):
         got = json.load(fh)
     if not isinstance(got, dict):
         raise ValueError(f'{path}: a JSON object expected')
-    numbers = calibrate.PARAM_NAMES + calibrate.WALL_PARAM_NAMES + ('wall_cutoff', 'Ag', 'group_dist')
+    numbers = calibrate.PARAM_NAMES + calibrate.WALL_PARAM_NAMES + ('wall_cutoff', 'Ag', 'group_dist', 'An', 'noise_tau')
     unknown = sorted(set(got) - {'version', *numbers})
     if unknown:
         raise ValueError(f'{path}: unknown keys {unknown} (expected version and {list(numbers)})')
@@ -213,10 +215,11 @@ def load_mlapm_params(path):
         if k in got and (isinstance(got[k], bool) or not isinstance(got[k], (int, float))):
             raise ValueError(f'{path}: {k} = {got[k]!r} is not a number')
     params.update(got)
-    from .models.mlapm import group_args, wall_args
+    from .models.mlapm import group_args, noise_args, wall_args
     try:
         wall_args(params)
         group_args(params)
+        noise_args(params)
     except ValueError as ex:
         raise ValueError(f'{path}: {ex}') from None
     return params
