@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import REPO, golden
+from mlapm_fit_ref import ucy_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -53,48 +54,6 @@ def test_loss_and_gradient_match_the_reference_autograd(version):
                 assert grad[q] == 0.0, (tag, name, grad[q])          # a constant the variant does not use
             else:
                 assert abs(grad[q] - gw[q]) <= 1e-5 * scale[q], (tag, name, grad[q], gw[q], scale[q])
-
-
-def ucy_reference(pack, params, dt, radius):
-    """Float64 restatement of the UCY law (mlapm.py:43-53 with coll.unsqueeze(-1)): the collision flag is a discrete
-    decision and is taken in the reference's float32 operations; everything smooth in float64 under autograd."""
-    prm = {k: torch.tensor(float(params[k]), dtype=torch.float64, requires_grad=True) for k in NAMES}
-    st, dst = pack.state.cpu(), pack.destination.cpu()
-    v0, tgt = pack.desired_speed.cpu(), pack.target.cpu()
-    off = pack.offsets.cpu().tolist()
-    total, count = 0.0, 0
-    for f in range(len(off) - 1):
-        a, b = off[f], off[f + 1]
-        s32 = st[a:b]
-        vr32, vv32 = s32[None, :, :2] - s32[:, None, :2], s32[None, :, 2:] - s32[:, None, 2:]
-        coll = vr32.norm(dim=-1) < radius * 2
-        coll |= (vr32 + vv32 * 1.0).norm(dim=-1) < radius * 2
-        tmin = -(vr32 * vv32).sum(-1) / (vv32 * vv32).sum(-1)
-        dmin = ((vr32 * vr32).sum(-1) - (vr32 * vv32).sum(-1) ** 2 / (vv32 * vv32).sum(-1)).sqrt()
-        coll |= (tmin > 0) & (tmin < 1) & (dmin < radius * 2)
-        s = s32.double()
-        p, v = s[:, :2], s[:, 2:]
-        ed = torch.nn.functional.normalize(dst[a:b].double() - p, dim=-1)
-        force = (v0[a:b].double()[:, None] * ed - v) / prm['tau']
-        vr = p[None] - p[:, None]
-        r = vr.norm(dim=-1)
-        view = (torch.einsum('nk,nmk->nm', v, vr) > 0).double()
-        sg = -torch.sign(vr[..., 0] * ed[:, None, 1] - vr[..., 1] * ed[:, None, 0])
-        sg = torch.where(sg == 0, torch.ones_like(sg), sg)
-        th = sg * prm['theta'] / 180 * math.pi
-        n = torch.nn.functional.normalize(vr, dim=-1)
-        dx, dy = th.cos() * n[..., 0] - th.sin() * n[..., 1], th.sin() * n[..., 0] + th.cos() * n[..., 1]
-        c = coll.double()
-        gfac = view * prm['A'] * torch.exp(prm['B'] * r * c + prm['C'] * c)
-        force = force - torch.stack(((gfac * dx).sum(1), (gfac * dy).sum(1)), -1)
-        pred = v + force * dt
-        t = tgt[a:b].double()
-        fin = torch.isfinite(t).all(-1)
-        total = total + ((pred[fin] - t[fin]) ** 2).sum()
-        count += int(fin.sum())
-    loss = total / count
-    grads = torch.autograd.grad(loss, [prm[k] for k in NAMES], allow_unused=True)
-    return float(loss.detach()), np.array([0.0 if x is None else float(x) for x in grads])
 
 
 def test_ucy_matches_a_float64_restatement():
