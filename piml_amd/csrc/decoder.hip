@@ -17,6 +17,7 @@
 #include "reduce.hpp"
 #include "stages.hpp"
 #include "x3.hpp"
+#include "store.hpp"
 #include "../../include/piml_hip.h"
 
 namespace piml {
@@ -686,15 +687,10 @@ __device__ __forceinline__ void dec_bwd_dw_body4(const DecArgs& A, int b, int p,
 #endif
     }
     {
-        float* P1 = P + (size_t)(4 * h) * DH + 32 * w + i;                       // row rho(r) + 4 h of dW1's halves
-        float* P2 = P + DD * DH + (32 * mb2 + 4 * h) * DD + 32 * nb2 + i;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int rr = (r & 3) + 8 * (r >> 2);
-            P1[rr * DH] = c1a[r];
-            P1[(32 + rr) * DH] = c1b[r];
-            P2[rr * DD] = c2[r];
-        }
+        // dW1's halves (row blocks 0 and 1, column block w) and dW2's block, written through (store.hpp): read by the NEXT launch
+        store_acc32<PIML_WT_DEC_BWD_SLOTS>(P + 32 * w, DH, lane, [&](int r) { return c1a[r]; });
+        store_acc32<PIML_WT_DEC_BWD_SLOTS>(P + 32 * DH + 32 * w, DH, lane, [&](int r) { return c1b[r]; });
+        store_acc32<PIML_WT_DEC_BWD_SLOTS>(P + DD * DH + 32 * mb2 * DD + 32 * nb2, DD, lane, [&](int r) { return c2[r]; });
         if (do3 && h == 0) {                                                       // dW3's two rows are registers 0 and 1 of half 0
             float* P3 = P + DD * DH + DD * DD + 32 * nb2 + i;
             P3[0] = c3[0]; P3[DD] = c3[1];

@@ -28,6 +28,7 @@
 #include "common.hpp"
 #include "encoder.hpp"
 #include "x3.hpp"
+#include "store.hpp"
 
 namespace piml {
 
@@ -705,10 +706,11 @@ __device__ __forceinline__ void enc_bwd_sums2_body(const F5Args& F) {
         }
         F5_STAMP(4);
         // ---- the slot: dW2 | dW1 ----
+        // (store.hpp: written through -- the slot is this workgroup's last action, all of it would be dirty in the XCD's L2 when
+        // the launch ends, and its readers are the slot sums of the NEXT launch)
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) P[(size_t)(32 * w + f5_rho(r) + 4 * h) * EH + 32 * jb + n] = c[jb][r] + sm[jb][r];
+            store_acc32<PIML_WT_ENC_BWD_SLOTS>(P + (size_t)(32 * w) * EH + 32 * jb, EH, lane, [&](int r) { return c[jb][r] + sm[jb][r]; });
 #pragma unroll
         for (int cc = 0; cc < INC; ++cc) w1acc[cc] += __shfl_xor(w1acc[cc], 32, 64);
         if (h == 0) {
