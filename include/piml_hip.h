@@ -585,6 +585,41 @@ int piml_flow_stats(const float* P, const float* V, const float* M, const int* n
                     long long* map_vy, void* workspace, long long workspace_bytes, void* stream);
 
 /*
+ * Heading-frame pair statistics (viewstats.hip), S members in one call: where the others are in a walking
+ * agent's own frame.  P, V, M, n_active, the frames [t0, t1), the lags and the box as for piml_pair_stats.  Agent i takes
+ * part in slice (s, t) as for piml_flow_stats (M == 1, P finite, both components of V below 1024 in magnitude, slot below
+ * n_active[s]); a mover has sp = sqrt(vx^2 + vy^2) >= v_min and the heading h = v / sp.  Focal: a participant mover of frame t
+ * with has_box == 0 or x0 <= x < x1 and y0 <= y < y1.  Pair slice (s, t, k) for t0 <= t and t + L_k < t1 pairs every focal i of
+ * frame t with every participant j != i (as a slot) of frame t + L_k, mover or not, ordered pairs.  Per pair in float32 (true
+ * divisions and square roots, no contraction): d = p_j - p_i, r = sqrt(dx^2 + dy^2); pairs with r >= r_max are skipped
+ * entirely (r_max <= 0: no cut-off); a = dx hx + dy hy is the distance ahead, l = dy hx - dx hy the distance to the left;
+ * class c = 0 when j is not a mover, otherwise with q = h_i.h_j: 1 (with) if q >= cos_same, 2 (against) if q <= -cos_same, 3
+ * (across) else; with X = (float)(cell * half) formed on the host, cx = floor((a + X) / cell), cy = floor((l + X) / cell) and
+ * G = 2 half.  Outputs, int64, zeroed by the call, Q = 2^20:
+ *   focal, pairs (S, K + 1): focal agent-frames, ordered pairs evaluated;
+ *   map (S, K + 1, 4, G, G): pairs by [c][cy][cx] where 0 <= cx, cy < G;
+ *   nn_map (S, G G + 1): lag 0, each focal agent's nearest source (smallest r, ties to the lowest slot) by cy G + cx; G G when
+ *     it lies outside the map or the agent has no source;
+ *   front_gap (S, gap_bins + 1): lag 0, per focal agent the smallest a over the sources with a > 0 and |l| < corridor by
+ *     b = floor(a / gap_bin); gap_bins when b >= gap_bins or nobody is in front;
+ *   front_speed (S, gap_bins): the sum of llrintf(sp_i Q) over the focal agents of front_gap's bin b < gap_bins.
+ * A lag that reaches past the frames has no slices and zero counts.  workspace: at least
+ * piml_view_stats_workspace_bytes(S, K, half, gap_bins) bytes (-1 for negative arguments).  One memset and two launches, no
+ * host synchronisation (capturable).  Deterministic: integer outputs only, added with integer atomics; member s's results
+ * are bitwise those of an S = 1 call on member s alone.
+ * hipErrorInvalidValue, before any HIP call: S, T or N <= 0, N > 65536 (the per-slice u32 counters), frames outside [0, T] or
+ * empty, K outside 0..8, lags NULL (K > 0), not positive or not ascending, v_min, cell, corridor or gap_bin <= 0 or not
+ * finite, half outside 1..16, cos_same outside [0, 1], r_max NaN, gap_bins outside 1..256, a non-finite or empty box, a NULL
+ * input, output or workspace, or a workspace too small.
+ */
+long long piml_view_stats_workspace_bytes(int S, int K, int half, int gap_bins);
+int piml_view_stats(const float* P, const float* V, const float* M, const int* n_active, int S, int T, int N, int t0, int t1,
+                    const int* lags, int K, float v_min, float cell, int half, float cos_same, float r_max, float corridor,
+                    float gap_bin, int gap_bins, int has_box, float x0, float x1, float y0, float y1, long long* focal,
+                    long long* pairs, long long* map, long long* nn_map, long long* front_gap, long long* front_speed,
+                    void* workspace, long long workspace_bytes, void* stream);
+
+/*
  * Track statistics (trackstats.hip), S members in one call: what an agent does along its own track.  Slot n of
  * member s is one agent for the whole run; P (S, T, N, 2) and M (S, T, N) float32, n_active (S) int32 or NULL and the frames
  * [t0, t1) as for piml_pair_stats; velocities are not an input.  Agent i takes part at (s, t) when M == 1 and both

@@ -162,6 +162,9 @@ SIGNATURES = {
     'piml_flow_stats_workspace_bytes': [_i, _i, _i, _i],
     'piml_flow_stats': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _f, _i, _i,
                         _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _ll, _p],
+    'piml_view_stats_workspace_bytes': [_i, _i, _i, _i],
+    'piml_view_stats': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _f, _f, _i, _f, _f, _f, _f, _i, _i, _f, _f, _f, _f,
+                        _p, _p, _p, _p, _p, _p, _p, _ll, _p],
     'piml_track_stats_workspace_bytes': [_i, _i, _i],
     'piml_track_stats': [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                          _p, _p, _ll, _p],
@@ -354,6 +357,7 @@ def lib():
         L.piml_crowd_stats_voronoi_workspace_bytes.restype = _ll
         L.piml_pair_stats_workspace_bytes.restype = _ll
         L.piml_flow_stats_workspace_bytes.restype = _ll
+        L.piml_view_stats_workspace_bytes.restype = _ll
         L.piml_track_stats_workspace_bytes.restype = _ll
         L.piml_obstacle_stats_workspace_bytes.restype = _ll
         L.piml_line_stats_workspace_bytes.restype = _ll

@@ -421,26 +421,34 @@ OBJECTIVE_KEYS = {'crowd': ('fd_distance', 'map_distance', 'mean_speed_diff'),
                   'obstacles': ('hit_track_fraction_diff', 'contact_rate_diff', 'clearance_l1'),
                   'groups': ('group_fraction_diff', 'size_l1', 'member_distance_l1', 'abreast_l1', 'speed_ratio_diff'),
                   'tracks': ('heading_ac_max_diff', 'persistence_time_diff', 'msd_exponent_diff', 'acc_l1',
-                             'mean_acceleration_diff', 'straightness_l1', 'speed_l1', 'duration_l1')}
+                             'mean_acceleration_diff', 'straightness_l1', 'speed_l1', 'duration_l1'),
+                  'views': ('map_l1', 'nn_map_l1', 'gap_l1', 'front_back_diff', 'passing_side_diff', 'g_map_max_diff',
+                            'headway_slope_diff', 'headway_intercept_diff')}
 # speed_ratio_diff needs min_count GROUPED tracks on both sides, which a recorded clip does not have (GC 11, UCY 26): NaN at
 # any honest min_count, and a NaN term of non-zero weight makes J infinite -- so it is off unless `weights` switches it on
 DEFAULT_WEIGHTS = {'speed_ratio_diff': 0.0}
 # the track side: persistence_time_diff is NaN for both recorded clips (their heading autocorrelation never falls to 1 / e
 # inside the lags); speed_l1 and duration_l1 belong to the scene (the desired speeds and the routes), not the law
 TRACK_DEFAULT_WEIGHTS = {'persistence_time_diff': 0.0, 'speed_l1': 0.0, 'duration_l1': 0.0}
+# the view side: g_map_max_diff and the headway fit need min_count pairs per cell / agents per gap bin on both sides, which
+# a short clip or a small ensemble does not hold -- NaN there, so they are off unless `weights` switches them on
+VIEW_DEFAULT_WEIGHTS = {'g_map_max_diff': 0.0, 'headway_slope_diff': 0.0, 'headway_intercept_diff': 0.0}
 DEFAULT_BOUNDS = {'tau': (1e-3, None), 'Aw': (0.0, None), 'Bw': (None, 0.0), 'Ag': (0.0, None), 'group_dist': (0.0, None),
                   'An': (0.0, None), 'noise_tau': (0.0, None)}
 GROUP_OPTION_KEYS = ('radius', 'dv_max', 'v_min', 'min_time', 'share', 'r_bin', 'r_bins', 'a_bins')
 
 
 def stats_objective(crowd=None, pairs=None, ref_crowd=None, ref_pairs=None, weights=None, min_count=50, obstacles=None,
-                    ref_obstacles=None, groups=None, ref_groups=None, tracks=None, ref_tracks=None):
+                    ref_obstacles=None, groups=None, ref_groups=None, tracks=None, ref_tracks=None, views=None,
+                    ref_views=None):
     """(J, terms): how far simulated statistics are from a reference's.  crowd / ref_crowd: CrowdStats, pairs / ref_pairs:
     PairStats, obstacles / ref_obstacles: ObstacleStats, groups / ref_groups: GroupStats, tracks / ref_tracks: TrackStats
     (compare_track_stats' terms, OBJECTIVE_KEYS['tracks']: weight 1.0 for heading_ac_max_diff, msd_exponent_diff, acc_l1,
     mean_acceleration_diff and straightness_l1, 0.0 by default (TRACK_DEFAULT_WEIGHTS) for persistence_time_diff -- NaN for
     both recorded clips -- and for speed_l1 and duration_l1, which belong to the scene, not the law); a side takes part when both of its
-    statistics are given.  terms is
+    statistics are given.  views / ref_views: ViewStats (compare_view_stats' terms, OBJECTIVE_KEYS['views']: weight 1.0 for
+    map_l1, nn_map_l1, gap_l1, front_back_diff and passing_side_diff, 0.0 by default (VIEW_DEFAULT_WEIGHTS) for
+    g_map_max_diff and the two headway terms, NaN on short clips).  terms is
     the union of compare_crowd_stats(crowd, ref_crowd, min_count), compare_pair_stats(pairs, ref_pairs, min_count),
     compare_obstacle_stats(obstacles, ref_obstacles, min_count) and compare_group_stats(groups, ref_groups, min_count) for
     the sides given, and
@@ -454,7 +462,7 @@ def stats_objective(crowd=None, pairs=None, ref_crowd=None, ref_pairs=None, weig
     from .crowdstats import compare_crowd_stats
     from .pairstats import compare_pair_stats
     known = OBJECTIVE_KEYS['crowd'] + OBJECTIVE_KEYS['pairs'] + OBJECTIVE_KEYS['obstacles'] + OBJECTIVE_KEYS['groups'] + \
-        OBJECTIVE_KEYS['tracks']
+        OBJECTIVE_KEYS['tracks'] + OBJECTIVE_KEYS['views']
     unknown = sorted(set(weights or {}) - set(known))
     if unknown:
         raise ValueError(f'stats_objective: weights for unknown terms {unknown} (of {known})')
@@ -477,11 +485,15 @@ def stats_objective(crowd=None, pairs=None, ref_crowd=None, ref_pairs=None, weig
         from .trackstats import compare_track_stats
         terms.update(compare_track_stats(tracks, ref_tracks, min_count))
         keys += OBJECTIVE_KEYS['tracks']
+    if views is not None and ref_views is not None:
+        from .viewstats import compare_view_stats
+        terms.update(compare_view_stats(views, ref_views, min_count))
+        keys += OBJECTIVE_KEYS['views']
     if not keys:
-        raise ValueError('stats_objective: neither crowd, pair, obstacle, group nor track statistics with a reference')
+        raise ValueError('stats_objective: neither crowd, pair, obstacle, group, track nor view statistics with a reference')
     J = 0.0
     for k in keys:
-        w = float((weights or {}).get(k, DEFAULT_WEIGHTS.get(k, TRACK_DEFAULT_WEIGHTS.get(k, 1.0))))
+        w = float((weights or {}).get(k, DEFAULT_WEIGHTS.get(k, TRACK_DEFAULT_WEIGHTS.get(k, VIEW_DEFAULT_WEIGHTS.get(k, 1.0)))))
         if terms[k] is None or w == 0.0:
             continue
         if math.isnan(terms[k]):
@@ -498,12 +510,16 @@ class _StatsEvaluator:
     """calibrate_mlapm_to_stats' objective on the GPU: list of candidate dicts -> list of J, one SweepRun generation each."""
 
     def __init__(self, scenario, reference, frames, seeds, population, radius, capacity, crowd_kw, pair_kw, weights,
-                 min_count, device, obstacle_kw=None, wall_cutoff=None, group_kw=None, components='device', track_kw=None):
+                 min_count, device, obstacle_kw=None, wall_cutoff=None, group_kw=None, components='device', track_kw=None,
+                 view_kw=None):
         from . import crowdstats, pairstats
         from .models.mlapm import DEFAULT_WALL_CUTOFF, SweepRun
-        self.ref_obstacles = self.ref_groups = self.ref_tracks = None
+        self.ref_obstacles = self.ref_groups = self.ref_tracks = self.ref_views = None
         if isinstance(reference, (tuple, list)):
-            if len(reference) == 5:                  # (crowd, pairs, obstacles, groups, tracks): the track side too
+            if len(reference) == 6:                  # (crowd, pairs, obstacles, groups, tracks, views): the view side too
+                self.ref_crowd, self.ref_pairs, self.ref_obstacles, self.ref_groups, self.ref_tracks, self.ref_views = \
+                    reference
+            elif len(reference) == 5:                  # (crowd, pairs, obstacles, groups, tracks): the track side too
                 self.ref_crowd, self.ref_pairs, self.ref_obstacles, self.ref_groups, self.ref_tracks = reference
             elif len(reference) == 4:                  # (crowd, pairs, obstacles, groups): the group side takes part too
                 self.ref_crowd, self.ref_pairs, self.ref_obstacles, self.ref_groups = reference
@@ -519,6 +535,9 @@ class _StatsEvaluator:
             if track_kw is None and self.ref_tracks is not None:
                 from .trackstats import OPTION_KEYS as TRACK_OPTION_KEYS
                 track_kw = _options_of(self.ref_tracks, [k for k in TRACK_OPTION_KEYS if k != 'dt'])
+            if view_kw is None and self.ref_views is not None:
+                from .viewstats import OPTION_KEYS as VIEW_OPTION_KEYS
+                view_kw = _options_of(self.ref_views, VIEW_OPTION_KEYS)
             if crowd_kw is None and self.ref_crowd is not None:
                 crowd_kw = crowdstats.call_options(self.ref_crowd)
             if pair_kw is None and self.ref_pairs is not None:
@@ -535,15 +554,18 @@ class _StatsEvaluator:
             if frames is None:
                 frames = int(torch.as_tensor(reference.position).shape[0])
         if self.ref_crowd is None and self.ref_pairs is None and self.ref_obstacles is None and self.ref_groups is None and \
-                self.ref_tracks is None:
+                self.ref_tracks is None and self.ref_views is None:
             raise ValueError('calibrate_mlapm_to_stats: the reference holds no statistics')
         self.crowd_kw, self.pair_kw, self.obstacle_kw = dict(crowd_kw or {}), dict(pair_kw or {}), dict(obstacle_kw or {})
         self.group_kw, self.components, self.track_kw = dict(group_kw or {}), components, dict(track_kw or {})
+        self.view_kw = dict(view_kw or {})
         self.weights, self.min_count, self.radius = weights, min_count, radius
         self.frames = 200 if frames is None else int(frames)
         self.run = SweepRun(scenario, self.frames, population, seeds, capacity=capacity, device=device,
                             wall_cutoff=DEFAULT_WALL_CUTOFF if wall_cutoff is None else wall_cutoff)
         self.seconds = {'run': 0.0, 'crowd': 0.0, 'pairs': 0.0, 'obstacles': 0.0, 'groups': 0.0, 'tracks': 0.0, 'host': 0.0}
+        if self.ref_views is not None:
+            self.seconds['views'] = 0.0
         self.last_terms = []
 
     def __call__(self, cands):
@@ -587,6 +609,12 @@ class _StatsEvaluator:
             kw = {'dt': float(sw.time_unit), **self.track_kw}
             tracks = track_stats(sw.position, mask, n_active=n_active, **kw)
         t3d = time.perf_counter()
+        views = None
+        if self.ref_views is not None:               # one call for every member and lag, the reference's options
+            from .viewstats import view_stats
+            views = view_stats(sw.position, sw.velocity, mask, n_active=n_active, **self.view_kw)
+            self.seconds['views'] += time.perf_counter() - t3d
+        t3e = time.perf_counter()
         out, self.last_terms = [], []
         for c in range(sw.n_candidates):
             group = sw.members_of(c)
@@ -599,12 +627,13 @@ class _StatsEvaluator:
                                        self.ref_crowd, self.ref_pairs, self.weights, self.min_count,
                                        None if obstacles is None else obstacles.select(group).pooled(), self.ref_obstacles,
                                        None if groups is None else groups.select(group).pooled(), self.ref_groups,
-                                       None if tracks is None else tracks.select(group).pooled(), self.ref_tracks)
+                                       None if tracks is None else tracks.select(group).pooled(), self.ref_tracks,
+                                       None if views is None else views.select(group).pooled(), self.ref_views)
             out.append(J)
             self.last_terms.append(terms)
         t4 = time.perf_counter()
         for k, dt in zip(('run', 'crowd', 'pairs', 'obstacles', 'groups', 'tracks', 'host'),
-                         (t1 - t0, t2 - t1, t3 - t2, t3b - t3, t3c - t3b, t3d - t3c, t4 - t3d)):
+                         (t1 - t0, t2 - t1, t3 - t2, t3b - t3, t3c - t3b, t3d - t3c, t4 - t3e)):
             self.seconds[k] += dt
         return out
 
@@ -613,8 +642,13 @@ def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=P
                              population=16, generations=30, elite=0.25, sigma=0.2, sigma_floor=1e-3, bounds=None,
                              weights=None, crowd_kw=None, pair_kw=None, search_seed=0, radius=0.3, capacity=None,
                              evaluate=None, min_count=50, device='cuda', obstacle_kw=None, wall_cutoff=None, group_kw=None,
-                             track_kw=None):
+                             track_kw=None, view_kw=None):
     """Fit MLAPM's constants so that the law, run open-world in `scenario`, reproduces the reference's crowd statistics.
+
+    The view side: a reference 6-tuple (CrowdStats | None, PairStats | None, ObstacleStats | None, GroupStats | None,
+    TrackStats | None, ViewStats | None) adds the heading-frame statistics, the side that sees the law's anisotropy (theta,
+    C, D): one view_stats call (view_kw, default the reference's viewstats.OPTION_KEYS options) covers every member and lag
+    of a generation and enters stats_objective with the reference's; `seconds` then has a 'views' entry.
 
     The fluctuation term: fit may also name An, noise_tau (NOISE_PARAM_NAMES), and init may carry them: the candidates then
     run the frames with the fluctuation term (MLAPM(..., An=, noise_tau=)), in any scene.  init must hold An when either is
@@ -715,7 +749,7 @@ def calibrate_mlapm_to_stats(scenario, reference, version='GC', init=None, fit=P
     if evaluate is None:
         evaluate = terms_of = _StatsEvaluator(scenario, reference, frames, seeds, population, radius, capacity, crowd_kw,
                                               pair_kw, weights, min_count, device, obstacle_kw, wall_cutoff, group_kw,
-                                              track_kw=track_kw)
+                                              track_kw=track_kw, view_kw=view_kw)
     scale = np.array([abs(start[k]) if start[k] != 0 else 1.0 for k in fit])
     lo = np.array([-np.inf if limits.get(k, (None, None))[0] is None else limits[k][0] for k in fit], np.float64)
     hi = np.array([np.inf if limits.get(k, (None, None))[1] is None else limits[k][1] for k in fit], np.float64)
@@ -806,7 +840,7 @@ def get_args(argv=None):
                    help="fit the law to the clip's crowd statistics, run open-world in the clip's own scene "
                         '(calibrate_mlapm_to_stats), instead of to its trajectories')
     p.add_argument('--match', type=str, default=None,
-                   help='--match-stats: the statistics to match (crowd, pairs, obstacles, groups, tracks); default crowd,pairs, '
+                   help='--match-stats: the statistics to match (crowd, pairs, obstacles, groups, tracks, views); default crowd,pairs, '
                         'obstacles too when the law has a wall term (--init Aw=..,Bw=..) and groups too when it has a group '
                         'term (--init Ag=..) and tracks too when it has a fluctuation term (--init An=..)')
     p.add_argument('--scene-groups', dest='scene_groups', type=str, default=None,
@@ -861,8 +895,8 @@ def get_args(argv=None):
             a.match = ('crowd,pairs,obstacles' if wall_names else 'crowd,pairs') + (',groups' if group_names else '') + \
                 (',tracks' if noise_names else '')
         a.match = tuple(filter(None, (x.strip() for x in a.match.split(','))))
-        if not a.match or any(x not in ('crowd', 'pairs', 'obstacles', 'groups', 'tracks') for x in a.match):
-            p.error(f"--match: 'crowd', 'pairs', 'obstacles', 'groups', 'tracks' or several expected, got {a.match}")
+        if not a.match or any(x not in ('crowd', 'pairs', 'obstacles', 'groups', 'tracks', 'views') for x in a.match):
+            p.error(f"--match: 'crowd', 'pairs', 'obstacles', 'groups', 'tracks', 'views' or several expected, got {a.match}")
         if a.scene_groups is not None and a.scene_groups != 'auto':
             try:
                 from .simulate import load_scene_groups
@@ -967,7 +1001,11 @@ def _main_stats(a, raw, init):
     if 'tracks' in a.match:
         from .trackstats import track_stats_of_raw
         ref_tracks = track_stats_of_raw(raw, frames=(lo, hi))
-    res = calibrate_mlapm_to_stats(scene, (ref_crowd, ref_pairs, ref_obstacles, ref_groups, ref_tracks), version=a.version, init=init, fit=a.fit,
+    reference = (ref_crowd, ref_pairs, ref_obstacles, ref_groups, ref_tracks)
+    if 'views' in a.match:
+        from .viewstats import view_stats_of_raw
+        reference += (view_stats_of_raw(raw, frames=(lo, hi)),)
+    res = calibrate_mlapm_to_stats(scene, reference, version=a.version, init=init, fit=a.fit,
                                    frames=hi - lo, seeds=a.seeds, population=a.population, generations=a.generations,
                                    search_seed=a.search_seed, radius=a.radius, wall_cutoff=a.wall_cutoff)
     print(f'[calibrate] {a.version} against the statistics ({", ".join(a.match)}) of frames {lo}:{hi}, {a.population} '

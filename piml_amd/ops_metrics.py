@@ -254,6 +254,57 @@ def flow_stats_frames(P, V, M, v_min=0.1, r_bin=0.1, r_bins=60, r_max=6.0, axis=
     return out
 
 
+VIEW_MAX_HALF = 16            # piml_view_stats' limits on half (the map is 2 half x 2 half), gap_bins, the number of lags
+VIEW_MAX_BINS = 256           # and the slots per frame
+VIEW_MAX_LAGS = 8
+VIEW_MAX_N = 65536
+VIEW_Q = 1 << 20              # the fixed-point scale of front_speed
+VIEW_COS_SAME = float(np.float32(np.cos(np.pi / 4)))
+
+
+def view_stats_frames(P, V, M, lags=(64, 128, 192), v_min=0.1, cell=0.25, half=12, cos_same=VIEW_COS_SAME, r_max=None,
+                      corridor=0.4, gap_bin=0.1, gap_bins=60, box=None, frames=None, n_active=None):
+    """The device half of piml_amd.viewstats.view_stats (piml_view_stats): P, V (S, T, N, 2) and M (S, T, N)
+    float32 GPU tensors, lags a sequence of K positive ascending ints, r_max a distance or None, box (x0, x1, y0, y1) or
+    None, frames (a, b) or None, n_active (S) int32 GPU tensor or None.  Returns a dict of int64 GPU tensors -- focal, pairs
+    (S, K+1), map (S, K+1, 4, G, G) with G = 2 half, nn_map (S, G G + 1), front_gap (S, gap_bins+1), front_speed (S,
+    gap_bins) -- with no host synchronisation (capturable in a graph)."""
+    import ctypes
+    P, V, M = _gpu_f32('P', P), _gpu_f32('V', V), _gpu_f32('M', M)
+    if P.dim() != 4 or P.shape[-1] != 2 or V.shape != P.shape or M.shape != P.shape[:3]:
+        raise ValueError(f'expected P, V (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(V.shape)}, '
+                         f'{tuple(M.shape)}')
+    S, T, N = P.shape[:3]
+    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    lags = [int(x) for x in lags]
+    K, H, GB = len(lags), int(half), int(gap_bins)
+    dev = P.device
+    if n_active is not None:
+        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
+                or tuple(n_active.shape) != (S,):
+            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
+        n_active = n_active.contiguous()
+    x0, x1, y0, y1 = (0.0, 0.0, 0.0, 0.0) if box is None else (float(v) for v in box)
+    i64 = dict(device=dev, dtype=torch.int64)
+    K1, G, GBc = K + 1, 2 * max(H, 0), max(GB, 0)
+    out = dict(focal=torch.empty(S, K1, **i64), pairs=torch.empty(S, K1, **i64), map=torch.empty(S, K1, 4, G, G, **i64),
+               nn_map=torch.empty(S, G * G + 1, **i64), front_gap=torch.empty(S, GBc + 1, **i64),
+               front_speed=torch.empty(S, GBc, **i64))
+    L = _lib.lib()
+    ws_bytes = L.piml_view_stats_workspace_bytes(S, K, max(H, 0), GBc)
+    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    lag_arr = (ctypes.c_int * max(K, 1))(*lags)
+    with torch.cuda.device(dev):
+        _lib.check(L.piml_view_stats(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), S, T, N, a, b,
+                                     ctypes.addressof(lag_arr) if K else None, K, float(v_min), float(cell), H,
+                                     float(cos_same), float(r_max) if r_max is not None else 0.0, float(corridor),
+                                     float(gap_bin), GB, int(box is not None), x0, x1, y0, y1,
+                                     *(_ptr(out[k]) for k in ('focal', 'pairs', 'map', 'nn_map', 'front_gap', 'front_speed')),
+                                     _ptr(ws), ws.numel(), _stream()),
+                   'piml_view_stats')
+    return out
+
+
 TRACK_TILE = 1024             # piml_track_stats: frames per staged LDS tile (PIML_TRACK_TILE), lags per pass
 TRACK_LAG_LANES = 128         # (PIML_TRACK_LAG_LANES), and its limits on n_lags, the slots per frame, acc_bins and d_max
 TRACK_MAX_LAGS = 512

@@ -489,6 +489,11 @@ class ScenarioResult(types.SimpleNamespace):
         from .flowstats import flow_stats
         return flow_stats(self.position, self.velocity, self.mask_p, n_active=[self.num_agents], **kw)
 
+    def view_stats(self, **kw):
+        """piml_amd.viewstats.view_stats of the run (simulated velocities; slots past num_agents not swept)."""
+        from .viewstats import view_stats
+        return view_stats(self.position, self.velocity, self.mask_p, n_active=[self.num_agents], **kw)
+
     def track_stats(self, **kw):
         """piml_amd.trackstats.track_stats of the run (positions only, dt = time_unit; slots past num_agents not swept)."""
         from .trackstats import track_stats
@@ -574,6 +579,13 @@ class ScenarioEnsemble(types.SimpleNamespace):
         cap = self.position.shape[2]
         return flow_stats(self.position, self.velocity, self.mask_p, n_active=[min(int(n), cap) for n in self.spawned], **kw)
 
+    def view_stats(self, **kw):
+        """piml_amd.viewstats.view_stats of every member in one call (member m's slots past its num_agents not swept):
+        member m's statistics are bitwise those of member(m).view_stats(**kw)."""
+        from .viewstats import view_stats
+        cap = self.position.shape[2]
+        return view_stats(self.position, self.velocity, self.mask_p, n_active=[min(int(n), cap) for n in self.spawned], **kw)
+
     def track_stats(self, **kw):
         """piml_amd.trackstats.track_stats of every member in one call (dt = time_unit; member m's slots past its num_agents
         not swept): member m's statistics are bitwise those of member(m).track_stats(**kw)."""
@@ -624,7 +636,7 @@ class ScenarioSweep(ScenarioEnsemble):
     """What `MLAPM.simulate_sweep` returns: a ScenarioEnsemble of n_candidates * seeds_per_candidate members laid out
     candidate-major -- member c * seeds_per_candidate + k ran law params[c] under the k-th seed -- plus params (the
     candidates' dicts), n_candidates and seeds_per_candidate.  `seeds` lists every member's seed (the seed list once per
-    candidate); crowd_stats / pair_stats / flow_stats / track_stats / obstacle_stats / line_stats / group_stats compute all members in one call, and `.select(sweep.members_of(c)).pooled()` of
+    candidate); crowd_stats / pair_stats / flow_stats / view_stats / track_stats / obstacle_stats / line_stats / group_stats compute all members in one call, and `.select(sweep.members_of(c)).pooled()` of
     the result pools one candidate."""
 
     def members_of(self, c):

@@ -87,6 +87,11 @@ def get_args(argv=None):
                         'defaults, no box) of the run or ensemble as JSON to this path instead of writing clips')
     p.add_argument('--flow-axis', dest='flow_axis', type=str, default='x',
                    help="--flow-stats: the lane axis, x, y, auto (principal axis of the velocities) or an angle in degrees")
+    p.add_argument('--view-stats', dest='view_stats', type=str, default=None,
+                   help='write the heading-frame pair statistics (piml_amd.viewstats: front/back ratio, passing side, '
+                        'headway; defaults, no box) of the run or ensemble as JSON to this path instead of writing clips')
+    p.add_argument('--view-lags', dest='view_lags', type=str, default='64,128,192',
+                   help='--view-stats: the scrambling lags in frames')
     p.add_argument('--track-stats', dest='track_stats', type=str, default=None,
                    help='write the track statistics (piml_amd.trackstats: heading persistence, MSD, acceleration, path '
                         'shape; defaults, dt = the time unit) of the run or ensemble as JSON to this path instead of writing '
@@ -118,6 +123,12 @@ def get_args(argv=None):
         own.flow_axis = parse_axis(own.flow_axis)
     except ValueError as ex:
         p.error(f'--flow-axis: {ex}')
+    try:
+        from .pairstats import parse_lags
+        from .viewstats import check_options
+        own.view_lags = check_options(lags=parse_lags(own.view_lags))[0]
+    except ValueError as ex:
+        p.error(f'--view-lags: {ex}')
     if (own.line_stats is None) != (own.lines is None):
         p.error('--line-stats needs --lines, and --lines feeds --line-stats only')
     if own.lines is not None:
@@ -324,7 +335,7 @@ def _clip_scene(own):
 
 def _stats_path(own):
     return ', '.join(p for p in (own.stats, own.pair_stats, own.flow_stats, own.track_stats, own.obstacle_stats, own.line_stats,
-                                 own.group_stats)
+                                 own.group_stats, own.view_stats)
                      if p is not None)
 
 
@@ -373,6 +384,11 @@ def _stats(res, own):
         gs = res.group_stats()
         gs.to_json(own.group_stats)
         groupstats.print_group_stats(gs, 'simulate --group-stats')
+    if own.view_stats is not None:
+        from . import viewstats
+        vs = res.view_stats(lags=own.view_lags)
+        vs.to_json(own.view_stats)
+        viewstats.print_view_stats(vs, 'simulate --view-stats')
 
 
 def _sweep(sim, scenario, own, run_kw):
@@ -427,6 +443,12 @@ def _sweep(sim, scenario, own, run_kw):
         entries = [{'params': sw.params[c], 'file': own.params_sweep[c], 'stats': gs.select(g).pooled().to_json()}
                    for c, g in enumerate(groups)]
         with open(own.group_stats, 'w') as fh:
+            json.dump({'seeds': own.seeds, 'candidates': entries}, fh)
+    if own.view_stats is not None:
+        vs = sw.view_stats(lags=own.view_lags)
+        entries = [{'params': sw.params[c], 'file': own.params_sweep[c], 'stats': vs.select(g).pooled().to_json()}
+                   for c, g in enumerate(groups)]
+        with open(own.view_stats, 'w') as fh:
             json.dump({'seeds': own.seeds, 'candidates': entries}, fh)
     where = _stats_path(own)
     if not where:
