@@ -441,6 +441,10 @@ int piml_collision_label(const float* ped_features, size_t rows, int row_stride,
  * err = sum_i |u_i - u_i'| is < thresh (the reference's break, :161-172, 2-D input).  Float32 arithmetic as the reference's,
  * the final sum(exp(M) * C) accumulated in float64.  cost (F) float32, iters (F) int32 = iterations run; u (F, n) and
  * v (F, m) (each may be NULL) = the final potentials at the frame's slots, 0 at absent ones.
+ * A frame with an empty side (the reference cannot run one) returns, leaves the other frames alone and has cost 0.  No
+ * present point in x: err is 0, so with thresh > 0 the loop stops after its first iteration (iters = min(1, max_iter)), and
+ * that iteration sets v to +inf at y's present slots.  Points in x but none in y: err is inf, then NaN, so iters = max_iter,
+ * and u is +inf at x's present slots (max_iter >= 1).  One point a side: the squared distance, u + v = it.
  * hipErrorInvalidValue: F, n or m < 0, n or m > 4096, eps <= 0 (or NaN), max_iter < 0, a NULL x / y (with points) or
  * cost / iters.  F == 0 is a no-op.
  */
@@ -454,7 +458,9 @@ int piml_sinkhorn_frames(const float* x, const float* y, const unsigned char* ma
  * the frame's (n+m)^2 pairs unless fix_sigma != 0 (Python truthiness: 0 means "computed"), divided by
  * kernel_mul^(kernel_num // 2); K = sum_i exp(-L2 / (bandwidth * kernel_mul^i)), i < kernel_num <= 8;
  * out[f] = XX / n^2 + YY / m^2 - XY / (n m) - YX / (m n) (an empty block adds 0).  float64 from the float32 positions on,
- * out (F) float32.  All points coinciding give bandwidth 0 and NaN, as in the reference.
+ * out (F) float32.  All points coinciding give bandwidth 0 and NaN, as in the reference.  With one side empty the result is
+ * the other side's block alone (YY / m^2 or XX / n^2, the bandwidth from its points); one point in total gives NaN
+ * ((n+m)^2 - (n+m) == 0), no point at all gives 0.
  * hipErrorInvalidValue: F, n or m < 0, n or m > 4096, kernel_num outside 1..8, a NULL x / y (with points) or out.
  * F == 0 is a no-op.
  */

@@ -15,9 +15,9 @@ THRESH = 0.1
 BAND = 1e-4
 
 
-def sinkhorn64(x, y, eps=0.1, max_iter=100, thresh=THRESH):
+def sinkhorn64(x, y, eps=0.1, max_iter=100, thresh=THRESH, potentials=False):
     """SinkhornDistance.forward (src/functions/metrics.py:129-187) on one frame in float64: (cost, iterations, [err of
-    every iteration run])"""
+    every iteration run]) and, with potentials, the final u and v"""
     x, y = torch.as_tensor(x, dtype=torch.float64), torch.as_tensor(y, dtype=torch.float64)
     C = ((x.unsqueeze(-2) - y.unsqueeze(-3)) ** 2).sum(-1)
     lmu, lnu = np.log(1.0 / x.shape[0] + 1e-8), np.log(1.0 / y.shape[0] + 1e-8)
@@ -30,7 +30,8 @@ def sinkhorn64(x, y, eps=0.1, max_iter=100, thresh=THRESH):
         u = un
         if errs[-1] < thresh:
             break
-    return float((torch.exp((-C + u.unsqueeze(-1) + v.unsqueeze(-2)) / eps) * C).sum()), len(errs), errs
+    out = float((torch.exp((-C + u.unsqueeze(-1) + v.unsqueeze(-2)) / eps) * C).sum()), len(errs), errs
+    return out + (u, v) if potentials else out
 
 
 def mmd64(x, y, kernel_mul=2.0, kernel_num=5, fix_sigma=None):
