@@ -367,11 +367,27 @@ def test_fused_row_decoder_matches_float64(rows, rowdec_products):
 
 
 @pytest.mark.parametrize('name', ['PINNSF_bottleneck_multitask', 'PINNSF_bottleneck'])
-def test_bottleneck_models_with_fused_row_decoder_match_library_decoders(name):
+@pytest.mark.parametrize('agents', [600, 2100])
+def test_bottleneck_models_with_fused_row_decoder_match_library_decoders(name, agents, rowdec_products):
     """The bottleneck models on the fused row decoder vs the same models with their decoders on library GEMMs
-    (PIML_FUSED_ROW_DECODER=0): every output and gradient."""
+    (PIML_FUSED_ROW_DECODER=0): every output and gradient.  600 agents stay on the few-rows kernels; 2100 give 12 600 +
+    21 000 rows = 1051 tiles, so the packed forward and (PINNSF_bottleneck: nothing reads `decoded`) the backward without
+    g_d2 run on the many-rows kernels inside the model, in both products modes.
+
+    The two sides sum a decoder's first layer in different orders, so a hidden unit whose pre-activation is within rounding
+    of zero can fall on either side of the ReLU's step, and that row's input gradient then differs by the whole term (at
+    2100 agents, f32 products: one unit of 2.15 million, float64 pre-activation 5.9e-10 on embeddings of order 1, put the
+    two models 6.8e-3 / 1.0e-2 apart: that row's gradient of the embeddings 5e-3 / 8e-3 of the tensor's max-abs from
+    float64, every other row within 2e-7; the library side was the nearer one, 2.7e-7, so the bound stays at 2e-5 and
+    split bf16 products passed it unguarded at 3.2e-6 / 3.7e-6).  As in test_fused_row_decoder_matches_float64 such rows are
+    taken out of the inputs: an agent that owns one (float64, within 1e-5) gets the features of an agent that owns none --
+    every agent is computed on its own.  A unit is that close with probability 64 * 2e-5 * (the density of the
+    pre-activations at zero, about 3.6: 155 of 33 600 rows at 2100 agents), 16 rows an agent: 7 % of the agents expected,
+    15 % allowed."""
     import types
     import piml_amd.models.model as MODEL
+    import rowdec_shapes
+    assert rowdec_shapes.many_rows((agents * 6, agents * 10)) == (agents == 2100)
     args = types.SimpleNamespace(
         ped_feature_dim=6, obs_feature_dim=6, self_feature_dim=7, encoder_hidden_size=128,
         processor_hidden_size=128, decoder_hidden_size=64, encoder_hidden_layers=3, processor_hidden_layers=16,
@@ -379,25 +395,56 @@ def test_bottleneck_models_with_fused_row_decoder_match_library_decoders(name):
     torch.manual_seed(0)
     net = getattr(MODEL, name)(args).to(DEV).eval()
     g = torch.Generator().manual_seed(2)
-    base = [torch.randn(600, 6, 6, generator=g).to(DEV), torch.randn(600, 10, 6, generator=g).to(DEV),
-            torch.randn(600, 7, generator=g).to(DEV)]
+    base = [torch.randn(agents, 6, 6, generator=g).to(DEV), torch.randn(agents, 10, 6, generator=g).to(DEV),
+            torch.randn(agents, 7, generator=g).to(DEV)]
     res = {}
+
+    def near_kink(guard):
+        """agents with a row-decoder hidden unit whose float64 pre-activation is within `guard` of zero"""
+        from piml_amd import ops
+        fed, real = [], ops.fused_row_decoder
+        ops.fused_row_decoder = lambda brs, packs=None: (fed.extend(brs), real(brs, packs=packs))[1]
+        try:
+            net(*[t.clone().requires_grad_(True) for t in base])
+        finally:
+            ops.fused_row_decoder = real
+        assert [tuple(b['emb'].shape) for b in fed] == [(agents, 6, 128), (agents, 10, 128)]
+        bad = torch.zeros(agents, dtype=torch.bool, device=DEV)
+        for b in fed:
+            z = b['emb'].detach().double() @ b['decoder'][0].detach().double().t() + b['decoder'][1].detach().double()
+            bad |= (z.abs() < guard).flatten(1).any(1)
+        return bad
+    bad = near_kink(1e-5)
+    clean = (~bad).nonzero().flatten()
+    print(f'[rowdec] {name}, {agents} agents: {int(bad.sum())} agents own a row on a ReLU kink of a decoder')
+    assert int(bad.sum()) <= 0.15 * agents
+    donors = clean[torch.arange(int(bad.sum()), device=DEV) % len(clean)]
+    for t in base:
+        t[bad] = t[donors]
+    assert not bool(near_kink(0.5e-5).any())
+
+    def step():
+        ins = [t.clone().requires_grad_(True) for t in base]
+        net.zero_grad(set_to_none=True)
+        out = net(*ins)
+        (out[0].square().sum() + out[1].sum() * 1e-2 + out[2].square().sum() * 1e-3 + out[-1].sum()).backward()
+        return [o.detach() for o in out] + [t.grad for t in ins] + [p.grad for p in net.parameters() if p.grad is not None]
     try:
         for fused in (True, False):
             MODEL.FUSED_ROW_DECODER = fused
-            ins = [t.clone().requires_grad_(True) for t in base]
-            net.zero_grad(set_to_none=True)
-            out = net(*ins)
-            (out[0].square().sum() + out[1].sum() * 1e-2 + out[2].square().sum() * 1e-3 + out[-1].sum()).backward()
-            res[fused] = [o.detach() for o in out] + [t.grad for t in ins] + \
-                [p.grad for p in net.parameters() if p.grad is not None]
+            res[fused] = step()
     finally:
         MODEL.FUSED_ROW_DECODER = True
+    with net.packed_weights():           # the forward on images packed ahead (piml_rowdecoder_fwd_packed): the same kernels
+        packed = step()
+    assert len(packed) == len(res[True])
+    for a, b in zip(packed, res[True]):
+        assert torch.equal(a, b)
     assert len(res[True]) == len(res[False])
     worst = 0.0
     for a, b in zip(res[True], res[False]):
         worst = max(worst, float((a - b).abs().max() / b.abs().max().clamp_min(1e-12)))
-    print(f'{name}: fused row decoder vs library decoders, max rel err {worst:.1e}')
+    print(f'[rowdec] {name}, {agents} agents ({rowdec_products}): fused row decoder vs library decoders, max rel err {worst:.1e}')
     assert worst <= 2e-5
 
 
