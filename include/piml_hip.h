@@ -1222,6 +1222,78 @@ int piml_scenario_step_mlapm_noise(const piml_scenario* s, const piml_scenario_r
                                    int frame_offset, void* stream);
 
 /*
+ * Routing by a static floor field for the MLAPM scenario frame (ABI 35, additive): for every gate g of a scene of gates
+ * (GC's spawn law: entries (E, P, 2), exit_idx) the geodesic distance u[g] to the gate over the free cells of a grid, which
+ * the agents descend instead of walking the straight line to their destination.
+ *
+ * The grid: gx x gy cells of side `cell` from the origin (x0, y0), 1 <= gx, gy <= 1024, a point's cell
+ * (floor((q.x - x0) / cell), floor((q.y - y0) / cell)) in float32 as in piml_wall_grid, planes row-major (gy, gx).
+ * blocked (gy, gx) bytes: the cells no agent may enter; cells outside the grid count as blocked.  goal (G, gy, gx) bytes:
+ * gate g's cells; a goal cell is free whatever `blocked` says.  u (G, gy, gx) float32 IN CELL UNITS.
+ *
+ * piml_nav_relax: `launches` launches of K = 8 Jacobi steps each of the first-order Godunov upwind update with h = 1,
+ *   a = min(left, right), b = min(down, up), lo = min(a, b), hi = max(a, b),
+ *   cand = lo + 1                                       when hi is not finite or hi - lo >= 1,
+ *        = 0.5 ((lo + hi) + sqrt(2 - (hi - lo)^2))      otherwise,
+ *   u' = cand < u ? cand : u;  a goal cell is 0 and any other blocked cell +inf, before and after,
+ * every operation one correctly rounded float32 operation, so a numpy float32 run is the same function bit for bit
+ * (tests/nav_ref.py).  Launch j reads u_a and writes u_b for even j and the other way round for odd j (ping-pong; every
+ * cell of the written buffer is written), so after an even number of launches the result is in u_a.  The caller
+ * initialises u_a (0 on goal cells, +inf elsewhere is the field's start; any state is stepped as it stands).  A workgroup
+ * of 256 threads takes a 32 x 32 tile of one gate's plane, stages it with a halo of K cells in LDS, steps K times on the
+ * shrinking region (trapezoidal blocking: bitwise K steps of the whole plane) and writes the tile.  changed (G) int32: a
+ * thread whose output cell differs from its input cell stores 1 into changed[g] (a plain store; never cleared here).  u
+ * only decreases, so a launch that changed nothing left a fixed point.  No atomics, no host synchronisation; capturable.
+ * hipErrorInvalidValue (before any launch): a NULL buffer; u_a == u_b; G outside 1..64; gx or gy outside 1..1024;
+ * launches < 0.  launches == 0 is a no-op.
+ *
+ * piml_nav_grid: the field as the lookup reads it.  near (cell units, >= 0): within it the agent walks to its own
+ * destination point.
+ *
+ * piml_nav_direction: for every row a unit vector e and a branch code, one wave per row (the loads are wave-uniform):
+ *   0, straight: e = (dest - p) / max(|dest - p|, 1e-12), bitwise the frame's own line -- when p is NaN, the gate is outside
+ *      0..G-1, p's cell c is outside the grid, u[c] is not finite, u[c] <= near, or neither branch below applies;
+ *   1, bilinear: the four cell centres around p are inside the grid and their u finite: e = -grad of their bilinear
+ *      interpolant at p, normalised; a gradient whose squared norm is 0 falls through to
+ *   2, descent: e points from p to the centre of the 8-neighbour n of c that maximises (u[c] - u[n]) / |n - c| > 0, u[n]
+ *      finite; a diagonal n is skipped when either orthogonal cell beside it is not finite (no corner is cut); ties go to
+ *      the first in the order E, W, N, S, NE, NW, SE, SW (N = +y); `neighbour` gets its position in that order, -1 in
+ *      the other branches.
+ * The selection (branch, neighbour) is exact float32; the value uses the fast reciprocal square root (1e-5 relative).
+ * position, destination, direction (rows, 2); gate, branch, neighbour (rows) int32; branch and neighbour may be NULL.
+ * rows == 0: success without a launch.
+ * hipErrorInvalidValue (before any launch): rows < 0; NULL g, g->u or direction; NULL position, gate or destination with
+ * rows > 0; G outside 1..64; gx or gy outside 1..1024; cell not finite and > 0; x0 or y0 not finite; near not finite or < 0.
+ *
+ * piml_scenario_step_mlapm_nav: the frame of piml_scenario_step_mlapm_noise for a scene without groups, with e of
+ *   F = ((v0 e - v) / tau - sum) [+ W] [+ eta']
+ * the frame's own line e = (target - p) / max(|target - p|, 1e-12) for the steering target fl(p + n.e), n = piml_nav_direction's
+ * result for (p, gate = exit_idx[flag], destination) of the slot, in its branches 1 and 2, and for the destination itself in
+ * branch 0: the frame is bitwise piml_scenario_step_mlapm_noise on a state whose destination was overwritten by p + n.e, and e is
+ * n.e to within ulp(p).  Everything else, arrival against the slot's destination included, is the same code.  noise == NULL:
+ * no fluctuation term (amp == 0).
+ * hipErrorInvalidValue (before any launch): the checks of piml_scenario_step_mlapm_noise with g == NULL and init == 0 (a
+ * NULL noise excepted) and of piml_nav_direction's grid; a scene rule other than GC's (r != NULL with another spawn law:
+ * only GC's law has gates and exit_idx); s->route_max_iters != 0 (with a detour point the waypoint's gate is not the
+ * destination's and the agent would never arrive); nav->G != s->E.  No atomics, capturable.
+ */
+typedef struct piml_nav_grid {
+    const float* u;                                         /* (G, gy, gx) device, cell units */
+    int G, gx, gy;
+    float x0, y0, cell, near;
+} piml_nav_grid;
+int piml_nav_relax(const unsigned char* blocked, const unsigned char* goal, float* u_a, float* u_b, int G, int gx, int gy,
+                   int launches, int* changed, void* stream);
+int piml_nav_direction(const float* position, const int* gate, const float* destination, long long rows,
+                       const piml_nav_grid* g, float* direction, int* branch /* may be NULL */,
+                       int* neighbour /* may be NULL */, void* stream);
+int piml_scenario_step_mlapm_nav(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                                 const piml_mlapm_law* law, const void* law_table_device,
+                                 const piml_wall_grid* wall_grid /* NULL: no wall term */, const piml_wall_law* wall,
+                                 const piml_wall_law* wall_table_device, const piml_nav_grid* nav,
+                                 const piml_noise_args* noise /* NULL: no fluctuation */, int frame_offset, void* stream);
+
+/*
  * utils.route (src/utils/utils.py:141-165) for n (o, d) pairs, one wave each, the device function the spawn path uses:
  * the segment o -> r is tested against the polyline's R-1 segments, the hit with the smallest alpha moves r to
  * crossing + clearance * normal, until nothing is hit or max_iters moves were made.  float32 in the reference's order.

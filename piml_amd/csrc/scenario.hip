@@ -99,6 +99,7 @@
 #include "common.hpp"
 #include "groups.hpp"
 #include "mlapm.hpp"
+#include "nav.hpp"
 #include "noise.hpp"
 #include "philox.hpp"
 #include "walls.hpp"
@@ -755,11 +756,20 @@ struct MlapmScenarioArgs {
 // NULL (amp is read again at the add: a flag kept across the tile loop cost the one scalar register that gave a kernel a
 // stack frame); amp == 0 skips the draw, the state and the add.  kNoise == false does not read NA: the kernels above compile
 // to the instructions they had.
-template <bool kTable, bool kWalls, bool kGroups, bool kNoise = false>
+//
+// kNav (piml_scenario_step_mlapm_nav): the agent steers by the floor field of nav.hpp.  n = nav_direction(NV, the gate of the
+// slot's current waypoint, p, destination); in its branches 1 and 2 the steering TARGET is the point one metre down the
+// field, fl(p + n.e) per component, and e is the frame's own line for that target in place of the destination -- so the frame
+// is bitwise the frame without the field run on a state whose destination was overwritten by p + n.e, and e is n.e to within
+// ulp(p).  In branch 0 the target is the destination: the straight line, bit for bit.  Everything else -- the force, the terms
+// above, integration, arrival against S.destination -- is the same code.  kNav == false does not read NV: the kernels above
+// compile to the instructions they had.
+template <bool kTable, bool kWalls, bool kGroups, bool kNoise = false, bool kNav = false>
 __device__ __forceinline__ void scenario_mlapm_body(const MlapmScenarioArgs& K0, const unsigned long long* __restrict__ seeds,
                                                     const MlapmParams* __restrict__ table, const WallArgs& WG,
                                                     const piml_wall_law& wall, const piml_wall_law* __restrict__ wall_table,
-                                                    const GroupArgs& GA, const piml_noise_args& NA = piml_noise_args{}) {
+                                                    const GroupArgs& GA, const piml_noise_args& NA = piml_noise_args{},
+                                                    const piml_nav_grid& NV = piml_nav_grid{}) {
     __shared__ float4 tile[kMlTile];                         // agent blocks: the sources (px, py, vx, vy); spawn blocks: entries
     __shared__ unsigned short ucy_ring[kMlScWaves][256];
     static_assert(kScenarioLdsPoints * sizeof(float2) <= sizeof(tile), "the entry points fit the source tile");
@@ -782,6 +792,15 @@ __device__ __forceinline__ void scenario_mlapm_body(const MlapmScenarioArgs& K0,
         const bool live = i < n_t && S.mask[i] != 0.f;       // wave-uniform
         float2 pi = make_float2(0.f, 0.f), vi = pi, di = pi;
         if (live) { pi = ((const float2*)S.position)[i]; vi = ((const float2*)S.velocity)[i]; di = ((const float2*)S.destination)[i]; }
+        float2 ti = di;                                      // what the agent steers to
+        if constexpr (kNav) {
+            if (live) {                                      // wave-uniform; the gate is range-checked by the lookup
+                const int gate = S.exit_idx[(size_t)S.flag[i] * cap + i];
+                const NavDir nd = nav_direction(NV, gate, pi, di);
+                const float tx = nd.branch ? __fadd_rn(pi.x, nd.e.x) : di.x, ty = nd.branch ? __fadd_rn(pi.y, nd.e.y) : di.y;
+                ti = make_float2(tx, ty);
+            }
+        }
         // the fluctuation of this step, drawn before the pair sum while few values are live (it depends on (seed, t, i) and
         // the slot's own state only); added to the force last, below
         float2 eta = make_float2(0.f, 0.f);
@@ -794,7 +813,7 @@ __device__ __forceinline__ void scenario_mlapm_body(const MlapmScenarioArgs& K0,
                 *st = eta;
             }
         }
-        float ex = di.x - pi.x, ey = di.y - pi.y;
+        float ex = ti.x - pi.x, ey = ti.y - pi.y;
         const float en = fmaxf(norm2(ex, ey), 1e-12f);      // mlapm.py:21
         ex /= en; ey /= en;
         const float2* pt = (const float2*)S.position_out + (size_t)t * cap;
@@ -918,6 +937,17 @@ __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_noise_kernel(c
                                                                               const piml_wall_law* __restrict__ wall_table,
                                                                               const GroupArgs GA, const piml_noise_args NA) {
     scenario_mlapm_body<kTable, kWalls, kGroups, true>(K0, seeds, table, WG, wall, wall_table, GA, NA);
+}
+
+// the frame routed by the floor field: a scene of gates without groups, the fluctuation term compiled in (amp == 0 skips it)
+template <bool kTable, bool kWalls>
+__global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_nav_kernel(const MlapmScenarioArgs K0,
+                                                                            const unsigned long long* __restrict__ seeds,
+                                                                            const MlapmParams* __restrict__ table,
+                                                                            const WallArgs WG, const piml_wall_law wall,
+                                                                            const piml_wall_law* __restrict__ wall_table,
+                                                                            const piml_noise_args NA, const piml_nav_grid NV) {
+    scenario_mlapm_body<kTable, kWalls, false, true, true>(K0, seeds, table, WG, wall, wall_table, GroupArgs{}, NA, NV);
 }
 
 }  // namespace piml
@@ -1222,6 +1252,51 @@ PIML_API int piml_scenario_step_mlapm_noise(const piml_scenario* s, const piml_s
     case 5: launch_mlapm_noise<true, false, true>(grid, st, K, sd, tb, WG, w, wall_table_device, GA, *noise); break;
     case 6: launch_mlapm_noise<true, true, false>(grid, st, K, sd, tb, WG, w, wall_table_device, GA, *noise); break;
     default: launch_mlapm_noise<true, true, true>(grid, st, K, sd, tb, WG, w, wall_table_device, GA, *noise); break;
+    }
+    return hipGetLastError();
+}
+
+template <bool kTable, bool kWalls>
+static void launch_mlapm_nav(dim3 grid, hipStream_t st, const piml::MlapmScenarioArgs& K, const unsigned long long* sd,
+                             const piml::MlapmParams* tb, const piml::WallArgs& WG, const piml_wall_law& w,
+                             const piml_wall_law* wt, const piml_noise_args& NA, const piml_nav_grid& NV) {
+    hipLaunchKernelGGL((piml::scenario_mlapm_nav_kernel<kTable, kWalls>), grid, dim3(piml::kMlScWaves * 64), 0, st, K, sd, tb,
+                       WG, w, wt, NA, NV);
+}
+
+PIML_API int piml_scenario_step_mlapm_nav(const piml_scenario* s, const piml_scenario_rules* r, int members,
+                                          const uint64_t* seeds, const piml_mlapm_law* law, const void* law_table_device,
+                                          const piml_wall_grid* wall_grid, const piml_wall_law* wall,
+                                          const piml_wall_law* wall_table_device, const piml_nav_grid* nav,
+                                          const piml_noise_args* noise, int frame_offset, void* stream) {
+    if (noise && (!noise->state || (!noise->law_table && !piml::noise_law_ok(noise->law.rho, noise->law.amp))))
+        return hipErrorInvalidValue;
+    if (!s || !seeds || members < 1 || members > 65535 || frame_offset < 0) return hipErrorInvalidValue;
+    if (r && r->spawn_law != PIML_SPAWN_GC) return hipErrorInvalidValue;      // only GC's law has gates and exit_idx
+    if (!frame_args_ok(*s, r, nullptr, 1)) return hipErrorInvalidValue;
+    if (s->route_max_iters != 0) return hipErrorInvalidValue;                 // a detour point's gate is not the destination's
+    if (!piml::nav_grid_ok(nav) || nav->G != s->E) return hipErrorInvalidValue;
+    if (!law == !law_table_device) return hipErrorInvalidValue;               // exactly one
+    if (law && !mlapm_law_ok(*law)) return hipErrorInvalidValue;
+    if (wall_grid ? (!wall == !wall_table_device) : (wall || wall_table_device)) return hipErrorInvalidValue;
+    if (wall_grid && (!piml::wall_grid_ok(wall_grid) || (wall && !piml::wall_law_ok(wall->A, wall->B))))
+        return hipErrorInvalidValue;
+    piml::MlapmScenarioArgs K;
+    const dim3 grid = mlapm_frame_launch(K, *s, r, members, frame_offset);
+    K.P = piml::MlapmParams{};                               // (not read with a table)
+    if (law) K.P = piml::make_params(law->variant, law->tau, law->A, law->B, law->C, law->D, law->theta_deg, law->radius, 1);
+    const piml::WallArgs WG = wall_grid ? piml::wall_args(*wall_grid) : piml::WallArgs{};
+    const piml_wall_law w = wall ? *wall : piml_wall_law{};
+    const piml_noise_args NA = noise ? *noise : piml_noise_args{};            // amp == 0: the term is skipped
+    const unsigned long long* sd = (const unsigned long long*)seeds;
+    const piml::MlapmParams* tb = (const piml::MlapmParams*)law_table_device;
+    hipStream_t st = piml::as_stream(stream);
+    if (law) {
+        if (wall_grid) launch_mlapm_nav<false, true>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav);
+        else launch_mlapm_nav<false, false>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav);
+    } else {
+        if (wall_grid) launch_mlapm_nav<true, true>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav);
+        else launch_mlapm_nav<true, false>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav);
     }
     return hipGetLastError();
 }

@@ -1,7 +1,7 @@
 """Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_step_rules,
 piml_scenario_step_members, piml_scenario_step_mlapm, piml_scenario_step_mlapm_laws, piml_scenario_step_mlapm_walls,
 piml_wall_force, piml_scenario_step_mlapm_groups, piml_group_force, piml_scenario_step_mlapm_noise, piml_noise_force,
-piml_scenario_route).
+piml_nav_relax, piml_nav_direction, piml_scenario_step_mlapm_nav, piml_scenario_route).
 
 `scenario_state` allocates the persistent (static-address) buffers of one simulation or an ensemble and the
 `piml_scenario` descriptor that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive,
@@ -535,7 +535,222 @@ def _group_arg_is_table(st, groups):
     return group_table
 
 
-def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, groups=None, init=False, noise=None):
+NAV_MAX_CELLS = 1024                   # per axis (nav.hpp)
+NAV_MAX_GATES = 64
+NAV_STEPS = 8                          # Jacobi steps of one piml_nav_relax launch
+NAV_BATCH = 16                         # launches queued between two looks at `changed`
+
+
+def nav_grid_host(scenario, cell=0.25, bounds=None):
+    """The floor field's grid over a scene of gates, on the host in numpy (no GPU call): a namespace of gx, gy and the
+    float32 scalars x0, y0, cell, of centres (gy, gx, 2) float32 -- x0 + (i + 0.5) cell, the points `blocked` is decided at --
+    and goal (G, gy, gx) uint8, the cells that hold gate g's sample points (a point's cell is floor((q - origin) / cell) in
+    float32, the wall grid's formula).  bounds = (xmin, ymin, xmax, ymax); default: the box of the obstacles and gate points
+    padded by spawn_offset + cell.  A box of more than 1024 cells per axis coarsens `cell`, with a warning.  ValueError for
+    more than 64 gates, a cell not finite and > 0, an empty box, or a gate without a point inside the grid."""
+    import numpy as np
+    f32 = np.float32
+    cell = float(cell)
+    if not math.isfinite(cell) or not cell > 0:
+        raise ValueError(f'nav_field: a finite cell > 0 expected, got {cell}')
+    ent = scenario.entries.detach().cpu().numpy().astype(f32)
+    if ent.ndim != 3 or ent.shape[0] < 1 or ent.shape[0] > NAV_MAX_GATES:
+        raise ValueError(f'nav_field: 1 .. {NAV_MAX_GATES} gates (E, P, 2) expected, got entries {tuple(ent.shape)}')
+    if bounds is None:
+        obs = scenario.obstacles.detach().cpu().numpy().astype(f32).reshape(-1, 2)
+        pts = np.concatenate([obs[np.isfinite(obs).all(1)], ent.reshape(-1, 2)])
+        pad = float(scenario.spawn_offset) + cell
+        lo, hi = pts.min(0).astype(np.float64) - pad, pts.max(0).astype(np.float64) + pad
+    else:
+        lo, hi = np.array(bounds[:2], np.float64), np.array(bounds[2:], np.float64)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
+        raise ValueError(f'nav_field: a finite, non-empty box expected, got {lo.tolist()} .. {hi.tolist()}')
+    span = float((hi - lo).max())
+    if span / cell > NAV_MAX_CELLS:
+        import warnings
+        coarse = span / (NAV_MAX_CELLS - 1)
+        warnings.warn(f'nav_field: the box spans {span:g} m, more than {NAV_MAX_CELLS} cells of {cell:g} m per axis: cells '
+                      f'coarsened to {coarse:g} m')
+        cell = coarse
+    g = types.SimpleNamespace(cell=float(f32(cell)), x0=float(f32(lo[0])), y0=float(f32(lo[1])))
+    g.gx = min(NAV_MAX_CELLS, max(1, int(math.ceil((hi[0] - lo[0]) / g.cell))))
+    g.gy = min(NAV_MAX_CELLS, max(1, int(math.ceil((hi[1] - lo[1]) / g.cell))))
+    c, x0, y0 = f32(g.cell), f32(g.x0), f32(g.y0)
+    cx = x0 + (np.arange(g.gx, dtype=f32) + f32(0.5)) * c
+    cy = y0 + (np.arange(g.gy, dtype=f32) + f32(0.5)) * c
+    g.centres = np.ascontiguousarray(np.stack(np.broadcast_arrays(cx[None, :], cy[:, None]), -1).astype(f32))
+    g.goal = np.zeros((ent.shape[0], g.gy, g.gx), np.uint8)
+    for e in range(ent.shape[0]):
+        q = ent[e][np.isfinite(ent[e]).all(1)]
+        ix, iy = np.floor((q[:, 0] - x0) / c), np.floor((q[:, 1] - y0) / c)
+        keep = (ix >= 0) & (ix < g.gx) & (iy >= 0) & (iy < g.gy)
+        if not keep.any():
+            raise ValueError(f'nav_field: gate {e} has no point inside the grid')
+        g.goal[e, iy[keep].astype(np.int64), ix[keep].astype(np.int64)] = 1
+    return g
+
+
+class NavField:
+    """The static floor field of a scene of gates (nav_field): u (G, gy, gx) float32 -- gate g's geodesic distance over the
+    free cells in CELL units, +inf on blocked and unreachable cells --, blocked (gy, gx) and goal (G, gy, gx) uint8, all on
+    the device; desc the piml_nav_grid over u; G, gx, gy, x0, y0, cell, near, clearance; iterations, the Jacobi steps
+    queued until a batch changed nothing."""
+
+    def __init__(self, u, blocked, goal, x0, y0, cell, near, clearance=None, iterations=0):
+        if not math.isfinite(float(near)) or float(near) < 0:
+            raise ValueError(f'nav field: a finite near >= 0 (cells) expected, got {near}')
+        self.u, self.blocked, self.goal = u, blocked, goal
+        self.G, self.gy, self.gx = (int(n) for n in u.shape)
+        self.x0, self.y0, self.cell, self.near = float(x0), float(y0), float(cell), float(near)
+        self.clearance, self.iterations = clearance, int(iterations)
+        d = _lib.NavGrid()
+        d.u, d.G, d.gx, d.gy = u.data_ptr(), self.G, self.gx, self.gy
+        d.x0, d.y0, d.cell, d.near = self.x0, self.y0, self.cell, self.near
+        self.desc = d
+
+    def to_numpy(self):
+        """a namespace of the numpy copies u, blocked, goal and the scalars"""
+        return types.SimpleNamespace(u=self.u.cpu().numpy(), blocked=self.blocked.cpu().numpy(), goal=self.goal.cpu().numpy(),
+                                     G=self.G, gx=self.gx, gy=self.gy, x0=self.x0, y0=self.y0, cell=self.cell, near=self.near)
+
+    def reachable(self, g):
+        """(gy, gx) bool: the cells gate g can be reached from (u[g] finite)"""
+        return torch.isfinite(self.u[int(g)])
+
+
+def nav_relax(blocked, goal, u=None, launches=None):
+    """The eikonal solve of piml_nav_relax on device tensors: blocked (gy, gx) uint8, goal (G, gy, gx) uint8 -> (u (G, gy, gx)
+    float32 in cell units, the number of Jacobi steps queued).  u: a start to step from (default 0 on goal cells, +inf
+    elsewhere); it is not written.  launches = None: batches of 16 launches of 8 steps until a batch changed nothing (a fixed
+    point: u only decreases); RuntimeError if gx gy steps were not enough.  launches = n: exactly n launches, wherever that
+    leaves the field."""
+    if blocked.dtype != torch.uint8 or goal.dtype != torch.uint8 or goal.dim() != 3 or tuple(blocked.shape) != tuple(goal.shape[1:]):
+        raise ValueError(f'nav_relax: blocked (gy, gx) and goal (G, gy, gx) uint8 expected, got {blocked.dtype} '
+                         f'{tuple(blocked.shape)}, {goal.dtype} {tuple(goal.shape)}')
+    if goal.device.type != 'cuda' or blocked.device != goal.device:
+        raise _lib.PimlHipError(f'nav_relax: GPU tensors on one device expected (piml_amd has no CPU path), got '
+                                f'{blocked.device}, {goal.device}')
+    G, gy, gx = (int(n) for n in goal.shape)
+    blocked, goal = blocked.contiguous(), goal.contiguous()
+    if u is None:
+        a = torch.full(goal.shape, float('inf'), device=goal.device, dtype=torch.float32)
+        a[goal != 0] = 0.0
+    else:
+        a = _gpu_f32('u', u).clone()
+        if tuple(a.shape) != tuple(goal.shape) or a.device != goal.device:
+            raise ValueError(f'nav_relax: u {tuple(goal.shape)} on {goal.device} expected, got {tuple(a.shape)} on {a.device}')
+    b = torch.empty_like(a)
+    changed = torch.zeros(G, device=goal.device, dtype=torch.int32)
+
+    def queue(n):
+        with torch.cuda.device(goal.device):
+            _lib.check(_lib.lib().piml_nav_relax(_ptr(blocked), _ptr(goal), _ptr(a), _ptr(b), G, gx, gy, int(n), _ptr(changed),
+                                                 _stream()), 'piml_nav_relax')
+    if launches is not None:
+        queue(launches)
+        return (b if int(launches) & 1 else a), int(launches) * NAV_STEPS
+    steps = 0
+    while True:
+        changed.zero_()
+        queue(NAV_BATCH)
+        steps += NAV_BATCH * NAV_STEPS
+        if not bool(changed.any().item()):
+            return a, steps
+        if steps - NAV_BATCH * NAV_STEPS >= gx * gy:         # the steps before this batch were enough, and it still changed
+            raise RuntimeError(f'nav_relax: no fixed point after {steps} steps on a {gx} x {gy} grid')
+
+
+def nav_field(scenario, cell=0.25, clearance=0.3, near=2.0, bounds=None, device='cuda'):
+    """The floor field of a scene of gates, built once per scene: for every gate g of scenario.entries the geodesic distance
+    u[g] to the gate's cells over the free cells of nav_grid_host's grid (piml_nav_relax).  A cell is blocked when an
+    obstacle point lies within `clearance` of its centre (wall_force's exact float32 dist2 against a wall_grid of cutoff
+    `clearance`); the cells that hold a gate's points are forced free.  near (cells): within it of the gate an agent walks
+    straight to its own destination point.  Returns a NavField."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.PimlHipError(f'nav_field: a GPU device expected (piml_amd has no CPU path), got {dev}')
+    clearance = float(clearance)
+    if not math.isfinite(clearance) or not clearance > 0:
+        raise ValueError(f'nav_field: a finite clearance > 0 expected, got {clearance}')
+    if not math.isfinite(float(near)) or float(near) < 0:
+        raise ValueError(f'nav_field: a finite near >= 0 (cells) expected, got {near}')
+    h = nav_grid_host(scenario, cell, bounds)
+    centres = torch.from_numpy(h.centres).to(dev)
+    _, _, index = wall_force(centres, wall_grid(scenario.obstacles, cutoff=clearance, device=dev), 0.0, 0.0,
+                             return_selection=True)
+    goal = torch.from_numpy(h.goal).to(dev)
+    blocked = ((index >= 0) & ~(goal != 0).any(0)).to(torch.uint8).contiguous()
+    u, steps = nav_relax(blocked, goal)
+    return NavField(u, blocked, goal, h.x0, h.y0, h.cell, near, clearance, steps)
+
+
+def nav_direction(position, gate, destination, field, return_branch=False):
+    """The desired direction of piml_nav_direction for every row: position (..., 2), gate (...) integers, destination
+    (..., 2) -> e (..., 2) unit vectors.  return_branch: also branch (...) int32 (0 straight, 1 bilinear, 2 descent) and
+    neighbour (...) int32 (branch 2's neighbour in the order E, W, N, S, NE, NW, SE, SW; -1 otherwise).  In branches 1 and 2
+    position + e (one float32 add) is bitwise the point scenario_step_mlapm(..., nav=field) steers an agent there to."""
+    if not isinstance(field, NavField):
+        raise TypeError(f'field: a nav_field(...) expected, got {type(field).__name__}')
+    p = _gpu_f32('position', position)
+    d = _gpu_f32('destination', destination)
+    if p.dim() < 1 or p.shape[-1] != 2 or p.shape != d.shape:
+        raise ValueError(f'position and destination: the same (..., 2) expected, got {tuple(p.shape)}, {tuple(d.shape)}')
+    if not isinstance(gate, torch.Tensor) or gate.is_floating_point() or tuple(gate.shape) != tuple(p.shape[:-1]):
+        raise ValueError(f'gate: an integer tensor {tuple(p.shape[:-1])} expected')
+    if field.u.device != p.device or gate.device != p.device or d.device != p.device:
+        raise ValueError(f'position on {p.device}, gate on {gate.device}, destination on {d.device}, the field on {field.u.device}')
+    g = gate.to(torch.int32).contiguous()
+    lead, rows = p.shape[:-1], p.numel() // 2
+    e = torch.zeros_like(p)
+    branch = torch.zeros(lead, device=p.device, dtype=torch.int32) if return_branch else None
+    nb = torch.full(lead, -1, device=p.device, dtype=torch.int32) if return_branch else None
+    if rows:                                     # (an empty problem keeps the fills above: the entry launches nothing)
+        with torch.cuda.device(p.device):
+            _lib.check(_lib.lib().piml_nav_direction(_ptr(p), _ptr(g), _ptr(d), rows, ctypes.byref(field.desc), _ptr(e),
+                                                     _ptr(branch), _ptr(nb), _stream()), 'piml_nav_direction')
+    return (e, branch, nb) if return_branch else e
+
+
+def _noise_arg_is_table(st, noise):
+    """scenario_step_mlapm's check of `noise`; True for a table"""
+    noise_table = isinstance(noise, torch.Tensor)
+    if noise_table:
+        if noise.dtype != torch.float32 or tuple(noise.shape) != (st.seeds.numel(), 2) or not noise.is_contiguous():
+            raise ValueError(f'noise table: a contiguous float32 ({st.seeds.numel()}, 2) tensor of noise_law_table '
+                             f'expected, got {noise.dtype} {tuple(noise.shape)}')
+        if noise.device != st.p.device:
+            raise ValueError(f'noise table on {noise.device}, the state on {st.p.device}')
+    elif not isinstance(noise, _lib.NoiseLaw):
+        raise TypeError(f'noise: a noise_law or a noise_law_table expected, got {type(noise).__name__}')
+    return noise_table
+
+
+def check_nav_scene(scenario):
+    """ValueError unless `scenario` can be routed by a floor field (piml_scenario_step_mlapm_nav's own refusals, said before
+    any state exists): GC's spawn law -- the only one with gates and exit_idx -- without groups, and route_max_iters == 0."""
+    if scenario.spawn_law == 'clip_groups':
+        raise ValueError('nav: a grouped scene cannot be routed by a floor field (its units follow recorded waypoints)')
+    if scenario.spawn_law != 'gc':
+        raise ValueError(f"nav: the floor field routes scenes of gates (spawn law 'gc') only, not {scenario.spawn_law!r}: "
+                         f'only that law has gates and exit_idx')
+    if int(scenario.route_max_iters) != 0:
+        raise ValueError(f'nav: route_max_iters must be 0, got {scenario.route_max_iters}: with a detour point the '
+                         f"agent's waypoint gate is not its destination gate and it would never arrive "
+                         f'(dataclasses.replace(scenario, route_max_iters=0))')
+
+
+def _check_nav(st, nav):
+    """scenario_step_mlapm's check of `nav`"""
+    if not isinstance(nav, NavField):
+        raise TypeError(f'nav: a nav_field(...) expected, got {type(nav).__name__}')
+    check_nav_scene(st.scenario)
+    if nav.G != st.scenario.entries.shape[0]:
+        raise ValueError(f'nav: a field of {nav.G} gates for a scene of {st.scenario.entries.shape[0]}')
+    if nav.u.device != st.p.device:
+        raise ValueError(f'nav field on {nav.u.device}, the state on {st.p.device}')
+
+
+def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, groups=None, init=False, noise=None, nav=None):
     """One launch: frame t -> t + 1 of st (single or ensemble state) under the MLAPM law `law` (mlapm_law(...)), t =
     st.t + frame_offset: the force of MLAPM.step from the agents present in frame t's records, v' = v + F dt, p' = p + v' dt
     (src/main_mlapm.py:18-36), a' = F, then the scene's arrivals, exits and spawns as scenario_step.  advance: add 1 to
@@ -556,7 +771,11 @@ def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, group
     noise = a noise_law(An, noise_tau, dt) for every member or a noise_law_table(...) with one row per member: any of the
     forms above with the fluctuation term (piml_scenario_step_mlapm_noise), F = (the above) + eta', added last; eta lives in
     scenario_noise_state(st), allocated at the first such frame (before any capture: a run's first frame is eager) and
-    zeroed by scenario_state_reset.  noise = None takes the entries above, untouched."""
+    zeroed by scenario_state_reset.  noise = None takes the entries above, untouched.
+    nav = a nav_field(...) of the scene: the frame routed by the floor field (piml_scenario_step_mlapm_nav): every slot
+    steers to p + nav_direction(p, the gate of its waypoint, destination) in place of its destination (to the destination
+    itself in the lookup's branch 0), with or without walls and noise; everything else is the same frame.  ValueError (check_nav_scene) for a grouped scene, a scene rule
+    other than GC's, route_max_iters != 0, or a field of another number of gates."""
     grouped = getattr(st, 'groups', None) is not None
     if init:
         if not grouped:
@@ -595,16 +814,32 @@ def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, group
             raise TypeError(f'walls: (wall_grid, wall_law or wall_law_table) expected, got {type(wall).__name__}')
         if grid.cell_start.device != st.p.device:
             raise ValueError(f'wall grid on {grid.cell_start.device}, the state on {st.p.device}')
+    if nav is not None:
+        _check_nav(st, nav)
+        grid, wall = walls if walls is not None else (None, None)
+        wall_table = isinstance(wall, torch.Tensor)
+        na = None
+        if noise is not None:
+            noise_table = _noise_arg_is_table(st, noise)
+            na = _lib.NoiseArgs()
+            na.state = scenario_noise_state(st).data_ptr()
+            if noise_table:
+                na.law_table = noise.data_ptr()
+            else:
+                na.law = noise
+        with torch.cuda.device(st.p.device):
+            _lib.check(_lib.lib().piml_scenario_step_mlapm_nav(
+                ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(), _ptr(st.seeds),
+                None if table else ctypes.byref(law), _ptr(law) if table else None,
+                None if grid is None else ctypes.byref(grid.desc),
+                None if wall is None or wall_table else ctypes.byref(wall), _ptr(wall) if wall_table else None,
+                ctypes.byref(nav.desc), None if na is None else ctypes.byref(na), int(frame_offset), _stream()),
+                'piml_scenario_step_mlapm_nav')
+            if advance:
+                st.t.add_(1)
+        return
     if noise is not None:
-        noise_table = isinstance(noise, torch.Tensor)
-        if noise_table:
-            if noise.dtype != torch.float32 or tuple(noise.shape) != (st.seeds.numel(), 2) or not noise.is_contiguous():
-                raise ValueError(f'noise table: a contiguous float32 ({st.seeds.numel()}, 2) tensor of noise_law_table '
-                                 f'expected, got {noise.dtype} {tuple(noise.shape)}')
-            if noise.device != st.p.device:
-                raise ValueError(f'noise table on {noise.device}, the state on {st.p.device}')
-        elif not isinstance(noise, _lib.NoiseLaw):
-            raise TypeError(f'noise: a noise_law or a noise_law_table expected, got {type(noise).__name__}')
+        noise_table = _noise_arg_is_table(st, noise)
         group_table = _group_arg_is_table(st, groups) if grouped else False
         grid, wall = walls if walls is not None else (None, None)
         wall_table = isinstance(wall, torch.Tensor)

@@ -16,6 +16,9 @@ leading member axis, each of them a `ScenarioResult` through `member(m)`.  `Scen
 `clip_scenario(raw_data)` makes a scene of any recorded clip: its geometry, the agents of its first frame, and arrivals
 resampled from its own tracks (PIML_SPAWN_CLIP: the table of tracks travels in `entries`).
 
+`floorplan_scenario(walls, gates)` / `load_floorplan(path)` write a user's floor plan down as a scene of gates under GC's law,
+with no detour route: the way round its walls is the floor field's (ops_scenario.nav_field).
+
 `save_clip` writes a simulation as the reference's `RawData.save_data` does (src/data/data.py:305-341, version v2.2), so
 that `RawData.load_trajectory_data` -- here and in the reference -- reads it back as a training clip (`--iter_flag`).
 """
@@ -134,6 +137,76 @@ def gc_scenario(time_unit=0.08, uniform_desired_speed=False):
     ])
     return Scenario(entries=entries, route_polyline=pillar, obstacles=torch.concat((wall, pillar), dim=0).contiguous(),
                     time_unit=time_unit, uniform_desired_speed=uniform_desired_speed, name='gc')
+
+
+FLOORPLAN_FIELDS = ('rate_per_s', 'n_initial', 'gate_points', 'wall_spacing', 'time_unit', 'speed_mean', 'speed_var',
+                    'speed_min', 'uniform_desired_speed', 'spawn_offset', 'arrival_radius', 'spawn_cap', 'name')
+
+
+def _sample_segment(a, b, n):
+    return torch.stack((torch.linspace(float(a[0]), float(b[0]), n), torch.linspace(float(a[1]), float(b[1]), n)), dim=1)
+
+
+def floorplan_scenario(walls, gates, rate_per_s=5.0, n_initial=20, gate_points=100, wall_spacing=0.05, **scenario_fields):
+    """A user's floor plan as a scene of gates under GC's law: walls, a list of polylines (each a list of >= 2 (x, y) points,
+    resampled per edge at most wall_spacing metres apart into the obstacle points), and gates, a list of 2 .. 64 segments ((ax, ay),
+    (bx, by)), each sampled into gate_points points -- the origins and destinations the arrivals are drawn from, GC's
+    `entries`.  route_max_iters is 0: the route is the destination itself and the way around the walls is the floor field's
+    (ops_scenario.nav_field; MLAPM.simulate_scenario(..., nav=True)); route_polyline is a two-point dummy that is never
+    read.  scenario_fields: further Scenario fields (time_unit, arrival_radius, spawn_offset, ...).  ValueError on a plan
+    that is not of that shape or a field the scene rule owns."""
+    def points(x, what, least):
+        try:
+            t = torch.tensor(x, dtype=torch.float32)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f'floorplan: {what}: a list of (x, y) points expected') from None
+        if t.dim() != 2 or t.shape[1] != 2 or t.shape[0] < least or not bool(torch.isfinite(t).all()):
+            raise ValueError(f'floorplan: {what}: at least {least} finite (x, y) points expected, got shape {tuple(t.shape)}')
+        return t
+    owned = {'entries', 'route_polyline', 'obstacles', 'route_max_iters', 'spawn_law', 'arrival_rule', 'num_waypoints'}
+    known = {f.name for f in dataclasses.fields(Scenario)}
+    bad = sorted(k for k in scenario_fields if k in owned or k not in known)
+    if bad:
+        raise ValueError(f'floorplan: {bad} are not fields a floor plan may set')
+    if not isinstance(gates, (list, tuple)) or not 2 <= len(gates) <= 64:
+        raise ValueError(f'floorplan: 2 .. 64 gates expected, got {len(gates) if isinstance(gates, (list, tuple)) else gates!r}')
+    if not isinstance(walls, (list, tuple)):
+        raise ValueError('floorplan: walls: a list of polylines expected')
+    gate_points, wall_spacing = int(gate_points), float(wall_spacing)
+    if gate_points < 1 or not math.isfinite(wall_spacing) or not wall_spacing > 0:
+        raise ValueError(f'floorplan: gate_points >= 1 and wall_spacing > 0 expected, got {gate_points}, {wall_spacing}')
+    entries = []
+    for k, gate in enumerate(gates):
+        g = points(gate, f'gate {k}', 2)
+        if g.shape[0] != 2:
+            raise ValueError(f'floorplan: gate {k}: a segment of two points expected, got {g.shape[0]}')
+        entries.append(_sample_segment(g[0], g[1], gate_points))
+    obstacles = []
+    for k, wall in enumerate(walls):
+        w = points(wall, f'wall {k}', 2)
+        for a, b in zip(w[:-1], w[1:]):
+            obstacles.append(_sample_segment(a, b, max(2, math.ceil(float(torch.linalg.norm(b - a)) / wall_spacing) + 1)))
+    obstacles = torch.concat(obstacles, dim=0).contiguous() if obstacles else torch.zeros(0, 2)
+    fields = dict(name='floorplan', **scenario_fields) if 'name' not in scenario_fields else dict(scenario_fields)
+    return Scenario(entries=torch.stack(entries).contiguous(), route_polyline=torch.zeros(2, 2), obstacles=obstacles,
+                    rate_per_s=float(rate_per_s), n_initial=int(n_initial), route_max_iters=0, **fields)
+
+
+def load_floorplan(path):
+    """floorplan_scenario of a JSON file: {"walls": [[[x, y], ...], ...], "gates": [[[ax, ay], [bx, by]], ...]} and, optionally,
+    any of FLOORPLAN_FIELDS.  ValueError on anything else."""
+    import json
+    with open(path) as fh:
+        got = json.load(fh)
+    if not isinstance(got, dict) or 'walls' not in got or 'gates' not in got:
+        raise ValueError(f"{path}: a JSON object with 'walls' and 'gates' expected")
+    unknown = sorted(set(got) - {'walls', 'gates', *FLOORPLAN_FIELDS})
+    if unknown:
+        raise ValueError(f"{path}: unknown keys {unknown} (expected walls, gates and {list(FLOORPLAN_FIELDS)})")
+    try:
+        return floorplan_scenario(got['walls'], got['gates'], **{k: v for k, v in got.items() if k not in ('walls', 'gates')})
+    except (TypeError, ValueError) as ex:
+        raise ValueError(f'{path}: {ex}') from None
 
 
 def _no_geometry():

@@ -23,6 +23,9 @@ reads.
     python -m piml_amd.simulate --law mlapm --scenario gc --seeds 0:32 --group-stats groups.json        (group statistics)
     python -m piml_amd.simulate --law mlapm --params-sweep a.json b.json --seeds 0:8 --stats sweep.json
                                 (one law per file, every law on every seed in ONE ensemble run; statistics per candidate)
+    python -m piml_amd.simulate --law mlapm --scene-plan plan.json --nav --seeds 0:32 --obstacle-stats walls.json
+                                (a floor plan -- walls as polylines, gates as segments -- routed by a static floor field)
+    python -m piml_amd.simulate --law mlapm --scenario gc --nav [--nav-cell 0.25] [--nav-clearance 0.3] --out clip.npy
 
 Model flags (--model, --hidden sizes, --topk_*, --num_history_velocity, ...) are those of `piml_amd.main`, with its
 defaults.  Without --checkpoint the network keeps its initial weights (a smoke run)."""
@@ -65,6 +68,15 @@ def get_args(argv=None):
                    help="--scene-from with --law mlapm: keep the clip's groups as arrival units whose members appear "
                         "together (scenarios.clip_scenario(groups=)): 'auto' (the clip's own group statistics) or a JSON "
                         'file holding a list of lists of track indices')
+    p.add_argument('--scene-plan', dest='scene_plan', type=str, default=None,
+                   help='a floor plan as the scene (scenarios.load_floorplan: JSON with "walls", polylines, and "gates", '
+                        'segments); --law mlapm only; not with --scenario or --scene-from')
+    p.add_argument('--nav', action='store_true',
+                   help='--law mlapm with --scenario gc (its route_max_iters becomes 0) or --scene-plan: the agents descend a '
+                        'static floor field to their gate instead of walking the straight line (ops_scenario.nav_field)')
+    p.add_argument('--nav-cell', dest='nav_cell', type=float, default=None, help='--nav: the grid cell in metres (default 0.25)')
+    p.add_argument('--nav-clearance', dest='nav_clearance', type=float, default=None,
+                   help='--nav: a cell is blocked when an obstacle point lies within this many metres of its centre (default 0.3)')
     p.add_argument('--frames', type=int, default=750)
     seed = p.add_mutually_exclusive_group()
     seed.add_argument('--seed', type=int, default=0, help='seed of the spawn schedule')
@@ -165,6 +177,29 @@ def get_args(argv=None):
                 p.error(f'--scene-groups: {ex}')
     elif own.scene_frames is not None or own.scene_jitter != 0.0 or own.scene_groups is not None:
         p.error('--scene-frames / --scene-jitter / --scene-groups need --scene-from')
+    own.plan = None
+    if own.scene_plan is not None:
+        if own.scene_from is not None or own.scenario != p.get_default('scenario'):
+            p.error('--scene-plan builds the scene from a floor plan: not with --scene-from or --scenario')
+        if own.law != 'mlapm':
+            p.error('--scene-plan: a floor plan runs under --law mlapm only: the network-driven frame has no floor field '
+                    '(piml_scenario_step_mlapm_nav is the MLAPM frame\'s), so with --law pinnsf nothing would route its agents')
+        try:
+            own.plan = SCENARIOS.load_floorplan(own.scene_plan)
+        except (OSError, ValueError) as ex:
+            p.error(f'--scene-plan: {ex}')
+    if own.nav:
+        if own.law != 'mlapm':
+            p.error('--nav needs --law mlapm (the network-driven frame has no floor field)')
+        if own.scene_from is not None or (own.scene_plan is None and own.scenario != 'gc'):
+            p.error('--nav routes scenes of gates: --scenario gc or --scene-plan (a clip scene carries recorded waypoints and '
+                    'no gates; the synthetic scenes have none either)')
+        own.nav_cell = 0.25 if own.nav_cell is None else own.nav_cell
+        own.nav_clearance = 0.3 if own.nav_clearance is None else own.nav_clearance
+        if not (own.nav_cell > 0 and own.nav_cell < float('inf') and own.nav_clearance > 0 and own.nav_clearance < float('inf')):
+            p.error(f'--nav-cell / --nav-clearance: finite values > 0 expected, got {own.nav_cell}, {own.nav_clearance}')
+    elif own.nav_cell is not None or own.nav_clearance is not None:
+        p.error('--nav-cell / --nav-clearance need --nav')
     if own.params_sweep is not None:
         if own.params is not None:
             p.error('--params-sweep takes the place of --params: not both')
@@ -293,6 +328,9 @@ def main(argv=None):
     if own.scene_from is not None:
         scenario = _clip_scene(own)
         own.scenario = scenario.name
+    elif own.plan is not None:
+        scenario = own.plan
+        own.scenario = scenario.name
     else:
         kw = {} if own.uniform_desired_speed is None else {'uniform_desired_speed': own.uniform_desired_speed}
         scenario = SCENARIOS.SCENARIOS[own.scenario](time_unit=own.time_unit, **kw)
@@ -308,6 +346,17 @@ def main(argv=None):
             check_scene_groups(scenario)
         except ValueError as ex:
             sys.exit(f'--params / --params-sweep: {ex} (--scene-from CLIP --scene-groups auto|FILE.json)')
+    if own.nav:
+        import dataclasses
+        from . import ops_scenario
+        scenario = dataclasses.replace(scenario, route_max_iters=0)       # (GC: the field routes, not the pillar's detour)
+        try:
+            run_kw['nav'] = ops_scenario.nav_field(scenario.to(args.device), cell=own.nav_cell, clearance=own.nav_clearance,
+                                                   device=args.device)
+        except (ValueError, RuntimeError) as ex:
+            sys.exit(f'--nav: {ex}')
+        print(f'[simulate] floor field: {run_kw["nav"].G} gates, {run_kw["nav"].gx} x {run_kw["nav"].gy} cells of '
+              f'{run_kw["nav"].cell:g} m, {run_kw["nav"].iterations} steps')
     if own.law == 'mlapm' and own.mlapm_sweep is not None:
         return _sweep(sim, scenario, own, run_kw)
     if own.seeds is not None:
