@@ -840,7 +840,9 @@ int piml_calc_acceleration(const float* relative_data, size_t rows, int row_stri
  *   Euler); waypoint switch when |p - dest| < 0.5; past the last waypoint the agent leaves the
  *   scene (p' = NaN, only if remove_arrived); agents entering at frame t+1 are re-initialised
  *   from the ground-truth series; history-velocity shift; columns 2.. of the next self_features
- *   row = (history, a', desired speed)  [columns 0..1 are written by piml_relfeat_fwd].
+ *   row = (history, a', desired speed)  [columns 0..1 are written by piml_relfeat_fwd].  NaN
+ *   components of v', a' are stored as 0 in the state and in the row's a' columns, as the feature
+ *   recomputation writes them into its arguments (src/data/data.py:483-484); the history keeps them.
  * State (C,N,.) is updated IN PLACE; a_next (C,N,2) is the model's prediction.  Series are
  * (C,T,N,.); new_flag (C,T+1,N) uint8 (frame T all zero); F = hist_width + 5; waypoints
  * (D,N,2) shared (waypoints_per_slice = 0) or (C,D,N,2).  The frame index t is read from DEVICE

@@ -1358,7 +1358,7 @@ struct RolloutArgs {
 
 // One thread per (slice, agent): record frame t, lagged explicit Euler (quirk Q6), waypoint switch
 // at 0.5 m, leave-scene NaN, injection of agents entering at frame t+1 from the ground truth,
-// history shift, and the (hist, a, v0) columns of the next self_features row.
+// history shift, NaN -> 0 of the new v, a, and the (hist, a, v0) columns of the next self_features row.
 __device__ __forceinline__ void rollout_step_agent(const RolloutArgs& A, long long g, float2 an) {
     const int c = (int)(g / A.N), i = (int)(g - (long long)c * A.N);
     const long long t = *A.t_dev;
@@ -1393,6 +1393,10 @@ __device__ __forceinline__ void rollout_step_agent(const RolloutArgs& A, long lo
         h[hw - 2] = vn.x; h[hw - 1] = vn.y;
         for (int q = 0; q < hw; ++q) so[2 + q] = h[q];
     }
+    // the NaN -> 0 that get_relative_features applies in place to the v, a it is handed (data.py:483-484, the views of :643):
+    // the history above took them as they were, the state and the row's a columns carry the zeros
+    vn.x = vn.x != vn.x ? 0.f : vn.x; vn.y = vn.y != vn.y ? 0.f : vn.y;
+    an.x = an.x != an.x ? 0.f : an.x; an.y = an.y != an.y ? 0.f : an.y;
     so[2 + hw] = an.x; so[3 + hw] = an.y; so[4 + hw] = A.desired_speed[g];             // :651
     A.p[g] = pn; A.v[g] = vn; A.a[g] = an; A.dest[g] = dn; A.dest_idx[g] = idx;
 }
