@@ -1296,6 +1296,81 @@ int piml_scenario_step_mlapm_nav(const piml_scenario* s, const piml_scenario_rul
                                  const piml_noise_args* noise /* NULL: no fluctuation */, int frame_offset, void* stream);
 
 /*
+ * The any-angle floor field: a second table beside u.  For every cell c of gate g, parent[g][c] is the next turning point
+ * of the taut string from c to the gate -- the gate cell itself in open space, a corner cell round a wall -- and w[g][c]
+ * the string's length in cells.  An agent in c steers at the centre of its parent along a straight segment that enters no
+ * blocked cell wherever in c it stands, so routed agents walk straight where piml_nav_direction's first-order gradient curves
+ * (3 degrees off on average in open space) and keep off the walls where it falls back to a neighbour's centre.
+ *
+ * The grid, blocked (gy, gx) and goal (G, gy, gx) are piml_nav_relax's: a cell outside the grid counts as blocked, a goal
+ * cell is free whatever `blocked` says (gate g sees the mask blocked & !goal[g]).  w (G, gy, gx) float32 in cell units;
+ * parent (G, gy, gx) int32, the linear index y gx + x, or -1.
+ *
+ * Start: goal cells w = 0, parent = self; every other cell w = +inf, parent = -1.  Goal and blocked cells never change.
+ * One Jacobi step k -> k + 1, for every free cell c = (x, y) that is no goal cell:
+ *   best = +inf, bp = -1; if parent_k[c] = q >= 0: best = fadd(w_k[q], dist(c, q)), bp = q.
+ *   For the neighbours n in the order E, W, N, S, NE, NW, SE, SW (N = +y): skip n outside the grid, blocked, or with w_k[n]
+ *   not finite; skip a diagonal n when either orthogonal cell beside it is blocked or outside (no corner is cut).
+ *   q = parent_k[n] (n itself for a goal cell); if !visible(c, q): q = n.  cand = fadd(w_k[q], dist(c, q)) replaces
+ *   (best, bp) only when cand < best strictly.
+ *   w_{k+1}[c] = best, parent_{k+1}[c] = bp.
+ * dist(c, q) = sqrtf((float)(dx dx + dy dy)): the integer is exact below 2^24, the root correctly rounded, so a numpy float32
+ * run with Python integers is the same function bit for bit (tests/navsight_ref.py).  w never increases; a step that changed
+ * nothing is a fixed point.
+ *
+ * visible(c, q), D = q - c: a cell X = c + a OBSTRUCTS when it is blocked (or outside) and there is a t in [0, 1] with
+ * |a.x - t D.x| < 1 - t / 2 and |a.y - t D.y| < 1 - t / 2: the open square of X meets the convex hull of c's square and q's
+ * centre, which at t is a square of half-width (1 - t) / 2 around c + t D.  visible is true when no cell obstructs.  Each
+ * inequality is two strict linear constraints on t with odd integer coefficients, t (2 D - 1) > 2 a - 2 and
+ * t (2 D + 1) < 2 a + 2, compared by integer cross-multiplication: no float is involved.  Walking along the face of a wall is
+ * visible; a diagonal pinch between two blocked cells never is.
+ *
+ * piml_nav_sight_relax: `launches` launches of ONE Jacobi step each, one wave per cell.  Launch j reads (w_a, parent_a) and
+ * writes (w_b, parent_b) for even j and the other way round for odd j (every cell of the written planes is written), so
+ * after an even number of launches the result is in the a planes.  The caller initialises the a planes (the start above;
+ * any state whose parents are -1 or cells with a finite w is stepped as it stands).  cache (G, gy, gx, 8) int32, filled with
+ * -1 by the caller before the first launch and kept between launches on the same mask: per cell and neighbour slot the last
+ * parent tested and whether c sees it, (q << 1) | visible.  It only saves walks: visible(c, q) is a property of the mask, so
+ * the planes are bitwise those of the plain step whatever valid entries it holds.  changed (G) int32: a wave whose cell's
+ * w or parent differs from its input stores 1 into changed[g] (a plain store; never cleared here).  No atomics, no host
+ * synchronisation; capturable.
+ * hipErrorInvalidValue (before any launch): a NULL buffer; w_a == w_b or parent_a == parent_b; G outside 1..64; gx or gy
+ * outside 1..1024; launches < 0.  launches == 0 is a no-op.
+ *
+ * piml_nav_sight: the parent planes as the lookup reads them, beside the piml_nav_grid of the same scene.
+ *
+ * piml_nav_direction_sight: piml_nav_direction with one branch in front of its branches 1 and 2:
+ *   3, sight: where the field applies (p inside the grid, the gate valid, u[c] finite and > near) and q = parent[g][c] >= 0
+ *      is not c itself: T = origin + (q + 0.5) cell per axis (branch 2's centre formula), h = T - p,
+ *      h2 = fadd(fmul(h.x, h.x), fmul(h.y, h.y)) > 0: e = h rsq(h2), neighbour -1.
+ * Otherwise branches 1, 2 and 0 as in piml_nav_direction, bit for bit.  Arguments and refusals are piml_nav_direction's, and
+ * hipErrorInvalidValue also for a NULL sight or sight->parent, or sight->G, gx, gy other than the grid's.
+ *
+ * piml_scenario_step_mlapm_sight: piml_scenario_step_mlapm_nav with n = piml_nav_direction_sight's result: the steering
+ * target is fl(p + n.e) in branches 1, 2 and 3, the destination in branch 0.  A parent plane that is all -1 gives
+ * piml_scenario_step_mlapm_nav bit for bit.  hipErrorInvalidValue (before any launch): everything piml_scenario_step_mlapm_nav
+ * refuses; a NULL sight or sight->parent; sight->G, gx, gy other than the grid's.  No atomics, capturable.
+ *
+ * Known limits: the agent heads for the centre of the gate CELL until `near`, not for its own destination point; parents are
+ * cell centres, so a path rounds a corner at half a cell plus the mask's clearance; the field is static.
+ */
+typedef struct piml_nav_sight {
+    const int* parent;                                      /* (G, gy, gx) device: y gx + x of the parent cell, or -1 */
+    int G, gx, gy;
+} piml_nav_sight;
+int piml_nav_sight_relax(const unsigned char* blocked, const unsigned char* goal, float* w_a, int* parent_a, float* w_b,
+                         int* parent_b, int* cache, int G, int gx, int gy, int launches, int* changed, void* stream);
+int piml_nav_direction_sight(const float* position, const int* gate, const float* destination, long long rows,
+                             const piml_nav_grid* g, const piml_nav_sight* sight, float* direction,
+                             int* branch /* may be NULL */, int* neighbour /* may be NULL */, void* stream);
+int piml_scenario_step_mlapm_sight(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                                   const piml_mlapm_law* law, const void* law_table_device,
+                                   const piml_wall_grid* wall_grid /* NULL: no wall term */, const piml_wall_law* wall,
+                                   const piml_wall_law* wall_table_device, const piml_nav_grid* nav,
+                                   const piml_nav_sight* sight, const piml_noise_args* noise /* NULL: no fluctuation */,
+                                   int frame_offset, void* stream);
+
+/*
  * utils.route (src/utils/utils.py:141-165) for n (o, d) pairs, one wave each, the device function the spawn path uses:
  * the segment o -> r is tested against the polyline's R-1 segments, the hit with the smallest alpha moves r to
  * crossing + clearance * normal, until nothing is hit or max_iters moves were made.  float32 in the reference's order.

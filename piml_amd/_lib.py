@@ -123,6 +123,11 @@ class NavGrid(ctypes.Structure):
     _fields_ = [('u', _p), ('G', _i), ('gx', _i), ('gy', _i), ('x0', _f), ('y0', _f), ('cell', _f), ('near', _f)]
 
 
+class NavSight(ctypes.Structure):
+    """piml_nav_sight (include/piml_hip.h)."""
+    _fields_ = [('parent', _p), ('G', _i), ('gx', _i), ('gy', _i)]
+
+
 SPAWN_LAWS = {'gc': 0, 'crosswalk': 1, 'square': 2, 'unit1': 3, 'unit2': 4, 'unit3': 5, 'clip': 6}     # PIML_SPAWN_*
 SPAWN_CLIP_GROUPS = 7          # PIML_SPAWN_CLIP_GROUPS ('clip_groups'): piml_scenario_step_mlapm_groups only, so not in SPAWN_LAWS
 ARRIVAL_RULES = {'gc': 0, 'radius': 1, 'x_band': 2, 'x_exit': 3}                             # PIML_ARRIVE_*
@@ -203,6 +208,9 @@ SIGNATURES = {
     'piml_nav_relax': [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
     'piml_nav_direction': [_p, _p, _p, _ll, _p, _p, _p, _p, _p],
     'piml_scenario_step_mlapm_nav': [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
+    'piml_nav_sight_relax': [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
+    'piml_nav_direction_sight': [_p, _p, _p, _ll, _p, _p, _p, _p, _p, _p],
+    'piml_scenario_step_mlapm_sight': [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
     'piml_scenario_route': [_p, _p, _i, _p, _i, _i, _f, _p, _p, _p],
     'piml_collision_correction_fwd': [_p, _p, _p, _z, _i, _i, _f, _f, _p, _p],
     'piml_collision_correction_bwd': [_p, _p, _p, _p, _z, _i, _i, _f, _f, _p, _p, _p, _p],

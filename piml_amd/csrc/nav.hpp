@@ -14,6 +14,8 @@
 //                is not finite (no corner is cut); ORDER: E, W, N, S, NE, NW, SE, SW, N = +y, and a later
 //                neighbour replaces an earlier one only when its s is strictly larger, so ties go to the first.  e points
 //                from p to n's centre origin + (n + 0.5) cell.  No neighbour qualifies: branch 0.
+//   3 sight:     (nav_direction<true> only) in front of 1 and 2: the centre of parent[g][c], the next turning point of the
+//                shortest path from c (piml_nav_sight_relax, navsight.hip); see kSight below.
 // Every predicate above is one correctly rounded float32 operation after another (tests/nav_ref.py restates them in numpy),
 // so branch and neighbour are exact; e uses the hardware rsq (1e-5 relative, as the pair law and the wall term).
 // Cells outside the grid read as +inf (the load is from the cell clamped into the grid) and g is range-checked: no index
@@ -61,7 +63,14 @@ __device__ __forceinline__ bool nav_finite(float x) { return fabsf(x) < INFINITY
 // One wave, one agent: p, dest and g are the same in every lane, and so is the result.  Written without branches: the three
 // candidates are all computed (13 loads of words every lane shares) and the result is selected, which keeps the frame's
 // scalar registers free of saved execution masks; what a refused branch computed (inf - inf, say) is never selected.
-__device__ __forceinline__ NavDir nav_direction(const piml_nav_grid& N, int g, float2 p, float2 dest) {
+//
+// kSight (piml_nav_direction_sight, piml_scenario_step_mlapm_sight): branch 3 in front of the other two.  parent (G, gy, gx) is
+// the any-angle table of piml_nav_sight_relax; where the field applies and q = parent[g][c] >= 0 is not c itself, e points
+// from p to q's centre (branch 2's centre formula), whose segment from any point of c enters no blocked cell.  One more load,
+// two integer divisions by gx, the same selects.  kSight == false does not read `parent` and compiles to what it was.
+template <bool kSight = false>
+__device__ __forceinline__ NavDir nav_direction(const piml_nav_grid& N, int g, float2 p, float2 dest,
+                                                const int* __restrict__ parent = nullptr) {
     const float2 e0 = nav_straight(p, dest);
     const float qx = __fdiv_rn(__fsub_rn(p.x, N.x0), N.cell), qy = __fdiv_rn(__fsub_rn(p.y, N.y0), N.cell);
     const float fcx = floorf(qx), fcy = floorf(qy);
@@ -106,13 +115,32 @@ __device__ __forceinline__ NavDir nav_direction(const piml_nav_grid& N, int g, f
     const float hy = __fsub_rn(__fadd_rn(N.y0, __fmul_rn(__fadd_rn((float)(cy + dy), 0.5f), N.cell)), p.y);
     const float h2 = __fadd_rn(__fmul_rn(hx, hx), __fmul_rn(hy, hy));
     const bool descent = field && !bilinear && k >= 0 && h2 > 0.f;
-    const float rinv = fast_rsq(bilinear ? g2 : h2);
-    NavDir d;
-    d.e.x = bilinear ? -gx * rinv : descent ? hx * rinv : e0.x;
-    d.e.y = bilinear ? -gy * rinv : descent ? hy * rinv : e0.y;
-    d.branch = bilinear ? 1 : descent ? 2 : 0;
-    d.neighbour = descent ? k : -1;
-    return d;
+    if constexpr (kSight) {
+        // 3: the parent's centre.  The load is from the cell clamped into the grid, the parent clamped into the plane
+        const int cells = N.gy * N.gx;
+        const int lin = min(max(cy, 0), N.gy - 1) * N.gx + min(max(cx, 0), N.gx - 1);
+        const int q = parent[(size_t)min(max(g, 0), N.G - 1) * (size_t)cells + (size_t)lin];
+        const int qc = min(max(q, 0), cells - 1);
+        const float sx = __fsub_rn(__fadd_rn(N.x0, __fmul_rn(__fadd_rn((float)(qc % N.gx), 0.5f), N.cell)), p.x);
+        const float sy = __fsub_rn(__fadd_rn(N.y0, __fmul_rn(__fadd_rn((float)(qc / N.gx), 0.5f), N.cell)), p.y);
+        const float s2 = __fadd_rn(__fmul_rn(sx, sx), __fmul_rn(sy, sy));
+        const bool sight = field && q >= 0 && q < cells && q != lin && s2 > 0.f;
+        const float rinv = fast_rsq(sight ? s2 : bilinear ? g2 : h2);
+        NavDir d;
+        d.e.x = sight ? sx * rinv : bilinear ? -gx * rinv : descent ? hx * rinv : e0.x;
+        d.e.y = sight ? sy * rinv : bilinear ? -gy * rinv : descent ? hy * rinv : e0.y;
+        d.branch = sight ? 3 : bilinear ? 1 : descent ? 2 : 0;
+        d.neighbour = descent && !sight ? k : -1;
+        return d;
+    } else {
+        const float rinv = fast_rsq(bilinear ? g2 : h2);
+        NavDir d;
+        d.e.x = bilinear ? -gx * rinv : descent ? hx * rinv : e0.x;
+        d.e.y = bilinear ? -gy * rinv : descent ? hy * rinv : e0.y;
+        d.branch = bilinear ? 1 : descent ? 2 : 0;
+        d.neighbour = descent ? k : -1;
+        return d;
+    }
 }
 
 // ---- host: the grid checks of piml_nav_direction and piml_scenario_step_mlapm_nav (include/piml_hip.h) ----
@@ -125,6 +153,11 @@ static inline bool nav_grid_ok(const piml_nav_grid* g) {
     if (!g || !g->u || !nav_dims_ok(g->G, g->gx, g->gy)) return false;
     if (!std::isfinite(g->cell) || !(g->cell > 0.f) || !std::isfinite(g->near) || g->near < 0.f) return false;
     return std::isfinite(g->x0) && std::isfinite(g->y0);
+}
+
+// the table of the sight branch against the grid it goes with
+static inline bool nav_sight_ok(const piml_nav_sight* s, const piml_nav_grid* g) {
+    return s && g && s->parent && s->G == g->G && s->gx == g->gx && s->gy == g->gy;
 }
 
 }  // namespace piml

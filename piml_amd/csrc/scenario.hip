@@ -764,12 +764,16 @@ struct MlapmScenarioArgs {
 // ulp(p).  In branch 0 the target is the destination: the straight line, bit for bit.  Everything else -- the force, the terms
 // above, integration, arrival against S.destination -- is the same code.  kNav == false does not read NV: the kernels above
 // compile to the instructions they had.
-template <bool kTable, bool kWalls, bool kGroups, bool kNoise = false, bool kNav = false>
+//
+// kSight (piml_scenario_step_mlapm_sight, with kNav): the lookup with its sight branch, nav_direction<true>(..., SV.parent): in
+// branch 3 the target is fl(p + n.e) as in branches 1 and 2.  One more load per agent; kSight == false does not read SV.
+template <bool kTable, bool kWalls, bool kGroups, bool kNoise = false, bool kNav = false, bool kSight = false>
 __device__ __forceinline__ void scenario_mlapm_body(const MlapmScenarioArgs& K0, const unsigned long long* __restrict__ seeds,
                                                     const MlapmParams* __restrict__ table, const WallArgs& WG,
                                                     const piml_wall_law& wall, const piml_wall_law* __restrict__ wall_table,
                                                     const GroupArgs& GA, const piml_noise_args& NA = piml_noise_args{},
-                                                    const piml_nav_grid& NV = piml_nav_grid{}) {
+                                                    const piml_nav_grid& NV = piml_nav_grid{},
+                                                    const piml_nav_sight& SV = piml_nav_sight{}) {
     __shared__ float4 tile[kMlTile];                         // agent blocks: the sources (px, py, vx, vy); spawn blocks: entries
     __shared__ unsigned short ucy_ring[kMlScWaves][256];
     static_assert(kScenarioLdsPoints * sizeof(float2) <= sizeof(tile), "the entry points fit the source tile");
@@ -796,7 +800,7 @@ __device__ __forceinline__ void scenario_mlapm_body(const MlapmScenarioArgs& K0,
         if constexpr (kNav) {
             if (live) {                                      // wave-uniform; the gate is range-checked by the lookup
                 const int gate = S.exit_idx[(size_t)S.flag[i] * cap + i];
-                const NavDir nd = nav_direction(NV, gate, pi, di);
+                const NavDir nd = nav_direction<kSight>(NV, gate, pi, di, SV.parent);
                 const float tx = nd.branch ? __fadd_rn(pi.x, nd.e.x) : di.x, ty = nd.branch ? __fadd_rn(pi.y, nd.e.y) : di.y;
                 ti = make_float2(tx, ty);
             }
@@ -948,6 +952,18 @@ __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_nav_kernel(con
                                                                             const piml_wall_law* __restrict__ wall_table,
                                                                             const piml_noise_args NA, const piml_nav_grid NV) {
     scenario_mlapm_body<kTable, kWalls, false, true, true>(K0, seeds, table, WG, wall, wall_table, GroupArgs{}, NA, NV);
+}
+
+// the frame routed by the floor field and its any-angle table (nav.hpp, branch 3)
+template <bool kTable, bool kWalls>
+__global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_sight_kernel(const MlapmScenarioArgs K0,
+                                                                              const unsigned long long* __restrict__ seeds,
+                                                                              const MlapmParams* __restrict__ table,
+                                                                              const WallArgs WG, const piml_wall_law wall,
+                                                                              const piml_wall_law* __restrict__ wall_table,
+                                                                              const piml_noise_args NA, const piml_nav_grid NV,
+                                                                              const piml_nav_sight SV) {
+    scenario_mlapm_body<kTable, kWalls, false, true, true, true>(K0, seeds, table, WG, wall, wall_table, GroupArgs{}, NA, NV, SV);
 }
 
 }  // namespace piml
@@ -1256,19 +1272,25 @@ PIML_API int piml_scenario_step_mlapm_noise(const piml_scenario* s, const piml_s
     return hipGetLastError();
 }
 
+// sight == NULL: the nav frame's kernels
 template <bool kTable, bool kWalls>
 static void launch_mlapm_nav(dim3 grid, hipStream_t st, const piml::MlapmScenarioArgs& K, const unsigned long long* sd,
                              const piml::MlapmParams* tb, const piml::WallArgs& WG, const piml_wall_law& w,
-                             const piml_wall_law* wt, const piml_noise_args& NA, const piml_nav_grid& NV) {
-    hipLaunchKernelGGL((piml::scenario_mlapm_nav_kernel<kTable, kWalls>), grid, dim3(piml::kMlScWaves * 64), 0, st, K, sd, tb,
-                       WG, w, wt, NA, NV);
+                             const piml_wall_law* wt, const piml_noise_args& NA, const piml_nav_grid& NV,
+                             const piml_nav_sight* sight) {
+    if (sight)
+        hipLaunchKernelGGL((piml::scenario_mlapm_sight_kernel<kTable, kWalls>), grid, dim3(piml::kMlScWaves * 64), 0, st, K, sd,
+                           tb, WG, w, wt, NA, NV, *sight);
+    else
+        hipLaunchKernelGGL((piml::scenario_mlapm_nav_kernel<kTable, kWalls>), grid, dim3(piml::kMlScWaves * 64), 0, st, K, sd, tb,
+                           WG, w, wt, NA, NV);
 }
 
-PIML_API int piml_scenario_step_mlapm_nav(const piml_scenario* s, const piml_scenario_rules* r, int members,
-                                          const uint64_t* seeds, const piml_mlapm_law* law, const void* law_table_device,
-                                          const piml_wall_grid* wall_grid, const piml_wall_law* wall,
-                                          const piml_wall_law* wall_table_device, const piml_nav_grid* nav,
-                                          const piml_noise_args* noise, int frame_offset, void* stream) {
+// piml_scenario_step_mlapm_nav (sight == NULL) and piml_scenario_step_mlapm_sight: one set of checks, one dispatch
+static int step_mlapm_nav(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                          const piml_mlapm_law* law, const void* law_table_device, const piml_wall_grid* wall_grid,
+                          const piml_wall_law* wall, const piml_wall_law* wall_table_device, const piml_nav_grid* nav,
+                          const piml_nav_sight* sight, const piml_noise_args* noise, int frame_offset, void* stream) {
     if (noise && (!noise->state || (!noise->law_table && !piml::noise_law_ok(noise->law.rho, noise->law.amp))))
         return hipErrorInvalidValue;
     if (!s || !seeds || members < 1 || members > 65535 || frame_offset < 0) return hipErrorInvalidValue;
@@ -1292,13 +1314,33 @@ PIML_API int piml_scenario_step_mlapm_nav(const piml_scenario* s, const piml_sce
     const piml::MlapmParams* tb = (const piml::MlapmParams*)law_table_device;
     hipStream_t st = piml::as_stream(stream);
     if (law) {
-        if (wall_grid) launch_mlapm_nav<false, true>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav);
-        else launch_mlapm_nav<false, false>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav);
+        if (wall_grid) launch_mlapm_nav<false, true>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav, sight);
+        else launch_mlapm_nav<false, false>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav, sight);
     } else {
-        if (wall_grid) launch_mlapm_nav<true, true>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav);
-        else launch_mlapm_nav<true, false>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav);
+        if (wall_grid) launch_mlapm_nav<true, true>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav, sight);
+        else launch_mlapm_nav<true, false>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav, sight);
     }
     return hipGetLastError();
+}
+
+PIML_API int piml_scenario_step_mlapm_nav(const piml_scenario* s, const piml_scenario_rules* r, int members,
+                                          const uint64_t* seeds, const piml_mlapm_law* law, const void* law_table_device,
+                                          const piml_wall_grid* wall_grid, const piml_wall_law* wall,
+                                          const piml_wall_law* wall_table_device, const piml_nav_grid* nav,
+                                          const piml_noise_args* noise, int frame_offset, void* stream) {
+    return step_mlapm_nav(s, r, members, seeds, law, law_table_device, wall_grid, wall, wall_table_device, nav, nullptr, noise,
+                          frame_offset, stream);
+}
+
+PIML_API int piml_scenario_step_mlapm_sight(const piml_scenario* s, const piml_scenario_rules* r, int members,
+                                            const uint64_t* seeds, const piml_mlapm_law* law, const void* law_table_device,
+                                            const piml_wall_grid* wall_grid, const piml_wall_law* wall,
+                                            const piml_wall_law* wall_table_device, const piml_nav_grid* nav,
+                                            const piml_nav_sight* sight, const piml_noise_args* noise, int frame_offset,
+                                            void* stream) {
+    if (!piml::nav_grid_ok(nav) || !piml::nav_sight_ok(sight, nav)) return hipErrorInvalidValue;
+    return step_mlapm_nav(s, r, members, seeds, law, law_table_device, wall_grid, wall, wall_table_device, nav, sight, noise,
+                          frame_offset, stream);
 }
 
 PIML_API int piml_scenario_route(const float* origin, const float* destination, int n, const float* polyline, int R,

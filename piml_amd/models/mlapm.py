@@ -173,8 +173,10 @@ class MLAPM:
         nav = True or an ops_scenario.nav_field(...) of the scene: the agents descend a static floor field -- per gate the
         geodesic distance over the free cells of a grid (piml_nav_relax) -- instead of walking the straight line to their
         destination (piml_scenario_step_mlapm_nav), so they go round walls; True builds the field with nav_field's defaults.
-        The field belongs to the scene, not the law.  A scene of gates only (gc_scenario() with route_max_iters=0,
-        scenarios.floorplan_scenario): ValueError otherwise (ops_scenario.check_nav_scene).
+        nav = 'sight' builds it with the any-angle table as well (nav_field(sight=True)): the agents then steer along lines
+        of sight, at the next turning point of the shortest path (piml_scenario_step_mlapm_sight); a passed field decides by
+        whether it has the table.  The field belongs to the scene, not the law.  A scene of gates only (gc_scenario() with
+        route_max_iters=0, scenarios.floorplan_scenario): ValueError otherwise (ops_scenario.check_nav_scene).
         Returns a scenarios.ScenarioResult."""
         return self._simulate(scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, nav=nav,
                               seed=seed)
@@ -196,6 +198,7 @@ class MLAPM:
         law = self._law(radius)
         nav = None if nav is False else nav
         if nav is not None:
+            ops_scenario.nav_wants_sight(nav)
             ops_scenario.check_nav_scene(scenario)
         wall = wall_args(self.args)
         if wall is not None:
@@ -208,8 +211,8 @@ class MLAPM:
         if wall is not None:
             walls = (ops_scenario.wall_grid(st.scenario.obstacles, wall[2], st.p.device), ops_scenario.wall_law(*wall[:2]))
         noise = noise_args(self.args)
-        if nav is True:
-            nav = ops_scenario.nav_field(st.scenario, device=st.p.device)
+        if not isinstance(nav, ops_scenario.NavField) and nav is not None:
+            nav = ops_scenario.nav_field(st.scenario, device=st.p.device, sight=ops_scenario.nav_wants_sight(nav))
         self._run_scenario(st, law, use_graph, frames_per_graph, walls=walls,
                            groups=None if group is None else ops_scenario.group_law(*group),
                            noise=None if noise is None else ops_scenario.noise_law(*noise, float(st.scenario.time_unit)),
@@ -414,6 +417,7 @@ class SweepRun:
         from .. import ops_scenario, scenarios
         self.nav = None if nav is False else nav              # True, or the scene's ops_scenario.nav_field: every run's
         if self.nav is not None:
+            ops_scenario.nav_wants_sight(self.nav)
             ops_scenario.check_nav_scene(scenario)
         self.seeds = [int(x) for x in seeds]
         self.n_candidates = int(n_candidates)
@@ -458,8 +462,9 @@ class SweepRun:
                 self.group_table = ops_scenario.group_law_table(group_rows, self.st.p.device)
             if noise is not None:
                 self.noise_table = ops_scenario.noise_law_table(noise_rows, dt, self.st.p.device)
-            if self.nav is True:
-                self.nav = ops_scenario.nav_field(self.st.scenario, device=self.st.p.device)
+            if not isinstance(self.nav, ops_scenario.NavField) and self.nav is not None:
+                self.nav = ops_scenario.nav_field(self.st.scenario, device=self.st.p.device,
+                                                  sight=ops_scenario.nav_wants_sight(self.nav))
         else:
             if (walls is None) != (self.wall_table is None):  # the captured frames are those of the first run's kernel
                 raise ValueError('SweepRun: every run of a sweep has a wall term (Aw, Bw) or none has')

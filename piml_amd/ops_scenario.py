@@ -539,6 +539,7 @@ NAV_MAX_CELLS = 1024                   # per axis (nav.hpp)
 NAV_MAX_GATES = 64
 NAV_STEPS = 8                          # Jacobi steps of one piml_nav_relax launch
 NAV_BATCH = 16                         # launches queued between two looks at `changed`
+NAV_SIGHT_BATCH = 32                   # the same for piml_nav_sight_relax, whose launch is one step
 
 
 def nav_grid_host(scenario, cell=0.25, bounds=None):
@@ -594,9 +595,12 @@ class NavField:
     """The static floor field of a scene of gates (nav_field): u (G, gy, gx) float32 -- gate g's geodesic distance over the
     free cells in CELL units, +inf on blocked and unreachable cells --, blocked (gy, gx) and goal (G, gy, gx) uint8, all on
     the device; desc the piml_nav_grid over u; G, gx, gy, x0, y0, cell, near, clearance; iterations, the Jacobi steps
-    queued until a batch changed nothing."""
+    queued until a batch changed nothing.
+    With the any-angle table (nav_field(..., sight=True)) also w (G, gy, gx) float32 and parent (G, gy, gx) int32 of
+    nav_sight_relax, sight_desc the piml_nav_sight over parent, and sight_iterations, its steps; all None / 0 otherwise."""
 
-    def __init__(self, u, blocked, goal, x0, y0, cell, near, clearance=None, iterations=0):
+    def __init__(self, u, blocked, goal, x0, y0, cell, near, clearance=None, iterations=0, *, w=None, parent=None,
+                 sight_iterations=0):
         if not math.isfinite(float(near)) or float(near) < 0:
             raise ValueError(f'nav field: a finite near >= 0 (cells) expected, got {near}')
         self.u, self.blocked, self.goal = u, blocked, goal
@@ -607,11 +611,24 @@ class NavField:
         d.u, d.G, d.gx, d.gy = u.data_ptr(), self.G, self.gx, self.gy
         d.x0, d.y0, d.cell, d.near = self.x0, self.y0, self.cell, self.near
         self.desc = d
+        self.w, self.parent, self.sight_desc, self.sight_iterations = w, parent, None, int(sight_iterations)
+        if parent is not None:
+            if parent.dtype != torch.int32 or tuple(parent.shape) != tuple(u.shape) or parent.device != u.device \
+                    or not parent.is_contiguous():
+                raise ValueError(f'nav field: parent, a contiguous int32 {tuple(u.shape)} tensor on {u.device} expected, got '
+                                 f'{parent.dtype} {tuple(parent.shape)} on {parent.device}')
+            sd = _lib.NavSight()
+            sd.parent, sd.G, sd.gx, sd.gy = parent.data_ptr(), self.G, self.gx, self.gy
+            self.sight_desc = sd
 
     def to_numpy(self):
-        """a namespace of the numpy copies u, blocked, goal and the scalars"""
-        return types.SimpleNamespace(u=self.u.cpu().numpy(), blocked=self.blocked.cpu().numpy(), goal=self.goal.cpu().numpy(),
-                                     G=self.G, gx=self.gx, gy=self.gy, x0=self.x0, y0=self.y0, cell=self.cell, near=self.near)
+        """a namespace of the numpy copies u, blocked, goal and the scalars; with the any-angle table also w and parent"""
+        out = types.SimpleNamespace(u=self.u.cpu().numpy(), blocked=self.blocked.cpu().numpy(), goal=self.goal.cpu().numpy(),
+                                    G=self.G, gx=self.gx, gy=self.gy, x0=self.x0, y0=self.y0, cell=self.cell, near=self.near)
+        if self.parent is not None:
+            out.parent = self.parent.cpu().numpy()
+            out.w = None if self.w is None else self.w.cpu().numpy()
+        return out
 
     def reachable(self, g):
         """(gy, gx) bool: the cells gate g can be reached from (u[g] finite)"""
@@ -660,12 +677,54 @@ def nav_relax(blocked, goal, u=None, launches=None):
             raise RuntimeError(f'nav_relax: no fixed point after {steps} steps on a {gx} x {gy} grid')
 
 
-def nav_field(scenario, cell=0.25, clearance=0.3, near=2.0, bounds=None, device='cuda'):
+def nav_sight_relax(blocked, goal, launches=None):
+    """The any-angle propagation of piml_nav_sight_relax from its start state on device tensors: blocked (gy, gx) uint8, goal
+    (G, gy, gx) uint8 -> (w (G, gy, gx) float32 in cell units, parent (G, gy, gx) int32, the number of Jacobi steps queued).
+    launches = None: batches of 32 launches of one step until a batch changed nothing (a fixed point: w only decreases);
+    RuntimeError if gx gy steps were not enough.  launches = n: exactly n steps, wherever that leaves the planes."""
+    if blocked.dtype != torch.uint8 or goal.dtype != torch.uint8 or goal.dim() != 3 or tuple(blocked.shape) != tuple(goal.shape[1:]):
+        raise ValueError(f'nav_sight_relax: blocked (gy, gx) and goal (G, gy, gx) uint8 expected, got {blocked.dtype} '
+                         f'{tuple(blocked.shape)}, {goal.dtype} {tuple(goal.shape)}')
+    if goal.device.type != 'cuda' or blocked.device != goal.device:
+        raise _lib.PimlHipError(f'nav_sight_relax: GPU tensors on one device expected (piml_amd has no CPU path), got '
+                                f'{blocked.device}, {goal.device}')
+    G, gy, gx = (int(n) for n in goal.shape)
+    blocked, goal = blocked.contiguous(), goal.contiguous()
+    wa = torch.full(goal.shape, float('inf'), device=goal.device, dtype=torch.float32)
+    wa[goal != 0] = 0.0
+    lin = torch.arange(gy * gx, device=goal.device, dtype=torch.int32).reshape(1, gy, gx).expand(G, gy, gx)
+    pa = torch.where(goal != 0, lin, torch.full_like(lin, -1)).contiguous()
+    wb, pb = torch.empty_like(wa), torch.empty_like(pa)
+    cache = torch.full((G, gy, gx, 8), -1, device=goal.device, dtype=torch.int32)
+    changed = torch.zeros(G, device=goal.device, dtype=torch.int32)
+
+    def queue(n):
+        with torch.cuda.device(goal.device):
+            _lib.check(_lib.lib().piml_nav_sight_relax(_ptr(blocked), _ptr(goal), _ptr(wa), _ptr(pa), _ptr(wb), _ptr(pb),
+                                                       _ptr(cache), G, gx, gy, int(n), _ptr(changed), _stream()),
+                       'piml_nav_sight_relax')
+    if launches is not None:
+        queue(launches)
+        return (wb, pb, int(launches)) if int(launches) & 1 else (wa, pa, int(launches))
+    steps = 0
+    while True:
+        changed.zero_()
+        queue(NAV_SIGHT_BATCH)
+        steps += NAV_SIGHT_BATCH
+        if not bool(changed.any().item()):
+            return wa, pa, steps
+        if steps - NAV_SIGHT_BATCH >= gx * gy:               # the steps before this batch were enough, and it still changed
+            raise RuntimeError(f'nav_sight_relax: no fixed point after {steps} steps on a {gx} x {gy} grid')
+
+
+def nav_field(scenario, cell=0.25, clearance=0.3, near=2.0, bounds=None, device='cuda', sight=False):
     """The floor field of a scene of gates, built once per scene: for every gate g of scenario.entries the geodesic distance
     u[g] to the gate's cells over the free cells of nav_grid_host's grid (piml_nav_relax).  A cell is blocked when an
     obstacle point lies within `clearance` of its centre (wall_force's exact float32 dist2 against a wall_grid of cutoff
     `clearance`); the cells that hold a gate's points are forced free.  near (cells): within it of the gate an agent walks
-    straight to its own destination point.  Returns a NavField."""
+    straight to its own destination point.  sight = True: also the any-angle table of the same mask (nav_sight_relax): the
+    field's w, parent, sight_desc and sight_iterations, which nav_direction and scenario_step_mlapm(nav=) then use.
+    Returns a NavField."""
     dev = torch.device(device)
     if dev.type != 'cuda':
         raise _lib.PimlHipError(f'nav_field: a GPU device expected (piml_amd has no CPU path), got {dev}')
@@ -681,16 +740,26 @@ def nav_field(scenario, cell=0.25, clearance=0.3, near=2.0, bounds=None, device=
     goal = torch.from_numpy(h.goal).to(dev)
     blocked = ((index >= 0) & ~(goal != 0).any(0)).to(torch.uint8).contiguous()
     u, steps = nav_relax(blocked, goal)
-    return NavField(u, blocked, goal, h.x0, h.y0, h.cell, near, clearance, steps)
+    if not sight:
+        return NavField(u, blocked, goal, h.x0, h.y0, h.cell, near, clearance, steps)
+    w, parent, sight_steps = nav_sight_relax(blocked, goal)
+    return NavField(u, blocked, goal, h.x0, h.y0, h.cell, near, clearance, steps, w=w, parent=parent,
+                    sight_iterations=sight_steps)
 
 
-def nav_direction(position, gate, destination, field, return_branch=False):
+def nav_direction(position, gate, destination, field, return_branch=False, sight=None):
     """The desired direction of piml_nav_direction for every row: position (..., 2), gate (...) integers, destination
     (..., 2) -> e (..., 2) unit vectors.  return_branch: also branch (...) int32 (0 straight, 1 bilinear, 2 descent) and
     neighbour (...) int32 (branch 2's neighbour in the order E, W, N, S, NE, NW, SE, SW; -1 otherwise).  In branches 1 and 2
-    position + e (one float32 add) is bitwise the point scenario_step_mlapm(..., nav=field) steers an agent there to."""
+    position + e (one float32 add) is bitwise the point scenario_step_mlapm(..., nav=field) steers an agent there to.
+    sight = None: a field with the any-angle table (nav_field(..., sight=True)) is looked up through it
+    (piml_nav_direction_sight: branch 3, sight, in front of 1 and 2; neighbour -1); sight = False forces the lookup without
+    the table; sight = True raises ValueError for a field without one."""
     if not isinstance(field, NavField):
         raise TypeError(f'field: a nav_field(...) expected, got {type(field).__name__}')
+    if sight and field.sight_desc is None:
+        raise ValueError('nav_direction: sight=True needs a field with the any-angle table (nav_field(..., sight=True))')
+    use_sight = field.sight_desc is not None if sight is None else bool(sight)
     p = _gpu_f32('position', position)
     d = _gpu_f32('destination', destination)
     if p.dim() < 1 or p.shape[-1] != 2 or p.shape != d.shape:
@@ -706,8 +775,13 @@ def nav_direction(position, gate, destination, field, return_branch=False):
     nb = torch.full(lead, -1, device=p.device, dtype=torch.int32) if return_branch else None
     if rows:                                     # (an empty problem keeps the fills above: the entry launches nothing)
         with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().piml_nav_direction(_ptr(p), _ptr(g), _ptr(d), rows, ctypes.byref(field.desc), _ptr(e),
-                                                     _ptr(branch), _ptr(nb), _stream()), 'piml_nav_direction')
+            if use_sight:
+                _lib.check(_lib.lib().piml_nav_direction_sight(_ptr(p), _ptr(g), _ptr(d), rows, ctypes.byref(field.desc),
+                                                               ctypes.byref(field.sight_desc), _ptr(e), _ptr(branch), _ptr(nb),
+                                                               _stream()), 'piml_nav_direction_sight')
+            else:
+                _lib.check(_lib.lib().piml_nav_direction(_ptr(p), _ptr(g), _ptr(d), rows, ctypes.byref(field.desc), _ptr(e),
+                                                         _ptr(branch), _ptr(nb), _stream()), 'piml_nav_direction')
     return (e, branch, nb) if return_branch else e
 
 
@@ -737,6 +811,18 @@ def check_nav_scene(scenario):
         raise ValueError(f'nav: route_max_iters must be 0, got {scenario.route_max_iters}: with a detour point the '
                          f"agent's waypoint gate is not its destination gate and it would never arrive "
                          f'(dataclasses.replace(scenario, route_max_iters=0))')
+
+
+def nav_wants_sight(nav):
+    """The nav= argument of MLAPM.simulate_* and SweepRun: True -> False (today's field), 'sight' -> True (the field with the
+    any-angle table), a NavField -> whether it has the table; TypeError for anything else."""
+    if isinstance(nav, NavField):
+        return nav.sight_desc is not None
+    if nav is True:
+        return False
+    if isinstance(nav, str) and nav == 'sight':
+        return True
+    raise TypeError(f"nav: True, 'sight' or a nav_field(...) expected, got {nav!r}")
 
 
 def _check_nav(st, nav):
@@ -775,7 +861,8 @@ def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, group
     nav = a nav_field(...) of the scene: the frame routed by the floor field (piml_scenario_step_mlapm_nav): every slot
     steers to p + nav_direction(p, the gate of its waypoint, destination) in place of its destination (to the destination
     itself in the lookup's branch 0), with or without walls and noise; everything else is the same frame.  ValueError (check_nav_scene) for a grouped scene, a scene rule
-    other than GC's, route_max_iters != 0, or a field of another number of gates."""
+    other than GC's, route_max_iters != 0, or a field of another number of gates.  A field with the any-angle table
+    (nav_field(..., sight=True)) goes to piml_scenario_step_mlapm_sight: the lookup with its sight branch, the same frame."""
     grouped = getattr(st, 'groups', None) is not None
     if init:
         if not grouped:
@@ -828,13 +915,17 @@ def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, group
             else:
                 na.law = noise
         with torch.cuda.device(st.p.device):
-            _lib.check(_lib.lib().piml_scenario_step_mlapm_nav(
-                ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(), _ptr(st.seeds),
-                None if table else ctypes.byref(law), _ptr(law) if table else None,
-                None if grid is None else ctypes.byref(grid.desc),
-                None if wall is None or wall_table else ctypes.byref(wall), _ptr(wall) if wall_table else None,
-                ctypes.byref(nav.desc), None if na is None else ctypes.byref(na), int(frame_offset), _stream()),
-                'piml_scenario_step_mlapm_nav')
+            head = (ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(), _ptr(st.seeds),
+                    None if table else ctypes.byref(law), _ptr(law) if table else None,
+                    None if grid is None else ctypes.byref(grid.desc),
+                    None if wall is None or wall_table else ctypes.byref(wall), _ptr(wall) if wall_table else None,
+                    ctypes.byref(nav.desc))
+            tail = (None if na is None else ctypes.byref(na), int(frame_offset), _stream())
+            if nav.sight_desc is not None:
+                _lib.check(_lib.lib().piml_scenario_step_mlapm_sight(*head, ctypes.byref(nav.sight_desc), *tail),
+                           'piml_scenario_step_mlapm_sight')
+            else:
+                _lib.check(_lib.lib().piml_scenario_step_mlapm_nav(*head, *tail), 'piml_scenario_step_mlapm_nav')
             if advance:
                 st.t.add_(1)
         return

@@ -26,6 +26,8 @@ reads.
     python -m piml_amd.simulate --law mlapm --scene-plan plan.json --nav --seeds 0:32 --obstacle-stats walls.json
                                 (a floor plan -- walls as polylines, gates as segments -- routed by a static floor field)
     python -m piml_amd.simulate --law mlapm --scenario gc --nav [--nav-cell 0.25] [--nav-clearance 0.3] --out clip.npy
+    python -m piml_amd.simulate --law mlapm --scene-plan plan.json --nav --nav-sight --out clip.npy
+                                (the same, steering along lines of sight: the field's any-angle table)
 
 Model flags (--model, --hidden sizes, --topk_*, --num_history_velocity, ...) are those of `piml_amd.main`, with its
 defaults.  Without --checkpoint the network keeps its initial weights (a smoke run)."""
@@ -77,6 +79,9 @@ def get_args(argv=None):
     p.add_argument('--nav-cell', dest='nav_cell', type=float, default=None, help='--nav: the grid cell in metres (default 0.25)')
     p.add_argument('--nav-clearance', dest='nav_clearance', type=float, default=None,
                    help='--nav: a cell is blocked when an obstacle point lies within this many metres of its centre (default 0.3)')
+    p.add_argument('--nav-sight', dest='nav_sight', action='store_true',
+                   help='--nav: also build the any-angle table (ops_scenario.nav_field(sight=True)); the agents steer along '
+                        'lines of sight, at the next turning point of their shortest path, instead of down the gradient')
     p.add_argument('--frames', type=int, default=750)
     seed = p.add_mutually_exclusive_group()
     seed.add_argument('--seed', type=int, default=0, help='seed of the spawn schedule')
@@ -200,6 +205,8 @@ def get_args(argv=None):
             p.error(f'--nav-cell / --nav-clearance: finite values > 0 expected, got {own.nav_cell}, {own.nav_clearance}')
     elif own.nav_cell is not None or own.nav_clearance is not None:
         p.error('--nav-cell / --nav-clearance need --nav')
+    elif own.nav_sight:
+        p.error('--nav-sight needs --nav (it adds the any-angle table to the floor field)')
     if own.params_sweep is not None:
         if own.params is not None:
             p.error('--params-sweep takes the place of --params: not both')
@@ -352,11 +359,13 @@ def main(argv=None):
         scenario = dataclasses.replace(scenario, route_max_iters=0)       # (GC: the field routes, not the pillar's detour)
         try:
             run_kw['nav'] = ops_scenario.nav_field(scenario.to(args.device), cell=own.nav_cell, clearance=own.nav_clearance,
-                                                   device=args.device)
+                                                   device=args.device, sight=own.nav_sight)
         except (ValueError, RuntimeError) as ex:
             sys.exit(f'--nav: {ex}')
         print(f'[simulate] floor field: {run_kw["nav"].G} gates, {run_kw["nav"].gx} x {run_kw["nav"].gy} cells of '
               f'{run_kw["nav"].cell:g} m, {run_kw["nav"].iterations} steps')
+        if own.nav_sight:
+            print(f'[simulate] lines of sight: {run_kw["nav"].sight_iterations} steps')
     if own.law == 'mlapm' and own.mlapm_sweep is not None:
         return _sweep(sim, scenario, own, run_kw)
     if own.seeds is not None:
