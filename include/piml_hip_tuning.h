@@ -96,6 +96,22 @@ int piml_encoder_sums_dec_slots(int on);
  * follows the pointers it is given; this switch is what piml_amd.ops asks before it sets them.  Environment at load time:
  * PIML_ENC_COMPACT=0 / 1.  Returns the previous value; < 0 only queries. */
 int piml_encoder_compact_rows(int on);
+/* Where a deferred weight pack (PIML_DEFER_PACK of piml_pinnsf_pack) rides in the next relative-feature forward launch; the packed
+ * images are bitwise the same either way.  0 (default) = TRAILING: its blocks are extra workgroups behind the search's; 1 = TAIL: in a
+ * split launch (pedestrian and obstacle passes in different workgroups) the obstacle workgroups run the blocks behind their own rows
+ * -- no extra workgroups; launches that are not split keep TRAILING.  TAIL is slower at every measured shape
+ * (profiles/r13_pack_placement.md) and is kept for A/B timings and the tests.  Environment at load time: PIML_RELFEAT_PACK_FORM=0 / 1.
+ * Returns the previous value; other arguments only query. */
+int piml_relfeat_pack_form(int form);
+/* Diagnostic (tests, tools): the form a split launch with `obstacle_workgroups` workgroups of `waves` (4 / 8 / 16) waves takes under
+ * `form` (1 = TAIL, 0 = TRAILING, < 0 = bad arguments) for a pack of `nbr` branches (with / without head, fold, the f32 fragment
+ * images); *pack_blocks = the pack's block count at waves * 64 threads, *share = the largest number of blocks one obstacle workgroup
+ * runs under TAIL (either may be NULL). */
+int piml_relfeat_pack_plan(int form, int waves, int obstacle_workgroups, int nbr, int has_head, int has_fold, int skip_f32,
+                           int* pack_blocks, int* share);
+/* Diagnostic: the pack blocks TAIL gives obstacle workgroup `b` of `nb` out of `total`, in the order it runs them (the stride
+ * functions the kernel uses).  Returns their number (< 0: bad arguments); the first `cap` are written to `out` (may be NULL). */
+int piml_relfeat_pack_tail_blocks(int b, int nb, int total, int* out, int cap);
 /* The library-owned side streams of PIML_FORK (piml_pinnsf_fwd / bwd with the independent stages forked: measured slower inside
  * captured graphs, kept for A/B): created per device on first use, outside any capture; idempotent. */
 int piml_pinnsf_streams_init(void);

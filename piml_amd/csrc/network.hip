@@ -83,7 +83,7 @@ int edge(hipStream_t from, hipStream_t to, hipEvent_t ev) {
 // ---- one launch for every weight image of the network: blockIdx.y = encoder branches, decoder branches, head (reduce.hpp) ----
 __global__ __launch_bounds__(256) void pinnsf_pack_kernel(PackAll A) {
     __shared__ double red[256];
-    pack_block(A, (int)blockIdx.x, 256, red);
+    pack_block(A, (int)blockIdx.x, 256, red, (int)threadIdx.x);
 }
 
 int launch_pack(const PackAll& A, hipStream_t s) {

@@ -178,8 +178,8 @@ __host__ __device__ inline int fold_blocks(const PackAll& A, int threads) {
 }
 // workgroup fb of fold_blocks(A, threads); red: threads doubles of LDS.  EVERY thread of the workgroup must call it (barrier).
 template <int CH>
-__device__ __forceinline__ void fold_block(const PackAll& A, int fb, int threads, double* red) {
-    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+__device__ __forceinline__ void fold_block(const PackAll& A, int fb, int threads, double* red, int tid) {
+    const int wave = tid >> 6, lane = tid & 63;
     const int grp = fb * ((threads >> 6) / CH) + wave / CH, chunk = wave % CH;
     const int f = grp / FOLD_GROUPS, r = grp - f * FOLD_GROUPS, i = r / 3, hc = r - 3 * i;
     const bool live = f < fold_sets(A);
@@ -192,33 +192,46 @@ __device__ __forceinline__ void fold_block(const PackAll& A, int fb, int threads
     double part = 0.0;
     if (have && (hc < 2 || lane == 0))
         part = fold_partial<CH>(w1 + (size_t)i * DH, hc < 2 ? w3 + 64 * hc + lane : b3, hc < 2 ? EH : 1, chunk);
-    red[threadIdx.x] = part;
+    red[tid] = part;
     __syncthreads();
     if (have && chunk == 0) {
         double sum = 0.0;
 #pragma unroll
-        for (int c = 0; c < CH; ++c) sum += red[threadIdx.x + 64 * c];
+        for (int c = 0; c < CH; ++c) sum += red[tid + 64 * c];
         if (is_head) head_fold_store(A.head, i, hc, lane, sum);
         else dec_fold_store(J, i, hc, lane, sum);
     }
 }
-// the pack as trailing workgroups of another launch: `threads` threads per workgroup, kPackPerThread elements per thread (a
-// thread's elements are `threads` apart: coalesced stores, independent gathers in flight together; fewer, fatter workgroups
-// -- 1 100 workgroups of one element per thread cost the relfeat forward 4 us of tail), then the fold workgroups
+// the pack inside another launch, cut into "pack blocks" of `threads` threads, kPackPerThread elements per thread (a
+// thread's elements are `threads` apart: coalesced stores, independent gathers in flight together; fewer, fatter blocks
+// -- 1 100 workgroups of one element per thread cost the relfeat forward 4 us of tail), then the fold blocks.  Two forms carry
+// them (relfeat.hip: relfeat_go; piml_relfeat_pack_form selects, TRAILING is the default and the faster one at every measured shape):
+//   TRAILING  every pack block is a workgroup of its own behind the launch's search workgroups (first_block >= 0).  A CU takes one
+//             only when a search workgroup has left it -- whichever CU is free first, which balances the launch's tail;
+//   TAIL      split launches only: obstacle workgroup b of nb -- the short half of the grid -- runs pack blocks b, b + nb, ...
+//             behind the epilogue of its own rows and a workgroup barrier per block (tail_stride = nb > 0, no extra workgroups):
+//             a fixed share per workgroup, kept for A/B and the tests (profiles/r13_pack_placement.md).
+// Same block decomposition, thread count and arithmetic either way: the images are bitwise the same.
 constexpr int kPackPerThread = 4;
 struct PackWork {
     PackAll A;
-    int first_block;          // blockIdx.x of the first pack workgroup; < 0: no pack rides in this launch
+    int first_block;          // TRAILING: blockIdx.x of the first pack workgroup; < 0: the launch has no pack workgroups
+    int tail_stride;          // TAIL: the number of obstacle workgroups, each takes every tail_stride-th pack block; 0: not this form
 };
+// TAIL: the pack blocks of obstacle workgroup b of nb are pack_tail_first(b), + pack_tail_stride(nb), ... below the total -- every
+// block exactly once over b = 0 .. nb - 1; pack_tail_share is the longest such chain
+__host__ __device__ inline int pack_tail_first(int b) { return b; }
+__host__ __device__ inline int pack_tail_stride(int nb) { return nb; }
+__host__ __device__ inline int pack_tail_share(int nb, int total) { return nb > 0 ? (total + nb - 1) / nb : total; }
 __host__ __device__ inline int pack_plain_blocks(const PackAll& A, int threads) {
     return (pack_elems_total(A) + threads * kPackPerThread - 1) / (threads * kPackPerThread);
 }
 // the zero-row constants of encoder branch y (pack.hpp: PACK_ZROW), one workgroup each: thread (feature j, part p of threads / 128)
 // sums 128 / parts terms of W2[j] . relu(b1) in float64, sixteen loads in flight; the parts meet in LDS in order.  The whole
 // workgroup calls it (barrier); red: `threads` doubles
-__device__ __forceinline__ void zrow_block(const PackAll& A, int y, int threads, double* red) {
+__device__ __forceinline__ void zrow_block(const PackAll& A, int y, int threads, double* red, int tid) {
     const piml_encoder_branch& J = A.enc[y];
-    const int t = (int)threadIdx.x, parts = threads >= 512 ? 4 : 2, per = EH / parts;
+    const int t = tid, parts = threads >= 512 ? 4 : 2, per = EH / parts;
     double part = 0.0;
     if (t < parts * EH) {
         const int j = t & (EH - 1), p = t >> 7;
@@ -242,22 +255,24 @@ __device__ __forceinline__ void zrow_block(const PackAll& A, int y, int threads,
     }
 }
 __host__ __device__ inline int pack_blocks_total(const PackAll& A, int threads) { return pack_plain_blocks(A, threads) + fold_blocks(A, threads) + A.nbr; }
-// red: `threads` doubles of LDS (the folded images' partial sums); the whole workgroup calls this
-__device__ __forceinline__ void pack_block(const PackAll& A, int bid, int threads, double* red) {
+// red: `threads` doubles of LDS (the folded images' partial sums); the whole workgroup calls this.  tid: the caller's threadIdx.x (a
+// caller that runs several blocks in a loop hands over a copy the compiler cannot see through, so that a block's per-thread address
+// arithmetic is not hoisted out of the loop and held in registers: relfeat_fwd_kernel)
+__device__ __forceinline__ void pack_block(const PackAll& A, int bid, int threads, double* red, int tid) {
     const int plain = pack_plain_blocks(A, threads);
     if (bid < plain) {
         const int total = pack_elems_total(A);
 #pragma unroll
         for (int j = 0; j < kPackPerThread; ++j) {
-            const int t = (bid * kPackPerThread + j) * threads + (int)threadIdx.x;
+            const int t = (bid * kPackPerThread + j) * threads + tid;
             if (t < total) pack_flat(A, t);
         }
     } else if (bid >= plain + fold_blocks(A, threads)) {
-        zrow_block(A, bid - plain - fold_blocks(A, threads), threads, red);
+        zrow_block(A, bid - plain - fold_blocks(A, threads), threads, red, tid);
     } else if (threads >= 512) {
-        fold_block<8>(A, bid - plain, threads, red);
+        fold_block<8>(A, bid - plain, threads, red, tid);
     } else {
-        fold_block<4>(A, bid - plain, threads, red);
+        fold_block<4>(A, bid - plain, threads, red, tid);
     }
 }
 int launch_pack(const PackAll& A, hipStream_t s);

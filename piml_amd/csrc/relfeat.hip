@@ -50,7 +50,8 @@ struct RelfeatArgs {
     float* zero; long zero_n;   // optional: buffer this launch clears (the state gradient its backward accumulates into)
     long long* tick;            // optional: device-side frame counter this launch advances by one (it does not read it)
     int* stats;   // PIML_RELFEAT_STATS builds only: per focal row {evals, drain rounds, insertions, candidates,
-                  // 7 phase stamps (cycles): entry, [tile staged, pass done] per pass ..., + 1 pad}
+                  // 5 phase stamps (cycles since entry): entry, [tile staged, pass done] per pass ..., entry and end of the passes on the
+                  // device's 100 MHz clock, XCC id}; behind 2 * C * fcnt such records, 4 ints per pack block of a deferred pack (stat_pack_block)
 };
 
 constexpr int kRfPedFeat = 1;    // write pedestrian features + indices
@@ -167,13 +168,45 @@ constexpr int relfeat_lds_bytes() { return (2 * kTile + WAVES * kRing / 2 + (RES
 // behind a workgroup barrier, i.e. all 16 waves wait for the slowest pedestrian pass before the obstacle pass can start:
 // measured at the 4096-agent scene (in-kernel stamps, tools/relfeat_stats.py) a median wave spent 7.5 k of its 32.6 k cycles
 // in that wait (per-row work is data dependent: 18 k median, 26 k max for the pedestrian pass).
+#ifdef PIML_RELFEAT_STATS
+// PIML_RELFEAT_STATS builds: pack block pb leaves {start, end (s_memrealtime, low 32 bits), its length in s_memtime ticks, blockIdx.x}
+// behind the rows' records (a split launch has 2 * C * fcnt of those); a row's record carries its wave's entry and pass end the same
+// way.  s_memtime counts per CU and is good for lengths only; the 100 MHz s_memrealtime is one clock for the device, which is what
+// sets workgroups on different CUs side by side
+__device__ __forceinline__ int stat_xcc() {
+    int id;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(id));
+    return id & 15;
+}
+__device__ __forceinline__ void stat_pack_block(const RelfeatArgs& A, int pb, unsigned long long t0, unsigned long long rt0) {
+    if (A.stats && threadIdx.x == 0) {
+        int* o = A.stats + (size_t)2 * A.C * A.fcnt * 12 + (size_t)pb * 4;
+        o[0] = (int)(unsigned)rt0; o[1] = (int)(unsigned)__builtin_amdgcn_s_memrealtime();
+        o[2] = (int)(__builtin_amdgcn_s_memtime() - t0); o[3] = (int)blockIdx.x;
+    }
+}
+#endif
+
+// (amdgpu_waves_per_eu: the search needs 67 - 72 registers = 7 waves a SIMD.  The pack loop at the kernel's end needs a few more in
+// one place, and once the seventh wave is out of reach the scheduler spends registers freely everywhere -- 108 / 113 / 161 for 16 / 8
+// / 4 waves without the bound, i.e. one workgroup less per CU for the eight- and four-wave forms.  With it 72 / 72 / 110, no
+// spill: the four-wave form keeps the four workgroups per CU its 40 KB of LDS allow anyway.)
 template <int WAVES, bool RES>
-__global__ __launch_bounds__(WAVES * 64) void relfeat_fwd_kernel(const RelfeatArgs A, const PackWork PK) {
-    // a deferred weight pack (PIML_DEFER_PACK, reduce.hpp) rides as the launch's trailing workgroups: they reach a CU when
-    // the short obstacle workgroups have left, under the tail of the pedestrian passes
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(RES ? 1 : (WAVES == 4 ? 4 : 7)))) void relfeat_fwd_kernel(const RelfeatArgs A, const PackWork PK) {
+    // a deferred weight pack (PIML_DEFER_PACK, reduce.hpp) rides in this launch in one of two forms.  TRAILING (here): its blocks are
+    // the launch's last workgroups, which reach a CU when a search workgroup has left it.  TAIL (the end of this kernel; split
+    // launches): the obstacle workgroups -- whose pass is a fraction of the pedestrian pass -- run the blocks behind their own rows,
+    // with no dispatch of their own.  Measured, TAIL is the slower one at every shape (a fixed share per workgroup against
+    // "whichever CU is free first"); it is selectable for A/B and the tests, and the launcher keeps TRAILING (relfeat_go)
     extern __shared__ __attribute__((aligned(16))) float rf_lds[];
     if (PK.first_block >= 0 && (int)blockIdx.x >= PK.first_block) {
-        pack_block(PK.A, (int)blockIdx.x - PK.first_block, WAVES * 64, reinterpret_cast<double*>(rf_lds));
+#ifdef PIML_RELFEAT_STATS
+        const unsigned long long pk_t0 = __builtin_amdgcn_s_memtime(), pk_rt0 = __builtin_amdgcn_s_memrealtime();
+#endif
+        pack_block(PK.A, (int)blockIdx.x - PK.first_block, WAVES * 64, reinterpret_cast<double*>(rf_lds), (int)threadIdx.x);
+#ifdef PIML_RELFEAT_STATS
+        stat_pack_block(A, (int)blockIdx.x - PK.first_block, pk_t0, pk_rt0);
+#endif
         return;
     }
     // source tiles, structure-of-arrays so that a lane fetches 4 consecutive points per
@@ -198,6 +231,8 @@ __global__ __launch_bounds__(WAVES * 64) void relfeat_fwd_kernel(const RelfeatAr
     // split launch: workgroups [0, C * bpc) run the pedestrian pass of their rows, [C * bpc, 2 C * bpc) the obstacle pass of the
     // same rows -- a row's two passes are independent, and a launch of a few thousand rows is bound by the LATENCY of a row (a
     // chain of dependent drains), not by issue slots: side by side the chain is one pass long instead of two
+    // (side by side on a CU for 4- and 8-wave workgroups; a 16-wave workgroup has a CU to itself at this kernel's 7 waves a SIMD, and
+    // its obstacle workgroups follow the pedestrian ones onto the CUs as those leave: profiles/r13_pack_placement.md)
     const int nb = A.C * bpc;
     const int kind = (!RES && A.split) ? ((int)blockIdx.x >= nb ? 2 : 1) : 0;
     const int bid = (int)blockIdx.x - (kind == 2 ? nb : 0);
@@ -238,6 +273,7 @@ __global__ __launch_bounds__(WAVES * 64) void relfeat_fwd_kernel(const RelfeatAr
     unsigned long long st_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int st_n = 0;
     st_t[st_n++] = __builtin_amdgcn_s_memtime();
+    const unsigned long long st_rt0 = __builtin_amdgcn_s_memrealtime();
 #define PIML_STAT(x) x
 #else
 #define PIML_STAT(x)
@@ -410,16 +446,41 @@ __global__ __launch_bounds__(WAVES * 64) void relfeat_fwd_kernel(const RelfeatAr
         if (pass == 0) lists[0] = mine; else lists[1] = mine;
     }
 
-    if (!has) return;
+    // (a wave without a row writes nothing but stays: the barriers below need every wave of the workgroup)
+    if (has) {
 #ifdef PIML_RELFEAT_STATS
-    if (A.stats && lane == 0) {
-        int* o = A.stats + ((size_t)c * A.fcnt + fl + (kind == 2 ? (size_t)A.C * A.fcnt : 0)) * 12;   // (split: the obstacle workgroups' rows behind the others)
-        o[0] = st_evals; o[1] = st_rounds; o[2] = st_ins; o[3] = st_cand;
-        for (int q = 0; q < 7; ++q) o[4 + q] = (int)(st_t[q] - st_t[0]);   // cycles since kernel entry of this wave
-    }
+        if (A.stats && lane == 0) {
+            int* o = A.stats + ((size_t)c * A.fcnt + fl + (kind == 2 ? (size_t)A.C * A.fcnt : 0)) * 12;   // (split: the obstacle workgroups' rows behind the others)
+            o[0] = st_evals; o[1] = st_rounds; o[2] = st_ins; o[3] = st_cand;
+            for (int q = 0; q < 5; ++q) o[4 + q] = (int)(st_t[q] - st_t[0]);   // cycles since kernel entry of this wave
+            o[9] = (int)(unsigned)st_rt0; o[10] = (int)(unsigned)__builtin_amdgcn_s_memrealtime();      // entry, passes done: the device's clock
+            o[11] = stat_xcc();
+        }
 #endif
+        relfeat_epilogue(A, flags, c, fl, lane, lists, pix, piy, vix, viy, aix, aiy, vi2, ai2);
+    }
 
-    relfeat_epilogue(A, flags, c, fl, lane, lists, pix, piy, vix, viy, aix, aiy, vi2, ai2);
+    // TAIL form of the deferred pack: obstacle workgroup `bid` of nb takes pack blocks bid, bid + nb, ...  Everything the loop and
+    // pack_block branch on (kind, bid, nb, the block count) is uniform over the workgroup, and no wave has left above, so every
+    // wave meets every barrier.  The barrier in front of a block is what lets pack_block's partial sums overlay the obstacle tile
+    // (all waves are done reading it) and, from the second block on, the previous block's sums (all waves are done reading those).
+    // Nothing in this launch reads the images; the launch boundary publishes them, as for the trailing form.
+    if (!RES && kind == 2 && PK.tail_stride > 0) {
+        const int total = pack_blocks_total(PK.A, WAVES * 64);
+#pragma unroll 1
+        for (int pb = pack_tail_first(bid); pb < total; pb += pack_tail_stride(PK.tail_stride)) {
+            __syncthreads();
+#ifdef PIML_RELFEAT_STATS
+            const unsigned long long pk_t0 = __builtin_amdgcn_s_memtime(), pk_rt0 = __builtin_amdgcn_s_memrealtime();
+#endif
+            int tid = (int)threadIdx.x;
+            asm volatile("" : "+v"(tid));       // opaque per trip: nothing of a block's per-thread arithmetic is carried round the loop
+            pack_block(PK.A, pb, WAVES * 64, reinterpret_cast<double*>(rf_lds), tid);
+#ifdef PIML_RELFEAT_STATS
+            stat_pack_block(A, pb, pk_t0, pk_rt0);
+#endif
+        }
+    }
 }
 
 // One wavefront per focal row; lane = slot * 8 + component (components 6, 7 idle), so a
@@ -623,16 +684,63 @@ static float dist2_cutoff(float thr) {
 
 using namespace piml;
 
+// Which form carries a deferred pack (reduce.hpp: PackWork): 0 (default) = TRAILING, 1 = TAIL in every split launch (non-split and
+// resident launches have no obstacle workgroups: TRAILING).  TAIL is kept for A/B and the tests only: measured it LOSES at every
+// shape (profiles/r13_pack_placement.md: 27.3 against 22.9 us at the 4096-agent scene, 20.9 against 9.3 at 1024 agents) -- a
+// 16-wave search workgroup has a CU to itself (67 registers: 7 waves a SIMD), so the obstacle workgroups do not run beside the
+// pedestrian ones but behind them, and the trailing blocks go to whichever CU is free first, which a fixed share cannot match.
+// Environment at load time: PIML_RELFEAT_PACK_FORM=0 / 1.
+static int g_pack_form = getenv("PIML_RELFEAT_PACK_FORM") ? atoi(getenv("PIML_RELFEAT_PACK_FORM")) == 1 : 0;
+
+static bool pack_takes_tail(int form, bool split, int obstacle_workgroups) { return form == 1 && split && obstacle_workgroups > 0; }
+
+// pack: the deferred pack this launch carries (relfeat_launch took it off the stream), or NULL
 template <int W, bool R>
-static void relfeat_go(dim3 grid, dim3 block, void* stream, const RelfeatArgs& A, bool forward_of_a_step = false) {
+static void relfeat_go(dim3 grid, dim3 block, void* stream, const RelfeatArgs& A, const PackAll* pack) {
     constexpr int bytes = relfeat_lds_bytes<W, R>();
     PackWork PK;
     PK.first_block = -1;
-    if (forward_of_a_step && pending_pack_take(as_stream(stream), &PK.A)) {     // a pack left by piml_pinnsf_pack(PIML_DEFER_PACK)
-        PK.first_block = (int)grid.x;
-        grid.x += (unsigned)pack_blocks_total(PK.A, W * 64);
+    PK.tail_stride = 0;
+    if (pack) {
+        PK.A = *pack;
+        const int blocks = pack_blocks_total(PK.A, W * 64), nb = (int)grid.x / 2;     // (split: pedestrian | obstacle workgroups)
+        if (pack_takes_tail(g_pack_form, !R && A.split, nb)) {
+            PK.tail_stride = nb;
+        } else {
+            PK.first_block = (int)grid.x;
+            grid.x += (unsigned)blocks;
+        }
     }
     relfeat_fwd_kernel<W, R><<<grid, block, bytes, as_stream(stream)>>>(A, PK);
+}
+
+PIML_API int piml_relfeat_pack_form(int form) {
+    const int old = g_pack_form;
+    if (form == 0 || form == 1) g_pack_form = form;
+    return old;
+}
+
+// Diagnostic (tests, tools): the form a split launch of `obstacle_workgroups` workgroups of `waves` waves gives a deferred pack of
+// this shape under `form` (1 = TAIL, 0 = TRAILING); *pack_blocks = its block count, *share = the longest per-workgroup chain of TAIL
+PIML_API int piml_relfeat_pack_plan(int form, int waves, int obstacle_workgroups, int nbr, int has_head, int has_fold, int skip_f32,
+                                    int* pack_blocks, int* share) {
+    if ((waves != 4 && waves != 8 && waves != 16) || nbr < 0 || nbr > 2 || form < 0 || form > 1) return -1;
+    PackAll P{};
+    P.nbr = nbr; P.has_head = has_head != 0; P.has_fold = has_fold != 0; P.skip_f32 = skip_f32 != 0;
+    const int blocks = pack_blocks_total(P, waves * 64);
+    if (pack_blocks) *pack_blocks = blocks;
+    if (share) *share = pack_tail_share(obstacle_workgroups, blocks);
+    return pack_takes_tail(form, true, obstacle_workgroups) ? 1 : 0;
+}
+
+// Diagnostic: the pack blocks TAIL gives obstacle workgroup b of nb, in the order it runs them (the kernel's own stride functions);
+// returns their number, the first `cap` of them in `out`
+PIML_API int piml_relfeat_pack_tail_blocks(int b, int nb, int total, int* out, int cap) {
+    if (b < 0 || nb <= 0 || b >= nb || total < 0) return -1;
+    int n = 0;
+    for (int pb = pack_tail_first(b); pb < total; pb += pack_tail_stride(nb), ++n)
+        if (out && n < cap) out[n] = pb;
+    return n;
 }
 template <int W>
 static int relfeat_attr() {
@@ -692,7 +800,21 @@ static int relfeat_launch(const float* position, const float* heading, const flo
     // -- round 6, tools/time_sharded_shapes.py: 4096 focal rows x 8192 / 16384 / 32768 sources 26.4 / 36.5 / 57.7 us against
     // 29.1 / 40.3 / 59.1 with sixteen (and 32.5 / 45.5 / 67.9 with four); 2048 x 16384: 29.7 / 32.8 / 34.0
     if (N > kTile && rows >= 1024) waves = 8;
+    // a pack left by piml_pinnsf_pack(PIML_DEFER_PACK) rides in this launch.  Where the search alone wants sixteen waves it takes
+    // eight with a pack on board: a 16-wave workgroup has a CU to itself (67 registers: 7 waves a SIMD), so every pack block waits
+    // for a whole search workgroup to leave; three 8-wave workgroups share a CU, and the pack's 512-thread blocks run beside the
+    // searches -- 22.9 -> 20.9 us for the launch at the 4096-agent scene, where the search alone is 20.3 with sixteen waves and
+    // 20.5 with eight (profiles/r13_pack_placement.md).  The images do not depend on it: 512 and 1024 threads cut the fold and the
+    // zero rows into the same partial sums.
+    PackAll pack_desc;
+    const bool has_pack = pending_pack_take(as_stream(stream), &pack_desc);
+    const PackAll* pack = has_pack ? &pack_desc : nullptr;
+    if (has_pack && waves == 16) waves = 8;
     if (const char* e = getenv("PIML_RELFEAT_WAVES")) waves = atoi(e);
+    if (waves != 4 && waves != 8 && waves != 16) {
+        if (has_pack) pending_pack_leave(pack_desc, as_stream(stream));      // (not lost: the next consumer runs it)
+        return hipErrorInvalidValue;
+    }
     const int bpc = (focal_count + waves - 1) / waves;
     const dim3 grid((unsigned)(C * bpc)), block((unsigned)(waves * 64));
     // both tiles resident (one barrier per launch) when the agent sources are one tile and the obstacle pass exists and fits
@@ -706,7 +828,10 @@ static int relfeat_launch(const float* position, const float* heading, const flo
             if (!attr) attr = relfeat_attr<8>();
             if (!attr) attr = relfeat_attr<4>();
         }
-        if (attr) return attr;
+        if (attr) {
+            if (has_pack) pending_pack_leave(pack_desc, as_stream(stream));
+            return attr;
+        }
     }
     // split launch (pedestrian and obstacle passes of a row in different workgroups): whenever the obstacle pass exists
     static const bool split_off = getenv("PIML_RELFEAT_SPLIT") && atoi(getenv("PIML_RELFEAT_SPLIT")) == 0;
@@ -717,20 +842,20 @@ static int relfeat_launch(const float* position, const float* heading, const flo
         A.split = 1;
         const dim3 grid2(grid.x * 2);
         switch (waves) {
-            case 16: relfeat_go<16, false>(grid2, block, stream, A, true); break;
-            case 8: relfeat_go<8, false>(grid2, block, stream, A, true); break;
-            case 4: relfeat_go<4, false>(grid2, block, stream, A, true); break;
+            case 16: relfeat_go<16, false>(grid2, block, stream, A, pack); break;
+            case 8: relfeat_go<8, false>(grid2, block, stream, A, pack); break;
+            case 4: relfeat_go<4, false>(grid2, block, stream, A, pack); break;
             default: return hipErrorInvalidValue;
         }
         return hipGetLastError();
     }
     switch (waves * 2 + (res ? 1 : 0)) {
-        case 33: relfeat_go<16, true>(grid, block, stream, A, true); break;
-        case 32: relfeat_go<16, false>(grid, block, stream, A, true); break;
-        case 17: relfeat_go<8, true>(grid, block, stream, A, true); break;
-        case 16: relfeat_go<8, false>(grid, block, stream, A, true); break;
-        case 9: relfeat_go<4, true>(grid, block, stream, A, true); break;
-        case 8: relfeat_go<4, false>(grid, block, stream, A, true); break;
+        case 33: relfeat_go<16, true>(grid, block, stream, A, pack); break;
+        case 32: relfeat_go<16, false>(grid, block, stream, A, pack); break;
+        case 17: relfeat_go<8, true>(grid, block, stream, A, pack); break;
+        case 16: relfeat_go<8, false>(grid, block, stream, A, pack); break;
+        case 9: relfeat_go<4, true>(grid, block, stream, A, pack); break;
+        case 8: relfeat_go<4, false>(grid, block, stream, A, pack); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
