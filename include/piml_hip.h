@@ -1371,6 +1371,33 @@ int piml_scenario_step_mlapm_sight(const piml_scenario* s, const piml_scenario_r
                                    int frame_offset, void* stream);
 
 /*
+ * The floor field under the network-driven frame (ABI 35, additive): piml_scenario_step_members' frame for a scene of gates,
+ * which also writes, per slot, the point the network should be steered to.  A PINNSF reads the destination only as a unit
+ * direction (columns 0..1 of self_features, the desired-force term), so the caller hands `steer` to the relative-feature
+ * launch in the place of the destination and the network follows the field; nothing else of its inputs changes.
+ * Buffers, r, members, a_next and init exactly as piml_scenario_step_members; seeds == NULL is the single run (members == 1,
+ * key s->seed, as piml_scenario_step).  steer (members, capacity, 2) float32, member-major as the state.
+ * With p', flag' and dest' the slot's position, flag and destination AFTER this frame's integration, arrival and retirement:
+ *   a slot that stays present:  steer = fl(p' + n.e) per component in n's branches 1, 2 (and 3), dest' in branch 0 --
+ *                               piml_scenario_step_mlapm_nav's target formula -- with n = piml_nav_direction's result (sight !=
+ *                               NULL: piml_nav_direction_sight's) for (p', gate = exit_idx[flag'], dest');
+ *   a slot that retires in this frame or was retired earlier: steer = (NaN, NaN); exit_idx is never read with flag' >= D;
+ *   a spawned agent (the init launch's too): steer from (origin, exit_idx[0], its first waypoint);
+ *   slots >= capacity and dropped ordinals: never written, as every other buffer.
+ * Position, velocity, history, arrival against the slot's destination, retirement, records, spawns and the Philox schedule
+ * are piml_scenario_step_members' bit for bit: the field moves nothing but `steer`.  One thread per slot, the lookup a gather
+ * of 13 words (14 with the table); one wave per spawned agent.  No atomics, capturable.
+ * hipErrorInvalidValue (before any launch): everything piml_scenario_step_members refuses (seeds == NULL is refused only with
+ * members != 1); everything piml_nav_direction refuses about the grid and, with sight != NULL, piml_nav_direction_sight about
+ * the table; a scene rule other than GC's (r != NULL with another spawn law); s->route_max_iters != 0; nav->G != s->E; a
+ * NULL steer.
+ */
+int piml_scenario_step_nav(const piml_scenario* s, const piml_scenario_rules* r /* NULL or GC's */, int members,
+                           const uint64_t* seeds /* NULL: members == 1, key s->seed */, const float* a_next, int init,
+                           const piml_nav_grid* nav, const piml_nav_sight* sight /* NULL: no any-angle table */,
+                           float* steer, void* stream);
+
+/*
  * utils.route (src/utils/utils.py:141-165) for n (o, d) pairs, one wave each, the device function the spawn path uses:
  * the segment o -> r is tested against the polyline's R-1 segments, the hit with the smallest alpha moves r to
  * crossing + clearance * normal, until nothing is hit or max_iters moves were made.  float32 in the reference's order.

@@ -211,6 +211,7 @@ SIGNATURES = {
     'piml_nav_sight_relax': [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
     'piml_nav_direction_sight': [_p, _p, _p, _ll, _p, _p, _p, _p, _p, _p],
     'piml_scenario_step_mlapm_sight': [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
+    'piml_scenario_step_nav': [_p, _p, _i, _p, _p, _i, _p, _p, _p, _p],
     'piml_scenario_route': [_p, _p, _i, _p, _i, _i, _f, _p, _p, _p],
     'piml_collision_correction_fwd': [_p, _p, _p, _z, _i, _i, _f, _f, _p, _p],
     'piml_collision_correction_bwd': [_p, _p, _p, _p, _z, _i, _i, _f, _f, _p, _p, _p, _p],

@@ -6,7 +6,8 @@
 //
 // Every network-driven entry (piml_scenario_step, piml_scenario_step_rules, piml_scenario_step_members) launches the one
 // frame kernel, scenario_frame_kernel<kGC>: kGC is GC's rule (entry points, route, exit distance), otherwise a scene rule of
-// piml_scenario_rules.  Grid (agent blocks + spawn blocks, members): a single run is one member whose Philox key is S.seed,
+// piml_scenario_rules.  piml_scenario_step_nav launches the same body as scenario_frame_nav_kernel<kSight>: GC's frame, which
+// also writes every slot's steering target from the floor field of nav.hpp (kNav in agent_step and spawn_block).  Grid (agent blocks + spawn blocks, members): a single run is one member whose Philox key is S.seed,
 // member m of an ensemble has key seeds[m] (member_view below).
 // Frame t -> t+1 (init == 0):
 //   agents   (one thread per slot i < min(n_t, capacity), n_t = agents spawned through frame t)
@@ -253,9 +254,15 @@ __device__ __forceinline__ int rules_arrive(const piml_scenario& S, const piml_s
     return f;
 }
 
+// what agent_retire_record left in slot i: whether it is still present, and its destination (NaN when not)
+struct SlotAfter {
+    bool present;
+    float2 dest;
+};
+
 // 3. retire (data.py:236-247) with the flag f after step 2 (gone: the rule retired the agent itself), then slot i's state
 // and frame t+1's record
-__device__ __forceinline__ void agent_retire_record(const piml_scenario& S, int i, long long t, int f, bool gone, float2 pn,
+__device__ __forceinline__ SlotAfter agent_retire_record(const piml_scenario& S, int i, long long t, int f, bool gone, float2 pn,
                                                     float2 vn, float2 an) {
     const long long tn = t + 1;
     const bool rec = tn < S.T;
@@ -285,14 +292,35 @@ __device__ __forceinline__ void agent_retire_record(const piml_scenario& S, int 
         ((float2*)S.destination_out)[fr] = dn;
         S.mask_out[fr] = m;
     }
+    return SlotAfter{!gone, dn};
 }
 
-// steps 1-3 and the record of slot i (member view S, the network's a_next); entries: GC's entry points (LDS or global)
-template <bool kGC>
+// The routed frame's arguments (piml_scenario_step_nav): the floor field, its any-angle table (read with kSight only) and
+// the steering targets it writes, (members, capacity, 2); member_view's layout.
+struct SteerArgs {
+    piml_nav_grid NV;
+    const int* parent;
+    float2* steer;
+};
+
+// the steering target of an agent at p bound for dest through `gate`: one metre down the field in the lookup's branches 1, 2
+// and 3, the destination in branch 0 (scenario_mlapm_body's kNav formula).  One thread per agent here, one wave there: the
+// lookup has no cross-lane operation.
+template <bool kSight>
+__device__ __forceinline__ float2 steer_target(const SteerArgs& A, int gate, float2 p, float2 dest) {
+    const NavDir nd = nav_direction<kSight>(A.NV, gate, p, dest, A.parent);
+    return make_float2(nd.branch ? __fadd_rn(p.x, nd.e.x) : dest.x, nd.branch ? __fadd_rn(p.y, nd.e.y) : dest.y);
+}
+
+// steps 1-3 and the record of slot i (member view S, the network's a_next); entries: GC's entry points (LDS or global).
+// kNav: then slot i's steering target, from what step 3 left -- the lookup for a slot that stays present (its flag is < D),
+// NaN for one that retires now or was retired earlier.  kNav == false reads neither the field nor steer.
+template <bool kGC, bool kNav = false, bool kSight = false>
 __device__ __forceinline__ void agent_step(const piml_scenario& S, const piml_scenario_rules& R, const float2* a_next,
-                                           const float2* entries, int i, long long t) {
+                                           const float2* entries, int i, long long t, const SteerArgs* A = nullptr) {
     if (S.mask[i] == 0.f) {                                  // retired for good
         record_retired(S, i, t);
+        if constexpr (kNav) A->steer[i] = make_float2(qnan(), qnan());
         return;
     }
     const float dt = S.dt;
@@ -314,7 +342,12 @@ __device__ __forceinline__ void agent_step(const piml_scenario& S, const piml_sc
     } else {
         fn = rules_arrive(S, R, f, pn, d, gone);
     }
-    agent_retire_record(S, i, t, fn, gone, pn, vn, an);      // 3. retire (data.py:236-247)
+    const SlotAfter after = agent_retire_record(S, i, t, fn, gone, pn, vn, an);   // 3. retire (data.py:236-247)
+    if constexpr (kNav) {
+        float2 target = make_float2(qnan(), qnan());
+        if (after.present) target = steer_target<kSight>(*A, S.exit_idx[(size_t)fn * S.capacity + i], pn, after.dest);
+        A->steer[i] = target;
+    }
 }
 
 // one wave: agent of ordinal `ord` (< capacity) appears in frame `f`
@@ -596,8 +629,12 @@ __device__ __forceinline__ void group_spawn_block(const piml_scenario& S, const 
 // stream 0x5CE0; a scene rule (the clip law too): k1 + k2 of stream 0x5CE1 --, its bookkeeping by one thread of block 0,
 // then one wave per new agent of ordinal n + j.  thr / R are the kernel arguments' (an indexed read of a local copy's table
 // would put the whole descriptor in scratch); ent: GC's entry points (LDS or global).
+// kNav (GC only): lane 0 of the new agent's wave then writes its steering target from what it has just written itself --
+// the origin, exit_idx[0] and the first waypoint.  kNav == false reads neither the field nor steer.
+template <bool kNav = false, bool kSight = false>
 __device__ __forceinline__ void spawn_block(bool gc, const piml_scenario& S, const piml_scenario_rules& R, const uint32_t* thr,
-                                            const float2* ent, int init, long long n, long long f, int b) {
+                                            const float2* ent, int init, long long n, long long f, int b,
+                                            const SteerArgs* A = nullptr) {
     int k1 = S.n_initial, k2 = 0;
     if (!init) {
         const PhiloxOut w = philox4x32_10((unsigned)f, (unsigned)((unsigned long long)f >> 32), 0u,
@@ -616,6 +653,12 @@ __device__ __forceinline__ void spawn_block(bool gc, const piml_scenario& S, con
     if (gc) spawn_agent(S, ent, n + j, f);
     else if (R.spawn_law == PIML_SPAWN_CLIP) clip_spawn_agent(S, R, init, n + j, f);
     else rules_spawn_agent(S, R, n + j, j >= k1, f);
+    if constexpr (kNav) {
+        if (lane_id() == 0) {                                // the lane that wrote them (flag 0: exit_idx row 0)
+            const size_t i = (size_t)(n + j);
+            A->steer[i] = steer_target<kSight>(*A, S.exit_idx[i], ((const float2*)S.position)[i], ((const float2*)S.destination)[i]);
+        }
+    }
 }
 
 // member m's view of the descriptor (the file header's layout); member 0's pointers are the bases
@@ -701,6 +744,39 @@ __global__ __launch_bounds__(256) void scenario_frame_kernel(const FrameArgs K0,
         return;
     }
     spawn_block(kGC, S, K0.R, K0.S.poisson_thresholds, ent, K0.init, n, f, (int)blockIdx.x - K0.agent_blocks);
+}
+
+// The frame routed by the floor field (piml_scenario_step_nav): scenario_frame_kernel<true>'s grid and steps -- GC's frame, bit
+// for bit -- with kNav in agent_step and spawn_block, so every slot the launch writes also gets its steering target: one
+// lookup of nav.hpp per slot that stays present, one per spawned agent.  kSight: the lookup with the any-angle table
+// (nav_direction<true>, branch 3).  A kernel of its own and not a third form of the one above: handing that kernel's body its
+// arguments by reference changed the instructions of the two existing kernels.
+template <bool kSight>
+__global__ __launch_bounds__(256) void scenario_frame_nav_kernel(const FrameArgs K0, const unsigned long long* __restrict__ seeds,
+                                                                 const SteerArgs A0) {
+    __shared__ float2 lds_entries[kScenarioLdsPoints];
+    piml_scenario S = K0.S;
+    const float2* a_next = K0.a_next;
+    member_view(S, a_next, (int)blockIdx.y);
+    SteerArgs A = A0;
+    A.steer += (size_t)blockIdx.y * (size_t)S.capacity;      // member_view's layout
+    if (seeds) S.seed = seeds[blockIdx.y];
+    const float2* ent = (const float2*)S.entries;
+    const bool lds = S.E * S.P <= kScenarioLdsPoints;        // kernel-uniform: every block stages the entry points
+    if (lds) {
+        for (int q = threadIdx.x; q < S.E * S.P; q += blockDim.x) lds_entries[q] = ent[q];
+        __syncthreads();
+        ent = lds_entries;
+    }
+    const long long t = *S.frame_counter;
+    const long long n = K0.init ? 0 : S.spawned[t & 1];
+    const long long f = K0.init ? t : t + 1;                 // the frame the new agents appear in
+    if ((int)blockIdx.x < K0.agent_blocks) {
+        const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < n && i < S.capacity) agent_step<true, true, kSight>(S, K0.R, a_next, ent, (int)i, t, &A);
+        return;
+    }
+    spawn_block<true, kSight>(true, S, K0.R, K0.S.poisson_thresholds, ent, K0.init, n, f, (int)blockIdx.x - K0.agent_blocks, &A);
 }
 
 
@@ -1049,6 +1125,30 @@ PIML_API int piml_scenario_step_members(const piml_scenario* s, const piml_scena
                                         const uint64_t* seeds, const float* a_next, int init, void* stream) {
     if (!s || !seeds || members < 1 || members > 65535 || !frame_args_ok(*s, r, a_next, init)) return hipErrorInvalidValue;
     return launch_frame(*s, r, members, seeds, a_next, init, stream);
+}
+
+PIML_API int piml_scenario_step_nav(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                                    const float* a_next, int init, const piml_nav_grid* nav, const piml_nav_sight* sight,
+                                    float* steer, void* stream) {
+    if (!s || !steer || members < 1 || members > 65535 || (!seeds && members != 1) || !frame_args_ok(*s, r, a_next, init))
+        return hipErrorInvalidValue;
+    if (r && r->spawn_law != PIML_SPAWN_GC) return hipErrorInvalidValue;      // only GC's law has gates and exit_idx
+    if (s->route_max_iters != 0) return hipErrorInvalidValue;                 // a detour point's gate is not the destination's
+    if (!piml::nav_grid_ok(nav) || nav->G != s->E || (sight && !piml::nav_sight_ok(sight, nav))) return hipErrorInvalidValue;
+    piml::FrameArgs K;
+    K.S = *s;
+    K.R = piml_scenario_rules{};
+    K.a_next = (const float2*)a_next;
+    K.init = init;
+    K.agent_blocks = init ? 0 : (s->capacity + 255) / 256;
+    const dim3 grid((unsigned)(K.agent_blocks + spawn_blocks(*s, nullptr, init)), (unsigned)members);
+    const piml::SteerArgs A{*nav, sight ? sight->parent : nullptr, (float2*)steer};
+    const unsigned long long* sd = (const unsigned long long*)seeds;
+    if (sight)
+        hipLaunchKernelGGL(piml::scenario_frame_nav_kernel<true>, grid, dim3(256), 0, piml::as_stream(stream), K, sd, A);
+    else
+        hipLaunchKernelGGL(piml::scenario_frame_nav_kernel<false>, grid, dim3(256), 0, piml::as_stream(stream), K, sd, A);
+    return hipGetLastError();
 }
 
 // the law checks of the MLAPM frame entries (include/piml_hip.h)

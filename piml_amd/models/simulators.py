@@ -463,26 +463,36 @@ class BaseSimulator(Pedestrians):
                              time_unit=data.time_unit)
 
     # ---- open-world simulation: the loop the reference stubs (BaseSimulator.run / run_single_step, simulators.py:834-838) ----
-    def simulate_scenario(self, scenario, frames, seed=0, capacity=None, use_graph=None):
+    def simulate_scenario(self, scenario, frames, seed=0, capacity=None, use_graph=None, nav=None):
         """Simulate `frames` frames of an entry / exit scene (piml_amd.scenarios.Scenario: gc_scenario() or a synthetic scene
         of piml_amd.scenarios.SCENARIOS) with the current model: frame 0 spawns the scenario's initial agents, every further
         frame is model -> one scenario_frame_kernel launch (integrate, arrive, retire, Poisson arrivals routed around the
         scenario's polyline or by the scene's spawn law, record) -> relative features.
         The frame is captured into one graph and replayed (`use_graph=None`: when more than 8 frames); the Philox draws
         make the spawn schedule a function of (seed, frame, ordinal).  `capacity` = agent slots (default: n_initial + a
-        1e-9 upper quantile of the arrivals); agents past it are dropped and counted.  Returns a ScenarioResult."""
-        return self._in_scenario_mode(lambda: self._simulate(scenario, frames, capacity, use_graph, seed=seed))
+        1e-9 upper quantile of the arrivals); agents past it are dropped and counted.
+        nav = True, 'sight' or an ops_scenario.nav_field(...) of the scene (MLAPM.simulate_scenario's vocabulary: True builds
+        the field with nav_field's defaults, 'sight' with the any-angle table as well): the network is steered by the floor
+        field.  The frame also writes, per agent, the point one metre down the field (piml_scenario_step_nav), and the
+        relative-feature launch takes that target in the place of the destination -- the network reads the destination only
+        as the unit direction of its desired-force term, so it follows the field round the walls while its obstacle branch
+        keeps it off them.  Arrival, retirement and the recorded `destination` stay the scene's own, and the arrivals do not
+        depend on the field.  res.state.steer holds the last frame's targets.  A scene of gates only (gc_scenario() with
+        route_max_iters=0, scenarios.floorplan_scenario): ValueError otherwise (ops_scenario.check_nav_scene).
+        Returns a ScenarioResult."""
+        return self._in_scenario_mode(lambda: self._simulate(scenario, frames, capacity, use_graph, nav=nav, seed=seed))
 
-    def simulate_ensemble(self, scenario, frames, seeds, capacity=None, use_graph=None):
+    def simulate_ensemble(self, scenario, frames, seeds, capacity=None, use_graph=None, nav=None):
         """`simulate_scenario` for every seed of `seeds` at once: S = len(seeds) simulations of one scene with one capacity
         (default: as simulate_scenario's, which does not depend on the seed), every frame of all of them one network
         forward over the S * capacity rows, one scenario_frame_kernel launch and one relative-feature launch
         (captured and replayed as simulate_scenario's frame).  Member m is the simulation of seed seeds[m]: the network
-        sees flat (S * capacity, .) rows, so members never see each other.  Returns a scenarios.ScenarioEnsemble."""
+        sees flat (S * capacity, .) rows, so members never see each other.  nav: simulate_scenario's; every member shares
+        the one field of the scene.  Returns a scenarios.ScenarioEnsemble."""
         seeds = [int(x) for x in seeds]
         if not seeds:
             raise ValueError('simulate_ensemble: at least one seed expected')
-        return self._in_scenario_mode(lambda: self._simulate(scenario, frames, capacity, use_graph, seeds=seeds))
+        return self._in_scenario_mode(lambda: self._simulate(scenario, frames, capacity, use_graph, nav=nav, seeds=seeds))
 
     def _in_scenario_mode(self, run):
         only = hasattr(self.model, 'predictions_only')
@@ -497,32 +507,41 @@ class BaseSimulator(Pedestrians):
                 if only:
                     self.model.predictions_only = before
 
-    def _simulate(self, scenario, frames, capacity, use_graph, **state_kw):
-        from .. import scenarios
+    def _simulate(self, scenario, frames, capacity, use_graph, nav=None, **state_kw):
+        from .. import ops_scenario, scenarios
         a = self.args
+        nav = None if nav is False else nav
+        if nav is not None:                               # said before any state exists
+            ops_scenario.nav_wants_sight(nav)
+            ops_scenario.check_nav_scene(scenario)
         st = scenarios.scenario_state_for(scenario, frames, capacity, a.device, 2 * int(a.num_history_velocity),
                                           topk_ped=a.topk_ped, topk_obs=a.topk_obs, **state_kw)
         rows = st.mask.numel()
         # flat 2-D rows: on a 3-D (S, cap, .) batch the model would normalise the desired force over the agent axis
         #  and couple the members
         inputs = (st.pf.view(rows, *st.pf.shape[-2:]), st.of.view(rows, *st.of.shape[-2:]), st.selff.view(rows, st.selff.shape[-1]))
-        self._run_scenario(st, inputs, use_graph)
+        if nav is not None and not isinstance(nav, ops_scenario.NavField):
+            nav = ops_scenario.nav_field(st.scenario, device=st.p.device, sight=ops_scenario.nav_wants_sight(nav))
+        self._run_scenario(st, inputs, use_graph, nav=nav)
         return scenarios.scenario_result(st)
 
-    def _run_scenario(self, st, inputs, use_graph):
+    def _run_scenario(self, st, inputs, use_graph, nav=None):
         """frame 0's spawn and features, then T - 1 frames of model(inputs) -> scenario_step -> relative features (the
-        model's rows `inputs` are views of st's feature buffers), captured and replayed when use_graph."""
+        model's rows `inputs` are views of st's feature buffers), captured and replayed when use_graph.  nav: None or the
+        scene's ops_scenario.nav_field: both scenario_step calls then also write st.steer (allocated by the init launch,
+        before any capture), which the relative-feature launches take in the place of st.dest."""
         from .. import ops_scenario, hip_graphs_safe
         a, sc, T = self.args, st.scenario, st.T
         feats = (st.pf, st.of, st.selff, st.ped_idx, st.obs_idx)
         geo = (a.topk_ped, a.sight_angle_ped, a.dist_threshold_ped, a.topk_obs, a.sight_angle_obs, a.dist_threshold_obs)
-        ops_scenario.scenario_step(st, init=True)                                         # frame 0: generate(n_initial)
-        ops.relative_features_into(feats, st.p, st.v, st.a, st.dest, sc.obstacles, *geo)
+        ops_scenario.scenario_step(st, init=True, nav=nav)                                # frame 0: generate(n_initial)
+        target = st.dest if nav is None else st.steer                                     # what the network is steered to
+        ops.relative_features_into(feats, st.p, st.v, st.a, target, sc.obstacles, *geo)
 
         def step():
             a_next = self.model(*inputs)[0]
-            ops_scenario.scenario_step(st, a_next.reshape(st.p.shape).contiguous())
-            ops.relative_features_into(feats, st.p, st.v, st.a, st.dest, sc.obstacles, *geo, tick=st.t)   # + st.t += 1
+            ops_scenario.scenario_step(st, a_next.reshape(st.p.shape).contiguous(), nav=nav)
+            ops.relative_features_into(feats, st.p, st.v, st.a, target, sc.obstacles, *geo, tick=st.t)   # + st.t += 1
 
         steps = T - 1
         if use_graph is None:

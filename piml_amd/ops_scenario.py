@@ -1,5 +1,5 @@
 """Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_step_rules,
-piml_scenario_step_members, piml_scenario_step_mlapm, piml_scenario_step_mlapm_laws, piml_scenario_step_mlapm_walls,
+piml_scenario_step_members, piml_scenario_step_nav, piml_scenario_step_mlapm, piml_scenario_step_mlapm_laws, piml_scenario_step_mlapm_walls,
 piml_wall_force, piml_scenario_step_mlapm_groups, piml_group_force, piml_scenario_step_mlapm_noise, piml_noise_force,
 piml_nav_relax, piml_nav_direction, piml_scenario_step_mlapm_nav, piml_scenario_route).
 
@@ -47,7 +47,8 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
     and st.rules the scene's piml_scenario_rules (GC's all-zero one for GC).  A grouped clip scene ('clip_groups') also
     gets st.group_first / st.group_size ((S,) capacity int32, zero: per slot the first slot and the size of its unit) and
     st.groups, the piml_scene_groups over them and the scene's row_unit / unit_rows.  st.noise_state is None until a frame
-    with the fluctuation term needs it (scenario_noise_state: (S,) capacity, 2 float32 zeros, eta of every slot)."""
+    with the fluctuation term needs it (scenario_noise_state: (S,) capacity, 2 float32 zeros, eta of every slot), st.steer
+    None until a frame routed by a floor field writes it (scenario_step(nav=): (S,) capacity, 2 float32, NaN)."""
     dev = scenario.entries.device
     if dev.type != 'cuda':
         raise _lib.PimlHipError(f'scenario_state: the scenario must be on a GPU (piml_amd has no CPU path), got {dev}')
@@ -119,6 +120,7 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
     st.rules = scenario_rules(scenario) if scenario.spawn_law != 'gc' else _lib.ScenarioRules()
     st.groups = None
     st.noise_state = None
+    st.steer = None
     if scenario.spawn_law == 'clip_groups':
         ru, ur = scenario.row_unit, scenario.unit_rows
         if ru is None or ur is None or ru.dtype != torch.int32 or ur.dtype != torch.int32 or ru.device != dev or \
@@ -149,6 +151,8 @@ def scenario_state_reset(st):
         st.group_size.zero_()
     if getattr(st, 'noise_state', None) is not None:
         st.noise_state.zero_()
+    if getattr(st, 'steer', None) is not None:
+        st.steer.fill_(nan)
 
 
 def scenario_noise_state(st):
@@ -186,11 +190,21 @@ def scenario_rules(scenario):
     return r
 
 
-def scenario_step(st, a_next=None, init=False):
+def scenario_step(st, a_next=None, init=False, nav=None):
     """One launch: init=True spawns the scenario's n_initial agents into frame st.t; otherwise frame st.t -> st.t + 1 with
     the network's accelerations a_next (capacity, 2), or (S, capacity, 2) for an ensemble state (every member in the same
     launch).  The caller advances st.t (ops.relative_features_into(tick=st.t)).  ValueError for a grouped clip scene
-    ('clip_groups'): its frames, the init launch included, are scenario_step_mlapm's."""
+    ('clip_groups'): its frames, the init launch included, are scenario_step_mlapm's.
+    nav = a nav_field(...) of the scene: the same frame through piml_scenario_step_nav, which also writes st.steer ((S,)
+    capacity, 2): per present slot the point one metre down the floor field from its new position -- position +
+    nav_direction(position, exit_idx[flag], destination), the destination itself in the lookup's branch 0 --, NaN for absent
+    and retired slots.  Handed to ops.relative_features_into in the place of st.dest it steers a PINNSF, which reads the
+    destination as a direction only; position, records and arrivals are the frame's without the field, bit for bit.  A field
+    with the any-angle table is looked up through it.  st.steer is allocated (NaN) at the first such call, the init launch,
+    and scenario_state_reset refills it.  TypeError unless nav is a NavField; ValueError (check_nav_scene) for a scene rule
+    other than GC's, route_max_iters != 0, or a field of another number of gates."""
+    if nav is not None:
+        _check_nav(st, nav)
     if getattr(st, 'groups', None) is not None:
         raise ValueError("scenario_step: a 'clip_groups' scene runs under the MLAPM frame only (scenario_step_mlapm)")
     if not init:
@@ -198,6 +212,16 @@ def scenario_step(st, a_next=None, init=False):
         want = (st.capacity, 2) if st.members is None else (st.members, st.capacity, 2)
         if tuple(a_next.shape) != want or a_next.device != st.p.device:
             raise ValueError(f'a_next: {want} on {st.p.device} expected, got {tuple(a_next.shape)} on {a_next.device}')
+    if nav is not None:
+        if getattr(st, 'steer', None) is None:
+            st.steer = torch.full_like(st.p, float('nan'))
+        with torch.cuda.device(st.p.device):
+            _lib.check(_lib.lib().piml_scenario_step_nav(
+                ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(), _ptr(st.seeds),
+                _ptr(a_next) if not init else None, int(bool(init)), ctypes.byref(nav.desc),
+                None if nav.sight_desc is None else ctypes.byref(nav.sight_desc), _ptr(st.steer), _stream()),
+                'piml_scenario_step_nav')
+        return
     with torch.cuda.device(st.p.device):
         _lib.check(_lib.lib().piml_scenario_step_members(ctypes.byref(st.desc), ctypes.byref(st.rules), st.seeds.numel(),
                                                          _ptr(st.seeds), _ptr(a_next) if not init else None,

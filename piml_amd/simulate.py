@@ -28,6 +28,8 @@ reads.
     python -m piml_amd.simulate --law mlapm --scenario gc --nav [--nav-cell 0.25] [--nav-clearance 0.3] --out clip.npy
     python -m piml_amd.simulate --law mlapm --scene-plan plan.json --nav --nav-sight --out clip.npy
                                 (the same, steering along lines of sight: the field's any-angle table)
+    python -m piml_amd.simulate --checkpoint model.pt --scene-plan plan.json --route field --seeds 0:32 --obstacle-stats walls.json
+                                (the network on a floor plan: --route field|sight steers either law by the floor field)
 
 Model flags (--model, --hidden sizes, --topk_*, --num_history_velocity, ...) are those of `piml_amd.main`, with its
 defaults.  Without --checkpoint the network keeps its initial weights (a smoke run)."""
@@ -72,13 +74,19 @@ def get_args(argv=None):
                         'file holding a list of lists of track indices')
     p.add_argument('--scene-plan', dest='scene_plan', type=str, default=None,
                    help='a floor plan as the scene (scenarios.load_floorplan: JSON with "walls", polylines, and "gates", '
-                        'segments); --law mlapm only; not with --scenario or --scene-from')
+                        'segments); under the network law it needs --route; not with --scenario or --scene-from')
+    p.add_argument('--route', type=str, default=None, choices=['field', 'sight'],
+                   help='either law with --scenario gc (its route_max_iters becomes 0) or --scene-plan: route the agents by a '
+                        "static floor field (ops_scenario.nav_field): 'field' down its gradient, 'sight' along lines of sight "
+                        '(the any-angle table as well).  The network is steered by the point one metre down the field in the '
+                        "place of its destination; under --law mlapm 'field' is --nav and 'sight' is --nav --nav-sight")
     p.add_argument('--nav', action='store_true',
                    help='--law mlapm with --scenario gc (its route_max_iters becomes 0) or --scene-plan: the agents descend a '
                         'static floor field to their gate instead of walking the straight line (ops_scenario.nav_field)')
-    p.add_argument('--nav-cell', dest='nav_cell', type=float, default=None, help='--nav: the grid cell in metres (default 0.25)')
+    p.add_argument('--nav-cell', dest='nav_cell', type=float, default=None, help='--nav / --route: the grid cell in metres (default 0.25)')
     p.add_argument('--nav-clearance', dest='nav_clearance', type=float, default=None,
-                   help='--nav: a cell is blocked when an obstacle point lies within this many metres of its centre (default 0.3)')
+                   help='--nav / --route: a cell is blocked when an obstacle point lies within this many metres of its centre '
+                        '(default 0.3)')
     p.add_argument('--nav-sight', dest='nav_sight', action='store_true',
                    help='--nav: also build the any-angle table (ops_scenario.nav_field(sight=True)); the agents steer along '
                         'lines of sight, at the next turning point of their shortest path, instead of down the gradient')
@@ -186,25 +194,30 @@ def get_args(argv=None):
     if own.scene_plan is not None:
         if own.scene_from is not None or own.scenario != p.get_default('scenario'):
             p.error('--scene-plan builds the scene from a floor plan: not with --scene-from or --scenario')
-        if own.law != 'mlapm':
-            p.error('--scene-plan: a floor plan runs under --law mlapm only: the network-driven frame has no floor field '
-                    '(piml_scenario_step_mlapm_nav is the MLAPM frame\'s), so with --law pinnsf nothing would route its agents')
+        if own.law != 'mlapm' and own.route is None:
+            p.error('--scene-plan: under --law pinnsf a floor plan needs --route field|sight: without the floor field '
+                    '(piml_scenario_step_nav) nothing would route the network\'s agents round the walls')
         try:
             own.plan = SCENARIOS.load_floorplan(own.scene_plan)
         except (OSError, ValueError) as ex:
             p.error(f'--scene-plan: {ex}')
-    if own.nav:
-        if own.law != 'mlapm':
-            p.error('--nav needs --law mlapm (the network-driven frame has no floor field)')
+    if own.route is not None and own.nav:
+        p.error('--route is the law-agnostic spelling of --nav [--nav-sight]: not both')
+    if own.route is not None and own.nav_sight:
+        p.error('--nav-sight goes with --nav; with --route say --route sight')
+    own.routed, own.route_sight = own.nav or own.route is not None, own.nav_sight or own.route == 'sight'
+    if own.routed:
+        if own.nav and own.law != 'mlapm':
+            p.error('--nav is the MLAPM law\'s spelling; the network is routed by the floor field with --route field|sight')
         if own.scene_from is not None or (own.scene_plan is None and own.scenario != 'gc'):
-            p.error('--nav routes scenes of gates: --scenario gc or --scene-plan (a clip scene carries recorded waypoints and '
-                    'no gates; the synthetic scenes have none either)')
+            p.error('--nav / --route route scenes of gates: --scenario gc or --scene-plan (a clip scene carries recorded '
+                    'waypoints and no gates; the synthetic scenes have none either)')
         own.nav_cell = 0.25 if own.nav_cell is None else own.nav_cell
         own.nav_clearance = 0.3 if own.nav_clearance is None else own.nav_clearance
         if not (own.nav_cell > 0 and own.nav_cell < float('inf') and own.nav_clearance > 0 and own.nav_clearance < float('inf')):
             p.error(f'--nav-cell / --nav-clearance: finite values > 0 expected, got {own.nav_cell}, {own.nav_clearance}')
     elif own.nav_cell is not None or own.nav_clearance is not None:
-        p.error('--nav-cell / --nav-clearance need --nav')
+        p.error('--nav-cell / --nav-clearance need --nav or --route')
     elif own.nav_sight:
         p.error('--nav-sight needs --nav (it adds the any-angle table to the floor field)')
     if own.params_sweep is not None:
@@ -353,18 +366,18 @@ def main(argv=None):
             check_scene_groups(scenario)
         except ValueError as ex:
             sys.exit(f'--params / --params-sweep: {ex} (--scene-from CLIP --scene-groups auto|FILE.json)')
-    if own.nav:
+    if own.routed:
         import dataclasses
         from . import ops_scenario
         scenario = dataclasses.replace(scenario, route_max_iters=0)       # (GC: the field routes, not the pillar's detour)
         try:
             run_kw['nav'] = ops_scenario.nav_field(scenario.to(args.device), cell=own.nav_cell, clearance=own.nav_clearance,
-                                                   device=args.device, sight=own.nav_sight)
+                                                   device=args.device, sight=own.route_sight)
         except (ValueError, RuntimeError) as ex:
-            sys.exit(f'--nav: {ex}')
+            sys.exit(f'--nav / --route: {ex}')
         print(f'[simulate] floor field: {run_kw["nav"].G} gates, {run_kw["nav"].gx} x {run_kw["nav"].gy} cells of '
               f'{run_kw["nav"].cell:g} m, {run_kw["nav"].iterations} steps')
-        if own.nav_sight:
+        if own.route_sight:
             print(f'[simulate] lines of sight: {run_kw["nav"].sight_iterations} steps')
     if own.law == 'mlapm' and own.mlapm_sweep is not None:
         return _sweep(sim, scenario, own, run_kw)
