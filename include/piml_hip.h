@@ -1296,6 +1296,64 @@ int piml_scenario_step_mlapm_nav(const piml_scenario* s, const piml_scenario_rul
                                  const piml_noise_args* noise /* NULL: no fluctuation */, int frame_offset, void* stream);
 
 /*
+ * The density-aware floor field (ABI 35, additive): the travel cost of a cell grows with the crowd in and around it, and the
+ * field is solved again per ensemble member while the scene runs, so routed agents use a second door when the first is
+ * congested (the dynamic navigation field of Hartmann et al. 2014).  The grid, blocked and goal are piml_nav_relax's and are
+ * shared by all members; count, cost (members, gy, gx) and u (members, G, gy, gx) have a member axis, 1 <= members <= 65535.
+ *
+ * piml_nav_density: count[m][c] = the number of present slots of member m whose cell is c.  position (members, capacity, 2),
+ * mask (members, capacity) float32 (a slot is present when its mask is not 0), count (members, gy, gx) int32.  A slot's cell is
+ * piml_nav_direction's, (floor(fdiv(fsub(p.x, x0), cell)), floor(fdiv(fsub(p.y, y0), cell))) in float32; an absent slot, a NaN
+ * position and a cell outside the grid deposit nothing.  The entry zeroes count itself (hipMemsetAsync on the stream) and
+ * then launches one thread per slot, grid.y = member: integer atomics only, so the result is deterministic, and two members
+ * never touch the same plane.  Capturable.
+ * hipErrorInvalidValue (before any launch): a NULL buffer; members outside 1..65535; capacity < 1; gx or gy outside 1..1024;
+ * cell not finite and > 0; x0 or y0 not finite.
+ *
+ * piml_nav_cost: the slowness f (members, gy, gx) float32 from the counts.  With s the integer sum of count over the
+ * (2r + 1)^2 window of the cell, r = radius_cells, cells outside the grid counting 0,
+ *   area = fmul((float)((2r + 1)^2), fmul(cell, cell)),
+ *   f = fminf(fadd(1, fmul(kd, fmaxf(fsub(fdiv((float)s, area), rho0), 0))), fmax),
+ * every operation one correctly rounded float32 operation (tests/navcost_ref.py gives the same bits).  A workgroup of 256
+ * threads stages a 32 x 32 tile of one member's counts with a halo of r cells in LDS and sums rows, then columns.  Known limit:
+ * blocked cells count in the window's area, so the density beside a wall reads low.
+ * hipErrorInvalidValue (before any launch): a NULL buffer; members outside 1..65535; gx or gy outside 1..1024; cell not finite
+ * and > 0; radius_cells outside 0..8; kd < 0, rho0 < 0, fmax < 1, or any of the three not finite.
+ *
+ * piml_nav_relax_cost: piml_nav_relax with the slowness in the update and a member axis.  One step is
+ *   cand = lo + f                                         when hi is not finite or hi - lo >= f,
+ *        = 0.5 ((lo + hi) + sqrt(2 f f - (hi - lo)^2))    otherwise (fmul(2, fmul(f, f)), then fsub),
+ *   u' = cand < u ? cand : u, goal cells 0 and other blocked cells +inf as in piml_nav_relax,
+ * with f = cost[member][cell] >= 1, each operation one correctly rounded float32 operation: bitwise tests/navcost_ref.py, and
+ * with cost == 1 everywhere bitwise piml_nav_relax.  cost (members, gy, gx); u_a, u_b (members, G, gy, gx), ping-pong as in
+ * piml_nav_relax; changed (members * G) int32, plane member * G + gate.  The same temporal blocking: K = 8 steps per launch on
+ * a 32 x 32 tile staged with a halo of 8 in two LDS planes, the member's cost tile staged once into a third (29952 bytes of
+ * LDS a workgroup: 5 workgroups a CU against piml_nav_relax's 7); grid.z = member * G + gate.  From the cold start (0 on goal
+ * cells, +inf elsewhere) u only decreases, so a launch that changed nothing left the fixed point, and
+ * u_static <= u <= max(f) u_static.  A warm start from a field of lower cost does NOT reach it (the minimum keeps stale low
+ * values): start cold.  No atomics, no host synchronisation; capturable.
+ * hipErrorInvalidValue (before any launch): members < 1; a NULL buffer; u_a == u_b; G outside 1..64; gx or gy outside
+ * 1..1024; launches < 0; members * G > 65535; more than 2^31 - 1 cells in u.  launches == 0 is a no-op.
+ *
+ * piml_scenario_step_mlapm_navdyn: piml_scenario_step_mlapm_nav with a field per member: member m looks its directions up in
+ * nav->u + m * member_stride (elements; G * gy * gx for the u of piml_nav_relax_cost), 0 meaning one field shared by all
+ * members -- then the frame is piml_scenario_step_mlapm_nav's bit for bit.  The caller guarantees members fields behind nav->u.
+ * There is no form with the any-angle table: that table is a uniform-cost construction.
+ * hipErrorInvalidValue (before any launch): piml_scenario_step_mlapm_nav's refusals; member_stride < 0.  No atomics, capturable.
+ */
+int piml_nav_density(const float* position, const float* mask, int members, int capacity, float x0, float y0, float cell,
+                     int gx, int gy, int* count, void* stream);
+int piml_nav_cost(const int* count, int members, int gx, int gy, float cell, int radius_cells, float kd, float rho0, float fmax,
+                  float* cost, void* stream);
+int piml_nav_relax_cost(const unsigned char* blocked, const unsigned char* goal, const float* cost, float* u_a, float* u_b,
+                        int members, int G, int gx, int gy, int launches, int* changed, void* stream);
+int piml_scenario_step_mlapm_navdyn(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
+                                    const piml_mlapm_law* law, const void* law_table_device,
+                                    const piml_wall_grid* wall_grid /* NULL: no wall term */, const piml_wall_law* wall,
+                                    const piml_wall_law* wall_table_device, const piml_nav_grid* nav, long long member_stride,
+                                    const piml_noise_args* noise /* NULL: no fluctuation */, int frame_offset, void* stream);
+
+/*
  * The any-angle floor field: a second table beside u.  For every cell c of gate g, parent[g][c] is the next turning point
  * of the taut string from c to the gate -- the gate cell itself in open space, a corner cell round a wall -- and w[g][c]
  * the string's length in cells.  An agent in c steers at the centre of its parent along a straight segment that enters no

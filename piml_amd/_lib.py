@@ -208,6 +208,10 @@ SIGNATURES = {
     'piml_nav_relax': [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
     'piml_nav_direction': [_p, _p, _p, _ll, _p, _p, _p, _p, _p],
     'piml_scenario_step_mlapm_nav': [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
+    'piml_nav_density': [_p, _p, _i, _i, _f, _f, _f, _i, _i, _p, _p],
+    'piml_nav_cost': [_p, _i, _i, _i, _f, _i, _f, _f, _f, _p, _p],
+    'piml_nav_relax_cost': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
+    'piml_scenario_step_mlapm_navdyn': [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _ll, _p, _i, _p],
     'piml_nav_sight_relax': [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
     'piml_nav_direction_sight': [_p, _p, _p, _ll, _p, _p, _p, _p, _p, _p],
     'piml_scenario_step_mlapm_sight': [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p],

@@ -1042,6 +1042,22 @@ __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_sight_kernel(c
     scenario_mlapm_body<kTable, kWalls, false, true, true, true>(K0, seeds, table, WG, wall, wall_table, GroupArgs{}, NA, NV, SV);
 }
 
+// the frame routed by a floor field per member (piml_scenario_step_mlapm_navdyn; navdensity.hip solves the fields): member
+// blockIdx.y looks its directions up in the planes member_stride elements further on.  The body is the nav kernel's, called
+// with a copy of the grid whose u was advanced; stride 0 is the nav kernel's frame bit for bit
+template <bool kTable, bool kWalls>
+__global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_navdyn_kernel(const MlapmScenarioArgs K0,
+                                                                               const unsigned long long* __restrict__ seeds,
+                                                                               const MlapmParams* __restrict__ table,
+                                                                               const WallArgs WG, const piml_wall_law wall,
+                                                                               const piml_wall_law* __restrict__ wall_table,
+                                                                               const piml_noise_args NA, const piml_nav_grid NV0,
+                                                                               const long long member_stride) {
+    piml_nav_grid NV = NV0;
+    NV.u = NV0.u + (long long)blockIdx.y * member_stride;
+    scenario_mlapm_body<kTable, kWalls, false, true, true>(K0, seeds, table, WG, wall, wall_table, GroupArgs{}, NA, NV);
+}
+
 }  // namespace piml
 
 namespace {
@@ -1372,13 +1388,16 @@ PIML_API int piml_scenario_step_mlapm_noise(const piml_scenario* s, const piml_s
     return hipGetLastError();
 }
 
-// sight == NULL: the nav frame's kernels
+// sight == NULL: the nav frame's kernels; stride >= 0: those of the frame with a field per member
 template <bool kTable, bool kWalls>
 static void launch_mlapm_nav(dim3 grid, hipStream_t st, const piml::MlapmScenarioArgs& K, const unsigned long long* sd,
                              const piml::MlapmParams* tb, const piml::WallArgs& WG, const piml_wall_law& w,
                              const piml_wall_law* wt, const piml_noise_args& NA, const piml_nav_grid& NV,
-                             const piml_nav_sight* sight) {
-    if (sight)
+                             const piml_nav_sight* sight, long long stride) {
+    if (stride >= 0)                                         // a field per member (sight == NULL)
+        hipLaunchKernelGGL((piml::scenario_mlapm_navdyn_kernel<kTable, kWalls>), grid, dim3(piml::kMlScWaves * 64), 0, st, K, sd,
+                           tb, WG, w, wt, NA, NV, stride);
+    else if (sight)
         hipLaunchKernelGGL((piml::scenario_mlapm_sight_kernel<kTable, kWalls>), grid, dim3(piml::kMlScWaves * 64), 0, st, K, sd,
                            tb, WG, w, wt, NA, NV, *sight);
     else
@@ -1386,11 +1405,13 @@ static void launch_mlapm_nav(dim3 grid, hipStream_t st, const piml::MlapmScenari
                            WG, w, wt, NA, NV);
 }
 
-// piml_scenario_step_mlapm_nav (sight == NULL) and piml_scenario_step_mlapm_sight: one set of checks, one dispatch
+// piml_scenario_step_mlapm_nav (sight == NULL), piml_scenario_step_mlapm_sight and piml_scenario_step_mlapm_navdyn (stride >= 0,
+// the elements between two members' fields; -1 otherwise): one set of checks, one dispatch
 static int step_mlapm_nav(const piml_scenario* s, const piml_scenario_rules* r, int members, const uint64_t* seeds,
                           const piml_mlapm_law* law, const void* law_table_device, const piml_wall_grid* wall_grid,
                           const piml_wall_law* wall, const piml_wall_law* wall_table_device, const piml_nav_grid* nav,
-                          const piml_nav_sight* sight, const piml_noise_args* noise, int frame_offset, void* stream) {
+                          const piml_nav_sight* sight, const piml_noise_args* noise, int frame_offset, void* stream,
+                          long long stride = -1) {
     if (noise && (!noise->state || (!noise->law_table && !piml::noise_law_ok(noise->law.rho, noise->law.amp))))
         return hipErrorInvalidValue;
     if (!s || !seeds || members < 1 || members > 65535 || frame_offset < 0) return hipErrorInvalidValue;
@@ -1414,11 +1435,11 @@ static int step_mlapm_nav(const piml_scenario* s, const piml_scenario_rules* r, 
     const piml::MlapmParams* tb = (const piml::MlapmParams*)law_table_device;
     hipStream_t st = piml::as_stream(stream);
     if (law) {
-        if (wall_grid) launch_mlapm_nav<false, true>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav, sight);
-        else launch_mlapm_nav<false, false>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav, sight);
+        if (wall_grid) launch_mlapm_nav<false, true>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav, sight, stride);
+        else launch_mlapm_nav<false, false>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav, sight, stride);
     } else {
-        if (wall_grid) launch_mlapm_nav<true, true>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav, sight);
-        else launch_mlapm_nav<true, false>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav, sight);
+        if (wall_grid) launch_mlapm_nav<true, true>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav, sight, stride);
+        else launch_mlapm_nav<true, false>(grid, st, K, sd, tb, WG, w, wall_table_device, NA, *nav, sight, stride);
     }
     return hipGetLastError();
 }
@@ -1441,6 +1462,17 @@ PIML_API int piml_scenario_step_mlapm_sight(const piml_scenario* s, const piml_s
     if (!piml::nav_grid_ok(nav) || !piml::nav_sight_ok(sight, nav)) return hipErrorInvalidValue;
     return step_mlapm_nav(s, r, members, seeds, law, law_table_device, wall_grid, wall, wall_table_device, nav, sight, noise,
                           frame_offset, stream);
+}
+
+PIML_API int piml_scenario_step_mlapm_navdyn(const piml_scenario* s, const piml_scenario_rules* r, int members,
+                                             const uint64_t* seeds, const piml_mlapm_law* law, const void* law_table_device,
+                                             const piml_wall_grid* wall_grid, const piml_wall_law* wall,
+                                             const piml_wall_law* wall_table_device, const piml_nav_grid* nav,
+                                             long long member_stride, const piml_noise_args* noise, int frame_offset,
+                                             void* stream) {
+    if (member_stride < 0) return hipErrorInvalidValue;
+    return step_mlapm_nav(s, r, members, seeds, law, law_table_device, wall_grid, wall, wall_table_device, nav, nullptr, noise,
+                          frame_offset, stream, member_stride);
 }
 
 PIML_API int piml_scenario_route(const float* origin, const float* destination, int n, const float* polyline, int R,

@@ -9,7 +9,9 @@ scene (scenarios.clip_scenario(groups=)) add a group cohesion term, a pull of Ag
 runs add a fluctuation term, an Ornstein-Uhlenbeck acceleration per agent of stationary standard deviation An and correlation
 time noise_tau (piml_scenario_step_mlapm_noise); again `step`, `rollout` and the gradient fits never have one.  The scene runs
 take nav=True | ops_scenario.nav_field(...): the agents of a scene of gates then descend a static floor field instead of
-walking the straight line to their destination (piml_scenario_step_mlapm_nav); the field is the scene's, not the law's."""
+walking the straight line to their destination (piml_scenario_step_mlapm_nav); the field is the scene's, not the law's.
+With nav_density=ops_scenario.nav_density_law(kd, ...) as well the field's travel cost grows with the local density and it is
+solved again, per member, while the scene runs (piml_scenario_step_mlapm_navdyn)."""
 from .. import ops
 
 DEFAULT_WALL_CUTOFF = 2.0     # metres
@@ -144,7 +146,7 @@ class MLAPM:
                                       a.get('theta', 0.0), radius)
 
     def simulate_scenario(self, scenario, frames, seed=0, capacity=None, use_graph=None, radius=0.3, device='cuda',
-                          hist_width=2, frames_per_graph=8, nav=None):
+                          hist_width=2, frames_per_graph=8, nav=None, nav_density=None):
         """Simulate `frames` frames of an entry / exit scene (piml_amd.scenarios: gc_scenario() or a scene of SCENARIOS)
         with this law, as BaseSimulator.simulate_scenario does with a PINNSF: frame 0 spawns the initial agents, every
         further frame is ONE launch -- MLAPM.step's force from the agents present in the frame (main_mlapm.py:18-36),
@@ -177,26 +179,34 @@ class MLAPM:
         of sight, at the next turning point of the shortest path (piml_scenario_step_mlapm_sight); a passed field decides by
         whether it has the table.  The field belongs to the scene, not the law.  A scene of gates only (gc_scenario() with
         route_max_iters=0, scenarios.floorplan_scenario): ValueError otherwise (ops_scenario.check_nav_scene).
+        nav_density = an ops_scenario.nav_density_law(kd, ...): the floor field's travel cost grows with the local density and
+        the field is solved again, per member, every law.every frames from the agents present then (density, cost, a solve
+        from the cold start: ops_scenario.nav_field_update; piml_scenario_step_mlapm_navdyn reads it), so routed agents go
+        round a congested door.  It needs nav = True or a field without the any-angle table: ValueError otherwise, and in a
+        captured run when law.every is not a multiple of frames_per_graph (the update runs between replays).  The field an
+        update leaves is read until the next one: it lags by up to law.every frames.
         Returns a scenarios.ScenarioResult."""
         return self._simulate(scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, nav=nav,
-                              seed=seed)
+                              nav_density=nav_density, seed=seed)
 
     def simulate_ensemble(self, scenario, frames, seeds, capacity=None, use_graph=None, radius=0.3, device='cuda',
-                          hist_width=2, frames_per_graph=8, nav=None):
+                          hist_width=2, frames_per_graph=8, nav=None, nav_density=None):
         """simulate_scenario for every seed of `seeds` in the same launches (grid.y = member; members never see each
         other).  Member m is bitwise simulate_scenario(seed=seeds[m]) with the same capacity; every member shares the
-        floor field of nav.  Returns a scenarios.ScenarioEnsemble."""
+        floor field of nav; with nav_density every member has a field of its own, solved from its own crowd.  Returns a
+        scenarios.ScenarioEnsemble."""
         seeds = [int(x) for x in seeds]
         if not seeds:
             raise ValueError('simulate_ensemble: at least one seed expected')
         return self._simulate(scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, nav=nav,
-                              seeds=seeds)
+                              nav_density=nav_density, seeds=seeds)
 
     def _simulate(self, scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, nav=None,
-                  **state_kw):
+                  nav_density=None, **state_kw):
         from .. import ops_scenario, scenarios
         law = self._law(radius)
         nav = None if nav is False else nav
+        check_nav_density(nav, nav_density)
         if nav is not None:
             ops_scenario.nav_wants_sight(nav)
             ops_scenario.check_nav_scene(scenario)
@@ -213,32 +223,53 @@ class MLAPM:
         noise = noise_args(self.args)
         if not isinstance(nav, ops_scenario.NavField) and nav is not None:
             nav = ops_scenario.nav_field(st.scenario, device=st.p.device, sight=ops_scenario.nav_wants_sight(nav))
+        if nav_density is not None:
+            nav_density.radius_cells(nav.cell)
+            nav = ops_scenario.NavFieldDynamic(nav, st.seeds.numel())
         self._run_scenario(st, law, use_graph, frames_per_graph, walls=walls,
                            groups=None if group is None else ops_scenario.group_law(*group),
                            noise=None if noise is None else ops_scenario.noise_law(*noise, float(st.scenario.time_unit)),
-                           nav=nav)
+                           nav=nav, nav_density=nav_density)
         return scenarios.scenario_result(st)
 
     @staticmethod
-    def _run_scenario(st, law, use_graph, frames_per_graph, graph=None, walls=None, groups=None, noise=None, nav=None):
+    def _run_scenario(st, law, use_graph, frames_per_graph, graph=None, walls=None, groups=None, noise=None, nav=None,
+                      nav_density=None):
         """frame 0's spawn, then T - 1 MLAPM frames: K = frames_per_graph of them (offsets 0 .. K-1 and one counter add)
         captured into one graph and replayed when use_graph, the rest eagerly.  law: a mlapm_law or a law table; walls:
         None or ops_scenario.scenario_step_mlapm's (grid, wall law or wall table) for the frames with the wall term; groups: None
         or its group law or group table (a grouped clip scene's frames with the group term); noise: None or its noise law or
         noise table (the frames with the fluctuation term; its state is allocated here, before any capture); nav: None or
-        the scene's ops_scenario.nav_field (the frames routed by the floor field).  Returns
+        the scene's ops_scenario.nav_field (the frames routed by the floor field).  nav_density: None or an
+        ops_scenario.nav_density_law, with nav an ops_scenario.NavFieldDynamic of the state's members: the field starts as its
+        static base and is updated (ops_scenario.nav_field_update) before the frame at counter value t whenever
+        (t - 1) % every == 0 -- a function of the frame counter alone, so eager and captured runs update at the same
+        frames; in a captured run that is between replays (a host read per batch of the solve, nothing captured), and every
+        must be a multiple of frames_per_graph: ValueError before any launch otherwise.  Returns
         the captured graph (None for an eager run); passed back as `graph` with the same state, the run replays it
         instead of capturing again."""
         import torch
         from .. import ops_scenario, hip_graphs_safe
+        steps = st.T - 1
+        if use_graph is None:
+            use_graph = steps > 8
+        per = max(1, int(frames_per_graph))
+        if nav_density is not None:
+            if not isinstance(nav, ops_scenario.NavFieldDynamic):
+                raise TypeError(f'nav_density: nav, an ops_scenario.NavFieldDynamic expected, got {type(nav).__name__}')
+            if use_graph and steps >= per + 1 and nav_density.every % per:
+                raise ValueError(f'nav_density: every = {nav_density.every} frames is not a multiple of frames_per_graph = '
+                                 f'{per}: a captured run updates the field between replays')
+
+        def update(t):                                       # before the frame at counter value t
+            if nav_density is not None and t >= 1 and (t - 1) % nav_density.every == 0:
+                ops_scenario.nav_field_update(nav, st, nav_density)
         with torch.no_grad():
+            if nav_density is not None:
+                nav.reset()                                  # frame 0 -> 1 reads the static field
             ops_scenario.scenario_step_mlapm(st, None, init=True)     # frame 0: generate(n_initial)
             if noise is not None:
                 ops_scenario.scenario_noise_state(st)
-            steps = st.T - 1
-            if use_graph is None:
-                use_graph = steps > 8
-            per = max(1, int(frames_per_graph))
             done = 0
             if use_graph and steps >= per + 1 and hip_graphs_safe():
                 ops_scenario.scenario_step_mlapm(st, law, walls=walls, groups=groups, noise=noise, nav=nav)     # a real frame, also warms the library up
@@ -251,17 +282,19 @@ class MLAPM:
                             ops_scenario.scenario_step_mlapm(st, law, frame_offset=k, advance=False, walls=walls, groups=groups,
                                                              noise=noise, nav=nav)
                         st.t.add_(per)
-                for _ in range((steps - done) // per):
+                for j in range((steps - done) // per):
+                    update(done + j * per)                   # (every is a multiple of per: no update falls inside a replay)
                     graph.replay()
                 done += (steps - done) // per * per
-            for _ in range(steps - done):
+            for t in range(done, steps):
+                update(t)
                 ops_scenario.scenario_step_mlapm(st, law, walls=walls, groups=groups, noise=noise, nav=nav)
         return graph
 
     # ---- one law per member (piml_scenario_step_mlapm_laws): a sweep of candidates x seeds in one ensemble run ----
     @staticmethod
     def simulate_sweep(scenario, frames, params, seeds, capacity=None, use_graph=None, radius=0.3, device='cuda',
-                       hist_width=2, frames_per_graph=8, wall_cutoff=DEFAULT_WALL_CUTOFF, nav=None):
+                       hist_width=2, frames_per_graph=8, wall_cutoff=DEFAULT_WALL_CUTOFF, nav=None, nav_density=None):
         """simulate_ensemble for every candidate of `params` in the same launches: params is a list of C dicts in
         MLAPM(**params) form (version, tau, A, B and optionally C, D, theta; an optional 'radius' overrides `radius` for
         that candidate; optionally the wall term's Aw, Bw, in every candidate or in none -- wall_cutoff is common to the
@@ -274,14 +307,33 @@ class MLAPM:
         ValueError: an empty list, an unknown or missing key, candidates with and without a wall term, a wall term in a
         scene without obstacles, candidates with and without a group term, a group term in a scene without groups,
         C * len(seeds) > 65535.  nav: simulate_scenario's; every candidate and seed shares the one field of the scene.
+        nav_density: simulate_scenario's; one density law per run, shared by every candidate, and a field per member.
         Returns a scenarios.ScenarioSweep."""
         return SweepRun(scenario, frames, len(params) if hasattr(params, '__len__') else 0, seeds, capacity, use_graph,
-                        device, hist_width, frames_per_graph, wall_cutoff, nav).run(params, radius)
+                        device, hist_width, frames_per_graph, wall_cutoff, nav, nav_density).run(params, radius)
 
 
 SWEEP_KEYS = ('version', 'tau', 'A', 'B', 'C', 'D', 'theta', 'radius', 'Aw', 'Bw')
 GROUP_KEYS = ('Ag', 'group_dist')       # a candidate's optional group term (a grouped clip scene)
 NOISE_KEYS = ('An', 'noise_tau')        # a candidate's optional fluctuation term
+
+
+def check_nav_density(nav, nav_density):
+    """The nav_density= argument of MLAPM.simulate_* and SweepRun against their nav= (False already None): TypeError unless it
+    is None or an ops_scenario.nav_density_law; ValueError without a floor field, or with one that has the any-angle table
+    (a uniform-cost construction)."""
+    from .. import ops_scenario
+    if nav_density is None:
+        return
+    if not isinstance(nav_density, ops_scenario.NavDensityLaw):
+        raise TypeError(f'nav_density: an ops_scenario.nav_density_law(...) expected, got {type(nav_density).__name__}')
+    if nav is None:
+        raise ValueError('nav_density: the density term belongs to the floor field and needs nav=True or a nav_field(...)')
+    if ops_scenario.nav_wants_sight(nav):
+        raise ValueError('nav_density: the any-angle table is a uniform-cost construction and cannot carry a density term '
+                         "(nav=True or a nav_field without sight=True, not 'sight')")
+    if isinstance(nav, ops_scenario.NavFieldDynamic):
+        raise ValueError('nav_density: nav, the scene\'s static nav_field(...) expected (the run makes its own dynamic field)')
 
 
 def noise_args(args):
@@ -413,9 +465,11 @@ class SweepRun:
     generation of calibrate.calibrate_mlapm_to_stats is.  Every run is bitwise a fresh MLAPM.simulate_sweep."""
 
     def __init__(self, scenario, frames, n_candidates, seeds, capacity=None, use_graph=None, device='cuda', hist_width=2,
-                 frames_per_graph=8, wall_cutoff=DEFAULT_WALL_CUTOFF, nav=None):
+                 frames_per_graph=8, wall_cutoff=DEFAULT_WALL_CUTOFF, nav=None, nav_density=None):
         from .. import ops_scenario, scenarios
         self.nav = None if nav is False else nav              # True, or the scene's ops_scenario.nav_field: every run's
+        self.nav_density = nav_density                        # None, or the one ops_scenario.nav_density_law of every run
+        check_nav_density(self.nav, nav_density)
         if self.nav is not None:
             ops_scenario.nav_wants_sight(self.nav)
             ops_scenario.check_nav_scene(scenario)
@@ -465,6 +519,9 @@ class SweepRun:
             if not isinstance(self.nav, ops_scenario.NavField) and self.nav is not None:
                 self.nav = ops_scenario.nav_field(self.st.scenario, device=self.st.p.device,
                                                   sight=ops_scenario.nav_wants_sight(self.nav))
+            if self.nav_density is not None:
+                self.nav_density.radius_cells(self.nav.cell)
+                self.nav = ops_scenario.NavFieldDynamic(self.nav, self.st.seeds.numel())
         else:
             if (walls is None) != (self.wall_table is None):  # the captured frames are those of the first run's kernel
                 raise ValueError('SweepRun: every run of a sweep has a wall term (Aw, Bw) or none has')
@@ -482,7 +539,8 @@ class SweepRun:
             ops_scenario.scenario_state_reset(self.st)
         self.graph = MLAPM._run_scenario(self.st, self.table, self.use_graph, self.frames_per_graph, graph=self.graph,
                                          walls=None if walls is None else (self.wall_grid, self.wall_table),
-                                         groups=self.group_table, noise=self.noise_table, nav=self.nav)
+                                         groups=self.group_table, noise=self.noise_table, nav=self.nav,
+                                         nav_density=self.nav_density)
         ens = scenarios.scenario_result(self.st)
         fields = dict(vars(ens))
         return scenarios.ScenarioSweep(params=params, n_candidates=self.n_candidates, seeds_per_candidate=S, **fields)

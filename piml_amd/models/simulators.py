@@ -48,6 +48,13 @@ class RolloutResult(types.SimpleNamespace):
     """What the reference returns as a `RawData` from get_multiple_rollouts (simulators.py:655-657)."""
 
 
+def _no_nav_density(nav_density):
+    """The density-aware floor field is built for the MLAPM-driven frame only."""
+    if nav_density is not None:
+        raise NotImplementedError('nav_density: the density-aware floor field is not built for the network-driven frame '
+                                  '(piml_scenario_step_nav shares one field); MLAPM.simulate_scenario / _ensemble / _sweep have it')
+
+
 def _gather_waypoints(waypoints, dest_idx):
     """waypoints (*c, D, N, 2), dest_idx (*c, N) -> (*c, N, 2)   (simulators.py:614-616)."""
     idx = dest_idx.unsqueeze(-2).unsqueeze(-1).expand(*dest_idx.shape[:-1], 1, dest_idx.shape[-1], 2)
@@ -463,7 +470,7 @@ class BaseSimulator(Pedestrians):
                              time_unit=data.time_unit)
 
     # ---- open-world simulation: the loop the reference stubs (BaseSimulator.run / run_single_step, simulators.py:834-838) ----
-    def simulate_scenario(self, scenario, frames, seed=0, capacity=None, use_graph=None, nav=None):
+    def simulate_scenario(self, scenario, frames, seed=0, capacity=None, use_graph=None, nav=None, nav_density=None):
         """Simulate `frames` frames of an entry / exit scene (piml_amd.scenarios.Scenario: gc_scenario() or a synthetic scene
         of piml_amd.scenarios.SCENARIOS) with the current model: frame 0 spawns the scenario's initial agents, every further
         frame is model -> one scenario_frame_kernel launch (integrate, arrive, retire, Poisson arrivals routed around the
@@ -479,16 +486,21 @@ class BaseSimulator(Pedestrians):
         keeps it off them.  Arrival, retirement and the recorded `destination` stay the scene's own, and the arrivals do not
         depend on the field.  res.state.steer holds the last frame's targets.  A scene of gates only (gc_scenario() with
         route_max_iters=0, scenarios.floorplan_scenario): ValueError otherwise (ops_scenario.check_nav_scene).
+        nav_density: NOT BUILT for the network-driven frame (MLAPM.simulate_scenario has it): anything but None raises
+        NotImplementedError.
         Returns a ScenarioResult."""
+        _no_nav_density(nav_density)
         return self._in_scenario_mode(lambda: self._simulate(scenario, frames, capacity, use_graph, nav=nav, seed=seed))
 
-    def simulate_ensemble(self, scenario, frames, seeds, capacity=None, use_graph=None, nav=None):
+    def simulate_ensemble(self, scenario, frames, seeds, capacity=None, use_graph=None, nav=None, nav_density=None):
         """`simulate_scenario` for every seed of `seeds` at once: S = len(seeds) simulations of one scene with one capacity
         (default: as simulate_scenario's, which does not depend on the seed), every frame of all of them one network
         forward over the S * capacity rows, one scenario_frame_kernel launch and one relative-feature launch
         (captured and replayed as simulate_scenario's frame).  Member m is the simulation of seed seeds[m]: the network
         sees flat (S * capacity, .) rows, so members never see each other.  nav: simulate_scenario's; every member shares
-        the one field of the scene.  Returns a scenarios.ScenarioEnsemble."""
+        the one field of the scene.  nav_density: simulate_scenario's (not built: NotImplementedError).  Returns a
+        scenarios.ScenarioEnsemble."""
+        _no_nav_density(nav_density)
         seeds = [int(x) for x in seeds]
         if not seeds:
             raise ValueError('simulate_ensemble: at least one seed expected')

@@ -1,7 +1,8 @@
 """Open-world scenario operators over the C ABI (include/piml_hip.h: piml_scenario_step, piml_scenario_step_rules,
 piml_scenario_step_members, piml_scenario_step_nav, piml_scenario_step_mlapm, piml_scenario_step_mlapm_laws, piml_scenario_step_mlapm_walls,
 piml_wall_force, piml_scenario_step_mlapm_groups, piml_group_force, piml_scenario_step_mlapm_noise, piml_noise_force,
-piml_nav_relax, piml_nav_direction, piml_scenario_step_mlapm_nav, piml_scenario_route).
+piml_nav_relax, piml_nav_direction, piml_scenario_step_mlapm_nav, piml_nav_density, piml_nav_cost, piml_nav_relax_cost,
+piml_scenario_step_mlapm_navdyn, piml_scenario_route).
 
 `scenario_state` allocates the persistent (static-address) buffers of one simulation or an ensemble and the
 `piml_scenario` descriptor that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive,
@@ -205,6 +206,9 @@ def scenario_step(st, a_next=None, init=False, nav=None):
     other than GC's, route_max_iters != 0, or a field of another number of gates."""
     if nav is not None:
         _check_nav(st, nav)
+        if isinstance(nav, NavFieldDynamic):
+            raise NotImplementedError('scenario_step: a field per member (NavFieldDynamic) is not built for the network-driven '
+                                      'frame; scenario_step_mlapm has it')
     if getattr(st, 'groups', None) is not None:
         raise ValueError("scenario_step: a 'clip_groups' scene runs under the MLAPM frame only (scenario_step_mlapm)")
     if not init:
@@ -809,6 +813,229 @@ def nav_direction(position, gate, destination, field, return_branch=False, sight
     return (e, branch, nb) if return_branch else e
 
 
+# ---- the density-aware floor field (piml_nav_density, piml_nav_cost, piml_nav_relax_cost; csrc/navdensity.hip) ----
+NAV_MAX_RADIUS = 8                     # cells: the cost window's radius (navdensity.hip)
+
+
+class NavDensityLaw:
+    """nav_density_law's value: kd, rho0, radius (metres), fmax, every (frames)"""
+
+    def __init__(self, kd, rho0, radius, fmax, every):
+        self.kd, self.rho0, self.radius, self.fmax, self.every = kd, rho0, radius, fmax, every
+
+    def radius_cells(self, cell):
+        """r = round(radius / cell) cells of a grid of side `cell`; ValueError beyond 8"""
+        r = int(round(self.radius / float(cell)))
+        if r > NAV_MAX_RADIUS:
+            raise ValueError(f'nav density law: radius {self.radius} m is {r} cells of {float(cell):g} m, more than '
+                             f'{NAV_MAX_RADIUS}')
+        return r
+
+    def __repr__(self):
+        return (f'nav_density_law(kd={self.kd}, rho0={self.rho0}, radius={self.radius}, fmax={self.fmax}, '
+                f'every={self.every})')
+
+
+def nav_density_law(kd, rho0=0.5, radius=0.75, fmax=8.0, every=8):
+    """The density term of a floor field: a cell's slowness is f = min(1 + kd max(rho - rho0, 0), fmax), rho (1/m^2) the
+    agents counted in the square window of about `radius` metres around the cell (r = round(radius / cell) cells, at most 8)
+    over its area, and the field is solved again every `every` frames.  kd (m^2) has no default: as with Aw, Ag and An there
+    is no density term unless one is given; kd = 0 is the static field, solved again.  ValueError unless kd >= 0, rho0 >= 0,
+    radius >= 0 and fmax >= 1 are finite and every is an integer >= 1."""
+    kd, rho0, radius, fmax = float(kd), float(rho0), float(radius), float(fmax)
+    if not all(math.isfinite(x) for x in (kd, rho0, radius, fmax)) or kd < 0 or rho0 < 0 or radius < 0 or fmax < 1:
+        raise ValueError(f'nav density law: finite kd >= 0, rho0 >= 0, radius >= 0 and fmax >= 1 expected, got kd={kd}, '
+                         f'rho0={rho0}, radius={radius}, fmax={fmax}')
+    if isinstance(every, bool) or int(every) != every or int(every) < 1:
+        raise ValueError(f'nav density law: every, a whole number of frames >= 1 expected, got {every!r}')
+    return NavDensityLaw(kd, rho0, radius, fmax, int(every))
+
+
+def _check_density_law(law):
+    if not isinstance(law, NavDensityLaw):
+        raise TypeError(f'law: a nav_density_law(...) expected, got {type(law).__name__}')
+
+
+def _base_field(field):
+    if not isinstance(field, NavField):
+        raise TypeError(f'field: a nav_field(...) expected, got {type(field).__name__}')
+    return field
+
+
+def nav_density(position, mask, field, out=None):
+    """The present agents per cell of `field`'s grid (piml_nav_density): position (members, capacity, 2) or (capacity, 2)
+    float32, mask (members, capacity) or (capacity), not 0 for a present slot -> count (members, gy, gx) int32 (one member
+    for a single run).  An agent's cell is nav_direction's; absent slots, NaN positions and cells outside the grid deposit
+    nothing.  out: a count tensor to write in place (it need not be zero)."""
+    field = _base_field(field)
+    p = _gpu_f32('position', position)
+    m = _gpu_f32('mask', mask)
+    if p.dim() == 2:
+        p, m = p.unsqueeze(0), m.unsqueeze(0)
+    if p.dim() != 3 or p.shape[-1] != 2 or tuple(m.shape) != tuple(p.shape[:2]) or p.shape[1] < 1 or p.shape[0] < 1:
+        raise ValueError(f'nav_density: position (members, capacity, 2) and mask (members, capacity) expected, got '
+                         f'{tuple(p.shape)}, {tuple(m.shape)}')
+    if p.device != field.blocked.device or m.device != p.device:
+        raise ValueError(f'nav_density: position on {p.device}, mask on {m.device}, the field on {field.blocked.device}')
+    M, cap = int(p.shape[0]), int(p.shape[1])
+    if out is None:
+        out = torch.empty(M, field.gy, field.gx, device=p.device, dtype=torch.int32)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (M, field.gy, field.gx) or out.device != p.device or not out.is_contiguous():
+        raise ValueError(f'nav_density: out, a contiguous int32 {(M, field.gy, field.gx)} tensor on {p.device} expected')
+    with torch.cuda.device(p.device):
+        _lib.check(_lib.lib().piml_nav_density(_ptr(p), _ptr(m), M, cap, field.x0, field.y0, field.cell, field.gx, field.gy,
+                                               _ptr(out), _stream()), 'piml_nav_density')
+    return out
+
+
+def nav_cost(count, field, law, out=None):
+    """The slowness planes of piml_nav_cost: count (members, gy, gx) int32 of nav_density -> f (members, gy, gx) float32 under
+    the nav_density_law `law` on `field`'s grid.  Blocked cells count in the window's area (a known limit)."""
+    field = _base_field(field)
+    _check_density_law(law)
+    r = law.radius_cells(field.cell)
+    if not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.dim() != 3 or \
+            tuple(count.shape[1:]) != (field.gy, field.gx):
+        raise ValueError(f'nav_cost: count, an int32 (members, {field.gy}, {field.gx}) tensor expected')
+    if count.device.type != 'cuda' or count.device != field.blocked.device:
+        raise _lib.PimlHipError(f'nav_cost: count on the field\'s GPU expected (piml_amd has no CPU path), got {count.device}')
+    count = count.contiguous()
+    if out is None:
+        out = torch.empty(count.shape, device=count.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != tuple(count.shape) or out.device != count.device or not out.is_contiguous():
+        raise ValueError(f'nav_cost: out, a contiguous float32 {tuple(count.shape)} tensor on {count.device} expected')
+    with torch.cuda.device(count.device):
+        _lib.check(_lib.lib().piml_nav_cost(_ptr(count), int(count.shape[0]), field.gx, field.gy, field.cell, r, law.kd,
+                                            law.rho0, law.fmax, _ptr(out), _stream()), 'piml_nav_cost')
+    return out
+
+
+def _relax_cost(blocked, goal, cost, a, b, changed, launches):
+    """nav_relax_cost's loop on buffers the caller owns; a holds the start.  -> (the buffer with the result, steps)"""
+    M, (G, gy, gx) = int(cost.shape[0]), (int(n) for n in goal.shape)
+
+    def queue(n):
+        with torch.cuda.device(goal.device):
+            _lib.check(_lib.lib().piml_nav_relax_cost(_ptr(blocked), _ptr(goal), _ptr(cost), _ptr(a), _ptr(b), M, G, gx, gy,
+                                                      int(n), _ptr(changed), _stream()), 'piml_nav_relax_cost')
+    if launches is not None:
+        queue(launches)
+        return (b if int(launches) & 1 else a), int(launches) * NAV_STEPS
+    steps = 0
+    while True:
+        changed.zero_()
+        queue(NAV_BATCH)                                     # an even number of launches: the result is in a
+        steps += NAV_BATCH * NAV_STEPS
+        if not bool(changed.any().item()):
+            return a, steps
+        if steps - NAV_BATCH * NAV_STEPS >= gx * gy:         # the steps before this batch were enough, and it still changed
+            raise RuntimeError(f'nav_relax_cost: no fixed point after {steps} steps on a {gx} x {gy} grid')
+
+
+def nav_relax_cost(blocked, goal, cost, launches=None):
+    """The weighted eikonal solve of piml_nav_relax_cost from the cold start: blocked (gy, gx) uint8 and goal (G, gy, gx)
+    uint8 shared by all members, cost (members, gy, gx) float32 >= 1 -> (u (members, G, gy, gx) float32 in cell units, the
+    number of Jacobi steps queued).  launches = None: batches of 16 launches of 8 steps until a batch changed nothing in any
+    plane (a fixed point: u only decreases from the cold start); RuntimeError if gx gy steps were not enough.  launches = n:
+    exactly n launches, wherever that leaves the field."""
+    if blocked.dtype != torch.uint8 or goal.dtype != torch.uint8 or goal.dim() != 3 or tuple(blocked.shape) != tuple(goal.shape[1:]):
+        raise ValueError(f'nav_relax_cost: blocked (gy, gx) and goal (G, gy, gx) uint8 expected, got {blocked.dtype} '
+                         f'{tuple(blocked.shape)}, {goal.dtype} {tuple(goal.shape)}')
+    if goal.device.type != 'cuda' or blocked.device != goal.device:
+        raise _lib.PimlHipError(f'nav_relax_cost: GPU tensors on one device expected (piml_amd has no CPU path), got '
+                                f'{blocked.device}, {goal.device}')
+    cost = _gpu_f32('cost', cost)
+    if cost.dim() != 3 or tuple(cost.shape[1:]) != tuple(blocked.shape) or cost.shape[0] < 1 or cost.device != goal.device:
+        raise ValueError(f'nav_relax_cost: cost (members, {blocked.shape[0]}, {blocked.shape[1]}) on {goal.device} expected, '
+                         f'got {tuple(cost.shape)} on {cost.device}')
+    M = int(cost.shape[0])
+    blocked, goal = blocked.contiguous(), goal.contiguous()
+    start = torch.where(goal != 0, 0.0, float('inf')).to(torch.float32)
+    a = start.unsqueeze(0).repeat(M, 1, 1, 1).contiguous()
+    b = torch.empty_like(a)
+    changed = torch.zeros(M * int(goal.shape[0]), device=goal.device, dtype=torch.int32)
+    return _relax_cost(blocked, goal, cost, a, b, changed, launches)
+
+
+class NavFieldDynamic(NavField):
+    """A floor field per member, solved again while the scene runs (nav_field_update): it wraps the scene's static NavField
+    `base` -- blocked, goal, the grid scalars and near are the base's -- and owns count, cost (members, gy, gx), u
+    (members, G, gy, gx) float32, which the frame reads (desc points at it; member_stride = G gy gx elements), the solver's
+    second buffer and its changed flags.  All are allocated here, once, before any capture, and written in place.  u starts
+    as the base's field in every member; iterations is the steps of the last update, updates their number.
+    ValueError for a base with the any-angle table: that table is a uniform-cost construction."""
+
+    def __init__(self, base, members=1):
+        if isinstance(base, NavFieldDynamic) or not isinstance(base, NavField):
+            raise TypeError(f'nav field: a static nav_field(...) expected, got {type(base).__name__}')
+        if base.sight_desc is not None:
+            raise ValueError('nav density: the any-angle table is a uniform-cost construction and cannot carry a density '
+                             'term (nav=True or a nav_field without sight=True)')
+        M = int(members)
+        if not 1 <= M <= MAX_MEMBERS or M * base.G > MAX_MEMBERS or M * base.G * base.gy * base.gx > 2 ** 31 - 1:
+            raise ValueError(f'nav density: {M} members x {base.G} gates on a {base.gx} x {base.gy} grid: at most '
+                             f'{MAX_MEMBERS} planes and 2^31 - 1 cells')
+        self.base, self.members = base, M
+        self.blocked, self.goal = base.blocked.contiguous(), base.goal.contiguous()
+        self.G, self.gy, self.gx = base.G, base.gy, base.gx
+        self.x0, self.y0, self.cell, self.near = base.x0, base.y0, base.cell, base.near
+        self.clearance, self.iterations, self.updates = base.clearance, 0, 0
+        dev = base.u.device
+        self.count = torch.zeros(M, self.gy, self.gx, device=dev, dtype=torch.int32)
+        self.cost = torch.ones(M, self.gy, self.gx, device=dev, dtype=torch.float32)
+        self.u = base.u.unsqueeze(0).repeat(M, 1, 1, 1).contiguous()
+        self.u_b = torch.empty_like(self.u)
+        self.changed = torch.zeros(M * self.G, device=dev, dtype=torch.int32)
+        self.start = torch.where(self.goal != 0, 0.0, float('inf')).to(torch.float32).contiguous()      # the cold start
+        self.member_stride = self.G * self.gy * self.gx
+        d = _lib.NavGrid()
+        d.u, d.G, d.gx, d.gy = self.u.data_ptr(), self.G, self.gx, self.gy
+        d.x0, d.y0, d.cell, d.near = self.x0, self.y0, self.cell, self.near
+        self.desc = d
+        self.w = self.parent = self.sight_desc = None
+        self.sight_iterations = 0
+
+    def reset(self):
+        """every member's u back to the base's static field, in place (the start of a run)"""
+        self.u.copy_(self.base.u.unsqueeze(0).expand_as(self.u))
+        self.iterations = self.updates = 0
+
+    def member(self, m):
+        """member m's planes as a static NavField (for nav_direction)"""
+        return NavField(self.u[int(m)], self.blocked, self.goal, self.x0, self.y0, self.cell, self.near, self.clearance,
+                        self.iterations)
+
+    def to_numpy(self):
+        out = super().to_numpy()
+        out.count, out.cost, out.members = self.count.cpu().numpy(), self.cost.cpu().numpy(), self.members
+        return out
+
+    def reachable(self, g):
+        return self.base.reachable(g)
+
+
+def nav_field_update(field, st, law):
+    """One update of a NavFieldDynamic from the state's present agents: density (st.p, st.mask -> field.count), cost
+    (-> field.cost) and a solve FROM THE COLD START into field.u, per member, all in place.  A warm start is wrong: the
+    minimum of the update keeps stale low values where the cost rose.  Batches of 16 launches (an even number, so the result
+    is in the buffer the frame reads) until a batch changed nothing: one host read per batch, so this is not capturable and
+    runs between replays.  Returns the steps queued (also field.iterations)."""
+    if not isinstance(field, NavFieldDynamic):
+        raise TypeError(f'field: a NavFieldDynamic expected, got {type(field).__name__}')
+    _check_density_law(law)
+    if field.members != st.seeds.numel():
+        raise ValueError(f'nav density: a field of {field.members} members for a state of {st.seeds.numel()}')
+    if field.u.device != st.p.device:
+        raise ValueError(f'nav field on {field.u.device}, the state on {st.p.device}')
+    nav_density(st.p, st.mask, field, out=field.count)
+    nav_cost(field.count, field, law, out=field.cost)
+    field.u.copy_(field.start.unsqueeze(0).expand_as(field.u))
+    u, steps = _relax_cost(field.blocked, field.goal, field.cost, field.u, field.u_b, field.changed, None)
+    assert u is field.u
+    field.iterations, field.updates = steps, field.updates + 1
+    return steps
+
+
 def _noise_arg_is_table(st, noise):
     """scenario_step_mlapm's check of `noise`; True for a table"""
     noise_table = isinstance(noise, torch.Tensor)
@@ -858,6 +1085,8 @@ def _check_nav(st, nav):
         raise ValueError(f'nav: a field of {nav.G} gates for a scene of {st.scenario.entries.shape[0]}')
     if nav.u.device != st.p.device:
         raise ValueError(f'nav field on {nav.u.device}, the state on {st.p.device}')
+    if isinstance(nav, NavFieldDynamic) and nav.members != st.seeds.numel():
+        raise ValueError(f'nav density: a field of {nav.members} members for a state of {st.seeds.numel()}')
 
 
 def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, groups=None, init=False, noise=None, nav=None):
@@ -886,7 +1115,9 @@ def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, group
     steers to p + nav_direction(p, the gate of its waypoint, destination) in place of its destination (to the destination
     itself in the lookup's branch 0), with or without walls and noise; everything else is the same frame.  ValueError (check_nav_scene) for a grouped scene, a scene rule
     other than GC's, route_max_iters != 0, or a field of another number of gates.  A field with the any-angle table
-    (nav_field(..., sight=True)) goes to piml_scenario_step_mlapm_sight: the lookup with its sight branch, the same frame."""
+    (nav_field(..., sight=True)) goes to piml_scenario_step_mlapm_sight: the lookup with its sight branch, the same frame.
+    A NavFieldDynamic (a field per member, nav_field_update) goes to piml_scenario_step_mlapm_navdyn: member m looks its
+    directions up in its own planes, the same frame; ValueError when its members are not the state's."""
     grouped = getattr(st, 'groups', None) is not None
     if init:
         if not grouped:
@@ -945,7 +1176,10 @@ def scenario_step_mlapm(st, law, frame_offset=0, advance=True, walls=None, group
                     None if wall is None or wall_table else ctypes.byref(wall), _ptr(wall) if wall_table else None,
                     ctypes.byref(nav.desc))
             tail = (None if na is None else ctypes.byref(na), int(frame_offset), _stream())
-            if nav.sight_desc is not None:
+            if isinstance(nav, NavFieldDynamic):
+                _lib.check(_lib.lib().piml_scenario_step_mlapm_navdyn(*head, nav.member_stride, *tail),
+                           'piml_scenario_step_mlapm_navdyn')
+            elif nav.sight_desc is not None:
                 _lib.check(_lib.lib().piml_scenario_step_mlapm_sight(*head, ctypes.byref(nav.sight_desc), *tail),
                            'piml_scenario_step_mlapm_sight')
             else:

@@ -28,6 +28,9 @@ reads.
     python -m piml_amd.simulate --law mlapm --scenario gc --nav [--nav-cell 0.25] [--nav-clearance 0.3] --out clip.npy
     python -m piml_amd.simulate --law mlapm --scene-plan plan.json --nav --nav-sight --out clip.npy
                                 (the same, steering along lines of sight: the field's any-angle table)
+    python -m piml_amd.simulate --law mlapm --scene-plan plan.json --nav --nav-density 2 [--nav-rho0 0.5]
+                                [--nav-density-radius 0.75] [--nav-fmax 8] [--nav-every 8] --seeds 0:32 --line-stats lines.json
+                                (the floor field's cost grows with the local density and is solved again every 8 frames)
     python -m piml_amd.simulate --checkpoint model.pt --scene-plan plan.json --route field --seeds 0:32 --obstacle-stats walls.json
                                 (the network on a floor plan: --route field|sight steers either law by the floor field)
 
@@ -90,6 +93,18 @@ def get_args(argv=None):
     p.add_argument('--nav-sight', dest='nav_sight', action='store_true',
                    help='--nav: also build the any-angle table (ops_scenario.nav_field(sight=True)); the agents steer along '
                         'lines of sight, at the next turning point of their shortest path, instead of down the gradient')
+    p.add_argument('--nav-density', dest='nav_density', type=float, default=None, metavar='KD',
+                   help='--law mlapm --nav: the density-aware floor field (ops_scenario.nav_density_law): a cell\'s travel cost '
+                        'is min(1 + KD max(rho - rho0, 0), fmax), and the field is solved again, per member, every --nav-every '
+                        'frames, so routed agents go round a congested door; not with --nav-sight, --route sight or --checkpoint')
+    p.add_argument('--nav-rho0', dest='nav_rho0', type=float, default=None, help='--nav-density: the density (1/m^2) the cost rises from (default 0.5)')
+    p.add_argument('--nav-density-radius', dest='nav_density_radius', type=float, default=None,
+                   help='--nav-density: half the side of the square window the density is counted in, metres (default 0.75; '
+                        'at most 8 cells)')
+    p.add_argument('--nav-fmax', dest='nav_fmax', type=float, default=None, help='--nav-density: the cap of the cost factor (default 8)')
+    p.add_argument('--nav-every', dest='nav_every', type=int, default=None,
+                   help='--nav-density: frames between two updates of the field (default 8; a multiple of 8, the frames of a '
+                        'captured graph)')
     p.add_argument('--frames', type=int, default=750)
     seed = p.add_mutually_exclusive_group()
     seed.add_argument('--seed', type=int, default=0, help='seed of the spawn schedule')
@@ -220,6 +235,25 @@ def get_args(argv=None):
         p.error('--nav-cell / --nav-clearance need --nav or --route')
     elif own.nav_sight:
         p.error('--nav-sight needs --nav (it adds the any-angle table to the floor field)')
+    own.density_law = None
+    if own.nav_density is not None:
+        if own.checkpoint or own.law != 'mlapm':
+            p.error('--nav-density is built for --law mlapm only: not with --checkpoint or the network law')
+        if own.route_sight:
+            p.error('--nav-density: the any-angle table is a uniform-cost construction: not with --nav-sight or --route sight')
+        if not own.routed:
+            p.error('--nav-density needs --nav (the density term belongs to the floor field)')
+        from .ops_scenario import nav_density_law
+        try:
+            own.density_law = nav_density_law(own.nav_density, 0.5 if own.nav_rho0 is None else own.nav_rho0,
+                                              0.75 if own.nav_density_radius is None else own.nav_density_radius,
+                                              8.0 if own.nav_fmax is None else own.nav_fmax,
+                                              8 if own.nav_every is None else own.nav_every)
+            own.density_law.radius_cells(own.nav_cell)
+        except ValueError as ex:
+            p.error(f'--nav-density: {ex}')
+    elif any(x is not None for x in (own.nav_rho0, own.nav_density_radius, own.nav_fmax, own.nav_every)):
+        p.error('--nav-rho0 / --nav-density-radius / --nav-fmax / --nav-every need --nav-density')
     if own.params_sweep is not None:
         if own.params is not None:
             p.error('--params-sweep takes the place of --params: not both')
@@ -379,6 +413,9 @@ def main(argv=None):
               f'{run_kw["nav"].cell:g} m, {run_kw["nav"].iterations} steps')
         if own.route_sight:
             print(f'[simulate] lines of sight: {run_kw["nav"].sight_iterations} steps')
+        if own.density_law is not None:
+            run_kw['nav_density'] = own.density_law
+            print(f'[simulate] density term: {own.density_law}')
     if own.law == 'mlapm' and own.mlapm_sweep is not None:
         return _sweep(sim, scenario, own, run_kw)
     if own.seeds is not None:
