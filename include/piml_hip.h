@@ -1354,6 +1354,54 @@ int piml_scenario_step_mlapm_navdyn(const piml_scenario* s, const piml_scenario_
                                     const piml_noise_args* noise /* NULL: no fluctuation */, int frame_offset, void* stream);
 
 /*
+ * Exit choice (ABI 35, additive): a routed agent re-decides which of a class of equivalent gates it is bound for.  The spawn
+ * law draws the destination gate uniformly at birth; u[g] at the agent's cell is the walking distance to gate g under the
+ * static field and a travel-time proxy under the density-weighted one, so the least u over a class is the nearest exit under
+ * the former and the quickest under the latter.
+ *
+ * piml_nav_choose_exit: ONE launch, in front of a scenario frame (network-driven or MLAPM), that re-decides the gate of every
+ * present slot of every member.  s, members and seeds are the frame entries' (seeds NULL: one member, key s->seed); nav and
+ * member_stride are piml_scenario_step_mlapm_navdyn's (0: one static field for all members); gate_class (G) device int32, the
+ * class of each gate, -1 = in no class; law->margin and law->commit in CELL units (metres / nav->cell, divided in float32 by
+ * the host); switch_count (members, capacity) device int32 or NULL; frame_offset as the MLAPM frame's.
+ * Schedule: with t = *frame_counter + frame_offset the kernel returns at once unless t >= 1 and (t - 1) % every == 0 -- the
+ * density update's schedule, tested on the device, so the launch can sit in front of every captured frame and eager and
+ * captured runs are bitwise each other; where an update falls on the same t the choice runs after it and reads the fresh field.
+ * Per slot i < min(spawned[t & 1], capacity) with mask != 0 and f = flag[i] in 0..1, cur = exit_idx[f][i]:
+ *   1. the spawn draws of calls 1 and 2 (stream 0x5CE00001 / 2, key = the member's seed, counter = ordinal i) are recomputed:
+ *      the origin gate oe, the destination point index di, the destination's offset words (w2.z, w2.w).  Nothing new is drawn
+ *      and no per-agent state is kept: slot = ordinal.
+ *   2. candidates: gates g with gate_class[g] == gate_class[cur] >= 0, g != oe and u[g][c] finite, c the agent's cell by
+ *      piml_nav_direction's cell formula.
+ *   3. the slot is left untouched when the position is NaN, c is outside the grid, cur is outside 0..G-1 or in no class, there
+ *      is no candidate, or u[cur][c] is finite and <= commit.
+ *   4. best = the candidate of least u, the lowest gate on a tie.  Switch iff u[cur][c] is not finite or
+ *      fadd(u[best][c], margin) < u[cur][c]: equality stays, best == cur never switches.  (An unreachable current gate is
+ *      left whatever the margin, +inf included.)
+ *   5. on a switch d' = entries[best][di] + unit24(w2.z, w2.w) spawn_offset, the spawn's formula operation for operation;
+ *      waypoints[q][i] = d' and exit_idx[q][i] = the entry nearest d' for q = f .. 1, destination[i] = d', switch_count[m][i]
+ *      += 1.  Rows below f, the recorded *_out buffers and every other field are not written.
+ * After a switch rows >= f are bitwise what the spawn would have written had its destination draw been `best`; a switch back
+ * restores the original destination bit for bit.  One wave per slot, lane g holding u[g]; no atomics, a slot's rows are
+ * written by its own wave only.  Every predicate is one correctly rounded float32 operation after another
+ * (tests/navchoice_ref.py gives the same bits).  Capturable.
+ * Known limits: a gate is both origin and destination under GC's law and only the agent's own origin gate is excluded; the
+ * class is looked up through exit_idx, the entry nearest the waypoint, not the drawn gate; the field may be up to `every`
+ * frames old; there is no per-agent preference or familiarity term.
+ * hipErrorInvalidValue (before any launch): a NULL s, nav, gate_class or law; the frame checks of piml_scenario_step on s;
+ * members outside 1..65535, a NULL seeds with members != 1; piml_nav_direction's grid checks; nav->G != s->E;
+ * s->route_max_iters != 0 or s->D < 2; law->every < 1; margin or commit negative or NaN; member_stride < 0; frame_offset < 0.
+ * gate_class is device memory: its values are the caller's to validate.
+ */
+typedef struct piml_exit_choice {
+    float margin, commit;                                   /* cell units */
+    int every;                                              /* frames between two passes, >= 1 */
+} piml_exit_choice;
+int piml_nav_choose_exit(const piml_scenario* s, int members, const uint64_t* seeds, const piml_nav_grid* nav,
+                         long long member_stride, const int* gate_class, const piml_exit_choice* law,
+                         int* switch_count /* may be NULL */, int frame_offset, void* stream);
+
+/*
  * The any-angle floor field: a second table beside u.  For every cell c of gate g, parent[g][c] is the next turning point
  * of the taut string from c to the gate -- the gate cell itself in open space, a corner cell round a wall -- and w[g][c]
  * the string's length in cells.  An agent in c steers at the centre of its parent along a straight segment that enters no

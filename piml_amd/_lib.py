@@ -128,6 +128,11 @@ class NavSight(ctypes.Structure):
     _fields_ = [('parent', _p), ('G', _i), ('gx', _i), ('gy', _i)]
 
 
+class ExitChoice(ctypes.Structure):
+    """piml_exit_choice (include/piml_hip.h)."""
+    _fields_ = [('margin', _f), ('commit', _f), ('every', _i)]
+
+
 SPAWN_LAWS = {'gc': 0, 'crosswalk': 1, 'square': 2, 'unit1': 3, 'unit2': 4, 'unit3': 5, 'clip': 6}     # PIML_SPAWN_*
 SPAWN_CLIP_GROUPS = 7          # PIML_SPAWN_CLIP_GROUPS ('clip_groups'): piml_scenario_step_mlapm_groups only, so not in SPAWN_LAWS
 ARRIVAL_RULES = {'gc': 0, 'radius': 1, 'x_band': 2, 'x_exit': 3}                             # PIML_ARRIVE_*
@@ -212,6 +217,7 @@ SIGNATURES = {
     'piml_nav_cost': [_p, _i, _i, _i, _f, _i, _f, _f, _f, _p, _p],
     'piml_nav_relax_cost': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
     'piml_scenario_step_mlapm_navdyn': [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _ll, _p, _i, _p],
+    'piml_nav_choose_exit': [_p, _i, _p, _p, _ll, _p, _p, _p, _i, _p],
     'piml_nav_sight_relax': [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
     'piml_nav_direction_sight': [_p, _p, _p, _ll, _p, _p, _p, _p, _p, _p],
     'piml_scenario_step_mlapm_sight': [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p],

@@ -36,6 +36,8 @@
 //                               each (w >> 8) 2^-24
 //                      call 3  (n lo, n hi, 0, 0x5CE00003): z = sqrt(-2 ln u1) cos(2 pi u2) in double, u1 = ((w0 >> 8) + 1)
 //                               2^-24, u2 = (w1 >> 8) 2^-24
+// The exit choice (piml_nav_choose_exit, scenario_choose_exit_kernel below) draws nothing new: it re-reads calls 1 and 2 of
+// the slot's ordinal -- the origin entry, the destination point index and the destination's offset words.
 // The dropout keep-mask stream uses c3 = (stream_id << 16) | sub with stream ids 0 and 1: stream 0x5CE0 is never one of
 // them.  The schedule depends on (seed, frame, ordinal) only, not on the dynamics; tests/scenario_ref.py restates it.
 //
@@ -1058,6 +1060,86 @@ __global__ __launch_bounds__(kMlScWaves * 64) void scenario_mlapm_navdyn_kernel(
     scenario_mlapm_body<kTable, kWalls, false, true, true>(K0, seeds, table, WG, wall, wall_table, GroupArgs{}, NA, NV);
 }
 
+// ---- exit choice (piml_nav_choose_exit): a routed agent re-decides which gate of its class it is bound for ----
+//
+// One launch in front of a frame, grid (agent blocks of 4 waves, members), one wave per slot.  It reads the frame counter t
+// (+ frame_offset, as the MLAPM frame) and returns at once unless t >= 1 and (t - 1) % every == 0 -- the density update's
+// schedule, on the device, so that the launch sits in front of every captured frame.  Lane g < G <= 64 holds u[g] at the
+// agent's cell (nav_direction's cell formula), the candidates -- gates of the current gate's class, the agent's own origin gate
+// excepted, u finite -- go through wave_argmin (least u, lowest gate on a tie), and the agent switches when its current gate
+// is unreachable or fadd(u[best], margin) < u[cur].  The origin gate, the destination point index and the offset words are
+// spawn_agent's draws of calls 1 and 2, recomputed from (seed, ordinal = slot): nothing new is drawn and nothing per agent is
+// stored.  On a switch rows flag .. 1 of waypoints / exit_idx and the destination are rewritten by lane 0 of the slot's own
+// wave, operation for operation as spawn_agent writes them (route_max_iters == 0: the waypoint is the destination); rows
+// below the flag, the records and every other field are not touched.  No atomics.
+struct ExitChoiceArgs {
+    piml_nav_grid NV;
+    long long member_stride;                                 // elements between two members' fields; 0: one field
+    const int* gate_class;                                   // (G), -1: in no class
+    piml_exit_choice law;                                    // margin, commit in cell units
+    int* switch_count;                                       // (members, capacity) or NULL
+    int frame_offset;
+};
+
+__global__ __launch_bounds__(kMlScWaves * 64) void scenario_choose_exit_kernel(const piml_scenario S0,
+                                                                              const unsigned long long* __restrict__ seeds,
+                                                                              const ExitChoiceArgs A) {
+    piml_scenario S = S0;
+    const float2* no_a = nullptr;
+    member_view(S, no_a, (int)blockIdx.y);
+    if (seeds) S.seed = seeds[blockIdx.y];
+    const long long t = *S.frame_counter + A.frame_offset;
+    if (t < 1 || (t - 1) % A.law.every != 0) return;         // (kernel-uniform) not a scheduled frame
+    const long long n = S.spawned[t & 1];
+    const int cap = S.capacity;
+    const int lane = threadIdx.x & 63;
+    const int i = (int)blockIdx.x * kMlScWaves + (int)(threadIdx.x >> 6);
+    if (i >= n || i >= cap) return;                          // wave-uniform from here on
+    if (S.mask[i] == 0.f) return;
+    const int f = S.flag[i];
+    if (f < 0 || f >= 2) return;
+    const piml_nav_grid& N = A.NV;
+    const int cur = S.exit_idx[(size_t)f * cap + i];
+    if (cur < 0 || cur >= N.G) return;
+    const int cls = A.gate_class[cur];
+    if (cls < 0) return;
+    const float2 p = ((const float2*)S.position)[i];
+    const float fcx = floorf(__fdiv_rn(__fsub_rn(p.x, N.x0), N.cell)), fcy = floorf(__fdiv_rn(__fsub_rn(p.y, N.y0), N.cell));
+    if (!(p.x == p.x && p.y == p.y && fcx >= 0.f && fcx < (float)N.gx && fcy >= 0.f && fcy < (float)N.gy)) return;
+    const size_t cells = (size_t)(N.gy * N.gx), c = (size_t)((int)fcy * N.gx + (int)fcx);
+    const float* __restrict__ u = N.u + (long long)blockIdx.y * A.member_stride;
+    const unsigned k0 = (unsigned)S.seed, k1 = (unsigned)(S.seed >> 32);
+    const PhiloxOut w1 = philox4x32_10((unsigned)i, 0u, 0u, kScenarioStream | 1u, k0, k1);
+    const int oe = (int)pick(w1.x, (unsigned)S.E);
+    const bool gate = lane < N.G;
+    const float ug = gate ? u[(size_t)lane * cells + c] : INFINITY;
+    const float ucur = __shfl(ug, cur, 64);
+    const bool cand = gate && lane != oe && nav_finite(ug) && A.gate_class[gate ? lane : 0] == cls;
+    float ub = cand ? ug : INFINITY;
+    int best = cand ? lane : 0x7fffffff;
+    wave_argmin(ub, best);
+    if (best == 0x7fffffff) return;                          // no candidate
+    const bool bound = nav_finite(ucur);
+    if (bound && ucur <= A.law.commit) return;               // committed to the gate in front of it
+    if (best == cur || !(!bound || __fadd_rn(ub, A.law.margin) < ucur)) return;
+    // the switch: spawn_agent's destination for the entry `best`, from the same point index and offset words
+    const PhiloxOut w2 = philox4x32_10((unsigned)i, 0u, 0u, kScenarioStream | 2u, k0, k1);
+    const unsigned di = pick(w1.w, (unsigned)S.P);
+    const float2* ent = (const float2*)S.entries;
+    const float2 ed = ent[(size_t)best * S.P + di];
+    const float2 d = make_float2(__fadd_rn(ed.x, __fmul_rn(unit24(w2.z), S.spawn_offset)),
+                                 __fadd_rn(ed.y, __fmul_rn(unit24(w2.w), S.spawn_offset)));
+    const int ex = nearest_entry_wave(d, ent, S.E, S.P);
+    if (lane == 0) {
+        for (int q = f; q < 2; ++q) {
+            ((float2*)S.waypoints)[(size_t)q * cap + i] = d;
+            S.exit_idx[(size_t)q * cap + i] = ex;
+        }
+        ((float2*)S.destination)[i] = d;
+        if (A.switch_count) A.switch_count[(size_t)blockIdx.y * (size_t)cap + (size_t)i] += 1;
+    }
+}
+
 }  // namespace piml
 
 namespace {
@@ -1473,6 +1555,29 @@ PIML_API int piml_scenario_step_mlapm_navdyn(const piml_scenario* s, const piml_
     if (member_stride < 0) return hipErrorInvalidValue;
     return step_mlapm_nav(s, r, members, seeds, law, law_table_device, wall_grid, wall, wall_table_device, nav, nullptr, noise,
                           frame_offset, stream, member_stride);
+}
+
+PIML_API int piml_nav_choose_exit(const piml_scenario* s, int members, const uint64_t* seeds, const piml_nav_grid* nav,
+                                  long long member_stride, const int* gate_class, const piml_exit_choice* law,
+                                  int* switch_count, int frame_offset, void* stream) {
+    if (!s || !gate_class || !law || members < 1 || members > 65535 || (!seeds && members != 1) || frame_offset < 0 ||
+        member_stride < 0)
+        return hipErrorInvalidValue;
+    if (!frame_args_ok(*s, nullptr, nullptr, 1)) return hipErrorInvalidValue;  // GC's descriptor (init = 1 waives a_next)
+    if (s->route_max_iters != 0 || s->D < 2) return hipErrorInvalidValue;      // the waypoint is the destination
+    if (!piml::nav_grid_ok(nav) || nav->G != s->E) return hipErrorInvalidValue;
+    if (law->every < 1 || !(law->margin >= 0.f) || !(law->commit >= 0.f)) return hipErrorInvalidValue;   // (NaN fails both)
+    piml::ExitChoiceArgs A;
+    A.NV = *nav;
+    A.member_stride = member_stride;
+    A.gate_class = gate_class;
+    A.law = *law;
+    A.switch_count = switch_count;
+    A.frame_offset = frame_offset;
+    const dim3 grid((unsigned)((s->capacity + piml::kMlScWaves - 1) / piml::kMlScWaves), (unsigned)members);
+    hipLaunchKernelGGL(piml::scenario_choose_exit_kernel, grid, dim3(piml::kMlScWaves * 64), 0, piml::as_stream(stream), *s,
+                       (const unsigned long long*)seeds, A);
+    return hipGetLastError();
 }
 
 PIML_API int piml_scenario_route(const float* origin, const float* destination, int n, const float* polyline, int R,

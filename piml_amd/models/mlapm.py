@@ -11,7 +11,9 @@ time noise_tau (piml_scenario_step_mlapm_noise); again `step`, `rollout` and the
 take nav=True | ops_scenario.nav_field(...): the agents of a scene of gates then descend a static floor field instead of
 walking the straight line to their destination (piml_scenario_step_mlapm_nav); the field is the scene's, not the law's.
 With nav_density=ops_scenario.nav_density_law(kd, ...) as well the field's travel cost grows with the local density and it is
-solved again, per member, while the scene runs (piml_scenario_step_mlapm_navdyn)."""
+solved again, per member, while the scene runs (piml_scenario_step_mlapm_navdyn).  With exit_choice=True | an
+ops_scenario.exit_choice_law(...) routed agents re-decide which gate of a class of equivalent exits they leave through
+(piml_nav_choose_exit, one launch in front of every frame)."""
 from .. import ops
 
 DEFAULT_WALL_CUTOFF = 2.0     # metres
@@ -146,7 +148,7 @@ class MLAPM:
                                       a.get('theta', 0.0), radius)
 
     def simulate_scenario(self, scenario, frames, seed=0, capacity=None, use_graph=None, radius=0.3, device='cuda',
-                          hist_width=2, frames_per_graph=8, nav=None, nav_density=None):
+                          hist_width=2, frames_per_graph=8, nav=None, nav_density=None, exit_choice=None):
         """Simulate `frames` frames of an entry / exit scene (piml_amd.scenarios: gc_scenario() or a scene of SCENARIOS)
         with this law, as BaseSimulator.simulate_scenario does with a PINNSF: frame 0 spawns the initial agents, every
         further frame is ONE launch -- MLAPM.step's force from the agents present in the frame (main_mlapm.py:18-36),
@@ -185,28 +187,37 @@ class MLAPM:
         round a congested door.  It needs nav = True or a field without the any-angle table: ValueError otherwise, and in a
         captured run when law.every is not a multiple of frames_per_graph (the update runs between replays).  The field an
         update leaves is read until the next one: it lags by up to law.every frames.
+        exit_choice = True or an ops_scenario.exit_choice_law(classes, margin, commit, every): every law.every frames a routed
+        agent bound for a gate of a class of equivalent exits re-decides among that class by the field's value at its cell --
+        the nearest exit under the static field, the quickest under nav_density's -- and, on a switch, gets the destination
+        the spawn would have given it for the new gate (piml_nav_choose_exit: one launch in front of every frame, inside the
+        captured graphs too; the schedule is tested on the device).  True takes the scene's exit_classes
+        (scenarios.floorplan_scenario(..., exits=)) with the law's defaults.  It needs nav: ValueError otherwise, for a
+        grouped scene, and for a gate beyond the scene's.  The result's exit_gate, exit_switches and exit_counts() tell who
+        left where.  Without the argument the run is what it was, bit for bit.
         Returns a scenarios.ScenarioResult."""
         return self._simulate(scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, nav=nav,
-                              nav_density=nav_density, seed=seed)
+                              nav_density=nav_density, exit_choice=exit_choice, seed=seed)
 
     def simulate_ensemble(self, scenario, frames, seeds, capacity=None, use_graph=None, radius=0.3, device='cuda',
-                          hist_width=2, frames_per_graph=8, nav=None, nav_density=None):
+                          hist_width=2, frames_per_graph=8, nav=None, nav_density=None, exit_choice=None):
         """simulate_scenario for every seed of `seeds` in the same launches (grid.y = member; members never see each
         other).  Member m is bitwise simulate_scenario(seed=seeds[m]) with the same capacity; every member shares the
-        floor field of nav; with nav_density every member has a field of its own, solved from its own crowd.  Returns a
-        scenarios.ScenarioEnsemble."""
+        floor field of nav; with nav_density every member has a field of its own, solved from its own crowd; exit_choice: simulate_scenario's, every member choosing by the field it
+        reads.  Returns a scenarios.ScenarioEnsemble."""
         seeds = [int(x) for x in seeds]
         if not seeds:
             raise ValueError('simulate_ensemble: at least one seed expected')
         return self._simulate(scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, nav=nav,
-                              nav_density=nav_density, seeds=seeds)
+                              nav_density=nav_density, exit_choice=exit_choice, seeds=seeds)
 
     def _simulate(self, scenario, frames, capacity, use_graph, radius, device, hist_width, frames_per_graph, nav=None,
-                  nav_density=None, **state_kw):
+                  nav_density=None, exit_choice=None, **state_kw):
         from .. import ops_scenario, scenarios
         law = self._law(radius)
         nav = None if nav is False else nav
         check_nav_density(nav, nav_density)
+        exit_choice = ops_scenario.resolve_exit_choice(scenario, exit_choice, nav)
         if nav is not None:
             ops_scenario.nav_wants_sight(nav)
             ops_scenario.check_nav_scene(scenario)
@@ -229,12 +240,12 @@ class MLAPM:
         self._run_scenario(st, law, use_graph, frames_per_graph, walls=walls,
                            groups=None if group is None else ops_scenario.group_law(*group),
                            noise=None if noise is None else ops_scenario.noise_law(*noise, float(st.scenario.time_unit)),
-                           nav=nav, nav_density=nav_density)
+                           nav=nav, nav_density=nav_density, exit_choice=exit_choice)
         return scenarios.scenario_result(st)
 
     @staticmethod
     def _run_scenario(st, law, use_graph, frames_per_graph, graph=None, walls=None, groups=None, noise=None, nav=None,
-                      nav_density=None):
+                      nav_density=None, exit_choice=None):
         """frame 0's spawn, then T - 1 MLAPM frames: K = frames_per_graph of them (offsets 0 .. K-1 and one counter add)
         captured into one graph and replayed when use_graph, the rest eagerly.  law: a mlapm_law or a law table; walls:
         None or ops_scenario.scenario_step_mlapm's (grid, wall law or wall table) for the frames with the wall term; groups: None
@@ -245,7 +256,10 @@ class MLAPM:
         static base and is updated (ops_scenario.nav_field_update) before the frame at counter value t whenever
         (t - 1) % every == 0 -- a function of the frame counter alone, so eager and captured runs update at the same
         frames; in a captured run that is between replays (a host read per batch of the solve, nothing captured), and every
-        must be a multiple of frames_per_graph: ValueError before any launch otherwise.  Returns
+        must be a multiple of frames_per_graph: ValueError before any launch otherwise.  exit_choice: None or an
+        ops_scenario.exit_choice_law, with nav: ops_scenario.nav_choose_exit goes in front of every frame, captured ones
+        too (its schedule is tested on the device, so it needs no such multiple; where an update falls on the same counter
+        value the update runs first and the choice reads the fresh field); st.exit_switches counts the switches.  Returns
         the captured graph (None for an eager run); passed back as `graph` with the same state, the run replays it
         instead of capturing again."""
         import torch
@@ -261,26 +275,35 @@ class MLAPM:
                 raise ValueError(f'nav_density: every = {nav_density.every} frames is not a multiple of frames_per_graph = '
                                  f'{per}: a captured run updates the field between replays')
 
+        if exit_choice is not None and nav is None:
+            raise ValueError('exit_choice: the choice reads the floor field and needs nav')
+
         def update(t):                                       # before the frame at counter value t
             if nav_density is not None and t >= 1 and (t - 1) % nav_density.every == 0:
                 ops_scenario.nav_field_update(nav, st, nav_density)
+
+        def frame(**kw):                                     # the choice launch, when there is one, then the frame
+            if exit_choice is not None:
+                ops_scenario.nav_choose_exit(st, nav, exit_choice, st.exit_switches, kw.get('frame_offset', 0))
+            ops_scenario.scenario_step_mlapm(st, law, walls=walls, groups=groups, noise=noise, nav=nav, **kw)
         with torch.no_grad():
             if nav_density is not None:
                 nav.reset()                                  # frame 0 -> 1 reads the static field
             ops_scenario.scenario_step_mlapm(st, None, init=True)     # frame 0: generate(n_initial)
             if noise is not None:
                 ops_scenario.scenario_noise_state(st)
+            if exit_choice is not None:
+                ops_scenario.scenario_exit_switches(st)      # (allocated before any capture)
             done = 0
             if use_graph and steps >= per + 1 and hip_graphs_safe():
-                ops_scenario.scenario_step_mlapm(st, law, walls=walls, groups=groups, noise=noise, nav=nav)     # a real frame, also warms the library up
+                frame()                                      # a real frame, also warms the library up
                 done = 1
                 if graph is None:
                     torch.cuda.synchronize()
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
                         for k in range(per):
-                            ops_scenario.scenario_step_mlapm(st, law, frame_offset=k, advance=False, walls=walls, groups=groups,
-                                                             noise=noise, nav=nav)
+                            frame(frame_offset=k, advance=False)
                         st.t.add_(per)
                 for j in range((steps - done) // per):
                     update(done + j * per)                   # (every is a multiple of per: no update falls inside a replay)
@@ -288,13 +311,14 @@ class MLAPM:
                 done += (steps - done) // per * per
             for t in range(done, steps):
                 update(t)
-                ops_scenario.scenario_step_mlapm(st, law, walls=walls, groups=groups, noise=noise, nav=nav)
+                frame()
         return graph
 
     # ---- one law per member (piml_scenario_step_mlapm_laws): a sweep of candidates x seeds in one ensemble run ----
     @staticmethod
     def simulate_sweep(scenario, frames, params, seeds, capacity=None, use_graph=None, radius=0.3, device='cuda',
-                       hist_width=2, frames_per_graph=8, wall_cutoff=DEFAULT_WALL_CUTOFF, nav=None, nav_density=None):
+                       hist_width=2, frames_per_graph=8, wall_cutoff=DEFAULT_WALL_CUTOFF, nav=None, nav_density=None,
+                       exit_choice=None):
         """simulate_ensemble for every candidate of `params` in the same launches: params is a list of C dicts in
         MLAPM(**params) form (version, tau, A, B and optionally C, D, theta; an optional 'radius' overrides `radius` for
         that candidate; optionally the wall term's Aw, Bw, in every candidate or in none -- wall_cutoff is common to the
@@ -308,9 +332,10 @@ class MLAPM:
         scene without obstacles, candidates with and without a group term, a group term in a scene without groups,
         C * len(seeds) > 65535.  nav: simulate_scenario's; every candidate and seed shares the one field of the scene.
         nav_density: simulate_scenario's; one density law per run, shared by every candidate, and a field per member.
+        exit_choice: simulate_scenario's; one law per run, shared by every candidate.
         Returns a scenarios.ScenarioSweep."""
         return SweepRun(scenario, frames, len(params) if hasattr(params, '__len__') else 0, seeds, capacity, use_graph,
-                        device, hist_width, frames_per_graph, wall_cutoff, nav, nav_density).run(params, radius)
+                        device, hist_width, frames_per_graph, wall_cutoff, nav, nav_density, exit_choice).run(params, radius)
 
 
 SWEEP_KEYS = ('version', 'tau', 'A', 'B', 'C', 'D', 'theta', 'radius', 'Aw', 'Bw')
@@ -465,11 +490,12 @@ class SweepRun:
     generation of calibrate.calibrate_mlapm_to_stats is.  Every run is bitwise a fresh MLAPM.simulate_sweep."""
 
     def __init__(self, scenario, frames, n_candidates, seeds, capacity=None, use_graph=None, device='cuda', hist_width=2,
-                 frames_per_graph=8, wall_cutoff=DEFAULT_WALL_CUTOFF, nav=None, nav_density=None):
+                 frames_per_graph=8, wall_cutoff=DEFAULT_WALL_CUTOFF, nav=None, nav_density=None, exit_choice=None):
         from .. import ops_scenario, scenarios
         self.nav = None if nav is False else nav              # True, or the scene's ops_scenario.nav_field: every run's
         self.nav_density = nav_density                        # None, or the one ops_scenario.nav_density_law of every run
         check_nav_density(self.nav, nav_density)
+        self.exit_choice = ops_scenario.resolve_exit_choice(scenario, exit_choice, self.nav)   # None, or every run's law
         if self.nav is not None:
             ops_scenario.nav_wants_sight(self.nav)
             ops_scenario.check_nav_scene(scenario)
@@ -540,7 +566,7 @@ class SweepRun:
         self.graph = MLAPM._run_scenario(self.st, self.table, self.use_graph, self.frames_per_graph, graph=self.graph,
                                          walls=None if walls is None else (self.wall_grid, self.wall_table),
                                          groups=self.group_table, noise=self.noise_table, nav=self.nav,
-                                         nav_density=self.nav_density)
+                                         nav_density=self.nav_density, exit_choice=self.exit_choice)
         ens = scenarios.scenario_result(self.st)
         fields = dict(vars(ens))
         return scenarios.ScenarioSweep(params=params, n_candidates=self.n_candidates, seeds_per_candidate=S, **fields)

@@ -470,7 +470,8 @@ class BaseSimulator(Pedestrians):
                              time_unit=data.time_unit)
 
     # ---- open-world simulation: the loop the reference stubs (BaseSimulator.run / run_single_step, simulators.py:834-838) ----
-    def simulate_scenario(self, scenario, frames, seed=0, capacity=None, use_graph=None, nav=None, nav_density=None):
+    def simulate_scenario(self, scenario, frames, seed=0, capacity=None, use_graph=None, nav=None, nav_density=None,
+                          exit_choice=None):
         """Simulate `frames` frames of an entry / exit scene (piml_amd.scenarios.Scenario: gc_scenario() or a synthetic scene
         of piml_amd.scenarios.SCENARIOS) with the current model: frame 0 spawns the scenario's initial agents, every further
         frame is model -> one scenario_frame_kernel launch (integrate, arrive, retire, Poisson arrivals routed around the
@@ -488,23 +489,30 @@ class BaseSimulator(Pedestrians):
         route_max_iters=0, scenarios.floorplan_scenario): ValueError otherwise (ops_scenario.check_nav_scene).
         nav_density: NOT BUILT for the network-driven frame (MLAPM.simulate_scenario has it): anything but None raises
         NotImplementedError.
+        exit_choice = True or an ops_scenario.exit_choice_law(...) (MLAPM.simulate_scenario's vocabulary; it needs nav): the
+        choice launch (piml_nav_choose_exit) goes in front of the frame launch.  The frame computes the steering target from
+        exit_idx after the move, so the target follows the new gate in the same frame; the network's acceleration of that
+        frame was computed for the old gate: one frame of lag.
         Returns a ScenarioResult."""
         _no_nav_density(nav_density)
-        return self._in_scenario_mode(lambda: self._simulate(scenario, frames, capacity, use_graph, nav=nav, seed=seed))
+        return self._in_scenario_mode(lambda: self._simulate(scenario, frames, capacity, use_graph, nav=nav,
+                                                             exit_choice=exit_choice, seed=seed))
 
-    def simulate_ensemble(self, scenario, frames, seeds, capacity=None, use_graph=None, nav=None, nav_density=None):
+    def simulate_ensemble(self, scenario, frames, seeds, capacity=None, use_graph=None, nav=None, nav_density=None,
+                          exit_choice=None):
         """`simulate_scenario` for every seed of `seeds` at once: S = len(seeds) simulations of one scene with one capacity
         (default: as simulate_scenario's, which does not depend on the seed), every frame of all of them one network
         forward over the S * capacity rows, one scenario_frame_kernel launch and one relative-feature launch
         (captured and replayed as simulate_scenario's frame).  Member m is the simulation of seed seeds[m]: the network
         sees flat (S * capacity, .) rows, so members never see each other.  nav: simulate_scenario's; every member shares
-        the one field of the scene.  nav_density: simulate_scenario's (not built: NotImplementedError).  Returns a
+        the one field of the scene.  nav_density: simulate_scenario's (not built: NotImplementedError).  exit_choice: simulate_scenario's.  Returns a
         scenarios.ScenarioEnsemble."""
         _no_nav_density(nav_density)
         seeds = [int(x) for x in seeds]
         if not seeds:
             raise ValueError('simulate_ensemble: at least one seed expected')
-        return self._in_scenario_mode(lambda: self._simulate(scenario, frames, capacity, use_graph, nav=nav, seeds=seeds))
+        return self._in_scenario_mode(lambda: self._simulate(scenario, frames, capacity, use_graph, nav=nav,
+                                                             exit_choice=exit_choice, seeds=seeds))
 
     def _in_scenario_mode(self, run):
         only = hasattr(self.model, 'predictions_only')
@@ -519,13 +527,14 @@ class BaseSimulator(Pedestrians):
                 if only:
                     self.model.predictions_only = before
 
-    def _simulate(self, scenario, frames, capacity, use_graph, nav=None, **state_kw):
+    def _simulate(self, scenario, frames, capacity, use_graph, nav=None, exit_choice=None, **state_kw):
         from .. import ops_scenario, scenarios
         a = self.args
         nav = None if nav is False else nav
         if nav is not None:                               # said before any state exists
             ops_scenario.nav_wants_sight(nav)
             ops_scenario.check_nav_scene(scenario)
+        exit_choice = ops_scenario.resolve_exit_choice(scenario, exit_choice, nav)
         st = scenarios.scenario_state_for(scenario, frames, capacity, a.device, 2 * int(a.num_history_velocity),
                                           topk_ped=a.topk_ped, topk_obs=a.topk_obs, **state_kw)
         rows = st.mask.numel()
@@ -534,14 +543,15 @@ class BaseSimulator(Pedestrians):
         inputs = (st.pf.view(rows, *st.pf.shape[-2:]), st.of.view(rows, *st.of.shape[-2:]), st.selff.view(rows, st.selff.shape[-1]))
         if nav is not None and not isinstance(nav, ops_scenario.NavField):
             nav = ops_scenario.nav_field(st.scenario, device=st.p.device, sight=ops_scenario.nav_wants_sight(nav))
-        self._run_scenario(st, inputs, use_graph, nav=nav)
+        self._run_scenario(st, inputs, use_graph, nav=nav, exit_choice=exit_choice)
         return scenarios.scenario_result(st)
 
-    def _run_scenario(self, st, inputs, use_graph, nav=None):
+    def _run_scenario(self, st, inputs, use_graph, nav=None, exit_choice=None):
         """frame 0's spawn and features, then T - 1 frames of model(inputs) -> scenario_step -> relative features (the
         model's rows `inputs` are views of st's feature buffers), captured and replayed when use_graph.  nav: None or the
         scene's ops_scenario.nav_field: both scenario_step calls then also write st.steer (allocated by the init launch,
-        before any capture), which the relative-feature launches take in the place of st.dest."""
+        before any capture), which the relative-feature launches take in the place of st.dest.  exit_choice: None or an
+        ops_scenario.exit_choice_law (with nav): ops_scenario.nav_choose_exit goes in front of every frame launch."""
         from .. import ops_scenario, hip_graphs_safe
         a, sc, T = self.args, st.scenario, st.T
         feats = (st.pf, st.of, st.selff, st.ped_idx, st.obs_idx)
@@ -550,8 +560,13 @@ class BaseSimulator(Pedestrians):
         target = st.dest if nav is None else st.steer                                     # what the network is steered to
         ops.relative_features_into(feats, st.p, st.v, st.a, target, sc.obstacles, *geo)
 
+        if exit_choice is not None:
+            ops_scenario.scenario_exit_switches(st)                                       # (allocated before any capture)
+
         def step():
             a_next = self.model(*inputs)[0]
+            if exit_choice is not None:
+                ops_scenario.nav_choose_exit(st, nav, exit_choice, st.exit_switches)
             ops_scenario.scenario_step(st, a_next.reshape(st.p.shape).contiguous(), nav=nav)
             ops.relative_features_into(feats, st.p, st.v, st.a, target, sc.obstacles, *geo, tick=st.t)   # + st.t += 1
 

@@ -2,7 +2,7 @@
 piml_scenario_step_members, piml_scenario_step_nav, piml_scenario_step_mlapm, piml_scenario_step_mlapm_laws, piml_scenario_step_mlapm_walls,
 piml_wall_force, piml_scenario_step_mlapm_groups, piml_group_force, piml_scenario_step_mlapm_noise, piml_noise_force,
 piml_nav_relax, piml_nav_direction, piml_scenario_step_mlapm_nav, piml_nav_density, piml_nav_cost, piml_nav_relax_cost,
-piml_scenario_step_mlapm_navdyn, piml_scenario_route).
+piml_scenario_step_mlapm_navdyn, piml_nav_choose_exit, piml_scenario_route).
 
 `scenario_state` allocates the persistent (static-address) buffers of one simulation or an ensemble and the
 `piml_scenario` descriptor that points at them; `scenario_step` is one launch per simulated frame (integrate, arrive,
@@ -49,7 +49,8 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
     gets st.group_first / st.group_size ((S,) capacity int32, zero: per slot the first slot and the size of its unit) and
     st.groups, the piml_scene_groups over them and the scene's row_unit / unit_rows.  st.noise_state is None until a frame
     with the fluctuation term needs it (scenario_noise_state: (S,) capacity, 2 float32 zeros, eta of every slot), st.steer
-    None until a frame routed by a floor field writes it (scenario_step(nav=): (S,) capacity, 2 float32, NaN)."""
+    None until a frame routed by a floor field writes it (scenario_step(nav=): (S,) capacity, 2 float32, NaN), st.exit_switches
+    None until a run with an exit choice counts its switches (scenario_exit_switches: (S,) capacity int32 zeros)."""
     dev = scenario.entries.device
     if dev.type != 'cuda':
         raise _lib.PimlHipError(f'scenario_state: the scenario must be on a GPU (piml_amd has no CPU path), got {dev}')
@@ -122,6 +123,7 @@ def scenario_state(scenario, capacity, frames, hist_width=2, seed=0, topk_ped=6,
     st.groups = None
     st.noise_state = None
     st.steer = None
+    st.exit_switches = None
     if scenario.spawn_law == 'clip_groups':
         ru, ur = scenario.row_unit, scenario.unit_rows
         if ru is None or ur is None or ru.dtype != torch.int32 or ur.dtype != torch.int32 or ru.device != dev or \
@@ -154,6 +156,8 @@ def scenario_state_reset(st):
         st.noise_state.zero_()
     if getattr(st, 'steer', None) is not None:
         st.steer.fill_(nan)
+    if getattr(st, 'exit_switches', None) is not None:
+        st.exit_switches.zero_()
 
 
 def scenario_noise_state(st):
@@ -1034,6 +1038,138 @@ def nav_field_update(field, st, law):
     assert u is field.u
     field.iterations, field.updates = steps, field.updates + 1
     return steps
+
+
+class ExitChoiceLaw:
+    """exit_choice_law's value: classes (a tuple of tuples of gate indices), margin and commit (metres), every (frames)"""
+
+    def __init__(self, classes, margin, commit, every):
+        self.classes, self.margin, self.commit, self.every = classes, margin, commit, every
+        self._tables = {}
+
+    def gate_class_host(self, G):
+        """the class of each of a scene's G gates as a list of ints, -1 for a gate in no class; ValueError for an index
+        outside 0 .. G-1"""
+        out = [-1] * int(G)
+        for k, cls in enumerate(self.classes):
+            for g in cls:
+                if not 0 <= g < G:
+                    raise ValueError(f'exit choice: gate {g} of class {k} is outside the scene\'s gates 0 .. {int(G) - 1}')
+                out[g] = k
+        return out
+
+    def gate_class(self, G, device):
+        """gate_class_host as a device int32 tensor (made once per scene size and device, before any capture)"""
+        key = (int(G), str(torch.device(device)))
+        if key not in self._tables:
+            self._tables[key] = torch.tensor(self.gate_class_host(G), dtype=torch.int32, device=device)
+        return self._tables[key]
+
+    def desc(self, cell):
+        """the piml_exit_choice of this law on a grid of side `cell`: margin and commit in cell units, divided in float32"""
+        import numpy as np
+        d = _lib.ExitChoice()
+        with np.errstate(over='ignore'):
+            d.margin = float(np.float32(self.margin) / np.float32(cell))
+            d.commit = float(np.float32(self.commit) / np.float32(cell))
+        d.every = self.every
+        return d
+
+    def __repr__(self):
+        return (f'exit_choice_law({[list(c) for c in self.classes]}, margin={self.margin}, commit={self.commit}, '
+                f'every={self.every})')
+
+
+def exit_choice_law(classes, margin=1.0, commit=2.0, every=8):
+    """The exit choice of a routed scene (piml_nav_choose_exit): `classes` is a list of lists of gate indices, each a set of
+    equivalent exits; every `every` frames an agent bound for a gate of a class re-decides among the class's gates (its own
+    origin gate excepted) by the floor field's u at its cell -- the walking distance under the static field, a travel-time
+    proxy under the density-weighted one -- and switches to the least when that is better by more than `margin` metres,
+    unless it is within `commit` metres (of walking distance) of its current gate.  margin = inf never switches from a
+    reachable gate.  ValueError for a class of fewer than two gates, a gate in two classes (or twice in one), a negative
+    index, margin or commit negative or NaN, every not a whole number >= 1; an index beyond the scene's gates is refused
+    when the law meets a scene."""
+    try:
+        cls = tuple(tuple(int(g) for g in c) for c in classes)
+        exact = all(int(g) == g and not isinstance(g, bool) for c in classes for g in c)
+    except (TypeError, ValueError):
+        raise ValueError(f'exit choice: classes, a list of lists of gate indices expected, got {classes!r}') from None
+    if not cls or not exact:
+        raise ValueError(f'exit choice: classes, a non-empty list of lists of whole gate indices expected, got {classes!r}')
+    seen = set()
+    for k, c in enumerate(cls):
+        if len(c) < 2:
+            raise ValueError(f'exit choice: class {k} has {len(c)} gates: at least two expected')
+        for g in c:
+            if g < 0:
+                raise ValueError(f'exit choice: gate index {g} of class {k} is negative')
+            if g in seen:
+                raise ValueError(f'exit choice: gate {g} is in two classes (or twice in class {k})')
+            seen.add(g)
+    margin, commit = float(margin), float(commit)
+    if not margin >= 0 or not commit >= 0:
+        raise ValueError(f'exit choice: margin >= 0 and commit >= 0 (metres) expected, got {margin}, {commit}')
+    if isinstance(every, bool) or int(every) != every or int(every) < 1:
+        raise ValueError(f'exit choice: every, a whole number of frames >= 1 expected, got {every!r}')
+    return ExitChoiceLaw(cls, margin, commit, int(every))
+
+
+def resolve_exit_choice(scenario, exit_choice, nav):
+    """The exit_choice= argument of the simulate_* methods against their scene and nav= (False already None): None for None or
+    False; True -> exit_choice_law(scenario.exit_classes); an ExitChoiceLaw as it is, checked against the scene's gates.
+    TypeError for anything else; ValueError without a floor field, for a scene the field cannot route, for True on a scene
+    without exit_classes, or for a gate index beyond the scene's gates."""
+    if exit_choice is None or exit_choice is False:
+        return None
+    if exit_choice is not True and not isinstance(exit_choice, ExitChoiceLaw):
+        raise TypeError(f'exit_choice: True or an ops_scenario.exit_choice_law(...) expected, got {type(exit_choice).__name__}')
+    if nav is None:
+        raise ValueError('exit_choice: the choice reads the floor field and needs nav (--nav / --route)')
+    check_nav_scene(scenario)
+    if exit_choice is True:
+        if not getattr(scenario, 'exit_classes', None):
+            raise ValueError('exit_choice=True: the scene has no exit_classes (floorplan_scenario(..., exits=[[1, 2], ...]), '
+                             'the plan\'s "exits", or an exit_choice_law(classes))')
+        exit_choice = exit_choice_law(scenario.exit_classes)
+    exit_choice.gate_class_host(scenario.entries.shape[0])
+    return exit_choice
+
+
+def scenario_exit_switches(st):
+    """The exit choice's per-slot switch counts of st ((S,) capacity int32), allocated as zeros when first needed and kept
+    (scenario_state_reset zeroes them in place)."""
+    if getattr(st, 'exit_switches', None) is None:
+        st.exit_switches = torch.zeros_like(st.flag)
+    return st.exit_switches
+
+
+def nav_choose_exit(st, field, law, switch_count=None, frame_offset=0):
+    """One launch of piml_nav_choose_exit on a scenario state, in front of a frame: at the counter values t = st.t +
+    frame_offset with t >= 1 and (t - 1) % law.every == 0 -- tested on the device, so the call can stand in front of every
+    frame, captured ones too -- every present agent bound for a gate of one of law's classes re-decides among that class by
+    field.u at its cell and, on a switch, gets the destination the spawn would have given it for the new gate (waypoints
+    and exit_idx rows flag .. 1, st.dest).  field: a NavField, with or without the any-angle table (u alone is read), or a
+    NavFieldDynamic of the state's members (member m reads its own planes).  law: an exit_choice_law(...).  switch_count:
+    None, or an int32 tensor of st.flag's shape that counts each slot's switches (scenario_exit_switches(st)).  The checks
+    are scenario_step_mlapm(nav=)'s; ValueError also for a gate of the law beyond the scene's."""
+    _check_nav(st, field)
+    if not isinstance(law, ExitChoiceLaw):
+        raise TypeError(f'law: an exit_choice_law(...) expected, got {type(law).__name__}')
+    if int(frame_offset) < 0:
+        raise ValueError(f'frame_offset must be >= 0, got {frame_offset}')
+    if switch_count is not None:
+        if not isinstance(switch_count, torch.Tensor) or switch_count.dtype != torch.int32 or \
+                tuple(switch_count.shape) != tuple(st.flag.shape) or switch_count.device != st.p.device or \
+                not switch_count.is_contiguous():
+            raise ValueError(f'switch_count: a contiguous int32 {tuple(st.flag.shape)} tensor on {st.p.device} expected')
+    classes = law.gate_class(field.G, st.p.device)
+    desc = law.desc(field.cell)
+    stride = field.member_stride if isinstance(field, NavFieldDynamic) else 0
+    with torch.cuda.device(st.p.device):
+        _lib.check(_lib.lib().piml_nav_choose_exit(
+            ctypes.byref(st.desc), st.seeds.numel(), _ptr(st.seeds), ctypes.byref(field.desc), stride, _ptr(classes),
+            ctypes.byref(desc), None if switch_count is None else _ptr(switch_count), int(frame_offset), _stream()),
+            'piml_nav_choose_exit')
 
 
 def _noise_arg_is_table(st, noise):

@@ -68,6 +68,8 @@ class Scenario:
     # 'clip_groups' (clip_scenario(groups=)): the table's rows bundled into units whose members appear together
     row_unit: torch.Tensor = None          # (E, 2) int32 per table row: its index inside its unit, the unit's size
     unit_rows: torch.Tensor = None         # (Ua,) int32 the first row of each arrival unit
+    # exit choice (ops_scenario.exit_choice_law): classes of equivalent exits, a list of lists of gate indices, or None
+    exit_classes: list = None
 
     def to(self, device):
         out = dataclasses.replace(self)
@@ -147,13 +149,15 @@ def _sample_segment(a, b, n):
     return torch.stack((torch.linspace(float(a[0]), float(b[0]), n), torch.linspace(float(a[1]), float(b[1]), n)), dim=1)
 
 
-def floorplan_scenario(walls, gates, rate_per_s=5.0, n_initial=20, gate_points=100, wall_spacing=0.05, **scenario_fields):
+def floorplan_scenario(walls, gates, rate_per_s=5.0, n_initial=20, gate_points=100, wall_spacing=0.05, exits=None,
+                       **scenario_fields):
     """A user's floor plan as a scene of gates under GC's law: walls, a list of polylines (each a list of >= 2 (x, y) points,
     resampled per edge at most wall_spacing metres apart into the obstacle points), and gates, a list of 2 .. 64 segments ((ax, ay),
     (bx, by)), each sampled into gate_points points -- the origins and destinations the arrivals are drawn from, GC's
     `entries`.  route_max_iters is 0: the route is the destination itself and the way around the walls is the floor field's
     (ops_scenario.nav_field; MLAPM.simulate_scenario(..., nav=True)); route_polyline is a two-point dummy that is never
-    read.  scenario_fields: further Scenario fields (time_unit, arrival_radius, spawn_offset, ...).  ValueError on a plan
+    read.  exits: None or the scene's classes of equivalent exits, a list of lists of gate indices (each of two or more,
+    no gate in two), kept as Scenario.exit_classes for MLAPM.simulate_scenario(..., exit_choice=True).  scenario_fields: further Scenario fields (time_unit, arrival_radius, spawn_offset, ...).  ValueError on a plan
     that is not of that shape or a field the scene rule owns."""
     def points(x, what, least):
         try:
@@ -163,7 +167,8 @@ def floorplan_scenario(walls, gates, rate_per_s=5.0, n_initial=20, gate_points=1
         if t.dim() != 2 or t.shape[1] != 2 or t.shape[0] < least or not bool(torch.isfinite(t).all()):
             raise ValueError(f'floorplan: {what}: at least {least} finite (x, y) points expected, got shape {tuple(t.shape)}')
         return t
-    owned = {'entries', 'route_polyline', 'obstacles', 'route_max_iters', 'spawn_law', 'arrival_rule', 'num_waypoints'}
+    owned = {'entries', 'route_polyline', 'obstacles', 'route_max_iters', 'spawn_law', 'arrival_rule', 'num_waypoints',
+             'exit_classes'}
     known = {f.name for f in dataclasses.fields(Scenario)}
     bad = sorted(k for k in scenario_fields if k in owned or k not in known)
     if bad:
@@ -172,6 +177,14 @@ def floorplan_scenario(walls, gates, rate_per_s=5.0, n_initial=20, gate_points=1
         raise ValueError(f'floorplan: 2 .. 64 gates expected, got {len(gates) if isinstance(gates, (list, tuple)) else gates!r}')
     if not isinstance(walls, (list, tuple)):
         raise ValueError('floorplan: walls: a list of polylines expected')
+    if exits is not None:
+        from . import ops_scenario
+        try:
+            law = ops_scenario.exit_choice_law(exits)
+            law.gate_class_host(len(gates))
+        except ValueError as ex:
+            raise ValueError(f'floorplan: exits: {ex}') from None
+        exits = [list(c) for c in law.classes]
     gate_points, wall_spacing = int(gate_points), float(wall_spacing)
     if gate_points < 1 or not math.isfinite(wall_spacing) or not wall_spacing > 0:
         raise ValueError(f'floorplan: gate_points >= 1 and wall_spacing > 0 expected, got {gate_points}, {wall_spacing}')
@@ -189,20 +202,20 @@ def floorplan_scenario(walls, gates, rate_per_s=5.0, n_initial=20, gate_points=1
     obstacles = torch.concat(obstacles, dim=0).contiguous() if obstacles else torch.zeros(0, 2)
     fields = dict(name='floorplan', **scenario_fields) if 'name' not in scenario_fields else dict(scenario_fields)
     return Scenario(entries=torch.stack(entries).contiguous(), route_polyline=torch.zeros(2, 2), obstacles=obstacles,
-                    rate_per_s=float(rate_per_s), n_initial=int(n_initial), route_max_iters=0, **fields)
+                    rate_per_s=float(rate_per_s), n_initial=int(n_initial), route_max_iters=0, exit_classes=exits, **fields)
 
 
 def load_floorplan(path):
     """floorplan_scenario of a JSON file: {"walls": [[[x, y], ...], ...], "gates": [[[ax, ay], [bx, by]], ...]} and, optionally,
-    any of FLOORPLAN_FIELDS.  ValueError on anything else."""
+    "exits": [[1, 2], ...] (floorplan_scenario's exits) and any of FLOORPLAN_FIELDS.  ValueError on anything else."""
     import json
     with open(path) as fh:
         got = json.load(fh)
     if not isinstance(got, dict) or 'walls' not in got or 'gates' not in got:
         raise ValueError(f"{path}: a JSON object with 'walls' and 'gates' expected")
-    unknown = sorted(set(got) - {'walls', 'gates', *FLOORPLAN_FIELDS})
+    unknown = sorted(set(got) - {'walls', 'gates', 'exits', *FLOORPLAN_FIELDS})
     if unknown:
-        raise ValueError(f"{path}: unknown keys {unknown} (expected walls, gates and {list(FLOORPLAN_FIELDS)})")
+        raise ValueError(f"{path}: unknown keys {unknown} (expected walls, gates, exits and {list(FLOORPLAN_FIELDS)})")
     try:
         return floorplan_scenario(got['walls'], got['gates'], **{k: v for k, v in got.items() if k not in ('walls', 'gates')})
     except (TypeError, ValueError) as ex:
@@ -509,7 +522,15 @@ class ScenarioResult(types.SimpleNamespace):
     dropped ones included), dropped (agents past the capacity, never simulated), spawn_count (T) per frame.  Slot n holds
     the agent of ordinal n; slots past min(spawned, cap) never held an agent.  A grouped clip scene's run ('clip_groups')
     also has group_first, group_size (cap) int32 -- per slot the first slot and the size of the unit it was spawned with, 0
-    for a slot that never held an agent -- (None for every other scene) and `planted_groups()`."""
+    for a slot that never held an agent -- (None for every other scene) and `planted_groups()`.  A scene of gates (GC's law)
+    also has exit_gate (cap) int32 -- the gate nearest each slot's destination at the end of the run (row 1 of exit_idx,
+    which survives retirement) --, exit_switches (cap) int32, the switches an exit choice made per slot (None without one),
+    and `exit_counts()`; exit_gate is None for every other scene."""
+
+    def exit_counts(self):
+        """Retired agents per gate: a list of E ints, how many of the slots that held an agent and are absent in the last
+        recorded frame were bound for each gate (exit_gate).  ValueError for a scene without gates."""
+        return _exit_counts(self.exit_gate, self.mask_p[-1], [self.num_agents], self.num_gates)[0]
 
     @property
     def num_agents(self):
@@ -600,12 +621,30 @@ def _index(x, key):
     return None if x is None else x[key]
 
 
+def _exit_counts(exit_gate, last_mask, n_active, num_gates):
+    """per member: retired agents per gate.  exit_gate, last_mask (S, cap) or (cap); n_active: a list of S ints"""
+    if exit_gate is None or not num_gates:
+        raise ValueError('exit_counts: the scene has no gates')
+    gate = exit_gate.reshape(len(n_active), -1).detach().cpu()
+    mask = last_mask.reshape(len(n_active), -1).detach().cpu()
+    out = []
+    for m, n in enumerate(n_active):
+        gone = gate[m, :n][mask[m, :n] == 0].long()
+        out.append(torch.bincount(gone.clamp(0, num_gates - 1), minlength=num_gates).tolist())
+    return out
+
+
 class ScenarioEnsemble(types.SimpleNamespace):
     """What `BaseSimulator.simulate_ensemble` returns: the ScenarioResult fields with a leading member axis -- position /
     velocity / acceleration / destination (S, T, cap, 2), mask_p (S, T, cap), waypoints (S, D, cap, 2), desired_speed
     (S, cap), spawn_count (S, T) -- and seeds, spawned, dropped as lists of S ints; obstacles, time_unit and capacity
     are shared; group_first, group_size (S, cap) for a grouped clip scene, else None.  Member m is the simulation of seed
-    seeds[m]."""
+    seeds[m].  exit_gate, exit_switches (S, cap) and exit_counts() as ScenarioResult's, per member."""
+
+    def exit_counts(self):
+        """ScenarioResult.exit_counts of every member: a list of S lists of E ints"""
+        cap = self.position.shape[2]
+        return _exit_counts(self.exit_gate, self.mask_p[:, -1], [min(int(n), cap) for n in self.spawned], self.num_gates)
 
     def __len__(self):
         return len(self.seeds)
@@ -618,7 +657,8 @@ class ScenarioEnsemble(types.SimpleNamespace):
             desired_speed=self.desired_speed[m], obstacles=self.obstacles, time_unit=self.time_unit,
             spawned=self.spawned[m], dropped=self.dropped[m], spawn_count=self.spawn_count[m], capacity=self.capacity,
             seed=self.seeds[m], group_first=_index(getattr(self, 'group_first', None), m),
-            group_size=_index(getattr(self, 'group_size', None), m))
+            group_size=_index(getattr(self, 'group_size', None), m), exit_gate=_index(getattr(self, 'exit_gate', None), m),
+            exit_switches=_index(getattr(self, 'exit_switches', None), m), num_gates=getattr(self, 'num_gates', 0))
 
     def planted_groups(self, member=0):
         """member(member).planted_groups(): the slot lists of the units of two or more spawned together."""
@@ -729,7 +769,8 @@ class ScenarioSweep(ScenarioEnsemble):
             desired_speed=self.desired_speed[sl], spawn_count=self.spawn_count[sl], obstacles=self.obstacles,
             time_unit=self.time_unit, capacity=self.capacity, seeds=self.seeds[sl], spawned=self.spawned[sl],
             dropped=self.dropped[sl], group_first=_index(getattr(self, 'group_first', None), sl),
-            group_size=_index(getattr(self, 'group_size', None), sl))
+            group_size=_index(getattr(self, 'group_size', None), sl), exit_gate=_index(getattr(self, 'exit_gate', None), sl),
+            exit_switches=_index(getattr(self, 'exit_switches', None), sl), num_gates=getattr(self, 'num_gates', 0))
 
     def save_data(self, pattern):
         """One v2.2 clip per member at pattern with '{candidate}' and '{seed}' replaced.  Returns the paths."""
@@ -759,7 +800,9 @@ def scenario_result(st):
     common = dict(position=st.p_res, velocity=st.v_res, acceleration=st.a_res, destination=st.dest_res, mask_p=st.mask_res,
                   waypoints=st.waypoints, desired_speed=st.desired_speed, obstacles=sc.obstacles, time_unit=sc.time_unit,
                   spawn_count=st.spawn_count, capacity=st.capacity, state=st,
-                  group_first=getattr(st, 'group_first', None), group_size=getattr(st, 'group_size', None))
+                  group_first=getattr(st, 'group_first', None), group_size=getattr(st, 'group_size', None),
+                  exit_gate=st.exit_idx[..., 1, :] if sc.spawn_law == 'gc' else None,
+                  exit_switches=getattr(st, 'exit_switches', None), num_gates=sc.entries.shape[0] if sc.spawn_law == 'gc' else 0)
     if st.members is None:
         return ScenarioResult(spawned=int(st.spawned[last & 1].item()), dropped=int(st.dropped.item()), seed=st.seed,
                               **common)

@@ -30,6 +30,8 @@ reads.
                                 (the same, steering along lines of sight: the field's any-angle table)
     python -m piml_amd.simulate --law mlapm --scene-plan plan.json --nav --nav-density 2 [--nav-rho0 0.5]
                                 [--nav-density-radius 0.75] [--nav-fmax 8] [--nav-every 8] --seeds 0:32 --line-stats lines.json
+    python -m piml_amd.simulate --law mlapm --scene-plan plan.json --nav --exit-choice [--exit-classes '1,2;3,4']
+                                [--exit-margin 1] [--exit-commit 2] [--exit-every 8] --seeds 0:32
                                 (the floor field's cost grows with the local density and is solved again every 8 frames)
     python -m piml_amd.simulate --checkpoint model.pt --scene-plan plan.json --route field --seeds 0:32 --obstacle-stats walls.json
                                 (the network on a floor plan: --route field|sight steers either law by the floor field)
@@ -105,6 +107,18 @@ def get_args(argv=None):
     p.add_argument('--nav-every', dest='nav_every', type=int, default=None,
                    help='--nav-density: frames between two updates of the field (default 8; a multiple of 8, the frames of a '
                         'captured graph)')
+    p.add_argument('--exit-choice', dest='exit_choice', action='store_true',
+                   help='--nav / --route: routed agents re-decide which gate of a class of equivalent exits they leave through '
+                        '(ops_scenario.exit_choice_law; the nearest under the static field, the quickest under --nav-density); '
+                        'the classes are the plan\'s "exits" unless --exit-classes is given; the report gains the exits per gate')
+    p.add_argument('--exit-classes', dest='exit_classes', type=str, default=None, metavar="'1,2;3,4'",
+                   help='--exit-choice: the classes of equivalent exits, gate indices separated by commas, classes by semicolons')
+    p.add_argument('--exit-margin', dest='exit_margin', type=float, default=None,
+                   help='--exit-choice: switch only when the other gate is better by more than this many metres (default 1)')
+    p.add_argument('--exit-commit', dest='exit_commit', type=float, default=None,
+                   help='--exit-choice: no switch within this many metres of walking distance of the current gate (default 2)')
+    p.add_argument('--exit-every', dest='exit_every', type=int, default=None,
+                   help='--exit-choice: frames between two passes (default 8)')
     p.add_argument('--frames', type=int, default=750)
     seed = p.add_mutually_exclusive_group()
     seed.add_argument('--seed', type=int, default=0, help='seed of the spawn schedule')
@@ -254,6 +268,24 @@ def get_args(argv=None):
             p.error(f'--nav-density: {ex}')
     elif any(x is not None for x in (own.nav_rho0, own.nav_density_radius, own.nav_fmax, own.nav_every)):
         p.error('--nav-rho0 / --nav-density-radius / --nav-fmax / --nav-every need --nav-density')
+    own.exit_law = None
+    if own.exit_choice:
+        if not own.routed:
+            p.error('--exit-choice reads the floor field: it needs --nav or --route field|sight')
+        from .ops_scenario import exit_choice_law
+        try:
+            classes = parse_exit_classes(own.exit_classes) if own.exit_classes is not None else \
+                (own.plan.exit_classes if own.plan is not None else None)
+            if not classes:
+                raise ValueError('no classes: give --exit-classes \'1,2;3,4\' or a plan with "exits"')
+            own.exit_law = exit_choice_law(classes, 1.0 if own.exit_margin is None else own.exit_margin,
+                                           2.0 if own.exit_commit is None else own.exit_commit,
+                                           8 if own.exit_every is None else own.exit_every)
+            own.exit_law.gate_class_host(own.plan.entries.shape[0] if own.plan is not None else 7)    # (GC has 7 gates)
+        except ValueError as ex:
+            p.error(f'--exit-choice: {ex}')
+    elif any(x is not None for x in (own.exit_classes, own.exit_margin, own.exit_commit, own.exit_every)):
+        p.error('--exit-classes / --exit-margin / --exit-commit / --exit-every need --exit-choice')
     if own.params_sweep is not None:
         if own.params is not None:
             p.error('--params-sweep takes the place of --params: not both')
@@ -275,6 +307,14 @@ def get_args(argv=None):
         p.error('--params needs --law mlapm')
     model_args = MAIN.get_args(rest)
     return own, model_args
+
+
+def parse_exit_classes(text):
+    """--exit-classes '1,2;3,4' -> [[1, 2], [3, 4]].  ValueError on anything else."""
+    try:
+        return [[int(g) for g in c.split(',')] for c in text.split(';')]
+    except ValueError:
+        raise ValueError(f"--exit-classes: gate indices separated by ',' and classes by ';' expected, got {text!r}") from None
 
 
 def load_scene_groups(path):
@@ -359,6 +399,8 @@ def _report(tag, frames, res, threshold, out, soft=None, hard=None):
         hard = METRIC.collision_count(pos, threshold / 2, reduction='sum')
     print(f'[simulate] {tag}: {frames} frames, capacity {res.capacity}: spawned {res.spawned}, '
           f'retired {retired}, dropped {res.dropped}; collisions soft {soft:g} hard {hard:g}; saved {out}')
+    if getattr(res, 'exit_switches', None) is not None:      # a run with an exit choice: who left where
+        print(f'[simulate] {tag}: exits per gate {res.exit_counts()}, switches {int(res.exit_switches[:n].sum().item())}')
     return res.spawned, retired, res.dropped, soft, hard
 
 
@@ -416,6 +458,9 @@ def main(argv=None):
         if own.density_law is not None:
             run_kw['nav_density'] = own.density_law
             print(f'[simulate] density term: {own.density_law}')
+        if own.exit_law is not None:
+            run_kw['exit_choice'] = own.exit_law
+            print(f'[simulate] exit choice: {own.exit_law}')
     if own.law == 'mlapm' and own.mlapm_sweep is not None:
         return _sweep(sim, scenario, own, run_kw)
     if own.seeds is not None:
@@ -497,6 +542,25 @@ def _stats(res, own):
         vs = res.view_stats(lags=own.view_lags)
         vs.to_json(own.view_stats)
         viewstats.print_view_stats(vs, 'simulate --view-stats')
+    if getattr(own, 'exit_law', None) is not None:
+        _add_exit_counts(res, own)
+
+
+def _add_exit_counts(res, own):
+    """--exit-choice: every statistics JSON of the run gains 'exit_counts' (retired agents per gate; per member for an
+    ensemble) and 'exit_switches' (the switches made), beside what the statistics wrote (their readers ignore other keys)."""
+    import json
+    counts, switches = res.exit_counts(), int(res.exit_switches.sum().item())
+    for path in (own.stats, own.pair_stats, own.flow_stats, own.track_stats, own.obstacle_stats, own.line_stats, own.group_stats,
+                 own.view_stats):
+        if path is None:
+            continue
+        with open(path) as fh:
+            got = json.load(fh)
+        if isinstance(got, dict):
+            got['exit_counts'], got['exit_switches'] = counts, switches
+            with open(path, 'w') as fh:
+                json.dump(got, fh)
 
 
 def _sweep(sim, scenario, own, run_kw):
@@ -567,6 +631,9 @@ def _sweep(sim, scenario, own, run_kw):
         dropped = [sw.dropped[m] for m in g]
         print(f'[simulate] {own.scenario} candidate {c} ({own.params_sweep[c]}): {len(g)} seeds x {own.frames} frames, '
               f'capacity {sw.capacity}: spawned {sum(spawned)}, dropped {sum(dropped)}; saved {where}')
+        if getattr(sw, 'exit_switches', None) is not None:
+            counts = sw.exit_counts()
+            print(f'[simulate] candidate {c}: exits per gate {[sum(counts[m][e] for m in g) for e in range(sw.num_gates)]}')
     return sw
 
 
