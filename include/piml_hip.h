@@ -1354,6 +1354,51 @@ int piml_scenario_step_mlapm_navdyn(const piml_scenario* s, const piml_scenario_
                                     const piml_noise_args* noise /* NULL: no fluctuation */, int frame_offset, void* stream);
 
 /*
+ * The direction-aware density (ABI 35, additive): a counted person weighs 1 - flow (v . d) / vref, d the way to the walker's
+ * gate, so each gate has a cost plane of its own: cost (members, G, gy, gx).  A standing person weighs 1 as in piml_nav_cost,
+ * one walking the walker's way at vref weighs 0, one coming at the walker at vref weighs 1 + flow.  Every operation below is
+ * one correctly rounded float32 operation and every sum an integer (tests/navflow_ref.py gives the same bits).
+ *
+ * piml_nav_descent: d (G, gy, gx, 2) float32 from the STATIC field u (G, gy, gx) of piml_nav_relax, once per scene: the upwind
+ * unit direction of steepest descent.  With L, R, D, U the four neighbours (+inf outside the grid), a = L < R ? L : R,
+ * b = D < U ? D : U: rx = (u, a finite and a < u) ? fsub(u, a) : 0, negated when L < R; ry likewise with b and D < U;
+ * n = sqrtf(fadd(fmul(rx, rx), fmul(ry, ry))); d = (fdiv(rx, n), fdiv(ry, n)) when n > 0, else (0, 0) -- goal cells, cells
+ * with u = +inf and blocked cells.  The static field, not the one being solved: the field under construction cannot define
+ * its own cost without an outer fixed-point loop.  One thread per cell.
+ * hipErrorInvalidValue (before any launch): a NULL buffer; G outside 1..64; gx or gy outside 1..1024.
+ *
+ * piml_nav_flow: piml_nav_density's deposit -- the same slots, cell formula and count -- which also adds the slot's velocity
+ * (members, capacity, 2) into mom (members, 2, gy, gx) int32, per component
+ *   q = isfinite(v) ? (int)rintf(fmul(fminf(fmaxf(v, -8), 8), 1024)) : 0            (2^-10 m/s; halves round to even).
+ * A slot that deposits no count deposits no momentum.  The entry zeroes count and mom itself (hipMemsetAsync on the stream);
+ * integer atomics only: deterministic.  Capturable.
+ * hipErrorInvalidValue (before any launch): piml_nav_density's refusals; a NULL velocity or mom; capacity >= 1 << 18 (a window
+ * sum of momenta stays inside int32).
+ *
+ * piml_nav_cost_flow: cost[m][g][c] from count, mom and d.  With s, px, py the integer sums of count, mom[0], mom[1] over
+ * piml_nav_cost's window and area piml_nav_cost's,
+ *   pd    = fadd(fmul((float)px, dx), fmul((float)py, dy)),      along = fdiv(pd, fmul(1024, vref)),
+ *   s_eff = fsub((float)s, fmul(flow, along)),
+ *   f     = fminf(fadd(1, fmul(kd, fmaxf(fsub(fdiv(s_eff, area), rho0), 0))), fmax)  >= 1.
+ * flow == 0 gives s_eff == s exactly: every gate's plane is piml_nav_cost's bit for bit, whatever the velocities.  A workgroup
+ * stages each of the member's three integer tiles with its halo once, takes the separable window sums into registers and
+ * loops over the gates (15360 bytes of LDS, piml_nav_cost's).
+ * hipErrorInvalidValue (before any launch): piml_nav_cost's refusals; a NULL mom or d; G outside 1..64; members * G > 65535 or
+ * more than 2^31 - 1 cells in cost (piml_nav_relax_cost_gates' limits); flow or vref not finite, flow < 0, vref <= 0.
+ *
+ * piml_nav_relax_cost_gates: piml_nav_relax_cost with the cost read from plane member * G + gate of cost (members, G, gy, gx)
+ * in place of plane member: the same update, temporal blocking, LDS, changed flags and refusals, and with the same cost in
+ * every gate's plane piml_nav_relax_cost bit for bit.
+ */
+int piml_nav_descent(const float* u, int G, int gx, int gy, float* d, void* stream);
+int piml_nav_flow(const float* position, const float* velocity, const float* mask, int members, int capacity, float x0,
+                  float y0, float cell, int gx, int gy, int* count, int* mom, void* stream);
+int piml_nav_cost_flow(const int* count, const int* mom, const float* d, int members, int G, int gx, int gy, float cell,
+                       int radius_cells, float kd, float rho0, float fmax, float flow, float vref, float* cost, void* stream);
+int piml_nav_relax_cost_gates(const unsigned char* blocked, const unsigned char* goal, const float* cost, float* u_a,
+                              float* u_b, int members, int G, int gx, int gy, int launches, int* changed, void* stream);
+
+/*
  * Exit choice (ABI 35, additive): a routed agent re-decides which of a class of equivalent gates it is bound for.  The spawn
  * law draws the destination gate uniformly at birth; u[g] at the agent's cell is the walking distance to gate g under the
  * static field and a travel-time proxy under the density-weighted one, so the least u over a class is the nearest exit under

@@ -6,7 +6,7 @@
 //   piml_nav_cost        f[m][c] = min(1 + kd max(s / area - rho0, 0), fmax), s the window sum of count: the slowness;
 //   piml_nav_relax_cost  piml_nav_relax (nav.hip) with f in the Godunov update and a member axis.
 //
-// The weighted step (nav_update_cost below; tests/navcost_ref.py is the same function in numpy float32): with the slowness
+// The weighted step (nav_update_cost, navcost.hpp; tests/navcost_ref.py is the same function in numpy float32): with the slowness
 // f >= 1 of the cell, cand = lo + f when hi is not finite or hi - lo >= f, else 0.5 ((lo + hi) + sqrt(2 f f - d d)).  f == 1
 // gives nav_update's operations on the same values (2 * (1 * 1) is exactly 2), so cost == 1 is piml_nav_relax bit for bit.
 // Every update restarts from the cold start (0 on goal cells, +inf elsewhere): min(cand, u) keeps a stale low value where
@@ -17,17 +17,9 @@
 // 3 x 9216 + 2304 = 29952 bytes of LDS against 20736, so 5 workgroups (20 waves) fit a CU's 160 KB where nav_relax_kernel
 // fits 7; the kernel is bound by its LDS round trips and barriers, not by latency it would need more waves to hide.
 // nav_relax_kernel itself is untouched: this is a kernel of its own in a translation unit of its own.
-#include "nav.hpp"
+#include "navcost.hpp"                                      // the tile constants and nav_update_cost
 
 namespace piml {
-
-constexpr int kNdK = 8;                                      // Jacobi steps per launch (nav.hip's kNavK)
-constexpr int kNdTile = 32;                                  // output tile side
-constexpr int kNdSide = kNdTile + 2 * kNdK;                  // staged side
-constexpr int kNdCells = kNdSide * kNdSide;
-constexpr int kNdThreads = 256;
-constexpr int kNdMaxRadius = 8;                              // the cost window's radius in cells
-constexpr int kNdMaxMembers = 65535;
 
 // ---- the deposit: one thread per slot, grid (slot blocks, members) ----
 __global__ __launch_bounds__(kNdThreads) void nav_density_kernel(const float2* __restrict__ position,
@@ -74,17 +66,6 @@ __global__ __launch_bounds__(kNdThreads) void nav_cost_kernel(const int* __restr
         const float over = fmaxf(__fsub_rn(__fdiv_rn((float)s, area), rho0), 0.f);
         cost[po + (size_t)y * (size_t)gx + (size_t)x] = fminf(__fadd_rn(1.f, __fmul_rn(kd, over)), fmax);
     }
-}
-
-// one cell's weighted step from its four neighbours; f is the cell's slowness
-__device__ __forceinline__ float nav_update_cost(float u, float left, float right, float down, float up, float f) {
-    const float a = left < right ? left : right, b = down < up ? down : up;
-    const float lo = a < b ? a : b, hi = a < b ? b : a;
-    const float d = __fsub_rn(hi, lo);
-    float cand;
-    if (!nav_finite(hi) || d >= f) cand = __fadd_rn(lo, f);
-    else cand = __fmul_rn(0.5f, __fadd_rn(__fadd_rn(lo, hi), sqrtf(__fsub_rn(__fmul_rn(2.f, __fmul_rn(f, f)), __fmul_rn(d, d)))));
-    return cand < u ? cand : u;
 }
 
 // grid (tiles x, tiles y, member * G + gate): blocked and goal are the scene's, cost the member's, u and changed the plane's
@@ -140,10 +121,6 @@ __global__ __launch_bounds__(kNdThreads) void nav_relax_cost_kernel(const unsign
         diff |= __float_as_uint(v) != __float_as_uint(u_in[c]);
     }
     if (diff) changed[z] = 1;                                // a plain store; every writer stores the same value
-}
-
-static inline bool nd_grid_ok(int members, int gx, int gy) {
-    return members >= 1 && members <= kNdMaxMembers && gx >= 1 && gx <= kNavMaxCells && gy >= 1 && gy <= kNavMaxCells;
 }
 
 }  // namespace piml

@@ -236,7 +236,7 @@ class MLAPM:
             nav = ops_scenario.nav_field(st.scenario, device=st.p.device, sight=ops_scenario.nav_wants_sight(nav))
         if nav_density is not None:
             nav_density.radius_cells(nav.cell)
-            nav = ops_scenario.NavFieldDynamic(nav, st.seeds.numel())
+            nav = ops_scenario.NavFieldDynamic(nav, st.seeds.numel(), flow=nav_density.flow > 0)
         self._run_scenario(st, law, use_graph, frames_per_graph, walls=walls,
                            groups=None if group is None else ops_scenario.group_law(*group),
                            noise=None if noise is None else ops_scenario.noise_law(*noise, float(st.scenario.time_unit)),
@@ -547,7 +547,7 @@ class SweepRun:
                                                   sight=ops_scenario.nav_wants_sight(self.nav))
             if self.nav_density is not None:
                 self.nav_density.radius_cells(self.nav.cell)
-                self.nav = ops_scenario.NavFieldDynamic(self.nav, self.st.seeds.numel())
+                self.nav = ops_scenario.NavFieldDynamic(self.nav, self.st.seeds.numel(), flow=self.nav_density.flow > 0)
         else:
             if (walls is None) != (self.wall_table is None):  # the captured frames are those of the first run's kernel
                 raise ValueError('SweepRun: every run of a sweep has a wall term (Aw, Bw) or none has')

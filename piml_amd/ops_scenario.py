@@ -2,6 +2,7 @@
 piml_scenario_step_members, piml_scenario_step_nav, piml_scenario_step_mlapm, piml_scenario_step_mlapm_laws, piml_scenario_step_mlapm_walls,
 piml_wall_force, piml_scenario_step_mlapm_groups, piml_group_force, piml_scenario_step_mlapm_noise, piml_noise_force,
 piml_nav_relax, piml_nav_direction, piml_scenario_step_mlapm_nav, piml_nav_density, piml_nav_cost, piml_nav_relax_cost,
+piml_nav_descent, piml_nav_flow, piml_nav_cost_flow, piml_nav_relax_cost_gates,
 piml_scenario_step_mlapm_navdyn, piml_nav_choose_exit, piml_scenario_route).
 
 `scenario_state` allocates the persistent (static-address) buffers of one simulation or an ensemble and the
@@ -822,10 +823,11 @@ NAV_MAX_RADIUS = 8                     # cells: the cost window's radius (navden
 
 
 class NavDensityLaw:
-    """nav_density_law's value: kd, rho0, radius (metres), fmax, every (frames)"""
+    """nav_density_law's value: kd, rho0, radius (metres), fmax, every (frames), flow and vref (m/s)"""
 
-    def __init__(self, kd, rho0, radius, fmax, every):
+    def __init__(self, kd, rho0, radius, fmax, every, flow=0.0, vref=1.3):
         self.kd, self.rho0, self.radius, self.fmax, self.every = kd, rho0, radius, fmax, every
+        self.flow, self.vref = flow, vref
 
     def radius_cells(self, cell):
         """r = round(radius / cell) cells of a grid of side `cell`; ValueError beyond 8"""
@@ -836,23 +838,30 @@ class NavDensityLaw:
         return r
 
     def __repr__(self):
+        tail = f', flow={self.flow}, vref={self.vref}' if self.flow else ''
         return (f'nav_density_law(kd={self.kd}, rho0={self.rho0}, radius={self.radius}, fmax={self.fmax}, '
-                f'every={self.every})')
+                f'every={self.every}{tail})')
 
 
-def nav_density_law(kd, rho0=0.5, radius=0.75, fmax=8.0, every=8):
+def nav_density_law(kd, rho0=0.5, radius=0.75, fmax=8.0, every=8, flow=0.0, vref=1.3):
     """The density term of a floor field: a cell's slowness is f = min(1 + kd max(rho - rho0, 0), fmax), rho (1/m^2) the
     agents counted in the square window of about `radius` metres around the cell (r = round(radius / cell) cells, at most 8)
     over its area, and the field is solved again every `every` frames.  kd (m^2) has no default: as with Aw, Ag and An there
-    is no density term unless one is given; kd = 0 is the static field, solved again.  ValueError unless kd >= 0, rho0 >= 0,
-    radius >= 0 and fmax >= 1 are finite and every is an integer >= 1."""
+    is no density term unless one is given; kd = 0 is the static field, solved again.  flow > 0: the direction-aware density
+    (piml_nav_cost_flow): a counted person weighs 1 - flow (v . d) / vref, d the static field's way to the walker's gate, so
+    one walking the walker's way at vref (m/s) weighs 0 and one coming at the walker 1 + flow, and every gate has a cost plane
+    of its own; flow = 0 is the head count.  ValueError unless kd >= 0, rho0 >= 0, radius >= 0, fmax >= 1, flow >= 0 and
+    vref > 0 are finite and every is an integer >= 1."""
     kd, rho0, radius, fmax = float(kd), float(rho0), float(radius), float(fmax)
     if not all(math.isfinite(x) for x in (kd, rho0, radius, fmax)) or kd < 0 or rho0 < 0 or radius < 0 or fmax < 1:
         raise ValueError(f'nav density law: finite kd >= 0, rho0 >= 0, radius >= 0 and fmax >= 1 expected, got kd={kd}, '
                          f'rho0={rho0}, radius={radius}, fmax={fmax}')
     if isinstance(every, bool) or int(every) != every or int(every) < 1:
         raise ValueError(f'nav density law: every, a whole number of frames >= 1 expected, got {every!r}')
-    return NavDensityLaw(kd, rho0, radius, fmax, int(every))
+    flow, vref = float(flow), float(vref)
+    if not (math.isfinite(flow) and math.isfinite(vref)) or flow < 0 or vref <= 0:
+        raise ValueError(f'nav density law: finite flow >= 0 and vref > 0 expected, got flow={flow}, vref={vref}')
+    return NavDensityLaw(kd, rho0, radius, fmax, int(every), flow, vref)
 
 
 def _check_density_law(law):
@@ -914,14 +923,16 @@ def nav_cost(count, field, law, out=None):
     return out
 
 
-def _relax_cost(blocked, goal, cost, a, b, changed, launches):
-    """nav_relax_cost's loop on buffers the caller owns; a holds the start.  -> (the buffer with the result, steps)"""
+def _relax_cost(blocked, goal, cost, a, b, changed, launches, gates=False):
+    """nav_relax_cost's loop on buffers the caller owns; a holds the start.  gates: cost has a plane per (member, gate)
+    (piml_nav_relax_cost_gates).  -> (the buffer with the result, steps)"""
     M, (G, gy, gx) = int(cost.shape[0]), (int(n) for n in goal.shape)
+    name = 'piml_nav_relax_cost_gates' if gates else 'piml_nav_relax_cost'
 
     def queue(n):
         with torch.cuda.device(goal.device):
-            _lib.check(_lib.lib().piml_nav_relax_cost(_ptr(blocked), _ptr(goal), _ptr(cost), _ptr(a), _ptr(b), M, G, gx, gy,
-                                                      int(n), _ptr(changed), _stream()), 'piml_nav_relax_cost')
+            _lib.check(getattr(_lib.lib(), name)(_ptr(blocked), _ptr(goal), _ptr(cost), _ptr(a), _ptr(b), M, G, gx, gy,
+                                                 int(n), _ptr(changed), _stream()), name)
     if launches is not None:
         queue(launches)
         return (b if int(launches) & 1 else a), int(launches) * NAV_STEPS
@@ -961,15 +972,129 @@ def nav_relax_cost(blocked, goal, cost, launches=None):
     return _relax_cost(blocked, goal, cost, a, b, changed, launches)
 
 
+# ---- the direction-aware density (piml_nav_descent, piml_nav_flow, piml_nav_cost_flow, piml_nav_relax_cost_gates; csrc/navflow.hip) ----
+NAV_FLOW_MAX_CAPACITY = (1 << 18) - 1  # slots: a window sum of momenta stays inside int32 (navflow.hip)
+
+
+def nav_descent(field, out=None):
+    """The way to each gate of piml_nav_descent: d (G, gy, gx, 2) float32, the upwind unit direction of steepest descent of
+    `field`'s STATIC u; (0, 0) on goal cells and where u is +inf.  Once per scene, before any capture."""
+    field = _base_field(field)
+    u = field.base.u if isinstance(field, NavFieldDynamic) else field.u
+    if u.device.type != 'cuda':
+        raise _lib.PimlHipError(f'nav_descent: a field on a GPU expected (piml_amd has no CPU path), got {u.device}')
+    u = u.contiguous()
+    shape = (field.G, field.gy, field.gx, 2)
+    if out is None:
+        out = torch.empty(shape, device=u.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != u.device or not out.is_contiguous():
+        raise ValueError(f'nav_descent: out, a contiguous float32 {shape} tensor on {u.device} expected')
+    with torch.cuda.device(u.device):
+        _lib.check(_lib.lib().piml_nav_descent(_ptr(u), field.G, field.gx, field.gy, _ptr(out), _stream()), 'piml_nav_descent')
+    return out
+
+
+def nav_flow(position, velocity, mask, field, out=None):
+    """nav_density with the velocities kept (piml_nav_flow): position, velocity (members, capacity, 2) or (capacity, 2)
+    float32, mask (members, capacity) or (capacity) -> (count (members, gy, gx) int32, nav_density's, and mom (members, 2, gy,
+    gx) int32: per cell the sum of the counted slots' velocity components in 2^-10 m/s, each clamped to +-8 m/s, rounded half
+    to even, 0 when not finite).  out: a (count, mom) pair to write in place (neither need be zero).  ValueError for
+    2^18 slots or more."""
+    field = _base_field(field)
+    p, v, m = _gpu_f32('position', position), _gpu_f32('velocity', velocity), _gpu_f32('mask', mask)
+    if p.dim() == 2:
+        p, v, m = p.unsqueeze(0), v.unsqueeze(0), m.unsqueeze(0)
+    if p.dim() != 3 or p.shape[-1] != 2 or tuple(v.shape) != tuple(p.shape) or tuple(m.shape) != tuple(p.shape[:2]) or \
+            p.shape[1] < 1 or p.shape[0] < 1:
+        raise ValueError(f'nav_flow: position and velocity (members, capacity, 2) and mask (members, capacity) expected, got '
+                         f'{tuple(p.shape)}, {tuple(v.shape)}, {tuple(m.shape)}')
+    if p.device != field.blocked.device or m.device != p.device or v.device != p.device:
+        raise ValueError(f'nav_flow: position on {p.device}, velocity on {v.device}, mask on {m.device}, the field on '
+                         f'{field.blocked.device}')
+    M, cap = int(p.shape[0]), int(p.shape[1])
+    if cap > NAV_FLOW_MAX_CAPACITY:
+        raise ValueError(f'nav_flow: {cap} slots, at most {NAV_FLOW_MAX_CAPACITY} (the momentum sums are int32)')
+    shapes = (M, field.gy, field.gx), (M, 2, field.gy, field.gx)
+    if out is None:
+        out = tuple(torch.empty(sh, device=p.device, dtype=torch.int32) for sh in shapes)
+    elif len(out) != 2 or any(o.dtype != torch.int32 or tuple(o.shape) != sh or o.device != p.device or not o.is_contiguous()
+                              for o, sh in zip(out, shapes)):
+        raise ValueError(f'nav_flow: out, contiguous int32 {shapes[0]} and {shapes[1]} tensors on {p.device} expected')
+    count, mom = out
+    with torch.cuda.device(p.device):
+        _lib.check(_lib.lib().piml_nav_flow(_ptr(p), _ptr(v), _ptr(m), M, cap, field.x0, field.y0, field.cell, field.gx,
+                                            field.gy, _ptr(count), _ptr(mom), _stream()), 'piml_nav_flow')
+    return count, mom
+
+
+def nav_cost_flow(count, mom, descent, field, law, out=None):
+    """The slowness planes per gate of piml_nav_cost_flow: count (members, gy, gx) and mom (members, 2, gy, gx) int32 of
+    nav_flow, descent (G, gy, gx, 2) float32 of nav_descent -> f (members, G, gy, gx) float32 under the nav_density_law `law`
+    (its flow and vref included) on `field`'s grid.  law.flow == 0: every gate's plane is nav_cost's bit for bit."""
+    field = _base_field(field)
+    _check_density_law(law)
+    r = law.radius_cells(field.cell)
+    if not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.dim() != 3 or \
+            tuple(count.shape[1:]) != (field.gy, field.gx):
+        raise ValueError(f'nav_cost_flow: count, an int32 (members, {field.gy}, {field.gx}) tensor expected')
+    M = int(count.shape[0])
+    if not isinstance(mom, torch.Tensor) or mom.dtype != torch.int32 or tuple(mom.shape) != (M, 2, field.gy, field.gx):
+        raise ValueError(f'nav_cost_flow: mom, an int32 {(M, 2, field.gy, field.gx)} tensor expected')
+    if not isinstance(descent, torch.Tensor) or descent.dtype != torch.float32 or \
+            tuple(descent.shape) != (field.G, field.gy, field.gx, 2):
+        raise ValueError(f'nav_cost_flow: descent, a float32 {(field.G, field.gy, field.gx, 2)} tensor expected')
+    dev = field.blocked.device
+    if count.device.type != 'cuda' or any(t.device != dev for t in (count, mom, descent)):
+        raise _lib.PimlHipError(f'nav_cost_flow: count, mom and descent on the field\'s GPU expected (piml_amd has no CPU '
+                                f'path), got {count.device}, {mom.device}, {descent.device}')
+    count, mom, descent = count.contiguous(), mom.contiguous(), descent.contiguous()
+    shape = (M, field.G, field.gy, field.gx)
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != dev or not out.is_contiguous():
+        raise ValueError(f'nav_cost_flow: out, a contiguous float32 {shape} tensor on {dev} expected')
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().piml_nav_cost_flow(_ptr(count), _ptr(mom), _ptr(descent), M, field.G, field.gx, field.gy,
+                                                 field.cell, r, law.kd, law.rho0, law.fmax, law.flow, law.vref, _ptr(out),
+                                                 _stream()), 'piml_nav_cost_flow')
+    return out
+
+
+def nav_relax_cost_gates(blocked, goal, cost, launches=None):
+    """nav_relax_cost with a cost plane per (member, gate) (piml_nav_relax_cost_gates): cost (members, G, gy, gx) float32 >= 1
+    -> (u (members, G, gy, gx), the Jacobi steps queued); launches as nav_relax_cost's.  With the same plane for every gate
+    of a member it is nav_relax_cost bit for bit."""
+    if blocked.dtype != torch.uint8 or goal.dtype != torch.uint8 or goal.dim() != 3 or tuple(blocked.shape) != tuple(goal.shape[1:]):
+        raise ValueError(f'nav_relax_cost_gates: blocked (gy, gx) and goal (G, gy, gx) uint8 expected, got {blocked.dtype} '
+                         f'{tuple(blocked.shape)}, {goal.dtype} {tuple(goal.shape)}')
+    if goal.device.type != 'cuda' or blocked.device != goal.device:
+        raise _lib.PimlHipError(f'nav_relax_cost_gates: GPU tensors on one device expected (piml_amd has no CPU path), got '
+                                f'{blocked.device}, {goal.device}')
+    cost = _gpu_f32('cost', cost)
+    if cost.dim() != 4 or tuple(cost.shape[1:]) != tuple(goal.shape) or cost.shape[0] < 1 or cost.device != goal.device:
+        raise ValueError(f'nav_relax_cost_gates: cost (members, {", ".join(str(int(n)) for n in goal.shape)}) on {goal.device} '
+                         f'expected, got {tuple(cost.shape)} on {cost.device}')
+    M = int(cost.shape[0])
+    blocked, goal = blocked.contiguous(), goal.contiguous()
+    start = torch.where(goal != 0, 0.0, float('inf')).to(torch.float32)
+    a = start.unsqueeze(0).repeat(M, 1, 1, 1).contiguous()
+    b = torch.empty_like(a)
+    changed = torch.zeros(M * int(goal.shape[0]), device=goal.device, dtype=torch.int32)
+    return _relax_cost(blocked, goal, cost, a, b, changed, launches, gates=True)
+
+
 class NavFieldDynamic(NavField):
     """A floor field per member, solved again while the scene runs (nav_field_update): it wraps the scene's static NavField
     `base` -- blocked, goal, the grid scalars and near are the base's -- and owns count, cost (members, gy, gx), u
     (members, G, gy, gx) float32, which the frame reads (desc points at it; member_stride = G gy gx elements), the solver's
     second buffer and its changed flags.  All are allocated here, once, before any capture, and written in place.  u starts
     as the base's field in every member; iterations is the steps of the last update, updates their number.
+    flow = True (a law with flow > 0, the direction-aware density): it also owns mom (members, 2, gy, gx) int32, descent
+    (G, gy, gx, 2) float32 -- nav_descent of the base, computed here -- and cost_gates (members, G, gy, gx) float32, the cost
+    the solver then reads; cost keeps its meaning, the head-count slowness, and is not written by a flow update.
     ValueError for a base with the any-angle table: that table is a uniform-cost construction."""
 
-    def __init__(self, base, members=1):
+    def __init__(self, base, members=1, flow=False):
         if isinstance(base, NavFieldDynamic) or not isinstance(base, NavField):
             raise TypeError(f'nav field: a static nav_field(...) expected, got {type(base).__name__}')
         if base.sight_desc is not None:
@@ -987,6 +1112,12 @@ class NavFieldDynamic(NavField):
         dev = base.u.device
         self.count = torch.zeros(M, self.gy, self.gx, device=dev, dtype=torch.int32)
         self.cost = torch.ones(M, self.gy, self.gx, device=dev, dtype=torch.float32)
+        self.flow = bool(flow)
+        self.mom = self.descent = self.cost_gates = None
+        if self.flow:
+            self.mom = torch.zeros(M, 2, self.gy, self.gx, device=dev, dtype=torch.int32)
+            self.descent = nav_descent(base)
+            self.cost_gates = torch.ones(M, self.G, self.gy, self.gx, device=dev, dtype=torch.float32)
         self.u = base.u.unsqueeze(0).repeat(M, 1, 1, 1).contiguous()
         self.u_b = torch.empty_like(self.u)
         self.changed = torch.zeros(M * self.G, device=dev, dtype=torch.int32)
@@ -1012,6 +1143,8 @@ class NavFieldDynamic(NavField):
     def to_numpy(self):
         out = super().to_numpy()
         out.count, out.cost, out.members = self.count.cpu().numpy(), self.cost.cpu().numpy(), self.members
+        if self.flow:
+            out.mom, out.descent, out.cost_gates = (x.cpu().numpy() for x in (self.mom, self.descent, self.cost_gates))
         return out
 
     def reachable(self, g):
@@ -1020,7 +1153,9 @@ class NavFieldDynamic(NavField):
 
 def nav_field_update(field, st, law):
     """One update of a NavFieldDynamic from the state's present agents: density (st.p, st.mask -> field.count), cost
-    (-> field.cost) and a solve FROM THE COLD START into field.u, per member, all in place.  A warm start is wrong: the
+    (-> field.cost) and a solve FROM THE COLD START into field.u, per member, all in place.  law.flow > 0: the
+    direction-aware path on a field built with flow=True (ValueError otherwise): st.p, st.v, st.mask -> field.count and
+    field.mom (nav_flow), -> field.cost_gates (nav_cost_flow), and the solve reads a plane per gate.  A warm start is wrong: the
     minimum of the update keeps stale low values where the cost rose.  Batches of 16 launches (an even number, so the result
     is in the buffer the frame reads) until a batch changed nothing: one host read per batch, so this is not capturable and
     runs between replays.  Returns the steps queued (also field.iterations)."""
@@ -1031,10 +1166,18 @@ def nav_field_update(field, st, law):
         raise ValueError(f'nav density: a field of {field.members} members for a state of {st.seeds.numel()}')
     if field.u.device != st.p.device:
         raise ValueError(f'nav field on {field.u.device}, the state on {st.p.device}')
-    nav_density(st.p, st.mask, field, out=field.count)
-    nav_cost(field.count, field, law, out=field.cost)
+    if law.flow > 0:
+        if not field.flow:
+            raise ValueError('nav density: a law with flow > 0 needs a field built for it (NavFieldDynamic(base, members, '
+                             'flow=True))')
+        nav_flow(st.p, st.v, st.mask, field, out=(field.count, field.mom))
+        nav_cost_flow(field.count, field.mom, field.descent, field, law, out=field.cost_gates)
+    else:
+        nav_density(st.p, st.mask, field, out=field.count)
+        nav_cost(field.count, field, law, out=field.cost)
     field.u.copy_(field.start.unsqueeze(0).expand_as(field.u))
-    u, steps = _relax_cost(field.blocked, field.goal, field.cost, field.u, field.u_b, field.changed, None)
+    u, steps = _relax_cost(field.blocked, field.goal, field.cost_gates if law.flow > 0 else field.cost, field.u, field.u_b,
+                           field.changed, None, gates=law.flow > 0)
     assert u is field.u
     field.iterations, field.updates = steps, field.updates + 1
     return steps

@@ -107,6 +107,13 @@ def get_args(argv=None):
     p.add_argument('--nav-every', dest='nav_every', type=int, default=None,
                    help='--nav-density: frames between two updates of the field (default 8; a multiple of 8, the frames of a '
                         'captured graph)')
+    p.add_argument('--nav-flow', dest='nav_flow', type=float, default=None, metavar='BETA',
+                   help='--nav-density: the direction-aware density: a counted person weighs 1 - BETA (v . d) / vref, d the way '
+                        'to the walker\'s gate, so a stream walking the walker\'s way does not close a door and one coming at '
+                        'the walker closes it more (default 0: heads are counted)')
+    p.add_argument('--nav-vref', dest='nav_vref', type=float, default=None,
+                   help='--nav-density --nav-flow: the speed (m/s) at which a person walking the walker\'s way weighs nothing '
+                        '(default 1.3)')
     p.add_argument('--exit-choice', dest='exit_choice', action='store_true',
                    help='--nav / --route: routed agents re-decide which gate of a class of equivalent exits they leave through '
                         '(ops_scenario.exit_choice_law; the nearest under the static field, the quickest under --nav-density); '
@@ -262,12 +269,15 @@ def get_args(argv=None):
             own.density_law = nav_density_law(own.nav_density, 0.5 if own.nav_rho0 is None else own.nav_rho0,
                                               0.75 if own.nav_density_radius is None else own.nav_density_radius,
                                               8.0 if own.nav_fmax is None else own.nav_fmax,
-                                              8 if own.nav_every is None else own.nav_every)
+                                              8 if own.nav_every is None else own.nav_every,
+                                              0.0 if own.nav_flow is None else own.nav_flow,
+                                              1.3 if own.nav_vref is None else own.nav_vref)
             own.density_law.radius_cells(own.nav_cell)
         except ValueError as ex:
             p.error(f'--nav-density: {ex}')
-    elif any(x is not None for x in (own.nav_rho0, own.nav_density_radius, own.nav_fmax, own.nav_every)):
-        p.error('--nav-rho0 / --nav-density-radius / --nav-fmax / --nav-every need --nav-density')
+    elif any(x is not None for x in (own.nav_rho0, own.nav_density_radius, own.nav_fmax, own.nav_every, own.nav_flow,
+                                     own.nav_vref)):
+        p.error('--nav-rho0 / --nav-density-radius / --nav-fmax / --nav-every / --nav-flow / --nav-vref need --nav-density')
     own.exit_law = None
     if own.exit_choice:
         if not own.routed:
