@@ -1399,6 +1399,29 @@ int piml_nav_relax_cost_gates(const unsigned char* blocked, const unsigned char*
                               float* u_b, int members, int G, int gx, int gy, int launches, int* changed, void* stream);
 
 /*
+ * The weighted solve by active tiles (ABI 35, additive; csrc/navactive.hip): piml_nav_relax_cost's (cost_per_gate = 0: cost
+ * (members, gy, gx), plane member) or piml_nav_relax_cost_gates' (cost_per_gate = 1: cost (members, G, gy, gx), plane
+ * member * G + gate) Jacobi sequence bit for bit -- the same grid (tiles x, tiles y, member * G + gate), temporal blocking,
+ * LDS planes and per-cell arithmetic --, skipping the tiles whose step reproduces what the written buffer already holds.
+ * u_a holds the cold start (0 on goal cells, +inf elsewhere); u_b may hold anything.  flags: device int32, two planes of
+ * members * G * ty * tx words (tx = ceil(gx / 32), ty = ceil(gy / 32)), ping-ponged per launch; they need no clearing.
+ * Launch 0 steps every tile; in a later launch a block reads the nine flags of its 3 x 3 tile neighbourhood from the launch
+ * before (outside the tile grid: 0); none set: it writes its own flag 0 and returns; otherwise it steps and writes the tile
+ * and its flag is whether any word of the tile differs from its input.  The buffer a launch writes always holds the whole
+ * next iterate, so after `launches` launches u_a is exactly what the dense entries leave there after the same number.
+ * work: NULL or device int32 (members * G): every block that stepped its tile adds 1 (integer atomics; the entry does not
+ * clear it).  stalled: device int32, one word: a block whose tile changed in the LAST launch stores 1 -- the launches were
+ * too few for the fixed point; the entry never clears it.  While it stays 0 after a call, u_a == u_b is the fixed point.
+ * The entry queues `launches` launches on `stream` and nothing else: no host read, no allocation, no memset; capturable.
+ * hipErrorInvalidValue (before any launch): piml_nav_relax_cost_gates' refusals (a NULL blocked, goal, cost, u_a or u_b;
+ * u_a == u_b; members < 1; G outside 1..64; gx or gy outside 1..1024; members * G > 65535; more than 2^31 - 1 cells in u);
+ * launches odd or < 2 (the result is in u_a); cost_per_gate neither 0 nor 1; a NULL flags or stalled.
+ */
+int piml_nav_relax_active(const unsigned char* blocked, const unsigned char* goal, const float* cost, int cost_per_gate,
+                          float* u_a, float* u_b, int members, int G, int gx, int gy, int launches, int* flags, int* work,
+                          int* stalled, void* stream);
+
+/*
  * Exit choice (ABI 35, additive): a routed agent re-decides which of a class of equivalent gates it is bound for.  The spawn
  * law draws the destination gate uniformly at birth; u[g] at the agent's cell is the walking distance to gate g under the
  * static field and a travel-time proxy under the density-weighted one, so the least u over a class is the nearest exit under

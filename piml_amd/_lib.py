@@ -221,6 +221,7 @@ SIGNATURES = {
     'piml_nav_flow': [_p, _p, _p, _i, _i, _f, _f, _f, _i, _i, _p, _p, _p],
     'piml_nav_cost_flow': [_p, _p, _p, _i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _f, _p, _p],
     'piml_nav_relax_cost_gates': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
+    'piml_nav_relax_active': [_p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p],
     'piml_nav_choose_exit': [_p, _i, _p, _p, _ll, _p, _p, _p, _i, _p],
     'piml_nav_sight_relax': [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
     'piml_nav_direction_sight': [_p, _p, _p, _ll, _p, _p, _p, _p, _p, _p],

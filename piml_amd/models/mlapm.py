@@ -186,7 +186,10 @@ class MLAPM:
         from the cold start: ops_scenario.nav_field_update; piml_scenario_step_mlapm_navdyn reads it), so routed agents go
         round a congested door.  It needs nav = True or a field without the any-angle table: ValueError otherwise, and in a
         captured run when law.every is not a multiple of frames_per_graph (the update runs between replays).  The field an
-        update leaves is read until the next one: it lags by up to law.every frames.
+        update leaves is read until the next one: it lags by up to law.every frames.  A law with solver='active' solves the
+        same field by active tiles with no host read (piml_nav_relax_active), so a captured run also takes an every that
+        divides frames_per_graph -- the update is captured with its frames --, and the run raises RuntimeError at its end
+        when the law's max_launches were too few for an update's fixed point.
         exit_choice = True or an ops_scenario.exit_choice_law(classes, margin, commit, every): every law.every frames a routed
         agent bound for a gate of a class of equivalent exits re-decides among that class by the field's value at its cell --
         the nearest exit under the static field, the quickest under nav_density's -- and, on a switch, gets the destination
@@ -256,7 +259,11 @@ class MLAPM:
         static base and is updated (ops_scenario.nav_field_update) before the frame at counter value t whenever
         (t - 1) % every == 0 -- a function of the frame counter alone, so eager and captured runs update at the same
         frames; in a captured run that is between replays (a host read per batch of the solve, nothing captured), and every
-        must be a multiple of frames_per_graph: ValueError before any launch otherwise.  exit_choice: None or an
+        must be a multiple of frames_per_graph: ValueError before any launch otherwise.  A law with solver='active' makes no
+        host read: an every that is a multiple of frames_per_graph is queued between replays as before, one that divides it
+        is captured inside the graph in front of the frames at offsets k with k % every == 0, anything else is the
+        ValueError; the run ends with nav.check_converged() (RuntimeError when an update's launches were too few).
+        exit_choice: None or an
         ops_scenario.exit_choice_law, with nav: ops_scenario.nav_choose_exit goes in front of every frame, captured ones
         too (its schedule is tested on the device, so it needs no such multiple; where an update falls on the same counter
         value the update runs first and the choice reads the fresh field); st.exit_switches counts the switches.  Returns
@@ -268,12 +275,20 @@ class MLAPM:
         if use_graph is None:
             use_graph = steps > 8
         per = max(1, int(frames_per_graph))
+        inside = False
         if nav_density is not None:
             if not isinstance(nav, ops_scenario.NavFieldDynamic):
                 raise TypeError(f'nav_density: nav, an ops_scenario.NavFieldDynamic expected, got {type(nav).__name__}')
-            if use_graph and steps >= per + 1 and nav_density.every % per:
-                raise ValueError(f'nav_density: every = {nav_density.every} frames is not a multiple of frames_per_graph = '
-                                 f'{per}: a captured run updates the field between replays')
+            every, active = nav_density.every, nav_density.solver == 'active'
+            inside = active and every % per != 0 and per % every == 0      # the update is captured in front of its frames
+            if use_graph and steps >= per + 1 and every % per and not inside:
+                if active:
+                    raise ValueError(f'nav_density: every = {every} frames is neither a multiple of frames_per_graph = {per} '
+                                     f'(the update runs between replays) nor a divisor of it (the update is captured with '
+                                     f'its frames)')
+                raise ValueError(f'nav_density: every = {every} frames is not a multiple of frames_per_graph = '
+                                 f"{per}: a captured run updates the field between replays (solver='active' also captures "
+                                 f'an update whose every divides frames_per_graph)')
 
         if exit_choice is not None and nav is None:
             raise ValueError('exit_choice: the choice reads the floor field and needs nav')
@@ -299,19 +314,34 @@ class MLAPM:
                 frame()                                      # a real frame, also warms the library up
                 done = 1
                 if graph is None:
+                    if inside:                               # the update's launches once outside a capture, then the field
+                        ops_scenario.nav_field_update(nav, st, nav_density)      # the frames read is put back, in place
+                        nav.u.copy_(nav.base.u.unsqueeze(0).expand_as(nav.u))
+                        nav.stalled.zero_()
                     torch.cuda.synchronize()
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
                         for k in range(per):
+                            # a replay starts at counter value 1 + j per, so with every dividing per the frame at offset k
+                            # is due an update exactly when k % every == 0, in every replay
+                            if inside and k % nav_density.every == 0:
+                                ops_scenario.nav_field_update(nav, st, nav_density)
                             frame(frame_offset=k, advance=False)
                         st.t.add_(per)
+                    if inside:
+                        nav.updates = 0                      # (queued so far: none that a replay did not run)
                 for j in range((steps - done) // per):
-                    update(done + j * per)                   # (every is a multiple of per: no update falls inside a replay)
+                    if inside:
+                        nav.updates += per // nav_density.every
+                    else:
+                        update(done + j * per)               # (every is a multiple of per: no update falls inside a replay)
                     graph.replay()
                 done += (steps - done) // per * per
             for t in range(done, steps):
                 update(t)
                 frame()
+            if nav_density is not None and nav_density.solver == 'active':
+                nav.check_converged()                        # the run's one host read of the solver's stalled word
         return graph
 
     # ---- one law per member (piml_scenario_step_mlapm_laws): a sweep of candidates x seeds in one ensemble run ----

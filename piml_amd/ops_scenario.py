@@ -2,7 +2,7 @@
 piml_scenario_step_members, piml_scenario_step_nav, piml_scenario_step_mlapm, piml_scenario_step_mlapm_laws, piml_scenario_step_mlapm_walls,
 piml_wall_force, piml_scenario_step_mlapm_groups, piml_group_force, piml_scenario_step_mlapm_noise, piml_noise_force,
 piml_nav_relax, piml_nav_direction, piml_scenario_step_mlapm_nav, piml_nav_density, piml_nav_cost, piml_nav_relax_cost,
-piml_nav_descent, piml_nav_flow, piml_nav_cost_flow, piml_nav_relax_cost_gates,
+piml_nav_descent, piml_nav_flow, piml_nav_cost_flow, piml_nav_relax_cost_gates, piml_nav_relax_active,
 piml_scenario_step_mlapm_navdyn, piml_nav_choose_exit, piml_scenario_route).
 
 `scenario_state` allocates the persistent (static-address) buffers of one simulation or an ensemble and the
@@ -820,14 +820,18 @@ def nav_direction(position, gate, destination, field, return_branch=False, sight
 
 # ---- the density-aware floor field (piml_nav_density, piml_nav_cost, piml_nav_relax_cost; csrc/navdensity.hip) ----
 NAV_MAX_RADIUS = 8                     # cells: the cost window's radius (navdensity.hip)
+NAV_SOLVERS = ('batch', 'active')      # nav_density_law(solver=): nav_relax_cost's batches, or piml_nav_relax_active
+NAV_TILE = 32                          # the solvers' output tile side (navcost.hpp)
 
 
 class NavDensityLaw:
-    """nav_density_law's value: kd, rho0, radius (metres), fmax, every (frames), flow and vref (m/s)"""
+    """nav_density_law's value: kd, rho0, radius (metres), fmax, every (frames), flow and vref (m/s), solver ('batch' or
+    'active') and max_launches (None: nav_field_update's default)"""
 
-    def __init__(self, kd, rho0, radius, fmax, every, flow=0.0, vref=1.3):
+    def __init__(self, kd, rho0, radius, fmax, every, flow=0.0, vref=1.3, solver='batch', max_launches=None):
         self.kd, self.rho0, self.radius, self.fmax, self.every = kd, rho0, radius, fmax, every
         self.flow, self.vref = flow, vref
+        self.solver, self.max_launches = solver, max_launches
 
     def radius_cells(self, cell):
         """r = round(radius / cell) cells of a grid of side `cell`; ValueError beyond 8"""
@@ -839,19 +843,26 @@ class NavDensityLaw:
 
     def __repr__(self):
         tail = f', flow={self.flow}, vref={self.vref}' if self.flow else ''
+        if self.solver != 'batch':
+            tail += f', solver={self.solver!r}' + (f', max_launches={self.max_launches}' if self.max_launches else '')
         return (f'nav_density_law(kd={self.kd}, rho0={self.rho0}, radius={self.radius}, fmax={self.fmax}, '
                 f'every={self.every}{tail})')
 
 
-def nav_density_law(kd, rho0=0.5, radius=0.75, fmax=8.0, every=8, flow=0.0, vref=1.3):
+def nav_density_law(kd, rho0=0.5, radius=0.75, fmax=8.0, every=8, flow=0.0, vref=1.3, solver='batch', max_launches=None):
     """The density term of a floor field: a cell's slowness is f = min(1 + kd max(rho - rho0, 0), fmax), rho (1/m^2) the
     agents counted in the square window of about `radius` metres around the cell (r = round(radius / cell) cells, at most 8)
     over its area, and the field is solved again every `every` frames.  kd (m^2) has no default: as with Aw, Ag and An there
     is no density term unless one is given; kd = 0 is the static field, solved again.  flow > 0: the direction-aware density
     (piml_nav_cost_flow): a counted person weighs 1 - flow (v . d) / vref, d the static field's way to the walker's gate, so
     one walking the walker's way at vref (m/s) weighs 0 and one coming at the walker 1 + flow, and every gate has a cost plane
-    of its own; flow = 0 is the head count.  ValueError unless kd >= 0, rho0 >= 0, radius >= 0, fmax >= 1, flow >= 0 and
-    vref > 0 are finite and every is an integer >= 1."""
+    of its own; flow = 0 is the head count.  solver: 'batch' solves an update by batches of 16 dense launches with a host
+    read after each (nav_relax_cost); 'active' by ONE queue of max_launches launches that step only the tiles that can still
+    move (piml_nav_relax_active: the same field bit for bit, no host read, capturable, so `every` may also divide a captured
+    run's frames_per_graph).  max_launches (solver='active' only): an even number >= 2; None: twice the launches the static
+    solve queued, rounded up to even (nav_field_update) -- a heuristic bound, NavFieldDynamic.check_converged tells when it
+    was too small.  ValueError unless kd >= 0, rho0 >= 0, radius >= 0, fmax >= 1, flow >= 0 and vref > 0 are finite, every
+    is an integer >= 1, solver is one of the two and max_launches fits it."""
     kd, rho0, radius, fmax = float(kd), float(rho0), float(radius), float(fmax)
     if not all(math.isfinite(x) for x in (kd, rho0, radius, fmax)) or kd < 0 or rho0 < 0 or radius < 0 or fmax < 1:
         raise ValueError(f'nav density law: finite kd >= 0, rho0 >= 0, radius >= 0 and fmax >= 1 expected, got kd={kd}, '
@@ -861,7 +872,15 @@ def nav_density_law(kd, rho0=0.5, radius=0.75, fmax=8.0, every=8, flow=0.0, vref
     flow, vref = float(flow), float(vref)
     if not (math.isfinite(flow) and math.isfinite(vref)) or flow < 0 or vref <= 0:
         raise ValueError(f'nav density law: finite flow >= 0 and vref > 0 expected, got flow={flow}, vref={vref}')
-    return NavDensityLaw(kd, rho0, radius, fmax, int(every), flow, vref)
+    if solver not in NAV_SOLVERS:
+        raise ValueError(f"nav density law: solver, one of {', '.join(map(repr, NAV_SOLVERS))} expected, got {solver!r}")
+    if max_launches is not None:
+        if solver != 'active':
+            raise ValueError("nav density law: max_launches belongs to solver='active'")
+        if isinstance(max_launches, bool) or int(max_launches) != max_launches or int(max_launches) < 2 or int(max_launches) & 1:
+            raise ValueError(f'nav density law: max_launches, an even number of launches >= 2 expected, got {max_launches!r}')
+        max_launches = int(max_launches)
+    return NavDensityLaw(kd, rho0, radius, fmax, int(every), flow, vref, solver, max_launches)
 
 
 def _check_density_law(law):
@@ -1083,11 +1102,65 @@ def nav_relax_cost_gates(blocked, goal, cost, launches=None):
     return _relax_cost(blocked, goal, cost, a, b, changed, launches, gates=True)
 
 
+# ---- the solve by active tiles (piml_nav_relax_active; csrc/navactive.hip) ----
+def _check_launches(name, launches):
+    if isinstance(launches, bool) or int(launches) != launches or int(launches) < 2 or int(launches) & 1:
+        raise ValueError(f'{name}: launches, an even number >= 2 expected (the result is in the first buffer), got {launches!r}')
+    return int(launches)
+
+
+def nav_active_buffers(planes, gy, gx, device):
+    """the solver's (flags (2, planes, ty, tx), work (planes), stalled (1)) int32, zeroed"""
+    ty, tx = (int(gy) + NAV_TILE - 1) // NAV_TILE, (int(gx) + NAV_TILE - 1) // NAV_TILE
+    return (torch.zeros(2, int(planes), ty, tx, device=device, dtype=torch.int32),
+            torch.zeros(int(planes), device=device, dtype=torch.int32), torch.zeros(1, device=device, dtype=torch.int32))
+
+
+def _relax_active(blocked, goal, cost, a, b, flags, work, stalled, launches):
+    """one call of piml_nav_relax_active on buffers the caller owns; a holds the cold start and gets the result"""
+    M, (G, gy, gx) = int(cost.shape[0]), (int(n) for n in goal.shape)
+    with torch.cuda.device(goal.device):
+        _lib.check(_lib.lib().piml_nav_relax_active(_ptr(blocked), _ptr(goal), _ptr(cost), int(cost.dim() == 4), _ptr(a), _ptr(b),
+                                                    M, G, gx, gy, int(launches), _ptr(flags), _ptr(work), _ptr(stalled),
+                                                    _stream()), 'piml_nav_relax_active')
+
+
+def nav_relax_active(blocked, goal, cost, launches):
+    """The weighted eikonal solve by active tiles (piml_nav_relax_active) from the cold start: blocked (gy, gx) uint8 and goal
+    (G, gy, gx) uint8 shared by all members; cost (members, gy, gx) float32 >= 1, a plane per member (nav_relax_cost's), or
+    (members, G, gy, gx), a plane per member and gate (nav_relax_cost_gates'); launches: an even number >= 2, all queued at
+    once, no host read.  -> (u (members, G, gy, gx) float32: the dense solvers' field after the same launches bit for bit;
+    work (members, G) int32: the tiles each plane stepped, over all launches; stalled (1,) int32: not 0 when the last launch
+    still changed a tile, so launches were too few for the fixed point)."""
+    launches = _check_launches('nav_relax_active', launches)
+    if blocked.dtype != torch.uint8 or goal.dtype != torch.uint8 or goal.dim() != 3 or tuple(blocked.shape) != tuple(goal.shape[1:]):
+        raise ValueError(f'nav_relax_active: blocked (gy, gx) and goal (G, gy, gx) uint8 expected, got {blocked.dtype} '
+                         f'{tuple(blocked.shape)}, {goal.dtype} {tuple(goal.shape)}')
+    if goal.device.type != 'cuda' or blocked.device != goal.device:
+        raise _lib.PimlHipError(f'nav_relax_active: GPU tensors on one device expected (piml_amd has no CPU path), got '
+                                f'{blocked.device}, {goal.device}')
+    cost = _gpu_f32('cost', cost)
+    if cost.dim() not in (3, 4) or cost.shape[0] < 1 or cost.device != goal.device or \
+            tuple(cost.shape[1:]) != (tuple(blocked.shape) if cost.dim() == 3 else tuple(goal.shape)):
+        raise ValueError(f'nav_relax_active: cost (members, {blocked.shape[0]}, {blocked.shape[1]}) or (members, '
+                         f'{", ".join(str(int(n)) for n in goal.shape)}) on {goal.device} expected, got {tuple(cost.shape)} on '
+                         f'{cost.device}')
+    M, G = int(cost.shape[0]), int(goal.shape[0])
+    blocked, goal = blocked.contiguous(), goal.contiguous()
+    start = torch.where(goal != 0, 0.0, float('inf')).to(torch.float32)
+    a = start.unsqueeze(0).repeat(M, 1, 1, 1).contiguous()
+    b = torch.empty_like(a)
+    flags, work, stalled = nav_active_buffers(M * G, blocked.shape[0], blocked.shape[1], goal.device)
+    _relax_active(blocked, goal, cost, a, b, flags, work, stalled, launches)
+    return a, work.view(M, G), stalled
+
+
 class NavFieldDynamic(NavField):
     """A floor field per member, solved again while the scene runs (nav_field_update): it wraps the scene's static NavField
     `base` -- blocked, goal, the grid scalars and near are the base's -- and owns count, cost (members, gy, gx), u
     (members, G, gy, gx) float32, which the frame reads (desc points at it; member_stride = G gy gx elements), the solver's
-    second buffer and its changed flags.  All are allocated here, once, before any capture, and written in place.  u starts
+    second buffer and its changed flags, and flags, work and stalled of the solve by active tiles (a law with
+    solver='active').  All are allocated here, once, before any capture, and written in place.  u starts
     as the base's field in every member; iterations is the steps of the last update, updates their number.
     flow = True (a law with flow > 0, the direction-aware density): it also owns mom (members, 2, gy, gx) int32, descent
     (G, gy, gx, 2) float32 -- nav_descent of the base, computed here -- and cost_gates (members, G, gy, gx) float32, the cost
@@ -1121,6 +1194,9 @@ class NavFieldDynamic(NavField):
         self.u = base.u.unsqueeze(0).repeat(M, 1, 1, 1).contiguous()
         self.u_b = torch.empty_like(self.u)
         self.changed = torch.zeros(M * self.G, device=dev, dtype=torch.int32)
+        # the solve by active tiles (a law with solver='active'): its flags, work and stalled word; max_launches of the last update
+        self.flags, self.work, self.stalled = nav_active_buffers(M * self.G, self.gy, self.gx, dev)
+        self.max_launches = 0
         self.start = torch.where(self.goal != 0, 0.0, float('inf')).to(torch.float32).contiguous()      # the cold start
         self.member_stride = self.G * self.gy * self.gx
         d = _lib.NavGrid()
@@ -1133,7 +1209,22 @@ class NavFieldDynamic(NavField):
     def reset(self):
         """every member's u back to the base's static field, in place (the start of a run)"""
         self.u.copy_(self.base.u.unsqueeze(0).expand_as(self.u))
+        self.stalled.zero_()
         self.iterations = self.updates = 0
+
+    def default_max_launches(self):
+        """the launches of an update under solver='active' when the law names none: twice the launches the static solve
+        queued, rounded up to even.  A heuristic bound (a crowd lengthens the quickest paths); check_converged catches it"""
+        n = max(2, -(-2 * int(self.base.iterations) // NAV_STEPS))
+        return n + (n & 1)
+
+    def check_converged(self):
+        """ONE host read of the stalled word of the updates under solver='active' since the last reset: RuntimeError when an
+        update's last launch still changed a tile, so its field was not the fixed point"""
+        if bool(self.stalled.item()):
+            raise RuntimeError(f'nav density: an update of the field had not reached its fixed point after max_launches = '
+                               f'{self.max_launches} launches on a {self.gx} x {self.gy} grid: give the law a larger '
+                               f"max_launches, or solver='batch'")
 
     def member(self, m):
         """member m's planes as a static NavField (for nav_direction)"""
@@ -1158,7 +1249,11 @@ def nav_field_update(field, st, law):
     field.mom (nav_flow), -> field.cost_gates (nav_cost_flow), and the solve reads a plane per gate.  A warm start is wrong: the
     minimum of the update keeps stale low values where the cost rose.  Batches of 16 launches (an even number, so the result
     is in the buffer the frame reads) until a batch changed nothing: one host read per batch, so this is not capturable and
-    runs between replays.  Returns the steps queued (also field.iterations)."""
+    runs between replays.  A law with solver='active': the same deposit, cost and cold-start copy, then ONE call of
+    piml_nav_relax_active with max_launches launches (the law's, or field.default_max_launches()) -- the same field bit for
+    bit when that many launches reach the fixed point, no host read, so the update is capturable; field.work holds the tiles
+    each plane stepped, field.stalled is set when the launches were too few (field.check_converged() reads it, once, at the
+    end of a run).  Returns the steps queued (also field.iterations)."""
     if not isinstance(field, NavFieldDynamic):
         raise TypeError(f'field: a NavFieldDynamic expected, got {type(field).__name__}')
     _check_density_law(law)
@@ -1176,6 +1271,14 @@ def nav_field_update(field, st, law):
         nav_density(st.p, st.mask, field, out=field.count)
         nav_cost(field.count, field, law, out=field.cost)
     field.u.copy_(field.start.unsqueeze(0).expand_as(field.u))
+    if law.solver == 'active':
+        n = field.default_max_launches() if law.max_launches is None else _check_launches('nav density law', law.max_launches)
+        field.work.zero_()
+        _relax_active(field.blocked, field.goal, field.cost_gates if law.flow > 0 else field.cost, field.u, field.u_b, field.flags,
+                      field.work, field.stalled, n)
+        field.max_launches = n
+        field.iterations, field.updates = n * NAV_STEPS, field.updates + 1
+        return field.iterations
     u, steps = _relax_cost(field.blocked, field.goal, field.cost_gates if law.flow > 0 else field.cost, field.u, field.u_b,
                            field.changed, None, gates=law.flow > 0)
     assert u is field.u

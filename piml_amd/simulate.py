@@ -29,7 +29,8 @@ reads.
     python -m piml_amd.simulate --law mlapm --scene-plan plan.json --nav --nav-sight --out clip.npy
                                 (the same, steering along lines of sight: the field's any-angle table)
     python -m piml_amd.simulate --law mlapm --scene-plan plan.json --nav --nav-density 2 [--nav-rho0 0.5]
-                                [--nav-density-radius 0.75] [--nav-fmax 8] [--nav-every 8] --seeds 0:32 --line-stats lines.json
+                                [--nav-density-radius 0.75] [--nav-fmax 8] [--nav-every 8]
+                                [--nav-solver batch|active [--nav-max-launches N]] --seeds 0:32 --line-stats lines.json
     python -m piml_amd.simulate --law mlapm --scene-plan plan.json --nav --exit-choice [--exit-classes '1,2;3,4']
                                 [--exit-margin 1] [--exit-commit 2] [--exit-every 8] --seeds 0:32
                                 (the floor field's cost grows with the local density and is solved again every 8 frames)
@@ -106,7 +107,7 @@ def get_args(argv=None):
     p.add_argument('--nav-fmax', dest='nav_fmax', type=float, default=None, help='--nav-density: the cap of the cost factor (default 8)')
     p.add_argument('--nav-every', dest='nav_every', type=int, default=None,
                    help='--nav-density: frames between two updates of the field (default 8; a multiple of 8, the frames of a '
-                        'captured graph)')
+                        'captured graph, or with --nav-solver active also 1, 2 or 4)')
     p.add_argument('--nav-flow', dest='nav_flow', type=float, default=None, metavar='BETA',
                    help='--nav-density: the direction-aware density: a counted person weighs 1 - BETA (v . d) / vref, d the way '
                         'to the walker\'s gate, so a stream walking the walker\'s way does not close a door and one coming at '
@@ -114,6 +115,13 @@ def get_args(argv=None):
     p.add_argument('--nav-vref', dest='nav_vref', type=float, default=None,
                    help='--nav-density --nav-flow: the speed (m/s) at which a person walking the walker\'s way weighs nothing '
                         '(default 1.3)')
+    p.add_argument('--nav-solver', dest='nav_solver', choices=('batch', 'active'), default=None,
+                   help='--nav-density: how an update is solved: batch (default), batches of 16 dense launches with a host '
+                        'read after each; active, one queue of launches that step only the tiles that can still move '
+                        '(piml_nav_relax_active): the same field bit for bit, no host read, and --nav-every may also divide 8')
+    p.add_argument('--nav-max-launches', dest='nav_max_launches', type=int, default=None, metavar='N',
+                   help='--nav-solver active: the launches of an update, an even number >= 2 (default: twice the static '
+                        'solve\'s; the run fails at its end when they were too few)')
     p.add_argument('--exit-choice', dest='exit_choice', action='store_true',
                    help='--nav / --route: routed agents re-decide which gate of a class of equivalent exits they leave through '
                         '(ops_scenario.exit_choice_law; the nearest under the static field, the quickest under --nav-density); '
@@ -271,13 +279,15 @@ def get_args(argv=None):
                                               8.0 if own.nav_fmax is None else own.nav_fmax,
                                               8 if own.nav_every is None else own.nav_every,
                                               0.0 if own.nav_flow is None else own.nav_flow,
-                                              1.3 if own.nav_vref is None else own.nav_vref)
+                                              1.3 if own.nav_vref is None else own.nav_vref,
+                                              'batch' if own.nav_solver is None else own.nav_solver, own.nav_max_launches)
             own.density_law.radius_cells(own.nav_cell)
         except ValueError as ex:
             p.error(f'--nav-density: {ex}')
     elif any(x is not None for x in (own.nav_rho0, own.nav_density_radius, own.nav_fmax, own.nav_every, own.nav_flow,
-                                     own.nav_vref)):
-        p.error('--nav-rho0 / --nav-density-radius / --nav-fmax / --nav-every / --nav-flow / --nav-vref need --nav-density')
+                                     own.nav_vref, own.nav_solver, own.nav_max_launches)):
+        p.error('--nav-rho0 / --nav-density-radius / --nav-fmax / --nav-every / --nav-flow / --nav-vref / --nav-solver / '
+                '--nav-max-launches need --nav-density')
     own.exit_law = None
     if own.exit_choice:
         if not own.routed:
