@@ -112,6 +112,17 @@ int piml_relfeat_pack_plan(int form, int waves, int obstacle_workgroups, int nbr
 /* Diagnostic: the pack blocks TAIL gives obstacle workgroup `b` of `nb` out of `total`, in the order it runs them (the stride
  * functions the kernel uses).  Returns their number (< 0: bad arguments); the first `cap` are written to `out` (may be NULL). */
 int piml_relfeat_pack_tail_blocks(int b, int nb, int total, int* out, int cap);
+/* Diagnostic (tests, tools): the form the relative-feature forward launcher gives a launch of C slices x focal_count focal rows over
+ * N agents and M obstacle points -- the launcher calls the same rule, and no GPU call is made here.  part: 0 = one launch, 1 = LOCAL,
+ * 2 = REMOTE of a sharded pair (piml_relfeat_self_fwd_part); has_pack: a deferred weight pack rides in the launch.
+ * *waves = waves per workgroup (4 / 8 / 16); *resident = 1: the kernel that keeps the agent and the obstacle tile in LDS side by side;
+ * *split = 1: the pedestrian and the obstacle pass of a row run in different workgroups; *agent_tiles / *obstacle_tiles = the
+ * 4096-point LDS tiles the two passes stage (REMOTE: counted for a block at focal_begin = 0; elsewhere the ranges either side of the
+ * block round up apiece).  Any output may be NULL.  PIML_RELFEAT_WAVES is read on every call, PIML_RELFEAT_SPLIT / PIML_RELFEAT_RESIDENT
+ * once per process, as the launcher does.  Returns 0, or hipErrorInvalidValue for sizes (or a PIML_RELFEAT_WAVES) the launcher refuses;
+ * an empty problem (C or focal_count 0) launches nothing: 0 with every output 0. */
+int piml_relfeat_plan(int C, int N, int M, int focal_count, int topk_ped, int topk_obs, int part, int has_pack, int* waves,
+                      int* resident, int* split, int* agent_tiles, int* obstacle_tiles);
 /* The library-owned side streams of PIML_FORK (piml_pinnsf_fwd / bwd with the independent stages forked: measured slower inside
  * captured graphs, kept for A/B): created per device on first use, outside any capture; idempotent. */
 int piml_pinnsf_streams_init(void);

@@ -294,6 +294,7 @@ SIGNATURES = {
     'piml_relfeat_pack_form': [_i],
     'piml_relfeat_pack_plan': [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)],
     'piml_relfeat_pack_tail_blocks': [_i, _i, _i, ctypes.POINTER(_i), _i],
+    'piml_relfeat_plan': [_i] * 8 + [ctypes.POINTER(_i)] * 5,
     'piml_rowdecoder_products': [_i],
     'piml_encoder_dw2': [_i],
     'piml_encoder_fused_bwd': [_i],

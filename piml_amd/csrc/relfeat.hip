@@ -748,6 +748,93 @@ static int relfeat_attr() {
     return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(relfeat_fwd_kernel<W, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
+// The form of a launch: workgroup size, whether both tiles are resident (relfeat_fwd_kernel<W, true>), whether the pedestrian and
+// obstacle passes of a row run in different workgroups, and the LDS tiles each pass stages.  relfeat_launch launches what this says;
+// piml_relfeat_plan hands the same answer to the tests.  kp / ko are the effective k (min(k, N) / min(k, M)).
+struct RelfeatPlan {
+    int waves;
+    bool fits_resident;     // both tiles fit the resident kernel's LDS; it is launched unless the launch is split
+    bool split;
+    int agent_tiles, obstacle_tiles;
+};
+
+static int relfeat_plan(int C, int N, int M, int focal_count, int kp, int ko, int flags, const int (&a_lo)[2], const int (&a_hi)[2],
+                        bool has_pack, RelfeatPlan* P) {
+    const long rows = (long)C * focal_count;
+    // Workgroup size: every workgroup stages the whole source array once, so bigger groups cut
+    // L2->LDS traffic, while smaller groups shorten the barrier tails (the per-wave work is
+    // data dependent) and spread small launches over more CUs.
+    int waves = rows >= 16384 ? 8 : (rows >= 4096 ? 16 : (rows >= 1024 ? 8 : 4));   // measured (tools/time_*.py)
+    // more sources than one tile (every pass re-stages the tile behind two barriers: the shapes of a sharded scene): eight waves
+    // -- round 6, tools/time_sharded_shapes.py: 4096 focal rows x 8192 / 16384 / 32768 sources 26.4 / 36.5 / 57.7 us against
+    // 29.1 / 40.3 / 59.1 with sixteen (and 32.5 / 45.5 / 67.9 with four); 2048 x 16384: 29.7 / 32.8 / 34.0
+    if (N > kTile && rows >= 1024) waves = 8;
+    // Where the search alone wants sixteen waves it takes eight with a deferred pack on board: a 16-wave workgroup has a CU to itself
+    // (67 registers: 7 waves a SIMD), so every pack block waits
+    // for a whole search workgroup to leave; three 8-wave workgroups share a CU, and the pack's 512-thread blocks run beside the
+    // searches -- 22.9 -> 20.9 us for the launch at the 4096-agent scene, where the search alone is 20.3 with sixteen waves and
+    // 20.5 with eight (profiles/r13_pack_placement.md).  The images do not depend on it: 512 and 1024 threads cut the fold and the
+    // zero rows into the same partial sums.
+    if (has_pack && waves == 16) waves = 8;
+    if (const char* e = getenv("PIML_RELFEAT_WAVES")) waves = atoi(e);
+    if (waves != 4 && waves != 8 && waves != 16) return hipErrorInvalidValue;
+    P->waves = waves;
+    // both tiles resident (one barrier per launch) when the agent sources are one tile and the obstacle pass exists and fits
+    static const bool res_off = getenv("PIML_RELFEAT_RESIDENT") && atoi(getenv("PIML_RELFEAT_RESIDENT")) == 0;
+    const bool res = !res_off && (flags & kRfObs) && M > 0 && M <= kObsTile && a_hi[1] == a_lo[1] && a_hi[0] - a_lo[0] <= kTile && ko > 0;
+    // split launch (pedestrian and obstacle passes of a row in different workgroups): whenever the obstacle pass exists
+    static const bool split_off = getenv("PIML_RELFEAT_SPLIT") && atoi(getenv("PIML_RELFEAT_SPLIT")) == 0;
+    // (measured, tools/time_relfeat.py: 8.4 -> 6.2 us at 122 agents, 10.6 -> 7.7 at 1024, 22.3 -> 21.8 at 4096 + 2000 points,
+    // 34.6 -> 29.3 for a rank's 2048 x 16384 share, 120 -> 115 at 16384; 64 slices of 128 agents -- 8192 short rows, bound by
+    // issue slots -- 17.9 -> 22.5: not split)
+    P->split = !split_off && (flags & kRfObs) && M > 0 && ko > 0 && kp > 0 && (C == 1 || rows <= 4096);
+    P->fits_resident = res;
+    P->agent_tiles = (a_hi[0] - a_lo[0] + kTile - 1) / kTile + (a_hi[1] - a_lo[1] + kTile - 1) / kTile;
+    P->obstacle_tiles = (flags & kRfObs) ? (M + kTile - 1) / kTile : 0;
+    return hipSuccess;
+}
+
+// The agent-pass source ranges and the flags of a launch's part (0 = the whole thing, 1 = LOCAL, 2 = REMOTE)
+static int relfeat_part(int part, int N, int focal_begin, int focal_count, int (&a_lo)[2], int (&a_hi)[2]) {
+    a_lo[0] = 0; a_hi[0] = N; a_lo[1] = 0; a_hi[1] = 0;
+    if (part == 1) {            // LOCAL: the focal block's own agents as sources + everything that needs no remote record
+        a_lo[0] = focal_begin; a_hi[0] = focal_begin + focal_count;
+        return kRfObs | kRfDest | kRfPedList;
+    }
+    if (part == 2) {            // REMOTE: the agents either side of the block, continuing the list of the LOCAL part
+        a_lo[0] = 0; a_hi[0] = focal_begin; a_lo[1] = focal_begin + focal_count; a_hi[1] = N;
+        return kRfPedFeat | kRfInit;
+    }
+    return kRfPedFeat | kRfObs | kRfDest;
+}
+
+// Diagnostic (tests, tools): the form relfeat_launch gives a launch of these sizes -- no GPU call is made.  part: 0 = one launch,
+// 1 = LOCAL, 2 = REMOTE of a sharded pair; has_pack: a deferred weight pack rides along.  *waves = 4 / 8 / 16, *resident = the
+// both-tiles-resident kernel, *split = pedestrian and obstacle passes in different workgroups, *agent_tiles / *obstacle_tiles = the
+// LDS tiles the two passes stage (REMOTE: for a block at focal_begin = 0; elsewhere the two ranges either side round up apiece).
+// Any output may be NULL.  Nonzero (hipErrorInvalidValue) for sizes the launcher refuses, a PIML_RELFEAT_WAVES it refuses included;
+// an empty problem (C or focal_count 0) launches nothing: 0, every output 0.
+PIML_API int piml_relfeat_plan(int C, int N, int M, int focal_count, int topk_ped, int topk_obs, int part, int has_pack, int* waves,
+                               int* resident, int* split, int* agent_tiles, int* obstacle_tiles) {
+    if (C < 0 || N < 0 || M < 0 || focal_count < 0 || focal_count > N || topk_ped < 0 || topk_obs < 0 || topk_ped > PIML_MAX_TOPK ||
+        topk_obs > PIML_MAX_TOPK || part < 0 || part > 2)
+        return hipErrorInvalidValue;
+    RelfeatPlan P{};
+    if (C > 0 && focal_count > 0) {
+        int a_lo[2], a_hi[2];
+        const int flags = relfeat_part(part, N, 0, focal_count, a_lo, a_hi);
+        if (int e = relfeat_plan(C, N, M, focal_count, topk_ped < N ? topk_ped : N, topk_obs < M ? topk_obs : M, flags, a_lo, a_hi,
+                                 has_pack != 0, &P))
+            return e;
+    }
+    if (waves) *waves = P.waves;
+    if (resident) *resident = P.fits_resident && !P.split;
+    if (split) *split = P.split;
+    if (agent_tiles) *agent_tiles = P.agent_tiles;
+    if (obstacle_tiles) *obstacle_tiles = P.obstacle_tiles;
+    return hipSuccess;
+}
+
 static int relfeat_launch(const float* position, const float* heading, const float* velocity,
                           const float* acceleration, int state_ld, const float* destination,
                           const float* obstacles, int C, int N, int M, int focal_begin,
@@ -767,16 +854,8 @@ static int relfeat_launch(const float* position, const float* heading, const flo
         return hipErrorInvalidValue;
     if (part != 1 && kpe_ > 0 && !ped_feat) return hipErrorInvalidValue;
     RelfeatArgs A;
-    A.a_lo[0] = 0; A.a_hi[0] = N; A.a_lo[1] = 0; A.a_hi[1] = 0;
-    A.flags = kRfPedFeat | kRfObs | kRfDest;
+    A.flags = relfeat_part(part, N, focal_begin, focal_count, A.a_lo, A.a_hi);
     A.split = 0;
-    if (part == 1) {            // LOCAL: the focal block's own agents as sources + everything that needs no remote record
-        A.a_lo[0] = focal_begin; A.a_hi[0] = focal_begin + focal_count;
-        A.flags = kRfObs | kRfDest | kRfPedList;
-    } else if (part == 2) {     // REMOTE: the agents either side of the block, continuing the list of the LOCAL part
-        A.a_lo[0] = 0; A.a_hi[0] = focal_begin; A.a_lo[1] = focal_begin + focal_count; A.a_hi[1] = N;
-        A.flags = kRfPedFeat | kRfInit;
-    }
     A.p = position; A.v = velocity; A.a = acceleration; A.ld = state_ld;
     A.hd = (const float2*)heading; A.dest = (const float2*)destination; A.obs = (const float2*)obstacles;
     A.C = C; A.N = N; A.M = M; A.f0 = focal_begin; A.fcnt = focal_count;
@@ -791,36 +870,19 @@ static int relfeat_launch(const float* position, const float* heading, const flo
 #ifdef PIML_RELFEAT_STATS
     if (const char* e = getenv("PIML_RELFEAT_STATS_PTR")) A.stats = (int*)strtoull(e, nullptr, 0);
 #endif
-    const long rows = (long)C * focal_count;
-    // Workgroup size: every workgroup stages the whole source array once, so bigger groups cut
-    // L2->LDS traffic, while smaller groups shorten the barrier tails (the per-wave work is
-    // data dependent) and spread small launches over more CUs.
-    int waves = rows >= 16384 ? 8 : (rows >= 4096 ? 16 : (rows >= 1024 ? 8 : 4));   // measured (tools/time_*.py)
-    // more sources than one tile (every pass re-stages the tile behind two barriers: the shapes of a sharded scene): eight waves
-    // -- round 6, tools/time_sharded_shapes.py: 4096 focal rows x 8192 / 16384 / 32768 sources 26.4 / 36.5 / 57.7 us against
-    // 29.1 / 40.3 / 59.1 with sixteen (and 32.5 / 45.5 / 67.9 with four); 2048 x 16384: 29.7 / 32.8 / 34.0
-    if (N > kTile && rows >= 1024) waves = 8;
-    // a pack left by piml_pinnsf_pack(PIML_DEFER_PACK) rides in this launch.  Where the search alone wants sixteen waves it takes
-    // eight with a pack on board: a 16-wave workgroup has a CU to itself (67 registers: 7 waves a SIMD), so every pack block waits
-    // for a whole search workgroup to leave; three 8-wave workgroups share a CU, and the pack's 512-thread blocks run beside the
-    // searches -- 22.9 -> 20.9 us for the launch at the 4096-agent scene, where the search alone is 20.3 with sixteen waves and
-    // 20.5 with eight (profiles/r13_pack_placement.md).  The images do not depend on it: 512 and 1024 threads cut the fold and the
-    // zero rows into the same partial sums.
+    // a pack left by piml_pinnsf_pack(PIML_DEFER_PACK) rides in this launch (relfeat_plan: what that does to the workgroup size)
     PackAll pack_desc;
     const bool has_pack = pending_pack_take(as_stream(stream), &pack_desc);
     const PackAll* pack = has_pack ? &pack_desc : nullptr;
-    if (has_pack && waves == 16) waves = 8;
-    if (const char* e = getenv("PIML_RELFEAT_WAVES")) waves = atoi(e);
-    if (waves != 4 && waves != 8 && waves != 16) {
+    RelfeatPlan P;
+    if (int e = relfeat_plan(C, N, M, focal_count, A.kp, A.ko, A.flags, A.a_lo, A.a_hi, has_pack, &P)) {
         if (has_pack) pending_pack_leave(pack_desc, as_stream(stream));      // (not lost: the next consumer runs it)
-        return hipErrorInvalidValue;
+        return e;
     }
+    const int waves = P.waves;
+    const bool res = P.fits_resident;
     const int bpc = (focal_count + waves - 1) / waves;
     const dim3 grid((unsigned)(C * bpc)), block((unsigned)(waves * 64));
-    // both tiles resident (one barrier per launch) when the agent sources are one tile and the obstacle pass exists and fits
-    static const bool res_off = getenv("PIML_RELFEAT_RESIDENT") && atoi(getenv("PIML_RELFEAT_RESIDENT")) == 0;
-    const bool res = !res_off && (A.flags & kRfObs) && M > 0 && M <= kObsTile && A.a_hi[1] == A.a_lo[1] &&
-                     A.a_hi[0] - A.a_lo[0] <= kTile && A.ko > 0;
     if (res) {
         static int attr = -1;      // dynamic LDS above 64 KB has to be enabled per kernel once per process
         if (attr < 0) {
@@ -833,12 +895,7 @@ static int relfeat_launch(const float* position, const float* heading, const flo
             return attr;
         }
     }
-    // split launch (pedestrian and obstacle passes of a row in different workgroups): whenever the obstacle pass exists
-    static const bool split_off = getenv("PIML_RELFEAT_SPLIT") && atoi(getenv("PIML_RELFEAT_SPLIT")) == 0;
-    // (measured, tools/time_relfeat.py: 8.4 -> 6.2 us at 122 agents, 10.6 -> 7.7 at 1024, 22.3 -> 21.8 at 4096 + 2000 points,
-    // 34.6 -> 29.3 for a rank's 2048 x 16384 share, 120 -> 115 at 16384; 64 slices of 128 agents -- 8192 short rows, bound by
-    // issue slots -- 17.9 -> 22.5: not split)
-    if (!split_off && (A.flags & kRfObs) && M > 0 && A.ko > 0 && A.kp > 0 && (C == 1 || rows <= 4096)) {
+    if (P.split) {
         A.split = 1;
         const dim3 grid2(grid.x * 2);
         switch (waves) {
