@@ -36,6 +36,52 @@ def _f32(x):
     return float(np.float32(x))
 
 
+# What the statistics modules' option checks, entries and comparisons share.
+def _positive(name, x):
+    if isinstance(x, bool) or not (math.isfinite(float(x)) and float(x) > 0 and _f32(x) > 0 and math.isfinite(_f32(x))):
+        raise ValueError(f'{name} must be a positive number, got {x}')
+
+
+def _count(name, x, hi):
+    if isinstance(x, bool) or int(x) != x or not 1 <= int(x) <= hi:
+        raise ValueError(f'{name} must be an integer in 1..{hi}, got {x}')
+
+
+def _window(frames, T):
+    """frames as (a, b) ints, or None; ValueError unless 0 <= a < b (<= T when T is known)"""
+    if frames is None:
+        return None
+    a, b = (int(v) for v in frames)
+    if a < 0 or b <= a or (T is not None and b > T):
+        raise ValueError(f'frames must satisfy 0 <= a < b <= {T}, got {tuple(frames)}')
+    return a, b
+
+
+def _bounds(n_active, S, N, device):
+    """n_active as an int32 (S,) tensor on the device, clamped to [0, N]; None stays None"""
+    if n_active is None:
+        return None
+    n_active = torch.as_tensor(n_active).reshape(-1)
+    if n_active.numel() != S:
+        raise ValueError(f'n_active: {n_active.numel()} bounds for {S} members')
+    return n_active.clamp(0, N).to(device=device, dtype=torch.int32)
+
+
+def _total(x):
+    """sum over the member axis, added in member order, keeping it; None stays None"""
+    if x is None:
+        return None
+    acc = x[0].copy()
+    for m in range(1, x.shape[0]):
+        acc += x[m]
+    return acc[None]
+
+
+def _l1(x, y):
+    """sum |x - y| of two share vectors (0 .. 2); NaN when either has no items"""
+    return float(np.abs(x - y).sum()) if np.isfinite(x).all() and np.isfinite(y).all() else float('nan')
+
+
 def grid_shape(box, cell):
     """(gx, gy) = (ceil((x1 - x0) / h), ceil((y1 - y0) / h)) of the float32 box and cell, in float64 on the host."""
     x0, x1, y0, y1 = (_f32(v) for v in box)
@@ -83,8 +129,7 @@ def check_options(radius=0.7, box=None, cell=0.5, rho_bin=0.25, rho_bins=24, fra
         raise ValueError(f'radius must be a positive number, got {radius}')
     if not (math.isfinite(float(rho_bin)) and float(rho_bin) > 0):
         raise ValueError(f'rho_bin must be a positive number, got {rho_bin}')
-    if isinstance(rho_bins, bool) or int(rho_bins) != rho_bins or not 1 <= int(rho_bins) <= CROWD_MAX_BINS:
-        raise ValueError(f'rho_bins must be an integer in 1..{CROWD_MAX_BINS}, got {rho_bins}')
+    _count('rho_bins', rho_bins, CROWD_MAX_BINS)
     grid = None
     if box is not None:
         box = tuple(float(v) for v in box)
@@ -95,12 +140,7 @@ def check_options(radius=0.7, box=None, cell=0.5, rho_bin=0.25, rho_bins=24, fra
         if not (math.isfinite(float(cell)) and float(cell) > 0):
             raise ValueError(f'cell must be a positive number, got {cell}')
         grid = grid_shape(box, cell)
-    if frames is not None:
-        a, b = (int(v) for v in frames)
-        if a < 0 or b <= a or (T is not None and b > T):
-            raise ValueError(f'frames must satisfy 0 <= a < b <= {T}, got {tuple(frames)}')
-        frames = (a, b)
-    return box, grid, frames
+    return box, grid, _window(frames, T)
 
 
 def _promote(P, V, M):
@@ -268,11 +308,7 @@ def crowd_stats(P, V, M, radius=0.7, box=None, cell=0.5, rho_bin=0.25, rho_bins=
     box, grid, frames = check_options(radius, box, cell, rho_bin, rho_bins, frames, T)
     density, cutoff, bounds, sides = check_density(density, cutoff, bounds, sides)
     frames = frames or (0, T)
-    if n_active is not None:
-        n_active = torch.as_tensor(n_active).reshape(-1)
-        if n_active.numel() != S:
-            raise ValueError(f'n_active: {n_active.numel()} bounds for {S} members')
-        n_active = n_active.clamp(0, N).to(device=P.device, dtype=torch.int32)
+    n_active = _bounds(n_active, S, N, P.device)
     if density == 'voronoi':
         out = ops_metrics.crowd_stats_voronoi_frames(P, V, M, cutoff, voronoi_dirs(sides), bounds, box, grid, cell, rho_bin,
                                                      int(rho_bins), frames, return_density, n_active)

@@ -56,9 +56,24 @@ __device__ __forceinline__ u64 shift_up1(u64 x) {
     unsigned hi = (unsigned)__shfl_up((int)(unsigned)(x >> 32), 1, 64);
     return ((u64)hi << 32) | lo;
 }
-__device__ __forceinline__ float wave_sum(float x) {
+// butterfly reductions over the 64 lanes (float, double, int, long long, unsigned long long): every lane returns the result;
+// min and max of floats are fminf / fmaxf (a NaN operand is skipped)
+template <class T>
+__device__ __forceinline__ T wave_sum(T x) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+template <class T>
+__device__ __forceinline__ T wave_min(T x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = min(x, __shfl_xor(x, o, 64));
+    return x;
+}
+template <class T>
+__device__ __forceinline__ T wave_max(T x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = max(x, __shfl_xor(x, o, 64));
     return x;
 }
 

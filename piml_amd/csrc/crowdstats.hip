@@ -75,8 +75,7 @@ __device__ __forceinline__ void crowd_density_body(const CrowdArgs& a) {
             bool focal = false;
             if (i < bound) {
                 pi = P[i];
-                focal = cd_present(M[i], pi) &&
-                        (!a.has_box || (a.x0 <= pi.x && pi.x < a.x1 && a.y0 <= pi.y && pi.y < a.y1));
+                focal = cd_present(M[i], pi) && in_box(a.has_box, a.x0, a.x1, a.y0, a.y1, pi);
             }
             float rho_given = 0.f;
             if constexpr (GIVEN) {
@@ -126,8 +125,8 @@ __device__ __forceinline__ void crowd_density_body(const CrowdArgs& a) {
                 const int bb = __shfl(bin, (int)__builtin_ctzll(pending), 64);
                 const bool mine = bin == bb;
                 const u64 mm = __ballot(mine);
-                const double su = cd_wave_sum(mine ? (double)u : 0.0);
-                const double su2 = cd_wave_sum(mine ? (double)u * (double)u : 0.0);
+                const double su = wave_sum(mine ? (double)u : 0.0);
+                const double su2 = wave_sum(mine ? (double)u * (double)u : 0.0);
                 if (lane == 0) {
                     w_sum[w][bb] += su;
                     w_sum2[w][bb] += su2;
@@ -139,10 +138,10 @@ __device__ __forceinline__ void crowd_density_body(const CrowdArgs& a) {
         if (a.density)
             for (int i = max(bound, 0) + tid; i < a.N; i += CD_THREADS) a.density[sl * a.N + i] = NAN;
         // the slice's series: lanes in butterfly order, then the waves in order
-        n_focal = cd_wave_sum(n_focal);
-        n_spd = cd_wave_sum(n_spd);
-        s_speed = cd_wave_sum(s_speed);
-        s_dens = cd_wave_sum(s_dens);
+        n_focal = wave_sum(n_focal);
+        n_spd = wave_sum(n_spd);
+        s_speed = wave_sum(s_speed);
+        s_dens = wave_sum(s_dens);
         if (lane == 0) {
             red_i[0][w] = n_focal;
             red_i[1][w] = n_spd;
@@ -196,9 +195,9 @@ __global__ void __launch_bounds__(CD_THREADS) crowd_fd_reduce_kernel(CrowdArgs a
         su2 += a.ws_sum2[k];
         c += a.ws_count[k];
     }
-    su = cd_wave_sum(su);
-    su2 = cd_wave_sum(su2);
-    c = cd_wave_sum(c);
+    su = wave_sum(su);
+    su2 = wave_sum(su2);
+    c = wave_sum(c);
     if (lane == 0) {
         red[0][w] = su;
         red[1][w] = su2;

@@ -1,8 +1,8 @@
 // What the two crowd-statistics entries share (crowdstats.hip: Gaussian density; voronoi.hip: Voronoi density): the kernel
-// arguments, the presence rule, the wave sums, the LDS staging of a slice's present agents, and the host half that checks
+// arguments, the presence rule, the LDS staging of a slice's present agents, and the host half that checks
 // the common arguments and launches the statistics pass and the diagram's reduce pass.
 #pragma once
-#include "common.hpp"
+#include "stats.hpp"
 
 namespace piml {
 
@@ -31,45 +31,14 @@ struct CrowdArgs {
     const float* rho_in;                      // (S T', N) densities computed beforehand (NaN: not focal), or NULL
 };
 
-__device__ __forceinline__ double cd_wave_sum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ __forceinline__ long long cd_wave_sum(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 __device__ __forceinline__ bool cd_present(float m, float2 p) { return m == 1.f && isfinite(p.x) && isfinite(p.y); }
 
-// Compacts the present agents of slots [lo, hi) (hi - lo <= CD_TILE) into src in slot order; returns their number.  Every
-// thread of the workgroup calls it; src may still be read by other waves on entry (no write before the first barrier).
+// Compacts the present agents of slots [lo, hi) (hi - lo <= CD_TILE) into src in slot order; returns their number
+// (wg_compact: every thread calls it, and src may still be read on entry).
 __device__ inline int cd_stage(const float2* P, const float* M, int lo, int hi, float2* src, int* wave_cnt) {
-    const int tid = threadIdx.x, w = tid >> 6;
-    int base = 0;
-    for (int s0 = lo; s0 < hi; s0 += CD_THREADS) {
-        const int j = s0 + tid;
-        float2 p = make_float2(0.f, 0.f);
-        bool pres = false;
-        if (j < hi) {
-            p = P[j];
-            pres = cd_present(M[j], p);
-        }
-        const u64 b = __ballot(pres);
-        if ((tid & 63) == 0) wave_cnt[w] = __popcll(b);
-        __syncthreads();
-        int before = base, total = base;
-        for (int k = 0; k < CD_WAVES; ++k) {
-            before += k < w ? wave_cnt[k] : 0;
-            total += wave_cnt[k];
-        }
-        if (pres) src[before + (int)mbcnt(b)] = p;
-        __syncthreads();                      // src complete; wave_cnt is rewritten by the next round
-        base = total;
-    }
-    return base;
+    float2 p;
+    return wg_compact<CD_THREADS>(
+        lo, hi, wave_cnt, [&](int j) { return p = P[j], cd_present(M[j], p); }, [&](int q, int) { src[q] = p; });
 }
 
 // crowdstats.hip.  cd_prepare: checks every argument the two entries share and fills `a` (workspace: the diagram's slots

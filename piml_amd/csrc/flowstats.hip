@@ -29,7 +29,7 @@
 //
 // No u32 counter overflows: per slice a wave's bin holds at most (ceil(N / 256) * 64) * N <= 2^30 pairs for N <= FS_MAX_N,
 // a lane's band at most N agents, and the u32 rows are folded into u64 after every slice.
-#include "common.hpp"
+#include "stats.hpp"
 #include "../../include/piml_hip.h"
 
 #include <cmath>
@@ -81,76 +81,19 @@ __device__ __forceinline__ FsAgent fs_agent(const FlowArgs& a, float2 v) {
     return g;
 }
 
-__device__ __forceinline__ long long fs_wave_sum(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 // Compacts the participants of slots [lo, hi) (hi - lo <= FS_TILE) into ph / ve / slot in slot order; returns their
-// number.  Every thread of the workgroup calls it; the tile may still be read by other waves on entry (no write before the
-// first barrier).
+// number (wg_compact: every thread calls it, and the tile may still be read on entry).
 __device__ int fs_stage(const FlowArgs& a, const float2* P, const float2* V, const float* M, int lo, int hi, float4* ph,
                         float* ve, int* slot, int* wave_cnt) {
-    const int tid = threadIdx.x, w = tid >> 6;
-    int base = 0;
-    for (int s0 = lo; s0 < hi; s0 += FS_THREADS) {
-        const int j = s0 + tid;
-        float2 p = make_float2(0.f, 0.f), v = make_float2(0.f, 0.f);
-        bool part = false;
-        if (j < hi) {
-            p = P[j];
-            v = V[j];
-            part = fs_participant(M[j], p, v);
-        }
-        const u64 b = __ballot(part);
-        if ((tid & 63) == 0) wave_cnt[w] = __popcll(b);
-        __syncthreads();
-        int before = base, total = base;
-        for (int k = 0; k < FS_WAVES; ++k) {
-            before += k < w ? wave_cnt[k] : 0;
-            total += wave_cnt[k];
-        }
-        if (part) {
-            const int q = before + (int)mbcnt(b);
+    float2 p, v;
+    return wg_compact<FS_THREADS>(
+        lo, hi, wave_cnt, [&](int j) { return p = P[j], v = V[j], fs_participant(M[j], p, v); },
+        [&](int q, int j) {
             const FsAgent g = fs_agent(a, v);
             ph[q] = make_float4(p.x, p.y, g.hx, g.hy);
             ve[q] = g.ve;
             slot[q] = j;
-        }
-        __syncthreads();                      // tile complete; wave_cnt is rewritten by the next round
-        base = total;
-    }
-    return base;
-}
-
-// Compacts the focal agents of slots [lo, hi) (hi - lo <= FS_TILE) into fslot in slot order; returns their number.  Every
-// thread of the workgroup calls it.
-__device__ int fs_stage_focal(const FlowArgs& a, const float2* P, const float2* V, const float* M, int lo, int hi, int* fslot,
-                              int* wave_cnt) {
-    const int tid = threadIdx.x, w = tid >> 6;
-    int base = 0;
-    for (int s0 = lo; s0 < hi; s0 += FS_THREADS) {
-        const int j = s0 + tid;
-        bool focal = false;
-        if (j < hi) {
-            const float2 p = P[j], v = V[j];
-            focal = fs_participant(M[j], p, v) &&
-                    (!a.has_box || (a.x0 <= p.x && p.x < a.x1 && a.y0 <= p.y && p.y < a.y1));
-        }
-        const u64 b = __ballot(focal);
-        if ((tid & 63) == 0) wave_cnt[w] = __popcll(b);
-        __syncthreads();
-        int before = base, total = base;
-        for (int k = 0; k < FS_WAVES; ++k) {
-            before += k < w ? wave_cnt[k] : 0;
-            total += wave_cnt[k];
-        }
-        if (focal) fslot[before + (int)mbcnt(b)] = j;
-        __syncthreads();                      // fslot complete; wave_cnt is rewritten by the next round
-        base = total;
-    }
-    return base;
+        });
 }
 
 // The sweep of one focal agent (slot i at pi, heading / v.e in g) over cnt staged sources: (a) into the wave's rows, (b)
@@ -242,7 +185,13 @@ __global__ void __launch_bounds__(FS_THREADS) flow_stats_kernel(FlowArgs a) {
             long long l_n = 0, l_sum = 0, l_same = 0, l_opp = 0, d_plus = 0, d_minus = 0;
             // focal agents: each tile of FS_TILE candidate slots compacted into fslot, then one per lane in chunks of 256
             for (int f_lo = 0; f_lo < bound; f_lo += FS_TILE) {
-                const int nf = fs_stage_focal(a, P, V, M, f_lo, min(f_lo + FS_TILE, bound), fslot, wave_cnt);
+                const int nf = wg_compact<FS_THREADS>(
+                    f_lo, min(f_lo + FS_TILE, bound), wave_cnt,
+                    [&](int j) {
+                        const float2 p = P[j];
+                        return fs_participant(M[j], p, V[j]) && in_box(a.has_box, a.x0, a.x1, a.y0, a.y1, p);
+                    },
+                    [&](int q, int j) { fslot[q] = j; });
                 for (int c0 = 0; c0 < nf; c0 += FS_THREADS) {
                     const bool focal = c0 + tid < nf;
                     const int i = focal ? fslot[c0 + tid] : -1;
@@ -291,8 +240,8 @@ __global__ void __launch_bounds__(FS_THREADS) flow_stats_kernel(FlowArgs a) {
                 __syncthreads();              // fslot is rewritten by the next focal tile
             }
             // the slice's series: lanes, then waves; its rows: the waves' rows added into the 64-bit accumulator
-            const long long ser[FS_SERIES] = {fs_wave_sum(l_n),    fs_wave_sum(l_sum),  fs_wave_sum(l_same),
-                                              fs_wave_sum(l_opp),  fs_wave_sum(d_plus), fs_wave_sum(d_minus)};
+            const long long ser[FS_SERIES] = {wave_sum(l_n),    wave_sum(l_sum),  wave_sum(l_same),
+                                              wave_sum(l_opp),  wave_sum(d_plus), wave_sum(d_minus)};
             if (lane == 0) {
 #pragma unroll
                 for (int k = 0; k < FS_SERIES; ++k) red[k][w] = ser[k];
@@ -375,8 +324,7 @@ PIML_API int piml_flow_stats(const float* P, const float* V, const float* M, con
     a.P = P, a.V = V, a.M = M, a.n_active = n_active;
     a.S = S, a.T = T, a.N = N, a.t0 = t0, a.Tp = t1 - t0, a.RB = r_bins;
     a.slices = (long long)S * a.Tp;
-    const long long run = a.slices / FS_TARGET_WG;
-    a.run = (int)(run < 1 ? 1 : run > FS_MAX_RUN ? FS_MAX_RUN : run);
+    const unsigned grid = stats_run_grid(a.slices, FS_TARGET_WG, FS_MAX_RUN, FS_MAX_GRID, &a.run);
     a.has_box = has_box ? 1 : 0, a.gx = has_box ? gx : 0, a.gy = has_box ? gy : 0;
     a.v_min = v_min, a.r_bin = r_bin, a.r_max = r_max, a.ex = ex, a.ey = ey;
     a.lane_width = lane_width, a.lane_length = lane_length;
@@ -395,9 +343,7 @@ PIML_API int piml_flow_stats(const float* P, const float* V, const float* M, con
     hipStream_t st = as_stream(stream);
     hipError_t e = hipMemsetAsync(workspace, 0, (size_t)need, st);
     if (e != hipSuccess) return e;
-    const long long runs = (a.slices + a.run - 1) / a.run;
-    hipLaunchKernelGGL(flow_stats_kernel, dim3((unsigned)(runs < FS_MAX_GRID ? runs : FS_MAX_GRID)), dim3(FS_THREADS), 0, st,
-                       a);
+    hipLaunchKernelGGL(flow_stats_kernel, dim3(grid), dim3(FS_THREADS), 0, st, a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     const long long elems = need / (long long)sizeof(unsigned long long);

@@ -63,21 +63,6 @@ __device__ __forceinline__ bool gs_participant(float m, float2 p) {
     return m == 1.f && fabsf(p.x) < GS_MAX_COORD && fabsf(p.y) < GS_MAX_COORD;
 }
 
-__device__ __forceinline__ long long gs_wave_sum(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ __forceinline__ int gs_wave_min(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = min(x, __shfl_xor(x, o, 64));
-    return x;
-}
-__device__ __forceinline__ int gs_wave_max(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = max(x, __shfl_xor(x, o, 64));
-    return x;
-}
 
 // the pair-frame predicate, shared by both passes: e = p_j - p_i, u_i, u_j
 __device__ __forceinline__ bool gs_together(float ex, float ey, float uix, float uiy, float ujx, float ujy, float r2,
@@ -111,7 +96,7 @@ __global__ void __launch_bounds__(GS_THREADS) group_pairs_kernel(GroupPairArgs a
                 }
             }
         }
-        first = gs_wave_min(first), last = gs_wave_max(last);
+        first = wave_min(first), last = wave_max(last);
         if (lane == 0) span[0][w] = first, span[1][w] = last;
         __syncthreads();
         first = span[0][0], last = span[1][0];
@@ -179,7 +164,7 @@ __global__ void __launch_bounds__(GS_THREADS) group_pairs_kernel(GroupPairArgs a
                     reinterpret_cast<int4*>(a.edges)[(long long)s * a.max_edges + pos] = make_int4(i, j, co, near);
             }
         }
-        steps = gs_wave_sum(steps), path = gs_wave_sum(path), pairs = gs_wave_sum(pairs), tog = gs_wave_sum(tog);
+        steps = wave_sum(steps), path = wave_sum(path), pairs = wave_sum(pairs), tog = wave_sum(tog);
         if (lane == 0) {
             red[0][w] = steps, red[1][w] = path;
             if (pairs) atomicAdd(a.pairs + s, (unsigned long long)pairs);
@@ -236,7 +221,7 @@ __global__ void __launch_bounds__(GS_THREADS) group_members_kernel(GroupMemberAr
                 atomicAdd(h_abr + (qa < (float)(AB - 1) ? (int)qa : AB - 1), 1u);
             }
         }
-        dsum = gs_wave_sum(dsum), skipped = gs_wave_sum(skipped), n = gs_wave_sum(n);
+        dsum = wave_sum(dsum), skipped = wave_sum(skipped), n = wave_sum(n);
         if (lane == 0) {
             if (dsum) atomicAdd(a.dist_sum + s, (unsigned long long)dsum);
             if (skipped) atomicAdd(a.skipped + s, (unsigned long long)skipped);

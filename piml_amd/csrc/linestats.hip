@@ -58,11 +58,6 @@ __device__ __forceinline__ bool ls_participant(float m, float2 p) {
     return m == 1.f && fabsf(p.x) < LS_MAX_COORD && fabsf(p.y) < LS_MAX_COORD;
 }
 
-__device__ __forceinline__ long long ls_wave_sum(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
 
 __global__ void __launch_bounds__(LS_THREADS) line_stats_kernel(LineArgs a) {
     __shared__ float ln[LS_MAX_L][8];              // ax, ay, dx, dy, len2, sqrt(len2)
@@ -129,7 +124,7 @@ __global__ void __launch_bounds__(LS_THREADS) line_stats_kernel(LineArgs a) {
             }
             if (steps) atomicAdd(a.ws + a.o_tsteps + (long long)s * a.N + i, (unsigned long long)steps);
         }
-        steps = ls_wave_sum(steps);
+        steps = wave_sum(steps);
         if (lane == 0 && steps) atomicAdd(a.ws + a.o_steps + s, (unsigned long long)steps);
     }
 }

@@ -33,16 +33,6 @@ static int metric_threads(int n, int m) {
     return t < 256 ? 256 : (t > 1024 ? 1024 : t);
 }
 
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
-    return x;
-}
-__device__ __forceinline__ double wave_sum_d(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
 
 // f(slot, compacted index or -1) for every slot of an n-point frame, in slot order; returns the number of present slots.
 // `wave_cnt` is MET_MAX_WAVES ints of LDS; every thread of the workgroup must call it.
@@ -77,7 +67,7 @@ __device__ __forceinline__ int compact(const float* pts, const unsigned char* ma
 // fixed-order sum over the waves of the workgroup of one value per wave (lane 0's); every thread returns the total
 __device__ __forceinline__ double block_sum_d(double x, double* red) {
     const int w = threadIdx.x >> 6, W = blockDim.x >> 6;
-    x = wave_sum_d(x);
+    x = wave_sum(x);
     __syncthreads();                          // red may still be read by a previous call
     if ((threadIdx.x & 63) == 0) red[w] = x;
     __syncthreads();

@@ -32,7 +32,7 @@
 // LDS: 32 KiB of points + 4 KiB of focal slots + 8.1 KiB of accumulator = 44.2 KiB, three workgroups (12 waves) per CU; the
 // sweep is bound by its ~45 vector instructions per point (the IEEE division of s among them), not by the broadcast read,
 // and the registers stay far below the 128 that 12 waves per CU allow.
-#include "common.hpp"
+#include "stats.hpp"
 #include "../../include/piml_hip.h"
 
 #include <cmath>
@@ -77,67 +77,19 @@ __device__ __forceinline__ bool os_participant(float m, float2 p, float2 v) {
 }
 
 // Compacts the valid points of obs[lo, hi) (hi - lo <= OS_TILE) into pts in list order; returns their number, rounded up to
-// an even one.  Every thread of the workgroup calls it; the tile may still be read by other waves on entry (no write before
-// the first barrier).
+// an even one (wg_compact: every thread calls it, and the tile may still be read on entry).
 __device__ int os_stage_points(const float2* obs, int lo, int hi, float2* pts, int* wave_cnt) {
-    const int tid = threadIdx.x, w = tid >> 6;
-    int base = 0;
-    for (int s0 = lo; s0 < hi; s0 += OS_THREADS) {
-        const int j = s0 + tid;
-        float2 q = make_float2(0.f, 0.f);
-        bool valid = false;
-        if (j < hi) {
-            q = obs[j];
-            valid = isfinite(q.x) && isfinite(q.y);
-        }
-        const u64 b = __ballot(valid);
-        if ((tid & 63) == 0) wave_cnt[w] = __popcll(b);
-        __syncthreads();
-        int before = base, total = base;
-        for (int k = 0; k < OS_WAVES; ++k) {
-            before += k < w ? wave_cnt[k] : 0;
-            total += wave_cnt[k];
-        }
-        if (valid) pts[before + (int)mbcnt(b)] = q;
-        __syncthreads();                      // tile complete; wave_cnt is rewritten by the next round
-        base = total;
-    }
+    float2 pt;
+    int cnt = wg_compact<OS_THREADS>(
+        lo, hi, wave_cnt, [&](int j) { return pt = obs[j], isfinite(pt.x) && isfinite(pt.y); },
+        [&](int q, int) { pts[q] = pt; });
     // an odd number is made even with a copy of the last point, which changes no minimum: the sweep reads pairs
-    if (base & 1) {
-        if (tid == 0) pts[base] = pts[base - 1];
-        ++base;
+    if (cnt & 1) {
+        if (threadIdx.x == 0) pts[cnt] = pts[cnt - 1];
+        ++cnt;
         __syncthreads();
     }
-    return base;
-}
-
-// Compacts the focal agents of slots [lo, hi) (hi - lo <= OS_FOCAL_TILE) of frame (P, V, M) into fslot in slot order;
-// returns their number.  Every thread of the workgroup calls it.
-__device__ int os_stage_focal(const ObstacleArgs& a, const float2* P, const float2* V, const float* M, int lo, int hi,
-                              int* fslot, int* wave_cnt) {
-    const int tid = threadIdx.x, w = tid >> 6;
-    int base = 0;
-    for (int s0 = lo; s0 < hi; s0 += OS_THREADS) {
-        const int j = s0 + tid;
-        bool focal = false;
-        if (j < hi) {
-            const float2 p = P[j], v = V[j];
-            focal = os_participant(M[j], p, v) &&
-                    (!a.has_box || (a.x0 <= p.x && p.x < a.x1 && a.y0 <= p.y && p.y < a.y1));
-        }
-        const u64 b = __ballot(focal);
-        if ((tid & 63) == 0) wave_cnt[w] = __popcll(b);
-        __syncthreads();
-        int before = base, total = base;
-        for (int k = 0; k < OS_WAVES; ++k) {
-            before += k < w ? wave_cnt[k] : 0;
-            total += wave_cnt[k];
-        }
-        if (focal) fslot[before + (int)mbcnt(b)] = j;
-        __syncthreads();                      // fslot complete; wave_cnt is rewritten by the next round
-        base = total;
-    }
-    return base;
+    return cnt;
 }
 
 struct OsLane {
@@ -231,7 +183,13 @@ __global__ void __launch_bounds__(OS_THREADS) obstacle_stats_kernel(ObstacleArgs
             if (a.n_active) bound = min(max(a.n_active[s], 0), N);
             unsigned long long* trk = w_trk + (long long)s * N;
             for (int f_lo = 0; f_lo < bound; f_lo += OS_FOCAL_TILE) {
-                const int nf = os_stage_focal(a, P0, V0, M0, f_lo, min(f_lo + OS_FOCAL_TILE, bound), fslot, wave_cnt);
+                const int nf = wg_compact<OS_THREADS>(
+                    f_lo, min(f_lo + OS_FOCAL_TILE, bound), wave_cnt,
+                    [&](int j) {
+                        const float2 p = P0[j];
+                        return os_participant(M0[j], p, V0[j]) && in_box(a.has_box, a.x0, a.x1, a.y0, a.y1, p);
+                    },
+                    [&](int q, int j) { fslot[q] = j; });
                 for (int c0 = 0; c0 < nf; c0 += OS_THREADS) {
                     const bool focal = c0 + tid < nf;
                     const int i = focal ? fslot[c0 + tid] : 0;
@@ -372,8 +330,7 @@ PIML_API int piml_obstacle_stats(const float* P, const float* V, const float* M,
     a.P = P, a.V = V, a.M = M, a.n_active = n_active, a.obs = obs;
     a.S = S, a.T = T, a.N = N, a.O = O, a.t0 = t0, a.Tp = t1 - t0, a.RB = r_bins, a.TB = tau_bins;
     a.slices = (long long)S * a.Tp;
-    const long long run = a.slices / OS_TARGET_WG;
-    a.run = (int)(run < 1 ? 1 : run > OS_MAX_RUN ? OS_MAX_RUN : run);
+    const unsigned grid = stats_run_grid(a.slices, OS_TARGET_WG, OS_MAX_RUN, OS_MAX_GRID, &a.run);
     a.has_box = has_box ? 1 : 0;
     a.x0 = x0, a.x1 = x1, a.y0 = y0, a.y1 = y1;
     a.radius = radius, a.r2 = radius * radius, a.hit_radius = hit_radius;
@@ -385,9 +342,7 @@ PIML_API int piml_obstacle_stats(const float* P, const float* V, const float* M,
     hipStream_t st = as_stream(stream);
     hipError_t e = hipMemsetAsync(workspace, 0, (size_t)need, st);
     if (e != hipSuccess) return e;
-    const long long runs = (a.slices + a.run - 1) / a.run;
-    hipLaunchKernelGGL(obstacle_stats_kernel, dim3((unsigned)(runs < OS_MAX_GRID ? runs : OS_MAX_GRID)), dim3(OS_THREADS), 0, st,
-                       a);
+    hipLaunchKernelGGL(obstacle_stats_kernel, dim3(grid), dim3(OS_THREADS), 0, st, a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     const long long elems = need / (long long)sizeof(unsigned long long);

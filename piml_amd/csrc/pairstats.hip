@@ -22,7 +22,7 @@
 //
 // No u32 counter overflows: per slice a wave's bin holds at most (ceil(N / 256) * 64) * N < 2^32 pairs for N <= PS_MAX_N,
 // and the u32 rows are folded into u64 after every slice.
-#include "common.hpp"
+#include "stats.hpp"
 #include "../../include/piml_hip.h"
 
 #include <cmath>
@@ -58,74 +58,14 @@ __device__ __forceinline__ bool ps_participant(float m, float2 p, float2 v) {
     return m == 1.f && isfinite(p.x) && isfinite(p.y) && isfinite(v.x) && isfinite(v.y);
 }
 
-__device__ __forceinline__ unsigned long long ps_wave_sum(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-// Compacts the participants of slots [lo, hi) (hi - lo <= PS_TILE) into pv / slot in slot order; returns their number.
-// Every thread of the workgroup calls it; the tile may still be read by other waves on entry (no write before the first
-// barrier).
+// Compacts the participants of slots [lo, hi) (hi - lo <= PS_TILE) into pv / slot in slot order; returns their number
+// (wg_compact: every thread calls it, and the tile may still be read on entry).
 __device__ int ps_stage(const float2* P, const float2* V, const float* M, int lo, int hi, float4* pv, int* slot,
                         int* wave_cnt) {
-    const int tid = threadIdx.x, w = tid >> 6;
-    int base = 0;
-    for (int s0 = lo; s0 < hi; s0 += PS_THREADS) {
-        const int j = s0 + tid;
-        float2 p = make_float2(0.f, 0.f), v = make_float2(0.f, 0.f);
-        bool part = false;
-        if (j < hi) {
-            p = P[j];
-            v = V[j];
-            part = ps_participant(M[j], p, v);
-        }
-        const u64 b = __ballot(part);
-        if ((tid & 63) == 0) wave_cnt[w] = __popcll(b);
-        __syncthreads();
-        int before = base, total = base;
-        for (int k = 0; k < PS_WAVES; ++k) {
-            before += k < w ? wave_cnt[k] : 0;
-            total += wave_cnt[k];
-        }
-        if (part) {
-            const int q = before + (int)mbcnt(b);
-            pv[q] = make_float4(p.x, p.y, v.x, v.y);
-            slot[q] = j;
-        }
-        __syncthreads();                      // tile complete; wave_cnt is rewritten by the next round
-        base = total;
-    }
-    return base;
-}
-
-// Compacts the focal agents of slots [lo, hi) (hi - lo <= PS_TILE) of frame (P, V, M) into fslot in slot order; returns
-// their number.  Every thread of the workgroup calls it.
-__device__ int ps_stage_focal(const PairArgs& a, const float2* P, const float2* V, const float* M, int lo, int hi,
-                              int* fslot, int* wave_cnt) {
-    const int tid = threadIdx.x, w = tid >> 6;
-    int base = 0;
-    for (int s0 = lo; s0 < hi; s0 += PS_THREADS) {
-        const int j = s0 + tid;
-        bool focal = false;
-        if (j < hi) {
-            const float2 p = P[j], v = V[j];
-            focal = ps_participant(M[j], p, v) &&
-                    (!a.has_box || (a.x0 <= p.x && p.x < a.x1 && a.y0 <= p.y && p.y < a.y1));
-        }
-        const u64 b = __ballot(focal);
-        if ((tid & 63) == 0) wave_cnt[w] = __popcll(b);
-        __syncthreads();
-        int before = base, total = base;
-        for (int k = 0; k < PS_WAVES; ++k) {
-            before += k < w ? wave_cnt[k] : 0;
-            total += wave_cnt[k];
-        }
-        if (focal) fslot[before + (int)mbcnt(b)] = j;
-        __syncthreads();                      // fslot complete; wave_cnt is rewritten by the next round
-        base = total;
-    }
-    return base;
+    float2 p, v;
+    return wg_compact<PS_THREADS>(
+        lo, hi, wave_cnt, [&](int j) { return p = P[j], v = V[j], ps_participant(M[j], p, v); },
+        [&](int q, int j) { pv[q] = make_float4(p.x, p.y, v.x, v.y), slot[q] = j; });
 }
 
 struct PsLane {
@@ -243,7 +183,13 @@ __global__ void __launch_bounds__(PS_THREADS) pair_stats_kernel(PairArgs a) {
             unsigned n_focal = 0;
             // focal agents: each tile of PS_TILE candidate slots compacted into fslot, then one per lane in chunks of 256
             for (int f_lo = 0; f_lo < bound; f_lo += PS_TILE) {
-                const int nf = ps_stage_focal(a, Pi, Vi, Mi, f_lo, min(f_lo + PS_TILE, bound), fslot, wave_cnt);
+                const int nf = wg_compact<PS_THREADS>(
+                    f_lo, min(f_lo + PS_TILE, bound), wave_cnt,
+                    [&](int j) {
+                        const float2 p = Pi[j];
+                        return ps_participant(Mi[j], p, Vi[j]) && in_box(a.has_box, a.x0, a.x1, a.y0, a.y1, p);
+                    },
+                    [&](int q, int j) { fslot[q] = j; });
                 for (int c0 = 0; c0 < nf; c0 += PS_THREADS) {
                     const bool focal = c0 + tid < nf;
                     const int i = focal ? fslot[c0 + tid] : -1;
@@ -275,9 +221,9 @@ __global__ void __launch_bounds__(PS_THREADS) pair_stats_kernel(PairArgs a) {
                 __syncthreads();              // fslot is rewritten by the next focal tile
             }
             // the slice's counters: lanes, then waves; its rows: the waves' u32 rows added into the u64 accumulator
-            const unsigned long long f = ps_wave_sum((unsigned long long)n_focal);
-            const unsigned long long p = ps_wave_sum((unsigned long long)l.pairs);
-            const unsigned long long o = ps_wave_sum((unsigned long long)l.overlap);
+            const unsigned long long f = wave_sum((unsigned long long)n_focal);
+            const unsigned long long p = wave_sum((unsigned long long)l.pairs);
+            const unsigned long long o = wave_sum((unsigned long long)l.overlap);
             if (lane == 0) {
                 red[0][w] = f;
                 red[1][w] = p;
@@ -368,8 +314,7 @@ PIML_API int piml_pair_stats(const float* P, const float* V, const float* M, con
     for (int k = K + 2; k < PS_MAX_LAGS + 2; ++k) a.off[k] = a.off[K + 1];
     a.per_member = a.off[K + 1];
     a.slices = (long long)S * a.per_member;
-    const long long run = a.slices / PS_TARGET_WG;
-    a.run = (int)(run < 1 ? 1 : run > PS_MAX_RUN ? PS_MAX_RUN : run);
+    const unsigned grid = stats_run_grid(a.slices, PS_TARGET_WG, PS_MAX_RUN, PS_MAX_GRID, &a.run);
     a.has_box = has_box ? 1 : 0;
     a.x0 = x0, a.x1 = x1, a.y0 = y0, a.y1 = y1;
     a.has_rmax = r_max > 0.f ? 1 : 0;
@@ -381,10 +326,8 @@ PIML_API int piml_pair_stats(const float* P, const float* V, const float* M, con
     hipStream_t st = as_stream(stream);
     hipError_t e = hipMemsetAsync(workspace, 0, (size_t)need, st);
     if (e != hipSuccess) return e;
-    const long long runs = (a.slices + a.run - 1) / a.run;
-    if (runs > 0) {
-        hipLaunchKernelGGL(pair_stats_kernel, dim3((unsigned)(runs < PS_MAX_GRID ? runs : PS_MAX_GRID)), dim3(PS_THREADS), 0,
-                           st, a);
+    if (grid > 0) {
+        hipLaunchKernelGGL(pair_stats_kernel, dim3(grid), dim3(PS_THREADS), 0, st, a);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

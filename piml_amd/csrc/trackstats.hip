@@ -67,21 +67,6 @@ __device__ __forceinline__ bool ts_participant(float m, float2 p) {
     return m == 1.f && fabsf(p.x) < TS_MAX_COORD && fabsf(p.y) < TS_MAX_COORD;
 }
 
-__device__ __forceinline__ long long ts_wave_sum(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ __forceinline__ int ts_wave_min(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = min(x, __shfl_xor(x, o, 64));
-    return x;
-}
-__device__ __forceinline__ int ts_wave_max(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = max(x, __shfl_xor(x, o, 64));
-    return x;
-}
 
 __global__ void __launch_bounds__(TS_THREADS) track_stats_kernel(TrackArgs a) {
     __shared__ float4 e[TS_ENTRIES];
@@ -115,7 +100,7 @@ __global__ void __launch_bounds__(TS_THREADS) track_stats_kernel(TrackArgs a) {
                 }
             }
         }
-        first = ts_wave_min(first), last = ts_wave_max(last), frames = (int)ts_wave_sum(frames);
+        first = wave_min(first), last = wave_max(last), frames = (int)wave_sum(frames);
         if (lane == 0) span[0][w] = first, span[1][w] = last, span[2][w] = frames;
         __syncthreads();
         first = span[0][0], last = span[1][0], frames = span[2][0];
@@ -212,7 +197,7 @@ __global__ void __launch_bounds__(TS_THREADS) track_stats_kernel(TrackArgs a) {
             }
         }
         // the track's row and its acceleration items
-        steps = ts_wave_sum(steps), path = ts_wave_sum(path), acc_sum = ts_wave_sum(acc_sum);
+        steps = wave_sum(steps), path = wave_sum(path), acc_sum = wave_sum(acc_sum);
         if (lane == 0) red[0][w] = steps, red[1][w] = path, red[2][w] = acc_sum;
         __syncthreads();                           // red and h_acc complete
         if (tid == 0) {

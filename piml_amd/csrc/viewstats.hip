@@ -33,7 +33,7 @@
 //
 // LDS per workgroup (static): tile 16 KiB + slots 4 KiB + focal slots 4 KiB + u32 rows (4 G G + G G + 1 + gap_bins + 1
 // <= 5378) 21.0 KiB + speed sums 2 KiB + counters: 47.0 KiB, three workgroups per CU.
-#include "common.hpp"
+#include "stats.hpp"
 #include "../../include/piml_hip.h"
 
 #include <cmath>
@@ -73,76 +73,19 @@ __device__ __forceinline__ bool vs_participant(float m, float2 p, float2 v) {
     return m == 1.f && isfinite(p.x) && isfinite(p.y) && fabsf(v.x) < VS_MAX_V && fabsf(v.y) < VS_MAX_V;
 }
 
-__device__ __forceinline__ unsigned long long vs_wave_sum(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-// Compacts the participants of slots [lo, hi) (hi - lo <= VS_TILE) into ph / slot in slot order; returns their number.
-// Every thread of the workgroup calls it; the tile may still be read by other waves on entry (no write before the first
-// barrier).
+// Compacts the participants of slots [lo, hi) (hi - lo <= VS_TILE) into ph / slot in slot order; returns their number
+// (wg_compact: every thread calls it, and the tile may still be read on entry).
 __device__ int vs_stage(const ViewArgs& a, const float2* P, const float2* V, const float* M, int lo, int hi, float4* ph,
                         int* slot, int* wave_cnt) {
-    const int tid = threadIdx.x, w = tid >> 6;
-    int base = 0;
-    for (int s0 = lo; s0 < hi; s0 += VS_THREADS) {
-        const int j = s0 + tid;
-        float2 p = make_float2(0.f, 0.f), v = make_float2(0.f, 0.f);
-        bool part = false;
-        if (j < hi) {
-            p = P[j];
-            v = V[j];
-            part = vs_participant(M[j], p, v);
-        }
-        const u64 b = __ballot(part);
-        if ((tid & 63) == 0) wave_cnt[w] = __popcll(b);
-        __syncthreads();
-        int before = base, total = base;
-        for (int k = 0; k < VS_WAVES; ++k) {
-            before += k < w ? wave_cnt[k] : 0;
-            total += wave_cnt[k];
-        }
-        if (part) {
-            const int q = before + (int)mbcnt(b);
+    float2 p, v;
+    return wg_compact<VS_THREADS>(
+        lo, hi, wave_cnt, [&](int j) { return p = P[j], v = V[j], vs_participant(M[j], p, v); },
+        [&](int q, int j) {
             const float sp = sqrtf(v.x * v.x + v.y * v.y);
             const bool mover = sp >= a.v_min;
             ph[q] = make_float4(p.x, p.y, mover ? v.x / sp : NAN, mover ? v.y / sp : 0.f);
             slot[q] = j;
-        }
-        __syncthreads();                      // tile complete; wave_cnt is rewritten by the next round
-        base = total;
-    }
-    return base;
-}
-
-// Compacts the focal agents of slots [lo, hi) (hi - lo <= VS_TILE) into fslot in slot order; returns their number.  Every
-// thread of the workgroup calls it.
-__device__ int vs_stage_focal(const ViewArgs& a, const float2* P, const float2* V, const float* M, int lo, int hi, int* fslot,
-                              int* wave_cnt) {
-    const int tid = threadIdx.x, w = tid >> 6;
-    int base = 0;
-    for (int s0 = lo; s0 < hi; s0 += VS_THREADS) {
-        const int j = s0 + tid;
-        bool focal = false;
-        if (j < hi) {
-            const float2 p = P[j], v = V[j];
-            focal = vs_participant(M[j], p, v) && sqrtf(v.x * v.x + v.y * v.y) >= a.v_min &&
-                    (!a.has_box || (a.x0 <= p.x && p.x < a.x1 && a.y0 <= p.y && p.y < a.y1));
-        }
-        const u64 b = __ballot(focal);
-        if ((tid & 63) == 0) wave_cnt[w] = __popcll(b);
-        __syncthreads();
-        int before = base, total = base;
-        for (int k = 0; k < VS_WAVES; ++k) {
-            before += k < w ? wave_cnt[k] : 0;
-            total += wave_cnt[k];
-        }
-        if (focal) fslot[before + (int)mbcnt(b)] = j;
-        __syncthreads();                      // fslot complete; wave_cnt is rewritten by the next round
-        base = total;
-    }
-    return base;
+        });
 }
 
 struct VsLane {
@@ -277,7 +220,14 @@ __global__ void __launch_bounds__(VS_THREADS) view_stats_kernel(ViewArgs a) {
             unsigned n_focal = 0, n_pairs = 0;
             // focal agents: each tile of VS_TILE candidate slots compacted into fslot, then one per lane in chunks of 256
             for (int f_lo = 0; f_lo < bound; f_lo += VS_TILE) {
-                const int nf = vs_stage_focal(a, Pi, Vi, Mi, f_lo, min(f_lo + VS_TILE, bound), fslot, wave_cnt);
+                const int nf = wg_compact<VS_THREADS>(
+                    f_lo, min(f_lo + VS_TILE, bound), wave_cnt,
+                    [&](int j) {
+                        const float2 p = Pi[j], v = Vi[j];
+                        return vs_participant(Mi[j], p, v) && sqrtf(v.x * v.x + v.y * v.y) >= a.v_min &&
+                               in_box(a.has_box, a.x0, a.x1, a.y0, a.y1, p);
+                    },
+                    [&](int q, int j) { fslot[q] = j; });
                 for (int c0 = 0; c0 < nf; c0 += VS_THREADS) {
                     const bool focal = c0 + tid < nf;
                     const int i = focal ? fslot[c0 + tid] : -1;
@@ -314,8 +264,8 @@ __global__ void __launch_bounds__(VS_THREADS) view_stats_kernel(ViewArgs a) {
                 __syncthreads();              // fslot is rewritten by the next focal tile
             }
             // the slice's counters: lanes, then one 64-bit LDS add per wave
-            const unsigned long long f = vs_wave_sum((unsigned long long)n_focal);
-            const unsigned long long p = vs_wave_sum((unsigned long long)n_pairs);
+            const unsigned long long f = wave_sum((unsigned long long)n_focal);
+            const unsigned long long p = wave_sum((unsigned long long)n_pairs);
             if (lane == 0) {
                 atomicAdd(cnt, f);
                 atomicAdd(cnt + 1, p);
@@ -390,8 +340,7 @@ PIML_API int piml_view_stats(const float* P, const float* V, const float* M, con
     for (int k = K + 2; k < VS_MAX_LAGS + 2; ++k) a.off[k] = a.off[K + 1];
     a.per_member = a.off[K + 1];
     a.slices = (long long)S * a.per_member;
-    const long long run = a.slices / VS_TARGET_WG;
-    a.run = (int)(run < 1 ? 1 : run > VS_MAX_RUN ? VS_MAX_RUN : run);
+    const unsigned grid = stats_run_grid(a.slices, VS_TARGET_WG, VS_MAX_RUN, VS_MAX_GRID, &a.run);
     a.has_box = has_box ? 1 : 0;
     a.x0 = x0, a.x1 = x1, a.y0 = y0, a.y1 = y1;
     a.has_rmax = r_max > 0.f ? 1 : 0;
@@ -403,10 +352,8 @@ PIML_API int piml_view_stats(const float* P, const float* V, const float* M, con
     hipStream_t st = as_stream(stream);
     hipError_t e = hipMemsetAsync(workspace, 0, (size_t)need, st);
     if (e != hipSuccess) return e;
-    const long long runs = (a.slices + a.run - 1) / a.run;
-    if (runs > 0) {
-        hipLaunchKernelGGL(view_stats_kernel, dim3((unsigned)(runs < VS_MAX_GRID ? runs : VS_MAX_GRID)), dim3(VS_THREADS), 0,
-                           st, a);
+    if (grid > 0) {
+        hipLaunchKernelGGL(view_stats_kernel, dim3(grid), dim3(VS_THREADS), 0, st, a);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

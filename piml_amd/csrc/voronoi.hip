@@ -133,7 +133,7 @@ __device__ __forceinline__ void vd_finish(const VoronoiArgs& a, const VdPoly& g,
     const int nx = lane + 1 < g.n ? lane + 1 : 0;
     const float xn = __shfl(g.x, nx, 64), yn = __shfl(g.y, nx, 64);
     const double term = lane < g.n ? (double)g.x * (double)yn - (double)xn * (double)g.y : 0.0;
-    const float area = (float)(0.5 * cd_wave_sum(term));
+    const float area = (float)(0.5 * wave_sum(term));
     const bool ok = g.n > 0 && area > 0.f;
     if (lane == 0) {
         a.rho[at] = ok ? 1.f / area : NAN;
@@ -142,7 +142,7 @@ __device__ __forceinline__ void vd_finish(const VoronoiArgs& a, const VdPoly& g,
 }
 
 __device__ __forceinline__ bool vd_focal(const VoronoiArgs& a, float m, float2 p) {
-    return cd_present(m, p) && (!a.has_box || (a.x0 <= p.x && p.x < a.x1 && a.y0 <= p.y && p.y < a.y1)) &&
+    return cd_present(m, p) && in_box(a.has_box, a.x0, a.x1, a.y0, a.y1, p) &&
            (!a.has_bounds || (a.bx0 <= p.x && p.x < a.bx1 && a.by0 <= p.y && p.y < a.by1));
 }
 

@@ -32,8 +32,8 @@ import sys
 import numpy as np
 import torch
 
-from .crowdstats import (_f32, _json_float, _json_floats, _load, _nan_div, _promote, auto_box, grid_shape, member_indices,
-                         parse_box, parse_frames)
+from .crowdstats import (_bounds, _f32, _json_float, _json_floats, _load, _nan_div, _positive, _promote, _total,
+                         _window, auto_box, grid_shape, member_indices, parse_box, parse_frames)
 
 JSON_VERSION = 1
 Q = 1 << 20
@@ -42,11 +42,6 @@ MAPS = ('map_n', 'map_vx', 'map_vy')
 ARRAYS = ('corr_pairs', 'corr_sum') + SERIES + MAPS + ('slices',)
 MAX_SPEED = 1024.0
 OPTION_KEYS = ('v_min', 'r_bin', 'r_bins', 'r_max', 'axis', 'lane_width', 'lane_length')     # what a comparison needs equal
-
-
-def _positive(name, x):
-    if isinstance(x, bool) or not (math.isfinite(float(x)) and float(x) > 0 and _f32(x) > 0 and math.isfinite(_f32(x))):
-        raise ValueError(f'{name} must be a positive number, got {x}')
 
 
 def parse_axis(axis):
@@ -109,12 +104,7 @@ def check_options(v_min=0.1, r_bin=0.1, r_bins=60, r_max=None, axis='x', lane_wi
         if not (_f32(box[0]) < _f32(box[1]) and _f32(box[2]) < _f32(box[3])):
             raise ValueError(f'box {box} is empty (need x0 < x1 and y0 < y1)')
         grid = grid_shape(box, cell)
-    if frames is not None:
-        a, b = (int(v) for v in frames)
-        if a < 0 or b <= a or (T is not None and b > T):
-            raise ValueError(f'frames must satisfy 0 <= a < b <= {T}, got {tuple(frames)}')
-        frames = (a, b)
-    return r_max, axis, box, grid, frames
+    return r_max, axis, box, grid, _window(frames, T)
 
 
 def auto_axis(P, V, M, n_active=None, frames=None):
@@ -138,16 +128,6 @@ def auto_axis(P, V, M, n_active=None, frames=None):
     if ex == 0.0:
         ey = abs(ey)
     return (ex, ey)
-
-
-def _total(x):
-    """sum over the member axis, added in member order, keeping it"""
-    if x is None:
-        return None
-    acc = x[0].copy()
-    for m in range(1, x.shape[0]):
-        acc += x[m]
-    return acc[None]
 
 
 class FlowStats:
@@ -336,11 +316,7 @@ def flow_stats(P, V, M, v_min=0.1, r_bin=0.1, r_bins=60, r_max=None, axis='x', l
     if N > ops_metrics.FLOW_MAX_N:
         raise ValueError(f'flow_stats: {N} slots per frame (at most {ops_metrics.FLOW_MAX_N})')
     frames = frames or (0, T)
-    if n_active is not None:
-        n_active = torch.as_tensor(n_active).reshape(-1)
-        if n_active.numel() != S:
-            raise ValueError(f'n_active: {n_active.numel()} bounds for {S} members')
-        n_active = n_active.clamp(0, N).to(device=P.device, dtype=torch.int32)
+    n_active = _bounds(n_active, S, N, P.device)
     if axis == 'auto':
         axis = auto_axis(P, V, M, n_active, frames)
     out = ops_metrics.flow_stats_frames(P, V, M, v_min, r_bin, int(r_bins), r_max, axis, lane_width, lane_length, box, grid,

@@ -46,7 +46,8 @@ import sys
 import numpy as np
 import torch
 
-from .crowdstats import _f32, _json_float, _json_floats, _load, _nan_div, member_indices, parse_frames
+from .crowdstats import (_bounds, _f32, _json_float, _json_floats, _l1, _load, _nan_div, _total, _window,
+                         member_indices, parse_frames)
 
 JSON_VERSION = 1
 Q = 1 << 20
@@ -83,11 +84,7 @@ def check_options(dt=0.08, radius=2.0, dv_max=0.5, v_min=0.1, min_time=2.0, shar
                          f'finite and the first two positive in float32, min_time / dt at most {GROUP_MAX_FRAMES}')
     if max_edges is not None and (isinstance(max_edges, bool) or int(max_edges) != max_edges or not 1 <= int(max_edges) < 2 ** 31):
         raise ValueError(f'max_edges must be None or a positive integer, got {max_edges}')
-    if frames is not None:
-        a, b = (int(v) for v in frames)
-        if a < 0 or b <= a or (T is not None and b > T):
-            raise ValueError(f'frames must satisfy 0 <= a < b <= {T}, got {tuple(frames)}')
-        frames = (a, b)
+    frames = _window(frames, T)
     span = (frames[1] - frames[0]) if frames is not None else (T or 0)
     if span > GROUP_MAX_FRAMES:
         raise ValueError(f'group_stats: {span} frames in the window (at most {GROUP_MAX_FRAMES})')
@@ -97,14 +94,6 @@ def check_options(dt=0.08, radius=2.0, dv_max=0.5, v_min=0.1, min_time=2.0, shar
         if not math.sqrt(r2) * Q * 0.5 * N * N * span < 2.0 ** 63:
             raise ValueError(f'group_stats: {N} slots x {span} frames could overflow the 64-bit distance sum (radius {radius})')
     return frames
-
-
-def _total(x):
-    """sum over the member axis, added in member order, keeping it"""
-    acc = x[0].copy()
-    for m in range(1, x.shape[0]):
-        acc += x[m]
-    return acc[None]
 
 
 def host_rows(rows, min_frames, share_q, g_max=G_MAX):
@@ -341,11 +330,7 @@ def group_stats(P, M, dt=0.08, radius=2.0, dv_max=0.5, v_min=0.1, min_time=2.0, 
     P, M = _promote(P, M)
     S, T, N = P.shape[:3]
     frames = frames or (0, T)
-    if n_active is not None:
-        n_active = torch.as_tensor(n_active).reshape(-1)
-        if n_active.numel() != S:
-            raise ValueError(f'n_active: {n_active.numel()} bounds for {S} members')
-        n_active = n_active.clamp(0, N).to(device=P.device, dtype=torch.int32)
+    n_active = _bounds(n_active, S, N, P.device)
     out = ops_metrics.group_stats_frames(P, M, dt, radius, dv_max, v_min, min_time, share, r_bin, int(r_bins), int(a_bins),
                                          frames, n_active, max_edges, components, G_MAX)
     host = {k: v.cpu().numpy() for k, v in out.items()}
@@ -366,12 +351,12 @@ def group_stats_of_raw(raw_data, **kw):
     return group_stats(raw_data.position, raw_data.mask_p, **kw)
 
 
-def _l1(ha, hb, min_count):
-    """sum |share_a - share_b| over the bins (0 .. 2); NaN with fewer than min_count items on either side"""
+def _hist_l1(ha, hb, min_count):
+    """_l1 of the shares of two histograms; NaN with fewer than min_count items on either side"""
     na, nb = int(ha.sum()), int(hb.sum())
     if min(na, nb) < max(int(min_count), 1):
         return float('nan')
-    return float(np.abs(ha / na - hb / nb).sum())
+    return _l1(ha / na, hb / nb)
 
 
 def compare_group_stats(a, b, min_count=20):
@@ -392,8 +377,8 @@ def compare_group_stats(a, b, min_count=20):
     enough = min(ta.sum(), tb.sum()) >= floor
     both = min(ta[1], tb[1], ta[2:].sum(), tb[2:].sum()) >= floor
     return {'group_fraction_diff': abs(a.group_fraction() - b.group_fraction()) if enough else float('nan'),
-            'size_l1': _l1(ta, tb, min_count), 'member_distance_l1': _l1(pa.dist[0], pb.dist[0], min_count),
-            'abreast_l1': _l1(pa.abreast[0], pb.abreast[0], min_count),
+            'size_l1': _hist_l1(ta, tb, min_count), 'member_distance_l1': _hist_l1(pa.dist[0], pb.dist[0], min_count),
+            'abreast_l1': _hist_l1(pa.abreast[0], pb.abreast[0], min_count),
             'speed_ratio_diff': abs(a.speed_ratio() - b.speed_ratio()) if both else float('nan')}
 
 

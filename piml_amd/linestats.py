@@ -53,7 +53,8 @@ import sys
 import numpy as np
 import torch
 
-from .crowdstats import (_f32, _json_float, _json_floats, _load, _nan_div, auto_box, member_indices, parse_box, parse_frames)
+from .crowdstats import (_bounds, _count, _f32, _json_float, _json_floats, _load, _nan_div, _positive, _total, _window,
+                         auto_box, member_indices, parse_box, parse_frames)
 
 JSON_VERSION = 1
 Q = 1 << 20
@@ -66,17 +67,6 @@ ADDITIVE = DIR_ROWS + ('steps',) + HISTS + ('slices',)
 ARRAYS = ADDITIVE + TRACK_ROWS
 # what a comparison needs equal (the lines are part of what was measured)
 OPTION_KEYS = ('dt', 'v_bin', 'v_bins', 'w_bins', 'h_bin', 'h_bins', 'tt_bin', 'tt_bins', 'n_lines', 'lines_hash')
-
-
-def _positive(name, x):
-    if isinstance(x, bool) or not (math.isfinite(float(x)) and float(x) > 0 and _f32(x) > 0 and math.isfinite(_f32(x))):
-        raise ValueError(f'{name} must be a positive number, got {x}')
-
-
-def _bins(name, x):
-    from .ops_metrics import LINE_MAX_BINS
-    if isinstance(x, bool) or int(x) != x or not 1 <= int(x) <= LINE_MAX_BINS:
-        raise ValueError(f'{name} must be an integer in 1..{LINE_MAX_BINS}, got {x}')
 
 
 def check_lines(lines):
@@ -141,16 +131,12 @@ def parse_lines(text):
 def check_options(dt=0.08, v_bin=0.1, v_bins=40, w_bins=16, h_bin=0.25, h_bins=80, tt_bin=1.0, tt_bins=60, frames=None,
                   T=None, N=None):
     """ValueError on a bad option; returns frames (a, b) or None."""
-    from .ops_metrics import LINE_MAX_FRAMES, LINE_MAX_N
+    from .ops_metrics import LINE_MAX_BINS, LINE_MAX_FRAMES, LINE_MAX_N
     for name, x in (('dt', dt), ('v_bin', v_bin), ('h_bin', h_bin), ('tt_bin', tt_bin)):
         _positive(name, x)
     for name, x in (('v_bins', v_bins), ('w_bins', w_bins), ('h_bins', h_bins), ('tt_bins', tt_bins)):
-        _bins(name, x)
-    if frames is not None:
-        a, b = (int(v) for v in frames)
-        if a < 0 or b <= a or (T is not None and b > T):
-            raise ValueError(f'frames must satisfy 0 <= a < b <= {T}, got {tuple(frames)}')
-        frames = (a, b)
+        _count(name, x, LINE_MAX_BINS)
+    frames = _window(frames, T)
     span = (frames[1] - frames[0]) if frames is not None else (T or 0)
     if span > LINE_MAX_FRAMES:
         raise ValueError(f'line_stats: {span} frames in the window (at most {LINE_MAX_FRAMES})')
@@ -162,14 +148,6 @@ def check_options(dt=0.08, v_bin=0.1, v_bins=40, w_bins=16, h_bin=0.25, h_bins=8
             raise ValueError(f'line_stats: {N} slots x {span} frames could overflow the 64-bit speed sum '
                              f'(v_bin * v_bins {v_bin * v_bins})')
     return frames
-
-
-def _total(x):
-    """sum over the member axis, added in member order, keeping it"""
-    acc = x[0].copy()
-    for m in range(1, x.shape[0]):
-        acc += x[m]
-    return acc[None]
 
 
 def host_rows(rows, dt=0.08, h_bin=0.25, h_bins=80, tt_bin=1.0, tt_bins=60):
@@ -425,11 +403,7 @@ def line_stats(P, M, lines, dt=0.08, v_bin=0.1, v_bins=40, w_bins=16, h_bin=0.25
     P, M = _promote(P, M)
     S, T, N = P.shape[:3]
     frames = frames or (0, T)
-    if n_active is not None:
-        n_active = torch.as_tensor(n_active).reshape(-1)
-        if n_active.numel() != S:
-            raise ValueError(f'n_active: {n_active.numel()} bounds for {S} members')
-        n_active = n_active.clamp(0, N).to(device=P.device, dtype=torch.int32)
+    n_active = _bounds(n_active, S, N, P.device)
     out = ops_metrics.line_stats_frames(P, M, torch.from_numpy(rows).to(P.device), dt, v_bin, int(v_bins), int(w_bins),
                                         frames, n_active)
     host = {k: v.cpu().numpy() for k, v in out.items()}

@@ -48,8 +48,8 @@ import warnings
 import numpy as np
 import torch
 
-from .crowdstats import (_f32, _json_float, _json_floats, _load, _nan_div, _promote, auto_box, member_indices, parse_box,
-                         parse_frames)
+from .crowdstats import (_bounds, _count, _f32, _json_float, _json_floats, _l1, _load, _nan_div, _positive, _promote,
+                         _total, _window, auto_box, member_indices, parse_box, parse_frames)
 
 JSON_VERSION = 1
 Q = 1 << 20
@@ -64,36 +64,21 @@ ARRAYS = ADDITIVE + TRACK_ROWS
 OPTION_KEYS = ('dt', 'radius', 'hit_radius', 'r_bin', 'r_bins', 'tau_bin', 'tau_bins', 'box', 'n_obstacles', 'obstacles_hash')
 
 
-def _positive(name, x):
-    if isinstance(x, bool) or not (math.isfinite(float(x)) and float(x) > 0 and _f32(x) > 0 and math.isfinite(_f32(x))):
-        raise ValueError(f'{name} must be a positive number, got {x}')
-
-
-def _bins(name, x):
-    from .ops_metrics import OBS_MAX_BINS
-    if isinstance(x, bool) or int(x) != x or not 1 <= int(x) <= OBS_MAX_BINS:
-        raise ValueError(f'{name} must be an integer in 1..{OBS_MAX_BINS}, got {x}')
-
-
 def check_options(dt=0.08, radius=0.25, hit_radius=0.1, r_bin=0.05, r_bins=100, tau_bin=0.1, tau_bins=100, box=None,
                   frames=None, T=None, N=None, O=None):
     """ValueError on a bad option; returns (box as 4 floats or None, frames (a, b) or None)."""
-    from .ops_metrics import OBS_MAX_N, OBS_MAX_O
+    from .ops_metrics import OBS_MAX_BINS, OBS_MAX_N, OBS_MAX_O
     for name, x in (('dt', dt), ('radius', radius), ('hit_radius', hit_radius), ('r_bin', r_bin), ('tau_bin', tau_bin)):
         _positive(name, x)
-    _bins('r_bins', r_bins)
-    _bins('tau_bins', tau_bins)
+    _count('r_bins', r_bins, OBS_MAX_BINS)
+    _count('tau_bins', tau_bins, OBS_MAX_BINS)
     if box is not None:
         box = tuple(float(v) for v in box)
         if len(box) != 4 or not all(math.isfinite(v) for v in box):
             raise ValueError(f'box must be four finite numbers (x0, x1, y0, y1), got {box}')
         if not (_f32(box[0]) < _f32(box[1]) and _f32(box[2]) < _f32(box[3])):
             raise ValueError(f'box {box} is empty (need x0 < x1 and y0 < y1)')
-    if frames is not None:
-        a, b = (int(v) for v in frames)
-        if a < 0 or b <= a or (T is not None and b > T):
-            raise ValueError(f'frames must satisfy 0 <= a < b <= {T}, got {tuple(frames)}')
-        frames = (a, b)
+    frames = _window(frames, T)
     if O is not None and O > OBS_MAX_O:
         raise ValueError(f'obstacle_stats: {O} obstacle points (at most {OBS_MAX_O})')
     if N is not None:
@@ -105,14 +90,6 @@ def check_options(dt=0.08, radius=0.25, hit_radius=0.1, r_bin=0.05, r_bins=100, 
             raise ValueError(f'obstacle_stats: {N} slots x {span} frames could overflow the 64-bit sums (speeds below 1449, '
                              f'r_bin * r_bins {r_bin * r_bins})')
     return box, frames
-
-
-def _total(x):
-    """sum over the member axis, added in member order, keeping it"""
-    acc = x[0].copy()
-    for m in range(1, x.shape[0]):
-        acc += x[m]
-    return acc[None]
 
 
 def _obstacle_array(obstacles):
@@ -366,11 +343,7 @@ def obstacle_stats(P, V, M, obstacles, dt=0.08, radius=0.25, hit_radius=0.1, r_b
     frames = frames or (0, T)
     digest = obstacles_hash(obs)
     _warn_sparse(obs, digest, hit_radius)
-    if n_active is not None:
-        n_active = torch.as_tensor(n_active).reshape(-1)
-        if n_active.numel() != S:
-            raise ValueError(f'n_active: {n_active.numel()} bounds for {S} members')
-        n_active = n_active.clamp(0, N).to(device=P.device, dtype=torch.int32)
+    n_active = _bounds(n_active, S, N, P.device)
     out = ops_metrics.obstacle_stats_frames(P, V, M, torch.from_numpy(obs).to(P.device), dt, radius, hit_radius, r_bin,
                                             int(r_bins), tau_bin, int(tau_bins), box, frames, n_active)
     host = {k: v.cpu().numpy() for k, v in out.items()}
@@ -387,11 +360,6 @@ def obstacle_stats_of_raw(raw_data, obstacles=None, **kw):
     kw.setdefault('dt', float(raw_data.time_unit))
     return obstacle_stats(raw_data.position, raw_data.velocity, raw_data.mask_p,
                           raw_data.obstacles if obstacles is None else obstacles, **kw)
-
-
-def _l1(x, y):
-    """sum |x - y| of two share vectors (0 .. 2); NaN when either has no items"""
-    return float(np.abs(x - y).sum()) if np.isfinite(x).all() and np.isfinite(y).all() else float('nan')
 
 
 def _shares(h):

@@ -76,24 +76,46 @@ def mmd_frames(x, y, mask_x=None, mask_y=None, kernel_mul=2.0, kernel_num=5, fix
     return out.reshape(lead)
 
 
-CROWD_MAX_BINS = 256          # piml_crowd_stats' limit on rho_bins
-
-
-def _crowd_setup(P, V, M, box, grid, rho_bins, frames, return_density, n_active):
-    """What the two crowd-statistics calls share: checked inputs, the frame range, the box as numbers and the outputs."""
-    P, V, M = _gpu_f32('P', P), _gpu_f32('V', V), _gpu_f32('M', M)
-    if P.dim() != 4 or P.shape[-1] != 2 or V.shape != P.shape or M.shape != P.shape[:3]:
+def _stats_setup(named, frames, n_active):
+    """What every statistics wrapper checks first.  named: its float32 inputs by name -- P (S, T, N, 2), V like P when the
+    call has one, M (S, T, N), then any further ones, whose shapes are the caller's to check -- in the order the messages
+    list them.  Returns the contiguous tensors in that order, (S, T, N, a, b) with the window (a, b) of `frames`, the device
+    and n_active, contiguous; ValueError unless every tensor, n_active included, is on P's device."""
+    t = {k: _gpu_f32(k, x) for k, x in named.items()}
+    P, V, M = t['P'], t.get('V'), t['M']
+    if P.dim() != 4 or P.shape[-1] != 2 or (V is not None and V.shape != P.shape) or M.shape != P.shape[:3]:
+        if V is None:
+            raise ValueError(f'expected P (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(M.shape)}')
         raise ValueError(f'expected P, V (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(V.shape)}, '
                          f'{tuple(M.shape)}')
+    dev = P.device
+    if any(x.device != dev for x in t.values()):
+        names = list(t)
+        raise ValueError(f'{", ".join(names[:-1])} and {names[-1]} on different devices')
     S, T, N = P.shape[:3]
     a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
-    Tp, B = b - a, int(rho_bins)
-    dev = P.device
     if n_active is not None:
         if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
                 or tuple(n_active.shape) != (S,):
             raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
         n_active = n_active.contiguous()
+    return tuple(t.values()), (S, T, N, a, b), dev, n_active
+
+
+def _stats_new(idle, dev, ws_bytes=None):
+    """The allocator of a call's outputs and its workspace (None without ws_bytes).  A call with nothing to do leaves its
+    outputs alone, so it is handed zeros."""
+    ws = None if ws_bytes is None else torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    return (torch.zeros if idle else torch.empty), ws
+
+
+CROWD_MAX_BINS = 256          # piml_crowd_stats' limit on rho_bins
+
+
+def _crowd_setup(P, V, M, box, grid, rho_bins, frames, return_density, n_active):
+    """What the two crowd-statistics calls share: checked inputs, the frame range, the box as numbers and the outputs."""
+    (P, V, M), (S, T, N, a, b), dev, n_active = _stats_setup(dict(P=P, V=V, M=M), frames, n_active)
+    Tp, B = b - a, int(rho_bins)
     gx, gy = (1, 1) if box is None else (int(grid[0]), int(grid[1]))
     rect = (0.0, 0.0, 0.0, 0.0) if box is None else tuple(float(v) for v in box)
     i64, f64 = dict(device=dev, dtype=torch.int64), dict(device=dev, dtype=torch.float64)
@@ -121,8 +143,7 @@ def crowd_stats_frames(P, V, M, radius=0.7, box=None, grid=None, cell=0.5, rho_b
     P, V, M, n_active, dims, (Tp, B), rect, (gx, gy), out = _crowd_setup(P, V, M, box, grid, rho_bins, frames,
                                                                          return_density, n_active)
     L = _lib.lib()
-    ws_bytes = L.piml_crowd_stats_workspace_bytes(dims[0], max(Tp, 0), max(B, 0))
-    ws = torch.empty(max(ws_bytes, 8), device=P.device, dtype=torch.uint8)
+    _, ws = _stats_new(False, P.device, L.piml_crowd_stats_workspace_bytes(dims[0], max(Tp, 0), max(B, 0)))
     with torch.cuda.device(P.device):
         _lib.check(L.piml_crowd_stats(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), *dims, float(radius),
                                       int(box is not None), *rect, float(cell), gx, gy, float(rho_bin), B,
@@ -147,8 +168,7 @@ def crowd_stats_voronoi_frames(P, V, M, cutoff=1.0, dirs=None, bounds=None, box=
     out['dropped'] = torch.empty(S, device=P.device, dtype=torch.int64)
     brect = (0.0, 0.0, 0.0, 0.0) if bounds is None else tuple(float(v) for v in bounds)
     L = _lib.lib()
-    ws_bytes = L.piml_crowd_stats_voronoi_workspace_bytes(S, max(Tp, 0), N, max(B, 0))
-    ws = torch.empty(max(ws_bytes, 8), device=P.device, dtype=torch.uint8)
+    _, ws = _stats_new(False, P.device, L.piml_crowd_stats_voronoi_workspace_bytes(S, max(Tp, 0), N, max(B, 0)))
     with torch.cuda.device(P.device):
         _lib.check(L.piml_crowd_stats_voronoi(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), *dims, float(cutoff),
                                               dirs.ctypes.data_as(ctypes.c_void_p), int(dirs.shape[0]),
@@ -172,20 +192,9 @@ def pair_stats_frames(P, V, M, radius=0.5, lags=(64, 128, 192), tau_bin=0.1, tau
     pairs, overlap (S, K+1), ttc (S, K+1, tau_bins), dist (S, K+1, r_bins), nn (S, r_bins+1), min_ttc (S, tau_bins+1) --
     with no host synchronisation (capturable in a graph)."""
     import ctypes
-    P, V, M = _gpu_f32('P', P), _gpu_f32('V', V), _gpu_f32('M', M)
-    if P.dim() != 4 or P.shape[-1] != 2 or V.shape != P.shape or M.shape != P.shape[:3]:
-        raise ValueError(f'expected P, V (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(V.shape)}, '
-                         f'{tuple(M.shape)}')
-    S, T, N = P.shape[:3]
-    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    (P, V, M), (S, T, N, a, b), dev, n_active = _stats_setup(dict(P=P, V=V, M=M), frames, n_active)
     lags = [int(x) for x in lags]
     K, TB, RB = len(lags), int(tau_bins), int(r_bins)
-    dev = P.device
-    if n_active is not None:
-        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
-                or tuple(n_active.shape) != (S,):
-            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
-        n_active = n_active.contiguous()
     x0, x1, y0, y1 = (0.0, 0.0, 0.0, 0.0) if box is None else (float(v) for v in box)
     i64 = dict(device=dev, dtype=torch.int64)
     K1, TBc, RBc = K + 1, max(TB, 0), max(RB, 0)
@@ -193,8 +202,7 @@ def pair_stats_frames(P, V, M, radius=0.5, lags=(64, 128, 192), tau_bin=0.1, tau
                ttc=torch.empty(S, K1, TBc, **i64), dist=torch.empty(S, K1, RBc, **i64), nn=torch.empty(S, RBc + 1, **i64),
                min_ttc=torch.empty(S, TBc + 1, **i64))
     L = _lib.lib()
-    ws_bytes = L.piml_pair_stats_workspace_bytes(S, K, TBc, RBc)
-    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    _, ws = _stats_new(False, dev, L.piml_pair_stats_workspace_bytes(S, K, TBc, RBc))
     lag_arr = (ctypes.c_int * max(K, 1))(*lags)
     with torch.cuda.device(dev):
         _lib.check(L.piml_pair_stats(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), S, T, N, a, b,
@@ -220,30 +228,16 @@ def flow_stats_frames(P, V, M, v_min=0.1, r_bin=0.1, r_bins=60, r_max=6.0, axis=
     n_active (S) int32 GPU tensor or None.  Returns a dict of int64 GPU tensors -- corr_pairs, corr_sum (S, r_bins);
     lane_n, lane_sum, lane_same, lane_opp, dir_plus, dir_minus (S, T'); map_n, map_vx, map_vy (S, gy, gx) or None -- with
     no host synchronisation (capturable in a graph)."""
-    P, V, M = _gpu_f32('P', P), _gpu_f32('V', V), _gpu_f32('M', M)
-    if P.dim() != 4 or P.shape[-1] != 2 or V.shape != P.shape or M.shape != P.shape[:3]:
-        raise ValueError(f'expected P, V (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(V.shape)}, '
-                         f'{tuple(M.shape)}')
-    S, T, N = P.shape[:3]
-    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    (P, V, M), (S, T, N, a, b), dev, n_active = _stats_setup(dict(P=P, V=V, M=M), frames, n_active)
     RB, Tp = int(r_bins), max(b - a, 0)
-    dev = P.device
-    if n_active is not None:
-        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
-                or tuple(n_active.shape) != (S,):
-            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
-        n_active = n_active.contiguous()
     gx, gy = (0, 0) if box is None else (int(grid[0]), int(grid[1]))
     rect = (0.0, 0.0, 0.0, 0.0) if box is None else tuple(float(v) for v in box)
-    # a call with nothing to do leaves its outputs alone: hand it zeros
-    new = torch.zeros if S * Tp * N == 0 else torch.empty
+    L = _lib.lib()
+    new, ws = _stats_new(S * Tp * N == 0, dev, L.piml_flow_stats_workspace_bytes(S, max(RB, 0), max(gx, 0), max(gy, 0)))
     i64 = dict(device=dev, dtype=torch.int64)
     out = {k: new(S, max(RB, 0), **i64) for k in ('corr_pairs', 'corr_sum')}
     out.update({k: new(S, Tp, **i64) for k in FLOW_SERIES})
     out.update({k: new(S, gy, gx, **i64) if box is not None else None for k in ('map_n', 'map_vx', 'map_vy')})
-    L = _lib.lib()
-    ws_bytes = L.piml_flow_stats_workspace_bytes(S, max(RB, 0), max(gx, 0), max(gy, 0))
-    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
     with torch.cuda.device(dev):
         _lib.check(L.piml_flow_stats(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), S, T, N, a, b, float(v_min), float(r_bin),
                                      RB, float(r_max), float(axis[0]), float(axis[1]), float(lane_width),
@@ -270,20 +264,9 @@ def view_stats_frames(P, V, M, lags=(64, 128, 192), v_min=0.1, cell=0.25, half=1
     (S, K+1), map (S, K+1, 4, G, G) with G = 2 half, nn_map (S, G G + 1), front_gap (S, gap_bins+1), front_speed (S,
     gap_bins) -- with no host synchronisation (capturable in a graph)."""
     import ctypes
-    P, V, M = _gpu_f32('P', P), _gpu_f32('V', V), _gpu_f32('M', M)
-    if P.dim() != 4 or P.shape[-1] != 2 or V.shape != P.shape or M.shape != P.shape[:3]:
-        raise ValueError(f'expected P, V (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(V.shape)}, '
-                         f'{tuple(M.shape)}')
-    S, T, N = P.shape[:3]
-    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    (P, V, M), (S, T, N, a, b), dev, n_active = _stats_setup(dict(P=P, V=V, M=M), frames, n_active)
     lags = [int(x) for x in lags]
     K, H, GB = len(lags), int(half), int(gap_bins)
-    dev = P.device
-    if n_active is not None:
-        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
-                or tuple(n_active.shape) != (S,):
-            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
-        n_active = n_active.contiguous()
     x0, x1, y0, y1 = (0.0, 0.0, 0.0, 0.0) if box is None else (float(v) for v in box)
     i64 = dict(device=dev, dtype=torch.int64)
     K1, G, GBc = K + 1, 2 * max(H, 0), max(GB, 0)
@@ -291,8 +274,7 @@ def view_stats_frames(P, V, M, lags=(64, 128, 192), v_min=0.1, cell=0.25, half=1
                nn_map=torch.empty(S, G * G + 1, **i64), front_gap=torch.empty(S, GBc + 1, **i64),
                front_speed=torch.empty(S, GBc, **i64))
     L = _lib.lib()
-    ws_bytes = L.piml_view_stats_workspace_bytes(S, K, max(H, 0), GBc)
-    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    _, ws = _stats_new(False, dev, L.piml_view_stats_workspace_bytes(S, K, max(H, 0), GBc))
     lag_arr = (ctypes.c_int * max(K, 1))(*lags)
     with torch.cuda.device(dev):
         _lib.check(L.piml_view_stats(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), S, T, N, a, b,
@@ -323,23 +305,11 @@ def track_stats_frames(P, M, dt=0.08, v_min=0.1, n_lags=128, d_max=64.0, acc_bin
     float32 GPU tensors, frames (a, b) or None, n_active (S) int32 GPU tensor or None.  Returns a dict of int64 GPU tensors --
     ac_n, ac_sum, msd_n, msd_sum, msd_far (S, n_lags); acc (S, acc_bins + 1); acc_sum (S); trk_frames, trk_steps, trk_first,
     trk_last, trk_path, trk_net (S, N) -- with no host synchronisation (capturable in a graph)."""
-    P, M = _gpu_f32('P', P), _gpu_f32('M', M)
-    if P.dim() != 4 or P.shape[-1] != 2 or M.shape != P.shape[:3]:
-        raise ValueError(f'expected P (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(M.shape)}')
-    if M.device != P.device:
-        raise ValueError('P and M on different devices')
-    S, T, N = P.shape[:3]
-    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    (P, M), (S, T, N, a, b), dev, n_active = _stats_setup(dict(P=P, M=M), frames, n_active)
     NL, AB, Tp = int(n_lags), int(acc_bins), max(b - a, 0)
-    dev = P.device
-    if n_active is not None:
-        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
-                or tuple(n_active.shape) != (S,):
-            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
-        n_active = n_active.contiguous()
-    # a call with nothing to do leaves its outputs alone: hand it the values of empty tracks
-    idle = S * Tp * N == 0
-    new = torch.zeros if idle else torch.empty
+    L = _lib.lib()
+    idle = S * Tp * N == 0                    # then the outputs get the values of empty tracks
+    new, ws = _stats_new(idle, dev, L.piml_track_stats_workspace_bytes(S, max(NL, 0), max(AB, 0)))
     i64 = dict(device=dev, dtype=torch.int64)
     out = {k: new(S, max(NL, 0), **i64) for k in TRACK_LAG_ROWS}
     out['acc'] = new(S, max(AB, 0) + 1, **i64)
@@ -348,9 +318,6 @@ def track_stats_frames(P, M, dt=0.08, v_min=0.1, n_lags=128, d_max=64.0, acc_bin
     if idle:
         out['trk_first'] -= 1
         out['trk_last'] -= 1
-    L = _lib.lib()
-    ws_bytes = L.piml_track_stats_workspace_bytes(S, max(NL, 0), max(AB, 0))
-    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
     with torch.cuda.device(dev):
         _lib.check(L.piml_track_stats(_ptr(P), _ptr(M), _ptr(n_active), S, T, N, a, b, float(dt), float(v_min), NL,
                                       float(d_max), float(acc_bin), AB,
@@ -377,28 +344,16 @@ def obstacle_stats_frames(P, V, M, obstacles, dt=0.08, radius=0.25, hit_radius=0
     int32 GPU tensor or None.  Returns a dict of int64 GPU tensors -- focal, steps, contact, hit, clear_sum (S); clear,
     clear_speed, swept (S, r_bins + 1); min_ttc (S, tau_bins + 1); trk_frames, trk_contacts, trk_hits, trk_min (S, N) -- with
     no host synchronisation (capturable in a graph)."""
-    P, V, M, obstacles = _gpu_f32('P', P), _gpu_f32('V', V), _gpu_f32('M', M), _gpu_f32('obstacles', obstacles)
-    if P.dim() != 4 or P.shape[-1] != 2 or V.shape != P.shape or M.shape != P.shape[:3]:
-        raise ValueError(f'expected P, V (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(V.shape)}, '
-                         f'{tuple(M.shape)}')
+    (P, V, M, obstacles), (S, T, N, a, b), dev, n_active = _stats_setup(dict(P=P, V=V, M=M, obstacles=obstacles), frames,
+                                                                        n_active)
     if obstacles.dim() != 2 or obstacles.shape[-1] != 2:
         raise ValueError(f'obstacles: expected (O, 2), got {tuple(obstacles.shape)}')
-    dev = P.device
-    if any(x.device != dev for x in (V, M, obstacles)):
-        raise ValueError('P, V, M and obstacles on different devices')
-    S, T, N = P.shape[:3]
     O = obstacles.shape[0]
-    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
     RB, TB, Tp = int(r_bins), int(tau_bins), max(b - a, 0)
-    if n_active is not None:
-        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
-                or tuple(n_active.shape) != (S,):
-            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
-        n_active = n_active.contiguous()
     x0, x1, y0, y1 = (0.0, 0.0, 0.0, 0.0) if box is None else (float(v) for v in box)
-    # a call with nothing to do leaves its outputs alone: hand it the values of an empty problem
-    idle = S * Tp * N * O == 0
-    new = torch.zeros if idle else torch.empty
+    L = _lib.lib()
+    idle = S * Tp * N * O == 0                # then the outputs get the values of an empty problem
+    new, ws = _stats_new(idle, dev, L.piml_obstacle_stats_workspace_bytes(S, N, max(RB, 0), max(TB, 0)))
     i64 = dict(device=dev, dtype=torch.int64)
     out = {k: new(S, **i64) for k in OBS_COUNTS}
     out.update({k: new(S, max(RB, 0) + 1, **i64) for k in OBS_R_ROWS})
@@ -406,9 +361,6 @@ def obstacle_stats_frames(P, V, M, obstacles, dt=0.08, radius=0.25, hit_radius=0
     out.update({k: new(S, N, **i64) for k in OBS_TRACK_ROWS})
     if idle:
         out['trk_min'] -= 1
-    L = _lib.lib()
-    ws_bytes = L.piml_obstacle_stats_workspace_bytes(S, N, max(RB, 0), max(TB, 0))
-    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
     with torch.cuda.device(dev):
         _lib.check(L.piml_obstacle_stats(_ptr(P), _ptr(V), _ptr(M), _ptr(n_active), S, T, N, a, b, _ptr(obstacles), O,
                                          float(dt), float(radius), float(hit_radius), int(box is not None), x0, x1, y0, y1,
@@ -437,26 +389,14 @@ def line_stats_frames(P, M, lines, dt=0.08, v_bin=0.1, v_bins=40, w_bins=16, fra
     crossing), frames (a, b) or None, n_active (S) int32 GPU tensor or None.  Returns a dict of int64 GPU tensors -- cross,
     speed_sum (S, L, 2); nt (S, L, 2, T'); speed (S, L, 2, v_bins + 1); profile (S, L, 2, w_bins); steps (S); trk_steps (S, N);
     trk_count, trk_first, trk_dir (S, L, N) -- with no host synchronisation (capturable in a graph)."""
-    P, M, lines = _gpu_f32('P', P), _gpu_f32('M', M), _gpu_f32('lines', lines)
-    if P.dim() != 4 or P.shape[-1] != 2 or M.shape != P.shape[:3]:
-        raise ValueError(f'expected P (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(M.shape)}')
+    (P, M, lines), (S, T, N, a, b), dev, n_active = _stats_setup(dict(P=P, M=M, lines=lines), frames, n_active)
     if lines.dim() != 2 or lines.shape[-1] != 4:
         raise ValueError(f'lines: expected (L, 4), got {tuple(lines.shape)}')
-    dev = P.device
-    if M.device != dev or lines.device != dev:
-        raise ValueError('P, M and lines on different devices')
-    S, T, N = P.shape[:3]
     NL = lines.shape[0]
-    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
     VB, WB, Tp = int(v_bins), int(w_bins), max(b - a, 0)
-    if n_active is not None:
-        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
-                or tuple(n_active.shape) != (S,):
-            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
-        n_active = n_active.contiguous()
-    # a call with nothing to do leaves its outputs alone: hand it the values of an empty problem
-    idle = S * Tp * N * NL == 0
-    new = torch.zeros if idle else torch.empty
+    L = _lib.lib()
+    idle = S * Tp * N * NL == 0               # then the outputs get the values of an empty problem
+    new, ws = _stats_new(idle, dev, L.piml_line_stats_workspace_bytes(S, N, NL, Tp, max(VB, 0), max(WB, 0)))
     i64 = dict(device=dev, dtype=torch.int64)
     out = {k: new(S, NL, 2, **i64) for k in LINE_DIR_ROWS}
     out['nt'] = new(S, NL, 2, Tp, **i64)
@@ -468,9 +408,6 @@ def line_stats_frames(P, M, lines, dt=0.08, v_bin=0.1, v_bins=40, w_bins=16, fra
     if idle:
         out['trk_first'] -= 1
         out['trk_dir'] -= 1
-    L = _lib.lib()
-    ws_bytes = L.piml_line_stats_workspace_bytes(S, N, NL, Tp, max(VB, 0), max(WB, 0))
-    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
     with torch.cuda.device(dev):
         _lib.check(L.piml_line_stats(_ptr(P), _ptr(M), _ptr(n_active), S, T, N, a, b, _ptr(lines), NL, float(dt),
                                      float(v_bin), VB, WB, *(_ptr(out[k]) for k in LINE_ROWS), _ptr(ws), ws.numel(),
@@ -498,35 +435,15 @@ def group_thresholds(dt, radius, dv_max, v_min, min_time, share):
     return r2, dv2, vm2, max(1, math.ceil(float(min_time) / dt)), int(round(float(share) * GROUP_SHARE_UNIT))
 
 
-def _group_setup(P, M, frames, n_active):
-    P, M = _gpu_f32('P', P), _gpu_f32('M', M)
-    if P.dim() != 4 or P.shape[-1] != 2 or M.shape != P.shape[:3]:
-        raise ValueError(f'expected P (S, T, N, 2) and M (S, T, N), got {tuple(P.shape)}, {tuple(M.shape)}')
-    dev = P.device
-    if M.device != dev:
-        raise ValueError('P and M on different devices')
-    S, T, N = P.shape[:3]
-    a, b = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
-    if n_active is not None:
-        if not isinstance(n_active, torch.Tensor) or n_active.device != dev or n_active.dtype != torch.int32 \
-                or tuple(n_active.shape) != (S,):
-            raise ValueError(f'n_active: expected an int32 ({S},) tensor on {dev}')
-        n_active = n_active.contiguous()
-    return P, M, n_active, a, b
-
-
 def group_pairs_frames(P, M, r2, dv2, vm2, min_frames, frames=None, n_active=None, max_edges=None):
     """Pass 1 of the group statistics alone (piml_group_pairs): P (S, T, N, 2), M (S, T, N) float32 GPU tensors,
     the thresholds of group_thresholds, frames (a, b) or None, n_active (S) int32 GPU tensor or None; max_edges None:
     min(N (N - 1) / 2, 2^20).  Returns a dict of GPU tensors -- edges (S, max_edges, 4) int32, rows (i, j, co, near) of the
     candidates in any order (rows at or past n_edges[s] hold nothing), n_edges (S) int32 the true count, trk_steps, trk_path
     (S, N) and pairs, together (S) int64 -- with no host synchronisation (capturable in a graph)."""
-    P, M, n_active, a, b = _group_setup(P, M, frames, n_active)
-    S, T, N = P.shape[:3]
-    dev = P.device
+    (P, M), (S, T, N, a, b), dev, n_active = _stats_setup(dict(P=P, M=M), frames, n_active)
     cap = min(N * (N - 1) // 2, GROUP_MAX_EDGES) if max_edges is None else int(max_edges)
-    idle = S * max(b - a, 0) * N == 0
-    new = torch.zeros if idle else torch.empty
+    new, _ = _stats_new(S * max(b - a, 0) * N == 0, dev)
     out = {'edges': new(S, max(cap, 0), 4, device=dev, dtype=torch.int32), 'n_edges': new(S, device=dev, dtype=torch.int32),
            'trk_steps': new(S, N, device=dev, dtype=torch.int64), 'trk_path': new(S, N, device=dev, dtype=torch.int64),
            'pairs': new(S, device=dev, dtype=torch.int64), 'together': new(S, device=dev, dtype=torch.int64)}
@@ -541,9 +458,7 @@ def group_pairs_frames(P, M, r2, dv2, vm2, min_frames, frames=None, n_active=Non
 def group_members_frames(P, M, links, r2, dv2, vm2, r_bin=0.1, r_bins=20, a_bins=10, frames=None):
     """Pass 2 of the group statistics alone (piml_group_members): links (K, 3) int32 GPU tensor, rows (member, i, j).  Returns
     a dict of int64 GPU tensors -- dist (S, r_bins + 1), abreast (S, a_bins), dist_sum, abreast_skipped, link_frames (S)."""
-    P, M, _, a, b = _group_setup(P, M, frames, None)
-    S, T, N = P.shape[:3]
-    dev = P.device
+    (P, M), (S, T, N, a, b), dev, _ = _stats_setup(dict(P=P, M=M), frames, None)
     if not isinstance(links, torch.Tensor) or links.device != dev or links.dtype != torch.int32 or links.dim() != 2 \
             or links.shape[1] != 3:
         raise ValueError(f'links: expected an int32 (K, 3) tensor on {dev}')

@@ -35,33 +35,22 @@ import sys
 import numpy as np
 import torch
 
-from .crowdstats import (_f32, _json_float, _json_floats, _load, _nan_div, _promote, auto_box, member_indices, parse_box,
-                         parse_frames)
+from .crowdstats import (_bounds, _count, _f32, _json_float, _json_floats, _load, _nan_div, _positive, _promote, _total,
+                         _window, auto_box, member_indices, parse_box, parse_frames)
 
 JSON_VERSION = 1
 ARRAYS = ('focal', 'pairs', 'overlap', 'ttc', 'dist', 'nn', 'min_ttc')
 
 
-def _positive(name, x):
-    if isinstance(x, bool) or not (math.isfinite(float(x)) and float(x) > 0 and _f32(x) > 0):
-        raise ValueError(f'{name} must be a positive number, got {x}')
-
-
-def _bins(name, x):
-    from .ops_metrics import PAIR_MAX_BINS
-    if isinstance(x, bool) or int(x) != x or not 1 <= int(x) <= PAIR_MAX_BINS:
-        raise ValueError(f'{name} must be an integer in 1..{PAIR_MAX_BINS}, got {x}')
-
-
 def check_options(radius=0.5, lags=(64, 128, 192), tau_bin=0.1, tau_bins=100, r_bin=0.05, r_bins=100, r_max=None,
                   box=None, frames=None, T=None):
     """ValueError on a bad option; returns (lags as a tuple of ints, box as 4 floats or None, frames (a, b) or None)."""
-    from .ops_metrics import PAIR_MAX_LAGS
+    from .ops_metrics import PAIR_MAX_BINS, PAIR_MAX_LAGS
     _positive('radius', radius)
     _positive('tau_bin', tau_bin)
     _positive('r_bin', r_bin)
-    _bins('tau_bins', tau_bins)
-    _bins('r_bins', r_bins)
+    _count('tau_bins', tau_bins, PAIR_MAX_BINS)
+    _count('r_bins', r_bins, PAIR_MAX_BINS)
     if r_max is not None:
         _positive('r_max', r_max)
     lags = tuple(lags)
@@ -75,20 +64,7 @@ def check_options(radius=0.5, lags=(64, 128, 192), tau_bin=0.1, tau_bins=100, r_
             raise ValueError(f'box must be four finite numbers (x0, x1, y0, y1), got {box}')
         if not (_f32(box[0]) < _f32(box[1]) and _f32(box[2]) < _f32(box[3])):
             raise ValueError(f'box {box} is empty (need x0 < x1 and y0 < y1)')
-    if frames is not None:
-        a, b = (int(v) for v in frames)
-        if a < 0 or b <= a or (T is not None and b > T):
-            raise ValueError(f'frames must satisfy 0 <= a < b <= {T}, got {tuple(frames)}')
-        frames = (a, b)
-    return lags, box, frames
-
-
-def _total(x):
-    """sum over the member axis, added in member order, keeping it"""
-    acc = x[0].copy()
-    for m in range(1, x.shape[0]):
-        acc += x[m]
-    return acc[None]
+    return lags, box, _window(frames, T)
 
 
 class PairStats:
@@ -287,11 +263,7 @@ def pair_stats(P, V, M, radius=0.5, lags=(64, 128, 192), tau_bin=0.1, tau_bins=1
     if N > ops_metrics.PAIR_MAX_N:
         raise ValueError(f'pair_stats: {N} slots per frame (at most {ops_metrics.PAIR_MAX_N})')
     frames = frames or (0, T)
-    if n_active is not None:
-        n_active = torch.as_tensor(n_active).reshape(-1)
-        if n_active.numel() != S:
-            raise ValueError(f'n_active: {n_active.numel()} bounds for {S} members')
-        n_active = n_active.clamp(0, N).to(device=P.device, dtype=torch.int32)
+    n_active = _bounds(n_active, S, N, P.device)
     out = ops_metrics.pair_stats_frames(P, V, M, radius, lags, tau_bin, int(tau_bins), r_bin, int(r_bins), r_max, box,
                                         frames, n_active)
     host = {k: v.cpu().numpy() for k, v in out.items()}

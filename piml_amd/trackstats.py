@@ -38,7 +38,8 @@ import sys
 import numpy as np
 import torch
 
-from .crowdstats import _f32, _json_float, _json_floats, _load, _nan_div, member_indices, parse_frames
+from .crowdstats import (_bounds, _count, _f32, _json_float, _json_floats, _l1, _load, _nan_div, _positive, _total,
+                         _window, member_indices, parse_frames)
 
 JSON_VERSION = 1
 Q = 1 << 20
@@ -51,16 +52,6 @@ ARRAYS = ADDITIVE + TRACK_ROWS
 OPTION_KEYS = ('dt', 'v_min', 'n_lags', 'd_max', 'acc_bin', 'acc_bins', 'speed_bin', 'speed_bins', 'dur_bin', 'dur_bins',
                'straight_bins')
 TRACKS = {'all': 0, 'complete': 1}
-
-
-def _positive(name, x):
-    if isinstance(x, bool) or not (math.isfinite(float(x)) and float(x) > 0 and _f32(x) > 0 and math.isfinite(_f32(x))):
-        raise ValueError(f'{name} must be a positive number, got {x}')
-
-
-def _count(name, x, hi):
-    if isinstance(x, bool) or int(x) != x or not 1 <= int(x) <= hi:
-        raise ValueError(f'{name} must be an integer in 1..{hi}, got {x}')
 
 
 def check_options(dt=0.08, v_min=0.1, n_lags=128, d_max=64.0, acc_bin=0.25, acc_bins=40, speed_bin=0.1, speed_bins=40,
@@ -76,11 +67,7 @@ def check_options(dt=0.08, v_min=0.1, n_lags=128, d_max=64.0, acc_bin=0.25, acc_
     _count('acc_bins', acc_bins, TRACK_MAX_BINS)
     for name, x in (('speed_bins', speed_bins), ('dur_bins', dur_bins), ('straight_bins', straight_bins)):
         _count(name, x, 1 << 16)
-    if frames is not None:
-        a, b = (int(v) for v in frames)
-        if a < 0 or b <= a or (T is not None and b > T):
-            raise ValueError(f'frames must satisfy 0 <= a < b <= {T}, got {tuple(frames)}')
-        frames = (a, b)
+    frames = _window(frames, T)
     if T is not None and ((frames[1] - frames[0]) if frames is not None else T) > TRACK_MAX_FRAMES:
         raise ValueError(f'track_stats: a window of more than {TRACK_MAX_FRAMES} frames')
     if N is not None:
@@ -92,14 +79,6 @@ def check_options(dt=0.08, v_min=0.1, n_lags=128, d_max=64.0, acc_bin=0.25, acc_
             raise ValueError(f'track_stats: {N} slots x {span} frames could overflow the 64-bit sums at d_max {d_max}, '
                              f'acc_bin * acc_bins {acc_bin * acc_bins}')
     return frames
-
-
-def _total(x):
-    """sum over the member axis, added in member order, keeping it"""
-    acc = x[0].copy()
-    for m in range(1, x.shape[0]):
-        acc += x[m]
-    return acc[None]
 
 
 def track_histograms(rows, Tp, dt, speed_bin=0.1, speed_bins=40, dur_bin=1.0, dur_bins=60, straight_bins=20):
@@ -334,11 +313,7 @@ def track_stats(P, M, dt=0.08, v_min=0.1, n_lags=128, d_max=64.0, acc_bin=0.25, 
     frames = check_options(dt, v_min, n_lags, d_max, acc_bin, acc_bins, speed_bin, speed_bins, dur_bin, dur_bins,
                            straight_bins, frames, T, N) or (0, T)
     P, M = (x.to(device=dev, dtype=torch.float32).contiguous() for x in (P, M))
-    if n_active is not None:
-        n_active = torch.as_tensor(n_active).reshape(-1)
-        if n_active.numel() != S:
-            raise ValueError(f'n_active: {n_active.numel()} bounds for {S} members')
-        n_active = n_active.clamp(0, N).to(device=P.device, dtype=torch.int32)
+    n_active = _bounds(n_active, S, N, P.device)
     out = ops_metrics.track_stats_frames(P, M, dt, v_min, int(n_lags), d_max, acc_bin, int(acc_bins), frames, n_active)
     host = {k: v.cpu().numpy() for k, v in out.items()}
     host.update(track_histograms(host, frames[1] - frames[0], dt, speed_bin, int(speed_bins), dur_bin, int(dur_bins),
@@ -354,11 +329,6 @@ def track_stats_of_raw(raw_data, **kw):
     unless given."""
     kw.setdefault('dt', float(raw_data.time_unit))
     return track_stats(raw_data.position, raw_data.mask_p, **kw)
-
-
-def _l1(x, y):
-    """sum |x - y| of two share vectors (0 .. 2); NaN when either has no items"""
-    return float(np.abs(x - y).sum()) if np.isfinite(x).all() and np.isfinite(y).all() else float('nan')
 
 
 def compare_track_stats(a, b, min_count=50):

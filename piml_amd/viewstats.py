@@ -38,9 +38,9 @@ import sys
 import numpy as np
 import torch
 
-from .crowdstats import (_f32, _json_float, _json_floats, _load, _nan_div, _promote, auto_box, member_indices, parse_box,
-                         parse_frames)
-from .pairstats import _positive, _total, parse_lags
+from .crowdstats import (_bounds, _f32, _json_float, _json_floats, _load, _nan_div, _positive, _promote, _total,
+                         _window, auto_box, member_indices, parse_box, parse_frames)
+from .pairstats import parse_lags
 
 JSON_VERSION = 1
 ARRAYS = ('focal', 'pairs', 'map', 'nn_map', 'front_gap', 'front_speed')
@@ -77,12 +77,7 @@ def check_options(lags=(64, 128, 192), v_min=0.1, cell=0.25, half=12, cos_same=C
             raise ValueError(f'box must be four finite numbers (x0, x1, y0, y1), got {box}')
         if not (_f32(box[0]) < _f32(box[1]) and _f32(box[2]) < _f32(box[3])):
             raise ValueError(f'box {box} is empty (need x0 < x1 and y0 < y1)')
-    if frames is not None:
-        a, b = (int(v) for v in frames)
-        if a < 0 or b <= a or (T is not None and b > T):
-            raise ValueError(f'frames must satisfy 0 <= a < b <= {T}, got {tuple(frames)}')
-        frames = (a, b)
-    return lags, box, frames
+    return lags, box, _window(frames, T)
 
 
 class ViewStats:
@@ -305,11 +300,7 @@ def view_stats(P, V, M, lags=(64, 128, 192), box=None, frames=None, n_active=Non
     if N > ops_metrics.VIEW_MAX_N:
         raise ValueError(f'view_stats: {N} slots per frame (at most {ops_metrics.VIEW_MAX_N})')
     frames = frames or (0, T)
-    if n_active is not None:
-        n_active = torch.as_tensor(n_active).reshape(-1)
-        if n_active.numel() != S:
-            raise ValueError(f'n_active: {n_active.numel()} bounds for {S} members')
-        n_active = n_active.clamp(0, N).to(device=P.device, dtype=torch.int32)
+    n_active = _bounds(n_active, S, N, P.device)
     out = ops_metrics.view_stats_frames(P, V, M, lags, v_min, cell, int(half), cos_same, r_max, corridor, gap_bin,
                                         int(gap_bins), box, frames, n_active)
     host = {k: v.cpu().numpy() for k, v in out.items()}

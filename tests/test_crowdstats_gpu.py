@@ -62,7 +62,8 @@ def check_against_ref(st, P, V, M, n_active=None, **kw):
     return exact
 
 
-CASES = [(1, 8, 50), (63, 8, 50), (64, 4, 30), (65, 8, 50), (1000, 2, 6), (4097, 1, 3)]
+# (1024 and 1025: a frame that just fills the staged tile and one that needs a second)
+CASES = [(1, 8, 50), (63, 8, 50), (64, 4, 30), (65, 8, 50), (1000, 2, 6), (4097, 1, 3), (1024, 2, 3), (1025, 2, 3)]
 
 
 @pytest.mark.parametrize('N,S,T', CASES)

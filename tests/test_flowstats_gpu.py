@@ -55,7 +55,8 @@ def check_against_ref(st, P, V, M, label, **kw):
     return want
 
 
-CASES = [(1500, 1, 4), (300, 3, 10), (65, 2, 6), (1, 1, 3)]
+# (1024 and 1025: a frame that just fills the staged tile and one that needs a second)
+CASES = [(1500, 1, 4), (300, 3, 10), (65, 2, 6), (1, 1, 3), (1024, 2, 3), (1025, 2, 3)]
 
 
 @pytest.mark.parametrize('N,S,T', CASES)

@@ -103,3 +103,40 @@ def test_cpu_wasserstein_unequal_sizes_and_batched_input():
     assert np.allclose(dist.numpy(), g['batch/dist'], rtol=1e-6, atol=0)
     per_frame = np.array([float(M.wasserstein_distance_2d(x[b], y[b])[0]) for b in range(3)])
     assert not np.allclose(per_frame, g['batch/dist'], rtol=1e-6, atol=0)      # the coupling is visible in this batch
+
+
+def test_stats_wrappers_refuse_inputs_on_another_device():
+    """every *_stats_frames wrapper (and both group passes) raises ValueError, before any library call, when V, M, the
+    obstacle points, the lines or n_active are not on P's device: tensors of two fake devices, so no GPU is needed"""
+    from torch._subclasses.fake_tensor import FakeTensorMode
+    from piml_amd import ops_metrics as OM
+    S, T, N = 2, 3, 4
+    with FakeTensorMode():
+        def f32(dev, *shape):
+            return torch.empty(*shape, device=dev, dtype=torch.float32)
+        P, V, M = f32('cuda:0', S, T, N, 2), f32('cuda:0', S, T, N, 2), f32('cuda:0', S, T, N)
+        V1, M1 = f32('cuda:1', S, T, N, 2), f32('cuda:1', S, T, N)
+        obs, obs1, lines, lines1 = f32('cuda:0', 5, 2), f32('cuda:1', 5, 2), f32('cuda:0', 2, 4), f32('cuda:1', 2, 4)
+        n1 = torch.empty(S, device='cuda:1', dtype=torch.int32)
+        box = dict(box=(0.0, 1.0, 0.0, 1.0), grid=(2, 2))
+        for fn, kw in ((OM.crowd_stats_frames, {}), (OM.crowd_stats_voronoi_frames, dict(dirs=np.zeros((4, 2), np.float32))),
+                       (OM.pair_stats_frames, {}), (OM.flow_stats_frames, box), (OM.view_stats_frames, {})):
+            for args in ((P, V1, M), (P, V, M1)):
+                with pytest.raises(ValueError, match='P, V and M on different devices'):
+                    fn(*args, **kw)
+            with pytest.raises(ValueError, match='n_active: expected an int32'):
+                fn(P, V, M, n_active=n1, **kw)
+        for args in ((P, V1, M, obs), (P, V, M1, obs), (P, V, M, obs1)):
+            with pytest.raises(ValueError, match='P, V, M and obstacles on different devices'):
+                OM.obstacle_stats_frames(*args)
+        for args in ((P, M1, lines), (P, M, lines1)):
+            with pytest.raises(ValueError, match='P, M and lines on different devices'):
+                OM.line_stats_frames(*args)
+        for fn, args in ((OM.track_stats_frames, ()), (OM.group_pairs_frames, (1.0, 1.0, 1.0, 1)),
+                         (OM.group_members_frames, (torch.empty(0, 3, device='cuda:0', dtype=torch.int32), 1.0, 1.0, 1.0))):
+            with pytest.raises(ValueError, match='P and M on different devices'):
+                fn(P, M1, *args)
+        for fn, args in ((OM.obstacle_stats_frames, (P, V, M, obs)), (OM.line_stats_frames, (P, M, lines)),
+                         (OM.track_stats_frames, (P, M)), (OM.group_pairs_frames, (P, M, 1.0, 1.0, 1.0, 1))):
+            with pytest.raises(ValueError, match='n_active: expected an int32'):
+                fn(*args, n_active=n1)

@@ -54,8 +54,10 @@ def option_sets(S, T, N, side):
 
 
 # N, S, T, O (None: one more than a tile), the share of NaN / infinite obstacle points
+# (N = 1100: more slots than one focal compaction takes, so its second round runs)
 CASES = [(1, 1, 1, 1, 0.0), (1, 1, 2, 1, 0.0), (65, 3, 40, 7, 0.0), (300, 2, 12, None, 0.0), (65, 2, 9, 900, 0.3),
-         (40, 2, 5, 0, 0.0)]
+         (40, 2, 5, 0, 0.0), (1100, 1, 3, 7, 0.0)]
+FOCAL_TILE = 1024                             # OS_FOCAL_TILE of obstaclestats.hip
 
 
 @pytest.mark.parametrize('N,S,T,O,bad', CASES)
@@ -71,8 +73,12 @@ def test_random_slices_against_numpy(N, S, T, O, bad):
         st = obstacle_stats(Pt, Vt, Mt, obs, **kw)
         want = check_against_ref(st, P, V, M, obs, f'N={N} S={S} T={T} O={O} {sorted(kw)}', **kw)
         assert st.clear.sum() == want['n_items'] == st.min_ttc.sum() and st.swept.sum() <= st.steps.sum()
-        if N >= 65:
-            for k in REF.OUTPUTS + REF.HISTS:                 # no output is vacuous
+        if N > FOCAL_TILE:                                    # agents of the second round are counted
+            assert (st.trk_frames[:, FOCAL_TILE:] > 0).any()
+        # no output is vacuous where there are enough frames and points for contacts: at 0.8 agents per m^2 and radius 0.25,
+        # about 0.16 a frame and point, and three frames of seven points have none
+        if N >= 65 and S * T * O >= 800:
+            for k in REF.OUTPUTS + REF.HISTS:
                 assert getattr(st, k).sum() > 0, k
             assert (st.trk_min >= 0).any() and st.min_ttc[:, :-1].sum() > 0
         if O == 0:

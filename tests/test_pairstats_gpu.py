@@ -52,7 +52,8 @@ def check_against_ref(st, P, V, M, label, **kw):
     return want
 
 
-CASES = [(1500, 1, 4, (1, 2, 8)), (300, 3, 10, (2, 5)), (65, 2, 6, (1,)), (1, 1, 3, ())]
+# (1024 and 1025: a frame that just fills the staged tile and one that needs a second)
+CASES = [(1500, 1, 4, (1, 2, 8)), (300, 3, 10, (2, 5)), (65, 2, 6, (1,)), (1, 1, 3, ()), (1024, 2, 3, (1,)), (1025, 2, 3, (1,))]
 
 
 @pytest.mark.parametrize('N,S,T,lags', CASES)

@@ -53,7 +53,9 @@ def test_random_slices_against_numpy(N, S, T):
         assert st.nn_map.sum() == st.focal[:, 0].sum() == st.front_gap.sum()
         assert st.map.sum() <= st.pairs.sum()
         if N >= 300:                               # not vacuous: every class, a front gap and a nearest neighbour on the map
-            assert (st.map.sum((0, 3, 4)) > 0).all() and st.front_gap[:, :-1].sum() > 0 and st.nn_map[:, :-1].sum() > 0
+            a, b = kw.get('frames', (0, T))            # (every class of every lag that has a slice in the window)
+            live = [k for k, lag in enumerate((0,) + tuple(kw['lags'])) if lag < b - a]
+            assert (st.map.sum((0, 3, 4))[live] > 0).all() and st.front_gap[:, :-1].sum() > 0 and st.nn_map[:, :-1].sum() > 0
             assert st.front_speed.sum() > 0
         if 'n_active' in kw and S > 1:             # the member without a slot: nothing
             assert all((getattr(st, k)[S // 2] == 0).all() for k in REF.OUTPUTS)

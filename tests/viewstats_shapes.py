@@ -129,7 +129,8 @@ MID_CALLS = (('base', None), ('empty_lag', None), ('base', 'n_active'))
 # ---------------------------------------------------------------------------------------------------------------------
 # the random slices of test_viewstats_gpu.py
 
-CASES = [(1500, 1, 4), (300, 3, 10), (65, 2, 6), (1, 1, 3)]
+# (1024 and 1025: a frame that just fills the staged tile and one that needs a second)
+CASES = [(1500, 1, 4), (300, 3, 10), (65, 2, 6), (1, 1, 3), (1024, 2, 3), (1025, 2, 3)]
 LAGS = (1, 2)
 
 
